@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
 """edges/sec (aggregate+score) at K=8, d=64 — the metric of BASELINE.json — on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload squirrel|chameleon|penn94|snap_patents|...]
-                    [--dtype f32|bf16] [--scaling weak|strong] [--sections all|headline,hbm_bound,...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                    [--workload squirrel|chameleon|penn94|snap_patents|...] [--dtype f32|bf16] [--scaling weak|strong]
+                    [--sections all|headline,hbm_bound,...]
 
 One "step" = one forward pass of the hot path over the whole training graph with inputs
 resident in HBM: route (model.py:56-72) + aggregate (model.py:73-75) over the E_sym directed
 non-zeros of the training adjacency, + the pair scorer (model.py:109-113) over the P scored
-training pairs.  value = (E_sym + P) / median step time  (SURVEY.md §8d headline rate).  The
+training pairs.  value = (E_sym + P) / step time  (SURVEY.md §8d headline rate).  The
 projection GEMM and the one-time CSR construction are outside the timed region, as §8d says.
 
-Timing: W warm-up steps, then warm-up BY TIME (blocks of K steps until at least 0.3 s have passed and three
+Timing: W warm-up steps, then warm-up BY TIME (blocks of min(K, 50) steps until at least 0.3 s have passed and three
 consecutive blocks agree within 2 % — a fresh GPU ramps its clocks for tens of milliseconds, far longer than any
-sensible W at 0.2 ms per step), then R blocks of exactly K steps, each bracketed by a device synchronise, R >= --repeats
-and large enough for the timed region to last >= 1 s; ms_per_step is the MEDIAN block, min / median / max are in the
-line.  The line also carries `parity`: the timed GPU outputs against the CPU oracle's dense pass on the same Z
-(max |dprob| over the scored pairs, AUC on both sides).
+sensible W at 0.2 ms per step), then exactly K timed steps between two device synchronisations; ms_per_step is their
+time / K.  --dump-outputs DIR writes what the last timed step computed (DIR/<name>.npy, float32).  A plain run stops
+there and prints the line.
+
+--full adds everything else: the per-kernel roofline table (a second pass of R blocks of K steps, R >= --repeats and
+>= 1 s in total, with HIP events on the phases; min / median / max of those blocks are in the line), the extra
+sections (--sections), the CPU baselines and `parity`: the timed GPU outputs against the CPU oracle's dense pass on
+the same Z (max |dprob| over the scored pairs, AUC on both sides; exit 4 when they do not match).
 
 Roofline accounting.  Two byte counts per kernel phase:
   * algorithmic_bytes — SURVEY.md §8(d)'s per-unit figures (no cache credit, every directed edge, the u rows of the
@@ -402,6 +407,55 @@ def steady_warmup(run_block, min_s=None, tol=0.02, max_s=4.0):
             return len(hist), el, settled
 
 
+def time_steps(step, steps, warmup):
+    """The headline's timing -> (seconds per timed step, the last timed step's outputs, warm-up info).  `warmup` steps,
+    warm-up by time (steady_warmup over blocks of at most 50 steps, so that it stays within its bound whatever --steps
+    is), then exactly `steps` steps between two device synchronisations."""
+    for _ in range(warmup):
+        step()
+    n_block = max(1, min(steps, 50))
+
+    def block():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n_block):
+            step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n_block
+    n_warm, warm_s, settled = steady_warmup(block)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        out = step()
+    torch.cuda.synchronize()
+    sec = (time.perf_counter() - t0) / steps
+    return sec, out, dict(warmup_blocks=n_warm, warmup_block_steps=n_block, warmup_s=warm_s,
+                          warmup_settled=bool(settled), timed_region_s=sec * steps)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: each array as DIR/<name>.npy in float32.  When all of them together exceed 64 MB, every array
+    above an equal share of that budget is replaced by a fixed sample of its flattened elements (seed 0, sorted, repeats
+    removed), the same on every run with the same arguments -> {name: shape written, or the sampled count}."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.numel() for a in arrays.values()) * 4
+    share = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    written = {}
+    for name, a in arrays.items():
+        a = a.detach()
+        if total > DUMP_BUDGET_BYTES and a.numel() > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.numel(), share))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+            written[name] = {"sampled": int(idx.size), "of": int(arrays[name].numel()), "shape": list(arrays[name].shape)}
+        else:
+            written[name] = {"shape": list(a.shape)}
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
+    return written
+
+
 def time_forward(ops, graph, pairs, Z, beta, t, steps, warmup, repeats, min_region_s=None, info=None):
     """-> (per-block seconds per step, per-phase kernel seconds (HIP events on the launch stream, median)).
     W warm-up steps, warm-up by time (steady_warmup), then max(repeats, enough for min_region_s) blocks of exactly
@@ -720,7 +774,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; ms_per_step is their median")
+    ap.add_argument("--repeats", type=int, default=5,
+                    help="--full: blocks of --steps steps of the per-kernel pass (ms_per_step_min_median_max)")
     ap.add_argument("--workload", default="auto",
                     help="N=1: auto = squirrel_real (the real geom-gcn edge list shipped as the parity fixture) when the "
                          "fixture is present, else the seeded squirrel-shaped graph.  N>1: auto = the three blocks of "
@@ -736,16 +791,30 @@ def main():
     ap.add_argument("--force-generic", action="store_true")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="storage type of the gathered Z/H tables (arithmetic is fp32 either way)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: its per-kernel roofline table, the extra sections (--sections), the CPU "
+                         "baselines and the parity of the timed step against the CPU oracle (exit 4 on a mismatch)")
     ap.add_argument("--sections", default="all",
-                    help="comma list of: headline, hbm_bound, fwd_bwd, scorer_train, projection, dense, epoch, cpu (default all)")
+                    help="with --full: comma list of headline, hbm_bound, fwd_bwd, scorer_train, projection, dense, epoch, "
+                         "dropin, cpu (default all)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (route p, a, s; H; the pair probabilities) as "
+                         "DIR/<name>.npy in float32, at most 64 MB in all (a fixed seeded sample of larger outputs)")
     ap.add_argument("--hbm-scale", type=float, default=0.25, help="scale of the snap_patents graph of the hbm_bound block")
     ap.add_argument("--hbm-steps", type=int, default=5)
     ap.add_argument("--warm-s", type=float, default=0.3, help="warm up by time for at least this long (0: --warmup steps only)")
-    ap.add_argument("--min-region-s", type=float, default=1.0, help="timed region: at least this long (0: --repeats blocks)")
+    ap.add_argument("--min-region-s", type=float, default=1.0,
+                    help="--full: the blocks of the per-kernel pass last at least this long (0: --repeats blocks)")
     argv = json.loads(os.environ["DL_BENCH_ARGV"]) if os.environ.get("DL_BENCH_ARGV") and under_launcher() else None
     args = ap.parse_args(argv)                                 # (self-launched ranks: see self_launch)
     WARM_S[0], REGION_S[0] = args.warm_s, args.min_region_s
     want = lambda s: args.sections == "all" or s in args.sections.split(",")
+    if args.sections != "all" and not args.full:
+        ap.error("--sections selects among the --full measurements: add --full")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and not want("headline"):
+        ap.error("--dump-outputs writes the headline's outputs: --sections must include headline")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.gpus > 1 and not under_launcher():                 # BEFORE any GPU call: the parent only starts and waits
@@ -799,6 +868,8 @@ def main():
     if sharded:
         import torch.distributed as dist
         from disenlink_amd import dist_bench
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs covers the one-GPU path only")
         result = dist_bench.bench_sharded(args, rank, world, device)
         if rank == 0:
             print(json.dumps(result), flush=True)
@@ -813,6 +884,41 @@ def main():
         Z = Z.to(torch.bfloat16)
 
     table_bytes = 2 * N * K * d * wbytes
+    units = E + P
+
+    def step():
+        p, a, s = ops.route_fwd(graph, Z, t)
+        H = ops.aggregate_fwd(graph, Z, beta, p, a, s)
+        return p, a, s, H, ops.score_pairs_fwd(Z, H, pairs.pu, pairs.pv, t, pairs)
+    step_s, last, tinfo = float("nan"), None, {}
+    if want("headline"):
+        step_s, last, tinfo = time_steps(step, args.steps, args.warmup)
+    result = {
+        "metric": "edges/sec (aggregate+score) at K=8 d=64",
+        "value": units / step_s,
+        "unit": "edges/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": step_s * 1e3,
+        "timing": {**tinfo, "note": "warm-up = --warmup steps, then blocks of min(--steps, 50) steps until >= 0.3 s AND three "
+                                    "consecutive blocks within 2 %; timed region = exactly --steps steps between two device "
+                                    "synchronisations, ms_per_step = its time / --steps"},
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "real edge rows, synthetic features" if args.workload.endswith("_real") else "synthetic",
+        "config": {"workload": f"{args.workload + ' (edge list of the parity fixture)' if args.workload.endswith('_real') else args.workload + '-synthetic'}(seed 0): N={N}, edge rows={sg.src.size}, 85/5/10 split, "
+                               f"E_sym={E}, scored train pairs P={P} (m=5), K={K}, d={d}, beta={beta}, t={t}; "
+                               "forward route+aggregate+score_pairs",
+                   "K": K, "d": d, "n_nodes": N, "E_sym": E, "P": P, "fast_path": bool(lib.dl_has_fast_path(K, d))
+                   and not args.force_generic},
+    }
+    if args.dump_outputs:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(
+            args.dump_outputs, dict(zip(("route_p", "route_a", "route_s", "H", "prob"), last)))}
+    del last
+    if not args.full:
+        print(json.dumps(result), flush=True)
+        return
+
+    # --full: everything beyond the headline figure
     tinfo = {}
     if want("headline"):
         blocks, ktime = time_forward(ops, graph, pairs, Z, beta, t, args.steps, args.warmup, args.repeats, info=tinfo)
@@ -823,7 +929,6 @@ def main():
         route_timed = (route_timed[0].clone(), route_timed[1].clone())
     else:
         blocks, ktime, prob_timed, ev_over_us, route_timed = [float("nan")], {n: float("nan") for n in NAMES}, None, None, (None, None)
-    step_s = float(np.median(blocks))
     abytes, mbytes = algorithmic_bytes(K, d, N, E, P, w=wbytes), moved_bytes(graph, pairs, K, d, w=wbytes)
     pmc_key = f"{args.workload}x{args.scale:g}_K{K}_d{d}_{args.dtype}"
     traffic, traffic_src = pmc_traffic(pmc_key)
@@ -1031,32 +1136,22 @@ def main():
         if split_d:
             dense["bf16_pipe_frac"] = 6.0 * fl_d / t_d / 1e12 / BF16_MFMA_PEAK_TFLOPS
 
-    units = E + P
     bound_note = ("Z+H (%.0f MB) sit in the XCD L2s / the Infinity Cache: the bytes the kernels move come from L2, priced "
                   "against the L2 bandwidth (MI355X_MICROARCH.md: 34.5 TB/s; its L2-resident row-gather rates are "
                   "16.8-18.8 TB/s, lower bounds); hbm_* = HBM-side bytes of the rocprofv3 PMC passes against 8 TB/s; "
                   "the HBM-bound measurement is the hbm_bound block" % (table_bytes / 1e6)) if in_cache else \
                  "the kernels' requests are served from HBM: HBM roofline"
-    result = {
-        "metric": "edges/sec (aggregate+score) at K=8 d=64",
-        "value": units / step_s,
-        "unit": "edges/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "repeats": len(blocks),
-        "ms_per_step": step_s * 1e3,
-        "ms_per_step_min_median_max": [float(np.min(blocks)) * 1e3, step_s * 1e3, float(np.max(blocks)) * 1e3],
+    result.update({
+        "repeats": len(blocks),
+        "ms_per_step_min_median_max": [float(np.min(blocks)) * 1e3, float(np.median(blocks)) * 1e3, float(np.max(blocks)) * 1e3],
         "ms_per_step_blocks": [round(b * 1e3, 5) for b in (blocks if len(blocks) <= 24 else
                                                             blocks[:8] + blocks[len(blocks) // 2 - 4:len(blocks) // 2 + 4] + blocks[-8:])],
         "ms_per_step_blocks_note": "all blocks" if len(blocks) <= 24 else "first 8, middle 8, last 8 of %d blocks" % len(blocks),
-        "timing": {"blocks_of_steps": args.steps, **tinfo,
-                   "note": "warm-up = --warmup steps, then blocks until >= 0.3 s AND three consecutive blocks within 2 %; "
-                           "timed region = R blocks of exactly --steps steps, R >= --repeats and >= 1 s in total"},
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "real edge rows, synthetic features" if args.workload.endswith("_real") else "synthetic",
-        "config": {"workload": f"{args.workload + ' (edge list of the parity fixture)' if args.workload.endswith('_real') else args.workload + '-synthetic'}(seed 0): N={N}, edge rows={sg.src.size}, 85/5/10 split, "
-                               f"E_sym={E}, scored train pairs P={P} (m=5), K={K}, d={d}, beta={beta}, t={t}; "
-                               "forward route+aggregate+score_pairs",
-                   "K": K, "d": d, "n_nodes": N, "E_sym": E, "P": P, "fast_path": bool(lib.dl_has_fast_path(K, d))
-                   and not args.force_generic},
+        "block_timing": {"blocks_of_steps": args.steps, **tinfo,
+                         "note": "the per-kernel pass (--full), after the headline's timed steps: warm-up = --warmup steps, "
+                                 "then blocks until >= 0.3 s AND three consecutive blocks within 2 %; R blocks of exactly "
+                                 "--steps steps, R >= --repeats and >= 1 s in total; ms_per_step_* = per-step time of those "
+                                 "blocks"},
         "roofline": {"bound": bound, "bound_decided_by": bound_how, "kernel": dom,
                      "achieved": kernels[dom]["achieved_GBs"],
                      "peak": peak, "unit": "GB/s", "frac": kernels[dom]["frac"],
@@ -1080,7 +1175,7 @@ def main():
         "phase_sum_over_step": sum(kernels[n]["avg_us"] for n in NAMES) * 1e-6 / step_s,
         "step_bytes_over_time_GBs": sum(mbytes.values()) / step_s / 1e9,
         "kernel_source_hash": kernel_source_hash(),
-    }
+    })
     if bound == "hbm" and kernels[dom]["frac"] > HBM_ACHIEVABLE_FRAC:
         result["roofline"]["frac_unverified"] = (
             "above the ~6.3 TB/s HBM can deliver: part of these bytes are served by the 256 MiB Infinity Cache " +

@@ -542,6 +542,36 @@ def test_bench_launches_its_own_ranks_when_started_plainly():
     assert r.returncode != 0 and "disagree" in r.stderr
 
 
+def test_bench_dump_outputs_are_float32_within_budget_and_sections_need_full(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): every array as float32 <name>.npy; over the budget, the arrays above their
+    share become the same seeded sample on every call.  --sections without --full is refused before any GPU call."""
+    import subprocess
+    import sys
+    import bench
+    arrays = {"p": torch.arange(40, dtype=torch.int8), "H": torch.randn(6, 4, 8).to(torch.bfloat16), "prob": torch.rand(30)}
+    got = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert got["H"] == {"shape": [6, 4, 8]}
+    for name, a in arrays.items():
+        back = np.load(tmp_path / "all" / f"{name}.npy")
+        assert back.dtype == np.float32 and np.array_equal(back.reshape(a.shape), a.float().numpy()), name
+    old = bench.DUMP_BUDGET_BYTES
+    try:
+        bench.DUMP_BUDGET_BYTES = 3 * 16 * 4                        # a share of 16 elements per array
+        one, two = bench.dump_outputs(str(tmp_path / "s1"), arrays), bench.dump_outputs(str(tmp_path / "s2"), arrays)
+    finally:
+        bench.DUMP_BUDGET_BYTES = old
+    assert one == two and one["H"]["of"] == 192 and 0 < one["H"]["sampled"] <= 16
+    total = 0
+    for name in arrays:
+        a, b = np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 3 * 16 * 4
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sections", "headline"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr and not r.stdout.strip()
+
+
 def test_bench_warmup_settles_and_parity_block_reports_both_sides():
     """bench.steady_warmup: blocks until >= min_s have passed AND three consecutive blocks agree within tol (a ramp keeps
     it going; max_s bounds it).  bench.parity_block: max |dprob| and the tie-aware AUC of both sides (the GPU side's AUC

@@ -8,7 +8,7 @@ for rep in 1 2; do
 for v in default nosgather rowscatter both; do
   for wl in squirrel_real chameleon; do
     if [ $v = default ]; then unset DL_LIB_PATH; else export DL_LIB_PATH=variants/libdisenlink_hip_$v.so; fi
-    python3 bench.py --workload $wl --sections headline --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | python3 -c "
+    python3 bench.py --full --workload $wl --sections headline --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=l['kernels']
 print('$v $wl rep$rep: step %.1f us  route %.1f  aggregate %.1f  score %.1f  edge_scatter %.1f' % (l['ms_per_step']*1e3, k['route']['avg_us'], k['aggregate']['avg_us'], k['score']['avg_us'], k['route']['avg_us']+k['aggregate']['avg_us']))"

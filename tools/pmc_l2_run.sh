@@ -13,10 +13,10 @@ i=0
 for c in "TCC_REQ_sum TCC_READ_sum TCC_WRITE_sum" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
   rm -rf /tmp/pmc_l2_$i
-  timeout -k 10 500 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmc_l2_$i -o out -- python3 "$root/bench.py" "$@" --no-cpu-baseline --warm-s 0 --min-region-s 0 > /tmp/pmc_l2_$i.log 2>&1 < /dev/null || { echo "pass $i ($c) failed"; tail -n 5 /tmp/pmc_l2_$i.log; exit 1; }
+  timeout -k 10 500 rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmc_l2_$i -o out -- python3 "$root/bench.py" --full "$@" --no-cpu-baseline --warm-s 0 --min-region-s 0 > /tmp/pmc_l2_$i.log 2>&1 < /dev/null || { echo "pass $i ($c) failed"; tail -n 5 /tmp/pmc_l2_$i.log; exit 1; }
 done
 a=$(find /tmp/pmc_l2_1 -name '*counter_collection.csv' | head -n 1)
 b=$(find /tmp/pmc_l2_2 -name '*counter_collection.csv' | head -n 1)
 if [ -z "$a" ] || [ -z "$b" ]; then echo "PMC output missing"; tail -n 5 /tmp/pmc_l2_1.log; exit 1; fi
 python3 "$root/tools/pmc_l2.py" "$a" "$b" "$root/gpurun_out/${tag}_pmc_l2.json" "$key" \
-  "rocprofv3 --kernel-trace --pmc TCC_REQ_sum TCC_READ_sum TCC_WRITE_sum | TCC_HIT_sum TCC_MISS_sum (separate passes) -- python3 bench.py $* --no-cpu-baseline --warm-s 0 --min-region-s 0"
+  "rocprofv3 --kernel-trace --pmc TCC_REQ_sum TCC_READ_sum TCC_WRITE_sum | TCC_HIT_sum TCC_MISS_sum (separate passes) -- python3 bench.py --full $* --no-cpu-baseline --warm-s 0 --min-region-s 0"
