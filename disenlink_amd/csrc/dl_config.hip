@@ -24,8 +24,6 @@ void read_environment() {
     Config c;
     const char* sr = getenv("DL_STREAM_ROWS");
     c.stream_rows = (sr == nullptr || sr[0] == '\0') ? -1 : (sr[0] == '1' ? 1 : 0);
-    c.route_ballot = flag("DL_ROUTE_BALLOT");
-    c.train_group_kernel = flag("DL_TRAIN_GROUP_KERNEL");
     c.fwd_group_kernel = flag("DL_FWD_GROUP_KERNEL");
     c.auc_target = (int)std::max(0LL, number("DL_AUC_TARGET"));
     c.project_fp32_mfma = getenv("DL_PROJECT_FP32_MFMA") != nullptr;
@@ -33,8 +31,6 @@ void read_environment() {
     c.fwd_block_rows = std::max(0LL, number("DL_FWD_BLOCK_ROWS"));
     c.bwd_block_bytes = std::max(0LL, number("DL_BWD_BLOCK_BYTES"));
     c.bwd_target = (int)std::max(0LL, number("DL_BWD_TARGET"));
-    c.dense_fp32_mfma = getenv("DL_DENSE_FP32_MFMA") != nullptr;
-    c.dense_dc32 = getenv("DL_DENSE_DC32") != nullptr;
     const char* ic = getenv("DL_INKERNEL_COMBINE");
     c.inkernel_combine = (ic == nullptr || ic[0] == '\0') ? 1 : std::max(0, std::min(2, atoi(ic)));
     g_config = c;

@@ -16,10 +16,11 @@
 // (register r supplies the k-pair {acc_row(r,0), acc_row(r,1)}); so the hidden activations never leave
 // the register file — no [N, K*nhid] tensor is written to HBM and re-read, unlike two library GEMMs.
 // The layer-1 operand tiles ([128 rows][32 features]: three bf16 planes at an 80-byte row pitch, or fp32 at
-// 36 / 68 floats: aligned, conflict-free b128 reads) are double-buffered in LDS and the next step's tiles are fetched into registers behind the
-// current step's MFMAs; the W2 operand (A[i = d][k = hidden], 4 consecutive hidden units per register
-// quad) is read straight from global memory, one d-tile ahead of its use.  The two hidden halves of a
-// node's Z are added through LDS at the end (fixed order).
+// 36 / 68 floats: aligned, conflict-free b128 reads) are double-buffered in LDS; the next step's tiles are copied
+// there behind the current step's MFMAs (bf16 planes by LDS-DMA, PlaneDma; fp32 tiles through registers).  The
+// fp32 path's W2 operand (A[i = d][k = hidden], 4 consecutive hidden units per register quad) is read straight
+// from global memory, one d-tile ahead of its use.  The two hidden halves of a node's Z are added through LDS at
+// the end (fixed order).
 // Small graphs: the hidden chunks are split over G workgroups per (node tile, k) whose partial Z go to
 // G slabs, added in slab order by z_slab_sum_kernel (no atomics; needs the workspace).
 #include <algorithm>
@@ -78,7 +79,7 @@ __device__ __forceinline__ float4 zero4(const float4& q, int base, int n) {
 // [3][K*D][nhid_p] bf16 with the hidden units in layer 2's k-slot order; a chunk's slice — D rows x 128 hidden x 3 planes —
 // was read straight from there by every wave, one K = 16 group ahead of its use: 16 bytes per lane from 32 different rows
 // per instruction (a quarter of every 128-byte line used), and a global round trip per group that no prefetch depth hid
-// (stamps, tools/proj_stamps.py: 9,000 cycles per chunk for 48 MFMAs = 1,536 cycles of issue).  Now the whole workgroup
+// (stamps: 9,000 cycles per chunk for 48 MFMAs = 1,536 cycles of issue).  Now the whole workgroup
 // copies the slice with fully coalesced 16-byte loads (issued at the top of the chunk's last layer-1 step) into the LDS tile
 // buffer that step has just finished reading, and layer 2 takes its A operands from there with ds_read_b128.
 template <int D, int THREADS>
@@ -104,16 +105,8 @@ struct W2Stage {
         }
     }
 };
-#ifndef DL_PROJ_STAGGER
-#define DL_PROJ_STAGGER 0         // 1: waves 4..7 of the forward stage before their first MFMA block — measured SLOWER (same box: 90.7 ->
-                                  // 95.4 us at the bench shape, 675 -> 748 at F = 2,088, 845 -> 868 at d = 128): the staging under a wave-uniform
-                                  // branch costs more than the overlap buys; kept for the record
-#endif
-#ifndef DL_W2_LDS
-#define DL_W2_LDS 1               // -DDL_W2_LDS=0: the W2 operand straight from global memory (the round-2 form), for A/B runs
-#endif
 
-// Layer-1 tiles by LDS-DMA (round 6; -DDL_PROJ_DMA=0: the register-staged form, for A/B runs).  A [3][128][32] bf16 plane tile
+// Layer-1 tiles by LDS-DMA (round 6; it replaced a register-staged form).  A [3][128][32] bf16 plane tile
 // (24 KB, contiguous in the plane array) goes to its padded LDS image — 384 rows of 80 bytes: 4 data pieces + 1 pad piece of
 // 16 bytes — by 30 global_load_lds_dwordx4 wave-instructions: the LDS side of such an instruction is linear (wave-uniform
 // base + 16 bytes per lane), the GLOBAL address is per lane, so lane l of instruction i fetches the piece that belongs at
@@ -121,9 +114,6 @@ struct W2Stage {
 // them L2 hits).  No staging registers (the register form held a whole tile pair: 30 registers), no ds_write pass, and no
 // vmcnt(0) in the middle of a step waiting for the tile loads: stamps of the register form showed 1,000-2,200 of a step's
 // 3,800 cycles in "stash" + "fetch issue".  Wave w issues instructions w, w + 8, w + 16, w + 24 of each tile.
-#ifndef DL_PROJ_DMA
-#define DL_PROJ_DMA 1
-#endif
 struct PlaneDma {
     static constexpr int PIECES = 3 * PLANE_ROWS * 5;           // padded 16-byte positions of a tile
     static constexpr int INSTR = PIECES / DL_WAVE;               // 30
@@ -161,22 +151,6 @@ struct FwdPlanes {
     const __bf16* w2; size_t w2_ps; int nhid_p;                    // planes [3][K*D][nhid_p] of W2 in layer 2's k-slot order
 };
 
-// -DDL_PROJ_STAMPS=<workgroup index>: DIAGNOSTIC build — waves 0 and 4 of that workgroup (two waves of one SIMD) record
-// s_memtime at the phase boundaries of every pipeline step into dl_proj_stamps (read back by dl_debug_read_stamps; the
-// stamps go nowhere else).  tools/proj_stamps.py prints the timeline.
-#ifdef DL_PROJ_STAMPS
-__device__ unsigned long long dl_proj_stamps[2][512];
-#define DL_STAMP(code)                                                                                  \
-    do {                                                                                                \
-        if (stamp_on && stamp_n < 510) {                                                                \
-            dl_proj_stamps[stamp_w][stamp_n++] = ((unsigned long long)(code) << 56) | (__builtin_amdgcn_s_memtime() & 0x00FFFFFFFFFFFFFFull); \
-            dl_proj_stamps[stamp_w][511] = stamp_n;                                                     \
-        }                                                                                               \
-    } while (0)
-#else
-#define DL_STAMP(code) do {} while (0)
-#endif
-
 template <int D, bool VEC, bool SPLIT>
 __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restrict__ x, int N, int F, int nhid,
                                                             const float* __restrict__ W1, const float* __restrict__ b1,
@@ -192,7 +166,7 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
     // one contiguous block (it also takes the W2 slice of a chunk's layer 2, W2Stage)
     constexpr int XBUF = 3 * TN * SPLIT_PITCH, PBUF = 3 * (TN + TH) * SPLIT_PITCH;
     __bf16* pbuf = reinterpret_cast<__bf16*>(lds);
-    constexpr bool W2LDS = SPLIT && DL_W2_LDS && D <= 64 && (size_t)W2Stage<D, NTHR>::PITCH * 3 * D <= (size_t)PBUF;
+    constexpr bool W2LDS = SPLIT && D <= 64 && (size_t)W2Stage<D, NTHR>::PITCH * 3 * D <= (size_t)PBUF;
     float* bias_s = reinterpret_cast<float*>(pbuf + 2 * PBUF);      // SPLIT: the 128 biases of the current hidden chunk
     float bias_q = 0.0f;
     const XcdItem item = xcd_item(blockIdx.x, (N + TN - 1) / TN, K * G);
@@ -202,12 +176,6 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int li = lane & 31, half = lane >> 5;
     const int wn = wave >> 1, wh = wave & 1;
-#ifdef DL_PROJ_STAMPS
-    const bool stamp_on = (int)blockIdx.x == DL_PROJ_STAMPS && (wave == 0 || wave == 4) && lane == 0;
-    const int stamp_w = wave >> 2;
-    int stamp_n = 0;
-#endif
-    DL_STAMP(1);
     const float* W1k = W1 + (size_t)k * nhid * F;
     const float* W2k = W2 + (size_t)k * D * nhid;
     const float* b1k = b1 + (size_t)k * nhid;
@@ -218,36 +186,25 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
     TileStage<TN, FC, VEC, NTHR> xt;
     TileStage<TH, FC, VEC, NTHR> wt;
     static_assert(TN == PLANE_ROWS && TH == PLANE_ROWS, "tiles of the plane arrays");
-    constexpr bool DMA = SPLIT && DL_PROJ_DMA;
-    PlaneStage<NTHR, DMA ? 8 * NTHR / PLANE_ROWS : SPLIT_COLS> xq, wq;   // (DMA: unused — the smallest instantiation)
     PlaneDma dma;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    if constexpr (DMA) dma.init(wave_s, lane);
-    // DMA: both tiles of step s straight into its parity buffer (which every wave left at the barrier before)
+    if constexpr (SPLIT) dma.init(wave_s, lane);
+    // SPLIT: both tiles of step s straight into its parity buffer (which every wave left at the barrier before)
     auto dma_tile = [&](int s) {
         const int hc = hc0 + s / nfc, fc = s % nfc;
         dma.issue(P.x + plane_tile<SPLIT_COLS>(item.a, fc, P.ncb), pbuf + (s & 1) * PBUF, wave_s);
         dma.issue(P.w + (size_t)k * P.w_batch + plane_tile<SPLIT_COLS>(hc, fc, P.ncb), pbuf + (s & 1) * PBUF + XBUF, wave_s);
     };
+    // !SPLIT: the fp32 tiles of step s into registers, and from there into its parity buffer
     auto fetch = [&](int s) {
-        const int hc = hc0 + s / nfc, fc = s % nfc;
-        if constexpr (DMA) {
-            (void)hc; (void)fc;
-        } else if constexpr (SPLIT) {
-            xq.fetch(P.x + plane_tile<SPLIT_COLS>(item.a, fc, P.ncb), tid);
-            wq.fetch(P.w + (size_t)k * P.w_batch + plane_tile<SPLIT_COLS>(hc, fc, P.ncb), tid);
-        } else {
+        if constexpr (!SPLIT) {
+            const int hc = hc0 + s / nfc, fc = s % nfc;
             xt.fetch(x + (size_t)n0 * F + fc * FC, F, N - n0, F - fc * FC, tid);
             wt.fetch(W1k + (size_t)hc * TH * F + fc * FC, F, nhid - hc * TH, F - fc * FC, tid);
         }
     };
     auto stash = [&](int s) {
-        if constexpr (DMA) {
-            (void)s;
-        } else if constexpr (SPLIT) {
-            xq.stash(pbuf + (s & 1) * PBUF, tid);
-            wq.stash(pbuf + (s & 1) * PBUF + XBUF, tid);
-        } else {
+        if constexpr (!SPLIT) {
             xt.template stash<LDT>(xs + (s & 1) * TN * LDT, tid);
             wt.template stash<LDT>(w1s + (s & 1) * TH * LDT, tid);
         }
@@ -267,39 +224,27 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) zero_acc(zacc[dt]);
 
-    // Software pipeline (one register set per tile, write-after-barrier): during step s the registers hold
+    // !SPLIT software pipeline (one register set per tile, write-after-barrier): during step s the registers hold
     // tile s+1, whose global loads were issued one step earlier; it goes to the other LDS buffer in the shadow
     // of the first MFMA block of step s (every wave left that buffer at the barrier before), and the loads of
     // tile s+2 are issued right behind it.
     if (steps > 0) {
-        if constexpr (DMA) {
+        if constexpr (SPLIT) {
             dma_tile(0);                                          // tiles 0 and 1 on their way into the two buffers together
             if (steps > 1) dma_tile(1);
-        } else if constexpr (SPLIT) {
-            // tiles 0 and 1 in flight together (a second register set while no accumulator is live yet): one global
-            // round trip in the prologue instead of two — a workgroup runs only 8 steps at F = 128
-            PlaneStage<NTHR, SPLIT_COLS> x0, w0;
-            x0.fetch(P.x + plane_tile<SPLIT_COLS>(item.a, 0, P.ncb), tid);
-            w0.fetch(P.w + (size_t)k * P.w_batch + plane_tile<SPLIT_COLS>(hc0, 0, P.ncb), tid);
-            fetch(min(1, steps - 1));
-            x0.stash(pbuf, tid);
-            w0.stash(pbuf + XBUF, tid);
         } else {
             fetch(0);
             stash(0);
             if (steps > 1) fetch(1);
         }
     }
-    DL_STAMP(2);
-    if constexpr (DMA) wait_vmem();
+    if constexpr (SPLIT) wait_vmem();
     __syncthreads();
-    DL_STAMP(3);
     for (int s = 0; s < steps; ++s) {
         const int hc = hc0 + s / nfc, fc = s % nfc;
         const bool last = fc == nfc - 1;
         const int hbase = hc * TH + wh * 64;                    // first hidden unit of this wave's tile
-        DL_STAMP(10);
-        if constexpr (DMA) {
+        if constexpr (SPLIT) {
             // tile s + 1 into the other buffer — free since the barrier that ended step s - 1 — with the whole step to land
             // (tile 1 left in the prologue); the barrier at the end of this step waits for it (vmcnt(0) + s_barrier)
             if (s >= 1 && s + 1 < steps) dma_tile(s + 1);
@@ -314,13 +259,12 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
                 load_w2(wnext, 0, hbase);
             }
         }
-        // SPLIT: nothing is requested from global memory at the top of a step.  s_waitcnt vmcnt counts in issue order, and the
-        // tile of step s+1 — requested a step ago — is written to LDS in the middle of this step: a load issued HERE would be
-        // younger than the tile's, the compiler cannot tell the two apart at the join of the `last` branch (it waits for
-        // vmcnt(0)), and the stash would sit out a whole global round trip (stamps: +2,800 cycles in every chunk's last
-        // step).  The chunk's biases and the W2 slice are requested BEHIND the stash instead (below); the biases — asked
-        // for a step ahead — go to LDS here, at the top of the chunk's last step, where everything younger than them was
-        // requested a step ago too.  (F <= 32, one step per chunk: requested here, staged before their use.)
+        // SPLIT: apart from the tile, nothing is requested from global memory at the top of a step.  s_waitcnt vmcnt counts in
+        // issue order, and the compiler cannot tell loads apart at the join of the `last` branch (it waits for vmcnt(0)): with
+        // the register-staged tiles this kernel had before LDS-DMA, a load issued HERE made the mid-step stash of the next tile
+        // sit out a whole global round trip (stamps: +2,800 cycles in every chunk's last step).  The chunk's biases and the
+        // W2 slice are requested between the step's MFMA blocks instead (below); the biases — asked for a step ahead — go to
+        // LDS here, at the top of the chunk's last step.  (F <= 32, one step per chunk: requested here, staged before their use.)
         if constexpr (SPLIT) {
             if (tid < TH) {
                 if (nfc == 1) {
@@ -345,11 +289,7 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
                 for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(src + p * P.w2_ps);
             }
         };
-        // one group in flight (issued here for the first, a layer-1 step ahead; three in flight measured no faster)
-#ifndef DL_W2PF
-#define DL_W2PF 1
-#endif
-        constexpr int W2PF = DL_W2PF;
+        constexpr int W2PF = 1;     // groups in flight (the first issued a layer-1 step ahead; three measured no faster)
         bf16x8 w2a[W2PF + 1][3];
         W2Stage<D, NTHR> w2st;
         if constexpr (SPLIT) {
@@ -366,11 +306,14 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
                     a0[kb][p] = *reinterpret_cast<const bf16x8*>(wb + p * TH * SPLIT_PITCH + kb * 16);
                     a1[kb][p] = *reinterpret_cast<const bf16x8*>(wb + (p * TH + 32) * SPLIT_PITCH + kb * 16);
                 }
-            // the step's staging work: tile s+1 to LDS, then the requests that must come behind that stash
+            mfma_split6(hacc[0], a0[0], b[0]);
+            mfma_split6(hacc[1], a1[0], b[0]);
+            // the step's other global requests, between the two MFMA blocks (see the top of the step): the chunk's 128
+            // biases — one float per thread of the first two waves, a step ahead of their use — and, in the chunk's last
+            // step, the W2 operand of layer 2.  (Staging in waves 4..7 before their first MFMA block instead, beside their
+            // SIMD partners' MFMAs, measured slower: 90.7 -> 95.4 us at the bench shape, 675 -> 748 at F = 2,088, 845 -> 868
+            // at d = 128.)  Kept a lambda: written inline, the same code compiles to a different register allocation.
             auto stage_work = [&]() {
-                if (s + 1 < steps) stash(s + 1);
-                // behind the stash (see the top of the step): the chunk's 128 biases — one float per thread of the first two
-                // waves, a step ahead of their use — and, in the chunk's last step, the W2 operand of layer 2
                 if (nfc >= 2 && fc == nfc - 2 && tid < TH) {
                     const int h = hc * TH + tid;
                     bias_q = b1k[h < nhid ? h : 0];
@@ -384,31 +327,10 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
                         for (int q = 0; q < W2PF; ++q) load_w2p(w2a[q], q);
                     }
                 }
-                // unconditional (the last steps fetch the last tile again): a fetch under a condition makes the
-                // registers a merge of old and new values, and hipcc then waits for the loads right here to copy them
-                DL_STAMP(13);
-                fetch(min(s + 2, steps - 1));
-                DL_STAMP(14);
             };
-#if DL_PROJ_STAGGER
-            // The two waves of a SIMD (w and w + 4) run the same program between the same barriers: in lockstep both stage
-            // at the same time and the matrix pipe idles meanwhile.  Waves 4..7 stage BEFORE their first MFMA block, waves
-            // 0..3 behind it: one wave's MFMAs run beside its SIMD partner's LDS stores and global requests.
-            const bool early = __builtin_amdgcn_readfirstlane(wave) >= 4;
-            if (early) stage_work();
-#endif
-            DL_STAMP(11);
-            mfma_split6(hacc[0], a0[0], b[0]);
-            mfma_split6(hacc[1], a1[0], b[0]);
-            DL_STAMP(12);
-#if DL_PROJ_STAGGER
-            if (!early) stage_work();
-#else
             stage_work();
-#endif
             mfma_split6(hacc[0], a0[1], b[1]);
             mfma_split6(hacc[1], a1[1], b[1]);
-            DL_STAMP(15);
         } else {
         // lane half h owns features h*FC/2 .. h*FC/2 + FC/2-1 of the chunk; MFMA block j takes 2 quads of them
         // per operand row (3 ds_read_b128, 16 MFMAs), block j+1's reads are issued ahead of block j's MFMAs
@@ -476,7 +398,6 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
                         if (h < nhid && n < N) hid_out[((size_t)k * nhid + h) * ldh + n] = hacc[ht][r];
                     }
             }
-            DL_STAMP(20);
             if constexpr (SPLIT) {
                 // layer 2 on the bf16 matrix path too: the post-ReLU accumulator is split into its three planes in
                 // registers (slot s of block b = register 8b + s), W2 comes pre-split in the matching order
@@ -498,13 +419,11 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
 #pragma unroll
                     for (int q = 0; q < W2PF; ++q) load_w2p(w2a[q], q);
                 }
-                DL_STAMP(21);
 #pragma unroll
                 for (int grp = 0; grp < 4 * DT; ++grp) {
                     if (grp + W2PF < 4 * DT) load_w2p(w2a[(grp + W2PF) % (W2PF + 1)], grp + W2PF);
                     mfma_split6(zacc[grp >> 2], w2a[grp % (W2PF + 1)], hp[(grp >> 1) & 1][grp & 1]);
                 }
-                DL_STAMP(22);
             } else {
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
@@ -528,13 +447,11 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
 #pragma unroll
             for (int ht = 0; ht < 2; ++ht) zero_acc(hacc[ht]);
         }
-        DL_STAMP(16);
         // LDS-DMA data is ordered for a ds_read only by the issuing wave's vmcnt followed by a barrier the reader has passed;
         // the workgroup fence of __syncthreads() waits for LDS operations only.  (hipcc already emitted this wait here, for
         // the pending bias load: written out so that the tile of step s + 1 does not depend on that.)
-        if constexpr (DMA) wait_vmem();
+        if constexpr (SPLIT) wait_vmem();
         __syncthreads();
-        DL_STAMP(17);
     }
     // The two hidden halves (wh = 0, 1) of a node quarter hold partial Z sums: wave wh = 1 hands its half
     // over through LDS and wave wh = 0 adds (fixed order), adds b2 and stores (registers 4g..4g+3 are 4
@@ -548,7 +465,6 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
     }
     __syncthreads();
     const int n = n0 + wn * 32 + li;
-    DL_STAMP(30);
     if (wh == 0 && n < N) {
         float* orow = out + (((size_t)grp * N + n) * K + k) * D;
 #pragma unroll
@@ -564,18 +480,8 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
                 *reinterpret_cast<float4*>(orow + dd) = make_float4(o[0] + bb.x, o[1] + bb.y, o[2] + bb.z, o[3] + bb.w);
             }
     }
-    DL_STAMP(31);
 }
 
-#ifdef DL_PROJ_STAMPS
-}  // namespace project
-}  // namespace dl
-extern "C" int dl_debug_read_stamps(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dl::project::dl_proj_stamps), sizeof(unsigned long long) * 2 * 512);
-}
-namespace dl {
-namespace project {
-#endif
 
 constexpr size_t project2_lds(int D, bool split) {
     const size_t red = sizeof(float) * 4 * (D / 32) * 16 * 64;                 // the Z hand-over at the end

@@ -48,12 +48,6 @@ constexpr int bwd_ht(int D) { return D <= 64 ? 2 : 1; }
 // reads along the node axis is written (zeros past N and past nhid).
 struct DhidPlanes { __bf16* base; size_t batch; int ncb; };       // factor k at base + k * batch; ncb 16-node chunks per row block
 
-#ifndef DL_BWD_A_BF16
-#define DL_BWD_A_BF16 1           // -DDL_BWD_A_BF16=0: kernel A's two products on fp32 MFMA (the round-2 form), for A/B runs
-#endif
-#ifndef DL_BWD_A_BF16_MAXD
-#define DL_BWD_A_BF16_MAXD 128    // largest factor width that takes the bf16 path (its planes must fit the kernel's LDS)
-#endif
 // LDS bytes of kernel A (also used by its launcher below)
 constexpr size_t project2_bwd_lds_bytes(int D) {
     const size_t ht = D <= 64 ? 2 : 1;
@@ -61,21 +55,6 @@ constexpr size_t project2_bwd_lds_bytes(int D) {
     const size_t red = 8 * (size_t)((D / 32) * ht * 16 + ht) * 64;
     return sizeof(float) * (stage > red ? stage : red);
 }
-
-// -DDL_PROJA_STAMPS=<workgroup index>: DIAGNOSTIC build (like DL_PROJ_STAMPS in dl_project.hip): s_memtime at the phase
-// boundaries of every node tile, waves 0 and 4 of one workgroup; read back by dl_debug_read_stamps_a.
-#ifdef DL_PROJA_STAMPS
-__device__ unsigned long long dl_proja_stamps[2][512];
-#define DLA_STAMP(code)                                                                                 \
-    do {                                                                                                \
-        if (stamp_on && stamp_n < 510) {                                                                \
-            dl_proja_stamps[stamp_w][stamp_n++] = ((unsigned long long)(code) << 56) | (__builtin_amdgcn_s_memtime() & 0x00FFFFFFFFFFFFFFull); \
-            dl_proja_stamps[stamp_w][511] = stamp_n;                                                    \
-        }                                                                                               \
-    } while (0)
-#else
-#define DLA_STAMP(code) do {} while (0)
-#endif
 
 template <int D, bool VEC, bool RECOMPUTE, bool PLANES>
 __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
@@ -92,11 +71,11 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
     float* w2t = dzs + TILE_N * LDZ;               // [HB][LDZ]       W2_k[:, chunk]^T, staged once
     // BF (round 5; kept hidden layer, d <= 64): both products of a node tile — dW2 += dZ^T . hid and dhid = dZ . W2^T — on
     // the bf16 matrix path from three bf16 planes per operand (dl_tiles.h: six exact products per term, fp32-grade) instead
-    // of fp32 MFMA: 96 MFMAs of 32 cycles per wave and tile instead of 128 of 64 (stamps, tools/proja_stamps.py: fp32 MFMA
+    // of fp32 MFMA: 96 MFMAs of 32 cycles per wave and tile instead of 128 of 64 (stamps: fp32 MFMA
     // issue was 58 % of a tile).  dZ tile and W2^T chunk live in LDS as planes [3][rows][ZP]; the A operand of the node
     // contraction (dZ^T: lane = dd, k-slots = 8 nodes) comes out of the [node][dd] image by the transposed LDS read
     // ds_read_b64_tr_b16; its B operand is the hidden layer in registers, split in place (slot s of block b = register 8b + s).
-    constexpr bool BF = DL_BWD_A_BF16 && PLANES && !RECOMPUTE && D <= DL_BWD_A_BF16_MAXD;
+    constexpr bool BF = PLANES && !RECOMPUTE;
     static_assert(!BF || sizeof(__bf16) * 3 * (TILE_N + HB) * (D + 8) <= project2_bwd_lds_bytes(D), "planes of the dZ tile and the W2^T chunk fit the kernel's LDS");
     constexpr int ZP = D + 8;                      // plane row pitch (bf16): 16-byte rows reads conflict-free, 8-byte aligned
     __bf16* dzp = reinterpret_cast<__bf16*>(lds);  // BF: [3][TILE_N][ZP]
@@ -118,16 +97,10 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
     const int nfc = RECOMPUTE ? (F + BFC - 1) / BFC : 1;
     const int steps = my_tiles * nfc;
     const int hw0 = hc * HB + wh * 32 * HT;        // first hidden unit of this wave
-#ifdef DL_PROJA_STAMPS
-    const bool stamp_on = (int)blockIdx.x == DL_PROJA_STAMPS && (wave == 0 || wave == 4) && lane == 0;
-    const int stamp_w = wave >> 2;
-    int stamp_n = 0;
-#endif
-    DLA_STAMP(1);
 
     {   // W2^T chunk: w2t[h][dd] = W2_k[dd][hc*HB + h].  All loads first, then the LDS stores: written as one loop the
         // compiler waited for every load before its store — 16 global round trips in a row, 16,000 cycles of a workgroup's
-        // 183,000 (stamps, tools/proja_stamps.py).
+        // 183,000 (stamps).
         constexpr int NW = HB * D / BTHR;
         static_assert(HB * D % BTHR == 0, "the W2^T chunk divides over the workgroup");
         float wv[NW];
@@ -252,7 +225,6 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
         }
         }   // RECOMPUTE
         if (last) {
-            DLA_STAMP(10);
             // every wave is past the previous tile's use of dzs (barrier at the end of that step)
             if constexpr (BF) {                                 // the dZ tile as three bf16 planes [node][dd]
                 const bool full = zt.rows_valid >= TILE_N && zt.cols_valid >= D;
@@ -274,9 +246,7 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
             } else {
                 zt.template stash<LDZ>(dzs, tid);
             }
-            DLA_STAMP(11);
             __syncthreads();
-            DLA_STAMP(12);
             float hid[HT][16];
             unsigned relu_bits[HT];                             // bit r: hid[ht][r] > 0 (the mask of the dhid epilogue)
 #pragma unroll
@@ -303,8 +273,7 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
                 for (int r = 0; r < 16; ++r) relu_bits[ht] |= (hid[ht][r] > 0.0f ? 1u : 0u) << r;
             }
             // kept form: the next tile's dZ rows and hidden quads are fetched behind this tile's MFMAs (unconditional —
-            // the last tile is fetched twice — see project2_fwd_kernel)
-            DLA_STAMP(13);
+            // the last tile is fetched twice — see TileStage, dl_tiles.h)
             const int n0n = (tile0 + min(tl + 1, my_tiles - 1)) * TILE_N;
             if constexpr (!RECOMPUTE) zt.fetch(dZk + (size_t)n0n * K * D, K * D, N - n0n, D, tid);
             // dW2[dd][hidden] += dZ[node][dd] . hid[node][hidden]: the k-pair of register r is the node pair
@@ -357,7 +326,6 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
                     for (int ht = 0; ht < HT; ++ht) DL_MFMA(w2acc[dt][ht], zv[r], hid[ht][r]);
             }
             }
-            DLA_STAMP(14);
             if constexpr (!RECOMPUTE) load_hq(n0n);             // hid has been consumed by the MFMAs above
             // dhid[node][hidden] = dZ[node][dd] . W2^T[hidden][dd], masked by the ReLU
 #pragma unroll
@@ -394,7 +362,6 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
 #pragma unroll
                 for (int ht = 0; ht < HT; ++ht) DL_MFMA(hacc[ht], zq.w, vq[ht].w);
             }
-            DLA_STAMP(15);
 #pragma unroll
             for (int ht = 0; ht < HT; ++ht) {
                 const int h = hw0 + ht * 32 + li;
@@ -446,10 +413,8 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
                 b1acc[ht] += colsum;
                 zero_acc(hacc[ht]);
             }
-            DLA_STAMP(16);
         }
         __syncthreads();
-        DLA_STAMP(17);
     }
     // cross-wave reduction (fixed order over the 4 node quarters) of the dW2 / db1 partials of this range
     constexpr int RW = DT * HT * 16 + HT;                       // floats per lane and wave
@@ -584,24 +549,9 @@ __global__ __launch_bounds__(256, 2) void nodes_contract_kernel(const float* __r
 // reach output rows / columns that are not stored).  Node chunk of 16 per step, double-buffered, 2 workgroups per CU.
 constexpr int PC = 16, PPITCH = PC + 8;
 
-// -DDL_PROJB_STAMPS=<workgroup index>: DIAGNOSTIC build (like DL_PROJA_STAMPS): s_memtime at the phase boundaries of every
-// node chunk, waves 0 and 2 of one workgroup of kernel B; read back by dl_debug_read_stamps_b (tools/projb_stamps.py).
 // What was tried on this kernel from its stamps and counters (profiles/r6_kernel_b_experiments.txt): a dictated issue order
 // (sched_group_barrier: staging instructions between the MFMAs), global loads two chunks ahead, two chunks per barrier,
 // 512 instead of 256 workgroups, every tile a cache hit (timing bound): all within 35 +- 3 us.
-#ifdef DL_PROJB_STAMPS
-__device__ unsigned long long dl_projb_stamps[2][512];
-#define DLB_STAMP(code)                                                                                 \
-    do {                                                                                                \
-        if (stamp_on && stamp_n < 510) {                                                                \
-            dl_projb_stamps[stamp_w][stamp_n++] = ((unsigned long long)(code) << 56) | (__builtin_amdgcn_s_memtime() & 0x00FFFFFFFFFFFFFFull); \
-            dl_projb_stamps[stamp_w][511] = stamp_n;                                                    \
-        }                                                                                               \
-    } while (0)
-#else
-#define DLB_STAMP(code) do {} while (0)
-#endif
-
 __global__ __launch_bounds__(256, 2) void nodes_contract_planes_kernel(const __bf16* __restrict__ Yp, size_t y_batch,
                                                                        const __bf16* __restrict__ Xp, int ncb, int n_chunks,
                                                                        int M, int F, int K, int chunks_per_range,
@@ -620,12 +570,6 @@ __global__ __launch_bounds__(256, 2) void nodes_contract_planes_kernel(const __b
     const int chunk0 = rng * chunks_per_range;
     const int my_chunks = max(0, min(chunks_per_range, n_chunks - chunk0));
     const __bf16* Yk = Yp + (size_t)k * y_batch;
-#ifdef DL_PROJB_STAMPS
-    const bool stamp_on = (int)blockIdx.x == DL_PROJB_STAMPS && (wave == 0 || wave == 2) && lane == 0;
-    const int stamp_w = wave >> 1;
-    int stamp_n = 0;
-#endif
-    DLB_STAMP(1);
 
     PlaneStage<256, PC> yq, xq;
     auto fetch = [&](int c) {
@@ -647,9 +591,7 @@ __global__ __launch_bounds__(256, 2) void nodes_contract_planes_kernel(const __b
         fetch(min(1, my_chunks - 1));
     }
     __syncthreads();
-    DLB_STAMP(2);
     for (int c = 0; c < my_chunks; ++c) {
-        DLB_STAMP(10);
         // lane half h supplies nodes 8h .. 8h+7 of the chunk: A = hidden rows of this wave (2 tiles), B = feature rows
         const __bf16* yb = ys + (c & 1) * 3 * PLANE_ROWS * PPITCH + (wm * 64 + li) * PPITCH + half * 8;
         const __bf16* xb = xs + (c & 1) * 3 * PLANE_ROWS * PPITCH + (wf * 64 + li) * PPITCH + half * 8;
@@ -663,15 +605,11 @@ __global__ __launch_bounds__(256, 2) void nodes_contract_planes_kernel(const __b
         }
         mfma_split6(acc[0][0], a0, b0);
         mfma_split6(acc[0][1], a0, b1);
-        DLB_STAMP(11);
         if (c + 1 < my_chunks) stash(c + 1);                    // staging in the shadow of the MFMAs
-        DLB_STAMP(12);
-        fetch(min(c + 2, my_chunks - 1));                       // unconditional: see project2_fwd_kernel
+        fetch(min(c + 2, my_chunks - 1));                       // unconditional: see TileStage (dl_tiles.h)
         mfma_split6(acc[1][0], a1, b0);
         mfma_split6(acc[1][1], a1, b1);
-        DLB_STAMP(13);
         __syncthreads();
-        DLB_STAMP(14);
     }
     float* out = C + ((size_t)rng * K + k) * M * F;
 #pragma unroll
@@ -685,7 +623,6 @@ __global__ __launch_bounds__(256, 2) void nodes_contract_planes_kernel(const __b
                 if (m < M && f < F) out[(size_t)m * F + f] = acc[a][b][r];
             }
         }
-    DLB_STAMP(20);
 }
 
 // out[i] (+)= sum_s slabs[s][i], s ascending (fixed order), for up to 4 independent (slabs, out) jobs in one
@@ -809,21 +746,6 @@ static BwdLayout bwd_layout(int N, int F, int K, int nhid, int d, bool two_layer
 }
 
 }  // namespace project
-
-#ifdef DL_PROJA_STAMPS
-}  // namespace dl
-extern "C" int dl_debug_read_stamps_a(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dl::project::dl_proja_stamps), sizeof(unsigned long long) * 2 * 512);
-}
-namespace dl {
-#endif
-#ifdef DL_PROJB_STAMPS
-}  // namespace dl
-extern "C" int dl_debug_read_stamps_b(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dl::project::dl_projb_stamps), sizeof(unsigned long long) * 2 * 512);
-}
-namespace dl {
-#endif
 
 size_t project_bwd_workspace_bytes(int N, int F, int K, int nhid, int d, bool two_layer) {
     if (N <= 0) return 0;

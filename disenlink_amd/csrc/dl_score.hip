@@ -82,25 +82,20 @@ __global__ __launch_bounds__(BLOCK, K <= 8 ? 4 : 1) void score_fwd_seg_kernel(dl
 // the u rows are re-read from the wave's LDS region every step, U = 4 pairs per step, the 16 partial dot products reduced
 // over the DPP row by one transposed reduction: one expf and one sigmoid per step.  No accumulators, so fewer registers
 // than the training kernel; the arithmetic up to the probability is that kernel's, operation for operation — the two give the
-// same bits.  The group-per-entry kernel above stays for every other shape (and as the reference form: -DDL_FWD_WAVE_KERNEL=0).
+// same bits.  The group-per-entry kernel above stays for every other shape (and as the reference form: DL_FWD_GROUP_KERNEL=1).
 // Why: the training kernel's bound build ran these very gathers, without arithmetic, at 0.86 of the L2 peak; the
 // group-per-entry forward reached 0.79.
-#ifndef DL_FWD_WAVE_KERNEL
-#define DL_FWD_WAVE_KERNEL 1
-#endif
-#ifndef DL_FWD_WAVE_MAXW
-#define DL_FWD_WAVE_MAXW 6            // waves per SIMD the register allocation aims at (4 / 5 / 6 measured: 156.6 / 156.8 / 154.4 us, profiles/r7n_*)
-#endif
+constexpr int FWD_WAVE_MAXW = 6;      // waves per SIMD the register allocation aims at (4 / 5 / 6 measured: 156.6 / 156.8 / 154.4 us, profiles/r7n_*)
 template <int K, int D>
 struct FwdWave {
-    static constexpr bool ok = DL_FWD_WAVE_KERNEL && D == 64 && (K == 4 || K == 8);
+    static constexpr bool ok = D == 64 && (K == 4 || K == 8);
     static constexpr int NJ = K * D / 256, U = 4;
 };
 
 // (amdgpu_waves_per_eu(4, 5): left to itself hipcc aims at 8 waves per SIMD = 64 registers — exactly the 16 gathered float4 of a
 // step — by requesting only 12 of them up front and the rest behind three more vmcnt(0) round trips per step.)
 template <int K, int D, bool T1, bool COEF>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, DL_FWD_WAVE_MAXW))) void score_fwd_wave_kernel(dl_csr_plan g, const int32_t* __restrict__ pair_id,
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WAVE_MAXW))) void score_fwd_wave_kernel(dl_csr_plan g, const int32_t* __restrict__ pair_id,
                                                                   const float* __restrict__ Z, const float* __restrict__ H, float t,
                                                                   float* __restrict__ prob, float* __restrict__ coef_e,
                                                                   float* __restrict__ coef_q) {

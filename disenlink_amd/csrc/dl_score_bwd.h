@@ -17,11 +17,9 @@ namespace fast {
 // rows are added in registers (one staged row per wave: 16 KB of LDS per workgroup instead of 64, so LDS does not cap the
 // occupancy at two either) — squirrel 478 -> 457 us, chameleon 99 -> 96; four waves (128 registers) spill 46 and take 3x;
 // d = 32 / 8 would spill a few registers at three waves and stay at two.
-#ifndef DL_TRAIN_WAVES
-#define DL_TRAIN_WAVES 3              // -DDL_TRAIN_WAVES=1 (DL_CXXFLAGS): the two-wave form with the groups' rows in LDS, for A/B runs
-#endif
+constexpr int FUSED_TRAIN_WAVES = 3;          // waves per SIMD of that kernel (measured as above)
 template <int K_, int D_, bool FUSED_>
-struct TrainWaves { static constexpr int value = (FUSED_ && K_ == 8 && D_ == 64) ? DL_TRAIN_WAVES : 1; };
+struct TrainWaves { static constexpr int value = (FUSED_ && K_ == 8 && D_ == 64) ? FUSED_TRAIN_WAVES : 1; };
 template <int K, int D, typename T, bool FUSED>
 __global__ __launch_bounds__(BLOCK, (TrainWaves<K, D, FUSED>::value)) void score_bwd_seg_kernel(dl_csr_plan g, const int32_t* __restrict__ inc_pair,
                                                               const T* __restrict__ Z, const T* __restrict__ H,

@@ -67,6 +67,9 @@ __device__ __forceinline__ XcdItem xcd_item(int h, int n_a, int n_b) {
 // Offsets are 32-bit from a wave-uniform origin (saddr + voffset addressing, no 64-bit VALU math).  Full
 // tiles take an unchecked path; edge tiles load from clamped, always valid addresses and select afterwards
 // (a branch around a load would make hipcc wait for each load separately).
+// The pipelines that stage through these registers fetch UNCONDITIONALLY (the last steps fetch the last tile again): a
+// fetch under a condition makes the registers a merge of old and new values, and hipcc then waits for the loads right at
+// the fetch to copy them.
 template <int ROWS, int COLS, bool VEC, int THREADS>
 struct TileStage {
     static constexpr int NV = ROWS * COLS / THREADS;   // floats per thread

@@ -50,12 +50,9 @@ __device__ __forceinline__ float row_allreduce_sum(float v) {
 
 // (dot4_packed: dl_fast.h — shared with the wave-per-entry forward scorer of dl_score.hip)
 
-#ifndef DL_TRAIN_WAVE_KERNEL
-#define DL_TRAIN_WAVE_KERNEL 1        // -DDL_TRAIN_WAVE_KERNEL=0: the group-per-entry kernel above, for A/B runs
-#endif
 template <int K, int D>
 struct TrainWave {
-    static constexpr bool ok = DL_TRAIN_WAVE_KERNEL && D == 64 && (K == 4 || K == 8);
+    static constexpr bool ok = D == 64 && (K == 4 || K == 8);
     static constexpr int NJ = K * D / 256;                          // float4 per lane per row
     static constexpr int U = 4;                                     // entries per step
 };
@@ -256,18 +253,9 @@ __global__ __launch_bounds__(BLOCK, (UREG ? 3 : 4)) void score_train_wave_kernel
 // Unit sum: the own-row regions (4 x 8 KB with bf16 tables) are too small to stage four [dZ | dH] rows of 16 KB at
 // once, so the unit is summed as a TREE in two rounds through two 16 KB slots — (s0 + s1) + (s2 + s3); which waves pair
 // up depends on the row's segments alone (shard-independent, reproducible).
-#ifndef DL_TRAIN_WIDE_KERNEL
-#define DL_TRAIN_WIDE_KERNEL 1        // -DDL_TRAIN_WIDE_KERNEL=0: the group-per-entry kernel, for A/B runs
-#endif
-#ifndef DL_TRAIN_WIDE_U_BF16
-#define DL_TRAIN_WIDE_U_BF16 1        // entries per step with bf16 tables ...
-#endif
-#ifndef DL_TRAIN_WIDE_WAVES_BF16
-#define DL_TRAIN_WIDE_WAVES_BF16 4    // ... and waves per SIMD (U = 2 needs 3)
-#endif
-#ifndef DL_TRAIN_WIDE_U_F32
-#define DL_TRAIN_WIDE_U_F32 1         // fp32 tables: U = 2 spills 17 registers at the 256 the two waves per SIMD allow
-#endif
+constexpr int TRAIN_WIDE_U_BF16 = 1;        // entries per step with bf16 tables ...
+constexpr int TRAIN_WIDE_WAVES_BF16 = 4;    // ... and waves per SIMD (U = 2 needs 3)
+constexpr int TRAIN_WIDE_U_F32 = 1;         // fp32 tables: U = 2 spills 17 registers at the 256 the two waves per SIMD allow
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 v2bf16 __attribute__((ext_vector_type(2)));
 
@@ -307,9 +295,9 @@ struct WideChunk<float> {
 
 template <int K, int D, typename T>
 struct TrainWide {
-    static constexpr bool ok = DL_TRAIN_WIDE_KERNEL && K == 16 && D == 128;
-    static constexpr int U = sizeof(T) == 2 ? DL_TRAIN_WIDE_U_BF16 : DL_TRAIN_WIDE_U_F32;
-    static constexpr int WAVES = sizeof(T) == 2 ? DL_TRAIN_WIDE_WAVES_BF16 : 2;      // fp32: 67 KB of LDS per workgroup
+    static constexpr bool ok = K == 16 && D == 128;
+    static constexpr int U = sizeof(T) == 2 ? TRAIN_WIDE_U_BF16 : TRAIN_WIDE_U_F32;
+    static constexpr int WAVES = sizeof(T) == 2 ? TRAIN_WIDE_WAVES_BF16 : 2;      // fp32: 67 KB of LDS per workgroup
 };
 
 // value of lane `idx` (0 .. 15, a constant once the caller's loops are unrolled) of this lane's DPP row: row_newbcast
@@ -559,7 +547,7 @@ struct TrainOps {
         const dl_csr_plan* g = &inc->csr;
         const float* no_x = nullptr;
         if constexpr (std::is_same<T, float>::value && TrainWave<K, D>::ok) {
-            if (g->seg_len <= 64 && g->seg_len % TrainWave<K, D>::U == 0 && !config().train_group_kernel) {
+            if (g->seg_len <= 64 && g->seg_len % TrainWave<K, D>::U == 0) {
                 auto launch = [&](auto kern) {
                     hipLaunchKernelGGL(kern, dim3(seg_blocks(g)), dim3(BLOCK), 0, st, *g, inc->inc_pair, (const float*)Z,
                                        (const float*)H, t, dZ, dH, part, y, w, prob);
@@ -574,7 +562,7 @@ struct TrainOps {
         }
         if constexpr (TrainWide<K, D, T>::ok) {
             constexpr int U = TrainWide<K, D, T>::U, WV = TrainWide<K, D, T>::WAVES;
-            if (g->seg_len <= 64 && g->seg_len % U == 0 && !config().train_group_kernel) {
+            if (g->seg_len <= 64 && g->seg_len % U == 0) {
                 auto launch = [&](auto kern) {
                     hipLaunchKernelGGL(kern, dim3(seg_blocks(g)), dim3(BLOCK), 0, st, *g, inc->inc_pair, (const T*)Z, (const T*)H,
                                        t, dZ, dH, part, y, w, prob);
