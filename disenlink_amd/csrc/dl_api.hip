@@ -296,6 +296,54 @@ int dl_score_allpairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_
     return generic_score_allpairs_fwd((const float*)Z, (const float*)H, N, K, d, t, prob, (hipStream_t)stream);
 }
 
+int dl_score_topk_supported(int K, int d) { return score_rank_supported(K, d) ? 1 : 0; }
+
+size_t dl_score_topk_workspace_bytes(int N, int K, int d, int n_queries, int k, int n_targets) {
+    if (N <= 0 || n_queries <= 0 || k < 0 || n_targets < 0 || !score_rank_supported(K, d)) return 0;
+    return score_rank_workspace_bytes(N, K, d, n_queries, k, n_targets);
+}
+
+static int check_rank_args(const void* Z, const void* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
+                           const int32_t* ex_rowptr, const int32_t* ex_col) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(score_rank_supported(K, d), "the ranking scan serves fp32 tables with 1 <= d <= 128, got d=%d", d);
+    DL_REQUIRE(N >= 1 && n_queries >= 0, "bad size N=%d n_queries=%d", N, n_queries);
+    DL_REQUIRE((long long)N * K * d < (1LL << 40), "tables too large");
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    DL_REQUIRE(n_queries == 0 || (Z && H && queries), "NULL argument");
+    DL_REQUIRE(ex_rowptr == nullptr || ex_col != nullptr, "exclusion rowptr without col");
+    return DL_OK;
+}
+
+int dl_score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries, int k,
+                  const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index, float* logit, float* prob,
+                  void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_rank_args(Z, H, N, K, d, t, queries, n_queries, ex_rowptr, ex_col)) return rc;
+    DL_REQUIRE(k >= 1 && k <= 128, "k=%d outside 1..128", k);
+    if (n_queries == 0) return DL_OK;
+    DL_REQUIRE(index && logit && prob, "NULL output");
+    const size_t need = score_rank_workspace_bytes(N, K, d, n_queries, k, 0);
+    DL_REQUIRE(ws != nullptr && ws_bytes >= need, "workspace too small: %zu < %zu bytes (dl_score_topk_workspace_bytes)",
+               ws ? ws_bytes : (size_t)0, need);
+    return score_topk(Z, H, N, K, d, t, queries, n_queries, k, ex_rowptr, ex_col, exclude_self, index, logit, prob, ws,
+                      (hipStream_t)stream);
+}
+
+int dl_score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
+                   const int32_t* tptr, const int32_t* tdst, int n_targets, const int32_t* ex_rowptr, const int32_t* ex_col,
+                   int64_t* greater, int64_t* ties, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_rank_args(Z, H, N, K, d, t, queries, n_queries, ex_rowptr, ex_col)) return rc;
+    DL_REQUIRE(n_targets >= 0, "negative size");
+    if (n_queries == 0 || n_targets == 0) return DL_OK;
+    DL_REQUIRE(tptr && tdst && greater && ties, "NULL argument");
+    DL_REQUIRE((long long)n_targets + n_queries < (1LL << 31), "too many targets");
+    const size_t need = score_rank_workspace_bytes(N, K, d, n_queries, 0, n_targets);
+    DL_REQUIRE(ws != nullptr && ws_bytes >= need, "workspace too small: %zu < %zu bytes (dl_score_topk_workspace_bytes)",
+               ws ? ws_bytes : (size_t)0, need);
+    return score_ranks(Z, H, N, K, d, t, queries, n_queries, tptr, tdst, n_targets, ex_rowptr, ex_col, greater, ties, ws,
+                       (hipStream_t)stream);
+}
+
 int dl_auc_pair_counts_supported(int n_pos, int n_neg) {
     return n_pos >= 0 && n_neg >= 0 && auc_counts_supported(n_pos, n_neg) ? 1 : 0;
 }

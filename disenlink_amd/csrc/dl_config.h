@@ -17,6 +17,7 @@ struct Config {
     int bwd_target;             // DL_BWD_TARGET: workgroups per launch of the projection backward (0 = default)
     int inkernel_combine;       // DL_INKERNEL_COMBINE: 0 = rows of several units always through the separate combine launch,
                                 // 1 (default) = inside the launch where the plan's rows are few units long, 2 = wherever a kernel can
+    int rank_slices;            // DL_RANK_SLICES: candidate slices of the ranking scan (0 = by the CU count; results do not depend on it)
 };
 
 const Config& config();

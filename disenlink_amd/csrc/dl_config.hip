@@ -33,6 +33,7 @@ void read_environment() {
     c.bwd_target = (int)std::max(0LL, number("DL_BWD_TARGET"));
     const char* ic = getenv("DL_INKERNEL_COMBINE");
     c.inkernel_combine = (ic == nullptr || ic[0] == '\0') ? 1 : std::max(0, std::min(2, atoi(ic)));
+    c.rank_slices = (int)std::max(0LL, number("DL_RANK_SLICES"));
     g_config = c;
 }
 

@@ -56,6 +56,16 @@ size_t dense_score_workspace_bytes(int N, int K, int d);
 int dense_mfma_score_allpairs_fwd(const float* Z, const float* H, int N, int K, int d, float t, float* prob, void* ws, size_t ws_bytes,
                                   hipStream_t st);
 
+// ranking of all candidates of query rows on the matrix cores (dl_score_rank.hip): fp32 tables, 1 <= d <= 128
+bool score_rank_supported(int K, int d);
+size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T);
+int score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, int k,
+               const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index, float* logit, float* prob,
+               void* ws, hipStream_t st);
+int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, const int32_t* tptr,
+                const int32_t* tdst, int T, const int32_t* ex_rowptr, const int32_t* ex_col, int64_t* greater, int64_t* ties,
+                void* ws, hipStream_t st);
+
 // tie-averaged AUC counts (dl_metrics.hip)
 bool auc_counts_supported(int n_pos, int n_neg);           // the smaller class fits the LDS
 int auc_pair_counts(const float* score, const int64_t* pos_idx, int n_pos, const int64_t* neg_idx, int n_neg,

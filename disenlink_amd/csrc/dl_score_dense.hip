@@ -108,15 +108,7 @@ __global__ __launch_bounds__(DTHR) void score_allpairs_split_kernel(const float*
         const __bf16* vb = vs + (s & 1) * 3 * TT * SLD + (wv * 64 + li) * SLD + half * 8;
 #pragma unroll
         for (int kb = 0; kb < SDC / 16; ++kb) {
-            bf16x8 a[3], b0[3], b1[3];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                a[p] = *reinterpret_cast<const bf16x8*>(ub + p * TT * SLD + kb * 16);
-                b0[p] = *reinterpret_cast<const bf16x8*>(vb + p * TT * SLD + kb * 16);
-                b1[p] = *reinterpret_cast<const bf16x8*>(vb + (p * TT + 32) * SLD + kb * 16);
-            }
-            mfma_split6(acc[0], a, b0);                         // six products, smallest terms first
-            mfma_split6(acc[1], a, b1);
+            gram_block_split6(acc, ub, vb, kb);                 // dl_tiles.h: six products, smallest terms first
             if (kb == 0) {
                 if (s + 1 < steps) stash(s + 1);
                 fetch(min(s + 2, steps - 1));                   // unconditional: see TileStage (dl_tiles.h)

@@ -1,0 +1,624 @@
+// Ranking of all candidate links of a set of query nodes on the matrix cores: top-k per query row (dl_score_topk) and
+// filtered rank counts of target pairs (dl_score_ranks), with the logit of the dense scorer (dl_score_dense.hip),
+//   s(u, v) = sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t),
+// and nothing of size Q x N in memory.
+//
+// Scan: one workgroup = 8 waves = a tile of 128 query rows against a SLICE of consecutive 128-row candidate tiles; per
+// candidate tile the Gram products run exactly as in the dense scorer (gram_block_split6 of dl_tiles.h: three bf16 planes
+// per operand, six exact products, double-buffered LDS staging, the query as the A operand).  The query rows are gathered
+// into a compact array and split once per call; the candidates are read from the plane arrays of Z and H (split_rows).
+// Work items (query tile x slice) are dealt to the XCDs by xcd_item.  What follows the products per candidate tile:
+//   * exclusion: a 128-bit mask per query row, from the row's ascending excluded columns (a cursor that only moves forward
+//     through the tiles of a slice: one binary search per row and workgroup).
+//   * top-k: a per-(row, slice) list in global memory of cap = k + 64 keys.  A candidate is appended only if its key beats
+//     the row's running threshold (the k-th best key of the list after its last compaction; kept in LDS).  A round of
+//     appends adds at most 64 keys per row (two waves x 32 lanes); a list that could overflow in the next round is
+//     compacted by one wave: its sorted prefix (the previous compaction's output) and the new keys are ranked against each
+//     other and the first k written back in order.  A merge kernel combines the slices' sorted lists by rank.
+//   * ranks: each query row's target logits, sorted once, live in global memory; a candidate that reaches the smallest
+//     of them finds its place by binary search and adds 1 to an integer counter (a difference array summed at the end).
+// Keys order the logits totally: larger first, +inf above every finite value, -inf below, NaN below everything; equal
+// values by candidate index, smaller first.  Everything selected or counted is a function of the logits alone, and the
+// logit of a pair does not depend on where in a tile its rows sit: results are independent of the slicing and of the run.
+#include "dl_common.h"
+#include "dl_kernels.h"
+#include "dl_tiles.h"
+
+namespace dl {
+namespace rank {
+
+using namespace project;       // PlaneStage, gram_block_split6, f32x16, acc_row, xcd_item, plane arrays
+
+constexpr int TT = 128;        // tile edge (query rows and candidate rows)
+constexpr int RTHR = 512;
+constexpr int SDC = SPLIT_COLS, SLD = SPLIT_PITCH;
+constexpr int MAX_K = 128;
+constexpr int ROUND = 64;      // keys one round of appends can add to a row's list
+constexpr int MAX_CAP = MAX_K + ROUND;
+constexpr int MAX_SLICES = 32;
+enum { TOPK = 0, RANKS = 1, DIAG = 2 };
+
+typedef unsigned long long u64;
+
+// Total order of the logits as an unsigned key: NaN -> 0, every other value (-0 taken as +0) to its order-preserving
+// image, which is >= 0x007FFFFF (-inf) and <= 0xFF800000 (+inf).
+__device__ __forceinline__ unsigned ord_key(float x) {
+    if (x != x) return 0u;
+    const unsigned b = __float_as_uint(x == 0.0f ? 0.0f : x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord_value(unsigned o) {
+    if (o == 0u) return __uint_as_float(0x7FC00000u);
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+// 64-bit selection key: the value's order, then the candidate index (smaller index = larger key).  Never 0.
+__device__ __forceinline__ u64 make_key(float x, int v) {
+    return ((u64)ord_key(x) << 32) | (u64)(0xFFFFFFFFu - (unsigned)v);
+}
+
+struct ScanArgs {
+    const __bf16 *qz, *qh;  size_t qbatch;     // planes of the gathered query rows (per factor: qbatch elements)
+    const __bf16 *cz, *ch;  size_t cbatch;     // planes of Z and H (the candidates)
+    int Q, N, K, nd;  float t;
+    const int32_t* qnode;                      // [Q] node of each query row
+    const int32_t *ex_rowptr, *ex_col;         // exclusion CSR over nodes (ascending columns), or NULL
+    int exclude_self;
+    int slices, tiles_per_slice;
+    int k, cap;  u64* lists;  int* counts;     // TOPK: lists [Q][slices][cap], counts [Q][slices]
+    const int32_t* tptr;  const unsigned* tord;  u64* gcnt;  u64* tcnt;   // RANKS
+    const int32_t *trow, *tdst;  int T;  float* tlogit;                 // DIAG: target i = (query row trow[i], node tdst[i])
+};
+
+// LDS beyond the two staging images (bytes): exclusion mask, per-row bookkeeping, per-wave compaction scratch
+constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
+constexpr size_t LDS_BYTES = STAGE_BYTES + TT * 4 * 4 + 6 * TT * 4 + TT * 8 + 8 * MAX_CAP * 8;
+
+// A PlaneStage tile whose 128 rows are gathered: row r of the tile is row rows[min(base + r, n - 1)] of the plane array.
+__device__ __forceinline__ void gather_fetch(PlaneStage<RTHR, SDC>& st, const __bf16* __restrict__ planes, const int32_t* rows,
+                                             int base, int n, int dc, int nd, int tid) {
+    static_assert(PlaneStage<RTHR, SDC>::PER == 1, "one 16-byte piece per plane and thread");
+    const int r = tid / (SDC / 8), c = (tid % (SDC / 8)) * 8;
+    const int row = rows[min(base + r, n - 1)];
+    const __bf16* src = planes + plane_tile<SDC>(row / PLANE_ROWS, dc, nd) + (row % PLANE_ROWS) * SDC + c;
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+        st.v[p] = *reinterpret_cast<const typename PlaneStage<RTHR, SDC>::u32x4*>(src + (size_t)p * PLANE_ROWS * SDC);
+}
+
+// Rank one row's list against itself and write its best min(n, k) keys back in order (one wave; between barriers).
+// Keys [0, srt) are sorted (descending) from the previous compaction, keys [srt, n) are new.
+__device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, int srt, int k, int lane, u64* thr_out,
+                                            int* cnt_out, int* srt_out) {
+    for (int i = lane; i < n; i += DL_WAVE) S[i] = L[i];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    constexpr int E = (MAX_CAP + DL_WAVE - 1) / DL_WAVE;
+    u64 mine[E];
+    int rk[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = lane + DL_WAVE * e;
+        mine[e] = i < n ? S[i] : 0ull;
+        rk[e] = 0;
+    }
+    for (int j = srt; j < n; ++j) {                             // against the new keys
+        const u64 x = S[j];
+#pragma unroll
+        for (int e = 0; e < E; ++e) rk[e] += x > mine[e] ? 1 : 0;
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = lane + DL_WAVE * e;
+        if (i < srt) {
+            rk[e] += i;                                         // the old keys above it: its position
+        } else {                                                // old keys above a new one: binary search
+            int lo = 0, hi = srt;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (S[mid] > mine[e]) lo = mid + 1; else hi = mid;
+            }
+            rk[e] += lo;
+        }
+    }
+    const int keep = min(n, k);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = lane + DL_WAVE * e;
+        if (i < n && rk[e] < keep) L[rk[e]] = mine[e];
+        if (i < n && n >= k && rk[e] == k - 1) *thr_out = mine[e];
+    }
+    if (lane == 0) {
+        *cnt_out = keep;
+        *srt_out = keep;
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
+    __bf16* vs = us + 2 * 3 * TT * SLD;
+    unsigned* exm = reinterpret_cast<unsigned*>(vs + 2 * 3 * TT * SLD);   // [TT][4]: excluded columns of the tile
+    int* cnt = reinterpret_cast<int*>(exm + TT * 4);           // TOPK: keys in the row's list
+    int* srt = cnt + TT;                                        // TOPK: of which sorted
+    int* excur = srt + TT;                                      // next exclusion entry of the row
+    int* rnode = excur + TT;                                    // node of the row (-1: no row)
+    int* rbase = rnode + TT;                                    // RANKS: first target of the row
+    int* rm = rbase + TT;                                       // RANKS: targets of the row
+    u64* thr = reinterpret_cast<u64*>(rm + TT);                 // TOPK: threshold key; RANKS: smallest target order
+    u64* scr = thr + TT;                                        // [8][MAX_CAP]: compaction scratch of each wave
+
+    const int nrows = MODE == DIAG ? A.T : A.Q;
+    const int qtiles = (nrows + TT - 1) / TT;
+    const int nslices = MODE == DIAG ? 1 : A.slices;
+    const XcdItem it = xcd_item((int)blockIdx.x, qtiles, nslices);
+    if (!it.valid) return;
+    const int qt = it.a, sl = it.b;
+    const int nt = (A.N + TT - 1) / TT;
+    int ct0 = qt, ntl = 1;
+    if constexpr (MODE != DIAG) {
+        ct0 = sl * A.tiles_per_slice;
+        ntl = max(0, min(nt, ct0 + A.tiles_per_slice) - ct0);
+    }
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 31, half = lane >> 5;
+    const int wu = wave >> 1, wv = wave & 1;
+    const int nd = A.nd;
+    const int per_tile = A.K * 2 * nd;
+    const int steps = ntl * per_tile;
+
+    if constexpr (MODE != DIAG) {
+        if (tid < TT) {
+            const int qi = qt * TT + tid;
+            const int node = qi < A.Q ? A.qnode[qi] : -1;
+            rnode[tid] = node;
+            cnt[tid] = 0;
+            srt[tid] = 0;
+            thr[tid] = 0ull;
+            if (node >= 0 && A.ex_rowptr != nullptr) {          // first excluded column >= the slice's first candidate
+                int lo = A.ex_rowptr[node], hi = A.ex_rowptr[node + 1];
+                const int v0 = ct0 * TT;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (A.ex_col[mid] < v0) lo = mid + 1; else hi = mid;
+                }
+                excur[tid] = lo;
+            }
+            if constexpr (MODE == RANKS) {
+                const int b = node >= 0 ? A.tptr[qi] : 0, m = node >= 0 ? A.tptr[qi + 1] - b : 0;
+                rbase[tid] = b;
+                rm[tid] = m;
+                thr[tid] = m > 0 ? (u64)A.tord[b] : 0ull;
+            }
+        }
+    }
+
+    PlaneStage<RTHR, SDC> uq, vq;
+    static_assert(TT == PLANE_ROWS, "tiles of the plane arrays");
+    auto fetch = [&](int s) {
+        const int j = s / per_tile, rem = s - j * per_tile;
+        const int k = rem / (2 * nd), r = rem - k * 2 * nd;
+        const int dc = r < nd ? r : r - nd;
+        const __bf16* qsrc = (r < nd ? A.qz : A.qh) + (size_t)k * A.qbatch;
+        const __bf16* csrc = (r < nd ? A.cz : A.ch) + (size_t)k * A.cbatch;
+        if constexpr (MODE == DIAG) {
+            gather_fetch(uq, qsrc, A.trow, qt * TT, A.T, dc, nd, tid);
+            gather_fetch(vq, csrc, A.tdst, qt * TT, A.T, dc, nd, tid);
+        } else {
+            uq.fetch(qsrc + plane_tile<SDC>(qt, dc, nd), tid);
+            vq.fetch(csrc + plane_tile<SDC>(ct0 + j, dc, nd), tid);
+        }
+    };
+    auto stash = [&](int s) {
+        uq.stash(us + (s & 1) * 3 * TT * SLD, tid);
+        vq.stash(vs + (s & 1) * 3 * TT * SLD, tid);
+    };
+
+    f32x16 acc[2], term[2];
+    float e[2][16];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        zero_acc(acc[b]);
+        zero_acc(term[b]);
+    }
+    if (steps > 0) {
+        fetch(0);
+        stash(0);
+        fetch(min(1, steps - 1));
+    }
+    __syncthreads();
+    for (int s = 0; s < steps; ++s) {
+        const int rem = s % per_tile;
+        const int r = rem % (2 * nd);
+        const __bf16* ub = us + (s & 1) * 3 * TT * SLD + (wu * 32 + li) * SLD + half * 8;
+        const __bf16* vb = vs + (s & 1) * 3 * TT * SLD + (wv * 64 + li) * SLD + half * 8;
+#pragma unroll
+        for (int kb = 0; kb < SDC / 16; ++kb) {
+            gram_block_split6(acc, ub, vb, kb);                 // the dense scorer's products (dl_tiles.h)
+            if (kb == 0) {
+                if (s + 1 < steps) stash(s + 1);
+                fetch(min(s + 2, steps - 1));                   // unconditional: see TileStage (dl_tiles.h)
+            }
+        }
+        if (r == nd - 1) {                                      // S complete: e = exp(S / t)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) e[bb][q] = expf(div_t(acc[bb][q], A.t));
+                zero_acc(acc[bb]);
+            }
+        } else if (r == 2 * nd - 1) {                           // Q complete: term += Q * e
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) term[bb][q] += acc[bb][q] * e[bb][q];
+                zero_acc(acc[bb]);
+            }
+        }
+        __syncthreads();
+        if (rem != per_tile - 1) continue;
+
+        // ---- candidate tile complete: term[bb][q] = s(query row wu*32 + acc_row(q, half), candidate vl = wv*64 + bb*32 + li)
+        const int v0 = (ct0 + s / per_tile) * TT;
+        if constexpr (MODE == DIAG) {
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int ul = wu * 32 + acc_row(q, half), vl = wv * 64 + bb * 32 + li;
+                    const int i = qt * TT + ul;
+                    if (ul == vl && i < A.T) A.tlogit[i] = term[bb][q];
+                }
+            }
+        } else {
+            if (tid < TT) {                                     // this tile's excluded columns of row tid
+                const int node = rnode[tid];
+                unsigned* m = exm + tid * 4;
+                m[0] = m[1] = m[2] = m[3] = 0u;
+                if (node >= 0 && A.ex_rowptr != nullptr) {
+                    int c = excur[tid];
+                    const int end = A.ex_rowptr[node + 1];
+                    for (; c < end; ++c) {
+                        const int col = A.ex_col[c] - v0;
+                        if (col >= TT) break;
+                        m[col >> 5] |= 1u << (col & 31);
+                    }
+                    excur[tid] = c;
+                }
+                if (node >= 0 && A.exclude_self && node >= v0 && node < v0 + TT) m[(node - v0) >> 5] |= 1u << ((node - v0) & 31);
+            }
+            __syncthreads();
+            // The logits go through LDS, one lane's own 16 values per round (no exchange between lanes), so that the
+            // candidate loop below need not be unrolled over the registers: into the staging image this step has finished
+            // reading (the next write to it is the stash in step s + 1, behind the barriers at the end of this epilogue).
+            float* lg = reinterpret_cast<float*>((wave < 4 ? us : vs) + (s & 1) * 3 * TT * SLD) + (wave & 3) * 16 * DL_WAVE;
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+                const int vl = wv * 64 + bb * 32 + li, v = v0 + vl;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) lg[q * DL_WAVE + lane] = term[bb][q];
+#pragma unroll 1
+                for (int q = 0; q < 16; ++q) {
+                    const int row = wu * 32 + acc_row(q, half);
+                    const bool ok = rnode[row] >= 0 && v < A.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u);
+                    if (!ok) continue;
+                    const int qi = qt * TT + row;
+                    const float x = lg[q * DL_WAVE + lane];
+                    if constexpr (MODE == TOPK) {
+                        const u64 key = make_key(x, v);
+                        if (key > thr[row]) {
+                            const int slot = atomicAdd(&cnt[row], 1);
+                            A.lists[((size_t)qi * A.slices + sl) * A.cap + slot] = key;
+                        }
+                    } else {
+                        const unsigned o = ord_key(x);
+                        const int m = rm[row];
+                        if (m > 0 && (u64)o >= thr[row]) {      // reaches the row's smallest target
+                            const unsigned* to = A.tord + rbase[row];
+                            int lo = 0, hi = m;                 // targets below o: [0, lo)
+                            while (lo < hi) {
+                                const int mid = (lo + hi) >> 1;
+                                if (to[mid] < o) lo = mid + 1; else hi = mid;
+                            }
+                            int lo2 = lo, hi2 = m;              // equal to o: [lo, lo2)
+                            while (lo2 < hi2) {
+                                const int mid = (lo2 + hi2) >> 1;
+                                if (to[mid] <= o) lo2 = mid + 1; else hi2 = mid;
+                            }
+                            if (lo > 0) atomicAdd(&A.gcnt[rbase[row] + qi + lo], 1ull);
+                            if (lo2 > lo) atomicAdd(&A.tcnt[rbase[row] + lo], 1ull);
+                        }
+                    }
+                }
+                if constexpr (MODE == TOPK) {                   // lists that could overflow in the next round
+                    __syncthreads();
+                    for (int row = wave; row < TT; row += 8) {
+                        const int n = cnt[row];
+                        if (n > A.cap - ROUND)
+                            compact_row(A.lists + ((size_t)(qt * TT + row) * A.slices + sl) * A.cap, scr + wave * MAX_CAP, n,
+                                        srt[row], A.k, lane, &thr[row], &cnt[row], &srt[row]);
+                    }
+                    __syncthreads();
+                }
+            }
+            if constexpr (MODE == RANKS) __syncthreads();
+        }
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb) zero_acc(term[bb]);
+    }
+    if constexpr (MODE == TOPK) {                               // every list of the work item sorted and truncated to k
+        __syncthreads();
+        for (int row = wave; row < TT; row += 8) {
+            const int qi = qt * TT + row;
+            if (qi >= A.Q) continue;
+            const int n = cnt[row];
+            if (n > srt[row])
+                compact_row(A.lists + ((size_t)qi * A.slices + sl) * A.cap, scr + wave * MAX_CAP, n, srt[row], A.k, lane,
+                            &thr[row], &cnt[row], &srt[row]);
+            if (lane == 0) A.counts[(size_t)qi * A.slices + sl] = min(n, A.k);
+        }
+    }
+}
+
+// One workgroup per query row: the slices' sorted lists are merged by rank (position in its own list + keys above it in
+// every other list, by binary search); ranks are unique (keys are), so every output slot is written once.
+__global__ __launch_bounds__(256) void topk_merge_kernel(const u64* __restrict__ lists, const int* __restrict__ counts,
+                                                         int slices, int cap, int k, int64_t* __restrict__ index,
+                                                         float* __restrict__ logit, float* __restrict__ prob) {
+    __shared__ u64 sm[MAX_SLICES * MAX_K];
+    __shared__ int off[MAX_SLICES + 1];
+    const int qi = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {
+        int o = 0;
+        for (int s = 0; s < slices; ++s) {
+            off[s] = o;
+            o += counts[(size_t)qi * slices + s];
+        }
+        off[slices] = o;
+    }
+    __syncthreads();
+    for (int s = 0; s < slices; ++s) {
+        const int n = off[s + 1] - off[s];
+        const u64* L = lists + ((size_t)qi * slices + s) * cap;
+        for (int i = tid; i < n; i += 256) sm[off[s] + i] = L[i];
+    }
+    __syncthreads();
+    const int total = off[slices];
+    for (int e = tid; e < total; e += 256) {
+        const u64 x = sm[e];
+        int rank = 0;
+        for (int s = 0; s < slices; ++s) {
+            const int b = off[s], n = off[s + 1] - b;
+            if (e >= b && e < b + n) {
+                rank += e - b;
+                continue;
+            }
+            int lo = 0, hi = n;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (sm[b + mid] > x) lo = mid + 1; else hi = mid;
+            }
+            rank += lo;
+        }
+        if (rank < k) {
+            const float val = ord_value((unsigned)(x >> 32));
+            const size_t o = (size_t)qi * k + rank;
+            index[o] = (int64_t)(0xFFFFFFFFu - (unsigned)x);
+            logit[o] = val;
+            prob[o] = sigmoid_ref(val);
+        }
+    }
+    for (int r = total + tid; r < k; r += 256) {                // fewer than k candidates: padding
+        const size_t o = (size_t)qi * k + r;
+        index[o] = -1;
+        logit[o] = __uint_as_float(0x7FC00000u);
+        prob[o] = __uint_as_float(0x7FC00000u);
+    }
+}
+
+__global__ void gather_rows_kernel(const float* __restrict__ Z, const float* __restrict__ H, const int32_t* __restrict__ rows,
+                                   int Q, int w, float* __restrict__ zq, float* __restrict__ hq) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= (size_t)Q * w) return;
+    const size_t r = g / w, c = g % w;
+    const size_t src = (size_t)rows[r] * w + c;
+    zq[g] = Z[src];
+    hq[g] = H[src];
+}
+
+// per target: its query row, from the CSR of targets by query
+__global__ void target_rows_kernel(const int32_t* __restrict__ tptr, int Q, int32_t* __restrict__ trow) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Q) return;
+    for (int i = tptr[q]; i < tptr[q + 1]; ++i) trow[i] = q;
+}
+
+// sort each row's target logits (ascending by value order; rows are short): position and first position of its value
+__global__ void target_sort_kernel(const int32_t* __restrict__ tptr, const int32_t* __restrict__ trow, const float* __restrict__ tlogit,
+                                   int T, unsigned* __restrict__ tord, int32_t* __restrict__ spos, int32_t* __restrict__ sfirst) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= T) return;
+    const int q = trow[i], b = tptr[q], e = tptr[q + 1];
+    const unsigned o = ord_key(tlogit[i]);
+    int lt = 0, pos = 0;
+    for (int j = b; j < e; ++j) {
+        const unsigned oj = ord_key(tlogit[j]);
+        lt += oj < o ? 1 : 0;
+        pos += (oj < o || (oj == o && j < i)) ? 1 : 0;
+    }
+    tord[b + pos] = o;
+    spos[i] = pos;
+    sfirst[i] = lt;
+}
+
+__global__ void target_finish_kernel(const int32_t* __restrict__ tptr, const int32_t* __restrict__ trow, const int32_t* __restrict__ tdst,
+                                     const int32_t* __restrict__ qnode, const int32_t* __restrict__ spos, const int32_t* __restrict__ sfirst,
+                                     const u64* __restrict__ gcnt, const u64* __restrict__ tcnt, const int32_t* __restrict__ ex_rowptr,
+                                     const int32_t* __restrict__ ex_col, int T, int64_t* __restrict__ greater, int64_t* __restrict__ ties) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= T) return;
+    const int q = trow[i], b = tptr[q], m = tptr[q + 1] - b;
+    u64 g = 0;
+    for (int p = spos[i] + 1; p <= m; ++p) g += gcnt[b + q + p];
+    u64 tie = tcnt[b + sfirst[i]];
+    const int node = qnode[q], v = tdst[i];
+    bool counted = v != node;                                   // the scan counted the target itself among the ties
+    if (counted && ex_rowptr != nullptr) {
+        int lo = ex_rowptr[node], hi = ex_rowptr[node + 1];
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ex_col[mid] < v) lo = mid + 1; else hi = mid;
+        }
+        counted = !(lo < ex_rowptr[node + 1] && ex_col[lo] == v);
+    }
+    greater[i] = (int64_t)g;
+    ties[i] = (int64_t)tie - (counted ? 1 : 0);
+}
+
+}  // namespace rank
+
+using namespace rank;
+
+bool score_rank_supported(int K, int d) { return K >= 1 && K <= DL_MAX_FACTORS && d >= 1 && d <= 128; }
+
+static int device_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, c = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+            n = c;
+        if (n <= 0) n = 256;
+    }
+    return n;
+}
+
+// Slicing of the candidate tiles: as many slices as keep one work item per CU busy (one workgroup per CU fits the LDS),
+// at most MAX_SLICES, never an empty slice.  DL_RANK_SLICES (test knob) forces the count; results do not depend on it.
+struct RankPlan { int nd, qtiles, nt, slices, tps, cap; size_t qbatch, cbatch; };
+static RankPlan rank_plan(int N, int d, int Q, int k) {
+    RankPlan p;
+    p.nd = (d + SDC - 1) / SDC;
+    p.qtiles = (Q + TT - 1) / TT;
+    p.nt = (N + TT - 1) / TT;
+    const int want = config().rank_slices > 0 ? config().rank_slices : device_cus() / max(1, p.qtiles);
+    const int s = max(1, min(min(want, MAX_SLICES), p.nt));
+    p.tps = (p.nt + s - 1) / s;
+    p.slices = (p.nt + p.tps - 1) / p.tps;
+    p.cap = k + ROUND;
+    p.qbatch = plane_array_elems(Q, d, SDC);
+    p.cbatch = plane_array_elems(N, d, SDC);
+    return p;
+}
+
+// Workspace (256-byte aligned blocks): gathered query rows (fp32) | their planes | planes of Z and H | TOPK: lists, counts |
+// RANKS: per-target arrays and the two counter arrays.
+struct RankWs {
+    float *zq, *hq, *tlogit;
+    __bf16 *qz, *qh, *cz, *ch;
+    u64 *lists, *gcnt, *tcnt;
+    int *counts;
+    int32_t *trow, *spos, *sfirst;
+    unsigned* tord;
+    size_t bytes;
+};
+static RankWs rank_carve(const RankPlan& p, int Q, int K, int d, int k, int T, void* ws) {
+    RankWs w = {};
+    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        char* r = base + o;
+        o += (bytes + 255) & ~(size_t)255;
+        return (void*)r;
+    };
+    w.zq = (float*)take(sizeof(float) * (size_t)Q * K * d);
+    w.hq = (float*)take(sizeof(float) * (size_t)Q * K * d);
+    w.qz = (__bf16*)take(2 * (size_t)K * p.qbatch);
+    w.qh = (__bf16*)take(2 * (size_t)K * p.qbatch);
+    w.cz = (__bf16*)take(2 * (size_t)K * p.cbatch);
+    w.ch = (__bf16*)take(2 * (size_t)K * p.cbatch);
+    if (k > 0) {
+        w.lists = (u64*)take(sizeof(u64) * (size_t)Q * p.slices * p.cap);
+        w.counts = (int*)take(sizeof(int) * (size_t)Q * p.slices);
+    }
+    if (T > 0) {
+        w.trow = (int32_t*)take(sizeof(int32_t) * (size_t)T);
+        w.spos = (int32_t*)take(sizeof(int32_t) * (size_t)T);
+        w.sfirst = (int32_t*)take(sizeof(int32_t) * (size_t)T);
+        w.tlogit = (float*)take(sizeof(float) * (size_t)T);
+        w.tord = (unsigned*)take(sizeof(unsigned) * (size_t)T);
+        w.gcnt = (u64*)take(sizeof(u64) * ((size_t)T + Q));
+        w.tcnt = (u64*)take(sizeof(u64) * (size_t)T);
+    }
+    w.bytes = o + 256;
+    return w;
+}
+
+size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T) {
+    return rank_carve(rank_plan(N, d, Q, k), Q, K, d, k, T, nullptr).bytes;
+}
+
+// the query rows gathered and split, the candidate tables split: the scan's operands
+static ScanArgs scan_operands(const RankPlan& p, const RankWs& w, const float* Z, const float* H, int N, int K, int d, float t,
+                              const int32_t* queries, int Q, const int32_t* exr, const int32_t* exc, hipStream_t st) {
+    const size_t n = (size_t)Q * K * d;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Z, H, queries, Q, K * d, w.zq, w.hq);
+    split_rows(w.zq, K, Q, d, K * d, (size_t)d, w.qz, st);
+    split_rows(w.hq, K, Q, d, K * d, (size_t)d, w.qh, st);
+    split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
+    split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
+    ScanArgs a = {};
+    a.qz = w.qz; a.qh = w.qh; a.qbatch = p.qbatch;
+    a.cz = w.cz; a.ch = w.ch; a.cbatch = p.cbatch;
+    a.Q = Q; a.N = N; a.K = K; a.nd = p.nd; a.t = t;
+    a.qnode = queries;
+    a.ex_rowptr = exr; a.ex_col = exc;
+    a.slices = p.slices; a.tiles_per_slice = p.tps;
+    return a;
+}
+
+int score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, int k,
+               const int32_t* exr, const int32_t* exc, int exclude_self, int64_t* index, float* logit, float* prob, void* ws,
+               hipStream_t st) {
+    static unsigned long long lds_done = 0;
+    const RankPlan p = rank_plan(N, d, Q, k);
+    const RankWs w = rank_carve(p, Q, K, d, k, 0, ws);
+    ScanArgs a = scan_operands(p, w, Z, H, N, K, d, t, queries, Q, exr, exc, st);
+    a.exclude_self = exclude_self ? 1 : 0;
+    a.k = k; a.cap = p.cap; a.lists = w.lists; a.counts = w.counts;
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<TOPK>), LDS_BYTES, lds_done);
+    hipLaunchKernelGGL(rank_scan_kernel<TOPK>, dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES, st, a);
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)Q), dim3(256), 0, st, w.lists, w.counts, p.slices, p.cap, k, index,
+                       logit, prob);
+    return check_launch("score_topk");
+}
+
+int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, const int32_t* tptr,
+                const int32_t* tdst, int T, const int32_t* exr, const int32_t* exc, int64_t* greater, int64_t* ties, void* ws,
+                hipStream_t st) {
+    static unsigned long long lds_diag = 0, lds_rank = 0;
+    const RankPlan p = rank_plan(N, d, Q, 0);
+    const RankWs w = rank_carve(p, Q, K, d, 0, T, ws);
+    ScanArgs a = scan_operands(p, w, Z, H, N, K, d, t, queries, Q, exr, exc, st);
+    hipLaunchKernelGGL(target_rows_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, tptr, Q, w.trow);
+    // the targets' own logits, from the scan's arithmetic with the query as the A operand: tile i of the targets against
+    // itself, the diagonal kept
+    ScanArgs g = a;
+    g.trow = w.trow; g.tdst = tdst; g.T = T; g.tlogit = w.tlogit;
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<DIAG>), LDS_BYTES, lds_diag);
+    hipLaunchKernelGGL(rank_scan_kernel<DIAG>, dim3((unsigned)xcd_grid((T + TT - 1) / TT, 1)), dim3(RTHR), LDS_BYTES, st, g);
+    const unsigned tb = (unsigned)((T + 255) / 256);
+    hipLaunchKernelGGL(target_sort_kernel, dim3(tb), dim3(256), 0, st, tptr, w.trow, w.tlogit, T, w.tord, w.spos, w.sfirst);
+    hipError_t e = hipMemsetAsync(w.gcnt, 0, sizeof(u64) * ((size_t)T + Q), st);
+    if (e == hipSuccess) e = hipMemsetAsync(w.tcnt, 0, sizeof(u64) * (size_t)T, st);
+    DL_REQUIRE(e == hipSuccess, "hipMemsetAsync: %s", hipGetErrorString(e));
+    a.exclude_self = 1;
+    a.tptr = tptr; a.tord = w.tord; a.gcnt = w.gcnt; a.tcnt = w.tcnt;
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<RANKS>), LDS_BYTES, lds_rank);
+    hipLaunchKernelGGL(rank_scan_kernel<RANKS>, dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES, st, a);
+    hipLaunchKernelGGL(target_finish_kernel, dim3(tb), dim3(256), 0, st, tptr, w.trow, tdst, queries, w.spos, w.sfirst, w.gcnt,
+                       w.tcnt, exr, exc, T, greater, ties);
+    return check_launch("score_ranks");
+}
+
+}  // namespace dl

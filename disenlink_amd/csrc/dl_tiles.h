@@ -156,6 +156,24 @@ __device__ __forceinline__ void mfma_split6(f32x16& acc, const bf16x8 (&a)[3], c
     acc = c;
 }
 
+// One K = 16 block (kb) of a 128 x 128 tile Gram product A . B^T from two LDS plane images [3][128][SPLIT_PITCH]: the wave
+// that owns rows 32 wu .. 32 wu + 31 of A and rows 64 wv .. 64 wv + 63 of B passes ub = A image + (32 wu + lane % 32) rows
+// + 8 (lane / 32) and vb likewise (64 wv), and accumulates the two 32 x 32 blocks acc[0] (B rows + 0) and acc[1] (+ 32).
+// Shared by the dense scorer (dl_score_dense.hip) and the ranking scan (dl_score_rank.hip): the same products in the
+// same order, so both form the same bits for the same pair of rows.
+__device__ __forceinline__ void gram_block_split6(f32x16 (&acc)[2], const __bf16* ub, const __bf16* vb, int kb) {
+    constexpr int T = 128;
+    bf16x8 a[3], b0[3], b1[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        a[p] = *reinterpret_cast<const bf16x8*>(ub + p * T * SPLIT_PITCH + kb * 16);
+        b0[p] = *reinterpret_cast<const bf16x8*>(vb + p * T * SPLIT_PITCH + kb * 16);
+        b1[p] = *reinterpret_cast<const bf16x8*>(vb + (p * T + 32) * SPLIT_PITCH + kb * 16);
+    }
+    mfma_split6(acc[0], a, b0);                                 // six products, smallest terms first
+    mfma_split6(acc[1], a, b1);
+}
+
 // Write a fetched [ROWS][32] tile (TileStage<ROWS, 32, true, THREADS>) to LDS as three bf16 planes; what lies outside
 // the matrix is written as zero.
 template <int ROWS, int THREADS>

@@ -55,6 +55,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "(libdisenlink_torch.so) is absent, eager when it is present — with it and the end-of-epoch "
                         "bookkeeping on the device the eager loop is gapless and 3-10 %% faster than the replay")
     p.add_argument("--quiet", action="store_true")
+    p.add_argument("--rank-eval", action="store_true",
+                   help="after each run, rank every test positive among all nodes (filtered by every dataset edge) and "
+                        "print MRR and Hits@{1,10,50,100}")
     p.add_argument("--gpus", type=int, default=1,
                    help="row-shard every run over this many GPUs of the node (one process per GPU, RCCL): started "
                         "plainly, the command launches its ranks itself (disenlink_amd/launch.py)")
@@ -157,6 +160,21 @@ def main_sharded(args):
         dist.destroy_process_group()
 
 
+def rank_eval(model, x, graph, split, known) -> dict:
+    """MRR and Hits@{1,10,50,100} of the test positives, each ranked among all nodes with every known edge filtered out
+    (Disentangle.link_ranks: the model with its best weights, as run_link_prediction leaves it)."""
+    from .metrics import ranking_metrics
+    pos = split.test.label > 0.5
+    src = torch.from_numpy(np.ascontiguousarray(split.test.u[pos])).to(x.device)
+    dst = torch.from_numpy(np.ascontiguousarray(split.test.v[pos])).to(x.device)
+    greater, ties = model.link_ranks(x, graph, src, dst, exclude=known)
+    return ranking_metrics(greater, ties)
+
+
+def _fmt_ranking(r: dict) -> str:
+    return " ".join(f"{key} {val:.4f}" for key, val in r.items())
+
+
 def _use_graph(args) -> bool:
     """--graph / --no-graph, else by what is faster: the replayed epoch saves host time per launch, which only matters when
     the launches go through the Python operators (chameleon 0.38 vs 0.76 ms); through the compiled binding, with early
@@ -173,6 +191,8 @@ def main(argv=None):
     args = build_parser().parse_known_args(argv)[0]                 # unknown tokens ignored, like :50
     if args.layer != 1:
         raise SystemExit("only --layer 1 exists in the reference (main_disentangled.py:147-148)")
+    if args.gpus > 1 and args.rank_eval:
+        raise SystemExit("--rank-eval runs on one GPU only (sharded ranking is not implemented): drop --gpus or --rank-eval")
     if args.gpus > 1:
         from .launch import launch_ranks, under_launcher
         if not under_launcher():                                    # BEFORE any GPU call: the parent starts and waits
@@ -197,6 +217,10 @@ def main(argv=None):
     x = torch.from_numpy(ds.x).to(device)
     tdt = torch.bfloat16 if args.table_dtype == "bf16" else torch.float32
     result = []
+    ranking = []
+    if args.rank_eval:                                              # filter: every dataset edge, both directions
+        s_all, d_all = torch.from_numpy(np.asarray(ds.src)).long(), torch.from_numpy(np.asarray(ds.dst)).long()
+        known = (torch.cat([s_all, d_all]).to(device), torch.cat([d_all, s_all]).to(device))
     for run in range(args.run):
         if not args.quiet:
             print("run:", run)
@@ -210,8 +234,16 @@ def main(argv=None):
         if not args.quiet:
             print("test auc:", res.test_auc)
         result.append(res.test_auc)
+        if args.rank_eval:
+            ranking.append(rank_eval(model, x, prepared.graph, split, known))
+            if not args.quiet:
+                print("test ranking:", _fmt_ranking(ranking[-1]))
     result = np.array(result)
-    print("final", result.mean(), result.std())
+    if args.rank_eval:                                              # the run means of the ranking metrics join the final line
+        print("final", result.mean(), result.std(),
+              _fmt_ranking({key: float(np.mean([r[key] for r in ranking])) for key in ranking[0]}))
+    else:
+        print("final", result.mean(), result.std())
     if args.save == 1:                                              # :225-246
         save_results(args, result)
     return result

@@ -6,6 +6,7 @@
   auc_tie_avg     main_disentangled.py:202-204, :217-219 — sklearn.roc_auc_score on fp32 probabilities,
                   i.e. Mann-Whitney U with tie-averaged ranks; computed with torch ops on the device so
                   the per-epoch device->host copy of all validation scores disappears.
+  ranking_metrics MRR and Hits@K of filtered ranks (ops.score_ranks); an extension, the reference has none.
 """
 from __future__ import annotations
 
@@ -180,3 +181,22 @@ class ShardedAucPlan:
         red = u2.cpu() if self._cpu_wire else u2
         self.dist.all_reduce(red, group=self.group)
         return self.auc_from_sum(red)
+
+
+def ranking_metrics(greater, ties, ks=(1, 10, 50, 100)) -> dict:
+    """{"mrr": ..., "hits@K": ...} of the ranks rank = 1 + greater + ties / 2 (ops.score_ranks; ties averaged as the AUC
+    does): MRR = mean(1 / rank), Hits@K = mean(rank <= K).  NaN for an empty set of targets."""
+    g = torch.as_tensor(greater).reshape(-1).to(torch.float64)
+    t = torch.as_tensor(ties).reshape(-1).to(torch.float64)
+    if g.numel() != t.numel():
+        raise ValueError("greater and ties differ in length")
+    out = {}
+    if g.numel() == 0:
+        out["mrr"] = float("nan")
+        out.update({f"hits@{int(k)}": float("nan") for k in ks})
+        return out
+    rank = 1.0 + g + t / 2.0
+    out["mrr"] = float((1.0 / rank).mean())
+    for k in ks:
+        out[f"hits@{int(k)}"] = float((rank <= k).to(torch.float64).mean())
+    return out

@@ -7,12 +7,15 @@ routing / aggregation / scoring path running on libdisenlink_hip.so.
     emb, a_pred = model(x, adj_sym)                       # main_disentangled.py:194
 
 For graphs where ``[N,N]`` cannot exist, ``forward_pairs(x, graph, pairs)`` scores a pair
-list instead; the reference has no counterpart for it.
+list instead; the reference has no counterpart for it.  Neither has ranking:
+``topk_links`` (the k most likely links of query nodes) and ``link_ranks`` (filtered ranks of target pairs among all
+nodes, for MRR / Hits@K) score every candidate on the matrix cores without an ``[N,N]`` tensor.
 """
 from __future__ import annotations
 
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -20,6 +23,9 @@ import torch.nn.functional as F
 
 from . import ops
 from .graph import Graph, PairList
+
+
+TopLinks = namedtuple("TopLinks", ["index", "logit", "prob"])
 
 
 class Factor(nn.Module):
@@ -316,3 +322,25 @@ class Disentangle(nn.Module):
         Z = self.project(x)
         H, prob = ops.HotPathPairs.apply(Z, graph, pairs, float(self.beta), float(self.temperature), self.table_dtype)
         return H.view(H.shape[0], -1), prob
+
+    # ------------------------------------------------------------------ ranking (inference only)
+    def _rank_tables(self, x, adj):
+        """Z and H of forward(x, adj) — the same projection and routing / aggregation, under no_grad."""
+        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        with torch.no_grad():
+            Z = self.project(x)
+            H = ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
+        return Z, H
+
+    def topk_links(self, x, adj, queries, k: int, exclude=None, exclude_self: bool = True) -> TopLinks:
+        """The k most likely links of every node in ``queries``: TopLinks(index int64 [Q,k], logit, prob f32 [Q,k]),
+        ranked by the pre-sigmoid logit of link_pred (prob = link_pred's value).  ``adj`` as in forward; ``exclude``: a
+        Graph, a dense [N,N] mask or (rows, cols) of pairs that are not candidates (ops.score_topk)."""
+        Z, H = self._rank_tables(x, adj)
+        return TopLinks(*ops.score_topk(Z, H, float(self.temperature), queries, k, exclude, exclude_self))
+
+    def link_ranks(self, x, adj, src, dst, exclude=None):
+        """(greater, ties) int64 per target pair (src[i], dst[i]) among all nodes except src[i] and its exclusion set
+        (ops.score_ranks; metrics.ranking_metrics turns them into MRR / Hits@K)."""
+        Z, H = self._rank_tables(x, adj)
+        return ops.score_ranks(Z, H, float(self.temperature), src, dst, exclude)

@@ -1049,3 +1049,134 @@ class ScoreAllPairs(torch.autograd.Function):
         if valid is not None:
             dZ, dH = dZ * valid, dH * valid
         return dZ, dH, None, None
+
+
+# ---------------------------------------------------------------------- ranking of all candidates (dl_score_rank.hip)
+RANK_MAX_K = 128
+
+
+def exclusion_csr(exclude, n_nodes: int, device=None):
+    """Normalise an exclusion set to the CSR the ranking kernels take: (rowptr int32 [N+1], col int32) with ascending,
+    distinct columns per row, on ``device`` (default: where the set lives), or (None, None) for ``exclude=None``.
+    ``exclude``: a ``Graph`` (its stored entries), a dense [N,N] mask (entries != 0) or a ``(rows, cols)`` pair of index
+    sequences.  Duplicates collapse (``torch.unique`` on row * N + col)."""
+    if exclude is None:
+        return None, None
+    N = int(n_nodes)
+    if isinstance(exclude, Graph):
+        if exclude.n_nodes != N:
+            raise ValueError(f"exclusion graph has {exclude.n_nodes} nodes, expected {N}")
+        ptr = exclude.rowptr.to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(exclude.row_offset, exclude.row_offset + exclude.n_rows,
+                                                    device=ptr.device), ptr[1:] - ptr[:-1])
+        cols = exclude.col[:rows.numel()].to(torch.int64)
+    elif isinstance(exclude, (tuple, list)):
+        if len(exclude) != 2:
+            raise ValueError("an exclusion pair list is (rows, cols)")
+        rows, cols = (torch.as_tensor(v, device=device).reshape(-1).to(torch.int64) for v in exclude)
+        if rows.numel() != cols.numel():
+            raise ValueError("exclusion rows and cols differ in length")
+        if rows.numel() and (int(rows.min()) < 0 or int(cols.min()) < 0 or int(rows.max()) >= N or int(cols.max()) >= N):
+            raise ValueError("exclusion pair outside [0, N)")
+    else:
+        m = torch.as_tensor(exclude, device=device)
+        if m.dim() != 2 or tuple(m.shape) != (N, N):
+            raise ValueError(f"an exclusion mask must be [N, N] = [{N}, {N}], got {tuple(m.shape)}")
+        rows, cols = torch.nonzero(m, as_tuple=True)
+    dev = rows.device if device is None else torch.device(device)
+    key = torch.unique(rows.to(dev) * N + cols.to(dev))               # sorted: rows ascending, columns ascending in a row
+    r = torch.div(key, N, rounding_mode="floor")
+    rowptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=N), dim=0)
+    return rowptr.to(torch.int32), (key - r * N).to(torch.int32)
+
+
+def _rank_tables(Z, H):
+    """fp32 [N,K,d] tables on the device, 1 <= d <= 128 (dl_score_topk_supported): the ranking kernels take nothing else."""
+    if Z.dtype != torch.float32 or H.dtype != torch.float32:
+        raise TypeError(f"the ranking kernels take fp32 tables, got {Z.dtype} / {H.dtype}")
+    _need_cuda(Z, H)
+    N, K, d = _nkd(Z)
+    if tuple(H.shape) != tuple(Z.shape):
+        raise ValueError("Z and H differ in shape")
+    if N < 1 or not _lib.load().dl_score_topk_supported(K, d):
+        raise _lib.DisenlinkHipError(f"the ranking kernels serve N >= 1, K <= 64 and 1 <= d <= 128 (got N={N}, K={K}, d={d})")
+    return Z.contiguous(), H.contiguous(), N, K, d
+
+
+def _node_ids(ids, N: int, device, what: str) -> torch.Tensor:
+    ids = torch.as_tensor(ids, device=device).reshape(-1)
+    if ids.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what} must be integer node ids, got {ids.dtype}")
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= N):
+        raise ValueError(f"{what} outside [0, {N})")
+    return ids.to(torch.int32).contiguous()
+
+
+def _csr_args(rowptr, col, device):
+    if rowptr is None:
+        return None, None, ()
+    if col.numel() == 0:                                             # a valid address for an empty column array
+        col = torch.zeros(1, dtype=torch.int32, device=device)
+    return rowptr.data_ptr(), col.data_ptr(), (rowptr, col)
+
+
+def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool = True):
+    """-> (index int64 [Q,k], logit f32 [Q,k], prob f32 [Q,k]): the k best candidates of every query node by the logit
+    s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), sorted (larger
+    first, +inf first, NaN last, equal logits by index), prob = sigmoid(logit).  Candidates: every node outside the
+    query's exclusion set (``exclusion_csr``) and, with ``exclude_self``, other than the query itself; rows with fewer than
+    k are padded with index -1 / NaN.  Inference only (dl_score_topk: nothing of size Q x N is formed)."""
+    lib = _lib.load()
+    Z, H, N, K, d = _rank_tables(Z, H)
+    k = int(k)
+    if not 1 <= k <= RANK_MAX_K:
+        raise ValueError(f"k={k} outside 1..{RANK_MAX_K}")
+    q = _node_ids(queries, N, Z.device, "queries")
+    Q = int(q.numel())
+    index = _empty((Q, k), torch.int64, Z.device)
+    logit = _empty((Q, k), torch.float32, Z.device)
+    prob = _empty((Q, k), torch.float32, Z.device)
+    if Q == 0:
+        return index, logit, prob
+    rp, cp, _keep = _csr_args(*exclusion_csr(exclude, N, Z.device), Z.device)
+    ws = _ws.get(int(lib.dl_score_topk_workspace_bytes(N, K, d, Q, k, 0)), Z.device)
+    _lib.check(lib.dl_score_topk(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), q.data_ptr(), Q, k, rp, cp,
+                                 1 if exclude_self else 0, index.data_ptr(), logit.data_ptr(), prob.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), _stream()), "dl_score_topk")
+    return index, logit, prob
+
+
+def score_ranks(Z, H, t: float, src, dst, exclude=None):
+    """-> (greater, ties) int64 [P] for the target pairs (src[i], dst[i]): how many candidates of src[i] (every node other
+    than src[i] and outside its exclusion set; dst[i] itself is never counted, and is ranked even when it is in the
+    exclusion set — the filtered protocol) have a logit strictly above / equal to the target's, by value.  The target's
+    logit is the one the scan computes.  rank = 1 + greater + ties / 2 (metrics.ranking_metrics).  dl_score_ranks."""
+    lib = _lib.load()
+    Z, H, N, K, d = _rank_tables(Z, H)
+    s = _node_ids(src, N, Z.device, "src")
+    v = _node_ids(dst, N, Z.device, "dst")
+    if s.numel() != v.numel():
+        raise ValueError("src and dst differ in length")
+    T = int(s.numel())
+    greater = _empty(T, torch.int64, Z.device)
+    ties = _empty(T, torch.int64, Z.device)
+    if T == 0:
+        return greater, ties
+    order = torch.argsort(s, stable=True)                              # targets grouped by query node
+    queries, counts = torch.unique_consecutive(s[order], return_counts=True)
+    Q = int(queries.numel())
+    tptr = torch.zeros(Q + 1, dtype=torch.int32, device=Z.device)
+    tptr[1:] = torch.cumsum(counts, dim=0).to(torch.int32)
+    tdst = v[order].contiguous()
+    queries = queries.to(torch.int32).contiguous()
+    g_sorted = _empty(T, torch.int64, Z.device)
+    t_sorted = _empty(T, torch.int64, Z.device)
+    rp, cp, _keep = _csr_args(*exclusion_csr(exclude, N, Z.device), Z.device)
+    ws = _ws.get(int(lib.dl_score_topk_workspace_bytes(N, K, d, Q, 0, T)), Z.device)
+    _lib.check(lib.dl_score_ranks(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), queries.data_ptr(), Q, tptr.data_ptr(),
+                                  tdst.data_ptr(), T, rp, cp, g_sorted.data_ptr(), t_sorted.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), _stream()), "dl_score_ranks")
+    greater[order] = g_sorted
+    ties[order] = t_sorted
+    return greater, ties

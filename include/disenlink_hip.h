@@ -295,6 +295,37 @@ int dl_score_allpairs_bwd(const void* Z, const void* H, int N, int K, int d, dl_
                           const float* prob, const float* g_prob, float* dZ, float* dH,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* Ranking of ALL candidate links of query nodes (an extension; the reference has no counterpart): the logit of the dense
+ * scorer, s(u,v) = sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), for every
+ * (query, candidate) pair on the matrix cores (the dense scorer's three-plane products, the query as the A operand;
+ * d padded to a multiple of 32 with zero columns), and nothing of size n_queries x N in memory.
+ * Total order: a larger logit ranks first; +inf above every finite value, -inf below every finite value, NaN below
+ * everything (-0 equals +0); equal logits by candidate index, the smaller first.
+ * Candidates of query row q (node u = queries[q], int32 in [0, N)): every v in [0, N) except the columns of row u of the
+ * exclusion CSR (ex_rowptr [N+1], ex_col: int32, ascending columns per row; both NULL = nothing excluded) and, when
+ * exclude_self != 0, u itself.  fp32 tables Z, H [N][K][d] with 1 <= d <= 128 (dl_score_topk_supported); anything else
+ * fails.  Inference only.
+ * ws: dl_score_topk_workspace_bytes(N, K, d, n_queries, k, 0) bytes for dl_score_topk and (.., n_queries, 0, n_targets)
+ * for dl_score_ranks: the gathered query rows and their planes, the planes of Z and H, and for top-k n_queries x slices
+ * lists of k + 64 8-byte keys.  Results are bitwise reproducible and do not depend on the slicing (DL_RANK_SLICES). */
+int dl_score_topk_supported(int K, int d);
+size_t dl_score_topk_workspace_bytes(int N, int K, int d, int n_queries, int k, int n_targets);
+/* Top-k (1 <= k <= 128) per query row: index int64 [n_queries][k], logit and prob = sigmoid(logit) fp32 [n_queries][k],
+ * sorted by the total order; a row with fewer than k candidates is padded at the end with index -1 and NaN.  Duplicate
+ * query ids are allowed. */
+int dl_score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries, int k,
+                  const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index, float* logit, float* prob,
+                  void* ws, size_t ws_bytes, void* stream);
+/* Filtered rank counts of target pairs, grouped by query: the targets of query row q are tdst[tptr[q] .. tptr[q+1])
+ * (tptr [n_queries+1] int32).  For target i = (u, v), with s_i = s(u, v) as the scan computes it (bit for bit):
+ *   greater[i] = #{candidates w != v of row q: s(u, w) ranks strictly above s_i by value}
+ *   ties[i]    = #{candidates w != v of row q: s(u, w) has the value of s_i}   (NaN equals NaN, inf equals inf)
+ * (int64).  The query node u itself is never a candidate; the target v is never excluded from being ranked even when it is
+ * in the exclusion set (the "filtered" protocol).  rank = 1 + greater + ties / 2. */
+int dl_score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
+                   const int32_t* tptr, const int32_t* tdst, int n_targets, const int32_t* ex_rowptr, const int32_t* ex_col,
+                   int64_t* greater, int64_t* ties, void* ws, size_t ws_bytes, void* stream);
+
 /* Tie-averaged AUC of a score vector against FIXED labels: replaces sklearn.metrics.roc_auc_score at
  * main_disentangled.py:202-204 / 217-219 (validation AUC every epoch, test AUC at the end).  pos_idx / neg_idx
  * (int64, device) are the positions of the positive and negative labels in score, found once per run; the call
