@@ -75,6 +75,9 @@ EXPORTS = {
     "dl_score_allpairs_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "dl_score_allpairs_fwd": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _z, _P]),
     "dl_score_allpairs_bwd": (_i, [_P, _P, _i, _i, _i, _i, _f, _I, _P, _P, _i, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_score_allpairs_bwd_dense_supported": (_i, [_i, _i]),
+    "dl_score_allpairs_bwd_dense_workspace_bytes": (_z, [_i, _i, _i]),
+    "dl_score_allpairs_bwd_dense": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_topk_supported": (_i, [_i, _i]),
     "dl_score_topk_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "dl_score_topk": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _i, _P, _P, _i, _P, _P, _P, _P, _z, _P]),

@@ -462,6 +462,32 @@ int dl_score_allpairs_bwd(const void* Z, const void* H, int N, int K, int d, dl_
     return dl_score_pairs_bwd(Z, H, K, d, dtype, t, inc, w.dw, w.dwr, nullptr, dZ, dH, ws, ws_bytes, stream);
 }
 
+int dl_score_allpairs_bwd_dense_supported(int K, int d) {
+    return K >= 1 && K <= DL_MAX_FACTORS && dense_bwd_supported(d) ? 1 : 0;
+}
+
+size_t dl_score_allpairs_bwd_dense_workspace_bytes(int N, int K, int d) {
+    if (N <= 0 || N > 46340 || !dl_score_allpairs_bwd_dense_supported(K, d)) return 0;
+    return dense_bwd_workspace_bytes(N, K, d);
+}
+
+int dl_score_allpairs_bwd_dense(const float* Z, const float* H, int N, int K, int d, float t, const float* prob,
+                                const float* g_prob, float* dZ, float* dH, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(dense_bwd_supported(d), "the dense backward serves fp32 tables with 1 <= d <= 128, got d=%d", d);
+    DL_REQUIRE(N >= 0 && N <= 46340, "dense [N,N] scoring needs 0 <= N <= 46340, got %d", N);
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    if (N == 0) return DL_OK;
+    DL_REQUIRE(Z && H && prob && g_prob && dZ && dH, "NULL argument");
+    const size_t need = dense_bwd_workspace_bytes(N, K, d);
+    if (!ws || ws_bytes < need) {
+        set_error("workspace too small: have %zu, need %zu (dl_score_allpairs_bwd_dense_workspace_bytes)", ws ? ws_bytes : (size_t)0,
+                  need);
+        return DL_E_WORKSPACE;
+    }
+    return dense_bwd_score_allpairs(Z, H, N, K, d, t, prob, g_prob, dZ, dH, ws, (hipStream_t)stream);
+}
+
 int dl_score_pairs_train_supported(const dl_pair_incidence* inc, int K, int d, dl_dtype dtype) {
     return inc != nullptr && use_fast(&inc->csr, K, d, dtype) ? 1 : 0;
 }

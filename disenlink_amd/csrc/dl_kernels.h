@@ -56,6 +56,12 @@ size_t dense_score_workspace_bytes(int N, int K, int d);
 int dense_mfma_score_allpairs_fwd(const float* Z, const float* H, int N, int K, int d, float t, float* prob, void* ws, size_t ws_bytes,
                                   hipStream_t st);
 
+// dense backward of the dense scorer on the matrix cores (dl_score_dense_bwd.hip): fp32 tables, 1 <= d <= 128
+bool dense_bwd_supported(int d);
+size_t dense_bwd_workspace_bytes(int N, int K, int d);
+int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d, float t, const float* prob, const float* g_prob,
+                             float* dZ, float* dH, void* ws, hipStream_t st);
+
 // ranking of all candidates of query rows on the matrix cores (dl_score_rank.hip): fp32 tables, 1 <= d <= 128
 bool score_rank_supported(int K, int d);
 size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T);

@@ -53,7 +53,7 @@ class Factor2(nn.Module):
 
 class Disentangle(nn.Module):
     def __init__(self, nfeat, nhid, nebed, nfactor, beta, t=1, table_dtype=torch.float32, projection="auto",
-                 use_torch_ops=False):
+                 use_torch_ops=False, link_pred_backward="plan"):
         """Extensions (the reference has neither):
         ``table_dtype``: storage type of the gathered Z / H tables in ``forward_pairs`` — torch.float32
         (reference precision) or torch.bfloat16 (half the gather bytes, fp32 arithmetic and gradients).
@@ -68,8 +68,17 @@ class Disentangle(nn.Module):
         ``use_torch_ops``: ``forward_pairs`` goes through the REGISTERED operators ``torch.ops.disenlink.*``
         (disenlink_amd/torch_ops.py: schema + fake + autograd via torch.library over the same C ABI) instead of the
         ctypes-calling autograd.Functions — same kernels and bits; what it buys is dispatcher visibility:
-        ``torch.compile(model.forward_pairs)`` traces the whole step without graph breaks."""
+        ``torch.compile(model.forward_pairs)`` traces the whole step without graph breaks.
+        ``link_pred_backward``: how ``forward(x, adj)``'s dense link_pred is differentiated.  "plan" = on the pair plan of
+        the caller's loss masks (declared with set_loss_pairs / assume_static_loss_masks, or learnt from the indexing of
+        link_pred): the cheapest backward for the reference's masked loss.  "dense" = the gradient of ANY loss on
+        link_pred — a whole-matrix reconstruction loss, ``link_pred.mean()``, a regulariser — by the dense matrix-core
+        backward (ops.score_allpairs_bwd_dense): link_pred is a plain tensor, nothing is declared or learnt, no host
+        read; it costs the same whatever the loss touches (INTEGRATION.md §1 on which to choose)."""
         super().__init__()
+        if link_pred_backward not in ("plan", "dense"):
+            raise ValueError("link_pred_backward must be 'plan' or 'dense'")
+        self.link_pred_backward = link_pred_backward
         self.use_torch_ops = bool(use_torch_ops)
         if projection not in ("auto", "mfma", "library"):
             raise ValueError("projection must be 'auto', 'mfma' or 'library'")
@@ -244,6 +253,7 @@ class Disentangle(nn.Module):
         plan of the dense backward (dl_score_allpairs_bwd), built once, on the module's device.  Without it the plan is
         learnt from the gradients (it grows until it covers the masks; ops.DensePairPlanCache).
         ``set_loss_pairs()`` with no argument forgets a declared set."""
+        self._no_declaration_in_dense_mode("set_loss_pairs")
         if not supports:
             self._dense_plan.clear()
             return self
@@ -263,6 +273,7 @@ class Disentangle(nn.Module):
         be broken.  The masks are REQUIRED (here or through set_loss_pairs before): the support of a loss cannot be
         inferred from a gradient, whose non-zero set moves with fp32 sigmoid saturation.
         ``assume_static_loss_masks(static=False)`` returns to the validated mode (one 16-byte read per backward)."""
+        self._no_declaration_in_dense_mode("assume_static_loss_masks")
         if len(masks) == 1 and isinstance(masks[0], bool):        # round-2 spelling: assume_static_loss_masks(False)
             static, masks = masks[0], ()
         if masks:
@@ -272,6 +283,11 @@ class Disentangle(nn.Module):
                              "neg_train_adj), or call set_loss_pairs(...) first")
         self._dense_plan.static = bool(static)
         return self
+
+    def _no_declaration_in_dense_mode(self, what: str):
+        if getattr(self, "link_pred_backward", "plan") == "dense":
+            raise ValueError(f"{what}: link_pred_backward=\"dense\" differentiates every entry of link_pred and needs no "
+                             "declaration of where the loss is taken")
 
     def _graph_for(self, adj: torch.Tensor) -> Graph:
         """CSR + plans of a dense adjacency, built once per adjacency tensor: keyed on the tensor OBJECT (weak
@@ -289,6 +305,12 @@ class Disentangle(nn.Module):
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
         Z = self.project(x)
         H = ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
+        if getattr(self, "link_pred_backward", "plan") == "dense":
+            if not (Z.dtype == torch.float32 and ops.score_allpairs_bwd_dense_supported(self.nfactor, self.nebed)):
+                raise ops._lib.DisenlinkHipError(
+                    f"link_pred_backward=\"dense\" serves fp32 tables and factor widths d <= 128 (got {Z.dtype}, "
+                    f"d = {self.nebed}); there is no eager fallback — use link_pred_backward=\"plan\"")
+            return H.view(H.shape[0], -1), ops.ScoreAllPairsDense.apply(Z, H, float(self.temperature))
         link_pred = ops.ScoreAllPairs.apply(Z, H, float(self.temperature), self._dense_plan)
         # (a Tensor whose indexing reports the entries taken to this module's pair-plan cache: ops.LinkPred)
         return H.view(H.shape[0], -1), ops.as_link_pred(link_pred, self._dense_plan)

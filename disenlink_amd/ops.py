@@ -1051,6 +1051,56 @@ class ScoreAllPairs(torch.autograd.Function):
         return dZ, dH, None, None
 
 
+# ---------------------------------------------------------------------- dense backward of link_pred (dl_score_dense_bwd.hip)
+def score_allpairs_bwd_dense_supported(K: int, d: int) -> bool:
+    """fp32 tables with 1 <= d <= 128."""
+    return bool(_lib.load().dl_score_allpairs_bwd_dense_supported(int(K), int(d)))
+
+
+def score_allpairs_bwd_dense(Z, H, t: float, prob, g_prob):
+    """-> dZ, dH f32[N,K,d]: backward of score_allpairs_fwd for ANY dense gradient ``g_prob`` [N,N] (not necessarily
+    symmetric, possibly expanded or transposed: it is made contiguous fp32 here) on the matrix cores — no pair plan, no
+    host read.  ``prob`` is the forward's output.  Every element of dZ and dH is written."""
+    lib = _lib.load()
+    Z, H, prob = _f32c(Z), _f32c(H), _f32c(prob)
+    _need_cuda(Z, H, prob, g_prob)
+    N, K, d = _nkd(Z)
+    if H.shape != Z.shape:
+        raise ValueError("Z and H differ in shape")
+    if tuple(prob.shape) != (N, N) or tuple(g_prob.shape) != (N, N):
+        raise ValueError("prob / g_prob must be the dense [N, N] arrays")
+    if not lib.dl_score_allpairs_bwd_dense_supported(K, d):
+        raise _lib.DisenlinkHipError(f"the dense backward of link_pred serves fp32 tables with 1 <= d <= 128 (got K = {K}, "
+                                     f"d = {d}); there is no eager fallback")
+    g_prob = g_prob.to(torch.float32).contiguous()              # stride-0 (mean()) and transposed gradients arrive here
+    dZ = _empty(Z.shape, torch.float32, Z.device)
+    dH = _empty(Z.shape, torch.float32, Z.device)
+    ws = _ws.get(int(lib.dl_score_allpairs_bwd_dense_workspace_bytes(N, K, d)), Z.device)
+    _lib.check(lib.dl_score_allpairs_bwd_dense(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), prob.data_ptr(),
+                                               g_prob.data_ptr(), dZ.data_ptr(), dH.data_ptr(), ws.data_ptr(), ws.numel(),
+                                               _stream()), "dl_score_allpairs_bwd_dense")
+    return dZ, dH
+
+
+class ScoreAllPairsDense(torch.autograd.Function):
+    """ScoreAllPairs' forward with the dense backward: the gradient of whatever the caller does with link_pred, as the
+    reference's autograd gives it (model.py:109-113, main_disentangled.py:198) — no plan, no declaration, no host read."""
+
+    @staticmethod
+    def forward(ctx, Z, H, t: float):
+        Z, H = _f32c(Z), _f32c(H)
+        prob = score_allpairs_fwd(Z, H, t)
+        ctx.t = t
+        ctx.save_for_backward(Z, H, prob)
+        return prob
+
+    @staticmethod
+    def backward(ctx, g_prob):
+        Z, H, prob = ctx.saved_tensors
+        dZ, dH = score_allpairs_bwd_dense(Z, H, ctx.t, prob, g_prob)
+        return dZ, dH, None
+
+
 # ---------------------------------------------------------------------- ranking of all candidates (dl_score_rank.hip)
 RANK_MAX_K = 128
 

@@ -295,6 +295,27 @@ int dl_score_allpairs_bwd(const void* Z, const void* H, int N, int K, int d, dl_
                           const float* prob, const float* g_prob, float* dZ, float* dH,
                           void* ws, size_t ws_bytes, void* stream);
 
+/* Dense backward of dl_score_allpairs_fwd: the gradient of ANY loss on link_pred — what the reference's autograd gives
+ * for whatever its caller does with the dense output (model.py:109-113 under loss.backward(), main_disentangled.py:198)
+ * — without a pair plan, a declaration or a host read.  prob is the forward's saved output, g_prob the dense gradient
+ * d loss / d link_pred, both [N][N] row-major; g_prob need not be symmetric.  With G = g_prob o prob o (1 - prob),
+ * G^ = G + G^T and per factor k  S = Z_k Z_k^T, E = exp(S / t), Q = H_k H_k^T:
+ *   dH_k = (G^ o E) . H_k          dZ_k = (G^ o Q o E / t) . Z_k          (the diagonal included as written),
+ * on the matrix cores: the forward's Gram products (three bf16 planes per operand, six exact products per term), the
+ * two weight tiles split into three bf16 planes as well and multiplied against the rows of H_k / Z_k the same way.
+ * Every tile is formed: a zero of G^ against an overflowed E = inf gives NaN, as autograd does.  fp32 tables with
+ * 1 <= d <= 128 (dl_score_allpairs_bwd_dense_supported; d is padded to a multiple of 32 with zero columns), N <= 46340.
+ * Every element of dZ, dH [N][K][d] is written.  No float atomics; the v range is sliced for occupancy as a function
+ * of (N, K, d) only and the slices are summed in order, so results are bitwise reproducible.  N = 0 succeeds.
+ * ws: dl_score_allpairs_bwd_dense_workspace_bytes(N, K, d) bytes (0 for unsupported shapes): G^, the planes of Z, H and
+ * of their transposes, and the slices' partial sums; a missing or short workspace fails with DL_E_WORKSPACE. */
+int dl_score_allpairs_bwd_dense_supported(int K, int d);              /* fp32 tables, 1 <= d <= 128 */
+size_t dl_score_allpairs_bwd_dense_workspace_bytes(int N, int K, int d);
+int dl_score_allpairs_bwd_dense(const float* Z, const float* H, int N, int K, int d, float t,
+                                const float* prob, const float* g_prob,   /* dense [N][N], row-major */
+                                float* dZ, float* dH,                     /* [N][K][d], every element written */
+                                void* ws, size_t ws_bytes, void* stream);
+
 /* Ranking of ALL candidate links of query nodes (an extension; the reference has no counterpart): the logit of the dense
  * scorer, s(u,v) = sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), for every
  * (query, candidate) pair on the matrix cores (the dense scorer's three-plane products, the query as the A operand;
