@@ -28,7 +28,8 @@ class DlGraph(C.Structure):
 
 
 class DlPairIncidence(C.Structure):
-    _fields_ = [("csr", DlCsrPlan), ("inc_pair", C.c_void_p), ("n_pairs", C.c_int32), ("entry_yw", C.c_void_p)]
+    _fields_ = [("csr", DlCsrPlan), ("inc_pair", C.c_void_p), ("n_pairs", C.c_int32), ("entry_yw", C.c_void_p),
+                ("inc_pair2", C.c_void_p), ("n_second", C.c_int32)]
 
 
 class DlHostCsr(C.Structure):

@@ -263,7 +263,8 @@ int dl_score_pairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_dty
     DL_REQUIRE(Z && H && pu && pv && prob, "NULL argument");
     if (by_u) {
         if (int rc = check_plan(&by_u->csr, "by_u")) return rc;
-        DL_REQUIRE(by_u->csr.n_entries == n_pairs && by_u->n_pairs == n_pairs && by_u->inc_pair,
+        const int n_second = by_u->inc_pair2 ? by_u->n_second : 0;      // mirrored pairs folded into one entry
+        DL_REQUIRE(n_second >= 0 && by_u->csr.n_entries + n_second == n_pairs && by_u->n_pairs == n_pairs && by_u->inc_pair,
                    "by_u must list each of the %d pairs exactly once", n_pairs);
         DL_REQUIRE(by_u->csr.n_total == N, "by_u.n_total=%d != N=%d", by_u->csr.n_total, N);
         if (use_fast(&by_u->csr, K, d, dtype))

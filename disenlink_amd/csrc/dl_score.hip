@@ -13,6 +13,7 @@ template <int K, int D, typename T, bool COEF>
 // 170 on squirrel; whether the u rows sit in registers or are re-read from LDS every iteration makes no difference:
 // the kernel is bound by the vector-L1 / L2 pipeline, 4.3 GB through 256 x 64 B/clk.)
 __global__ __launch_bounds__(BLOCK, K <= 8 ? 4 : 1) void score_fwd_seg_kernel(dl_csr_plan g, const int32_t* __restrict__ pair_id,
+                                                              const int32_t* __restrict__ pair_id2,
                                                               const T* __restrict__ Z, const T* __restrict__ H,
                                                               float t, float* __restrict__ prob,
                                                               float* __restrict__ coef_e,
@@ -32,16 +33,18 @@ __global__ __launch_bounds__(BLOCK, K <= 8 ? 4 : 1) void score_fwd_seg_kernel(dl
     if (!active) return;
     const int c = lane % G, grp = lane / G;
     const int kbb = FLB::factor_base(c);
-    int my_col = si.grow, my_pair = 0;
+    int my_col = si.grow, my_pair = 0, my_pair2 = -1;                // pair_id2: the mirrored pair an entry also scores (-1 = none)
     if (si.beg + lane < si.end) {
         my_col = g.col[si.beg + lane];
         my_pair = pair_id[si.beg + lane];
+        if (pair_id2 != nullptr) my_pair2 = pair_id2[si.beg + lane];
     }
     for (int base = si.beg; base < si.end; base += EPW) {
         const int it = base + grp;
         const bool live = it < si.end;
         const size_t v = (size_t)entry_scalar<EPW>(my_col, base - si.beg, grp);
         const int q = entry_scalar<EPW>(my_pair, base - si.beg, grp);
+        const int q2 = entry_scalar<EPW>(my_pair2, base - si.beg, grp);
         // factors are processed in blocks of KB <= 8: at most 2*KB row chunks live at a time, whatever K is
         float term = 0.0f;
 #pragma unroll
@@ -66,12 +69,20 @@ __global__ __launch_bounds__(BLOCK, K <= 8 ? 4 : 1) void score_fwd_seg_kernel(dl
                     if (COEF && live) {                         // per-factor logit terms for the backward
                         coef_e[(size_t)q * K + k] = ek;
                         coef_q[(size_t)q * K + k] = qe;
+                        if (q2 >= 0) {
+                            coef_e[(size_t)q2 * K + k] = ek;
+                            coef_q[(size_t)q2 * K + k] = qe;
+                        }
                     }
                 }
             }
         }
         const float logit = group_allreduce_sum<G>(term);
-        if (live && c == 0) prob[q] = sigmoid_ref(logit);
+        if (live && c == 0) {
+            const float p = sigmoid_ref(logit);
+            prob[q] = p;
+            if (q2 >= 0) prob[q2] = p;
+        }
     }
 }
 
@@ -94,8 +105,14 @@ struct FwdWave {
 
 // (amdgpu_waves_per_eu(4, 5): left to itself hipcc aims at 8 waves per SIMD = 64 registers — exactly the 16 gathered float4 of a
 // step — by requesting only 12 of them up front and the rest behind three more vmcnt(0) round trips per step.)
-template <int K, int D, bool T1, bool COEF>
+// FOLD: the plan folds mirrored pairs (dl_pair_incidence.inc_pair2) — an entry's probability and terms go to a second pair id
+// as well, from the lanes that store the first; same arithmetic, same bits.  The last step of a segment issues no gathers
+// for the entries past its end (a wave-uniform branch per entry; their lanes compute on zeros and store nothing): the
+// padding of squirrel's short segments was 5.9 % of all gathers and, although it hit in the vector L1, 7.7 % of the
+// kernel's time (154.3 -> 142.5 us; folding 151.6; both 139.9 — profiles/r9_fwd_fold_bound.txt).
+template <int K, int D, bool T1, bool COEF, bool FOLD>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WAVE_MAXW))) void score_fwd_wave_kernel(dl_csr_plan g, const int32_t* __restrict__ pair_id,
+                                                                  const int32_t* __restrict__ pair_id2,
                                                                   const float* __restrict__ Z, const float* __restrict__ H, float t,
                                                                   float* __restrict__ prob, float* __restrict__ coef_e,
                                                                   float* __restrict__ coef_q) {
@@ -103,7 +120,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
     constexpr int NJ = FW::NJ, U = FW::U, ROW = K * D;
     static_assert(D == 64 && NJ >= 1 && U * NJ <= 8, "one DPP row of 16 lanes per factor slice; at most 8 exponents per row and step");
     __shared__ __attribute__((aligned(16))) float4 urow[WAVES_PER_BLOCK][2 * ROW / 4];      // [Z row | H row] of the segment's u
-    __shared__ int ent_q[WAVES_PER_BLOCK][DL_WAVE];
+    __shared__ int ent_q[WAVES_PER_BLOCK][(FOLD ? 2 : 1) * DL_WAVE];
     const WaveSeg ws = load_wave_seg(g);
     if (!ws.active) return;                                         // no barrier in this kernel: every region is its wave's own
     const SegInfo si = ws.si;
@@ -115,24 +132,33 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
         mine[j * 64 + lane] = *reinterpret_cast<const float4*>(Z + (size_t)si.grow * ROW + (j * 64 + lane) * 4);
         mine[ROW / 4 + j * 64 + lane] = *reinterpret_cast<const float4*>(H + (size_t)si.grow * ROW + (j * 64 + lane) * 4);
     }
-    int my_col = si.grow, my_q = 0;
+    int my_col = si.grow, my_q = 0, my_q2 = -1;
     if (si.beg + lane < si.end) {
         my_col = g.col[si.beg + lane];
         my_q = pair_id[si.beg + lane];
+        if constexpr (FOLD) my_q2 = pair_id2[si.beg + lane];
     }
     ent_q[wave][lane] = my_q;                                       // written and read by this wave only
-    const int nsteps = (si.end - si.beg + U - 1) / U;               // entries past the end repeat a valid row, nothing is stored for them
-    for (int step = 0; step < nsteps; ++step) {
+    if constexpr (FOLD) ent_q[wave][DL_WAVE + lane] = my_q2;
+    const int len = si.end - si.beg;
+    // one step = U entries; n_live of them are gathered (all U, known at compile time, in every step but a segment's last)
+    auto do_step = [&](const int step, auto tail, const int n_live) {
+        constexpr bool TAIL = decltype(tail)::value;
         float4 zv[U][NJ], hv[U][NJ];
 #pragma unroll
         for (int e = 0; e < U; ++e) {
-            const size_t v = (size_t)(unsigned)__builtin_amdgcn_readlane(my_col, (step * U + e) & 63);
-            const auto* zr = uniform_row<dl_vf4>(Z, v * ROW * sizeof(float));     // row base in SGPRs (dl_fast.h)
-            const auto* hr = uniform_row<dl_vf4>(H, v * ROW * sizeof(float));
+            if (!TAIL || e < n_live) {                              // wave-uniform
+                const size_t v = (size_t)(unsigned)__builtin_amdgcn_readlane(my_col, (step * U + e) & 63);
+                const auto* zr = uniform_row<dl_vf4>(Z, v * ROW * sizeof(float));     // row base in SGPRs (dl_fast.h)
+                const auto* hr = uniform_row<dl_vf4>(H, v * ROW * sizeof(float));
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                zv[e][j] = as_float4(zr[(unsigned)(lane + j * 64)]);
-                hv[e][j] = as_float4(hr[(unsigned)(lane + j * 64)]);
+                for (int j = 0; j < NJ; ++j) {
+                    zv[e][j] = as_float4(zr[(unsigned)(lane + j * 64)]);
+                    hv[e][j] = as_float4(hr[(unsigned)(lane + j * 64)]);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) zv[e][j] = hv[e][j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
         }
         float val[16];                                              // index = table * 8 + chunk * 4 + entry
@@ -157,17 +183,29 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
         const float logit = add_xor<32>(add_xor<16>(term));         // over the 4 DPP rows: all factors
         const float p = sigmoid_ref(logit);
         const int idx = step * U + (i & 3);
-        const bool live = si.beg + idx < si.end;
+        const bool live = idx < len;
         const int qq = ent_q[wave][idx & 63];
-        if (lane >= 8 && lane < 12 && live) prob[qq] = p;
+        int qq2 = -1;
+        if constexpr (FOLD) qq2 = ent_q[wave][DL_WAVE + (idx & 63)];
+        if (lane >= 8 && lane < 12 && live) {
+            prob[qq] = p;
+            if (FOLD && qq2 >= 0) prob[qq2] = p;
+        }
         if constexpr (COEF) {                                       // per-factor terms for the separate backward: e_k, q_k e_k
             const int k = 4 * ((i & 7) >> 2) + r;                   // the factor this lane's sum belongs to (chunk j holds the factors 4 j + r)
             if (live && (NJ == 2 || (i & 7) < 4)) {
                 if (i < 8) coef_e[(size_t)qq * K + k] = ex;
                 else coef_q[(size_t)qq * K + k] = ttv;
+                if (FOLD && qq2 >= 0) {
+                    if (i < 8) coef_e[(size_t)qq2 * K + k] = ex;
+                    else coef_q[(size_t)qq2 * K + k] = ttv;
+                }
             }
         }
-    }
+    };
+    const int nfull = len / U;
+    for (int step = 0; step < nfull; ++step) do_step(step, std::false_type{}, U);
+    if (len % U != 0) do_step(nfull, std::true_type{}, len % U);
 }
 
 // Dense [N][N] scorer (the reference's link_pred, model.py:109-113): no pair list at all.  One wave = one
@@ -304,20 +342,25 @@ struct ScoreOps {
         if constexpr (std::is_same<T, float>::value && FwdWave<K, D>::ok) {
             if (g->seg_len <= 64 && g->seg_len % FwdWave<K, D>::U == 0 && !config().fwd_group_kernel) {
                 auto launch = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, dim3(seg_blocks(g)), dim3(BLOCK), 0, st, *g, by_u->inc_pair, (const float*)Z,
-                                       (const float*)H, t, prob, coef, coef_q);
+                    hipLaunchKernelGGL(kern, dim3(seg_blocks(g)), dim3(BLOCK), 0, st, *g, by_u->inc_pair, by_u->inc_pair2,
+                                       (const float*)Z, (const float*)H, t, prob, coef, coef_q);
                 };
-                if (coef) { if (t == 1.0f) launch(score_fwd_wave_kernel<K, D, true, true>); else launch(score_fwd_wave_kernel<K, D, false, true>); }
-                else { if (t == 1.0f) launch(score_fwd_wave_kernel<K, D, true, false>); else launch(score_fwd_wave_kernel<K, D, false, false>); }
+                auto pick_fold = [&](auto t1, auto cf) {
+                    constexpr bool T1 = decltype(t1)::value, CF = decltype(cf)::value;
+                    if (by_u->inc_pair2) launch(score_fwd_wave_kernel<K, D, T1, CF, true>);
+                    else launch(score_fwd_wave_kernel<K, D, T1, CF, false>);
+                };
+                if (coef) { if (t == 1.0f) pick_fold(std::true_type{}, std::true_type{}); else pick_fold(std::false_type{}, std::true_type{}); }
+                else { if (t == 1.0f) pick_fold(std::true_type{}, std::false_type{}); else pick_fold(std::false_type{}, std::false_type{}); }
                 return check_launch("score_pairs_fwd(fast, wave per entry)");
             }
         }
         if (coef)
             hipLaunchKernelGGL((score_fwd_seg_kernel<K, D, T, true>), dim3(seg_blocks(g)), dim3(BLOCK), 0, st, *g,
-                               by_u->inc_pair, (const T*)Z, (const T*)H, t, prob, coef, coef_q);
+                               by_u->inc_pair, by_u->inc_pair2, (const T*)Z, (const T*)H, t, prob, coef, coef_q);
         else
             hipLaunchKernelGGL((score_fwd_seg_kernel<K, D, T, false>), dim3(seg_blocks(g)), dim3(BLOCK), 0, st, *g,
-                               by_u->inc_pair, (const T*)Z, (const T*)H, t, prob, coef, coef_q);
+                               by_u->inc_pair, by_u->inc_pair2, (const T*)Z, (const T*)H, t, prob, coef, coef_q);
         return check_launch("score_pairs_fwd(fast)");
     }
 

@@ -479,12 +479,47 @@ class Graph:
         return C.byref(self._struct.csr)
 
 
+def mirror_partners(pu: torch.Tensor, pv: torch.Tensor, n_nodes: int) -> torch.Tensor:
+    """-> second int64[P]: ``second[q] = q'`` where pair q = (u, v), u < v, is matched with a listed reverse q' = (v, u),
+    else -1.  The matching is one to one: the j-th copy of an ordered pair is matched with the j-th copy of its reverse
+    (in list order), surplus copies on either side stay unmatched, and so do self pairs.  The matched entry stays in the
+    row of min(u, v): which of the two segments would end up with the shorter tail depends on the slicing that follows,
+    and the tail steps it could save are the ones the scorer no longer gathers for anyway."""
+    P, dev = pu.numel(), pu.device
+    second = torch.full((P,), -1, dtype=torch.int64, device=dev)
+    if P == 0:
+        return second
+    lo_, hi_ = torch.minimum(pu, pv), torch.maximum(pu, pv)
+    # occurrence number of every pair among the copies of the same ORDERED pair, in list order
+    okey = pu * n_nodes + pv
+    order = torch.argsort(okey, stable=True)
+    sk = okey[order]
+    first = torch.ones(P, dtype=torch.bool, device=dev)
+    first[1:] = sk[1:] != sk[:-1]
+    pos = torch.arange(P, device=dev)
+    occ = torch.empty(P, dtype=torch.int64, device=dev)
+    occ[order] = pos - torch.cummax(torch.where(first, pos, torch.zeros_like(pos)), 0).values
+    # lexicographic order by (unordered pair, occurrence, direction): partners become neighbours, u < v first
+    perm = torch.argsort((pu > pv).to(torch.int64), stable=True)
+    perm = perm[torch.argsort(occ[perm], stable=True)]
+    perm = perm[torch.argsort((lo_ * n_nodes + hi_)[perm], stable=True)]
+    a, b = perm[:-1], perm[1:]
+    match = (lo_[a] == lo_[b]) & (hi_[a] == hi_[b]) & (occ[a] == occ[b]) & (pu[a] < pv[a]) & (pu[b] > pv[b])
+    second[a[match]] = b[match]
+    return second
+
+
 @dataclass
 class PairList:
     """Scored pairs ``(pu[q], pv[q])`` with the two CSR views the kernels walk:
     ``by_u`` — every pair once, in the row of its first endpoint (forward scorer), and
     ``inc``  — every pair twice, once per endpoint (backward; rows = nodes ``[row_offset, +n_rows)``).
-    Both are XCD-sliced by the second endpoint by default."""
+    Both are XCD-sliced by the second endpoint by default.
+
+    ``fwd`` is the plan the forward scorer walks: ``by_u`` itself, or (``fold_mirrors``, the default, where the list holds
+    mirrors) a by-u plan in which a listed ``(u, v)`` whose reverse ``(v, u)`` is listed too occupies ONE entry that carries
+    both pair ids (``fwd_pair`` and ``fwd_pair2``, -1 = none) — the score is symmetric, the second gather of the two rows
+    is work the result does not need."""
     n_nodes: int
     pu: torch.Tensor
     pv: torch.Tensor
@@ -492,6 +527,9 @@ class PairList:
     by_u_pair: torch.Tensor
     inc: CsrPlan
     inc_pair: torch.Tensor
+    fwd: CsrPlan | None = None                       # None = by_u (nothing folded)
+    fwd_pair: torch.Tensor | None = None
+    fwd_pair2: torch.Tensor | None = None
     _struct: _lib.DlPairIncidence | None = field(default=None, repr=False)
     _struct_u: _lib.DlPairIncidence | None = field(default=None, repr=False)
     _yw: torch.Tensor | None = field(default=None, repr=False)      # per-entry (label, signed weight): bind_labels
@@ -546,12 +584,14 @@ class PairList:
     def build(pu: torch.Tensor, pv: torch.Tensor, n_nodes: int, seg_len: int = DEFAULT_INC_SEG_LEN,
               run_len: int = DEFAULT_RUN_LEN, row_range: tuple[int, int] | None = None,
               n_slices: int | None = None, by_u_range: tuple[int, int] | None = None,
-              build_by_u: bool = True, row_bytes: int = 2048, inc_slices: int | None = None) -> "PairList":
+              build_by_u: bool = True, row_bytes: int = 2048, inc_slices: int | None = None,
+              fold_mirrors: bool = True) -> "PairList":
         """``row_range`` restricts the incidence rows to one shard's nodes (the pair ids in ``inc_pair``
         then index prob / g_prob arrays covering the whole pair list); ``by_u_range`` restricts the rows
         of the forward plan (every pu must lie inside it).  ``n_slices`` / ``inc_slices``: column slices of the forward
         plan / of the incidence plan (defaults: auto_slices / auto_inc_slices — the incidence plan pays a partial slot
-        per (row, slice) group, the forward plan sums nothing across segments)."""
+        per (row, slice) group, the forward plan sums nothing across segments).  ``fold_mirrors=False`` keeps the forward
+        scorer on ``by_u`` (one entry per listed pair), which is built the same either way."""
         pu = pu.reshape(-1).to(torch.int64)
         pv = pv.reshape(-1).to(torch.int64)
         if pu.numel() != pv.numel():
@@ -569,19 +609,20 @@ class PairList:
         dev = pu.device
         ids = torch.arange(P, device=dev)
 
-        def csr(node, other, pair, lo, hi, seg, unit_segs=UNIT_SEGS, slices=None):
+        def csr(node, other, pair, lo, hi, seg, unit_segs=UNIT_SEGS, slices=None, pair2=None):
             slices = n_slices if slices is None else slices
             # slice boundaries from ALL entries of the list (before the row range cuts it): the same for every shard
             bnd = slice_bounds(other, slices) if slices > 1 and other.numel() else None
             keep = (node >= lo) & (node < hi)
             node, other, pair = node[keep], other[keep], pair[keep]
+            pair2 = None if pair2 is None else pair2[keep]
             order = torch.argsort((node - lo) * n_nodes + other, stable=True)   # fixed order -> reproducible sums
             rowptr = torch.zeros(hi - lo + 1, dtype=torch.int64, device=dev)
             if node.numel():
                 rowptr[1:] = torch.cumsum(torch.bincount(node - lo, minlength=hi - lo), dim=0)
             plan = CsrPlan.build(rowptr, other[order], n_nodes, row_offset=lo, seg_len=seg, n_slices=slices,
                                  unit_segs=unit_segs, by_length=length_order(n_nodes, row_bytes), bounds=bnd)
-            return plan, _i32(pair[order])
+            return (plan, _i32(pair[order])) if pair2 is None else (plan, _i32(pair[order]), _i32(pair2[order]))
 
         ulo, uhi = (0, n_nodes) if by_u_range is None else by_u_range
         if P and build_by_u and (int(pu.min()) < ulo or int(pu.max()) >= uhi):
@@ -592,7 +633,15 @@ class PairList:
             by_u, by_u_pair = csr(pu[:0], pv[:0], ids[:0], 0, 0, run_len, unit_segs=1)
         lo, hi = (0, n_nodes) if row_range is None else row_range
         inc, inc_pair = csr(torch.cat([pu, pv]), torch.cat([pv, pu]), ids.repeat(2), lo, hi, seg_len, slices=inc_slices)
-        return PairList(n_nodes, _i32(pu), _i32(pv), by_u, by_u_pair, inc, inc_pair)
+        fwd = fwd_pair = fwd_pair2 = None
+        if build_by_u and fold_mirrors:
+            second = mirror_partners(pu, pv, n_nodes)
+            if bool((second >= 0).any()):
+                kept = torch.ones(P, dtype=torch.bool, device=dev)
+                kept[second[second >= 0]] = False                  # the partner is scored by the entry that names it
+                fwd, fwd_pair, fwd_pair2 = csr(pu[kept], pv[kept], ids[kept], ulo, uhi, run_len, unit_segs=1,
+                                               pair2=second[kept])
+        return PairList(n_nodes, _i32(pu), _i32(pv), by_u, by_u_pair, inc, inc_pair, fwd, fwd_pair, fwd_pair2)
 
     def c_struct(self, n_pairs_total: int | None = None):
         if self._struct is None:
@@ -601,8 +650,13 @@ class PairList:
         return C.byref(self._struct)
 
     def c_struct_by_u(self):
+        """The forward scorer's plan: ``fwd`` (mirrors folded) where there is one, else ``by_u``."""
         if self._struct_u is None:
-            self._struct_u = _lib.DlPairIncidence(self.by_u.c_value(), self.by_u_pair.data_ptr(), self.n_pairs)
+            if self.fwd is None:
+                self._struct_u = _lib.DlPairIncidence(self.by_u.c_value(), self.by_u_pair.data_ptr(), self.n_pairs)
+            else:
+                self._struct_u = _lib.DlPairIncidence(self.fwd.c_value(), self.fwd_pair.data_ptr(), self.n_pairs, None,
+                                                      self.fwd_pair2.data_ptr(), self.n_pairs - self.fwd.n_entries)
         return C.byref(self._struct_u)
 
     def c_plan(self):

@@ -127,6 +127,13 @@ typedef struct dl_pair_incidence {
      * Whoever sets it keeps it consistent with the y / w passed alongside (disenlink_amd/graph.py caches it per label /
      * weight tensor). */
     const float* entry_yw;
+    /* Optional (NULL = not given), read by dl_score_pairs_fwd only: a forward plan with mirrored pairs folded.  The
+     * score is symmetric in its endpoints, so where the list holds both (u,v) and (v,u) one entry can stand for the
+     * two: inc_pair2[e] is the id of the second pair entry e scores (-1 = none), its probability and per-factor terms
+     * are written next to those of inc_pair[e].  n_second counts the entries with inc_pair2[e] >= 0: such a plan lists
+     * every pair exactly once as a first or a second id, csr.n_entries + n_second == n_pairs. */
+    const int32_t* inc_pair2;   /* [csr.n_entries] */
+    int32_t n_second;
 } dl_pair_incidence;
 
 /* ---- host-side graph preparation (no GPU; the only entry points that allocate: malloc'd outputs are
@@ -256,7 +263,8 @@ int dl_aggregate_fwd(const dl_graph* g, const void* Z, int K, int d, dl_dtype dt
 /* Pair-list link scorer: replaces model.py:109-113 evaluated at the listed (u,v) only.
  *   prob[q] = sigmoid( sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t) )    (raw exp, not softmax)
  * by_u (optional, may be NULL): the same pairs as a CSR by first endpoint (each pair once, inc_pair =
- * position in pu/pv/prob); lets a wavefront keep the u rows in LDS for a whole segment and, when
+ * position in pu/pv/prob — or, with inc_pair2, a listed (u,v) and its listed reverse (v,u) as ONE entry
+ * that names both positions); lets a wavefront keep the u rows in LDS for a whole segment and, when
  * sliced, keeps the gathered v rows inside one XCD's L2.
  * coef (optional, may be NULL; training only): [2][n_pairs][K] — coef[0][q][k] = e_k = exp(z_k[u].z_k[v]/t)
  * and coef[1][q][k] = (h_k[u].h_k[v]) * e_k, the per-factor terms of the logit.  Handing them to
