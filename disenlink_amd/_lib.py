@@ -63,6 +63,8 @@ EXPORTS = {
     "dl_project_supported": (_i, [_i]),
     "dl_project_fwd_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "dl_project_hidden_floats": (_z, [_i, _i, _i]),
+    "dl_project_fwd_form": (_i, [_i, _i, _i, _i, _i, _i, _z, _i, C.POINTER(C.c_int)]),
+    "dl_project_bwd_form": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
     "dl_project_fwd": (_i, [_P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _z, _P]),
     "dl_project_xplanes_bytes": (_z, [_i, _i]),
     "dl_project_xplanes_build": (_i, [_P, _i, _i, _P, _z, _P]),
@@ -147,6 +149,25 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().dl_last_error().decode(errors="replace")
         raise DisenlinkHipError(f"{what} failed (code {rc}): {msg}")
+
+
+PROJECT_FWD_FORM = ("split", "vec", "G", "chunks_per_group", "rows_per_launch", "launches", "xplanes")
+PROJECT_BWD_FORM = ("planes", "vecA", "vecB", "recompute", "sA", "tiles_per_range", "sB", "chunks_per_range", "sC", "direct",
+                    "blocked", "block_rows", "blocks", "xplanes")
+
+
+def project_fwd_form(N: int, F: int, K: int, nhid: int, d: int, two_layer: bool, ws_bytes: int, have_xplanes: bool = False) -> dict:
+    """Which kernel instantiation and launch mode dl_project_fwd takes for this problem (dl_project_fwd_form)."""
+    out = (C.c_int * len(PROJECT_FWD_FORM))()
+    check(load().dl_project_fwd_form(N, F, K, nhid, d, int(two_layer), ws_bytes, int(have_xplanes), out), "dl_project_fwd_form")
+    return dict(zip(PROJECT_FWD_FORM, out))
+
+
+def project_bwd_form(N: int, F: int, K: int, nhid: int, d: int, two_layer: bool, have_hid: bool, have_xplanes: bool = False) -> dict:
+    """Which kernels the first node block of dl_project_bwd runs for this problem (dl_project_bwd_form)."""
+    out = (C.c_int * len(PROJECT_BWD_FORM))()
+    check(load().dl_project_bwd_form(N, F, K, nhid, d, int(two_layer), int(have_hid), int(have_xplanes), out), "dl_project_bwd_form")
+    return dict(zip(PROJECT_BWD_FORM, out))
 
 
 def config_reload() -> None:

@@ -127,6 +127,18 @@ size_t dl_project_fwd_workspace_bytes(int N, int F, int K, int nhid, int d, int 
     return project_fwd_workspace_bytes(N, F, K, nhid, d, two_layer != 0);
 }
 
+int dl_project_fwd_form(int N, int F, int K, int nhid, int d, int two_layer, size_t ws_bytes, int have_xplanes, int* out) {
+    DL_REQUIRE(out != nullptr && project_supported(d) && N >= 1 && F >= 1 && K >= 1 && nhid >= 1, "bad argument");
+    project_fwd_form(N, F, K, two_layer ? nhid : 1, d, two_layer != 0, ws_bytes, have_xplanes != 0, out);
+    return DL_OK;
+}
+
+int dl_project_bwd_form(int N, int F, int K, int nhid, int d, int two_layer, int have_hid, int have_xplanes, int* out) {
+    DL_REQUIRE(out != nullptr && project_supported(d) && N >= 1 && F >= 1 && K >= 1 && nhid >= 1, "bad argument");
+    project_bwd_form(N, F, K, two_layer ? nhid : 1, d, two_layer != 0, have_hid != 0, have_xplanes != 0, out);
+    return DL_OK;
+}
+
 size_t dl_project_hidden_floats(int N, int K, int nhid) {
     if (N <= 0 || K < 1 || nhid < 1) return 0;
     return (size_t)K * nhid * (size_t)((N + 3) & ~3);

@@ -101,6 +101,9 @@ const void* project_xplanes_xT(const void* xplanes, int N, int F);
 int project_xplanes_build(const float* x, int N, int F, void* xplanes, hipStream_t st);
 // its backward (dl_project_bwd.hip): weight / bias gradients, W2 == nullptr for the single layer
 size_t project_bwd_workspace_bytes(int N, int F, int K, int nhid, int d, bool two_layer);
+// the dispatch decisions of project_fwd / project_bwd for a problem (host only; include/disenlink_hip.h lists the entries)
+void project_fwd_form(int N, int F, int K, int nhid, int d, bool two_layer, size_t ws_bytes, bool have_xplanes, int* out);
+void project_bwd_form(int N, int F, int K, int nhid, int d, bool two_layer, bool have_hid, bool have_xplanes, int* out);
 int project_bwd(const float* x, int N, int F, int K, int nhid, int d, const float* W1, const float* b1,
                 const float* W2, const float* dZ, const float* hid, float* dW1, float* db1, float* dW2, float* db2,
                 void* ws, hipStream_t st, const void* xplanes = nullptr);

@@ -609,6 +609,38 @@ size_t project_fwd_workspace_bytes(int N, int F, int K, int nhid, int d, bool tw
     return fwd_layout(N, F, K, nhid, d).bytes;
 }
 
+// What the two-layer forward does with a workspace of ws_bytes: which project2_fwd_kernel<D, VEC, SPLIT> runs, over how
+// many hidden-chunk groups, in how many launches of how many rows, and whether persistent x planes serve it.  project_fwd
+// dispatches on exactly this.  A layout of 0 bytes (fp32 MFMA, one group) needs no workspace, so it fits with or without one:
+// the form then does not depend on whether the caller's empty workspace has an address.
+struct FwdForm { bool fits, split, vec, xplanes; int G, cpg, R, launches; };
+static FwdForm fwd_form(const FwdLayout& L, int N, int F, int nhid, bool have_ws, size_t ws_bytes, bool have_xplanes) {
+    FwdForm f{};
+    f.fits = (have_ws || L.bytes == 0) && ws_bytes >= L.bytes;
+    f.split = split_products() && f.fits;                   // no workspace: fp32 MFMA straight from x and W1
+    f.vec = (f.split || F % 4 == 0) && (nhid % 4 == 0);     // quads never straddle a row end
+    f.G = f.fits ? L.G : 1;                                 // no workspace: one group
+    const int nhc = (nhid + project::TH - 1) / project::TH;
+    f.cpg = (nhc + f.G - 1) / f.G;
+    f.R = f.fits ? L.R : N;                                 // rows per launch (G == 1 whenever R < N)
+    f.launches = f.R > 0 ? (N + f.R - 1) / f.R : 0;
+    f.xplanes = f.split && f.R >= N && have_xplanes;        // one node block on planes: x was split once for the run
+    return f;
+}
+
+// ws_bytes = 0 stands for "no workspace" (ws == nullptr in project_fwd).
+void project_fwd_form(int N, int F, int K, int nhid, int d, bool two_layer, size_t ws_bytes, bool have_xplanes, int* out) {
+    if (!two_layer) {                                       // project1_fwd_kernel<d>: one launch, no workspace, no planes
+        const int one[7] = {0, 0, 1, 0, N, 1, 0};
+        std::copy(one, one + 7, out);
+        return;
+    }
+    const FwdLayout L = fwd_layout(N, F, K, nhid, d);
+    const FwdForm f = fwd_form(L, N, F, nhid, ws_bytes > 0, ws_bytes, have_xplanes);
+    const int two[7] = {f.split, f.vec, f.G, f.cpg, f.R, f.launches, f.xplanes};
+    std::copy(two, two + 7, out);
+}
+
 template <int D, bool VEC, bool SPLIT>
 static void launch2_t(int N, int K, int G, int cpg, hipStream_t st, const float* x, int F, int nhid, const float* W1,
                       const float* b1, const float* W2, const float* b2, float* out, float* hid_out, int ldh,
@@ -659,19 +691,18 @@ int project_fwd(const float* x, int N, int F, int K, int nhid, int d, const floa
         return check_launch("project_fwd");
     }
     const FwdLayout L = fwd_layout(N, F, K, nhid, d);
-    const bool fits = ws != nullptr && ws_bytes >= L.bytes;
-    const bool split = split_products() && fits;            // no workspace: fp32 MFMA straight from x and W1
-    const bool vec = (split || F % 4 == 0) && (nhid % 4 == 0);      // quads never straddle a row end
-    const int G = fits ? L.G : 1;                           // no workspace: one group
+    const FwdForm form = fwd_form(L, N, F, nhid, ws != nullptr, ws_bytes, xplanes != nullptr);
+    const bool split = form.split, vec = form.vec;
+    const int G = form.G;
     FwdPlanes P{};
     if (split) {
         char* base = static_cast<char*>(ws);
         __bf16* xP = reinterpret_cast<__bf16*>(base + L.off_xp);
         __bf16* wP = reinterpret_cast<__bf16*>(base + L.off_wp);
         __bf16* w2P = reinterpret_cast<__bf16*>(base + L.off_w2p);
-        if (L.R >= N) {                                     // one node block: all three operand splits in one launch
-            if (xplanes) xP = const_cast<__bf16*>(static_cast<const __bf16*>(xplanes));     // x was split once for the run
-            split_fwd_operands(xplanes ? nullptr : x, N, F, xP, W1, K, nhid, wP, W2, d, w2P, L.nhid_p, st);
+        if (form.R >= N) {                                  // one node block: all three operand splits in one launch
+            if (form.xplanes) xP = const_cast<__bf16*>(static_cast<const __bf16*>(xplanes));     // x was split once for the run
+            split_fwd_operands(form.xplanes ? nullptr : x, N, F, xP, W1, K, nhid, wP, W2, d, w2P, L.nhid_p, st);
         } else {
             split_rows(W1, K, nhid, F, F, (size_t)nhid * F, wP, st);
             split_w2(W2, K * d, nhid, w2P, L.nhid_p, st);
@@ -679,17 +710,16 @@ int project_fwd(const float* x, int N, int F, int K, int nhid, int d, const floa
         P = FwdPlanes{xP, wP, plane_array_elems(nhid, F, SPLIT_COLS), plane_chunks<SPLIT_COLS>(F, SPLIT_COLS),
                       w2P, (size_t)K * d * L.nhid_p, L.nhid_p};
     }
-    const int nhc = (nhid + TH - 1) / TH;
-    const int cpg = (nhc + G - 1) / G;
+    const int cpg = form.cpg;
     float* out = G > 1 ? static_cast<float*>(ws) : Z;
     const float* bias2 = G > 1 ? nullptr : b2;
-    const int R = fits ? L.R : N;                           // rows per launch (G == 1 whenever R < N)
+    const int R = form.R;
     for (int row0 = 0; row0 < N; row0 += R) {
         const int rows = std::min(R, N - row0);
         const float* xb = x + (size_t)row0 * F;
         float* ob = out + (size_t)row0 * K * d;
         float* hb = hid_out ? hid_out + row0 : nullptr;
-        if (split && L.R < N) split_rows(xb, 1, rows, F, F, 0, const_cast<__bf16*>(P.x), st);
+        if (split && form.R < N) split_rows(xb, 1, rows, F, F, 0, const_cast<__bf16*>(P.x), st);
 #define DL_P2(DD)                                                                                       \
     if (d == DD) {                                                                                      \
         if (split && vec) launch2_t<DD, true, true>(rows, K, G, cpg, st, xb, F, nhid, W1, b1, W2, bias2, ob, hb, ldh, P);   \

@@ -745,7 +745,36 @@ static BwdLayout bwd_layout(int N, int F, int K, int nhid, int d, bool two_layer
     return L;
 }
 
+// Which kernels one node block of the backward runs, given its layout: project_bwd_block dispatches on exactly this.
+//   vecA: the VEC argument of kernel A (the kept form reads no x / W1 rows: always the aligned instantiation);
+//   vecB: nodes_contract_kernel<VEC> (only without planes);  direct: kernel B writes dW1 itself, no slab sum;
+//   xplanes: the persistent x^T planes serve kernel B (one block on planes; project_bwd asks here too).
+struct BwdForm { bool planes, vecA, vecB, recompute, direct, xplanes; };
+static BwdForm bwd_form(const BwdLayout& L, int F, bool two, bool have_hid, bool blocked, bool have_xplanes = false) {
+    BwdForm f{};
+    f.planes = L.planes;
+    f.recompute = two && !have_hid;
+    f.vecA = F % 4 == 0 || (two && have_hid);                       // kernel A: x and W1 rows
+    f.vecB = F % 4 == 0 && L.Mb % 4 == 0;                           // kernel B: Y rows (stride K*Mb) and x rows
+    f.direct = L.sB == 1 && !blocked;                               // one range, one block: straight into dW1
+    f.xplanes = !blocked && have_xplanes && L.planes;               // L.planes: two layers and three-plane products
+    return f;
+}
+
 }  // namespace project
+
+void project_bwd_form(int N, int F, int K, int nhid, int d, bool two_layer, bool have_hid, bool have_xplanes, int* out) {
+    using namespace project;
+    have_hid = have_hid && two_layer;
+    const int R = bwd_block_rows(N, K, nhid, two_layer);
+    const bool blocked = R < N;
+    const BwdLayout L = bwd_layout(R, F, K, nhid, d, two_layer, blocked, !have_hid);   // the first block (the last may be shorter)
+    const BwdForm f = bwd_form(L, F, two_layer, have_hid, blocked, have_xplanes);
+    const int v[14] = {f.planes, f.vecA, f.vecB, f.recompute, L.sA, L.tiles_per_range, L.sB, L.chunks_per_range, L.sC,
+                       f.direct, blocked, R, R > 0 ? (N + R - 1) / R : 0,
+                       f.xplanes};
+    std::copy(v, v + 14, out);
+}
 
 size_t project_bwd_workspace_bytes(int N, int F, int K, int nhid, int d, bool two_layer) {
     if (N <= 0) return 0;
@@ -809,8 +838,7 @@ static void project_bwd_block(const float* x, int N, int F, int K, int nhid, int
     float* w2p = reinterpret_cast<float*>(base + L.off_w2p);
     float* b1p = reinterpret_cast<float*>(base + L.off_b1p);
     float* b2p = reinterpret_cast<float*>(base + L.off_b2p);
-    const bool vecA = F % 4 == 0;                                   // kernel A: x and W1 rows
-    const bool vecB = F % 4 == 0 && L.Mb % 4 == 0;                  // kernel B: Y rows (stride K*Mb) and x rows
+    const BwdForm form = bwd_form(L, F, two, hidT != nullptr, blocked, xT_planes != nullptr);
 
     // bias of the output layer: column sums of dZ [N][K*d]
     float* dbo = two ? db2 : db1;
@@ -828,11 +856,11 @@ static void project_bwd_block(const float* x, int N, int F, int K, int nhid, int
         const dim3 grid((unsigned)xcd_grid(L.sA, ceil_div(nhid, 64 * bwd_ht(d)) * K));
 #define DL_PA(DD)                                                                                               \
     if (d == DD) {                                                                                              \
-        if (hidT) launchA_p<DD, true, false>(L.planes, grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, L.tiles_per_range, dhid,   \
-                                             w2p, b1p, hidT, ldh, hid_cols, dhp);                                       \
-        else if (vecA) launchA_p<DD, true, true>(L.planes, grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, L.tiles_per_range,    \
-                                                 dhid, w2p, b1p, nullptr, 0, 0, dhp);                                   \
-        else launchA_p<DD, false, true>(L.planes, grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p,  \
+        if (!form.recompute) launchA_p<DD, true, false>(form.planes, grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, L.tiles_per_range,  \
+                                                        dhid, w2p, b1p, hidT, ldh, hid_cols, dhp);                       \
+        else if (form.vecA) launchA_p<DD, true, true>(form.planes, grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, L.tiles_per_range,    \
+                                                      dhid, w2p, b1p, nullptr, 0, 0, dhp);                               \
+        else launchA_p<DD, false, true>(form.planes, grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p,  \
                                         b1p, nullptr, 0, 0, dhp);                                                       \
     }
         DL_PA(32) DL_PA(64) DL_PA(128)
@@ -842,14 +870,14 @@ static void project_bwd_block(const float* x, int N, int F, int K, int nhid, int
         Y = dhid;
         ldY = K * nhid;
     }
-    if (L.planes) {
+    if (form.planes) {
         static unsigned long long lds_done_p = 0;
         const size_t lds = sizeof(__bf16) * 2 * 2 * 3 * PLANE_ROWS * PPITCH;
         ensure_dynamic_lds(reinterpret_cast<const void*>(&nodes_contract_planes_kernel), lds, lds_done_p);
-        if (xT_planes) xTP = const_cast<__bf16*>(static_cast<const __bf16*>(xT_planes));     // split once for the run
+        if (form.xplanes) xTP = const_cast<__bf16*>(static_cast<const __bf16*>(xT_planes));     // split once for the run
         else split_transposed(x, N, F, F, xTP, st);
         const dim3 grid((unsigned)xcd_grid(L.sB * ceil_div(F, CT), ceil_div(L.Mb, CT) * K));
-        const bool direct = L.sB == 1 && !blocked;
+        const bool direct = form.direct;
         float* out = direct ? dW1 : w1p;
         hipLaunchKernelGGL(nodes_contract_planes_kernel, grid, dim3(256), lds, st, dhP, dhp.batch, xTP, L.ncb, L.n_chunks16,
                            L.Mb, F, K, L.chunks_per_range, out);
@@ -860,9 +888,9 @@ static void project_bwd_block(const float* x, int N, int F, int K, int nhid, int
         ensure_dynamic_lds(reinterpret_cast<const void*>(&nodes_contract_kernel<true>), lds, lds_done_v);
         ensure_dynamic_lds(reinterpret_cast<const void*>(&nodes_contract_kernel<false>), lds, lds_done_s);
         const dim3 grid((unsigned)xcd_grid(L.sB * ceil_div(F, CT), ceil_div(L.Mb, CT) * K));
-        const bool direct = L.sB == 1 && !blocked;                  // one range, one block: straight into dW1
+        const bool direct = form.direct;
         float* out = direct ? dW1 : w1p;
-        if (vecB) hipLaunchKernelGGL(nodes_contract_kernel<true>, grid, dim3(256), lds, st, Y, ldY, L.Mb, x, F, N, K,
+        if (form.vecB) hipLaunchKernelGGL(nodes_contract_kernel<true>, grid, dim3(256), lds, st, Y, ldY, L.Mb, x, F, N, K,
                                     L.chunks_per_range, out);
         else hipLaunchKernelGGL(nodes_contract_kernel<false>, grid, dim3(256), lds, st, Y, ldY, L.Mb, x, F, N, K,
                                 L.chunks_per_range, out);
@@ -877,8 +905,8 @@ int project_bwd(const float* x, int N, int F, int K, int nhid, int d, const floa
     const bool two = W2 != nullptr;
     const int R = project::bwd_block_rows(N, K, nhid, two);
     const bool blocked = R < N;
-    if (!blocked && xplanes && two && split_products()) {     // one block: the persistent x^T planes serve it
-        project_bwd_block(x, N, F, K, nhid, d, W1, b1, W2, dZ, hid, (N + 3) & ~3, (N + 3) & ~3, dW1, db1, dW2, db2, ws, false,
+    if (!blocked && xplanes) {                                // one block: the persistent x^T planes serve it where it runs on planes
+        project_bwd_block(x, N, F, K, nhid, d, W1, b1, W2, dZ, two ? hid : nullptr, (N + 3) & ~3, (N + 3) & ~3, dW1, db1, dW2, db2, ws, false,
                           false, st, project_xplanes_xT(xplanes, N, F));
         return check_launch("project_bwd");
     }

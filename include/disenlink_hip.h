@@ -202,7 +202,9 @@ size_t dl_workspace_bytes(const dl_csr_plan* plan, int K, int d);
  * exact k-ordered fmaf chain).
  * ws (optional, dl_project_fwd_workspace_bytes): the plane arrays, and on small graphs the partial sums of the
  * several workgroups per node tile that share the hidden layer (added in a fixed order); without it one workgroup
- * walks the whole hidden layer with fp32 MFMA — same result up to rounding / summation order, slower. */
+ * walks the whole hidden layer with fp32 MFMA — same result up to rounding / summation order, slower.
+ * ws == NULL is equivalent to a workspace of 0 bytes: where the layout needs none (DL_PROJECT_FP32_MFMA=1 with one
+ * hidden-chunk group) both run the same form, node blocks of DL_FWD_BLOCK_ROWS included. */
 int dl_project_supported(int d);
 size_t dl_project_fwd_workspace_bytes(int N, int F, int K, int nhid, int d, int two_layer);
 /* hid_out (optional, two-layer form, dl_project_hidden_floats(N, K, nhid) floats): keep the hidden layer
@@ -244,6 +246,23 @@ int dl_project_bwd(const float* x, int N, int F, int K, int nhid, int d,
                    const float* hid /* hid_out of the forward, or NULL = recompute */,
                    float* dW1, float* db1, float* dW2, float* db2,
                    void* ws, size_t ws_bytes, void* stream);
+
+/* Which form of the projection a problem runs (host only, nothing is launched): the decisions dl_project_fwd /
+ * dl_project_bwd take, computed by the code that takes them, under the current DL_* switches.  For tests that must
+ * know which kernel instantiation and launch mode a shape reaches.
+ *   dl_project_fwd_form   ws_bytes = 0: no workspace.  out[DL_PROJECT_FWD_FORM_LEN] =
+ *       [0] three-plane products (else fp32 MFMA)  [1] VEC  [2] hidden-chunk groups G  [3] chunks per group
+ *       [4] rows per launch  [5] launches  [6] the persistent x planes are used
+ *       (single layer: 0, 0, 1, 0, N, 1, 0)
+ *   dl_project_bwd_form   of the first node block (a last block may be shorter).  out[DL_PROJECT_BWD_FORM_LEN] =
+ *       [0] plane dhid + plane kernel B  [1] VEC of kernel A  [2] VEC of the fp32 kernel B  [3] hidden layer recomputed
+ *       [4] node ranges of kernel A  [5] node tiles per range  [6] node ranges of kernel B  [7] node chunks per range
+ *       [8] ranges of the column sums  [9] kernel B writes dW1 directly  [10] node blocks accumulate  [11] rows per block
+ *       [12] blocks  [13] the persistent x^T planes are used */
+#define DL_PROJECT_FWD_FORM_LEN 7
+#define DL_PROJECT_BWD_FORM_LEN 14
+int dl_project_fwd_form(int N, int F, int K, int nhid, int d, int two_layer, size_t ws_bytes, int have_xplanes, int* out);
+int dl_project_bwd_form(int N, int F, int K, int nhid, int d, int two_layer, int have_hid, int have_xplanes, int* out);
 
 /* Routing: replaces model.py:56-72 restricted to adj==1 entries.
  *   per edge e=(i,j):  sigma_k = z_k[i].z_k[j] / t ; e_k = exp(sigma_k) ; alpha_k = e_k / sum_k e_k
