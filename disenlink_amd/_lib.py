@@ -76,6 +76,9 @@ EXPORTS = {
     "dl_aggregate_fwd": (_i, [_G, _P, _i, _i, _i, _f, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_pairs_fwd": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _i, _I, _P, _P, _P]),
     "dl_score_allpairs_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dl_score_allpairs_fwd_form": (_i, [_i, _i, _i, _i, _z, C.POINTER(C.c_int)]),
+    "dl_score_allpairs_bwd_dense_form": (_i, [_i, _i, _i, C.POINTER(C.c_int)]),
+    "dl_score_topk_form": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
     "dl_score_allpairs_fwd": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _z, _P]),
     "dl_score_allpairs_bwd": (_i, [_P, _P, _i, _i, _i, _i, _f, _I, _P, _P, _i, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_allpairs_bwd_dense_supported": (_i, [_i, _i]),
@@ -168,6 +171,33 @@ def project_bwd_form(N: int, F: int, K: int, nhid: int, d: int, two_layer: bool,
     out = (C.c_int * len(PROJECT_BWD_FORM))()
     check(load().dl_project_bwd_form(N, F, K, nhid, d, int(two_layer), int(have_hid), int(have_xplanes), out), "dl_project_bwd_form")
     return dict(zip(PROJECT_BWD_FORM, out))
+
+
+SCORE_ALLPAIRS_FWD_FORM = ("kernel", "items", "grid", "n_slices", "slice_w", "chunks_per_u")
+SCORE_ALLPAIRS_KERNELS = ("generic", "per shape", "matrix cores, split on stage", "matrix cores, from planes")
+SCORE_ALLPAIRS_BWD_DENSE_FORM = ("Np", "NCB", "nslice", "min_tiles", "max_tiles")
+SCORE_TOPK_FORM = ("nd", "qtiles", "slices", "tiles_per_slice", "last_tiles", "cap")
+
+
+def score_allpairs_fwd_form(N: int, K: int, d: int, dtype: int, ws_bytes: int) -> dict:
+    """Which kernel and launch geometry dl_score_allpairs_fwd takes for this problem (dl_score_allpairs_fwd_form)."""
+    out = (C.c_int * len(SCORE_ALLPAIRS_FWD_FORM))()
+    check(load().dl_score_allpairs_fwd_form(N, K, d, dtype, ws_bytes, out), "dl_score_allpairs_fwd_form")
+    return dict(zip(SCORE_ALLPAIRS_FWD_FORM, out))
+
+
+def score_allpairs_bwd_dense_form(N: int, K: int, d: int) -> dict:
+    """The launch form of dl_score_allpairs_bwd_dense for this problem (dl_score_allpairs_bwd_dense_form)."""
+    out = (C.c_int * len(SCORE_ALLPAIRS_BWD_DENSE_FORM))()
+    check(load().dl_score_allpairs_bwd_dense_form(N, K, d, out), "dl_score_allpairs_bwd_dense_form")
+    return dict(zip(SCORE_ALLPAIRS_BWD_DENSE_FORM, out))
+
+
+def score_topk_form(N: int, K: int, d: int, Q: int, k: int) -> dict:
+    """The ranking scan's plan for this problem under the current DL_RANK_SLICES (dl_score_topk_form)."""
+    out = (C.c_int * len(SCORE_TOPK_FORM))()
+    check(load().dl_score_topk_form(N, K, d, Q, k, out), "dl_score_topk_form")
+    return dict(zip(SCORE_TOPK_FORM, out))
 
 
 def config_reload() -> None:

@@ -88,6 +88,14 @@ static bool use_fast(const dl_csr_plan* c, int K, int d, int dtype) {
     return !g_force_generic && fast_supported(K, d, dtype) && has_seg_plan(c);
 }
 
+// which dense scorer serves (K, d, dtype): the one decision of dl_score_allpairs_fwd and dl_score_allpairs_fwd_form
+enum AllpairsKernel { ALLPAIRS_GENERIC = 0, ALLPAIRS_PER_SHAPE = 1, ALLPAIRS_MFMA = 2 };
+static AllpairsKernel allpairs_kernel(int K, int d, int dtype) {
+    if (!g_force_generic && dtype == DL_F32 && dense_mfma_supported(d)) return ALLPAIRS_MFMA;      // Gram products on the matrix cores
+    if (!g_force_generic && fast_supported(K, d, dtype)) return ALLPAIRS_PER_SHAPE;
+    return ALLPAIRS_GENERIC;
+}
+
 // bf16 tables exist only on the tuned path
 static int check_dtype(const dl_csr_plan* c, int K, int d, int dtype) {
     DL_REQUIRE(dtype == DL_F32 || dtype == DL_BF16, "unknown dtype %d", dtype);
@@ -300,16 +308,36 @@ int dl_score_allpairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     if (N == 0) return DL_OK;
     DL_REQUIRE(Z && H && prob, "NULL argument");
-    if (!g_force_generic && dtype == DL_F32 && dense_mfma_supported(d))      // Gram products on the matrix cores
+    const AllpairsKernel which = allpairs_kernel(K, d, dtype);
+    if (which == ALLPAIRS_MFMA)
         return dense_mfma_score_allpairs_fwd((const float*)Z, (const float*)H, N, K, d, t, prob, ws, ws_bytes,
                                              (hipStream_t)stream);
-    if (!g_force_generic && fast_supported(K, d, dtype))
+    if (which == ALLPAIRS_PER_SHAPE)
         return fast_score_allpairs_fwd(Z, H, N, K, d, dtype, t, prob, (hipStream_t)stream);
     DL_REQUIRE(dtype == DL_F32, "bf16 tables need a tuned kernel for K=%d d=%d", K, d);
     return generic_score_allpairs_fwd((const float*)Z, (const float*)H, N, K, d, t, prob, (hipStream_t)stream);
 }
 
+int dl_score_allpairs_fwd_form(int N, int K, int d, dl_dtype dtype, size_t ws_bytes, int* out) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(out != nullptr && (dtype == DL_F32 || dtype == DL_BF16) && N >= 1 && N <= 46340, "bad argument");
+    for (int i = 0; i < DL_SCORE_ALLPAIRS_FWD_FORM_LEN; ++i) out[i] = 0;
+    const AllpairsKernel which = allpairs_kernel(K, d, dtype);
+    DL_REQUIRE(which != ALLPAIRS_GENERIC || dtype == DL_F32, "bf16 tables need a tuned kernel for K=%d d=%d", K, d);
+    out[0] = (int)which;
+    if (which == ALLPAIRS_MFMA) dense_mfma_form(N, K, d, ws_bytes, out);
+    else if (which == ALLPAIRS_PER_SHAPE) fast_score_allpairs_form(N, K, d, dtype, out);
+    else generic_score_allpairs_form(N, out);
+    return DL_OK;
+}
+
 int dl_score_topk_supported(int K, int d) { return score_rank_supported(K, d) ? 1 : 0; }
+
+int dl_score_topk_form(int N, int K, int d, int n_queries, int k, int* out) {
+    DL_REQUIRE(out != nullptr && N >= 1 && n_queries >= 1 && k >= 0 && k <= 128 && score_rank_supported(K, d), "bad argument");
+    score_topk_form(N, d, n_queries, k, out);
+    return DL_OK;
+}
 
 size_t dl_score_topk_workspace_bytes(int N, int K, int d, int n_queries, int k, int n_targets) {
     if (N <= 0 || n_queries <= 0 || k < 0 || n_targets < 0 || !score_rank_supported(K, d)) return 0;
@@ -482,6 +510,12 @@ int dl_score_allpairs_bwd_dense_supported(int K, int d) {
 size_t dl_score_allpairs_bwd_dense_workspace_bytes(int N, int K, int d) {
     if (N <= 0 || N > 46340 || !dl_score_allpairs_bwd_dense_supported(K, d)) return 0;
     return dense_bwd_workspace_bytes(N, K, d);
+}
+
+int dl_score_allpairs_bwd_dense_form(int N, int K, int d, int* out) {
+    DL_REQUIRE(out != nullptr && N >= 1 && N <= 46340 && dl_score_allpairs_bwd_dense_supported(K, d), "bad argument");
+    dense_bwd_form(N, K, d, out);
+    return DL_OK;
 }
 
 int dl_score_allpairs_bwd_dense(const float* Z, const float* H, int N, int K, int d, float t, const float* prob,

@@ -283,10 +283,18 @@ int generic_score_pairs_fwd(const float* Z, const float* H, int K, int d, float 
     return check_launch("score_pairs_fwd(generic)");
 }
 
+static unsigned allpairs_blocks(long long n) { return (unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK); }
+
+void generic_score_allpairs_form(int N, int* out) {
+    const long long n = (long long)N * N;
+    out[1] = (int)n;                                            // one wave per ordered pair
+    out[2] = (int)allpairs_blocks(n);
+}
+
 int generic_score_allpairs_fwd(const float* Z, const float* H, int N, int K, int d, float t, float* prob,
                                hipStream_t st) {
     const long long n = (long long)N * N;
-    hipLaunchKernelGGL(score_allpairs_fwd_kernel, dim3((unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK)),
+    hipLaunchKernelGGL(score_allpairs_fwd_kernel, dim3(allpairs_blocks(n)),
                        dim3(BLOCK), 0, st, Z, H, N, K, d, t, prob);
     return check_launch("score_allpairs_fwd(generic)");
 }

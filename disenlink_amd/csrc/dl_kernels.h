@@ -50,6 +50,14 @@ int fast_score_allpairs_fwd(const void* Z, const void* H, int N, int K, int d, i
 int generic_score_allpairs_fwd(const float* Z, const float* H, int N, int K, int d, float t, float* prob,
                                hipStream_t st);
 
+// the launch decisions of the three dense scorers, the dense backward and the ranking scan for a problem (host only;
+// include/disenlink_hip.h lists the entries): each fills its part of the form from the code its launch calls
+void generic_score_allpairs_form(int N, int* out);
+void fast_score_allpairs_form(int N, int K, int d, int dtype, int* out);
+void dense_mfma_form(int N, int K, int d, size_t ws_bytes, int* out);
+void dense_bwd_form(int N, int K, int d, int* out);
+void score_topk_form(int N, int d, int Q, int k, int* out);
+
 // dense scorer on the matrix cores (dl_score_dense.hip): fp32 tables, d % 32 == 0
 bool dense_mfma_supported(int d);
 size_t dense_score_workspace_bytes(int N, int K, int d);

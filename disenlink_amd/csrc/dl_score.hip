@@ -332,6 +332,20 @@ __global__ __launch_bounds__(BLOCK) void score_bwd_coef_seg_kernel(dl_csr_plan g
     }
 }
 
+// Launch geometry of score_allpairs_kernel for rows of row_bytes bytes: slice the columns 8 ways only while a slice of
+// Z+H can live in an XCD's L2 (like graph.auto_slices).  Shared by the launch and by fast_score_allpairs_form.
+struct AllpairsGeo { int n_slices, slice_w, chunks_per_u; long long items; unsigned blocks; };
+static AllpairsGeo allpairs_geo(int N, size_t row_bytes) {
+    AllpairsGeo g;
+    const double table = 2.0 * N * (double)row_bytes;
+    g.n_slices = table <= 8.0 * 8.0 * (4 << 20) && N >= 64 ? 8 : 1;
+    g.slice_w = (N + g.n_slices - 1) / g.n_slices;
+    g.chunks_per_u = (g.slice_w + 255) / 256;
+    g.items = (long long)N * g.chunks_per_u;
+    g.blocks = (unsigned)(g.n_slices * ((g.items + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK));
+    return g;
+}
+
 template <int K, int D, typename T>
 struct ScoreOps {
     static constexpr int ROW = K * D;
@@ -365,15 +379,9 @@ struct ScoreOps {
     }
 
     static int score_allpairs(const void* Z, const void* H, int N, float t, float* prob, hipStream_t st) {
-        // slice the columns 8 ways only while a slice of Z+H can live in an XCD's L2 (like graph.auto_slices)
-        const double table = 2.0 * N * ROW * sizeof(T);
-        const int n_slices = table <= 8.0 * 8.0 * (4 << 20) && N >= 64 ? 8 : 1;
-        const int slice_w = (N + n_slices - 1) / n_slices;
-        const int chunks_per_u = (slice_w + 255) / 256;
-        const long long items = (long long)N * chunks_per_u;
-        const unsigned blocks = (unsigned)(n_slices * ((items + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK));
-        hipLaunchKernelGGL((score_allpairs_kernel<K, D, T>), dim3(blocks), dim3(BLOCK), 0, st, (const T*)Z, (const T*)H, N,
-                           t, n_slices, slice_w, chunks_per_u, prob);
+        const AllpairsGeo g = allpairs_geo(N, ROW * sizeof(T));
+        hipLaunchKernelGGL((score_allpairs_kernel<K, D, T>), dim3(g.blocks), dim3(BLOCK), 0, st, (const T*)Z, (const T*)H, N,
+                           t, g.n_slices, g.slice_w, g.chunks_per_u, prob);
         return check_launch("score_allpairs_fwd(fast)");
     }
 
@@ -430,6 +438,15 @@ int fast_score_allpairs_fwd(const void* Z, const void* H, int N, int K, int d, i
     DL_DISPATCH(X)
 #undef X_F32
 #undef X_BF16
+}
+
+void fast_score_allpairs_form(int N, int K, int d, int dtype, int* out) {
+    const fast::AllpairsGeo g = fast::allpairs_geo(N, (size_t)K * d * (dtype == DL_BF16 ? sizeof(fast::bf16_t) : sizeof(float)));
+    out[1] = (int)g.items;
+    out[2] = (int)g.blocks;
+    out[3] = g.n_slices;
+    out[4] = g.slice_w;
+    out[5] = g.chunks_per_u;
 }
 
 }  // namespace dl

@@ -178,16 +178,35 @@ size_t dense_score_workspace_bytes(int N, int K, int d) {
     return 2 * sizeof(__bf16) * (size_t)K * project::plane_array_elems(N, d, project::SPLIT_COLS);
 }
 
+// Work items (tile pairs u tile <= v tile), the grid that deals them to the XCDs in rounds of 256, and whether a
+// workspace of ws_bytes holds the planes.  Shared by the launch and by dense_mfma_form.
+namespace dense {
+struct Launch { int items; unsigned grid; bool planes; };
+static Launch launch_of(int N, int K, int d, bool have_ws, size_t ws_bytes) {
+    Launch L;
+    const int nt = (N + TT - 1) / TT;
+    L.items = nt * (nt + 1) / 2;
+    L.grid = (unsigned)((L.items + 255) / 256 * 256);
+    L.planes = have_ws && ws_bytes >= dense_score_workspace_bytes(N, K, d);
+    return L;
+}
+}  // namespace dense
+
+void dense_mfma_form(int N, int K, int d, size_t ws_bytes, int* out) {
+    const dense::Launch L = dense::launch_of(N, K, d, ws_bytes > 0, ws_bytes);
+    out[0] = L.planes ? 3 : 2;
+    out[1] = L.items;
+    out[2] = (int)L.grid;
+}
+
 int dense_mfma_score_allpairs_fwd(const float* Z, const float* H, int N, int K, int d, float t, float* prob, void* ws,
                                   size_t ws_bytes, hipStream_t st) {
     using namespace dense;
     static unsigned long long lds_done_p = 0, lds_done_s = 0;
     constexpr size_t lds = (size_t)2 * 2 * 3 * TT * SLD * 2;
-    const int nt = (N + TT - 1) / TT;
-    const int items = nt * (nt + 1) / 2;
-    const dim3 grid((unsigned)((items + 255) / 256 * 256));
-    const size_t need = dense_score_workspace_bytes(N, K, d);
-    if (ws != nullptr && ws_bytes >= need) {                // planes made once per call
+    const Launch L = launch_of(N, K, d, ws != nullptr, ws_bytes);
+    const dim3 grid(L.grid);
+    if (L.planes) {                                         // planes made once per call
         const size_t batch = project::plane_array_elems(N, d, project::SPLIT_COLS);
         __bf16* zp = static_cast<__bf16*>(ws);
         __bf16* hp = zp + (size_t)K * batch;

@@ -304,6 +304,24 @@ bool dense_bwd_supported(int d) { return d >= 1 && d <= 128; }
 
 size_t dense_bwd_workspace_bytes(int N, int K, int d) { return dense_bwd::layout(N, K, d).bytes; }
 
+// out = Np, NCB, nslice (from layout, which the launch calls), and the v tiles of the shortest and of the longest slice:
+// a host restatement of the split the kernel takes in device code (slice s walks the tiles [s nvt / nslice, (s + 1) nvt / nslice))
+void dense_bwd_form(int N, int K, int d, int* out) {
+    const dense_bwd::Layout L = dense_bwd::layout(N, K, d);
+    const int nvt = L.Np / dense_bwd::TT;
+    int lo = nvt, hi = 0;
+    for (int s = 0; s < L.nslice; ++s) {
+        const int n = (int)((long long)(s + 1) * nvt / L.nslice) - (int)((long long)s * nvt / L.nslice);
+        lo = std::min(lo, n);
+        hi = std::max(hi, n);
+    }
+    out[0] = L.Np;
+    out[1] = L.dp / dense_bwd::SDC;
+    out[2] = L.nslice;
+    out[3] = lo;
+    out[4] = hi;
+}
+
 int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d, float t, const float* prob, const float* g_prob,
                              float* dZ, float* dH, void* ws, hipStream_t st) {
     using namespace dense_bwd;

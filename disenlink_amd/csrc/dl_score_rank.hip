@@ -511,6 +511,17 @@ static RankPlan rank_plan(int N, int d, int Q, int k) {
     return p;
 }
 
+// out = nd, qtiles, slices, tiles per slice, tiles of the last slice, cap: rank_plan under the current configuration
+void score_topk_form(int N, int d, int Q, int k, int* out) {
+    const RankPlan p = rank_plan(N, d, Q, k);
+    out[0] = p.nd;
+    out[1] = p.qtiles;
+    out[2] = p.slices;
+    out[3] = p.tps;
+    out[4] = p.nt - (p.slices - 1) * p.tps;
+    out[5] = p.cap;
+}
+
 // Workspace (256-byte aligned blocks): gathered query rows (fp32) | their planes | planes of Z and H | TOPK: lists, counts |
 // RANKS: per-target arrays and the two counter arrays.
 struct RankWs {

@@ -160,7 +160,9 @@ __device__ __forceinline__ void mfma_split6(f32x16& acc, const bf16x8 (&a)[3], c
 // that owns rows 32 wu .. 32 wu + 31 of A and rows 64 wv .. 64 wv + 63 of B passes ub = A image + (32 wu + lane % 32) rows
 // + 8 (lane / 32) and vb likewise (64 wv), and accumulates the two 32 x 32 blocks acc[0] (B rows + 0) and acc[1] (+ 32).
 // Shared by the dense scorer (dl_score_dense.hip) and the ranking scan (dl_score_rank.hip): the same products in the
-// same order, so both form the same bits for the same pair of rows.
+// same order, so both form the same bits for the same ORDERED pair of rows (A row, B row), wherever in a tile the rows sit.
+// Swapping the operands swaps hi*lo with lo*hi in the accumulation order and may move the last bit: the dense scorer forms
+// every entry once, with the smaller node index as the A row, and the scan (query = A) meets its bits for query < candidate.
 __device__ __forceinline__ void gram_block_split6(f32x16 (&acc)[2], const __bf16* ub, const __bf16* vb, int kb) {
     constexpr int T = 128;
     bf16x8 a[3], b0[3], b1[3];

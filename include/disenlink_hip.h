@@ -302,6 +302,14 @@ int dl_score_pairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_dty
  * ws (optional, dl_score_allpairs_workspace_bytes): the bf16 planes of Z and H, split once per call; without it
  * (NULL / too small) every tile pair splits the rows it stages — same result bit for bit, slower. */
 size_t dl_score_allpairs_workspace_bytes(int N, int K, int d, dl_dtype dtype);
+/* Which kernel and launch geometry dl_score_allpairs_fwd takes (host only, nothing is launched; honours
+ * dl_set_force_generic), computed by the code that takes the decision.  ws_bytes = 0: no workspace.
+ * out[DL_SCORE_ALLPAIRS_FWD_FORM_LEN] =
+ *   [0] kernel: 0 generic, 1 per shape, 2 matrix cores splitting what they stage, 3 matrix cores from planes
+ *   [1] work items (generic: ordered pairs; per shape: rows x chunks; matrix cores: tile pairs u tile <= v tile)
+ *   [2] workgroups  [3] column slices  [4] slice width  [5] 256-column chunks per row and slice ([3..5]: per shape only) */
+#define DL_SCORE_ALLPAIRS_FWD_FORM_LEN 6
+int dl_score_allpairs_fwd_form(int N, int K, int d, dl_dtype dtype, size_t ws_bytes, int* out);
 int dl_score_allpairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
                           float* prob, void* ws, size_t ws_bytes, void* stream);
 
@@ -337,6 +345,13 @@ int dl_score_allpairs_bwd(const void* Z, const void* H, int N, int K, int d, dl_
  * ws: dl_score_allpairs_bwd_dense_workspace_bytes(N, K, d) bytes (0 for unsupported shapes): G^, the planes of Z, H and
  * of their transposes, and the slices' partial sums; a missing or short workspace fails with DL_E_WORKSPACE. */
 int dl_score_allpairs_bwd_dense_supported(int K, int d);              /* fp32 tables, 1 <= d <= 128 */
+/* The launch form of dl_score_allpairs_bwd_dense (host only).  out[DL_SCORE_ALLPAIRS_BWD_DENSE_FORM_LEN] =
+ *   [0] Np  [1] 32-column chunks of the padded factor width (the kernel's NCB)  [2] slices of the v range (1: no combine
+ *   launch)  [3] v tiles of the shortest slice  [4] v tiles of the longest slice
+ * [0..2] come from the layout code the launch calls; [3] and [4] restate on the host the split the kernel itself takes
+ * (slice s walks the tiles [s nvt / nslice, (s + 1) nvt / nslice)), which lives in device code. */
+#define DL_SCORE_ALLPAIRS_BWD_DENSE_FORM_LEN 5
+int dl_score_allpairs_bwd_dense_form(int N, int K, int d, int* out);
 size_t dl_score_allpairs_bwd_dense_workspace_bytes(int N, int K, int d);
 int dl_score_allpairs_bwd_dense(const float* Z, const float* H, int N, int K, int d, float t,
                                 const float* prob, const float* g_prob,   /* dense [N][N], row-major */
@@ -357,6 +372,12 @@ int dl_score_allpairs_bwd_dense(const float* Z, const float* H, int N, int K, in
  * for dl_score_ranks: the gathered query rows and their planes, the planes of Z and H, and for top-k n_queries x slices
  * lists of k + 64 8-byte keys.  Results are bitwise reproducible and do not depend on the slicing (DL_RANK_SLICES). */
 int dl_score_topk_supported(int K, int d);
+/* The scan's plan for a problem under the current DL_RANK_SLICES (host only; without the switch the slice count follows
+ * the device's CU count, 256 where no device answers).  out[DL_SCORE_TOPK_FORM_LEN] =
+ *   [0] 32-column chunks of the padded factor width  [1] query tiles  [2] candidate slices  [3] candidate tiles per slice
+ *   [4] tiles of the last slice  [5] keys per (row, slice) list */
+#define DL_SCORE_TOPK_FORM_LEN 6
+int dl_score_topk_form(int N, int K, int d, int n_queries, int k, int* out);
 size_t dl_score_topk_workspace_bytes(int N, int K, int d, int n_queries, int k, int n_targets);
 /* Top-k (1 <= k <= 128) per query row: index int64 [n_queries][k], logit and prob = sigmoid(logit) fp32 [n_queries][k],
  * sorted by the total order; a row with fewer than k candidates is padded at the end with index -1 and NaN.  Duplicate
