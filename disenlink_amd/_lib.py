@@ -43,9 +43,17 @@ class DlHostPlan(C.Structure):
                                                     "multi_row", "multi_slot0", "slot_multi")]
 
 
+class DlSparseFeatures(C.Structure):
+    _fields_ = [("N", C.c_int32), ("F", C.c_int32), ("nnz", C.c_int32),
+                ("rowptr", C.c_void_p), ("col", C.c_void_p), ("val", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
+                ("colptr", C.c_void_p), ("csc_row", C.c_void_p), ("csc_entry", C.c_void_p),
+                ("seg_len", C.c_int32), ("n_seg", C.c_int32), ("colseg", C.c_void_p), ("seg_col", C.c_void_p)]
+
+
 _P = C.c_void_p          # device pointers travel as integers
 _G, _I = C.POINTER(DlGraph), C.POINTER(DlPairIncidence)
 _i, _f, _z = C.c_int, C.c_float, C.c_size_t
+_S = C.POINTER(DlSparseFeatures)
 EXPORTS = {
     # name: (restype, argtypes) -- one entry per symbol declared in include/disenlink_hip.h
     "dl_host_csr_from_edges": (_i, [_P, _P, C.c_int64, C.c_int32, _i, C.POINTER(DlHostCsr)]),
@@ -72,6 +80,12 @@ EXPORTS = {
     "dl_project_bwd_xp": (_i, [_P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _z, _P, _P]),
     "dl_project_bwd_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "dl_project_bwd": (_i, [_P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_sparse_seg_len": (_i, []),
+    "dl_project_sparse_fwd_workspace_bytes": (_z, [_S, _i, _i, _i, _i]),
+    "dl_project_sparse_bwd_workspace_bytes": (_z, [_S, _i, _i, _i, _i]),
+    "dl_project_sparse_form": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "dl_project_sparse_fwd": (_i, [_S, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_project_sparse_bwd": (_i, [_S, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _z, _P]),
     "dl_route_fwd": (_i, [_G, _P, _i, _i, _i, _f, _P, _P, _P, _P, _z, _P]),
     "dl_aggregate_fwd": (_i, [_G, _P, _i, _i, _i, _f, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_pairs_fwd": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _i, _I, _P, _P, _P]),
@@ -171,6 +185,17 @@ def project_bwd_form(N: int, F: int, K: int, nhid: int, d: int, two_layer: bool,
     out = (C.c_int * len(PROJECT_BWD_FORM))()
     check(load().dl_project_bwd_form(N, F, K, nhid, d, int(two_layer), int(have_hid), int(have_xplanes), out), "dl_project_bwd_form")
     return dict(zip(PROJECT_BWD_FORM, out))
+
+
+PROJECT_SPARSE_FORM = ("chunks", "last_chunk_cols", "affine", "max_segments", "seg_len", "two_layer", "width", "vec",
+                       "sA", "g_ranges")
+
+
+def project_sparse_form(N: int, F: int, K: int, nhid: int, d: int, two_layer: bool, affine: bool, max_col_len: int) -> dict:
+    """The launch decisions of dl_project_sparse_fwd / _bwd for this problem (dl_project_sparse_form)."""
+    out = (C.c_int * len(PROJECT_SPARSE_FORM))()
+    check(load().dl_project_sparse_form(N, F, K, nhid, d, int(two_layer), int(affine), max_col_len, out), "dl_project_sparse_form")
+    return dict(zip(PROJECT_SPARSE_FORM, out))
 
 
 SCORE_ALLPAIRS_FWD_FORM = ("kernel", "items", "grid", "n_slices", "slice_w", "chunks_per_u")

@@ -116,4 +116,20 @@ int project_bwd(const float* x, int N, int F, int K, int nhid, int d, const floa
                 const float* W2, const float* dZ, const float* hid, float* dW1, float* db1, float* dW2, float* db2,
                 void* ws, hipStream_t st, const void* xplanes = nullptr);
 
+// the kept-hidden-layer half of the backward without the dW1 contraction (dl_project_bwd.hip), for dl_project_sparse.hip
+size_t project_bwd_kept_workspace_bytes(int N, int K, int nhid, int d, bool two_layer);
+void project_bwd_kept_form(int N, int K, int nhid, int d, bool two_layer, int* out3);   // sA, tiles per range, sC
+void project_bwd_kept(int N, int K, int nhid, int d, const float* b1, const float* W2, const float* dZ, const float* hidT,
+                      float* dhid, float* db1, float* dW2, float* db2, void* ws, hipStream_t st);
+
+// projection of sparse features (dl_project_sparse.hip): layer 1 and dW1 as gathers over the CSR / CSC of x
+int sparse_seg_len();
+size_t project_sparse_fwd_workspace_bytes(const dl_sparse_features* x, int K, int nhid, int d, bool two_layer);
+size_t project_sparse_bwd_workspace_bytes(const dl_sparse_features* x, int K, int nhid, int d, bool two_layer);
+void project_sparse_form(int N, int F, int K, int nhid, int d, bool two_layer, bool affine, int max_col_len, int* out);
+int project_sparse_fwd(const dl_sparse_features* x, int K, int nhid, int d, const float* W1, const float* b1, const float* W2,
+                       const float* b2, float* Z, float* hid_out, void* ws, hipStream_t st);
+int project_sparse_bwd(const dl_sparse_features* x, int K, int nhid, int d, const float* b1, const float* W2, const float* dZ,
+                       const float* hid, float* dW1, float* db1, float* dW2, float* db2, void* ws, hipStream_t st);
+
 }  // namespace dl

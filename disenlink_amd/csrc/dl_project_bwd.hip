@@ -899,6 +899,61 @@ static void project_bwd_block(const float* x, int N, int F, int K, int nhid, int
     sums.run(acc, st);
 }
 
+// Everything of the backward except the dW1 contraction, from a kept hidden layer, for a caller that contracts over the
+// nodes itself (dl_project_sparse.hip: x is a CSR there): the bias gradient of the output layer (column sums of dZ) and,
+// two-layer, kernel A in its kept fp32 form — dW2, db1 and the masked hidden gradient dhid as fp32 [N][K*nhid] — through
+// the launchers, ranges and slab sums project_bwd_block uses.  One node block whatever N.  Single layer (W2 == nullptr):
+// db1 = column sums of dZ, nothing else.
+struct KeptLayout { int sA, tiles_per_range, sC, rows_per_range; size_t off_w2p, off_b1p, off_b2p, bytes; };
+static KeptLayout kept_layout(int N, int K, int nhid, int d, bool two) {
+    const project::BwdLayout B = project::bwd_layout(N, 4, K, nhid, d, two, false, false);
+    KeptLayout L{B.sA, B.tiles_per_range, B.sC, B.rows_per_range, 0, 0, 0, 0};
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t off = 0;
+    L.off_w2p = off;  off += two ? al(sizeof(float) * (size_t)L.sA * K * d * nhid) : 0;
+    L.off_b1p = off;  off += two ? al(sizeof(float) * (size_t)L.sA * K * nhid) : 0;
+    L.off_b2p = off;  off += al(sizeof(float) * (size_t)L.sC * K * d);
+    L.bytes = off;
+    return L;
+}
+
+size_t project_bwd_kept_workspace_bytes(int N, int K, int nhid, int d, bool two_layer) {
+    return N > 0 ? kept_layout(N, K, nhid, d, two_layer).bytes : 0;
+}
+
+void project_bwd_kept_form(int N, int K, int nhid, int d, bool two_layer, int* out3) {
+    const KeptLayout L = kept_layout(N, K, nhid, d, two_layer);
+    out3[0] = two_layer ? L.sA : 0;
+    out3[1] = two_layer ? L.tiles_per_range : 0;
+    out3[2] = L.sC;
+}
+
+void project_bwd_kept(int N, int K, int nhid, int d, const float* b1, const float* W2, const float* dZ, const float* hidT,
+                      float* dhid, float* db1, float* dW2, float* db2, void* ws, hipStream_t st) {
+    using namespace project;
+    const bool two = W2 != nullptr;
+    const KeptLayout L = kept_layout(N, K, nhid, d, two);
+    char* base = static_cast<char*>(ws);
+    float* w2p = reinterpret_cast<float*>(base + L.off_w2p);
+    float* b1p = reinterpret_cast<float*>(base + L.off_b1p);
+    float* b2p = reinterpret_cast<float*>(base + L.off_b2p);
+    hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)ceil_div((long long)K * d, 64), (unsigned)L.sC), dim3(256), 0, st,
+                       dZ, N, K * d, L.rows_per_range, b2p);
+    SlabBatch sums;
+    sums.add(b2p, L.sC, (size_t)K * d, two ? db2 : db1);
+    if (two) {
+        const int ldh = (N + 3) & ~3;
+        const dim3 grid((unsigned)xcd_grid(L.sA, ceil_div(nhid, 64 * bwd_ht(d)) * K));
+        const DhidPlanes none{nullptr, 0, 0};
+        if (d == 32) launchA_t<32, true, false, false>(grid, st, nullptr, N, 4, nhid, nullptr, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p, b1p, hidT, ldh, ldh, none);
+        if (d == 64) launchA_t<64, true, false, false>(grid, st, nullptr, N, 4, nhid, nullptr, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p, b1p, hidT, ldh, ldh, none);
+        if (d == 128) launchA_t<128, true, false, false>(grid, st, nullptr, N, 4, nhid, nullptr, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p, b1p, hidT, ldh, ldh, none);
+        sums.add(w2p, L.sA, (size_t)K * d * nhid, dW2);
+        sums.add(b1p, L.sA, (size_t)K * nhid, db1);
+    }
+    sums.run(false, st);
+}
+
 int project_bwd(const float* x, int N, int F, int K, int nhid, int d, const float* W1, const float* b1,
                 const float* W2, const float* dZ, const float* hid, float* dW1, float* db1, float* dW2, float* db2,
                 void* ws, hipStream_t st, const void* xplanes) {

@@ -547,6 +547,9 @@ class Shard:
 
     def pad_rows(self, x_local_real: torch.Tensor) -> torch.Tensor:
         """Feature rows of this rank's block, zero rows for padding nodes."""
+        if not torch.is_tensor(x_local_real):
+            raise TypeError("the sharded path takes dense feature rows: a SparseFeatures input (disenlink_amd/features.py) is "
+                            "served on one GPU only — pass x.to_dense()[lo:hi], or run unsharded")
         rows = self.hi - self.lo
         if x_local_real.shape[0] == rows:
             return x_local_real

@@ -58,14 +58,47 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rank-eval", action="store_true",
                    help="after each run, rank every test positive among all nodes (filtered by every dataset edge) and "
                         "print MRR and Hits@{1,10,50,100}")
+    p.add_argument("--sparse-features", action="store_true",
+                   help="hand the features to the model as features.SparseFeatures (scale * X + shift with X a CSR): layer 1 "
+                        "of the projection and its gradient run as gathers over the non-zero entries; for binary / one-hot "
+                        "features, standardised or not (single GPU)")
     p.add_argument("--gpus", type=int, default=1,
                    help="row-shard every run over this many GPUs of the node (one process per GPU, RCCL): started "
                         "plainly, the command launches its ranks itself (disenlink_amd/launch.py)")
     return p
 
 
-def load_dataset(args):
+_STANDARDISING_LOADERS = ("load_npz", "load_fb100", "load_twitch", "load_webkb", "load_amazon_npz", "load_deezer",
+                          "load_arxiv_year_mini")
+
+
+def load_dataset(args, raw: bool = False):
+    """The dataset of the command line.  raw=True (--sparse-features): -> (dataset with UNstandardised features, whether
+    the loader would have standardised their rows) — features.SparseFeatures.from_dense applies the standardisation as its
+    per-row scale and shift."""
     from . import datasets
+    if not raw:
+        return _load_dataset(args, datasets)
+
+    class _Raw:                                                      # the loaders that standardise, asked not to
+        def __init__(self):
+            self.standardised = False
+
+        def __getattr__(self, name):
+            fn = getattr(datasets, name)
+            if name not in _STANDARDISING_LOADERS:
+                return fn
+
+            def call(*a, **kw):
+                self.standardised = True
+                return fn(*a, standardise=False, **kw)
+            return call
+    shim = _Raw()
+    ds = _load_dataset(args, shim)
+    return ds, shim.standardised
+
+
+def _load_dataset(args, datasets):
     from .data import SPECS, synthetic_graph
     if args.data_file:
         return datasets.load_binary(args.data_file)
@@ -191,6 +224,8 @@ def main(argv=None):
     args = build_parser().parse_known_args(argv)[0]                 # unknown tokens ignored, like :50
     if args.layer != 1:
         raise SystemExit("only --layer 1 exists in the reference (main_disentangled.py:147-148)")
+    if args.gpus > 1 and args.sparse_features:
+        raise SystemExit("--sparse-features runs on one GPU only (the sharded path takes dense feature rows): drop --gpus")
     if args.gpus > 1 and args.rank_eval:
         raise SystemExit("--rank-eval runs on one GPU only (sharded ranking is not implemented): drop --gpus or --rank-eval")
     if args.gpus > 1:
@@ -210,11 +245,18 @@ def main(argv=None):
     from .train import prepare_run, run_link_prediction
     device = torch.device("cuda", args.gpu)
     torch.cuda.set_device(device)
-    ds = load_dataset(args)
+    ds, standardise = load_dataset(args, raw=True) if args.sparse_features else (load_dataset(args), False)
     if not args.quiet:
         print(args)
         print(f"dataset {ds.name}: N={ds.n_nodes} F={ds.x.shape[1]} edge rows={ds.src.size}")
-    x = torch.from_numpy(ds.x).to(device)
+    if args.sparse_features:
+        from .features import SparseFeatures
+        x = SparseFeatures.from_dense(ds.x, standardise=standardise).to(device)
+        if not args.quiet:
+            print(f"sparse features: {x.nnz} non-zero entries of {x.shape[0]} x {x.shape[1]}"
+                  f"{', row-standardised' if standardise else ''}")
+    else:
+        x = torch.from_numpy(ds.x).to(device)
     tdt = torch.bfloat16 if args.table_dtype == "bf16" else torch.float32
     result = []
     ranking = []

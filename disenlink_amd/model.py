@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .features import SparseFeatures
 from .graph import Graph, PairList
 
 
@@ -206,6 +207,25 @@ class Disentangle(nn.Module):
         a CUDA tensor whose shape the kernels do not serve raises instead of falling back."""
         fs = self.factors
         K, d = self.nfactor, self.nebed
+        if isinstance(x, SparseFeatures):
+            # features.py: scale * X + shift with X a CSR.  On the GPU layer 1 and dW1 are gathers (ops.ProjectSparse) and
+            # there is never a dense product; a CPU object takes the CPU branch below on to_dense() (host tests only)
+            if not x.is_cuda:
+                return self.project(x.to_dense())
+            if not ops.project_supported(d):
+                raise ops._lib.DisenlinkHipError(f"the sparse projection kernels serve factor widths d <= 128 (got d = {d})")
+            flat = self._stacked_params()
+            st = self._stacked
+            if flat is not None:
+                bufs = ((st[("mlp", "weight")], st[("mlp", "bias")], None, None) if self.single_layer else
+                        (st[("mlp1", "weight")], st[("mlp1", "bias")], st[("mlp2", "weight")], st[("mlp2", "bias")]))
+                return ops.ProjectSparse.apply(x, bufs, K, *flat)
+            if self.single_layer:
+                return ops.ProjectSparse.apply(x, None, K, torch.stack([f.mlp.weight for f in fs]),
+                                               torch.stack([f.mlp.bias for f in fs]), None, None)
+            return ops.ProjectSparse.apply(x, None, K, torch.stack([f.mlp1.weight for f in fs]),
+                                           torch.stack([f.mlp1.bias for f in fs]), torch.stack([f.mlp2.weight for f in fs]),
+                                           torch.stack([f.mlp2.bias for f in fs]))
         if x.is_cuda and self.projection != "library" and not (x.dtype == torch.float32 and ops.project_supported(d)):
             raise ops._lib.DisenlinkHipError(
                 f"the projection kernels serve fp32 features and factor widths d <= 128 (got {x.dtype}, d = {d}); "
@@ -337,6 +357,9 @@ class Disentangle(nn.Module):
 
     def forward_pairs(self, x, graph: Graph, pairs: PairList):
         """(emb [N,K*d], prob [P]) — the same model evaluated on a pair list only."""
+        if self.use_torch_ops and isinstance(x, SparseFeatures):
+            raise TypeError("use_torch_ops=True: the registered torch.ops.disenlink operators take dense features; a "
+                            "SparseFeatures input runs through the autograd.Functions (use_torch_ops=False)")
         if self.use_torch_ops and not self.single_layer and self.table_dtype == torch.float32 and x.is_cuda \
                 and ops.project_supported(self.nebed):
             from . import torch_ops

@@ -87,6 +87,8 @@ def hot_path_pairs_loss(Z: torch.Tensor, graph: Graph, pairs: PairList, beta: fl
 def project_ok(x: torch.Tensor, d: int, single_layer: bool) -> bool:
     """Does the compiled projection node serve this call?  (two-layer form, fp32 rows of 16-byte-aligned length, a factor
     width the kernels are instantiated for; the Python operator pads / re-stacks everything else)"""
+    if not torch.is_tensor(x):                                      # a SparseFeatures: served by ops.ProjectSparse only
+        return False
     return load() and not single_layer and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] % 4 == 0 \
         and d in (32, 64, 128) and os.environ.get("DL_PROJECT_BWD", "native") != "library"
 

@@ -15,6 +15,7 @@ import weakref
 import torch
 
 from . import _lib
+from .features import SparseFeatures
 from .graph import Graph, PairList
 
 
@@ -376,7 +377,10 @@ _xpad = _PaddedFeatures()
 
 
 def padded_features(x: torch.Tensor) -> torch.Tensor:
-    """The tensor project_fwd / project_bwd actually read for x (x itself when its rows are 16-byte aligned)."""
+    """The tensor project_fwd / project_bwd actually read for x (x itself when its rows are 16-byte aligned; a
+    SparseFeatures passes through untouched: the sparse kernels read its arrays)."""
+    if isinstance(x, SparseFeatures):
+        return x
     F = x.shape[1]
     Fp = (F + 3) // 4 * 4
     return x if Fp == F else _xpad.get(x, Fp)
@@ -432,7 +436,10 @@ _xplanes = _XPlanes()
 
 def xplanes_for(x: torch.Tensor, force: bool = False):
     """The persistent planes of the tensor the projection kernels read for x (its zero-padded copy when F % 4 != 0), or
-    None (first sight of the tensor, a blocked graph, DL_X_PLANES=0).  force=True builds them now (before a graph capture)."""
+    None (first sight of the tensor, a blocked graph, DL_X_PLANES=0, a SparseFeatures: the sparse kernels use no planes of
+    x).  force=True builds them now (before a graph capture)."""
+    if isinstance(x, SparseFeatures):
+        return None
     return _xplanes.get(padded_features(_f32c(x)), force)
 
 
@@ -613,7 +620,126 @@ def project_supported(d: int) -> bool:
     return project_tile_width(int(d)) is not None
 
 
+def _sparse_shapes(sf, W1, b1, W2, b2=None):
+    if not isinstance(sf, SparseFeatures) or not sf.is_cuda:
+        raise _lib.DisenlinkHipError("the sparse projection kernels take a SparseFeatures on the GPU")
+    W1, b1 = _f32c(W1), _f32c(b1)
+    _need_cuda(W1, b1)
+    N, F = sf.shape
+    K = W1.shape[0]
+    if W1.shape[2] != F:
+        raise ValueError("W1 does not match the feature count of x")
+    two = W2 is not None
+    d_true = W2.shape[1] if two else W1.shape[1]
+    dp = project_tile_width(d_true)
+    if dp is None:
+        raise _lib.DisenlinkHipError(f"projection kernels serve d <= {_TILE_WIDTHS[-1]}, got {d_true}")
+    nhid = W1.shape[1] if two else 1
+    if two:
+        W2 = _f32c(W2)
+        if W2.shape != (K, d_true, nhid) or b1.shape != (K, nhid) or (b2 is not None and b2.shape != (K, d_true)):
+            raise ValueError("inconsistent projection weight shapes")
+    return W1, b1, W2, N, F, K, nhid, d_true, dp, two
+
+
+def project_sparse_fwd(sf, W1, b1, W2=None, b2=None):
+    """project_fwd for a SparseFeatures input (dl_project_sparse_fwd): layer 1 as a gather over the CSR of x.  Two-layer:
+    returns (Z, hid) — the hidden layer is always kept, the backward has no recompute form; single layer: Z.
+    Any d <= 128, as project_fwd."""
+    lib = _lib.load()
+    W1, b1, W2, N, F, K, nhid, d_true, dp, two = _sparse_shapes(sf, W1, b1, W2, b2)
+    if dp != d_true:                                           # run at the tile width, hand back the first d columns
+        if not two:
+            W1p, b1p = _pad_out_rows(W1, b1, dp)
+            return project_sparse_fwd(sf, W1p, b1p)[:, :, :d_true].contiguous()
+        W2p, b2p = _pad_out_rows(W2, _f32c(b2), dp)
+        Z, hid = project_sparse_fwd(sf, W1, b1, W2p, b2p)
+        return Z[:, :, :d_true].contiguous(), hid
+    b2 = _f32c(b2) if two else None
+    Z = _empty((N, K, dp), torch.float32, sf.device)
+    hid = _empty(int(lib.dl_project_hidden_floats(N, K, nhid)), torch.float32, sf.device) if two else None
+    ref = sf.c_struct()
+    ws = _ws.get(int(lib.dl_project_sparse_fwd_workspace_bytes(ref, K, nhid, dp, int(two))), sf.device)
+    _lib.check(lib.dl_project_sparse_fwd(ref, K, nhid, dp, W1.data_ptr(), b1.data_ptr(), W2.data_ptr() if two else None,
+                                         b2.data_ptr() if two else None, Z.data_ptr(), hid.data_ptr() if two else None,
+                                         ws.data_ptr(), ws.numel(), _stream()), "dl_project_sparse_fwd")
+    return (Z, hid) if two else Z
+
+
+def project_sparse_bwd(sf, W1, b1, W2, dZ, hid=None):
+    """project_bwd for a SparseFeatures input (dl_project_sparse_bwd): (dW1, db1, dW2, db2) from dZ [N,K,d] and the hidden
+    layer project_sparse_fwd kept; dW1 as a gather over the CSC view of x.  The gradients are views of one flat buffer where
+    their sizes allow, like project_bwd's."""
+    lib = _lib.load()
+    W1, b1, W2, N, F, K, nhid, d_true, dp, two = _sparse_shapes(sf, W1, b1, W2)
+    dZ = _f32c(dZ)
+    _need_cuda(dZ)
+    if dZ.shape != (N, K, d_true):
+        raise ValueError("inconsistent projection shapes")
+    if dp != d_true:                                           # zero-padded output columns carry zero gradient in
+        dZp = torch.nn.functional.pad(dZ, (0, dp - d_true))
+        if not two:
+            W1p, b1p = _pad_out_rows(W1, b1, dp)
+            dW1, db1, _n1, _n2 = project_sparse_bwd(sf, W1p, b1p, None, dZp)
+            return dW1[:, :d_true].contiguous(), db1[:, :d_true].contiguous(), None, None
+        W2p = torch.nn.functional.pad(W2, (0, 0, 0, dp - d_true))
+        dW1, db1, dW2, db2 = project_sparse_bwd(sf, W1, b1, W2p, dZp, hid=hid)
+        return dW1, db1, dW2[:, :d_true].contiguous(), db2[:, :d_true].contiguous()
+    if two and hid is None:
+        raise _lib.DisenlinkHipError("the sparse backward has no recompute form: pass the hidden layer project_sparse_fwd kept")
+    shapes = [tuple(W1.shape), tuple(b1.shape)] + ([tuple(W2.shape), (K, dp)] if two else [])
+    sizes = [int(torch.Size(sh).numel()) for sh in shapes]
+    if all(n % 4 == 0 for n in sizes):
+        flat = _empty((sum(sizes),), torch.float32, sf.device)
+        parts, off = [], 0
+        for sh, n in zip(shapes, sizes):
+            parts.append(flat[off:off + n].view(sh))
+            off += n
+    else:
+        parts = [_empty(sh, torch.float32, sf.device) for sh in shapes]
+    dW1, db1 = parts[0], parts[1]
+    dW2, db2 = (parts[2], parts[3]) if two else (None, None)
+    ref = sf.c_struct()
+    ws = _ws.get(int(lib.dl_project_sparse_bwd_workspace_bytes(ref, K, nhid, dp, int(two))), sf.device)
+    _lib.check(lib.dl_project_sparse_bwd(ref, K, nhid, dp, W1.data_ptr(), b1.data_ptr(), W2.data_ptr() if two else None,
+                                         dZ.data_ptr(), hid.data_ptr() if two else None, dW1.data_ptr(), db1.data_ptr(),
+                                         dW2.data_ptr() if two else None, db2.data_ptr() if two else None,
+                                         ws.data_ptr(), ws.numel(), _stream()), "dl_project_sparse_bwd")
+    return dW1, db1, dW2, db2
+
+
 # ---------------------------------------------------------------------- autograd
+class ProjectSparse(torch.autograd.Function):
+    """Z = MLP_k(x~) for all k on a SparseFeatures x (features.py): forward dl_project_sparse_fwd (the hidden layer is
+    kept), backward dl_project_sparse_bwd.  Weights: the module's shared [K, ...] buffers (bufs, with the K per-factor
+    Parameters as autograd inputs, as ProjectStacked) or, with bufs = None, four stacked tensors in `params`.  x is data
+    and gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, sf, bufs, K, *params):
+        stacked = bufs is not None
+        W1, b1, W2, b2 = bufs if stacked else params
+        ctx.sf, ctx.stacked, ctx.K = sf, stacked, K
+        ctx.weights = (W1, b1, W2)
+        if W2 is None:
+            ctx.hid = None
+            return project_sparse_fwd(sf, W1, b1)
+        Z, ctx.hid = project_sparse_fwd(sf, W1, b1, W2, b2)
+        return Z
+
+    @staticmethod
+    def backward(ctx, dZ):
+        W1, b1, W2 = ctx.weights
+        dW1, db1, dW2, db2 = project_sparse_bwd(ctx.sf, W1, b1, W2, dZ.contiguous(), ctx.hid)
+        ctx.hid = None
+        if not ctx.stacked:
+            return (None, None, None, dW1, db1, dW2, db2)
+        grads = list(dW1.unbind(0)) + list(db1.unbind(0))
+        if W2 is not None:
+            grads += list(dW2.unbind(0)) + list(db2.unbind(0))
+        return (None, None, None, *grads)
+
+
 class Project(torch.autograd.Function):
     """Z = MLP_k(x) for all k.  Forward: the fused MFMA kernel (hidden activations never leave the
     register file).  Backward: dl_project_bwd (hidden layer recomputed on the matrix cores); x is data and

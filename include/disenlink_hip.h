@@ -264,6 +264,69 @@ int dl_project_bwd(const float* x, int N, int F, int K, int nhid, int d,
 int dl_project_fwd_form(int N, int F, int K, int nhid, int d, int two_layer, size_t ws_bytes, int have_xplanes, int* out);
 int dl_project_bwd_form(int N, int F, int K, int nhid, int d, int two_layer, int have_hid, int have_xplanes, int* out);
 
+/* Sparse feature input of the projection (replaces model.py:13-15 / 24-27 fanned out at model.py:106 for features that
+ * are sparse, or two-valued per row after row standardisation):
+ *     x~[i][f] = scale[i] * X[i][f] + shift[i]
+ * X is a CSR (columns strictly ascending within a row; val == NULL: all ones), scale / shift are per node (NULL: 1 / 0).
+ * The struct also carries the CSC view of X (rows ascending within a column; csc_entry = index of the entry in col / val)
+ * and the segment plan of the dW1 gather: column f is cut into ceil(len / seg_len) segments of seg_len consecutive entries
+ * (the last may be shorter), numbered colseg[f] .. colseg[f+1]-1; seg_col[s] is the column of segment s.  How a column is
+ * cut depends on that column alone.  seg_len must be dl_sparse_seg_len() (512 entries unless DL_SPARSE_SEG is set).
+ * Every pointer is a device pointer; N, F, nnz, seg_len, n_seg are host values. */
+typedef struct dl_sparse_features {
+    int32_t N, F, nnz;
+    const int32_t* rowptr;      /* [N+1] */
+    const int32_t* col;         /* [nnz] */
+    const float* val;           /* [nnz] or NULL = ones */
+    const float* scale;         /* [N] or NULL = 1 */
+    const float* shift;         /* [N] or NULL = 0 */
+    const int32_t* colptr;      /* [F+1] */
+    const int32_t* csc_row;     /* [nnz] */
+    const int32_t* csc_entry;   /* [nnz] */
+    int32_t seg_len, n_seg;
+    const int32_t* colseg;      /* [F+1] */
+    const int32_t* seg_col;     /* [n_seg] */
+} dl_sparse_features;
+int dl_sparse_seg_len(void);
+
+/* Projection of sparse features: model.py:13-15 / 24-27 at model.py:106 with layer 1 as a gather.  The arguments are those
+ * of dl_project_fwd with the struct in place of x (N and F are the struct's).  Per node i and output column c of layer 1
+ * (c = k * nhid + h; single layer: c = k * d + dd):
+ *     acc = sum over the entries e of row i, ascending, of val[e] * W1[c][col[e]]          (one fp32 fma chain)
+ *     pre = scale[i] * acc + shift[i] * csum[c] + b1[c],   csum[c] = sum_f W1[c][f]  (formed only when shift is given)
+ * two-layer: hid = relu(pre) goes to hid_out (REQUIRED, dl_project_hidden_floats(N, K, nhid) floats, the layout of
+ * dl_project_fwd's hid_out) and Z = W2 . hid + b2 is formed from it on the matrix cores (three bf16 planes per operand,
+ * six exact products per term); single layer (W2 = b2 = NULL, nhid = 1): Z = pre.  d in {32, 64, 128}.
+ * A row's result depends on that row alone.  No float atomics: bitwise reproducible.
+ * ws (required): dl_project_sparse_fwd_workspace_bytes — W1 transposed to [F][K*nhid] (per call: the weights move every
+ * step) and csum. */
+size_t dl_project_sparse_fwd_workspace_bytes(const dl_sparse_features* x, int K, int nhid, int d, int two_layer);
+int dl_project_sparse_fwd(const dl_sparse_features* x, int K, int nhid, int d,
+                          const float* W1, const float* b1, const float* W2, const float* b2,
+                          float* Z, float* hid_out, void* ws, size_t ws_bytes, void* stream);
+
+/* Its backward (autograd of model.py:13-15 / 24-27 under loss.backward(), main_disentangled.py:198): the gradients of
+ * dl_project_bwd.  hid (two-layer) is REQUIRED: there is no recompute form.  dW2, db2, db1 and the masked hidden
+ * gradient dhid come from the kept form of dl_project_bwd's first kernel; dW1 is a gather over the CSC view:
+ *     dW1[c][f] = sum over the entries e of column f, rows ascending, of (scale[i] * val[e]) * dhid[i][c]  +  g[c],
+ *     g[c] = sum_i shift[i] * dhid[i][c]   (only with shift; node ranges summed in a fixed order),
+ * column segments summed by separate waves and added in segment order.  Every element of every gradient is written
+ * (empty columns included).  No float atomics.  ws (required): dl_project_sparse_bwd_workspace_bytes. */
+size_t dl_project_sparse_bwd_workspace_bytes(const dl_sparse_features* x, int K, int nhid, int d, int two_layer);
+int dl_project_sparse_bwd(const dl_sparse_features* x, int K, int nhid, int d,
+                          const float* W1, const float* b1, const float* W2, const float* dZ, const float* hid,
+                          float* dW1, float* db1, float* dW2, float* db2, void* ws, size_t ws_bytes, void* stream);
+
+/* The launch decisions of the two entries above for a shape (host only, nothing is launched; model.py:13-15, 24-27, 106),
+ * under the current DL_SPARSE_SEG / DL_BWD_TARGET.  affine: shift is given; max_col_len: entries of the longest column.
+ * out[DL_PROJECT_SPARSE_FORM_LEN] =
+ *   [0] 256-column chunks of the layer-1 output  [1] columns of the last chunk (256 = not ragged)  [2] the affine term
+ *   (csum, g) is formed  [3] segments of the longest column  [4] entries per segment  [5] two-layer  [6] width of the
+ *   layer-2 kernel and of kernel A (0: single layer, neither runs)  [7] the dW1 gather reads dhid rows as aligned quads
+ *   [8] node ranges of kernel A  [9] node ranges of g */
+#define DL_PROJECT_SPARSE_FORM_LEN 10
+int dl_project_sparse_form(int N, int F, int K, int nhid, int d, int two_layer, int affine, int max_col_len, int* out);
+
 /* Routing: replaces model.py:56-72 restricted to adj==1 entries.
  *   per edge e=(i,j):  sigma_k = z_k[i].z_k[j] / t ; e_k = exp(sigma_k) ; alpha_k = e_k / sum_k e_k
  *                      p[e] = argmax_k alpha_k (first max; NaN counts as max) ; a[e] = alpha_p
