@@ -27,9 +27,18 @@ class DlGraph(C.Structure):
     _fields_ = [("csr", DlCsrPlan), ("route", DlCsrPlan), ("rev", C.c_void_p), ("route_mirror", C.c_int32)]
 
 
+class DlPairHub(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("block_row", C.c_void_p),
+                ("n_items", C.c_int32), ("n_slices", C.c_int32), ("slice_max_item", C.c_int32),
+                ("slice_item0", C.c_void_p), ("item_block", C.c_void_p), ("item_step", C.c_void_p),
+                ("n_steps", C.c_int32), ("step_v", C.c_void_p), ("step_u", C.c_void_p), ("step_q", C.c_void_p),
+                ("step_q2", C.c_void_p), ("n_entries", C.c_int32),
+                ("rest", DlCsrPlan), ("rest_pair", C.c_void_p), ("rest_pair2", C.c_void_p)]
+
+
 class DlPairIncidence(C.Structure):
     _fields_ = [("csr", DlCsrPlan), ("inc_pair", C.c_void_p), ("n_pairs", C.c_int32), ("entry_yw", C.c_void_p),
-                ("inc_pair2", C.c_void_p), ("n_second", C.c_int32)]
+                ("inc_pair2", C.c_void_p), ("n_second", C.c_int32), ("hub", C.POINTER(DlPairHub))]
 
 
 class DlHostCsr(C.Structure):

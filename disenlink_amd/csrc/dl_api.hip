@@ -287,6 +287,24 @@ int dl_score_pairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_dty
         DL_REQUIRE(n_second >= 0 && by_u->csr.n_entries + n_second == n_pairs && by_u->n_pairs == n_pairs && by_u->inc_pair,
                    "by_u must list each of the %d pairs exactly once", n_pairs);
         DL_REQUIRE(by_u->csr.n_total == N, "by_u.n_total=%d != N=%d", by_u->csr.n_total, N);
+        if (const dl_pair_hub* hp = by_u->hub) {                        // hub blocks + residual plan: the same entries, cut in two
+            DL_REQUIRE(hp->n_items >= 0 && hp->n_entries >= 0 && hp->rest.n_entries >= 0 &&
+                       hp->n_entries + hp->rest.n_entries == by_u->csr.n_entries,
+                       "by_u.hub must hold each of the plan's %d entries exactly once", by_u->csr.n_entries);
+            if (hp->n_items > 0) {
+                DL_REQUIRE(hp->n_slices >= 1 && hp->slice_max_item >= 1 && hp->n_blocks >= 1 && hp->n_steps >= 1, "by_u.hub: empty grid");
+                DL_REQUIRE(hp->block_row && hp->slice_item0 && hp->item_block && hp->item_step && hp->step_v && hp->step_u &&
+                           hp->step_q && (hp->step_q2 || !by_u->inc_pair2), "by_u.hub: NULL array");
+                // a step's four words are read as one 16-byte scalar load
+                DL_REQUIRE((((uintptr_t)hp->step_v | (uintptr_t)hp->step_u | (uintptr_t)hp->step_q | (uintptr_t)hp->step_q2) & 15) == 0,
+                           "by_u.hub: step_v, step_u, step_q and step_q2 must be 16-byte aligned");
+            }
+            if (hp->rest.n_entries > 0) {
+                if (int rc = check_plan(&hp->rest, "by_u.hub.rest")) return rc;
+                DL_REQUIRE(hp->rest.n_total == N && hp->rest.seg_len == by_u->csr.seg_len && hp->rest_pair &&
+                           (hp->rest_pair2 || !by_u->inc_pair2), "by_u.hub.rest does not match by_u");
+            }
+        }
         if (use_fast(&by_u->csr, K, d, dtype))
             return fast_score_pairs_fwd(by_u, Z, H, K, d, dtype, t, prob, coef, (hipStream_t)stream);
     }

@@ -25,6 +25,8 @@ void read_environment() {
     const char* sr = getenv("DL_STREAM_ROWS");
     c.stream_rows = (sr == nullptr || sr[0] == '\0') ? -1 : (sr[0] == '1' ? 1 : 0);
     c.fwd_group_kernel = flag("DL_FWD_GROUP_KERNEL");
+    const char* fh = getenv("DL_FWD_HUB");
+    c.fwd_hub = !(fh != nullptr && fh[0] == '0' && fh[1] == '\0');
     c.auc_target = (int)std::max(0LL, number("DL_AUC_TARGET"));
     c.project_fp32_mfma = getenv("DL_PROJECT_FP32_MFMA") != nullptr;
     c.fwd_groups = (int)std::max(0LL, number("DL_FWD_GROUPS"));

@@ -208,6 +208,139 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
     if (len % U != 0) do_step(nfull, std::true_type{}, len % U);
 }
 
+// ---------------------------------------------------------------------------- forward scorer over a hub plan
+// The wave-per-entry kernel above gathers one [Z row | H row] pair per entry and is bound by those bytes.  On a skewed pair
+// list most entries sit in a few long rows that score against many of the SAME partner rows: a workgroup that holds a
+// block of 16 such rows in LDS (dl_pair_hub, disenlink_hip.h) gathers a partner row once for up to four of them.
+// Eight waves stage the block's rows (64 KB at K = 8: two workgroups per CU), ONE barrier, and from there on every wave
+// runs on its own: wave w takes the steps w, w + 8, ... of the item, counted through its three lists [A | B | C] so that
+// no two waves differ by more than one step.  A step is the step of the kernel above — 4 / 2 / 1 partner rows gathered
+// into registers through a scalar row base, 16 float4 in flight before anything waits, the same dot4_packed calls into
+// val[table * 8 + chunk * 4 + slot], the same reduction, expf and sigmoid — except that every slot reads ITS OWN u row
+// from LDS, and that the partner registers a slot uses are fixed by the step's shape (NV = gathered rows: slot e uses
+// set e * NV / 4).  The value of a slot never meets another slot's, and the reduction adds the same 16 lanes in the same
+// order whichever slot a value sits in: every pair gets the bits of the kernel above.
+// The base name is that kernel's on purpose: the per-phase accounting of the benchmark matches kernels by base name.
+namespace hub {
+constexpr int WAVES = 8, THREADS = WAVES * DL_WAVE;
+
+// Four consecutive plan words at a wave-uniform index, as ONE scalar load: the pointer is typed constant address space, which
+// is what lets hipcc use the scalar cache for a load that follows the kernel's own stores (to prob — never to a plan array).
+typedef int dl_vi4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ dl_vi4 plan_words(const int32_t* a, int idx) {
+    const auto* g = (const __attribute__((address_space(1))) int32_t*)a;
+    return reinterpret_cast<const __attribute__((address_space(4))) dl_vi4*>((const __attribute__((address_space(4))) int32_t*)g)[idx];
+}
+
+template <int K, int D, bool T1, bool COEF, bool FOLD>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void score_fwd_wave_kernel(
+    dl_pair_hub h, const float* __restrict__ Z, const float* __restrict__ H, float t, float* __restrict__ prob,
+    float* __restrict__ coef_e, float* __restrict__ coef_q) {
+    using FW = FwdWave<K, D>;
+    constexpr int NJ = FW::NJ, U = FW::U, ROW = K * D, R4 = 2 * ROW / 4;      // R4: float4 of one [Z row | H row]
+    static_assert(D == 64 && NJ >= 1 && U == 4 && U * NJ <= 8, "the step geometry of score_fwd_wave_kernel");
+    static_assert(DL_HUB_W == 2 * WAVES, "every wave stages two rows of the block");
+    __shared__ __attribute__((aligned(16))) float4 urow[DL_HUB_W * R4];
+    const int x = blockIdx.x % h.n_slices;
+    const int it = h.slice_item0[x] + (int)(blockIdx.x / h.n_slices);
+    if (it >= h.slice_item0[x + 1]) return;                          // the whole workgroup, before the barrier
+    const int wave = wave_index(), lane = lane_id();
+    const int i = lane & 15, r = lane >> 4;
+    const int blk = h.item_block[it];
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        const int ul = 2 * wave + rr;
+        const int row = h.block_row[blk * DL_HUB_W + ul];             // wave-uniform; -1: the last block is short
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+            if (row >= 0) {
+                a = *reinterpret_cast<const float4*>(Z + (size_t)row * ROW + (j * 64 + lane) * 4);
+                b = *reinterpret_cast<const float4*>(H + (size_t)row * ROW + (j * 64 + lane) * 4);
+            }
+            urow[ul * R4 + j * 64 + lane] = a;
+            urow[ul * R4 + ROW / 4 + j * 64 + lane] = b;
+        }
+    }
+    __syncthreads();                                                 // the only one: nothing below waits for another wave
+    const int s_a = h.item_step[4 * it], s_b = h.item_step[4 * it + 1], s_c = h.item_step[4 * it + 2],
+              s_end = h.item_step[4 * it + 3];
+    auto do_step = [&](const int step, auto shape) {
+        constexpr int NV = decltype(shape)::value;                   // gathered partner rows: 4 (A), 2 (B), 1 (C)
+        const int s = __builtin_amdgcn_readfirstlane(step);
+        // the step's 16 words through the scalar cache (the plan is read-only for the whole launch)
+        const dl_vi4 v4 = plan_words(h.step_v, s), u4 = plan_words(h.step_u, s), q4 = plan_words(h.step_q, s);
+        dl_vi4 p4 = {-1, -1, -1, -1};
+        if constexpr (FOLD) p4 = plan_words(h.step_q2, s);
+        const int sv[4] = {v4.x, v4.y, v4.z, v4.w}, su[4] = {u4.x, u4.y, u4.z, u4.w}, sq[4] = {q4.x, q4.y, q4.z, q4.w},
+                  sq2[4] = {p4.x, p4.y, p4.z, p4.w};
+        float4 zv[NV][NJ], hv[NV][NJ];
+#pragma unroll
+        for (int n = 0; n < NV; ++n) {
+            if (NV == 1 || sv[n] >= 0) {                             // wave-uniform; a C step has no dead row
+                const size_t v = (size_t)(unsigned)sv[n];
+                const auto* zr = uniform_row<dl_vf4>(Z, v * ROW * sizeof(float));
+                const auto* hr = uniform_row<dl_vf4>(H, v * ROW * sizeof(float));
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    zv[n][j] = as_float4(zr[(unsigned)(lane + j * 64)]);
+                    hv[n][j] = as_float4(hr[(unsigned)(lane + j * 64)]);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) zv[n][j] = hv[n][j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+        }
+        float val[16];                                              // index = table * 8 + chunk * 4 + slot
+#pragma unroll
+        for (int q = 0; q < 16; ++q) val[q] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+            for (int e = 0; e < U; ++e) {
+                const float4* mine = urow + (su[e] & (DL_HUB_W - 1)) * R4;     // this slot's own u row
+                const float4 a4 = mine[j * 64 + lane], b4 = mine[ROW / 4 + j * 64 + lane];
+                val[j * 4 + e] = dot4_packed(a4, zv[e * NV / 4][j]);
+                val[8 + j * 4 + e] = dot4_packed(b4, hv[e * NV / 4][j]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        TransposedReduce<16, 8>::run(val, i);
+        const float mine_v = val[0];
+        const float ex = expf(T1 ? mine_v : mine_v / t);
+        const float ttv = mine_v * xor_lane<8>(ex);
+        float term = ttv;
+        if constexpr (NJ == 2) term += xor_lane<4>(ttv);
+        const float logit = add_xor<32>(add_xor<16>(term));
+        const float p = sigmoid_ref(logit);
+        const int e_me = i & 3;
+        const int qq = e_me == 0 ? sq[0] : e_me == 1 ? sq[1] : e_me == 2 ? sq[2] : sq[3];
+        const int qq2 = e_me == 0 ? sq2[0] : e_me == 1 ? sq2[1] : e_me == 2 ? sq2[2] : sq2[3];
+        const bool live = qq >= 0;
+        if (lane >= 8 && lane < 12 && live) {
+            prob[qq] = p;
+            if (FOLD && qq2 >= 0) prob[qq2] = p;
+        }
+        if constexpr (COEF) {
+            const int k = 4 * ((i & 7) >> 2) + r;
+            if (live && (NJ == 2 || (i & 7) < 4)) {
+                if (i < 8) coef_e[(size_t)qq * K + k] = ex;
+                else coef_q[(size_t)qq * K + k] = ttv;
+                if (FOLD && qq2 >= 0) {
+                    if (i < 8) coef_e[(size_t)qq2 * K + k] = ex;
+                    else coef_q[(size_t)qq2 * K + k] = ttv;
+                }
+            }
+        }
+    };
+    // step number n of the item (n = wave, wave + 8, ...) lies in list A, B or C by its place in [s_a, s_end)
+    int s = s_a + wave;
+    for (; s < s_b; s += WAVES) do_step(s, std::integral_constant<int, 4>{});
+    for (; s < s_c; s += WAVES) do_step(s, std::integral_constant<int, 2>{});
+    for (; s < s_end; s += WAVES) do_step(s, std::integral_constant<int, 1>{});
+}
+}  // namespace hub
+
 // Dense [N][N] scorer (the reference's link_pred, model.py:109-113): no pair list at all.  One wave = one
 // row u x one chunk of <= VCH consecutive columns; the column space is cut into n_slices XCD slices exactly
 // like the pair plans (workgroup b serves slice b % n_slices), so an XCD's L2 holds the v rows it gathers.
@@ -355,17 +488,34 @@ struct ScoreOps {
         float* coef_q = coef ? coef + (size_t)by_u->n_pairs * K : nullptr;
         if constexpr (std::is_same<T, float>::value && FwdWave<K, D>::ok) {
             if (g->seg_len <= 64 && g->seg_len % FwdWave<K, D>::U == 0 && !config().fwd_group_kernel) {
-                auto launch = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, dim3(seg_blocks(g)), dim3(BLOCK), 0, st, *g, by_u->inc_pair, by_u->inc_pair2,
-                                       (const float*)Z, (const float*)H, t, prob, coef, coef_q);
+                // the three flags of both wave kernels: temperature 1, stored terms, folded mirrors
+                auto pick = [&](auto launch) {
+                    auto fold = [&](auto t1, auto cf) {
+                        if (by_u->inc_pair2) launch(t1, cf, std::true_type{});
+                        else launch(t1, cf, std::false_type{});
+                    };
+                    if (coef) { if (t == 1.0f) fold(std::true_type{}, std::true_type{}); else fold(std::false_type{}, std::true_type{}); }
+                    else { if (t == 1.0f) fold(std::true_type{}, std::false_type{}); else fold(std::false_type{}, std::false_type{}); }
                 };
-                auto pick_fold = [&](auto t1, auto cf) {
-                    constexpr bool T1 = decltype(t1)::value, CF = decltype(cf)::value;
-                    if (by_u->inc_pair2) launch(score_fwd_wave_kernel<K, D, T1, CF, true>);
-                    else launch(score_fwd_wave_kernel<K, D, T1, CF, false>);
+                auto wave_plan = [&](const dl_csr_plan* c, const int32_t* pair, const int32_t* pair2) {
+                    pick([&](auto t1, auto cf, auto fo) {
+                        hipLaunchKernelGGL((score_fwd_wave_kernel<K, D, decltype(t1)::value, decltype(cf)::value, decltype(fo)::value>),
+                                           dim3(seg_blocks(c)), dim3(BLOCK), 0, st, *c, pair, pair2, (const float*)Z,
+                                           (const float*)H, t, prob, coef, coef_q);
+                    });
                 };
-                if (coef) { if (t == 1.0f) pick_fold(std::true_type{}, std::true_type{}); else pick_fold(std::false_type{}, std::true_type{}); }
-                else { if (t == 1.0f) pick_fold(std::true_type{}, std::false_type{}); else pick_fold(std::false_type{}, std::false_type{}); }
+                const dl_pair_hub* hp = config().fwd_hub ? by_u->hub : nullptr;
+                if (hp != nullptr && hp->n_items > 0) {
+                    // hub rows by blocks of 16 (hub::score_fwd_wave_kernel), then every other row as before
+                    pick([&](auto t1, auto cf, auto fo) {
+                        hipLaunchKernelGGL((hub::score_fwd_wave_kernel<K, D, decltype(t1)::value, decltype(cf)::value, decltype(fo)::value>),
+                                           dim3((unsigned)hp->n_slices * (unsigned)hp->slice_max_item), dim3(hub::THREADS), 0,
+                                           st, *hp, (const float*)Z, (const float*)H, t, prob, coef, coef_q);
+                    });
+                    if (hp->rest.n_entries > 0) wave_plan(&hp->rest, hp->rest_pair, hp->rest_pair2);
+                    return check_launch("score_pairs_fwd(fast, hub blocks + wave per entry)");
+                }
+                wave_plan(g, by_u->inc_pair, by_u->inc_pair2);
                 return check_launch("score_pairs_fwd(fast, wave per entry)");
             }
         }

@@ -509,6 +509,209 @@ def mirror_partners(pu: torch.Tensor, pv: torch.Tensor, n_nodes: int) -> torch.T
     return second
 
 
+# ---------------------------------------------------------------------------------------------- hub plan (forward scorer)
+HUB_W = 16                  # rows of a hub block (DL_HUB_W: 16 [Z | H] rows of K = 8, d = 64, fp32 are 64 KB of LDS)
+# Automatic choice of the hub rows: a list whose FIRST block of HUB_W ranked rows scores at least HUB_MIN_SHARE entries per
+# gathered row pair gets a hub plan over EVERY row with entries; any other list gets none (1.0 = nothing shared: uniform
+# sparse lists stay exactly as they were).  Taking blocks only while they reach the threshold was measured and lost: on
+# squirrel_real the scorer alone takes (us per call, median of 12 interleaved rounds, profiles/r10_fwd_hub.txt) 146.3
+# without hub rows, 148.1 / 139.1 / 136.7 / 137.2 with the top 512 / 1,024 / 1,376 (= every block at >= 1.25) / 2,048
+# rows and 132.9 with all 5,144 — the residual launch behind the hub launch, with its own tail, costs more than the
+# blocks near 1.0 do, and a block at 1.0 is still a step of four gathers like the wave-per-entry kernel's.
+HUB_MIN_SHARE = 1.25
+# A (block, slice) whose steps gather more partner rows than this is cut into several work items, each staging the
+# block's rows again: the longest (block, slice) of squirrel_real has ~1,300 steps, five times what a workgroup gets on
+# average, and uncut it would be the tail of the launch.  256 is what every figure above was measured with; its sweep
+# (tools/fwd_hub_ab.py --items) is still to be run (profiles/r10_fwd_hub.txt, section 4).
+HUB_ITEM_ROWS = 256
+
+
+def hub_gathers(c: torch.Tensor) -> torch.Tensor:
+    """Partner rows gathered for c slots on one partner row: c // 4 steps of shape C, a remainder of 2 or 3 a half of a
+    shape B step, a remainder of 1 or 3 a slot of a shape A step."""
+    return c // 4 + torch.tensor([0, 1, 1, 2], device=c.device)[c % 4]
+
+
+def hub_rank(row: torch.Tensor, n_nodes: int):
+    """Rows ranked by entry count, most first, ties by row index -> (rank of every row, rows with entries)."""
+    cnt = torch.bincount(row, minlength=n_nodes)
+    order = torch.argsort(-cnt, stable=True)
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(n_nodes, device=row.device)
+    return rank, order, int((cnt > 0).sum())
+
+
+def hub_block_counts(row: torch.Tensor, col: torch.Tensor, n_nodes: int):
+    """(entries, gathered row pairs) of every block of HUB_W consecutive ranked rows under the packing of
+    HubPlan.build — what a (block, partner row) combination gathers does not depend on slices or work items."""
+    rank, _, n_live = hub_rank(row, n_nodes)
+    nb = (n_live + HUB_W - 1) // HUB_W
+    blk = torch.div(rank[row], HUB_W, rounding_mode="floor")
+    key, c = torch.unique(blk * n_nodes + col, return_counts=True)
+    gathers = torch.zeros(nb, dtype=torch.int64, device=row.device).index_add_(0, torch.div(key, n_nodes, rounding_mode="floor"),
+                                                                             hub_gathers(c))
+    return torch.bincount(blk, minlength=nb), gathers
+
+
+def auto_hub_rows(row: torch.Tensor, col: torch.Tensor, n_nodes: int, min_share: float | None = None) -> int:
+    """Hub rows of a list: every row with entries if the first block shares at least min_share entries per gathered row
+    pair, else none."""
+    if row.numel() == 0:
+        return 0
+    entries, gathers = hub_block_counts(row, col, n_nodes)
+    if float(entries[0]) < (HUB_MIN_SHARE if min_share is None else min_share) * float(gathers[0]):
+        return 0
+    return int((torch.bincount(row, minlength=n_nodes) > 0).sum())
+
+
+@dataclass
+class HubPlan:
+    """The forward entries of the T rows with the most entries as blocks of HUB_W rows, work items and steps of four
+    slots (dl_pair_hub, include/disenlink_hip.h), and the residual plan over every other row."""
+    n_rows: int                     # T
+    n_blocks: int
+    block_row: torch.Tensor         # [n_blocks * HUB_W]
+    n_items: int
+    n_slices: int                   # slice streams
+    slice_max_item: int
+    slice_item0: torch.Tensor       # [n_slices + 1]
+    item_block: torch.Tensor        # [n_items]
+    item_slice: torch.Tensor        # [n_items] column slice (not passed to the library)
+    item_step: torch.Tensor         # [n_items, 4]
+    step_v: torch.Tensor            # [n_steps, 4]
+    step_u: torch.Tensor
+    step_q: torch.Tensor
+    step_q2: torch.Tensor | None
+    n_entries: int
+    rest: CsrPlan | None
+    rest_pair: torch.Tensor | None
+    rest_pair2: torch.Tensor | None
+    _struct: _lib.DlPairHub | None = field(default=None, repr=False)
+
+    @property
+    def n_steps(self) -> int:
+        return int(self.step_v.shape[0])
+
+    @property
+    def n_gathered(self) -> int:
+        """Partner row pairs the hub steps gather."""
+        return int((self.step_v >= 0).sum())
+
+    @staticmethod
+    def build(row, col, pair, pair2, n_nodes: int, n_rows: int, n_slices: int, bounds, rest_csr) -> "HubPlan":
+        """``row, col, pair, pair2`` (int64; pair2 may be None): the forward entries; ``n_rows`` = T; ``bounds`` the
+        list's column slice boundaries; ``rest_csr(keep)`` builds the residual plan from the entries ``keep`` selects."""
+        dev = row.device
+        ar = lambda n: torch.arange(n, device=dev)
+        excl = lambda x: torch.cumsum(x, 0) - x
+        rank, order, n_live = hub_rank(row, n_nodes)
+        T = max(0, min(int(n_rows), n_live))
+        nb = (T + HUB_W - 1) // HUB_W
+        block_row = torch.full((nb * HUB_W,), -1, dtype=torch.int64, device=dev)
+        block_row[:T] = order[:T]
+        in_hub = rank[row] < T
+        hrow, v, q = row[in_hub], col[in_hub], pair[in_hub]
+        q2 = None if pair2 is None else pair2[in_hub]
+        E = int(v.numel())
+        blk = torch.div(rank[hrow], HUB_W, rounding_mode="floor")
+        ul = rank[hrow] - blk * HUB_W
+        sl = torch.bucketize(v, bounds.to(dev), right=True) if n_slices > 1 else torch.zeros_like(v)
+        n_streams = min(n_slices, DEFAULT_SLICES)
+        # groups = the entries of one (block, slice) on one partner row; a partner row lies in one slice
+        key = (blk * n_slices + sl) * n_nodes + v
+        perm = torch.argsort(key, stable=True)
+        key, blk, sl, v, ul, q = key[perm], blk[perm], sl[perm], v[perm], ul[perm], q[perm]
+        q2 = None if q2 is None else q2[perm]
+        gnew = torch.ones(E, dtype=torch.bool, device=dev)
+        gnew[1:] = key[1:] != key[:-1]
+        gfirst = torch.nonzero(gnew).reshape(-1)
+        g_of = torch.cumsum(gnew, 0) - 1
+        G = int(gfirst.numel())
+        c = torch.bincount(g_of, minlength=G)
+        g_bs = torch.div(key[gfirst], n_nodes, rounding_mode="floor")          # block * n_slices + slice
+        nC, rem = torch.div(c, 4, rounding_mode="floor"), c % 4
+        hasB, hasA = (rem >= 2).long(), ((rem == 1) | (rem == 3)).long()
+        gath = nC + hasB + hasA
+        # work items: a (block, slice), cut where its groups have gathered HUB_ITEM_ROWS partner rows
+        bs_new = torch.ones(G, dtype=torch.bool, device=dev)
+        bs_new[1:] = g_bs[1:] != g_bs[:-1]
+        bs_first = torch.nonzero(bs_new).reshape(-1)
+        bs_of = torch.cumsum(bs_new, 0) - 1
+        cum = excl(gath)
+        part = torch.div(cum - cum[bs_first][bs_of], HUB_ITEM_ROWS, rounding_mode="floor")
+        inew = bs_new.clone()
+        inew[1:] |= part[1:] != part[:-1]
+        ifirst = torch.nonzero(inew).reshape(-1)
+        i_of = torch.cumsum(inew, 0) - 1                                        # item of every group
+        I = int(ifirst.numel())
+        within = lambda x: excl(x) - excl(x)[ifirst][i_of]                      # exclusive count inside the item
+        cC, cB, cA = within(nC), within(hasB), within(hasA)
+        tot = lambda x: torch.zeros(I, dtype=torch.int64, device=dev).index_add_(0, i_of, x)
+        nC_i, nB_i, nA_i = tot(nC), (tot(hasB) + 1) // 2, (tot(hasA) + 3) // 4
+        n_i = nA_i + nB_i + nC_i
+        i_blk = torch.div(g_bs[ifirst], n_slices, rounding_mode="floor")
+        i_sl = g_bs[ifirst] - i_blk * n_slices
+        # storage: one stream of items per XCD, the slices of a stream one after the other, largest item first inside
+        big = int(n_i.max()) + 1 if I else 1
+        iperm = torch.argsort(((i_sl % n_streams) * (n_slices + 1) + i_sl) * big + (big - 1 - n_i), stable=True)
+        ipos = torch.empty_like(iperm)
+        ipos[iperm] = ar(I)
+        base = torch.empty(I, dtype=torch.int64, device=dev)
+        base[iperm] = excl(n_i[iperm])
+        item_step = torch.stack([base, base + nA_i, base + nA_i + nB_i, base + n_i], dim=1)
+        per_stream = torch.bincount(i_sl % n_streams, minlength=n_streams)
+        slice_item0 = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+        slice_item0[1:] = torch.cumsum(per_stream, 0)
+        S = int(n_i.sum())
+        # slots
+        p = ar(E) - gfirst[g_of]
+        e_c, e_nC, e_item = c[g_of], nC[g_of], i_of[g_of]
+        r = p - 4 * e_nC
+        isC = r < 0
+        isB = ~isC & (e_c % 4 >= 2) & (r < 2)
+        isA = ~isC & ~isB
+        eA, eB, eC = item_step[e_item, 0], item_step[e_item, 1], item_step[e_item, 2]
+        half, aslot = cB[g_of], cA[g_of]
+        step = torch.where(isC, eC + cC[g_of] + torch.div(p, 4, rounding_mode="floor"),
+                           torch.where(isB, eB + torch.div(half, 2, rounding_mode="floor"),
+                                       eA + torch.div(aslot, 4, rounding_mode="floor")))
+        slot = torch.where(isC, p % 4, torch.where(isB, (half % 2) * 2 + r, aslot % 4))
+        vset = torch.where(isC, torch.zeros_like(p), torch.where(isB, half % 2, aslot % 4))
+        mk = lambda fill: torch.full((S, 4), fill, dtype=torch.int64, device=dev)
+        step_v, step_u, step_q = mk(-1), mk(0), mk(-1)
+        step_v[step, vset] = v
+        step_u[step, slot] = ul
+        step_q[step, slot] = q
+        step_q2 = None
+        if q2 is not None:
+            step_q2 = mk(-1)
+            step_q2[step, slot] = q2
+        rest = rest_pair = rest_pair2 = None
+        if int((~in_hub).sum()):
+            got = rest_csr(~in_hub)
+            rest, rest_pair = got[0], got[1]
+            rest_pair2 = got[2] if len(got) > 2 else None
+        item_block = torch.empty(I, dtype=torch.int64, device=dev)
+        item_block[ipos] = i_blk
+        item_slice = torch.empty(I, dtype=torch.int64, device=dev)
+        item_slice[ipos] = i_sl
+        item_step_s = torch.empty_like(item_step)
+        item_step_s[ipos] = item_step
+        return HubPlan(T, nb, _i32(block_row), I, n_streams, int(per_stream.max()) if I else 0, _i32(slice_item0),
+                       _i32(item_block), _i32(item_slice), _i32(item_step_s), _i32(step_v), _i32(step_u), _i32(step_q),
+                       None if step_q2 is None else _i32(step_q2), E, rest, rest_pair, rest_pair2)
+
+    def c_value(self) -> _lib.DlPairHub:
+        if self._struct is None:
+            ptr = lambda t: None if t is None else t.data_ptr()
+            self._struct = _lib.DlPairHub(
+                self.n_blocks, ptr(self.block_row), self.n_items, self.n_slices, self.slice_max_item, ptr(self.slice_item0),
+                ptr(self.item_block), ptr(self.item_step), self.n_steps, ptr(self.step_v), ptr(self.step_u),
+                ptr(self.step_q), ptr(self.step_q2), self.n_entries,
+                self.rest.c_value() if self.rest is not None else _lib.DlCsrPlan(), ptr(self.rest_pair), ptr(self.rest_pair2))
+        return self._struct
+
+
 @dataclass
 class PairList:
     """Scored pairs ``(pu[q], pv[q])`` with the two CSR views the kernels walk:
@@ -530,6 +733,7 @@ class PairList:
     fwd: CsrPlan | None = None                       # None = by_u (nothing folded)
     fwd_pair: torch.Tensor | None = None
     fwd_pair2: torch.Tensor | None = None
+    hub: HubPlan | None = None                       # the forward entries as hub blocks + a residual plan (None: no hub rows)
     _struct: _lib.DlPairIncidence | None = field(default=None, repr=False)
     _struct_u: _lib.DlPairIncidence | None = field(default=None, repr=False)
     _yw: torch.Tensor | None = field(default=None, repr=False)      # per-entry (label, signed weight): bind_labels
@@ -585,13 +789,15 @@ class PairList:
               run_len: int = DEFAULT_RUN_LEN, row_range: tuple[int, int] | None = None,
               n_slices: int | None = None, by_u_range: tuple[int, int] | None = None,
               build_by_u: bool = True, row_bytes: int = 2048, inc_slices: int | None = None,
-              fold_mirrors: bool = True) -> "PairList":
+              fold_mirrors: bool = True, hub_rows: int | None = None) -> "PairList":
         """``row_range`` restricts the incidence rows to one shard's nodes (the pair ids in ``inc_pair``
         then index prob / g_prob arrays covering the whole pair list); ``by_u_range`` restricts the rows
         of the forward plan (every pu must lie inside it).  ``n_slices`` / ``inc_slices``: column slices of the forward
         plan / of the incidence plan (defaults: auto_slices / auto_inc_slices — the incidence plan pays a partial slot
         per (row, slice) group, the forward plan sums nothing across segments).  ``fold_mirrors=False`` keeps the forward
-        scorer on ``by_u`` (one entry per listed pair), which is built the same either way."""
+        scorer on ``by_u`` (one entry per listed pair), which is built the same either way.  ``hub_rows``: how many of the
+        rows with the most forward entries are scored by blocks of HUB_W rows (HubPlan) — None = auto_hub_rows (a list
+        without hub rows, or a row shard, gets none and nothing changes), 0 = none."""
         pu = pu.reshape(-1).to(torch.int64)
         pv = pv.reshape(-1).to(torch.int64)
         if pu.numel() != pv.numel():
@@ -609,10 +815,11 @@ class PairList:
         dev = pu.device
         ids = torch.arange(P, device=dev)
 
-        def csr(node, other, pair, lo, hi, seg, unit_segs=UNIT_SEGS, slices=None, pair2=None):
+        def csr(node, other, pair, lo, hi, seg, unit_segs=UNIT_SEGS, slices=None, pair2=None, bnd=None):
             slices = n_slices if slices is None else slices
             # slice boundaries from ALL entries of the list (before the row range cuts it): the same for every shard
-            bnd = slice_bounds(other, slices) if slices > 1 and other.numel() else None
+            if bnd is None:
+                bnd = slice_bounds(other, slices) if slices > 1 and other.numel() else None
             keep = (node >= lo) & (node < hi)
             node, other, pair = node[keep], other[keep], pair[keep]
             pair2 = None if pair2 is None else pair2[keep]
@@ -634,14 +841,25 @@ class PairList:
         lo, hi = (0, n_nodes) if row_range is None else row_range
         inc, inc_pair = csr(torch.cat([pu, pv]), torch.cat([pv, pu]), ids.repeat(2), lo, hi, seg_len, slices=inc_slices)
         fwd = fwd_pair = fwd_pair2 = None
+        f_u, f_v, f_q, f_q2 = pu, pv, ids, None                    # the forward entries
         if build_by_u and fold_mirrors:
             second = mirror_partners(pu, pv, n_nodes)
             if bool((second >= 0).any()):
                 kept = torch.ones(P, dtype=torch.bool, device=dev)
                 kept[second[second >= 0]] = False                  # the partner is scored by the entry that names it
-                fwd, fwd_pair, fwd_pair2 = csr(pu[kept], pv[kept], ids[kept], ulo, uhi, run_len, unit_segs=1,
-                                               pair2=second[kept])
-        return PairList(n_nodes, _i32(pu), _i32(pv), by_u, by_u_pair, inc, inc_pair, fwd, fwd_pair, fwd_pair2)
+                f_u, f_v, f_q, f_q2 = pu[kept], pv[kept], ids[kept], second[kept]
+                fwd, fwd_pair, fwd_pair2 = csr(f_u, f_v, f_q, ulo, uhi, run_len, unit_segs=1, pair2=f_q2)
+        hub = None
+        if hub_rows is not None and hub_rows > 0 and (by_u_range is not None or not build_by_u):
+            raise ValueError("hub rows need the full-range forward plan")
+        if build_by_u and by_u_range is None and P and hub_rows != 0:
+            T = auto_hub_rows(f_u, f_v, n_nodes) if hub_rows is None else int(hub_rows)
+            if T > 0:
+                bnd = slice_bounds(f_v, n_slices) if n_slices > 1 else None     # the forward plan's own boundaries
+                rest_csr = lambda keep: csr(f_u[keep], f_v[keep], f_q[keep], 0, n_nodes, run_len, unit_segs=1,
+                                            pair2=None if f_q2 is None else f_q2[keep], bnd=bnd)
+                hub = HubPlan.build(f_u, f_v, f_q, f_q2, n_nodes, T, n_slices, bnd, rest_csr)
+        return PairList(n_nodes, _i32(pu), _i32(pv), by_u, by_u_pair, inc, inc_pair, fwd, fwd_pair, fwd_pair2, hub)
 
     def c_struct(self, n_pairs_total: int | None = None):
         if self._struct is None:
@@ -657,6 +875,8 @@ class PairList:
             else:
                 self._struct_u = _lib.DlPairIncidence(self.fwd.c_value(), self.fwd_pair.data_ptr(), self.n_pairs, None,
                                                       self.fwd_pair2.data_ptr(), self.n_pairs - self.fwd.n_entries)
+            if self.hub is not None and self.hub.n_items > 0:
+                self._struct_u.hub = C.pointer(self.hub.c_value())
         return C.byref(self._struct_u)
 
     def c_plan(self):

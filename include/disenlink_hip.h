@@ -134,7 +134,44 @@ typedef struct dl_pair_incidence {
      * every pair exactly once as a first or a second id, csr.n_entries + n_second == n_pairs. */
     const int32_t* inc_pair2;   /* [csr.n_entries] */
     int32_t n_second;
+    /* Optional (NULL = not given), read by dl_score_pairs_fwd only: the same entries cut into a hub plan and a residual
+     * plan (dl_pair_hub below).  csr / inc_pair / inc_pair2 still describe the whole list. */
+    const struct dl_pair_hub* hub;
 } dl_pair_incidence;
+
+/* Hub plan of the forward scorer.  The rows with the most entries ("hub rows", ranked by entry count) are cut into
+ * blocks of DL_HUB_W consecutive ranked rows; the 16 rows of a block score against many of the same partner rows, and a
+ * workgroup that holds the block's [Z | H] rows in LDS gathers such a partner row ONCE for up to four of them.
+ * A work item is one (block, column slice) — long ones are cut into several items — and holds three lists of STEPS of
+ * four SLOTS; a slot is one entry (u_local = its row's place in the block, its pair id, its second pair id or -1):
+ *   shape A: four gathered partner rows, slot e scores against row e;
+ *   shape B: two gathered rows, slots 0,1 against the first and 2,3 against the second;
+ *   shape C: one gathered row, all four slots against it.
+ * A dead slot has pair id -1, a dead partner row -1; only the last step of a list holds any.  Steps are stored item by
+ * item as [A steps | B steps | C steps], item_step = the four boundaries.  Items are stored slice-major like the
+ * positions of a dl_csr_plan: workgroup b serves slice stream b % n_slices.  Every entry of the list is a live slot of
+ * exactly one step or an entry of `rest`, a plan of the usual form over the rows that are no hub rows.
+ * The four step_* arrays must be 16-byte aligned: a step's four words are read as one vector. */
+#define DL_HUB_W 16
+typedef struct dl_pair_hub {
+    int32_t n_blocks;
+    const int32_t* block_row;   /* [n_blocks * DL_HUB_W] global node id of the block's rows, -1 = none */
+    int32_t n_items;
+    int32_t n_slices;           /* slice streams (the grid's stride) */
+    int32_t slice_max_item;     /* most items in one stream (sizes the grid) */
+    const int32_t* slice_item0; /* [n_slices + 1] first item of each stream */
+    const int32_t* item_block;  /* [n_items] */
+    const int32_t* item_step;   /* [n_items][4]: A steps [0],[1)  B steps [1],[2)  C steps [2],[3) */
+    int32_t n_steps;
+    const int32_t* step_v;      /* [n_steps][4] partner rows (A: 4, B: the first 2, C: the first), -1 = dead */
+    const int32_t* step_u;      /* [n_steps][4] u_local of each slot, 0 .. DL_HUB_W - 1 */
+    const int32_t* step_q;      /* [n_steps][4] pair id of each slot, -1 = dead */
+    const int32_t* step_q2;     /* [n_steps][4] second pair id (-1 = none); NULL when inc_pair2 is NULL */
+    int32_t n_entries;          /* live slots */
+    dl_csr_plan rest;           /* residual plan (rest.n_entries + n_entries == csr.n_entries) */
+    const int32_t* rest_pair;   /* [rest.n_entries] */
+    const int32_t* rest_pair2;  /* [rest.n_entries], NULL when inc_pair2 is NULL */
+} dl_pair_hub;
 
 /* ---- host-side graph preparation (no GPU; the only entry points that allocate: malloc'd outputs are
  * released by the matching *_free).  Counterpart of the dense adjacency construction of
