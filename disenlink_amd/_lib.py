@@ -111,6 +111,10 @@ EXPORTS = {
     "dl_score_topk_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
     "dl_score_topk": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _i, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
     "dl_score_ranks": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_score_mine_supported": (_i, [_i, _i]),
+    "dl_score_mine_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "dl_score_mine_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dl_score_mine": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _i, _P, _P, _P, _P, _P, _P, _z, _P]),
     "dl_auc_pair_counts_supported": (_i, [_i, _i]),
     "dl_auc_pair_counts": (_i, [_P, _P, _i, _P, _i, _P, _P]),
     "dl_auc_pair_counts_add": (_i, [_P, _P, _i, _P, _i, _P, _P]),
@@ -211,6 +215,7 @@ SCORE_ALLPAIRS_FWD_FORM = ("kernel", "items", "grid", "n_slices", "slice_w", "ch
 SCORE_ALLPAIRS_KERNELS = ("generic", "per shape", "matrix cores, split on stage", "matrix cores, from planes")
 SCORE_ALLPAIRS_BWD_DENSE_FORM = ("Np", "NCB", "nslice", "min_tiles", "max_tiles")
 SCORE_TOPK_FORM = ("nd", "qtiles", "slices", "tiles_per_slice", "last_tiles", "cap")
+SCORE_MINE_FORM = ("nd", "tiles", "pairs", "pairs_per_wg", "grid", "max_scans", "scans_offset")
 
 
 def score_allpairs_fwd_form(N: int, K: int, d: int, dtype: int, ws_bytes: int) -> dict:
@@ -232,6 +237,13 @@ def score_topk_form(N: int, K: int, d: int, Q: int, k: int) -> dict:
     out = (C.c_int * len(SCORE_TOPK_FORM))()
     check(load().dl_score_topk_form(N, K, d, Q, k, out), "dl_score_topk_form")
     return dict(zip(SCORE_TOPK_FORM, out))
+
+
+def score_mine_form(N: int, K: int, d: int, m: int) -> dict:
+    """The link-mining scan's plan for this problem under the current DL_MINE_TILES (dl_score_mine_form)."""
+    out = (C.c_int * len(SCORE_MINE_FORM))()
+    check(load().dl_score_mine_form(N, K, d, m, out), "dl_score_mine_form")
+    return dict(zip(SCORE_MINE_FORM, out))
 
 
 def config_reload() -> None:

@@ -403,6 +403,44 @@ int dl_score_ranks(const float* Z, const float* H, int N, int K, int d, float t,
                        (hipStream_t)stream);
 }
 
+int dl_score_mine_supported(int K, int d) { return score_mine_supported(K, d) ? 1 : 0; }
+
+static int check_mine_shape(int N, int K, int d, int m) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(score_mine_supported(K, d), "the link-mining scan serves fp32 tables with 1 <= d <= 128, got d=%d", d);
+    DL_REQUIRE(N >= 0 && N <= 46340, "N=%d outside 0..46340 (the pair index u N + v must fit 31 bits)", N);
+    DL_REQUIRE(m >= 1 && m <= 65536, "m=%d outside 1..65536", m);
+    return DL_OK;
+}
+
+int dl_score_mine_form(int N, int K, int d, int m, int* out) {
+    if (int rc = check_mine_shape(N, K, d, m)) return rc;
+    DL_REQUIRE(out != nullptr, "out is NULL");
+    score_mine_form(N, d, m, out);
+    return DL_OK;
+}
+
+size_t dl_score_mine_workspace_bytes(int N, int K, int d, int m) {
+    if (N < 0 || N > 46340 || m < 1 || m > 65536 || !score_mine_supported(K, d)) return 0;
+    return score_mine_workspace_bytes(N, K, d, m);
+}
+
+int dl_score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
+                  float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws,
+                  size_t ws_bytes, void* stream) {
+    if (int rc = check_mine_shape(N, K, d, m)) return rc;
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    DL_REQUIRE(N == 0 || (Z && H), "NULL argument");
+    DL_REQUIRE((ex_rowptr == nullptr) == (ex_col == nullptr), "exclusion rowptr and col go together");
+    DL_REQUIRE(src && dst && logit && prob && count, "NULL output");
+    const size_t need = score_mine_workspace_bytes(N, K, d, m);
+    if (!ws || ws_bytes < need) {
+        set_error("workspace too small: have %zu, need %zu (dl_score_mine_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
+        return DL_E_WORKSPACE;
+    }
+    return score_mine(Z, H, N, K, d, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws, (hipStream_t)stream);
+}
+
 int dl_auc_pair_counts_supported(int n_pos, int n_neg) {
     return n_pos >= 0 && n_neg >= 0 && auc_counts_supported(n_pos, n_neg) ? 1 : 0;
 }

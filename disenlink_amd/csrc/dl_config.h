@@ -19,6 +19,7 @@ struct Config {
     int inkernel_combine;       // DL_INKERNEL_COMBINE: 0 = rows of several units always through the separate combine launch,
                                 // 1 (default) = inside the launch where the plan's rows are few units long, 2 = wherever a kernel can
     int rank_slices;            // DL_RANK_SLICES: candidate slices of the ranking scan (0 = by the CU count; results do not depend on it)
+    int mine_tiles;             // DL_MINE_TILES: tile pairs per workgroup of the link-mining scans (0 = by the CU count; results do not depend on it)
     int sparse_seg;             // DL_SPARSE_SEG: entries per column segment of the sparse projection's dW1 gather (0 = default; tests)
 };
 

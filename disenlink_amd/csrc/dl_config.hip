@@ -36,6 +36,7 @@ void read_environment() {
     const char* ic = getenv("DL_INKERNEL_COMBINE");
     c.inkernel_combine = (ic == nullptr || ic[0] == '\0') ? 1 : std::max(0, std::min(2, atoi(ic)));
     c.rank_slices = (int)std::max(0LL, number("DL_RANK_SLICES"));
+    c.mine_tiles = (int)std::max(0LL, std::min(1LL << 20, number("DL_MINE_TILES")));
     c.sparse_seg = (int)std::max(0LL, std::min(1LL << 20, number("DL_SPARSE_SEG")));
     g_config = c;
 }

@@ -57,6 +57,7 @@ void fast_score_allpairs_form(int N, int K, int d, int dtype, int* out);
 void dense_mfma_form(int N, int K, int d, size_t ws_bytes, int* out);
 void dense_bwd_form(int N, int K, int d, int* out);
 void score_topk_form(int N, int d, int Q, int k, int* out);
+void score_mine_form(int N, int d, int m, int* out);
 
 // dense scorer on the matrix cores (dl_score_dense.hip): fp32 tables, d % 32 == 0
 bool dense_mfma_supported(int d);
@@ -79,6 +80,13 @@ int score_topk(const float* Z, const float* H, int N, int K, int d, float t, con
 int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, const int32_t* tptr,
                 const int32_t* tdst, int T, const int32_t* ex_rowptr, const int32_t* ex_col, int64_t* greater, int64_t* ties,
                 void* ws, hipStream_t st);
+
+// global top-m of the logits of all unordered pairs on the matrix cores (dl_score_mine.hip): fp32 tables, 1 <= d <= 128
+bool score_mine_supported(int K, int d);
+size_t score_mine_workspace_bytes(int N, int K, int d, int m);
+int score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
+               float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws,
+               hipStream_t st);
 
 // tie-averaged AUC counts (dl_metrics.hip)
 bool auc_counts_supported(int n_pos, int n_neg);           // the smaller class fits the LDS

@@ -1,0 +1,474 @@
+// Mining of the graph's m most likely missing links (dl_score_mine): an exact, deterministic global top-m over the logits
+//   s(u, v) = sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t)
+// of all unordered pairs u < v, with nothing of size N x N in memory.
+//
+// Scan: the tile loop of the ranking scan (dl_score_rank.hip) over the tile pairs (u tile <= v tile) of the dense scorer: one
+// workgroup = 8 waves = a run of consecutive tile pairs in row-major order, per pair the Gram products of gram_block_split6
+// (dl_tiles.h) from the plane arrays of Z and H (split_rows), the rows of the SMALLER endpoint as the A operand — the bits
+// dl_score_topk forms for query u, candidate v.  A candidate is a pair u < v < N outside the exclusion CSR (a 128-bit
+// mask per u row and tile, as in the ranking scan) whose logit reaches the floor; NaN reaches no floor.
+//
+// Selection: a radix select over the 64-bit key  (order key of the logit) << 32 | ~(u N + v)  (keys are distinct; a larger
+// key ranks first).  Up to six HISTOGRAM scans, one per digit (11, 11, 10 bits of the value, then of the index), count the
+// candidates whose higher digits equal the threshold's so far (LDS-private bins, flushed with integer atomics); a
+// one-workgroup kernel picks the digit in which the m-th best key lies.  As soon as the keys with the chosen prefix are
+// exactly the ones still needed (always, once the prefix holds a single key), a device flag ends the search: the
+// remaining histogram scans return at workgroup start.  One EMIT scan appends every candidate at or above the threshold to
+// a key array (exactly count = min(m, candidates) of them, in arbitrary order), and a rank-by-counting kernel puts them
+// in order and writes the outputs and the padding.
+// EVERY scan recomputes the logits with the same instruction stream (scan_tiles below, one body for both modes), and the
+// logit of a pair does not depend on where in a tile its rows sit or on which workgroup forms it: the keys are the same
+// bits in every scan, which is what makes the histograms, the threshold and the emitted set consistent.  Nothing is keyed
+// on a float sum or on an arrival order, so the outputs are the same bits on every call and under every geometry.
+#include <cstddef>
+#include "dl_common.h"
+#include "dl_config.h"
+#include "dl_kernels.h"
+#include "dl_tiles.h"
+
+namespace dl {
+namespace mine {
+
+using namespace project;
+
+constexpr int TT = 128;
+constexpr int MTHR = 512;
+constexpr int SDC = SPLIT_COLS, SLD = SPLIT_PITCH;
+constexpr int BINS = 2048;                 // the widest digit
+constexpr int PASSES = 6;
+constexpr int MAX_M = 65536;
+enum { HIST = 0, EMIT = 1 };
+
+typedef unsigned long long u64;
+
+// the digits of the key, from the top: value 11 + 11 + 10 bits, index 11 + 11 + 10 bits
+__host__ __device__ inline int digit_shift(int p) { return p == 0 ? 53 : p == 1 ? 42 : p == 2 ? 32 : p == 3 ? 21 : p == 4 ? 10 : 0; }
+__host__ __device__ inline int digit_bits(int p) { return (p == 2 || p == 5) ? 10 : 11; }
+
+// dl_score_rank.hip's total order: NaN -> 0, every other value (-0 taken as +0) to its order-preserving image
+__device__ __forceinline__ unsigned ord_key(float x) {
+    if (x != x) return 0u;
+    const unsigned b = __float_as_uint(x == 0.0f ? 0.0f : x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord_value(unsigned o) {
+    if (o == 0u) return __uint_as_float(0x7FC00000u);
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+
+// Selection state in the workspace (device memory; the library's host code never reads it)
+struct State {
+    u64 prefix;            // the threshold key's digits chosen so far, lower bits zero
+    unsigned need;         // keys still to take among those with this prefix
+    unsigned done;         // 1: prefix is the final threshold
+    unsigned count;        // min(m, candidates), once done
+    unsigned emitted;      // EMIT: keys appended
+    unsigned scans;        // scans that ran (a measurement: tools/mine_time.py)
+    unsigned pad;
+};
+
+struct ScanArgs {
+    const __bf16 *cz, *ch;  size_t cbatch;     // planes of Z and H
+    int N, K, nd, nt;  float t;
+    const int32_t *ex_rowptr, *ex_col;
+    float min_logit;
+    int m;
+    int pairs, per_wg;                         // tile pairs, tile pairs per workgroup
+    int pass;                                  // HIST: the digit
+    State* state;  unsigned* hist;  u64* keys;
+};
+
+constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
+constexpr size_t LDS_BYTES = STAGE_BYTES + TT * 4 * 4 + BINS * 4;
+
+template <int MODE>
+__global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
+    __bf16* vs = us + 2 * 3 * TT * SLD;
+    unsigned* exm = reinterpret_cast<unsigned*>(vs + 2 * 3 * TT * SLD);   // [TT][4]: excluded columns of the tile
+    unsigned* bins = exm + TT * 4;                              // HIST: [BINS]
+
+    // device-side state, read at workgroup start: a finished search makes the remaining histogram scans return at once
+    const State S = *A.state;
+    if (MODE == HIST && S.done) return;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if (blockIdx.x == 0 && tid == 0) atomicAdd(&A.state->scans, 1u);
+    const int p0 = (int)blockIdx.x * A.per_wg;
+    const int ntl = max(0, min(A.pairs, p0 + A.per_wg) - p0);
+    if (ntl == 0) return;
+    // tile pair p0 in the row-major order of (qt, ct >= qt)
+    int qt = 0, ct = 0;
+    {
+        int rest = p0;
+        while (rest >= A.nt - qt) {
+            rest -= A.nt - qt;
+            ++qt;
+        }
+        ct = qt + rest;
+    }
+    int qt2 = ct + 1 < A.nt ? qt : qt + 1, ct2 = ct + 1 < A.nt ? ct + 1 : qt + 1;      // the pair after it
+
+    const int li = lane & 31, half = lane >> 5;
+    const int wu = wave >> 1, wv = wave & 1;
+    const int nd = A.nd;
+    const int per_tile = A.K * 2 * nd;
+    const int steps = ntl * per_tile;
+    const int shift = MODE == HIST ? digit_shift(A.pass) : 0;
+    const unsigned dmask = MODE == HIST ? (1u << digit_bits(A.pass)) - 1u : 0u;
+    const int hs = shift + (MODE == HIST ? digit_bits(A.pass) : 0);          // bits below the chosen prefix
+    if constexpr (MODE == HIST)
+        for (int i = tid; i < BINS; i += MTHR) bins[i] = 0u;
+
+    PlaneStage<MTHR, SDC> uq, vq;
+    static_assert(TT == PLANE_ROWS, "tiles of the plane arrays");
+    int jcur = 0;                                               // tile pair (of this workgroup) the products are in
+    auto fetch = [&](int s) {
+        const int j = s / per_tile, rem = s - j * per_tile;
+        const int k = rem / (2 * nd), r = rem - k * 2 * nd;
+        const int dc = r < nd ? r : r - nd;
+        const __bf16* src = (r < nd ? A.cz : A.ch) + (size_t)k * A.cbatch;
+        const int fq = j == jcur ? qt : qt2, fc = j == jcur ? ct : ct2;      // a fetch runs at most one pair ahead
+        uq.fetch(src + plane_tile<SDC>(fq, dc, nd), tid);
+        vq.fetch(src + plane_tile<SDC>(fc, dc, nd), tid);
+    };
+    auto stash = [&](int s) {
+        uq.stash(us + (s & 1) * 3 * TT * SLD, tid);
+        vq.stash(vs + (s & 1) * 3 * TT * SLD, tid);
+    };
+
+    f32x16 acc[2], term[2];
+    float e[2][16];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        zero_acc(acc[b]);
+        zero_acc(term[b]);
+    }
+    fetch(0);
+    stash(0);
+    fetch(min(1, steps - 1));
+    __syncthreads();
+    for (int s = 0; s < steps; ++s) {
+        const int rem = s % per_tile;
+        const int r = rem % (2 * nd);
+        const __bf16* ub = us + (s & 1) * 3 * TT * SLD + (wu * 32 + li) * SLD + half * 8;
+        const __bf16* vb = vs + (s & 1) * 3 * TT * SLD + (wv * 64 + li) * SLD + half * 8;
+#pragma unroll
+        for (int kb = 0; kb < SDC / 16; ++kb) {
+            gram_block_split6(acc, ub, vb, kb);                 // the ranking scan's products (dl_tiles.h)
+            if (kb == 0) {
+                if (s + 1 < steps) stash(s + 1);
+                fetch(min(s + 2, steps - 1));                   // unconditional: see TileStage (dl_tiles.h)
+            }
+        }
+        if (r == nd - 1) {                                      // S complete: e = exp(S / t)
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) e[bb][q] = expf(div_t(acc[bb][q], A.t));
+                zero_acc(acc[bb]);
+            }
+        } else if (r == 2 * nd - 1) {                           // Q complete: term += Q * e
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) term[bb][q] += acc[bb][q] * e[bb][q];
+                zero_acc(acc[bb]);
+            }
+        }
+        __syncthreads();
+        if (rem != per_tile - 1) continue;
+
+        // ---- tile pair complete: term[bb][q] = s(u = qt*128 + wu*32 + acc_row(q, half), v = ct*128 + wv*64 + bb*32 + li)
+        const int u0 = qt * TT, v0 = ct * TT;
+        if (tid < TT) {                                         // this tile's excluded columns of row u0 + tid
+            unsigned* m = exm + tid * 4;
+            m[0] = m[1] = m[2] = m[3] = 0u;
+            const int node = u0 + tid;
+            if (node < A.N && A.ex_rowptr != nullptr) {
+                int lo = A.ex_rowptr[node];
+                const int end = A.ex_rowptr[node + 1];
+                int hi = end;
+                while (lo < hi) {                               // first excluded column >= v0
+                    const int mid = (lo + hi) >> 1;
+                    if (A.ex_col[mid] < v0) lo = mid + 1; else hi = mid;
+                }
+                for (int c = lo; c < end; ++c) {
+                    const int col = A.ex_col[c] - v0;
+                    if (col >= TT) break;
+                    m[col >> 5] |= 1u << (col & 31);
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb) {
+            const int vl = wv * 64 + bb * 32 + li, v = v0 + vl;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int row = wu * 32 + acc_row(q, half), u = u0 + row;
+                const float x = term[bb][q];
+                bool ok = u < v && v < A.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u) && x >= A.min_logit;
+                const u64 key = ((u64)ord_key(x) << 32) | (u64)(0xFFFFFFFFu - ((unsigned)u * (unsigned)A.N + (unsigned)v));
+                if constexpr (MODE == HIST) {
+                    if (hs < 64) ok = ok && (key >> hs) == (S.prefix >> hs);
+                    const unsigned dg = (unsigned)(key >> shift) & dmask;
+                    const u64 act = __ballot(ok);
+                    if (act != 0ull) {                          // wave-uniform: logits cluster, so one bin per wave is common
+                        const int first = __ffsll((long long)act) - 1;
+                        const unsigned d0 = (unsigned)__shfl((int)dg, first, DL_WAVE);
+                        if (__ballot(ok && dg == d0) == act) {
+                            if (lane == first) atomicAdd(&bins[d0], (unsigned)__popcll(act));
+                        } else if (ok) {
+                            atomicAdd(&bins[dg], 1u);
+                        }
+                    }
+                } else {
+                    if (ok && key >= S.prefix) {
+                        const unsigned slot = atomicAdd(&A.state->emitted, 1u);
+                        if (slot < (unsigned)A.m) A.keys[slot] = key;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int bb = 0; bb < 2; ++bb) zero_acc(term[bb]);
+        ++jcur;                                                 // on to the next pair (uniform; fetches are already there)
+        qt = qt2;
+        ct = ct2;
+        qt2 = ct + 1 < A.nt ? qt : qt + 1;
+        ct2 = ct + 1 < A.nt ? ct + 1 : qt + 1;
+    }
+    if constexpr (MODE == HIST) {
+        __syncthreads();
+        for (int i = tid; i < BINS; i += MTHR) {
+            const unsigned c = bins[i];
+            if (c) atomicAdd(&A.hist[i], c);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void init_kernel(State* st, unsigned* hist, int m) {
+    for (int i = threadIdx.x; i < BINS; i += 256) hist[i] = 0u;
+    if (threadIdx.x == 0) {
+        State s = {};
+        s.need = (unsigned)m;
+        *st = s;
+    }
+}
+
+// One workgroup: the digit of pass `pass` in which the need-th best key with the current prefix lies.  Counts are integers
+// and complete (the launch boundary), so the choice is a function of the candidates alone.
+__global__ __launch_bounds__(256) void pick_kernel(State* st, unsigned* hist, int pass, int m) {
+    __shared__ unsigned part[256];
+    __shared__ unsigned chunk[3];                               // all taken?, chunk of the digit, keys above the chunk
+    const int tid = threadIdx.x;
+    const State s0 = *st;
+    if (s0.done) return;
+    const int nb = 1 << digit_bits(pass);
+    constexpr int PER = BINS / 256;
+    unsigned mine[PER], sum = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {                             // thread tid: bins nb-1 - (tid*PER + j), from the top
+        const int b = nb - 1 - (tid * PER + j);
+        mine[j] = b >= 0 ? hist[b] : 0u;
+        sum += mine[j];
+    }
+    part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned total = 0;
+        for (int i = 0; i < 256; ++i) total += part[i];
+        unsigned above = 0;
+        int c = 0;
+        if (total >= s0.need)
+            while (c < 255 && above + part[c] < s0.need) above += part[c++];
+        chunk[0] = total < s0.need ? 1u : 0u;
+        chunk[1] = (unsigned)c;
+        chunk[2] = above;
+    }
+    __syncthreads();
+    if (chunk[0]) {                                             // (first pass only) fewer candidates than m: all of them
+        if (tid == 0) {
+            State s = s0;
+            s.prefix = 0ull;
+            unsigned total = 0;
+            for (int i = 0; i < 256; ++i) total += part[i];
+            s.count = total;
+            s.need = 0;
+            s.done = 1;
+            *st = s;
+        }
+    } else if (tid == (int)chunk[1]) {
+        State s = s0;
+        unsigned above = chunk[2], cnt = 0;
+        int sel = -1;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            if (sel < 0) {
+                if (above + mine[j] >= s.need) {
+                    sel = j;
+                    cnt = mine[j];
+                } else {
+                    above += mine[j];
+                }
+            }
+        }
+        const int b = max(0, nb - 1 - (tid * PER + max(sel, 0)));
+        s.prefix |= (u64)(unsigned)b << digit_shift(pass);
+        s.need -= above;
+        if (cnt == s.need) {                                    // every key with this prefix is taken: the threshold
+            s.done = 1;
+            s.count = (unsigned)m;
+        }
+        *st = s;
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {                             // the next pass counts from zero
+        const int b = nb - 1 - (tid * PER + j);
+        if (b >= 0) hist[b] = 0u;
+    }
+}
+
+// Rank by counting: the emitted keys are distinct, so the ranks are a permutation of [0, count).  Every element of every
+// output is written: thread i < count writes slot rank(i), thread i >= count writes the padding of slot i.
+__global__ __launch_bounds__(256) void order_kernel(const State* st, const u64* __restrict__ keys, int N, int m, int32_t* src,
+                                                    int32_t* dst, float* logit, float* prob, int64_t* count) {
+    __shared__ u64 sm[1024];
+    const int count_ = (int)min(st->count, (unsigned)m);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) count[0] = (int64_t)count_;
+    if ((int)blockIdx.x * 256 >= count_) {                      // a workgroup of padding only (uniform)
+        if (i < m) {
+            src[i] = -1;
+            dst[i] = -1;
+            logit[i] = __uint_as_float(0x7FC00000u);
+            prob[i] = __uint_as_float(0x7FC00000u);
+        }
+        return;
+    }
+    const u64 x = i < count_ ? keys[i] : 0ull;
+    int rank = 0;
+    for (int b = 0; b < count_; b += 1024) {
+        __syncthreads();
+        for (int j = threadIdx.x; j < 1024; j += 256) sm[j] = b + j < count_ ? keys[b + j] : 0ull;
+        __syncthreads();
+#pragma unroll 8
+        for (int j = 0; j < 1024; ++j) rank += sm[j] > x ? 1 : 0;
+    }
+    if (i < count_) {
+        const float val = ord_value((unsigned)(x >> 32));
+        const unsigned pair = 0xFFFFFFFFu - (unsigned)x;
+        src[rank] = (int32_t)(pair / (unsigned)N);
+        dst[rank] = (int32_t)(pair % (unsigned)N);
+        logit[rank] = val;
+        prob[rank] = sigmoid_ref(val);
+    } else if (i < m) {
+        src[i] = -1;
+        dst[i] = -1;
+        logit[i] = __uint_as_float(0x7FC00000u);
+        prob[i] = __uint_as_float(0x7FC00000u);
+    }
+}
+
+}  // namespace mine
+
+using namespace mine;
+
+static int mine_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, c = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+            n = c;
+        if (n <= 0) n = 256;
+    }
+    return n;
+}
+
+// Tile pairs per workgroup: eight workgroups' worth of pairs per CU (one workgroup per CU fits the LDS; short runs keep the
+// tail of the grid short, consecutive pairs of a run share their u tile).  DL_MINE_TILES (test knob) forces the run length;
+// results do not depend on it.
+struct MinePlan { int nd, nt, pairs, per_wg, grid; size_t cbatch; };
+static MinePlan mine_plan(int N, int d) {
+    MinePlan p;
+    p.nd = (d + SDC - 1) / SDC;
+    p.nt = (N + TT - 1) / TT;
+    p.pairs = N >= 2 ? p.nt * (p.nt + 1) / 2 : 0;
+    const int want = config().mine_tiles > 0 ? config().mine_tiles : (p.pairs + 8 * mine_cus() - 1) / (8 * mine_cus());
+    p.per_wg = max(1, min(want, max(1, p.pairs)));
+    p.grid = (p.pairs + p.per_wg - 1) / p.per_wg;
+    p.cbatch = plane_array_elems(N, d, SDC);
+    return p;
+}
+
+bool score_mine_supported(int K, int d) { return score_rank_supported(K, d); }
+
+// out = nd, tiles, tile pairs, tile pairs per workgroup, workgroups of a scan, scans at most (digits + emit), byte offset of
+// the 32-bit count of scans that ran inside the (256-byte aligned) workspace
+void score_mine_form(int N, int d, int m, int* out) {
+    (void)m;
+    const MinePlan p = mine_plan(N, d);
+    out[0] = p.nd;
+    out[1] = p.nt;
+    out[2] = p.pairs;
+    out[3] = p.per_wg;
+    out[4] = p.grid;
+    out[5] = p.pairs > 0 ? PASSES + 1 : 0;
+    out[6] = (int)offsetof(State, scans);
+}
+
+// Workspace (256-byte aligned blocks): selection state | histogram | keys [m] | planes of Z and H
+struct MineWs { State* state; unsigned* hist; u64* keys; __bf16 *cz, *ch; size_t bytes; };
+static MineWs mine_carve(const MinePlan& p, int K, int m, void* ws) {
+    MineWs w = {};
+    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        char* r = base + o;
+        o += (bytes + 255) & ~(size_t)255;
+        return (void*)r;
+    };
+    w.state = (State*)take(sizeof(State));
+    w.hist = (unsigned*)take(sizeof(unsigned) * BINS);
+    w.keys = (u64*)take(sizeof(u64) * (size_t)m);
+    w.cz = (__bf16*)take(2 * (size_t)K * p.cbatch);
+    w.ch = (__bf16*)take(2 * (size_t)K * p.cbatch);
+    w.bytes = o + 256;
+    return w;
+}
+
+size_t score_mine_workspace_bytes(int N, int K, int d, int m) { return mine_carve(mine_plan(N, d), K, m, nullptr).bytes; }
+
+int score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
+               int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws, hipStream_t st) {
+    static unsigned long long lds_hist = 0, lds_emit = 0;
+    const MinePlan p = mine_plan(N, d);
+    const MineWs w = mine_carve(p, K, m, ws);
+    hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, m);
+    if (p.pairs > 0) {
+        split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
+        split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
+        ScanArgs a = {};
+        a.cz = w.cz; a.ch = w.ch; a.cbatch = p.cbatch;
+        a.N = N; a.K = K; a.nd = p.nd; a.nt = p.nt; a.t = t;
+        a.ex_rowptr = exr; a.ex_col = exc;
+        a.min_logit = min_logit;
+        a.m = m;
+        a.pairs = p.pairs; a.per_wg = p.per_wg;
+        a.state = w.state; a.hist = w.hist; a.keys = w.keys;
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<HIST>), LDS_BYTES, lds_hist);
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<EMIT>), LDS_BYTES, lds_emit);
+        for (int pass = 0; pass < PASSES; ++pass) {
+            a.pass = pass;
+            hipLaunchKernelGGL(scan_tiles<HIST>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
+            hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
+        }
+        hipLaunchKernelGGL(scan_tiles<EMIT>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
+    }
+    hipLaunchKernelGGL(order_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.state, w.keys, max(N, 1), m, src, dst,
+                       logit, prob, count);
+    return check_launch("score_mine");
+}
+
+}  // namespace dl

@@ -58,6 +58,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rank-eval", action="store_true",
                    help="after each run, rank every test positive among all nodes (filtered by every dataset edge) and "
                         "print MRR and Hits@{1,10,50,100}")
+    p.add_argument("--mine", type=int, default=0, metavar="M",
+                   help="after the last run, list the M (<= 65536) most likely links of the whole graph that are not dataset "
+                        "edges (Disentangle.top_missing_links; single GPU, fp32 tables)")
+    p.add_argument("--mine-out", type=str, default=None, metavar="FILE",
+                   help="with --mine: write the list to FILE as text, one `src dst logit prob` line per pair")
     p.add_argument("--sparse-features", action="store_true",
                    help="hand the features to the model as features.SparseFeatures (scale * X + shift with X a CSR): layer 1 "
                         "of the projection and its gradient run as gathers over the non-zero entries; for binary / one-hot "
@@ -204,6 +209,21 @@ def rank_eval(model, x, graph, split, known) -> dict:
     return ranking_metrics(greater, ties)
 
 
+def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=print):
+    """--mine: the m most likely links outside ``known`` (Disentangle.top_missing_links), the first ``show`` printed and,
+    with ``out``, all of them written as `src dst logit prob` lines."""
+    mined = model.top_missing_links(x, graph, m, exclude=known)
+    src, dst, logit, prob = (v.cpu().numpy() for v in mined)
+    log(f"mined {src.size} links (of {m} asked for); first {min(show, src.size)}: src dst logit prob")
+    for i in range(min(show, src.size)):
+        log(f"{src[i]} {dst[i]} {logit[i]:.6g} {prob[i]:.6g}")
+    if out:
+        with open(out, "w") as fh:
+            for i in range(src.size):
+                fh.write(f"{src[i]} {dst[i]} {logit[i]:.9g} {prob[i]:.9g}\n")
+    return mined
+
+
 def _fmt_ranking(r: dict) -> str:
     return " ".join(f"{key} {val:.4f}" for key, val in r.items())
 
@@ -228,6 +248,11 @@ def main(argv=None):
         raise SystemExit("--sparse-features runs on one GPU only (the sharded path takes dense feature rows): drop --gpus")
     if args.gpus > 1 and args.rank_eval:
         raise SystemExit("--rank-eval runs on one GPU only (sharded ranking is not implemented): drop --gpus or --rank-eval")
+    if args.mine and (args.gpus > 1 or args.table_dtype == "bf16"):
+        raise SystemExit("--mine runs on one GPU with fp32 tables only (sharded and bf16 mining are not implemented): drop "
+                         "--gpus / --table-dtype bf16 or --mine")
+    if args.mine and not 1 <= args.mine <= 65536:
+        raise SystemExit("--mine M: 1 <= M <= 65536")
     if args.gpus > 1:
         from .launch import launch_ranks, under_launcher
         if not under_launcher():                                    # BEFORE any GPU call: the parent starts and waits
@@ -260,7 +285,7 @@ def main(argv=None):
     tdt = torch.bfloat16 if args.table_dtype == "bf16" else torch.float32
     result = []
     ranking = []
-    if args.rank_eval:                                              # filter: every dataset edge, both directions
+    if args.rank_eval or args.mine:                                 # filter: every dataset edge, both directions
         s_all, d_all = torch.from_numpy(np.asarray(ds.src)).long(), torch.from_numpy(np.asarray(ds.dst)).long()
         known = (torch.cat([s_all, d_all]).to(device), torch.cat([d_all, s_all]).to(device))
     for run in range(args.run):
@@ -280,6 +305,8 @@ def main(argv=None):
             ranking.append(rank_eval(model, x, prepared.graph, split, known))
             if not args.quiet:
                 print("test ranking:", _fmt_ranking(ranking[-1]))
+    if args.mine and args.run > 0:                                  # the last run's model, its best weights
+        mine_links(model, x, prepared.graph, known, args.mine, args.mine_out)
     result = np.array(result)
     if args.rank_eval:                                              # the run means of the ranking metrics join the final line
         print("final", result.mean(), result.std(),

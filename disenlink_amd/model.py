@@ -9,10 +9,12 @@ routing / aggregation / scoring path running on libdisenlink_hip.so.
 For graphs where ``[N,N]`` cannot exist, ``forward_pairs(x, graph, pairs)`` scores a pair
 list instead; the reference has no counterpart for it.  Neither has ranking:
 ``topk_links`` (the k most likely links of query nodes) and ``link_ranks`` (filtered ranks of target pairs among all
-nodes, for MRR / Hits@K) score every candidate on the matrix cores without an ``[N,N]`` tensor.
+nodes, for MRR / Hits@K) score every candidate on the matrix cores without an ``[N,N]`` tensor, and
+``top_missing_links`` mines the m most likely links of the whole graph that are not known yet the same way.
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 from collections import namedtuple
@@ -27,6 +29,7 @@ from .graph import Graph, PairList
 
 
 TopLinks = namedtuple("TopLinks", ["index", "logit", "prob"])
+MinedLinks = namedtuple("MinedLinks", ["src", "dst", "logit", "prob"])
 
 
 class Factor(nn.Module):
@@ -389,3 +392,20 @@ class Disentangle(nn.Module):
         (ops.score_ranks; metrics.ranking_metrics turns them into MRR / Hits@K)."""
         Z, H = self._rank_tables(x, adj)
         return ops.score_ranks(Z, H, float(self.temperature), src, dst, exclude)
+
+    def top_missing_links(self, x, adj, m: int, exclude=None, min_prob=None) -> MinedLinks:
+        """The m most likely links of the WHOLE graph that are not known yet: MinedLinks(src, dst int32 [c], logit, prob
+        f32 [c]) with src < dst, c = min(m, eligible pairs), ranked by the pre-sigmoid logit of link_pred over all
+        unordered pairs (ops.score_mine; nothing of size N x N is formed).  ``exclude``: the known pairs, as a Graph, a
+        dense [N,N] mask or (rows, cols), in either orientation; None = the edges of ``adj`` itself.  ``min_prob``: keep
+        only pairs with link_pred >= min_prob (turned into a logit floor on the host: 0.5 -> 0.0)."""
+        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        Z, H = self._rank_tables(x, graph)
+        floor = float("-inf")
+        if min_prob is not None:
+            p = float(min_prob)
+            if not 0.0 <= p <= 1.0:
+                raise ValueError(f"min_prob={p} outside [0, 1]")
+            floor = float("-inf") if p == 0.0 else float("inf") if p == 1.0 else math.log(p) - math.log1p(-p)
+        with torch.no_grad():
+            return MinedLinks(*ops.score_mine(Z, H, float(self.temperature), m, graph if exclude is None else exclude, floor))

@@ -1356,3 +1356,45 @@ def score_ranks(Z, H, t: float, src, dst, exclude=None):
     greater[order] = g_sorted
     ties[order] = t_sorted
     return greater, ties
+
+
+# ---------------------------------------------------------------------- the graph's most likely missing links (dl_score_mine.hip)
+MINE_MAX_M = 65536
+MINE_MAX_N = 46340
+
+
+def _unordered_exclusion_csr(exclude, N: int, device):
+    """``exclusion_csr`` of an UNORDERED pair set: every listed pair (a, b), in either order, as column max(a, b) of row
+    min(a, b) — the only row dl_score_mine looks in."""
+    rowptr, col = exclusion_csr(exclude, N, device)
+    if rowptr is None:
+        return None, None
+    ptr = rowptr.to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(N, device=ptr.device), ptr[1:] - ptr[:-1])
+    cols = col.to(torch.int64)
+    return exclusion_csr((torch.minimum(rows, cols), torch.maximum(rows, cols)), N, device)
+
+
+def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf")):
+    """-> (src int32 [c], dst int32 [c], logit f32 [c], prob f32 [c]), c = min(m, eligible): the m best unordered pairs
+    src < dst of the WHOLE graph by the logit s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid
+    link_pred), sorted in ``score_topk``'s order (larger first, +inf first, equal logits by src * N + dst), with the bits
+    ``score_topk`` returns for query src, candidate dst.  ``exclude`` (a ``Graph``, a dense [N,N] mask or ``(rows, cols)``)
+    is taken as a set of unordered pairs; a pair is eligible iff its logit is >= ``min_logit`` (NaN never is).
+    1 <= m <= 65,536, N <= 46,340.  Inference only; nothing of size N x N is formed (dl_score_mine), and the one host read
+    is that of the count, at the very end."""
+    lib = _lib.load()
+    Z, H, N, K, d = _rank_tables(Z, H)
+    m = int(m)
+    rp, cp, _keep = _csr_args(*_unordered_exclusion_csr(exclude, N, Z.device), Z.device)
+    src = _empty(max(m, 0), torch.int32, Z.device)
+    dst = _empty(max(m, 0), torch.int32, Z.device)
+    logit = _empty(max(m, 0), torch.float32, Z.device)
+    prob = _empty(max(m, 0), torch.float32, Z.device)
+    count = _empty(1, torch.int64, Z.device)
+    ws = _ws.get(max(256, int(lib.dl_score_mine_workspace_bytes(N, K, d, m))), Z.device)
+    _lib.check(lib.dl_score_mine(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, float(min_logit), m, src.data_ptr(),
+                                 dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), _stream()), "dl_score_mine")
+    c = int(count.item())
+    return src[:c], dst[:c], logit[:c], prob[:c]

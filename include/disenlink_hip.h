@@ -495,6 +495,47 @@ int dl_score_ranks(const float* Z, const float* H, int N, int K, int d, float t,
                    const int32_t* tptr, const int32_t* tdst, int n_targets, const int32_t* ex_rowptr, const int32_t* ex_col,
                    int64_t* greater, int64_t* ties, void* ws, size_t ws_bytes, void* stream);
 
+/* The graph's m most likely missing links (an extension; the reference has no counterpart): the global top-m of the logit
+ * s(u,v) = sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t) over ALL unordered pairs, with nothing of size N x N in memory.
+ * Candidates: the unordered pairs {u, v}, 0 <= u < v < N, each considered once; self pairs never.  Pair (u, v) is
+ * excluded iff v is among the columns of row u of the exclusion CSR (ex_rowptr [N+1], ex_col: int32, ascending columns
+ * per row, the layout dl_score_topk takes; both NULL = nothing excluded).  Only the row of the SMALLER endpoint is looked
+ * at: a caller with an unordered set lists every pair in that row (or symmetrises the set).
+ * Score: on the matrix cores with the three-plane, six-product scheme of the dense scorer, the rows of the smaller
+ * endpoint as the A operand, d padded to a multiple of 32 with zero columns: for every returned pair the logit has the
+ * bits dl_score_topk returns for query u, candidate v.
+ * Eligible: s >= min_logit.  A NaN logit is never eligible, whatever the floor; min_logit = -inf admits everything else,
+ * -inf included.
+ * Result: the first min(m, eligible) eligible candidates in dl_score_topk's total order (a larger logit first, +inf
+ * above every finite value, -0 equal to +0), equal logits by u N + v, the smaller first: src[i] < dst[i] (int32 [m]),
+ * logit[i], prob[i] = sigmoid(logit[i]) (fp32 [m]), sorted; entries i >= count are padded with index -1 and NaN;
+ * count[0] = min(m, eligible) (int64, a DEVICE value: the call reads nothing back, never synchronises and never
+ * allocates).  Every element of every output array is written on every call.
+ * Limits: 1 <= m <= 65536; N <= 46340 (the pair index fits 31 bits, the dense scorer's limit); fp32 tables with
+ * 1 <= d <= 128 (dl_score_mine_supported, as dl_score_topk_supported); anything else fails.  N < 2 succeeds with count = 0.
+ * Method: a radix select over the 64-bit key (order of the logit, then ~(u N + v)): up to six histogram scans of the
+ * tile pairs (u tile <= v tile), one per 10/11-bit digit, each followed by a one-workgroup kernel that picks the digit;
+ * a device flag ends the search as soon as the chosen prefix holds exactly the keys still needed, and the remaining
+ * histogram scans return at once; one emit scan and a sort of the <= m emitted keys.  Every scan recomputes the logits
+ * with the same instruction stream.  Integer atomics only: the outputs are the same bits on every call and do not depend
+ * on how the tile pairs are spread over workgroups (DL_MINE_TILES).
+ * ws: dl_score_mine_workspace_bytes(N, K, d, m) bytes (0 for arguments out of range): the selection state, a histogram,
+ * m 8-byte keys and the planes of Z and H; a missing or short workspace fails with DL_E_WORKSPACE. */
+int dl_score_mine_supported(int K, int d);                 /* fp32 tables, 1 <= d <= 128, as dl_score_topk_supported */
+/* The launch plan for a problem under the current DL_MINE_TILES (host only; without the switch the run length follows
+ * the device's CU count, 256 where no device answers).  out[DL_SCORE_MINE_FORM_LEN] =
+ *   [0] 32-column chunks of the padded factor width  [1] 128-row tiles  [2] tile pairs (u tile <= v tile)
+ *   [3] tile pairs per workgroup  [4] workgroups of a scan  [5] scans at most (six digits and the emit; 0 for N < 2)
+ *   [6] byte offset, from the workspace rounded up to 256 bytes, of the 32-bit count of scans that ran in the last call */
+#define DL_SCORE_MINE_FORM_LEN 7
+int dl_score_mine_form(int N, int K, int d, int m, int* out);
+size_t dl_score_mine_workspace_bytes(int N, int K, int d, int m);
+int dl_score_mine(const float* Z, const float* H, int N, int K, int d, float t,
+                  const int32_t* ex_rowptr, const int32_t* ex_col,      /* known pairs, both NULL = none */
+                  float min_logit, int m,
+                  int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count,
+                  void* ws, size_t ws_bytes, void* stream);
+
 /* Tie-averaged AUC of a score vector against FIXED labels: replaces sklearn.metrics.roc_auc_score at
  * main_disentangled.py:202-204 / 217-219 (validation AUC every epoch, test AUC at the end).  pos_idx / neg_idx
  * (int64, device) are the positions of the positive and negative labels in score, found once per run; the call
