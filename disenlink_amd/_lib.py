@@ -115,6 +115,12 @@ EXPORTS = {
     "dl_score_mine_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "dl_score_mine_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "dl_score_mine": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _i, _P, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_score_pair_ranks_supported": (_i, [_i, _i]),
+    "dl_score_pair_ranks_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "dl_score_pair_logits_workspace_bytes": (_z, [_i, _i, _i]),
+    "dl_score_pair_ranks_workspace_bytes": (_z, [_i, _i, _i]),
+    "dl_score_pair_logits": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _i, _P, _P, _z, _P]),
+    "dl_score_pair_ranks": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
     "dl_auc_pair_counts_supported": (_i, [_i, _i]),
     "dl_auc_pair_counts": (_i, [_P, _P, _i, _P, _i, _P, _P]),
     "dl_auc_pair_counts_add": (_i, [_P, _P, _i, _P, _i, _P, _P]),
@@ -244,6 +250,17 @@ def score_mine_form(N: int, K: int, d: int, m: int) -> dict:
     out = (C.c_int * len(SCORE_MINE_FORM))()
     check(load().dl_score_mine_form(N, K, d, m, out), "dl_score_mine_form")
     return dict(zip(SCORE_MINE_FORM, out))
+
+
+SCORE_PAIR_RANKS_FORM = ("nd", "tiles", "pairs", "pairs_per_wg", "grid", "separators", "targets_per_separator", "lds_levels",
+                         "global_levels")
+
+
+def score_pair_ranks_form(N: int, K: int, d: int, T: int) -> dict:
+    """The counting scan's plan for this problem under the current DL_MINE_TILES (dl_score_pair_ranks_form)."""
+    out = (C.c_int * len(SCORE_PAIR_RANKS_FORM))()
+    check(load().dl_score_pair_ranks_form(N, K, d, T, out), "dl_score_pair_ranks_form")
+    return dict(zip(SCORE_PAIR_RANKS_FORM, out))
 
 
 def config_reload() -> None:

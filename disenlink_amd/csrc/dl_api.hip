@@ -441,6 +441,69 @@ int dl_score_mine(const float* Z, const float* H, int N, int K, int d, float t, 
     return score_mine(Z, H, N, K, d, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws, (hipStream_t)stream);
 }
 
+int dl_score_pair_ranks_supported(int K, int d) { return score_rank_supported(K, d) ? 1 : 0; }
+
+// 128-row tiles whose pair count fits an int32: N <= 65,535 * 128
+static int check_pair_shape(int N, int K, int d) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(score_rank_supported(K, d), "the pair scans serve fp32 tables with 1 <= d <= 128, got d=%d", d);
+    DL_REQUIRE(N >= 1 && N <= DL_SCORE_PAIR_RANKS_MAX_N, "N=%d outside 1..%d (the tile-pair count must fit 31 bits)", N,
+               DL_SCORE_PAIR_RANKS_MAX_N);
+    static_assert((DL_SCORE_PAIR_RANKS_MAX_N / 128LL) * (DL_SCORE_PAIR_RANKS_MAX_N / 128LL + 1) / 2 <= 2147483647LL &&
+                  DL_SCORE_PAIR_RANKS_MAX_N % 128 == 0, "65,535 tiles of 128 rows: 2,147,450,880 tile pairs");
+    DL_REQUIRE((long long)N * K * d < (1LL << 40), "tables too large");
+    return DL_OK;
+}
+
+int dl_score_pair_ranks_form(int N, int K, int d, int n_targets, int* out) {
+    if (int rc = check_pair_shape(N, K, d)) return rc;
+    DL_REQUIRE(out != nullptr && n_targets >= 0, "bad argument");
+    score_pair_ranks_form(N, d, n_targets, out);
+    return DL_OK;
+}
+
+size_t dl_score_pair_logits_workspace_bytes(int N, int K, int d) {
+    if (N < 1 || N > DL_SCORE_PAIR_RANKS_MAX_N || !score_rank_supported(K, d) || (long long)N * K * d >= (1LL << 40)) return 0;
+    return score_pair_logits_workspace_bytes(N, K, d);
+}
+
+size_t dl_score_pair_ranks_workspace_bytes(int N, int K, int d) {
+    if (N < 1 || N > DL_SCORE_PAIR_RANKS_MAX_N || !score_rank_supported(K, d) || (long long)N * K * d >= (1LL << 40)) return 0;
+    return score_pair_ranks_workspace_bytes(N, K, d);
+}
+
+int dl_score_pair_logits(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
+                         int n_pairs, float* logit, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_pair_shape(N, K, d)) return rc;
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    DL_REQUIRE(n_pairs >= 0 && n_pairs <= (1 << 30), "n_pairs=%d outside 0..2^30", n_pairs);
+    if (n_pairs == 0) return DL_OK;
+    DL_REQUIRE(Z && H && a && b && logit, "NULL argument");
+    const size_t need = score_pair_logits_workspace_bytes(N, K, d);
+    if (!ws || ws_bytes < need) {
+        set_error("workspace too small: have %zu, need %zu (dl_score_pair_logits_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
+        return DL_E_WORKSPACE;
+    }
+    return score_pair_logits(Z, H, N, K, d, t, a, b, n_pairs, logit, ws, (hipStream_t)stream);
+}
+
+int dl_score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
+                        const int32_t* ex_col, const uint32_t* target_order, int n_targets, unsigned long long* above,
+                        unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_pair_shape(N, K, d)) return rc;
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    DL_REQUIRE(n_targets >= 0 && n_targets <= (1 << 30), "n_targets=%d outside 0..2^30", n_targets);
+    DL_REQUIRE(Z && H && above && equal && n_candidates && (n_targets == 0 || target_order), "NULL argument");
+    DL_REQUIRE((ex_rowptr == nullptr) == (ex_col == nullptr), "exclusion rowptr and col go together");
+    const size_t need = score_pair_ranks_workspace_bytes(N, K, d);
+    if (!ws || ws_bytes < need) {
+        set_error("workspace too small: have %zu, need %zu (dl_score_pair_ranks_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
+        return DL_E_WORKSPACE;
+    }
+    return score_pair_ranks(Z, H, N, K, d, t, ex_rowptr, ex_col, target_order, n_targets, above, equal, n_candidates, ws,
+                            (hipStream_t)stream);
+}
+
 int dl_auc_pair_counts_supported(int n_pos, int n_neg) {
     return n_pos >= 0 && n_neg >= 0 && auc_counts_supported(n_pos, n_neg) ? 1 : 0;
 }

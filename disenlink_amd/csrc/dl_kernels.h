@@ -58,6 +58,7 @@ void dense_mfma_form(int N, int K, int d, size_t ws_bytes, int* out);
 void dense_bwd_form(int N, int K, int d, int* out);
 void score_topk_form(int N, int d, int Q, int k, int* out);
 void score_mine_form(int N, int d, int m, int* out);
+void score_pair_ranks_form(int N, int d, int T, int* out);
 
 // dense scorer on the matrix cores (dl_score_dense.hip): fp32 tables, d % 32 == 0
 bool dense_mfma_supported(int d);
@@ -87,6 +88,16 @@ size_t score_mine_workspace_bytes(int N, int K, int d, int m);
 int score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
                float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws,
                hipStream_t st);
+
+// logits of given (A row, B row) pairs with the bits of the scans (dl_score_rank.hip), and the global rank counts of sorted
+// target keys among all unordered pairs (dl_score_mine.hip, one counting scan): fp32 tables, 1 <= d <= 128
+size_t score_pair_logits_workspace_bytes(int N, int K, int d);
+int score_pair_logits(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* a, const int32_t* b, int T,
+                      float* logit, void* ws, hipStream_t st);
+size_t score_pair_ranks_workspace_bytes(int N, int K, int d);
+int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
+                     const unsigned* tord, int T, unsigned long long* gcnt, unsigned long long* tcnt, unsigned long long* ncand,
+                     void* ws, hipStream_t st);
 
 // tie-averaged AUC counts (dl_metrics.hip)
 bool auc_counts_supported(int n_pos, int n_neg);           // the smaller class fits the LDS

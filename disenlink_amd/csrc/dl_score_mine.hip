@@ -16,10 +16,18 @@
 // remaining histogram scans return at workgroup start.  One EMIT scan appends every candidate at or above the threshold to
 // a key array (exactly count = min(m, candidates) of them, in arbitrary order), and a rank-by-counting kernel puts them
 // in order and writes the outputs and the padding.
-// EVERY scan recomputes the logits with the same instruction stream (scan_tiles below, one body for both modes), and the
+// EVERY scan recomputes the logits with the same instruction stream (scan_tiles below, one body for all modes), and the
 // logit of a pair does not depend on where in a tile its rows sit or on which workgroup forms it: the keys are the same
 // bits in every scan, which is what makes the histograms, the threshold and the emitted set consistent.  Nothing is keyed
 // on a float sum or on an arrival order, so the outputs are the same bits on every call and under every geometry.
+//
+// Counting (dl_score_pair_ranks, mode COUNT of the same body): where T given target pairs stand among ALL candidates.  The
+// caller passes the targets' order keys in ascending order; every candidate (NaN logits included, no floor) finds lo = the
+// number of target keys strictly below its own — a table of <= SEPS separators in LDS (every stride-th key), then a binary
+// search among the <= stride keys between two separators in global memory — and adds 1 to the 64-bit difference array
+// gcnt[lo] and, if the key at lo equals its own, to tcnt[lo]; candidates below the smallest key add nothing, those above the
+// largest are summed per lane and added once per wave, and a wave whose lanes all found the same place adds once.  ncand
+// receives the number of candidates.  Suffix sums and the correction for the target itself are the caller's (ops.py).
 #include <cstddef>
 #include "dl_common.h"
 #include "dl_config.h"
@@ -37,7 +45,8 @@ constexpr int SDC = SPLIT_COLS, SLD = SPLIT_PITCH;
 constexpr int BINS = 2048;                 // the widest digit
 constexpr int PASSES = 6;
 constexpr int MAX_M = 65536;
-enum { HIST = 0, EMIT = 1 };
+enum { HIST = 0, EMIT = 1, COUNT = 2 };
+constexpr int SEPS = 4096;                 // COUNT: first-level separators of the sorted targets, in LDS
 
 typedef unsigned long long u64;
 
@@ -76,10 +85,25 @@ struct ScanArgs {
     int pairs, per_wg;                         // tile pairs, tile pairs per workgroup
     int pass;                                  // HIST: the digit
     State* state;  unsigned* hist;  u64* keys;
+    // COUNT (dl_score_pair_ranks): the ascending order keys of the T targets, every stride-th of them a separator, and the
+    // 64-bit counters: gcnt [T+1] (difference array of "greater"), tcnt [T+1] (equal range, at its first place), ncand [1]
+    const unsigned* tord;  int T, stride, nsep;
+    u64 *gcnt, *tcnt, *ncand;
 };
 
 constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
 constexpr size_t LDS_BYTES = STAGE_BYTES + TT * 4 * 4 + BINS * 4;
+constexpr size_t LDS_BYTES_COUNT = STAGE_BYTES + TT * 4 * 4 + SEPS * 4;
+static_assert(LDS_BYTES_COUNT <= 160 * 1024, "LDS of a CU");
+
+__device__ __forceinline__ u64 wave_sum(u64 x) {
+#pragma unroll
+    for (int o = DL_WAVE / 2; o > 0; o >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)x, o, DL_WAVE), hi = (unsigned)__shfl_xor((int)(unsigned)(x >> 32), o, DL_WAVE);
+        x += ((u64)hi << 32) | lo;
+    }
+    return x;
+}
 
 template <int MODE>
 __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
@@ -87,7 +111,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
     __bf16* vs = us + 2 * 3 * TT * SLD;
     unsigned* exm = reinterpret_cast<unsigned*>(vs + 2 * 3 * TT * SLD);   // [TT][4]: excluded columns of the tile
-    unsigned* bins = exm + TT * 4;                              // HIST: [BINS]
+    unsigned* bins = exm + TT * 4;                              // HIST: [BINS]; COUNT: [SEPS] separators
 
     // device-side state, read at workgroup start: a finished search makes the remaining histogram scans return at once
     const State S = *A.state;
@@ -95,7 +119,8 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     if (blockIdx.x == 0 && tid == 0) atomicAdd(&A.state->scans, 1u);
     const int p0 = (int)blockIdx.x * A.per_wg;
-    const int ntl = max(0, min(A.pairs, p0 + A.per_wg) - p0);
+    // COUNT serves tile-pair counts close to 2^31, where p0 + per_wg would overflow; the other modes keep their form (N <= 46,340)
+    const int ntl = MODE == COUNT ? max(0, min(A.per_wg, A.pairs - p0)) : max(0, min(A.pairs, p0 + A.per_wg) - p0);
     if (ntl == 0) return;
     // tile pair p0 in the row-major order of (qt, ct >= qt)
     int qt = 0, ct = 0;
@@ -119,6 +144,16 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     const int hs = shift + (MODE == HIST ? digit_bits(A.pass) : 0);          // bits below the chosen prefix
     if constexpr (MODE == HIST)
         for (int i = tid; i < BINS; i += MTHR) bins[i] = 0u;
+    // COUNT: separator j = target j * stride; the smallest and the largest target bound the candidates that need a search
+    unsigned tmin = 0xFFFFFFFFu, tmax = 0u;
+    u64 ncount = 0ull, nabove = 0ull;                           // this lane's candidates, and those above every target
+    if constexpr (MODE == COUNT) {
+        for (int i = tid; i < A.nsep; i += MTHR) bins[i] = A.tord[(size_t)i * A.stride];
+        if (A.T > 0) {
+            tmin = A.tord[0];
+            tmax = A.tord[A.T - 1];
+        }
+    }
 
     PlaneStage<MTHR, SDC> uq, vq;
     static_assert(TT == PLANE_ROWS, "tiles of the plane arrays");
@@ -208,7 +243,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
             for (int q = 0; q < 16; ++q) {
                 const int row = wu * 32 + acc_row(q, half), u = u0 + row;
                 const float x = term[bb][q];
-                bool ok = u < v && v < A.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u) && x >= A.min_logit;
+                bool ok = u < v && v < A.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u) && (MODE == COUNT || x >= A.min_logit);
                 const u64 key = ((u64)ord_key(x) << 32) | (u64)(0xFFFFFFFFu - ((unsigned)u * (unsigned)A.N + (unsigned)v));
                 if constexpr (MODE == HIST) {
                     if (hs < 64) ok = ok && (key >> hs) == (S.prefix >> hs);
@@ -223,10 +258,50 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                             atomicAdd(&bins[dg], 1u);
                         }
                     }
-                } else {
+                } else if constexpr (MODE == EMIT) {
                     if (ok && key >= S.prefix) {
                         const unsigned slot = atomicAdd(&A.state->emitted, 1u);
                         if (slot < (unsigned)A.m) A.keys[slot] = key;
+                    }
+                } else {
+                    // place of the candidate among the sorted targets: lo = targets strictly below it (they count it as
+                    // "greater": +1 at gcnt[lo], summed from the top on the host), and the equal range, if any, starts at lo
+                    const unsigned o = ord_key(x);
+                    ncount += ok ? 1ull : 0ull;
+                    nabove += (ok && o > tmax) ? 1ull : 0ull;
+                    const bool in = ok && o >= tmin && o <= tmax;
+                    int lo = 0;
+                    bool tie = false;
+                    if (in) {
+                        int a = 0, b = A.nsep;                  // separators below o: [0, a)
+                        while (a < b) {
+                            const int mid = (a + b) >> 1;
+                            if (bins[mid] < o) a = mid + 1; else b = mid;
+                        }
+                        if (a > 0) {                            // target (a-1) stride < o <= target a stride (or the end)
+                            int l = (a - 1) * A.stride + 1, h = min(a * A.stride, A.T);
+                            while (l < h) {
+                                const int mid = (l + h) >> 1;
+                                if (A.tord[mid] < o) l = mid + 1; else h = mid;
+                            }
+                            lo = l;
+                        }
+                        tie = A.tord[lo] == o;                  // lo < T: o <= tmax
+                    }
+                    const u64 act = __ballot(in);
+                    if (act != 0ull) {                          // wave-uniform; one place per wave where the logits cluster
+                        const int first = __ffsll((long long)act) - 1;
+                        const int l0 = __shfl(lo, first, DL_WAVE);
+                        if (__ballot(in && lo == l0) == act) {
+                            const u64 eq = __ballot(in && tie);
+                            if (lane == first) {
+                                if (l0 > 0) atomicAdd(&A.gcnt[l0], (u64)__popcll(act));
+                                if (eq != 0ull) atomicAdd(&A.tcnt[l0], (u64)__popcll(eq));
+                            }
+                        } else if (in) {
+                            if (lo > 0) atomicAdd(&A.gcnt[lo], 1ull);
+                            if (tie) atomicAdd(&A.tcnt[lo], 1ull);
+                        }
                     }
                 }
             }
@@ -244,6 +319,14 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         for (int i = tid; i < BINS; i += MTHR) {
             const unsigned c = bins[i];
             if (c) atomicAdd(&A.hist[i], c);
+        }
+    }
+    if constexpr (MODE == COUNT) {                              // one add per wave
+        ncount = wave_sum(ncount);
+        nabove = wave_sum(nabove);
+        if (lane == 0) {
+            if (ncount) atomicAdd(A.ncand, ncount);
+            if (nabove) atomicAdd(&A.gcnt[A.T], nabove);
         }
     }
 }
@@ -394,10 +477,13 @@ static MinePlan mine_plan(int N, int d) {
     MinePlan p;
     p.nd = (d + SDC - 1) / SDC;
     p.nt = (N + TT - 1) / TT;
-    p.pairs = N >= 2 ? p.nt * (p.nt + 1) / 2 : 0;
-    const int want = config().mine_tiles > 0 ? config().mine_tiles : (p.pairs + 8 * mine_cus() - 1) / (8 * mine_cus());
+    // 64-bit: nt (nt + 1) / 2 fits an int32 up to nt = 65,535 (the callers' limit on N), its intermediates do not
+    const long long pairs = N >= 2 ? (long long)p.nt * (p.nt + 1) / 2 : 0;
+    p.pairs = (int)pairs;
+    const long long per_cu = 8LL * mine_cus();
+    const int want = config().mine_tiles > 0 ? config().mine_tiles : (int)((pairs + per_cu - 1) / per_cu);
     p.per_wg = max(1, min(want, max(1, p.pairs)));
-    p.grid = (p.pairs + p.per_wg - 1) / p.per_wg;
+    p.grid = (int)((pairs + p.per_wg - 1) / p.per_wg);
     p.cbatch = plane_array_elems(N, d, SDC);
     return p;
 }
@@ -469,6 +555,88 @@ int score_mine(const float* Z, const float* H, int N, int K, int d, float t, con
     hipLaunchKernelGGL(order_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.state, w.keys, max(N, 1), m, src, dst,
                        logit, prob, count);
     return check_launch("score_mine");
+}
+
+// ---- dl_score_pair_ranks: ONE counting scan (scan_tiles<COUNT>) over the sorted order keys of T target pairs
+struct PairRankPlan { MinePlan m; int stride, nsep, lds_levels, global_levels; };
+static int search_levels(int n) {                               // iterations of a lower-bound search over n elements, at most
+    int l = 0;
+    while (n > 0) {
+        ++l;
+        n >>= 1;
+    }
+    return l;
+}
+static PairRankPlan pair_rank_plan(int N, int d, int T) {
+    PairRankPlan p;
+    p.m = mine_plan(N, d);
+    p.stride = max(1, (T + SEPS - 1) / SEPS);
+    p.nsep = (T + p.stride - 1) / p.stride;
+    p.lds_levels = search_levels(p.nsep);
+    p.global_levels = search_levels(p.stride - 1);
+    return p;
+}
+
+// out = nd, tiles, tile pairs, tile pairs per workgroup, workgroups, separators in LDS, targets per separator, search
+// levels in LDS, search levels in global memory
+void score_pair_ranks_form(int N, int d, int T, int* out) {
+    const PairRankPlan p = pair_rank_plan(N, d, T);
+    out[0] = p.m.nd;
+    out[1] = p.m.nt;
+    out[2] = p.m.pairs;
+    out[3] = p.m.per_wg;
+    out[4] = p.m.grid;
+    out[5] = p.nsep;
+    out[6] = p.stride;
+    out[7] = p.lds_levels;
+    out[8] = p.global_levels;
+}
+
+// Workspace (256-byte aligned blocks): scan state | planes of Z and H
+struct PairRankWs { State* state; __bf16 *cz, *ch; size_t bytes; };
+static PairRankWs pair_rank_carve(const MinePlan& p, int K, void* ws) {
+    PairRankWs w = {};
+    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        char* r = base + o;
+        o += (bytes + 255) & ~(size_t)255;
+        return (void*)r;
+    };
+    w.state = (State*)take(sizeof(State));
+    w.cz = (__bf16*)take(2 * (size_t)K * p.cbatch);
+    w.ch = (__bf16*)take(2 * (size_t)K * p.cbatch);
+    w.bytes = o + 256;
+    return w;
+}
+
+size_t score_pair_ranks_workspace_bytes(int N, int K, int d) { return pair_rank_carve(mine_plan(N, d), K, nullptr).bytes; }
+
+int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
+                     const unsigned* tord, int T, u64* gcnt, u64* tcnt, u64* ncand, void* ws, hipStream_t st) {
+    static unsigned long long lds_count = 0;
+    const PairRankPlan p = pair_rank_plan(N, d, T);
+    const PairRankWs w = pair_rank_carve(p.m, K, ws);
+    hipError_t e = hipMemsetAsync(w.state, 0, sizeof(State), st);
+    if (e == hipSuccess) e = hipMemsetAsync(gcnt, 0, sizeof(u64) * ((size_t)T + 1), st);
+    if (e == hipSuccess) e = hipMemsetAsync(tcnt, 0, sizeof(u64) * ((size_t)T + 1), st);
+    if (e == hipSuccess) e = hipMemsetAsync(ncand, 0, sizeof(u64), st);
+    DL_REQUIRE(e == hipSuccess, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (p.m.pairs > 0) {
+        split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
+        split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
+        ScanArgs a = {};
+        a.cz = w.cz; a.ch = w.ch; a.cbatch = p.m.cbatch;
+        a.N = N; a.K = K; a.nd = p.m.nd; a.nt = p.m.nt; a.t = t;
+        a.ex_rowptr = exr; a.ex_col = exc;
+        a.pairs = p.m.pairs; a.per_wg = p.m.per_wg;
+        a.state = w.state;
+        a.tord = tord; a.T = T; a.stride = p.stride; a.nsep = p.nsep;
+        a.gcnt = gcnt; a.tcnt = tcnt; a.ncand = ncand;
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<COUNT>), LDS_BYTES_COUNT, lds_count);
+        hipLaunchKernelGGL(scan_tiles<COUNT>, dim3((unsigned)p.m.grid), dim3(MTHR), LDS_BYTES_COUNT, st, a);
+    }
+    return check_launch("score_pair_ranks");
 }
 
 }  // namespace dl

@@ -632,4 +632,36 @@ int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, co
     return check_launch("score_ranks");
 }
 
+// ---- dl_score_pair_logits: the DIAG pass on its own, with the plane arrays of Z and H as BOTH sides: pair i = (row a[i] as
+// the A operand, row b[i]), tile i of the pairs against itself, the diagonal kept.  Workspace: planes of Z and H.
+struct PairWs { __bf16 *cz, *ch; size_t cbatch, bytes; };
+static PairWs pair_carve(int N, int K, int d, void* ws) {
+    PairWs w = {};
+    w.cbatch = plane_array_elems(N, d, SDC);
+    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    const size_t one = (2 * (size_t)K * w.cbatch + 255) & ~(size_t)255;
+    w.cz = (__bf16*)base;
+    w.ch = (__bf16*)(base + one);
+    w.bytes = 2 * one + 256;
+    return w;
+}
+
+size_t score_pair_logits_workspace_bytes(int N, int K, int d) { return pair_carve(N, K, d, nullptr).bytes; }
+
+int score_pair_logits(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* a, const int32_t* b, int T,
+                      float* logit, void* ws, hipStream_t st) {
+    static unsigned long long lds_diag = 0;
+    const PairWs w = pair_carve(N, K, d, ws);
+    split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
+    split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
+    ScanArgs g = {};
+    g.qz = w.cz; g.qh = w.ch; g.qbatch = w.cbatch;
+    g.cz = w.cz; g.ch = w.ch; g.cbatch = w.cbatch;
+    g.N = N; g.K = K; g.nd = (d + SDC - 1) / SDC; g.t = t;
+    g.trow = a; g.tdst = b; g.T = T; g.tlogit = logit;
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<DIAG>), LDS_BYTES, lds_diag);
+    hipLaunchKernelGGL(rank_scan_kernel<DIAG>, dim3((unsigned)xcd_grid((T + TT - 1) / TT, 1)), dim3(RTHR), LDS_BYTES, st, g);
+    return check_launch("score_pair_logits");
+}
+
 }  // namespace dl

@@ -58,6 +58,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--rank-eval", action="store_true",
                    help="after each run, rank every test positive among all nodes (filtered by every dataset edge) and "
                         "print MRR and Hits@{1,10,50,100}")
+    p.add_argument("--global-rank-eval", action="store_true",
+                   help="after each run, rank every test positive among ALL unordered pairs of the graph (filtered by every "
+                        "dataset edge) and print the AUC against every non-edge, mean rank, MRR and recall@{100,1000,10000} "
+                        "(Disentangle.missing_link_ranks; single GPU, fp32 tables)")
     p.add_argument("--mine", type=int, default=0, metavar="M",
                    help="after the last run, list the M (<= 65536) most likely links of the whole graph that are not dataset "
                         "edges (Disentangle.top_missing_links; single GPU, fp32 tables)")
@@ -209,6 +213,19 @@ def rank_eval(model, x, graph, split, known) -> dict:
     return ranking_metrics(greater, ties)
 
 
+def global_rank_eval(model, x, graph, split, known) -> dict:
+    """AUC against every non-edge, mean rank, MRR and recall@M of the test positives, each ranked among all unordered
+    pairs of the graph with every known edge filtered out (Disentangle.missing_link_ranks, the model's best weights);
+    self loops among the positives are left out."""
+    from .metrics import global_ranking_metrics
+    pos = split.test.label > 0.5
+    src = torch.from_numpy(np.ascontiguousarray(split.test.u[pos])).to(x.device)
+    dst = torch.from_numpy(np.ascontiguousarray(split.test.v[pos])).to(x.device)
+    keep = src != dst                                               # a self loop of the dataset is no pair of the graph
+    r = model.missing_link_ranks(x, graph, src[keep], dst[keep], exclude=known)
+    return global_ranking_metrics(r.greater, r.ties, r.n_others)
+
+
 def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=print):
     """--mine: the m most likely links outside ``known`` (Disentangle.top_missing_links), the first ``show`` printed and,
     with ``out``, all of them written as `src dst logit prob` lines."""
@@ -248,6 +265,9 @@ def main(argv=None):
         raise SystemExit("--sparse-features runs on one GPU only (the sharded path takes dense feature rows): drop --gpus")
     if args.gpus > 1 and args.rank_eval:
         raise SystemExit("--rank-eval runs on one GPU only (sharded ranking is not implemented): drop --gpus or --rank-eval")
+    if args.global_rank_eval and (args.gpus > 1 or args.table_dtype == "bf16"):
+        raise SystemExit("--global-rank-eval runs on one GPU with fp32 tables only (sharded and bf16 global ranking are not "
+                         "implemented): drop --gpus / --table-dtype bf16 or --global-rank-eval")
     if args.mine and (args.gpus > 1 or args.table_dtype == "bf16"):
         raise SystemExit("--mine runs on one GPU with fp32 tables only (sharded and bf16 mining are not implemented): drop "
                          "--gpus / --table-dtype bf16 or --mine")
@@ -285,7 +305,8 @@ def main(argv=None):
     tdt = torch.bfloat16 if args.table_dtype == "bf16" else torch.float32
     result = []
     ranking = []
-    if args.rank_eval or args.mine:                                 # filter: every dataset edge, both directions
+    global_ranking = []
+    if args.rank_eval or args.mine or args.global_rank_eval:        # filter: every dataset edge, both directions
         s_all, d_all = torch.from_numpy(np.asarray(ds.src)).long(), torch.from_numpy(np.asarray(ds.dst)).long()
         known = (torch.cat([s_all, d_all]).to(device), torch.cat([d_all, s_all]).to(device))
     for run in range(args.run):
@@ -305,14 +326,19 @@ def main(argv=None):
             ranking.append(rank_eval(model, x, prepared.graph, split, known))
             if not args.quiet:
                 print("test ranking:", _fmt_ranking(ranking[-1]))
+        if args.global_rank_eval:
+            global_ranking.append(global_rank_eval(model, x, prepared.graph, split, known))
+            if not args.quiet:
+                print("test global ranking:", _fmt_ranking(global_ranking[-1]))
     if args.mine and args.run > 0:                                  # the last run's model, its best weights
         mine_links(model, x, prepared.graph, known, args.mine, args.mine_out)
     result = np.array(result)
-    if args.rank_eval:                                              # the run means of the ranking metrics join the final line
-        print("final", result.mean(), result.std(),
-              _fmt_ranking({key: float(np.mean([r[key] for r in ranking])) for key in ranking[0]}))
-    else:
-        print("final", result.mean(), result.std())
+    tail = []                                                       # the run means of the ranking metrics join the final line
+    if args.rank_eval:
+        tail.append(_fmt_ranking({key: float(np.mean([r[key] for r in ranking])) for key in ranking[0]}))
+    if args.global_rank_eval:
+        tail.append(_fmt_ranking({key: float(np.mean([r[key] for r in global_ranking])) for key in global_ranking[0]}))
+    print("final", result.mean(), result.std(), *tail)
     if args.save == 1:                                              # :225-246
         save_results(args, result)
     return result

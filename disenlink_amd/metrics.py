@@ -7,6 +7,8 @@
                   i.e. Mann-Whitney U with tie-averaged ranks; computed with torch ops on the device so
                   the per-epoch device->host copy of all validation scores disappears.
   ranking_metrics MRR and Hits@K of filtered ranks (ops.score_ranks); an extension, the reference has none.
+  global_ranking_metrics  AUC against every non-edge, mean rank, MRR and recall@M of ranks among ALL pairs of the graph
+                  (ops.score_pair_ranks); an extension, the reference has none.
 """
 from __future__ import annotations
 
@@ -199,4 +201,26 @@ def ranking_metrics(greater, ties, ks=(1, 10, 50, 100)) -> dict:
     out["mrr"] = float((1.0 / rank).mean())
     for k in ks:
         out[f"hits@{int(k)}"] = float((rank <= k).to(torch.float64).mean())
+    return out
+
+
+def global_ranking_metrics(greater, ties, n_others, ms=(100, 1000, 10000)) -> dict:
+    """{"auc_all", "mean_rank", "mrr", "recall@M"} of targets ranked among all pairs of the graph (ops.score_pair_ranks),
+    rank = 1 + greater + ties / 2:  auc_all = 1 - mean((greater + ties / 2) / n_others), the tie-averaged AUC of the
+    targets against EVERY other candidate pair; recall@M = the share of targets with rank <= M, i.e. found by reviewing
+    the M best pairs.  A target with no other candidate (n_others = 0) counts as perfectly ranked.  NaN for no targets."""
+    g = torch.as_tensor(greater).reshape(-1).to(torch.float64)
+    t = torch.as_tensor(ties).reshape(-1).to(torch.float64)
+    n = torch.as_tensor(n_others).reshape(-1).to(torch.float64)
+    if not g.numel() == t.numel() == n.numel():
+        raise ValueError("greater, ties and n_others differ in length")
+    keys = ["auc_all", "mean_rank", "mrr"] + [f"recall@{int(m)}" for m in ms]
+    if g.numel() == 0:
+        return {k: float("nan") for k in keys}
+    below = g + t / 2.0
+    rank = 1.0 + below
+    out = {"auc_all": float(1.0 - (below / n.clamp(min=1.0)).mean()), "mean_rank": float(rank.mean()),
+           "mrr": float((1.0 / rank).mean())}
+    for m in ms:
+        out[f"recall@{int(m)}"] = float((rank <= m).to(torch.float64).mean())
     return out

@@ -30,6 +30,7 @@ from .graph import Graph, PairList
 
 TopLinks = namedtuple("TopLinks", ["index", "logit", "prob"])
 MinedLinks = namedtuple("MinedLinks", ["src", "dst", "logit", "prob"])
+PairRanks = namedtuple("PairRanks", ["greater", "ties", "logit", "n_others"])
 
 
 class Factor(nn.Module):
@@ -409,3 +410,14 @@ class Disentangle(nn.Module):
             floor = float("-inf") if p == 0.0 else float("inf") if p == 1.0 else math.log(p) - math.log1p(-p)
         with torch.no_grad():
             return MinedLinks(*ops.score_mine(Z, H, float(self.temperature), m, graph if exclude is None else exclude, floor))
+
+    def missing_link_ranks(self, x, adj, src, dst, exclude=None) -> PairRanks:
+        """Where the unordered pairs {src[i], dst[i]} stand among ALL unordered pairs of the graph, in the order
+        ``top_missing_links`` lists from the top: PairRanks(greater, ties int64 [T], logit f32 [T], n_others int64 [T])
+        (ops.score_pair_ranks: one target pass and one scan, nothing of size N x N; metrics.global_ranking_metrics turns
+        them into the AUC against every non-edge, MRR and recall@M).  ``exclude``: the pairs that are no candidates, as
+        in ``top_missing_links``; None = the edges of ``adj``.  A target is ranked whether or not it is excluded."""
+        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        Z, H = self._rank_tables(x, graph)
+        with torch.no_grad():
+            return PairRanks(*ops.score_pair_ranks(Z, H, float(self.temperature), src, dst, graph if exclude is None else exclude))

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 
@@ -1398,3 +1399,112 @@ def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-
                                  ws.numel(), _stream()), "dl_score_mine")
     c = int(count.item())
     return src[:c], dst[:c], logit[:c], prob[:c]
+
+
+# ---------------------------------------------------------------------- where given pairs stand among ALL pairs (COUNT scan)
+def _order_keys(logit: torch.Tensor) -> torch.Tensor:
+    """The scans' total order of fp32 values as int64 keys in [0, 2^32): NaN -> 0, -0 as +0, larger value = larger key."""
+    x = torch.where(logit == 0, torch.zeros_like(logit), logit)
+    b = x.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    key = torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b + 0x80000000)
+    return torch.where(torch.isnan(logit), torch.zeros_like(key), key)
+
+
+PairExclusion = namedtuple("PairExclusion", ["n_nodes", "rowptr", "col", "key", "n_pairs"])
+
+
+def pair_exclusion(exclude, N: int, device) -> PairExclusion:
+    """An exclusion set normalised once for ``score_pair_ranks`` (a caller with a fixed graph passes the result as
+    ``exclude`` and skips the normalisation per call): the CSR of ``_unordered_exclusion_csr``, its sorted pair keys
+    u * N + v and the int64 [1] number of pairs u < v among them ((u, u) entries exclude nothing)."""
+    rowptr, col = _unordered_exclusion_csr(exclude, N, device)
+    if rowptr is None:
+        return PairExclusion(N, None, None, None, torch.zeros(1, dtype=torch.int64, device=device))
+    ptr = rowptr.to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(N, device=ptr.device), ptr[1:] - ptr[:-1])
+    cols = col.to(torch.int64)
+    return PairExclusion(N, rowptr, col, rows * N + cols, (cols > rows).sum().reshape(1))
+
+
+def score_pair_logits(Z, H, t: float, a, b):
+    """-> logit f32 [P]: s(a[i], b[i]) with row a[i] as the A operand, from the products of the scans — the bits
+    ``score_topk`` returns for query a[i], candidate b[i] (dl_score_pair_logits; a -0 comes back as +0, as the keyed
+    outputs of ``score_topk`` and ``score_mine`` report it)."""
+    lib = _lib.load()
+    Z, H, N, K, d = _rank_tables(Z, H)
+    a = _node_ids(a, N, Z.device, "a")
+    b = _node_ids(b, N, Z.device, "b")
+    if a.numel() != b.numel():
+        raise ValueError("a and b differ in length")
+    P = int(a.numel())
+    logit = _empty(P, torch.float32, Z.device)
+    if P == 0:
+        return logit
+    ws = _ws.get(max(256, int(lib.dl_score_pair_logits_workspace_bytes(N, K, d))), Z.device)
+    _lib.check(lib.dl_score_pair_logits(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), a.data_ptr(), b.data_ptr(), P,
+                                        logit.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "dl_score_pair_logits")
+    return torch.where(logit == 0, torch.zeros_like(logit), logit)
+
+
+def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None):
+    """The hook of the tests and of tools/pair_rank_time.py, not part of the interface: ``score_pair_ranks`` and, as a fifth
+    value, the int64 [1] DEVICE count of the candidates the scan counted, which equals N (N - 1) / 2 - |excluded pairs| (the
+    one exact check that works where nothing can be enumerated)."""
+    lib = _lib.load()
+    Z, H, N, K, d = _rank_tables(Z, H)
+    dev = Z.device
+    s = _node_ids(src, N, dev, "src")
+    v = _node_ids(dst, N, dev, "dst")
+    if s.numel() != v.numel():
+        raise ValueError("src and dst differ in length")
+    if bool((s == v).any()):
+        raise ValueError("a target is a self pair (src[i] == dst[i])")
+    T = int(s.numel())
+    ex = exclude if isinstance(exclude, PairExclusion) else pair_exclusion(exclude, N, dev)
+    if ex.n_nodes != N:
+        raise ValueError(f"exclusion set of {ex.n_nodes} nodes, expected {N}")
+    rowptr, col, ex_key = ex.rowptr, ex.col, ex.key
+    total = N * (N - 1) // 2 - ex.n_pairs
+    if T == 0:
+        e = torch.zeros(0, dtype=torch.int64, device=dev)
+        return e, e.clone(), torch.zeros(0, dtype=torch.float32, device=dev), e.clone(), total
+    lo, hi = torch.minimum(s, v).contiguous(), torch.maximum(s, v).contiguous()
+    logit = score_pair_logits(Z, H, t, lo, hi)                        # the smaller endpoint as the A operand
+    key = _order_keys(logit)
+    ksorted, order = torch.sort(key, stable=True)
+    first = torch.searchsorted(ksorted, ksorted)                      # first place of each target's value
+    tord = torch.where(ksorted >= 0x80000000, ksorted - 0x100000000, ksorted).to(torch.int32).contiguous()      # uint32 bits
+    above = _empty(T + 1, torch.int64, dev)
+    equal = _empty(T + 1, torch.int64, dev)
+    counted = _empty(1, torch.int64, dev)
+    rp, cp, _keep = _csr_args(rowptr, col, dev)
+    ws = _ws.get(max(256, int(lib.dl_score_pair_ranks_workspace_bytes(N, K, d))), dev)
+    _lib.check(lib.dl_score_pair_ranks(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, tord.data_ptr(), T,
+                                       above.data_ptr(), equal.data_ptr(), counted.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream()), "dl_score_pair_ranks")
+    cs = torch.cumsum(above, dim=0)
+    g_sorted = cs[T] - cs[:T]                                         # candidates that found more than p targets below them
+    t_sorted = equal[first]
+    in_c = torch.ones(T, dtype=torch.int64, device=dev)               # the target itself is a candidate unless excluded
+    if rowptr is not None and ex_key.numel():
+        tkey = lo.to(torch.int64) * N + hi.to(torch.int64)
+        pos = torch.searchsorted(ex_key, tkey).clamp_(max=ex_key.numel() - 1)
+        in_c = (ex_key[pos] != tkey).to(torch.int64)
+    greater = torch.empty(T, dtype=torch.int64, device=dev)
+    ties = torch.empty(T, dtype=torch.int64, device=dev)
+    greater[order] = g_sorted
+    ties[order] = t_sorted
+    return greater, ties - in_c, logit, total - in_c, counted
+
+
+def score_pair_ranks(Z, H, t: float, src, dst, exclude=None):
+    """-> (greater int64, ties int64, logit f32, n_others int64), each [T]: where the unordered target pairs
+    {src[i], dst[i]} (either orientation; duplicates allowed; no self pairs) stand among ALL unordered pairs u < v < N of
+    the graph outside ``exclude`` (a set of unordered pairs, as in ``score_mine``, or a prepared ``pair_exclusion``).  logit[i] is formed with the smaller
+    endpoint as the A operand (the bits ``score_mine`` lists); greater / ties count the candidates other than the target
+    itself whose logit is strictly above / equal by value (+inf above everything finite, -0 equal to +0, NaN below
+    everything and equal only to NaN).  The filtered protocol of ``score_ranks``: a target is ranked whether or not it is
+    excluded, other targets count as candidates unless excluded.  n_others[i] = candidates - [target i is one], so
+    greater + ties <= n_others; rank = 1 + greater + ties / 2 (metrics.global_ranking_metrics).  Inference only; one
+    target pass and ONE scan (dl_score_pair_logits, dl_score_pair_ranks), nothing of size N x N, no cap at N = 46,340."""
+    return score_pair_ranks_counted(Z, H, t, src, dst, exclude)[:4]

@@ -536,6 +536,50 @@ int dl_score_mine(const float* Z, const float* H, int N, int K, int d, float t,
                   int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count,
                   void* ws, size_t ws_bytes, void* stream);
 
+/* Global rank counts of target pairs among ALL unordered pairs of the graph (an extension; the reference has no
+ * counterpart): where T given pairs stand in the order dl_score_mine lists from the top, with nothing of size N x N in
+ * memory and no cap on N other than the tile-pair count (N <= 8,388,480) and N K d < 2^40.  Two calls:
+ *
+ * dl_score_pair_logits (an extension; the reference has no counterpart): logit[i] = s(a[i], b[i]) for n_pairs given pairs
+ * (int32 node ids in [0, N), not checked), row a[i] as the A operand, from the products of the scans: the bits
+ * dl_score_topk returns for query a[i], candidate b[i], and dl_score_mine lists for a[i] < b[i] (except that a -0 is
+ * written as it is, where those two report +0: their outputs are rebuilt from order keys).  Useful alone: "score these
+ * pairs with the bits of the scans".  ws: dl_score_pair_logits_workspace_bytes(N, K, d): the planes of Z and H.
+ *
+ * dl_score_pair_ranks (an extension; the reference has no counterpart): ONE scan of the tile pairs of dl_score_mine (the
+ * same walk, staging, products and exclusion mask: pair (u, v), u < v, is a candidate iff v is not among the columns of
+ * row u of the exclusion CSR; NaN logits ARE candidates here).  target_order [n_targets]: the order keys of the target
+ * logits, ASCENDING, where the key of x is 0 for NaN and otherwise b ^ 0x80000000 for b >= 0, ~b for b < 0 (b = the bits
+ * of x, -0 taken as +0): larger value = larger key, NaN below everything and equal only to NaN.  Every candidate finds
+ * lo = the number of target keys strictly below its own (a separator table of <= 4,096 keys in LDS, then a binary search
+ * in target_order) and adds 1 to above[lo] (lo > 0) and, if target_order[lo] equals its key, to equal[lo]:
+ *   above [n_targets + 1]: candidates strictly above sorted target p = sum of above[p + 1 .. n_targets]
+ *   equal [n_targets + 1]: candidates with the key of sorted target p = equal[first place of that key]
+ *   n_candidates [1]     : candidates counted = N (N - 1) / 2 - entries (u, v > u) of the exclusion CSR
+ * (64-bit DEVICE values; the call zeroes them itself).  A target that is a candidate counts itself once in its equal
+ * range: the caller subtracts it.  Integer atomics only: the same bits on every call and under every DL_MINE_TILES.
+ * ws: dl_score_pair_ranks_workspace_bytes(N, K, d) (0 for arguments out of range); a short workspace fails with
+ * DL_E_WORKSPACE.  No allocation, no synchronisation, no host read; the caller's stream. */
+int dl_score_pair_ranks_supported(int K, int d);           /* fp32 tables, 1 <= d <= 128, as dl_score_topk_supported */
+/* The launch plan under the current DL_MINE_TILES (host only; an extension, the reference has no counterpart).
+ * out[DL_SCORE_PAIR_RANKS_FORM_LEN] =
+ *   [0] 32-column chunks of the padded factor width  [1] 128-row tiles  [2] tile pairs  [3] tile pairs per workgroup
+ *   [4] workgroups  [5] separators in LDS  [6] targets per separator  [7] search levels in LDS, at most
+ *   [8] search levels in global memory, at most */
+#define DL_SCORE_PAIR_RANKS_FORM_LEN 9
+#define DL_SCORE_PAIR_RANKS_MAX_N 8388480     /* 65,535 tiles of 128 rows: 2,147,450,880 tile pairs, the most an int32 holds */
+int dl_score_pair_ranks_form(int N, int K, int d, int n_targets, int* out);
+size_t dl_score_pair_logits_workspace_bytes(int N, int K, int d);
+size_t dl_score_pair_ranks_workspace_bytes(int N, int K, int d);
+int dl_score_pair_logits(const float* Z, const float* H, int N, int K, int d, float t,
+                         const int32_t* a, const int32_t* b, int n_pairs, float* logit,
+                         void* ws, size_t ws_bytes, void* stream);
+int dl_score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t,
+                        const int32_t* ex_rowptr, const int32_t* ex_col,      /* excluded pairs, both NULL = none */
+                        const uint32_t* target_order, int n_targets,
+                        unsigned long long* above, unsigned long long* equal, unsigned long long* n_candidates,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* Tie-averaged AUC of a score vector against FIXED labels: replaces sklearn.metrics.roc_auc_score at
  * main_disentangled.py:202-204 / 217-219 (validation AUC every epoch, test AUC at the end).  pos_idx / neg_idx
  * (int64, device) are the positions of the positive and negative labels in score, found once per run; the call
