@@ -59,10 +59,15 @@ class DlSparseFeatures(C.Structure):
                 ("seg_len", C.c_int32), ("n_seg", C.c_int32), ("colseg", C.c_void_p), ("seg_col", C.c_void_p)]
 
 
+class DlNodeFilter(C.Structure):
+    _fields_ = [("group", C.c_void_p), ("n_groups", C.c_int32), ("allow", C.c_void_p)]
+
+
 _P = C.c_void_p          # device pointers travel as integers
 _G, _I = C.POINTER(DlGraph), C.POINTER(DlPairIncidence)
 _i, _f, _z = C.c_int, C.c_float, C.c_size_t
 _S = C.POINTER(DlSparseFeatures)
+_NF = C.POINTER(DlNodeFilter)
 EXPORTS = {
     # name: (restype, argtypes) -- one entry per symbol declared in include/disenlink_hip.h
     "dl_host_csr_from_edges": (_i, [_P, _P, C.c_int64, C.c_int32, _i, C.POINTER(DlHostCsr)]),
@@ -121,6 +126,10 @@ EXPORTS = {
     "dl_score_pair_ranks_workspace_bytes": (_z, [_i, _i, _i]),
     "dl_score_pair_logits": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _i, _P, _P, _z, _P]),
     "dl_score_pair_ranks": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
+    "dl_score_topk_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _i, _P, _P, _i, _P, _P, _P, _P, _z, _P, _NF]),
+    "dl_score_ranks_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P, _z, _P, _NF]),
+    "dl_score_mine_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _i, _P, _P, _P, _P, _P, _P, _z, _P, _NF]),
+    "dl_score_pair_ranks_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _i, _P, _P, _P, _P, _z, _P, _NF]),
     "dl_auc_pair_counts_supported": (_i, [_i, _i]),
     "dl_auc_pair_counts": (_i, [_P, _P, _i, _P, _i, _P, _P]),
     "dl_auc_pair_counts_add": (_i, [_P, _P, _i, _P, _i, _P, _P]),

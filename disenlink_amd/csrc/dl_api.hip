@@ -374,10 +374,26 @@ static int check_rank_args(const void* Z, const void* H, int N, int K, int d, fl
     return DL_OK;
 }
 
+// a node-group rule (NULL = none): host-side checks only, the arrays are device memory
+static int check_filter(const dl_node_filter* f) {
+    if (f == nullptr) return DL_OK;
+    DL_REQUIRE(f->n_groups >= 1 && f->n_groups <= 64, "node filter: n_groups=%d outside 1..64", f->n_groups);
+    DL_REQUIRE(f->group != nullptr && f->allow != nullptr, "node filter: NULL group or allow array");
+    return DL_OK;
+}
+
 int dl_score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries, int k,
                   const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index, float* logit, float* prob,
                   void* ws, size_t ws_bytes, void* stream) {
+    return dl_score_topk_filtered(Z, H, N, K, d, t, queries, n_queries, k, ex_rowptr, ex_col, exclude_self, index, logit, prob, ws,
+                                  ws_bytes, stream, nullptr);
+}
+
+int dl_score_topk_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
+                           int k, const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index, float* logit,
+                           float* prob, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter) {
     if (int rc = check_rank_args(Z, H, N, K, d, t, queries, n_queries, ex_rowptr, ex_col)) return rc;
+    if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(k >= 1 && k <= 128, "k=%d outside 1..128", k);
     if (n_queries == 0) return DL_OK;
     DL_REQUIRE(index && logit && prob, "NULL output");
@@ -385,13 +401,22 @@ int dl_score_topk(const float* Z, const float* H, int N, int K, int d, float t, 
     DL_REQUIRE(ws != nullptr && ws_bytes >= need, "workspace too small: %zu < %zu bytes (dl_score_topk_workspace_bytes)",
                ws ? ws_bytes : (size_t)0, need);
     return score_topk(Z, H, N, K, d, t, queries, n_queries, k, ex_rowptr, ex_col, exclude_self, index, logit, prob, ws,
-                      (hipStream_t)stream);
+                      (hipStream_t)stream, filter);
 }
 
 int dl_score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
                    const int32_t* tptr, const int32_t* tdst, int n_targets, const int32_t* ex_rowptr, const int32_t* ex_col,
                    int64_t* greater, int64_t* ties, void* ws, size_t ws_bytes, void* stream) {
+    return dl_score_ranks_filtered(Z, H, N, K, d, t, queries, n_queries, tptr, tdst, n_targets, ex_rowptr, ex_col, greater, ties,
+                                   ws, ws_bytes, stream, nullptr);
+}
+
+int dl_score_ranks_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
+                            const int32_t* tptr, const int32_t* tdst, int n_targets, const int32_t* ex_rowptr,
+                            const int32_t* ex_col, int64_t* greater, int64_t* ties, void* ws, size_t ws_bytes, void* stream,
+                            const dl_node_filter* filter) {
     if (int rc = check_rank_args(Z, H, N, K, d, t, queries, n_queries, ex_rowptr, ex_col)) return rc;
+    if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(n_targets >= 0, "negative size");
     if (n_queries == 0 || n_targets == 0) return DL_OK;
     DL_REQUIRE(tptr && tdst && greater && ties, "NULL argument");
@@ -400,7 +425,7 @@ int dl_score_ranks(const float* Z, const float* H, int N, int K, int d, float t,
     DL_REQUIRE(ws != nullptr && ws_bytes >= need, "workspace too small: %zu < %zu bytes (dl_score_topk_workspace_bytes)",
                ws ? ws_bytes : (size_t)0, need);
     return score_ranks(Z, H, N, K, d, t, queries, n_queries, tptr, tdst, n_targets, ex_rowptr, ex_col, greater, ties, ws,
-                       (hipStream_t)stream);
+                       (hipStream_t)stream, filter);
 }
 
 int dl_score_mine_supported(int K, int d) { return score_mine_supported(K, d) ? 1 : 0; }
@@ -428,7 +453,15 @@ size_t dl_score_mine_workspace_bytes(int N, int K, int d, int m) {
 int dl_score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
                   float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws,
                   size_t ws_bytes, void* stream) {
+    return dl_score_mine_filtered(Z, H, N, K, d, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws, ws_bytes,
+                                  stream, nullptr);
+}
+
+int dl_score_mine_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
+                           const int32_t* ex_col, float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob,
+                           int64_t* count, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter) {
     if (int rc = check_mine_shape(N, K, d, m)) return rc;
+    if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     DL_REQUIRE(N == 0 || (Z && H), "NULL argument");
     DL_REQUIRE((ex_rowptr == nullptr) == (ex_col == nullptr), "exclusion rowptr and col go together");
@@ -438,7 +471,8 @@ int dl_score_mine(const float* Z, const float* H, int N, int K, int d, float t, 
         set_error("workspace too small: have %zu, need %zu (dl_score_mine_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
         return DL_E_WORKSPACE;
     }
-    return score_mine(Z, H, N, K, d, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws, (hipStream_t)stream);
+    return score_mine(Z, H, N, K, d, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws, (hipStream_t)stream,
+                      filter);
 }
 
 int dl_score_pair_ranks_supported(int K, int d) { return score_rank_supported(K, d) ? 1 : 0; }
@@ -490,7 +524,16 @@ int dl_score_pair_logits(const float* Z, const float* H, int N, int K, int d, fl
 int dl_score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
                         const int32_t* ex_col, const uint32_t* target_order, int n_targets, unsigned long long* above,
                         unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes, void* stream) {
+    return dl_score_pair_ranks_filtered(Z, H, N, K, d, t, ex_rowptr, ex_col, target_order, n_targets, above, equal, n_candidates,
+                                        ws, ws_bytes, stream, nullptr);
+}
+
+int dl_score_pair_ranks_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
+                                 const int32_t* ex_col, const uint32_t* target_order, int n_targets, unsigned long long* above,
+                                 unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes,
+                                 void* stream, const dl_node_filter* filter) {
     if (int rc = check_pair_shape(N, K, d)) return rc;
+    if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     DL_REQUIRE(n_targets >= 0 && n_targets <= (1 << 30), "n_targets=%d outside 0..2^30", n_targets);
     DL_REQUIRE(Z && H && above && equal && n_candidates && (n_targets == 0 || target_order), "NULL argument");
@@ -501,7 +544,7 @@ int dl_score_pair_ranks(const float* Z, const float* H, int N, int K, int d, flo
         return DL_E_WORKSPACE;
     }
     return score_pair_ranks(Z, H, N, K, d, t, ex_rowptr, ex_col, target_order, n_targets, above, equal, n_candidates, ws,
-                            (hipStream_t)stream);
+                            (hipStream_t)stream, filter);
 }
 
 int dl_auc_pair_counts_supported(int n_pos, int n_neg) {

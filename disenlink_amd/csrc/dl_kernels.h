@@ -77,17 +77,17 @@ bool score_rank_supported(int K, int d);
 size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T);
 int score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, int k,
                const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index, float* logit, float* prob,
-               void* ws, hipStream_t st);
+               void* ws, hipStream_t st, const dl_node_filter* filter = nullptr);       // filter: checked by the caller
 int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, const int32_t* tptr,
                 const int32_t* tdst, int T, const int32_t* ex_rowptr, const int32_t* ex_col, int64_t* greater, int64_t* ties,
-                void* ws, hipStream_t st);
+                void* ws, hipStream_t st, const dl_node_filter* filter = nullptr);
 
 // global top-m of the logits of all unordered pairs on the matrix cores (dl_score_mine.hip): fp32 tables, 1 <= d <= 128
 bool score_mine_supported(int K, int d);
 size_t score_mine_workspace_bytes(int N, int K, int d, int m);
 int score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
                float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws,
-               hipStream_t st);
+               hipStream_t st, const dl_node_filter* filter = nullptr);
 
 // logits of given (A row, B row) pairs with the bits of the scans (dl_score_rank.hip), and the global rank counts of sorted
 // target keys among all unordered pairs (dl_score_mine.hip, one counting scan): fp32 tables, 1 <= d <= 128
@@ -97,7 +97,7 @@ int score_pair_logits(const float* Z, const float* H, int N, int K, int d, float
 size_t score_pair_ranks_workspace_bytes(int N, int K, int d);
 int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
                      const unsigned* tord, int T, unsigned long long* gcnt, unsigned long long* tcnt, unsigned long long* ncand,
-                     void* ws, hipStream_t st);
+                     void* ws, hipStream_t st, const dl_node_filter* filter = nullptr);
 
 // tie-averaged AUC counts (dl_metrics.hip)
 bool auc_counts_supported(int n_pos, int n_neg);           // the smaller class fits the LDS

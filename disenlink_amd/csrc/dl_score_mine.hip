@@ -28,6 +28,9 @@
 // gcnt[lo] and, if the key at lo equals its own, to tcnt[lo]; candidates below the smallest key add nothing, those above the
 // largest are summed per lane and added once per wave, and a wave whose lanes all found the same place adds once.  ncand
 // receives the number of candidates.  Suffix sums and the correction for the target itself are the caller's (ops.py).
+//
+// Node groups (the FILT instantiations; dl_score_mine_filtered, dl_score_pair_ranks_filtered): a symmetric rule on the groups
+// of u and v, formed into the row mask ahead of the exclusion; a candidate passes both.  The epilogues do not change.
 #include <cstddef>
 #include "dl_common.h"
 #include "dl_config.h"
@@ -89,12 +92,13 @@ struct ScanArgs {
     // 64-bit counters: gcnt [T+1] (difference array of "greater"), tcnt [T+1] (equal range, at its first place), ncand [1]
     const unsigned* tord;  int T, stride, nsep;
     u64 *gcnt, *tcnt, *ncand;
+    FilterArgs filt;                           // FILT: the node-group rule (dl_tiles.h); symmetric, so the u row decides
 };
 
 constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
 constexpr size_t LDS_BYTES = STAGE_BYTES + TT * 4 * 4 + BINS * 4;
 constexpr size_t LDS_BYTES_COUNT = STAGE_BYTES + TT * 4 * 4 + SEPS * 4;
-static_assert(LDS_BYTES_COUNT <= 160 * 1024, "LDS of a CU");
+static_assert(LDS_BYTES % 16 == 0 && LDS_BYTES_COUNT % 16 == 0 && LDS_BYTES_COUNT + FILTER_LDS_BYTES <= 160 * 1024, "LDS of a CU");
 
 __device__ __forceinline__ u64 wave_sum(u64 x) {
 #pragma unroll
@@ -105,13 +109,18 @@ __device__ __forceinline__ u64 wave_sum(u64 x) {
     return x;
 }
 
-template <int MODE>
+// FILT: the node-group rule on top of the exclusion, as in the ranking scan (dl_score_rank.hip): the groups of the pair's v
+// and u nodes are staged in the pair's last step but one, all 512 threads form the mask from the rule, one word each, in its
+// last step, and the row threads OR the exclusion into it where the unfiltered kernel starts from zero.
+template <int MODE, bool FILT = false>
 __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
     __bf16* vs = us + 2 * 3 * TT * SLD;
     unsigned* exm = reinterpret_cast<unsigned*>(vs + 2 * 3 * TT * SLD);   // [TT][4]: excluded columns of the tile
     unsigned* bins = exm + TT * 4;                              // HIST: [BINS]; COUNT: [SEPS] separators
+    u64* fal = reinterpret_cast<u64*>(bins + (MODE == COUNT ? SEPS : BINS));           // FILT: allow [64] | cgrp [TT] | rgrp [TT]
+    unsigned char* cgrp = reinterpret_cast<unsigned char*>(fal + 64);
 
     // device-side state, read at workgroup start: a finished search makes the remaining histogram scans return at once
     const State S = *A.state;
@@ -154,6 +163,8 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
             tmax = A.tord[A.T - 1];
         }
     }
+    if constexpr (FILT)
+        if (tid < 64) fal[tid] = tid < A.filt.n_groups ? A.filt.allow[tid] : 0ull;
 
     PlaneStage<MTHR, SDC> uq, vq;
     static_assert(TT == PLANE_ROWS, "tiles of the plane arrays");
@@ -186,6 +197,11 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     for (int s = 0; s < steps; ++s) {
         const int rem = s % per_tile;
         const int r = rem % (2 * nd);
+        unsigned char gb = 0;                                   // FILT: group of node tid of (v tile | u tile), on its way to LDS
+        if constexpr (FILT) {
+            const int node = (tid < TT ? ct * TT : (qt - 1) * TT) + tid;
+            if (rem == per_tile - 2 && tid < 2 * TT && node < A.N) gb = A.filt.group[node];
+        }
         const __bf16* ub = us + (s & 1) * 3 * TT * SLD + (wu * 32 + li) * SLD + half * 8;
         const __bf16* vb = vs + (s & 1) * 3 * TT * SLD + (wv * 64 + li) * SLD + half * 8;
 #pragma unroll
@@ -211,6 +227,13 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                 zero_acc(acc[bb]);
             }
         }
+        if constexpr (FILT) {
+            if (rem == per_tile - 2) {
+                if (tid < 2 * TT) cgrp[tid] = gb;
+            } else if (rem == per_tile - 1) {                   // word tid & 3 of row tid >> 2
+                exm[tid] = filter_word(fal[cgrp[TT + (tid >> 2)] & 63], cgrp + (tid & 3) * 32);
+            }
+        }
         __syncthreads();
         if (rem != per_tile - 1) continue;
 
@@ -218,7 +241,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         const int u0 = qt * TT, v0 = ct * TT;
         if (tid < TT) {                                         // this tile's excluded columns of row u0 + tid
             unsigned* m = exm + tid * 4;
-            m[0] = m[1] = m[2] = m[3] = 0u;
+            if constexpr (!FILT) m[0] = m[1] = m[2] = m[3] = 0u;
             const int node = u0 + tid;
             if (node < A.N && A.ex_rowptr != nullptr) {
                 int lo = A.ex_rowptr[node];
@@ -527,8 +550,9 @@ static MineWs mine_carve(const MinePlan& p, int K, int m, void* ws) {
 size_t score_mine_workspace_bytes(int N, int K, int d, int m) { return mine_carve(mine_plan(N, d), K, m, nullptr).bytes; }
 
 int score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
-               int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws, hipStream_t st) {
-    static unsigned long long lds_hist = 0, lds_emit = 0;
+               int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws, hipStream_t st,
+               const dl_node_filter* nf) {
+    static unsigned long long lds_hist = 0, lds_emit = 0, lds_hist_f = 0, lds_emit_f = 0;
     const MinePlan p = mine_plan(N, d);
     const MineWs w = mine_carve(p, K, m, ws);
     hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, m);
@@ -543,14 +567,27 @@ int score_mine(const float* Z, const float* H, int N, int K, int d, float t, con
         a.m = m;
         a.pairs = p.pairs; a.per_wg = p.per_wg;
         a.state = w.state; a.hist = w.hist; a.keys = w.keys;
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<HIST>), LDS_BYTES, lds_hist);
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<EMIT>), LDS_BYTES, lds_emit);
-        for (int pass = 0; pass < PASSES; ++pass) {
-            a.pass = pass;
-            hipLaunchKernelGGL(scan_tiles<HIST>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
-            hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
+        if (nf != nullptr) {
+            constexpr size_t LB = LDS_BYTES + FILTER_LDS_BYTES;
+            a.filt = FilterArgs{nf->group, (const u64*)nf->allow, nf->n_groups};
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<HIST, true>), LB, lds_hist_f);
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<EMIT, true>), LB, lds_emit_f);
+            for (int pass = 0; pass < PASSES; ++pass) {
+                a.pass = pass;
+                hipLaunchKernelGGL((scan_tiles<HIST, true>), dim3((unsigned)p.grid), dim3(MTHR), LB, st, a);
+                hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
+            }
+            hipLaunchKernelGGL((scan_tiles<EMIT, true>), dim3((unsigned)p.grid), dim3(MTHR), LB, st, a);
+        } else {
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<HIST>), LDS_BYTES, lds_hist);
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<EMIT>), LDS_BYTES, lds_emit);
+            for (int pass = 0; pass < PASSES; ++pass) {
+                a.pass = pass;
+                hipLaunchKernelGGL(scan_tiles<HIST>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
+                hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
+            }
+            hipLaunchKernelGGL(scan_tiles<EMIT>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
         }
-        hipLaunchKernelGGL(scan_tiles<EMIT>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
     }
     hipLaunchKernelGGL(order_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.state, w.keys, max(N, 1), m, src, dst,
                        logit, prob, count);
@@ -613,8 +650,9 @@ static PairRankWs pair_rank_carve(const MinePlan& p, int K, void* ws) {
 size_t score_pair_ranks_workspace_bytes(int N, int K, int d) { return pair_rank_carve(mine_plan(N, d), K, nullptr).bytes; }
 
 int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
-                     const unsigned* tord, int T, u64* gcnt, u64* tcnt, u64* ncand, void* ws, hipStream_t st) {
-    static unsigned long long lds_count = 0;
+                     const unsigned* tord, int T, u64* gcnt, u64* tcnt, u64* ncand, void* ws, hipStream_t st,
+                     const dl_node_filter* nf) {
+    static unsigned long long lds_count = 0, lds_count_f = 0;
     const PairRankPlan p = pair_rank_plan(N, d, T);
     const PairRankWs w = pair_rank_carve(p.m, K, ws);
     hipError_t e = hipMemsetAsync(w.state, 0, sizeof(State), st);
@@ -633,8 +671,15 @@ int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float 
         a.state = w.state;
         a.tord = tord; a.T = T; a.stride = p.stride; a.nsep = p.nsep;
         a.gcnt = gcnt; a.tcnt = tcnt; a.ncand = ncand;
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<COUNT>), LDS_BYTES_COUNT, lds_count);
-        hipLaunchKernelGGL(scan_tiles<COUNT>, dim3((unsigned)p.m.grid), dim3(MTHR), LDS_BYTES_COUNT, st, a);
+        if (nf != nullptr) {
+            constexpr size_t LB = LDS_BYTES_COUNT + FILTER_LDS_BYTES;
+            a.filt = FilterArgs{nf->group, (const u64*)nf->allow, nf->n_groups};
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<COUNT, true>), LB, lds_count_f);
+            hipLaunchKernelGGL((scan_tiles<COUNT, true>), dim3((unsigned)p.m.grid), dim3(MTHR), LB, st, a);
+        } else {
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<COUNT>), LDS_BYTES_COUNT, lds_count);
+            hipLaunchKernelGGL(scan_tiles<COUNT>, dim3((unsigned)p.m.grid), dim3(MTHR), LDS_BYTES_COUNT, st, a);
+        }
     }
     return check_launch("score_pair_ranks");
 }

@@ -10,6 +10,8 @@
 // Work items (query tile x slice) are dealt to the XCDs by xcd_item.  What follows the products per candidate tile:
 //   * exclusion: a 128-bit mask per query row, from the row's ascending excluded columns (a cursor that only moves forward
 //     through the tiles of a slice: one binary search per row and workgroup).
+//   * node groups (the FILT instantiations; dl_score_topk_filtered, dl_score_ranks_filtered): a rule on the groups of the
+//     row's and the candidate's node, formed into the same mask ahead of the exclusion (see rank_scan_kernel).
 //   * top-k: a per-(row, slice) list in global memory of cap = k + 64 keys.  A candidate is appended only if its key beats
 //     the row's running threshold (the k-th best key of the list after its last compaction; kept in LDS).  A round of
 //     appends adds at most 64 keys per row (two waves x 32 lanes); a list that could overflow in the next round is
@@ -67,11 +69,14 @@ struct ScanArgs {
     int k, cap;  u64* lists;  int* counts;     // TOPK: lists [Q][slices][cap], counts [Q][slices]
     const int32_t* tptr;  const unsigned* tord;  u64* gcnt;  u64* tcnt;   // RANKS
     const int32_t *trow, *tdst;  int T;  float* tlogit;                 // DIAG: target i = (query row trow[i], node tdst[i])
+    FilterArgs filt;                                                    // FILT: the node-group rule (dl_tiles.h)
 };
 
 // LDS beyond the two staging images (bytes): exclusion mask, per-row bookkeeping, per-wave compaction scratch
 constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
 constexpr size_t LDS_BYTES = STAGE_BYTES + TT * 4 * 4 + 6 * TT * 4 + TT * 8 + 8 * MAX_CAP * 8;
+constexpr size_t LDS_BYTES_FILT = LDS_BYTES + FILTER_LDS_BYTES;
+static_assert(LDS_BYTES % 16 == 0 && LDS_BYTES_FILT <= 160 * 1024, "LDS of a CU");
 
 // A PlaneStage tile whose 128 rows are gathered: row r of the tile is row rows[min(base + r, n - 1)] of the plane array.
 __device__ __forceinline__ void gather_fetch(PlaneStage<RTHR, SDC>& st, const __bf16* __restrict__ planes, const int32_t* rows,
@@ -134,8 +139,13 @@ __device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, 
     }
 }
 
-template <int MODE>
+// FILT: the node-group rule on top of the exclusion.  All 512 threads form the tile's mask from the rule, one word each, in
+// the tile's last pipeline step (the candidates' groups were staged one step earlier: a tile has K * 2 * nd >= 2 steps, and
+// every reader of the previous tile's mask and groups is behind a barrier by then); the row threads then OR the exclusion
+// into it where the unfiltered kernel starts from zero.  The epilogue is the unfiltered one.
+template <int MODE, bool FILT = false>
 __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
+    static_assert(!(FILT && MODE == DIAG), "the target pass has no mask");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
     __bf16* vs = us + 2 * 3 * TT * SLD;
@@ -148,6 +158,9 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
     int* rm = rbase + TT;                                       // RANKS: targets of the row
     u64* thr = reinterpret_cast<u64*>(rm + TT);                 // TOPK: threshold key; RANKS: smallest target order
     u64* scr = thr + TT;                                        // [8][MAX_CAP]: compaction scratch of each wave
+    u64* fal = scr + 8 * MAX_CAP;                               // FILT: allow [64] | cgrp [TT] | rgrp [TT]
+    unsigned char* cgrp = reinterpret_cast<unsigned char*>(fal + 64);
+    unsigned char* rgrp = cgrp + TT;
 
     const int nrows = MODE == DIAG ? A.T : A.Q;
     const int qtiles = (nrows + TT - 1) / TT;
@@ -176,6 +189,10 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
             cnt[tid] = 0;
             srt[tid] = 0;
             thr[tid] = 0ull;
+            if constexpr (FILT) {
+                rgrp[tid] = node >= 0 ? A.filt.group[node] : (unsigned char)0;
+                if (tid < 64) fal[tid] = tid < A.filt.n_groups ? A.filt.allow[tid] : 0ull;
+            }
             if (node >= 0 && A.ex_rowptr != nullptr) {          // first excluded column >= the slice's first candidate
                 int lo = A.ex_rowptr[node], hi = A.ex_rowptr[node + 1];
                 const int v0 = ct0 * TT;
@@ -231,6 +248,11 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
     for (int s = 0; s < steps; ++s) {
         const int rem = s % per_tile;
         const int r = rem % (2 * nd);
+        unsigned char gb = 0;                                   // FILT: group of candidate tid of this tile, on its way to LDS
+        if constexpr (FILT) {
+            const int v = (ct0 + s / per_tile) * TT + tid;
+            if (rem == per_tile - 2 && tid < TT && v < A.N) gb = A.filt.group[v];
+        }
         const __bf16* ub = us + (s & 1) * 3 * TT * SLD + (wu * 32 + li) * SLD + half * 8;
         const __bf16* vb = vs + (s & 1) * 3 * TT * SLD + (wv * 64 + li) * SLD + half * 8;
 #pragma unroll
@@ -256,6 +278,13 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
                 zero_acc(acc[bb]);
             }
         }
+        if constexpr (FILT) {
+            if (rem == per_tile - 2) {
+                if (tid < TT) cgrp[tid] = gb;
+            } else if (rem == per_tile - 1) {                   // word tid & 3 of row tid >> 2
+                exm[tid] = filter_word(fal[rgrp[tid >> 2] & 63], cgrp + (tid & 3) * 32);
+            }
+        }
         __syncthreads();
         if (rem != per_tile - 1) continue;
 
@@ -275,7 +304,7 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
             if (tid < TT) {                                     // this tile's excluded columns of row tid
                 const int node = rnode[tid];
                 unsigned* m = exm + tid * 4;
-                m[0] = m[1] = m[2] = m[3] = 0u;
+                if constexpr (!FILT) m[0] = m[1] = m[2] = m[3] = 0u;
                 if (node >= 0 && A.ex_rowptr != nullptr) {
                     int c = excur[tid];
                     const int end = A.ex_rowptr[node + 1];
@@ -476,6 +505,26 @@ __global__ void target_finish_kernel(const int32_t* __restrict__ tptr, const int
     ties[i] = (int64_t)tie - (counted ? 1 : 0);
 }
 
+// Under a node-group rule the scan counted a target itself only where the rule allows it: behind target_finish_kernel, give
+// a target the rule does not allow the 1 back that was taken from its ties.
+__global__ void target_unallowed_kernel(const int32_t* __restrict__ trow, const int32_t* __restrict__ tdst,
+                                        const int32_t* __restrict__ qnode, const int32_t* __restrict__ ex_rowptr,
+                                        const int32_t* __restrict__ ex_col, int T, FilterArgs filt, int64_t* __restrict__ ties) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= T) return;
+    const int node = qnode[trow[i]], v = tdst[i];
+    if (v == node || ((filt.allow[filt.group[node]] >> (filt.group[v] & 63)) & 1ull)) return;
+    if (ex_rowptr != nullptr) {
+        int lo = ex_rowptr[node], hi = ex_rowptr[node + 1];
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ex_col[mid] < v) lo = mid + 1; else hi = mid;
+        }
+        if (lo < ex_rowptr[node + 1] && ex_col[lo] == v) return;       // excluded: nothing was taken
+    }
+    ties[i] += 1;
+}
+
 }  // namespace rank
 
 using namespace rank;
@@ -569,6 +618,8 @@ size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T) {
     return rank_carve(rank_plan(N, d, Q, k), Q, K, d, k, T, nullptr).bytes;
 }
 
+static FilterArgs filter_args(const dl_node_filter* nf) { return FilterArgs{nf->group, (const u64*)nf->allow, nf->n_groups}; }
+
 // the query rows gathered and split, the candidate tables split: the scan's operands
 static ScanArgs scan_operands(const RankPlan& p, const RankWs& w, const float* Z, const float* H, int N, int K, int d, float t,
                               const int32_t* queries, int Q, const int32_t* exr, const int32_t* exc, hipStream_t st) {
@@ -590,15 +641,22 @@ static ScanArgs scan_operands(const RankPlan& p, const RankWs& w, const float* Z
 
 int score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, int k,
                const int32_t* exr, const int32_t* exc, int exclude_self, int64_t* index, float* logit, float* prob, void* ws,
-               hipStream_t st) {
-    static unsigned long long lds_done = 0;
+               hipStream_t st, const dl_node_filter* nf) {
+    static unsigned long long lds_done = 0, lds_filt = 0;
     const RankPlan p = rank_plan(N, d, Q, k);
     const RankWs w = rank_carve(p, Q, K, d, k, 0, ws);
     ScanArgs a = scan_operands(p, w, Z, H, N, K, d, t, queries, Q, exr, exc, st);
     a.exclude_self = exclude_self ? 1 : 0;
     a.k = k; a.cap = p.cap; a.lists = w.lists; a.counts = w.counts;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<TOPK>), LDS_BYTES, lds_done);
-    hipLaunchKernelGGL(rank_scan_kernel<TOPK>, dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES, st, a);
+    if (nf != nullptr) {
+        a.filt = filter_args(nf);
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<TOPK, true>), LDS_BYTES_FILT, lds_filt);
+        hipLaunchKernelGGL((rank_scan_kernel<TOPK, true>), dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES_FILT,
+                           st, a);
+    } else {
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<TOPK>), LDS_BYTES, lds_done);
+        hipLaunchKernelGGL(rank_scan_kernel<TOPK>, dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES, st, a);
+    }
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)Q), dim3(256), 0, st, w.lists, w.counts, p.slices, p.cap, k, index,
                        logit, prob);
     return check_launch("score_topk");
@@ -606,8 +664,8 @@ int score_topk(const float* Z, const float* H, int N, int K, int d, float t, con
 
 int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, const int32_t* tptr,
                 const int32_t* tdst, int T, const int32_t* exr, const int32_t* exc, int64_t* greater, int64_t* ties, void* ws,
-                hipStream_t st) {
-    static unsigned long long lds_diag = 0, lds_rank = 0;
+                hipStream_t st, const dl_node_filter* nf) {
+    static unsigned long long lds_diag = 0, lds_rank = 0, lds_filt = 0;
     const RankPlan p = rank_plan(N, d, Q, 0);
     const RankWs w = rank_carve(p, Q, K, d, 0, T, ws);
     ScanArgs a = scan_operands(p, w, Z, H, N, K, d, t, queries, Q, exr, exc, st);
@@ -625,10 +683,19 @@ int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, co
     DL_REQUIRE(e == hipSuccess, "hipMemsetAsync: %s", hipGetErrorString(e));
     a.exclude_self = 1;
     a.tptr = tptr; a.tord = w.tord; a.gcnt = w.gcnt; a.tcnt = w.tcnt;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<RANKS>), LDS_BYTES, lds_rank);
-    hipLaunchKernelGGL(rank_scan_kernel<RANKS>, dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES, st, a);
+    if (nf != nullptr) {
+        a.filt = filter_args(nf);
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<RANKS, true>), LDS_BYTES_FILT, lds_filt);
+        hipLaunchKernelGGL((rank_scan_kernel<RANKS, true>), dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES_FILT,
+                           st, a);
+    } else {
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<RANKS>), LDS_BYTES, lds_rank);
+        hipLaunchKernelGGL(rank_scan_kernel<RANKS>, dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES, st, a);
+    }
     hipLaunchKernelGGL(target_finish_kernel, dim3(tb), dim3(256), 0, st, tptr, w.trow, tdst, queries, w.spos, w.sfirst, w.gcnt,
                        w.tcnt, exr, exc, T, greater, ties);
+    if (nf != nullptr)
+        hipLaunchKernelGGL(target_unallowed_kernel, dim3(tb), dim3(256), 0, st, w.trow, tdst, queries, exr, exc, T, a.filt, ties);
     return check_launch("score_ranks");
 }
 

@@ -245,5 +245,26 @@ void split_w2(const float* W2, int rows, int nhid, __bf16* dst, int nhid_p, hipS
 void split_fwd_operands(const float* x, int N, int F, __bf16* xP, const float* W1, int K, int nhid, __bf16* wP,
                         const float* W2, int d, __bf16* w2P, int nhid_p, hipStream_t st);
 
+// Node-group rule of the candidate scans (dl_score_rank.hip, dl_score_mine.hip; dl_node_filter of the header): bit h of
+// allow[g] set = a row of group g may take a partner of group h.  The filtered instantiations keep, behind their other LDS,
+//   allow [64] (the table, entries >= n_groups zero) | cgrp [128] (groups of the candidate tile's nodes) | rgrp [128] (of the rows)
+// and every thread of the 512 forms one 32-bit word of the tile's [128][4] mask: filter_word.
+struct FilterArgs { const unsigned char* group; const unsigned long long* allow; int n_groups; };
+constexpr int FILTER_LDS_BYTES = 64 * 8 + 2 * PLANE_ROWS;
+// bit c set = the candidate whose group is byte c of g[0..32) (16-byte aligned) is NOT allowed by the row's allow word
+__device__ __forceinline__ unsigned filter_word(unsigned long long allow, const unsigned char* g) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 lo = *reinterpret_cast<const u32x4*>(g), hi = *reinterpret_cast<const u32x4*>(g + 16);
+    const unsigned w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    const unsigned long long deny = ~allow;
+    unsigned m = 0u;
+#pragma unroll
+    for (int c = 0; c < 32; ++c) {
+        const unsigned grp = (w[c >> 2] >> ((c & 3) * 8)) & 63u;      // 64-bit shift: groups 32..63 are upper bits
+        m |= ((unsigned)(deny >> grp) & 1u) << c;
+    }
+    return m;
+}
+
 }  // namespace project
 }  // namespace dl

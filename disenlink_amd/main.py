@@ -67,6 +67,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "edges (Disentangle.top_missing_links; single GPU, fp32 tables)")
     p.add_argument("--mine-out", type=str, default=None, metavar="FILE",
                    help="with --mine: write the list to FILE as text, one `src dst logit prob` line per pair")
+    p.add_argument("--node-groups", type=str, default=None, metavar="FILE",
+                   help="with --link-rule: the group (an integer in 0..63) of every node, one per node, as text or .npy")
+    p.add_argument("--link-rule", choices=["same", "different"], default=None,
+                   help="with --node-groups: --rank-eval, --global-rank-eval and --mine take as candidates only links "
+                        "between nodes of the same / of different groups (ops.NodeFilter)")
     p.add_argument("--sparse-features", action="store_true",
                    help="hand the features to the model as features.SparseFeatures (scale * X + shift with X a CSR): layer 1 "
                         "of the projection and its gradient run as gathers over the non-zero entries; for binary / one-hot "
@@ -202,18 +207,34 @@ def main_sharded(args):
         dist.destroy_process_group()
 
 
-def rank_eval(model, x, graph, split, known) -> dict:
+def load_node_groups(path: str, n_nodes: int, rule: str, device):
+    """--node-groups FILE --link-rule RULE as an ops.NodeFilter on ``device``."""
+    from .ops import NodeFilter
+    try:
+        g = np.load(path, allow_pickle=False) if path.endswith(".npy") else np.loadtxt(path, dtype=np.int64, ndmin=1)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--node-groups {path}: {e}")
+    g = np.asarray(g)
+    if g.ndim != 1 or g.size != n_nodes or not np.issubdtype(g.dtype, np.integer):
+        raise SystemExit(f"--node-groups {path}: expected one integer per node ({n_nodes}), got shape {g.shape} {g.dtype}")
+    if g.size and (g.min() < 0 or g.max() > 63):
+        raise SystemExit(f"--node-groups {path}: groups outside 0..63")
+    make = NodeFilter.same if rule == "same" else NodeFilter.different
+    return make(torch.from_numpy(g.astype(np.int64)), device=device)
+
+
+def rank_eval(model, x, graph, split, known, node_filter=None) -> dict:
     """MRR and Hits@{1,10,50,100} of the test positives, each ranked among all nodes with every known edge filtered out
     (Disentangle.link_ranks: the model with its best weights, as run_link_prediction leaves it)."""
     from .metrics import ranking_metrics
     pos = split.test.label > 0.5
     src = torch.from_numpy(np.ascontiguousarray(split.test.u[pos])).to(x.device)
     dst = torch.from_numpy(np.ascontiguousarray(split.test.v[pos])).to(x.device)
-    greater, ties = model.link_ranks(x, graph, src, dst, exclude=known)
+    greater, ties = model.link_ranks(x, graph, src, dst, exclude=known, node_filter=node_filter)
     return ranking_metrics(greater, ties)
 
 
-def global_rank_eval(model, x, graph, split, known) -> dict:
+def global_rank_eval(model, x, graph, split, known, node_filter=None) -> dict:
     """AUC against every non-edge, mean rank, MRR and recall@M of the test positives, each ranked among all unordered
     pairs of the graph with every known edge filtered out (Disentangle.missing_link_ranks, the model's best weights);
     self loops among the positives are left out."""
@@ -222,14 +243,14 @@ def global_rank_eval(model, x, graph, split, known) -> dict:
     src = torch.from_numpy(np.ascontiguousarray(split.test.u[pos])).to(x.device)
     dst = torch.from_numpy(np.ascontiguousarray(split.test.v[pos])).to(x.device)
     keep = src != dst                                               # a self loop of the dataset is no pair of the graph
-    r = model.missing_link_ranks(x, graph, src[keep], dst[keep], exclude=known)
+    r = model.missing_link_ranks(x, graph, src[keep], dst[keep], exclude=known, node_filter=node_filter)
     return global_ranking_metrics(r.greater, r.ties, r.n_others)
 
 
-def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=print):
+def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=print, node_filter=None):
     """--mine: the m most likely links outside ``known`` (Disentangle.top_missing_links), the first ``show`` printed and,
     with ``out``, all of them written as `src dst logit prob` lines."""
-    mined = model.top_missing_links(x, graph, m, exclude=known)
+    mined = model.top_missing_links(x, graph, m, exclude=known, node_filter=node_filter)
     src, dst, logit, prob = (v.cpu().numpy() for v in mined)
     log(f"mined {src.size} links (of {m} asked for); first {min(show, src.size)}: src dst logit prob")
     for i in range(min(show, src.size)):
@@ -273,6 +294,10 @@ def main(argv=None):
                          "--gpus / --table-dtype bf16 or --mine")
     if args.mine and not 1 <= args.mine <= 65536:
         raise SystemExit("--mine M: 1 <= M <= 65536")
+    if (args.node_groups is None) != (args.link_rule is None):
+        raise SystemExit("--node-groups FILE and --link-rule {same,different} go together")
+    if args.link_rule and not (args.rank_eval or args.global_rank_eval or args.mine):
+        raise SystemExit("--link-rule restricts the candidates of --rank-eval, --global-rank-eval and --mine: give one of them")
     if args.gpus > 1:
         from .launch import launch_ranks, under_launcher
         if not under_launcher():                                    # BEFORE any GPU call: the parent starts and waits
@@ -309,6 +334,7 @@ def main(argv=None):
     if args.rank_eval or args.mine or args.global_rank_eval:        # filter: every dataset edge, both directions
         s_all, d_all = torch.from_numpy(np.asarray(ds.src)).long(), torch.from_numpy(np.asarray(ds.dst)).long()
         known = (torch.cat([s_all, d_all]).to(device), torch.cat([d_all, s_all]).to(device))
+    node_filter = load_node_groups(args.node_groups, ds.n_nodes, args.link_rule, device) if args.link_rule else None
     for run in range(args.run):
         if not args.quiet:
             print("run:", run)
@@ -323,15 +349,15 @@ def main(argv=None):
             print("test auc:", res.test_auc)
         result.append(res.test_auc)
         if args.rank_eval:
-            ranking.append(rank_eval(model, x, prepared.graph, split, known))
+            ranking.append(rank_eval(model, x, prepared.graph, split, known, node_filter))
             if not args.quiet:
                 print("test ranking:", _fmt_ranking(ranking[-1]))
         if args.global_rank_eval:
-            global_ranking.append(global_rank_eval(model, x, prepared.graph, split, known))
+            global_ranking.append(global_rank_eval(model, x, prepared.graph, split, known, node_filter))
             if not args.quiet:
                 print("test global ranking:", _fmt_ranking(global_ranking[-1]))
     if args.mine and args.run > 0:                                  # the last run's model, its best weights
-        mine_links(model, x, prepared.graph, known, args.mine, args.mine_out)
+        mine_links(model, x, prepared.graph, known, args.mine, args.mine_out, node_filter=node_filter)
     result = np.array(result)
     tail = []                                                       # the run means of the ranking metrics join the final line
     if args.rank_eval:

@@ -381,25 +381,28 @@ class Disentangle(nn.Module):
             H = ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
         return Z, H
 
-    def topk_links(self, x, adj, queries, k: int, exclude=None, exclude_self: bool = True) -> TopLinks:
+    def topk_links(self, x, adj, queries, k: int, exclude=None, exclude_self: bool = True, node_filter=None) -> TopLinks:
         """The k most likely links of every node in ``queries``: TopLinks(index int64 [Q,k], logit, prob f32 [Q,k]),
         ranked by the pre-sigmoid logit of link_pred (prob = link_pred's value).  ``adj`` as in forward; ``exclude``: a
-        Graph, a dense [N,N] mask or (rows, cols) of pairs that are not candidates (ops.score_topk)."""
+        Graph, a dense [N,N] mask or (rows, cols) of pairs that are not candidates; ``node_filter``: an ops.NodeFilter, a
+        rule on node groups that candidates must pass as well (ops.score_topk)."""
         Z, H = self._rank_tables(x, adj)
-        return TopLinks(*ops.score_topk(Z, H, float(self.temperature), queries, k, exclude, exclude_self))
+        return TopLinks(*ops.score_topk(Z, H, float(self.temperature), queries, k, exclude, exclude_self, node_filter))
 
-    def link_ranks(self, x, adj, src, dst, exclude=None):
+    def link_ranks(self, x, adj, src, dst, exclude=None, node_filter=None):
         """(greater, ties) int64 per target pair (src[i], dst[i]) among all nodes except src[i] and its exclusion set
+        and, with ``node_filter`` (an ops.NodeFilter), the nodes its group may not take
         (ops.score_ranks; metrics.ranking_metrics turns them into MRR / Hits@K)."""
         Z, H = self._rank_tables(x, adj)
-        return ops.score_ranks(Z, H, float(self.temperature), src, dst, exclude)
+        return ops.score_ranks(Z, H, float(self.temperature), src, dst, exclude, node_filter)
 
-    def top_missing_links(self, x, adj, m: int, exclude=None, min_prob=None) -> MinedLinks:
+    def top_missing_links(self, x, adj, m: int, exclude=None, min_prob=None, node_filter=None) -> MinedLinks:
         """The m most likely links of the WHOLE graph that are not known yet: MinedLinks(src, dst int32 [c], logit, prob
         f32 [c]) with src < dst, c = min(m, eligible pairs), ranked by the pre-sigmoid logit of link_pred over all
         unordered pairs (ops.score_mine; nothing of size N x N is formed).  ``exclude``: the known pairs, as a Graph, a
         dense [N,N] mask or (rows, cols), in either orientation; None = the edges of ``adj`` itself.  ``min_prob``: keep
-        only pairs with link_pred >= min_prob (turned into a logit floor on the host: 0.5 -> 0.0)."""
+        only pairs with link_pred >= min_prob (turned into a logit floor on the host: 0.5 -> 0.0).  ``node_filter``: a
+        symmetric ops.NodeFilter, a rule on node groups that pairs must pass as well."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
         Z, H = self._rank_tables(x, graph)
         floor = float("-inf")
@@ -409,15 +412,18 @@ class Disentangle(nn.Module):
                 raise ValueError(f"min_prob={p} outside [0, 1]")
             floor = float("-inf") if p == 0.0 else float("inf") if p == 1.0 else math.log(p) - math.log1p(-p)
         with torch.no_grad():
-            return MinedLinks(*ops.score_mine(Z, H, float(self.temperature), m, graph if exclude is None else exclude, floor))
+            return MinedLinks(*ops.score_mine(Z, H, float(self.temperature), m, graph if exclude is None else exclude, floor,
+                                              node_filter))
 
-    def missing_link_ranks(self, x, adj, src, dst, exclude=None) -> PairRanks:
+    def missing_link_ranks(self, x, adj, src, dst, exclude=None, node_filter=None) -> PairRanks:
         """Where the unordered pairs {src[i], dst[i]} stand among ALL unordered pairs of the graph, in the order
         ``top_missing_links`` lists from the top: PairRanks(greater, ties int64 [T], logit f32 [T], n_others int64 [T])
         (ops.score_pair_ranks: one target pass and one scan, nothing of size N x N; metrics.global_ranking_metrics turns
         them into the AUC against every non-edge, MRR and recall@M).  ``exclude``: the pairs that are no candidates, as
-        in ``top_missing_links``; None = the edges of ``adj``.  A target is ranked whether or not it is excluded."""
+        in ``top_missing_links``; None = the edges of ``adj``.  ``node_filter``: a symmetric ops.NodeFilter that candidates
+        must pass as well.  A target is ranked whether or not it is excluded or allowed."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
         Z, H = self._rank_tables(x, graph)
         with torch.no_grad():
-            return PairRanks(*ops.score_pair_ranks(Z, H, float(self.temperature), src, dst, graph if exclude is None else exclude))
+            return PairRanks(*ops.score_pair_ranks(Z, H, float(self.temperature), src, dst, graph if exclude is None else exclude,
+                                                   node_filter))

@@ -1298,13 +1298,153 @@ def _csr_args(rowptr, col, device):
     return rowptr.data_ptr(), col.data_ptr(), (rowptr, col)
 
 
-def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool = True):
+class NodeFilter:
+    """A rule on node GROUPS for the candidate scans (dl_node_filter): ``groups`` [N] gives every node a group below
+    ``n_groups`` <= 64, and the boolean matrix ``allow`` [n_groups, n_groups] says whether a row of group g may take a
+    partner of group h — what an exclusion set could only say by listing O(N^2) pairs.  Prepared once, like
+    ``pair_exclusion``: the arrays are converted and moved, and ONE host read checks groups.max() < n_groups.
+    Ordered scans (``score_topk``, ``score_ranks``): the row is the query, the partner the candidate, ``allow`` may be
+    asymmetric.  Unordered scans (``score_mine``, ``score_pair_ranks``) need a symmetric rule (``symmetric``) and raise
+    ValueError otherwise; ``candidates`` carries a rule of its own for them (both endpoints in the pool)."""
+
+    def __init__(self, groups, allow, device=None, _pair_allow=None):
+        g = torch.as_tensor(groups)
+        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex:
+            raise ValueError(f"groups must be a 1-D integer array, got {tuple(g.shape)} {g.dtype}")
+        a = torch.as_tensor(allow).detach().to("cpu")
+        if a.dim() != 2 or a.shape[0] != a.shape[1] or not 1 <= a.shape[0] <= 64:
+            raise ValueError(f"allow must be [n_groups, n_groups] with 1 <= n_groups <= 64, got {tuple(a.shape)}")
+        a = a != 0
+        n = int(a.shape[0])
+        if g.numel():
+            lo, hi = (int(v) for v in torch.stack(torch.aminmax(g.to(torch.int64))).tolist())       # the one host read
+            if lo < 0 or hi >= n:
+                raise ValueError(f"groups outside [0, {n}): min {lo}, max {hi}")
+        self.symmetric = bool(torch.equal(a, a.t()))
+        pair = _pair_allow if _pair_allow is not None else a if self.symmetric else None      # the unordered scans' rule
+        dev = g.device if device is None else torch.device(device)
+        self.n_nodes, self.n_groups = int(g.numel()), n
+        self.groups = g.to(device=dev, dtype=torch.uint8).contiguous()
+        self.allow = a.to(dev)
+        self.pair_allow = None if pair is None else pair.to(dev)
+        self._words = self._pack(a).to(dev)
+        self._pair_words = None if pair is None else self._pack(pair).to(dev)
+
+    @staticmethod
+    def _pack(a: torch.Tensor) -> torch.Tensor:
+        """allow [n, n] bool -> the uint64 words of dl_node_filter (bit h of word g), as int64 bits."""
+        words = [sum(1 << h for h in range(a.shape[1]) if bool(a[g, h])) for g in range(a.shape[0])]
+        return torch.tensor([w - (1 << 64) if w >= (1 << 63) else w for w in words], dtype=torch.int64)
+
+    @staticmethod
+    def _dense_groups(groups):
+        g = torch.as_tensor(groups)
+        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex:
+            raise ValueError(f"groups must be a 1-D integer array, got {tuple(g.shape)} {g.dtype}")
+        n = int(g.max()) + 1 if g.numel() else 1
+        if n > 64 or (g.numel() and int(g.min()) < 0):
+            raise ValueError(f"a node filter takes groups 0..63, got {int(g.min())}..{n - 1}")
+        return g, max(n, 1)
+
+    @classmethod
+    def same(cls, groups, device=None) -> "NodeFilter":
+        """Only links between nodes of the same group."""
+        g, n = cls._dense_groups(groups)
+        return cls(g, torch.eye(n, dtype=torch.bool), device)
+
+    @classmethod
+    def different(cls, groups, device=None) -> "NodeFilter":
+        """Only links between nodes of different groups."""
+        g, n = cls._dense_groups(groups)
+        return cls(g, ~torch.eye(n, dtype=torch.bool), device)
+
+    @classmethod
+    def between(cls, mask_a, mask_b, both_ways: bool = True, device=None) -> "NodeFilter":
+        """Rows in ``mask_a`` take partners in ``mask_b`` (users -> items); with ``both_ways`` also the reverse, which
+        makes the rule symmetric.  The masks are boolean [N] and may overlap."""
+        ma, mb = torch.as_tensor(mask_a) != 0, torch.as_tensor(mask_b) != 0
+        if ma.dim() != 1 or ma.shape != mb.shape:
+            raise ValueError(f"the masks must be 1-D and of one length, got {tuple(ma.shape)} and {tuple(mb.shape)}")
+        g = ma.to(torch.uint8) + 2 * mb.to(ma.device).to(torch.uint8)      # 0 neither, 1 a, 2 b, 3 both
+        allow = torch.zeros(4, 4, dtype=torch.bool)
+        for r in range(4):
+            for c in range(4):
+                allow[r, c] = bool(r & 1 and c & 2) or bool(both_ways and r & 2 and c & 1)
+        return cls(g, allow, device)
+
+    @classmethod
+    def candidates(cls, mask, device=None) -> "NodeFilter":
+        """A fixed candidate pool (boolean [N]).  Ordered scans: any query takes only pool members.  Unordered scans: both
+        endpoints are in the pool."""
+        m = torch.as_tensor(mask) != 0
+        if m.dim() != 1:
+            raise ValueError(f"the mask must be 1-D, got {tuple(m.shape)}")
+        return cls(m.to(torch.uint8), torch.tensor([[False, True], [False, True]]), device,
+                   _pair_allow=torch.tensor([[False, False], [False, True]]))
+
+    def to(self, device) -> "NodeFilter":
+        """The same filter with its arrays on ``device`` (no check is repeated)."""
+        f = object.__new__(NodeFilter)
+        f.n_nodes, f.n_groups, f.symmetric = self.n_nodes, self.n_groups, self.symmetric
+        for name in ("groups", "allow", "pair_allow", "_words", "_pair_words"):
+            v = getattr(self, name)
+            setattr(f, name, None if v is None else v.to(device))
+        return f
+
+    def allowed(self, u, v, unordered: bool = False) -> torch.Tensor:
+        """bool per pair: may row u[i] take partner v[i]?  The kernels' rule in torch on index tensors (for tests and
+        callers that post-process; no hot path uses it).  ``unordered``: the rule of the unordered scans."""
+        a = self._pair_rule() if unordered else self.allow
+        u = torch.as_tensor(u, device=self.groups.device).long()
+        v = torch.as_tensor(v, device=self.groups.device).long()
+        return a[self.groups[u].long(), self.groups[v].long()]
+
+    def _pair_rule(self) -> torch.Tensor:
+        if self.pair_allow is None:
+            raise ValueError("an unordered scan needs a symmetric node filter (allow[g][h] == allow[h][g]); "
+                             "this one is asymmetric")
+        return self.pair_allow
+
+    def _n_pairs_allowed(self) -> torch.Tensor:
+        """int64 [1] on the filter's device: unordered pairs u < v the rule admits, from the group sizes."""
+        a = self._pair_rule().to(torch.int64)
+        c = torch.bincount(self.groups.long(), minlength=self.n_groups).to(torch.int64)
+        cross = (a * c[:, None] * c[None, :]).sum() - (a.diagonal() * c * c).sum()
+        return (cross // 2 + (a.diagonal() * (c * (c - 1) // 2)).sum()).reshape(1)
+
+    def _c_arg(self, N: int, device, unordered: bool):
+        """(byref(dl_node_filter), keep-alive) for a scan over N nodes on ``device``; raises before anything launches."""
+        words = self._words
+        if unordered:
+            self._pair_rule()
+            words = self._pair_words
+        if self.groups.device != torch.device(device):
+            raise ValueError(f"node filter on {self.groups.device}, tables on {device}: use NodeFilter.to(device)")
+        st = _lib.DlNodeFilter(self.groups.data_ptr(), self.n_groups, words.data_ptr())
+        return C.byref(st), (st, self.groups, words)
+
+
+def _filter_check(node_filter, Z, unordered: bool) -> None:
+    """The host-side refusals of a node filter, ahead of every other check and of any launch."""
+    if node_filter is None:
+        return
+    if not isinstance(node_filter, NodeFilter):
+        raise TypeError(f"node_filter must be an ops.NodeFilter, got {type(node_filter).__name__}")
+    if node_filter.n_nodes != int(Z.shape[0]):
+        raise ValueError(f"node filter of {node_filter.n_nodes} nodes, tables of {int(Z.shape[0])}")
+    if unordered:
+        node_filter._pair_rule()
+
+
+def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool = True, node_filter=None):
     """-> (index int64 [Q,k], logit f32 [Q,k], prob f32 [Q,k]): the k best candidates of every query node by the logit
     s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), sorted (larger
     first, +inf first, NaN last, equal logits by index), prob = sigmoid(logit).  Candidates: every node outside the
     query's exclusion set (``exclusion_csr``) and, with ``exclude_self``, other than the query itself; rows with fewer than
-    k are padded with index -1 / NaN.  Inference only (dl_score_topk: nothing of size Q x N is formed)."""
+    k are padded with index -1 / NaN.  ``node_filter`` (a ``NodeFilter``): only candidates whose group the query's group
+    allows, on top of the exclusion.  Inference only (dl_score_topk: nothing of size Q x N is formed)."""
     lib = _lib.load()
+    _filter_check(node_filter, Z, False)
     Z, H, N, K, d = _rank_tables(Z, H)
     k = int(k)
     if not 1 <= k <= RANK_MAX_K:
@@ -1318,18 +1458,26 @@ def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool
         return index, logit, prob
     rp, cp, _keep = _csr_args(*exclusion_csr(exclude, N, Z.device), Z.device)
     ws = _ws.get(int(lib.dl_score_topk_workspace_bytes(N, K, d, Q, k, 0)), Z.device)
+    if node_filter is not None:
+        nf, _keep_nf = node_filter._c_arg(N, Z.device, False)
+        _lib.check(lib.dl_score_topk_filtered(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), q.data_ptr(), Q, k, rp, cp,
+                                              1 if exclude_self else 0, index.data_ptr(), logit.data_ptr(), prob.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _stream(), nf), "dl_score_topk_filtered")
+        return index, logit, prob
     _lib.check(lib.dl_score_topk(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), q.data_ptr(), Q, k, rp, cp,
                                  1 if exclude_self else 0, index.data_ptr(), logit.data_ptr(), prob.data_ptr(),
                                  ws.data_ptr(), ws.numel(), _stream()), "dl_score_topk")
     return index, logit, prob
 
 
-def score_ranks(Z, H, t: float, src, dst, exclude=None):
+def score_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None):
     """-> (greater, ties) int64 [P] for the target pairs (src[i], dst[i]): how many candidates of src[i] (every node other
     than src[i] and outside its exclusion set; dst[i] itself is never counted, and is ranked even when it is in the
     exclusion set — the filtered protocol) have a logit strictly above / equal to the target's, by value.  The target's
-    logit is the one the scan computes.  rank = 1 + greater + ties / 2 (metrics.ranking_metrics).  dl_score_ranks."""
+    logit is the one the scan computes.  rank = 1 + greater + ties / 2 (metrics.ranking_metrics).  ``node_filter``: only
+    candidates the rule allows for src[i] are counted; a target is ranked whether or not it is allowed.  dl_score_ranks."""
     lib = _lib.load()
+    _filter_check(node_filter, Z, False)
     Z, H, N, K, d = _rank_tables(Z, H)
     s = _node_ids(src, N, Z.device, "src")
     v = _node_ids(dst, N, Z.device, "dst")
@@ -1351,9 +1499,16 @@ def score_ranks(Z, H, t: float, src, dst, exclude=None):
     t_sorted = _empty(T, torch.int64, Z.device)
     rp, cp, _keep = _csr_args(*exclusion_csr(exclude, N, Z.device), Z.device)
     ws = _ws.get(int(lib.dl_score_topk_workspace_bytes(N, K, d, Q, 0, T)), Z.device)
-    _lib.check(lib.dl_score_ranks(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), queries.data_ptr(), Q, tptr.data_ptr(),
-                                  tdst.data_ptr(), T, rp, cp, g_sorted.data_ptr(), t_sorted.data_ptr(), ws.data_ptr(),
-                                  ws.numel(), _stream()), "dl_score_ranks")
+    if node_filter is not None:
+        nf, _keep_nf = node_filter._c_arg(N, Z.device, False)
+        _lib.check(lib.dl_score_ranks_filtered(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), queries.data_ptr(), Q,
+                                               tptr.data_ptr(), tdst.data_ptr(), T, rp, cp, g_sorted.data_ptr(),
+                                               t_sorted.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf),
+                   "dl_score_ranks_filtered")
+    else:
+        _lib.check(lib.dl_score_ranks(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), queries.data_ptr(), Q, tptr.data_ptr(),
+                                      tdst.data_ptr(), T, rp, cp, g_sorted.data_ptr(), t_sorted.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), _stream()), "dl_score_ranks")
     greater[order] = g_sorted
     ties[order] = t_sorted
     return greater, ties
@@ -1376,15 +1531,17 @@ def _unordered_exclusion_csr(exclude, N: int, device):
     return exclusion_csr((torch.minimum(rows, cols), torch.maximum(rows, cols)), N, device)
 
 
-def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf")):
+def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf"), node_filter=None):
     """-> (src int32 [c], dst int32 [c], logit f32 [c], prob f32 [c]), c = min(m, eligible): the m best unordered pairs
     src < dst of the WHOLE graph by the logit s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid
     link_pred), sorted in ``score_topk``'s order (larger first, +inf first, equal logits by src * N + dst), with the bits
     ``score_topk`` returns for query src, candidate dst.  ``exclude`` (a ``Graph``, a dense [N,N] mask or ``(rows, cols)``)
     is taken as a set of unordered pairs; a pair is eligible iff its logit is >= ``min_logit`` (NaN never is).
     1 <= m <= 65,536, N <= 46,340.  Inference only; nothing of size N x N is formed (dl_score_mine), and the one host read
-    is that of the count, at the very end."""
+    is that of the count, at the very end.  ``node_filter`` (a symmetric ``NodeFilter``): only pairs whose groups the rule
+    allows, on top of the exclusion and the floor."""
     lib = _lib.load()
+    _filter_check(node_filter, Z, True)
     Z, H, N, K, d = _rank_tables(Z, H)
     m = int(m)
     rp, cp, _keep = _csr_args(*_unordered_exclusion_csr(exclude, N, Z.device), Z.device)
@@ -1394,9 +1551,16 @@ def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-
     prob = _empty(max(m, 0), torch.float32, Z.device)
     count = _empty(1, torch.int64, Z.device)
     ws = _ws.get(max(256, int(lib.dl_score_mine_workspace_bytes(N, K, d, m))), Z.device)
-    _lib.check(lib.dl_score_mine(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, float(min_logit), m, src.data_ptr(),
-                                 dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(), ws.data_ptr(),
-                                 ws.numel(), _stream()), "dl_score_mine")
+    if node_filter is not None:
+        nf, _keep_nf = node_filter._c_arg(N, Z.device, True)
+        _lib.check(lib.dl_score_mine_filtered(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, float(min_logit), m,
+                                              src.data_ptr(), dst.data_ptr(), logit.data_ptr(), prob.data_ptr(),
+                                              count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf),
+                   "dl_score_mine_filtered")
+    else:
+        _lib.check(lib.dl_score_mine(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, float(min_logit), m, src.data_ptr(),
+                                     dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), _stream()), "dl_score_mine")
     c = int(count.item())
     return src[:c], dst[:c], logit[:c], prob[:c]
 
@@ -1446,11 +1610,13 @@ def score_pair_logits(Z, H, t: float, a, b):
     return torch.where(logit == 0, torch.zeros_like(logit), logit)
 
 
-def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None):
+def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter=None):
     """The hook of the tests and of tools/pair_rank_time.py, not part of the interface: ``score_pair_ranks`` and, as a fifth
     value, the int64 [1] DEVICE count of the candidates the scan counted, which equals N (N - 1) / 2 - |excluded pairs| (the
-    one exact check that works where nothing can be enumerated)."""
+    one exact check that works where nothing can be enumerated; under a ``node_filter``: the pairs the rule allows, less
+    the excluded ones among them)."""
     lib = _lib.load()
+    _filter_check(node_filter, Z, True)
     Z, H, N, K, d = _rank_tables(Z, H)
     dev = Z.device
     s = _node_ids(src, N, dev, "src")
@@ -1465,6 +1631,12 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None):
         raise ValueError(f"exclusion set of {ex.n_nodes} nodes, expected {N}")
     rowptr, col, ex_key = ex.rowptr, ex.col, ex.key
     total = N * (N - 1) // 2 - ex.n_pairs
+    if node_filter is not None:                                       # allowed pairs, less the excluded ones among them
+        nf, _keep_nf = node_filter._c_arg(N, dev, True)
+        total = node_filter._n_pairs_allowed()
+        if ex_key is not None and ex_key.numel():
+            er, ec = torch.div(ex_key, N, rounding_mode="floor"), ex_key % N
+            total = total - ((ec > er) & node_filter.allowed(er, ec, unordered=True)).sum().reshape(1)
     if T == 0:
         e = torch.zeros(0, dtype=torch.int64, device=dev)
         return e, e.clone(), torch.zeros(0, dtype=torch.float32, device=dev), e.clone(), total
@@ -1479,9 +1651,14 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None):
     counted = _empty(1, torch.int64, dev)
     rp, cp, _keep = _csr_args(rowptr, col, dev)
     ws = _ws.get(max(256, int(lib.dl_score_pair_ranks_workspace_bytes(N, K, d))), dev)
-    _lib.check(lib.dl_score_pair_ranks(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, tord.data_ptr(), T,
-                                       above.data_ptr(), equal.data_ptr(), counted.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       _stream()), "dl_score_pair_ranks")
+    if node_filter is not None:
+        _lib.check(lib.dl_score_pair_ranks_filtered(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, tord.data_ptr(), T,
+                                                    above.data_ptr(), equal.data_ptr(), counted.data_ptr(), ws.data_ptr(),
+                                                    ws.numel(), _stream(), nf), "dl_score_pair_ranks_filtered")
+    else:
+        _lib.check(lib.dl_score_pair_ranks(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, tord.data_ptr(), T,
+                                           above.data_ptr(), equal.data_ptr(), counted.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           _stream()), "dl_score_pair_ranks")
     cs = torch.cumsum(above, dim=0)
     g_sorted = cs[T] - cs[:T]                                         # candidates that found more than p targets below them
     t_sorted = equal[first]
@@ -1490,6 +1667,8 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None):
         tkey = lo.to(torch.int64) * N + hi.to(torch.int64)
         pos = torch.searchsorted(ex_key, tkey).clamp_(max=ex_key.numel() - 1)
         in_c = (ex_key[pos] != tkey).to(torch.int64)
+    if node_filter is not None:                                       # ... and only where the rule allows it
+        in_c = in_c * node_filter.allowed(lo, hi, unordered=True).to(torch.int64)
     greater = torch.empty(T, dtype=torch.int64, device=dev)
     ties = torch.empty(T, dtype=torch.int64, device=dev)
     greater[order] = g_sorted
@@ -1497,7 +1676,7 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None):
     return greater, ties - in_c, logit, total - in_c, counted
 
 
-def score_pair_ranks(Z, H, t: float, src, dst, exclude=None):
+def score_pair_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None):
     """-> (greater int64, ties int64, logit f32, n_others int64), each [T]: where the unordered target pairs
     {src[i], dst[i]} (either orientation; duplicates allowed; no self pairs) stand among ALL unordered pairs u < v < N of
     the graph outside ``exclude`` (a set of unordered pairs, as in ``score_mine``, or a prepared ``pair_exclusion``).  logit[i] is formed with the smaller
@@ -1506,5 +1685,7 @@ def score_pair_ranks(Z, H, t: float, src, dst, exclude=None):
     everything and equal only to NaN).  The filtered protocol of ``score_ranks``: a target is ranked whether or not it is
     excluded, other targets count as candidates unless excluded.  n_others[i] = candidates - [target i is one], so
     greater + ties <= n_others; rank = 1 + greater + ties / 2 (metrics.global_ranking_metrics).  Inference only; one
-    target pass and ONE scan (dl_score_pair_logits, dl_score_pair_ranks), nothing of size N x N, no cap at N = 46,340."""
-    return score_pair_ranks_counted(Z, H, t, src, dst, exclude)[:4]
+    target pass and ONE scan (dl_score_pair_logits, dl_score_pair_ranks), nothing of size N x N, no cap at N = 46,340.
+    ``node_filter`` (a symmetric ``NodeFilter``): the candidates are the pairs the rule allows outside ``exclude``; a target
+    is ranked whether or not it is allowed."""
+    return score_pair_ranks_counted(Z, H, t, src, dst, exclude, node_filter)[:4]

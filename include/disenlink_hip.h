@@ -580,6 +580,43 @@ int dl_score_pair_ranks(const float* Z, const float* H, int N, int K, int d, flo
                         unsigned long long* above, unsigned long long* equal, unsigned long long* n_candidates,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* A rule on node groups for the four candidate scans above (an extension; the reference has no counterpart): which KINDS of
+ * node may be linked, where an exclusion CSR could only list the O(N^2) pairs one by one.
+ *   group    [N] uint8, DEVICE: the group of every node, each < n_groups (a precondition: device data is not read back)
+ *   n_groups 1..64
+ *   allow    [n_groups] uint64, DEVICE: bit h of allow[g] set = a row of group g may take a partner of group h
+ * Ordered scans (dl_score_topk_filtered, dl_score_ranks_filtered): the row is the query node, the partner the candidate;
+ * allow may be asymmetric.  Unordered scans (dl_score_mine_filtered, dl_score_pair_ranks_filtered): the pair u < v is a
+ * candidate iff bit group[v] of allow[group[u]] is set; allow MUST be symmetric (bit h of allow[g] == bit g of allow[h]:
+ * a precondition, the rule of a pair would otherwise depend on the numbering of its nodes).
+ * The rule combines with the exclusion CSR, exclude_self and min_logit by AND: a candidate passes all of them.  Targets keep
+ * their contract: a target is ranked whether or not the rule allows it, and counts as a candidate of the other targets
+ * only if allowed and not excluded; n_candidates of dl_score_pair_ranks_filtered counts allowed, non-excluded pairs.
+ * The rule enters the scans' 128-bit row masks (group bytes of the candidate tile and the allow table in 768 bytes of
+ * LDS); products, logits, order, limits, supported shapes, workspace sizes and the _form functions are those of the
+ * unfiltered entries, and results stay independent of DL_RANK_SLICES / DL_MINE_TILES.  Every tile pair is still formed.
+ * Each entry takes the arguments of its unfiltered counterpart followed by the filter; NULL = no rule = the unfiltered
+ * call.  n_groups outside 1..64 or a NULL member fails with DL_E_ARG.  No allocation, no synchronisation, no host read. */
+typedef struct dl_node_filter {
+    const uint8_t* group;
+    int32_t n_groups;
+    const uint64_t* allow;
+} dl_node_filter;
+int dl_score_topk_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
+                           int k, const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index, float* logit,
+                           float* prob, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter);
+int dl_score_ranks_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
+                            const int32_t* tptr, const int32_t* tdst, int n_targets, const int32_t* ex_rowptr,
+                            const int32_t* ex_col, int64_t* greater, int64_t* ties, void* ws, size_t ws_bytes, void* stream,
+                            const dl_node_filter* filter);
+int dl_score_mine_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
+                           const int32_t* ex_col, float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob,
+                           int64_t* count, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter);
+int dl_score_pair_ranks_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
+                                 const int32_t* ex_col, const uint32_t* target_order, int n_targets, unsigned long long* above,
+                                 unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes,
+                                 void* stream, const dl_node_filter* filter);
+
 /* Tie-averaged AUC of a score vector against FIXED labels: replaces sklearn.metrics.roc_auc_score at
  * main_disentangled.py:202-204 / 217-219 (validation AUC every epoch, test AUC at the end).  pos_idx / neg_idx
  * (int64, device) are the positions of the positive and negative labels in score, found once per run; the call
