@@ -130,6 +130,11 @@ EXPORTS = {
     "dl_score_ranks_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P, _z, _P, _NF]),
     "dl_score_mine_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _i, _P, _P, _P, _P, _P, _P, _z, _P, _NF]),
     "dl_score_pair_ranks_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _i, _P, _P, _P, _P, _z, _P, _NF]),
+    "dl_score_links_supported": (_i, [_i, _i]),
+    "dl_score_links_form": (_i, [_i, _i, _i, C.POINTER(C.c_int)]),
+    "dl_score_links_workspace_bytes": (_z, [_i, _i, _i]),
+    "dl_score_links_count": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _NF, _P, _z, _P, _P]),
+    "dl_score_links_fill": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _NF, _P, _z, _P, C.c_int64, _P, _P, _P, _P]),
     "dl_auc_pair_counts_supported": (_i, [_i, _i]),
     "dl_auc_pair_counts": (_i, [_P, _P, _i, _P, _i, _P, _P]),
     "dl_auc_pair_counts_add": (_i, [_P, _P, _i, _P, _i, _P, _P]),
@@ -270,6 +275,16 @@ def score_pair_ranks_form(N: int, K: int, d: int, T: int) -> dict:
     out = (C.c_int * len(SCORE_PAIR_RANKS_FORM))()
     check(load().dl_score_pair_ranks_form(N, K, d, T, out), "dl_score_pair_ranks_form")
     return dict(zip(SCORE_PAIR_RANKS_FORM, out))
+
+
+SCORE_LINKS_FORM = ("nd", "tiles", "pairs", "pairs_per_wg", "grid", "scans", "cells")
+
+
+def score_links_form(N: int, K: int, d: int) -> dict:
+    """The link-graph scans' plan for this problem under the current DL_MINE_TILES (dl_score_links_form)."""
+    out = (C.c_int * len(SCORE_LINKS_FORM))()
+    check(load().dl_score_links_form(N, K, d, out), "dl_score_links_form")
+    return dict(zip(SCORE_LINKS_FORM, out))
 
 
 def config_reload() -> None:

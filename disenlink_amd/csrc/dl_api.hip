@@ -475,6 +475,61 @@ int dl_score_mine_filtered(const float* Z, const float* H, int N, int K, int d, 
                       filter);
 }
 
+int dl_score_links_supported(int K, int d) { return score_links_supported(K, d) ? 1 : 0; }
+
+static int check_links_shape(int N, int K, int d) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(score_links_supported(K, d), "the link-graph scan serves fp32 tables with 1 <= d <= 128, got d=%d", d);
+    DL_REQUIRE(N >= 1 && N <= DL_SCORE_LINKS_MAX_N, "N=%d outside 1..%d (the tile-pair walk of dl_score_mine)", N,
+               DL_SCORE_LINKS_MAX_N);
+    return DL_OK;
+}
+
+int dl_score_links_form(int N, int K, int d, int* out) {
+    if (int rc = check_links_shape(N, K, d)) return rc;
+    DL_REQUIRE(out != nullptr, "out is NULL");
+    score_links_form(N, d, out);
+    return DL_OK;
+}
+
+size_t dl_score_links_workspace_bytes(int N, int K, int d) {
+    if (N < 1 || N > DL_SCORE_LINKS_MAX_N || !score_links_supported(K, d)) return 0;
+    return score_links_workspace_bytes(N, K, d);
+}
+
+static int check_links_args(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
+                            const int32_t* ex_col, const dl_node_filter* filter, const void* ws, size_t ws_bytes,
+                            const int64_t* rowptr) {
+    if (int rc = check_links_shape(N, K, d)) return rc;
+    if (int rc = check_filter(filter)) return rc;
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    DL_REQUIRE(Z && H && rowptr, "NULL argument");
+    DL_REQUIRE((ex_rowptr == nullptr) == (ex_col == nullptr), "exclusion rowptr and col go together");
+    const size_t need = score_links_workspace_bytes(N, K, d);
+    if (!ws || ws_bytes < need) {
+        set_error("workspace too small: have %zu, need %zu (dl_score_links_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
+        return DL_E_WORKSPACE;
+    }
+    return DL_OK;
+}
+
+int dl_score_links_count(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
+                         const int32_t* ex_col, float min_logit, const dl_node_filter* filter, void* ws, size_t ws_bytes,
+                         int64_t* rowptr, void* stream) {
+    if (int rc = check_links_args(Z, H, N, K, d, t, ex_rowptr, ex_col, filter, ws, ws_bytes, rowptr)) return rc;
+    return score_links_count(Z, H, N, K, d, t, ex_rowptr, ex_col, min_logit, filter, ws, rowptr, (hipStream_t)stream);
+}
+
+int dl_score_links_fill(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
+                        const int32_t* ex_col, float min_logit, const dl_node_filter* filter, void* ws, size_t ws_bytes,
+                        const int64_t* rowptr, int64_t nnz, int32_t* col, float* logit, float* prob, void* stream) {
+    if (int rc = check_links_args(Z, H, N, K, d, t, ex_rowptr, ex_col, filter, ws, ws_bytes, rowptr)) return rc;
+    DL_REQUIRE(nnz >= 0, "nnz=%lld is negative", (long long)nnz);
+    DL_REQUIRE(nnz == 0 || (col && logit), "NULL output");
+    return score_links_fill(N, K, d, t, ex_rowptr, ex_col, min_logit, filter, ws, rowptr, (long long)nnz, col, logit, prob,
+                            (hipStream_t)stream);
+}
+
 int dl_score_pair_ranks_supported(int K, int d) { return score_rank_supported(K, d) ? 1 : 0; }
 
 // 128-row tiles whose pair count fits an int32: N <= 65,535 * 128

@@ -59,6 +59,7 @@ void dense_bwd_form(int N, int K, int d, int* out);
 void score_topk_form(int N, int d, int Q, int k, int* out);
 void score_mine_form(int N, int d, int m, int* out);
 void score_pair_ranks_form(int N, int d, int T, int* out);
+void score_links_form(int N, int d, int* out);
 
 // dense scorer on the matrix cores (dl_score_dense.hip): fp32 tables, d % 32 == 0
 bool dense_mfma_supported(int d);
@@ -98,6 +99,16 @@ size_t score_pair_ranks_workspace_bytes(int N, int K, int d);
 int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
                      const unsigned* tord, int T, unsigned long long* gcnt, unsigned long long* tcnt, unsigned long long* ncand,
                      void* ws, hipStream_t st, const dl_node_filter* filter = nullptr);
+
+// every unordered pair whose logit reaches a floor, as a symmetric CSR (dl_score_mine.hip: a counting scan, the offsets, a
+// filling scan over the workspace the count left): fp32 tables, 1 <= d <= 128, N <= 46,340
+bool score_links_supported(int K, int d);
+size_t score_links_workspace_bytes(int N, int K, int d);
+int score_links_count(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
+                      float min_logit, const dl_node_filter* filter, void* ws, int64_t* rowptr, hipStream_t st);
+int score_links_fill(int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit,
+                     const dl_node_filter* filter, void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit,
+                     float* prob, hipStream_t st);
 
 // tie-averaged AUC counts (dl_metrics.hip)
 bool auc_counts_supported(int n_pos, int n_neg);           // the smaller class fits the LDS

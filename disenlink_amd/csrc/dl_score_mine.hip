@@ -29,6 +29,17 @@
 // largest are summed per lane and added once per wave, and a wave whose lanes all found the same place adds once.  ncand
 // receives the number of candidates.  Suffix sums and the correction for the target itself are the caller's (ops.py).
 //
+// Link graph (dl_score_links_count / dl_score_links_fill, modes DEG and FILL of the same body): EVERY candidate at or above
+// the floor, however many, as a symmetric CSR with ascending columns, with no atomics and no arrival order on the output
+// path.  When a tile pair (qt, ct) completes, the waves form its 128 x 128 pass mask with ballots, row-major and
+// column-major (2 KB each, where the bins are in the other modes).  DEG: the row threads write popc of the rows to cell
+// (u, ct) of cnt [N][nt] and popc of the columns to cell (v, qt); on a diagonal pair both sides of a node are one cell, the
+// smaller neighbours first.  Every cell is written exactly once, by the workgroup that forms its tile pair, zeros included:
+// nothing is cleared beforehand and nothing is added.  Offsets: a wave per node turns its cells into their exclusive
+// prefix, and one workgroup scans the degrees into rowptr (64-bit).  FILL: the same scan and the same masks again; every
+// value that passed goes to slot rowptr[u] + cnt[u][ct] + (passed columns of its row below v), and likewise for (v, u);
+// a slot >= the caller's nnz is not written.  The walk of the tile pairs and its cap N <= 46,340 are the mining's.
+//
 // Node groups (the FILT instantiations; dl_score_mine_filtered, dl_score_pair_ranks_filtered): a symmetric rule on the groups
 // of u and v, formed into the row mask ahead of the exclusion; a candidate passes both.  The epilogues do not change.
 #include <cstddef>
@@ -48,7 +59,7 @@ constexpr int SDC = SPLIT_COLS, SLD = SPLIT_PITCH;
 constexpr int BINS = 2048;                 // the widest digit
 constexpr int PASSES = 6;
 constexpr int MAX_M = 65536;
-enum { HIST = 0, EMIT = 1, COUNT = 2 };
+enum { HIST = 0, EMIT = 1, COUNT = 2, DEG = 3, FILL = 4 };
 constexpr int SEPS = 4096;                 // COUNT: first-level separators of the sorted targets, in LDS
 
 typedef unsigned long long u64;
@@ -93,6 +104,10 @@ struct ScanArgs {
     const unsigned* tord;  int T, stride, nsep;
     u64 *gcnt, *tcnt, *ncand;
     FilterArgs filt;                           // FILT: the node-group rule (dl_tiles.h); symmetric, so the u row decides
+    // DEG / FILL (dl_score_links): cnt [N][nt], the eligible pairs of node r with partners in tile t (DEG writes the counts,
+    // the offsets kernel turns each row into its exclusive prefix, FILL reads that), and FILL's CSR (slots >= nnz are skipped)
+    unsigned* cnt;  const int64_t* rowptr;  long long nnz;
+    int32_t* col;  float *logit, *prob;
 };
 
 constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
@@ -122,11 +137,15 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     u64* fal = reinterpret_cast<u64*>(bins + (MODE == COUNT ? SEPS : BINS));           // FILT: allow [64] | cgrp [TT] | rgrp [TT]
     unsigned char* cgrp = reinterpret_cast<unsigned char*>(fal + 64);
 
+    constexpr bool LINKS = MODE == DEG || MODE == FILL;        // dl_score_links: no selection state, masks where the bins are
+    static_assert(2 * TT * 4 * 4 + 2 * TT * 8 <= BINS * 4, "the link masks and bases fit where the bins are");
+
     // device-side state, read at workgroup start: a finished search makes the remaining histogram scans return at once
-    const State S = *A.state;
+    const State S = LINKS ? State{} : *A.state;
     if (MODE == HIST && S.done) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (blockIdx.x == 0 && tid == 0) atomicAdd(&A.state->scans, 1u);
+    if constexpr (!LINKS)
+        if (blockIdx.x == 0 && tid == 0) atomicAdd(&A.state->scans, 1u);
     const int p0 = (int)blockIdx.x * A.per_wg;
     // COUNT serves tile-pair counts close to 2^31, where p0 + per_wg would overflow; the other modes keep their form (N <= 46,340)
     const int ntl = MODE == COUNT ? max(0, min(A.per_wg, A.pairs - p0)) : max(0, min(A.pairs, p0 + A.per_wg) - p0);
@@ -258,72 +277,170 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                 }
             }
         }
+        if constexpr (MODE == FILL) {                           // where the cells of this tile pair start in the CSR
+            long long* ubase = reinterpret_cast<long long*>(bins + 2 * TT * 4), *vbase = ubase + TT;
+            if (tid < TT) {
+                const int node = u0 + tid;
+                ubase[tid] = node < A.N ? (long long)A.rowptr[node] + (long long)A.cnt[(size_t)node * A.nt + ct] : 0ll;
+            } else if (tid < 2 * TT) {
+                const int node = v0 + tid - TT;
+                vbase[tid - TT] = node < A.N ? (long long)A.rowptr[node] + (long long)A.cnt[(size_t)node * A.nt + qt] : 0ll;
+            }
+        }
         __syncthreads();
+        if constexpr (LINKS) {
+            unsigned* pm = bins;                                // [TT][4] pass mask, bit v of row u
+            unsigned* pmt = bins + TT * 4;                      // [TT][4] its transpose, bit u of column v
+            const long long* ubase = reinterpret_cast<const long long*>(bins + 2 * TT * 4);    // FILL: [TT] first slot of cell (u, ct)
+            const long long* vbase = ubase + TT;                // FILL: [TT] first slot of cell (v, qt)
+            // The tile's pass mask, row-major and column-major, without atomics: a ballot holds 32 columns of two rows (one
+            // per half of the wave), and a lane gathers the 16 rows of its half for its column, the other half's by a swap.
+            // Ranks come from these masks, never from the order of lanes or of acc_row.
+            // Wave-uniform and constant terms are kept apart from the lane's (rows of a lane: rbase + acc_row(q, 0)), so that
+            // nothing per q is loop-invariant and held in registers across the product loop.
+            const int swu = __builtin_amdgcn_readfirstlane(wu), swv = __builtin_amdgcn_readfirstlane(wv);
+            const int hs4 = half * 4, rbase = swu * 32 + hs4;
+            unsigned okm = 0u;                                  // bit bb * 16 + q: this lane's value passed
 #pragma unroll
-        for (int bb = 0; bb < 2; ++bb) {
-            const int vl = wv * 64 + bb * 32 + li, v = v0 + vl;
+            for (int bb = 0; bb < 2; ++bb) {
+                const int vw = swv * 2 + bb, vl = vw * 32 + li, v = v0 + vl;
+                unsigned rows = 0u;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int row = wu * 32 + acc_row(q, half), u = u0 + row;
-                const float x = term[bb][q];
-                bool ok = u < v && v < A.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u) && (MODE == COUNT || x >= A.min_logit);
-                const u64 key = ((u64)ord_key(x) << 32) | (u64)(0xFFFFFFFFu - ((unsigned)u * (unsigned)A.N + (unsigned)v));
-                if constexpr (MODE == HIST) {
-                    if (hs < 64) ok = ok && (key >> hs) == (S.prefix >> hs);
-                    const unsigned dg = (unsigned)(key >> shift) & dmask;
-                    const u64 act = __ballot(ok);
-                    if (act != 0ull) {                          // wave-uniform: logits cluster, so one bin per wave is common
-                        const int first = __ffsll((long long)act) - 1;
-                        const unsigned d0 = (unsigned)__shfl((int)dg, first, DL_WAVE);
-                        if (__ballot(ok && dg == d0) == act) {
-                            if (lane == first) atomicAdd(&bins[d0], (unsigned)__popcll(act));
-                        } else if (ok) {
-                            atomicAdd(&bins[dg], 1u);
+                for (int q = 0; q < 16; ++q) {
+                    const int row = rbase + acc_row(q, 0), u = u0 + row;
+                    const bool ok = u < v && v < A.N && !((exm[row * 4 + vw] >> li) & 1u) && term[bb][q] >= A.min_logit;
+                    const u64 b = __ballot(ok);
+                    if (li == 0) pm[row * 4 + vw] = half ? (unsigned)(b >> 32) : (unsigned)b;
+                    rows |= ok ? 1u << acc_row(q, 0) : 0u;
+                    okm |= ok ? 1u << (bb * 16 + q) : 0u;
+                }
+                rows <<= hs4;
+                rows |= (unsigned)__shfl_xor((int)rows, 32, DL_WAVE);
+                if (half == 0) pmt[vl * 4 + swu] = rows;
+            }
+            __syncthreads();
+            const bool diag = qt == ct;
+            if constexpr (MODE == DEG) {
+                // cell (u, ct) from the rows, cell (v, qt) from the columns; on the diagonal both sides of a node are one cell.
+                // Every cell of every node < N is written once, by the one workgroup that forms its tile pair, zeros included.
+                if (tid < TT) {
+                    const int node = u0 + tid;
+                    const unsigned* w = pm + tid * 4;
+                    unsigned c = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
+                    if (diag) {
+                        const unsigned* wt = pmt + tid * 4;
+                        c += __popc(wt[0]) + __popc(wt[1]) + __popc(wt[2]) + __popc(wt[3]);
+                    }
+                    if (node < A.N) A.cnt[(size_t)node * A.nt + ct] = c;
+                } else if (tid < 2 * TT && !diag) {
+                    const int node = v0 + tid - TT;
+                    const unsigned* wt = pmt + (tid - TT) * 4;
+                    if (node < A.N) A.cnt[(size_t)node * A.nt + qt] = __popc(wt[0]) + __popc(wt[1]) + __popc(wt[2]) + __popc(wt[3]);
+                }
+            } else {
+                // slot of (u, v) in row u: the cell's start, on the diagonal the smaller neighbours of u first, then the passed
+                // columns below v; in row v: the cell's start and the passed rows below u.  Columns ascend within a row.
+#pragma unroll
+                for (int bb = 0; bb < 2; ++bb) {
+                    const int vw = swv * 2 + bb, vl = vw * 32 + li, v = v0 + vl;
+                    const unsigned* wt = pmt + vl * 4;
+                    const unsigned vword = wt[swu], vsh = vword >> hs4;
+                    const long long vb = vbase[vl] + (swu > 0 ? __popc(wt[0]) : 0) + (swu > 1 ? __popc(wt[1]) : 0) +
+                                         (swu > 2 ? __popc(wt[2]) : 0) + __popc(vword & ((1u << hs4) - 1u));
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        if (!((okm >> (bb * 16 + q)) & 1u)) continue;
+                        const int row = rbase + acc_row(q, 0), u = u0 + row;
+                        const unsigned* w = pm + row * 4;
+                        long long su = ubase[row] + (vw > 0 ? __popc(w[0]) : 0) + (vw > 1 ? __popc(w[1]) : 0) + (vw > 2 ? __popc(w[2]) : 0) +
+                                       __popc(w[vw] & ((1u << li) - 1u));
+                        if (diag) {
+                            const unsigned* ut = pmt + row * 4;
+                            su += __popc(ut[0]) + __popc(ut[1]) + __popc(ut[2]) + __popc(ut[3]);
+                        }
+                        const long long sv = vb + __popc(vsh & ((1u << acc_row(q, 0)) - 1u));
+                        const float x = term[bb][q] == 0.0f ? 0.0f : term[bb][q];      // -0 is reported as +0
+                        const float pr = A.prob != nullptr ? sigmoid_ref(x) : 0.0f;
+                        if ((u64)su < (u64)A.nnz) {
+                            A.col[su] = v;
+                            A.logit[su] = x;
+                            if (A.prob != nullptr) A.prob[su] = pr;
+                        }
+                        if ((u64)sv < (u64)A.nnz) {
+                            A.col[sv] = u;
+                            A.logit[sv] = x;
+                            if (A.prob != nullptr) A.prob[sv] = pr;
                         }
                     }
-                } else if constexpr (MODE == EMIT) {
-                    if (ok && key >= S.prefix) {
-                        const unsigned slot = atomicAdd(&A.state->emitted, 1u);
-                        if (slot < (unsigned)A.m) A.keys[slot] = key;
-                    }
-                } else {
-                    // place of the candidate among the sorted targets: lo = targets strictly below it (they count it as
-                    // "greater": +1 at gcnt[lo], summed from the top on the host), and the equal range, if any, starts at lo
-                    const unsigned o = ord_key(x);
-                    ncount += ok ? 1ull : 0ull;
-                    nabove += (ok && o > tmax) ? 1ull : 0ull;
-                    const bool in = ok && o >= tmin && o <= tmax;
-                    int lo = 0;
-                    bool tie = false;
-                    if (in) {
-                        int a = 0, b = A.nsep;                  // separators below o: [0, a)
-                        while (a < b) {
-                            const int mid = (a + b) >> 1;
-                            if (bins[mid] < o) a = mid + 1; else b = mid;
-                        }
-                        if (a > 0) {                            // target (a-1) stride < o <= target a stride (or the end)
-                            int l = (a - 1) * A.stride + 1, h = min(a * A.stride, A.T);
-                            while (l < h) {
-                                const int mid = (l + h) >> 1;
-                                if (A.tord[mid] < o) l = mid + 1; else h = mid;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int bb = 0; bb < 2; ++bb) {
+                const int vl = wv * 64 + bb * 32 + li, v = v0 + vl;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int row = wu * 32 + acc_row(q, half), u = u0 + row;
+                    const float x = term[bb][q];
+                    bool ok = u < v && v < A.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u) && (MODE == COUNT || x >= A.min_logit);
+                    const u64 key = ((u64)ord_key(x) << 32) | (u64)(0xFFFFFFFFu - ((unsigned)u * (unsigned)A.N + (unsigned)v));
+                    if constexpr (MODE == HIST) {
+                        if (hs < 64) ok = ok && (key >> hs) == (S.prefix >> hs);
+                        const unsigned dg = (unsigned)(key >> shift) & dmask;
+                        const u64 act = __ballot(ok);
+                        if (act != 0ull) {                          // wave-uniform: logits cluster, so one bin per wave is common
+                            const int first = __ffsll((long long)act) - 1;
+                            const unsigned d0 = (unsigned)__shfl((int)dg, first, DL_WAVE);
+                            if (__ballot(ok && dg == d0) == act) {
+                                if (lane == first) atomicAdd(&bins[d0], (unsigned)__popcll(act));
+                            } else if (ok) {
+                                atomicAdd(&bins[dg], 1u);
                             }
-                            lo = l;
                         }
-                        tie = A.tord[lo] == o;                  // lo < T: o <= tmax
-                    }
-                    const u64 act = __ballot(in);
-                    if (act != 0ull) {                          // wave-uniform; one place per wave where the logits cluster
-                        const int first = __ffsll((long long)act) - 1;
-                        const int l0 = __shfl(lo, first, DL_WAVE);
-                        if (__ballot(in && lo == l0) == act) {
-                            const u64 eq = __ballot(in && tie);
-                            if (lane == first) {
-                                if (l0 > 0) atomicAdd(&A.gcnt[l0], (u64)__popcll(act));
-                                if (eq != 0ull) atomicAdd(&A.tcnt[l0], (u64)__popcll(eq));
+                    } else if constexpr (MODE == EMIT) {
+                        if (ok && key >= S.prefix) {
+                            const unsigned slot = atomicAdd(&A.state->emitted, 1u);
+                            if (slot < (unsigned)A.m) A.keys[slot] = key;
+                        }
+                    } else {
+                        // place of the candidate among the sorted targets: lo = targets strictly below it (they count it as
+                        // "greater": +1 at gcnt[lo], summed from the top on the host), and the equal range, if any, starts at lo
+                        const unsigned o = ord_key(x);
+                        ncount += ok ? 1ull : 0ull;
+                        nabove += (ok && o > tmax) ? 1ull : 0ull;
+                        const bool in = ok && o >= tmin && o <= tmax;
+                        int lo = 0;
+                        bool tie = false;
+                        if (in) {
+                            int a = 0, b = A.nsep;                  // separators below o: [0, a)
+                            while (a < b) {
+                                const int mid = (a + b) >> 1;
+                                if (bins[mid] < o) a = mid + 1; else b = mid;
                             }
-                        } else if (in) {
-                            if (lo > 0) atomicAdd(&A.gcnt[lo], 1ull);
-                            if (tie) atomicAdd(&A.tcnt[lo], 1ull);
+                            if (a > 0) {                            // target (a-1) stride < o <= target a stride (or the end)
+                                int l = (a - 1) * A.stride + 1, h = min(a * A.stride, A.T);
+                                while (l < h) {
+                                    const int mid = (l + h) >> 1;
+                                    if (A.tord[mid] < o) l = mid + 1; else h = mid;
+                                }
+                                lo = l;
+                            }
+                            tie = A.tord[lo] == o;                  // lo < T: o <= tmax
+                        }
+                        const u64 act = __ballot(in);
+                        if (act != 0ull) {                          // wave-uniform; one place per wave where the logits cluster
+                            const int first = __ffsll((long long)act) - 1;
+                            const int l0 = __shfl(lo, first, DL_WAVE);
+                            if (__ballot(in && lo == l0) == act) {
+                                const u64 eq = __ballot(in && tie);
+                                if (lane == first) {
+                                    if (l0 > 0) atomicAdd(&A.gcnt[l0], (u64)__popcll(act));
+                                    if (eq != 0ull) atomicAdd(&A.tcnt[l0], (u64)__popcll(eq));
+                                }
+                            } else if (in) {
+                                if (lo > 0) atomicAdd(&A.gcnt[lo], 1ull);
+                                if (tie) atomicAdd(&A.tcnt[lo], 1ull);
+                            }
                         }
                     }
                 }
@@ -475,6 +592,53 @@ __global__ __launch_bounds__(256) void order_kernel(const State* st, const u64* 
         logit[i] = __uint_as_float(0x7FC00000u);
         prob[i] = __uint_as_float(0x7FC00000u);
     }
+}
+
+// ---- dl_score_links: the offsets between the DEG and the FILL scan
+// One wave per node: its nt cells become their exclusive prefix in place (at most N - 1 < 2^16 in all), the total its degree.
+__global__ __launch_bounds__(256) void link_cells_kernel(unsigned* cnt, unsigned* deg, int N, int nt) {
+    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= N) return;                                       // wave-uniform
+    unsigned* c = cnt + (size_t)row * nt;
+    unsigned run = 0u;
+    for (int b = 0; b < nt; b += DL_WAVE) {
+        const int i = b + lane;
+        const unsigned x = i < nt ? c[i] : 0u;
+        unsigned inc = x;
+#pragma unroll
+        for (int o = 1; o < DL_WAVE; o <<= 1) {
+            const unsigned y = (unsigned)__shfl_up((int)inc, o, DL_WAVE);
+            if (lane >= o) inc += y;
+        }
+        if (i < nt) c[i] = run + inc - x;
+        run += (unsigned)__shfl((int)inc, DL_WAVE - 1, DL_WAVE);
+    }
+    if (lane == 0) deg[row] = run;
+}
+
+// One workgroup: rowptr = the exclusive 64-bit prefix of the degrees, rowptr[N] = nnz.  Thread i sums a run of consecutive
+// nodes, the 1,024 sums are scanned in LDS, and the thread walks its run again.  scanned = 0 (N < 2): no pair, all zeros.
+__global__ __launch_bounds__(1024) void link_rowptr_kernel(const unsigned* __restrict__ deg, int64_t* rowptr, int N, int scanned) {
+    __shared__ long long part[1024];
+    const int tid = threadIdx.x, per = (N + 1023) / 1024;
+    const int lo = min(N, tid * per), hi = min(N, lo + per);
+    long long sum = 0;
+    if (scanned)
+        for (int i = lo; i < hi; ++i) sum += (long long)deg[i];
+    part[tid] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const long long y = tid >= o ? part[tid - o] : 0ll;
+        __syncthreads();
+        part[tid] += y;
+        __syncthreads();
+    }
+    long long run = part[tid] - sum;
+    for (int i = lo; i < hi; ++i) {
+        rowptr[i] = (int64_t)run;
+        if (scanned) run += (long long)deg[i];
+    }
+    if (tid == 1023) rowptr[N] = (int64_t)part[1023];
 }
 
 }  // namespace mine
@@ -682,6 +846,99 @@ int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float 
         }
     }
     return check_launch("score_pair_ranks");
+}
+
+// ---- dl_score_links: every eligible pair as a symmetric CSR — a DEG scan, the offsets, then (second call) a FILL scan
+bool score_links_supported(int K, int d) { return score_mine_supported(K, d); }
+
+// out = nd, tiles, tile pairs, tile pairs per workgroup, workgroups of a scan, scans of count + fill, cells of cnt
+void score_links_form(int N, int d, int* out) {
+    const MinePlan p = mine_plan(N, d);
+    out[0] = p.nd;
+    out[1] = p.nt;
+    out[2] = p.pairs;
+    out[3] = p.per_wg;
+    out[4] = p.grid;
+    out[5] = p.pairs > 0 ? 2 : 0;
+    out[6] = N * p.nt;                                          // <= 46,340 * 363
+}
+
+// Workspace (256-byte aligned blocks): planes of Z and H | cnt [N][nt] | deg [N]
+struct LinksWs { __bf16 *cz, *ch; unsigned *cnt, *deg; size_t bytes; };
+static LinksWs links_carve(const MinePlan& p, int N, int K, void* ws) {
+    LinksWs w = {};
+    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        char* r = base + o;
+        o += (bytes + 255) & ~(size_t)255;
+        return (void*)r;
+    };
+    w.cz = (__bf16*)take(2 * (size_t)K * p.cbatch);
+    w.ch = (__bf16*)take(2 * (size_t)K * p.cbatch);
+    w.cnt = (unsigned*)take(sizeof(unsigned) * (size_t)N * p.nt);
+    w.deg = (unsigned*)take(sizeof(unsigned) * (size_t)N);
+    w.bytes = o + 256;
+    return w;
+}
+
+size_t score_links_workspace_bytes(int N, int K, int d) { return links_carve(mine_plan(N, d), N, K, nullptr).bytes; }
+
+static ScanArgs links_args(const MinePlan& p, const LinksWs& w, int N, int K, float t, const int32_t* exr, const int32_t* exc,
+                           float min_logit, const dl_node_filter* nf) {
+    ScanArgs a = {};
+    a.cz = w.cz; a.ch = w.ch; a.cbatch = p.cbatch;
+    a.N = N; a.K = K; a.nd = p.nd; a.nt = p.nt; a.t = t;
+    a.ex_rowptr = exr; a.ex_col = exc;
+    a.min_logit = min_logit;
+    a.pairs = p.pairs; a.per_wg = p.per_wg;
+    a.cnt = w.cnt;
+    if (nf != nullptr) a.filt = FilterArgs{nf->group, (const u64*)nf->allow, nf->n_groups};
+    return a;
+}
+
+int score_links_count(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
+                      float min_logit, const dl_node_filter* nf, void* ws, int64_t* rowptr, hipStream_t st) {
+    static unsigned long long lds_deg = 0, lds_deg_f = 0;
+    const MinePlan p = mine_plan(N, d);
+    const LinksWs w = links_carve(p, N, K, ws);
+    if (p.pairs > 0) {
+        split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
+        split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
+        const ScanArgs a = links_args(p, w, N, K, t, exr, exc, min_logit, nf);
+        if (nf != nullptr) {
+            constexpr size_t LB = LDS_BYTES + FILTER_LDS_BYTES;
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<DEG, true>), LB, lds_deg_f);
+            hipLaunchKernelGGL((scan_tiles<DEG, true>), dim3((unsigned)p.grid), dim3(MTHR), LB, st, a);
+        } else {
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<DEG>), LDS_BYTES, lds_deg);
+            hipLaunchKernelGGL(scan_tiles<DEG>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
+        }
+        hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, w.cnt, w.deg, N, p.nt);
+    }
+    hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, w.deg, rowptr, N, p.pairs > 0 ? 1 : 0);
+    return check_launch("score_links_count");
+}
+
+int score_links_fill(int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit, const dl_node_filter* nf,
+                     void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit, float* prob, hipStream_t st) {
+    static unsigned long long lds_fill = 0, lds_fill_f = 0;
+    const MinePlan p = mine_plan(N, d);
+    const LinksWs w = links_carve(p, N, K, ws);
+    if (p.pairs > 0 && nnz > 0) {
+        ScanArgs a = links_args(p, w, N, K, t, exr, exc, min_logit, nf);
+        a.rowptr = rowptr; a.nnz = nnz;
+        a.col = col; a.logit = logit; a.prob = prob;
+        if (nf != nullptr) {
+            constexpr size_t LB = LDS_BYTES + FILTER_LDS_BYTES;
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<FILL, true>), LB, lds_fill_f);
+            hipLaunchKernelGGL((scan_tiles<FILL, true>), dim3((unsigned)p.grid), dim3(MTHR), LB, st, a);
+        } else {
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<FILL>), LDS_BYTES, lds_fill);
+            hipLaunchKernelGGL(scan_tiles<FILL>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
+        }
+    }
+    return check_launch("score_links_fill");
 }
 
 }  // namespace dl

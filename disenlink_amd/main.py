@@ -67,11 +67,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "edges (Disentangle.top_missing_links; single GPU, fp32 tables)")
     p.add_argument("--mine-out", type=str, default=None, metavar="FILE",
                    help="with --mine: write the list to FILE as text, one `src dst logit prob` line per pair")
+    p.add_argument("--predict-links", type=float, default=None, metavar="P",
+                   help="after the last run, form the predicted graph: every pair that is not a dataset edge and whose "
+                        "link_pred reaches P (Disentangle.predicted_links; single GPU, fp32 tables, N <= 46340), and print "
+                        "the number of links, the density and the mean / max predicted degree")
+    p.add_argument("--links-out", type=str, default=None, metavar="FILE",
+                   help="with --predict-links: write the links to FILE as text, one `src dst prob` line per pair, src < dst")
     p.add_argument("--node-groups", type=str, default=None, metavar="FILE",
                    help="with --link-rule: the group (an integer in 0..63) of every node, one per node, as text or .npy")
     p.add_argument("--link-rule", choices=["same", "different"], default=None,
-                   help="with --node-groups: --rank-eval, --global-rank-eval and --mine take as candidates only links "
-                        "between nodes of the same / of different groups (ops.NodeFilter)")
+                   help="with --node-groups: --rank-eval, --global-rank-eval, --mine and --predict-links take as candidates "
+                        "only links between nodes of the same / of different groups (ops.NodeFilter)")
     p.add_argument("--sparse-features", action="store_true",
                    help="hand the features to the model as features.SparseFeatures (scale * X + shift with X a CSR): layer 1 "
                         "of the projection and its gradient run as gathers over the non-zero entries; for binary / one-hot "
@@ -262,6 +268,24 @@ def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=pri
     return mined
 
 
+def predict_links(model, x, graph, known, min_prob: float, out=None, log=print, node_filter=None):
+    """--predict-links: every link outside ``known`` whose link_pred reaches ``min_prob`` (Disentangle.predicted_links), a
+    summary line printed and, with ``out``, all of them written as `src dst prob` lines, src < dst."""
+    links = model.predicted_links(x, graph, min_prob, exclude=known, node_filter=node_filter)
+    n = links.n_nodes
+    src, dst, _, prob = (v.cpu().numpy() for v in links.pairs())
+    deg = links.degree.cpu().numpy()
+    density = src.size / (n * (n - 1) / 2) if n > 1 else 0.0
+    log(f"predicted {src.size} links at prob >= {min_prob:g}: density {density:.6g} mean degree {deg.mean():.6g} "
+        f"max degree {int(deg.max())}")
+    if out:
+        with open(out, "w") as fh:                                   # millions of lines at a useful threshold: by chunks
+            for i in range(0, src.size, 1 << 16):
+                rows = zip(src[i:i + (1 << 16)].tolist(), dst[i:i + (1 << 16)].tolist(), prob[i:i + (1 << 16)].tolist())
+                fh.write("".join(f"{a} {b} {p:.9g}\n" for a, b, p in rows))
+    return links
+
+
 def _fmt_ranking(r: dict) -> str:
     return " ".join(f"{key} {val:.4f}" for key, val in r.items())
 
@@ -294,10 +318,18 @@ def main(argv=None):
                          "--gpus / --table-dtype bf16 or --mine")
     if args.mine and not 1 <= args.mine <= 65536:
         raise SystemExit("--mine M: 1 <= M <= 65536")
+    if args.predict_links is not None and (args.gpus > 1 or args.table_dtype == "bf16"):
+        raise SystemExit("--predict-links runs on one GPU with fp32 tables only (sharded and bf16 link graphs are not "
+                         "implemented): drop --gpus / --table-dtype bf16 or --predict-links")
+    if args.predict_links is not None and not 0.0 <= args.predict_links <= 1.0:
+        raise SystemExit("--predict-links P: 0 <= P <= 1")
+    if args.links_out and args.predict_links is None:
+        raise SystemExit("--links-out FILE goes with --predict-links P")
     if (args.node_groups is None) != (args.link_rule is None):
         raise SystemExit("--node-groups FILE and --link-rule {same,different} go together")
-    if args.link_rule and not (args.rank_eval or args.global_rank_eval or args.mine):
-        raise SystemExit("--link-rule restricts the candidates of --rank-eval, --global-rank-eval and --mine: give one of them")
+    if args.link_rule and not (args.rank_eval or args.global_rank_eval or args.mine or args.predict_links is not None):
+        raise SystemExit("--link-rule restricts the candidates of --rank-eval, --global-rank-eval, --mine and --predict-links: "
+                         "give one of them")
     if args.gpus > 1:
         from .launch import launch_ranks, under_launcher
         if not under_launcher():                                    # BEFORE any GPU call: the parent starts and waits
@@ -331,7 +363,7 @@ def main(argv=None):
     result = []
     ranking = []
     global_ranking = []
-    if args.rank_eval or args.mine or args.global_rank_eval:        # filter: every dataset edge, both directions
+    if args.rank_eval or args.mine or args.global_rank_eval or args.predict_links is not None:      # filter: every dataset edge, both directions
         s_all, d_all = torch.from_numpy(np.asarray(ds.src)).long(), torch.from_numpy(np.asarray(ds.dst)).long()
         known = (torch.cat([s_all, d_all]).to(device), torch.cat([d_all, s_all]).to(device))
     node_filter = load_node_groups(args.node_groups, ds.n_nodes, args.link_rule, device) if args.link_rule else None
@@ -358,6 +390,8 @@ def main(argv=None):
                 print("test global ranking:", _fmt_ranking(global_ranking[-1]))
     if args.mine and args.run > 0:                                  # the last run's model, its best weights
         mine_links(model, x, prepared.graph, known, args.mine, args.mine_out, node_filter=node_filter)
+    if args.predict_links is not None and args.run > 0:
+        predict_links(model, x, prepared.graph, known, args.predict_links, args.links_out, node_filter=node_filter)
     result = np.array(result)
     tail = []                                                       # the run means of the ranking metrics join the final line
     if args.rank_eval:

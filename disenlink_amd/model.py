@@ -33,6 +33,35 @@ MinedLinks = namedtuple("MinedLinks", ["src", "dst", "logit", "prob"])
 PairRanks = namedtuple("PairRanks", ["greater", "ties", "logit", "n_others"])
 
 
+class PredictedLinks(namedtuple("PredictedLinks", ["rowptr", "col", "logit", "prob"])):
+    """The predicted graph of ``Disentangle.predicted_links``: a symmetric CSR over all nodes (rowptr int64 [N+1], col int32
+    [nnz], logit / prob f32 [nnz]); every link {u, v} is stored as (u, v) and as (v, u), columns ascending within a row."""
+    __slots__ = ()
+
+    @property
+    def n_nodes(self) -> int:
+        return int(self.rowptr.numel()) - 1
+
+    @property
+    def degree(self) -> torch.Tensor:
+        """int64 [N]: the predicted degree of every node."""
+        return self.rowptr[1:] - self.rowptr[:-1]
+
+    def _rows(self) -> torch.Tensor:
+        return torch.repeat_interleave(torch.arange(self.n_nodes, device=self.rowptr.device), self.degree)
+
+    def pairs(self):
+        """(src int64 [P], dst int64 [P], logit f32 [P], prob f32 [P]): every link once, src < dst, in ascending
+        src * N + dst order (the order of the CSR's upper triangle)."""
+        rows, cols = self._rows(), self.col.long()
+        keep = rows < cols
+        return rows[keep], cols[keep], self.logit[keep], self.prob[keep]
+
+    def to_graph(self) -> Graph:
+        """The links as a graph.Graph, as ``Disentangle.forward`` takes it."""
+        return Graph.from_edge_rows(self._rows(), self.col.long(), self.n_nodes, symmetrise=False)
+
+
 class Factor(nn.Module):
     """One Linear(F -> d); used when nhid == 1 (model.py:7-15, :94-95)."""
 
@@ -414,6 +443,24 @@ class Disentangle(nn.Module):
         with torch.no_grad():
             return MinedLinks(*ops.score_mine(Z, H, float(self.temperature), m, graph if exclude is None else exclude, floor,
                                               node_filter))
+
+    def predicted_links(self, x, adj, min_prob, exclude=None, node_filter=None) -> PredictedLinks:
+        """The predicted graph: EVERY unordered pair whose link_pred reaches ``min_prob`` and that is not known yet, as
+        PredictedLinks(rowptr, col, logit, prob), a symmetric CSR over all nodes with ``.degree``, ``.pairs()`` and
+        ``.to_graph()`` (ops.score_links: two scans, nothing of size N x N is formed, no cap on the number of links).
+        ``exclude``: the known pairs, as a Graph, a dense [N,N] mask or (rows, cols), in either orientation; None = the
+        edges of ``adj`` itself.  ``min_prob`` in [0, 1] is turned into a logit floor on the host, as in
+        ``top_missing_links`` (0.5 -> 0.0).  ``node_filter``: a symmetric ops.NodeFilter that pairs must pass as well.
+        N <= 46,340, fp32 tables."""
+        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        Z, H = self._rank_tables(x, graph)
+        p = float(min_prob)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"min_prob={p} outside [0, 1]")
+        floor = float("-inf") if p == 0.0 else float("inf") if p == 1.0 else math.log(p) - math.log1p(-p)
+        with torch.no_grad():
+            return PredictedLinks(*ops.score_links(Z, H, float(self.temperature), floor, graph if exclude is None else exclude,
+                                                   node_filter))
 
     def missing_link_ranks(self, x, adj, src, dst, exclude=None, node_filter=None) -> PairRanks:
         """Where the unordered pairs {src[i], dst[i]} stand among ALL unordered pairs of the graph, in the order

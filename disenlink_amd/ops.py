@@ -1565,6 +1565,57 @@ def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-
     return src[:c], dst[:c], logit[:c], prob[:c]
 
 
+# ---------------------------------------------------------------------- every pair above a floor, as a CSR (DEG / FILL scans)
+LINKS_MAX_N = MINE_MAX_N
+
+
+def _links_count(Z, H, t, min_logit, exclude, node_filter):
+    """The count pass of ``score_links``: -> (rowptr int64 [N+1] on the device, the arguments of the fill pass)."""
+    lib = _lib.load()
+    _filter_check(node_filter, Z, True)
+    Z, H, N, K, d = _rank_tables(Z, H)
+    if N > LINKS_MAX_N:
+        raise ValueError(f"N={N} above {LINKS_MAX_N} (the tile-pair walk of dl_score_mine)")
+    excl = _csr_args(*_unordered_exclusion_csr(exclude, N, Z.device), Z.device)
+    nf, _keep_nf = node_filter._c_arg(N, Z.device, True) if node_filter is not None else (None, ())
+    # a workspace of its own, held across the two calls: the shared grow-only buffer may be handed out (and, under DL_POISON,
+    # refilled) in between, and the fill pass reads the planes and the cell offsets the count pass left
+    ws = _empty(max(256, int(lib.dl_score_links_workspace_bytes(N, K, d))), torch.uint8, Z.device)
+    rowptr = _empty(N + 1, torch.int64, Z.device)
+    head = (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), excl[0], excl[1], float(min_logit), nf, ws.data_ptr(), ws.numel(),
+            rowptr.data_ptr())
+    _lib.check(lib.dl_score_links_count(*head, _stream()), "dl_score_links_count")
+    return rowptr, head, (Z, H, excl, _keep_nf, ws)
+
+
+def score_links(Z, H, t: float, min_logit: float, exclude=None, node_filter=None):
+    """-> (rowptr int64 [N+1], col int32 [nnz], logit f32 [nnz], prob f32 [nnz]): the predicted graph, EVERY unordered pair
+    whose logit s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred) reaches ``min_logit``, as a
+    symmetric CSR over all N nodes — each pair as (u, v) and as (v, u) with the same bits, columns ascending within a row,
+    prob = sigmoid(logit).  Eligibility is ``score_mine``'s without m: u != v, outside ``exclude`` (a ``Graph``, a dense
+    [N,N] mask or ``(rows, cols)``, taken as unordered pairs), allowed by ``node_filter`` (a symmetric ``NodeFilter``), NaN
+    never; the bits are those of ``score_pair_logits(min(u, v), max(u, v))``.  N <= 46,340, fp32 tables.  Inference only;
+    nothing of size N x N is formed (dl_score_links_count / dl_score_links_fill: two scans), there is no cap on nnz, and the
+    one host read is that of rowptr[N], between the scans, to allocate the outputs.  Same bits on every call."""
+    lib = _lib.load()
+    rowptr, head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter)
+    nnz = int(rowptr[-1].item())                                      # the one host read
+    dev = rowptr.device
+    col = _empty(nnz, torch.int32, dev)
+    logit = _empty(nnz, torch.float32, dev)
+    prob = _empty(nnz, torch.float32, dev)
+    _lib.check(lib.dl_score_links_fill(*head, nnz, col.data_ptr(), logit.data_ptr(), prob.data_ptr(), _stream()),
+               "dl_score_links_fill")
+    return rowptr, col, logit, prob
+
+
+def score_link_degrees(Z, H, t: float, min_logit: float, exclude=None, node_filter=None):
+    """-> int64 [N]: the predicted degree of every node, i.e. how many partners ``score_links`` would list for it — the
+    count pass alone (dl_score_links_count): one scan, no host read, no fill."""
+    rowptr, _head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter)
+    return rowptr[1:] - rowptr[:-1]
+
+
 # ---------------------------------------------------------------------- where given pairs stand among ALL pairs (COUNT scan)
 def _order_keys(logit: torch.Tensor) -> torch.Tensor:
     """The scans' total order of fp32 values as int64 keys in [0, 2^32): NaN -> 0, -0 as +0, larger value = larger key."""

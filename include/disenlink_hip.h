@@ -617,6 +617,49 @@ int dl_score_pair_ranks_filtered(const float* Z, const float* H, int N, int K, i
                                  unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes,
                                  void* stream, const dl_node_filter* filter);
 
+/* The thresholded link graph (an extension; the reference has no counterpart): EVERY unordered pair whose logit reaches a
+ * floor, as a symmetric CSR over all N nodes, with nothing of size N x N in memory and no cap on the number of pairs.
+ * Eligible: exactly dl_score_mine's rule without m — u < v < N, v not among the columns of row u of the exclusion CSR
+ * (the row of the SMALLER endpoint, as there), allowed by the node filter if one is given (symmetric, NULL = none), and
+ * s >= min_logit (a NaN logit is never eligible; -0 reaches a floor of 0).  The logit has the bits dl_score_pair_logits
+ * returns for (u, v), the smaller endpoint as the A operand; a -0 is reported as +0.
+ * Result: rowptr int64 [N+1], col int32 [nnz], logit / prob fp32 [nnz] (prob = sigmoid(logit)); every eligible pair {u, v}
+ * appears as (u, v) and as (v, u) with the same bits, columns within a row strictly ascending; nnz = rowptr[N] = twice the
+ * number of eligible pairs, rowptr[r + 1] - rowptr[r] the predicted degree of node r.
+ * Two calls with the same arguments, because the caller allocates col / logit / prob between them:
+ *   dl_score_links_count: splits the planes of Z and H into the workspace, runs one scan of dl_score_mine's tile pairs that
+ *     writes, per node and 128-node tile, the number of eligible partners in that tile (cnt [N][tiles] in the workspace: each
+ *     cell is written exactly once, so nothing is zeroed first and nothing is added atomically), turns every row of cnt into
+ *     its exclusive prefix and writes rowptr (a DEVICE array; the call reads nothing back).
+ *   dl_score_links_fill: one more scan over the workspace the count left (Z and H are not read again: the workspace must be
+ *     the same memory, untouched in between), which recomputes the logits with the same instruction stream and writes every
+ *     eligible pair at rowptr[u] + cnt[u][tile of v] + its rank in the tile's pass mask, and likewise for (v, u).  nnz is the
+ *     length of col / logit / prob (the caller's read of rowptr[N]); a slot >= nnz is not written, so a call that does not
+ *     match its count cannot write out of bounds.  prob may be NULL (not wanted); nnz = 0 launches nothing.
+ * No atomics on the output path and no dependence on arrival order: the same bits on every call and under every
+ * DL_MINE_TILES.
+ * Limits: 1 <= N <= 46340 (DL_SCORE_LINKS_MAX_N: the tile-pair walk of dl_score_mine); fp32 tables with 1 <= d <= 128
+ * (dl_score_links_supported, as dl_score_mine_supported); anything else fails, as do nnz < 0, NULL tables, a bad filter and
+ * a missing or short workspace (DL_E_WORKSPACE).  No allocation, no synchronisation, no host read; the caller's stream.
+ * ws: dl_score_links_workspace_bytes(N, K, d) (0 for arguments out of range): the planes of Z and H, cnt (4 N tiles bytes:
+ * 60 MB at N = 41,554 against 6.9 GB for an [N,N] fp32 matrix) and the degrees. */
+#define DL_SCORE_LINKS_MAX_N 46340
+int dl_score_links_supported(int K, int d);                /* fp32 tables, 1 <= d <= 128, as dl_score_mine_supported */
+/* The launch plan under the current DL_MINE_TILES (host only).  out[DL_SCORE_LINKS_FORM_LEN] =
+ *   [0] 32-column chunks of the padded factor width  [1] 128-row tiles  [2] tile pairs (u tile <= v tile)
+ *   [3] tile pairs per workgroup  [4] workgroups of a scan  [5] scans of count + fill (0 for N < 2)  [6] cells of cnt */
+#define DL_SCORE_LINKS_FORM_LEN 7
+int dl_score_links_form(int N, int K, int d, int* out);
+size_t dl_score_links_workspace_bytes(int N, int K, int d);
+int dl_score_links_count(const float* Z, const float* H, int N, int K, int d, float t,
+                         const int32_t* ex_rowptr, const int32_t* ex_col,      /* known pairs, both NULL = none */
+                         float min_logit, const dl_node_filter* filter,        /* NULL = no rule */
+                         void* ws, size_t ws_bytes, int64_t* rowptr, void* stream);
+int dl_score_links_fill(const float* Z, const float* H, int N, int K, int d, float t,
+                        const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit, const dl_node_filter* filter,
+                        void* ws, size_t ws_bytes, const int64_t* rowptr, int64_t nnz,
+                        int32_t* col, float* logit, float* prob, void* stream);
+
 /* Tie-averaged AUC of a score vector against FIXED labels: replaces sklearn.metrics.roc_auc_score at
  * main_disentangled.py:202-204 / 217-219 (validation AUC every epoch, test AUC at the end).  pos_idx / neg_idx
  * (int64, device) are the positions of the positive and negative labels in score, found once per run; the call
