@@ -362,24 +362,70 @@ size_t dl_score_topk_workspace_bytes(int N, int K, int d, int n_queries, int k, 
     return score_rank_workspace_bytes(N, K, d, n_queries, k, n_targets);
 }
 
-static int check_rank_args(const void* Z, const void* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
-                           const int32_t* ex_rowptr, const int32_t* ex_col) {
-    if (int rc = check_shape(K, d)) return rc;
-    DL_REQUIRE(score_rank_supported(K, d), "the ranking scan serves fp32 tables with 1 <= d <= 128, got d=%d", d);
-    DL_REQUIRE(N >= 1 && n_queries >= 0, "bad size N=%d n_queries=%d", N, n_queries);
-    DL_REQUIRE((long long)N * K * d < (1LL << 40), "tables too large");
-    DL_REQUIRE(t != 0.0f, "temperature is 0");
-    DL_REQUIRE(n_queries == 0 || (Z && H && queries), "NULL argument");
-    DL_REQUIRE(ex_rowptr == nullptr || ex_col != nullptr, "exclusion rowptr without col");
-    return DL_OK;
-}
-
 // a node-group rule (NULL = none): host-side checks only, the arrays are device memory
 static int check_filter(const dl_node_filter* f) {
     if (f == nullptr) return DL_OK;
     DL_REQUIRE(f->n_groups >= 1 && f->n_groups <= 64, "node filter: n_groups=%d outside 1..64", f->n_groups);
     DL_REQUIRE(f->group != nullptr && f->allow != nullptr, "node filter: NULL group or allow array");
     return DL_OK;
+}
+
+// ---- the all-pairs scans (dl_score_rank.hip, dl_score_mine.hip): one checklist, and what differs between the families
+enum ScanFlags : unsigned {
+    OWN_N = 1,          // the entry reports the range of N itself, with its own text
+    CAP_ELEMS = 2,      // N K d < 2^40
+    EX_TOGETHER = 4,    // exclusion rowptr and col go together (else: col follows rowptr)
+    WS_CODE = 8,        // a small workspace is DL_E_WORKSPACE (else DL_E_ARG, in the ranking entries' words)
+};
+struct ScanSpec {
+    const char* serves;                        // who refuses an unsupported (K, d)
+    int n_min, n_max;  const char* n_why;      // range of N and its reason
+    unsigned flags;
+};
+static const ScanSpec RANK_SCAN = {"the ranking scan serves", 1, 2147483647, "", OWN_N};
+static const ScanSpec MINE_SCAN = {"the link-mining scan serves", 0, 46340, "the pair index u N + v must fit 31 bits",
+                                   EX_TOGETHER | WS_CODE};
+static const ScanSpec LINKS_SCAN = {"the link-graph scan serves", 1, DL_SCORE_LINKS_MAX_N, "the tile-pair walk of dl_score_mine",
+                                    EX_TOGETHER | WS_CODE};
+// 128-row tiles whose pair count fits an int32: N <= 65,535 * 128
+static const ScanSpec PAIR_SCAN = {"the pair scans serve", 1, DL_SCORE_PAIR_RANKS_MAX_N, "the tile-pair count must fit 31 bits",
+                                   CAP_ELEMS | EX_TOGETHER | WS_CODE};
+static_assert((DL_SCORE_PAIR_RANKS_MAX_N / 128LL) * (DL_SCORE_PAIR_RANKS_MAX_N / 128LL + 1) / 2 <= 2147483647LL &&
+              DL_SCORE_PAIR_RANKS_MAX_N % 128 == 0, "65,535 tiles of 128 rows: 2,147,450,880 tile pairs");
+
+static bool scan_shape_ok(const ScanSpec& s, int N, int K, int d) {      // the *_workspace_bytes entries: 0 where a call is refused
+    return N >= s.n_min && N <= s.n_max && score_rank_supported(K, d) &&
+           (!(s.flags & CAP_ELEMS) || (long long)N * K * d < (1LL << 40));
+}
+static int check_scan_shape(const ScanSpec& s, int N, int K, int d) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(score_rank_supported(K, d), "%s fp32 tables with 1 <= d <= 128, got d=%d", s.serves, d);
+    if (!(s.flags & OWN_N)) DL_REQUIRE(N >= s.n_min && N <= s.n_max, "N=%d outside %d..%d (%s)", N, s.n_min, s.n_max, s.n_why);
+    if (s.flags & CAP_ELEMS) DL_REQUIRE((long long)N * K * d < (1LL << 40), "tables too large");
+    return DL_OK;
+}
+// have_args: the entry's pointers are there.  Filter, t and ranges stay with the entry: their order decides what is reported.
+static int check_scan_ptrs(const ScanSpec& s, bool have_args, const int32_t* ex_rowptr, const int32_t* ex_col) {
+    DL_REQUIRE(have_args, "NULL argument");
+    if (s.flags & EX_TOGETHER) DL_REQUIRE((ex_rowptr == nullptr) == (ex_col == nullptr), "exclusion rowptr and col go together");
+    else DL_REQUIRE(ex_rowptr == nullptr || ex_col != nullptr, "exclusion rowptr without col");
+    return DL_OK;
+}
+static int check_scan_ws(const ScanSpec& s, const void* ws, size_t ws_bytes, size_t need, const char* sizer) {
+    if (ws != nullptr && ws_bytes >= need) return DL_OK;
+    const size_t have = ws ? ws_bytes : (size_t)0;
+    if (s.flags & WS_CODE) set_error("workspace too small: have %zu, need %zu (%s)", have, need, sizer);
+    else set_error("workspace too small: %zu < %zu bytes (%s)", have, need, sizer);
+    return (s.flags & WS_CODE) ? DL_E_WORKSPACE : DL_E_ARG;
+}
+
+static int check_rank_args(const void* Z, const void* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
+                           const int32_t* ex_rowptr, const int32_t* ex_col) {
+    if (int rc = check_scan_shape(RANK_SCAN, N, K, d)) return rc;
+    DL_REQUIRE(N >= 1 && n_queries >= 0, "bad size N=%d n_queries=%d", N, n_queries);
+    DL_REQUIRE((long long)N * K * d < (1LL << 40), "tables too large");
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    return check_scan_ptrs(RANK_SCAN, n_queries == 0 || (Z && H && queries), ex_rowptr, ex_col);
 }
 
 int dl_score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries, int k,
@@ -398,8 +444,7 @@ int dl_score_topk_filtered(const float* Z, const float* H, int N, int K, int d, 
     if (n_queries == 0) return DL_OK;
     DL_REQUIRE(index && logit && prob, "NULL output");
     const size_t need = score_rank_workspace_bytes(N, K, d, n_queries, k, 0);
-    DL_REQUIRE(ws != nullptr && ws_bytes >= need, "workspace too small: %zu < %zu bytes (dl_score_topk_workspace_bytes)",
-               ws ? ws_bytes : (size_t)0, need);
+    if (int rc = check_scan_ws(RANK_SCAN, ws, ws_bytes, need, "dl_score_topk_workspace_bytes")) return rc;
     return score_topk(Z, H, N, K, d, t, queries, n_queries, k, ex_rowptr, ex_col, exclude_self, index, logit, prob, ws,
                       (hipStream_t)stream, filter);
 }
@@ -422,8 +467,7 @@ int dl_score_ranks_filtered(const float* Z, const float* H, int N, int K, int d,
     DL_REQUIRE(tptr && tdst && greater && ties, "NULL argument");
     DL_REQUIRE((long long)n_targets + n_queries < (1LL << 31), "too many targets");
     const size_t need = score_rank_workspace_bytes(N, K, d, n_queries, 0, n_targets);
-    DL_REQUIRE(ws != nullptr && ws_bytes >= need, "workspace too small: %zu < %zu bytes (dl_score_topk_workspace_bytes)",
-               ws ? ws_bytes : (size_t)0, need);
+    if (int rc = check_scan_ws(RANK_SCAN, ws, ws_bytes, need, "dl_score_topk_workspace_bytes")) return rc;
     return score_ranks(Z, H, N, K, d, t, queries, n_queries, tptr, tdst, n_targets, ex_rowptr, ex_col, greater, ties, ws,
                        (hipStream_t)stream, filter);
 }
@@ -431,9 +475,7 @@ int dl_score_ranks_filtered(const float* Z, const float* H, int N, int K, int d,
 int dl_score_mine_supported(int K, int d) { return score_mine_supported(K, d) ? 1 : 0; }
 
 static int check_mine_shape(int N, int K, int d, int m) {
-    if (int rc = check_shape(K, d)) return rc;
-    DL_REQUIRE(score_mine_supported(K, d), "the link-mining scan serves fp32 tables with 1 <= d <= 128, got d=%d", d);
-    DL_REQUIRE(N >= 0 && N <= 46340, "N=%d outside 0..46340 (the pair index u N + v must fit 31 bits)", N);
+    if (int rc = check_scan_shape(MINE_SCAN, N, K, d)) return rc;
     DL_REQUIRE(m >= 1 && m <= 65536, "m=%d outside 1..65536", m);
     return DL_OK;
 }
@@ -446,7 +488,7 @@ int dl_score_mine_form(int N, int K, int d, int m, int* out) {
 }
 
 size_t dl_score_mine_workspace_bytes(int N, int K, int d, int m) {
-    if (N < 0 || N > 46340 || m < 1 || m > 65536 || !score_mine_supported(K, d)) return 0;
+    if (!scan_shape_ok(MINE_SCAN, N, K, d) || m < 1 || m > 65536) return 0;
     return score_mine_workspace_bytes(N, K, d, m);
 }
 
@@ -463,54 +505,36 @@ int dl_score_mine_filtered(const float* Z, const float* H, int N, int K, int d, 
     if (int rc = check_mine_shape(N, K, d, m)) return rc;
     if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
-    DL_REQUIRE(N == 0 || (Z && H), "NULL argument");
-    DL_REQUIRE((ex_rowptr == nullptr) == (ex_col == nullptr), "exclusion rowptr and col go together");
+    if (int rc = check_scan_ptrs(MINE_SCAN, N == 0 || (Z && H), ex_rowptr, ex_col)) return rc;
     DL_REQUIRE(src && dst && logit && prob && count, "NULL output");
-    const size_t need = score_mine_workspace_bytes(N, K, d, m);
-    if (!ws || ws_bytes < need) {
-        set_error("workspace too small: have %zu, need %zu (dl_score_mine_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
-        return DL_E_WORKSPACE;
-    }
+    if (int rc = check_scan_ws(MINE_SCAN, ws, ws_bytes, score_mine_workspace_bytes(N, K, d, m), "dl_score_mine_workspace_bytes"))
+        return rc;
     return score_mine(Z, H, N, K, d, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws, (hipStream_t)stream,
                       filter);
 }
 
 int dl_score_links_supported(int K, int d) { return score_links_supported(K, d) ? 1 : 0; }
 
-static int check_links_shape(int N, int K, int d) {
-    if (int rc = check_shape(K, d)) return rc;
-    DL_REQUIRE(score_links_supported(K, d), "the link-graph scan serves fp32 tables with 1 <= d <= 128, got d=%d", d);
-    DL_REQUIRE(N >= 1 && N <= DL_SCORE_LINKS_MAX_N, "N=%d outside 1..%d (the tile-pair walk of dl_score_mine)", N,
-               DL_SCORE_LINKS_MAX_N);
-    return DL_OK;
-}
-
 int dl_score_links_form(int N, int K, int d, int* out) {
-    if (int rc = check_links_shape(N, K, d)) return rc;
+    if (int rc = check_scan_shape(LINKS_SCAN, N, K, d)) return rc;
     DL_REQUIRE(out != nullptr, "out is NULL");
     score_links_form(N, d, out);
     return DL_OK;
 }
 
 size_t dl_score_links_workspace_bytes(int N, int K, int d) {
-    if (N < 1 || N > DL_SCORE_LINKS_MAX_N || !score_links_supported(K, d)) return 0;
-    return score_links_workspace_bytes(N, K, d);
+    return scan_shape_ok(LINKS_SCAN, N, K, d) ? score_links_workspace_bytes(N, K, d) : 0;
 }
 
+// what the count and the fill call check alike
 static int check_links_args(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
                             const int32_t* ex_col, const dl_node_filter* filter, const void* ws, size_t ws_bytes,
                             const int64_t* rowptr) {
-    if (int rc = check_links_shape(N, K, d)) return rc;
+    if (int rc = check_scan_shape(LINKS_SCAN, N, K, d)) return rc;
     if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
-    DL_REQUIRE(Z && H && rowptr, "NULL argument");
-    DL_REQUIRE((ex_rowptr == nullptr) == (ex_col == nullptr), "exclusion rowptr and col go together");
-    const size_t need = score_links_workspace_bytes(N, K, d);
-    if (!ws || ws_bytes < need) {
-        set_error("workspace too small: have %zu, need %zu (dl_score_links_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
-        return DL_E_WORKSPACE;
-    }
-    return DL_OK;
+    if (int rc = check_scan_ptrs(LINKS_SCAN, Z && H && rowptr, ex_rowptr, ex_col)) return rc;
+    return check_scan_ws(LINKS_SCAN, ws, ws_bytes, score_links_workspace_bytes(N, K, d), "dl_score_links_workspace_bytes");
 }
 
 int dl_score_links_count(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
@@ -532,47 +556,31 @@ int dl_score_links_fill(const float* Z, const float* H, int N, int K, int d, flo
 
 int dl_score_pair_ranks_supported(int K, int d) { return score_rank_supported(K, d) ? 1 : 0; }
 
-// 128-row tiles whose pair count fits an int32: N <= 65,535 * 128
-static int check_pair_shape(int N, int K, int d) {
-    if (int rc = check_shape(K, d)) return rc;
-    DL_REQUIRE(score_rank_supported(K, d), "the pair scans serve fp32 tables with 1 <= d <= 128, got d=%d", d);
-    DL_REQUIRE(N >= 1 && N <= DL_SCORE_PAIR_RANKS_MAX_N, "N=%d outside 1..%d (the tile-pair count must fit 31 bits)", N,
-               DL_SCORE_PAIR_RANKS_MAX_N);
-    static_assert((DL_SCORE_PAIR_RANKS_MAX_N / 128LL) * (DL_SCORE_PAIR_RANKS_MAX_N / 128LL + 1) / 2 <= 2147483647LL &&
-                  DL_SCORE_PAIR_RANKS_MAX_N % 128 == 0, "65,535 tiles of 128 rows: 2,147,450,880 tile pairs");
-    DL_REQUIRE((long long)N * K * d < (1LL << 40), "tables too large");
-    return DL_OK;
-}
-
 int dl_score_pair_ranks_form(int N, int K, int d, int n_targets, int* out) {
-    if (int rc = check_pair_shape(N, K, d)) return rc;
+    if (int rc = check_scan_shape(PAIR_SCAN, N, K, d)) return rc;
     DL_REQUIRE(out != nullptr && n_targets >= 0, "bad argument");
     score_pair_ranks_form(N, d, n_targets, out);
     return DL_OK;
 }
 
 size_t dl_score_pair_logits_workspace_bytes(int N, int K, int d) {
-    if (N < 1 || N > DL_SCORE_PAIR_RANKS_MAX_N || !score_rank_supported(K, d) || (long long)N * K * d >= (1LL << 40)) return 0;
-    return score_pair_logits_workspace_bytes(N, K, d);
+    return scan_shape_ok(PAIR_SCAN, N, K, d) ? score_pair_logits_workspace_bytes(N, K, d) : 0;
 }
 
 size_t dl_score_pair_ranks_workspace_bytes(int N, int K, int d) {
-    if (N < 1 || N > DL_SCORE_PAIR_RANKS_MAX_N || !score_rank_supported(K, d) || (long long)N * K * d >= (1LL << 40)) return 0;
-    return score_pair_ranks_workspace_bytes(N, K, d);
+    return scan_shape_ok(PAIR_SCAN, N, K, d) ? score_pair_ranks_workspace_bytes(N, K, d) : 0;
 }
 
 int dl_score_pair_logits(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
                          int n_pairs, float* logit, void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = check_pair_shape(N, K, d)) return rc;
+    if (int rc = check_scan_shape(PAIR_SCAN, N, K, d)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     DL_REQUIRE(n_pairs >= 0 && n_pairs <= (1 << 30), "n_pairs=%d outside 0..2^30", n_pairs);
     if (n_pairs == 0) return DL_OK;
-    DL_REQUIRE(Z && H && a && b && logit, "NULL argument");
-    const size_t need = score_pair_logits_workspace_bytes(N, K, d);
-    if (!ws || ws_bytes < need) {
-        set_error("workspace too small: have %zu, need %zu (dl_score_pair_logits_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
-        return DL_E_WORKSPACE;
-    }
+    if (int rc = check_scan_ptrs(PAIR_SCAN, Z && H && a && b && logit, nullptr, nullptr)) return rc;
+    if (int rc = check_scan_ws(PAIR_SCAN, ws, ws_bytes, score_pair_logits_workspace_bytes(N, K, d),
+                               "dl_score_pair_logits_workspace_bytes"))
+        return rc;
     return score_pair_logits(Z, H, N, K, d, t, a, b, n_pairs, logit, ws, (hipStream_t)stream);
 }
 
@@ -587,17 +595,14 @@ int dl_score_pair_ranks_filtered(const float* Z, const float* H, int N, int K, i
                                  const int32_t* ex_col, const uint32_t* target_order, int n_targets, unsigned long long* above,
                                  unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes,
                                  void* stream, const dl_node_filter* filter) {
-    if (int rc = check_pair_shape(N, K, d)) return rc;
+    if (int rc = check_scan_shape(PAIR_SCAN, N, K, d)) return rc;
     if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     DL_REQUIRE(n_targets >= 0 && n_targets <= (1 << 30), "n_targets=%d outside 0..2^30", n_targets);
-    DL_REQUIRE(Z && H && above && equal && n_candidates && (n_targets == 0 || target_order), "NULL argument");
-    DL_REQUIRE((ex_rowptr == nullptr) == (ex_col == nullptr), "exclusion rowptr and col go together");
+    const bool have = Z && H && above && equal && n_candidates && (n_targets == 0 || target_order);
+    if (int rc = check_scan_ptrs(PAIR_SCAN, have, ex_rowptr, ex_col)) return rc;
     const size_t need = score_pair_ranks_workspace_bytes(N, K, d);
-    if (!ws || ws_bytes < need) {
-        set_error("workspace too small: have %zu, need %zu (dl_score_pair_ranks_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
-        return DL_E_WORKSPACE;
-    }
+    if (int rc = check_scan_ws(PAIR_SCAN, ws, ws_bytes, need, "dl_score_pair_ranks_workspace_bytes")) return rc;
     return score_pair_ranks(Z, H, N, K, d, t, ex_rowptr, ex_col, target_order, n_targets, above, equal, n_candidates, ws,
                             (hipStream_t)stream, filter);
 }

@@ -15,12 +15,13 @@
 #include <cstdlib>
 #include "dl_common.h"
 #include "dl_kernels.h"
-#include "dl_tiles.h"
+#include "dl_scan.h"
 
 namespace dl {
 namespace dense {
 
 using namespace project;       // TileStage, PlaneStage, f32x16, acc_row, split3 planes
+using namespace scan;          // the step arithmetic the candidate scans share
 
 constexpr int TT = 128;        // tile edge (u and v)
 constexpr int DTHR = 512;
@@ -104,8 +105,8 @@ __global__ __launch_bounds__(DTHR) void score_allpairs_split_kernel(const float*
     for (int s = 0; s < steps; ++s) {
         const int r = s % (2 * nd);
         // lane half h supplies k = 8h .. 8h+7 of each 16-wide block; A = u rows of this quarter, B = v rows
-        const __bf16* ub = us + (s & 1) * 3 * TT * SLD + (wu * 32 + li) * SLD + half * 8;
-        const __bf16* vb = vs + (s & 1) * 3 * TT * SLD + (wv * 64 + li) * SLD + half * 8;
+        const __bf16* ub = gram_operand(us, s, wu * 32 + li, half);
+        const __bf16* vb = gram_operand(vs, s, wv * 64 + li, half);
 #pragma unroll
         for (int kb = 0; kb < SDC / 16; ++kb) {
             gram_block_split6(acc, ub, vb, kb);                 // dl_tiles.h: six products, smallest terms first
@@ -114,21 +115,7 @@ __global__ __launch_bounds__(DTHR) void score_allpairs_split_kernel(const float*
                 fetch(min(s + 2, steps - 1));                   // unconditional: see TileStage (dl_tiles.h)
             }
         }
-        if (r == nd - 1) {                                      // S complete: e = exp(S / t)
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) e[bb][q] = expf(div_t(acc[bb][q], t));
-                zero_acc(acc[bb]);
-            }
-        } else if (r == 2 * nd - 1) {                           // Q complete: term += Q * e
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) term[bb][q] += acc[bb][q] * e[bb][q];
-                zero_acc(acc[bb]);
-            }
-        }
+        factor_update(acc, e, term, r, nd, t);                  // S complete: e = exp(S / t); Q complete: term += Q * e
         __syncthreads();
     }
     // Stores.  The two products of a swapped pair are accumulated in a different order here (hi*lo before lo*hi), so
@@ -202,23 +189,17 @@ void dense_mfma_form(int N, int K, int d, size_t ws_bytes, int* out) {
 int dense_mfma_score_allpairs_fwd(const float* Z, const float* H, int N, int K, int d, float t, float* prob, void* ws,
                                   size_t ws_bytes, hipStream_t st) {
     using namespace dense;
-    static unsigned long long lds_done_p = 0, lds_done_s = 0;
     constexpr size_t lds = (size_t)2 * 2 * 3 * TT * SLD * 2;
     const Launch L = launch_of(N, K, d, ws != nullptr, ws_bytes);
-    const dim3 grid(L.grid);
     if (L.planes) {                                         // planes made once per call
         const size_t batch = project::plane_array_elems(N, d, project::SPLIT_COLS);
         __bf16* zp = static_cast<__bf16*>(ws);
         __bf16* hp = zp + (size_t)K * batch;
         project::split_rows(Z, K, N, d, K * d, (size_t)d, zp, st);
         project::split_rows(H, K, N, d, K * d, (size_t)d, hp, st);
-        project::ensure_dynamic_lds(reinterpret_cast<const void*>(&score_allpairs_split_kernel<true>), lds, lds_done_p);
-        hipLaunchKernelGGL(score_allpairs_split_kernel<true>, grid, dim3(DTHR), lds, st, Z, H, N, K, d, t, prob,
-                           DensePlanes{zp, hp, batch});
+        launch_lds<score_allpairs_split_kernel<true>>(L.grid, DTHR, lds, st, Z, H, N, K, d, t, prob, DensePlanes{zp, hp, batch});
     } else {                                                // no workspace: every tile pair splits what it stages
-        project::ensure_dynamic_lds(reinterpret_cast<const void*>(&score_allpairs_split_kernel<false>), lds, lds_done_s);
-        hipLaunchKernelGGL(score_allpairs_split_kernel<false>, grid, dim3(DTHR), lds, st, Z, H, N, K, d, t, prob,
-                           DensePlanes{nullptr, nullptr, 0});
+        launch_lds<score_allpairs_split_kernel<false>>(L.grid, DTHR, lds, st, Z, H, N, K, d, t, prob, DensePlanes{nullptr, nullptr, 0});
     }
     return check_launch("score_allpairs_fwd(split bf16)");
 }

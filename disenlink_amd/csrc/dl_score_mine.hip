@@ -46,12 +46,12 @@
 #include "dl_common.h"
 #include "dl_config.h"
 #include "dl_kernels.h"
-#include "dl_tiles.h"
+#include "dl_scan.h"
 
 namespace dl {
 namespace mine {
 
-using namespace project;
+using namespace scan;         // the step arithmetic, keys, exclusion walk and host scaffolding of the scans
 
 constexpr int TT = 128;
 constexpr int MTHR = 512;
@@ -62,22 +62,9 @@ constexpr int MAX_M = 65536;
 enum { HIST = 0, EMIT = 1, COUNT = 2, DEG = 3, FILL = 4 };
 constexpr int SEPS = 4096;                 // COUNT: first-level separators of the sorted targets, in LDS
 
-typedef unsigned long long u64;
-
 // the digits of the key, from the top: value 11 + 11 + 10 bits, index 11 + 11 + 10 bits
 __host__ __device__ inline int digit_shift(int p) { return p == 0 ? 53 : p == 1 ? 42 : p == 2 ? 32 : p == 3 ? 21 : p == 4 ? 10 : 0; }
 __host__ __device__ inline int digit_bits(int p) { return (p == 2 || p == 5) ? 10 : 11; }
-
-// dl_score_rank.hip's total order: NaN -> 0, every other value (-0 taken as +0) to its order-preserving image
-__device__ __forceinline__ unsigned ord_key(float x) {
-    if (x != x) return 0u;
-    const unsigned b = __float_as_uint(x == 0.0f ? 0.0f : x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord_value(unsigned o) {
-    if (o == 0u) return __uint_as_float(0x7FC00000u);
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
 
 // Selection state in the workspace (device memory; the library's host code never reads it)
 struct State {
@@ -90,24 +77,32 @@ struct State {
     unsigned pad;
 };
 
+// One kernel argument: what every scan reads, then what one family of modes reads
+struct SelectArgs {                            // HIST / EMIT (dl_score_mine)
+    int m, pass;                               // pass: HIST's digit
+    unsigned* hist;  u64* keys;
+};
+struct CountArgs {                             // COUNT (dl_score_pair_ranks): the ascending order keys of the T targets, every
+    const unsigned* tord;                      // stride-th of them a separator, and the 64-bit counters: gcnt [T+1] (difference
+    int T, stride, nsep;                       // array of "greater"), tcnt [T+1] (equal range, at its first place), ncand [1]
+    u64 *gcnt, *tcnt, *ncand;
+};
+struct LinkArgs {                              // DEG / FILL (dl_score_links): cnt [N][nt], the eligible pairs of node r with
+    unsigned* cnt;                             // partners in tile t (DEG writes the counts, the offsets kernel turns each row into
+    const int64_t* rowptr;  long long nnz;     // its exclusive prefix, FILL reads that), and FILL's CSR (slots >= nnz are skipped)
+    int32_t* col;  float *logit, *prob;
+};
 struct ScanArgs {
     const __bf16 *cz, *ch;  size_t cbatch;     // planes of Z and H
     int N, K, nd, nt;  float t;
     const int32_t *ex_rowptr, *ex_col;
-    float min_logit;
-    int m;
+    float min_logit;                           // the floor (COUNT has none)
     int pairs, per_wg;                         // tile pairs, tile pairs per workgroup
-    int pass;                                  // HIST: the digit
-    State* state;  unsigned* hist;  u64* keys;
-    // COUNT (dl_score_pair_ranks): the ascending order keys of the T targets, every stride-th of them a separator, and the
-    // 64-bit counters: gcnt [T+1] (difference array of "greater"), tcnt [T+1] (equal range, at its first place), ncand [1]
-    const unsigned* tord;  int T, stride, nsep;
-    u64 *gcnt, *tcnt, *ncand;
     FilterArgs filt;                           // FILT: the node-group rule (dl_tiles.h); symmetric, so the u row decides
-    // DEG / FILL (dl_score_links): cnt [N][nt], the eligible pairs of node r with partners in tile t (DEG writes the counts,
-    // the offsets kernel turns each row into its exclusive prefix, FILL reads that), and FILL's CSR (slots >= nnz are skipped)
-    unsigned* cnt;  const int64_t* rowptr;  long long nnz;
-    int32_t* col;  float *logit, *prob;
+    State* state;                              // HIST / EMIT / COUNT: the selection state and the count of scans; DEG / FILL: none
+    SelectArgs sel;
+    CountArgs cnt;
+    LinkArgs link;
 };
 
 constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
@@ -124,6 +119,87 @@ __device__ __forceinline__ u64 wave_sum(u64 x) {
     return x;
 }
 
+// ---- the epilogues: what a mode does with a complete tile pair.  term[bb][q] = s(u, v) of row L.row(q) and column L.col(bb)
+// of the pair's 128 x 128 tile, exm its [128][4] mask of columns a row may not take (exclusion and, FILT, the group rule).
+struct Lane {
+    int wu, wv, li, half, lane;
+    __device__ __forceinline__ int row(int q) const { return wu * 32 + acc_row(q, half); }
+    __device__ __forceinline__ int col(int bb) const { return wv * 64 + bb * 32 + li; }
+};
+struct Tile { int u0, v0, N; };               // first node of the u tile and of the v tile; nodes of the graph
+__device__ __forceinline__ bool eligible(const unsigned* exm, const Tile T, int row, int vl) {
+    return T.u0 + row < T.v0 + vl && T.v0 + vl < T.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u);
+}
+
+// HIST: the digit of pass `pass` of the keys that carry the threshold's higher digits, counted in the LDS bins
+struct Digit { int shift, hs; unsigned dmask; u64 prefix; };      // hs: bits below the chosen prefix
+__device__ __forceinline__ void hist_epilogue(const f32x16 (&term)[2], const unsigned* exm, unsigned* bins, const Lane L, const Tile T,
+                                              float min_logit, const Digit D) {
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb) {
+        const int vl = L.col(bb);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int row = L.row(q);
+            const float x = term[bb][q];
+            bool ok = eligible(exm, T, row, vl) && x >= min_logit;
+            const u64 key = make_key(x, (unsigned)(T.u0 + row) * (unsigned)T.N + (unsigned)(T.v0 + vl));
+            if (D.hs < 64) ok = ok && (key >> D.hs) == (D.prefix >> D.hs);
+            const unsigned dg = (unsigned)(key >> D.shift) & D.dmask;
+            const u64 act = __ballot(ok);
+            if (act != 0ull) {                                  // wave-uniform: logits cluster, so one bin per wave is common
+                const int first = __ffsll((long long)act) - 1;
+                const unsigned d0 = (unsigned)__shfl((int)dg, first, DL_WAVE);
+                if (__ballot(ok && dg == d0) == act) {
+                    if (L.lane == first) atomicAdd(&bins[d0], (unsigned)__popcll(act));
+                } else if (ok) {
+                    atomicAdd(&bins[dg], 1u);
+                }
+            }
+        }
+    }
+}
+__device__ __forceinline__ void hist_flush(const unsigned* bins, unsigned* hist, int tid) {
+    __syncthreads();
+    for (int i = tid; i < BINS; i += MTHR) {
+        const unsigned c = bins[i];
+        if (c) atomicAdd(&hist[i], c);
+    }
+}
+
+// EMIT: every candidate at or above the threshold key, appended in arrival order (order_kernel sorts)
+__device__ __forceinline__ void emit_epilogue(const f32x16 (&term)[2], const unsigned* exm, const Lane L, const Tile T, float min_logit,
+                                              u64 threshold, State* state, u64* keys, int m) {
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb) {
+        const int vl = L.col(bb);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int row = L.row(q);
+            const float x = term[bb][q];
+            const bool ok = eligible(exm, T, row, vl) && x >= min_logit;
+            const u64 key = make_key(x, (unsigned)(T.u0 + row) * (unsigned)T.N + (unsigned)(T.v0 + vl));
+            if (ok && key >= threshold) {
+                const unsigned slot = atomicAdd(&state->emitted, 1u);
+                if (slot < (unsigned)m) keys[slot] = key;
+            }
+        }
+    }
+}
+
+// COUNT, at the end of the kernel: one add per wave
+__device__ __forceinline__ void count_flush(const CountArgs& C, u64 ncount, u64 nabove, int lane) {
+    ncount = wave_sum(ncount);
+    nabove = wave_sum(nabove);
+    if (lane == 0) {
+        if (ncount) atomicAdd(C.ncand, ncount);
+        if (nabove) atomicAdd(&C.gcnt[C.T], nabove);
+    }
+}
+
+// One body for all modes: every scan forms the logits with this loop (fetch, stash, products, factor update), so that the
+// keys are the same bits in every scan; a mode's epilogue is a function above (HIST, EMIT) or, where that spilled or ran
+// slower, a block of the body (COUNT, the link modes).  A new mode adds an epilogue and its part of ScanArgs, not a loop.
 // FILT: the node-group rule on top of the exclusion, as in the ranking scan (dl_score_rank.hip): the groups of the pair's v
 // and u nodes are staged in the pair's last step but one, all 512 threads form the mask from the rule, one word each, in its
 // last step, and the row threads OR the exclusion into it where the unfiltered kernel starts from zero.
@@ -133,17 +209,20 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
     __bf16* vs = us + 2 * 3 * TT * SLD;
     unsigned* exm = reinterpret_cast<unsigned*>(vs + 2 * 3 * TT * SLD);   // [TT][4]: excluded columns of the tile
-    unsigned* bins = exm + TT * 4;                              // HIST: [BINS]; COUNT: [SEPS] separators
+    unsigned* bins = exm + TT * 4;                              // HIST: [BINS]; COUNT: [SEPS] separators; DEG / FILL: masks, bases
     u64* fal = reinterpret_cast<u64*>(bins + (MODE == COUNT ? SEPS : BINS));           // FILT: allow [64] | cgrp [TT] | rgrp [TT]
     unsigned char* cgrp = reinterpret_cast<unsigned char*>(fal + 64);
-
     constexpr bool LINKS = MODE == DEG || MODE == FILL;        // dl_score_links: no selection state, masks where the bins are
     static_assert(2 * TT * 4 * 4 + 2 * TT * 8 <= BINS * 4, "the link masks and bases fit where the bins are");
 
-    // device-side state, read at workgroup start: a finished search makes the remaining histogram scans return at once
-    const State S = LINKS ? State{} : *A.state;
-    if (MODE == HIST && S.done) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    // device-side state, read at workgroup start: a finished search makes the remaining histogram scans return at once
+    Digit D = {};
+    if constexpr (MODE == HIST || MODE == EMIT) {
+        const State S = *A.state;
+        if (MODE == HIST && S.done) return;
+        D.prefix = S.prefix;
+    }
     if constexpr (!LINKS)
         if (blockIdx.x == 0 && tid == 0) atomicAdd(&A.state->scans, 1u);
     const int p0 = (int)blockIdx.x * A.per_wg;
@@ -167,19 +246,20 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     const int nd = A.nd;
     const int per_tile = A.K * 2 * nd;
     const int steps = ntl * per_tile;
-    const int shift = MODE == HIST ? digit_shift(A.pass) : 0;
-    const unsigned dmask = MODE == HIST ? (1u << digit_bits(A.pass)) - 1u : 0u;
-    const int hs = shift + (MODE == HIST ? digit_bits(A.pass) : 0);          // bits below the chosen prefix
-    if constexpr (MODE == HIST)
+    if constexpr (MODE == HIST) {
+        D.shift = digit_shift(A.sel.pass);
+        D.dmask = (1u << digit_bits(A.sel.pass)) - 1u;
+        D.hs = D.shift + digit_bits(A.sel.pass);
         for (int i = tid; i < BINS; i += MTHR) bins[i] = 0u;
+    }
     // COUNT: separator j = target j * stride; the smallest and the largest target bound the candidates that need a search
     unsigned tmin = 0xFFFFFFFFu, tmax = 0u;
-    u64 ncount = 0ull, nabove = 0ull;                           // this lane's candidates, and those above every target
+    u64 ncount = 0ull, nabove = 0ull;
     if constexpr (MODE == COUNT) {
-        for (int i = tid; i < A.nsep; i += MTHR) bins[i] = A.tord[(size_t)i * A.stride];
-        if (A.T > 0) {
-            tmin = A.tord[0];
-            tmax = A.tord[A.T - 1];
+        for (int i = tid; i < A.cnt.nsep; i += MTHR) bins[i] = A.cnt.tord[(size_t)i * A.cnt.stride];
+        if (A.cnt.T > 0) {
+            tmin = A.cnt.tord[0];
+            tmax = A.cnt.tord[A.cnt.T - 1];
         }
     }
     if constexpr (FILT)
@@ -221,8 +301,8 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
             const int node = (tid < TT ? ct * TT : (qt - 1) * TT) + tid;
             if (rem == per_tile - 2 && tid < 2 * TT && node < A.N) gb = A.filt.group[node];
         }
-        const __bf16* ub = us + (s & 1) * 3 * TT * SLD + (wu * 32 + li) * SLD + half * 8;
-        const __bf16* vb = vs + (s & 1) * 3 * TT * SLD + (wv * 64 + li) * SLD + half * 8;
+        const __bf16* ub = gram_operand(us, s, wu * 32 + li, half);
+        const __bf16* vb = gram_operand(vs, s, wv * 64 + li, half);
 #pragma unroll
         for (int kb = 0; kb < SDC / 16; ++kb) {
             gram_block_split6(acc, ub, vb, kb);                 // the ranking scan's products (dl_tiles.h)
@@ -231,21 +311,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                 fetch(min(s + 2, steps - 1));                   // unconditional: see TileStage (dl_tiles.h)
             }
         }
-        if (r == nd - 1) {                                      // S complete: e = exp(S / t)
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) e[bb][q] = expf(div_t(acc[bb][q], A.t));
-                zero_acc(acc[bb]);
-            }
-        } else if (r == 2 * nd - 1) {                           // Q complete: term += Q * e
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) term[bb][q] += acc[bb][q] * e[bb][q];
-                zero_acc(acc[bb]);
-            }
-        }
+        factor_update(acc, e, term, r, nd, A.t);                // S complete: e = exp(S / t); Q complete: term += Q * e
         if constexpr (FILT) {
             if (rem == per_tile - 2) {
                 if (tid < 2 * TT) cgrp[tid] = gb;
@@ -257,38 +323,28 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         if (rem != per_tile - 1) continue;
 
         // ---- tile pair complete: term[bb][q] = s(u = qt*128 + wu*32 + acc_row(q, half), v = ct*128 + wv*64 + bb*32 + li)
-        const int u0 = qt * TT, v0 = ct * TT;
+        const Tile T = {qt * TT, ct * TT, A.N};
         if (tid < TT) {                                         // this tile's excluded columns of row u0 + tid
             unsigned* m = exm + tid * 4;
             if constexpr (!FILT) m[0] = m[1] = m[2] = m[3] = 0u;
-            const int node = u0 + tid;
+            const int node = T.u0 + tid;
             if (node < A.N && A.ex_rowptr != nullptr) {
-                int lo = A.ex_rowptr[node];
                 const int end = A.ex_rowptr[node + 1];
-                int hi = end;
-                while (lo < hi) {                               // first excluded column >= v0
-                    const int mid = (lo + hi) >> 1;
-                    if (A.ex_col[mid] < v0) lo = mid + 1; else hi = mid;
-                }
-                for (int c = lo; c < end; ++c) {
-                    const int col = A.ex_col[c] - v0;
-                    if (col >= TT) break;
-                    m[col >> 5] |= 1u << (col & 31);
-                }
+                exclusion_mask(A.ex_col, first_col_at_least(A.ex_col, A.ex_rowptr[node], end, T.v0), end, T.v0, m);
             }
         }
         if constexpr (MODE == FILL) {                           // where the cells of this tile pair start in the CSR
             long long* ubase = reinterpret_cast<long long*>(bins + 2 * TT * 4), *vbase = ubase + TT;
             if (tid < TT) {
-                const int node = u0 + tid;
-                ubase[tid] = node < A.N ? (long long)A.rowptr[node] + (long long)A.cnt[(size_t)node * A.nt + ct] : 0ll;
+                const int node = T.u0 + tid;
+                ubase[tid] = node < A.N ? (long long)A.link.rowptr[node] + (long long)A.link.cnt[(size_t)node * A.nt + ct] : 0ll;
             } else if (tid < 2 * TT) {
-                const int node = v0 + tid - TT;
-                vbase[tid - TT] = node < A.N ? (long long)A.rowptr[node] + (long long)A.cnt[(size_t)node * A.nt + qt] : 0ll;
+                const int node = T.v0 + tid - TT;
+                vbase[tid - TT] = node < A.N ? (long long)A.link.rowptr[node] + (long long)A.link.cnt[(size_t)node * A.nt + qt] : 0ll;
             }
         }
         __syncthreads();
-        if constexpr (LINKS) {
+        if constexpr (LINKS) {                                  // in the body: as functions FILL measured 0.7-1.0 % slower
             unsigned* pm = bins;                                // [TT][4] pass mask, bit v of row u
             unsigned* pmt = bins + TT * 4;                      // [TT][4] its transpose, bit u of column v
             const long long* ubase = reinterpret_cast<const long long*>(bins + 2 * TT * 4);    // FILL: [TT] first slot of cell (u, ct)
@@ -303,11 +359,11 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
             unsigned okm = 0u;                                  // bit bb * 16 + q: this lane's value passed
 #pragma unroll
             for (int bb = 0; bb < 2; ++bb) {
-                const int vw = swv * 2 + bb, vl = vw * 32 + li, v = v0 + vl;
+                const int vw = swv * 2 + bb, vl = vw * 32 + li, v = T.v0 + vl;
                 unsigned rows = 0u;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    const int row = rbase + acc_row(q, 0), u = u0 + row;
+                    const int row = rbase + acc_row(q, 0), u = T.u0 + row;
                     const bool ok = u < v && v < A.N && !((exm[row * 4 + vw] >> li) & 1u) && term[bb][q] >= A.min_logit;
                     const u64 b = __ballot(ok);
                     if (li == 0) pm[row * 4 + vw] = half ? (unsigned)(b >> 32) : (unsigned)b;
@@ -324,25 +380,25 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                 // cell (u, ct) from the rows, cell (v, qt) from the columns; on the diagonal both sides of a node are one cell.
                 // Every cell of every node < N is written once, by the one workgroup that forms its tile pair, zeros included.
                 if (tid < TT) {
-                    const int node = u0 + tid;
+                    const int node = T.u0 + tid;
                     const unsigned* w = pm + tid * 4;
                     unsigned c = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
                     if (diag) {
                         const unsigned* wt = pmt + tid * 4;
                         c += __popc(wt[0]) + __popc(wt[1]) + __popc(wt[2]) + __popc(wt[3]);
                     }
-                    if (node < A.N) A.cnt[(size_t)node * A.nt + ct] = c;
+                    if (node < A.N) A.link.cnt[(size_t)node * A.nt + ct] = c;
                 } else if (tid < 2 * TT && !diag) {
-                    const int node = v0 + tid - TT;
+                    const int node = T.v0 + tid - TT;
                     const unsigned* wt = pmt + (tid - TT) * 4;
-                    if (node < A.N) A.cnt[(size_t)node * A.nt + qt] = __popc(wt[0]) + __popc(wt[1]) + __popc(wt[2]) + __popc(wt[3]);
+                    if (node < A.N) A.link.cnt[(size_t)node * A.nt + qt] = __popc(wt[0]) + __popc(wt[1]) + __popc(wt[2]) + __popc(wt[3]);
                 }
             } else {
                 // slot of (u, v) in row u: the cell's start, on the diagonal the smaller neighbours of u first, then the passed
                 // columns below v; in row v: the cell's start and the passed rows below u.  Columns ascend within a row.
 #pragma unroll
                 for (int bb = 0; bb < 2; ++bb) {
-                    const int vw = swv * 2 + bb, vl = vw * 32 + li, v = v0 + vl;
+                    const int vw = swv * 2 + bb, vl = vw * 32 + li, v = T.v0 + vl;
                     const unsigned* wt = pmt + vl * 4;
                     const unsigned vword = wt[swu], vsh = vword >> hs4;
                     const long long vb = vbase[vl] + (swu > 0 ? __popc(wt[0]) : 0) + (swu > 1 ? __popc(wt[1]) : 0) +
@@ -350,7 +406,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
                         if (!((okm >> (bb * 16 + q)) & 1u)) continue;
-                        const int row = rbase + acc_row(q, 0), u = u0 + row;
+                        const int row = rbase + acc_row(q, 0), u = T.u0 + row;
                         const unsigned* w = pm + row * 4;
                         long long su = ubase[row] + (vw > 0 ? __popc(w[0]) : 0) + (vw > 1 ? __popc(w[1]) : 0) + (vw > 2 ? __popc(w[2]) : 0) +
                                        __popc(w[vw] & ((1u << li) - 1u));
@@ -360,86 +416,70 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                         }
                         const long long sv = vb + __popc(vsh & ((1u << acc_row(q, 0)) - 1u));
                         const float x = term[bb][q] == 0.0f ? 0.0f : term[bb][q];      // -0 is reported as +0
-                        const float pr = A.prob != nullptr ? sigmoid_ref(x) : 0.0f;
-                        if ((u64)su < (u64)A.nnz) {
-                            A.col[su] = v;
-                            A.logit[su] = x;
-                            if (A.prob != nullptr) A.prob[su] = pr;
+                        const float pr = A.link.prob != nullptr ? sigmoid_ref(x) : 0.0f;
+                        if ((u64)su < (u64)A.link.nnz) {
+                            A.link.col[su] = v;
+                            A.link.logit[su] = x;
+                            if (A.link.prob != nullptr) A.link.prob[su] = pr;
                         }
-                        if ((u64)sv < (u64)A.nnz) {
-                            A.col[sv] = u;
-                            A.logit[sv] = x;
-                            if (A.prob != nullptr) A.prob[sv] = pr;
+                        if ((u64)sv < (u64)A.link.nnz) {
+                            A.link.col[sv] = u;
+                            A.link.logit[sv] = x;
+                            if (A.link.prob != nullptr) A.link.prob[sv] = pr;
                         }
                     }
                 }
             }
         } else {
+            const Lane L = {wu, wv, li, half, lane};
+            if constexpr (MODE == HIST) hist_epilogue(term, exm, bins, L, T, A.min_logit, D);
+            else if constexpr (MODE == EMIT) emit_epilogue(term, exm, L, T, A.min_logit, D.prefix, A.state, A.sel.keys, A.sel.m);
+            else {
+                // COUNT: the place of every candidate among the sorted targets: lo = targets strictly below it (they count it
+                // as "greater": +1 at gcnt[lo], summed from the top on the host), and the equal range, if any, starts at lo.
+                // Kept in the kernel body: as a function of its own it takes the instantiation from 250 to 256 VGPRs and spills.
 #pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-                const int vl = wv * 64 + bb * 32 + li, v = v0 + vl;
+                for (int bb = 0; bb < 2; ++bb) {
+                    const int vl = wv * 64 + bb * 32 + li;
 #pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int row = wu * 32 + acc_row(q, half), u = u0 + row;
-                    const float x = term[bb][q];
-                    bool ok = u < v && v < A.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u) && (MODE == COUNT || x >= A.min_logit);
-                    const u64 key = ((u64)ord_key(x) << 32) | (u64)(0xFFFFFFFFu - ((unsigned)u * (unsigned)A.N + (unsigned)v));
-                    if constexpr (MODE == HIST) {
-                        if (hs < 64) ok = ok && (key >> hs) == (S.prefix >> hs);
-                        const unsigned dg = (unsigned)(key >> shift) & dmask;
-                        const u64 act = __ballot(ok);
-                        if (act != 0ull) {                          // wave-uniform: logits cluster, so one bin per wave is common
-                            const int first = __ffsll((long long)act) - 1;
-                            const unsigned d0 = (unsigned)__shfl((int)dg, first, DL_WAVE);
-                            if (__ballot(ok && dg == d0) == act) {
-                                if (lane == first) atomicAdd(&bins[d0], (unsigned)__popcll(act));
-                            } else if (ok) {
-                                atomicAdd(&bins[dg], 1u);
-                            }
-                        }
-                    } else if constexpr (MODE == EMIT) {
-                        if (ok && key >= S.prefix) {
-                            const unsigned slot = atomicAdd(&A.state->emitted, 1u);
-                            if (slot < (unsigned)A.m) A.keys[slot] = key;
-                        }
-                    } else {
-                        // place of the candidate among the sorted targets: lo = targets strictly below it (they count it as
-                        // "greater": +1 at gcnt[lo], summed from the top on the host), and the equal range, if any, starts at lo
-                        const unsigned o = ord_key(x);
+                    for (int q = 0; q < 16; ++q) {
+                        const int row = wu * 32 + acc_row(q, half), u = T.u0 + row, v = T.v0 + vl;
+                        const bool ok = u < v && v < T.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u);
+                        const unsigned o = ord_key(term[bb][q]);
                         ncount += ok ? 1ull : 0ull;
                         nabove += (ok && o > tmax) ? 1ull : 0ull;
                         const bool in = ok && o >= tmin && o <= tmax;
                         int lo = 0;
                         bool tie = false;
                         if (in) {
-                            int a = 0, b = A.nsep;                  // separators below o: [0, a)
+                            int a = 0, b = A.cnt.nsep;              // separators below o: [0, a)
                             while (a < b) {
                                 const int mid = (a + b) >> 1;
                                 if (bins[mid] < o) a = mid + 1; else b = mid;
                             }
-                            if (a > 0) {                            // target (a-1) stride < o <= target a stride (or the end)
-                                int l = (a - 1) * A.stride + 1, h = min(a * A.stride, A.T);
+                            if (a > 0) {                        // target (a-1) stride < o <= target a stride (or the end)
+                                int l = (a - 1) * A.cnt.stride + 1, h = min(a * A.cnt.stride, A.cnt.T);
                                 while (l < h) {
                                     const int mid = (l + h) >> 1;
-                                    if (A.tord[mid] < o) l = mid + 1; else h = mid;
+                                    if (A.cnt.tord[mid] < o) l = mid + 1; else h = mid;
                                 }
                                 lo = l;
                             }
-                            tie = A.tord[lo] == o;                  // lo < T: o <= tmax
+                            tie = A.cnt.tord[lo] == o;              // lo < T: o <= tmax
                         }
                         const u64 act = __ballot(in);
-                        if (act != 0ull) {                          // wave-uniform; one place per wave where the logits cluster
+                        if (act != 0ull) {                      // wave-uniform; one place per wave where the logits cluster
                             const int first = __ffsll((long long)act) - 1;
                             const int l0 = __shfl(lo, first, DL_WAVE);
                             if (__ballot(in && lo == l0) == act) {
                                 const u64 eq = __ballot(in && tie);
                                 if (lane == first) {
-                                    if (l0 > 0) atomicAdd(&A.gcnt[l0], (u64)__popcll(act));
-                                    if (eq != 0ull) atomicAdd(&A.tcnt[l0], (u64)__popcll(eq));
+                                    if (l0 > 0) atomicAdd(&A.cnt.gcnt[l0], (u64)__popcll(act));
+                                    if (eq != 0ull) atomicAdd(&A.cnt.tcnt[l0], (u64)__popcll(eq));
                                 }
                             } else if (in) {
-                                if (lo > 0) atomicAdd(&A.gcnt[lo], 1ull);
-                                if (tie) atomicAdd(&A.tcnt[lo], 1ull);
+                                if (lo > 0) atomicAdd(&A.cnt.gcnt[lo], 1ull);
+                                if (tie) atomicAdd(&A.cnt.tcnt[lo], 1ull);
                             }
                         }
                     }
@@ -454,21 +494,8 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         qt2 = ct + 1 < A.nt ? qt : qt + 1;
         ct2 = ct + 1 < A.nt ? ct + 1 : qt + 1;
     }
-    if constexpr (MODE == HIST) {
-        __syncthreads();
-        for (int i = tid; i < BINS; i += MTHR) {
-            const unsigned c = bins[i];
-            if (c) atomicAdd(&A.hist[i], c);
-        }
-    }
-    if constexpr (MODE == COUNT) {                              // one add per wave
-        ncount = wave_sum(ncount);
-        nabove = wave_sum(nabove);
-        if (lane == 0) {
-            if (ncount) atomicAdd(A.ncand, ncount);
-            if (nabove) atomicAdd(&A.gcnt[A.T], nabove);
-        }
-    }
+    if constexpr (MODE == HIST) hist_flush(bins, A.sel.hist, tid);
+    if constexpr (MODE == COUNT) count_flush(A.cnt, ncount, nabove, lane);
 }
 
 __global__ __launch_bounds__(256) void init_kernel(State* st, unsigned* hist, int m) {
@@ -645,17 +672,6 @@ __global__ __launch_bounds__(1024) void link_rowptr_kernel(const unsigned* __res
 
 using namespace mine;
 
-static int mine_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, c = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-            n = c;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
-
 // Tile pairs per workgroup: eight workgroups' worth of pairs per CU (one workgroup per CU fits the LDS; short runs keep the
 // tail of the grid short, consecutive pairs of a run share their u tile).  DL_MINE_TILES (test knob) forces the run length;
 // results do not depend on it.
@@ -667,12 +683,33 @@ static MinePlan mine_plan(int N, int d) {
     // 64-bit: nt (nt + 1) / 2 fits an int32 up to nt = 65,535 (the callers' limit on N), its intermediates do not
     const long long pairs = N >= 2 ? (long long)p.nt * (p.nt + 1) / 2 : 0;
     p.pairs = (int)pairs;
-    const long long per_cu = 8LL * mine_cus();
+    const long long per_cu = 8LL * device_cus();
     const int want = config().mine_tiles > 0 ? config().mine_tiles : (int)((pairs + per_cu - 1) / per_cu);
     p.per_wg = max(1, min(want, max(1, p.pairs)));
     p.grid = (int)((pairs + p.per_wg - 1) / p.per_wg);
     p.cbatch = plane_array_elems(N, d, SDC);
     return p;
+}
+
+// The planes of Z and H, and what every scan of the family reads
+static void split_tables(const float* Z, const float* H, int N, int K, int d, __bf16* cz, __bf16* ch, hipStream_t st) {
+    split_rows(Z, K, N, d, K * d, (size_t)d, cz, st);
+    split_rows(H, K, N, d, K * d, (size_t)d, ch, st);
+}
+static ScanArgs scan_args(const MinePlan& p, const __bf16* cz, const __bf16* ch, int N, int K, float t, const int32_t* exr,
+                          const int32_t* exc, float min_logit, const dl_node_filter* nf) {
+    ScanArgs a = {};
+    a.cz = cz; a.ch = ch; a.cbatch = p.cbatch;
+    a.N = N; a.K = K; a.nd = p.nd; a.nt = p.nt; a.t = t;
+    a.ex_rowptr = exr; a.ex_col = exc;
+    a.min_logit = min_logit;
+    a.pairs = p.pairs; a.per_wg = p.per_wg;
+    a.filt = filter_args(nf);
+    return a;
+}
+template <int MODE>
+static void launch_tiles(const MinePlan& p, const ScanArgs& a, const dl_node_filter* nf, hipStream_t st) {
+    launch_scan<scan_tiles<MODE>, scan_tiles<MODE, true>>(nf, (unsigned)p.grid, MTHR, MODE == COUNT ? LDS_BYTES_COUNT : LDS_BYTES, st, a);
 }
 
 bool score_mine_supported(int K, int d) { return score_rank_supported(K, d); }
@@ -695,19 +732,13 @@ void score_mine_form(int N, int d, int m, int* out) {
 struct MineWs { State* state; unsigned* hist; u64* keys; __bf16 *cz, *ch; size_t bytes; };
 static MineWs mine_carve(const MinePlan& p, int K, int m, void* ws) {
     MineWs w = {};
-    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char* r = base + o;
-        o += (bytes + 255) & ~(size_t)255;
-        return (void*)r;
-    };
-    w.state = (State*)take(sizeof(State));
-    w.hist = (unsigned*)take(sizeof(unsigned) * BINS);
-    w.keys = (u64*)take(sizeof(u64) * (size_t)m);
-    w.cz = (__bf16*)take(2 * (size_t)K * p.cbatch);
-    w.ch = (__bf16*)take(2 * (size_t)K * p.cbatch);
-    w.bytes = o + 256;
+    Carver c(ws);
+    w.state = c.take<State>(1);
+    w.hist = c.take<unsigned>(BINS);
+    w.keys = c.take<u64>((size_t)m);
+    w.cz = c.take<__bf16>((size_t)K * p.cbatch);
+    w.ch = c.take<__bf16>((size_t)K * p.cbatch);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -716,42 +747,20 @@ size_t score_mine_workspace_bytes(int N, int K, int d, int m) { return mine_carv
 int score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
                int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws, hipStream_t st,
                const dl_node_filter* nf) {
-    static unsigned long long lds_hist = 0, lds_emit = 0, lds_hist_f = 0, lds_emit_f = 0;
     const MinePlan p = mine_plan(N, d);
     const MineWs w = mine_carve(p, K, m, ws);
     hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, m);
     if (p.pairs > 0) {
-        split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
-        split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
-        ScanArgs a = {};
-        a.cz = w.cz; a.ch = w.ch; a.cbatch = p.cbatch;
-        a.N = N; a.K = K; a.nd = p.nd; a.nt = p.nt; a.t = t;
-        a.ex_rowptr = exr; a.ex_col = exc;
-        a.min_logit = min_logit;
-        a.m = m;
-        a.pairs = p.pairs; a.per_wg = p.per_wg;
-        a.state = w.state; a.hist = w.hist; a.keys = w.keys;
-        if (nf != nullptr) {
-            constexpr size_t LB = LDS_BYTES + FILTER_LDS_BYTES;
-            a.filt = FilterArgs{nf->group, (const u64*)nf->allow, nf->n_groups};
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<HIST, true>), LB, lds_hist_f);
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<EMIT, true>), LB, lds_emit_f);
-            for (int pass = 0; pass < PASSES; ++pass) {
-                a.pass = pass;
-                hipLaunchKernelGGL((scan_tiles<HIST, true>), dim3((unsigned)p.grid), dim3(MTHR), LB, st, a);
-                hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
-            }
-            hipLaunchKernelGGL((scan_tiles<EMIT, true>), dim3((unsigned)p.grid), dim3(MTHR), LB, st, a);
-        } else {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<HIST>), LDS_BYTES, lds_hist);
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<EMIT>), LDS_BYTES, lds_emit);
-            for (int pass = 0; pass < PASSES; ++pass) {
-                a.pass = pass;
-                hipLaunchKernelGGL(scan_tiles<HIST>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
-                hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
-            }
-            hipLaunchKernelGGL(scan_tiles<EMIT>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
+        split_tables(Z, H, N, K, d, w.cz, w.ch, st);
+        ScanArgs a = scan_args(p, w.cz, w.ch, N, K, t, exr, exc, min_logit, nf);
+        a.state = w.state;
+        a.sel.m = m; a.sel.hist = w.hist; a.sel.keys = w.keys;
+        for (int pass = 0; pass < PASSES; ++pass) {
+            a.sel.pass = pass;
+            launch_tiles<HIST>(p, a, nf, st);
+            hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
         }
+        launch_tiles<EMIT>(p, a, nf, st);
     }
     hipLaunchKernelGGL(order_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.state, w.keys, max(N, 1), m, src, dst,
                        logit, prob, count);
@@ -797,17 +806,11 @@ void score_pair_ranks_form(int N, int d, int T, int* out) {
 struct PairRankWs { State* state; __bf16 *cz, *ch; size_t bytes; };
 static PairRankWs pair_rank_carve(const MinePlan& p, int K, void* ws) {
     PairRankWs w = {};
-    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char* r = base + o;
-        o += (bytes + 255) & ~(size_t)255;
-        return (void*)r;
-    };
-    w.state = (State*)take(sizeof(State));
-    w.cz = (__bf16*)take(2 * (size_t)K * p.cbatch);
-    w.ch = (__bf16*)take(2 * (size_t)K * p.cbatch);
-    w.bytes = o + 256;
+    Carver c(ws);
+    w.state = c.take<State>(1);
+    w.cz = c.take<__bf16>((size_t)K * p.cbatch);
+    w.ch = c.take<__bf16>((size_t)K * p.cbatch);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -816,7 +819,6 @@ size_t score_pair_ranks_workspace_bytes(int N, int K, int d) { return pair_rank_
 int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
                      const unsigned* tord, int T, u64* gcnt, u64* tcnt, u64* ncand, void* ws, hipStream_t st,
                      const dl_node_filter* nf) {
-    static unsigned long long lds_count = 0, lds_count_f = 0;
     const PairRankPlan p = pair_rank_plan(N, d, T);
     const PairRankWs w = pair_rank_carve(p.m, K, ws);
     hipError_t e = hipMemsetAsync(w.state, 0, sizeof(State), st);
@@ -825,25 +827,11 @@ int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float 
     if (e == hipSuccess) e = hipMemsetAsync(ncand, 0, sizeof(u64), st);
     DL_REQUIRE(e == hipSuccess, "hipMemsetAsync: %s", hipGetErrorString(e));
     if (p.m.pairs > 0) {
-        split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
-        split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
-        ScanArgs a = {};
-        a.cz = w.cz; a.ch = w.ch; a.cbatch = p.m.cbatch;
-        a.N = N; a.K = K; a.nd = p.m.nd; a.nt = p.m.nt; a.t = t;
-        a.ex_rowptr = exr; a.ex_col = exc;
-        a.pairs = p.m.pairs; a.per_wg = p.m.per_wg;
+        split_tables(Z, H, N, K, d, w.cz, w.ch, st);
+        ScanArgs a = scan_args(p.m, w.cz, w.ch, N, K, t, exr, exc, 0.0f, nf);
         a.state = w.state;
-        a.tord = tord; a.T = T; a.stride = p.stride; a.nsep = p.nsep;
-        a.gcnt = gcnt; a.tcnt = tcnt; a.ncand = ncand;
-        if (nf != nullptr) {
-            constexpr size_t LB = LDS_BYTES_COUNT + FILTER_LDS_BYTES;
-            a.filt = FilterArgs{nf->group, (const u64*)nf->allow, nf->n_groups};
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<COUNT, true>), LB, lds_count_f);
-            hipLaunchKernelGGL((scan_tiles<COUNT, true>), dim3((unsigned)p.m.grid), dim3(MTHR), LB, st, a);
-        } else {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<COUNT>), LDS_BYTES_COUNT, lds_count);
-            hipLaunchKernelGGL(scan_tiles<COUNT>, dim3((unsigned)p.m.grid), dim3(MTHR), LDS_BYTES_COUNT, st, a);
-        }
+        a.cnt = CountArgs{tord, T, p.stride, p.nsep, gcnt, tcnt, ncand};
+        launch_tiles<COUNT>(p.m, a, nf, st);
     }
     return check_launch("score_pair_ranks");
 }
@@ -867,53 +855,26 @@ void score_links_form(int N, int d, int* out) {
 struct LinksWs { __bf16 *cz, *ch; unsigned *cnt, *deg; size_t bytes; };
 static LinksWs links_carve(const MinePlan& p, int N, int K, void* ws) {
     LinksWs w = {};
-    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char* r = base + o;
-        o += (bytes + 255) & ~(size_t)255;
-        return (void*)r;
-    };
-    w.cz = (__bf16*)take(2 * (size_t)K * p.cbatch);
-    w.ch = (__bf16*)take(2 * (size_t)K * p.cbatch);
-    w.cnt = (unsigned*)take(sizeof(unsigned) * (size_t)N * p.nt);
-    w.deg = (unsigned*)take(sizeof(unsigned) * (size_t)N);
-    w.bytes = o + 256;
+    Carver c(ws);
+    w.cz = c.take<__bf16>((size_t)K * p.cbatch);
+    w.ch = c.take<__bf16>((size_t)K * p.cbatch);
+    w.cnt = c.take<unsigned>((size_t)N * p.nt);
+    w.deg = c.take<unsigned>((size_t)N);
+    w.bytes = c.bytes();
     return w;
 }
 
 size_t score_links_workspace_bytes(int N, int K, int d) { return links_carve(mine_plan(N, d), N, K, nullptr).bytes; }
 
-static ScanArgs links_args(const MinePlan& p, const LinksWs& w, int N, int K, float t, const int32_t* exr, const int32_t* exc,
-                           float min_logit, const dl_node_filter* nf) {
-    ScanArgs a = {};
-    a.cz = w.cz; a.ch = w.ch; a.cbatch = p.cbatch;
-    a.N = N; a.K = K; a.nd = p.nd; a.nt = p.nt; a.t = t;
-    a.ex_rowptr = exr; a.ex_col = exc;
-    a.min_logit = min_logit;
-    a.pairs = p.pairs; a.per_wg = p.per_wg;
-    a.cnt = w.cnt;
-    if (nf != nullptr) a.filt = FilterArgs{nf->group, (const u64*)nf->allow, nf->n_groups};
-    return a;
-}
-
 int score_links_count(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
                       float min_logit, const dl_node_filter* nf, void* ws, int64_t* rowptr, hipStream_t st) {
-    static unsigned long long lds_deg = 0, lds_deg_f = 0;
     const MinePlan p = mine_plan(N, d);
     const LinksWs w = links_carve(p, N, K, ws);
     if (p.pairs > 0) {
-        split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
-        split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
-        const ScanArgs a = links_args(p, w, N, K, t, exr, exc, min_logit, nf);
-        if (nf != nullptr) {
-            constexpr size_t LB = LDS_BYTES + FILTER_LDS_BYTES;
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<DEG, true>), LB, lds_deg_f);
-            hipLaunchKernelGGL((scan_tiles<DEG, true>), dim3((unsigned)p.grid), dim3(MTHR), LB, st, a);
-        } else {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<DEG>), LDS_BYTES, lds_deg);
-            hipLaunchKernelGGL(scan_tiles<DEG>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
-        }
+        split_tables(Z, H, N, K, d, w.cz, w.ch, st);
+        ScanArgs a = scan_args(p, w.cz, w.ch, N, K, t, exr, exc, min_logit, nf);
+        a.link.cnt = w.cnt;
+        launch_tiles<DEG>(p, a, nf, st);
         hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, w.cnt, w.deg, N, p.nt);
     }
     hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, w.deg, rowptr, N, p.pairs > 0 ? 1 : 0);
@@ -922,21 +883,12 @@ int score_links_count(const float* Z, const float* H, int N, int K, int d, float
 
 int score_links_fill(int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit, const dl_node_filter* nf,
                      void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit, float* prob, hipStream_t st) {
-    static unsigned long long lds_fill = 0, lds_fill_f = 0;
     const MinePlan p = mine_plan(N, d);
     const LinksWs w = links_carve(p, N, K, ws);
     if (p.pairs > 0 && nnz > 0) {
-        ScanArgs a = links_args(p, w, N, K, t, exr, exc, min_logit, nf);
-        a.rowptr = rowptr; a.nnz = nnz;
-        a.col = col; a.logit = logit; a.prob = prob;
-        if (nf != nullptr) {
-            constexpr size_t LB = LDS_BYTES + FILTER_LDS_BYTES;
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<FILL, true>), LB, lds_fill_f);
-            hipLaunchKernelGGL((scan_tiles<FILL, true>), dim3((unsigned)p.grid), dim3(MTHR), LB, st, a);
-        } else {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_tiles<FILL>), LDS_BYTES, lds_fill);
-            hipLaunchKernelGGL(scan_tiles<FILL>, dim3((unsigned)p.grid), dim3(MTHR), LDS_BYTES, st, a);
-        }
+        ScanArgs a = scan_args(p, w.cz, w.ch, N, K, t, exr, exc, min_logit, nf);
+        a.link = LinkArgs{w.cnt, rowptr, nnz, col, logit, prob};
+        launch_tiles<FILL>(p, a, nf, st);
     }
     return check_launch("score_links_fill");
 }

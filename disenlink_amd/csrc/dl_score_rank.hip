@@ -24,12 +24,13 @@
 // logit of a pair does not depend on where in a tile its rows sit: results are independent of the slicing and of the run.
 #include "dl_common.h"
 #include "dl_kernels.h"
-#include "dl_tiles.h"
+#include "dl_scan.h"
 
 namespace dl {
 namespace rank {
 
 using namespace project;       // PlaneStage, gram_block_split6, f32x16, acc_row, xcd_item, plane arrays
+using namespace scan;          // ord_key / ord_value / make_key, the exclusion search of the target kernels, host scaffolding
 
 constexpr int TT = 128;        // tile edge (query rows and candidate rows)
 constexpr int RTHR = 512;
@@ -39,24 +40,6 @@ constexpr int ROUND = 64;      // keys one round of appends can add to a row's l
 constexpr int MAX_CAP = MAX_K + ROUND;
 constexpr int MAX_SLICES = 32;
 enum { TOPK = 0, RANKS = 1, DIAG = 2 };
-
-typedef unsigned long long u64;
-
-// Total order of the logits as an unsigned key: NaN -> 0, every other value (-0 taken as +0) to its order-preserving
-// image, which is >= 0x007FFFFF (-inf) and <= 0xFF800000 (+inf).
-__device__ __forceinline__ unsigned ord_key(float x) {
-    if (x != x) return 0u;
-    const unsigned b = __float_as_uint(x == 0.0f ? 0.0f : x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord_value(unsigned o) {
-    if (o == 0u) return __uint_as_float(0x7FC00000u);
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-// 64-bit selection key: the value's order, then the candidate index (smaller index = larger key).  Never 0.
-__device__ __forceinline__ u64 make_key(float x, int v) {
-    return ((u64)ord_key(x) << 32) | (u64)(0xFFFFFFFFu - (unsigned)v);
-}
 
 struct ScanArgs {
     const __bf16 *qz, *qh;  size_t qbatch;     // planes of the gathered query rows (per factor: qbatch elements)
@@ -75,8 +58,7 @@ struct ScanArgs {
 // LDS beyond the two staging images (bytes): exclusion mask, per-row bookkeeping, per-wave compaction scratch
 constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
 constexpr size_t LDS_BYTES = STAGE_BYTES + TT * 4 * 4 + 6 * TT * 4 + TT * 8 + 8 * MAX_CAP * 8;
-constexpr size_t LDS_BYTES_FILT = LDS_BYTES + FILTER_LDS_BYTES;
-static_assert(LDS_BYTES % 16 == 0 && LDS_BYTES_FILT <= 160 * 1024, "LDS of a CU");
+static_assert(LDS_BYTES % 16 == 0 && LDS_BYTES + FILTER_LDS_BYTES <= 160 * 1024, "LDS of a CU");
 
 // A PlaneStage tile whose 128 rows are gathered: row r of the tile is row rows[min(base + r, n - 1)] of the plane array.
 __device__ __forceinline__ void gather_fetch(PlaneStage<RTHR, SDC>& st, const __bf16* __restrict__ planes, const int32_t* rows,
@@ -494,11 +476,7 @@ __global__ void target_finish_kernel(const int32_t* __restrict__ tptr, const int
     const int node = qnode[q], v = tdst[i];
     bool counted = v != node;                                   // the scan counted the target itself among the ties
     if (counted && ex_rowptr != nullptr) {
-        int lo = ex_rowptr[node], hi = ex_rowptr[node + 1];
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ex_col[mid] < v) lo = mid + 1; else hi = mid;
-        }
+        const int lo = first_col_at_least(ex_col, ex_rowptr[node], ex_rowptr[node + 1], v);
         counted = !(lo < ex_rowptr[node + 1] && ex_col[lo] == v);
     }
     greater[i] = (int64_t)g;
@@ -515,11 +493,7 @@ __global__ void target_unallowed_kernel(const int32_t* __restrict__ trow, const 
     const int node = qnode[trow[i]], v = tdst[i];
     if (v == node || ((filt.allow[filt.group[node]] >> (filt.group[v] & 63)) & 1ull)) return;
     if (ex_rowptr != nullptr) {
-        int lo = ex_rowptr[node], hi = ex_rowptr[node + 1];
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ex_col[mid] < v) lo = mid + 1; else hi = mid;
-        }
+        const int lo = first_col_at_least(ex_col, ex_rowptr[node], ex_rowptr[node + 1], v);
         if (lo < ex_rowptr[node + 1] && ex_col[lo] == v) return;       // excluded: nothing was taken
     }
     ties[i] += 1;
@@ -530,17 +504,6 @@ __global__ void target_unallowed_kernel(const int32_t* __restrict__ trow, const 
 using namespace rank;
 
 bool score_rank_supported(int K, int d) { return K >= 1 && K <= DL_MAX_FACTORS && d >= 1 && d <= 128; }
-
-static int device_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, c = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-            n = c;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
 
 // Slicing of the candidate tiles: as many slices as keep one work item per CU busy (one workgroup per CU fits the LDS),
 // at most MAX_SLICES, never an empty slice.  DL_RANK_SLICES (test knob) forces the count; results do not depend on it.
@@ -584,41 +547,33 @@ struct RankWs {
 };
 static RankWs rank_carve(const RankPlan& p, int Q, int K, int d, int k, int T, void* ws) {
     RankWs w = {};
-    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        char* r = base + o;
-        o += (bytes + 255) & ~(size_t)255;
-        return (void*)r;
-    };
-    w.zq = (float*)take(sizeof(float) * (size_t)Q * K * d);
-    w.hq = (float*)take(sizeof(float) * (size_t)Q * K * d);
-    w.qz = (__bf16*)take(2 * (size_t)K * p.qbatch);
-    w.qh = (__bf16*)take(2 * (size_t)K * p.qbatch);
-    w.cz = (__bf16*)take(2 * (size_t)K * p.cbatch);
-    w.ch = (__bf16*)take(2 * (size_t)K * p.cbatch);
+    Carver c(ws);
+    w.zq = c.take<float>((size_t)Q * K * d);
+    w.hq = c.take<float>((size_t)Q * K * d);
+    w.qz = c.take<__bf16>((size_t)K * p.qbatch);
+    w.qh = c.take<__bf16>((size_t)K * p.qbatch);
+    w.cz = c.take<__bf16>((size_t)K * p.cbatch);
+    w.ch = c.take<__bf16>((size_t)K * p.cbatch);
     if (k > 0) {
-        w.lists = (u64*)take(sizeof(u64) * (size_t)Q * p.slices * p.cap);
-        w.counts = (int*)take(sizeof(int) * (size_t)Q * p.slices);
+        w.lists = c.take<u64>((size_t)Q * p.slices * p.cap);
+        w.counts = c.take<int>((size_t)Q * p.slices);
     }
     if (T > 0) {
-        w.trow = (int32_t*)take(sizeof(int32_t) * (size_t)T);
-        w.spos = (int32_t*)take(sizeof(int32_t) * (size_t)T);
-        w.sfirst = (int32_t*)take(sizeof(int32_t) * (size_t)T);
-        w.tlogit = (float*)take(sizeof(float) * (size_t)T);
-        w.tord = (unsigned*)take(sizeof(unsigned) * (size_t)T);
-        w.gcnt = (u64*)take(sizeof(u64) * ((size_t)T + Q));
-        w.tcnt = (u64*)take(sizeof(u64) * (size_t)T);
+        w.trow = c.take<int32_t>((size_t)T);
+        w.spos = c.take<int32_t>((size_t)T);
+        w.sfirst = c.take<int32_t>((size_t)T);
+        w.tlogit = c.take<float>((size_t)T);
+        w.tord = c.take<unsigned>((size_t)T);
+        w.gcnt = c.take<u64>((size_t)T + Q);
+        w.tcnt = c.take<u64>((size_t)T);
     }
-    w.bytes = o + 256;
+    w.bytes = c.bytes();
     return w;
 }
 
 size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T) {
     return rank_carve(rank_plan(N, d, Q, k), Q, K, d, k, T, nullptr).bytes;
 }
-
-static FilterArgs filter_args(const dl_node_filter* nf) { return FilterArgs{nf->group, (const u64*)nf->allow, nf->n_groups}; }
 
 // the query rows gathered and split, the candidate tables split: the scan's operands
 static ScanArgs scan_operands(const RankPlan& p, const RankWs& w, const float* Z, const float* H, int N, int K, int d, float t,
@@ -642,21 +597,14 @@ static ScanArgs scan_operands(const RankPlan& p, const RankWs& w, const float* Z
 int score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, int k,
                const int32_t* exr, const int32_t* exc, int exclude_self, int64_t* index, float* logit, float* prob, void* ws,
                hipStream_t st, const dl_node_filter* nf) {
-    static unsigned long long lds_done = 0, lds_filt = 0;
     const RankPlan p = rank_plan(N, d, Q, k);
     const RankWs w = rank_carve(p, Q, K, d, k, 0, ws);
     ScanArgs a = scan_operands(p, w, Z, H, N, K, d, t, queries, Q, exr, exc, st);
     a.exclude_self = exclude_self ? 1 : 0;
     a.k = k; a.cap = p.cap; a.lists = w.lists; a.counts = w.counts;
-    if (nf != nullptr) {
-        a.filt = filter_args(nf);
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<TOPK, true>), LDS_BYTES_FILT, lds_filt);
-        hipLaunchKernelGGL((rank_scan_kernel<TOPK, true>), dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES_FILT,
-                           st, a);
-    } else {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<TOPK>), LDS_BYTES, lds_done);
-        hipLaunchKernelGGL(rank_scan_kernel<TOPK>, dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES, st, a);
-    }
+    a.filt = filter_args(nf);
+    launch_scan<rank_scan_kernel<TOPK>, rank_scan_kernel<TOPK, true>>(nf, (unsigned)xcd_grid(p.qtiles, p.slices), RTHR, LDS_BYTES,
+                                                                      st, a);
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)Q), dim3(256), 0, st, w.lists, w.counts, p.slices, p.cap, k, index,
                        logit, prob);
     return check_launch("score_topk");
@@ -665,7 +613,6 @@ int score_topk(const float* Z, const float* H, int N, int K, int d, float t, con
 int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, const int32_t* tptr,
                 const int32_t* tdst, int T, const int32_t* exr, const int32_t* exc, int64_t* greater, int64_t* ties, void* ws,
                 hipStream_t st, const dl_node_filter* nf) {
-    static unsigned long long lds_diag = 0, lds_rank = 0, lds_filt = 0;
     const RankPlan p = rank_plan(N, d, Q, 0);
     const RankWs w = rank_carve(p, Q, K, d, 0, T, ws);
     ScanArgs a = scan_operands(p, w, Z, H, N, K, d, t, queries, Q, exr, exc, st);
@@ -674,8 +621,7 @@ int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, co
     // itself, the diagonal kept
     ScanArgs g = a;
     g.trow = w.trow; g.tdst = tdst; g.T = T; g.tlogit = w.tlogit;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<DIAG>), LDS_BYTES, lds_diag);
-    hipLaunchKernelGGL(rank_scan_kernel<DIAG>, dim3((unsigned)xcd_grid((T + TT - 1) / TT, 1)), dim3(RTHR), LDS_BYTES, st, g);
+    launch_lds<rank_scan_kernel<DIAG>>((unsigned)xcd_grid((T + TT - 1) / TT, 1), RTHR, LDS_BYTES, st, g);
     const unsigned tb = (unsigned)((T + 255) / 256);
     hipLaunchKernelGGL(target_sort_kernel, dim3(tb), dim3(256), 0, st, tptr, w.trow, w.tlogit, T, w.tord, w.spos, w.sfirst);
     hipError_t e = hipMemsetAsync(w.gcnt, 0, sizeof(u64) * ((size_t)T + Q), st);
@@ -683,15 +629,9 @@ int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, co
     DL_REQUIRE(e == hipSuccess, "hipMemsetAsync: %s", hipGetErrorString(e));
     a.exclude_self = 1;
     a.tptr = tptr; a.tord = w.tord; a.gcnt = w.gcnt; a.tcnt = w.tcnt;
-    if (nf != nullptr) {
-        a.filt = filter_args(nf);
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<RANKS, true>), LDS_BYTES_FILT, lds_filt);
-        hipLaunchKernelGGL((rank_scan_kernel<RANKS, true>), dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES_FILT,
-                           st, a);
-    } else {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<RANKS>), LDS_BYTES, lds_rank);
-        hipLaunchKernelGGL(rank_scan_kernel<RANKS>, dim3((unsigned)xcd_grid(p.qtiles, p.slices)), dim3(RTHR), LDS_BYTES, st, a);
-    }
+    a.filt = filter_args(nf);
+    launch_scan<rank_scan_kernel<RANKS>, rank_scan_kernel<RANKS, true>>(nf, (unsigned)xcd_grid(p.qtiles, p.slices), RTHR, LDS_BYTES,
+                                                                        st, a);
     hipLaunchKernelGGL(target_finish_kernel, dim3(tb), dim3(256), 0, st, tptr, w.trow, tdst, queries, w.spos, w.sfirst, w.gcnt,
                        w.tcnt, exr, exc, T, greater, ties);
     if (nf != nullptr)
@@ -705,11 +645,10 @@ struct PairWs { __bf16 *cz, *ch; size_t cbatch, bytes; };
 static PairWs pair_carve(int N, int K, int d, void* ws) {
     PairWs w = {};
     w.cbatch = plane_array_elems(N, d, SDC);
-    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    const size_t one = (2 * (size_t)K * w.cbatch + 255) & ~(size_t)255;
-    w.cz = (__bf16*)base;
-    w.ch = (__bf16*)(base + one);
-    w.bytes = 2 * one + 256;
+    Carver c(ws);
+    w.cz = c.take<__bf16>((size_t)K * w.cbatch);
+    w.ch = c.take<__bf16>((size_t)K * w.cbatch);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -717,7 +656,6 @@ size_t score_pair_logits_workspace_bytes(int N, int K, int d) { return pair_carv
 
 int score_pair_logits(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* a, const int32_t* b, int T,
                       float* logit, void* ws, hipStream_t st) {
-    static unsigned long long lds_diag = 0;
     const PairWs w = pair_carve(N, K, d, ws);
     split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
     split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
@@ -726,8 +664,7 @@ int score_pair_logits(const float* Z, const float* H, int N, int K, int d, float
     g.cz = w.cz; g.ch = w.ch; g.cbatch = w.cbatch;
     g.N = N; g.K = K; g.nd = (d + SDC - 1) / SDC; g.t = t;
     g.trow = a; g.tdst = b; g.T = T; g.tlogit = logit;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&rank_scan_kernel<DIAG>), LDS_BYTES, lds_diag);
-    hipLaunchKernelGGL(rank_scan_kernel<DIAG>, dim3((unsigned)xcd_grid((T + TT - 1) / TT, 1)), dim3(RTHR), LDS_BYTES, st, g);
+    launch_lds<rank_scan_kernel<DIAG>>((unsigned)xcd_grid((T + TT - 1) / TT, 1), RTHR, LDS_BYTES, st, g);
     return check_launch("score_pair_logits");
 }
 

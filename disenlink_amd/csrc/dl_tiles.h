@@ -159,8 +159,10 @@ __device__ __forceinline__ void mfma_split6(f32x16& acc, const bf16x8 (&a)[3], c
 // One K = 16 block (kb) of a 128 x 128 tile Gram product A . B^T from two LDS plane images [3][128][SPLIT_PITCH]: the wave
 // that owns rows 32 wu .. 32 wu + 31 of A and rows 64 wv .. 64 wv + 63 of B passes ub = A image + (32 wu + lane % 32) rows
 // + 8 (lane / 32) and vb likewise (64 wv), and accumulates the two 32 x 32 blocks acc[0] (B rows + 0) and acc[1] (+ 32).
-// Shared by the dense scorer (dl_score_dense.hip) and the ranking scan (dl_score_rank.hip): the same products in the
-// same order, so both form the same bits for the same ORDERED pair of rows (A row, B row), wherever in a tile the rows sit.
+// Shared by the dense scorer (dl_score_dense.hip) and the candidate scans (dl_score_rank.hip, dl_score_mine.hip): the same
+// products in the same order, so all form the same bits for the same ORDERED pair of rows (A row, B row), wherever in a tile
+// the rows sit.  The rest of a step (gram_operand, factor_update) is in dl_scan.h for the dense scorer and scan_tiles;
+// rank_scan_kernel spells the same expressions out (its text is kept as measured).
 // Swapping the operands swaps hi*lo with lo*hi in the accumulation order and may move the last bit: the dense scorer forms
 // every entry once, with the smaller node index as the A row, and the scan (query = A) meets its bits for query < candidate.
 __device__ __forceinline__ void gram_block_split6(f32x16 (&acc)[2], const __bf16* ub, const __bf16* vb, int kb) {

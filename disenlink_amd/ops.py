@@ -1436,6 +1436,32 @@ def _filter_check(node_filter, Z, unordered: bool) -> None:
         node_filter._pair_rule()
 
 
+def _scan_tables(Z, H, node_filter, unordered: bool):
+    """How every scan starts: the refusals of the node filter, then of the tables -> (Z, H, N, K, d)."""
+    _filter_check(node_filter, Z, unordered)
+    return _rank_tables(Z, H)
+
+
+def _scan_buffers(excl, ws_bytes: int, device):
+    """-> (ex_rowptr, ex_col, workspace, keep-alive): the exclusion CSR ``excl`` = (rowptr, col) as C arguments and the
+    shared workspace of ``ws_bytes``."""
+    rp, cp, keep = _csr_args(*excl, device)
+    return rp, cp, _ws.get(max(256, int(ws_bytes)), device), keep
+
+
+def _filter_arg(node_filter, N: int, device, unordered: bool):
+    """(dl_node_filter* or None, keep-alive) for ``_scan_call``."""
+    return (None, ()) if node_filter is None else node_filter._c_arg(N, device, unordered)
+
+
+def _scan_call(name: str, args, nf) -> None:
+    """The one call path of the scans: the C entry ``name``, or ``name``_filtered with the rule appended where there is
+    one (``nf`` from ``_filter_arg``) — both entries stay in use, and each argument list is written once."""
+    if nf[0] is not None:
+        name, args = name + "_filtered", (*args, nf[0])
+    _lib.check(getattr(_lib.load(), name)(*args), name)
+
+
 def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool = True, node_filter=None):
     """-> (index int64 [Q,k], logit f32 [Q,k], prob f32 [Q,k]): the k best candidates of every query node by the logit
     s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), sorted (larger
@@ -1444,8 +1470,7 @@ def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool
     k are padded with index -1 / NaN.  ``node_filter`` (a ``NodeFilter``): only candidates whose group the query's group
     allows, on top of the exclusion.  Inference only (dl_score_topk: nothing of size Q x N is formed)."""
     lib = _lib.load()
-    _filter_check(node_filter, Z, False)
-    Z, H, N, K, d = _rank_tables(Z, H)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, False)
     k = int(k)
     if not 1 <= k <= RANK_MAX_K:
         raise ValueError(f"k={k} outside 1..{RANK_MAX_K}")
@@ -1456,17 +1481,12 @@ def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool
     prob = _empty((Q, k), torch.float32, Z.device)
     if Q == 0:
         return index, logit, prob
-    rp, cp, _keep = _csr_args(*exclusion_csr(exclude, N, Z.device), Z.device)
-    ws = _ws.get(int(lib.dl_score_topk_workspace_bytes(N, K, d, Q, k, 0)), Z.device)
-    if node_filter is not None:
-        nf, _keep_nf = node_filter._c_arg(N, Z.device, False)
-        _lib.check(lib.dl_score_topk_filtered(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), q.data_ptr(), Q, k, rp, cp,
-                                              1 if exclude_self else 0, index.data_ptr(), logit.data_ptr(), prob.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), _stream(), nf), "dl_score_topk_filtered")
-        return index, logit, prob
-    _lib.check(lib.dl_score_topk(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), q.data_ptr(), Q, k, rp, cp,
-                                 1 if exclude_self else 0, index.data_ptr(), logit.data_ptr(), prob.data_ptr(),
-                                 ws.data_ptr(), ws.numel(), _stream()), "dl_score_topk")
+    rp, cp, ws, _keep = _scan_buffers(exclusion_csr(exclude, N, Z.device), lib.dl_score_topk_workspace_bytes(N, K, d, Q, k, 0),
+                                      Z.device)
+    _scan_call("dl_score_topk", (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), q.data_ptr(), Q, k, rp, cp,
+                                 1 if exclude_self else 0, index.data_ptr(), logit.data_ptr(), prob.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), _stream()),
+               _filter_arg(node_filter, N, Z.device, False))
     return index, logit, prob
 
 
@@ -1477,8 +1497,7 @@ def score_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None):
     logit is the one the scan computes.  rank = 1 + greater + ties / 2 (metrics.ranking_metrics).  ``node_filter``: only
     candidates the rule allows for src[i] are counted; a target is ranked whether or not it is allowed.  dl_score_ranks."""
     lib = _lib.load()
-    _filter_check(node_filter, Z, False)
-    Z, H, N, K, d = _rank_tables(Z, H)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, False)
     s = _node_ids(src, N, Z.device, "src")
     v = _node_ids(dst, N, Z.device, "dst")
     if s.numel() != v.numel():
@@ -1497,18 +1516,12 @@ def score_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None):
     queries = queries.to(torch.int32).contiguous()
     g_sorted = _empty(T, torch.int64, Z.device)
     t_sorted = _empty(T, torch.int64, Z.device)
-    rp, cp, _keep = _csr_args(*exclusion_csr(exclude, N, Z.device), Z.device)
-    ws = _ws.get(int(lib.dl_score_topk_workspace_bytes(N, K, d, Q, 0, T)), Z.device)
-    if node_filter is not None:
-        nf, _keep_nf = node_filter._c_arg(N, Z.device, False)
-        _lib.check(lib.dl_score_ranks_filtered(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), queries.data_ptr(), Q,
-                                               tptr.data_ptr(), tdst.data_ptr(), T, rp, cp, g_sorted.data_ptr(),
-                                               t_sorted.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf),
-                   "dl_score_ranks_filtered")
-    else:
-        _lib.check(lib.dl_score_ranks(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), queries.data_ptr(), Q, tptr.data_ptr(),
-                                      tdst.data_ptr(), T, rp, cp, g_sorted.data_ptr(), t_sorted.data_ptr(), ws.data_ptr(),
-                                      ws.numel(), _stream()), "dl_score_ranks")
+    rp, cp, ws, _keep = _scan_buffers(exclusion_csr(exclude, N, Z.device), lib.dl_score_topk_workspace_bytes(N, K, d, Q, 0, T),
+                                      Z.device)
+    _scan_call("dl_score_ranks", (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), queries.data_ptr(), Q, tptr.data_ptr(),
+                                  tdst.data_ptr(), T, rp, cp, g_sorted.data_ptr(), t_sorted.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  _stream()),
+               _filter_arg(node_filter, N, Z.device, False))
     greater[order] = g_sorted
     ties[order] = t_sorted
     return greater, ties
@@ -1541,26 +1554,19 @@ def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-
     is that of the count, at the very end.  ``node_filter`` (a symmetric ``NodeFilter``): only pairs whose groups the rule
     allows, on top of the exclusion and the floor."""
     lib = _lib.load()
-    _filter_check(node_filter, Z, True)
-    Z, H, N, K, d = _rank_tables(Z, H)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True)
     m = int(m)
-    rp, cp, _keep = _csr_args(*_unordered_exclusion_csr(exclude, N, Z.device), Z.device)
+    rp, cp, ws, _keep = _scan_buffers(_unordered_exclusion_csr(exclude, N, Z.device), lib.dl_score_mine_workspace_bytes(N, K, d, m),
+                                      Z.device)
     src = _empty(max(m, 0), torch.int32, Z.device)
     dst = _empty(max(m, 0), torch.int32, Z.device)
     logit = _empty(max(m, 0), torch.float32, Z.device)
     prob = _empty(max(m, 0), torch.float32, Z.device)
     count = _empty(1, torch.int64, Z.device)
-    ws = _ws.get(max(256, int(lib.dl_score_mine_workspace_bytes(N, K, d, m))), Z.device)
-    if node_filter is not None:
-        nf, _keep_nf = node_filter._c_arg(N, Z.device, True)
-        _lib.check(lib.dl_score_mine_filtered(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, float(min_logit), m,
-                                              src.data_ptr(), dst.data_ptr(), logit.data_ptr(), prob.data_ptr(),
-                                              count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf),
-                   "dl_score_mine_filtered")
-    else:
-        _lib.check(lib.dl_score_mine(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, float(min_logit), m, src.data_ptr(),
-                                     dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), _stream()), "dl_score_mine")
+    _scan_call("dl_score_mine", (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, float(min_logit), m, src.data_ptr(),
+                                 dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
+                                 _stream()),
+               _filter_arg(node_filter, N, Z.device, True))
     c = int(count.item())
     return src[:c], dst[:c], logit[:c], prob[:c]
 
@@ -1572,12 +1578,11 @@ LINKS_MAX_N = MINE_MAX_N
 def _links_count(Z, H, t, min_logit, exclude, node_filter):
     """The count pass of ``score_links``: -> (rowptr int64 [N+1] on the device, the arguments of the fill pass)."""
     lib = _lib.load()
-    _filter_check(node_filter, Z, True)
-    Z, H, N, K, d = _rank_tables(Z, H)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True)
     if N > LINKS_MAX_N:
         raise ValueError(f"N={N} above {LINKS_MAX_N} (the tile-pair walk of dl_score_mine)")
     excl = _csr_args(*_unordered_exclusion_csr(exclude, N, Z.device), Z.device)
-    nf, _keep_nf = node_filter._c_arg(N, Z.device, True) if node_filter is not None else (None, ())
+    nf, _keep_nf = _filter_arg(node_filter, N, Z.device, True)
     # a workspace of its own, held across the two calls: the shared grow-only buffer may be handed out (and, under DL_POISON,
     # refilled) in between, and the fill pass reads the planes and the cell offsets the count pass left
     ws = _empty(max(256, int(lib.dl_score_links_workspace_bytes(N, K, d))), torch.uint8, Z.device)
@@ -1667,8 +1672,7 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter
     one exact check that works where nothing can be enumerated; under a ``node_filter``: the pairs the rule allows, less
     the excluded ones among them)."""
     lib = _lib.load()
-    _filter_check(node_filter, Z, True)
-    Z, H, N, K, d = _rank_tables(Z, H)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True)
     dev = Z.device
     s = _node_ids(src, N, dev, "src")
     v = _node_ids(dst, N, dev, "dst")
@@ -1682,8 +1686,8 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter
         raise ValueError(f"exclusion set of {ex.n_nodes} nodes, expected {N}")
     rowptr, col, ex_key = ex.rowptr, ex.col, ex.key
     total = N * (N - 1) // 2 - ex.n_pairs
+    nf = _filter_arg(node_filter, N, dev, True)
     if node_filter is not None:                                       # allowed pairs, less the excluded ones among them
-        nf, _keep_nf = node_filter._c_arg(N, dev, True)
         total = node_filter._n_pairs_allowed()
         if ex_key is not None and ex_key.numel():
             er, ec = torch.div(ex_key, N, rounding_mode="floor"), ex_key % N
@@ -1700,16 +1704,10 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter
     above = _empty(T + 1, torch.int64, dev)
     equal = _empty(T + 1, torch.int64, dev)
     counted = _empty(1, torch.int64, dev)
-    rp, cp, _keep = _csr_args(rowptr, col, dev)
-    ws = _ws.get(max(256, int(lib.dl_score_pair_ranks_workspace_bytes(N, K, d))), dev)
-    if node_filter is not None:
-        _lib.check(lib.dl_score_pair_ranks_filtered(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, tord.data_ptr(), T,
-                                                    above.data_ptr(), equal.data_ptr(), counted.data_ptr(), ws.data_ptr(),
-                                                    ws.numel(), _stream(), nf), "dl_score_pair_ranks_filtered")
-    else:
-        _lib.check(lib.dl_score_pair_ranks(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, tord.data_ptr(), T,
-                                           above.data_ptr(), equal.data_ptr(), counted.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           _stream()), "dl_score_pair_ranks")
+    rp, cp, ws, _keep = _scan_buffers((rowptr, col), lib.dl_score_pair_ranks_workspace_bytes(N, K, d), dev)
+    _scan_call("dl_score_pair_ranks", (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, tord.data_ptr(), T,
+                                       above.data_ptr(), equal.data_ptr(), counted.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream()), nf)
     cs = torch.cumsum(above, dim=0)
     g_sorted = cs[T] - cs[:T]                                         # candidates that found more than p targets below them
     t_sorted = equal[first]
