@@ -357,9 +357,18 @@ int dl_score_topk_form(int N, int K, int d, int n_queries, int k, int* out) {
     return DL_OK;
 }
 
+static bool known_dtype(dl_dtype dtype) { return dtype == DL_F32 || dtype == DL_BF16; }
+
+// every scan of the family serves the same (K, d), with fp32 tables (three planes, six products) and with bf16 tables (one)
+int dl_score_scan_supported(int K, int d, dl_dtype dtype) { return known_dtype(dtype) && score_rank_supported(K, d) ? 1 : 0; }
+
 size_t dl_score_topk_workspace_bytes(int N, int K, int d, int n_queries, int k, int n_targets) {
-    if (N <= 0 || n_queries <= 0 || k < 0 || n_targets < 0 || !score_rank_supported(K, d)) return 0;
-    return score_rank_workspace_bytes(N, K, d, n_queries, k, n_targets);
+    return dl_score_topk_workspace_bytes_dtype(N, K, d, DL_F32, n_queries, k, n_targets);
+}
+
+size_t dl_score_topk_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype, int n_queries, int k, int n_targets) {
+    if (N <= 0 || n_queries <= 0 || k < 0 || n_targets < 0 || !score_rank_supported(K, d) || !known_dtype(dtype)) return 0;
+    return score_rank_workspace_bytes(N, K, d, n_queries, k, n_targets, dtype);
 }
 
 // a node-group rule (NULL = none): host-side checks only, the arrays are device memory
@@ -397,7 +406,8 @@ static bool scan_shape_ok(const ScanSpec& s, int N, int K, int d) {      // the 
     return N >= s.n_min && N <= s.n_max && score_rank_supported(K, d) &&
            (!(s.flags & CAP_ELEMS) || (long long)N * K * d < (1LL << 40));
 }
-static int check_scan_shape(const ScanSpec& s, int N, int K, int d) {
+static int check_scan_shape(const ScanSpec& s, int N, int K, int d, dl_dtype dtype = DL_F32) {
+    DL_REQUIRE(known_dtype(dtype), "unknown dtype %d", (int)dtype);
     if (int rc = check_shape(K, d)) return rc;
     DL_REQUIRE(score_rank_supported(K, d), "%s fp32 tables with 1 <= d <= 128, got d=%d", s.serves, d);
     if (!(s.flags & OWN_N)) DL_REQUIRE(N >= s.n_min && N <= s.n_max, "N=%d outside %d..%d (%s)", N, s.n_min, s.n_max, s.n_why);
@@ -419,9 +429,9 @@ static int check_scan_ws(const ScanSpec& s, const void* ws, size_t ws_bytes, siz
     return (s.flags & WS_CODE) ? DL_E_WORKSPACE : DL_E_ARG;
 }
 
-static int check_rank_args(const void* Z, const void* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
-                           const int32_t* ex_rowptr, const int32_t* ex_col) {
-    if (int rc = check_scan_shape(RANK_SCAN, N, K, d)) return rc;
+static int check_rank_args(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* queries,
+                           int n_queries, const int32_t* ex_rowptr, const int32_t* ex_col) {
+    if (int rc = check_scan_shape(RANK_SCAN, N, K, d, dtype)) return rc;
     DL_REQUIRE(N >= 1 && n_queries >= 0, "bad size N=%d n_queries=%d", N, n_queries);
     DL_REQUIRE((long long)N * K * d < (1LL << 40), "tables too large");
     DL_REQUIRE(t != 0.0f, "temperature is 0");
@@ -438,14 +448,22 @@ int dl_score_topk(const float* Z, const float* H, int N, int K, int d, float t, 
 int dl_score_topk_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int n_queries,
                            int k, const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index, float* logit,
                            float* prob, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter) {
-    if (int rc = check_rank_args(Z, H, N, K, d, t, queries, n_queries, ex_rowptr, ex_col)) return rc;
+    return dl_score_topk_dtype(Z, H, N, K, d, DL_F32, t, queries, n_queries, k, ex_rowptr, ex_col, exclude_self, index, logit, prob,
+                               ws, ws_bytes, stream, filter);
+}
+
+// The *_dtype entries are the implementations; the fp32 entries above and below call them with DL_F32.
+int dl_score_topk_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* queries,
+                        int n_queries, int k, const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index,
+                        float* logit, float* prob, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter) {
+    if (int rc = check_rank_args(Z, H, N, K, d, dtype, t, queries, n_queries, ex_rowptr, ex_col)) return rc;
     if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(k >= 1 && k <= 128, "k=%d outside 1..128", k);
     if (n_queries == 0) return DL_OK;
     DL_REQUIRE(index && logit && prob, "NULL output");
-    const size_t need = score_rank_workspace_bytes(N, K, d, n_queries, k, 0);
+    const size_t need = score_rank_workspace_bytes(N, K, d, n_queries, k, 0, dtype);
     if (int rc = check_scan_ws(RANK_SCAN, ws, ws_bytes, need, "dl_score_topk_workspace_bytes")) return rc;
-    return score_topk(Z, H, N, K, d, t, queries, n_queries, k, ex_rowptr, ex_col, exclude_self, index, logit, prob, ws,
+    return score_topk(Z, H, dtype, N, K, d, t, queries, n_queries, k, ex_rowptr, ex_col, exclude_self, index, logit, prob, ws,
                       (hipStream_t)stream, filter);
 }
 
@@ -460,22 +478,30 @@ int dl_score_ranks_filtered(const float* Z, const float* H, int N, int K, int d,
                             const int32_t* tptr, const int32_t* tdst, int n_targets, const int32_t* ex_rowptr,
                             const int32_t* ex_col, int64_t* greater, int64_t* ties, void* ws, size_t ws_bytes, void* stream,
                             const dl_node_filter* filter) {
-    if (int rc = check_rank_args(Z, H, N, K, d, t, queries, n_queries, ex_rowptr, ex_col)) return rc;
+    return dl_score_ranks_dtype(Z, H, N, K, d, DL_F32, t, queries, n_queries, tptr, tdst, n_targets, ex_rowptr, ex_col, greater, ties,
+                                ws, ws_bytes, stream, filter);
+}
+
+int dl_score_ranks_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* queries,
+                         int n_queries, const int32_t* tptr, const int32_t* tdst, int n_targets, const int32_t* ex_rowptr,
+                         const int32_t* ex_col, int64_t* greater, int64_t* ties, void* ws, size_t ws_bytes, void* stream,
+                         const dl_node_filter* filter) {
+    if (int rc = check_rank_args(Z, H, N, K, d, dtype, t, queries, n_queries, ex_rowptr, ex_col)) return rc;
     if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(n_targets >= 0, "negative size");
     if (n_queries == 0 || n_targets == 0) return DL_OK;
     DL_REQUIRE(tptr && tdst && greater && ties, "NULL argument");
     DL_REQUIRE((long long)n_targets + n_queries < (1LL << 31), "too many targets");
-    const size_t need = score_rank_workspace_bytes(N, K, d, n_queries, 0, n_targets);
+    const size_t need = score_rank_workspace_bytes(N, K, d, n_queries, 0, n_targets, dtype);
     if (int rc = check_scan_ws(RANK_SCAN, ws, ws_bytes, need, "dl_score_topk_workspace_bytes")) return rc;
-    return score_ranks(Z, H, N, K, d, t, queries, n_queries, tptr, tdst, n_targets, ex_rowptr, ex_col, greater, ties, ws,
+    return score_ranks(Z, H, dtype, N, K, d, t, queries, n_queries, tptr, tdst, n_targets, ex_rowptr, ex_col, greater, ties, ws,
                        (hipStream_t)stream, filter);
 }
 
 int dl_score_mine_supported(int K, int d) { return score_mine_supported(K, d) ? 1 : 0; }
 
-static int check_mine_shape(int N, int K, int d, int m) {
-    if (int rc = check_scan_shape(MINE_SCAN, N, K, d)) return rc;
+static int check_mine_shape(int N, int K, int d, int m, dl_dtype dtype = DL_F32) {
+    if (int rc = check_scan_shape(MINE_SCAN, N, K, d, dtype)) return rc;
     DL_REQUIRE(m >= 1 && m <= 65536, "m=%d outside 1..65536", m);
     return DL_OK;
 }
@@ -487,9 +513,11 @@ int dl_score_mine_form(int N, int K, int d, int m, int* out) {
     return DL_OK;
 }
 
-size_t dl_score_mine_workspace_bytes(int N, int K, int d, int m) {
-    if (!scan_shape_ok(MINE_SCAN, N, K, d) || m < 1 || m > 65536) return 0;
-    return score_mine_workspace_bytes(N, K, d, m);
+size_t dl_score_mine_workspace_bytes(int N, int K, int d, int m) { return dl_score_mine_workspace_bytes_dtype(N, K, d, DL_F32, m); }
+
+size_t dl_score_mine_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype, int m) {
+    if (!scan_shape_ok(MINE_SCAN, N, K, d) || !known_dtype(dtype) || m < 1 || m > 65536) return 0;
+    return score_mine_workspace_bytes(N, K, d, m, dtype);
 }
 
 int dl_score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
@@ -502,14 +530,21 @@ int dl_score_mine(const float* Z, const float* H, int N, int K, int d, float t, 
 int dl_score_mine_filtered(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
                            const int32_t* ex_col, float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob,
                            int64_t* count, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter) {
-    if (int rc = check_mine_shape(N, K, d, m)) return rc;
+    return dl_score_mine_dtype(Z, H, N, K, d, DL_F32, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws, ws_bytes,
+                               stream, filter);
+}
+
+int dl_score_mine_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
+                        const int32_t* ex_col, float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob,
+                        int64_t* count, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter) {
+    if (int rc = check_mine_shape(N, K, d, m, dtype)) return rc;
     if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     if (int rc = check_scan_ptrs(MINE_SCAN, N == 0 || (Z && H), ex_rowptr, ex_col)) return rc;
     DL_REQUIRE(src && dst && logit && prob && count, "NULL output");
-    if (int rc = check_scan_ws(MINE_SCAN, ws, ws_bytes, score_mine_workspace_bytes(N, K, d, m), "dl_score_mine_workspace_bytes"))
+    if (int rc = check_scan_ws(MINE_SCAN, ws, ws_bytes, score_mine_workspace_bytes(N, K, d, m, dtype), "dl_score_mine_workspace_bytes"))
         return rc;
-    return score_mine(Z, H, N, K, d, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws, (hipStream_t)stream,
+    return score_mine(Z, H, dtype, N, K, d, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws, (hipStream_t)stream,
                       filter);
 }
 
@@ -522,35 +557,50 @@ int dl_score_links_form(int N, int K, int d, int* out) {
     return DL_OK;
 }
 
-size_t dl_score_links_workspace_bytes(int N, int K, int d) {
-    return scan_shape_ok(LINKS_SCAN, N, K, d) ? score_links_workspace_bytes(N, K, d) : 0;
+size_t dl_score_links_workspace_bytes(int N, int K, int d) { return dl_score_links_workspace_bytes_dtype(N, K, d, DL_F32); }
+
+size_t dl_score_links_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype) {
+    return scan_shape_ok(LINKS_SCAN, N, K, d) && known_dtype(dtype) ? score_links_workspace_bytes(N, K, d, dtype) : 0;
 }
 
 // what the count and the fill call check alike
-static int check_links_args(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
+static int check_links_args(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
                             const int32_t* ex_col, const dl_node_filter* filter, const void* ws, size_t ws_bytes,
                             const int64_t* rowptr) {
-    if (int rc = check_scan_shape(LINKS_SCAN, N, K, d)) return rc;
+    if (int rc = check_scan_shape(LINKS_SCAN, N, K, d, dtype)) return rc;
     if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     if (int rc = check_scan_ptrs(LINKS_SCAN, Z && H && rowptr, ex_rowptr, ex_col)) return rc;
-    return check_scan_ws(LINKS_SCAN, ws, ws_bytes, score_links_workspace_bytes(N, K, d), "dl_score_links_workspace_bytes");
+    return check_scan_ws(LINKS_SCAN, ws, ws_bytes, score_links_workspace_bytes(N, K, d, dtype), "dl_score_links_workspace_bytes");
 }
 
 int dl_score_links_count(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
                          const int32_t* ex_col, float min_logit, const dl_node_filter* filter, void* ws, size_t ws_bytes,
                          int64_t* rowptr, void* stream) {
-    if (int rc = check_links_args(Z, H, N, K, d, t, ex_rowptr, ex_col, filter, ws, ws_bytes, rowptr)) return rc;
-    return score_links_count(Z, H, N, K, d, t, ex_rowptr, ex_col, min_logit, filter, ws, rowptr, (hipStream_t)stream);
+    return dl_score_links_count_dtype(Z, H, N, K, d, DL_F32, t, ex_rowptr, ex_col, min_logit, filter, ws, ws_bytes, rowptr, stream);
+}
+
+int dl_score_links_count_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
+                               const int32_t* ex_col, float min_logit, const dl_node_filter* filter, void* ws, size_t ws_bytes,
+                               int64_t* rowptr, void* stream) {
+    if (int rc = check_links_args(Z, H, N, K, d, dtype, t, ex_rowptr, ex_col, filter, ws, ws_bytes, rowptr)) return rc;
+    return score_links_count(Z, H, dtype, N, K, d, t, ex_rowptr, ex_col, min_logit, filter, ws, rowptr, (hipStream_t)stream);
 }
 
 int dl_score_links_fill(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
                         const int32_t* ex_col, float min_logit, const dl_node_filter* filter, void* ws, size_t ws_bytes,
                         const int64_t* rowptr, int64_t nnz, int32_t* col, float* logit, float* prob, void* stream) {
-    if (int rc = check_links_args(Z, H, N, K, d, t, ex_rowptr, ex_col, filter, ws, ws_bytes, rowptr)) return rc;
+    return dl_score_links_fill_dtype(Z, H, N, K, d, DL_F32, t, ex_rowptr, ex_col, min_logit, filter, ws, ws_bytes, rowptr, nnz, col,
+                                     logit, prob, stream);
+}
+
+int dl_score_links_fill_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
+                              const int32_t* ex_col, float min_logit, const dl_node_filter* filter, void* ws, size_t ws_bytes,
+                              const int64_t* rowptr, int64_t nnz, int32_t* col, float* logit, float* prob, void* stream) {
+    if (int rc = check_links_args(Z, H, N, K, d, dtype, t, ex_rowptr, ex_col, filter, ws, ws_bytes, rowptr)) return rc;
     DL_REQUIRE(nnz >= 0, "nnz=%lld is negative", (long long)nnz);
     DL_REQUIRE(nnz == 0 || (col && logit), "NULL output");
-    return score_links_fill(N, K, d, t, ex_rowptr, ex_col, min_logit, filter, ws, rowptr, (long long)nnz, col, logit, prob,
+    return score_links_fill(dtype, N, K, d, t, ex_rowptr, ex_col, min_logit, filter, ws, rowptr, (long long)nnz, col, logit, prob,
                             (hipStream_t)stream);
 }
 
@@ -563,25 +613,34 @@ int dl_score_pair_ranks_form(int N, int K, int d, int n_targets, int* out) {
     return DL_OK;
 }
 
-size_t dl_score_pair_logits_workspace_bytes(int N, int K, int d) {
-    return scan_shape_ok(PAIR_SCAN, N, K, d) ? score_pair_logits_workspace_bytes(N, K, d) : 0;
+size_t dl_score_pair_logits_workspace_bytes(int N, int K, int d) { return dl_score_pair_logits_workspace_bytes_dtype(N, K, d, DL_F32); }
+
+size_t dl_score_pair_logits_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype) {
+    return scan_shape_ok(PAIR_SCAN, N, K, d) && known_dtype(dtype) ? score_pair_logits_workspace_bytes(N, K, d, dtype) : 0;
 }
 
-size_t dl_score_pair_ranks_workspace_bytes(int N, int K, int d) {
-    return scan_shape_ok(PAIR_SCAN, N, K, d) ? score_pair_ranks_workspace_bytes(N, K, d) : 0;
+size_t dl_score_pair_ranks_workspace_bytes(int N, int K, int d) { return dl_score_pair_ranks_workspace_bytes_dtype(N, K, d, DL_F32); }
+
+size_t dl_score_pair_ranks_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype) {
+    return scan_shape_ok(PAIR_SCAN, N, K, d) && known_dtype(dtype) ? score_pair_ranks_workspace_bytes(N, K, d, dtype) : 0;
 }
 
 int dl_score_pair_logits(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
                          int n_pairs, float* logit, void* ws, size_t ws_bytes, void* stream) {
-    if (int rc = check_scan_shape(PAIR_SCAN, N, K, d)) return rc;
+    return dl_score_pair_logits_dtype(Z, H, N, K, d, DL_F32, t, a, b, n_pairs, logit, ws, ws_bytes, stream);
+}
+
+int dl_score_pair_logits_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* a,
+                               const int32_t* b, int n_pairs, float* logit, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_scan_shape(PAIR_SCAN, N, K, d, dtype)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     DL_REQUIRE(n_pairs >= 0 && n_pairs <= (1 << 30), "n_pairs=%d outside 0..2^30", n_pairs);
     if (n_pairs == 0) return DL_OK;
     if (int rc = check_scan_ptrs(PAIR_SCAN, Z && H && a && b && logit, nullptr, nullptr)) return rc;
-    if (int rc = check_scan_ws(PAIR_SCAN, ws, ws_bytes, score_pair_logits_workspace_bytes(N, K, d),
+    if (int rc = check_scan_ws(PAIR_SCAN, ws, ws_bytes, score_pair_logits_workspace_bytes(N, K, d, dtype),
                                "dl_score_pair_logits_workspace_bytes"))
         return rc;
-    return score_pair_logits(Z, H, N, K, d, t, a, b, n_pairs, logit, ws, (hipStream_t)stream);
+    return score_pair_logits(Z, H, dtype, N, K, d, t, a, b, n_pairs, logit, ws, (hipStream_t)stream);
 }
 
 int dl_score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
@@ -595,15 +654,23 @@ int dl_score_pair_ranks_filtered(const float* Z, const float* H, int N, int K, i
                                  const int32_t* ex_col, const uint32_t* target_order, int n_targets, unsigned long long* above,
                                  unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes,
                                  void* stream, const dl_node_filter* filter) {
-    if (int rc = check_scan_shape(PAIR_SCAN, N, K, d)) return rc;
+    return dl_score_pair_ranks_dtype(Z, H, N, K, d, DL_F32, t, ex_rowptr, ex_col, target_order, n_targets, above, equal, n_candidates,
+                                     ws, ws_bytes, stream, filter);
+}
+
+int dl_score_pair_ranks_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
+                              const int32_t* ex_col, const uint32_t* target_order, int n_targets, unsigned long long* above,
+                              unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes, void* stream,
+                              const dl_node_filter* filter) {
+    if (int rc = check_scan_shape(PAIR_SCAN, N, K, d, dtype)) return rc;
     if (int rc = check_filter(filter)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     DL_REQUIRE(n_targets >= 0 && n_targets <= (1 << 30), "n_targets=%d outside 0..2^30", n_targets);
     const bool have = Z && H && above && equal && n_candidates && (n_targets == 0 || target_order);
     if (int rc = check_scan_ptrs(PAIR_SCAN, have, ex_rowptr, ex_col)) return rc;
-    const size_t need = score_pair_ranks_workspace_bytes(N, K, d);
+    const size_t need = score_pair_ranks_workspace_bytes(N, K, d, dtype);
     if (int rc = check_scan_ws(PAIR_SCAN, ws, ws_bytes, need, "dl_score_pair_ranks_workspace_bytes")) return rc;
-    return score_pair_ranks(Z, H, N, K, d, t, ex_rowptr, ex_col, target_order, n_targets, above, equal, n_candidates, ws,
+    return score_pair_ranks(Z, H, dtype, N, K, d, t, ex_rowptr, ex_col, target_order, n_targets, above, equal, n_candidates, ws,
                             (hipStream_t)stream, filter);
 }
 

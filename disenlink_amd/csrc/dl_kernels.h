@@ -75,38 +75,40 @@ int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d
 
 // ranking of all candidates of query rows on the matrix cores (dl_score_rank.hip): fp32 tables, 1 <= d <= 128
 bool score_rank_supported(int K, int d);
-size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T);
-int score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, int k,
+// dt: the type of the tables Z and H, DL_F32 (three bf16 planes per operand, six products) or DL_BF16 (the table is its own
+// plane, one product); the launch forms do not depend on it, the workspace does
+size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T, dl_dtype dt = DL_F32);
+int score_topk(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* queries, int Q, int k,
                const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index, float* logit, float* prob,
                void* ws, hipStream_t st, const dl_node_filter* filter = nullptr);       // filter: checked by the caller
-int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, const int32_t* tptr,
+int score_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* queries, int Q, const int32_t* tptr,
                 const int32_t* tdst, int T, const int32_t* ex_rowptr, const int32_t* ex_col, int64_t* greater, int64_t* ties,
                 void* ws, hipStream_t st, const dl_node_filter* filter = nullptr);
 
 // global top-m of the logits of all unordered pairs on the matrix cores (dl_score_mine.hip): fp32 tables, 1 <= d <= 128
 bool score_mine_supported(int K, int d);
-size_t score_mine_workspace_bytes(int N, int K, int d, int m);
-int score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
+size_t score_mine_workspace_bytes(int N, int K, int d, int m, dl_dtype dt = DL_F32);
+int score_mine(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
                float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws,
                hipStream_t st, const dl_node_filter* filter = nullptr);
 
 // logits of given (A row, B row) pairs with the bits of the scans (dl_score_rank.hip), and the global rank counts of sorted
 // target keys among all unordered pairs (dl_score_mine.hip, one counting scan): fp32 tables, 1 <= d <= 128
-size_t score_pair_logits_workspace_bytes(int N, int K, int d);
-int score_pair_logits(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* a, const int32_t* b, int T,
+size_t score_pair_logits_workspace_bytes(int N, int K, int d, dl_dtype dt = DL_F32);
+int score_pair_logits(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b, int T,
                       float* logit, void* ws, hipStream_t st);
-size_t score_pair_ranks_workspace_bytes(int N, int K, int d);
-int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
+size_t score_pair_ranks_workspace_bytes(int N, int K, int d, dl_dtype dt = DL_F32);
+int score_pair_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
                      const unsigned* tord, int T, unsigned long long* gcnt, unsigned long long* tcnt, unsigned long long* ncand,
                      void* ws, hipStream_t st, const dl_node_filter* filter = nullptr);
 
 // every unordered pair whose logit reaches a floor, as a symmetric CSR (dl_score_mine.hip: a counting scan, the offsets, a
 // filling scan over the workspace the count left): fp32 tables, 1 <= d <= 128, N <= 46,340
 bool score_links_supported(int K, int d);
-size_t score_links_workspace_bytes(int N, int K, int d);
-int score_links_count(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
+size_t score_links_workspace_bytes(int N, int K, int d, dl_dtype dt = DL_F32);
+int score_links_count(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
                       float min_logit, const dl_node_filter* filter, void* ws, int64_t* rowptr, hipStream_t st);
-int score_links_fill(int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit,
+int score_links_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit,
                      const dl_node_filter* filter, void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit,
                      float* prob, hipStream_t st);
 

@@ -1,5 +1,6 @@
 // fp32 matrix -> three bf16 planes (x = hi + mid + lo, dl_tiles.h) in global memory, tile-major and zero-filled out
-// to the padded extents, for the projection kernels that run fp32-grade products on the bf16 matrix path.
+// to the padded extents, for the projection kernels that run fp32-grade products on the bf16 matrix path; and a bf16
+// matrix -> its one plane in the same layout (copy_rows), for the all-pairs scans over bf16 tables.
 #include "dl_common.h"
 #include "dl_kernels.h"
 #include "dl_tiles.h"
@@ -37,6 +38,26 @@ __device__ __forceinline__ void split_rows_body(const RowsJob& j, size_t g, int 
 }
 __global__ __launch_bounds__(256) void split_rows_kernel(RowsJob j) {
     split_rows_body(j, (size_t)blockIdx.x * 256 + threadIdx.x, blockIdx.y);
+}
+
+// bf16 source: the value is its own (only) plane.  The same walk, tiles of [1][128][32]; the elements are copied as 16-bit
+// words (a row of odd length has no wider alignment), what lies outside the matrix is written as zero.  rows != NULL: a gather.
+struct CopyJob { const unsigned short* src; const int32_t* rows; int R, C, ld; size_t sb; unsigned short* dst; int nrb, ncb; size_t db; };
+__global__ __launch_bounds__(256) void copy_rows_kernel(CopyJob j) {
+    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+    constexpr int PLANE_TILE = PLANE_ROWS * SPLIT_COLS, PIECES = PLANE_TILE / 8;
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= (size_t)j.nrb * j.ncb * PIECES) return;
+    const int t = (int)(g / PIECES), q = (int)(g % PIECES);
+    const int rb = t / j.ncb, cb = t % j.ncb;
+    const int r = rb * PLANE_ROWS + (q >> 2), c0 = cb * SPLIT_COLS + (q & 3) * 8;
+    const bool row_ok = r < j.R;
+    const size_t srow = row_ok ? (size_t)(j.rows != nullptr ? j.rows[r] : r) : 0;
+    const unsigned short* __restrict__ s = j.src + (size_t)blockIdx.y * j.sb + srow * j.ld;
+    u16x8 p;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) p[e] = (row_ok && c0 + e < j.C) ? s[c0 + e] : (unsigned short)0;
+    *reinterpret_cast<u16x8*>(j.dst + (size_t)blockIdx.y * j.db + plane_tile<SPLIT_COLS, 1>(rb, cb, j.ncb) + q * 8) = p;
 }
 
 // Planes of the transpose: rows = c (columns of src), columns = r.  Block = a 64 x 64 tile of src through LDS:
@@ -139,6 +160,14 @@ void split_w2(const float* W2, int rows, int nhid, __bf16* dst, int nhid_p, hipS
 void split_rows(const float* src, int B, int R, int C, int ld, size_t sb, __bf16* dst, hipStream_t st) {
     const RowsJob j = rows_job(src, R, C, ld, sb, dst);
     hipLaunchKernelGGL(split_rows_kernel, dim3(rows_blocks(j), (unsigned)B), dim3(256), 0, st, j);
+}
+
+void copy_rows(const __bf16* src, const int32_t* rows, int B, int R, int C, int ld, size_t sb, __bf16* dst, hipStream_t st) {
+    const int nrb = (int)(round_up(R, PLANE_ROWS) / PLANE_ROWS), ncb = plane_chunks<SPLIT_COLS>(C, SPLIT_COLS);
+    const CopyJob j = {reinterpret_cast<const unsigned short*>(src), rows, R, C, ld, sb, reinterpret_cast<unsigned short*>(dst), nrb, ncb,
+                       plane_array_elems<1>(R, C, SPLIT_COLS)};
+    const unsigned blocks = (unsigned)(((size_t)nrb * ncb * (PLANE_ROWS * SPLIT_COLS / 8) + 255) / 256);
+    hipLaunchKernelGGL(copy_rows_kernel, dim3(blocks, (unsigned)B), dim3(256), 0, st, j);
 }
 
 void split_fwd_operands(const float* x, int N, int F, __bf16* xP, const float* W1, int K, int nhid, __bf16* wP,

@@ -13,11 +13,14 @@ using namespace project;
 
 typedef unsigned long long u64;
 
-// ---- a pipeline step (after the products of gram_block_split6, dl_tiles.h) -----------------------------------------
-// The operand of a wave in step s: row `row` of the LDS plane image [2][3][128][SPLIT_PITCH] the step reads (A: row =
+// ---- a pipeline step (after the products of gram_block<P>, dl_tiles.h) ---------------------------------------------
+// P = planes per operand: 3 for fp32 tables, 1 for bf16 tables (the instantiations the *_dtype entries launch with DL_BF16).
+// Everything after the products (factor_update, the masks, every epilogue) does not know P.
+// The operand of a wave in step s: row `row` of the LDS plane image [2][P][128][SPLIT_PITCH] the step reads (A: row =
 // 32 wu + lane % 32 of the u image, B: 64 wv + lane % 32 of the v image), lane half h at k = 8h .. 8h + 7 of a block.
+template <int P = 3>
 __device__ __forceinline__ const __bf16* gram_operand(const __bf16* image, int s, int row, int half) {
-    return image + (s & 1) * 3 * PLANE_ROWS * SPLIT_PITCH + row * SPLIT_PITCH + half * 8;
+    return image + (s & 1) * P * PLANE_ROWS * SPLIT_PITCH + row * SPLIT_PITCH + half * 8;
 }
 
 // Step r of a factor's 2 nd steps is over: S = z.z complete (r = nd - 1) gives e = exp(S / t), Q = h.h complete
@@ -113,6 +116,16 @@ inline void launch_lds(unsigned grid, int threads, size_t lds, hipStream_t st, c
     ensure_dynamic_lds(reinterpret_cast<const void*>(KERNEL), lds, done);
     hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(threads), lds, st, args...);
 }
+// The tables of a scan as its one-plane or three-plane arrays: dst = K matrices of plane_array_elems<P>(N, d, 32) elements.
+// DL_BF16 tables are copied (rows != NULL: gathered), DL_F32 tables split; a gather of fp32 rows is the caller's.
+inline void table_planes(const void* T, dl_dtype dt, const int32_t* rows, int R, int K, int d, __bf16* dst, hipStream_t st) {
+    if (dt == DL_BF16) copy_rows((const __bf16*)T, rows, K, R, d, K * d, (size_t)d, dst, st);
+    else split_rows((const float*)T, K, R, d, K * d, (size_t)d, dst, st);
+}
+inline size_t table_plane_elems(dl_dtype dt, size_t rows, size_t cols) {
+    return dt == DL_BF16 ? plane_array_elems<1>(rows, cols, SPLIT_COLS) : plane_array_elems<3>(rows, cols, SPLIT_COLS);
+}
+
 // ... of a scan in its plain or, under a node-group rule, its FILT instantiation (which keeps FILTER_LDS_BYTES behind `lds`)
 template <auto PLAIN, auto FILTERED, class Args>
 inline void launch_scan(const dl_node_filter* nf, unsigned grid, int threads, size_t lds, hipStream_t st, const Args& a) {

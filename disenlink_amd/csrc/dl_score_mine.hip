@@ -42,6 +42,10 @@
 //
 // Node groups (the FILT instantiations; dl_score_mine_filtered, dl_score_pair_ranks_filtered): a symmetric rule on the groups
 // of u and v, formed into the row mask ahead of the exclusion; a candidate passes both.  The epilogues do not change.
+//
+// bf16 tables (the *_dtype entries with DL_BF16; the P = 1 instantiations): the table is its own single plane (copy_rows), a
+// step stages one plane per operand and issues one product per block (gram_block<1>).  On the same values the logits are the
+// bits of the three-plane scan (dl_tiles.h), so everything above holds unchanged; only the plane arrays of the workspace shrink.
 #include <cstddef>
 #include "dl_common.h"
 #include "dl_config.h"
@@ -105,10 +109,10 @@ struct ScanArgs {
     LinkArgs link;
 };
 
-constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
-constexpr size_t LDS_BYTES = STAGE_BYTES + TT * 4 * 4 + BINS * 4;
-constexpr size_t LDS_BYTES_COUNT = STAGE_BYTES + TT * 4 * 4 + SEPS * 4;
-static_assert(LDS_BYTES % 16 == 0 && LDS_BYTES_COUNT % 16 == 0 && LDS_BYTES_COUNT + FILTER_LDS_BYTES <= 160 * 1024, "LDS of a CU");
+// LDS of an instantiation with P planes per operand: the two double-buffered images, the exclusion mask, the mode's table
+constexpr size_t lds_bytes(int mode, int P) { return (size_t)2 * 2 * P * TT * SLD * 2 + TT * 4 * 4 + (mode == COUNT ? SEPS : BINS) * 4; }
+static_assert(lds_bytes(HIST, 3) % 16 == 0 && lds_bytes(COUNT, 3) % 16 == 0 && lds_bytes(HIST, 1) % 16 == 0 &&
+              lds_bytes(COUNT, 1) % 16 == 0 && lds_bytes(COUNT, 3) + FILTER_LDS_BYTES <= 160 * 1024, "LDS of a CU");
 
 __device__ __forceinline__ u64 wave_sum(u64 x) {
 #pragma unroll
@@ -203,12 +207,14 @@ __device__ __forceinline__ void count_flush(const CountArgs& C, u64 ncount, u64 
 // FILT: the node-group rule on top of the exclusion, as in the ranking scan (dl_score_rank.hip): the groups of the pair's v
 // and u nodes are staged in the pair's last step but one, all 512 threads form the mask from the rule, one word each, in its
 // last step, and the row threads OR the exclusion into it where the unfiltered kernel starts from zero.
-template <int MODE, bool FILT = false>
+// P: planes per operand, 3 (fp32 tables, split_rows) or 1 (bf16 tables, copy_rows); it reaches the staging and the products
+// only.  The one-plane step keeps the 32-column width: k-blocks are added in ascending k exactly as in the three-plane step.
+template <int MODE, bool FILT = false, int P = 3>
 __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
-    __bf16* vs = us + 2 * 3 * TT * SLD;
-    unsigned* exm = reinterpret_cast<unsigned*>(vs + 2 * 3 * TT * SLD);   // [TT][4]: excluded columns of the tile
+    __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][P][TT][SLD]
+    __bf16* vs = us + 2 * P * TT * SLD;
+    unsigned* exm = reinterpret_cast<unsigned*>(vs + 2 * P * TT * SLD);   // [TT][4]: excluded columns of the tile
     unsigned* bins = exm + TT * 4;                              // HIST: [BINS]; COUNT: [SEPS] separators; DEG / FILL: masks, bases
     u64* fal = reinterpret_cast<u64*>(bins + (MODE == COUNT ? SEPS : BINS));           // FILT: allow [64] | cgrp [TT] | rgrp [TT]
     unsigned char* cgrp = reinterpret_cast<unsigned char*>(fal + 64);
@@ -265,7 +271,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     if constexpr (FILT)
         if (tid < 64) fal[tid] = tid < A.filt.n_groups ? A.filt.allow[tid] : 0ull;
 
-    PlaneStage<MTHR, SDC> uq, vq;
+    PlaneStage<MTHR, SDC, P> uq, vq;
     static_assert(TT == PLANE_ROWS, "tiles of the plane arrays");
     int jcur = 0;                                               // tile pair (of this workgroup) the products are in
     auto fetch = [&](int s) {
@@ -274,12 +280,12 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         const int dc = r < nd ? r : r - nd;
         const __bf16* src = (r < nd ? A.cz : A.ch) + (size_t)k * A.cbatch;
         const int fq = j == jcur ? qt : qt2, fc = j == jcur ? ct : ct2;      // a fetch runs at most one pair ahead
-        uq.fetch(src + plane_tile<SDC>(fq, dc, nd), tid);
-        vq.fetch(src + plane_tile<SDC>(fc, dc, nd), tid);
+        uq.fetch(src + plane_tile<SDC, P>(fq, dc, nd), tid);
+        vq.fetch(src + plane_tile<SDC, P>(fc, dc, nd), tid);
     };
     auto stash = [&](int s) {
-        uq.stash(us + (s & 1) * 3 * TT * SLD, tid);
-        vq.stash(vs + (s & 1) * 3 * TT * SLD, tid);
+        uq.stash(us + (s & 1) * P * TT * SLD, tid);
+        vq.stash(vs + (s & 1) * P * TT * SLD, tid);
     };
 
     f32x16 acc[2], term[2];
@@ -301,11 +307,11 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
             const int node = (tid < TT ? ct * TT : (qt - 1) * TT) + tid;
             if (rem == per_tile - 2 && tid < 2 * TT && node < A.N) gb = A.filt.group[node];
         }
-        const __bf16* ub = gram_operand(us, s, wu * 32 + li, half);
-        const __bf16* vb = gram_operand(vs, s, wv * 64 + li, half);
+        const __bf16* ub = gram_operand<P>(us, s, wu * 32 + li, half);
+        const __bf16* vb = gram_operand<P>(vs, s, wv * 64 + li, half);
 #pragma unroll
         for (int kb = 0; kb < SDC / 16; ++kb) {
-            gram_block_split6(acc, ub, vb, kb);                 // the ranking scan's products (dl_tiles.h)
+            gram_block<P>(acc, ub, vb, kb);                     // the ranking scan's products (dl_tiles.h)
             if (kb == 0) {
                 if (s + 1 < steps) stash(s + 1);
                 fetch(min(s + 2, steps - 1));                   // unconditional: see TileStage (dl_tiles.h)
@@ -675,8 +681,8 @@ using namespace mine;
 // Tile pairs per workgroup: eight workgroups' worth of pairs per CU (one workgroup per CU fits the LDS; short runs keep the
 // tail of the grid short, consecutive pairs of a run share their u tile).  DL_MINE_TILES (test knob) forces the run length;
 // results do not depend on it.
-struct MinePlan { int nd, nt, pairs, per_wg, grid; size_t cbatch; };
-static MinePlan mine_plan(int N, int d) {
+struct MinePlan { int nd, nt, pairs, per_wg, grid; size_t cbatch; dl_dtype dt; };
+static MinePlan mine_plan(int N, int d, dl_dtype dt = DL_F32) {
     MinePlan p;
     p.nd = (d + SDC - 1) / SDC;
     p.nt = (N + TT - 1) / TT;
@@ -687,14 +693,15 @@ static MinePlan mine_plan(int N, int d) {
     const int want = config().mine_tiles > 0 ? config().mine_tiles : (int)((pairs + per_cu - 1) / per_cu);
     p.per_wg = max(1, min(want, max(1, p.pairs)));
     p.grid = (int)((pairs + p.per_wg - 1) / p.per_wg);
-    p.cbatch = plane_array_elems(N, d, SDC);
+    p.cbatch = table_plane_elems(dt, N, d);                    // the one thing of a plan that depends on the table type
+    p.dt = dt;
     return p;
 }
 
-// The planes of Z and H, and what every scan of the family reads
-static void split_tables(const float* Z, const float* H, int N, int K, int d, __bf16* cz, __bf16* ch, hipStream_t st) {
-    split_rows(Z, K, N, d, K * d, (size_t)d, cz, st);
-    split_rows(H, K, N, d, K * d, (size_t)d, ch, st);
+// The planes of Z and H (three per fp32 table, the one of a bf16 table), and what every scan of the family reads
+static void split_tables(const MinePlan& p, const void* Z, const void* H, int N, int K, int d, __bf16* cz, __bf16* ch, hipStream_t st) {
+    table_planes(Z, p.dt, nullptr, N, K, d, cz, st);
+    table_planes(H, p.dt, nullptr, N, K, d, ch, st);
 }
 static ScanArgs scan_args(const MinePlan& p, const __bf16* cz, const __bf16* ch, int N, int K, float t, const int32_t* exr,
                           const int32_t* exc, float min_logit, const dl_node_filter* nf) {
@@ -709,7 +716,10 @@ static ScanArgs scan_args(const MinePlan& p, const __bf16* cz, const __bf16* ch,
 }
 template <int MODE>
 static void launch_tiles(const MinePlan& p, const ScanArgs& a, const dl_node_filter* nf, hipStream_t st) {
-    launch_scan<scan_tiles<MODE>, scan_tiles<MODE, true>>(nf, (unsigned)p.grid, MTHR, MODE == COUNT ? LDS_BYTES_COUNT : LDS_BYTES, st, a);
+    if (p.dt == DL_BF16)
+        launch_scan<scan_tiles<MODE, false, 1>, scan_tiles<MODE, true, 1>>(nf, (unsigned)p.grid, MTHR, lds_bytes(MODE, 1), st, a);
+    else
+        launch_scan<scan_tiles<MODE>, scan_tiles<MODE, true>>(nf, (unsigned)p.grid, MTHR, lds_bytes(MODE, 3), st, a);
 }
 
 bool score_mine_supported(int K, int d) { return score_rank_supported(K, d); }
@@ -742,16 +752,16 @@ static MineWs mine_carve(const MinePlan& p, int K, int m, void* ws) {
     return w;
 }
 
-size_t score_mine_workspace_bytes(int N, int K, int d, int m) { return mine_carve(mine_plan(N, d), K, m, nullptr).bytes; }
+size_t score_mine_workspace_bytes(int N, int K, int d, int m, dl_dtype dt) { return mine_carve(mine_plan(N, d, dt), K, m, nullptr).bytes; }
 
-int score_mine(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
-               int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws, hipStream_t st,
+int score_mine(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
+               float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws, hipStream_t st,
                const dl_node_filter* nf) {
-    const MinePlan p = mine_plan(N, d);
+    const MinePlan p = mine_plan(N, d, dt);
     const MineWs w = mine_carve(p, K, m, ws);
     hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, m);
     if (p.pairs > 0) {
-        split_tables(Z, H, N, K, d, w.cz, w.ch, st);
+        split_tables(p, Z, H, N, K, d, w.cz, w.ch, st);
         ScanArgs a = scan_args(p, w.cz, w.ch, N, K, t, exr, exc, min_logit, nf);
         a.state = w.state;
         a.sel.m = m; a.sel.hist = w.hist; a.sel.keys = w.keys;
@@ -777,9 +787,9 @@ static int search_levels(int n) {                               // iterations of
     }
     return l;
 }
-static PairRankPlan pair_rank_plan(int N, int d, int T) {
+static PairRankPlan pair_rank_plan(int N, int d, int T, dl_dtype dt = DL_F32) {
     PairRankPlan p;
-    p.m = mine_plan(N, d);
+    p.m = mine_plan(N, d, dt);
     p.stride = max(1, (T + SEPS - 1) / SEPS);
     p.nsep = (T + p.stride - 1) / p.stride;
     p.lds_levels = search_levels(p.nsep);
@@ -814,12 +824,12 @@ static PairRankWs pair_rank_carve(const MinePlan& p, int K, void* ws) {
     return w;
 }
 
-size_t score_pair_ranks_workspace_bytes(int N, int K, int d) { return pair_rank_carve(mine_plan(N, d), K, nullptr).bytes; }
+size_t score_pair_ranks_workspace_bytes(int N, int K, int d, dl_dtype dt) { return pair_rank_carve(mine_plan(N, d, dt), K, nullptr).bytes; }
 
-int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
+int score_pair_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
                      const unsigned* tord, int T, u64* gcnt, u64* tcnt, u64* ncand, void* ws, hipStream_t st,
                      const dl_node_filter* nf) {
-    const PairRankPlan p = pair_rank_plan(N, d, T);
+    const PairRankPlan p = pair_rank_plan(N, d, T, dt);
     const PairRankWs w = pair_rank_carve(p.m, K, ws);
     hipError_t e = hipMemsetAsync(w.state, 0, sizeof(State), st);
     if (e == hipSuccess) e = hipMemsetAsync(gcnt, 0, sizeof(u64) * ((size_t)T + 1), st);
@@ -827,7 +837,7 @@ int score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float 
     if (e == hipSuccess) e = hipMemsetAsync(ncand, 0, sizeof(u64), st);
     DL_REQUIRE(e == hipSuccess, "hipMemsetAsync: %s", hipGetErrorString(e));
     if (p.m.pairs > 0) {
-        split_tables(Z, H, N, K, d, w.cz, w.ch, st);
+        split_tables(p.m, Z, H, N, K, d, w.cz, w.ch, st);
         ScanArgs a = scan_args(p.m, w.cz, w.ch, N, K, t, exr, exc, 0.0f, nf);
         a.state = w.state;
         a.cnt = CountArgs{tord, T, p.stride, p.nsep, gcnt, tcnt, ncand};
@@ -864,14 +874,14 @@ static LinksWs links_carve(const MinePlan& p, int N, int K, void* ws) {
     return w;
 }
 
-size_t score_links_workspace_bytes(int N, int K, int d) { return links_carve(mine_plan(N, d), N, K, nullptr).bytes; }
+size_t score_links_workspace_bytes(int N, int K, int d, dl_dtype dt) { return links_carve(mine_plan(N, d, dt), N, K, nullptr).bytes; }
 
-int score_links_count(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
+int score_links_count(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
                       float min_logit, const dl_node_filter* nf, void* ws, int64_t* rowptr, hipStream_t st) {
-    const MinePlan p = mine_plan(N, d);
+    const MinePlan p = mine_plan(N, d, dt);
     const LinksWs w = links_carve(p, N, K, ws);
     if (p.pairs > 0) {
-        split_tables(Z, H, N, K, d, w.cz, w.ch, st);
+        split_tables(p, Z, H, N, K, d, w.cz, w.ch, st);
         ScanArgs a = scan_args(p, w.cz, w.ch, N, K, t, exr, exc, min_logit, nf);
         a.link.cnt = w.cnt;
         launch_tiles<DEG>(p, a, nf, st);
@@ -881,9 +891,10 @@ int score_links_count(const float* Z, const float* H, int N, int K, int d, float
     return check_launch("score_links_count");
 }
 
-int score_links_fill(int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit, const dl_node_filter* nf,
-                     void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit, float* prob, hipStream_t st) {
-    const MinePlan p = mine_plan(N, d);
+int score_links_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
+                     const dl_node_filter* nf, void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit, float* prob,
+                     hipStream_t st) {
+    const MinePlan p = mine_plan(N, d, dt);
     const LinksWs w = links_carve(p, N, K, ws);
     if (p.pairs > 0 && nnz > 0) {
         ScanArgs a = scan_args(p, w.cz, w.ch, N, K, t, exr, exc, min_logit, nf);

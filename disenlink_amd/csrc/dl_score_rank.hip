@@ -22,6 +22,8 @@
 // Keys order the logits totally: larger first, +inf above every finite value, -inf below, NaN below everything; equal
 // values by candidate index, smaller first.  Everything selected or counted is a function of the logits alone, and the
 // logit of a pair does not depend on where in a tile its rows sit: results are independent of the slicing and of the run.
+// bf16 tables (the *_dtype entries with DL_BF16): the P = 1 instantiations, one plane per operand (copy_rows, which also
+// gathers the query rows) and one product per block; on the same values, the bits of the three-plane scan.
 #include "dl_common.h"
 #include "dl_kernels.h"
 #include "dl_scan.h"
@@ -55,21 +57,29 @@ struct ScanArgs {
     FilterArgs filt;                                                    // FILT: the node-group rule (dl_tiles.h)
 };
 
-// LDS beyond the two staging images (bytes): exclusion mask, per-row bookkeeping, per-wave compaction scratch
-constexpr size_t STAGE_BYTES = (size_t)2 * 2 * 3 * TT * SLD * 2;
-constexpr size_t LDS_BYTES = STAGE_BYTES + TT * 4 * 4 + 6 * TT * 4 + TT * 8 + 8 * MAX_CAP * 8;
-static_assert(LDS_BYTES % 16 == 0 && LDS_BYTES + FILTER_LDS_BYTES <= 160 * 1024, "LDS of a CU");
+// LDS with P planes per operand (bytes): the two double-buffered staging images, the logits' way through LDS, then the
+// exclusion mask, per-row bookkeeping, per-wave compaction scratch.  The epilogue passes each wave's logits through 4 KiB of
+// LDS: with three planes that is the staging image the step has finished reading (30 KiB, four waves each); a one-plane
+// image (10 KiB) is too small for that, so the one-plane instantiations keep 8 x 4 KiB of their own behind the images.
+constexpr size_t LG_WAVE = 16 * DL_WAVE;                       // floats per wave
+constexpr size_t lg_bytes(int P) { return P == 3 ? 0 : 8 * LG_WAVE * 4; }
+constexpr size_t lds_bytes(int P) {
+    return (size_t)2 * 2 * P * TT * SLD * 2 + lg_bytes(P) + TT * 4 * 4 + 6 * TT * 4 + TT * 8 + 8 * MAX_CAP * 8;
+}
+static_assert(lds_bytes(3) % 16 == 0 && lds_bytes(1) % 16 == 0 && lds_bytes(3) + FILTER_LDS_BYTES <= 160 * 1024, "LDS of a CU");
+static_assert(4 * LG_WAVE * 4 <= (size_t)3 * TT * SLD * 2, "four waves' logits fit a three-plane image");
 
 // A PlaneStage tile whose 128 rows are gathered: row r of the tile is row rows[min(base + r, n - 1)] of the plane array.
-__device__ __forceinline__ void gather_fetch(PlaneStage<RTHR, SDC>& st, const __bf16* __restrict__ planes, const int32_t* rows,
+template <int P>
+__device__ __forceinline__ void gather_fetch(PlaneStage<RTHR, SDC, P>& st, const __bf16* __restrict__ planes, const int32_t* rows,
                                              int base, int n, int dc, int nd, int tid) {
-    static_assert(PlaneStage<RTHR, SDC>::PER == 1, "one 16-byte piece per plane and thread");
+    static_assert(PlaneStage<RTHR, SDC, P>::PER == 1, "one 16-byte piece per plane and thread");
     const int r = tid / (SDC / 8), c = (tid % (SDC / 8)) * 8;
     const int row = rows[min(base + r, n - 1)];
-    const __bf16* src = planes + plane_tile<SDC>(row / PLANE_ROWS, dc, nd) + (row % PLANE_ROWS) * SDC + c;
+    const __bf16* src = planes + plane_tile<SDC, P>(row / PLANE_ROWS, dc, nd) + (row % PLANE_ROWS) * SDC + c;
 #pragma unroll
-    for (int p = 0; p < 3; ++p)
-        st.v[p] = *reinterpret_cast<const typename PlaneStage<RTHR, SDC>::u32x4*>(src + (size_t)p * PLANE_ROWS * SDC);
+    for (int p = 0; p < P; ++p)
+        st.v[p] = *reinterpret_cast<const typename PlaneStage<RTHR, SDC, P>::u32x4*>(src + (size_t)p * PLANE_ROWS * SDC);
 }
 
 // Rank one row's list against itself and write its best min(n, k) keys back in order (one wave; between barriers).
@@ -125,13 +135,16 @@ __device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, 
 // the tile's last pipeline step (the candidates' groups were staged one step earlier: a tile has K * 2 * nd >= 2 steps, and
 // every reader of the previous tile's mask and groups is behind a barrier by then); the row threads then OR the exclusion
 // into it where the unfiltered kernel starts from zero.  The epilogue is the unfiltered one.
-template <int MODE, bool FILT = false>
+// P: planes per operand, 3 (fp32 tables) or 1 (bf16 tables: one bf16x8 and one MFMA per operand and block, gram_block<1>); the
+// step keeps its 32 columns, so the k-blocks of a product are added in the same ascending order in both.
+template <int MODE, bool FILT = false, int P = 3>
 __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
     static_assert(!(FILT && MODE == DIAG), "the target pass has no mask");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
-    __bf16* vs = us + 2 * 3 * TT * SLD;
-    unsigned* exm = reinterpret_cast<unsigned*>(vs + 2 * 3 * TT * SLD);   // [TT][4]: excluded columns of the tile
+    __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][P][TT][SLD]
+    __bf16* vs = us + 2 * P * TT * SLD;
+    float* lgs = reinterpret_cast<float*>(vs + 2 * P * TT * SLD);         // P = 1: [8][LG_WAVE], see lg_bytes
+    unsigned* exm = reinterpret_cast<unsigned*>(lgs + lg_bytes(P) / 4);   // [TT][4]: excluded columns of the tile
     int* cnt = reinterpret_cast<int*>(exm + TT * 4);           // TOPK: keys in the row's list
     int* srt = cnt + TT;                                        // TOPK: of which sorted
     int* excur = srt + TT;                                      // next exclusion entry of the row
@@ -193,7 +206,7 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
         }
     }
 
-    PlaneStage<RTHR, SDC> uq, vq;
+    PlaneStage<RTHR, SDC, P> uq, vq;
     static_assert(TT == PLANE_ROWS, "tiles of the plane arrays");
     auto fetch = [&](int s) {
         const int j = s / per_tile, rem = s - j * per_tile;
@@ -205,13 +218,13 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
             gather_fetch(uq, qsrc, A.trow, qt * TT, A.T, dc, nd, tid);
             gather_fetch(vq, csrc, A.tdst, qt * TT, A.T, dc, nd, tid);
         } else {
-            uq.fetch(qsrc + plane_tile<SDC>(qt, dc, nd), tid);
-            vq.fetch(csrc + plane_tile<SDC>(ct0 + j, dc, nd), tid);
+            uq.fetch(qsrc + plane_tile<SDC, P>(qt, dc, nd), tid);
+            vq.fetch(csrc + plane_tile<SDC, P>(ct0 + j, dc, nd), tid);
         }
     };
     auto stash = [&](int s) {
-        uq.stash(us + (s & 1) * 3 * TT * SLD, tid);
-        vq.stash(vs + (s & 1) * 3 * TT * SLD, tid);
+        uq.stash(us + (s & 1) * P * TT * SLD, tid);
+        vq.stash(vs + (s & 1) * P * TT * SLD, tid);
     };
 
     f32x16 acc[2], term[2];
@@ -235,11 +248,11 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
             const int v = (ct0 + s / per_tile) * TT + tid;
             if (rem == per_tile - 2 && tid < TT && v < A.N) gb = A.filt.group[v];
         }
-        const __bf16* ub = us + (s & 1) * 3 * TT * SLD + (wu * 32 + li) * SLD + half * 8;
-        const __bf16* vb = vs + (s & 1) * 3 * TT * SLD + (wv * 64 + li) * SLD + half * 8;
+        const __bf16* ub = us + (s & 1) * P * TT * SLD + (wu * 32 + li) * SLD + half * 8;
+        const __bf16* vb = vs + (s & 1) * P * TT * SLD + (wv * 64 + li) * SLD + half * 8;
 #pragma unroll
         for (int kb = 0; kb < SDC / 16; ++kb) {
-            gram_block_split6(acc, ub, vb, kb);                 // the dense scorer's products (dl_tiles.h)
+            gram_block<P>(acc, ub, vb, kb);                     // the dense scorer's products (dl_tiles.h)
             if (kb == 0) {
                 if (s + 1 < steps) stash(s + 1);
                 fetch(min(s + 2, steps - 1));                   // unconditional: see TileStage (dl_tiles.h)
@@ -303,7 +316,8 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
             // The logits go through LDS, one lane's own 16 values per round (no exchange between lanes), so that the
             // candidate loop below need not be unrolled over the registers: into the staging image this step has finished
             // reading (the next write to it is the stash in step s + 1, behind the barriers at the end of this epilogue).
-            float* lg = reinterpret_cast<float*>((wave < 4 ? us : vs) + (s & 1) * 3 * TT * SLD) + (wave & 3) * 16 * DL_WAVE;
+            float* lg = P == 3 ? reinterpret_cast<float*>((wave < 4 ? us : vs) + (s & 1) * 3 * TT * SLD) + (wave & 3) * 16 * DL_WAVE
+                               : lgs + wave * LG_WAVE;          // one plane: the wave's own 4 KiB behind the images
 #pragma unroll
             for (int bb = 0; bb < 2; ++bb) {
                 const int vl = wv * 64 + bb * 32 + li, v = v0 + vl;
@@ -507,8 +521,8 @@ bool score_rank_supported(int K, int d) { return K >= 1 && K <= DL_MAX_FACTORS &
 
 // Slicing of the candidate tiles: as many slices as keep one work item per CU busy (one workgroup per CU fits the LDS),
 // at most MAX_SLICES, never an empty slice.  DL_RANK_SLICES (test knob) forces the count; results do not depend on it.
-struct RankPlan { int nd, qtiles, nt, slices, tps, cap; size_t qbatch, cbatch; };
-static RankPlan rank_plan(int N, int d, int Q, int k) {
+struct RankPlan { int nd, qtiles, nt, slices, tps, cap; size_t qbatch, cbatch; dl_dtype dt; };
+static RankPlan rank_plan(int N, int d, int Q, int k, dl_dtype dt = DL_F32) {
     RankPlan p;
     p.nd = (d + SDC - 1) / SDC;
     p.qtiles = (Q + TT - 1) / TT;
@@ -518,8 +532,9 @@ static RankPlan rank_plan(int N, int d, int Q, int k) {
     p.tps = (p.nt + s - 1) / s;
     p.slices = (p.nt + p.tps - 1) / p.tps;
     p.cap = k + ROUND;
-    p.qbatch = plane_array_elems(Q, d, SDC);
-    p.cbatch = plane_array_elems(N, d, SDC);
+    p.qbatch = table_plane_elems(dt, Q, d);                    // only the plane arrays depend on the table type
+    p.cbatch = table_plane_elems(dt, N, d);
+    p.dt = dt;
     return p;
 }
 
@@ -534,8 +549,8 @@ void score_topk_form(int N, int d, int Q, int k, int* out) {
     out[5] = p.cap;
 }
 
-// Workspace (256-byte aligned blocks): gathered query rows (fp32) | their planes | planes of Z and H | TOPK: lists, counts |
-// RANKS: per-target arrays and the two counter arrays.
+// Workspace (256-byte aligned blocks): gathered query rows (fp32 tables only: bf16 rows are gathered by the copy into their
+// plane) | their planes | planes of Z and H | TOPK: lists, counts | RANKS: per-target arrays and the two counter arrays.
 struct RankWs {
     float *zq, *hq, *tlogit;
     __bf16 *qz, *qh, *cz, *ch;
@@ -548,8 +563,10 @@ struct RankWs {
 static RankWs rank_carve(const RankPlan& p, int Q, int K, int d, int k, int T, void* ws) {
     RankWs w = {};
     Carver c(ws);
-    w.zq = c.take<float>((size_t)Q * K * d);
-    w.hq = c.take<float>((size_t)Q * K * d);
+    if (p.dt == DL_F32) {
+        w.zq = c.take<float>((size_t)Q * K * d);
+        w.hq = c.take<float>((size_t)Q * K * d);
+    }
     w.qz = c.take<__bf16>((size_t)K * p.qbatch);
     w.qh = c.take<__bf16>((size_t)K * p.qbatch);
     w.cz = c.take<__bf16>((size_t)K * p.cbatch);
@@ -571,19 +588,25 @@ static RankWs rank_carve(const RankPlan& p, int Q, int K, int d, int k, int T, v
     return w;
 }
 
-size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T) {
-    return rank_carve(rank_plan(N, d, Q, k), Q, K, d, k, T, nullptr).bytes;
+size_t score_rank_workspace_bytes(int N, int K, int d, int Q, int k, int T, dl_dtype dt) {
+    return rank_carve(rank_plan(N, d, Q, k, dt), Q, K, d, k, T, nullptr).bytes;
 }
 
 // the query rows gathered and split, the candidate tables split: the scan's operands
-static ScanArgs scan_operands(const RankPlan& p, const RankWs& w, const float* Z, const float* H, int N, int K, int d, float t,
+static ScanArgs scan_operands(const RankPlan& p, const RankWs& w, const void* Z, const void* H, int N, int K, int d, float t,
                               const int32_t* queries, int Q, const int32_t* exr, const int32_t* exc, hipStream_t st) {
-    const size_t n = (size_t)Q * K * d;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Z, H, queries, Q, K * d, w.zq, w.hq);
-    split_rows(w.zq, K, Q, d, K * d, (size_t)d, w.qz, st);
-    split_rows(w.hq, K, Q, d, K * d, (size_t)d, w.qh, st);
-    split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
-    split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
+    if (p.dt == DL_BF16) {                                      // the gather is part of the copy into the plane
+        table_planes(Z, p.dt, queries, Q, K, d, w.qz, st);
+        table_planes(H, p.dt, queries, Q, K, d, w.qh, st);
+    } else {
+        const size_t n = (size_t)Q * K * d;
+        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)Z, (const float*)H,
+                           queries, Q, K * d, w.zq, w.hq);
+        split_rows(w.zq, K, Q, d, K * d, (size_t)d, w.qz, st);
+        split_rows(w.hq, K, Q, d, K * d, (size_t)d, w.qh, st);
+    }
+    table_planes(Z, p.dt, nullptr, N, K, d, w.cz, st);
+    table_planes(H, p.dt, nullptr, N, K, d, w.ch, st);
     ScanArgs a = {};
     a.qz = w.qz; a.qh = w.qh; a.qbatch = p.qbatch;
     a.cz = w.cz; a.ch = w.ch; a.cbatch = p.cbatch;
@@ -594,26 +617,39 @@ static ScanArgs scan_operands(const RankPlan& p, const RankWs& w, const float* Z
     return a;
 }
 
-int score_topk(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, int k,
+// the scan in its three-plane or one-plane instantiation (FILT where there is a rule and the mode has one)
+template <int MODE>
+static void launch_rank(dl_dtype dt, const dl_node_filter* nf, unsigned grid, hipStream_t st, const ScanArgs& a) {
+    if constexpr (MODE == DIAG) {
+        if (dt == DL_BF16) launch_lds<rank_scan_kernel<DIAG, false, 1>>(grid, RTHR, lds_bytes(1), st, a);
+        else launch_lds<rank_scan_kernel<DIAG>>(grid, RTHR, lds_bytes(3), st, a);
+    } else {
+        if (dt == DL_BF16)
+            launch_scan<rank_scan_kernel<MODE, false, 1>, rank_scan_kernel<MODE, true, 1>>(nf, grid, RTHR, lds_bytes(1), st, a);
+        else
+            launch_scan<rank_scan_kernel<MODE>, rank_scan_kernel<MODE, true>>(nf, grid, RTHR, lds_bytes(3), st, a);
+    }
+}
+
+int score_topk(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* queries, int Q, int k,
                const int32_t* exr, const int32_t* exc, int exclude_self, int64_t* index, float* logit, float* prob, void* ws,
                hipStream_t st, const dl_node_filter* nf) {
-    const RankPlan p = rank_plan(N, d, Q, k);
+    const RankPlan p = rank_plan(N, d, Q, k, dt);
     const RankWs w = rank_carve(p, Q, K, d, k, 0, ws);
     ScanArgs a = scan_operands(p, w, Z, H, N, K, d, t, queries, Q, exr, exc, st);
     a.exclude_self = exclude_self ? 1 : 0;
     a.k = k; a.cap = p.cap; a.lists = w.lists; a.counts = w.counts;
     a.filt = filter_args(nf);
-    launch_scan<rank_scan_kernel<TOPK>, rank_scan_kernel<TOPK, true>>(nf, (unsigned)xcd_grid(p.qtiles, p.slices), RTHR, LDS_BYTES,
-                                                                      st, a);
+    launch_rank<TOPK>(dt, nf, (unsigned)xcd_grid(p.qtiles, p.slices), st, a);
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)Q), dim3(256), 0, st, w.lists, w.counts, p.slices, p.cap, k, index,
                        logit, prob);
     return check_launch("score_topk");
 }
 
-int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* queries, int Q, const int32_t* tptr,
-                const int32_t* tdst, int T, const int32_t* exr, const int32_t* exc, int64_t* greater, int64_t* ties, void* ws,
-                hipStream_t st, const dl_node_filter* nf) {
-    const RankPlan p = rank_plan(N, d, Q, 0);
+int score_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* queries, int Q,
+                const int32_t* tptr, const int32_t* tdst, int T, const int32_t* exr, const int32_t* exc, int64_t* greater, int64_t* ties,
+                void* ws, hipStream_t st, const dl_node_filter* nf) {
+    const RankPlan p = rank_plan(N, d, Q, 0, dt);
     const RankWs w = rank_carve(p, Q, K, d, 0, T, ws);
     ScanArgs a = scan_operands(p, w, Z, H, N, K, d, t, queries, Q, exr, exc, st);
     hipLaunchKernelGGL(target_rows_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, tptr, Q, w.trow);
@@ -621,7 +657,7 @@ int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, co
     // itself, the diagonal kept
     ScanArgs g = a;
     g.trow = w.trow; g.tdst = tdst; g.T = T; g.tlogit = w.tlogit;
-    launch_lds<rank_scan_kernel<DIAG>>((unsigned)xcd_grid((T + TT - 1) / TT, 1), RTHR, LDS_BYTES, st, g);
+    launch_rank<DIAG>(dt, nullptr, (unsigned)xcd_grid((T + TT - 1) / TT, 1), st, g);
     const unsigned tb = (unsigned)((T + 255) / 256);
     hipLaunchKernelGGL(target_sort_kernel, dim3(tb), dim3(256), 0, st, tptr, w.trow, w.tlogit, T, w.tord, w.spos, w.sfirst);
     hipError_t e = hipMemsetAsync(w.gcnt, 0, sizeof(u64) * ((size_t)T + Q), st);
@@ -630,8 +666,7 @@ int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, co
     a.exclude_self = 1;
     a.tptr = tptr; a.tord = w.tord; a.gcnt = w.gcnt; a.tcnt = w.tcnt;
     a.filt = filter_args(nf);
-    launch_scan<rank_scan_kernel<RANKS>, rank_scan_kernel<RANKS, true>>(nf, (unsigned)xcd_grid(p.qtiles, p.slices), RTHR, LDS_BYTES,
-                                                                        st, a);
+    launch_rank<RANKS>(dt, nf, (unsigned)xcd_grid(p.qtiles, p.slices), st, a);
     hipLaunchKernelGGL(target_finish_kernel, dim3(tb), dim3(256), 0, st, tptr, w.trow, tdst, queries, w.spos, w.sfirst, w.gcnt,
                        w.tcnt, exr, exc, T, greater, ties);
     if (nf != nullptr)
@@ -642,9 +677,9 @@ int score_ranks(const float* Z, const float* H, int N, int K, int d, float t, co
 // ---- dl_score_pair_logits: the DIAG pass on its own, with the plane arrays of Z and H as BOTH sides: pair i = (row a[i] as
 // the A operand, row b[i]), tile i of the pairs against itself, the diagonal kept.  Workspace: planes of Z and H.
 struct PairWs { __bf16 *cz, *ch; size_t cbatch, bytes; };
-static PairWs pair_carve(int N, int K, int d, void* ws) {
+static PairWs pair_carve(int N, int K, int d, dl_dtype dt, void* ws) {
     PairWs w = {};
-    w.cbatch = plane_array_elems(N, d, SDC);
+    w.cbatch = table_plane_elems(dt, N, d);
     Carver c(ws);
     w.cz = c.take<__bf16>((size_t)K * w.cbatch);
     w.ch = c.take<__bf16>((size_t)K * w.cbatch);
@@ -652,19 +687,19 @@ static PairWs pair_carve(int N, int K, int d, void* ws) {
     return w;
 }
 
-size_t score_pair_logits_workspace_bytes(int N, int K, int d) { return pair_carve(N, K, d, nullptr).bytes; }
+size_t score_pair_logits_workspace_bytes(int N, int K, int d, dl_dtype dt) { return pair_carve(N, K, d, dt, nullptr).bytes; }
 
-int score_pair_logits(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* a, const int32_t* b, int T,
-                      float* logit, void* ws, hipStream_t st) {
-    const PairWs w = pair_carve(N, K, d, ws);
-    split_rows(Z, K, N, d, K * d, (size_t)d, w.cz, st);
-    split_rows(H, K, N, d, K * d, (size_t)d, w.ch, st);
+int score_pair_logits(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
+                      int T, float* logit, void* ws, hipStream_t st) {
+    const PairWs w = pair_carve(N, K, d, dt, ws);
+    table_planes(Z, dt, nullptr, N, K, d, w.cz, st);
+    table_planes(H, dt, nullptr, N, K, d, w.ch, st);
     ScanArgs g = {};
     g.qz = w.cz; g.qh = w.ch; g.qbatch = w.cbatch;
     g.cz = w.cz; g.ch = w.ch; g.cbatch = w.cbatch;
     g.N = N; g.K = K; g.nd = (d + SDC - 1) / SDC; g.t = t;
     g.trow = a; g.tdst = b; g.T = T; g.tlogit = logit;
-    launch_lds<rank_scan_kernel<DIAG>>((unsigned)xcd_grid((T + TT - 1) / TT, 1), RTHR, LDS_BYTES, st, g);
+    launch_rank<DIAG>(dt, nullptr, (unsigned)xcd_grid((T + TT - 1) / TT, 1), st, g);
     return check_launch("score_pair_logits");
 }
 

@@ -178,6 +178,24 @@ __device__ __forceinline__ void gram_block_split6(f32x16 (&acc)[2], const __bf16
     mfma_split6(acc[1], a, b1);
 }
 
+// The same block from images of P planes, [P][128][SPLIT_PITCH].  P = 3: gram_block_split6.  P = 1: the operands ARE bf16 (the
+// value is its own hi plane, mid = lo = 0), so the one hi*hi product is the whole block: one bf16x8 per operand, one MFMA per
+// accumulator.  The five products it leaves out would add exact zeros to an accumulator that starts at +0 (x + 0 = x, and +0
+// + +-0 = +0), so on bf16-exact finite tables both forms leave the same bits; k-blocks are added in ascending k in both.
+template <int P>
+__device__ __forceinline__ void gram_block(f32x16 (&acc)[2], const __bf16* ub, const __bf16* vb, int kb) {
+    static_assert(P == 1 || P == 3, "one plane (bf16 tables) or three (fp32 tables)");
+    if constexpr (P == 3) {
+        gram_block_split6(acc, ub, vb, kb);
+    } else {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(ub + kb * 16);
+        const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(vb + kb * 16);
+        const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(vb + 32 * SPLIT_PITCH + kb * 16);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b1, acc[1], 0, 0, 0);
+    }
+}
+
 // Write a fetched [ROWS][32] tile (TileStage<ROWS, 32, true, THREADS>) to LDS as three bf16 planes; what lies outside
 // the matrix is written as zero.
 template <int ROWS, int THREADS>
@@ -206,30 +224,33 @@ __device__ __forceinline__ void stash_planes(const TileStage<ROWS, SPLIT_COLS, t
 // [3 planes][128][COLS] bf16 — the order the kernels consume it in, so a tile is a straight, fully coalesced copy
 // global -> registers -> LDS image [3][128][COLS + 8] without masks (rows and columns are zero-filled out to
 // multiples of 128 rows and of the array's column padding).  Tile (rb, cb) of a matrix with ncb column chunks starts at plane_tile<COLS>(rb, cb, ncb).
+// P, the plane count, is 3 throughout for fp32 sources; a bf16 source is its own single plane (P = 1, copy_rows of
+// dl_planes.hip): the same tiles, [1][128][COLS] each.
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 constexpr int PLANE_ROWS = 128;
-template <int COLS>
-__host__ __device__ inline size_t plane_tile(int rb, int cb, int ncb) { return ((size_t)rb * ncb + cb) * 3 * PLANE_ROWS * COLS; }
+template <int COLS, int P = 3>
+__host__ __device__ inline size_t plane_tile(int rb, int cb, int ncb) { return ((size_t)rb * ncb + cb) * P * PLANE_ROWS * COLS; }
 // elements of the plane array of a [rows][cols] matrix whose columns are padded to a multiple of col_pad
-inline size_t plane_array_elems(size_t rows, size_t cols, int col_pad) { return 3 * round_up(rows, PLANE_ROWS) * round_up(cols, col_pad); }
+template <int P = 3>
+inline size_t plane_array_elems(size_t rows, size_t cols, int col_pad) { return P * round_up(rows, PLANE_ROWS) * round_up(cols, col_pad); }
 template <int COLS>
 inline int plane_chunks(size_t cols, int col_pad) { return (int)(round_up(cols, col_pad) / COLS); }
 
-template <int THREADS, int COLS>
+template <int THREADS, int COLS, int P = 3>
 struct PlaneStage {
     static constexpr int PIECES = PLANE_ROWS * COLS / 8;       // 16-byte pieces per plane of the tile
     static constexpr int PITCH = COLS + 8;                     // LDS row pitch (bf16): conflict-free b128 reads
     static_assert(PIECES % THREADS == 0, "a plane of the tile divides over the workgroup");
     static constexpr int PER = PIECES / THREADS;
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));    // (HIP's uint4 class kept the array in scratch)
-    u32x4 v[3 * PER];
+    u32x4 v[P * PER];
     __device__ __forceinline__ void fetch(const __bf16* __restrict__ tile, int tid) {
 #pragma unroll
-        for (int j = 0; j < 3 * PER; ++j) v[j] = *reinterpret_cast<const u32x4*>(tile + (unsigned)((tid + THREADS * j) * 8));
+        for (int j = 0; j < P * PER; ++j) v[j] = *reinterpret_cast<const u32x4*>(tile + (unsigned)((tid + THREADS * j) * 8));
     }
     __device__ __forceinline__ void stash(__bf16* lds, int tid) const {
 #pragma unroll
-        for (int j = 0; j < 3 * PER; ++j) {
+        for (int j = 0; j < P * PER; ++j) {
             const int q = tid + THREADS * j, p = q / PIECES, r = (q % PIECES) / (COLS / 8), c = (q % (COLS / 8)) * 8;
             *reinterpret_cast<u32x4*>(lds + (p * PLANE_ROWS + r) * PITCH + c) = v[j];
         }
@@ -241,6 +262,9 @@ struct PlaneStage {
 // the padded extents is written.
 void split_rows(const float* src, int B, int R, int C, int ld, size_t sb, __bf16* dst, hipStream_t st);      // 32-column tiles, columns padded to 32
 void split_transposed(const float* src, int R, int C, int ld, __bf16* dst, hipStream_t st);
+// the ONE plane of B bf16 matrices src [B][R][C], copied into the same tile-major layout with P = 1 (no arithmetic on the
+// values); rows != NULL: row r of every matrix is source row rows[r] (the query gather of the ranking scans)
+void copy_rows(const __bf16* src, const int32_t* rows, int B, int R, int C, int ld, size_t sb, __bf16* dst, hipStream_t st);
 // W2 [rows][nhid] -> planes [3][rows][nhid_p] in the k-slot order of the forward's layer 2 (dl_planes.hip)
 void split_w2(const float* W2, int rows, int nhid, __bf16* dst, int nhid_p, hipStream_t st);                 // 16-column tiles, columns (= R) padded to 128
 // x [N][F], W1 [K][nhid][F] and W2 [K*d][nhid] in one launch (the two-layer forward's operands)

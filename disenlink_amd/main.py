@@ -55,6 +55,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "(libdisenlink_torch.so) is absent, eager when it is present — with it and the end-of-epoch "
                         "bookkeeping on the device the eager loop is gapless and 3-10 %% faster than the replay")
     p.add_argument("--quiet", action="store_true")
+    p.add_argument("--scan-dtype", choices=["f32", "bf16"], default="f32",
+                   help="tables of the all-pairs scans (--rank-eval, --global-rank-eval, --mine, --predict-links): f32, or "
+                        "bf16 = Z rounded to bf16 and H aggregated from it, as the bf16 training step forms them; one "
+                        "matrix-core product per block instead of six and a third of the plane workspace")
     p.add_argument("--rank-eval", action="store_true",
                    help="after each run, rank every test positive among all nodes (filtered by every dataset edge) and "
                         "print MRR and Hits@{1,10,50,100}")
@@ -229,18 +233,23 @@ def load_node_groups(path: str, n_nodes: int, rule: str, device):
     return make(torch.from_numpy(g.astype(np.int64)), device=device)
 
 
-def rank_eval(model, x, graph, split, known, node_filter=None) -> dict:
+def scan_table_dtype(args):
+    """--scan-dtype as the ``table_dtype`` keyword of the Disentangle scan methods (None = fp32 tables)."""
+    return torch.bfloat16 if args.scan_dtype == "bf16" else None
+
+
+def rank_eval(model, x, graph, split, known, node_filter=None, table_dtype=None) -> dict:
     """MRR and Hits@{1,10,50,100} of the test positives, each ranked among all nodes with every known edge filtered out
     (Disentangle.link_ranks: the model with its best weights, as run_link_prediction leaves it)."""
     from .metrics import ranking_metrics
     pos = split.test.label > 0.5
     src = torch.from_numpy(np.ascontiguousarray(split.test.u[pos])).to(x.device)
     dst = torch.from_numpy(np.ascontiguousarray(split.test.v[pos])).to(x.device)
-    greater, ties = model.link_ranks(x, graph, src, dst, exclude=known, node_filter=node_filter)
+    greater, ties = model.link_ranks(x, graph, src, dst, exclude=known, node_filter=node_filter, table_dtype=table_dtype)
     return ranking_metrics(greater, ties)
 
 
-def global_rank_eval(model, x, graph, split, known, node_filter=None) -> dict:
+def global_rank_eval(model, x, graph, split, known, node_filter=None, table_dtype=None) -> dict:
     """AUC against every non-edge, mean rank, MRR and recall@M of the test positives, each ranked among all unordered
     pairs of the graph with every known edge filtered out (Disentangle.missing_link_ranks, the model's best weights);
     self loops among the positives are left out."""
@@ -249,14 +258,14 @@ def global_rank_eval(model, x, graph, split, known, node_filter=None) -> dict:
     src = torch.from_numpy(np.ascontiguousarray(split.test.u[pos])).to(x.device)
     dst = torch.from_numpy(np.ascontiguousarray(split.test.v[pos])).to(x.device)
     keep = src != dst                                               # a self loop of the dataset is no pair of the graph
-    r = model.missing_link_ranks(x, graph, src[keep], dst[keep], exclude=known, node_filter=node_filter)
+    r = model.missing_link_ranks(x, graph, src[keep], dst[keep], exclude=known, node_filter=node_filter, table_dtype=table_dtype)
     return global_ranking_metrics(r.greater, r.ties, r.n_others)
 
 
-def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=print, node_filter=None):
+def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=print, node_filter=None, table_dtype=None):
     """--mine: the m most likely links outside ``known`` (Disentangle.top_missing_links), the first ``show`` printed and,
     with ``out``, all of them written as `src dst logit prob` lines."""
-    mined = model.top_missing_links(x, graph, m, exclude=known, node_filter=node_filter)
+    mined = model.top_missing_links(x, graph, m, exclude=known, node_filter=node_filter, table_dtype=table_dtype)
     src, dst, logit, prob = (v.cpu().numpy() for v in mined)
     log(f"mined {src.size} links (of {m} asked for); first {min(show, src.size)}: src dst logit prob")
     for i in range(min(show, src.size)):
@@ -268,10 +277,10 @@ def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=pri
     return mined
 
 
-def predict_links(model, x, graph, known, min_prob: float, out=None, log=print, node_filter=None):
+def predict_links(model, x, graph, known, min_prob: float, out=None, log=print, node_filter=None, table_dtype=None):
     """--predict-links: every link outside ``known`` whose link_pred reaches ``min_prob`` (Disentangle.predicted_links), a
     summary line printed and, with ``out``, all of them written as `src dst prob` lines, src < dst."""
-    links = model.predicted_links(x, graph, min_prob, exclude=known, node_filter=node_filter)
+    links = model.predicted_links(x, graph, min_prob, exclude=known, node_filter=node_filter, table_dtype=table_dtype)
     n = links.n_nodes
     src, dst, _, prob = (v.cpu().numpy() for v in links.pairs())
     deg = links.degree.cpu().numpy()
@@ -360,6 +369,7 @@ def main(argv=None):
     else:
         x = torch.from_numpy(ds.x).to(device)
     tdt = torch.bfloat16 if args.table_dtype == "bf16" else torch.float32
+    sdt = scan_table_dtype(args)
     result = []
     ranking = []
     global_ranking = []
@@ -381,17 +391,18 @@ def main(argv=None):
             print("test auc:", res.test_auc)
         result.append(res.test_auc)
         if args.rank_eval:
-            ranking.append(rank_eval(model, x, prepared.graph, split, known, node_filter))
+            ranking.append(rank_eval(model, x, prepared.graph, split, known, node_filter, table_dtype=sdt))
             if not args.quiet:
                 print("test ranking:", _fmt_ranking(ranking[-1]))
         if args.global_rank_eval:
-            global_ranking.append(global_rank_eval(model, x, prepared.graph, split, known, node_filter))
+            global_ranking.append(global_rank_eval(model, x, prepared.graph, split, known, node_filter, table_dtype=sdt))
             if not args.quiet:
                 print("test global ranking:", _fmt_ranking(global_ranking[-1]))
     if args.mine and args.run > 0:                                  # the last run's model, its best weights
-        mine_links(model, x, prepared.graph, known, args.mine, args.mine_out, node_filter=node_filter)
+        mine_links(model, x, prepared.graph, known, args.mine, args.mine_out, node_filter=node_filter, table_dtype=sdt)
     if args.predict_links is not None and args.run > 0:
-        predict_links(model, x, prepared.graph, known, args.predict_links, args.links_out, node_filter=node_filter)
+        predict_links(model, x, prepared.graph, known, args.predict_links, args.links_out, node_filter=node_filter,
+                      table_dtype=sdt)
     result = np.array(result)
     tail = []                                                       # the run means of the ranking metrics join the final line
     if args.rank_eval:

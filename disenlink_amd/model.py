@@ -402,30 +402,47 @@ class Disentangle(nn.Module):
         return H.view(H.shape[0], -1), prob
 
     # ------------------------------------------------------------------ ranking (inference only)
-    def _rank_tables(self, x, adj):
-        """Z and H of forward(x, adj) — the same projection and routing / aggregation, under no_grad."""
+    def _rank_tables(self, x, adj, table_dtype=None):
+        """Z and H of forward(x, adj) — the same projection and routing / aggregation, under no_grad.  ``table_dtype``:
+        None = fp32 tables; torch.bfloat16 = the tables the training step of a bf16 module gathers from (the sequence of
+        ops.HotPathPairs.forward): Z rounded to bf16, H routed and aggregated from THAT Z and stored as bf16."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
         with torch.no_grad():
             Z = self.project(x)
-            H = ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
-        return Z, H
+            if table_dtype is None or table_dtype is torch.float32:
+                return Z, ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
+            if table_dtype is not torch.bfloat16:
+                raise TypeError(f"table_dtype must be None, torch.float32 or torch.bfloat16, got {table_dtype!r}")
+            Zt = ops._f32c(Z).to(torch.bfloat16)
+            p, a, s = ops.route_fwd(graph, Zt, float(self.temperature))
+            return Zt, ops.aggregate_fwd(graph, Zt, float(self.beta), p, a, s)
 
-    def topk_links(self, x, adj, queries, k: int, exclude=None, exclude_self: bool = True, node_filter=None) -> TopLinks:
+    @staticmethod
+    def _scan_dtype(table_dtype):
+        """The ``table_dtype`` keyword of the ops scans for this one (None = fp32)."""
+        return torch.float32 if table_dtype is None else table_dtype
+
+    def topk_links(self, x, adj, queries, k: int, exclude=None, exclude_self: bool = True, node_filter=None,
+                   table_dtype=None) -> TopLinks:
         """The k most likely links of every node in ``queries``: TopLinks(index int64 [Q,k], logit, prob f32 [Q,k]),
         ranked by the pre-sigmoid logit of link_pred (prob = link_pred's value).  ``adj`` as in forward; ``exclude``: a
         Graph, a dense [N,N] mask or (rows, cols) of pairs that are not candidates; ``node_filter``: an ops.NodeFilter, a
-        rule on node groups that candidates must pass as well (ops.score_topk)."""
-        Z, H = self._rank_tables(x, adj)
-        return TopLinks(*ops.score_topk(Z, H, float(self.temperature), queries, k, exclude, exclude_self, node_filter))
+        rule on node groups that candidates must pass as well (ops.score_topk).  ``table_dtype`` (here and in the four
+        methods below): None = fp32 tables; torch.bfloat16 = the scan runs on the bf16 tables the training step gathers
+        from (a module trained with ``table_dtype=torch.bfloat16`` passes ``model.table_dtype`` to rank the model it
+        trained; on an fp32-trained module it is an approximation: operands rounded to bf16, exact arithmetic on them)."""
+        Z, H = self._rank_tables(x, adj, table_dtype)
+        return TopLinks(*ops.score_topk(Z, H, float(self.temperature), queries, k, exclude, exclude_self, node_filter,
+                                        self._scan_dtype(table_dtype)))
 
-    def link_ranks(self, x, adj, src, dst, exclude=None, node_filter=None):
+    def link_ranks(self, x, adj, src, dst, exclude=None, node_filter=None, table_dtype=None):
         """(greater, ties) int64 per target pair (src[i], dst[i]) among all nodes except src[i] and its exclusion set
         and, with ``node_filter`` (an ops.NodeFilter), the nodes its group may not take
         (ops.score_ranks; metrics.ranking_metrics turns them into MRR / Hits@K)."""
-        Z, H = self._rank_tables(x, adj)
-        return ops.score_ranks(Z, H, float(self.temperature), src, dst, exclude, node_filter)
+        Z, H = self._rank_tables(x, adj, table_dtype)
+        return ops.score_ranks(Z, H, float(self.temperature), src, dst, exclude, node_filter, self._scan_dtype(table_dtype))
 
-    def top_missing_links(self, x, adj, m: int, exclude=None, min_prob=None, node_filter=None) -> MinedLinks:
+    def top_missing_links(self, x, adj, m: int, exclude=None, min_prob=None, node_filter=None, table_dtype=None) -> MinedLinks:
         """The m most likely links of the WHOLE graph that are not known yet: MinedLinks(src, dst int32 [c], logit, prob
         f32 [c]) with src < dst, c = min(m, eligible pairs), ranked by the pre-sigmoid logit of link_pred over all
         unordered pairs (ops.score_mine; nothing of size N x N is formed).  ``exclude``: the known pairs, as a Graph, a
@@ -433,7 +450,7 @@ class Disentangle(nn.Module):
         only pairs with link_pred >= min_prob (turned into a logit floor on the host: 0.5 -> 0.0).  ``node_filter``: a
         symmetric ops.NodeFilter, a rule on node groups that pairs must pass as well."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
-        Z, H = self._rank_tables(x, graph)
+        Z, H = self._rank_tables(x, graph, table_dtype)
         floor = float("-inf")
         if min_prob is not None:
             p = float(min_prob)
@@ -442,27 +459,27 @@ class Disentangle(nn.Module):
             floor = float("-inf") if p == 0.0 else float("inf") if p == 1.0 else math.log(p) - math.log1p(-p)
         with torch.no_grad():
             return MinedLinks(*ops.score_mine(Z, H, float(self.temperature), m, graph if exclude is None else exclude, floor,
-                                              node_filter))
+                                              node_filter, self._scan_dtype(table_dtype)))
 
-    def predicted_links(self, x, adj, min_prob, exclude=None, node_filter=None) -> PredictedLinks:
+    def predicted_links(self, x, adj, min_prob, exclude=None, node_filter=None, table_dtype=None) -> PredictedLinks:
         """The predicted graph: EVERY unordered pair whose link_pred reaches ``min_prob`` and that is not known yet, as
         PredictedLinks(rowptr, col, logit, prob), a symmetric CSR over all nodes with ``.degree``, ``.pairs()`` and
         ``.to_graph()`` (ops.score_links: two scans, nothing of size N x N is formed, no cap on the number of links).
         ``exclude``: the known pairs, as a Graph, a dense [N,N] mask or (rows, cols), in either orientation; None = the
         edges of ``adj`` itself.  ``min_prob`` in [0, 1] is turned into a logit floor on the host, as in
         ``top_missing_links`` (0.5 -> 0.0).  ``node_filter``: a symmetric ops.NodeFilter that pairs must pass as well.
-        N <= 46,340, fp32 tables."""
+        N <= 46,340."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
-        Z, H = self._rank_tables(x, graph)
+        Z, H = self._rank_tables(x, graph, table_dtype)
         p = float(min_prob)
         if not 0.0 <= p <= 1.0:
             raise ValueError(f"min_prob={p} outside [0, 1]")
         floor = float("-inf") if p == 0.0 else float("inf") if p == 1.0 else math.log(p) - math.log1p(-p)
         with torch.no_grad():
             return PredictedLinks(*ops.score_links(Z, H, float(self.temperature), floor, graph if exclude is None else exclude,
-                                                   node_filter))
+                                                   node_filter, self._scan_dtype(table_dtype)))
 
-    def missing_link_ranks(self, x, adj, src, dst, exclude=None, node_filter=None) -> PairRanks:
+    def missing_link_ranks(self, x, adj, src, dst, exclude=None, node_filter=None, table_dtype=None) -> PairRanks:
         """Where the unordered pairs {src[i], dst[i]} stand among ALL unordered pairs of the graph, in the order
         ``top_missing_links`` lists from the top: PairRanks(greater, ties int64 [T], logit f32 [T], n_others int64 [T])
         (ops.score_pair_ranks: one target pass and one scan, nothing of size N x N; metrics.global_ranking_metrics turns
@@ -470,7 +487,7 @@ class Disentangle(nn.Module):
         in ``top_missing_links``; None = the edges of ``adj``.  ``node_filter``: a symmetric ops.NodeFilter that candidates
         must pass as well.  A target is ranked whether or not it is excluded or allowed."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
-        Z, H = self._rank_tables(x, graph)
+        Z, H = self._rank_tables(x, graph, table_dtype)
         with torch.no_grad():
             return PairRanks(*ops.score_pair_ranks(Z, H, float(self.temperature), src, dst, graph if exclude is None else exclude,
-                                                   node_filter))
+                                                   node_filter, self._scan_dtype(table_dtype)))

@@ -1268,10 +1268,28 @@ def exclusion_csr(exclude, n_nodes: int, device=None):
     return rowptr.to(torch.int32), (key - r * N).to(torch.int32)
 
 
-def _rank_tables(Z, H):
-    """fp32 [N,K,d] tables on the device, 1 <= d <= 128 (dl_score_topk_supported): the ranking kernels take nothing else."""
-    if Z.dtype != torch.float32 or H.dtype != torch.float32:
-        raise TypeError(f"the ranking kernels take fp32 tables, got {Z.dtype} / {H.dtype}")
+def _scan_dtype(table_dtype) -> int:
+    """The dl_dtype of a scan's ``table_dtype`` keyword: fp32 (the default) or bf16."""
+    if table_dtype is torch.float32:
+        return _lib.DL_F32
+    if table_dtype is torch.bfloat16:
+        return _lib.DL_BF16
+    raise TypeError(f"table_dtype must be torch.float32 or torch.bfloat16, got {table_dtype!r}")
+
+
+def _rank_tables(Z, H, table_dtype=torch.float32):
+    """[N,K,d] tables on the device, 1 <= d <= 128 (dl_score_topk_supported).  ``table_dtype=torch.float32`` (the default):
+    fp32 tensors, nothing else.  ``torch.bfloat16``: Z and H are both bf16 tensors, used as they are, or both fp32 tensors,
+    rounded to nearest-even here exactly as the training step rounds its tables (``HotPathPairs``); the scans then run their
+    one-plane kernels (dl_score_*_dtype with DL_BF16)."""
+    if _scan_dtype(table_dtype) == _lib.DL_F32:
+        if Z.dtype != torch.float32 or H.dtype != torch.float32:
+            raise TypeError(f"the ranking kernels take fp32 tables, got {Z.dtype} / {H.dtype}")
+    else:
+        if Z.dtype != H.dtype or Z.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"table_dtype=torch.bfloat16 takes Z and H both bf16 or both fp32, got {Z.dtype} / {H.dtype}")
+        _need_cuda(Z, H)
+        Z, H = Z.to(torch.bfloat16), H.to(torch.bfloat16)
     _need_cuda(Z, H)
     N, K, d = _nkd(Z)
     if tuple(H.shape) != tuple(Z.shape):
@@ -1436,10 +1454,10 @@ def _filter_check(node_filter, Z, unordered: bool) -> None:
         node_filter._pair_rule()
 
 
-def _scan_tables(Z, H, node_filter, unordered: bool):
+def _scan_tables(Z, H, node_filter, unordered: bool, table_dtype=torch.float32):
     """How every scan starts: the refusals of the node filter, then of the tables -> (Z, H, N, K, d)."""
     _filter_check(node_filter, Z, unordered)
-    return _rank_tables(Z, H)
+    return _rank_tables(Z, H, table_dtype)
 
 
 def _scan_buffers(excl, ws_bytes: int, device):
@@ -1454,23 +1472,38 @@ def _filter_arg(node_filter, N: int, device, unordered: bool):
     return (None, ()) if node_filter is None else node_filter._c_arg(N, device, unordered)
 
 
-def _scan_call(name: str, args, nf) -> None:
+def _scan_call(name: str, args, nf, dt: int = _lib.DL_F32) -> None:
     """The one call path of the scans: the C entry ``name``, or ``name``_filtered with the rule appended where there is
-    one (``nf`` from ``_filter_arg``) — both entries stay in use, and each argument list is written once."""
-    if nf[0] is not None:
+    one (``nf`` from ``_filter_arg``) — both entries stay in use, and each argument list is written once.  bf16 tables
+    (``dt`` = DL_BF16) take ``name``_dtype: the same list with the type behind (Z, H, N, K, d) and the rule, or NULL, last."""
+    if dt != _lib.DL_F32:
+        name, args = name + "_dtype", (*args[:5], dt, *args[5:], nf[0])
+    elif nf[0] is not None:
         name, args = name + "_filtered", (*args, nf[0])
     _lib.check(getattr(_lib.load(), name)(*args), name)
 
 
-def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool = True, node_filter=None):
+def _scan_ws_bytes(name: str, dt: int, N: int, K: int, d: int, *rest) -> int:
+    """dl_score_``name``_workspace_bytes for fp32 tables, its _dtype form for bf16 ones."""
+    lib = _lib.load()
+    if dt == _lib.DL_F32:
+        return getattr(lib, f"dl_score_{name}_workspace_bytes")(N, K, d, *rest)
+    return getattr(lib, f"dl_score_{name}_workspace_bytes_dtype")(N, K, d, dt, *rest)
+
+
+def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool = True, node_filter=None,
+               table_dtype=torch.float32):
     """-> (index int64 [Q,k], logit f32 [Q,k], prob f32 [Q,k]): the k best candidates of every query node by the logit
     s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), sorted (larger
     first, +inf first, NaN last, equal logits by index), prob = sigmoid(logit).  Candidates: every node outside the
     query's exclusion set (``exclusion_csr``) and, with ``exclude_self``, other than the query itself; rows with fewer than
     k are padded with index -1 / NaN.  ``node_filter`` (a ``NodeFilter``): only candidates whose group the query's group
-    allows, on top of the exclusion.  Inference only (dl_score_topk: nothing of size Q x N is formed)."""
-    lib = _lib.load()
-    Z, H, N, K, d = _scan_tables(Z, H, node_filter, False)
+    allows, on top of the exclusion.  Inference only (dl_score_topk: nothing of size Q x N is formed).
+    ``table_dtype=torch.bfloat16`` (here and in every scan below): the scan runs on bf16 tables — bf16 tensors as they are,
+    fp32 tensors rounded to nearest-even — with one matrix-core product per block instead of six and a third of the plane
+    workspace; it returns bit for bit what the fp32 scan returns on the rounded tables (``Z.bfloat16().float()``)."""
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, False, table_dtype)
     k = int(k)
     if not 1 <= k <= RANK_MAX_K:
         raise ValueError(f"k={k} outside 1..{RANK_MAX_K}")
@@ -1481,23 +1514,22 @@ def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool
     prob = _empty((Q, k), torch.float32, Z.device)
     if Q == 0:
         return index, logit, prob
-    rp, cp, ws, _keep = _scan_buffers(exclusion_csr(exclude, N, Z.device), lib.dl_score_topk_workspace_bytes(N, K, d, Q, k, 0),
-                                      Z.device)
+    rp, cp, ws, _keep = _scan_buffers(exclusion_csr(exclude, N, Z.device), _scan_ws_bytes("topk", dt, N, K, d, Q, k, 0), Z.device)
     _scan_call("dl_score_topk", (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), q.data_ptr(), Q, k, rp, cp,
                                  1 if exclude_self else 0, index.data_ptr(), logit.data_ptr(), prob.data_ptr(), ws.data_ptr(),
                                  ws.numel(), _stream()),
-               _filter_arg(node_filter, N, Z.device, False))
+               _filter_arg(node_filter, N, Z.device, False), dt)
     return index, logit, prob
 
 
-def score_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None):
+def score_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None, table_dtype=torch.float32):
     """-> (greater, ties) int64 [P] for the target pairs (src[i], dst[i]): how many candidates of src[i] (every node other
     than src[i] and outside its exclusion set; dst[i] itself is never counted, and is ranked even when it is in the
     exclusion set — the filtered protocol) have a logit strictly above / equal to the target's, by value.  The target's
     logit is the one the scan computes.  rank = 1 + greater + ties / 2 (metrics.ranking_metrics).  ``node_filter``: only
     candidates the rule allows for src[i] are counted; a target is ranked whether or not it is allowed.  dl_score_ranks."""
-    lib = _lib.load()
-    Z, H, N, K, d = _scan_tables(Z, H, node_filter, False)
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, False, table_dtype)
     s = _node_ids(src, N, Z.device, "src")
     v = _node_ids(dst, N, Z.device, "dst")
     if s.numel() != v.numel():
@@ -1516,12 +1548,11 @@ def score_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None):
     queries = queries.to(torch.int32).contiguous()
     g_sorted = _empty(T, torch.int64, Z.device)
     t_sorted = _empty(T, torch.int64, Z.device)
-    rp, cp, ws, _keep = _scan_buffers(exclusion_csr(exclude, N, Z.device), lib.dl_score_topk_workspace_bytes(N, K, d, Q, 0, T),
-                                      Z.device)
+    rp, cp, ws, _keep = _scan_buffers(exclusion_csr(exclude, N, Z.device), _scan_ws_bytes("topk", dt, N, K, d, Q, 0, T), Z.device)
     _scan_call("dl_score_ranks", (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), queries.data_ptr(), Q, tptr.data_ptr(),
                                   tdst.data_ptr(), T, rp, cp, g_sorted.data_ptr(), t_sorted.data_ptr(), ws.data_ptr(), ws.numel(),
                                   _stream()),
-               _filter_arg(node_filter, N, Z.device, False))
+               _filter_arg(node_filter, N, Z.device, False), dt)
     greater[order] = g_sorted
     ties[order] = t_sorted
     return greater, ties
@@ -1544,7 +1575,8 @@ def _unordered_exclusion_csr(exclude, N: int, device):
     return exclusion_csr((torch.minimum(rows, cols), torch.maximum(rows, cols)), N, device)
 
 
-def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf"), node_filter=None):
+def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf"), node_filter=None,
+               table_dtype=torch.float32):
     """-> (src int32 [c], dst int32 [c], logit f32 [c], prob f32 [c]), c = min(m, eligible): the m best unordered pairs
     src < dst of the WHOLE graph by the logit s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid
     link_pred), sorted in ``score_topk``'s order (larger first, +inf first, equal logits by src * N + dst), with the bits
@@ -1553,10 +1585,10 @@ def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-
     1 <= m <= 65,536, N <= 46,340.  Inference only; nothing of size N x N is formed (dl_score_mine), and the one host read
     is that of the count, at the very end.  ``node_filter`` (a symmetric ``NodeFilter``): only pairs whose groups the rule
     allows, on top of the exclusion and the floor."""
-    lib = _lib.load()
-    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True)
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
     m = int(m)
-    rp, cp, ws, _keep = _scan_buffers(_unordered_exclusion_csr(exclude, N, Z.device), lib.dl_score_mine_workspace_bytes(N, K, d, m),
+    rp, cp, ws, _keep = _scan_buffers(_unordered_exclusion_csr(exclude, N, Z.device), _scan_ws_bytes("mine", dt, N, K, d, m),
                                       Z.device)
     src = _empty(max(m, 0), torch.int32, Z.device)
     dst = _empty(max(m, 0), torch.int32, Z.device)
@@ -1566,7 +1598,7 @@ def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-
     _scan_call("dl_score_mine", (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, float(min_logit), m, src.data_ptr(),
                                  dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
                                  _stream()),
-               _filter_arg(node_filter, N, Z.device, True))
+               _filter_arg(node_filter, N, Z.device, True), dt)
     c = int(count.item())
     return src[:c], dst[:c], logit[:c], prob[:c]
 
@@ -1575,25 +1607,29 @@ def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-
 LINKS_MAX_N = MINE_MAX_N
 
 
-def _links_count(Z, H, t, min_logit, exclude, node_filter):
+def _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype=torch.float32):
     """The count pass of ``score_links``: -> (rowptr int64 [N+1] on the device, the arguments of the fill pass)."""
     lib = _lib.load()
-    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True)
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
     if N > LINKS_MAX_N:
         raise ValueError(f"N={N} above {LINKS_MAX_N} (the tile-pair walk of dl_score_mine)")
     excl = _csr_args(*_unordered_exclusion_csr(exclude, N, Z.device), Z.device)
     nf, _keep_nf = _filter_arg(node_filter, N, Z.device, True)
     # a workspace of its own, held across the two calls: the shared grow-only buffer may be handed out (and, under DL_POISON,
     # refilled) in between, and the fill pass reads the planes and the cell offsets the count pass left
-    ws = _empty(max(256, int(lib.dl_score_links_workspace_bytes(N, K, d))), torch.uint8, Z.device)
+    ws = _empty(max(256, int(_scan_ws_bytes("links", dt, N, K, d))), torch.uint8, Z.device)
     rowptr = _empty(N + 1, torch.int64, Z.device)
     head = (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), excl[0], excl[1], float(min_logit), nf, ws.data_ptr(), ws.numel(),
             rowptr.data_ptr())
-    _lib.check(lib.dl_score_links_count(*head, _stream()), "dl_score_links_count")
-    return rowptr, head, (Z, H, excl, _keep_nf, ws)
+    sfx = ""
+    if dt != _lib.DL_F32:                                            # the _dtype entries: the type behind (Z, H, N, K, d)
+        head, sfx = (*head[:5], dt, *head[5:]), "_dtype"
+    _lib.check(getattr(lib, "dl_score_links_count" + sfx)(*head, _stream()), "dl_score_links_count" + sfx)
+    return rowptr, (head, sfx), (Z, H, excl, _keep_nf, ws)
 
 
-def score_links(Z, H, t: float, min_logit: float, exclude=None, node_filter=None):
+def score_links(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32):
     """-> (rowptr int64 [N+1], col int32 [nnz], logit f32 [nnz], prob f32 [nnz]): the predicted graph, EVERY unordered pair
     whose logit s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred) reaches ``min_logit``, as a
     symmetric CSR over all N nodes — each pair as (u, v) and as (v, u) with the same bits, columns ascending within a row,
@@ -1603,21 +1639,21 @@ def score_links(Z, H, t: float, min_logit: float, exclude=None, node_filter=None
     nothing of size N x N is formed (dl_score_links_count / dl_score_links_fill: two scans), there is no cap on nnz, and the
     one host read is that of rowptr[N], between the scans, to allocate the outputs.  Same bits on every call."""
     lib = _lib.load()
-    rowptr, head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter)
+    rowptr, (head, sfx), _keep = _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
     nnz = int(rowptr[-1].item())                                      # the one host read
     dev = rowptr.device
     col = _empty(nnz, torch.int32, dev)
     logit = _empty(nnz, torch.float32, dev)
     prob = _empty(nnz, torch.float32, dev)
-    _lib.check(lib.dl_score_links_fill(*head, nnz, col.data_ptr(), logit.data_ptr(), prob.data_ptr(), _stream()),
-               "dl_score_links_fill")
+    _lib.check(getattr(lib, "dl_score_links_fill" + sfx)(*head, nnz, col.data_ptr(), logit.data_ptr(), prob.data_ptr(), _stream()),
+               "dl_score_links_fill" + sfx)
     return rowptr, col, logit, prob
 
 
-def score_link_degrees(Z, H, t: float, min_logit: float, exclude=None, node_filter=None):
+def score_link_degrees(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32):
     """-> int64 [N]: the predicted degree of every node, i.e. how many partners ``score_links`` would list for it — the
     count pass alone (dl_score_links_count): one scan, no host read, no fill."""
-    rowptr, _head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter)
+    rowptr, _head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
     return rowptr[1:] - rowptr[:-1]
 
 
@@ -1646,12 +1682,13 @@ def pair_exclusion(exclude, N: int, device) -> PairExclusion:
     return PairExclusion(N, rowptr, col, rows * N + cols, (cols > rows).sum().reshape(1))
 
 
-def score_pair_logits(Z, H, t: float, a, b):
+def score_pair_logits(Z, H, t: float, a, b, table_dtype=torch.float32):
     """-> logit f32 [P]: s(a[i], b[i]) with row a[i] as the A operand, from the products of the scans — the bits
     ``score_topk`` returns for query a[i], candidate b[i] (dl_score_pair_logits; a -0 comes back as +0, as the keyed
     outputs of ``score_topk`` and ``score_mine`` report it)."""
     lib = _lib.load()
-    Z, H, N, K, d = _rank_tables(Z, H)
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _rank_tables(Z, H, table_dtype)
     a = _node_ids(a, N, Z.device, "a")
     b = _node_ids(b, N, Z.device, "b")
     if a.numel() != b.numel():
@@ -1660,19 +1697,22 @@ def score_pair_logits(Z, H, t: float, a, b):
     logit = _empty(P, torch.float32, Z.device)
     if P == 0:
         return logit
-    ws = _ws.get(max(256, int(lib.dl_score_pair_logits_workspace_bytes(N, K, d))), Z.device)
-    _lib.check(lib.dl_score_pair_logits(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), a.data_ptr(), b.data_ptr(), P,
-                                        logit.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "dl_score_pair_logits")
+    ws = _ws.get(max(256, int(_scan_ws_bytes("pair_logits", dt, N, K, d))), Z.device)
+    tail = (float(t), a.data_ptr(), b.data_ptr(), P, logit.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    if dt == _lib.DL_F32:
+        _lib.check(lib.dl_score_pair_logits(Z.data_ptr(), H.data_ptr(), N, K, d, *tail), "dl_score_pair_logits")
+    else:
+        _lib.check(lib.dl_score_pair_logits_dtype(Z.data_ptr(), H.data_ptr(), N, K, d, dt, *tail), "dl_score_pair_logits_dtype")
     return torch.where(logit == 0, torch.zeros_like(logit), logit)
 
 
-def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter=None):
+def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter=None, table_dtype=torch.float32):
     """The hook of the tests and of tools/pair_rank_time.py, not part of the interface: ``score_pair_ranks`` and, as a fifth
     value, the int64 [1] DEVICE count of the candidates the scan counted, which equals N (N - 1) / 2 - |excluded pairs| (the
     one exact check that works where nothing can be enumerated; under a ``node_filter``: the pairs the rule allows, less
     the excluded ones among them)."""
-    lib = _lib.load()
-    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True)
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
     dev = Z.device
     s = _node_ids(src, N, dev, "src")
     v = _node_ids(dst, N, dev, "dst")
@@ -1696,7 +1736,7 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter
         e = torch.zeros(0, dtype=torch.int64, device=dev)
         return e, e.clone(), torch.zeros(0, dtype=torch.float32, device=dev), e.clone(), total
     lo, hi = torch.minimum(s, v).contiguous(), torch.maximum(s, v).contiguous()
-    logit = score_pair_logits(Z, H, t, lo, hi)                        # the smaller endpoint as the A operand
+    logit = score_pair_logits(Z, H, t, lo, hi, table_dtype)           # the smaller endpoint as the A operand
     key = _order_keys(logit)
     ksorted, order = torch.sort(key, stable=True)
     first = torch.searchsorted(ksorted, ksorted)                      # first place of each target's value
@@ -1704,10 +1744,10 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter
     above = _empty(T + 1, torch.int64, dev)
     equal = _empty(T + 1, torch.int64, dev)
     counted = _empty(1, torch.int64, dev)
-    rp, cp, ws, _keep = _scan_buffers((rowptr, col), lib.dl_score_pair_ranks_workspace_bytes(N, K, d), dev)
+    rp, cp, ws, _keep = _scan_buffers((rowptr, col), _scan_ws_bytes("pair_ranks", dt, N, K, d), dev)
     _scan_call("dl_score_pair_ranks", (Z.data_ptr(), H.data_ptr(), N, K, d, float(t), rp, cp, tord.data_ptr(), T,
                                        above.data_ptr(), equal.data_ptr(), counted.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       _stream()), nf)
+                                       _stream()), nf, dt)
     cs = torch.cumsum(above, dim=0)
     g_sorted = cs[T] - cs[:T]                                         # candidates that found more than p targets below them
     t_sorted = equal[first]
@@ -1725,7 +1765,7 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter
     return greater, ties - in_c, logit, total - in_c, counted
 
 
-def score_pair_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None):
+def score_pair_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None, table_dtype=torch.float32):
     """-> (greater int64, ties int64, logit f32, n_others int64), each [T]: where the unordered target pairs
     {src[i], dst[i]} (either orientation; duplicates allowed; no self pairs) stand among ALL unordered pairs u < v < N of
     the graph outside ``exclude`` (a set of unordered pairs, as in ``score_mine``, or a prepared ``pair_exclusion``).  logit[i] is formed with the smaller
@@ -1737,4 +1777,4 @@ def score_pair_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None):
     target pass and ONE scan (dl_score_pair_logits, dl_score_pair_ranks), nothing of size N x N, no cap at N = 46,340.
     ``node_filter`` (a symmetric ``NodeFilter``): the candidates are the pairs the rule allows outside ``exclude``; a target
     is ranked whether or not it is allowed."""
-    return score_pair_ranks_counted(Z, H, t, src, dst, exclude, node_filter)[:4]
+    return score_pair_ranks_counted(Z, H, t, src, dst, exclude, node_filter, table_dtype)[:4]

@@ -660,6 +660,47 @@ int dl_score_links_fill(const float* Z, const float* H, int N, int K, int d, flo
                         void* ws, size_t ws_bytes, const int64_t* rowptr, int64_t nnz,
                         int32_t* col, float* logit, float* prob, void* stream);
 
+/* ---- The all-pairs scans over tables of either type.  One entry per launch entry of the family above, with the argument
+ * list of its *_filtered form (filter NULL = no rule) and `dtype`, the element type of Z and H, behind d.  DL_F32: exactly
+ * the entry above, which is a call of this one.  DL_BF16: Z and H are bf16 [N][K][d].  A bf16 value is its own hi plane
+ * (mid = lo = 0), so the scan stages ONE bf16 plane per operand instead of three and issues ONE matrix-core product per
+ * K = 16 block instead of six; the plane arrays of the workspace shrink to a third (for mine, pair logits / ranks and links:
+ * by exactly 8 K Np dp bytes, Np = N rounded up to 128, dp = d to 32; top-k / ranks also lose the fp32 copy of the gathered
+ * query rows).  Nothing else differs: limits, outputs, order, padding, determinism and the launch forms (*_form) are those
+ * of the fp32 entries.
+ * Bit contract: for finite tables, a DL_BF16 call returns bit for bit what the DL_F32 call returns on the same tables
+ * widened to fp32 -- the five products it leaves out add exact zeros to an accumulator that starts at +0.
+ * An unknown dtype is DL_E_ARG (the *_workspace_bytes_dtype functions return 0 for it).  dl_score_links_fill_dtype reads the
+ * workspace dl_score_links_count_dtype left with the SAME dtype. */
+int dl_score_scan_supported(int K, int d, dl_dtype dtype);  /* every scan of the family: 1 <= K <= 64, 1 <= d <= 128 */
+size_t dl_score_topk_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype, int n_queries, int k, int n_targets);
+size_t dl_score_mine_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype, int m);
+size_t dl_score_pair_logits_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype);
+size_t dl_score_pair_ranks_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype);
+size_t dl_score_links_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype);
+int dl_score_topk_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* queries,
+                        int n_queries, int k, const int32_t* ex_rowptr, const int32_t* ex_col, int exclude_self, int64_t* index,
+                        float* logit, float* prob, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter);
+int dl_score_ranks_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* queries,
+                         int n_queries, const int32_t* tptr, const int32_t* tdst, int n_targets, const int32_t* ex_rowptr,
+                         const int32_t* ex_col, int64_t* greater, int64_t* ties, void* ws, size_t ws_bytes, void* stream,
+                         const dl_node_filter* filter);
+int dl_score_mine_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
+                        const int32_t* ex_col, float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob,
+                        int64_t* count, void* ws, size_t ws_bytes, void* stream, const dl_node_filter* filter);
+int dl_score_pair_logits_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* a,
+                               const int32_t* b, int n_pairs, float* logit, void* ws, size_t ws_bytes, void* stream);
+int dl_score_pair_ranks_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
+                              const int32_t* ex_col, const uint32_t* target_order, int n_targets, unsigned long long* above,
+                              unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes, void* stream,
+                              const dl_node_filter* filter);
+int dl_score_links_count_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
+                               const int32_t* ex_col, float min_logit, const dl_node_filter* filter, void* ws, size_t ws_bytes,
+                               int64_t* rowptr, void* stream);
+int dl_score_links_fill_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
+                              const int32_t* ex_col, float min_logit, const dl_node_filter* filter, void* ws, size_t ws_bytes,
+                              const int64_t* rowptr, int64_t nnz, int32_t* col, float* logit, float* prob, void* stream);
+
 /* Tie-averaged AUC of a score vector against FIXED labels: replaces sklearn.metrics.roc_auc_score at
  * main_disentangled.py:202-204 / 217-219 (validation AUC every epoch, test AUC at the end).  pos_idx / neg_idx
  * (int64, device) are the positions of the positive and negative labels in score, found once per run; the call
