@@ -126,6 +126,8 @@ EXPORTS = {
     "dl_score_pair_ranks_workspace_bytes": (_z, [_i, _i, _i]),
     "dl_score_pair_logits": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _i, _P, _P, _z, _P]),
     "dl_score_pair_ranks": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
+    "dl_score_pair_terms_workspace_bytes": (_z, [_i, _i, _i]),
+    "dl_score_pair_terms": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
     "dl_score_topk_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _i, _P, _P, _i, _P, _P, _P, _P, _z, _P, _NF]),
     "dl_score_ranks_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P, _z, _P, _NF]),
     "dl_score_mine_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _i, _P, _P, _P, _P, _P, _P, _z, _P, _NF]),
@@ -146,6 +148,8 @@ EXPORTS = {
     "dl_score_mine_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _f, _i, _P, _P, _P, _P, _P, _P, _z, _P, _NF]),
     "dl_score_pair_logits_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _i, _P, _P, _z, _P]),
     "dl_score_pair_ranks_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _P, _i, _P, _P, _P, _P, _z, _P, _NF]),
+    "dl_score_pair_terms_workspace_bytes_dtype": (_z, [_i, _i, _i, _i]),
+    "dl_score_pair_terms_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
     "dl_score_links_count_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _f, _NF, _P, _z, _P, _P]),
     "dl_score_links_fill_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _f, _NF, _P, _z, _P, C.c_int64, _P, _P, _P, _P]),
     "dl_auc_pair_counts_supported": (_i, [_i, _i]),

@@ -643,6 +643,33 @@ int dl_score_pair_logits_dtype(const void* Z, const void* H, int N, int K, int d
     return score_pair_logits(Z, H, dtype, N, K, d, t, a, b, n_pairs, logit, ws, (hipStream_t)stream);
 }
 
+size_t dl_score_pair_terms_workspace_bytes(int N, int K, int d) { return dl_score_pair_terms_workspace_bytes_dtype(N, K, d, DL_F32); }
+
+size_t dl_score_pair_terms_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype) {
+    return dl_score_pair_logits_workspace_bytes_dtype(N, K, d, dtype);
+}
+
+int dl_score_pair_terms(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
+                        int n_pairs, float* e, float* q, float* cum, void* ws, size_t ws_bytes, void* stream) {
+    return dl_score_pair_terms_dtype(Z, H, N, K, d, DL_F32, t, a, b, n_pairs, e, q, cum, ws, ws_bytes, stream);
+}
+
+// the checks of dl_score_pair_logits_dtype in its order; what is there of the outputs belongs to the pointers
+int dl_score_pair_terms_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* a,
+                              const int32_t* b, int n_pairs, float* e, float* q, float* cum, void* ws, size_t ws_bytes,
+                              void* stream) {
+    if (int rc = check_scan_shape(PAIR_SCAN, N, K, d, dtype)) return rc;
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    DL_REQUIRE(n_pairs >= 0 && n_pairs <= (1 << 30), "n_pairs=%d outside 0..2^30", n_pairs);
+    if (n_pairs == 0) return DL_OK;
+    if (int rc = check_scan_ptrs(PAIR_SCAN, Z && H && a && b, nullptr, nullptr)) return rc;
+    DL_REQUIRE(e || q || cum, "NULL output: e, q and cum are all NULL");
+    if (int rc = check_scan_ws(PAIR_SCAN, ws, ws_bytes, score_pair_logits_workspace_bytes(N, K, d, dtype),
+                               "dl_score_pair_terms_workspace_bytes"))
+        return rc;
+    return score_pair_terms(Z, H, dtype, N, K, d, t, a, b, n_pairs, e, q, cum, ws, (hipStream_t)stream);
+}
+
 int dl_score_pair_ranks(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* ex_rowptr,
                         const int32_t* ex_col, const uint32_t* target_order, int n_targets, unsigned long long* above,
                         unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes, void* stream) {

@@ -97,6 +97,10 @@ int score_mine(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, f
 size_t score_pair_logits_workspace_bytes(int N, int K, int d, dl_dtype dt = DL_F32);
 int score_pair_logits(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b, int T,
                       float* logit, void* ws, hipStream_t st);
+// the per-factor terms of given pairs from the same pass (e, q, cum: [T][K] each, NULL = not wanted; not all NULL); the
+// workspace is score_pair_logits_workspace_bytes
+int score_pair_terms(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b, int T,
+                     float* e, float* q, float* cum, void* ws, hipStream_t st);
 size_t score_pair_ranks_workspace_bytes(int N, int K, int d, dl_dtype dt = DL_F32);
 int score_pair_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
                      const unsigned* tord, int T, unsigned long long* gcnt, unsigned long long* tcnt, unsigned long long* ncand,

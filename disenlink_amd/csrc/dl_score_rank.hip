@@ -22,6 +22,9 @@
 // Keys order the logits totally: larger first, +inf above every finite value, -inf below, NaN below everything; equal
 // values by candidate index, smaller first.  Everything selected or counted is a function of the logits alone, and the
 // logit of a pair does not depend on where in a tile its rows sit: results are independent of the slicing and of the run.
+// Given pairs (dl_score_pair_logits, dl_score_pair_terms): the DIAG and TERMS instantiations, a tile of 128 pairs against itself
+// with the diagonal kept.  DIAG writes the logit; TERMS writes, per factor, what the pass holds on the way to it: e = exp(S / t),
+// q = h.h and the running sum, whose last column has the logit's bits ("which factor makes this link").
 // bf16 tables (the *_dtype entries with DL_BF16): the P = 1 instantiations, one plane per operand (copy_rows, which also
 // gathers the query rows) and one product per block; on the same values, the bits of the three-plane scan.
 #include "dl_common.h"
@@ -41,7 +44,7 @@ constexpr int MAX_K = 128;
 constexpr int ROUND = 64;      // keys one round of appends can add to a row's list
 constexpr int MAX_CAP = MAX_K + ROUND;
 constexpr int MAX_SLICES = 32;
-enum { TOPK = 0, RANKS = 1, DIAG = 2 };
+enum { TOPK = 0, RANKS = 1, DIAG = 2, TERMS = 3 };
 
 struct ScanArgs {
     const __bf16 *qz, *qh;  size_t qbatch;     // planes of the gathered query rows (per factor: qbatch elements)
@@ -55,6 +58,7 @@ struct ScanArgs {
     const int32_t* tptr;  const unsigned* tord;  u64* gcnt;  u64* tcnt;   // RANKS
     const int32_t *trow, *tdst;  int T;  float* tlogit;                 // DIAG: target i = (query row trow[i], node tdst[i])
     FilterArgs filt;                                                    // FILT: the node-group rule (dl_tiles.h)
+    float *te, *tq, *tcum;                     // TERMS: [T][K] each, NULL = not wanted (targets as in DIAG)
 };
 
 // LDS with P planes per operand (bytes): the two double-buffered staging images, the logits' way through LDS, then the
@@ -80,6 +84,40 @@ __device__ __forceinline__ void gather_fetch(PlaneStage<RTHR, SDC, P>& st, const
 #pragma unroll
     for (int p = 0; p < P; ++p)
         st.v[p] = *reinterpret_cast<const typename PlaneStage<RTHR, SDC, P>::u32x4*>(src + (size_t)p * PLANE_ROWS * SDC);
+}
+
+// TERMS: which of a lane's 2 x 16 accumulator elements lies on the tile's diagonal (DIAG's ul == vl), as bb * 16 + q, or -1:
+// at most one per lane.  Found once per workgroup, so that a store is a tree of selects on the bits of the index and the
+// 32 values stay in registers.
+__device__ __forceinline__ int diagonal_element(int wu, int wv, int li, int half) {
+    int sel = -1;
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if (wu * 32 + acc_row(q, half) == wv * 64 + bb * 32 + li) sel = bb * 16 + q;
+    }
+    return sel;
+}
+// x[sel >> 4][sel & 15], sel in [0, 32).  Every value passes an empty asm on its way into a select: the compiler would
+// otherwise turn selects of array elements into one load at a selected address, which puts the array into scratch.
+__device__ __forceinline__ float in_register(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ float pick2(bool odd, float even_v, float odd_v) { return in_register(odd ? odd_v : even_v); }
+template <class V>
+__device__ __forceinline__ float pick16(const V& x, bool b0, bool b1, bool b2, bool b3) {
+#define DL_PAIR(j) pick2(b0, in_register(x[2 * (j)]), in_register(x[2 * (j) + 1]))
+    const float c0 = pick2(b2, pick2(b1, DL_PAIR(0), DL_PAIR(1)), pick2(b1, DL_PAIR(2), DL_PAIR(3)));
+    const float c1 = pick2(b2, pick2(b1, DL_PAIR(4), DL_PAIR(5)), pick2(b1, DL_PAIR(6), DL_PAIR(7)));
+#undef DL_PAIR
+    return pick2(b3, c0, c1);
+}
+template <class V>
+__device__ __forceinline__ float pick_element(const V (&x)[2], int sel) {
+    const bool b0 = sel & 1, b1 = sel & 2, b2 = sel & 4, b3 = sel & 8;
+    return pick2(sel & 16, pick16(x[0], b0, b1, b2, b3), pick16(x[1], b0, b1, b2, b3));
 }
 
 // Rank one row's list against itself and write its best min(n, k) keys back in order (one wave; between barriers).
@@ -139,7 +177,8 @@ __device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, 
 // step keeps its 32 columns, so the k-blocks of a product are added in the same ascending order in both.
 template <int MODE, bool FILT = false, int P = 3>
 __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
-    static_assert(!(FILT && MODE == DIAG), "the target pass has no mask");
+    static_assert(!(FILT && (MODE == DIAG || MODE == TERMS)), "the target passes have no mask");
+    constexpr bool PAIRS = MODE == DIAG || MODE == TERMS;      // TERMS: DIAG's geometry and gathers, other stores
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][P][TT][SLD]
     __bf16* vs = us + 2 * P * TT * SLD;
@@ -157,15 +196,15 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
     unsigned char* cgrp = reinterpret_cast<unsigned char*>(fal + 64);
     unsigned char* rgrp = cgrp + TT;
 
-    const int nrows = MODE == DIAG ? A.T : A.Q;
+    const int nrows = PAIRS ? A.T : A.Q;
     const int qtiles = (nrows + TT - 1) / TT;
-    const int nslices = MODE == DIAG ? 1 : A.slices;
+    const int nslices = PAIRS ? 1 : A.slices;
     const XcdItem it = xcd_item((int)blockIdx.x, qtiles, nslices);
     if (!it.valid) return;
     const int qt = it.a, sl = it.b;
     const int nt = (A.N + TT - 1) / TT;
     int ct0 = qt, ntl = 1;
-    if constexpr (MODE != DIAG) {
+    if constexpr (!PAIRS) {
         ct0 = sl * A.tiles_per_slice;
         ntl = max(0, min(nt, ct0 + A.tiles_per_slice) - ct0);
     }
@@ -176,7 +215,7 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
     const int per_tile = A.K * 2 * nd;
     const int steps = ntl * per_tile;
 
-    if constexpr (MODE != DIAG) {
+    if constexpr (!PAIRS) {
         if (tid < TT) {
             const int qi = qt * TT + tid;
             const int node = qi < A.Q ? A.qnode[qi] : -1;
@@ -206,6 +245,15 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
         }
     }
 
+    int tsel = -1;                                              // TERMS: the lane's diagonal element and its pair's row [K]
+    size_t tcell = 0;
+    if constexpr (MODE == TERMS) {
+        tsel = diagonal_element(wu, wv, li, half);
+        const int i = qt * TT + wv * 64 + (tsel >> 4) * 32 + li;
+        if (i >= A.T) tsel = -1;
+        tcell = (size_t)i * A.K;
+    }
+
     PlaneStage<RTHR, SDC, P> uq, vq;
     static_assert(TT == PLANE_ROWS, "tiles of the plane arrays");
     auto fetch = [&](int s) {
@@ -214,7 +262,7 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
         const int dc = r < nd ? r : r - nd;
         const __bf16* qsrc = (r < nd ? A.qz : A.qh) + (size_t)k * A.qbatch;
         const __bf16* csrc = (r < nd ? A.cz : A.ch) + (size_t)k * A.cbatch;
-        if constexpr (MODE == DIAG) {
+        if constexpr (PAIRS) {
             gather_fetch(uq, qsrc, A.trow, qt * TT, A.T, dc, nd, tid);
             gather_fetch(vq, csrc, A.tdst, qt * TT, A.T, dc, nd, tid);
         } else {
@@ -265,12 +313,21 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
                 for (int q = 0; q < 16; ++q) e[bb][q] = expf(div_t(acc[bb][q], A.t));
                 zero_acc(acc[bb]);
             }
+            if constexpr (MODE == TERMS) {
+                if (A.te != nullptr && tsel >= 0) A.te[tcell + rem / (2 * nd)] = pick_element(e, tsel);
+            }
         } else if (r == 2 * nd - 1) {                           // Q complete: term += Q * e
+            if constexpr (MODE == TERMS) {
+                if (A.tq != nullptr && tsel >= 0) A.tq[tcell + rem / (2 * nd)] = pick_element(acc, tsel);
+            }
 #pragma unroll
             for (int bb = 0; bb < 2; ++bb) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) term[bb][q] += acc[bb][q] * e[bb][q];
                 zero_acc(acc[bb]);
+            }
+            if constexpr (MODE == TERMS) {                      // the running sum: column K - 1 has DIAG's bits
+                if (A.tcum != nullptr && tsel >= 0) A.tcum[tcell + rem / (2 * nd)] = pick_element(term, tsel);
             }
         }
         if constexpr (FILT) {
@@ -285,7 +342,8 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
 
         // ---- candidate tile complete: term[bb][q] = s(query row wu*32 + acc_row(q, half), candidate vl = wv*64 + bb*32 + li)
         const int v0 = (ct0 + s / per_tile) * TT;
-        if constexpr (MODE == DIAG) {
+        if constexpr (MODE == TERMS) {                          // everything was written on the way
+        } else if constexpr (MODE == DIAG) {
 #pragma unroll
             for (int bb = 0; bb < 2; ++bb) {
 #pragma unroll
@@ -701,6 +759,25 @@ int score_pair_logits(const void* Z, const void* H, dl_dtype dt, int N, int K, i
     g.trow = a; g.tdst = b; g.T = T; g.tlogit = logit;
     launch_rank<DIAG>(dt, nullptr, (unsigned)xcd_grid((T + TT - 1) / TT, 1), st, g);
     return check_launch("score_pair_logits");
+}
+
+// ---- dl_score_pair_terms: the same pass in its TERMS instantiation, which writes what the pass holds per factor (e, q, the
+// running sum) for the pair on the diagonal instead of the final sum alone.  Same workspace, same operands, same products.
+int score_pair_terms(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
+                     int T, float* e, float* q, float* cum, void* ws, hipStream_t st) {
+    const PairWs w = pair_carve(N, K, d, dt, ws);
+    table_planes(Z, dt, nullptr, N, K, d, w.cz, st);
+    table_planes(H, dt, nullptr, N, K, d, w.ch, st);
+    ScanArgs g = {};
+    g.qz = w.cz; g.qh = w.ch; g.qbatch = w.cbatch;
+    g.cz = w.cz; g.ch = w.ch; g.cbatch = w.cbatch;
+    g.N = N; g.K = K; g.nd = (d + SDC - 1) / SDC; g.t = t;
+    g.trow = a; g.tdst = b; g.T = T;
+    g.te = e; g.tq = q; g.tcum = cum;
+    const unsigned grid = (unsigned)xcd_grid((T + TT - 1) / TT, 1);
+    if (dt == DL_BF16) launch_lds<rank_scan_kernel<TERMS, false, 1>>(grid, RTHR, lds_bytes(1), st, g);
+    else launch_lds<rank_scan_kernel<TERMS>>(grid, RTHR, lds_bytes(3), st, g);
+    return check_launch("score_pair_terms");
 }
 
 }  // namespace dl

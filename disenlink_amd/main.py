@@ -77,6 +77,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "the number of links, the density and the mean / max predicted degree")
     p.add_argument("--links-out", type=str, default=None, metavar="FILE",
                    help="with --predict-links: write the links to FILE as text, one `src dst prob` line per pair, src < dst")
+    p.add_argument("--explain", action="store_true",
+                   help="with --mine / --predict-links: say which of the K factors makes each listed link "
+                        "(Disentangle.explain_links: the per-factor terms of the scans' own pass).  --mine-out lines gain "
+                        "`factor contrib[factor]`, --links-out lines gain `factor`, and the number of links per dominant "
+                        "factor is printed")
     p.add_argument("--node-groups", type=str, default=None, metavar="FILE",
                    help="with --link-rule: the group (an integer in 0..63) of every node, one per node, as text or .npy")
     p.add_argument("--link-rule", choices=["same", "different"], default=None,
@@ -262,36 +267,66 @@ def global_rank_eval(model, x, graph, split, known, node_filter=None, table_dtyp
     return global_ranking_metrics(r.greater, r.ties, r.n_others)
 
 
-def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=print, node_filter=None, table_dtype=None):
+def explain(model, x, graph, src, dst, what: str, log=print, table_dtype=None):
+    """--explain: the dominant factor of every listed link and its contribution (Disentangle.explain_links) as numpy arrays
+    (a link whose terms hold a NaN has factor -1 and contribution NaN), and one line: links per dominant factor."""
+    terms = model.explain_links(x, graph, src, dst, table_dtype=table_dtype)
+    factor = terms.factor
+    top = terms.contrib.gather(1, factor.clamp(min=0)[:, None])[:, 0]
+    top = torch.where(factor < 0, torch.full_like(top, float("nan")), top)
+    counts = torch.bincount(factor[factor >= 0], minlength=terms.cum.shape[1]).tolist()
+    nan = int((factor < 0).sum())
+    log(f"{what} links by dominant factor: " + " ".join(f"{k}:{c}" for k, c in enumerate(counts)) +
+        (f" nan:{nan}" if nan else ""))
+    return factor.cpu().numpy(), top.cpu().numpy()
+
+
+def mine_links(model, x, graph, known, m: int, out=None, show: int = 10, log=print, node_filter=None, table_dtype=None,
+               explained: bool = False):
     """--mine: the m most likely links outside ``known`` (Disentangle.top_missing_links), the first ``show`` printed and,
-    with ``out``, all of them written as `src dst logit prob` lines."""
+    with ``out``, all of them written as `src dst logit prob` lines; ``explained`` (--explain): every line, printed or
+    written, ends in `factor contrib[factor]`."""
     mined = model.top_missing_links(x, graph, m, exclude=known, node_filter=node_filter, table_dtype=table_dtype)
     src, dst, logit, prob = (v.cpu().numpy() for v in mined)
-    log(f"mined {src.size} links (of {m} asked for); first {min(show, src.size)}: src dst logit prob")
+    more = [""] * src.size
+    if explained:
+        factor, top = explain(model, x, graph, mined.src, mined.dst, "mined", log, table_dtype)
+        more = [f" {f} {c:.9g}" for f, c in zip(factor.tolist(), top.tolist())]
+    log(f"mined {src.size} links (of {m} asked for); first {min(show, src.size)}: src dst logit prob"
+        f"{' factor contrib' if explained else ''}")
     for i in range(min(show, src.size)):
-        log(f"{src[i]} {dst[i]} {logit[i]:.6g} {prob[i]:.6g}")
+        log(f"{src[i]} {dst[i]} {logit[i]:.6g} {prob[i]:.6g}{more[i]}")
     if out:
         with open(out, "w") as fh:
             for i in range(src.size):
-                fh.write(f"{src[i]} {dst[i]} {logit[i]:.9g} {prob[i]:.9g}\n")
+                fh.write(f"{src[i]} {dst[i]} {logit[i]:.9g} {prob[i]:.9g}{more[i]}\n")
     return mined
 
 
-def predict_links(model, x, graph, known, min_prob: float, out=None, log=print, node_filter=None, table_dtype=None):
+def predict_links(model, x, graph, known, min_prob: float, out=None, log=print, node_filter=None, table_dtype=None,
+                  explained: bool = False):
     """--predict-links: every link outside ``known`` whose link_pred reaches ``min_prob`` (Disentangle.predicted_links), a
-    summary line printed and, with ``out``, all of them written as `src dst prob` lines, src < dst."""
+    summary line printed and, with ``out``, all of them written as `src dst prob` lines, src < dst; ``explained``
+    (--explain): the lines end in `factor`, each unordered pair explained once."""
     links = model.predicted_links(x, graph, min_prob, exclude=known, node_filter=node_filter, table_dtype=table_dtype)
     n = links.n_nodes
-    src, dst, _, prob = (v.cpu().numpy() for v in links.pairs())
+    pairs = links.pairs()
+    src, dst, _, prob = (v.cpu().numpy() for v in pairs)
     deg = links.degree.cpu().numpy()
     density = src.size / (n * (n - 1) / 2) if n > 1 else 0.0
     log(f"predicted {src.size} links at prob >= {min_prob:g}: density {density:.6g} mean degree {deg.mean():.6g} "
         f"max degree {int(deg.max())}")
+    factor = None
+    if explained:
+        factor, _ = explain(model, x, graph, pairs[0], pairs[1], "predicted", log, table_dtype)
     if out:
         with open(out, "w") as fh:                                   # millions of lines at a useful threshold: by chunks
             for i in range(0, src.size, 1 << 16):
                 rows = zip(src[i:i + (1 << 16)].tolist(), dst[i:i + (1 << 16)].tolist(), prob[i:i + (1 << 16)].tolist())
-                fh.write("".join(f"{a} {b} {p:.9g}\n" for a, b, p in rows))
+                if factor is None:
+                    fh.write("".join(f"{a} {b} {p:.9g}\n" for a, b, p in rows))
+                else:
+                    fh.write("".join(f"{a} {b} {p:.9g} {f}\n" for (a, b, p), f in zip(rows, factor[i:i + (1 << 16)].tolist())))
     return links
 
 
@@ -334,6 +369,8 @@ def main(argv=None):
         raise SystemExit("--predict-links P: 0 <= P <= 1")
     if args.links_out and args.predict_links is None:
         raise SystemExit("--links-out FILE goes with --predict-links P")
+    if args.explain and not (args.mine or args.predict_links is not None):
+        raise SystemExit("--explain names the factor behind the links of --mine and --predict-links: give one of them")
     if (args.node_groups is None) != (args.link_rule is None):
         raise SystemExit("--node-groups FILE and --link-rule {same,different} go together")
     if args.link_rule and not (args.rank_eval or args.global_rank_eval or args.mine or args.predict_links is not None):
@@ -399,10 +436,11 @@ def main(argv=None):
             if not args.quiet:
                 print("test global ranking:", _fmt_ranking(global_ranking[-1]))
     if args.mine and args.run > 0:                                  # the last run's model, its best weights
-        mine_links(model, x, prepared.graph, known, args.mine, args.mine_out, node_filter=node_filter, table_dtype=sdt)
+        mine_links(model, x, prepared.graph, known, args.mine, args.mine_out, node_filter=node_filter, table_dtype=sdt,
+                   explained=args.explain)
     if args.predict_links is not None and args.run > 0:
         predict_links(model, x, prepared.graph, known, args.predict_links, args.links_out, node_filter=node_filter,
-                      table_dtype=sdt)
+                      table_dtype=sdt, explained=args.explain)
     result = np.array(result)
     tail = []                                                       # the run means of the ranking metrics join the final line
     if args.rank_eval:

@@ -479,6 +479,15 @@ class Disentangle(nn.Module):
             return PredictedLinks(*ops.score_links(Z, H, float(self.temperature), floor, graph if exclude is None else exclude,
                                                    node_filter, self._scan_dtype(table_dtype)))
 
+    def explain_links(self, x, adj, src, dst, table_dtype=None) -> "ops.PairTerms":
+        """Which factor makes the links (src[i], dst[i]): ops.PairTerms(e, q, cum) f32 [P, K] with ``.logit``, ``.contrib``
+        [P, K] and ``.factor`` int64 [P] (ops.score_pair_terms: the pass of the scans with its per-factor terms written
+        out).  Row src[i] is the A operand: pass the pairs as ``top_missing_links`` or ``predicted_links().pairs()``
+        list them (src < dst) and ``.logit`` has the bits they report."""
+        Z, H = self._rank_tables(x, adj, table_dtype)
+        with torch.no_grad():
+            return ops.score_pair_terms(Z, H, float(self.temperature), src, dst, self._scan_dtype(table_dtype))
+
     def missing_link_ranks(self, x, adj, src, dst, exclude=None, node_filter=None, table_dtype=None) -> PairRanks:
         """Where the unordered pairs {src[i], dst[i]} stand among ALL unordered pairs of the graph, in the order
         ``top_missing_links`` lists from the top: PairRanks(greater, ties int64 [T], logit f32 [T], n_others int64 [T])

@@ -1706,6 +1706,61 @@ def score_pair_logits(Z, H, t: float, a, b, table_dtype=torch.float32):
     return torch.where(logit == 0, torch.zeros_like(logit), logit)
 
 
+class PairTerms(namedtuple("PairTerms", ["e", "q", "cum"])):
+    """The per-factor terms of scored pairs (``score_pair_terms``), fp32 [P, K] each: ``e`` = exp(z_k[a].z_k[b] / t),
+    ``q`` = h_k[a].h_k[b], ``cum`` = the scan's running sum after factor k (its last column is the logit)."""
+    __slots__ = ()
+
+    @property
+    def logit(self) -> torch.Tensor:
+        """f32 [P]: ``cum[:, -1]`` with a -0 reported as +0 — the bits the scans report for the pair."""
+        x = self.cum[:, -1]
+        return torch.where(x == 0, torch.zeros_like(x), x)
+
+    @property
+    def contrib(self) -> torch.Tensor:
+        """f32 [P, K]: what factor k added to the sum: cum[:, 0], then cum[:, k] - cum[:, k-1]."""
+        out = self.cum.clone()
+        out[:, 1:] -= self.cum[:, :-1]
+        return out
+
+    @property
+    def factor(self) -> torch.Tensor:
+        """int64 [P]: the factor with the largest contribution (the first of equals), -1 where the row holds a NaN."""
+        c = self.contrib
+        top = c.max(dim=1, keepdim=True).values
+        first = (c == top).to(torch.int64).argmax(dim=1)          # argmax of 0/1 values: the first 1
+        return torch.where(torch.isnan(c).any(dim=1), torch.full_like(first, -1), first)
+
+
+def score_pair_terms(Z, H, t: float, a, b, table_dtype=torch.float32) -> PairTerms:
+    """-> PairTerms(e, q, cum), fp32 [P, K] each: WHY the pair (a[i], b[i]) scores as it does — per factor k the routing
+    weight e = exp(z_k[a].z_k[b] / t), the Gram product q = h_k[a].h_k[b] and the running sum cum of the very pass
+    ``score_pair_logits`` runs (dl_score_pair_terms: same gathers and products, row a[i] as the A operand).
+    ``cum[:, -1]`` has the bits ``score_pair_logits`` returns, hence those ``score_topk``, ``score_mine`` and
+    ``score_links`` list (``.logit``: with their -0 -> +0); ``cum[:, k]`` is the logit of the tables cut to factors 0..k.
+    ``.contrib`` and ``.factor`` name the factor that makes the link.  Inference only."""
+    lib = _lib.load()
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _rank_tables(Z, H, table_dtype)
+    a = _node_ids(a, N, Z.device, "a")
+    b = _node_ids(b, N, Z.device, "b")
+    if a.numel() != b.numel():
+        raise ValueError("a and b differ in length")
+    P = int(a.numel())
+    out = PairTerms(*(_empty((P, K), torch.float32, Z.device) for _ in range(3)))
+    if P == 0:
+        return out
+    ws = _ws.get(max(256, int(_scan_ws_bytes("pair_terms", dt, N, K, d))), Z.device)
+    tail = (float(t), a.data_ptr(), b.data_ptr(), P, out.e.data_ptr(), out.q.data_ptr(), out.cum.data_ptr(), ws.data_ptr(),
+            ws.numel(), _stream())
+    if dt == _lib.DL_F32:
+        _lib.check(lib.dl_score_pair_terms(Z.data_ptr(), H.data_ptr(), N, K, d, *tail), "dl_score_pair_terms")
+    else:
+        _lib.check(lib.dl_score_pair_terms_dtype(Z.data_ptr(), H.data_ptr(), N, K, d, dt, *tail), "dl_score_pair_terms_dtype")
+    return out
+
+
 def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter=None, table_dtype=torch.float32):
     """The hook of the tests and of tools/pair_rank_time.py, not part of the interface: ``score_pair_ranks`` and, as a fifth
     value, the int64 [1] DEVICE count of the candidates the scan counted, which equals N (N - 1) / 2 - |excluded pairs| (the

@@ -580,6 +580,35 @@ int dl_score_pair_ranks(const float* Z, const float* H, int N, int K, int d, flo
                         unsigned long long* above, unsigned long long* equal, unsigned long long* n_candidates,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* dl_score_pair_terms (an extension; the reference has no counterpart): WHY a pair scores as it does — the per-factor terms
+ * of s(a[i], b[i]) = sum_k q_k e_k for n_pairs given pairs, from the very pass dl_score_pair_logits runs (same gathers, same
+ * products, row a[i] as the A operand), which writes what it holds per factor instead of the final sum alone.  Three fp32
+ * arrays [n_pairs][K], row-major; each may be NULL (not wanted), not all three:
+ *   e  [i][k] = exp(z_k[a].z_k[b] / t)   the routing weight of factor k
+ *   q  [i][k] = h_k[a].h_k[b]            the Gram product of factor k
+ *   cum[i][k] = the running sum after factor k has been added: the logit of the tables cut to factors 0..k
+ * Bit contract: cum[i][K-1] has the bits dl_score_pair_logits returns for the pair, hence the bits dl_score_topk,
+ * dl_score_mine and dl_score_links_fill report for it (with their rule that a -0 is reported as +0: here, as in
+ * dl_score_pair_logits, a -0 is written as it is).  The contribution of factor k is cum[i][k] - cum[i][k-1] (cum[i][0] for
+ * k = 0); q[i][k] * e[i][k] is the same term before it is rounded into the sum.  A NaN or +-inf in factor k shows in
+ * cum[i][k..] exactly as it does in the logit.  Every cell of a non-NULL array is written once, without atomics: the same
+ * bits on every call.
+ * Limits, supported shapes, codes and the order of the checks are those of dl_score_pair_logits_dtype (node ids in [0, N),
+ * not checked; N <= DL_SCORE_PAIR_RANKS_MAX_N; N K d < 2^40; n_pairs <= 2^30; t != 0; a missing or short workspace is
+ * DL_E_WORKSPACE); e, q and cum all NULL is DL_E_ARG.  n_pairs = 0 succeeds and launches nothing.
+ * ws: dl_score_pair_terms_workspace_bytes(N, K, d) = dl_score_pair_logits_workspace_bytes(N, K, d).  No allocation, no
+ * synchronisation, no host read; the caller's stream.  The _dtype forms (DL_BF16: bf16 tables, one plane, one product; the
+ * bits of the DL_F32 call on the widened tables) follow the rules of the *_dtype family below. */
+size_t dl_score_pair_terms_workspace_bytes(int N, int K, int d);
+size_t dl_score_pair_terms_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype);
+int dl_score_pair_terms(const float* Z, const float* H, int N, int K, int d, float t,
+                        const int32_t* a, const int32_t* b, int n_pairs,
+                        float* e, float* q, float* cum,                        /* [n_pairs][K] each; NULL = not wanted */
+                        void* ws, size_t ws_bytes, void* stream);
+int dl_score_pair_terms_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                              const int32_t* a, const int32_t* b, int n_pairs, float* e, float* q, float* cum,
+                              void* ws, size_t ws_bytes, void* stream);
+
 /* A rule on node groups for the four candidate scans above (an extension; the reference has no counterpart): which KINDS of
  * node may be linked, where an exclusion CSR could only list the O(N^2) pairs one by one.
  *   group    [N] uint8, DEVICE: the group of every node, each < n_groups (a precondition: device data is not read back)
