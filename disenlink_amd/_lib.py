@@ -113,45 +113,13 @@ EXPORTS = {
     "dl_score_allpairs_bwd_dense_workspace_bytes": (_z, [_i, _i, _i]),
     "dl_score_allpairs_bwd_dense": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_topk_supported": (_i, [_i, _i]),
-    "dl_score_topk_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
-    "dl_score_topk": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _i, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
-    "dl_score_ranks": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_mine_supported": (_i, [_i, _i]),
     "dl_score_mine_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
-    "dl_score_mine_workspace_bytes": (_z, [_i, _i, _i, _i]),
-    "dl_score_mine": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _i, _P, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_pair_ranks_supported": (_i, [_i, _i]),
     "dl_score_pair_ranks_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
-    "dl_score_pair_logits_workspace_bytes": (_z, [_i, _i, _i]),
-    "dl_score_pair_ranks_workspace_bytes": (_z, [_i, _i, _i]),
-    "dl_score_pair_logits": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _i, _P, _P, _z, _P]),
-    "dl_score_pair_ranks": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
-    "dl_score_pair_terms_workspace_bytes": (_z, [_i, _i, _i]),
-    "dl_score_pair_terms": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
-    "dl_score_topk_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _i, _P, _P, _i, _P, _P, _P, _P, _z, _P, _NF]),
-    "dl_score_ranks_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P, _z, _P, _NF]),
-    "dl_score_mine_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _i, _P, _P, _P, _P, _P, _P, _z, _P, _NF]),
-    "dl_score_pair_ranks_filtered": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _i, _P, _P, _P, _P, _z, _P, _NF]),
     "dl_score_links_supported": (_i, [_i, _i]),
     "dl_score_links_form": (_i, [_i, _i, _i, C.POINTER(C.c_int)]),
-    "dl_score_links_workspace_bytes": (_z, [_i, _i, _i]),
-    "dl_score_links_count": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _NF, _P, _z, _P, _P]),
-    "dl_score_links_fill": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _f, _NF, _P, _z, _P, C.c_int64, _P, _P, _P, _P]),
     "dl_score_scan_supported": (_i, [_i, _i, _i]),
-    "dl_score_topk_workspace_bytes_dtype": (_z, [_i, _i, _i, _i, _i, _i, _i]),
-    "dl_score_mine_workspace_bytes_dtype": (_z, [_i, _i, _i, _i, _i]),
-    "dl_score_pair_logits_workspace_bytes_dtype": (_z, [_i, _i, _i, _i]),
-    "dl_score_pair_ranks_workspace_bytes_dtype": (_z, [_i, _i, _i, _i]),
-    "dl_score_links_workspace_bytes_dtype": (_z, [_i, _i, _i, _i]),
-    "dl_score_topk_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _i, _i, _P, _P, _i, _P, _P, _P, _P, _z, _P, _NF]),
-    "dl_score_ranks_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P, _z, _P, _NF]),
-    "dl_score_mine_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _f, _i, _P, _P, _P, _P, _P, _P, _z, _P, _NF]),
-    "dl_score_pair_logits_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _i, _P, _P, _z, _P]),
-    "dl_score_pair_ranks_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _P, _i, _P, _P, _P, _P, _z, _P, _NF]),
-    "dl_score_pair_terms_workspace_bytes_dtype": (_z, [_i, _i, _i, _i]),
-    "dl_score_pair_terms_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _i, _P, _P, _P, _P, _z, _P]),
-    "dl_score_links_count_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _f, _NF, _P, _z, _P, _P]),
-    "dl_score_links_fill_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _f, _NF, _P, _z, _P, C.c_int64, _P, _P, _P, _P]),
     "dl_auc_pair_counts_supported": (_i, [_i, _i]),
     "dl_auc_pair_counts": (_i, [_P, _P, _i, _P, _i, _P, _P]),
     "dl_auc_pair_counts_add": (_i, [_P, _P, _i, _P, _i, _P, _P]),
@@ -168,6 +136,34 @@ EXPORTS = {
     "dl_route_aggregate_bwd": (_i, [_G, _P, _i, _i, _i, _f, _f, _P, _P, _P, _P, _P, _i, _P, _z, _P]),
     "dl_route_aggregate_bwd_scaled": (_i, [_G, _P, _i, _i, _i, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P, _z, _P]),
 }
+
+
+def _scan_rows(name: str, res, codes: list, at: int, filtered: bool = False) -> dict:
+    """The EXPORTS rows of one scan entry (or sizer) from the argument codes of its plain form, written once: ``name``;
+    ``name``_dtype, the same list with the dl_dtype behind its first ``at`` codes; and, where ``filtered``, ``name``_filtered,
+    the list plus the node filter — which the _dtype entry then takes last as well."""
+    rows = {name: (res, codes), name + "_dtype": (res, codes[:at] + [_i] + codes[at:] + [_NF] * filtered)}
+    if filtered:
+        rows[name + "_filtered"] = (res, codes + [_NF])
+    return rows
+
+
+_TAB = [_P, _P, _i, _i, _i, _f]                       # Z, H, N, K, d, t: how every scan entry starts
+_EX = [_P, _P]                                        # exclusion rowptr, col
+_WS = [_P, _z, _P]                                    # workspace, its size, stream
+_LINKS = _TAB + _EX + [_f, _NF, _P, _z, _P]           # ... min_logit, filter, workspace, its size, rowptr
+for _name, _codes, _filtered in (
+        ("topk", _TAB + [_P, _i, _i] + _EX + [_i, _P, _P, _P] + _WS, True),
+        ("ranks", _TAB + [_P, _i, _P, _P, _i] + _EX + [_P, _P] + _WS, True),
+        ("mine", _TAB + _EX + [_f, _i, _P, _P, _P, _P, _P] + _WS, True),
+        ("pair_ranks", _TAB + _EX + [_P, _i, _P, _P, _P] + _WS, True),
+        ("pair_logits", _TAB + [_P, _P, _i, _P] + _WS, False),
+        ("pair_terms", _TAB + [_P, _P, _i, _P, _P, _P] + _WS, False),
+        ("links_count", _LINKS + [_P], False),
+        ("links_fill", _LINKS + [C.c_int64, _P, _P, _P, _P], False)):
+    EXPORTS.update(_scan_rows("dl_score_" + _name, _i, _codes, 5, _filtered))
+for _name, _n in (("topk", 6), ("mine", 4), ("pair_logits", 3), ("pair_ranks", 3), ("pair_terms", 3), ("links", 3)):
+    EXPORTS.update(_scan_rows(f"dl_score_{_name}_workspace_bytes", _z, [_i] * _n, 3))
 
 DL_F32, DL_BF16 = 0, 1
 

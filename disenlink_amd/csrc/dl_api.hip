@@ -630,13 +630,19 @@ int dl_score_pair_logits(const float* Z, const float* H, int N, int K, int d, fl
     return dl_score_pair_logits_dtype(Z, H, N, K, d, DL_F32, t, a, b, n_pairs, logit, ws, ws_bytes, stream);
 }
 
-int dl_score_pair_logits_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* a,
-                               const int32_t* b, int n_pairs, float* logit, void* ws, size_t ws_bytes, void* stream) {
+// what the two scorers of given pairs check alike, up to their pointers (have_args; not looked at for n_pairs == 0, where
+// the entry returns DL_OK after this).  What follows stays with the entry: the workspace, under its own sizer's name.
+static int check_pair_args(int N, int K, int d, dl_dtype dtype, float t, int n_pairs, bool have_args) {
     if (int rc = check_scan_shape(PAIR_SCAN, N, K, d, dtype)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     DL_REQUIRE(n_pairs >= 0 && n_pairs <= (1 << 30), "n_pairs=%d outside 0..2^30", n_pairs);
+    return n_pairs == 0 ? DL_OK : check_scan_ptrs(PAIR_SCAN, have_args, nullptr, nullptr);
+}
+
+int dl_score_pair_logits_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* a,
+                               const int32_t* b, int n_pairs, float* logit, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_pair_args(N, K, d, dtype, t, n_pairs, Z && H && a && b && logit)) return rc;
     if (n_pairs == 0) return DL_OK;
-    if (int rc = check_scan_ptrs(PAIR_SCAN, Z && H && a && b && logit, nullptr, nullptr)) return rc;
     if (int rc = check_scan_ws(PAIR_SCAN, ws, ws_bytes, score_pair_logits_workspace_bytes(N, K, d, dtype),
                                "dl_score_pair_logits_workspace_bytes"))
         return rc;
@@ -654,15 +660,12 @@ int dl_score_pair_terms(const float* Z, const float* H, int N, int K, int d, flo
     return dl_score_pair_terms_dtype(Z, H, N, K, d, DL_F32, t, a, b, n_pairs, e, q, cum, ws, ws_bytes, stream);
 }
 
-// the checks of dl_score_pair_logits_dtype in its order; what is there of the outputs belongs to the pointers
+// any of e, q, cum may be NULL, so none of them counts among the arguments; all three NULL is refused on its own
 int dl_score_pair_terms_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* a,
                               const int32_t* b, int n_pairs, float* e, float* q, float* cum, void* ws, size_t ws_bytes,
                               void* stream) {
-    if (int rc = check_scan_shape(PAIR_SCAN, N, K, d, dtype)) return rc;
-    DL_REQUIRE(t != 0.0f, "temperature is 0");
-    DL_REQUIRE(n_pairs >= 0 && n_pairs <= (1 << 30), "n_pairs=%d outside 0..2^30", n_pairs);
+    if (int rc = check_pair_args(N, K, d, dtype, t, n_pairs, Z && H && a && b)) return rc;
     if (n_pairs == 0) return DL_OK;
-    if (int rc = check_scan_ptrs(PAIR_SCAN, Z && H && a && b, nullptr, nullptr)) return rc;
     DL_REQUIRE(e || q || cum, "NULL output: e, q and cum are all NULL");
     if (int rc = check_scan_ws(PAIR_SCAN, ws, ws_bytes, score_pair_logits_workspace_bytes(N, K, d, dtype),
                                "dl_score_pair_terms_workspace_bytes"))

@@ -1,0 +1,594 @@
+"""The all-pairs inference scans over libdisenlink_hip.so: top-k and ranks of a node's candidates, mining, the
+thresholded link graph, pair ranks, and the logits and per-factor terms of given pairs — with the exclusion sets and
+node-group rules they take.  Nothing here is differentiable.
+
+Every scan goes through ONE C entry, ``dl_score_<name>_dtype`` (the implementation; the plain and ``_filtered`` entries
+of the C ABI forward to it), sized by ``dl_score_<name>_workspace_bytes_dtype``; each writes its argument list once,
+in that entry's order.  ``ops`` re-exports the public names.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from collections import namedtuple
+
+import torch
+
+from . import _lib
+from ._dev import _empty, _need_cuda, _nkd, _stream, _ws
+from .graph import Graph
+
+
+# ---------------------------------------------------------------------- ranking of all candidates (dl_score_rank.hip)
+RANK_MAX_K = 128
+
+
+def exclusion_csr(exclude, n_nodes: int, device=None):
+    """Normalise an exclusion set to the CSR the ranking kernels take: (rowptr int32 [N+1], col int32) with ascending,
+    distinct columns per row, on ``device`` (default: where the set lives), or (None, None) for ``exclude=None``.
+    ``exclude``: a ``Graph`` (its stored entries), a dense [N,N] mask (entries != 0) or a ``(rows, cols)`` pair of index
+    sequences.  Duplicates collapse (``torch.unique`` on row * N + col)."""
+    if exclude is None:
+        return None, None
+    N = int(n_nodes)
+    if isinstance(exclude, Graph):
+        if exclude.n_nodes != N:
+            raise ValueError(f"exclusion graph has {exclude.n_nodes} nodes, expected {N}")
+        ptr = exclude.rowptr.to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(exclude.row_offset, exclude.row_offset + exclude.n_rows,
+                                                    device=ptr.device), ptr[1:] - ptr[:-1])
+        cols = exclude.col[:rows.numel()].to(torch.int64)
+    elif isinstance(exclude, (tuple, list)):
+        if len(exclude) != 2:
+            raise ValueError("an exclusion pair list is (rows, cols)")
+        rows, cols = (torch.as_tensor(v, device=device).reshape(-1).to(torch.int64) for v in exclude)
+        if rows.numel() != cols.numel():
+            raise ValueError("exclusion rows and cols differ in length")
+        if rows.numel() and (int(rows.min()) < 0 or int(cols.min()) < 0 or int(rows.max()) >= N or int(cols.max()) >= N):
+            raise ValueError("exclusion pair outside [0, N)")
+    else:
+        m = torch.as_tensor(exclude, device=device)
+        if m.dim() != 2 or tuple(m.shape) != (N, N):
+            raise ValueError(f"an exclusion mask must be [N, N] = [{N}, {N}], got {tuple(m.shape)}")
+        rows, cols = torch.nonzero(m, as_tuple=True)
+    dev = rows.device if device is None else torch.device(device)
+    key = torch.unique(rows.to(dev) * N + cols.to(dev))               # sorted: rows ascending, columns ascending in a row
+    r = torch.div(key, N, rounding_mode="floor")
+    rowptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=N), dim=0)
+    return rowptr.to(torch.int32), (key - r * N).to(torch.int32)
+
+
+def _scan_dtype(table_dtype) -> int:
+    """The dl_dtype of a scan's ``table_dtype`` keyword: fp32 (the default) or bf16."""
+    if table_dtype is torch.float32:
+        return _lib.DL_F32
+    if table_dtype is torch.bfloat16:
+        return _lib.DL_BF16
+    raise TypeError(f"table_dtype must be torch.float32 or torch.bfloat16, got {table_dtype!r}")
+
+
+def _rank_tables(Z, H, table_dtype=torch.float32):
+    """[N,K,d] tables on the device, 1 <= d <= 128 (dl_score_topk_supported).  ``table_dtype=torch.float32`` (the default):
+    fp32 tensors, nothing else.  ``torch.bfloat16``: Z and H are both bf16 tensors, used as they are, or both fp32 tensors,
+    rounded to nearest-even here exactly as the training step rounds its tables (``HotPathPairs``); the scans then run their
+    one-plane kernels (dl_score_*_dtype with DL_BF16)."""
+    if _scan_dtype(table_dtype) == _lib.DL_F32:
+        if Z.dtype != torch.float32 or H.dtype != torch.float32:
+            raise TypeError(f"the ranking kernels take fp32 tables, got {Z.dtype} / {H.dtype}")
+    else:
+        if Z.dtype != H.dtype or Z.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"table_dtype=torch.bfloat16 takes Z and H both bf16 or both fp32, got {Z.dtype} / {H.dtype}")
+        _need_cuda(Z, H)
+        Z, H = Z.to(torch.bfloat16), H.to(torch.bfloat16)
+    _need_cuda(Z, H)
+    N, K, d = _nkd(Z)
+    if tuple(H.shape) != tuple(Z.shape):
+        raise ValueError("Z and H differ in shape")
+    if N < 1 or not _lib.load().dl_score_topk_supported(K, d):
+        raise _lib.DisenlinkHipError(f"the ranking kernels serve N >= 1, K <= 64 and 1 <= d <= 128 (got N={N}, K={K}, d={d})")
+    return Z.contiguous(), H.contiguous(), N, K, d
+
+
+def _node_ids(ids, N: int, device, what: str) -> torch.Tensor:
+    ids = torch.as_tensor(ids, device=device).reshape(-1)
+    if ids.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what} must be integer node ids, got {ids.dtype}")
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= N):
+        raise ValueError(f"{what} outside [0, {N})")
+    return ids.to(torch.int32).contiguous()
+
+
+def _id_pairs(a, b, N: int, device, what_a: str, what_b: str):
+    """The two ends of listed pairs as ``_node_ids``, of one length."""
+    a, b = _node_ids(a, N, device, what_a), _node_ids(b, N, device, what_b)
+    if a.numel() != b.numel():
+        raise ValueError(f"{what_a} and {what_b} differ in length")
+    return a, b
+
+
+def _csr_args(rowptr, col, device):
+    if rowptr is None:
+        return None, None, ()
+    if col.numel() == 0:                                             # a valid address for an empty column array
+        col = torch.zeros(1, dtype=torch.int32, device=device)
+    return rowptr.data_ptr(), col.data_ptr(), (rowptr, col)
+
+
+class NodeFilter:
+    """A rule on node GROUPS for the candidate scans (dl_node_filter): ``groups`` [N] gives every node a group below
+    ``n_groups`` <= 64, and the boolean matrix ``allow`` [n_groups, n_groups] says whether a row of group g may take a
+    partner of group h — what an exclusion set could only say by listing O(N^2) pairs.  Prepared once, like
+    ``pair_exclusion``: the arrays are converted and moved, and ONE host read checks groups.max() < n_groups.
+    Ordered scans (``score_topk``, ``score_ranks``): the row is the query, the partner the candidate, ``allow`` may be
+    asymmetric.  Unordered scans (``score_mine``, ``score_pair_ranks``) need a symmetric rule (``symmetric``) and raise
+    ValueError otherwise; ``candidates`` carries a rule of its own for them (both endpoints in the pool)."""
+
+    def __init__(self, groups, allow, device=None, _pair_allow=None):
+        g = torch.as_tensor(groups)
+        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex:
+            raise ValueError(f"groups must be a 1-D integer array, got {tuple(g.shape)} {g.dtype}")
+        a = torch.as_tensor(allow).detach().to("cpu")
+        if a.dim() != 2 or a.shape[0] != a.shape[1] or not 1 <= a.shape[0] <= 64:
+            raise ValueError(f"allow must be [n_groups, n_groups] with 1 <= n_groups <= 64, got {tuple(a.shape)}")
+        a = a != 0
+        n = int(a.shape[0])
+        if g.numel():
+            lo, hi = (int(v) for v in torch.stack(torch.aminmax(g.to(torch.int64))).tolist())       # the one host read
+            if lo < 0 or hi >= n:
+                raise ValueError(f"groups outside [0, {n}): min {lo}, max {hi}")
+        self.symmetric = bool(torch.equal(a, a.t()))
+        pair = _pair_allow if _pair_allow is not None else a if self.symmetric else None      # the unordered scans' rule
+        dev = g.device if device is None else torch.device(device)
+        self.n_nodes, self.n_groups = int(g.numel()), n
+        self.groups = g.to(device=dev, dtype=torch.uint8).contiguous()
+        self.allow = a.to(dev)
+        self.pair_allow = None if pair is None else pair.to(dev)
+        self._words = self._pack(a).to(dev)
+        self._pair_words = None if pair is None else self._pack(pair).to(dev)
+
+    @staticmethod
+    def _pack(a: torch.Tensor) -> torch.Tensor:
+        """allow [n, n] bool -> the uint64 words of dl_node_filter (bit h of word g), as int64 bits."""
+        words = [sum(1 << h for h in range(a.shape[1]) if bool(a[g, h])) for g in range(a.shape[0])]
+        return torch.tensor([w - (1 << 64) if w >= (1 << 63) else w for w in words], dtype=torch.int64)
+
+    @staticmethod
+    def _dense_groups(groups):
+        g = torch.as_tensor(groups)
+        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex:
+            raise ValueError(f"groups must be a 1-D integer array, got {tuple(g.shape)} {g.dtype}")
+        n = int(g.max()) + 1 if g.numel() else 1
+        if n > 64 or (g.numel() and int(g.min()) < 0):
+            raise ValueError(f"a node filter takes groups 0..63, got {int(g.min())}..{n - 1}")
+        return g, max(n, 1)
+
+    @classmethod
+    def same(cls, groups, device=None) -> "NodeFilter":
+        """Only links between nodes of the same group."""
+        g, n = cls._dense_groups(groups)
+        return cls(g, torch.eye(n, dtype=torch.bool), device)
+
+    @classmethod
+    def different(cls, groups, device=None) -> "NodeFilter":
+        """Only links between nodes of different groups."""
+        g, n = cls._dense_groups(groups)
+        return cls(g, ~torch.eye(n, dtype=torch.bool), device)
+
+    @classmethod
+    def between(cls, mask_a, mask_b, both_ways: bool = True, device=None) -> "NodeFilter":
+        """Rows in ``mask_a`` take partners in ``mask_b`` (users -> items); with ``both_ways`` also the reverse, which
+        makes the rule symmetric.  The masks are boolean [N] and may overlap."""
+        ma, mb = torch.as_tensor(mask_a) != 0, torch.as_tensor(mask_b) != 0
+        if ma.dim() != 1 or ma.shape != mb.shape:
+            raise ValueError(f"the masks must be 1-D and of one length, got {tuple(ma.shape)} and {tuple(mb.shape)}")
+        g = ma.to(torch.uint8) + 2 * mb.to(ma.device).to(torch.uint8)      # 0 neither, 1 a, 2 b, 3 both
+        allow = torch.zeros(4, 4, dtype=torch.bool)
+        for r in range(4):
+            for c in range(4):
+                allow[r, c] = bool(r & 1 and c & 2) or bool(both_ways and r & 2 and c & 1)
+        return cls(g, allow, device)
+
+    @classmethod
+    def candidates(cls, mask, device=None) -> "NodeFilter":
+        """A fixed candidate pool (boolean [N]).  Ordered scans: any query takes only pool members.  Unordered scans: both
+        endpoints are in the pool."""
+        m = torch.as_tensor(mask) != 0
+        if m.dim() != 1:
+            raise ValueError(f"the mask must be 1-D, got {tuple(m.shape)}")
+        return cls(m.to(torch.uint8), torch.tensor([[False, True], [False, True]]), device,
+                   _pair_allow=torch.tensor([[False, False], [False, True]]))
+
+    def to(self, device) -> "NodeFilter":
+        """The same filter with its arrays on ``device`` (no check is repeated)."""
+        f = object.__new__(NodeFilter)
+        f.n_nodes, f.n_groups, f.symmetric = self.n_nodes, self.n_groups, self.symmetric
+        for name in ("groups", "allow", "pair_allow", "_words", "_pair_words"):
+            v = getattr(self, name)
+            setattr(f, name, None if v is None else v.to(device))
+        return f
+
+    def allowed(self, u, v, unordered: bool = False) -> torch.Tensor:
+        """bool per pair: may row u[i] take partner v[i]?  The kernels' rule in torch on index tensors (for tests and
+        callers that post-process; no hot path uses it).  ``unordered``: the rule of the unordered scans."""
+        a = self._pair_rule() if unordered else self.allow
+        u = torch.as_tensor(u, device=self.groups.device).long()
+        v = torch.as_tensor(v, device=self.groups.device).long()
+        return a[self.groups[u].long(), self.groups[v].long()]
+
+    def _pair_rule(self) -> torch.Tensor:
+        if self.pair_allow is None:
+            raise ValueError("an unordered scan needs a symmetric node filter (allow[g][h] == allow[h][g]); "
+                             "this one is asymmetric")
+        return self.pair_allow
+
+    def _n_pairs_allowed(self) -> torch.Tensor:
+        """int64 [1] on the filter's device: unordered pairs u < v the rule admits, from the group sizes."""
+        a = self._pair_rule().to(torch.int64)
+        c = torch.bincount(self.groups.long(), minlength=self.n_groups).to(torch.int64)
+        cross = (a * c[:, None] * c[None, :]).sum() - (a.diagonal() * c * c).sum()
+        return (cross // 2 + (a.diagonal() * (c * (c - 1) // 2)).sum()).reshape(1)
+
+    def _c_arg(self, N: int, device, unordered: bool):
+        """(byref(dl_node_filter), keep-alive) for a scan over N nodes on ``device``; raises before anything launches."""
+        words = self._words
+        if unordered:
+            self._pair_rule()
+            words = self._pair_words
+        if self.groups.device != torch.device(device):
+            raise ValueError(f"node filter on {self.groups.device}, tables on {device}: use NodeFilter.to(device)")
+        st = _lib.DlNodeFilter(self.groups.data_ptr(), self.n_groups, words.data_ptr())
+        return C.byref(st), (st, self.groups, words)
+
+
+def _filter_check(node_filter, Z, unordered: bool) -> None:
+    """The host-side refusals of a node filter, ahead of every other check and of any launch."""
+    if node_filter is None:
+        return
+    if not isinstance(node_filter, NodeFilter):
+        raise TypeError(f"node_filter must be an ops.NodeFilter, got {type(node_filter).__name__}")
+    if node_filter.n_nodes != int(Z.shape[0]):
+        raise ValueError(f"node filter of {node_filter.n_nodes} nodes, tables of {int(Z.shape[0])}")
+    if unordered:
+        node_filter._pair_rule()
+
+
+def _scan_tables(Z, H, node_filter, unordered: bool, table_dtype=torch.float32):
+    """How every scan starts: the refusals of the node filter, then of the tables -> (Z, H, N, K, d)."""
+    _filter_check(node_filter, Z, unordered)
+    return _rank_tables(Z, H, table_dtype)
+
+
+def _scan_buffers(excl, ws_bytes: int, device):
+    """-> (ex_rowptr, ex_col, workspace, keep-alive): the exclusion CSR ``excl`` = (rowptr, col) as C arguments and the
+    shared workspace of ``ws_bytes``."""
+    rp, cp, keep = _csr_args(*excl, device)
+    return rp, cp, _ws.get(max(256, int(ws_bytes)), device), keep
+
+
+def _filter_arg(node_filter, N: int, device, unordered: bool):
+    """(dl_node_filter* or None, keep-alive) for ``_scan_call``."""
+    return (None, ()) if node_filter is None else node_filter._c_arg(N, device, unordered)
+
+
+def _scan_call(name: str, *args) -> None:
+    """The one call path of the scans: the C entry dl_score_``name``_dtype with ``args`` in that entry's own order —
+    (Z, H, N, K, d, dt, t, ...), the rule of ``_filter_arg`` or None where the entry has it."""
+    entry = f"dl_score_{name}_dtype"
+    _lib.check(getattr(_lib.load(), entry)(*args), entry)
+
+
+def _scan_ws_bytes(name: str, N: int, K: int, d: int, dt: int, *rest) -> int:
+    """dl_score_``name``_workspace_bytes_dtype: the workspace of the scan on tables of type ``dt``."""
+    return int(getattr(_lib.load(), f"dl_score_{name}_workspace_bytes_dtype")(N, K, d, dt, *rest))
+
+
+def score_topk(Z, H, t: float, queries, k: int, exclude=None, exclude_self: bool = True, node_filter=None,
+               table_dtype=torch.float32):
+    """-> (index int64 [Q,k], logit f32 [Q,k], prob f32 [Q,k]): the k best candidates of every query node by the logit
+    s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), sorted (larger
+    first, +inf first, NaN last, equal logits by index), prob = sigmoid(logit).  Candidates: every node outside the
+    query's exclusion set (``exclusion_csr``) and, with ``exclude_self``, other than the query itself; rows with fewer than
+    k are padded with index -1 / NaN.  ``node_filter`` (a ``NodeFilter``): only candidates whose group the query's group
+    allows, on top of the exclusion.  Inference only (dl_score_topk: nothing of size Q x N is formed).
+    ``table_dtype=torch.bfloat16`` (here and in every scan below): the scan runs on bf16 tables — bf16 tensors as they are,
+    fp32 tensors rounded to nearest-even — with one matrix-core product per block instead of six and a third of the plane
+    workspace; it returns bit for bit what the fp32 scan returns on the rounded tables (``Z.bfloat16().float()``)."""
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, False, table_dtype)
+    k = int(k)
+    if not 1 <= k <= RANK_MAX_K:
+        raise ValueError(f"k={k} outside 1..{RANK_MAX_K}")
+    q = _node_ids(queries, N, Z.device, "queries")
+    Q = int(q.numel())
+    index = _empty((Q, k), torch.int64, Z.device)
+    logit = _empty((Q, k), torch.float32, Z.device)
+    prob = _empty((Q, k), torch.float32, Z.device)
+    if Q == 0:
+        return index, logit, prob
+    rp, cp, ws, _keep = _scan_buffers(exclusion_csr(exclude, N, Z.device), _scan_ws_bytes("topk", N, K, d, dt, Q, k, 0), Z.device)
+    nf, _keep_nf = _filter_arg(node_filter, N, Z.device, False)
+    _scan_call("topk", Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), q.data_ptr(), Q, k, rp, cp,
+               1 if exclude_self else 0, index.data_ptr(), logit.data_ptr(), prob.data_ptr(), ws.data_ptr(), ws.numel(),
+               _stream(), nf)
+    return index, logit, prob
+
+
+def score_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None, table_dtype=torch.float32):
+    """-> (greater, ties) int64 [P] for the target pairs (src[i], dst[i]): how many candidates of src[i] (every node other
+    than src[i] and outside its exclusion set; dst[i] itself is never counted, and is ranked even when it is in the
+    exclusion set — the filtered protocol) have a logit strictly above / equal to the target's, by value.  The target's
+    logit is the one the scan computes.  rank = 1 + greater + ties / 2 (metrics.ranking_metrics).  ``node_filter``: only
+    candidates the rule allows for src[i] are counted; a target is ranked whether or not it is allowed.  dl_score_ranks."""
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, False, table_dtype)
+    s, v = _id_pairs(src, dst, N, Z.device, "src", "dst")
+    T = int(s.numel())
+    greater = _empty(T, torch.int64, Z.device)
+    ties = _empty(T, torch.int64, Z.device)
+    if T == 0:
+        return greater, ties
+    order = torch.argsort(s, stable=True)                              # targets grouped by query node
+    queries, counts = torch.unique_consecutive(s[order], return_counts=True)
+    Q = int(queries.numel())
+    tptr = torch.zeros(Q + 1, dtype=torch.int32, device=Z.device)
+    tptr[1:] = torch.cumsum(counts, dim=0).to(torch.int32)
+    tdst = v[order].contiguous()
+    queries = queries.to(torch.int32).contiguous()
+    g_sorted = _empty(T, torch.int64, Z.device)
+    t_sorted = _empty(T, torch.int64, Z.device)
+    rp, cp, ws, _keep = _scan_buffers(exclusion_csr(exclude, N, Z.device), _scan_ws_bytes("topk", N, K, d, dt, Q, 0, T), Z.device)
+    nf, _keep_nf = _filter_arg(node_filter, N, Z.device, False)
+    _scan_call("ranks", Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), queries.data_ptr(), Q, tptr.data_ptr(),
+               tdst.data_ptr(), T, rp, cp, g_sorted.data_ptr(), t_sorted.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf)
+    greater[order] = g_sorted
+    ties[order] = t_sorted
+    return greater, ties
+
+
+# ---------------------------------------------------------------------- the graph's most likely missing links (dl_score_mine.hip)
+MINE_MAX_M = 65536
+MINE_MAX_N = 46340
+
+
+def _unordered_exclusion_csr(exclude, N: int, device):
+    """``exclusion_csr`` of an UNORDERED pair set: every listed pair (a, b), in either order, as column max(a, b) of row
+    min(a, b) — the only row dl_score_mine looks in."""
+    rowptr, col = exclusion_csr(exclude, N, device)
+    if rowptr is None:
+        return None, None
+    ptr = rowptr.to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(N, device=ptr.device), ptr[1:] - ptr[:-1])
+    cols = col.to(torch.int64)
+    return exclusion_csr((torch.minimum(rows, cols), torch.maximum(rows, cols)), N, device)
+
+
+def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf"), node_filter=None,
+               table_dtype=torch.float32):
+    """-> (src int32 [c], dst int32 [c], logit f32 [c], prob f32 [c]), c = min(m, eligible): the m best unordered pairs
+    src < dst of the WHOLE graph by the logit s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid
+    link_pred), sorted in ``score_topk``'s order (larger first, +inf first, equal logits by src * N + dst), with the bits
+    ``score_topk`` returns for query src, candidate dst.  ``exclude`` (a ``Graph``, a dense [N,N] mask or ``(rows, cols)``)
+    is taken as a set of unordered pairs; a pair is eligible iff its logit is >= ``min_logit`` (NaN never is).
+    1 <= m <= 65,536, N <= 46,340.  Inference only; nothing of size N x N is formed (dl_score_mine), and the one host read
+    is that of the count, at the very end.  ``node_filter`` (a symmetric ``NodeFilter``): only pairs whose groups the rule
+    allows, on top of the exclusion and the floor."""
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
+    m = int(m)
+    rp, cp, ws, _keep = _scan_buffers(_unordered_exclusion_csr(exclude, N, Z.device), _scan_ws_bytes("mine", N, K, d, dt, m),
+                                      Z.device)
+    nf, _keep_nf = _filter_arg(node_filter, N, Z.device, True)
+    src = _empty(max(m, 0), torch.int32, Z.device)
+    dst = _empty(max(m, 0), torch.int32, Z.device)
+    logit = _empty(max(m, 0), torch.float32, Z.device)
+    prob = _empty(max(m, 0), torch.float32, Z.device)
+    count = _empty(1, torch.int64, Z.device)
+    _scan_call("mine", Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), rp, cp, float(min_logit), m, src.data_ptr(),
+               dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf)
+    c = int(count.item())
+    return src[:c], dst[:c], logit[:c], prob[:c]
+
+
+# ---------------------------------------------------------------------- every pair above a floor, as a CSR (DEG / FILL scans)
+LINKS_MAX_N = MINE_MAX_N
+
+
+def _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype=torch.float32):
+    """The count pass of ``score_links``: -> (rowptr int64 [N+1] on the device, the arguments the fill pass shares with it,
+    keep-alive)."""
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
+    if N > LINKS_MAX_N:
+        raise ValueError(f"N={N} above {LINKS_MAX_N} (the tile-pair walk of dl_score_mine)")
+    excl = _csr_args(*_unordered_exclusion_csr(exclude, N, Z.device), Z.device)
+    nf, _keep_nf = _filter_arg(node_filter, N, Z.device, True)
+    # a workspace of its own, held across the two calls: the shared grow-only buffer may be handed out (and, under DL_POISON,
+    # refilled) in between, and the fill pass reads the planes and the cell offsets the count pass left
+    ws = _empty(max(256, _scan_ws_bytes("links", N, K, d, dt)), torch.uint8, Z.device)
+    rowptr = _empty(N + 1, torch.int64, Z.device)
+    head = (Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), excl[0], excl[1], float(min_logit), nf, ws.data_ptr(), ws.numel(),
+            rowptr.data_ptr())
+    _scan_call("links_count", *head, _stream())
+    return rowptr, head, (Z, H, excl, _keep_nf, ws)
+
+
+def score_links(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32):
+    """-> (rowptr int64 [N+1], col int32 [nnz], logit f32 [nnz], prob f32 [nnz]): the predicted graph, EVERY unordered pair
+    whose logit s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred) reaches ``min_logit``, as a
+    symmetric CSR over all N nodes — each pair as (u, v) and as (v, u) with the same bits, columns ascending within a row,
+    prob = sigmoid(logit).  Eligibility is ``score_mine``'s without m: u != v, outside ``exclude`` (a ``Graph``, a dense
+    [N,N] mask or ``(rows, cols)``, taken as unordered pairs), allowed by ``node_filter`` (a symmetric ``NodeFilter``), NaN
+    never; the bits are those of ``score_pair_logits(min(u, v), max(u, v))``.  N <= 46,340, fp32 or bf16 tables.  Inference only;
+    nothing of size N x N is formed (dl_score_links_count / dl_score_links_fill: two scans), there is no cap on nnz, and the
+    one host read is that of rowptr[N], between the scans, to allocate the outputs.  Same bits on every call."""
+    rowptr, head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
+    nnz = int(rowptr[-1].item())                                      # the one host read
+    dev = rowptr.device
+    col = _empty(nnz, torch.int32, dev)
+    logit = _empty(nnz, torch.float32, dev)
+    prob = _empty(nnz, torch.float32, dev)
+    _scan_call("links_fill", *head, nnz, col.data_ptr(), logit.data_ptr(), prob.data_ptr(), _stream())
+    return rowptr, col, logit, prob
+
+
+def score_link_degrees(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32):
+    """-> int64 [N]: the predicted degree of every node, i.e. how many partners ``score_links`` would list for it — the
+    count pass alone (dl_score_links_count): one scan, no host read, no fill."""
+    rowptr, _head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
+    return rowptr[1:] - rowptr[:-1]
+
+
+# ---------------------------------------------------------------------- where given pairs stand among ALL pairs (COUNT scan)
+def _order_keys(logit: torch.Tensor) -> torch.Tensor:
+    """The scans' total order of fp32 values as int64 keys in [0, 2^32): NaN -> 0, -0 as +0, larger value = larger key."""
+    x = torch.where(logit == 0, torch.zeros_like(logit), logit)
+    b = x.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    key = torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b + 0x80000000)
+    return torch.where(torch.isnan(logit), torch.zeros_like(key), key)
+
+
+PairExclusion = namedtuple("PairExclusion", ["n_nodes", "rowptr", "col", "key", "n_pairs"])
+
+
+def pair_exclusion(exclude, N: int, device) -> PairExclusion:
+    """An exclusion set normalised once for ``score_pair_ranks`` (a caller with a fixed graph passes the result as
+    ``exclude`` and skips the normalisation per call): the CSR of ``_unordered_exclusion_csr``, its sorted pair keys
+    u * N + v and the int64 [1] number of pairs u < v among them ((u, u) entries exclude nothing)."""
+    rowptr, col = _unordered_exclusion_csr(exclude, N, device)
+    if rowptr is None:
+        return PairExclusion(N, None, None, None, torch.zeros(1, dtype=torch.int64, device=device))
+    ptr = rowptr.to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(N, device=ptr.device), ptr[1:] - ptr[:-1])
+    cols = col.to(torch.int64)
+    return PairExclusion(N, rowptr, col, rows * N + cols, (cols > rows).sum().reshape(1))
+
+
+def _score_pairs(name: str, Z, H, t: float, a, b, table_dtype, per_factor: bool):
+    """What ``score_pair_logits`` and ``score_pair_terms`` share: tables, the two id arrays of one length, the fp32 outputs
+    (three [P, K] arrays if ``per_factor``, else one [P]), the workspace and the call of dl_score_``name``_dtype (none for
+    P = 0) -> the list of outputs."""
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _rank_tables(Z, H, table_dtype)
+    a, b = _id_pairs(a, b, N, Z.device, "a", "b")
+    P = int(a.numel())
+    out = [_empty((P, K) if per_factor else (P,), torch.float32, Z.device) for _ in range(3 if per_factor else 1)]
+    if P:
+        ws = _ws.get(max(256, _scan_ws_bytes(name, N, K, d, dt)), Z.device)
+        _scan_call(name, Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), a.data_ptr(), b.data_ptr(), P,
+                   *(o.data_ptr() for o in out), ws.data_ptr(), ws.numel(), _stream())
+    return out
+
+
+def score_pair_logits(Z, H, t: float, a, b, table_dtype=torch.float32):
+    """-> logit f32 [P]: s(a[i], b[i]) with row a[i] as the A operand, from the products of the scans — the bits
+    ``score_topk`` returns for query a[i], candidate b[i] (dl_score_pair_logits; a -0 comes back as +0, as the keyed
+    outputs of ``score_topk`` and ``score_mine`` report it)."""
+    (logit,) = _score_pairs("pair_logits", Z, H, t, a, b, table_dtype, per_factor=False)
+    return torch.where(logit == 0, torch.zeros_like(logit), logit)
+
+
+class PairTerms(namedtuple("PairTerms", ["e", "q", "cum"])):
+    """The per-factor terms of scored pairs (``score_pair_terms``), fp32 [P, K] each: ``e`` = exp(z_k[a].z_k[b] / t),
+    ``q`` = h_k[a].h_k[b], ``cum`` = the scan's running sum after factor k (its last column is the logit)."""
+    __slots__ = ()
+
+    @property
+    def logit(self) -> torch.Tensor:
+        """f32 [P]: ``cum[:, -1]`` with a -0 reported as +0 — the bits the scans report for the pair."""
+        x = self.cum[:, -1]
+        return torch.where(x == 0, torch.zeros_like(x), x)
+
+    @property
+    def contrib(self) -> torch.Tensor:
+        """f32 [P, K]: what factor k added to the sum: cum[:, 0], then cum[:, k] - cum[:, k-1]."""
+        out = self.cum.clone()
+        out[:, 1:] -= self.cum[:, :-1]
+        return out
+
+    @property
+    def factor(self) -> torch.Tensor:
+        """int64 [P]: the factor with the largest contribution (the first of equals), -1 where the row holds a NaN."""
+        c = self.contrib
+        top = c.max(dim=1, keepdim=True).values
+        first = (c == top).to(torch.int64).argmax(dim=1)          # argmax of 0/1 values: the first 1
+        return torch.where(torch.isnan(c).any(dim=1), torch.full_like(first, -1), first)
+
+
+def score_pair_terms(Z, H, t: float, a, b, table_dtype=torch.float32) -> PairTerms:
+    """-> PairTerms(e, q, cum), fp32 [P, K] each: WHY the pair (a[i], b[i]) scores as it does — per factor k the routing
+    weight e = exp(z_k[a].z_k[b] / t), the Gram product q = h_k[a].h_k[b] and the running sum cum of the very pass
+    ``score_pair_logits`` runs (dl_score_pair_terms: same gathers and products, row a[i] as the A operand).
+    ``cum[:, -1]`` has the bits ``score_pair_logits`` returns, hence those ``score_topk``, ``score_mine`` and
+    ``score_links`` list (``.logit``: with their -0 -> +0); ``cum[:, k]`` is the logit of the tables cut to factors 0..k.
+    ``.contrib`` and ``.factor`` name the factor that makes the link.  Inference only."""
+    return PairTerms(*_score_pairs("pair_terms", Z, H, t, a, b, table_dtype, per_factor=True))
+
+
+def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter=None, table_dtype=torch.float32):
+    """The hook of the tests and of tools/pair_rank_time.py, not part of the interface: ``score_pair_ranks`` and, as a fifth
+    value, the int64 [1] DEVICE count of the candidates the scan counted, which equals N (N - 1) / 2 - |excluded pairs| (the
+    one exact check that works where nothing can be enumerated; under a ``node_filter``: the pairs the rule allows, less
+    the excluded ones among them)."""
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
+    dev = Z.device
+    s, v = _id_pairs(src, dst, N, dev, "src", "dst")
+    if bool((s == v).any()):
+        raise ValueError("a target is a self pair (src[i] == dst[i])")
+    T = int(s.numel())
+    ex = exclude if isinstance(exclude, PairExclusion) else pair_exclusion(exclude, N, dev)
+    if ex.n_nodes != N:
+        raise ValueError(f"exclusion set of {ex.n_nodes} nodes, expected {N}")
+    rowptr, col, ex_key = ex.rowptr, ex.col, ex.key
+    total = N * (N - 1) // 2 - ex.n_pairs
+    nf, _keep_nf = _filter_arg(node_filter, N, dev, True)
+    if node_filter is not None:                                       # allowed pairs, less the excluded ones among them
+        total = node_filter._n_pairs_allowed()
+        if ex_key is not None and ex_key.numel():
+            er, ec = torch.div(ex_key, N, rounding_mode="floor"), ex_key % N
+            total = total - ((ec > er) & node_filter.allowed(er, ec, unordered=True)).sum().reshape(1)
+    if T == 0:
+        e = torch.zeros(0, dtype=torch.int64, device=dev)
+        return e, e.clone(), torch.zeros(0, dtype=torch.float32, device=dev), e.clone(), total
+    lo, hi = torch.minimum(s, v).contiguous(), torch.maximum(s, v).contiguous()
+    logit = score_pair_logits(Z, H, t, lo, hi, table_dtype)           # the smaller endpoint as the A operand
+    key = _order_keys(logit)
+    ksorted, order = torch.sort(key, stable=True)
+    first = torch.searchsorted(ksorted, ksorted)                      # first place of each target's value
+    tord = torch.where(ksorted >= 0x80000000, ksorted - 0x100000000, ksorted).to(torch.int32).contiguous()      # uint32 bits
+    above = _empty(T + 1, torch.int64, dev)
+    equal = _empty(T + 1, torch.int64, dev)
+    counted = _empty(1, torch.int64, dev)
+    rp, cp, ws, _keep = _scan_buffers((rowptr, col), _scan_ws_bytes("pair_ranks", N, K, d, dt), dev)
+    _scan_call("pair_ranks", Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), rp, cp, tord.data_ptr(), T, above.data_ptr(),
+               equal.data_ptr(), counted.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf)
+    cs = torch.cumsum(above, dim=0)
+    g_sorted = cs[T] - cs[:T]                                         # candidates that found more than p targets below them
+    t_sorted = equal[first]
+    in_c = torch.ones(T, dtype=torch.int64, device=dev)               # the target itself is a candidate unless excluded
+    if rowptr is not None and ex_key.numel():
+        tkey = lo.to(torch.int64) * N + hi.to(torch.int64)
+        pos = torch.searchsorted(ex_key, tkey).clamp_(max=ex_key.numel() - 1)
+        in_c = (ex_key[pos] != tkey).to(torch.int64)
+    if node_filter is not None:                                       # ... and only where the rule allows it
+        in_c = in_c * node_filter.allowed(lo, hi, unordered=True).to(torch.int64)
+    greater = torch.empty(T, dtype=torch.int64, device=dev)
+    ties = torch.empty(T, dtype=torch.int64, device=dev)
+    greater[order] = g_sorted
+    ties[order] = t_sorted
+    return greater, ties - in_c, logit, total - in_c, counted
+
+
+def score_pair_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None, table_dtype=torch.float32):
+    """-> (greater int64, ties int64, logit f32, n_others int64), each [T]: where the unordered target pairs
+    {src[i], dst[i]} (either orientation; duplicates allowed; no self pairs) stand among ALL unordered pairs u < v < N of
+    the graph outside ``exclude`` (a set of unordered pairs, as in ``score_mine``, or a prepared ``pair_exclusion``).  logit[i] is formed with the smaller
+    endpoint as the A operand (the bits ``score_mine`` lists); greater / ties count the candidates other than the target
+    itself whose logit is strictly above / equal by value (+inf above everything finite, -0 equal to +0, NaN below
+    everything and equal only to NaN).  The filtered protocol of ``score_ranks``: a target is ranked whether or not it is
+    excluded, other targets count as candidates unless excluded.  n_others[i] = candidates - [target i is one], so
+    greater + ties <= n_others; rank = 1 + greater + ties / 2 (metrics.global_ranking_metrics).  Inference only; one
+    target pass and ONE scan (dl_score_pair_logits, dl_score_pair_ranks), nothing of size N x N, no cap at N = 46,340.
+    ``node_filter`` (a symmetric ``NodeFilter``): the candidates are the pairs the rule allows outside ``exclude``; a target
+    is ranked whether or not it is allowed."""
+    return score_pair_ranks_counted(Z, H, t, src, dst, exclude, node_filter, table_dtype)[:4]

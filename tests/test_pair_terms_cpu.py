@@ -88,7 +88,7 @@ def test_refusals_of_the_c_entry_are_those_of_the_pair_logits():
 
 
 def test_ops_refusals(monkeypatch):
-    from disenlink_amd import ops
+    from disenlink_amd import ops, scans
     Z, H = torch.randn(10, 2, 32), torch.randn(10, 2, 32)
     ids = torch.arange(4)
     with pytest.raises(_lib.DisenlinkHipError, match="only on the GPU"):        # there is no CPU path
@@ -103,7 +103,7 @@ def test_ops_refusals(monkeypatch):
         with pytest.raises(TypeError, match="table_dtype"):
             ops.score_pair_terms(Z, H, 1.0, ids, ids, table_dtype=bad)
     # the checks behind the device check, which come before anything is launched: reached here with the device check lifted
-    monkeypatch.setattr(ops, "_need_cuda", lambda *tensors: None)
+    monkeypatch.setattr(scans, "_need_cuda", lambda *tensors: None)
     for call in (ops.score_pair_terms, ops.score_pair_logits):        # the same checks in both
         with pytest.raises(ValueError, match="differ in length"):
             call(Z, H, 1.0, ids, ids[:3])

@@ -22,6 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from disenlink_amd import _lib, ops  # noqa: E402
+from disenlink_amd.scans import _order_keys, _unordered_exclusion_csr  # noqa: E402
 from mine_time import interleaved, peak_of, tables  # noqa: E402
 
 
@@ -50,7 +51,7 @@ def scans(Z, H, N, K, d, known, src, dst):
         _lib.check(rc, "dl_score_mine")
 
     lo, hi = torch.minimum(src, dst), torch.maximum(src, dst)
-    key = torch.sort(ops._order_keys(ops.score_pair_logits(Z, H, 1.0, lo, hi))).values
+    key = torch.sort(_order_keys(ops.score_pair_logits(Z, H, 1.0, lo, hi))).values
     tord = torch.where(key >= 0x80000000, key - 0x100000000, key).to(torch.int32).contiguous()
     T = int(tord.numel())
     above, equal = (torch.empty(T + 1, dtype=torch.int64, device=dev) for _ in range(2))
@@ -70,7 +71,7 @@ def scans(Z, H, N, K, d, known, src, dst):
                 ops._stream())
         _lib.check(lib.dl_score_topk(*args) if nf is None else lib.dl_score_topk_filtered(*args, nf), "dl_score_topk")
 
-    unordered = lambda pairs: ops._unordered_exclusion_csr(pairs, N, dev)          # noqa: E731
+    unordered = lambda pairs: _unordered_exclusion_csr(pairs, N, dev)          # noqa: E731
     ordered = lambda pairs: ops.exclusion_csr((torch.cat([pairs[0], pairs[1]]), torch.cat([pairs[1], pairs[0]])), N, dev)    # noqa: E731
     return {"score_mine": (mine, unordered, ncand), "score_pair_ranks": (pair_ranks, unordered, ncand), "score_topk": (topk, ordered, None)}
 

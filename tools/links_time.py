@@ -22,7 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from disenlink_amd import _lib, ops  # noqa: E402
+from disenlink_amd import _lib, ops, scans  # noqa: E402
 from mine_time import interleaved, peak_of, tables  # noqa: E402
 
 
@@ -44,7 +44,7 @@ def shape(name, N, K, d, seed, seconds, out):
     g = torch.Generator(device="cuda").manual_seed(seed + 100)
     rows = torch.randint(0, N, (25 * N,), device="cuda", generator=g)
     cols = torch.randint(0, N, (25 * N,), device="cuda", generator=g)
-    ex = ops._unordered_exclusion_csr((rows, cols), N, Z.device)      # the CSR once, as a caller with a fixed graph would
+    ex = scans._unordered_exclusion_csr((rows, cols), N, Z.device)      # the CSR once, as a caller with a fixed graph would
     ptr = ex[0].to(torch.int64)
     ex_pairs = (torch.repeat_interleave(torch.arange(N, device="cuda"), ptr[1:] - ptr[:-1]), ex[1].to(torch.int64))
     known = int((ex_pairs[0] < ex_pairs[1]).sum())

@@ -18,7 +18,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from disenlink_amd import _lib, ops  # noqa: E402
+from disenlink_amd import _lib, ops, scans  # noqa: E402
 
 
 def tables(N, K, d, seed):
@@ -68,7 +68,7 @@ def shape(name, N, K, d, seed, seconds, out):
     g = torch.Generator(device="cuda").manual_seed(seed + 100)
     rows = torch.randint(0, N, (25 * N,), device="cuda", generator=g)
     cols = torch.randint(0, N, (25 * N,), device="cuda", generator=g)
-    ex = ops._unordered_exclusion_csr((rows, cols), N, Z.device)      # the CSR once, as a caller with a fixed graph would
+    ex = scans._unordered_exclusion_csr((rows, cols), N, Z.device)      # the CSR once, as a caller with a fixed graph would
     ptr = ex[0].to(torch.int64)
     ex_pairs = (torch.repeat_interleave(torch.arange(N, device="cuda"), ptr[1:] - ptr[:-1]), ex[1].to(torch.int64))
     for m in (100, 10000):

@@ -23,7 +23,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from disenlink_amd import _lib, ops  # noqa: E402
+from disenlink_amd import _lib, ops, scans  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from mine_time import interleaved, peak_of, tables  # noqa: E402
 
@@ -36,7 +36,7 @@ def shape(name, N, K, d, seed, src, dst, known, seconds, out, dense_sort=True):
     lo, hi = torch.minimum(src, dst), torch.maximum(src, dst)
     T = int(src.numel())
     lib = _lib.load()
-    tord = torch.sort(ops._order_keys(ops.score_pair_logits(Z, H, 1.0, lo, hi))).values
+    tord = torch.sort(scans._order_keys(ops.score_pair_logits(Z, H, 1.0, lo, hi))).values
     tord = torch.where(tord >= 0x80000000, tord - 0x100000000, tord).to(torch.int32).contiguous()
     cnt = torch.empty(2 * (T + 1) + 1, dtype=torch.int64, device="cuda")
     ws = ops._ws.get(int(lib.dl_score_pair_ranks_workspace_bytes(N, K, d)), Z.device)

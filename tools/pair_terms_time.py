@@ -24,7 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from disenlink_amd import _lib, ops  # noqa: E402
+from disenlink_amd import _lib, ops, scans  # noqa: E402
 from links_time import floor_for  # noqa: E402
 from mine_time import interleaved, tables  # noqa: E402
 
@@ -92,7 +92,7 @@ def links_case(name, Z, H, seed, seconds, out):
     g = torch.Generator(device="cuda").manual_seed(seed + 100)
     rows = torch.randint(0, N, (25 * N,), device="cuda", generator=g)
     cols = torch.randint(0, N, (25 * N,), device="cuda", generator=g)
-    ex = ops._unordered_exclusion_csr((rows, cols), N, Z.device)
+    ex = scans._unordered_exclusion_csr((rows, cols), N, Z.device)
     ptr = ex[0].to(torch.int64)
     ex_pairs = (torch.repeat_interleave(torch.arange(N, device="cuda"), ptr[1:] - ptr[:-1]), ex[1].to(torch.int64))
     known = int((ex_pairs[0] < ex_pairs[1]).sum())
