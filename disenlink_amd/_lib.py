@@ -164,6 +164,14 @@ for _name, _codes, _filtered in (
     EXPORTS.update(_scan_rows("dl_score_" + _name, _i, _codes, 5, _filtered))
 for _name, _n in (("topk", 6), ("mine", 4), ("pair_logits", 3), ("pair_ranks", 3), ("pair_terms", 3), ("links", 3)):
     EXPORTS.update(_scan_rows(f"dl_score_{_name}_workspace_bytes", _z, [_i] * _n, 3))
+# the budgeted link graph has the _dtype entries only: ... N, K, d, dtype, t, exclusion, min_logit, m (64-bit), filter, ...
+_LINKS_TOP = _TAB[:5] + [_i, _f] + _EX + [_f, C.c_int64, _NF, _P, _z, _P]
+EXPORTS.update({
+    "dl_score_links_top_form": (_i, [_i, _i, _i, C.POINTER(C.c_int)]),
+    "dl_score_links_top_workspace_bytes_dtype": (_z, [_i] * 4),
+    "dl_score_links_top_count_dtype": (_i, _LINKS_TOP + [_P]),
+    "dl_score_links_top_fill_dtype": (_i, _LINKS_TOP + [C.c_int64, _P, _P, _P, _P]),
+})
 
 DL_F32, DL_BF16 = 0, 1
 
@@ -298,6 +306,18 @@ def score_links_form(N: int, K: int, d: int) -> dict:
     out = (C.c_int * len(SCORE_LINKS_FORM))()
     check(load().dl_score_links_form(N, K, d, out), "dl_score_links_form")
     return dict(zip(SCORE_LINKS_FORM, out))
+
+
+SCORE_LINKS_TOP_FORM = SCORE_LINKS_FORM + ("scans_offset",)
+
+
+def score_links_top_form(N: int, K: int, d: int) -> dict:
+    """The budgeted link graph's plan for this problem under the current DL_MINE_TILES (dl_score_links_top_form): the
+    fields of ``score_links_form`` with ``scans`` = histogram scans at most + count + fill, and where in the aligned
+    workspace the number of histogram scans that ran stands."""
+    out = (C.c_int * len(SCORE_LINKS_TOP_FORM))()
+    check(load().dl_score_links_top_form(N, K, d, out), "dl_score_links_top_form")
+    return dict(zip(SCORE_LINKS_TOP_FORM, out))
 
 
 def config_reload() -> None:

@@ -604,6 +604,49 @@ int dl_score_links_fill_dtype(const void* Z, const void* H, int N, int K, int d,
                             (hipStream_t)stream);
 }
 
+// ---- the budgeted link graph: the links entries' checklist, and m
+int dl_score_links_top_form(int N, int K, int d, int* out) {
+    if (int rc = check_scan_shape(LINKS_SCAN, N, K, d)) return rc;
+    DL_REQUIRE(out != nullptr, "out is NULL");
+    score_links_top_form(N, d, out);
+    return DL_OK;
+}
+
+size_t dl_score_links_top_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype) {
+    return scan_shape_ok(LINKS_SCAN, N, K, d) && known_dtype(dtype) ? score_links_top_workspace_bytes(N, K, d, dtype) : 0;
+}
+
+static int check_links_top_args(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* ex_rowptr,
+                                const int32_t* ex_col, int64_t m, const dl_node_filter* filter, const void* ws, size_t ws_bytes,
+                                const int64_t* rowptr) {
+    if (int rc = check_scan_shape(LINKS_SCAN, N, K, d, dtype)) return rc;
+    if (int rc = check_filter(filter)) return rc;
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    DL_REQUIRE(m >= 1, "m=%lld below 1", (long long)m);
+    if (int rc = check_scan_ptrs(LINKS_SCAN, Z && H && rowptr, ex_rowptr, ex_col)) return rc;
+    return check_scan_ws(LINKS_SCAN, ws, ws_bytes, score_links_top_workspace_bytes(N, K, d, dtype),
+                         "dl_score_links_top_workspace_bytes_dtype");
+}
+
+int dl_score_links_top_count_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                                   const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit, int64_t m,
+                                   const dl_node_filter* filter, void* ws, size_t ws_bytes, int64_t* rowptr, void* stream) {
+    if (int rc = check_links_top_args(Z, H, N, K, d, dtype, t, ex_rowptr, ex_col, m, filter, ws, ws_bytes, rowptr)) return rc;
+    return score_links_top_count(Z, H, dtype, N, K, d, t, ex_rowptr, ex_col, min_logit, (long long)m, filter, ws, rowptr,
+                                 (hipStream_t)stream);
+}
+
+int dl_score_links_top_fill_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                                  const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit, int64_t m,
+                                  const dl_node_filter* filter, void* ws, size_t ws_bytes, const int64_t* rowptr, int64_t nnz,
+                                  int32_t* col, float* logit, float* prob, void* stream) {
+    if (int rc = check_links_top_args(Z, H, N, K, d, dtype, t, ex_rowptr, ex_col, m, filter, ws, ws_bytes, rowptr)) return rc;
+    DL_REQUIRE(nnz >= 0, "nnz=%lld is negative", (long long)nnz);
+    DL_REQUIRE(nnz == 0 || (col && logit), "NULL output");
+    return score_links_top_fill(dtype, N, K, d, t, ex_rowptr, ex_col, min_logit, filter, ws, rowptr, (long long)nnz, col, logit, prob,
+                                (hipStream_t)stream);
+}
+
 int dl_score_pair_ranks_supported(int K, int d) { return score_rank_supported(K, d) ? 1 : 0; }
 
 int dl_score_pair_ranks_form(int N, int K, int d, int n_targets, int* out) {

@@ -116,6 +116,17 @@ int score_links_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* e
                      const dl_node_filter* filter, void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit,
                      float* prob, hipStream_t st);
 
+// the m best unordered pairs, any m, as that CSR (dl_score_mine.hip: the select of score_mine, then the link scans under the
+// threshold key it left in the workspace): the limits of score_links
+void score_links_top_form(int N, int d, int* out);
+size_t score_links_top_workspace_bytes(int N, int K, int d, dl_dtype dt = DL_F32);
+int score_links_top_count(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* ex_rowptr,
+                          const int32_t* ex_col, float min_logit, long long m, const dl_node_filter* filter, void* ws, int64_t* rowptr,
+                          hipStream_t st);
+int score_links_top_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit,
+                         const dl_node_filter* filter, void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit,
+                         float* prob, hipStream_t st);
+
 // tie-averaged AUC counts (dl_metrics.hip)
 bool auc_counts_supported(int n_pos, int n_neg);           // the smaller class fits the LDS
 int auc_pair_counts(const float* score, const int64_t* pos_idx, int n_pos, const int64_t* neg_idx, int n_neg,

@@ -40,6 +40,13 @@
 // value that passed goes to slot rowptr[u] + cnt[u][ct] + (passed columns of its row below v), and likewise for (v, u);
 // a slot >= the caller's nnz is not written.  The walk of the tile pairs and its cap N <= 46,340 are the mining's.
 //
+// Budgeted link graph (dl_score_links_top_count / _fill, modes DEG_TOP and FILL_TOP): the m best candidates, ANY m, as that
+// CSR.  The radix select above runs unchanged (its counts are 32-bit and the candidates number < 2^32, so it finds the m-th
+// key for every m; only EMIT and the ordering need m <= 65,536, and neither runs) and leaves the threshold key in
+// State::prefix; the link modes then pass a pair only if its 64-bit key also reaches that threshold.  Keys are distinct, so
+// exactly min(m, candidates) pairs pass: the set dl_score_mine would list without its cap, a class of tied logits cut where
+// it cuts it (smaller u N + v first).  Nothing is read back between the select and the count.
+//
 // Node groups (the FILT instantiations; dl_score_mine_filtered, dl_score_pair_ranks_filtered): a symmetric rule on the groups
 // of u and v, formed into the row mask ahead of the exclusion; a candidate passes both.  The epilogues do not change.
 //
@@ -63,7 +70,7 @@ constexpr int SDC = SPLIT_COLS, SLD = SPLIT_PITCH;
 constexpr int BINS = 2048;                 // the widest digit
 constexpr int PASSES = 6;
 constexpr int MAX_M = 65536;
-enum { HIST = 0, EMIT = 1, COUNT = 2, DEG = 3, FILL = 4 };
+enum { HIST = 0, EMIT = 1, COUNT = 2, DEG = 3, FILL = 4, DEG_TOP = 5, FILL_TOP = 6 };      // *_TOP: DEG / FILL under the selected key
 constexpr int SEPS = 4096;                 // COUNT: first-level separators of the sorted targets, in LDS
 
 // the digits of the key, from the top: value 11 + 11 + 10 bits, index 11 + 11 + 10 bits
@@ -103,7 +110,8 @@ struct ScanArgs {
     float min_logit;                           // the floor (COUNT has none)
     int pairs, per_wg;                         // tile pairs, tile pairs per workgroup
     FilterArgs filt;                           // FILT: the node-group rule (dl_tiles.h); symmetric, so the u row decides
-    State* state;                              // HIST / EMIT / COUNT: the selection state and the count of scans; DEG / FILL: none
+    State* state;                              // HIST / EMIT / COUNT: the selection state and the count of scans; DEG / FILL: none;
+                                               // DEG_TOP / FILL_TOP: the state the select left (prefix = the threshold key)
     SelectArgs sel;
     CountArgs cnt;
     LinkArgs link;
@@ -218,7 +226,9 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     unsigned* bins = exm + TT * 4;                              // HIST: [BINS]; COUNT: [SEPS] separators; DEG / FILL: masks, bases
     u64* fal = reinterpret_cast<u64*>(bins + (MODE == COUNT ? SEPS : BINS));           // FILT: allow [64] | cgrp [TT] | rgrp [TT]
     unsigned char* cgrp = reinterpret_cast<unsigned char*>(fal + 64);
-    constexpr bool LINKS = MODE == DEG || MODE == FILL;        // dl_score_links: no selection state, masks where the bins are
+    constexpr bool KEYED = MODE == DEG_TOP || MODE == FILL_TOP;       // dl_score_links_top: a pair also has to reach the selected key
+    constexpr bool DEGS = MODE == DEG || MODE == DEG_TOP, FILLS = MODE == FILL || MODE == FILL_TOP;
+    constexpr bool LINKS = DEGS || FILLS;                      // dl_score_links: no selection state, masks where the bins are
     static_assert(2 * TT * 4 * 4 + 2 * TT * 8 <= BINS * 4, "the link masks and bases fit where the bins are");
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -231,6 +241,9 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     }
     if constexpr (!LINKS)
         if (blockIdx.x == 0 && tid == 0) atomicAdd(&A.state->scans, 1u);
+    // KEYED: the threshold key the select left (uniform; complete at the launch boundary, pick_kernel has finished)
+    u64 threshold = 0ull;
+    if constexpr (KEYED) threshold = A.state->prefix;
     const int p0 = (int)blockIdx.x * A.per_wg;
     // COUNT serves tile-pair counts close to 2^31, where p0 + per_wg would overflow; the other modes keep their form (N <= 46,340)
     const int ntl = MODE == COUNT ? max(0, min(A.per_wg, A.pairs - p0)) : max(0, min(A.pairs, p0 + A.per_wg) - p0);
@@ -339,7 +352,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                 exclusion_mask(A.ex_col, first_col_at_least(A.ex_col, A.ex_rowptr[node], end, T.v0), end, T.v0, m);
             }
         }
-        if constexpr (MODE == FILL) {                           // where the cells of this tile pair start in the CSR
+        if constexpr (FILLS) {                                  // where the cells of this tile pair start in the CSR
             long long* ubase = reinterpret_cast<long long*>(bins + 2 * TT * 4), *vbase = ubase + TT;
             if (tid < TT) {
                 const int node = T.u0 + tid;
@@ -370,7 +383,8 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const int row = rbase + acc_row(q, 0), u = T.u0 + row;
-                    const bool ok = u < v && v < A.N && !((exm[row * 4 + vw] >> li) & 1u) && term[bb][q] >= A.min_logit;
+                    bool ok = u < v && v < A.N && !((exm[row * 4 + vw] >> li) & 1u) && term[bb][q] >= A.min_logit;
+                    if constexpr (KEYED) ok = ok && make_key(term[bb][q], (unsigned)u * (unsigned)A.N + (unsigned)v) >= threshold;
                     const u64 b = __ballot(ok);
                     if (li == 0) pm[row * 4 + vw] = half ? (unsigned)(b >> 32) : (unsigned)b;
                     rows |= ok ? 1u << acc_row(q, 0) : 0u;
@@ -382,7 +396,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
             }
             __syncthreads();
             const bool diag = qt == ct;
-            if constexpr (MODE == DEG) {
+            if constexpr (DEGS) {
                 // cell (u, ct) from the rows, cell (v, qt) from the columns; on the diagonal both sides of a node are one cell.
                 // Every cell of every node < N is written once, by the one workgroup that forms its tile pair, zeros included.
                 if (tid < TT) {
@@ -863,15 +877,18 @@ void score_links_form(int N, int d, int* out) {
 
 // Workspace (256-byte aligned blocks): planes of Z and H | cnt [N][nt] | deg [N]
 struct LinksWs { __bf16 *cz, *ch; unsigned *cnt, *deg; size_t bytes; };
-static LinksWs links_carve(const MinePlan& p, int N, int K, void* ws) {
+static LinksWs links_carve(const MinePlan& p, int N, int K, Carver& c) {
     LinksWs w = {};
-    Carver c(ws);
     w.cz = c.take<__bf16>((size_t)K * p.cbatch);
     w.ch = c.take<__bf16>((size_t)K * p.cbatch);
     w.cnt = c.take<unsigned>((size_t)N * p.nt);
     w.deg = c.take<unsigned>((size_t)N);
     w.bytes = c.bytes();
     return w;
+}
+static LinksWs links_carve(const MinePlan& p, int N, int K, void* ws) {
+    Carver c(ws);
+    return links_carve(p, N, K, c);
 }
 
 size_t score_links_workspace_bytes(int N, int K, int d, dl_dtype dt) { return links_carve(mine_plan(N, d, dt), N, K, nullptr).bytes; }
@@ -902,6 +919,74 @@ int score_links_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* e
         launch_tiles<FILL>(p, a, nf, st);
     }
     return check_launch("score_links_fill");
+}
+
+// ---- dl_score_links_top: the m best candidates as that CSR — the select of score_mine (no EMIT, no ordering), then the link
+// scans under the threshold key it left on the device
+// out = the fields of score_links_form with scans at most = digits + count + fill, then the byte offset of the 32-bit count
+// of HISTOGRAM scans that ran inside the (256-byte aligned) workspace
+void score_links_top_form(int N, int d, int* out) {
+    score_links_form(N, d, out);
+    out[5] = out[2] > 0 ? PASSES + 2 : 0;
+    out[7] = (int)offsetof(State, scans);
+}
+
+// Workspace (256-byte aligned blocks): selection state | histogram | the links workspace (planes of Z and H | cnt | deg)
+struct LinksTopWs { State* state; unsigned* hist; LinksWs links; size_t bytes; };
+static LinksTopWs links_top_carve(const MinePlan& p, int N, int K, void* ws) {
+    LinksTopWs w = {};
+    Carver c(ws);
+    w.state = c.take<State>(1);
+    w.hist = c.take<unsigned>(BINS);
+    w.links = links_carve(p, N, K, c);
+    w.bytes = w.links.bytes;
+    return w;
+}
+
+size_t score_links_top_workspace_bytes(int N, int K, int d, dl_dtype dt) {
+    return links_top_carve(mine_plan(N, d, dt), N, K, nullptr).bytes;
+}
+
+int score_links_top_count(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* exr,
+                          const int32_t* exc, float min_logit, long long m, const dl_node_filter* nf, void* ws, int64_t* rowptr,
+                          hipStream_t st) {
+    const MinePlan p = mine_plan(N, d, dt);
+    const LinksTopWs w = links_top_carve(p, N, K, ws);
+    // a budget above all pairs means every candidate; what is left fits the select's 32-bit counts (N <= 46,340)
+    const long long all = (long long)N * (N - 1) / 2;
+    const int need = (int)(m < all ? m : all);
+    static_assert((long long)DL_SCORE_LINKS_MAX_N * (DL_SCORE_LINKS_MAX_N - 1) / 2 <= 2147483647LL, "pairs fit the select's need");
+    hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, need);
+    if (p.pairs > 0) {
+        split_tables(p, Z, H, N, K, d, w.links.cz, w.links.ch, st);
+        ScanArgs a = scan_args(p, w.links.cz, w.links.ch, N, K, t, exr, exc, min_logit, nf);
+        a.state = w.state;
+        a.sel.m = need; a.sel.hist = w.hist;
+        for (int pass = 0; pass < PASSES; ++pass) {
+            a.sel.pass = pass;
+            launch_tiles<HIST>(p, a, nf, st);
+            hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, need);
+        }
+        a.link.cnt = w.links.cnt;
+        launch_tiles<DEG_TOP>(p, a, nf, st);
+        hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, w.links.cnt, w.links.deg, N, p.nt);
+    }
+    hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, w.links.deg, rowptr, N, p.pairs > 0 ? 1 : 0);
+    return check_launch("score_links_top_count");
+}
+
+int score_links_top_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
+                         const dl_node_filter* nf, void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit,
+                         float* prob, hipStream_t st) {
+    const MinePlan p = mine_plan(N, d, dt);
+    const LinksTopWs w = links_top_carve(p, N, K, ws);
+    if (p.pairs > 0 && nnz > 0) {
+        ScanArgs a = scan_args(p, w.links.cz, w.links.ch, N, K, t, exr, exc, min_logit, nf);
+        a.state = w.state;                                      // the threshold the count's select left
+        a.link = LinkArgs{w.links.cnt, rowptr, nnz, col, logit, prob};
+        launch_tiles<FILL_TOP>(p, a, nf, st);
+    }
+    return check_launch("score_links_top_fill");
 }
 
 }  // namespace dl

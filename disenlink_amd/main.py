@@ -56,7 +56,8 @@ def build_parser() -> argparse.ArgumentParser:
                         "bookkeeping on the device the eager loop is gapless and 3-10 %% faster than the replay")
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--scan-dtype", choices=["f32", "bf16"], default="f32",
-                   help="tables of the all-pairs scans (--rank-eval, --global-rank-eval, --mine, --predict-links): f32, or "
+                   help="tables of the all-pairs scans (--rank-eval, --global-rank-eval, --mine, --predict-links, --predict-top): f32, "
+                        "or "
                         "bf16 = Z rounded to bf16 and H aggregated from it, as the bf16 training step forms them; one "
                         "matrix-core product per block instead of six and a third of the plane workspace")
     p.add_argument("--rank-eval", action="store_true",
@@ -75,10 +76,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="after the last run, form the predicted graph: every pair that is not a dataset edge and whose "
                         "link_pred reaches P (Disentangle.predicted_links; single GPU, fp32 tables, N <= 46340), and print "
                         "the number of links, the density and the mean / max predicted degree")
+    p.add_argument("--predict-top", type=int, default=None, metavar="M",
+                   help="after the last run, form the predicted graph under a budget: the M most likely pairs that are not "
+                        "dataset edges, for any M >= 1 (Disentangle.top_predicted_links; single GPU, fp32 tables, "
+                        "N <= 46340), printed as --predict-links prints its links; not together with --predict-links")
     p.add_argument("--links-out", type=str, default=None, metavar="FILE",
-                   help="with --predict-links: write the links to FILE as text, one `src dst prob` line per pair, src < dst")
+                   help="with --predict-links / --predict-top: write the links to FILE as text, one `src dst prob` line per pair, src < dst")
     p.add_argument("--explain", action="store_true",
-                   help="with --mine / --predict-links: say which of the K factors makes each listed link "
+                   help="with --mine / --predict-links / --predict-top: say which of the K factors makes each listed link "
                         "(Disentangle.explain_links: the per-factor terms of the scans' own pass).  --mine-out lines gain "
                         "`factor contrib[factor]`, --links-out lines gain `factor`, and the number of links per dominant "
                         "factor is printed")
@@ -309,12 +314,25 @@ def predict_links(model, x, graph, known, min_prob: float, out=None, log=print, 
     summary line printed and, with ``out``, all of them written as `src dst prob` lines, src < dst; ``explained``
     (--explain): the lines end in `factor`, each unordered pair explained once."""
     links = model.predicted_links(x, graph, min_prob, exclude=known, node_filter=node_filter, table_dtype=table_dtype)
+    return _report_links(model, x, graph, links, f"at prob >= {min_prob:g}", out, log, table_dtype, explained)
+
+
+def predict_top_links(model, x, graph, known, m: int, out=None, log=print, node_filter=None, table_dtype=None,
+                      explained: bool = False):
+    """--predict-top: the ``m`` most likely links outside ``known`` (Disentangle.top_predicted_links), printed and written
+    exactly as --predict-links prints and writes its links."""
+    links = model.top_predicted_links(x, graph, m, exclude=known, node_filter=node_filter, table_dtype=table_dtype)
+    return _report_links(model, x, graph, links, f"under a budget of {m}", out, log, table_dtype, explained)
+
+
+def _report_links(model, x, graph, links, how: str, out, log, table_dtype, explained: bool):
+    """What --predict-links and --predict-top share: the summary line of a PredictedLinks, --explain and --links-out."""
     n = links.n_nodes
     pairs = links.pairs()
     src, dst, _, prob = (v.cpu().numpy() for v in pairs)
     deg = links.degree.cpu().numpy()
     density = src.size / (n * (n - 1) / 2) if n > 1 else 0.0
-    log(f"predicted {src.size} links at prob >= {min_prob:g}: density {density:.6g} mean degree {deg.mean():.6g} "
+    log(f"predicted {src.size} links {how}: density {density:.6g} mean degree {deg.mean():.6g} "
         f"max degree {int(deg.max())}")
     factor = None
     if explained:
@@ -367,13 +385,21 @@ def main(argv=None):
                          "implemented): drop --gpus / --table-dtype bf16 or --predict-links")
     if args.predict_links is not None and not 0.0 <= args.predict_links <= 1.0:
         raise SystemExit("--predict-links P: 0 <= P <= 1")
-    if args.links_out and args.predict_links is None:
+    if args.predict_top is not None and args.predict_links is not None:
+        raise SystemExit("--predict-top M and --predict-links P each form the predicted graph: give one of them")
+    if args.predict_top is not None and (args.gpus > 1 or args.table_dtype == "bf16"):
+        raise SystemExit("--predict-top runs on one GPU with fp32 tables only (sharded and bf16 link graphs are not "
+                         "implemented): drop --gpus / --table-dtype bf16 or --predict-top")
+    if args.predict_top is not None and args.predict_top < 1:
+        raise SystemExit("--predict-top M: M >= 1")
+    if args.links_out and args.predict_links is None and args.predict_top is None:
         raise SystemExit("--links-out FILE goes with --predict-links P")
-    if args.explain and not (args.mine or args.predict_links is not None):
+    if args.explain and not (args.mine or args.predict_links is not None or args.predict_top is not None):
         raise SystemExit("--explain names the factor behind the links of --mine and --predict-links: give one of them")
     if (args.node_groups is None) != (args.link_rule is None):
         raise SystemExit("--node-groups FILE and --link-rule {same,different} go together")
-    if args.link_rule and not (args.rank_eval or args.global_rank_eval or args.mine or args.predict_links is not None):
+    if args.link_rule and not (args.rank_eval or args.global_rank_eval or args.mine or args.predict_links is not None or
+                               args.predict_top is not None):
         raise SystemExit("--link-rule restricts the candidates of --rank-eval, --global-rank-eval, --mine and --predict-links: "
                          "give one of them")
     if args.gpus > 1:
@@ -410,7 +436,8 @@ def main(argv=None):
     result = []
     ranking = []
     global_ranking = []
-    if args.rank_eval or args.mine or args.global_rank_eval or args.predict_links is not None:      # filter: every dataset edge, both directions
+    if (args.rank_eval or args.mine or args.global_rank_eval or args.predict_links is not None or
+            args.predict_top is not None):                               # filter: every dataset edge, both directions
         s_all, d_all = torch.from_numpy(np.asarray(ds.src)).long(), torch.from_numpy(np.asarray(ds.dst)).long()
         known = (torch.cat([s_all, d_all]).to(device), torch.cat([d_all, s_all]).to(device))
     node_filter = load_node_groups(args.node_groups, ds.n_nodes, args.link_rule, device) if args.link_rule else None
@@ -441,6 +468,9 @@ def main(argv=None):
     if args.predict_links is not None and args.run > 0:
         predict_links(model, x, prepared.graph, known, args.predict_links, args.links_out, node_filter=node_filter,
                       table_dtype=sdt, explained=args.explain)
+    if args.predict_top is not None and args.run > 0:
+        predict_top_links(model, x, prepared.graph, known, args.predict_top, args.links_out, node_filter=node_filter,
+                          table_dtype=sdt, explained=args.explain)
     result = np.array(result)
     tail = []                                                       # the run means of the ranking metrics join the final line
     if args.rank_eval:

@@ -422,6 +422,16 @@ class Disentangle(nn.Module):
         """The ``table_dtype`` keyword of the ops scans for this one (None = fp32)."""
         return torch.float32 if table_dtype is None else table_dtype
 
+    @staticmethod
+    def _logit_floor(min_prob) -> float:
+        """``min_prob`` in [0, 1] as the logit floor of the scans (0.5 -> 0.0; None = no floor)."""
+        if min_prob is None:
+            return float("-inf")
+        p = float(min_prob)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"min_prob={p} outside [0, 1]")
+        return float("-inf") if p == 0.0 else float("inf") if p == 1.0 else math.log(p) - math.log1p(-p)
+
     def topk_links(self, x, adj, queries, k: int, exclude=None, exclude_self: bool = True, node_filter=None,
                    table_dtype=None) -> TopLinks:
         """The k most likely links of every node in ``queries``: TopLinks(index int64 [Q,k], logit, prob f32 [Q,k]),
@@ -451,12 +461,7 @@ class Disentangle(nn.Module):
         symmetric ops.NodeFilter, a rule on node groups that pairs must pass as well."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
         Z, H = self._rank_tables(x, graph, table_dtype)
-        floor = float("-inf")
-        if min_prob is not None:
-            p = float(min_prob)
-            if not 0.0 <= p <= 1.0:
-                raise ValueError(f"min_prob={p} outside [0, 1]")
-            floor = float("-inf") if p == 0.0 else float("inf") if p == 1.0 else math.log(p) - math.log1p(-p)
+        floor = self._logit_floor(min_prob)
         with torch.no_grad():
             return MinedLinks(*ops.score_mine(Z, H, float(self.temperature), m, graph if exclude is None else exclude, floor,
                                               node_filter, self._scan_dtype(table_dtype)))
@@ -471,13 +476,26 @@ class Disentangle(nn.Module):
         N <= 46,340."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
         Z, H = self._rank_tables(x, graph, table_dtype)
-        p = float(min_prob)
-        if not 0.0 <= p <= 1.0:
-            raise ValueError(f"min_prob={p} outside [0, 1]")
-        floor = float("-inf") if p == 0.0 else float("inf") if p == 1.0 else math.log(p) - math.log1p(-p)
+        floor = self._logit_floor(float(min_prob))
         with torch.no_grad():
             return PredictedLinks(*ops.score_links(Z, H, float(self.temperature), floor, graph if exclude is None else exclude,
                                                    node_filter, self._scan_dtype(table_dtype)))
+
+    def top_predicted_links(self, x, adj, m: int, exclude=None, min_prob=None, node_filter=None,
+                            table_dtype=None) -> PredictedLinks:
+        """The predicted graph under a BUDGET: the m most likely links that are not known yet, for any m >= 1 ("the 1 % most
+        likely pairs", "five million links"), as the PredictedLinks of ``predicted_links`` — the pairs ``top_missing_links``
+        would list if it had no cap on m, in the layout of a graph (ops.score_top_links: the select of the mining, then the
+        two scans of ``predicted_links``; nothing of size N x N is formed and no threshold has to be known).  There are
+        exactly min(m, eligible pairs) links; tied logits across the cut are taken by ascending src * N + dst.  ``exclude``,
+        ``min_prob`` and ``node_filter`` as in ``top_missing_links`` (``exclude`` may also be a prepared
+        ``ops.pair_exclusion``); ``min_prob`` and the budget both hold.  N <= 46,340."""
+        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        Z, H = self._rank_tables(x, graph, table_dtype)
+        floor = self._logit_floor(min_prob)
+        with torch.no_grad():
+            return PredictedLinks(*ops.score_top_links(Z, H, float(self.temperature), m, graph if exclude is None else exclude,
+                                                       floor, node_filter, self._scan_dtype(table_dtype)))
 
     def explain_links(self, x, adj, src, dst, table_dtype=None) -> "ops.PairTerms":
         """Which factor makes the links (src[i], dst[i]): ops.PairTerms(e, q, cum) f32 [P, K] with ``.logit``, ``.contrib``

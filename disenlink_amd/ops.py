@@ -21,7 +21,7 @@ from .graph import Graph, PairList
 from .scans import (                                                    # noqa: F401  (the all-pairs scans: ops.score_* as before)
     LINKS_MAX_N, MINE_MAX_M, MINE_MAX_N, RANK_MAX_K, NodeFilter, PairExclusion, PairTerms, exclusion_csr, pair_exclusion,
     score_link_degrees, score_links, score_mine, score_pair_logits, score_pair_ranks, score_pair_ranks_counted,
-    score_pair_terms, score_ranks, score_topk)
+    score_pair_terms, score_ranks, score_top_links, score_topk)
 
 
 def _tab(t: torch.Tensor):

@@ -1,5 +1,5 @@
 """The all-pairs inference scans over libdisenlink_hip.so: top-k and ranks of a node's candidates, mining, the
-thresholded link graph, pair ranks, and the logits and per-factor terms of given pairs — with the exclusion sets and
+thresholded and the budgeted link graph, pair ranks, and the logits and per-factor terms of given pairs — with the exclusion sets and
 node-group rules they take.  Nothing here is differentiable.
 
 Every scan goes through ONE C entry, ``dl_score_<name>_dtype`` (the implementation; the plain and ``_filtered`` entries
@@ -412,6 +412,18 @@ def _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype=torch.flo
     return rowptr, head, (Z, H, excl, _keep_nf, ws)
 
 
+def _links_fill(name: str, rowptr, head):
+    """The fill pass of a link graph: the one host read, of rowptr[N], the three arrays of that length, and the fill entry
+    ``name`` with the count's arguments ``head`` -> (rowptr, col, logit, prob)."""
+    nnz = int(rowptr[-1].item())                                      # the one host read
+    dev = rowptr.device
+    col = _empty(nnz, torch.int32, dev)
+    logit = _empty(nnz, torch.float32, dev)
+    prob = _empty(nnz, torch.float32, dev)
+    _scan_call(name, *head, nnz, col.data_ptr(), logit.data_ptr(), prob.data_ptr(), _stream())
+    return rowptr, col, logit, prob
+
+
 def score_links(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32):
     """-> (rowptr int64 [N+1], col int32 [nnz], logit f32 [nnz], prob f32 [nnz]): the predicted graph, EVERY unordered pair
     whose logit s(u,v) = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred) reaches ``min_logit``, as a
@@ -422,13 +434,7 @@ def score_links(Z, H, t: float, min_logit: float, exclude=None, node_filter=None
     nothing of size N x N is formed (dl_score_links_count / dl_score_links_fill: two scans), there is no cap on nnz, and the
     one host read is that of rowptr[N], between the scans, to allocate the outputs.  Same bits on every call."""
     rowptr, head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
-    nnz = int(rowptr[-1].item())                                      # the one host read
-    dev = rowptr.device
-    col = _empty(nnz, torch.int32, dev)
-    logit = _empty(nnz, torch.float32, dev)
-    prob = _empty(nnz, torch.float32, dev)
-    _scan_call("links_fill", *head, nnz, col.data_ptr(), logit.data_ptr(), prob.data_ptr(), _stream())
-    return rowptr, col, logit, prob
+    return _links_fill("links_fill", rowptr, head)
 
 
 def score_link_degrees(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32):
@@ -436,6 +442,47 @@ def score_link_degrees(Z, H, t: float, min_logit: float, exclude=None, node_filt
     count pass alone (dl_score_links_count): one scan, no host read, no fill."""
     rowptr, _head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
     return rowptr[1:] - rowptr[:-1]
+
+
+# ---------------------------------------------------------------------- the m best pairs, any m, as a CSR (select, then DEG / FILL)
+_INT64_MAX = (1 << 63) - 1
+
+
+def score_top_links(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf"), node_filter=None,
+                    table_dtype=torch.float32):
+    """-> (rowptr int64 [N+1], col int32 [nnz], logit f32 [nnz], prob f32 [nnz]), nnz = 2 min(m, eligible): the m most
+    likely unordered pairs of the WHOLE graph, for any m >= 1, in ``score_links``' layout — the set ``score_mine`` would list
+    if it had no cap (its eligibility: ``exclude``, ``node_filter``, logit >= ``min_logit``, NaN never; its order: larger
+    logit first, equal logits by src * N + dst, so a cut through tied logits keeps the smaller), each pair as (u, v) and as
+    (v, u) with the bits of ``score_pair_logits(min(u, v), max(u, v))``, columns ascending within a row, not sorted by
+    logit.  An m above N (N - 1) / 2 means every eligible pair.  ``exclude``: as in ``score_links``, or a prepared
+    ``pair_exclusion(...)``, which skips the normalisation per call.  N <= 46,340, fp32 or bf16 tables.  Inference only;
+    nothing of size N x N is formed (dl_score_links_top_count / _fill: the select of ``score_mine``, at most six histogram
+    scans, then the two scans of ``score_links`` under the threshold key it left on the device), and the one host read is
+    that of rowptr[N], to allocate the outputs.  Same bits on every call."""
+    dt = _scan_dtype(table_dtype)
+    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
+    if N > LINKS_MAX_N:
+        raise ValueError(f"N={N} above {LINKS_MAX_N} (the tile-pair walk of dl_score_mine)")
+    m = min(int(m), _INT64_MAX)
+    if isinstance(exclude, PairExclusion):
+        if exclude.n_nodes != N:
+            raise ValueError(f"exclusion set of {exclude.n_nodes} nodes, expected {N}")
+        if exclude.rowptr is not None and exclude.rowptr.device != Z.device:
+            raise ValueError(f"exclusion set on {exclude.rowptr.device}, tables on {Z.device}")
+        csr = (exclude.rowptr, exclude.col)
+    else:
+        csr = _unordered_exclusion_csr(exclude, N, Z.device)
+    excl = _csr_args(*csr, Z.device)
+    nf, _keep_nf = _filter_arg(node_filter, N, Z.device, True)
+    # a workspace of its own, held across the two calls, as in ``_links_count``: the fill reads the threshold, the planes and
+    # the cell offsets the count left
+    ws = _empty(max(256, _scan_ws_bytes("links_top", N, K, d, dt)), torch.uint8, Z.device)
+    rowptr = _empty(N + 1, torch.int64, Z.device)
+    head = (Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), excl[0], excl[1], float(min_logit), m, nf, ws.data_ptr(),
+            ws.numel(), rowptr.data_ptr())
+    _scan_call("links_top_count", *head, _stream())
+    return _links_fill("links_top_fill", rowptr, head)
 
 
 # ---------------------------------------------------------------------- where given pairs stand among ALL pairs (COUNT scan)

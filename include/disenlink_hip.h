@@ -730,6 +730,50 @@ int dl_score_links_fill_dtype(const void* Z, const void* H, int N, int K, int d,
                               const int32_t* ex_col, float min_logit, const dl_node_filter* filter, void* ws, size_t ws_bytes,
                               const int64_t* rowptr, int64_t nnz, int32_t* col, float* logit, float* prob, void* stream);
 
+/* The budgeted link graph (an extension; the reference has no counterpart): the m most likely unordered pairs of the whole
+ * graph, for ANY m, as the symmetric CSR of dl_score_links -- what a caller wants who knows how many links to take ("the
+ * 1 % most likely pairs") and not the probability that yields them.  Provided in the _dtype argument convention only.
+ * Eligible: dl_score_mine's rule -- u < v < N, v not among the columns of row u of the exclusion CSR (the row of the SMALLER
+ * endpoint), allowed by the node filter if one is given (symmetric, NULL = none), s >= min_logit, NaN never.  min_logit and
+ * the budget combine by AND: the result holds the min(m, eligible) best eligible pairs.
+ * Order: dl_score_mine's -- larger logit first (+inf above everything finite, -0 equal to +0), equal logits by u N + v, the
+ * smaller first.  The result is exactly the set dl_score_mine would list if it had no cap on m; a cut through a class of
+ * tied logits falls where it puts it.
+ * Output: dl_score_links_fill's -- rowptr int64 [N+1], col int32 [nnz], logit / prob fp32 [nnz], every chosen pair as (u, v)
+ * and as (v, u) with the same bits, columns within a row strictly ascending, a -0 reported as +0, prob = sigmoid(logit) formed
+ * where the logit is in a register, prob NULL allowed.  rowptr[N] = nnz = 2 min(m, eligible).  The CSR is not sorted by
+ * logit; it carries the logits, and a caller who wants a list sorts it.
+ * Two calls with the same arguments, as for dl_score_links:
+ *   dl_score_links_top_count_dtype: splits the planes once, runs dl_score_mine's radix select on the 64-bit key (up to six
+ *     histogram scans and one-workgroup picks; once the threshold key is final the remaining histogram scans return at
+ *     workgroup start), which leaves the key of the m-th best pair in the workspace, then dl_score_links_count's scan with
+ *     one more condition (the pair's key reaches that threshold), the offsets and rowptr.  Neither the emit scan nor the
+ *     ordering of dl_score_mine runs, which is why m has no cap.  Nothing is read back between the select and the count.
+ *   dl_score_links_top_fill_dtype: dl_score_links_fill's scan under the same condition over the workspace the count left
+ *     (the same memory, untouched in between: it holds the threshold, the planes and cnt); a slot >= nnz is not written.
+ * m is 64-bit, m >= 1; a value above N (N - 1) / 2 means every eligible pair.
+ * Integer atomics appear in the histograms only (counts: their order does not matter); nothing on the output path is atomic
+ * or depends on an arrival order, so a call gives the same bits every time and under every DL_MINE_TILES.
+ * Limits: 1 <= N <= DL_SCORE_LINKS_MAX_N, d <= 128, fp32 and bf16 tables (dl_score_scan_supported).  Codes, texts and the
+ * order of the checks are the links entries': dtype, K and d, N, filter, t, then m >= 1, NULL tables or rowptr, the exclusion
+ * pair, the workspace (DL_E_WORKSPACE); the fill then nnz >= 0 and its outputs.  No allocation, no synchronisation, no host
+ * read; the caller's stream.
+ * ws: dl_score_links_top_workspace_bytes_dtype(N, K, d, dtype) (0 for arguments out of range): dl_score_links' workspace plus
+ * the selection state and one histogram of 2,048 counts (8,448 bytes more).
+ * The launch plan (host only): out[DL_SCORE_LINKS_TOP_FORM_LEN] = the fields [0..6] of dl_score_links_form with
+ *   [5] scans at most: six histogram scans + count + fill (0 for N < 2)
+ *   [7] byte offset, inside the 256-byte aligned workspace, of the 32-bit number of histogram scans that ran */
+#define DL_SCORE_LINKS_TOP_FORM_LEN 8
+int dl_score_links_top_form(int N, int K, int d, int* out);
+size_t dl_score_links_top_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype);
+int dl_score_links_top_count_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                                   const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit, int64_t m,
+                                   const dl_node_filter* filter, void* ws, size_t ws_bytes, int64_t* rowptr, void* stream);
+int dl_score_links_top_fill_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                                  const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit, int64_t m,
+                                  const dl_node_filter* filter, void* ws, size_t ws_bytes, const int64_t* rowptr, int64_t nnz,
+                                  int32_t* col, float* logit, float* prob, void* stream);
+
 /* Tie-averaged AUC of a score vector against FIXED labels: replaces sklearn.metrics.roc_auc_score at
  * main_disentangled.py:202-204 / 217-219 (validation AUC every epoch, test AUC at the end).  pos_idx / neg_idx
  * (int64, device) are the positions of the positive and negative labels in score, found once per run; the call
