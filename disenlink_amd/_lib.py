@@ -63,11 +63,16 @@ class DlNodeFilter(C.Structure):
     _fields_ = [("group", C.c_void_p), ("n_groups", C.c_int32), ("allow", C.c_void_p)]
 
 
+class DlNodeFilterBetween(C.Structure):
+    _fields_ = [("group_a", C.c_void_p), ("group_b", C.c_void_p), ("n_groups", C.c_int32), ("allow", C.c_void_p)]
+
+
 _P = C.c_void_p          # device pointers travel as integers
 _G, _I = C.POINTER(DlGraph), C.POINTER(DlPairIncidence)
 _i, _f, _z = C.c_int, C.c_float, C.c_size_t
 _S = C.POINTER(DlSparseFeatures)
 _NF = C.POINTER(DlNodeFilter)
+_NFB = C.POINTER(DlNodeFilterBetween)
 EXPORTS = {
     # name: (restype, argtypes) -- one entry per symbol declared in include/disenlink_hip.h
     "dl_host_csr_from_edges": (_i, [_P, _P, C.c_int64, C.c_int32, _i, C.POINTER(DlHostCsr)]),
@@ -171,6 +176,18 @@ EXPORTS.update({
     "dl_score_links_top_workspace_bytes_dtype": (_z, [_i] * 4),
     "dl_score_links_top_count_dtype": (_i, _LINKS_TOP + [_P]),
     "dl_score_links_top_fill_dtype": (_i, _LINKS_TOP + [C.c_int64, _P, _P, _P, _P]),
+})
+# the scans between two node sets have the _dtype entries only: ZA, HA, nA, ZB, HB, nB, K, d, dtype, t, exclusion, min_logit, ...
+_BETWEEN = [_P, _P, _i, _P, _P, _i, _i, _i, _i, _f] + _EX + [_f]
+_LINKS_BETWEEN = _BETWEEN + [_NFB, _P, _z, _P, _P]   # ... the two-sided rule, workspace, its size, rowptr_a, rowptr_b
+EXPORTS.update({
+    "dl_score_mine_between_form": (_i, [_i] * 5 + [C.POINTER(C.c_int)]),
+    "dl_score_mine_between_workspace_bytes_dtype": (_z, [_i] * 6),
+    "dl_score_mine_between_dtype": (_i, _BETWEEN + [_i, _P, _P, _P, _P, _P] + _WS + [_NFB]),
+    "dl_score_links_between_form": (_i, [_i] * 4 + [C.POINTER(C.c_int)]),
+    "dl_score_links_between_workspace_bytes_dtype": (_z, [_i] * 5),
+    "dl_score_links_between_count_dtype": (_i, _LINKS_BETWEEN + [_P]),
+    "dl_score_links_between_fill_dtype": (_i, _LINKS_BETWEEN + [C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
 })
 
 DL_F32, DL_BF16 = 0, 1
@@ -318,6 +335,24 @@ def score_links_top_form(N: int, K: int, d: int) -> dict:
     out = (C.c_int * len(SCORE_LINKS_TOP_FORM))()
     check(load().dl_score_links_top_form(N, K, d, out), "dl_score_links_top_form")
     return dict(zip(SCORE_LINKS_TOP_FORM, out))
+
+
+SCORE_MINE_BETWEEN_FORM = ("nd", "tiles_a", "tiles_b", "pairs", "pairs_per_wg", "grid", "max_scans", "scans_offset")
+SCORE_LINKS_BETWEEN_FORM = SCORE_MINE_BETWEEN_FORM[:6] + ("scans", "cells_a", "cells_b")
+
+
+def score_mine_between_form(nA: int, nB: int, K: int, d: int, m: int) -> dict:
+    """The plan of the rectangular mining scan under the current DL_MINE_TILES (dl_score_mine_between_form)."""
+    out = (C.c_int * len(SCORE_MINE_BETWEEN_FORM))()
+    check(load().dl_score_mine_between_form(nA, nB, K, d, m, out), "dl_score_mine_between_form")
+    return dict(zip(SCORE_MINE_BETWEEN_FORM, out))
+
+
+def score_links_between_form(nA: int, nB: int, K: int, d: int) -> dict:
+    """The plan of the rectangular link-graph scans under the current DL_MINE_TILES (dl_score_links_between_form)."""
+    out = (C.c_int * len(SCORE_LINKS_BETWEEN_FORM))()
+    check(load().dl_score_links_between_form(nA, nB, K, d, out), "dl_score_links_between_form")
+    return dict(zip(SCORE_LINKS_BETWEEN_FORM, out))
 
 
 def config_reload() -> None:

@@ -647,6 +647,108 @@ int dl_score_links_top_fill_dtype(const void* Z, const void* H, int N, int K, in
                                 (hipStream_t)stream);
 }
 
+// ---- the scans between two node sets: the checklist of the mining / links entries on (nA, nB), and the two-sided rule
+static const ScanSpec BETWEEN_SCAN = {"the scans between two node sets serve", 1, DL_SCORE_BETWEEN_MAX_N,
+                                      "the pair index a nB + b must fit 31 bits", OWN_N | EX_TOGETHER | WS_CODE};
+static_assert((long long)DL_SCORE_BETWEEN_MAX_N * DL_SCORE_BETWEEN_MAX_N <= 2147483647LL, "the pair index and the candidate count");
+
+static bool between_shape_ok(int nA, int nB, int K, int d, dl_dtype dtype) {
+    return scan_shape_ok(BETWEEN_SCAN, nA, K, d) && scan_shape_ok(BETWEEN_SCAN, nB, K, d) && known_dtype(dtype);
+}
+static int check_between_shape(int nA, int nB, int K, int d, dl_dtype dtype) {
+    if (int rc = check_scan_shape(BETWEEN_SCAN, nA, K, d, dtype)) return rc;
+    DL_REQUIRE(nA >= 1 && nA <= DL_SCORE_BETWEEN_MAX_N, "nA=%d outside 1..%d (%s)", nA, DL_SCORE_BETWEEN_MAX_N, BETWEEN_SCAN.n_why);
+    DL_REQUIRE(nB >= 1 && nB <= DL_SCORE_BETWEEN_MAX_N, "nB=%d outside 1..%d (%s)", nB, DL_SCORE_BETWEEN_MAX_N, BETWEEN_SCAN.n_why);
+    return DL_OK;
+}
+static int check_filter_between(const dl_node_filter_between* f) {
+    if (f == nullptr) return DL_OK;
+    DL_REQUIRE(f->n_groups >= 1 && f->n_groups <= 64, "node filter: n_groups=%d outside 1..64", f->n_groups);
+    DL_REQUIRE(f->group_a != nullptr && f->group_b != nullptr && f->allow != nullptr, "node filter: NULL group or allow array");
+    return DL_OK;
+}
+
+int dl_score_mine_between_form(int nA, int nB, int K, int d, int m, int* out) {
+    if (int rc = check_between_shape(nA, nB, K, d, DL_F32)) return rc;
+    DL_REQUIRE(m >= 1 && m <= 65536, "m=%d outside 1..65536", m);
+    DL_REQUIRE(out != nullptr, "out is NULL");
+    score_mine_between_form(nA, nB, d, out);
+    return DL_OK;
+}
+
+size_t dl_score_mine_between_workspace_bytes_dtype(int nA, int nB, int K, int d, dl_dtype dtype, int m) {
+    if (!between_shape_ok(nA, nB, K, d, dtype) || m < 1 || m > 65536) return 0;
+    return score_mine_between_workspace_bytes(nA, nB, K, d, m, dtype);
+}
+
+int dl_score_mine_between_dtype(const void* ZA, const void* HA, int nA, const void* ZB, const void* HB, int nB, int K, int d,
+                                dl_dtype dtype, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit, int m,
+                                int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws, size_t ws_bytes,
+                                void* stream, const dl_node_filter_between* filter) {
+    if (int rc = check_between_shape(nA, nB, K, d, dtype)) return rc;
+    DL_REQUIRE(m >= 1 && m <= 65536, "m=%d outside 1..65536", m);
+    if (int rc = check_filter_between(filter)) return rc;
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    if (int rc = check_scan_ptrs(BETWEEN_SCAN, ZA && HA && ZB && HB, ex_rowptr, ex_col)) return rc;
+    DL_REQUIRE(src && dst && logit && prob && count, "NULL output");
+    if (int rc = check_scan_ws(BETWEEN_SCAN, ws, ws_bytes, score_mine_between_workspace_bytes(nA, nB, K, d, m, dtype),
+                               "dl_score_mine_between_workspace_bytes_dtype"))
+        return rc;
+    return score_mine_between(ZA, HA, ZB, HB, dtype, nA, nB, K, d, t, ex_rowptr, ex_col, min_logit, m, src, dst, logit, prob, count, ws,
+                              (hipStream_t)stream, filter);
+}
+
+int dl_score_links_between_form(int nA, int nB, int K, int d, int* out) {
+    if (int rc = check_between_shape(nA, nB, K, d, DL_F32)) return rc;
+    DL_REQUIRE(out != nullptr, "out is NULL");
+    score_links_between_form(nA, nB, d, out);
+    return DL_OK;
+}
+
+size_t dl_score_links_between_workspace_bytes_dtype(int nA, int nB, int K, int d, dl_dtype dtype) {
+    return between_shape_ok(nA, nB, K, d, dtype) ? score_links_between_workspace_bytes(nA, nB, K, d, dtype) : 0;
+}
+
+// what the count and the fill call check alike
+static int check_links_between_args(const void* ZA, const void* HA, int nA, const void* ZB, const void* HB, int nB, int K, int d,
+                                    dl_dtype dtype, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
+                                    const dl_node_filter_between* filter, const void* ws, size_t ws_bytes, const int64_t* rowptr_a,
+                                    const int64_t* rowptr_b) {
+    if (int rc = check_between_shape(nA, nB, K, d, dtype)) return rc;
+    if (int rc = check_filter_between(filter)) return rc;
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    if (int rc = check_scan_ptrs(BETWEEN_SCAN, ZA && HA && ZB && HB && rowptr_a && rowptr_b, ex_rowptr, ex_col)) return rc;
+    return check_scan_ws(BETWEEN_SCAN, ws, ws_bytes, score_links_between_workspace_bytes(nA, nB, K, d, dtype),
+                         "dl_score_links_between_workspace_bytes_dtype");
+}
+
+int dl_score_links_between_count_dtype(const void* ZA, const void* HA, int nA, const void* ZB, const void* HB, int nB, int K, int d,
+                                       dl_dtype dtype, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit,
+                                       const dl_node_filter_between* filter, void* ws, size_t ws_bytes, int64_t* rowptr_a,
+                                       int64_t* rowptr_b, void* stream) {
+    if (int rc = check_links_between_args(ZA, HA, nA, ZB, HB, nB, K, d, dtype, t, ex_rowptr, ex_col, filter, ws, ws_bytes, rowptr_a,
+                                          rowptr_b))
+        return rc;
+    return score_links_between_count(ZA, HA, ZB, HB, dtype, nA, nB, K, d, t, ex_rowptr, ex_col, min_logit, filter, ws, rowptr_a,
+                                     rowptr_b, (hipStream_t)stream);
+}
+
+int dl_score_links_between_fill_dtype(const void* ZA, const void* HA, int nA, const void* ZB, const void* HB, int nB, int K, int d,
+                                      dl_dtype dtype, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit,
+                                      const dl_node_filter_between* filter, void* ws, size_t ws_bytes, const int64_t* rowptr_a,
+                                      const int64_t* rowptr_b, int64_t nnz_a, int32_t* col_a, float* logit_a, float* prob_a,
+                                      int64_t nnz_b, int32_t* col_b, float* logit_b, float* prob_b, void* stream) {
+    if (int rc = check_links_between_args(ZA, HA, nA, ZB, HB, nB, K, d, dtype, t, ex_rowptr, ex_col, filter, ws, ws_bytes, rowptr_a,
+                                          rowptr_b))
+        return rc;
+    DL_REQUIRE(nnz_a >= 0 && nnz_b >= 0, "nnz=%lld is negative", (long long)(nnz_a < 0 ? nnz_a : nnz_b));
+    DL_REQUIRE((nnz_a == 0 || (col_a && logit_a)) && (nnz_b == 0 || (col_b && logit_b)), "NULL output");
+    DL_REQUIRE((prob_a == nullptr) == (prob_b == nullptr), "prob_a and prob_b go together");
+    return score_links_between_fill(dtype, nA, nB, K, d, t, ex_rowptr, ex_col, min_logit, filter, ws, rowptr_a, rowptr_b,
+                                    (long long)nnz_a, col_a, logit_a, prob_a, (long long)nnz_b, col_b, logit_b, prob_b,
+                                    (hipStream_t)stream);
+}
+
 int dl_score_pair_ranks_supported(int K, int d) { return score_rank_supported(K, d) ? 1 : 0; }
 
 int dl_score_pair_ranks_form(int N, int K, int d, int n_targets, int* out) {

@@ -116,6 +116,23 @@ int score_links_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* e
                      const dl_node_filter* filter, void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit,
                      float* prob, hipStream_t st);
 
+// rows of a table A against rows of a table B (dl_score_mine.hip, the RECT instantiations): the top m and the thresholded
+// link graph of the nA x nB rectangle, 1 <= nA, nB <= 46,340; the rule has a group array per side (checked by the caller)
+void score_mine_between_form(int nA, int nB, int d, int* out);
+size_t score_mine_between_workspace_bytes(int nA, int nB, int K, int d, int m, dl_dtype dt);
+int score_mine_between(const void* ZA, const void* HA, const void* ZB, const void* HB, dl_dtype dt, int nA, int nB, int K, int d, float t,
+                       const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit, int m, int32_t* src, int32_t* dst, float* logit,
+                       float* prob, int64_t* count, void* ws, hipStream_t st, const dl_node_filter_between* filter);
+void score_links_between_form(int nA, int nB, int d, int* out);
+size_t score_links_between_workspace_bytes(int nA, int nB, int K, int d, dl_dtype dt);
+int score_links_between_count(const void* ZA, const void* HA, const void* ZB, const void* HB, dl_dtype dt, int nA, int nB, int K, int d,
+                              float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit,
+                              const dl_node_filter_between* filter, void* ws, int64_t* rowptr_a, int64_t* rowptr_b, hipStream_t st);
+int score_links_between_fill(dl_dtype dt, int nA, int nB, int K, int d, float t, const int32_t* ex_rowptr, const int32_t* ex_col,
+                             float min_logit, const dl_node_filter_between* filter, void* ws, const int64_t* rowptr_a,
+                             const int64_t* rowptr_b, long long nnz_a, int32_t* col_a, float* logit_a, float* prob_a, long long nnz_b,
+                             int32_t* col_b, float* logit_b, float* prob_b, hipStream_t st);
+
 // the m best unordered pairs, any m, as that CSR (dl_score_mine.hip: the select of score_mine, then the link scans under the
 // threshold key it left in the workspace): the limits of score_links
 void score_links_top_form(int N, int d, int* out);

@@ -47,6 +47,12 @@
 // exactly min(m, candidates) pairs pass: the set dl_score_mine would list without its cap, a class of tied logits cut where
 // it cuts it (smaller u N + v first).  Nothing is read back between the select and the count.
 //
+// Two node sets (dl_score_mine_between, dl_score_links_between_count / _fill; the modes HIST_RECT, EMIT_RECT, DEG_RECT,
+// FILL_RECT): rows of a table A against rows of a table B, every tile pair of the ntA x ntB grid, the pair index a nB + b
+// local to the rectangle (nA, nB <= 46,340).  The select, the ordering, the offsets and the epilogues are the ones above;
+// there is no u < v and no diagonal, and the link modes keep cells and a CSR per side.  A graph of any size is the union of
+// its diagonal blocks (the entries above, on row slices) and of such rectangles; the caller merges them (scans.py).
+//
 // Node groups (the FILT instantiations; dl_score_mine_filtered, dl_score_pair_ranks_filtered): a symmetric rule on the groups
 // of u and v, formed into the row mask ahead of the exclusion; a candidate passes both.  The epilogues do not change.
 //
@@ -70,7 +76,10 @@ constexpr int SDC = SPLIT_COLS, SLD = SPLIT_PITCH;
 constexpr int BINS = 2048;                 // the widest digit
 constexpr int PASSES = 6;
 constexpr int MAX_M = 65536;
-enum { HIST = 0, EMIT = 1, COUNT = 2, DEG = 3, FILL = 4, DEG_TOP = 5, FILL_TOP = 6 };      // *_TOP: DEG / FILL under the selected key
+enum { HIST = 0, EMIT = 1, COUNT = 2, DEG = 3, FILL = 4, DEG_TOP = 5, FILL_TOP = 6,      // *_TOP: DEG / FILL under the selected key
+       HIST_RECT = 7, EMIT_RECT = 8, DEG_RECT = 9, FILL_RECT = 10 };                     // *_RECT: rows of A against rows of B
+constexpr int rect_mode(int mode) { return mode == HIST ? HIST_RECT : mode == EMIT ? EMIT_RECT : mode == DEG ? DEG_RECT : FILL_RECT; }
+constexpr int base_mode(int mode) { return mode == HIST_RECT ? HIST : mode == EMIT_RECT ? EMIT : mode == DEG_RECT ? DEG : mode == FILL_RECT ? FILL : mode; }
 constexpr int SEPS = 4096;                 // COUNT: first-level separators of the sorted targets, in LDS
 
 // the digits of the key, from the top: value 11 + 11 + 10 bits, index 11 + 11 + 10 bits
@@ -103,6 +112,12 @@ struct LinkArgs {                              // DEG / FILL (dl_score_links): c
     const int64_t* rowptr;  long long nnz;     // its exclusive prefix, FILL reads that), and FILL's CSR (slots >= nnz are skipped)
     int32_t* col;  float *logit, *prob;
 };
+struct RectArgs {                              // RECT (dl_score_*_between): the v side is a table B of its own — its planes, rows
+    const __bf16 *cz, *ch;  size_t cbatch;     // and tiles, the groups of its rows (FILT), and the cells and the CSR of its side
+    int N, nt;                                 // (DEG / FILL: cnt [nB][ntA], columns = rows of A)
+    const unsigned char* group;
+    LinkArgs link;
+};
 struct ScanArgs {
     const __bf16 *cz, *ch;  size_t cbatch;     // planes of Z and H
     int N, K, nd, nt;  float t;
@@ -115,6 +130,7 @@ struct ScanArgs {
     SelectArgs sel;
     CountArgs cnt;
     LinkArgs link;
+    RectArgs rect;                             // last: the offsets of everything above are those of the triangular scans
 };
 
 // LDS of an instantiation with P planes per operand: the two double-buffered images, the exclusion mask, the mode's table
@@ -138,13 +154,17 @@ struct Lane {
     __device__ __forceinline__ int row(int q) const { return wu * 32 + acc_row(q, half); }
     __device__ __forceinline__ int col(int bb) const { return wv * 64 + bb * 32 + li; }
 };
-struct Tile { int u0, v0, N; };               // first node of the u tile and of the v tile; nodes of the graph
+struct Tile { int u0, v0, N, nu; };           // first node of the u tile and of the v tile; nodes of the graph (RECT: rows of
+                                              // B, which the pair index a nB + b counts in, and nu = rows of A)
+template <bool RECT = false>
 __device__ __forceinline__ bool eligible(const unsigned* exm, const Tile T, int row, int vl) {
-    return T.u0 + row < T.v0 + vl && T.v0 + vl < T.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u);
+    const bool in = RECT ? T.u0 + row < T.nu : T.u0 + row < T.v0 + vl;      // a rectangle has no u < v and no diagonal
+    return in && T.v0 + vl < T.N && !((exm[row * 4 + (vl >> 5)] >> (vl & 31)) & 1u);
 }
 
 // HIST: the digit of pass `pass` of the keys that carry the threshold's higher digits, counted in the LDS bins
 struct Digit { int shift, hs; unsigned dmask; u64 prefix; };      // hs: bits below the chosen prefix
+template <bool RECT = false>
 __device__ __forceinline__ void hist_epilogue(const f32x16 (&term)[2], const unsigned* exm, unsigned* bins, const Lane L, const Tile T,
                                               float min_logit, const Digit D) {
 #pragma unroll
@@ -154,7 +174,7 @@ __device__ __forceinline__ void hist_epilogue(const f32x16 (&term)[2], const uns
         for (int q = 0; q < 16; ++q) {
             const int row = L.row(q);
             const float x = term[bb][q];
-            bool ok = eligible(exm, T, row, vl) && x >= min_logit;
+            bool ok = eligible<RECT>(exm, T, row, vl) && x >= min_logit;
             const u64 key = make_key(x, (unsigned)(T.u0 + row) * (unsigned)T.N + (unsigned)(T.v0 + vl));
             if (D.hs < 64) ok = ok && (key >> D.hs) == (D.prefix >> D.hs);
             const unsigned dg = (unsigned)(key >> D.shift) & D.dmask;
@@ -180,6 +200,7 @@ __device__ __forceinline__ void hist_flush(const unsigned* bins, unsigned* hist,
 }
 
 // EMIT: every candidate at or above the threshold key, appended in arrival order (order_kernel sorts)
+template <bool RECT = false>
 __device__ __forceinline__ void emit_epilogue(const f32x16 (&term)[2], const unsigned* exm, const Lane L, const Tile T, float min_logit,
                                               u64 threshold, State* state, u64* keys, int m) {
 #pragma unroll
@@ -189,7 +210,7 @@ __device__ __forceinline__ void emit_epilogue(const f32x16 (&term)[2], const uns
         for (int q = 0; q < 16; ++q) {
             const int row = L.row(q);
             const float x = term[bb][q];
-            const bool ok = eligible(exm, T, row, vl) && x >= min_logit;
+            const bool ok = eligible<RECT>(exm, T, row, vl) && x >= min_logit;
             const u64 key = make_key(x, (unsigned)(T.u0 + row) * (unsigned)T.N + (unsigned)(T.v0 + vl));
             if (ok && key >= threshold) {
                 const unsigned slot = atomicAdd(&state->emitted, 1u);
@@ -217,8 +238,15 @@ __device__ __forceinline__ void count_flush(const CountArgs& C, u64 ncount, u64 
 // last step, and the row threads OR the exclusion into it where the unfiltered kernel starts from zero.
 // P: planes per operand, 3 (fp32 tables, split_rows) or 1 (bf16 tables, copy_rows); it reaches the staging and the products
 // only.  The one-plane step keeps the 32-column width: k-blocks are added in ascending k exactly as in the three-plane step.
-template <int MODE, bool FILT = false, int P = 3>
+// RECT (dl_score_mine_between, dl_score_links_between; the modes HIST_RECT, EMIT_RECT, DEG_RECT, FILL_RECT — further values
+// of the mode, not a further template parameter, so that no existing kernel changes its name): the u side reads table A
+// (A.N rows, A.nt tiles), the v side table B (A.rect), every tile pair of the ntA x ntB grid in row-major order.  A pair is in range iff a < nA and
+// b < nB: no u < v, no diagonal; the exclusion CSR has the rows of A and B-local columns, the rule reads the groups of A for
+// the rows and of B for the columns, the pair index is a nB + b, and the link modes keep one cell array and one CSR per side.
+template <int MODE_, bool FILT = false, int P = 3>
 __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
+    constexpr bool RECT = MODE_ >= HIST_RECT;                  // the rectangular form of ...
+    constexpr int MODE = base_mode(MODE_);                     // ... this mode, which is all the body below asks for
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][P][TT][SLD]
     __bf16* vs = us + 2 * P * TT * SLD;
@@ -246,11 +274,15 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
     if constexpr (KEYED) threshold = A.state->prefix;
     const int p0 = (int)blockIdx.x * A.per_wg;
     // COUNT serves tile-pair counts close to 2^31, where p0 + per_wg would overflow; the other modes keep their form (N <= 46,340)
-    const int ntl = MODE == COUNT ? max(0, min(A.per_wg, A.pairs - p0)) : max(0, min(A.pairs, p0 + A.per_wg) - p0);
+    const int ntl = MODE == COUNT || RECT ? max(0, min(A.per_wg, A.pairs - p0)) : max(0, min(A.pairs, p0 + A.per_wg) - p0);
     if (ntl == 0) return;
-    // tile pair p0 in the row-major order of (qt, ct >= qt)
+    // tile pair p0 in the row-major order of (qt, ct >= qt); RECT: of the whole ntA x ntB grid
+    const int ntc = RECT ? A.rect.nt : A.nt;                    // tiles of the v side
     int qt = 0, ct = 0;
-    {
+    if constexpr (RECT) {
+        qt = p0 / ntc;
+        ct = p0 - qt * ntc;
+    } else {
         int rest = p0;
         while (rest >= A.nt - qt) {
             rest -= A.nt - qt;
@@ -258,7 +290,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         }
         ct = qt + rest;
     }
-    int qt2 = ct + 1 < A.nt ? qt : qt + 1, ct2 = ct + 1 < A.nt ? ct + 1 : qt + 1;      // the pair after it
+    int qt2 = ct + 1 < ntc ? qt : qt + 1, ct2 = ct + 1 < ntc ? ct + 1 : RECT ? 0 : qt + 1;      // the pair after it
 
     const int li = lane & 31, half = lane >> 5;
     const int wu = wave >> 1, wv = wave & 1;
@@ -294,7 +326,12 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         const __bf16* src = (r < nd ? A.cz : A.ch) + (size_t)k * A.cbatch;
         const int fq = j == jcur ? qt : qt2, fc = j == jcur ? ct : ct2;      // a fetch runs at most one pair ahead
         uq.fetch(src + plane_tile<SDC, P>(fq, dc, nd), tid);
-        vq.fetch(src + plane_tile<SDC, P>(fc, dc, nd), tid);
+        if constexpr (RECT) {
+            const __bf16* srb = (r < nd ? A.rect.cz : A.rect.ch) + (size_t)k * A.rect.cbatch;
+            vq.fetch(srb + plane_tile<SDC, P>(fc, dc, nd), tid);
+        } else {
+            vq.fetch(src + plane_tile<SDC, P>(fc, dc, nd), tid);
+        }
     };
     auto stash = [&](int s) {
         uq.stash(us + (s & 1) * P * TT * SLD, tid);
@@ -318,7 +355,12 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         unsigned char gb = 0;                                   // FILT: group of node tid of (v tile | u tile), on its way to LDS
         if constexpr (FILT) {
             const int node = (tid < TT ? ct * TT : (qt - 1) * TT) + tid;
-            if (rem == per_tile - 2 && tid < 2 * TT && node < A.N) gb = A.filt.group[node];
+            if constexpr (RECT) {                               // each side against its own length, from its own array
+                if (rem == per_tile - 2 && tid < 2 * TT && node < (tid < TT ? A.rect.N : A.N))
+                    gb = (tid < TT ? A.rect.group : A.filt.group)[node];
+            } else {
+                if (rem == per_tile - 2 && tid < 2 * TT && node < A.N) gb = A.filt.group[node];
+            }
         }
         const __bf16* ub = gram_operand<P>(us, s, wu * 32 + li, half);
         const __bf16* vb = gram_operand<P>(vs, s, wv * 64 + li, half);
@@ -342,7 +384,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         if (rem != per_tile - 1) continue;
 
         // ---- tile pair complete: term[bb][q] = s(u = qt*128 + wu*32 + acc_row(q, half), v = ct*128 + wv*64 + bb*32 + li)
-        const Tile T = {qt * TT, ct * TT, A.N};
+        const Tile T = {qt * TT, ct * TT, RECT ? A.rect.N : A.N, A.N};
         if (tid < TT) {                                         // this tile's excluded columns of row u0 + tid
             unsigned* m = exm + tid * 4;
             if constexpr (!FILT) m[0] = m[1] = m[2] = m[3] = 0u;
@@ -356,10 +398,14 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
             long long* ubase = reinterpret_cast<long long*>(bins + 2 * TT * 4), *vbase = ubase + TT;
             if (tid < TT) {
                 const int node = T.u0 + tid;
-                ubase[tid] = node < A.N ? (long long)A.link.rowptr[node] + (long long)A.link.cnt[(size_t)node * A.nt + ct] : 0ll;
+                ubase[tid] = node < A.N ? (long long)A.link.rowptr[node] + (long long)A.link.cnt[(size_t)node * ntc + ct] : 0ll;
             } else if (tid < 2 * TT) {
                 const int node = T.v0 + tid - TT;
-                vbase[tid - TT] = node < A.N ? (long long)A.link.rowptr[node] + (long long)A.link.cnt[(size_t)node * A.nt + qt] : 0ll;
+                if constexpr (RECT)                             // the B side's own CSR: cell (b, qt) of cnt [nB][ntA]
+                    vbase[tid - TT] = node < A.rect.N ? (long long)A.rect.link.rowptr[node] +
+                                                        (long long)A.rect.link.cnt[(size_t)node * A.nt + qt] : 0ll;
+                else
+                    vbase[tid - TT] = node < A.N ? (long long)A.link.rowptr[node] + (long long)A.link.cnt[(size_t)node * A.nt + qt] : 0ll;
             }
         }
         __syncthreads();
@@ -383,7 +429,8 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const int row = rbase + acc_row(q, 0), u = T.u0 + row;
-                    bool ok = u < v && v < A.N && !((exm[row * 4 + vw] >> li) & 1u) && term[bb][q] >= A.min_logit;
+                    bool ok = (RECT ? u < A.N && v < A.rect.N : u < v && v < A.N) && !((exm[row * 4 + vw] >> li) & 1u) &&
+                              term[bb][q] >= A.min_logit;
                     if constexpr (KEYED) ok = ok && make_key(term[bb][q], (unsigned)u * (unsigned)A.N + (unsigned)v) >= threshold;
                     const u64 b = __ballot(ok);
                     if (li == 0) pm[row * 4 + vw] = half ? (unsigned)(b >> 32) : (unsigned)b;
@@ -395,7 +442,7 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                 if (half == 0) pmt[vl * 4 + swu] = rows;
             }
             __syncthreads();
-            const bool diag = qt == ct;
+            const bool diag = !RECT && qt == ct;                // RECT: never; its diag branches fold away
             if constexpr (DEGS) {
                 // cell (u, ct) from the rows, cell (v, qt) from the columns; on the diagonal both sides of a node are one cell.
                 // Every cell of every node < N is written once, by the one workgroup that forms its tile pair, zeros included.
@@ -407,11 +454,16 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                         const unsigned* wt = pmt + tid * 4;
                         c += __popc(wt[0]) + __popc(wt[1]) + __popc(wt[2]) + __popc(wt[3]);
                     }
-                    if (node < A.N) A.link.cnt[(size_t)node * A.nt + ct] = c;
+                    if (node < A.N) A.link.cnt[(size_t)node * ntc + ct] = c;
                 } else if (tid < 2 * TT && !diag) {
                     const int node = T.v0 + tid - TT;
                     const unsigned* wt = pmt + (tid - TT) * 4;
-                    if (node < A.N) A.link.cnt[(size_t)node * A.nt + qt] = __popc(wt[0]) + __popc(wt[1]) + __popc(wt[2]) + __popc(wt[3]);
+                    if constexpr (RECT) {                       // cell (b, qt) of the B side's cnt [nB][ntA]
+                        if (node < A.rect.N)
+                            A.rect.link.cnt[(size_t)node * A.nt + qt] = __popc(wt[0]) + __popc(wt[1]) + __popc(wt[2]) + __popc(wt[3]);
+                    } else {
+                        if (node < A.N) A.link.cnt[(size_t)node * A.nt + qt] = __popc(wt[0]) + __popc(wt[1]) + __popc(wt[2]) + __popc(wt[3]);
+                    }
                 }
             } else {
                 // slot of (u, v) in row u: the cell's start, on the diagonal the smaller neighbours of u first, then the passed
@@ -442,7 +494,13 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
                             A.link.logit[su] = x;
                             if (A.link.prob != nullptr) A.link.prob[su] = pr;
                         }
-                        if ((u64)sv < (u64)A.link.nnz) {
+                        if constexpr (RECT) {                   // (b, a) in the B side's CSR, under its own nnz
+                            if ((u64)sv < (u64)A.rect.link.nnz) {
+                                A.rect.link.col[sv] = u;
+                                A.rect.link.logit[sv] = x;
+                                if (A.link.prob != nullptr) A.rect.link.prob[sv] = pr;
+                            }
+                        } else if ((u64)sv < (u64)A.link.nnz) {
                             A.link.col[sv] = u;
                             A.link.logit[sv] = x;
                             if (A.link.prob != nullptr) A.link.prob[sv] = pr;
@@ -452,8 +510,8 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
             }
         } else {
             const Lane L = {wu, wv, li, half, lane};
-            if constexpr (MODE == HIST) hist_epilogue(term, exm, bins, L, T, A.min_logit, D);
-            else if constexpr (MODE == EMIT) emit_epilogue(term, exm, L, T, A.min_logit, D.prefix, A.state, A.sel.keys, A.sel.m);
+            if constexpr (MODE == HIST) hist_epilogue<RECT>(term, exm, bins, L, T, A.min_logit, D);
+            else if constexpr (MODE == EMIT) emit_epilogue<RECT>(term, exm, L, T, A.min_logit, D.prefix, A.state, A.sel.keys, A.sel.m);
             else {
                 // COUNT: the place of every candidate among the sorted targets: lo = targets strictly below it (they count it
                 // as "greater": +1 at gcnt[lo], summed from the top on the host), and the equal range, if any, starts at lo.
@@ -511,8 +569,8 @@ __global__ __launch_bounds__(MTHR) void scan_tiles(ScanArgs A) {
         ++jcur;                                                 // on to the next pair (uniform; fetches are already there)
         qt = qt2;
         ct = ct2;
-        qt2 = ct + 1 < A.nt ? qt : qt + 1;
-        ct2 = ct + 1 < A.nt ? ct + 1 : qt + 1;
+        qt2 = ct + 1 < ntc ? qt : qt + 1;
+        ct2 = ct + 1 < ntc ? ct + 1 : RECT ? 0 : qt + 1;
     }
     if constexpr (MODE == HIST) hist_flush(bins, A.sel.hist, tid);
     if constexpr (MODE == COUNT) count_flush(A.cnt, ncount, nabove, lane);
@@ -919,6 +977,183 @@ int score_links_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* e
         launch_tiles<FILL>(p, a, nf, st);
     }
     return check_launch("score_links_fill");
+}
+
+// ---- dl_score_mine_between / dl_score_links_between: rows of a table A against rows of a table B (the RECT instantiations).
+// The same select, ordering, offsets and epilogues over the ntA x ntB grid of tile pairs, the pair index a nB + b local to the
+// rectangle; a graph past the cap of the triangular walk is the union of its diagonal blocks (the entries above on row
+// slices) and of such rectangles, merged by the caller (scans.py).
+struct RectPlan { int nd, ntA, ntB, pairs, per_wg, grid; size_t cbatchA, cbatchB; dl_dtype dt; };
+static RectPlan rect_plan(int nA, int nB, int d, dl_dtype dt = DL_F32) {
+    RectPlan p;
+    p.nd = (d + SDC - 1) / SDC;
+    p.ntA = (nA + TT - 1) / TT;
+    p.ntB = (nB + TT - 1) / TT;
+    const long long pairs = (long long)p.ntA * p.ntB;           // <= 363^2
+    p.pairs = (int)pairs;
+    const long long per_cu = 8LL * device_cus();                // the run length of mine_plan
+    const int want = config().mine_tiles > 0 ? config().mine_tiles : (int)((pairs + per_cu - 1) / per_cu);
+    p.per_wg = max(1, min(want, max(1, p.pairs)));
+    p.grid = (int)((pairs + p.per_wg - 1) / p.per_wg);
+    p.cbatchA = table_plane_elems(dt, nA, d);
+    p.cbatchB = table_plane_elems(dt, nB, d);
+    p.dt = dt;
+    return p;
+}
+struct RectPlanes { __bf16 *za, *ha, *zb, *hb; };
+static RectPlanes rect_planes(const RectPlan& p, int K, Carver& c) {
+    RectPlanes w;
+    w.za = c.take<__bf16>((size_t)K * p.cbatchA);
+    w.ha = c.take<__bf16>((size_t)K * p.cbatchA);
+    w.zb = c.take<__bf16>((size_t)K * p.cbatchB);
+    w.hb = c.take<__bf16>((size_t)K * p.cbatchB);
+    return w;
+}
+static void rect_split(const RectPlan& p, const RectPlanes& w, const void* ZA, const void* HA, const void* ZB, const void* HB, int nA,
+                       int nB, int K, int d, hipStream_t st) {
+    table_planes(ZA, p.dt, nullptr, nA, K, d, w.za, st);
+    table_planes(HA, p.dt, nullptr, nA, K, d, w.ha, st);
+    table_planes(ZB, p.dt, nullptr, nB, K, d, w.zb, st);
+    table_planes(HB, p.dt, nullptr, nB, K, d, w.hb, st);
+}
+// the rule of a rectangle as the kernels take it: the groups of A and the allow table where the triangular scans have theirs
+static FilterArgs between_filter_args(const dl_node_filter_between* nf) {
+    return nf != nullptr ? FilterArgs{nf->group_a, (const u64*)nf->allow, nf->n_groups} : FilterArgs{nullptr, nullptr, 0};
+}
+static ScanArgs rect_args(const RectPlan& p, const RectPlanes& w, int nA, int nB, int K, float t, const int32_t* exr, const int32_t* exc,
+                          float min_logit, const dl_node_filter_between* nf) {
+    ScanArgs a = {};
+    a.cz = w.za; a.ch = w.ha; a.cbatch = p.cbatchA;
+    a.N = nA; a.K = K; a.nd = p.nd; a.nt = p.ntA; a.t = t;
+    a.ex_rowptr = exr; a.ex_col = exc;
+    a.min_logit = min_logit;
+    a.pairs = p.pairs; a.per_wg = p.per_wg;
+    a.filt = between_filter_args(nf);
+    a.rect.cz = w.zb; a.rect.ch = w.hb; a.rect.cbatch = p.cbatchB;
+    a.rect.N = nB; a.rect.nt = p.ntB;
+    a.rect.group = nf != nullptr ? nf->group_b : nullptr;
+    return a;
+}
+template <int MODE>
+static void launch_rect(const RectPlan& p, const ScanArgs& a, bool filtered, hipStream_t st) {
+    if (p.dt == DL_BF16) {
+        if (filtered) launch_lds<scan_tiles<rect_mode(MODE), true, 1>>((unsigned)p.grid, MTHR, lds_bytes(MODE, 1) + FILTER_LDS_BYTES, st, a);
+        else launch_lds<scan_tiles<rect_mode(MODE), false, 1>>((unsigned)p.grid, MTHR, lds_bytes(MODE, 1), st, a);
+    } else {
+        if (filtered) launch_lds<scan_tiles<rect_mode(MODE), true, 3>>((unsigned)p.grid, MTHR, lds_bytes(MODE, 3) + FILTER_LDS_BYTES, st, a);
+        else launch_lds<scan_tiles<rect_mode(MODE), false, 3>>((unsigned)p.grid, MTHR, lds_bytes(MODE, 3), st, a);
+    }
+}
+
+// out = nd, tiles of A, tiles of B, tile pairs, tile pairs per workgroup, workgroups of a scan, scans at most (digits + emit),
+// byte offset of the 32-bit count of scans that ran inside the (256-byte aligned) workspace
+void score_mine_between_form(int nA, int nB, int d, int* out) {
+    const RectPlan p = rect_plan(nA, nB, d);
+    out[0] = p.nd;
+    out[1] = p.ntA;
+    out[2] = p.ntB;
+    out[3] = p.pairs;
+    out[4] = p.per_wg;
+    out[5] = p.grid;
+    out[6] = PASSES + 1;
+    out[7] = (int)offsetof(State, scans);
+}
+
+// Workspace (256-byte aligned blocks): selection state | histogram | keys [m] | planes of ZA, HA, ZB, HB
+struct MineBetweenWs { State* state; unsigned* hist; u64* keys; RectPlanes pl; size_t bytes; };
+static MineBetweenWs mine_between_carve(const RectPlan& p, int K, int m, void* ws) {
+    MineBetweenWs w = {};
+    Carver c(ws);
+    w.state = c.take<State>(1);
+    w.hist = c.take<unsigned>(BINS);
+    w.keys = c.take<u64>((size_t)m);
+    w.pl = rect_planes(p, K, c);
+    w.bytes = c.bytes();
+    return w;
+}
+
+size_t score_mine_between_workspace_bytes(int nA, int nB, int K, int d, int m, dl_dtype dt) {
+    return mine_between_carve(rect_plan(nA, nB, d, dt), K, m, nullptr).bytes;
+}
+
+int score_mine_between(const void* ZA, const void* HA, const void* ZB, const void* HB, dl_dtype dt, int nA, int nB, int K, int d, float t,
+                       const int32_t* exr, const int32_t* exc, float min_logit, int m, int32_t* src, int32_t* dst, float* logit,
+                       float* prob, int64_t* count, void* ws, hipStream_t st, const dl_node_filter_between* nf) {
+    const RectPlan p = rect_plan(nA, nB, d, dt);
+    const MineBetweenWs w = mine_between_carve(p, K, m, ws);
+    hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, m);
+    rect_split(p, w.pl, ZA, HA, ZB, HB, nA, nB, K, d, st);
+    ScanArgs a = rect_args(p, w.pl, nA, nB, K, t, exr, exc, min_logit, nf);
+    a.state = w.state;
+    a.sel.m = m; a.sel.hist = w.hist; a.sel.keys = w.keys;
+    for (int pass = 0; pass < PASSES; ++pass) {
+        a.sel.pass = pass;
+        launch_rect<HIST>(p, a, nf != nullptr, st);
+        hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
+    }
+    launch_rect<EMIT>(p, a, nf != nullptr, st);
+    hipLaunchKernelGGL(order_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.state, w.keys, nB, m, src, dst, logit, prob,
+                       count);                                  // the pair index decodes with nB: src A-local, dst B-local
+    return check_launch("score_mine_between");
+}
+
+// out = the first six fields of score_mine_between_form, scans of count + fill, cells of the A side, cells of the B side
+void score_links_between_form(int nA, int nB, int d, int* out) {
+    score_mine_between_form(nA, nB, d, out);
+    const RectPlan p = rect_plan(nA, nB, d);
+    out[6] = 2;
+    out[7] = nA * p.ntB;                                        // <= 46,340 * 363
+    out[8] = nB * p.ntA;
+}
+
+// Workspace (256-byte aligned blocks): planes of ZA, HA, ZB, HB | cnt_a [nA][ntB] | cnt_b [nB][ntA] | deg_a [nA] | deg_b [nB]
+struct LinksBetweenWs { RectPlanes pl; unsigned *cnt_a, *cnt_b, *deg_a, *deg_b; size_t bytes; };
+static LinksBetweenWs links_between_carve(const RectPlan& p, int nA, int nB, int K, void* ws) {
+    LinksBetweenWs w = {};
+    Carver c(ws);
+    w.pl = rect_planes(p, K, c);
+    w.cnt_a = c.take<unsigned>((size_t)nA * p.ntB);
+    w.cnt_b = c.take<unsigned>((size_t)nB * p.ntA);
+    w.deg_a = c.take<unsigned>((size_t)nA);
+    w.deg_b = c.take<unsigned>((size_t)nB);
+    w.bytes = c.bytes();
+    return w;
+}
+
+size_t score_links_between_workspace_bytes(int nA, int nB, int K, int d, dl_dtype dt) {
+    return links_between_carve(rect_plan(nA, nB, d, dt), nA, nB, K, nullptr).bytes;
+}
+
+int score_links_between_count(const void* ZA, const void* HA, const void* ZB, const void* HB, dl_dtype dt, int nA, int nB, int K, int d,
+                              float t, const int32_t* exr, const int32_t* exc, float min_logit, const dl_node_filter_between* nf,
+                              void* ws, int64_t* rowptr_a, int64_t* rowptr_b, hipStream_t st) {
+    const RectPlan p = rect_plan(nA, nB, d, dt);
+    const LinksBetweenWs w = links_between_carve(p, nA, nB, K, ws);
+    rect_split(p, w.pl, ZA, HA, ZB, HB, nA, nB, K, d, st);
+    ScanArgs a = rect_args(p, w.pl, nA, nB, K, t, exr, exc, min_logit, nf);
+    a.link.cnt = w.cnt_a;
+    a.rect.link.cnt = w.cnt_b;
+    launch_rect<DEG>(p, a, nf != nullptr, st);
+    hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((nA + 3) / 4)), dim3(256), 0, st, w.cnt_a, w.deg_a, nA, p.ntB);
+    hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((nB + 3) / 4)), dim3(256), 0, st, w.cnt_b, w.deg_b, nB, p.ntA);
+    hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, w.deg_a, rowptr_a, nA, 1);
+    hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, w.deg_b, rowptr_b, nB, 1);
+    return check_launch("score_links_between_count");
+}
+
+int score_links_between_fill(dl_dtype dt, int nA, int nB, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
+                             const dl_node_filter_between* nf, void* ws, const int64_t* rowptr_a, const int64_t* rowptr_b,
+                             long long nnz_a, int32_t* col_a, float* logit_a, float* prob_a, long long nnz_b, int32_t* col_b,
+                             float* logit_b, float* prob_b, hipStream_t st) {
+    const RectPlan p = rect_plan(nA, nB, d, dt);
+    const LinksBetweenWs w = links_between_carve(p, nA, nB, K, ws);
+    if (nnz_a > 0 || nnz_b > 0) {                               // a side of length 0 takes no write: every slot is >= its nnz
+        ScanArgs a = rect_args(p, w.pl, nA, nB, K, t, exr, exc, min_logit, nf);
+        a.link = LinkArgs{w.cnt_a, rowptr_a, nnz_a, col_a, logit_a, prob_a};
+        a.rect.link = LinkArgs{w.cnt_b, rowptr_b, nnz_b, col_b, logit_b, prob_b};
+        launch_rect<FILL>(p, a, nf != nullptr, st);
+    }
+    return check_launch("score_links_between_fill");
 }
 
 // ---- dl_score_links_top: the m best candidates as that CSR — the select of score_mine (no EMIT, no ordering), then the link

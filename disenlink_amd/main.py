@@ -69,12 +69,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "(Disentangle.missing_link_ranks; single GPU, fp32 tables)")
     p.add_argument("--mine", type=int, default=0, metavar="M",
                    help="after the last run, list the M (<= 65536) most likely links of the whole graph that are not dataset "
-                        "edges (Disentangle.top_missing_links; single GPU, fp32 tables)")
+                        "edges (Disentangle.top_missing_links; single GPU, fp32 tables; graphs of more than 46340 nodes are "
+                        "scanned by blocks of 46208)")
     p.add_argument("--mine-out", type=str, default=None, metavar="FILE",
                    help="with --mine: write the list to FILE as text, one `src dst logit prob` line per pair")
     p.add_argument("--predict-links", type=float, default=None, metavar="P",
                    help="after the last run, form the predicted graph: every pair that is not a dataset edge and whose "
-                        "link_pred reaches P (Disentangle.predicted_links; single GPU, fp32 tables, N <= 46340), and print "
+                        "link_pred reaches P (Disentangle.predicted_links; single GPU, fp32 tables; graphs of more than 46340 "
+                        "nodes are scanned by blocks of 46208), and print "
                         "the number of links, the density and the mean / max predicted degree")
     p.add_argument("--predict-top", type=int, default=None, metavar="M",
                    help="after the last run, form the predicted graph under a budget: the M most likely pairs that are not "

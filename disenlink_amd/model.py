@@ -452,34 +452,47 @@ class Disentangle(nn.Module):
         Z, H = self._rank_tables(x, adj, table_dtype)
         return ops.score_ranks(Z, H, float(self.temperature), src, dst, exclude, node_filter, self._scan_dtype(table_dtype))
 
-    def top_missing_links(self, x, adj, m: int, exclude=None, min_prob=None, node_filter=None, table_dtype=None) -> MinedLinks:
+    def top_missing_links(self, x, adj, m: int, exclude=None, min_prob=None, node_filter=None, table_dtype=None,
+                          block_nodes=None) -> MinedLinks:
         """The m most likely links of the WHOLE graph that are not known yet: MinedLinks(src, dst int32 [c], logit, prob
         f32 [c]) with src < dst, c = min(m, eligible pairs), ranked by the pre-sigmoid logit of link_pred over all
         unordered pairs (ops.score_mine; nothing of size N x N is formed).  ``exclude``: the known pairs, as a Graph, a
         dense [N,N] mask or (rows, cols), in either orientation; None = the edges of ``adj`` itself.  ``min_prob``: keep
         only pairs with link_pred >= min_prob (turned into a logit floor on the host: 0.5 -> 0.0).  ``node_filter``: a
-        symmetric ops.NodeFilter, a rule on node groups that pairs must pass as well."""
+        symmetric ops.NodeFilter, a rule on node groups that pairs must pass as well.  Graphs of more than 46,340 nodes
+        (or any graph, with ``block_nodes``: rows per block, a multiple of 128) are scanned by blocks
+        (ops.score_mine_blocks): the same list, equal logits ordered by the 64-bit src * N + dst."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
         Z, H = self._rank_tables(x, graph, table_dtype)
         floor = self._logit_floor(min_prob)
+        known = graph if exclude is None else exclude
         with torch.no_grad():
-            return MinedLinks(*ops.score_mine(Z, H, float(self.temperature), m, graph if exclude is None else exclude, floor,
-                                              node_filter, self._scan_dtype(table_dtype)))
+            if block_nodes is not None or int(Z.shape[0]) > ops.MINE_MAX_N:
+                return MinedLinks(*ops.score_mine_blocks(Z, H, float(self.temperature), m, known, floor, node_filter,
+                                                         self._scan_dtype(table_dtype), block_nodes))
+            return MinedLinks(*ops.score_mine(Z, H, float(self.temperature), m, known, floor, node_filter,
+                                              self._scan_dtype(table_dtype)))
 
-    def predicted_links(self, x, adj, min_prob, exclude=None, node_filter=None, table_dtype=None) -> PredictedLinks:
+    def predicted_links(self, x, adj, min_prob, exclude=None, node_filter=None, table_dtype=None,
+                        block_nodes=None) -> PredictedLinks:
         """The predicted graph: EVERY unordered pair whose link_pred reaches ``min_prob`` and that is not known yet, as
         PredictedLinks(rowptr, col, logit, prob), a symmetric CSR over all nodes with ``.degree``, ``.pairs()`` and
         ``.to_graph()`` (ops.score_links: two scans, nothing of size N x N is formed, no cap on the number of links).
         ``exclude``: the known pairs, as a Graph, a dense [N,N] mask or (rows, cols), in either orientation; None = the
         edges of ``adj`` itself.  ``min_prob`` in [0, 1] is turned into a logit floor on the host, as in
         ``top_missing_links`` (0.5 -> 0.0).  ``node_filter``: a symmetric ops.NodeFilter that pairs must pass as well.
-        N <= 46,340."""
+        Graphs of more than 46,340 nodes (or any graph, with ``block_nodes``: rows per block, a multiple of 128) are
+        scanned by blocks (ops.score_links_blocks): the same CSR."""
         graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
         Z, H = self._rank_tables(x, graph, table_dtype)
         floor = self._logit_floor(float(min_prob))
+        known = graph if exclude is None else exclude
         with torch.no_grad():
-            return PredictedLinks(*ops.score_links(Z, H, float(self.temperature), floor, graph if exclude is None else exclude,
-                                                   node_filter, self._scan_dtype(table_dtype)))
+            if block_nodes is not None or int(Z.shape[0]) > ops.LINKS_MAX_N:
+                return PredictedLinks(*ops.score_links_blocks(Z, H, float(self.temperature), floor, known, node_filter,
+                                                              self._scan_dtype(table_dtype), block_nodes))
+            return PredictedLinks(*ops.score_links(Z, H, float(self.temperature), floor, known, node_filter,
+                                                   self._scan_dtype(table_dtype)))
 
     def top_predicted_links(self, x, adj, m: int, exclude=None, min_prob=None, node_filter=None,
                             table_dtype=None) -> PredictedLinks:

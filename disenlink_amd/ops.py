@@ -19,9 +19,11 @@ from ._dev import _POISON, _Workspace, _empty, _empty_like, _f32c, _need_cuda, _
 from .features import SparseFeatures
 from .graph import Graph, PairList
 from .scans import (                                                    # noqa: F401  (the all-pairs scans: ops.score_* as before)
-    LINKS_MAX_N, MINE_MAX_M, MINE_MAX_N, RANK_MAX_K, NodeFilter, PairExclusion, PairTerms, exclusion_csr, pair_exclusion,
-    score_link_degrees, score_links, score_mine, score_pair_logits, score_pair_ranks, score_pair_ranks_counted,
-    score_pair_terms, score_ranks, score_top_links, score_topk)
+    BETWEEN_MAX_N, BLOCK_NODES, BLOCKS_MAX_N, LINKS_MAX_N, MINE_MAX_M, MINE_MAX_N, RANK_MAX_K, LinksBetween, NodeFilter,
+    PairExclusion, PairTerms, bipartite_exclusion_csr, exclusion_csr, pair_exclusion, score_link_degrees,
+    score_link_degrees_blocks, score_links, score_links_between, score_links_blocks, score_mine, score_mine_between,
+    score_mine_blocks, score_pair_logits, score_pair_ranks, score_pair_ranks_counted, score_pair_terms, score_ranks,
+    score_top_links, score_topk)
 
 
 def _tab(t: torch.Tensor):

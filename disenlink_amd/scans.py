@@ -1,6 +1,7 @@
 """The all-pairs inference scans over libdisenlink_hip.so: top-k and ranks of a node's candidates, mining, the
 thresholded and the budgeted link graph, pair ranks, and the logits and per-factor terms of given pairs — with the exclusion sets and
-node-group rules they take.  Nothing here is differentiable.
+node-group rules they take — and, at the end, mining and the link graph between two node sets and by blocks on graphs of
+any size.  Nothing here is differentiable.
 
 Every scan goes through ONE C entry, ``dl_score_<name>_dtype`` (the implementation; the plain and ``_filtered`` entries
 of the C ABI forward to it), sized by ``dl_score_<name>_workspace_bytes_dtype``; each writes its argument list once,
@@ -639,3 +640,377 @@ def score_pair_ranks(Z, H, t: float, src, dst, exclude=None, node_filter=None, t
     ``node_filter`` (a symmetric ``NodeFilter``): the candidates are the pairs the rule allows outside ``exclude``; a target
     is ranked whether or not it is allowed."""
     return score_pair_ranks_counted(Z, H, t, src, dst, exclude, node_filter, table_dtype)[:4]
+
+
+# ---------------------------------------------------------------------- two node sets: rows of A against rows of B (RECT scans)
+BETWEEN_MAX_N = MINE_MAX_N
+BLOCK_NODES = 46208                                                    # the default block of the *_blocks scans: 361 tiles
+BLOCKS_MAX_N = 8388480                                                 # DL_SCORE_PAIR_RANKS_MAX_N
+
+
+def bipartite_exclusion_csr(exclude, nA: int, nB: int, device=None):
+    """An exclusion set between two node sets as the CSR the rectangular scans take: (rowptr int32 [nA+1], col int32) with
+    B-local, strictly ascending columns per row of A, or (None, None) for ``exclude=None``.  ``exclude``: ``(rows_a,
+    cols_b)`` index sequences or a dense [nA, nB] mask (entries != 0).  Duplicates collapse."""
+    if exclude is None:
+        return None, None
+    nA, nB = int(nA), int(nB)
+    if isinstance(exclude, (tuple, list)):
+        if len(exclude) != 2:
+            raise ValueError("an exclusion pair list is (rows_a, cols_b)")
+        rows, cols = (torch.as_tensor(v, device=device).reshape(-1).to(torch.int64) for v in exclude)
+        if rows.numel() != cols.numel():
+            raise ValueError("exclusion rows and cols differ in length")
+        if rows.numel() and (int(rows.min()) < 0 or int(cols.min()) < 0 or int(rows.max()) >= nA or int(cols.max()) >= nB):
+            raise ValueError(f"exclusion pair outside [0, {nA}) x [0, {nB})")
+    else:
+        m = torch.as_tensor(exclude, device=device)
+        if m.dim() != 2 or tuple(m.shape) != (nA, nB):
+            raise ValueError(f"an exclusion mask must be [nA, nB] = [{nA}, {nB}], got {tuple(m.shape)}")
+        rows, cols = torch.nonzero(m, as_tuple=True)
+    dev = rows.device if device is None else torch.device(device)
+    return _local_csr(*_split_keys(torch.unique(rows.to(dev) * nB + cols.to(dev)), nB), nA)
+
+
+def _split_keys(key: torch.Tensor, n_cols: int):
+    r = torch.div(key, n_cols, rounding_mode="floor")
+    return r, key - r * n_cols
+
+
+def _local_csr(rows: torch.Tensor, cols: torch.Tensor, n_rows: int):
+    """(rowptr int32 [n_rows+1], col int32) of int64 pairs already sorted by row, then column."""
+    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), dim=0)
+    return rowptr.to(torch.int32), cols.to(torch.int32)
+
+
+def _between_rule(rule, nA: int, nB: int, device):
+    """``rule`` = (groups_a [nA], groups_b [nB], allow [g, h]) -> (groups_a uint8, groups_b uint8, allow words int64 [n],
+    n): pair (a, b) is allowed iff allow[groups_a[a], groups_b[b]]; the row of A decides, so allow need not be symmetric."""
+    if not isinstance(rule, (tuple, list)) or len(rule) != 3:
+        raise TypeError("rule is (groups_a, groups_b, allow[g, h])")
+    ga, gb = (torch.as_tensor(v) for v in rule[:2])
+    allow = torch.as_tensor(rule[2]).detach().to("cpu") != 0
+    for g, n, what in ((ga, nA, "groups_a"), (gb, nB, "groups_b")):
+        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex or g.numel() != n:
+            raise ValueError(f"{what} must be a 1-D integer array of {n} entries, got {tuple(g.shape)} {g.dtype}")
+    if allow.dim() != 2 or not (1 <= allow.shape[0] <= 64 and 1 <= allow.shape[1] <= 64):
+        raise ValueError(f"allow must be [g, h] with 1 <= g, h <= 64, got {tuple(allow.shape)}")
+    for g, n, what in ((ga, int(allow.shape[0]), "groups_a"), (gb, int(allow.shape[1]), "groups_b")):
+        lo, hi = (int(v) for v in torch.stack(torch.aminmax(g.to(torch.int64))).tolist())
+        if lo < 0 or hi >= n:
+            raise ValueError(f"{what} outside [0, {n}): min {lo}, max {hi}")
+    n = int(max(allow.shape))
+    square = torch.zeros(n, n, dtype=torch.bool)
+    square[:allow.shape[0], :allow.shape[1]] = allow
+    return (ga.to(device=device, dtype=torch.uint8).contiguous(), gb.to(device=device, dtype=torch.uint8).contiguous(),
+            NodeFilter._pack(square).to(device), n)
+
+
+def _between_filter_arg(groups_a, groups_b, words, n_groups: int):
+    """(byref(dl_node_filter_between), keep-alive) of prepared device arrays."""
+    st = _lib.DlNodeFilterBetween(groups_a.data_ptr(), groups_b.data_ptr(), n_groups, words.data_ptr())
+    return C.byref(st), (st, groups_a, groups_b, words)
+
+
+def _between_tables(ZA, HA, ZB, HB, table_dtype):
+    if ZA.dim() == 3 and ZB.dim() == 3 and tuple(ZA.shape[1:]) != tuple(ZB.shape[1:]):
+        raise ValueError(f"tables A are {list(ZA.shape)}, tables B {list(ZB.shape)}: K and d must agree")
+    ZA, HA, nA, K, d = _rank_tables(ZA, HA, table_dtype)
+    ZB, HB, nB, _, _ = _rank_tables(ZB, HB, table_dtype)
+    if ZA.device != ZB.device:
+        raise ValueError(f"tables A on {ZA.device}, tables B on {ZB.device}")
+    for n, what in ((nA, "nA"), (nB, "nB")):
+        if n > BETWEEN_MAX_N:
+            raise ValueError(f"{what}={n} above {BETWEEN_MAX_N} (the pair index a nB + b of the rectangular scans)")
+    return ZA, HA, ZB, HB, nA, nB, K, d
+
+
+def _mine_between(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, m, excl, min_logit, nf):
+    """One rectangular mining call on prepared tables, exclusion CSR ``excl`` = (rowptr, col) and rule argument ``nf`` ->
+    (src A-local, dst B-local, logit, prob), cut to the count (the one host read)."""
+    dev = ZA.device
+    rp, cp, ws, _keep = _scan_buffers(excl, _scan_ws_bytes("mine_between", nA, nB, K, d, dt, m), dev)
+    src, dst = _empty(max(m, 0), torch.int32, dev), _empty(max(m, 0), torch.int32, dev)
+    logit, prob = _empty(max(m, 0), torch.float32, dev), _empty(max(m, 0), torch.float32, dev)
+    count = _empty(1, torch.int64, dev)
+    _scan_call("mine_between", ZA.data_ptr(), HA.data_ptr(), nA, ZB.data_ptr(), HB.data_ptr(), nB, K, d, dt, float(t), rp, cp,
+               float(min_logit), m, src.data_ptr(), dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(),
+               ws.data_ptr(), ws.numel(), _stream(), nf)
+    c = int(count.item())
+    return src[:c], dst[:c], logit[:c], prob[:c]
+
+
+def score_mine_between(ZA, HA, ZB, HB, t: float, m: int, exclude=None, min_logit: float = float("-inf"), rule=None,
+                       table_dtype=torch.float32):
+    """-> (src int32 [c], dst int32 [c], logit f32 [c], prob f32 [c]), c = min(m, eligible): the m best pairs (a, b) of rows
+    of tables A [nA,K,d] against rows of tables B [nB,K,d] — users x items, new nodes x old nodes — by the logit of
+    ``score_mine``, rows of A as the A operand: the bits ``score_pair_logits`` gives for (a, nA + b) on ``cat(A, B)``.  src
+    is A-local, dst B-local; the order is ``score_mine``'s (larger logit first, equal logits by src * nB + dst).  Every one of
+    the nA nB pairs is a candidate (there is no src < dst) unless it is in ``exclude`` (``(rows_a, cols_b)`` or a dense
+    [nA, nB] mask), forbidden by ``rule`` = (groups_a, groups_b, allow[g, h]) (allowed iff allow[groups_a[a], groups_b[b]];
+    it need not be symmetric) or below ``min_logit`` (NaN never is eligible).  1 <= m <= 65,536, nA, nB <= 46,340.  Only the
+    ceil(nA/128) x ceil(nB/128) tile pairs of the rectangle are formed (dl_score_mine_between_dtype), where
+    ``NodeFilter.between`` on the concatenated table walks (nA + nB)^2 / 2 products for the same result."""
+    dt = _scan_dtype(table_dtype)
+    ruled = None if rule is None else _between_rule(rule, int(ZA.shape[0]), int(ZB.shape[0]), ZA.device)      # its refusals first
+    ZA, HA, ZB, HB, nA, nB, K, d = _between_tables(ZA, HA, ZB, HB, table_dtype)
+    nf, _keep_nf = (None, ()) if ruled is None else _between_filter_arg(*ruled)
+    return _mine_between(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, int(m), bipartite_exclusion_csr(exclude, nA, nB, ZA.device),
+                         min_logit, nf)
+
+
+LinksBetween = namedtuple("LinksBetween", ["ab", "ba"])
+
+
+def _links_between_count(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, excl, min_logit, nf):
+    """The count pass of a rectangle -> (rowptr_a, rowptr_b, the arguments the fill shares with it, keep-alive)."""
+    dev = ZA.device
+    ex = _csr_args(*excl, dev)
+    ws = _empty(max(256, _scan_ws_bytes("links_between", nA, nB, K, d, dt)), torch.uint8, dev)      # held across the two calls
+    rowptr_a, rowptr_b = _empty(nA + 1, torch.int64, dev), _empty(nB + 1, torch.int64, dev)
+    head = (ZA.data_ptr(), HA.data_ptr(), nA, ZB.data_ptr(), HB.data_ptr(), nB, K, d, dt, float(t), ex[0], ex[1],
+            float(min_logit), nf, ws.data_ptr(), ws.numel(), rowptr_a.data_ptr(), rowptr_b.data_ptr())
+    _scan_call("links_between_count", *head, _stream())
+    return rowptr_a, rowptr_b, head, (ex, ws)
+
+
+def _links_between(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, excl, min_logit, nf) -> LinksBetween:
+    rowptr_a, rowptr_b, head, _keep = _links_between_count(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, excl, min_logit, nf)
+    nnz = int(rowptr_a[-1].item())                                    # the one host read: both sides hold every pair once
+    dev = ZA.device
+    sides = [[_empty(nnz, torch.int32, dev), _empty(nnz, torch.float32, dev), _empty(nnz, torch.float32, dev)] for _ in range(2)]
+    _scan_call("links_between_fill", *head, nnz, *(v.data_ptr() for v in sides[0]), nnz, *(v.data_ptr() for v in sides[1]),
+               _stream())
+    return LinksBetween((rowptr_a, *sides[0]), (rowptr_b, *sides[1]))
+
+
+def score_links_between(ZA, HA, ZB, HB, t: float, min_logit: float, exclude=None, rule=None,
+                        table_dtype=torch.float32) -> LinksBetween:
+    """-> LinksBetween(ab, ba), two (rowptr int64, col int32, logit f32, prob f32) tuples: EVERY pair (a, b) of rows of A
+    against rows of B whose logit reaches ``min_logit``, as the CSR of the A side (``ab``: rowptr [nA+1], columns = rows of
+    B) and of the B side (``ba``: rowptr [nB+1], columns = rows of A).  Every pair appears in both with the same bits,
+    columns ascending within a row, a -0 as +0.  Logit, eligibility, ``exclude`` and ``rule`` as in ``score_mine_between``;
+    two scans and the one host read of the number of pairs, as in ``score_links`` (dl_score_links_between_count_dtype /
+    _fill_dtype).  nA, nB <= 46,340."""
+    dt = _scan_dtype(table_dtype)
+    ruled = None if rule is None else _between_rule(rule, int(ZA.shape[0]), int(ZB.shape[0]), ZA.device)      # its refusals first
+    ZA, HA, ZB, HB, nA, nB, K, d = _between_tables(ZA, HA, ZB, HB, table_dtype)
+    nf, _keep_nf = (None, ()) if ruled is None else _between_filter_arg(*ruled)
+    return _links_between(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, bipartite_exclusion_csr(exclude, nA, nB, ZA.device), min_logit, nf)
+
+
+# ---------------------------------------------------------------------- any N: diagonal blocks and rectangles, merged on the host
+def _block_bounds(N: int, block_nodes):
+    bn = BLOCK_NODES if block_nodes is None else int(block_nodes)
+    if bn < 128 or bn % 128 or bn > BLOCK_NODES:
+        raise ValueError(f"block_nodes={bn}: a multiple of 128 in 128..{BLOCK_NODES}")
+    if N > BLOCKS_MAX_N:
+        raise ValueError(f"N={N} above {BLOCKS_MAX_N}")
+    return bn, [(lo, min(lo + bn, N)) for lo in range(0, N, bn)]
+
+
+class _BlockWindows:
+    """What the windows of a blocked scan share: the tables, the blocks, the exclusion set cut by window (ONE pass over the
+    pairs u < v: a stable sort by (block of u, block of v), then a slice per window, shifted to local ids) and the rule."""
+
+    def __init__(self, Z, H, t, exclude, node_filter, table_dtype, block_nodes):
+        self.dt = _scan_dtype(table_dtype)
+        _filter_check(node_filter, Z, True)                            # the host-side refusals, ahead of the tables' own
+        self.bn, self.blocks = _block_bounds(int(Z.shape[0]), block_nodes)
+        self.Z, self.H, self.N, self.K, self.d = _rank_tables(Z, H, table_dtype)
+        self.t, self.dev = float(t), self.Z.device
+        nb = len(self.blocks)
+        self.filter = node_filter
+        if node_filter is not None:
+            node_filter._c_arg(self.N, self.dev, True)                 # its refusals (device, symmetry), ahead of any launch
+        rowptr, col = _unordered_exclusion_csr(exclude, self.N, self.dev)
+        self.ex = None
+        if rowptr is not None and col.numel():
+            ptr = rowptr.to(torch.int64)
+            r = torch.repeat_interleave(torch.arange(self.N, device=ptr.device), ptr[1:] - ptr[:-1])
+            c = col.to(torch.int64)
+            keep = c > r                                               # (u, u) entries exclude nothing
+            r, c = r[keep], c[keep]
+            w = torch.div(r, self.bn, rounding_mode="floor") * nb + torch.div(c, self.bn, rounding_mode="floor")
+            order = torch.argsort(w, stable=True)                     # within a window: rows ascending, columns ascending
+            start = torch.zeros(nb * nb + 1, dtype=torch.int64)
+            start[1:] = torch.cumsum(torch.bincount(w, minlength=nb * nb), dim=0).cpu()      # one host read, nb^2 numbers
+            self.ex = (r[order], c[order], start.tolist())
+
+    def windows(self):
+        """(i, j) with i <= j, row-major: the pieces of every row block then arrive in ascending column blocks."""
+        nb = len(self.blocks)
+        return [(i, j) for i in range(nb) for j in range(i, nb)]
+
+    def tables(self, i):
+        lo, hi = self.blocks[i]
+        return self.Z[lo:hi], self.H[lo:hi]
+
+    def exclusion(self, i, j):
+        """The sub-CSR of window (i, j): rows local to block i, columns local to block j (None, None: nothing excluded)."""
+        if self.ex is None:
+            return None, None
+        r, c, start = self.ex
+        w = i * len(self.blocks) + j
+        s, e = start[w], start[w + 1]
+        if s == e:
+            return None, None
+        (lo_i, hi_i), (lo_j, _) = self.blocks[i], self.blocks[j]
+        return _local_csr(r[s:e] - lo_i, c[s:e] - lo_j, hi_i - lo_i)
+
+    def rule(self, i, j):
+        """The rule of window (i, j) as its entry takes it: a dl_node_filter on the group bytes of block i (diagonal), or a
+        dl_node_filter_between on those of blocks i and j; the unordered scans' symmetric allow words either way."""
+        f = self.filter
+        if f is None:
+            return None, ()
+        ga = f.groups[self.blocks[i][0]:self.blocks[i][1]]
+        if i == j:
+            st = _lib.DlNodeFilter(ga.data_ptr(), f.n_groups, f._pair_words.data_ptr())
+            return C.byref(st), (st, ga, f._pair_words)
+        return _between_filter_arg(ga, f.groups[self.blocks[j][0]:self.blocks[j][1]], f._pair_words, f.n_groups)
+
+
+def _merge_top(best, new, N: int, m: int):
+    """The m best of two lists of (src int64, dst int64, logit, prob) in the scans' total order: larger order key first,
+    equal keys by the 64-bit global pair index src * N + dst."""
+    if best is None:
+        cat = new
+    else:
+        cat = tuple(torch.cat((a, b)) for a, b in zip(best, new))
+    src, dst, logit, prob = cat
+    by_index = torch.argsort(src * N + dst, stable=True)
+    by_key = torch.argsort(_order_keys(logit[by_index]), stable=True, descending=True)
+    take = by_index[by_key][:m]
+    return src[take], dst[take], logit[take], prob[take]
+
+
+def score_mine_blocks(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf"), node_filter=None,
+                      table_dtype=torch.float32, block_nodes=None):
+    """``score_mine`` for ANY N up to 8,388,480: -> (src int32 [c], dst int32 [c], logit f32 [c], prob f32 [c]) with
+    src < dst in GLOBAL ids, c = min(m, eligible), larger logit first, equal logits by the 64-bit src * N + dst.  The nodes
+    are cut into contiguous blocks of ``block_nodes`` rows (a multiple of 128, default 46,208); every diagonal block goes
+    through dl_score_mine_dtype on its row slice, every pair of blocks i < j through dl_score_mine_between_dtype with block i
+    as A — the bits the triangular scan forms for u < v — and the windows' lists are merged with torch.  Once m pairs are
+    held, their last logit is the (inclusive) floor of the windows after, so ties survive.  For N <= 46,340 the result is bit
+    for bit ``score_mine``'s, for every block size.  Peak memory: the workspace of ONE window and O(N + m) arrays; one host
+    read per window (its count)."""
+    m = int(m)
+    if not 1 <= m <= MINE_MAX_M:
+        raise ValueError(f"m={m} outside 1..{MINE_MAX_M}")
+    W = _BlockWindows(Z, H, t, exclude, node_filter, table_dtype, block_nodes)
+    floor, best = float(min_logit), None
+    n0 = W.blocks[0][1] - W.blocks[0][0]                               # the shared workspace once, at the largest window's size
+    need = _scan_ws_bytes("mine", n0, W.K, W.d, W.dt, m)
+    if len(W.blocks) > 1:
+        need = max(need, _scan_ws_bytes("mine_between", n0, W.blocks[1][1] - W.blocks[1][0], W.K, W.d, W.dt, m))
+    _ws.get(max(256, need), W.dev)
+    for i, j in W.windows():
+        (lo_i, hi_i), (lo_j, hi_j) = W.blocks[i], W.blocks[j]
+        ZA, HA = W.tables(i)
+        nf, _keep_nf = W.rule(i, j)
+        excl = W.exclusion(i, j)
+        if i == j:
+            n = hi_i - lo_i
+            rp, cp, ws, _keep = _scan_buffers(excl, _scan_ws_bytes("mine", n, W.K, W.d, W.dt, m), W.dev)
+            out = [_empty(m, dt_, W.dev) for dt_ in (torch.int32, torch.int32, torch.float32, torch.float32)]
+            count = _empty(1, torch.int64, W.dev)
+            _scan_call("mine", ZA.data_ptr(), HA.data_ptr(), n, W.K, W.d, W.dt, W.t, rp, cp, floor, m,
+                       *(o.data_ptr() for o in out), count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf)
+            c = int(count.item())
+            src, dst, logit, prob = (o[:c] for o in out)
+        else:
+            ZB, HB = W.tables(j)
+            src, dst, logit, prob = _mine_between(ZA, HA, ZB, HB, hi_i - lo_i, hi_j - lo_j, W.K, W.d, W.dt, W.t, m, excl,
+                                                  floor, nf)
+        if src.numel() == 0:
+            continue
+        best = _merge_top(best, (src.to(torch.int64) + lo_i, dst.to(torch.int64) + lo_j, logit, prob), W.N, m)
+        if best[0].numel() == m:                                      # full: nothing below the m-th can enter any more
+            last = float(best[2][-1].item())
+            floor = max(floor, last) if last == last else floor
+    if best is None:
+        e = torch.zeros(0, dtype=torch.int32, device=W.dev)
+        return e, e.clone(), torch.zeros(0, dtype=torch.float32, device=W.dev), torch.zeros(0, dtype=torch.float32, device=W.dev)
+    return best[0].to(torch.int32), best[1].to(torch.int32), best[2], best[3]
+
+
+def _links_windows(W: _BlockWindows, min_logit: float, fill: bool):
+    """Runs every window of a blocked link graph; yields, per window side, (row block, column offset, piece) where piece is
+    (rowptr int64 [rows+1], col, logit, prob) — col / logit / prob are None for ``fill=False`` (the count pass alone)."""
+    for i, j in W.windows():
+        (lo_i, hi_i), (lo_j, hi_j) = W.blocks[i], W.blocks[j]
+        ZA, HA = W.tables(i)
+        nf, _keep_nf = W.rule(i, j)
+        excl = W.exclusion(i, j)
+        if i == j:
+            n = hi_i - lo_i
+            ex = _csr_args(*excl, W.dev)
+            ws = _empty(max(256, _scan_ws_bytes("links", n, W.K, W.d, W.dt)), torch.uint8, W.dev)
+            rowptr = _empty(n + 1, torch.int64, W.dev)
+            head = (ZA.data_ptr(), HA.data_ptr(), n, W.K, W.d, W.dt, W.t, ex[0], ex[1], float(min_logit), nf, ws.data_ptr(),
+                    ws.numel(), rowptr.data_ptr())
+            _scan_call("links_count", *head, _stream())
+            yield i, lo_i, (_links_fill("links_fill", rowptr, head) if fill else (rowptr, None, None, None))
+        else:
+            ZB, HB = W.tables(j)
+            args = (ZA, HA, ZB, HB, hi_i - lo_i, hi_j - lo_j, W.K, W.d, W.dt, W.t, excl, min_logit, nf)
+            if fill:
+                ab, ba = _links_between(*args)
+            else:
+                rowptr_a, rowptr_b, _head, _keep = _links_between_count(*args)
+                ab, ba = (rowptr_a, None, None, None), (rowptr_b, None, None, None)
+            yield i, lo_j, ab
+            yield j, lo_i, ba
+
+
+def score_link_degrees_blocks(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32,
+                              block_nodes=None):
+    """``score_link_degrees`` for any N up to 8,388,480 -> int64 [N]: the count passes of the windows of
+    ``score_links_blocks`` alone, added up per node."""
+    W = _BlockWindows(Z, H, t, exclude, node_filter, table_dtype, block_nodes)
+    deg = torch.zeros(W.N, dtype=torch.int64, device=W.dev)
+    for b, _off, (rowptr, _c, _l, _p) in _links_windows(W, min_logit, fill=False):
+        lo, hi = W.blocks[b]
+        deg[lo:hi] += rowptr[1:] - rowptr[:-1]
+    return deg
+
+
+def score_links_blocks(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32,
+                       block_nodes=None):
+    """``score_links`` for ANY N up to 8,388,480 -> (rowptr int64 [N+1], col int32 [nnz], logit f32 [nnz], prob f32 [nnz]): the
+    symmetric CSR over all N nodes in GLOBAL ids, columns strictly ascending, each pair twice with the same bits.  Blocks as
+    in ``score_mine_blocks``: diagonal blocks through dl_score_links_count_dtype / _fill_dtype on row slices, block pairs
+    i < j through the _between entries, whose A side is a piece of the rows of block i and whose B side one of block j.  The
+    windows run in row-major order, so the pieces of a row arrive in ascending column blocks and are copied to their place
+    behind one another: no sort of the result.  For N <= 46,340 the result is bit for bit ``score_links``'s, for every block
+    size.  Peak memory: the pieces and the result (2 x the result arrays), the workspace of ONE window, O(N) arrays and one
+    int32 degree per row and piece (N x blocks); one host read per window."""
+    W = _BlockWindows(Z, H, t, exclude, node_filter, table_dtype, block_nodes)
+    deg = torch.zeros(W.N, dtype=torch.int64, device=W.dev)
+    pieces = []
+    for b, off, (rowptr, col, logit, prob) in _links_windows(W, min_logit, fill=True):
+        lo, hi = W.blocks[b]
+        d32 = (rowptr[1:] - rowptr[:-1]).to(torch.int32)
+        deg[lo:hi] += d32
+        if col.numel():
+            pieces.append((b, off, d32, col, logit, prob))
+    out_rowptr = torch.zeros(W.N + 1, dtype=torch.int64, device=W.dev)
+    out_rowptr[1:] = torch.cumsum(deg, dim=0)
+    nnz = int(out_rowptr[-1].item())
+    out_col = _empty(nnz, torch.int32, W.dev)
+    out_logit, out_prob = _empty(nnz, torch.float32, W.dev), _empty(nnz, torch.float32, W.dev)
+    cursor = out_rowptr[:-1].clone()                                   # where the next piece of every row starts
+    pieces.reverse()
+    while pieces:                                                      # in arrival order; a piece is freed once it is placed
+        b, off, d32, col, logit, prob = pieces.pop()
+        lo, hi = W.blocks[b]
+        d64 = d32.to(torch.int64)
+        first = torch.cumsum(d64, dim=0) - d64                         # the piece's own exclusive prefix
+        dest = torch.repeat_interleave(cursor[lo:hi] - first, d64) + torch.arange(col.numel(), device=W.dev)
+        out_col[dest] = col + off
+        out_logit[dest] = logit
+        out_prob[dest] = prob
+        cursor[lo:hi] += d64
+    return out_rowptr, out_col, out_logit, out_prob

@@ -774,6 +774,69 @@ int dl_score_links_top_fill_dtype(const void* Z, const void* H, int N, int K, in
                                   const dl_node_filter* filter, void* ws, size_t ws_bytes, const int64_t* rowptr, int64_t nnz,
                                   int32_t* col, float* logit, float* prob, void* stream);
 
+/* Link scans BETWEEN TWO NODE SETS (an extension; the reference has no counterpart): rows of a table A [nA][K][d] against
+ * rows of a table B [nB][K][d] -- users x items, new nodes x old nodes, or block i x block j of one graph past the cap of
+ * the triangular walk.  Every tile pair of the ceil(nA/128) x ceil(nB/128) grid is formed, in row-major order, by the
+ * kernels of dl_score_mine / dl_score_links in their rectangular form: nA nB candidates cost nA nB products, where the
+ * triangular scan of the concatenated table under a node filter costs (nA + nB)^2 / 2.  Provided in the _dtype argument
+ * convention only (tables of either type; both tables have the one dtype).
+ * Logit: rows of A are the A operand.  The logit of (a, b) has the bits dl_score_pair_logits returns for (a, nA + b) on the
+ * table cat(A, B); for blocks i < j of one graph these are the bits the triangular scans form for u < v.
+ * Eligible: a < nA, b < nB (no a < b test, no diagonal: the two sets are distinct tables), b not among the columns of row a
+ * of the exclusion CSR (BIPARTITE: ex_rowptr int32 [nA+1], columns B-local and strictly ascending; both NULL = none),
+ * allowed by the rule if one is given, and s >= min_logit (NaN never; -0 reaches a floor of 0).
+ * Rule (dl_node_filter_between, NULL = none): group_a [nA] and group_b [nB] give every row a group below n_groups <= 64;
+ * (a, b) is allowed iff bit group_b[b] of allow[group_a[a]] is set.  The row of A decides: the rule need not be symmetric.
+ * Nothing past group_a[nA-1] or group_b[nB-1] is read.
+ * dl_score_mine_between_dtype: the m best pairs, 1 <= m <= 65536, with dl_score_mine's select (up to six histogram scans,
+ *   one emit scan, the ordering) on the key (order of the logit, then a nB + b, the smaller first).  Outputs as dl_score_mine:
+ *   src (A-local) / dst (B-local) int32 [m], logit / prob fp32 [m], padded with -1 / NaN, count[0] = min(m, eligible).
+ * dl_score_links_between_count_dtype / _fill_dtype: every eligible pair, as TWO CSRs: the A side (rowptr_a int64 [nA+1],
+ *   columns = rows of B) and the B side (rowptr_b int64 [nB+1], columns = rows of A).  Every pair appears once in each, with
+ *   the same bits, columns strictly ascending, a -0 reported as +0; rowptr_a[nA] = rowptr_b[nB] = the number of pairs.  Two
+ *   calls with the same arguments over the same untouched workspace, as for dl_score_links: the count writes, per row and
+ *   128-row tile of the other side, the number of eligible partners (cnt_a [nA][tiles of B], cnt_b [nB][tiles of A]; every
+ *   cell is written exactly once, zeros included: no memset, no atomics), their prefixes and the two rowptr arrays; the fill
+ *   recomputes the logits with the same instruction stream and writes each pair to its slot in both sides.  A slot >= nnz_a
+ *   (>= nnz_b) is not written.  prob_a and prob_b may be NULL together (not wanted).
+ * Same bits on every call and under every DL_MINE_TILES.  Limits: 1 <= nA, nB <= DL_SCORE_BETWEEN_MAX_N (the pair index
+ * a nB + b must fit 31 bits); K, d, t, dtype as for the other scans.  Order of the checks: dtype, K and d, nA, nB, (m,) the
+ * rule, t, NULL arguments, the exclusion pair, the workspace (DL_E_WORKSPACE); the fill then nnz >= 0 and its outputs.  No
+ * allocation, no synchronisation, no host read, the environment is not read; the caller's stream.
+ * ws: the *_workspace_bytes_dtype functions (0 for arguments out of range): the planes of the four tables, and the selection
+ * state, one histogram and m keys (mine) or the two cell arrays and the degrees (links).
+ * The launch plans under the current DL_MINE_TILES (host only):
+ *   out[DL_SCORE_MINE_BETWEEN_FORM_LEN] = [0] 32-column chunks of the padded factor width  [1] tiles of A  [2] tiles of B
+ *     [3] tile pairs  [4] tile pairs per workgroup  [5] workgroups of a scan  [6] scans at most (six digits + emit)
+ *     [7] byte offset, inside the 256-byte aligned workspace, of the 32-bit number of scans that ran
+ *   out[DL_SCORE_LINKS_BETWEEN_FORM_LEN] = [0..5] the same  [6] scans of count + fill  [7] cells of cnt_a  [8] cells of cnt_b */
+typedef struct dl_node_filter_between {
+    const uint8_t* group_a;
+    const uint8_t* group_b;
+    int32_t n_groups;
+    const uint64_t* allow;
+} dl_node_filter_between;
+#define DL_SCORE_BETWEEN_MAX_N 46340
+#define DL_SCORE_MINE_BETWEEN_FORM_LEN 8
+#define DL_SCORE_LINKS_BETWEEN_FORM_LEN 9
+int dl_score_mine_between_form(int nA, int nB, int K, int d, int m, int* out);
+size_t dl_score_mine_between_workspace_bytes_dtype(int nA, int nB, int K, int d, dl_dtype dtype, int m);
+int dl_score_mine_between_dtype(const void* ZA, const void* HA, int nA, const void* ZB, const void* HB, int nB, int K, int d,
+                                dl_dtype dtype, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit, int m,
+                                int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws, size_t ws_bytes,
+                                void* stream, const dl_node_filter_between* filter);
+int dl_score_links_between_form(int nA, int nB, int K, int d, int* out);
+size_t dl_score_links_between_workspace_bytes_dtype(int nA, int nB, int K, int d, dl_dtype dtype);
+int dl_score_links_between_count_dtype(const void* ZA, const void* HA, int nA, const void* ZB, const void* HB, int nB, int K, int d,
+                                       dl_dtype dtype, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit,
+                                       const dl_node_filter_between* filter, void* ws, size_t ws_bytes, int64_t* rowptr_a,
+                                       int64_t* rowptr_b, void* stream);
+int dl_score_links_between_fill_dtype(const void* ZA, const void* HA, int nA, const void* ZB, const void* HB, int nB, int K, int d,
+                                      dl_dtype dtype, float t, const int32_t* ex_rowptr, const int32_t* ex_col, float min_logit,
+                                      const dl_node_filter_between* filter, void* ws, size_t ws_bytes, const int64_t* rowptr_a,
+                                      const int64_t* rowptr_b, int64_t nnz_a, int32_t* col_a, float* logit_a, float* prob_a,
+                                      int64_t nnz_b, int32_t* col_b, float* logit_b, float* prob_b, void* stream);
+
 /* Tie-averaged AUC of a score vector against FIXED labels: replaces sklearn.metrics.roc_auc_score at
  * main_disentangled.py:202-204 / 217-219 (validation AUC every epoch, test AUC at the end).  pos_idx / neg_idx
  * (int64, device) are the positions of the positive and negative labels in score, found once per run; the call
