@@ -59,6 +59,12 @@
 // bf16 tables (the *_dtype entries with DL_BF16; the P = 1 instantiations): the table is its own single plane (copy_rows), a
 // step stages one plane per operand and issues one product per block (gram_block<1>).  On the same values the logits are the
 // bits of the three-plane scan (dl_tiles.h), so everything above holds unchanged; only the plane arrays of the workspace shrink.
+//
+// Host side (behind namespace mine): every entry is made of the same parts — the Plan of the tile walk (a triangle is the
+// rectangle whose B is A; the run length and DL_MINE_TILES live there), carve (the workspace as the select's blocks, the planes
+// and the link cells, in that order), split_tables, scan_args (either kind of rule), launch<MODE> (RECT, P and FILT from the
+// plan), select (the histogram rounds) and link_offsets (cells, then rowptr, per side).  A new mode adds its epilogue and its
+// part of ScanArgs on the device side, and on the host side a driver that names its passes.
 #include <cstddef>
 #include "dl_common.h"
 #include "dl_config.h"
@@ -750,107 +756,230 @@ __global__ __launch_bounds__(1024) void link_rowptr_kernel(const unsigned* __res
 
 using namespace mine;
 
+// ---- The parts every driver below is made of: the plan of the tile walk, the carving of the workspace, the tables' planes,
+// the builder of ScanArgs, the launcher, the select and the offsets step.  A driver names its passes.
+
+// The tile walk of rows of a table A against rows of a table B, over tables of one shape (K, d) and type.  A triangle is the
+// case "B is A": the tile pairs u tile <= v tile, none for N < 2; a rectangle walks every tile pair of the ntA x ntB grid.
 // Tile pairs per workgroup: eight workgroups' worth of pairs per CU (one workgroup per CU fits the LDS; short runs keep the
 // tail of the grid short, consecutive pairs of a run share their u tile).  DL_MINE_TILES (test knob) forces the run length;
 // results do not depend on it.
-struct MinePlan { int nd, nt, pairs, per_wg, grid; size_t cbatch; dl_dtype dt; };
-static MinePlan mine_plan(int N, int d, dl_dtype dt = DL_F32) {
-    MinePlan p;
+struct Plan { bool rect; int nA, nB, K, d, nd, ntA, ntB, pairs, per_wg, grid; size_t cbatchA, cbatchB; dl_dtype dt; };
+static Plan tile_plan(bool rect, int nA, int nB, int K, int d, dl_dtype dt) {
+    Plan p = {};
+    p.rect = rect; p.nA = nA; p.nB = nB; p.K = K; p.d = d; p.dt = dt;
     p.nd = (d + SDC - 1) / SDC;
-    p.nt = (N + TT - 1) / TT;
-    // 64-bit: nt (nt + 1) / 2 fits an int32 up to nt = 65,535 (the callers' limit on N), its intermediates do not
-    const long long pairs = N >= 2 ? (long long)p.nt * (p.nt + 1) / 2 : 0;
+    p.ntA = (nA + TT - 1) / TT;
+    p.ntB = (nB + TT - 1) / TT;
+    // 64-bit: nt (nt + 1) / 2 fits an int32 up to nt = 65,535 (the callers' limit on N), its intermediates do not; a
+    // rectangle has <= 363^2
+    const long long pairs = rect ? (long long)p.ntA * p.ntB : nA >= 2 ? (long long)p.ntA * (p.ntA + 1) / 2 : 0;
     p.pairs = (int)pairs;
     const long long per_cu = 8LL * device_cus();
     const int want = config().mine_tiles > 0 ? config().mine_tiles : (int)((pairs + per_cu - 1) / per_cu);
     p.per_wg = max(1, min(want, max(1, p.pairs)));
     p.grid = (int)((pairs + p.per_wg - 1) / p.per_wg);
-    p.cbatch = table_plane_elems(dt, N, d);                    // the one thing of a plan that depends on the table type
-    p.dt = dt;
+    p.cbatchA = table_plane_elems(dt, nA, d);                  // the one thing of a plan that depends on the table type
+    p.cbatchB = table_plane_elems(dt, nB, d);
     return p;
 }
-
-// The planes of Z and H (three per fp32 table, the one of a bf16 table), and what every scan of the family reads
-static void split_tables(const MinePlan& p, const void* Z, const void* H, int N, int K, int d, __bf16* cz, __bf16* ch, hipStream_t st) {
-    table_planes(Z, p.dt, nullptr, N, K, d, cz, st);
-    table_planes(H, p.dt, nullptr, N, K, d, ch, st);
+// what every *_form reports of a plan: out = nd, tiles (of A, then of B: rectangle), tile pairs, tile pairs per workgroup,
+// workgroups of a scan
+static void plan_form(const Plan& p, int* out) {
+    *out++ = p.nd;
+    *out++ = p.ntA;
+    if (p.rect) *out++ = p.ntB;
+    *out++ = p.pairs;
+    *out++ = p.per_wg;
+    *out++ = p.grid;
 }
-static ScanArgs scan_args(const MinePlan& p, const __bf16* cz, const __bf16* ch, int N, int K, float t, const int32_t* exr,
-                          const int32_t* exc, float min_logit, const dl_node_filter* nf) {
+static Plan triangle(int N, int K, int d, dl_dtype dt = DL_F32) { return tile_plan(false, N, N, K, d, dt); }
+static Plan rectangle(int nA, int nB, int K, int d, dl_dtype dt = DL_F32) { return tile_plan(true, nA, nB, K, d, dt); }
+
+// The workspace (256-byte aligned blocks), always in this order, of the pieces a driver names:
+//   the select's:    selection state | histogram | keys [keys]          (WS_STATE: the state alone; keys = 0: no key array)
+//   the planes:      of Z and H (triangle), of ZA, HA, ZB, HB (rectangle); three per fp32 table, the one of a bf16 table
+//   the link cells:  cnt [N][nt] | deg [N] (triangle), cnt_a [nA][ntB] | cnt_b [nB][ntA] | deg_a [nA] | deg_b [nB] (rectangle)
+enum { WS_STATE = 1, WS_HIST = 2, WS_SELECT = WS_STATE | WS_HIST, WS_CELLS = 4 };
+struct Ws { State* state; unsigned* hist; u64* keys; __bf16 *za, *ha, *zb, *hb; unsigned *cnt_a, *cnt_b, *deg_a, *deg_b; size_t bytes; };
+static Ws carve(const Plan& p, int pieces, size_t keys, void* ws) {
+    Ws w = {};
+    Carver c(ws);
+    if (pieces & WS_STATE) w.state = c.take<State>(1);
+    if (pieces & WS_HIST) w.hist = c.take<unsigned>(BINS);
+    if (keys > 0) w.keys = c.take<u64>(keys);
+    w.zb = w.za = c.take<__bf16>((size_t)p.K * p.cbatchA);     // a triangle's B is its A
+    w.hb = w.ha = c.take<__bf16>((size_t)p.K * p.cbatchA);
+    if (p.rect) {
+        w.zb = c.take<__bf16>((size_t)p.K * p.cbatchB);
+        w.hb = c.take<__bf16>((size_t)p.K * p.cbatchB);
+    }
+    if (pieces & WS_CELLS) {
+        w.cnt_a = c.take<unsigned>((size_t)p.nA * p.ntB);      // <= 46,340 * 363 cells
+        if (p.rect) w.cnt_b = c.take<unsigned>((size_t)p.nB * p.ntA);
+        w.deg_a = c.take<unsigned>((size_t)p.nA);
+        if (p.rect) w.deg_b = c.take<unsigned>((size_t)p.nB);
+    }
+    w.bytes = c.bytes();
+    return w;
+}
+
+// The tables of a scan (a triangle has no ZB, HB) and their split into the planes of the workspace
+struct Tables { const void *ZA, *HA, *ZB, *HB; };
+static void split_tables(const Plan& p, const Ws& w, const Tables& T, hipStream_t st) {
+    table_planes(T.ZA, p.dt, nullptr, p.nA, p.K, p.d, w.za, st);
+    table_planes(T.HA, p.dt, nullptr, p.nA, p.K, p.d, w.ha, st);
+    if (!p.rect) return;
+    table_planes(T.ZB, p.dt, nullptr, p.nB, p.K, p.d, w.zb, st);
+    table_planes(T.HB, p.dt, nullptr, p.nB, p.K, p.d, w.hb, st);
+}
+
+// Either kind of node-group rule as the kernels take it: the groups of the rows (of A) and the allow table, and the groups
+// of the rows of B where B has its own
+struct Rule { bool on; FilterArgs filt; const unsigned char* group_b; };
+static Rule rule_of(const dl_node_filter* nf) { return Rule{nf != nullptr, filter_args(nf), nullptr}; }
+static Rule rule_of(const dl_node_filter_between* nf) {
+    if (nf == nullptr) return Rule{false, FilterArgs{nullptr, nullptr, 0}, nullptr};
+    return Rule{true, FilterArgs{nf->group_a, (const u64*)nf->allow, nf->n_groups}, nf->group_b};
+}
+
+// What every scan of the family reads; a mode's own part of ScanArgs is its driver's
+static ScanArgs scan_args(const Plan& p, const Ws& w, float t, const int32_t* exr, const int32_t* exc, float min_logit, const Rule& r) {
     ScanArgs a = {};
-    a.cz = cz; a.ch = ch; a.cbatch = p.cbatch;
-    a.N = N; a.K = K; a.nd = p.nd; a.nt = p.nt; a.t = t;
+    a.cz = w.za; a.ch = w.ha; a.cbatch = p.cbatchA;
+    a.N = p.nA; a.K = p.K; a.nd = p.nd; a.nt = p.ntA; a.t = t;
     a.ex_rowptr = exr; a.ex_col = exc;
     a.min_logit = min_logit;
     a.pairs = p.pairs; a.per_wg = p.per_wg;
-    a.filt = filter_args(nf);
+    a.filt = r.filt;
+    if (p.rect) {
+        a.rect.cz = w.zb; a.rect.ch = w.hb; a.rect.cbatch = p.cbatchB;
+        a.rect.N = p.nB; a.rect.nt = p.ntB;
+        a.rect.group = r.group_b;
+    }
     return a;
 }
+
+// The instantiations of scan_tiles, named once in the order in which the code object holds them.  The compiler emits kernels
+// in the order of their first use, so with this list a change of the host code below leaves the device assembly of the unit
+// the same text, which is how such a change is checked (hipcc -S --cuda-device-only, before and after).
+#define DL_SCAN_FORMS(MODE, F0, F1) scan_tiles<MODE, F0, 1>, scan_tiles<MODE, F1, 1>, scan_tiles<MODE, F0, 3>, scan_tiles<MODE, F1, 3>
+[[maybe_unused]] static void (*const SCAN_FORMS[])(ScanArgs) = {
+    DL_SCAN_FORMS(HIST, false, true), DL_SCAN_FORMS(EMIT, false, true), DL_SCAN_FORMS(COUNT, false, true),
+    DL_SCAN_FORMS(DEG, false, true), DL_SCAN_FORMS(FILL, false, true),
+    DL_SCAN_FORMS(HIST_RECT, true, false), DL_SCAN_FORMS(EMIT_RECT, true, false), DL_SCAN_FORMS(DEG_RECT, true, false),
+    DL_SCAN_FORMS(FILL_RECT, true, false), DL_SCAN_FORMS(DEG_TOP, false, true), DL_SCAN_FORMS(FILL_TOP, false, true)};
+#undef DL_SCAN_FORMS
+
+// One scan in the instantiation the plan asks for: the RECT form of the mode on a rectangle (HIST, EMIT, DEG and FILL have
+// one), one plane per operand on bf16 tables, FILT (which keeps FILTER_LDS_BYTES behind the mode's LDS) under a rule
+constexpr bool has_rect(int mode) { return mode == HIST || mode == EMIT || mode == DEG || mode == FILL; }
+template <int MODE, int P>
+static void launch_planes(const Plan& p, const ScanArgs& a, bool filtered, hipStream_t st) {
+    const unsigned grid = (unsigned)p.grid;
+    const size_t lds = lds_bytes(MODE, P) + (filtered ? FILTER_LDS_BYTES : 0);
+    if constexpr (has_rect(MODE)) {
+        if (p.rect) {
+            if (filtered) launch_lds<scan_tiles<rect_mode(MODE), true, P>>(grid, MTHR, lds, st, a);
+            else launch_lds<scan_tiles<rect_mode(MODE), false, P>>(grid, MTHR, lds, st, a);
+            return;
+        }
+    }
+    if (filtered) launch_lds<scan_tiles<MODE, true, P>>(grid, MTHR, lds, st, a);
+    else launch_lds<scan_tiles<MODE, false, P>>(grid, MTHR, lds, st, a);
+}
 template <int MODE>
-static void launch_tiles(const MinePlan& p, const ScanArgs& a, const dl_node_filter* nf, hipStream_t st) {
-    if (p.dt == DL_BF16)
-        launch_scan<scan_tiles<MODE, false, 1>, scan_tiles<MODE, true, 1>>(nf, (unsigned)p.grid, MTHR, lds_bytes(MODE, 1), st, a);
-    else
-        launch_scan<scan_tiles<MODE>, scan_tiles<MODE, true>>(nf, (unsigned)p.grid, MTHR, lds_bytes(MODE, 3), st, a);
+static void launch(const Plan& p, const ScanArgs& a, bool filtered, hipStream_t st) {
+    if (p.dt == DL_BF16) launch_planes<MODE, 1>(p, a, filtered, st);
+    else launch_planes<MODE, 3>(p, a, filtered, st);
 }
 
+// The radix select of the `need` best keys: the state and the histogram cleared, the tables split, then one HIST scan and one
+// pick per digit.  It leaves the threshold key in State::prefix and the select's part of `a` filled in; without a tile pair
+// only the state is set (no candidate, count 0).
+static void select(const Plan& p, const Ws& w, const Tables& T, ScanArgs& a, int need, bool filtered, hipStream_t st) {
+    hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, need);
+    if (p.pairs == 0) return;
+    split_tables(p, w, T, st);
+    a.state = w.state;
+    a.sel.m = need; a.sel.hist = w.hist; a.sel.keys = w.keys;
+    for (int pass = 0; pass < PASSES; ++pass) {
+        a.sel.pass = pass;
+        launch<HIST>(p, a, filtered, st);
+        hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, need);
+    }
+}
+
+// The offsets of one side of a link graph, between its count and its fill: every node's cells [n][nt] into their exclusive
+// prefix and its degree, then the degrees into rowptr.  scanned = false (no tile pair wrote a cell): rowptr is all zero.
+static void link_offsets(unsigned* cnt, unsigned* deg, int n, int nt, bool scanned, int64_t* rowptr, hipStream_t st) {
+    if (scanned) hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, cnt, deg, n, nt);
+    hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, deg, rowptr, n, scanned ? 1 : 0);
+}
+
+// The count pass of a link graph over split tables: the DEG scan (DEG_TOP: under the key a select left), then the offsets of
+// the A side and, on a rectangle, of the B side
+template <int MODE>
+static void count_links(const Plan& p, const Ws& w, ScanArgs& a, bool filtered, int64_t* rowptr_a, int64_t* rowptr_b, hipStream_t st) {
+    if (p.pairs > 0) {
+        a.link.cnt = w.cnt_a;
+        if (p.rect) a.rect.link.cnt = w.cnt_b;
+        launch<MODE>(p, a, filtered, st);
+    }
+    link_offsets(w.cnt_a, w.deg_a, p.nA, p.ntB, p.pairs > 0, rowptr_a, st);
+    if (p.rect) link_offsets(w.cnt_b, w.deg_b, p.nB, p.ntA, p.pairs > 0, rowptr_b, st);
+}
+
+// The fill pass over the planes and cells the count left: the CSR of the A side and, on a rectangle, of the B side.  A side
+// of length 0 takes no write (every slot is >= its nnz); nothing to write at all: no scan.
+template <int MODE>
+static void fill_links(const Plan& p, ScanArgs& a, bool filtered, const LinkArgs& side_a, const LinkArgs& side_b, hipStream_t st) {
+    if (p.pairs == 0 || (side_a.nnz <= 0 && side_b.nnz <= 0)) return;
+    a.link = side_a;
+    if (p.rect) a.rect.link = side_b;
+    launch<MODE>(p, a, filtered, st);
+}
+
+// The m best pairs of a plan, in order: the select, an EMIT scan of the keys at or above its threshold, the ordering, which
+// decodes the pair index with the row length of the walk (N; nB on a rectangle: src A-local, dst B-local)
+static int mine_pairs(const char* what, const Plan& p, const Tables& T, float t, const int32_t* exr, const int32_t* exc, float min_logit,
+                      int m, const Rule& r, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws,
+                      hipStream_t st) {
+    const Ws w = carve(p, WS_SELECT, (size_t)m, ws);
+    ScanArgs a = scan_args(p, w, t, exr, exc, min_logit, r);
+    select(p, w, T, a, m, r.on, st);
+    if (p.pairs > 0) launch<EMIT>(p, a, r.on, st);
+    hipLaunchKernelGGL(order_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.state, w.keys, p.rect ? p.nB : max(p.nA, 1),
+                       m, src, dst, logit, prob, count);
+    return check_launch(what);
+}
+
+// ---- dl_score_mine: the m best unordered pairs u < v of one table
 bool score_mine_supported(int K, int d) { return score_rank_supported(K, d); }
 
 // out = nd, tiles, tile pairs, tile pairs per workgroup, workgroups of a scan, scans at most (digits + emit), byte offset of
 // the 32-bit count of scans that ran inside the (256-byte aligned) workspace
 void score_mine_form(int N, int d, int m, int* out) {
     (void)m;
-    const MinePlan p = mine_plan(N, d);
-    out[0] = p.nd;
-    out[1] = p.nt;
-    out[2] = p.pairs;
-    out[3] = p.per_wg;
-    out[4] = p.grid;
+    const Plan p = triangle(N, 0, d);
+    plan_form(p, out);
     out[5] = p.pairs > 0 ? PASSES + 1 : 0;
     out[6] = (int)offsetof(State, scans);
 }
 
-// Workspace (256-byte aligned blocks): selection state | histogram | keys [m] | planes of Z and H
-struct MineWs { State* state; unsigned* hist; u64* keys; __bf16 *cz, *ch; size_t bytes; };
-static MineWs mine_carve(const MinePlan& p, int K, int m, void* ws) {
-    MineWs w = {};
-    Carver c(ws);
-    w.state = c.take<State>(1);
-    w.hist = c.take<unsigned>(BINS);
-    w.keys = c.take<u64>((size_t)m);
-    w.cz = c.take<__bf16>((size_t)K * p.cbatch);
-    w.ch = c.take<__bf16>((size_t)K * p.cbatch);
-    w.bytes = c.bytes();
-    return w;
+size_t score_mine_workspace_bytes(int N, int K, int d, int m, dl_dtype dt) {
+    return carve(triangle(N, K, d, dt), WS_SELECT, (size_t)m, nullptr).bytes;
 }
-
-size_t score_mine_workspace_bytes(int N, int K, int d, int m, dl_dtype dt) { return mine_carve(mine_plan(N, d, dt), K, m, nullptr).bytes; }
 
 int score_mine(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
                float min_logit, int m, int32_t* src, int32_t* dst, float* logit, float* prob, int64_t* count, void* ws, hipStream_t st,
                const dl_node_filter* nf) {
-    const MinePlan p = mine_plan(N, d, dt);
-    const MineWs w = mine_carve(p, K, m, ws);
-    hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, m);
-    if (p.pairs > 0) {
-        split_tables(p, Z, H, N, K, d, w.cz, w.ch, st);
-        ScanArgs a = scan_args(p, w.cz, w.ch, N, K, t, exr, exc, min_logit, nf);
-        a.state = w.state;
-        a.sel.m = m; a.sel.hist = w.hist; a.sel.keys = w.keys;
-        for (int pass = 0; pass < PASSES; ++pass) {
-            a.sel.pass = pass;
-            launch_tiles<HIST>(p, a, nf, st);
-            hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
-        }
-        launch_tiles<EMIT>(p, a, nf, st);
-    }
-    hipLaunchKernelGGL(order_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.state, w.keys, max(N, 1), m, src, dst,
-                       logit, prob, count);
-    return check_launch("score_mine");
+    return mine_pairs("score_mine", triangle(N, K, d, dt), Tables{Z, H, nullptr, nullptr}, t, exr, exc, min_logit, m, rule_of(nf), src,
+                      dst, logit, prob, count, ws, st);
 }
 
 // ---- dl_score_pair_ranks: ONE counting scan (scan_tiles<COUNT>) over the sorted order keys of T target pairs
-struct PairRankPlan { MinePlan m; int stride, nsep, lds_levels, global_levels; };
+struct PairRankPlan { Plan m; int stride, nsep, lds_levels, global_levels; };
 static int search_levels(int n) {                               // iterations of a lower-bound search over n elements, at most
     int l = 0;
     while (n > 0) {
@@ -859,9 +988,9 @@ static int search_levels(int n) {                               // iterations of
     }
     return l;
 }
-static PairRankPlan pair_rank_plan(int N, int d, int T, dl_dtype dt = DL_F32) {
+static PairRankPlan pair_rank_plan(int N, int K, int d, int T, dl_dtype dt = DL_F32) {
     PairRankPlan p;
-    p.m = mine_plan(N, d, dt);
+    p.m = triangle(N, K, d, dt);
     p.stride = max(1, (T + SEPS - 1) / SEPS);
     p.nsep = (T + p.stride - 1) / p.stride;
     p.lds_levels = search_levels(p.nsep);
@@ -872,48 +1001,33 @@ static PairRankPlan pair_rank_plan(int N, int d, int T, dl_dtype dt = DL_F32) {
 // out = nd, tiles, tile pairs, tile pairs per workgroup, workgroups, separators in LDS, targets per separator, search
 // levels in LDS, search levels in global memory
 void score_pair_ranks_form(int N, int d, int T, int* out) {
-    const PairRankPlan p = pair_rank_plan(N, d, T);
-    out[0] = p.m.nd;
-    out[1] = p.m.nt;
-    out[2] = p.m.pairs;
-    out[3] = p.m.per_wg;
-    out[4] = p.m.grid;
+    const PairRankPlan p = pair_rank_plan(N, 0, d, T);
+    plan_form(p.m, out);
     out[5] = p.nsep;
     out[6] = p.stride;
     out[7] = p.lds_levels;
     out[8] = p.global_levels;
 }
 
-// Workspace (256-byte aligned blocks): scan state | planes of Z and H
-struct PairRankWs { State* state; __bf16 *cz, *ch; size_t bytes; };
-static PairRankWs pair_rank_carve(const MinePlan& p, int K, void* ws) {
-    PairRankWs w = {};
-    Carver c(ws);
-    w.state = c.take<State>(1);
-    w.cz = c.take<__bf16>((size_t)K * p.cbatch);
-    w.ch = c.take<__bf16>((size_t)K * p.cbatch);
-    w.bytes = c.bytes();
-    return w;
-}
-
-size_t score_pair_ranks_workspace_bytes(int N, int K, int d, dl_dtype dt) { return pair_rank_carve(mine_plan(N, d, dt), K, nullptr).bytes; }
+size_t score_pair_ranks_workspace_bytes(int N, int K, int d, dl_dtype dt) { return carve(triangle(N, K, d, dt), WS_STATE, 0, nullptr).bytes; }
 
 int score_pair_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
                      const unsigned* tord, int T, u64* gcnt, u64* tcnt, u64* ncand, void* ws, hipStream_t st,
                      const dl_node_filter* nf) {
-    const PairRankPlan p = pair_rank_plan(N, d, T, dt);
-    const PairRankWs w = pair_rank_carve(p.m, K, ws);
+    const PairRankPlan p = pair_rank_plan(N, K, d, T, dt);
+    const Ws w = carve(p.m, WS_STATE, 0, ws);
     hipError_t e = hipMemsetAsync(w.state, 0, sizeof(State), st);
     if (e == hipSuccess) e = hipMemsetAsync(gcnt, 0, sizeof(u64) * ((size_t)T + 1), st);
     if (e == hipSuccess) e = hipMemsetAsync(tcnt, 0, sizeof(u64) * ((size_t)T + 1), st);
     if (e == hipSuccess) e = hipMemsetAsync(ncand, 0, sizeof(u64), st);
     DL_REQUIRE(e == hipSuccess, "hipMemsetAsync: %s", hipGetErrorString(e));
     if (p.m.pairs > 0) {
-        split_tables(p.m, Z, H, N, K, d, w.cz, w.ch, st);
-        ScanArgs a = scan_args(p.m, w.cz, w.ch, N, K, t, exr, exc, 0.0f, nf);
+        const Rule r = rule_of(nf);
+        split_tables(p.m, w, Tables{Z, H, nullptr, nullptr}, st);
+        ScanArgs a = scan_args(p.m, w, t, exr, exc, 0.0f, r);
         a.state = w.state;
         a.cnt = CountArgs{tord, T, p.stride, p.nsep, gcnt, tcnt, ncand};
-        launch_tiles<COUNT>(p.m, a, nf, st);
+        launch<COUNT>(p.m, a, r.on, st);
     }
     return check_launch("score_pair_ranks");
 }
@@ -923,237 +1037,34 @@ bool score_links_supported(int K, int d) { return score_mine_supported(K, d); }
 
 // out = nd, tiles, tile pairs, tile pairs per workgroup, workgroups of a scan, scans of count + fill, cells of cnt
 void score_links_form(int N, int d, int* out) {
-    const MinePlan p = mine_plan(N, d);
-    out[0] = p.nd;
-    out[1] = p.nt;
-    out[2] = p.pairs;
-    out[3] = p.per_wg;
-    out[4] = p.grid;
+    const Plan p = triangle(N, 0, d);
+    plan_form(p, out);
     out[5] = p.pairs > 0 ? 2 : 0;
-    out[6] = N * p.nt;                                          // <= 46,340 * 363
+    out[6] = N * p.ntA;                                         // <= 46,340 * 363
 }
 
-// Workspace (256-byte aligned blocks): planes of Z and H | cnt [N][nt] | deg [N]
-struct LinksWs { __bf16 *cz, *ch; unsigned *cnt, *deg; size_t bytes; };
-static LinksWs links_carve(const MinePlan& p, int N, int K, Carver& c) {
-    LinksWs w = {};
-    w.cz = c.take<__bf16>((size_t)K * p.cbatch);
-    w.ch = c.take<__bf16>((size_t)K * p.cbatch);
-    w.cnt = c.take<unsigned>((size_t)N * p.nt);
-    w.deg = c.take<unsigned>((size_t)N);
-    w.bytes = c.bytes();
-    return w;
-}
-static LinksWs links_carve(const MinePlan& p, int N, int K, void* ws) {
-    Carver c(ws);
-    return links_carve(p, N, K, c);
-}
-
-size_t score_links_workspace_bytes(int N, int K, int d, dl_dtype dt) { return links_carve(mine_plan(N, d, dt), N, K, nullptr).bytes; }
+size_t score_links_workspace_bytes(int N, int K, int d, dl_dtype dt) { return carve(triangle(N, K, d, dt), WS_CELLS, 0, nullptr).bytes; }
 
 int score_links_count(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc,
                       float min_logit, const dl_node_filter* nf, void* ws, int64_t* rowptr, hipStream_t st) {
-    const MinePlan p = mine_plan(N, d, dt);
-    const LinksWs w = links_carve(p, N, K, ws);
-    if (p.pairs > 0) {
-        split_tables(p, Z, H, N, K, d, w.cz, w.ch, st);
-        ScanArgs a = scan_args(p, w.cz, w.ch, N, K, t, exr, exc, min_logit, nf);
-        a.link.cnt = w.cnt;
-        launch_tiles<DEG>(p, a, nf, st);
-        hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, w.cnt, w.deg, N, p.nt);
-    }
-    hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, w.deg, rowptr, N, p.pairs > 0 ? 1 : 0);
+    const Plan p = triangle(N, K, d, dt);
+    const Ws w = carve(p, WS_CELLS, 0, ws);
+    const Rule r = rule_of(nf);
+    if (p.pairs > 0) split_tables(p, w, Tables{Z, H, nullptr, nullptr}, st);
+    ScanArgs a = scan_args(p, w, t, exr, exc, min_logit, r);
+    count_links<DEG>(p, w, a, r.on, rowptr, nullptr, st);
     return check_launch("score_links_count");
 }
 
 int score_links_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
                      const dl_node_filter* nf, void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit, float* prob,
                      hipStream_t st) {
-    const MinePlan p = mine_plan(N, d, dt);
-    const LinksWs w = links_carve(p, N, K, ws);
-    if (p.pairs > 0 && nnz > 0) {
-        ScanArgs a = scan_args(p, w.cz, w.ch, N, K, t, exr, exc, min_logit, nf);
-        a.link = LinkArgs{w.cnt, rowptr, nnz, col, logit, prob};
-        launch_tiles<FILL>(p, a, nf, st);
-    }
+    const Plan p = triangle(N, K, d, dt);
+    const Ws w = carve(p, WS_CELLS, 0, ws);
+    const Rule r = rule_of(nf);
+    ScanArgs a = scan_args(p, w, t, exr, exc, min_logit, r);
+    fill_links<FILL>(p, a, r.on, LinkArgs{w.cnt_a, rowptr, nnz, col, logit, prob}, LinkArgs{}, st);
     return check_launch("score_links_fill");
-}
-
-// ---- dl_score_mine_between / dl_score_links_between: rows of a table A against rows of a table B (the RECT instantiations).
-// The same select, ordering, offsets and epilogues over the ntA x ntB grid of tile pairs, the pair index a nB + b local to the
-// rectangle; a graph past the cap of the triangular walk is the union of its diagonal blocks (the entries above on row
-// slices) and of such rectangles, merged by the caller (scans.py).
-struct RectPlan { int nd, ntA, ntB, pairs, per_wg, grid; size_t cbatchA, cbatchB; dl_dtype dt; };
-static RectPlan rect_plan(int nA, int nB, int d, dl_dtype dt = DL_F32) {
-    RectPlan p;
-    p.nd = (d + SDC - 1) / SDC;
-    p.ntA = (nA + TT - 1) / TT;
-    p.ntB = (nB + TT - 1) / TT;
-    const long long pairs = (long long)p.ntA * p.ntB;           // <= 363^2
-    p.pairs = (int)pairs;
-    const long long per_cu = 8LL * device_cus();                // the run length of mine_plan
-    const int want = config().mine_tiles > 0 ? config().mine_tiles : (int)((pairs + per_cu - 1) / per_cu);
-    p.per_wg = max(1, min(want, max(1, p.pairs)));
-    p.grid = (int)((pairs + p.per_wg - 1) / p.per_wg);
-    p.cbatchA = table_plane_elems(dt, nA, d);
-    p.cbatchB = table_plane_elems(dt, nB, d);
-    p.dt = dt;
-    return p;
-}
-struct RectPlanes { __bf16 *za, *ha, *zb, *hb; };
-static RectPlanes rect_planes(const RectPlan& p, int K, Carver& c) {
-    RectPlanes w;
-    w.za = c.take<__bf16>((size_t)K * p.cbatchA);
-    w.ha = c.take<__bf16>((size_t)K * p.cbatchA);
-    w.zb = c.take<__bf16>((size_t)K * p.cbatchB);
-    w.hb = c.take<__bf16>((size_t)K * p.cbatchB);
-    return w;
-}
-static void rect_split(const RectPlan& p, const RectPlanes& w, const void* ZA, const void* HA, const void* ZB, const void* HB, int nA,
-                       int nB, int K, int d, hipStream_t st) {
-    table_planes(ZA, p.dt, nullptr, nA, K, d, w.za, st);
-    table_planes(HA, p.dt, nullptr, nA, K, d, w.ha, st);
-    table_planes(ZB, p.dt, nullptr, nB, K, d, w.zb, st);
-    table_planes(HB, p.dt, nullptr, nB, K, d, w.hb, st);
-}
-// the rule of a rectangle as the kernels take it: the groups of A and the allow table where the triangular scans have theirs
-static FilterArgs between_filter_args(const dl_node_filter_between* nf) {
-    return nf != nullptr ? FilterArgs{nf->group_a, (const u64*)nf->allow, nf->n_groups} : FilterArgs{nullptr, nullptr, 0};
-}
-static ScanArgs rect_args(const RectPlan& p, const RectPlanes& w, int nA, int nB, int K, float t, const int32_t* exr, const int32_t* exc,
-                          float min_logit, const dl_node_filter_between* nf) {
-    ScanArgs a = {};
-    a.cz = w.za; a.ch = w.ha; a.cbatch = p.cbatchA;
-    a.N = nA; a.K = K; a.nd = p.nd; a.nt = p.ntA; a.t = t;
-    a.ex_rowptr = exr; a.ex_col = exc;
-    a.min_logit = min_logit;
-    a.pairs = p.pairs; a.per_wg = p.per_wg;
-    a.filt = between_filter_args(nf);
-    a.rect.cz = w.zb; a.rect.ch = w.hb; a.rect.cbatch = p.cbatchB;
-    a.rect.N = nB; a.rect.nt = p.ntB;
-    a.rect.group = nf != nullptr ? nf->group_b : nullptr;
-    return a;
-}
-template <int MODE>
-static void launch_rect(const RectPlan& p, const ScanArgs& a, bool filtered, hipStream_t st) {
-    if (p.dt == DL_BF16) {
-        if (filtered) launch_lds<scan_tiles<rect_mode(MODE), true, 1>>((unsigned)p.grid, MTHR, lds_bytes(MODE, 1) + FILTER_LDS_BYTES, st, a);
-        else launch_lds<scan_tiles<rect_mode(MODE), false, 1>>((unsigned)p.grid, MTHR, lds_bytes(MODE, 1), st, a);
-    } else {
-        if (filtered) launch_lds<scan_tiles<rect_mode(MODE), true, 3>>((unsigned)p.grid, MTHR, lds_bytes(MODE, 3) + FILTER_LDS_BYTES, st, a);
-        else launch_lds<scan_tiles<rect_mode(MODE), false, 3>>((unsigned)p.grid, MTHR, lds_bytes(MODE, 3), st, a);
-    }
-}
-
-// out = nd, tiles of A, tiles of B, tile pairs, tile pairs per workgroup, workgroups of a scan, scans at most (digits + emit),
-// byte offset of the 32-bit count of scans that ran inside the (256-byte aligned) workspace
-void score_mine_between_form(int nA, int nB, int d, int* out) {
-    const RectPlan p = rect_plan(nA, nB, d);
-    out[0] = p.nd;
-    out[1] = p.ntA;
-    out[2] = p.ntB;
-    out[3] = p.pairs;
-    out[4] = p.per_wg;
-    out[5] = p.grid;
-    out[6] = PASSES + 1;
-    out[7] = (int)offsetof(State, scans);
-}
-
-// Workspace (256-byte aligned blocks): selection state | histogram | keys [m] | planes of ZA, HA, ZB, HB
-struct MineBetweenWs { State* state; unsigned* hist; u64* keys; RectPlanes pl; size_t bytes; };
-static MineBetweenWs mine_between_carve(const RectPlan& p, int K, int m, void* ws) {
-    MineBetweenWs w = {};
-    Carver c(ws);
-    w.state = c.take<State>(1);
-    w.hist = c.take<unsigned>(BINS);
-    w.keys = c.take<u64>((size_t)m);
-    w.pl = rect_planes(p, K, c);
-    w.bytes = c.bytes();
-    return w;
-}
-
-size_t score_mine_between_workspace_bytes(int nA, int nB, int K, int d, int m, dl_dtype dt) {
-    return mine_between_carve(rect_plan(nA, nB, d, dt), K, m, nullptr).bytes;
-}
-
-int score_mine_between(const void* ZA, const void* HA, const void* ZB, const void* HB, dl_dtype dt, int nA, int nB, int K, int d, float t,
-                       const int32_t* exr, const int32_t* exc, float min_logit, int m, int32_t* src, int32_t* dst, float* logit,
-                       float* prob, int64_t* count, void* ws, hipStream_t st, const dl_node_filter_between* nf) {
-    const RectPlan p = rect_plan(nA, nB, d, dt);
-    const MineBetweenWs w = mine_between_carve(p, K, m, ws);
-    hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, m);
-    rect_split(p, w.pl, ZA, HA, ZB, HB, nA, nB, K, d, st);
-    ScanArgs a = rect_args(p, w.pl, nA, nB, K, t, exr, exc, min_logit, nf);
-    a.state = w.state;
-    a.sel.m = m; a.sel.hist = w.hist; a.sel.keys = w.keys;
-    for (int pass = 0; pass < PASSES; ++pass) {
-        a.sel.pass = pass;
-        launch_rect<HIST>(p, a, nf != nullptr, st);
-        hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, m);
-    }
-    launch_rect<EMIT>(p, a, nf != nullptr, st);
-    hipLaunchKernelGGL(order_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, w.state, w.keys, nB, m, src, dst, logit, prob,
-                       count);                                  // the pair index decodes with nB: src A-local, dst B-local
-    return check_launch("score_mine_between");
-}
-
-// out = the first six fields of score_mine_between_form, scans of count + fill, cells of the A side, cells of the B side
-void score_links_between_form(int nA, int nB, int d, int* out) {
-    score_mine_between_form(nA, nB, d, out);
-    const RectPlan p = rect_plan(nA, nB, d);
-    out[6] = 2;
-    out[7] = nA * p.ntB;                                        // <= 46,340 * 363
-    out[8] = nB * p.ntA;
-}
-
-// Workspace (256-byte aligned blocks): planes of ZA, HA, ZB, HB | cnt_a [nA][ntB] | cnt_b [nB][ntA] | deg_a [nA] | deg_b [nB]
-struct LinksBetweenWs { RectPlanes pl; unsigned *cnt_a, *cnt_b, *deg_a, *deg_b; size_t bytes; };
-static LinksBetweenWs links_between_carve(const RectPlan& p, int nA, int nB, int K, void* ws) {
-    LinksBetweenWs w = {};
-    Carver c(ws);
-    w.pl = rect_planes(p, K, c);
-    w.cnt_a = c.take<unsigned>((size_t)nA * p.ntB);
-    w.cnt_b = c.take<unsigned>((size_t)nB * p.ntA);
-    w.deg_a = c.take<unsigned>((size_t)nA);
-    w.deg_b = c.take<unsigned>((size_t)nB);
-    w.bytes = c.bytes();
-    return w;
-}
-
-size_t score_links_between_workspace_bytes(int nA, int nB, int K, int d, dl_dtype dt) {
-    return links_between_carve(rect_plan(nA, nB, d, dt), nA, nB, K, nullptr).bytes;
-}
-
-int score_links_between_count(const void* ZA, const void* HA, const void* ZB, const void* HB, dl_dtype dt, int nA, int nB, int K, int d,
-                              float t, const int32_t* exr, const int32_t* exc, float min_logit, const dl_node_filter_between* nf,
-                              void* ws, int64_t* rowptr_a, int64_t* rowptr_b, hipStream_t st) {
-    const RectPlan p = rect_plan(nA, nB, d, dt);
-    const LinksBetweenWs w = links_between_carve(p, nA, nB, K, ws);
-    rect_split(p, w.pl, ZA, HA, ZB, HB, nA, nB, K, d, st);
-    ScanArgs a = rect_args(p, w.pl, nA, nB, K, t, exr, exc, min_logit, nf);
-    a.link.cnt = w.cnt_a;
-    a.rect.link.cnt = w.cnt_b;
-    launch_rect<DEG>(p, a, nf != nullptr, st);
-    hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((nA + 3) / 4)), dim3(256), 0, st, w.cnt_a, w.deg_a, nA, p.ntB);
-    hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((nB + 3) / 4)), dim3(256), 0, st, w.cnt_b, w.deg_b, nB, p.ntA);
-    hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, w.deg_a, rowptr_a, nA, 1);
-    hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, w.deg_b, rowptr_b, nB, 1);
-    return check_launch("score_links_between_count");
-}
-
-int score_links_between_fill(dl_dtype dt, int nA, int nB, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
-                             const dl_node_filter_between* nf, void* ws, const int64_t* rowptr_a, const int64_t* rowptr_b,
-                             long long nnz_a, int32_t* col_a, float* logit_a, float* prob_a, long long nnz_b, int32_t* col_b,
-                             float* logit_b, float* prob_b, hipStream_t st) {
-    const RectPlan p = rect_plan(nA, nB, d, dt);
-    const LinksBetweenWs w = links_between_carve(p, nA, nB, K, ws);
-    if (nnz_a > 0 || nnz_b > 0) {                               // a side of length 0 takes no write: every slot is >= its nnz
-        ScanArgs a = rect_args(p, w.pl, nA, nB, K, t, exr, exc, min_logit, nf);
-        a.link = LinkArgs{w.cnt_a, rowptr_a, nnz_a, col_a, logit_a, prob_a};
-        a.rect.link = LinkArgs{w.cnt_b, rowptr_b, nnz_b, col_b, logit_b, prob_b};
-        launch_rect<FILL>(p, a, nf != nullptr, st);
-    }
-    return check_launch("score_links_between_fill");
 }
 
 // ---- dl_score_links_top: the m best candidates as that CSR — the select of score_mine (no EMIT, no ordering), then the link
@@ -1166,62 +1077,96 @@ void score_links_top_form(int N, int d, int* out) {
     out[7] = (int)offsetof(State, scans);
 }
 
-// Workspace (256-byte aligned blocks): selection state | histogram | the links workspace (planes of Z and H | cnt | deg)
-struct LinksTopWs { State* state; unsigned* hist; LinksWs links; size_t bytes; };
-static LinksTopWs links_top_carve(const MinePlan& p, int N, int K, void* ws) {
-    LinksTopWs w = {};
-    Carver c(ws);
-    w.state = c.take<State>(1);
-    w.hist = c.take<unsigned>(BINS);
-    w.links = links_carve(p, N, K, c);
-    w.bytes = w.links.bytes;
-    return w;
-}
-
 size_t score_links_top_workspace_bytes(int N, int K, int d, dl_dtype dt) {
-    return links_top_carve(mine_plan(N, d, dt), N, K, nullptr).bytes;
+    return carve(triangle(N, K, d, dt), WS_SELECT | WS_CELLS, 0, nullptr).bytes;
 }
 
 int score_links_top_count(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* exr,
                           const int32_t* exc, float min_logit, long long m, const dl_node_filter* nf, void* ws, int64_t* rowptr,
                           hipStream_t st) {
-    const MinePlan p = mine_plan(N, d, dt);
-    const LinksTopWs w = links_top_carve(p, N, K, ws);
+    const Plan p = triangle(N, K, d, dt);
+    const Ws w = carve(p, WS_SELECT | WS_CELLS, 0, ws);
+    const Rule r = rule_of(nf);
     // a budget above all pairs means every candidate; what is left fits the select's 32-bit counts (N <= 46,340)
     const long long all = (long long)N * (N - 1) / 2;
     const int need = (int)(m < all ? m : all);
     static_assert((long long)DL_SCORE_LINKS_MAX_N * (DL_SCORE_LINKS_MAX_N - 1) / 2 <= 2147483647LL, "pairs fit the select's need");
-    hipLaunchKernelGGL(init_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, need);
-    if (p.pairs > 0) {
-        split_tables(p, Z, H, N, K, d, w.links.cz, w.links.ch, st);
-        ScanArgs a = scan_args(p, w.links.cz, w.links.ch, N, K, t, exr, exc, min_logit, nf);
-        a.state = w.state;
-        a.sel.m = need; a.sel.hist = w.hist;
-        for (int pass = 0; pass < PASSES; ++pass) {
-            a.sel.pass = pass;
-            launch_tiles<HIST>(p, a, nf, st);
-            hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, st, w.state, w.hist, pass, need);
-        }
-        a.link.cnt = w.links.cnt;
-        launch_tiles<DEG_TOP>(p, a, nf, st);
-        hipLaunchKernelGGL(link_cells_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, w.links.cnt, w.links.deg, N, p.nt);
-    }
-    hipLaunchKernelGGL(link_rowptr_kernel, dim3(1), dim3(1024), 0, st, w.links.deg, rowptr, N, p.pairs > 0 ? 1 : 0);
+    ScanArgs a = scan_args(p, w, t, exr, exc, min_logit, r);
+    select(p, w, Tables{Z, H, nullptr, nullptr}, a, need, r.on, st);
+    count_links<DEG_TOP>(p, w, a, r.on, rowptr, nullptr, st);
     return check_launch("score_links_top_count");
 }
 
 int score_links_top_fill(dl_dtype dt, int N, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
                          const dl_node_filter* nf, void* ws, const int64_t* rowptr, long long nnz, int32_t* col, float* logit,
                          float* prob, hipStream_t st) {
-    const MinePlan p = mine_plan(N, d, dt);
-    const LinksTopWs w = links_top_carve(p, N, K, ws);
-    if (p.pairs > 0 && nnz > 0) {
-        ScanArgs a = scan_args(p, w.links.cz, w.links.ch, N, K, t, exr, exc, min_logit, nf);
-        a.state = w.state;                                      // the threshold the count's select left
-        a.link = LinkArgs{w.links.cnt, rowptr, nnz, col, logit, prob};
-        launch_tiles<FILL_TOP>(p, a, nf, st);
-    }
+    const Plan p = triangle(N, K, d, dt);
+    const Ws w = carve(p, WS_SELECT | WS_CELLS, 0, ws);
+    const Rule r = rule_of(nf);
+    ScanArgs a = scan_args(p, w, t, exr, exc, min_logit, r);
+    a.state = w.state;                                          // the threshold the count's select left
+    fill_links<FILL_TOP>(p, a, r.on, LinkArgs{w.cnt_a, rowptr, nnz, col, logit, prob}, LinkArgs{}, st);
     return check_launch("score_links_top_fill");
+}
+
+// ---- dl_score_mine_between / dl_score_links_between: rows of a table A against rows of a table B (the RECT instantiations).
+// The same passes over the ntA x ntB grid of tile pairs, the pair index a nB + b local to the rectangle; a graph past the cap
+// of the triangular walk is the union of its diagonal blocks (the entries above on row slices) and of such rectangles, merged
+// by the caller (scans.py).
+// out = nd, tiles of A, tiles of B, tile pairs, tile pairs per workgroup, workgroups of a scan, scans at most (digits + emit),
+// byte offset of the 32-bit count of scans that ran inside the (256-byte aligned) workspace
+void score_mine_between_form(int nA, int nB, int d, int* out) {
+    plan_form(rectangle(nA, nB, 0, d), out);
+    out[6] = PASSES + 1;
+    out[7] = (int)offsetof(State, scans);
+}
+
+size_t score_mine_between_workspace_bytes(int nA, int nB, int K, int d, int m, dl_dtype dt) {
+    return carve(rectangle(nA, nB, K, d, dt), WS_SELECT, (size_t)m, nullptr).bytes;
+}
+
+int score_mine_between(const void* ZA, const void* HA, const void* ZB, const void* HB, dl_dtype dt, int nA, int nB, int K, int d, float t,
+                       const int32_t* exr, const int32_t* exc, float min_logit, int m, int32_t* src, int32_t* dst, float* logit,
+                       float* prob, int64_t* count, void* ws, hipStream_t st, const dl_node_filter_between* nf) {
+    return mine_pairs("score_mine_between", rectangle(nA, nB, K, d, dt), Tables{ZA, HA, ZB, HB}, t, exr, exc, min_logit, m, rule_of(nf),
+                      src, dst, logit, prob, count, ws, st);
+}
+
+// out = the first six fields of score_mine_between_form, scans of count + fill, cells of the A side, cells of the B side
+void score_links_between_form(int nA, int nB, int d, int* out) {
+    score_mine_between_form(nA, nB, d, out);
+    out[6] = 2;
+    out[7] = nA * out[2];                                       // <= 46,340 * 363
+    out[8] = nB * out[1];
+}
+
+size_t score_links_between_workspace_bytes(int nA, int nB, int K, int d, dl_dtype dt) {
+    return carve(rectangle(nA, nB, K, d, dt), WS_CELLS, 0, nullptr).bytes;
+}
+
+int score_links_between_count(const void* ZA, const void* HA, const void* ZB, const void* HB, dl_dtype dt, int nA, int nB, int K, int d,
+                              float t, const int32_t* exr, const int32_t* exc, float min_logit, const dl_node_filter_between* nf,
+                              void* ws, int64_t* rowptr_a, int64_t* rowptr_b, hipStream_t st) {
+    const Plan p = rectangle(nA, nB, K, d, dt);
+    const Ws w = carve(p, WS_CELLS, 0, ws);
+    const Rule r = rule_of(nf);
+    split_tables(p, w, Tables{ZA, HA, ZB, HB}, st);
+    ScanArgs a = scan_args(p, w, t, exr, exc, min_logit, r);
+    count_links<DEG>(p, w, a, r.on, rowptr_a, rowptr_b, st);
+    return check_launch("score_links_between_count");
+}
+
+int score_links_between_fill(dl_dtype dt, int nA, int nB, int K, int d, float t, const int32_t* exr, const int32_t* exc, float min_logit,
+                             const dl_node_filter_between* nf, void* ws, const int64_t* rowptr_a, const int64_t* rowptr_b,
+                             long long nnz_a, int32_t* col_a, float* logit_a, float* prob_a, long long nnz_b, int32_t* col_b,
+                             float* logit_b, float* prob_b, hipStream_t st) {
+    const Plan p = rectangle(nA, nB, K, d, dt);
+    const Ws w = carve(p, WS_CELLS, 0, ws);
+    const Rule r = rule_of(nf);
+    ScanArgs a = scan_args(p, w, t, exr, exc, min_logit, r);
+    fill_links<FILL>(p, a, r.on, LinkArgs{w.cnt_a, rowptr_a, nnz_a, col_a, logit_a, prob_a},
+                     LinkArgs{w.cnt_b, rowptr_b, nnz_b, col_b, logit_b, prob_b}, st);
+    return check_launch("score_links_between_fill");
 }
 
 }  // namespace dl

@@ -747,24 +747,9 @@ static PairWs pair_carve(int N, int K, int d, dl_dtype dt, void* ws) {
 
 size_t score_pair_logits_workspace_bytes(int N, int K, int d, dl_dtype dt) { return pair_carve(N, K, d, dt, nullptr).bytes; }
 
-int score_pair_logits(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
-                      int T, float* logit, void* ws, hipStream_t st) {
-    const PairWs w = pair_carve(N, K, d, dt, ws);
-    table_planes(Z, dt, nullptr, N, K, d, w.cz, st);
-    table_planes(H, dt, nullptr, N, K, d, w.ch, st);
-    ScanArgs g = {};
-    g.qz = w.cz; g.qh = w.ch; g.qbatch = w.cbatch;
-    g.cz = w.cz; g.ch = w.ch; g.cbatch = w.cbatch;
-    g.N = N; g.K = K; g.nd = (d + SDC - 1) / SDC; g.t = t;
-    g.trow = a; g.tdst = b; g.T = T; g.tlogit = logit;
-    launch_rank<DIAG>(dt, nullptr, (unsigned)xcd_grid((T + TT - 1) / TT, 1), st, g);
-    return check_launch("score_pair_logits");
-}
-
-// ---- dl_score_pair_terms: the same pass in its TERMS instantiation, which writes what the pass holds per factor (e, q, the
-// running sum) for the pair on the diagonal instead of the final sum alone.  Same workspace, same operands, same products.
-int score_pair_terms(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
-                     int T, float* e, float* q, float* cum, void* ws, hipStream_t st) {
+// the tables split into the workspace, and the pass's operands and pairs; what the pass writes is its caller's
+static ScanArgs pair_operands(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
+                              int T, void* ws, hipStream_t st) {
     const PairWs w = pair_carve(N, K, d, dt, ws);
     table_planes(Z, dt, nullptr, N, K, d, w.cz, st);
     table_planes(H, dt, nullptr, N, K, d, w.ch, st);
@@ -773,6 +758,22 @@ int score_pair_terms(const void* Z, const void* H, dl_dtype dt, int N, int K, in
     g.cz = w.cz; g.ch = w.ch; g.cbatch = w.cbatch;
     g.N = N; g.K = K; g.nd = (d + SDC - 1) / SDC; g.t = t;
     g.trow = a; g.tdst = b; g.T = T;
+    return g;
+}
+
+int score_pair_logits(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
+                      int T, float* logit, void* ws, hipStream_t st) {
+    ScanArgs g = pair_operands(Z, H, dt, N, K, d, t, a, b, T, ws, st);
+    g.tlogit = logit;
+    launch_rank<DIAG>(dt, nullptr, (unsigned)xcd_grid((T + TT - 1) / TT, 1), st, g);
+    return check_launch("score_pair_logits");
+}
+
+// ---- dl_score_pair_terms: the same pass in its TERMS instantiation, which writes what the pass holds per factor (e, q, the
+// running sum) for the pair on the diagonal instead of the final sum alone.  Same workspace, same operands, same products.
+int score_pair_terms(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, float t, const int32_t* a, const int32_t* b,
+                     int T, float* e, float* q, float* cum, void* ws, hipStream_t st) {
+    ScanArgs g = pair_operands(Z, H, dt, N, K, d, t, a, b, T, ws, st);
     g.te = e; g.tq = q; g.tcum = cum;
     const unsigned grid = (unsigned)xcd_grid((T + TT - 1) / TT, 1);
     if (dt == DL_BF16) launch_lds<rank_scan_kernel<TERMS, false, 1>>(grid, RTHR, lds_bytes(1), st, g);

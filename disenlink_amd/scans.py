@@ -34,29 +34,56 @@ def exclusion_csr(exclude, n_nodes: int, device=None):
     if isinstance(exclude, Graph):
         if exclude.n_nodes != N:
             raise ValueError(f"exclusion graph has {exclude.n_nodes} nodes, expected {N}")
-        ptr = exclude.rowptr.to(torch.int64)
-        rows = torch.repeat_interleave(torch.arange(exclude.row_offset, exclude.row_offset + exclude.n_rows,
-                                                    device=ptr.device), ptr[1:] - ptr[:-1])
-        cols = exclude.col[:rows.numel()].to(torch.int64)
-    elif isinstance(exclude, (tuple, list)):
+        rows = _csr_rows(exclude.rowptr, exclude.row_offset)
+        key = _sorted_keys(rows, exclude.col[:rows.numel()].to(torch.int64), N, device)
+    else:
+        key = _pair_keys(exclude, N, N, device, ("(rows, cols)", "[0, N)", "[N, N]"))
+    return _local_csr(*_split_keys(key, N), N)
+
+
+def _csr_rows(rowptr: torch.Tensor, first_row: int = 0) -> torch.Tensor:
+    """int64 [nnz]: the row of every entry of a CSR whose rows start at ``first_row``."""
+    ptr = rowptr.to(torch.int64)
+    return torch.repeat_interleave(torch.arange(first_row, first_row + ptr.numel() - 1, device=ptr.device), ptr[1:] - ptr[:-1])
+
+
+def _sorted_keys(rows: torch.Tensor, cols: torch.Tensor, n_cols: int, device) -> torch.Tensor:
+    """The distinct keys row * n_cols + col of int64 pairs, ascending (rows ascending, columns ascending in a row), on
+    ``device`` (default: where the pairs live)."""
+    dev = rows.device if device is None else torch.device(device)
+    return torch.unique(rows.to(dev) * n_cols + cols.to(dev))
+
+
+def _pair_keys(exclude, n_rows: int, n_cols: int, device, names) -> torch.Tensor:
+    """``_sorted_keys`` of an exclusion set given as a pair of index sequences or as a dense [n_rows, n_cols] mask
+    (entries != 0); ``names`` = how the refusals call the pair list, its range and the mask's shape."""
+    if isinstance(exclude, (tuple, list)):
         if len(exclude) != 2:
-            raise ValueError("an exclusion pair list is (rows, cols)")
+            raise ValueError(f"an exclusion pair list is {names[0]}")
         rows, cols = (torch.as_tensor(v, device=device).reshape(-1).to(torch.int64) for v in exclude)
         if rows.numel() != cols.numel():
             raise ValueError("exclusion rows and cols differ in length")
-        if rows.numel() and (int(rows.min()) < 0 or int(cols.min()) < 0 or int(rows.max()) >= N or int(cols.max()) >= N):
-            raise ValueError("exclusion pair outside [0, N)")
+        if rows.numel() and (int(rows.min()) < 0 or int(cols.min()) < 0 or int(rows.max()) >= n_rows
+                             or int(cols.max()) >= n_cols):
+            raise ValueError(f"exclusion pair outside {names[1]}")
     else:
         m = torch.as_tensor(exclude, device=device)
-        if m.dim() != 2 or tuple(m.shape) != (N, N):
-            raise ValueError(f"an exclusion mask must be [N, N] = [{N}, {N}], got {tuple(m.shape)}")
+        if m.dim() != 2 or tuple(m.shape) != (n_rows, n_cols):
+            raise ValueError(f"an exclusion mask must be {names[2]} = [{n_rows}, {n_cols}], got {tuple(m.shape)}")
         rows, cols = torch.nonzero(m, as_tuple=True)
-    dev = rows.device if device is None else torch.device(device)
-    key = torch.unique(rows.to(dev) * N + cols.to(dev))               # sorted: rows ascending, columns ascending in a row
-    r = torch.div(key, N, rounding_mode="floor")
-    rowptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
-    rowptr[1:] = torch.cumsum(torch.bincount(r, minlength=N), dim=0)
-    return rowptr.to(torch.int32), (key - r * N).to(torch.int32)
+    return _sorted_keys(rows, cols, n_cols, device)
+
+
+def _split_keys(key: torch.Tensor, n_cols: int):
+    r = torch.div(key, n_cols, rounding_mode="floor")
+    return r, key - r * n_cols
+
+
+def _local_csr(rows: torch.Tensor, cols: torch.Tensor, n_rows: int):
+    """(rowptr int32 [n_rows+1], col int32) of int64 pairs already sorted by row, then column."""
+    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), dim=0)
+    return rowptr.to(torch.int32), cols.to(torch.int32)
 
 
 def _scan_dtype(table_dtype) -> int:
@@ -115,6 +142,22 @@ def _csr_args(rowptr, col, device):
     return rowptr.data_ptr(), col.data_ptr(), (rowptr, col)
 
 
+def _group_array(groups, what: str = "groups", n=None) -> torch.Tensor:
+    """The one check of a group array's form: 1-D, of an integer type and, where ``n`` is given, of n entries."""
+    g = torch.as_tensor(groups)
+    if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex or (n is not None and g.numel() != n):
+        of = "" if n is None else f" of {n} entries"
+        raise ValueError(f"{what} must be a 1-D integer array{of}, got {tuple(g.shape)} {g.dtype}")
+    return g
+
+
+def _group_range(g: torch.Tensor, n: int, what: str = "groups") -> None:
+    """... and of its values, all in [0, n): ONE host read."""
+    lo, hi = (int(v) for v in torch.stack(torch.aminmax(g.to(torch.int64))).tolist())
+    if lo < 0 or hi >= n:
+        raise ValueError(f"{what} outside [0, {n}): min {lo}, max {hi}")
+
+
 class NodeFilter:
     """A rule on node GROUPS for the candidate scans (dl_node_filter): ``groups`` [N] gives every node a group below
     ``n_groups`` <= 64, and the boolean matrix ``allow`` [n_groups, n_groups] says whether a row of group g may take a
@@ -125,18 +168,14 @@ class NodeFilter:
     ValueError otherwise; ``candidates`` carries a rule of its own for them (both endpoints in the pool)."""
 
     def __init__(self, groups, allow, device=None, _pair_allow=None):
-        g = torch.as_tensor(groups)
-        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex:
-            raise ValueError(f"groups must be a 1-D integer array, got {tuple(g.shape)} {g.dtype}")
+        g = _group_array(groups)
         a = torch.as_tensor(allow).detach().to("cpu")
         if a.dim() != 2 or a.shape[0] != a.shape[1] or not 1 <= a.shape[0] <= 64:
             raise ValueError(f"allow must be [n_groups, n_groups] with 1 <= n_groups <= 64, got {tuple(a.shape)}")
         a = a != 0
         n = int(a.shape[0])
         if g.numel():
-            lo, hi = (int(v) for v in torch.stack(torch.aminmax(g.to(torch.int64))).tolist())       # the one host read
-            if lo < 0 or hi >= n:
-                raise ValueError(f"groups outside [0, {n}): min {lo}, max {hi}")
+            _group_range(g, n)                                         # the one host read
         self.symmetric = bool(torch.equal(a, a.t()))
         pair = _pair_allow if _pair_allow is not None else a if self.symmetric else None      # the unordered scans' rule
         dev = g.device if device is None else torch.device(device)
@@ -155,9 +194,7 @@ class NodeFilter:
 
     @staticmethod
     def _dense_groups(groups):
-        g = torch.as_tensor(groups)
-        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex:
-            raise ValueError(f"groups must be a 1-D integer array, got {tuple(g.shape)} {g.dtype}")
+        g = _group_array(groups)
         n = int(g.max()) + 1 if g.numel() else 1
         if n > 64 or (g.numel() and int(g.min()) < 0):
             raise ValueError(f"a node filter takes groups 0..63, got {int(g.min())}..{n - 1}")
@@ -357,10 +394,35 @@ def _unordered_exclusion_csr(exclude, N: int, device):
     rowptr, col = exclusion_csr(exclude, N, device)
     if rowptr is None:
         return None, None
-    ptr = rowptr.to(torch.int64)
-    rows = torch.repeat_interleave(torch.arange(N, device=ptr.device), ptr[1:] - ptr[:-1])
-    cols = col.to(torch.int64)
+    rows, cols = _csr_rows(rowptr), col.to(torch.int64)
     return exclusion_csr((torch.minimum(rows, cols), torch.maximum(rows, cols)), N, device)
+
+
+def _operands(tables, K: int, d: int, dt: int):
+    """The tables of a scan of the mining family — ``[(Z, H)]``: the unordered pairs of one node set, a triangle;
+    ``[(ZA, HA), (ZB, HB)]``: rows of A against rows of B, a rectangle — as their C entries take them -> (the suffix of
+    the entries' names, the leading arguments of the entry, the arguments of its sizer, the rows per side)."""
+    (ZA, HA), nA = tables[0], int(tables[0][0].shape[0])
+    if len(tables) == 1:
+        return "", (ZA.data_ptr(), HA.data_ptr(), nA, K, d, dt), (nA, K, d, dt), (nA,)
+    (ZB, HB), nB = tables[1], int(tables[1][0].shape[0])
+    return ("_between", (ZA.data_ptr(), HA.data_ptr(), nA, ZB.data_ptr(), HB.data_ptr(), nB, K, d, dt), (nA, nB, K, d, dt),
+            (nA, nB))
+
+
+def _mine(tables, K: int, d: int, dt: int, t, m: int, excl, min_logit, nf):
+    """One mining call on prepared ``tables`` (``_operands``), exclusion CSR ``excl`` = (rowptr, col) and rule argument
+    ``nf`` -> (src, dst, logit, prob), local to the tables, cut to the count (the one host read)."""
+    between, lead, shape, _rows = _operands(tables, K, d, dt)
+    dev = tables[0][0].device
+    rp, cp, ws, _keep = _scan_buffers(excl, _scan_ws_bytes("mine" + between, *shape, m), dev)
+    src, dst = _empty(max(m, 0), torch.int32, dev), _empty(max(m, 0), torch.int32, dev)
+    logit, prob = _empty(max(m, 0), torch.float32, dev), _empty(max(m, 0), torch.float32, dev)
+    count = _empty(1, torch.int64, dev)
+    _scan_call("mine" + between, *lead, float(t), rp, cp, float(min_logit), m, src.data_ptr(), dst.data_ptr(), logit.data_ptr(),
+               prob.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf)
+    c = int(count.item())
+    return src[:c], dst[:c], logit[:c], prob[:c]
 
 
 def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf"), node_filter=None,
@@ -376,53 +438,71 @@ def score_mine(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-
     dt = _scan_dtype(table_dtype)
     Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
     m = int(m)
-    rp, cp, ws, _keep = _scan_buffers(_unordered_exclusion_csr(exclude, N, Z.device), _scan_ws_bytes("mine", N, K, d, dt, m),
-                                      Z.device)
+    excl = _unordered_exclusion_csr(exclude, N, Z.device)
     nf, _keep_nf = _filter_arg(node_filter, N, Z.device, True)
-    src = _empty(max(m, 0), torch.int32, Z.device)
-    dst = _empty(max(m, 0), torch.int32, Z.device)
-    logit = _empty(max(m, 0), torch.float32, Z.device)
-    prob = _empty(max(m, 0), torch.float32, Z.device)
-    count = _empty(1, torch.int64, Z.device)
-    _scan_call("mine", Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), rp, cp, float(min_logit), m, src.data_ptr(),
-               dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf)
-    c = int(count.item())
-    return src[:c], dst[:c], logit[:c], prob[:c]
+    return _mine([(Z, H)], K, d, dt, t, m, excl, min_logit, nf)
 
 
 # ---------------------------------------------------------------------- every pair above a floor, as a CSR (DEG / FILL scans)
 LINKS_MAX_N = MINE_MAX_N
+_INT64_MAX = (1 << 63) - 1
 
 
-def _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype=torch.float32):
-    """The count pass of ``score_links``: -> (rowptr int64 [N+1] on the device, the arguments the fill pass shares with it,
-    keep-alive)."""
+def _links_count(tables, K: int, d: int, dt: int, t, excl, min_logit, nf, budget=None):
+    """The count pass of a link graph on prepared ``tables`` (``_operands``), exclusion CSR ``excl`` and rule argument
+    ``nf``; ``budget``: the m of the budgeted graph (one node set only) -> (the int64 rowptr of every side, on the device;
+    the name of the graph's entries; the arguments the fill pass shares with the count; keep-alive)."""
+    between, lead, shape, rows = _operands(tables, K, d, dt)
+    name = "links" + (between if budget is None else "_top")
+    dev = tables[0][0].device
+    ex = _csr_args(*excl, dev)
+    # a workspace of its own, held across the two calls: the shared grow-only buffer may be handed out (and, under DL_POISON,
+    # refilled) in between, and the fill pass reads the planes, the cell offsets and (budgeted) the threshold the count left
+    ws = _empty(max(256, _scan_ws_bytes(name, *shape)), torch.uint8, dev)
+    rowptrs = [_empty(n + 1, torch.int64, dev) for n in rows]
+    head = (*lead, float(t), ex[0], ex[1], float(min_logit), *(() if budget is None else (budget,)), nf, ws.data_ptr(),
+            ws.numel(), *map(torch.Tensor.data_ptr, rowptrs))
+    _scan_call(name + "_count", *head, _stream())
+    return rowptrs, name, head, (tables, ex, ws)
+
+
+def _links_fill(rowptrs, name: str, head):
+    """The fill pass of a link graph: the one host read, of the number of entries (every side holds every pair once, a
+    symmetric CSR twice), three arrays of that length per side, and the fill entry with the count's arguments ``head`` ->
+    a (rowptr, col, logit, prob) per side."""
+    nnz = int(rowptrs[0][-1].item())                                  # the one host read
+    dev = rowptrs[0].device
+    sides, args = [], []
+    for rowptr in rowptrs:
+        col, logit, prob = _empty(nnz, torch.int32, dev), _empty(nnz, torch.float32, dev), _empty(nnz, torch.float32, dev)
+        sides.append((rowptr, col, logit, prob))
+        args += (nnz, col.data_ptr(), logit.data_ptr(), prob.data_ptr())
+    _scan_call(name + "_fill", *head, *args, _stream())
+    return sides
+
+
+def _links(tables, K: int, d: int, dt: int, t, excl, min_logit, nf, fill: bool = True):
+    """Both passes -> a (rowptr, col, logit, prob) per side; ``fill=False``: the count alone, col / logit / prob None."""
+    rowptrs, name, head, _keep = _links_count(tables, K, d, dt, t, excl, min_logit, nf)
+    return _links_fill(rowptrs, name, head) if fill else [(rowptr, None, None, None) for rowptr in rowptrs]
+
+
+def _graph_count(Z, H, t, min_logit, exclude, node_filter, table_dtype, budget=None):
+    """How ``score_links``, ``score_link_degrees`` and (with the ``budget`` m) ``score_top_links`` start: the refusals, the
+    exclusion CSR, the rule, then ``_links_count`` on the one table pair."""
     dt = _scan_dtype(table_dtype)
     Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
     if N > LINKS_MAX_N:
         raise ValueError(f"N={N} above {LINKS_MAX_N} (the tile-pair walk of dl_score_mine)")
-    excl = _csr_args(*_unordered_exclusion_csr(exclude, N, Z.device), Z.device)
-    nf, _keep_nf = _filter_arg(node_filter, N, Z.device, True)
-    # a workspace of its own, held across the two calls: the shared grow-only buffer may be handed out (and, under DL_POISON,
-    # refilled) in between, and the fill pass reads the planes and the cell offsets the count pass left
-    ws = _empty(max(256, _scan_ws_bytes("links", N, K, d, dt)), torch.uint8, Z.device)
-    rowptr = _empty(N + 1, torch.int64, Z.device)
-    head = (Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), excl[0], excl[1], float(min_logit), nf, ws.data_ptr(), ws.numel(),
-            rowptr.data_ptr())
-    _scan_call("links_count", *head, _stream())
-    return rowptr, head, (Z, H, excl, _keep_nf, ws)
-
-
-def _links_fill(name: str, rowptr, head):
-    """The fill pass of a link graph: the one host read, of rowptr[N], the three arrays of that length, and the fill entry
-    ``name`` with the count's arguments ``head`` -> (rowptr, col, logit, prob)."""
-    nnz = int(rowptr[-1].item())                                      # the one host read
-    dev = rowptr.device
-    col = _empty(nnz, torch.int32, dev)
-    logit = _empty(nnz, torch.float32, dev)
-    prob = _empty(nnz, torch.float32, dev)
-    _scan_call(name, *head, nnz, col.data_ptr(), logit.data_ptr(), prob.data_ptr(), _stream())
-    return rowptr, col, logit, prob
+    if budget is None:
+        excl = _unordered_exclusion_csr(exclude, N, Z.device)
+    else:
+        budget = min(int(budget), _INT64_MAX)
+        ex = _exclusion_arg(exclude, N, Z.device, keyed=False)
+        excl = (ex.rowptr, ex.col)
+    nf, keep_nf = _filter_arg(node_filter, N, Z.device, True)
+    rowptrs, name, head, keep = _links_count([(Z, H)], K, d, dt, t, excl, min_logit, nf, budget)
+    return rowptrs, name, head, (keep, keep_nf)
 
 
 def score_links(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32):
@@ -434,21 +514,18 @@ def score_links(Z, H, t: float, min_logit: float, exclude=None, node_filter=None
     never; the bits are those of ``score_pair_logits(min(u, v), max(u, v))``.  N <= 46,340, fp32 or bf16 tables.  Inference only;
     nothing of size N x N is formed (dl_score_links_count / dl_score_links_fill: two scans), there is no cap on nnz, and the
     one host read is that of rowptr[N], between the scans, to allocate the outputs.  Same bits on every call."""
-    rowptr, head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
-    return _links_fill("links_fill", rowptr, head)
+    rowptrs, name, head, _keep = _graph_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
+    return _links_fill(rowptrs, name, head)[0]
 
 
 def score_link_degrees(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32):
     """-> int64 [N]: the predicted degree of every node, i.e. how many partners ``score_links`` would list for it — the
     count pass alone (dl_score_links_count): one scan, no host read, no fill."""
-    rowptr, _head, _keep = _links_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
+    (rowptr,), _name, _head, _keep = _graph_count(Z, H, t, min_logit, exclude, node_filter, table_dtype)
     return rowptr[1:] - rowptr[:-1]
 
 
 # ---------------------------------------------------------------------- the m best pairs, any m, as a CSR (select, then DEG / FILL)
-_INT64_MAX = (1 << 63) - 1
-
-
 def score_top_links(Z, H, t: float, m: int, exclude=None, min_logit: float = float("-inf"), node_filter=None,
                     table_dtype=torch.float32):
     """-> (rowptr int64 [N+1], col int32 [nnz], logit f32 [nnz], prob f32 [nnz]), nnz = 2 min(m, eligible): the m most
@@ -461,29 +538,8 @@ def score_top_links(Z, H, t: float, m: int, exclude=None, min_logit: float = flo
     nothing of size N x N is formed (dl_score_links_top_count / _fill: the select of ``score_mine``, at most six histogram
     scans, then the two scans of ``score_links`` under the threshold key it left on the device), and the one host read is
     that of rowptr[N], to allocate the outputs.  Same bits on every call."""
-    dt = _scan_dtype(table_dtype)
-    Z, H, N, K, d = _scan_tables(Z, H, node_filter, True, table_dtype)
-    if N > LINKS_MAX_N:
-        raise ValueError(f"N={N} above {LINKS_MAX_N} (the tile-pair walk of dl_score_mine)")
-    m = min(int(m), _INT64_MAX)
-    if isinstance(exclude, PairExclusion):
-        if exclude.n_nodes != N:
-            raise ValueError(f"exclusion set of {exclude.n_nodes} nodes, expected {N}")
-        if exclude.rowptr is not None and exclude.rowptr.device != Z.device:
-            raise ValueError(f"exclusion set on {exclude.rowptr.device}, tables on {Z.device}")
-        csr = (exclude.rowptr, exclude.col)
-    else:
-        csr = _unordered_exclusion_csr(exclude, N, Z.device)
-    excl = _csr_args(*csr, Z.device)
-    nf, _keep_nf = _filter_arg(node_filter, N, Z.device, True)
-    # a workspace of its own, held across the two calls, as in ``_links_count``: the fill reads the threshold, the planes and
-    # the cell offsets the count left
-    ws = _empty(max(256, _scan_ws_bytes("links_top", N, K, d, dt)), torch.uint8, Z.device)
-    rowptr = _empty(N + 1, torch.int64, Z.device)
-    head = (Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), excl[0], excl[1], float(min_logit), m, nf, ws.data_ptr(),
-            ws.numel(), rowptr.data_ptr())
-    _scan_call("links_top_count", *head, _stream())
-    return _links_fill("links_top_fill", rowptr, head)
+    rowptrs, name, head, _keep = _graph_count(Z, H, t, min_logit, exclude, node_filter, table_dtype, budget=m)
+    return _links_fill(rowptrs, name, head)[0]
 
 
 # ---------------------------------------------------------------------- where given pairs stand among ALL pairs (COUNT scan)
@@ -505,10 +561,23 @@ def pair_exclusion(exclude, N: int, device) -> PairExclusion:
     rowptr, col = _unordered_exclusion_csr(exclude, N, device)
     if rowptr is None:
         return PairExclusion(N, None, None, None, torch.zeros(1, dtype=torch.int64, device=device))
-    ptr = rowptr.to(torch.int64)
-    rows = torch.repeat_interleave(torch.arange(N, device=ptr.device), ptr[1:] - ptr[:-1])
-    cols = col.to(torch.int64)
+    rows, cols = _csr_rows(rowptr), col.to(torch.int64)
     return PairExclusion(N, rowptr, col, rows * N + cols, (cols > rows).sum().reshape(1))
+
+
+def _exclusion_arg(exclude, N: int, device, keyed: bool) -> PairExclusion:
+    """``exclude`` as a scan takes it: a prepared ``PairExclusion``, accepted if it is of N nodes and on ``device``, or a raw
+    set of unordered pairs, normalised here — with its keys and pair count (``pair_exclusion``) if ``keyed``, else the CSR
+    alone."""
+    if not isinstance(exclude, PairExclusion):
+        if keyed:
+            return pair_exclusion(exclude, N, device)
+        return PairExclusion(N, *_unordered_exclusion_csr(exclude, N, device), None, None)
+    if exclude.n_nodes != N:
+        raise ValueError(f"exclusion set of {exclude.n_nodes} nodes, expected {N}")
+    if exclude.rowptr is not None and exclude.rowptr.device != device:
+        raise ValueError(f"exclusion set on {exclude.rowptr.device}, tables on {device}")
+    return exclude
 
 
 def _score_pairs(name: str, Z, H, t: float, a, b, table_dtype, per_factor: bool):
@@ -584,9 +653,7 @@ def score_pair_ranks_counted(Z, H, t: float, src, dst, exclude=None, node_filter
     if bool((s == v).any()):
         raise ValueError("a target is a self pair (src[i] == dst[i])")
     T = int(s.numel())
-    ex = exclude if isinstance(exclude, PairExclusion) else pair_exclusion(exclude, N, dev)
-    if ex.n_nodes != N:
-        raise ValueError(f"exclusion set of {ex.n_nodes} nodes, expected {N}")
+    ex = _exclusion_arg(exclude, N, dev, keyed=True)
     rowptr, col, ex_key = ex.rowptr, ex.col, ex.key
     total = N * (N - 1) // 2 - ex.n_pairs
     nf, _keep_nf = _filter_arg(node_filter, N, dev, True)
@@ -655,33 +722,8 @@ def bipartite_exclusion_csr(exclude, nA: int, nB: int, device=None):
     if exclude is None:
         return None, None
     nA, nB = int(nA), int(nB)
-    if isinstance(exclude, (tuple, list)):
-        if len(exclude) != 2:
-            raise ValueError("an exclusion pair list is (rows_a, cols_b)")
-        rows, cols = (torch.as_tensor(v, device=device).reshape(-1).to(torch.int64) for v in exclude)
-        if rows.numel() != cols.numel():
-            raise ValueError("exclusion rows and cols differ in length")
-        if rows.numel() and (int(rows.min()) < 0 or int(cols.min()) < 0 or int(rows.max()) >= nA or int(cols.max()) >= nB):
-            raise ValueError(f"exclusion pair outside [0, {nA}) x [0, {nB})")
-    else:
-        m = torch.as_tensor(exclude, device=device)
-        if m.dim() != 2 or tuple(m.shape) != (nA, nB):
-            raise ValueError(f"an exclusion mask must be [nA, nB] = [{nA}, {nB}], got {tuple(m.shape)}")
-        rows, cols = torch.nonzero(m, as_tuple=True)
-    dev = rows.device if device is None else torch.device(device)
-    return _local_csr(*_split_keys(torch.unique(rows.to(dev) * nB + cols.to(dev)), nB), nA)
-
-
-def _split_keys(key: torch.Tensor, n_cols: int):
-    r = torch.div(key, n_cols, rounding_mode="floor")
-    return r, key - r * n_cols
-
-
-def _local_csr(rows: torch.Tensor, cols: torch.Tensor, n_rows: int):
-    """(rowptr int32 [n_rows+1], col int32) of int64 pairs already sorted by row, then column."""
-    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=rows.device)
-    rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n_rows), dim=0)
-    return rowptr.to(torch.int32), cols.to(torch.int32)
+    key = _pair_keys(exclude, nA, nB, device, ("(rows_a, cols_b)", f"[0, {nA}) x [0, {nB})", "[nA, nB]"))
+    return _local_csr(*_split_keys(key, nB), nA)
 
 
 def _between_rule(rule, nA: int, nB: int, device):
@@ -691,15 +733,12 @@ def _between_rule(rule, nA: int, nB: int, device):
         raise TypeError("rule is (groups_a, groups_b, allow[g, h])")
     ga, gb = (torch.as_tensor(v) for v in rule[:2])
     allow = torch.as_tensor(rule[2]).detach().to("cpu") != 0
-    for g, n, what in ((ga, nA, "groups_a"), (gb, nB, "groups_b")):
-        if g.dim() != 1 or g.dtype.is_floating_point or g.dtype.is_complex or g.numel() != n:
-            raise ValueError(f"{what} must be a 1-D integer array of {n} entries, got {tuple(g.shape)} {g.dtype}")
+    _group_array(ga, "groups_a", nA)
+    _group_array(gb, "groups_b", nB)
     if allow.dim() != 2 or not (1 <= allow.shape[0] <= 64 and 1 <= allow.shape[1] <= 64):
         raise ValueError(f"allow must be [g, h] with 1 <= g, h <= 64, got {tuple(allow.shape)}")
-    for g, n, what in ((ga, int(allow.shape[0]), "groups_a"), (gb, int(allow.shape[1]), "groups_b")):
-        lo, hi = (int(v) for v in torch.stack(torch.aminmax(g.to(torch.int64))).tolist())
-        if lo < 0 or hi >= n:
-            raise ValueError(f"{what} outside [0, {n}): min {lo}, max {hi}")
+    _group_range(ga, int(allow.shape[0]), "groups_a")
+    _group_range(gb, int(allow.shape[1]), "groups_b")
     n = int(max(allow.shape))
     square = torch.zeros(n, n, dtype=torch.bool)
     square[:allow.shape[0], :allow.shape[1]] = allow
@@ -726,19 +765,14 @@ def _between_tables(ZA, HA, ZB, HB, table_dtype):
     return ZA, HA, ZB, HB, nA, nB, K, d
 
 
-def _mine_between(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, m, excl, min_logit, nf):
-    """One rectangular mining call on prepared tables, exclusion CSR ``excl`` = (rowptr, col) and rule argument ``nf`` ->
-    (src A-local, dst B-local, logit, prob), cut to the count (the one host read)."""
-    dev = ZA.device
-    rp, cp, ws, _keep = _scan_buffers(excl, _scan_ws_bytes("mine_between", nA, nB, K, d, dt, m), dev)
-    src, dst = _empty(max(m, 0), torch.int32, dev), _empty(max(m, 0), torch.int32, dev)
-    logit, prob = _empty(max(m, 0), torch.float32, dev), _empty(max(m, 0), torch.float32, dev)
-    count = _empty(1, torch.int64, dev)
-    _scan_call("mine_between", ZA.data_ptr(), HA.data_ptr(), nA, ZB.data_ptr(), HB.data_ptr(), nB, K, d, dt, float(t), rp, cp,
-               float(min_logit), m, src.data_ptr(), dst.data_ptr(), logit.data_ptr(), prob.data_ptr(), count.data_ptr(),
-               ws.data_ptr(), ws.numel(), _stream(), nf)
-    c = int(count.item())
-    return src[:c], dst[:c], logit[:c], prob[:c]
+def _between_start(ZA, HA, ZB, HB, rule, table_dtype):
+    """How the scans between two node sets start: the refusals of the rule, then of the tables -> (tables as ``_operands``
+    takes them, nA, nB, K, d, dt, rule argument, its keep-alive)."""
+    dt = _scan_dtype(table_dtype)
+    ruled = None if rule is None else _between_rule(rule, int(ZA.shape[0]), int(ZB.shape[0]), ZA.device)      # its refusals first
+    ZA, HA, ZB, HB, nA, nB, K, d = _between_tables(ZA, HA, ZB, HB, table_dtype)
+    nf, keep_nf = (None, ()) if ruled is None else _between_filter_arg(*ruled)
+    return [(ZA, HA), (ZB, HB)], nA, nB, K, d, dt, nf, keep_nf
 
 
 def score_mine_between(ZA, HA, ZB, HB, t: float, m: int, exclude=None, min_logit: float = float("-inf"), rule=None,
@@ -752,37 +786,11 @@ def score_mine_between(ZA, HA, ZB, HB, t: float, m: int, exclude=None, min_logit
     it need not be symmetric) or below ``min_logit`` (NaN never is eligible).  1 <= m <= 65,536, nA, nB <= 46,340.  Only the
     ceil(nA/128) x ceil(nB/128) tile pairs of the rectangle are formed (dl_score_mine_between_dtype), where
     ``NodeFilter.between`` on the concatenated table walks (nA + nB)^2 / 2 products for the same result."""
-    dt = _scan_dtype(table_dtype)
-    ruled = None if rule is None else _between_rule(rule, int(ZA.shape[0]), int(ZB.shape[0]), ZA.device)      # its refusals first
-    ZA, HA, ZB, HB, nA, nB, K, d = _between_tables(ZA, HA, ZB, HB, table_dtype)
-    nf, _keep_nf = (None, ()) if ruled is None else _between_filter_arg(*ruled)
-    return _mine_between(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, int(m), bipartite_exclusion_csr(exclude, nA, nB, ZA.device),
-                         min_logit, nf)
+    tables, nA, nB, K, d, dt, nf, _keep_nf = _between_start(ZA, HA, ZB, HB, rule, table_dtype)
+    return _mine(tables, K, d, dt, t, int(m), bipartite_exclusion_csr(exclude, nA, nB, tables[0][0].device), min_logit, nf)
 
 
 LinksBetween = namedtuple("LinksBetween", ["ab", "ba"])
-
-
-def _links_between_count(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, excl, min_logit, nf):
-    """The count pass of a rectangle -> (rowptr_a, rowptr_b, the arguments the fill shares with it, keep-alive)."""
-    dev = ZA.device
-    ex = _csr_args(*excl, dev)
-    ws = _empty(max(256, _scan_ws_bytes("links_between", nA, nB, K, d, dt)), torch.uint8, dev)      # held across the two calls
-    rowptr_a, rowptr_b = _empty(nA + 1, torch.int64, dev), _empty(nB + 1, torch.int64, dev)
-    head = (ZA.data_ptr(), HA.data_ptr(), nA, ZB.data_ptr(), HB.data_ptr(), nB, K, d, dt, float(t), ex[0], ex[1],
-            float(min_logit), nf, ws.data_ptr(), ws.numel(), rowptr_a.data_ptr(), rowptr_b.data_ptr())
-    _scan_call("links_between_count", *head, _stream())
-    return rowptr_a, rowptr_b, head, (ex, ws)
-
-
-def _links_between(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, excl, min_logit, nf) -> LinksBetween:
-    rowptr_a, rowptr_b, head, _keep = _links_between_count(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, excl, min_logit, nf)
-    nnz = int(rowptr_a[-1].item())                                    # the one host read: both sides hold every pair once
-    dev = ZA.device
-    sides = [[_empty(nnz, torch.int32, dev), _empty(nnz, torch.float32, dev), _empty(nnz, torch.float32, dev)] for _ in range(2)]
-    _scan_call("links_between_fill", *head, nnz, *(v.data_ptr() for v in sides[0]), nnz, *(v.data_ptr() for v in sides[1]),
-               _stream())
-    return LinksBetween((rowptr_a, *sides[0]), (rowptr_b, *sides[1]))
 
 
 def score_links_between(ZA, HA, ZB, HB, t: float, min_logit: float, exclude=None, rule=None,
@@ -793,11 +801,8 @@ def score_links_between(ZA, HA, ZB, HB, t: float, min_logit: float, exclude=None
     columns ascending within a row, a -0 as +0.  Logit, eligibility, ``exclude`` and ``rule`` as in ``score_mine_between``;
     two scans and the one host read of the number of pairs, as in ``score_links`` (dl_score_links_between_count_dtype /
     _fill_dtype).  nA, nB <= 46,340."""
-    dt = _scan_dtype(table_dtype)
-    ruled = None if rule is None else _between_rule(rule, int(ZA.shape[0]), int(ZB.shape[0]), ZA.device)      # its refusals first
-    ZA, HA, ZB, HB, nA, nB, K, d = _between_tables(ZA, HA, ZB, HB, table_dtype)
-    nf, _keep_nf = (None, ()) if ruled is None else _between_filter_arg(*ruled)
-    return _links_between(ZA, HA, ZB, HB, nA, nB, K, d, dt, t, bipartite_exclusion_csr(exclude, nA, nB, ZA.device), min_logit, nf)
+    tables, nA, nB, K, d, dt, nf, _keep_nf = _between_start(ZA, HA, ZB, HB, rule, table_dtype)
+    return LinksBetween(*_links(tables, K, d, dt, t, bipartite_exclusion_csr(exclude, nA, nB, tables[0][0].device), min_logit, nf))
 
 
 # ---------------------------------------------------------------------- any N: diagonal blocks and rectangles, merged on the host
@@ -827,10 +832,8 @@ class _BlockWindows:
         rowptr, col = _unordered_exclusion_csr(exclude, self.N, self.dev)
         self.ex = None
         if rowptr is not None and col.numel():
-            ptr = rowptr.to(torch.int64)
-            r = torch.repeat_interleave(torch.arange(self.N, device=ptr.device), ptr[1:] - ptr[:-1])
-            c = col.to(torch.int64)
-            keep = c > r                                               # (u, u) entries exclude nothing
+            r, c = _csr_rows(rowptr), col.to(torch.int64)
+            keep = c > r                                              # (u, u) entries exclude nothing
             r, c = r[keep], c[keep]
             w = torch.div(r, self.bn, rounding_mode="floor") * nb + torch.div(c, self.bn, rounding_mode="floor")
             order = torch.argsort(w, stable=True)                     # within a window: rows ascending, columns ascending
@@ -843,9 +846,9 @@ class _BlockWindows:
         nb = len(self.blocks)
         return [(i, j) for i in range(nb) for j in range(i, nb)]
 
-    def tables(self, i):
-        lo, hi = self.blocks[i]
-        return self.Z[lo:hi], self.H[lo:hi]
+    def tables(self, i, j):
+        """The tables of window (i, j) as ``_operands`` takes them: the row slice of block i and, off the diagonal, of j."""
+        return [(self.Z[lo:hi], self.H[lo:hi]) for lo, hi in ([self.blocks[i]] if i == j else [self.blocks[i], self.blocks[j]])]
 
     def exclusion(self, i, j):
         """The sub-CSR of window (i, j): rows local to block i, columns local to block j (None, None: nothing excluded)."""
@@ -907,26 +910,11 @@ def score_mine_blocks(Z, H, t: float, m: int, exclude=None, min_logit: float = f
         need = max(need, _scan_ws_bytes("mine_between", n0, W.blocks[1][1] - W.blocks[1][0], W.K, W.d, W.dt, m))
     _ws.get(max(256, need), W.dev)
     for i, j in W.windows():
-        (lo_i, hi_i), (lo_j, hi_j) = W.blocks[i], W.blocks[j]
-        ZA, HA = W.tables(i)
         nf, _keep_nf = W.rule(i, j)
-        excl = W.exclusion(i, j)
-        if i == j:
-            n = hi_i - lo_i
-            rp, cp, ws, _keep = _scan_buffers(excl, _scan_ws_bytes("mine", n, W.K, W.d, W.dt, m), W.dev)
-            out = [_empty(m, dt_, W.dev) for dt_ in (torch.int32, torch.int32, torch.float32, torch.float32)]
-            count = _empty(1, torch.int64, W.dev)
-            _scan_call("mine", ZA.data_ptr(), HA.data_ptr(), n, W.K, W.d, W.dt, W.t, rp, cp, floor, m,
-                       *(o.data_ptr() for o in out), count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(), nf)
-            c = int(count.item())
-            src, dst, logit, prob = (o[:c] for o in out)
-        else:
-            ZB, HB = W.tables(j)
-            src, dst, logit, prob = _mine_between(ZA, HA, ZB, HB, hi_i - lo_i, hi_j - lo_j, W.K, W.d, W.dt, W.t, m, excl,
-                                                  floor, nf)
+        src, dst, logit, prob = _mine(W.tables(i, j), W.K, W.d, W.dt, W.t, m, W.exclusion(i, j), floor, nf)
         if src.numel() == 0:
             continue
-        best = _merge_top(best, (src.to(torch.int64) + lo_i, dst.to(torch.int64) + lo_j, logit, prob), W.N, m)
+        best = _merge_top(best, (src.to(torch.int64) + W.blocks[i][0], dst.to(torch.int64) + W.blocks[j][0], logit, prob), W.N, m)
         if best[0].numel() == m:                                      # full: nothing below the m-th can enter any more
             last = float(best[2][-1].item())
             floor = max(floor, last) if last == last else floor
@@ -940,29 +928,11 @@ def _links_windows(W: _BlockWindows, min_logit: float, fill: bool):
     """Runs every window of a blocked link graph; yields, per window side, (row block, column offset, piece) where piece is
     (rowptr int64 [rows+1], col, logit, prob) — col / logit / prob are None for ``fill=False`` (the count pass alone)."""
     for i, j in W.windows():
-        (lo_i, hi_i), (lo_j, hi_j) = W.blocks[i], W.blocks[j]
-        ZA, HA = W.tables(i)
         nf, _keep_nf = W.rule(i, j)
-        excl = W.exclusion(i, j)
-        if i == j:
-            n = hi_i - lo_i
-            ex = _csr_args(*excl, W.dev)
-            ws = _empty(max(256, _scan_ws_bytes("links", n, W.K, W.d, W.dt)), torch.uint8, W.dev)
-            rowptr = _empty(n + 1, torch.int64, W.dev)
-            head = (ZA.data_ptr(), HA.data_ptr(), n, W.K, W.d, W.dt, W.t, ex[0], ex[1], float(min_logit), nf, ws.data_ptr(),
-                    ws.numel(), rowptr.data_ptr())
-            _scan_call("links_count", *head, _stream())
-            yield i, lo_i, (_links_fill("links_fill", rowptr, head) if fill else (rowptr, None, None, None))
-        else:
-            ZB, HB = W.tables(j)
-            args = (ZA, HA, ZB, HB, hi_i - lo_i, hi_j - lo_j, W.K, W.d, W.dt, W.t, excl, min_logit, nf)
-            if fill:
-                ab, ba = _links_between(*args)
-            else:
-                rowptr_a, rowptr_b, _head, _keep = _links_between_count(*args)
-                ab, ba = (rowptr_a, None, None, None), (rowptr_b, None, None, None)
-            yield i, lo_j, ab
-            yield j, lo_i, ba
+        sides = _links(W.tables(i, j), W.K, W.d, W.dt, W.t, W.exclusion(i, j), min_logit, nf, fill)
+        yield i, W.blocks[j][0], sides[0]                              # rows of block i, columns local to block j
+        if i != j:
+            yield j, W.blocks[i][0], sides[1]
 
 
 def score_link_degrees_blocks(Z, H, t: float, min_logit: float, exclude=None, node_filter=None, table_dtype=torch.float32,

@@ -142,7 +142,7 @@ def test_form_and_workspace_are_host_only():
     assert _lib.score_pair_ranks_form(1, 2, 32, 3)["pairs"] == 0
 
 
-def test_form_at_the_largest_accepted_n_and_the_refusal_beyond_it(lib_env):
+def test_form_at_the_largest_accepted_n_and_the_refusal_beyond_it(lib_env, monkeypatch):
     """N = 8,388,480 = 65,535 tiles: 2,147,450,880 tile pairs, the most an int32 holds; the intermediates of the pair count
     and of the grid do not fit 32 bits there."""
     from disenlink_amd import _lib
@@ -168,6 +168,14 @@ def test_form_at_the_largest_accepted_n_and_the_refusal_beyond_it(lib_env):
     one = (lib.dl_score_pair_ranks(1, 1, top + 1, 1, 8, 1.0, None, None, None, 0, 1, 1, 1, None, 0, None),
            lib.dl_score_pair_logits(1, 1, top + 1, 1, 8, 1.0, 1, 1, 1, 1, None, 0, None))
     assert all(rc < 0 for rc in one) and b"8388480" in lib.dl_last_error()      # refused on the shape, before anything is read
+    # ... and, in Python, a prepared exclusion set on another device than the tables: refused before any call is made
+    from disenlink_amd import scans
+    monkeypatch.setattr(scans, "_need_cuda", lambda *tensors: None)
+    monkeypatch.setattr(scans, "_scan_call", lambda name, *args: pytest.fail(f"dl_score_{name} was called"))
+    Z = torch.zeros(8, 1, 8)
+    ex = scans.pair_exclusion((torch.tensor([0]), torch.tensor([1])), 8, "cpu")
+    with pytest.raises(ValueError, match="exclusion set on meta, tables on cpu"):
+        scans.score_pair_ranks(Z, Z, 1.0, [0, 2], [1, 3], exclude=ex._replace(rowptr=ex.rowptr.to("meta")))
 
 
 def test_gpu_cases_reach_every_chunk_count_and_run_length(lib_env):

@@ -59,6 +59,7 @@ SCANS = {                                         # name: (call(Z, H, **kw), tak
     "score_mine": (lambda Z, H, **kw: scans.score_mine(Z, H, 1.0, 16, exclude=EXCLUDE, **kw), True),
     "score_links": (lambda Z, H, **kw: scans.score_links(Z, H, 1.0, 0.0, exclude=EXCLUDE, **kw), True),
     "score_link_degrees": (lambda Z, H, **kw: scans.score_link_degrees(Z, H, 1.0, 0.0, exclude=EXCLUDE, **kw), True),
+    "score_top_links": (lambda Z, H, **kw: scans.score_top_links(Z, H, 1.0, 5, exclude=EXCLUDE, **kw), True),
     "score_pair_ranks": (lambda Z, H, **kw: scans.score_pair_ranks(Z, H, 1.0, IDS, OTHER, exclude=EXCLUDE, **kw), True),
     "score_pair_logits": (lambda Z, H, **kw: scans.score_pair_logits(Z, H, 1.0, IDS, OTHER, **kw), False),
     "score_pair_terms": (lambda Z, H, **kw: scans.score_pair_terms(Z, H, 1.0, IDS, OTHER, **kw), False),
@@ -69,6 +70,7 @@ ENTRIES = {                                       # the C entries each scan is m
     "score_mine": ["dl_score_mine_dtype"],
     "score_links": ["dl_score_links_count_dtype", "dl_score_links_fill_dtype"],
     "score_link_degrees": ["dl_score_links_count_dtype"],
+    "score_top_links": ["dl_score_links_top_count_dtype", "dl_score_links_top_fill_dtype"],
     "score_pair_ranks": ["dl_score_pair_logits_dtype", "dl_score_pair_ranks_dtype"],
     "score_pair_logits": ["dl_score_pair_logits_dtype"],
     "score_pair_terms": ["dl_score_pair_terms_dtype"],
@@ -98,7 +100,8 @@ def test_every_call_is_the_dtype_entry_with_its_own_argument_list(rec, name, tab
         assert args[:3] == (N, K, D) if "_workspace_bytes" in entry else args[2:5] == (N, K, D), entry
         if _lib._NF in codes:
             assert (args[codes.index(_lib._NF)] is None) == (not filtered), entry
-    if name == "score_links":
+    if name in ("score_links", "score_top_links"):
         (_, count), (_, fill) = [c for c in calls if "_workspace_bytes" not in c[0]]
-        assert fill[:13] == count[:13]
-        assert fill[13] == count[13] and fill[14] == 0                         # the same rowptr, then nnz
+        n = 13 if name == "score_links" else 14                                # the budgeted graph's m sits ahead of the rule
+        assert fill[:n] == count[:n]
+        assert fill[n] == count[n] and fill[n + 1] == 0                        # the same rowptr, then nnz
