@@ -9,7 +9,7 @@ formula above — not any dense matrix the object was made from — defines the 
 
 The object also holds the CSC view of X (``colptr`` [F+1], and per entry its row and its CSR entry index, rows ascending
 within a column), built once at construction: x is data and never changes during a run.  ``Disentangle.project`` hands a
-CUDA ``SparseFeatures`` to dl_project_sparse_fwd / _bwd (ops.ProjectSparse); a CPU one goes through ``to_dense``.
+CUDA ``SparseFeatures`` to dl_project_sparse_fwd / _bwd (ops.Project); a CPU one goes through ``to_dense``.
 """
 from __future__ import annotations
 

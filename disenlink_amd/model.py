@@ -238,48 +238,52 @@ class Disentangle(nn.Module):
         ``Disentangle(projection="library")``, kept for timing comparisons — or for CPU tensors, which no product path
         serves (the CPU tests of the host logic and of the sharding choreography use it with the oracle as the backend);
         a CUDA tensor whose shape the kernels do not serve raises instead of falling back."""
-        fs = self.factors
         K, d = self.nfactor, self.nebed
-        if isinstance(x, SparseFeatures):
-            # features.py: scale * X + shift with X a CSR.  On the GPU layer 1 and dW1 are gathers (ops.ProjectSparse) and
-            # there is never a dense product; a CPU object takes the CPU branch below on to_dense() (host tests only)
+        sparse = isinstance(x, SparseFeatures)
+        if sparse:
+            # features.py: scale * X + shift with X a CSR.  On the GPU layer 1 and dW1 are gathers (dl_project_sparse_fwd / _bwd)
+            # and there is never a dense product; a CPU object takes the GEMM branch on to_dense() (host tests only)
             if not x.is_cuda:
                 return self.project(x.to_dense())
             if not ops.project_supported(d):
                 raise ops._lib.DisenlinkHipError(f"the sparse projection kernels serve factor widths d <= 128 (got d = {d})")
-            flat = self._stacked_params()
-            st = self._stacked
-            if flat is not None:
-                bufs = ((st[("mlp", "weight")], st[("mlp", "bias")], None, None) if self.single_layer else
-                        (st[("mlp1", "weight")], st[("mlp1", "bias")], st[("mlp2", "weight")], st[("mlp2", "bias")]))
-                return ops.ProjectSparse.apply(x, bufs, K, *flat)
-            if self.single_layer:
-                return ops.ProjectSparse.apply(x, None, K, torch.stack([f.mlp.weight for f in fs]),
-                                               torch.stack([f.mlp.bias for f in fs]), None, None)
-            return ops.ProjectSparse.apply(x, None, K, torch.stack([f.mlp1.weight for f in fs]),
-                                           torch.stack([f.mlp1.bias for f in fs]), torch.stack([f.mlp2.weight for f in fs]),
-                                           torch.stack([f.mlp2.bias for f in fs]))
-        if x.is_cuda and self.projection != "library" and not (x.dtype == torch.float32 and ops.project_supported(d)):
+        elif not x.is_cuda or self.projection == "library":
+            return self._project_gemm(x)
+        elif not (x.dtype == torch.float32 and ops.project_supported(d)):
             raise ops._lib.DisenlinkHipError(
                 f"the projection kernels serve fp32 features and factor widths d <= 128 (got {x.dtype}, d = {d}); "
                 "there is no eager fallback on the GPU — construct the module with projection=\"library\" to use the library GEMMs")
-        use_kernel = x.is_cuda and self.projection != "library"
-        if use_kernel:
-            flat = self._stacked_params()
-            if flat is not None:                                # zero-copy: the kernel reads the shared buffers
-                st = self._stacked
-                bufs = ((st[("mlp", "weight")], st[("mlp", "bias")], None, None) if self.single_layer else
-                        (st[("mlp1", "weight")], st[("mlp1", "bias")], st[("mlp2", "weight")], st[("mlp2", "bias")]))
-                from . import native
-                if native.project_ok(x, d, self.single_layer):   # the same kernels from a C++ autograd node (no Python in the backward)
-                    return native.project_stacked(x, bufs, flat)
-                return ops.ProjectStacked.apply(x, bufs, K, *flat)
-            # parameters were re-pointed by the caller: stack them (one copy per call)
-            if self.single_layer:
-                return ops.Project.apply(x, torch.stack([f.mlp.weight for f in fs]),
-                                         torch.stack([f.mlp.bias for f in fs]), None, None)
-            return ops.Project.apply(x, torch.stack([f.mlp1.weight for f in fs]), torch.stack([f.mlp1.bias for f in fs]),
-                                     torch.stack([f.mlp2.weight for f in fs]), torch.stack([f.mlp2.bias for f in fs]))
+        bufs, params = self._project_weights()
+        if bufs is not None and not sparse:
+            from . import native
+            if native.project_ok(x, d, self.single_layer):       # the same kernels from a C++ autograd node (no Python in the backward)
+                return native.project_stacked(x, bufs, params)
+        return ops.Project.apply(x, bufs, K, *params)
+
+    def _stacked_weights(self):
+        """(W1, b1, W2, b2) stacked from the K factors' LIVE Parameters, one copy each (W2 = b2 = None for the single layer)."""
+        fs = self.factors
+        if self.single_layer:
+            return torch.stack([f.mlp.weight for f in fs]), torch.stack([f.mlp.bias for f in fs]), None, None
+        return (torch.stack([f.mlp1.weight for f in fs]), torch.stack([f.mlp1.bias for f in fs]),
+                torch.stack([f.mlp2.weight for f in fs]), torch.stack([f.mlp2.bias for f in fs]))
+
+    def _project_weights(self):
+        """The weights of one projection call, as ops.Project takes them: (the shared [K, ...] buffers, the flat list of
+        per-factor Parameters) while every Parameter still aliases its place in the buffers — zero-copy: the kernel reads
+        the buffers — else (None, the four stacked tensors): the caller re-pointed a Parameter, one stacking copy per call."""
+        flat = self._stacked_params()
+        if flat is None:
+            return None, self._stacked_weights()
+        st = self._stacked
+        if self.single_layer:
+            return (st[("mlp", "weight")], st[("mlp", "bias")], None, None), flat
+        return (st[("mlp1", "weight")], st[("mlp1", "bias")], st[("mlp2", "weight")], st[("mlp2", "bias")]), flat
+
+    def _project_gemm(self, x):
+        """project() as library GEMMs (one wide GEMM + one K-batched GEMM), differentiated by autograd."""
+        fs = self.factors
+        K, d = self.nfactor, self.nebed
         if self.single_layer:
             W = torch.cat([f.mlp.weight for f in fs], dim=0)             # [K*d, F]
             b = torch.cat([f.mlp.bias for f in fs], dim=0)

@@ -87,14 +87,14 @@ def hot_path_pairs_loss(Z: torch.Tensor, graph: Graph, pairs: PairList, beta: fl
 def project_ok(x: torch.Tensor, d: int, single_layer: bool) -> bool:
     """Does the compiled projection node serve this call?  (two-layer form, fp32 rows of 16-byte-aligned length, a factor
     width the kernels are instantiated for; the Python operator pads / re-stacks everything else)"""
-    if not torch.is_tensor(x):                                      # a SparseFeatures: served by ops.ProjectSparse only
+    if not torch.is_tensor(x):                                      # a SparseFeatures: served by ops.Project only
         return False
     return load() and not single_layer and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] % 4 == 0 \
-        and d in (32, 64, 128) and os.environ.get("DL_PROJECT_BWD", "native") != "library"
+        and d in (32, 64, 128)
 
 
 def project_stacked(x: torch.Tensor, bufs, params) -> torch.Tensor:
-    """Z [N,K,d] = the K factor MLPs of x over the module's shared buffers (ops.ProjectStacked as a C++ autograd node):
+    """Z [N,K,d] = the K factor MLPs of x over the module's shared buffers (ops.Project on dense x as a C++ autograd node):
     bufs = (W1 [K,nhid,F], b1, W2 [K,d,nhid], b2), params = the 4 K per-factor Parameters that view them."""
     W1, b1, W2, b2 = bufs
     need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)

@@ -21,7 +21,7 @@ _HOST_STEP = _os.environ.get("DL_ADAM_HOST_STEP", "1") != "0"      # 0: always t
 
 def stacked_grad(ps, buf) -> torch.Tensor:
     """The K gradients of one parameter group as ONE [K, ...] tensor shaped like the group's shared buffer.  The
-    projection's backward hands out the K slices of a stacked gradient (ops.ProjectStacked): when the K .grad tensors
+    projection's backward hands out the K slices of a stacked gradient (ops.Project): when the K .grad tensors
     lie back to back in one storage — checked by address, since views made in a backward (grad mode off) carry no
     ``_base`` — the stacked tensor is a view over them (no copy); otherwise they are stacked (one copy)."""
     g0 = ps[0].grad

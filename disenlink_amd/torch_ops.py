@@ -223,9 +223,7 @@ project_fwd.register_autograd(_pj_backward, setup_context=_pj_setup)
 def forward_pairs(model, x: Tensor, graph: int, pairs: int):
     """(emb [N,K*d], prob [P]) of a two-layer ``Disentangle`` through the registered operators only — the function
     ``torch.compile`` traces end to end (``Disentangle(use_torch_ops=True).forward_pairs`` calls it)."""
-    fs = model.factors                                         # the K per-factor Parameters are the autograd leaves
-    Z = torch.ops.disenlink.project_fwd(x, torch.stack([f.mlp1.weight for f in fs]), torch.stack([f.mlp1.bias for f in fs]),
-                                        torch.stack([f.mlp2.weight for f in fs]), torch.stack([f.mlp2.bias for f in fs]))
+    Z = torch.ops.disenlink.project_fwd(x, *model._stacked_weights())     # the K per-factor Parameters are the autograd leaves
     H = torch.ops.disenlink.route_aggregate(Z, graph, float(model.beta), float(model.temperature))[0]
     prob = score_pairs(Z, H, pairs, float(model.temperature))
     return H.reshape(H.shape[0], -1), prob

@@ -1832,7 +1832,7 @@ def test_compiled_projection_adam_auc_and_bf16_hot_path_equal_the_python_operato
         st = m._stacked
         bufs = (st[("mlp1", "weight")], st[("mlp1", "bias")], st[("mlp2", "weight")], st[("mlp2", "bias")])
         assert native.project_ok(x, d, False)
-        Z = ops.ProjectStacked.apply(x, bufs, K, *flat) if which == "python" else native.project_stacked(x, bufs, flat)
+        Z = ops.Project.apply(x, bufs, K, *flat) if which == "python" else native.project_stacked(x, bufs, flat)
         Z.backward(gZ)
         grads = [p.grad for p in flat]
         assert flat_view([g for g in grads]) is not None             # back to back: one all-reduce, no stacking copy in Adam
