@@ -35,6 +35,21 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+def table_code(dtype) -> int:
+    """The dl_dtype code of a node table's storage type: the ONE rule (fp32 or bf16, nothing else)."""
+    if dtype == torch.float32:
+        return _lib.DL_F32
+    if dtype == torch.bfloat16:
+        return _lib.DL_BF16
+    raise TypeError(f"node tables must be float32 or bfloat16, got {dtype}")
+
+
+def _tab(t: torch.Tensor):
+    """A node table (Z or H): fp32 or bf16 storage -> (contiguous tensor, dl_dtype code)."""
+    code = table_code(t.dtype)
+    return t.contiguous(), code
+
+
 def _nkd(Z: torch.Tensor):
     if Z.dim() != 3:
         raise ValueError("Z/H must be [N, K, d]")

@@ -341,8 +341,7 @@ class HipBackend:
         """Whether dl_route_fwd walks only the entries of the graph's ROUTING plan (the tuned kernels do; the generic
         path — dl_set_force_generic or a (K, d) without a tuned instantiation — routes every entry whatever the plan
         says, so per-peer passes under an asynchronous gather would read blocks that have not arrived)."""
-        dt = self.ops._lib.DL_F32 if table_dtype == torch.float32 else self.ops._lib.DL_BF16
-        return self.ops.score_terms_available(K, d, dt)
+        return self.ops.score_terms_available(K, d, self.ops.table_code(table_dtype))
 
     def aggregate_fwd(self, g, Z, beta, p, a, s, H_out):
         self.ops.aggregate_fwd(g, Z, beta, p, a, s, H_out=H_out)
@@ -354,8 +353,7 @@ class HipBackend:
         self.ops.score_pairs_bwd(Z, H, inc, t, prob, g_prob, dZ_out=dZ_out, dH_out=dH_out)
 
     def score_pairs_train_supported(self, inc, K, d, table_dtype) -> bool:
-        dt = self.ops._lib.DL_F32 if table_dtype == torch.float32 else self.ops._lib.DL_BF16
-        return self.ops.score_pairs_train_supported(inc, K, d, dt)
+        return self.ops.score_pairs_train_supported(inc, K, d, self.ops.table_code(table_dtype))
 
     def score_pairs_train(self, Z, H, inc, t, label, weight):
         """-> prob [P total] (entries of the pairs touching the plan's rows), dZ, dH [n_pad,K,d] (the plan's rows)"""
@@ -371,25 +369,11 @@ class HipBackend:
 
     def pair_bce_grad(self, prob, label, weight):
         """-> (sum_q weight BCE(prob, label), d that / d prob) from ONE kernel (dl_pair_bce)"""
-        lib = self.ops._lib.load()
-        loss = torch.empty(1, dtype=torch.float32, device=prob.device)
-        g = torch.empty_like(prob)
-        ws = self.ops._ws_bce(prob.device)
-        self.ops._lib.check(lib.dl_pair_bce(prob.data_ptr(), label.data_ptr(), weight.data_ptr(), prob.numel(),
-                                            loss.data_ptr(), g.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            torch.cuda.current_stream().cuda_stream), "dl_pair_bce")
-        return loss[0], g
+        return self.ops.pair_bce(prob, label, weight)
 
     def pair_bce_sum(self, prob, label, weight):
         """sum_q weight BCE(prob, label) with the reference's clamps (no autograd: the gradient came from the scorer)"""
-        lib = self.ops._lib.load()
-        loss = torch.empty(1, dtype=torch.float32, device=prob.device)
-        g = torch.empty_like(prob)
-        ws = self.ops._ws.get(8192, prob.device)
-        self.ops._lib.check(lib.dl_pair_bce(prob.data_ptr(), label.data_ptr(), weight.data_ptr(), prob.numel(),
-                                            loss.data_ptr(), g.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            torch.cuda.current_stream().cuda_stream), "dl_pair_bce")
-        return loss[0]
+        return self.ops.pair_bce(prob, label, weight)[0]
 
     def bwd_phase1(self, g, Z, beta, p, a, s, dH, ds_out):
         return self.ops.route_aggregate_bwd_phase1(g, Z, beta, p, a, s, dH, ds_out)

@@ -157,6 +157,18 @@ def by_handle(handle: int, kind):
     return obj if isinstance(obj, kind) else None
 
 
+class _PlanOwner:
+    """What Graph and PairList share as owners of a plan the kernels walk (``c_plan()``): the scratch that plan needs."""
+
+    def workspace_bytes(self, K: int, d: int) -> int:
+        """Bytes of workspace the kernels over this object's plan need at (K, d): dl_workspace_bytes, asked once per
+        (K, d) and remembered here — the plan of an object never changes."""
+        need = self._ws_need.get((K, d))
+        if need is None:
+            need = self._ws_need[(K, d)] = int(_lib.load().dl_workspace_bytes(self.c_plan(), K, d))
+        return need
+
+
 @dataclass
 class CsrPlan:
     """Rows [row_offset, row_offset + n_rows) of a CSR over n_total nodes + its segment plan.
@@ -364,13 +376,14 @@ class CsrPlan:
 
 
 @dataclass
-class Graph:
+class Graph(_PlanOwner):
     plan: CsrPlan
     rev: torch.Tensor | None = None      # reverse-edge permutation (unsharded builds only)
     route: CsrPlan | None = None         # plan walked by the routing kernel: XCD-sliced, and (unsharded builds)
     route_mirror: bool = False           # covering col >= row only — routing is symmetric, so each undirected
                                          # edge is computed once and written to both entries through rev
     _struct: _lib.DlGraph | None = field(default=None, repr=False)
+    _ws_need: dict = field(default_factory=dict, repr=False)          # (K, d) -> bytes: workspace_bytes
 
     def __post_init__(self):
         _assign_handle(self)
@@ -713,7 +726,7 @@ class HubPlan:
 
 
 @dataclass
-class PairList:
+class PairList(_PlanOwner):
     """Scored pairs ``(pu[q], pv[q])`` with the two CSR views the kernels walk:
     ``by_u`` — every pair once, in the row of its first endpoint (forward scorer), and
     ``inc``  — every pair twice, once per endpoint (backward; rows = nodes ``[row_offset, +n_rows)``).
@@ -739,6 +752,7 @@ class PairList:
     _yw: torch.Tensor | None = field(default=None, repr=False)      # per-entry (label, signed weight): bind_labels
     _yw_key: tuple | None = field(default=None, repr=False)
     _yw_seen: tuple | None = field(default=None, repr=False)
+    _ws_need: dict = field(default_factory=dict, repr=False)          # (K, d) -> bytes: workspace_bytes
 
     def __post_init__(self):
         _assign_handle(self)

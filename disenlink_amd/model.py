@@ -346,6 +346,10 @@ class Disentangle(nn.Module):
             raise ValueError(f"{what}: link_pred_backward=\"dense\" differentiates every entry of link_pred and needs no "
                              "declaration of where the loss is taken")
 
+    def _graph_of(self, adj) -> Graph:
+        """``adj`` as the methods below take it: a prebuilt Graph, or the dense adj_sym."""
+        return adj if isinstance(adj, Graph) else self._graph_for(adj)
+
     def _graph_for(self, adj: torch.Tensor) -> Graph:
         """CSR + plans of a dense adjacency, built once per adjacency tensor: keyed on the tensor OBJECT (weak
         reference) and its version counter — an address can be reused by a different tensor, an object cannot."""
@@ -359,7 +363,7 @@ class Disentangle(nn.Module):
     def forward(self, x, adj):
         """(emb [N,K*d], link_pred [N,N]) exactly as model.py:105-114; ``adj`` is the dense adj_sym
         (or a prebuilt ``Graph``)."""
-        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        graph = self._graph_of(adj)
         Z = self.project(x)
         H = ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
         if getattr(self, "link_pred_backward", "plan") == "dense":
@@ -377,7 +381,7 @@ class Disentangle(nn.Module):
         list; metrics.pair_bce_weights): the training step's scorer runs forward and backward in one pass
         (ops.HotPathPairsLoss).  Falls back to forward_pairs + the fused loss where no tuned kernel exists."""
         Z = self.project(x)
-        dt = ops._lib.DL_F32 if self.table_dtype == torch.float32 else ops._lib.DL_BF16
+        dt = ops.table_code(self.table_dtype)
         one_pass = ops.one_pass_scorer_wanted(self.table_dtype, Z.shape[0], Z.shape[1], Z.shape[2])     # the rule and its numbers: there
         if one_pass and ops.score_pairs_train_supported(pairs, Z.shape[1], Z.shape[2], dt):
             if Z.dtype == torch.float32 and graph.n_rows == graph.n_nodes:
@@ -408,18 +412,17 @@ class Disentangle(nn.Module):
     # ------------------------------------------------------------------ ranking (inference only)
     def _rank_tables(self, x, adj, table_dtype=None):
         """Z and H of forward(x, adj) — the same projection and routing / aggregation, under no_grad.  ``table_dtype``:
-        None = fp32 tables; torch.bfloat16 = the tables the training step of a bf16 module gathers from (the sequence of
-        ops.HotPathPairs.forward): Z rounded to bf16, H routed and aggregated from THAT Z and stored as bf16."""
-        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        None = fp32 tables; torch.bfloat16 = the tables the training step of a bf16 module gathers from (ops.step_tables,
+        which ops.HotPathPairs.forward calls too): Z rounded to bf16, H routed and aggregated from THAT Z and stored as bf16."""
+        graph = self._graph_of(adj)
         with torch.no_grad():
             Z = self.project(x)
             if table_dtype is None or table_dtype is torch.float32:
                 return Z, ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
             if table_dtype is not torch.bfloat16:
                 raise TypeError(f"table_dtype must be None, torch.float32 or torch.bfloat16, got {table_dtype!r}")
-            Zt = ops._f32c(Z).to(torch.bfloat16)
-            p, a, s = ops.route_fwd(graph, Zt, float(self.temperature))
-            return Zt, ops.aggregate_fwd(graph, Zt, float(self.beta), p, a, s)
+            Zt, _p, _a, _s, H = ops.step_tables(graph, Z, float(self.beta), float(self.temperature), table_dtype)
+            return Zt, H
 
     @staticmethod
     def _scan_dtype(table_dtype):
@@ -466,7 +469,7 @@ class Disentangle(nn.Module):
         symmetric ops.NodeFilter, a rule on node groups that pairs must pass as well.  Graphs of more than 46,340 nodes
         (or any graph, with ``block_nodes``: rows per block, a multiple of 128) are scanned by blocks
         (ops.score_mine_blocks): the same list, equal logits ordered by the 64-bit src * N + dst."""
-        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        graph = self._graph_of(adj)
         Z, H = self._rank_tables(x, graph, table_dtype)
         floor = self._logit_floor(min_prob)
         known = graph if exclude is None else exclude
@@ -487,7 +490,7 @@ class Disentangle(nn.Module):
         ``top_missing_links`` (0.5 -> 0.0).  ``node_filter``: a symmetric ops.NodeFilter that pairs must pass as well.
         Graphs of more than 46,340 nodes (or any graph, with ``block_nodes``: rows per block, a multiple of 128) are
         scanned by blocks (ops.score_links_blocks): the same CSR."""
-        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        graph = self._graph_of(adj)
         Z, H = self._rank_tables(x, graph, table_dtype)
         floor = self._logit_floor(float(min_prob))
         known = graph if exclude is None else exclude
@@ -507,7 +510,7 @@ class Disentangle(nn.Module):
         exactly min(m, eligible pairs) links; tied logits across the cut are taken by ascending src * N + dst.  ``exclude``,
         ``min_prob`` and ``node_filter`` as in ``top_missing_links`` (``exclude`` may also be a prepared
         ``ops.pair_exclusion``); ``min_prob`` and the budget both hold.  N <= 46,340."""
-        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        graph = self._graph_of(adj)
         Z, H = self._rank_tables(x, graph, table_dtype)
         floor = self._logit_floor(min_prob)
         with torch.no_grad():
@@ -530,7 +533,7 @@ class Disentangle(nn.Module):
         them into the AUC against every non-edge, MRR and recall@M).  ``exclude``: the pairs that are no candidates, as
         in ``top_missing_links``; None = the edges of ``adj``.  ``node_filter``: a symmetric ops.NodeFilter that candidates
         must pass as well.  A target is ranked whether or not it is excluded or allowed."""
-        graph = adj if isinstance(adj, Graph) else self._graph_for(adj)
+        graph = self._graph_of(adj)
         Z, H = self._rank_tables(x, graph, table_dtype)
         with torch.no_grad():
             return PairRanks(*ops.score_pair_ranks(Z, H, float(self.temperature), src, dst, graph if exclude is None else exclude,

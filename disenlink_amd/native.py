@@ -65,18 +65,14 @@ def hot_path_pairs_loss(Z: torch.Tensor, graph: Graph, pairs: PairList, beta: fl
     if not load():
         raise _lib.DisenlinkHipError("libdisenlink_torch.so is not built (python -m disenlink_amd.build)")
     N, K, d = Z.shape
-    P = int(label.numel())
-    if P != pairs.n_pairs:
-        raise ValueError("label / weight must cover the pair list")
     graph.c_struct()
-    pairs.bind_labels(label, weight, P)                             # per-entry labels once the same tensors come back (graph.py)
-    pairs.c_struct(P)
-    ws_g = ops._workspace(graph.c_plan(), Z.device, K, d)
-    ws_p = ops._workspace(pairs.c_plan(), Z.device, K, d)
+    ops._train_pairs(pairs, label, weight)                          # the operands of ops.score_pairs_train, set up the same way
+    ws_g = ops._workspace(graph, Z.device, K, d)
+    ws_p = ops._workspace(pairs, Z.device, K, d)
     ws_b = ops._ws_bce(Z.device)
     H, prob, loss = torch.ops.disenlink_native.hot_path_pairs_loss(Z, C.addressof(graph._struct), C.addressof(pairs._struct),
                                                                    graph.n_edges, float(beta), float(t), label, weight, ws_g, ws_p, ws_b,
-                                                                   1 if table_dtype == torch.bfloat16 else 0)
+                                                                   ops.table_code(table_dtype))
     # the node's backward dereferences the two structs (and the device arrays they point to): they live exactly as long as
     # the node does, whatever the caller does with its Graph / PairList in between (a per-epoch resampled pair list)
     if loss.grad_fn is not None:

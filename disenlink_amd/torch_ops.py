@@ -144,8 +144,7 @@ def score_pairs_terms(Z: Tensor, H: Tensor, pairs: int, t: float) -> tuple[Tenso
 @score_pairs_terms.register_fake
 def _(Z, H, pairs, t):
     P = _p(pairs).n_pairs
-    dt = _lib.DL_BF16 if Z.dtype == torch.bfloat16 else _lib.DL_F32   # the same rule as the real operator (ops.score_pairs_fwd)
-    terms = ops.score_terms_available(Z.shape[1], Z.shape[2], dt)
+    terms = ops.score_terms_available(Z.shape[1], Z.shape[2], ops.table_code(Z.dtype))   # the real operator's rule
     return Z.new_empty(P, dtype=torch.float32), Z.new_empty((2, P, Z.shape[1]) if terms else (0,), dtype=torch.float32)
 
 
