@@ -220,6 +220,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
 // from LDS, and that the partner registers a slot uses are fixed by the step's shape (NV = gathered rows: slot e uses
 // set e * NV / 4).  The value of a slot never meets another slot's, and the reduction adds the same 16 lanes in the same
 // order whichever slot a value sits in: every pair gets the bits of the kernel above.
+// Like that kernel's TAIL, dead-row handling is compiled into the LAST step of list A and of list B only: the plan holds dead
+// rows nowhere else (disenlink_hip.h; graph.HubPlan.check refuses a plan that does before it is bound), so a full step has no
+// sign test and no zero fill of gather registers, and a wave requests the plan words of its next step while it works on
+// the current one.
 // The base name is that kernel's on purpose: the per-phase accounting of the benchmark matches kernels by base name.
 namespace hub {
 constexpr int WAVES = 8, THREADS = WAVES * DL_WAVE;
@@ -231,6 +235,11 @@ __device__ __forceinline__ dl_vi4 plan_words(const int32_t* a, int idx) {
     const auto* g = (const __attribute__((address_space(1))) int32_t*)a;
     return reinterpret_cast<const __attribute__((address_space(4))) dl_vi4*>((const __attribute__((address_space(4))) int32_t*)g)[idx];
 }
+
+// The 16 plan words of one step: partner rows, u_local, pair id and second pair id of its four slots.
+struct StepWords {
+    dl_vi4 v, u, q, p;
+};
 
 template <int K, int D, bool T1, bool COEF, bool FOLD>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void score_fwd_wave_kernel(
@@ -247,6 +256,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int wave = wave_index(), lane = lane_id();
     const int i = lane & 15, r = lane >> 4;
     const int blk = h.item_block[it];
+    // the item's boundaries are asked for with its block, ahead of the staging loads — not behind the barrier
+    const int s_a = h.item_step[4 * it], s_b = h.item_step[4 * it + 1], s_c = h.item_step[4 * it + 2],
+              s_end = h.item_step[4 * it + 3];
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
         const int ul = 2 * wave + rr;
@@ -263,21 +275,27 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
         }
     }
     __syncthreads();                                                 // the only one: nothing below waits for another wave
-    const int s_a = h.item_step[4 * it], s_b = h.item_step[4 * it + 1], s_c = h.item_step[4 * it + 2],
-              s_end = h.item_step[4 * it + 3];
-    auto do_step = [&](const int step, auto shape) {
-        constexpr int NV = decltype(shape)::value;                   // gathered partner rows: 4 (A), 2 (B), 1 (C)
+    // a step's 16 words through the scalar cache (the plan is read-only for the whole launch)
+    auto fetch = [&](const int step) {
         const int s = __builtin_amdgcn_readfirstlane(step);
-        // the step's 16 words through the scalar cache (the plan is read-only for the whole launch)
-        const dl_vi4 v4 = plan_words(h.step_v, s), u4 = plan_words(h.step_u, s), q4 = plan_words(h.step_q, s);
-        dl_vi4 p4 = {-1, -1, -1, -1};
-        if constexpr (FOLD) p4 = plan_words(h.step_q2, s);
-        const int sv[4] = {v4.x, v4.y, v4.z, v4.w}, su[4] = {u4.x, u4.y, u4.z, u4.w}, sq[4] = {q4.x, q4.y, q4.z, q4.w},
-                  sq2[4] = {p4.x, p4.y, p4.z, p4.w};
+        StepWords w;
+        w.v = plan_words(h.step_v, s), w.u = plan_words(h.step_u, s), w.q = plan_words(h.step_q, s);
+        w.p = dl_vi4{-1, -1, -1, -1};
+        if constexpr (FOLD) w.p = plan_words(h.step_q2, s);
+        return w;
+    };
+    // LAST: the step may hold dead partner rows.  Only the last step of a list does (disenlink_hip.h); every other step
+    // gathers its NV rows without a test and without the zero fill of a dead row's registers, as the wave-per-entry kernel
+    // does outside its TAIL step.
+    auto do_step = [&](const StepWords& w, auto shape, auto last) {
+        constexpr int NV = decltype(shape)::value;                   // gathered partner rows: 4 (A), 2 (B), 1 (C)
+        constexpr bool LAST = decltype(last)::value;
+        const int sv[4] = {w.v.x, w.v.y, w.v.z, w.v.w}, su[4] = {w.u.x, w.u.y, w.u.z, w.u.w}, sq[4] = {w.q.x, w.q.y, w.q.z, w.q.w},
+                  sq2[4] = {w.p.x, w.p.y, w.p.z, w.p.w};
         float4 zv[NV][NJ], hv[NV][NJ];
 #pragma unroll
         for (int n = 0; n < NV; ++n) {
-            if (NV == 1 || sv[n] >= 0) {                             // wave-uniform; a C step has no dead row
+            if (!LAST || sv[n] >= 0) {                               // wave-uniform
                 const size_t v = (size_t)(unsigned)sv[n];
                 const auto* zr = uniform_row<dl_vf4>(Z, v * ROW * sizeof(float));
                 const auto* hr = uniform_row<dl_vf4>(H, v * ROW * sizeof(float));
@@ -333,11 +351,28 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
             }
         }
     };
+    using FULL = std::false_type;
+    using LAST = std::true_type;
+    constexpr std::integral_constant<int, 4> SHAPE_A{};
+    constexpr std::integral_constant<int, 2> SHAPE_B{};
+    constexpr std::integral_constant<int, 1> SHAPE_C{};
     // step number n of the item (n = wave, wave + 8, ...) lies in list A, B or C by its place in [s_a, s_end)
     int s = s_a + wave;
-    for (; s < s_b; s += WAVES) do_step(s, std::integral_constant<int, 4>{});
-    for (; s < s_c; s += WAVES) do_step(s, std::integral_constant<int, 2>{});
-    for (; s < s_end; s += WAVES) do_step(s, std::integral_constant<int, 1>{});
+    // The words of the wave's NEXT step (s + WAVES, whichever list it lies in) are requested at the top of the current one,
+    // into a second set of SGPRs and never past the item's last step: a step starts from words that are already there
+    // instead of behind a scalar-cache round trip at the head of its chain.
+    StepWords nxt = {};
+    if (s < s_end) nxt = fetch(s);
+    auto take = [&](const int step) {
+        const StepWords w = nxt;
+        if (step + WAVES < s_end) nxt = fetch(step + WAVES);
+        return w;
+    };
+    for (; s < s_b - 1; s += WAVES) do_step(take(s), SHAPE_A, FULL{});
+    if (s == s_b - 1) do_step(take(s), SHAPE_A, LAST{}), s += WAVES;
+    for (; s < s_c - 1; s += WAVES) do_step(take(s), SHAPE_B, FULL{});
+    if (s == s_c - 1) do_step(take(s), SHAPE_B, LAST{}), s += WAVES;
+    for (; s < s_end; s += WAVES) do_step(take(s), SHAPE_C, FULL{});        // a C step has no dead row
 }
 }  // namespace hub
 

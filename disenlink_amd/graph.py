@@ -714,8 +714,34 @@ class HubPlan:
                        _i32(item_block), _i32(item_slice), _i32(item_step_s), _i32(step_v), _i32(step_u), _i32(step_q),
                        None if step_q2 is None else _i32(step_q2), E, rest, rest_pair, rest_pair2)
 
+    def check(self) -> None:
+        """Refuse a plan the kernel would fault on.  hub::score_fwd_wave_kernel gathers the partner rows of every step but
+        the last of an item's A list and B list without looking at them: a dead partner row (-1) anywhere else, or in
+        front of a live one, is a read outside the tables.  Run once, when the plan is bound (c_value)."""
+        if self.n_items == 0:
+            return
+        dev = self.step_v.device
+        st = self.item_step.long()
+        lens = torch.stack([st[:, 1] - st[:, 0], st[:, 2] - st[:, 1], st[:, 3] - st[:, 2]], dim=1).reshape(-1)
+        ends = torch.cumsum(lens, 0)
+        ok = bool((lens >= 0).all()) and int(ends[-1]) == self.n_steps and bool((st[1:, 0] == st[:-1, 3]).all()) \
+            and int(st[0, 0]) == 0
+        if ok:
+            nv = torch.repeat_interleave(torch.tensor([4, 2, 1], device=dev).repeat(self.n_items), lens)
+            last = torch.zeros(self.n_steps, dtype=torch.bool, device=dev)
+            last[(ends - 1)[lens > 0]] = True
+            used = torch.arange(4, device=dev)[None, :] < nv[:, None]            # the partner rows a step of this shape gathers
+            live = (self.step_v >= 0) & used
+            full = ~last | (nv == 1)                                            # a C step is never short
+            ok = not bool(((used & ~live)[full]).any()) and bool(live[:, 0].all()) \
+                and not bool((live[:, 1:] & ~live[:, :-1]).any())
+        if not ok:
+            raise ValueError("hub plan: dead partner rows may only close the last step of an item's A list and B list "
+                             "(dl_pair_hub, disenlink_hip.h)")
+
     def c_value(self) -> _lib.DlPairHub:
         if self._struct is None:
+            self.check()
             ptr = lambda t: None if t is None else t.data_ptr()
             self._struct = _lib.DlPairHub(
                 self.n_blocks, ptr(self.block_row), self.n_items, self.n_slices, self.slice_max_item, ptr(self.slice_item0),

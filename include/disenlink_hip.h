@@ -147,7 +147,8 @@ typedef struct dl_pair_incidence {
  *   shape A: four gathered partner rows, slot e scores against row e;
  *   shape B: two gathered rows, slots 0,1 against the first and 2,3 against the second;
  *   shape C: one gathered row, all four slots against it.
- * A dead slot has pair id -1, a dead partner row -1; only the last step of a list holds any.  Steps are stored item by
+ * A dead slot has pair id -1, a dead partner row -1; only the last step of a list holds any, behind its live ones — the
+ * kernel relies on it: it gathers the partner rows of every other step without looking at them.  Steps are stored item by
  * item as [A steps | B steps | C steps], item_step = the four boundaries.  Items are stored slice-major like the
  * positions of a dl_csr_plan: workgroup b serves slice stream b % n_slices.  Every entry of the list is a live slot of
  * exactly one step or an entry of `rest`, a plan of the usual form over the rows that are no hub rows.
