@@ -117,6 +117,10 @@ EXPORTS = {
     "dl_score_allpairs_bwd_dense_supported": (_i, [_i, _i]),
     "dl_score_allpairs_bwd_dense_workspace_bytes": (_z, [_i, _i, _i]),
     "dl_score_allpairs_bwd_dense": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_score_recon_supported": (_i, [_i, _i]),
+    "dl_score_recon_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "dl_score_recon_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dl_score_recon": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _P, _f, _f, _i, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_topk_supported": (_i, [_i, _i]),
     "dl_score_mine_supported": (_i, [_i, _i]),
     "dl_score_mine_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
@@ -288,6 +292,17 @@ def score_allpairs_bwd_dense_form(N: int, K: int, d: int) -> dict:
     out = (C.c_int * len(SCORE_ALLPAIRS_BWD_DENSE_FORM))()
     check(load().dl_score_allpairs_bwd_dense_form(N, K, d, out), "dl_score_allpairs_bwd_dense_form")
     return dict(zip(SCORE_ALLPAIRS_BWD_DENSE_FORM, out))
+
+
+SCORE_RECON_FORM = ("Np", "strips", "block_rows", "nslice")
+
+
+def score_recon_form(N: int, K: int, d: int, block_rows: int = 0) -> dict:
+    """The strips of dl_score_recon for this problem (``block_rows`` = 0: the default height) and the slice count of its
+    backward, which is the dense backward's for the whole N (dl_score_recon_form)."""
+    out = (C.c_int * len(SCORE_RECON_FORM))()
+    check(load().dl_score_recon_form(N, K, d, block_rows, out), "dl_score_recon_form")
+    return dict(zip(SCORE_RECON_FORM, out))
 
 
 def score_topk_form(N: int, K: int, d: int, Q: int, k: int) -> dict:

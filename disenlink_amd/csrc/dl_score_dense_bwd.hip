@@ -22,6 +22,7 @@
 #include <type_traits>
 #include "dl_common.h"
 #include "dl_kernels.h"
+#include "dl_scan.h"
 #include "dl_tiles.h"
 
 namespace dl {
@@ -112,15 +113,18 @@ struct BwdArgs {
     const __bf16 *zp, *hp;     // row planes (split_rows): per factor plane_array_elems(N, d, 32) elements
     const __bf16 *zT, *hT;     // transposed planes (split_cols_kernel), the same size per factor
     size_t batch;
-    const float* ghat;         // [Np][Np]
+    const float* ghat;         // [Np][Np], or a strip of it: the rows of the u tiles from ut0 on
     int N, Np, K, d;
     float t;
     float *dZ, *dH;            // slice s writes at + s * slice_stride
     int nslice;
     size_t slice_stride;
+    int ut0;                   // STRIP: first u tile of the launch
 };
 
-template <int NCB>             // 32-column chunks of the padded factor width
+// NCB: 32-column chunks of the padded factor width.  STRIP (dl_score_recon.hip): the launch covers the u tiles from ut0 on
+// and ghat holds their rows only; everything a workgroup computes for its u tile is the same.
+template <int NCB, bool STRIP = false>
 __global__ __launch_bounds__(BTHR) void score_dense_bwd_kernel(BwdArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(BTHR) void score_dense_bwd_kernel(BwdArgs A) {
     constexpr int nd = NCB, steps = 2 * nd, dp = 32 * NCB;
     const int nvt = A.Np / TT;
     const int slice = blockIdx.x % A.nslice, rest = blockIdx.x / A.nslice;
-    const int k = rest % A.K, ut = rest / A.K;
+    const int k = rest % A.K, ut = STRIP ? A.ut0 + rest / A.K : rest / A.K;
     const int vt_beg = (int)((long long)slice * nvt / A.nslice), vt_end = (int)((long long)(slice + 1) * nvt / A.nslice);
     const int u0 = ut * TT;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -176,7 +180,7 @@ __global__ __launch_bounds__(BTHR) void score_dense_bwd_kernel(BwdArgs A) {
                         stash(s + 1);
                         fetch(min(s + 2, steps - 1));           // unconditional: see TileStage (dl_tiles.h)
                     } else {                                    // the staging registers are free: G^ arrives under the last products
-                        const float* gp = A.ghat + (size_t)(u0 + wu * 32 + 4 * half) * A.Np + (size_t)vt * TT + wv * 64 + li;
+                        const float* gp = A.ghat + (size_t)((STRIP ? u0 - A.ut0 * TT : u0) + wu * 32 + 4 * half) * A.Np + (size_t)vt * TT + wv * 64 + li;
 #pragma unroll
                         for (int bb = 0; bb < 2; ++bb)
 #pragma unroll
@@ -322,39 +326,46 @@ void dense_bwd_form(int N, int K, int d, int* out) {
     out[4] = hi;
 }
 
-int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d, float t, const float* prob, const float* g_prob,
-                             float* dZ, float* dH, void* ws, hipStream_t st) {
+// The planes of Z_k^T and H_k^T (stage 2) into zT / hT, K * plane_array_elems(N, d, 32) elements each
+void dense_bwd_cols(const float* Z, const float* H, int N, int K, int d, __bf16* zT, __bf16* hT, hipStream_t st) {
     using namespace dense_bwd;
-    static unsigned long long lds_done[4] = {0, 0, 0, 0};
-    const Layout L = layout(N, K, d);
-    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    float* ghat = (float*)(base + L.ghat);
-    __bf16 *zp = (__bf16*)(base + L.zp), *hp = (__bf16*)(base + L.hp), *zT = (__bf16*)(base + L.zT), *hT = (__bf16*)(base + L.hT);
-    float* part = (float*)(base + L.part);
-    const int nt = L.Np / TT, ncb = L.dp / SDC;
+    const int nt = (int)round_up(N, TT) / TT, dp = (int)round_up(d, SDC);
+    hipLaunchKernelGGL(split_cols_kernel, dim3((unsigned)(nt * (dp / SDC)), (unsigned)K, 2u), dim3(256), 0, st,
+                       ColsJob{Z, H, zT, hT, N, K, d, dp, plane_array_elems(N, d, SDC)});
+}
+
+int dense_bwd_nslice(int N, int K) { return dense_bwd::slices(N, K); }
+
+// floats of the slices' partial sums (0 where the v range is not cut)
+size_t dense_bwd_part_floats(int N, int K, int d) {
+    const int ns = dense_bwd::slices(N, K);
+    return ns > 1 ? (size_t)ns * 2 * N * K * d : 0;
+}
+
+// Stage 3 over the u tiles [ut0, ut0 + n_ut): ghat = the Np-wide rows of G^ from row ut0 * 128 on (`strip`), or the whole
+// matrix (ut0 = 0, n_ut = Np / 128: the dense entry's instantiation).  The v range is cut into dense_bwd_nslice(N, K) slices whatever the u range; with more than
+// one, the rows of the launch go to `part` (dense_bwd_part_floats) and dense_bwd_combine sums them once every row is there.
+void dense_bwd_tiles(const __bf16* zp, const __bf16* hp, const __bf16* zT, const __bf16* hT, const float* ghat, int N, int K, int d,
+                     float t, int ut0, int n_ut, bool strip, float* part, float* dZ, float* dH, hipStream_t st) {
+    using namespace dense_bwd;
+    const int ncb = (int)round_up(d, SDC) / SDC, nslice = slices(N, K);
     const size_t n = (size_t)N * K * d;
-
-    hipLaunchKernelGGL(ghat_kernel, dim3((unsigned)(L.Np / 64), (unsigned)(L.Np / 64)), dim3(256), 0, st, prob, g_prob, N, L.Np, ghat);
-    project::split_rows(Z, K, N, d, K * d, (size_t)d, zp, st);
-    project::split_rows(H, K, N, d, K * d, (size_t)d, hp, st);
-    hipLaunchKernelGGL(split_cols_kernel, dim3((unsigned)(nt * ncb), (unsigned)K, 2u), dim3(256), 0, st,
-                       ColsJob{Z, H, zT, hT, N, K, d, L.dp, L.batch});
-
     BwdArgs A;
     A.zp = zp; A.hp = hp; A.zT = zT; A.hT = hT;
-    A.batch = L.batch;
+    A.batch = plane_array_elems(N, d, SDC);
     A.ghat = ghat;
-    A.N = N; A.Np = L.Np; A.K = K; A.d = d;
+    A.N = N; A.Np = (int)round_up(N, TT); A.K = K; A.d = d;
+    A.ut0 = ut0;
     A.t = t;
-    A.nslice = L.nslice;
-    A.dZ = L.nslice > 1 ? part : dZ;
-    A.dH = L.nslice > 1 ? part + n : dH;
-    A.slice_stride = L.nslice > 1 ? 2 * n : 0;
-    const dim3 grid((unsigned)((size_t)nt * K * L.nslice));
+    A.nslice = nslice;
+    A.dZ = nslice > 1 ? part : dZ;
+    A.dH = nslice > 1 ? part + n : dH;
+    A.slice_stride = nslice > 1 ? 2 * n : 0;
+    const unsigned grid = (unsigned)((size_t)n_ut * K * nslice);
 #define DL_LAUNCH_BWD(NCB)                                                                                               \
     do {                                                                                                                 \
-        project::ensure_dynamic_lds(reinterpret_cast<const void*>(&score_dense_bwd_kernel<NCB>), LDS_BYTES, lds_done[NCB - 1]); \
-        hipLaunchKernelGGL(score_dense_bwd_kernel<NCB>, grid, dim3(BTHR), LDS_BYTES, st, A);                             \
+        if (strip) scan::launch_lds<score_dense_bwd_kernel<NCB, true>>(grid, BTHR, LDS_BYTES, st, A);                    \
+        else scan::launch_lds<score_dense_bwd_kernel<NCB>>(grid, BTHR, LDS_BYTES, st, A);                                \
     } while (0)
     switch (ncb) {
         case 1: DL_LAUNCH_BWD(1); break;
@@ -363,8 +374,31 @@ int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d
         default: DL_LAUNCH_BWD(4); break;
     }
 #undef DL_LAUNCH_BWD
-    if (L.nslice > 1)
-        hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, st, part, n, L.nslice, dZ, dH);
+}
+
+void dense_bwd_combine(const float* part, int N, int K, int d, float* dZ, float* dH, hipStream_t st) {
+    using namespace dense_bwd;
+    const int nslice = slices(N, K);
+    const size_t n = (size_t)N * K * d;
+    if (nslice > 1)
+        hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, st, part, n, nslice, dZ, dH);
+}
+
+int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d, float t, const float* prob, const float* g_prob,
+                             float* dZ, float* dH, void* ws, hipStream_t st) {
+    using namespace dense_bwd;
+    const Layout L = layout(N, K, d);
+    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    float* ghat = (float*)(base + L.ghat);
+    __bf16 *zp = (__bf16*)(base + L.zp), *hp = (__bf16*)(base + L.hp), *zT = (__bf16*)(base + L.zT), *hT = (__bf16*)(base + L.hT);
+    float* part = (float*)(base + L.part);
+
+    hipLaunchKernelGGL(ghat_kernel, dim3((unsigned)(L.Np / 64), (unsigned)(L.Np / 64)), dim3(256), 0, st, prob, g_prob, N, L.Np, ghat);
+    project::split_rows(Z, K, N, d, K * d, (size_t)d, zp, st);
+    project::split_rows(H, K, N, d, K * d, (size_t)d, hp, st);
+    dense_bwd_cols(Z, H, N, K, d, zT, hT, st);
+    dense_bwd_tiles(zp, hp, zT, hT, ghat, N, K, d, t, 0, L.Np / TT, false, part, dZ, dH, st);
+    dense_bwd_combine(part, N, K, d, dZ, dH, st);
     return check_launch("score_allpairs_bwd_dense");
 }
 

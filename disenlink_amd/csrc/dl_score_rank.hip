@@ -25,6 +25,9 @@
 // Given pairs (dl_score_pair_logits, dl_score_pair_terms): the DIAG and TERMS instantiations, a tile of 128 pairs against itself
 // with the diagonal kept.  DIAG writes the logit; TERMS writes, per factor, what the pass holds on the way to it: e = exp(S / t),
 // q = h.h and the running sum, whose last column has the logit's bits ("which factor makes this link").
+// Reconstruction loss (dl_score_recon, driven by dl_score_recon.hip): the RECON instantiation, a strip of consecutive rows as
+// the queries against all candidate tiles; its epilogue writes, per value, the loss gradient into a strip of G^ for the dense
+// backward's kernel and, per (row, candidate tile), one loss cell and one count cell (recon_epilogue).
 // bf16 tables (the *_dtype entries with DL_BF16): the P = 1 instantiations, one plane per operand (copy_rows, which also
 // gathers the query rows) and one product per block; on the same values, the bits of the three-plane scan.
 #include "dl_common.h"
@@ -44,7 +47,7 @@ constexpr int MAX_K = 128;
 constexpr int ROUND = 64;      // keys one round of appends can add to a row's list
 constexpr int MAX_CAP = MAX_K + ROUND;
 constexpr int MAX_SLICES = 32;
-enum { TOPK = 0, RANKS = 1, DIAG = 2, TERMS = 3 };
+enum { TOPK = 0, RANKS = 1, DIAG = 2, TERMS = 3, RECON = 4 };
 
 struct ScanArgs {
     const __bf16 *qz, *qh;  size_t qbatch;     // planes of the gathered query rows (per factor: qbatch elements)
@@ -60,6 +63,17 @@ struct ScanArgs {
     FilterArgs filt;                                                    // FILT: the node-group rule (dl_tiles.h)
     float *te, *tq, *tcum;                     // TERMS: [T][K] each, NULL = not wanted (targets as in DIAG)
 };
+// RECON has arguments of its own behind them (the other modes' kernels keep their argument block): query row i is node
+// q0 + i (no qnode array); ex_* = the positives, ig_* = the ignored pairs (NULL: none), both symmetric CSRs; ghat
+// [>= 128 qtiles][128 nt] and one cell per (row, candidate tile): the row's loss over the tile and its positives | negatives << 16
+struct ReconArgs : ScanArgs {
+    int q0;
+    const int32_t *ig_rowptr, *ig_col;
+    float w_pos, w_neg;
+    float* ghat;  float* lcell;  unsigned* ccell;
+};
+template <int MODE> struct ModeArgs { typedef ScanArgs type; };
+template <> struct ModeArgs<RECON> { typedef ReconArgs type; };
 
 // LDS with P planes per operand (bytes): the two double-buffered staging images, the logits' way through LDS, then the
 // exclusion mask, per-row bookkeeping, per-wave compaction scratch.  The epilogue passes each wave's logits through 4 KiB of
@@ -169,6 +183,83 @@ __device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, 
     }
 }
 
+// RECON: the whole-graph reconstruction loss of a candidate tile (dl_score_recon.hip has the contract).  Two masks per row,
+// positives and ignored (the second one and the sums of the two v halves live where the top-k modes keep their compaction
+// scratch); per value p = sigmoid(s), the weighted BCE term with F.binary_cross_entropy's clamps and g = w (p - y) in the
+// one-pass scorer's form (dl_train.hip), written to the strip of G^ — zero where the pair carries no loss: ignored, the
+// diagonal, outside N.  As in the other modes the values go through LDS so that the loop over a lane's 16 rows stays rolled
+// (lg: RLG floats of the wave's own, pitch 65: the transposed read below is conflict-free); the loss terms come back the
+// same way and the 128 terms of a row are added in one fixed order — 16 consecutive columns by one lane, the two halves of a
+// 32-column block, the two blocks of a wave, the two waves — so a cell is a function of its logits alone.  Counts: ballots.
+constexpr int RPITCH = DL_WAVE + 1, RLG = 16 * RPITCH;
+static_assert(4 * RLG * 4 <= 3 * TT * SLD * 2, "four waves' terms fit a three-plane image");
+__device__ __forceinline__ void recon_epilogue(const ReconArgs& A, const f32x16 (&term)[2], float* lg, unsigned* pom, unsigned* scr,
+                                               int* pocur, int* igcur, const int* rnode, int qt, int ct, int nt, int tid) {
+    unsigned* igm = scr;                                        // [TT][4]: ignored columns of the tile, the diagonal among them
+    float* redl = reinterpret_cast<float*>(scr + TT * 4);       // [2 v halves][TT]
+    unsigned* redc = scr + TT * 4 + 2 * TT;                     // [2][TT]
+    const int wave = tid >> 6, lane = tid & 63, li = lane & 31, half = lane >> 5, wu = wave >> 1, wv = wave & 1;
+    const int v0 = ct * TT;
+    if (tid < TT) {
+        const int node = rnode[tid];
+        unsigned *m = pom + tid * 4, *g = igm + tid * 4;
+        m[0] = m[1] = m[2] = m[3] = 0u;
+        g[0] = g[1] = g[2] = g[3] = 0u;
+        if (node >= 0) {
+            pocur[tid] = exclusion_mask(A.ex_col, pocur[tid], A.ex_rowptr[node + 1], v0, m);
+            if (A.ig_rowptr != nullptr) igcur[tid] = exclusion_mask(A.ig_col, igcur[tid], A.ig_rowptr[node + 1], v0, g);
+            if (node >= v0 && node < v0 + TT) g[(node - v0) >> 5] |= 1u << ((node - v0) & 31);
+        }
+    }
+    __syncthreads();
+    const size_t Np = (size_t)nt * TT;
+    const int sq = lane & 15, sh = (lane >> 4) & 1, sp = lane >> 5;   // the sums: row (sq, sh), columns 16 sp .. 16 sp + 15 of a block
+    float racc = 0.0f;
+#pragma unroll
+    for (int bb = 0; bb < 2; ++bb) {
+        const int w = wv * 2 + bb;                              // the mask word of this 32-column block: bit li
+        const bool inside = v0 + w * 32 + li < A.N;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) lg[q * RPITCH + lane] = term[bb][q];
+#pragma unroll 1
+        for (int q = 0; q < 16; ++q) {
+            const int row = wu * 32 + acc_row(q, half);
+            const bool live = inside && rnode[row] >= 0 && !((igm[row * 4 + w] >> li) & 1u);
+            const bool pos = (pom[row * 4 + w] >> li) & 1u;
+            const float p = sigmoid_ref(lg[q * RPITCH + lane]);
+            const float lgp = logf(pos ? p : 1.0f - p);         // F.binary_cross_entropy: the log clamped at -100 (dl_pair_bce)
+            const float ww = pos ? A.w_pos : A.w_neg, r = p * (1.0f - p);
+            const float bce = ww * -(lgp < -100.0f ? -100.0f : lgp);
+            const float gl = ww * (p - (pos ? 1.0f : 0.0f)) * (r >= 1e-12f ? 1.0f : r * 1e12f);
+            A.ghat[((size_t)qt * TT + row) * Np + v0 + w * 32 + li] = live ? gl : 0.0f;
+            lg[q * RPITCH + lane] = live ? bce : 0.0f;
+            const u64 mp = __ballot(live && pos), mn = __ballot(live && !pos);
+            if (li == 0) {
+                const unsigned c = __popc((unsigned)(mp >> (32 * half))) | ((unsigned)__popc((unsigned)(mn >> (32 * half))) << 16);
+                redc[wv * TT + row] = bb == 0 ? c : redc[wv * TT + row] + c;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        float a = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a += lg[sq * RPITCH + sh * 32 + sp * 16 + i];
+        a += __shfl_xor(a, 32);
+        racc = bb == 0 ? a : racc + a;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (lane < 32) redl[wv * TT + wu * 32 + acc_row(sq, sh)] = racc;
+    __syncthreads();
+    if (tid < TT) {                                             // every cell written once, zeros included
+        const size_t cell = ((size_t)qt * TT + tid) * nt + ct;
+        A.lcell[cell] = redl[tid] + redl[TT + tid];
+        A.ccell[cell] = redc[tid] + redc[TT + tid];
+    }
+}
+
 // FILT: the node-group rule on top of the exclusion.  All 512 threads form the tile's mask from the rule, one word each, in
 // the tile's last pipeline step (the candidates' groups were staged one step earlier: a tile has K * 2 * nd >= 2 steps, and
 // every reader of the previous tile's mask and groups is behind a barrier by then); the row threads then OR the exclusion
@@ -176,7 +267,7 @@ __device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, 
 // P: planes per operand, 3 (fp32 tables) or 1 (bf16 tables: one bf16x8 and one MFMA per operand and block, gram_block<1>); the
 // step keeps its 32 columns, so the k-blocks of a product are added in the same ascending order in both.
 template <int MODE, bool FILT = false, int P = 3>
-__global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
+__global__ __launch_bounds__(RTHR) void rank_scan_kernel(typename ModeArgs<MODE>::type A) {
     static_assert(!(FILT && (MODE == DIAG || MODE == TERMS)), "the target passes have no mask");
     constexpr bool PAIRS = MODE == DIAG || MODE == TERMS;      // TERMS: DIAG's geometry and gathers, other stores
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -218,7 +309,9 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
     if constexpr (!PAIRS) {
         if (tid < TT) {
             const int qi = qt * TT + tid;
-            const int node = qi < A.Q ? A.qnode[qi] : -1;
+            int node = -1;
+            if constexpr (MODE == RECON) node = qi < A.Q ? A.q0 + qi : -1;
+            else node = qi < A.Q ? A.qnode[qi] : -1;
             rnode[tid] = node;
             cnt[tid] = 0;
             srt[tid] = 0;
@@ -235,6 +328,10 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
                     if (A.ex_col[mid] < v0) lo = mid + 1; else hi = mid;
                 }
                 excur[tid] = lo;
+            }
+            if constexpr (MODE == RECON) {                       // cnt: the cursor into the row's ignored columns
+                if (node >= 0 && A.ig_rowptr != nullptr)
+                    cnt[tid] = first_col_at_least(A.ig_col, A.ig_rowptr[node], A.ig_rowptr[node + 1], ct0 * TT);
             }
             if constexpr (MODE == RANKS) {
                 const int b = node >= 0 ? A.tptr[qi] : 0, m = node >= 0 ? A.tptr[qi + 1] - b : 0;
@@ -353,6 +450,9 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(ScanArgs A) {
                     if (ul == vl && i < A.T) A.tlogit[i] = term[bb][q];
                 }
             }
+        } else if constexpr (MODE == RECON) {
+            float* lg = reinterpret_cast<float*>((wave < 4 ? us : vs) + (s & 1) * 3 * TT * SLD) + (wave & 3) * (3 * TT * SLD / 8);
+            recon_epilogue(A, term, lg, exm, reinterpret_cast<unsigned*>(scr), excur, cnt, rnode, qt, ct0 + s / per_tile, nt, tid);
         } else {
             if (tid < TT) {                                     // this tile's excluded columns of row tid
                 const int node = rnode[tid];
@@ -730,6 +830,27 @@ int score_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, 
     if (nf != nullptr)
         hipLaunchKernelGGL(target_unallowed_kernel, dim3(tb), dim3(256), 0, st, w.trow, tdst, queries, exr, exc, T, a.filt, ties);
     return check_launch("score_ranks");
+}
+
+// ---- the RECON scan of one strip of rows (dl_score_recon.hip drives it): rows [q0, q0 + rows) of the graph, q0 a multiple of
+// 128, as the query tiles — read where they stand in the plane arrays of Z and H, which are the candidates too — against all
+// candidate tiles.  ghat: rows x Np floats and the cells [rows rounded up to 128][Np / 128], all of it written.
+void score_recon_strip(const __bf16* cz, const __bf16* ch, int N, int K, int d, float t, int q0, int rows, const int32_t* pos_rowptr,
+                       const int32_t* pos_col, const int32_t* ig_rowptr, const int32_t* ig_col, float w_pos, float w_neg, float* ghat,
+                       float* lcell, unsigned* ccell, hipStream_t st) {
+    const RankPlan p = rank_plan(N, d, rows, 0);
+    ReconArgs a = {};
+    const size_t first = plane_tile<SDC, 3>(q0 / TT, 0, p.nd);
+    a.qz = cz + first; a.qh = ch + first; a.qbatch = p.cbatch;
+    a.cz = cz; a.ch = ch; a.cbatch = p.cbatch;
+    a.Q = rows; a.N = N; a.K = K; a.nd = p.nd; a.t = t;
+    a.ex_rowptr = pos_rowptr; a.ex_col = pos_col;
+    a.slices = p.slices; a.tiles_per_slice = p.tps;
+    a.q0 = q0;
+    a.ig_rowptr = ig_rowptr; a.ig_col = ig_col;
+    a.w_pos = w_pos; a.w_neg = w_neg;
+    a.ghat = ghat; a.lcell = lcell; a.ccell = ccell;
+    launch_lds<rank_scan_kernel<RECON>>((unsigned)xcd_grid(p.qtiles, p.slices), RTHR, lds_bytes(3), st, a);
 }
 
 // ---- dl_score_pair_logits: the DIAG pass on its own, with the plane arrays of Z and H as BOTH sides: pair i = (row a[i] as

@@ -48,6 +48,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--data-file", type=str, default=None, help="binary dataset written by datasets.save_binary")
     p.add_argument("--synthetic", action="store_true", help="seeded synthetic stand-in of --dataset")
     p.add_argument("--table-dtype", choices=["f32", "bf16"], default="f32")
+    p.add_argument("--objective", choices=["pairs", "recon"], default="pairs",
+                   help="the training loss: pairs = the reference's BCE on m sampled negatives per edge; recon = the "
+                        "whole-graph reconstruction loss, every non-edge a negative and the edges up-weighted, with the "
+                        "validation and test pairs ignored (Disentangle.forward_recon_loss: nothing of size N x N is formed; "
+                        "one GPU, fp32 tables, eager loop)")
+    p.add_argument("--pos-weight", type=float, default=None,
+                   help="with --objective recon: the weight of a positive pair (default: negatives / positives)")
+    p.add_argument("--recon-block-rows", type=int, default=None,
+                   help="with --objective recon: rows per strip, a multiple of 128 (default: the largest strip of at most 1 GiB)")
     p.add_argument("--no-graph", action="store_true",
                    help="launch every epoch from Python instead of replaying it from a captured HIP graph")
     p.add_argument("--graph", action="store_true",
@@ -404,6 +413,9 @@ def main(argv=None):
                                args.predict_top is not None):
         raise SystemExit("--link-rule restricts the candidates of --rank-eval, --global-rank-eval, --mine and --predict-links: "
                          "give one of them")
+    if args.objective == "recon" and (args.gpus > 1 or args.table_dtype == "bf16" or args.graph):
+        raise SystemExit("--objective recon runs on one GPU with fp32 tables in the eager loop only (sharded, bf16 and "
+                         "graph-replayed reconstruction epochs are not implemented): drop --gpus / --table-dtype bf16 / --graph")
     if args.gpus > 1:
         from .launch import launch_ranks, under_launcher
         if not under_launcher():                                    # BEFORE any GPU call: the parent starts and waits
@@ -452,7 +464,9 @@ def main(argv=None):
         model = Disentangle(x.shape[1], args.nhidden, args.nembed, nfactor=args.nfactor, beta=args.beta,
                             t=args.temperature, table_dtype=tdt).to(device)
         res = run_link_prediction(model, x, prepared, epochs=args.epochs, lr=args.lr,
-                                  log=None if args.quiet else print, use_graph=_use_graph(args))
+                                  log=None if args.quiet else print,
+                                  use_graph=_use_graph(args) and args.objective == "pairs", objective=args.objective,
+                                  pos_weight=args.pos_weight, recon_block_rows=args.recon_block_rows)
         if not args.quiet:
             print("test auc:", res.test_auc)
         result.append(res.test_auc)

@@ -22,6 +22,8 @@ from .link_pred import (                                                # noqa: 
 from .project import (                                                  # noqa: F401  (the projection: ops.project_* as before)
     Project, _pad_features, _XPlanes, keep_hidden, padded_features, project_bwd, project_fwd, project_sparse_bwd,
     project_sparse_fwd, project_supported, project_tile_width, xplanes_for)
+from .recon import (                                                    # noqa: F401  (the whole-graph reconstruction loss)
+    ReconLoss, ReconSets, check_recon_counts, recon_sets, recon_weights, score_recon_loss)
 from .scans import (                                                    # noqa: F401  (the all-pairs scans: ops.score_* as before)
     BETWEEN_MAX_N, BLOCK_NODES, BLOCKS_MAX_N, LINKS_MAX_N, MINE_MAX_M, MINE_MAX_N, RANK_MAX_K, LinksBetween, NodeFilter,
     PairExclusion, PairTerms, bipartite_exclusion_csr, exclusion_csr, pair_exclusion, score_link_degrees,

@@ -1,0 +1,167 @@
+"""The whole-graph reconstruction objective over libdisenlink_hip.so (dl_score_recon): every non-edge is a negative, the
+positives are up-weighted, and loss and gradient come from one call that forms nothing of size N x N.  A leaf beside
+``scans``: it imports ``_dev``, ``_lib`` and the set normalisation of ``scans``; ``ops`` re-exports the public names.
+
+The contract (restated in fp64 by tests/recon_ref.py).  Included pairs: all unordered {u, v}, u != v, outside ``ignore``;
+a pair listed in both sets is ignored.  For an included pair, with s = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) and
+p = sigmoid(s):  y = 1 if the pair is in ``positives`` else 0;  w = pos_weight / C for y = 1, else 1 / C, with
+C = n_pos + n_neg the number of included pairs;  loss = sum w BCE(p, y) with F.binary_cross_entropy's clamps;
+d loss / d s = w (p - y) in the one-pass scorer's form (saturated pairs contribute exactly 0).  No tile of the scan is
+skipped: a zero gradient against an overflowed exp(z.z / t) = inf gives NaN in dZ / dH, exactly as the dense backward
+(``score_allpairs_bwd_dense``) documents — it is the same kernel.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+
+import torch
+
+from . import _lib
+from ._dev import _empty, _need_cuda, _nkd, _stream, _ws
+from .scans import _csr_args, _csr_rows, _exclusion_arg, exclusion_csr
+
+
+ReconSets = namedtuple("ReconSets", ["n_nodes", "pos_rowptr", "pos_col", "ign_rowptr", "ign_col", "n_pos", "n_neg", "n_ignored"])
+ReconSets.__doc__ = """The two pair sets of the reconstruction loss, normalised once (``recon_sets``): symmetric CSRs (int32, every
+pair in both of its rows, columns ascending and distinct) of the positives that are not ignored and of the ignored pairs
+(``ign_*`` None where there are none), and the host's counts: ``n_pos`` included positives, ``n_neg`` = N (N - 1) / 2 -
+n_ignored - n_pos included negatives.  A caller with fixed sets passes the result instead of the raw sets and skips the
+normalisation, and its host read, per call."""
+
+
+def _unordered_keys(pairs, N: int, device) -> torch.Tensor:
+    """int64 keys u * N + v, u < v, ascending and distinct, of a set of unordered pairs in any form ``pair_exclusion``
+    takes (a ``Graph``, a dense [N,N] mask, ``(rows, cols)`` or a prepared ``PairExclusion``): either orientation, duplicates
+    collapsed, self pairs dropped."""
+    if pairs is None:
+        return torch.zeros(0, dtype=torch.int64, device=device)
+    ex = _exclusion_arg(pairs, N, torch.device(device), keyed=False)
+    if ex.rowptr is None:
+        return torch.zeros(0, dtype=torch.int64, device=device)
+    rows, cols = _csr_rows(ex.rowptr), ex.col.to(torch.int64)          # column max(a, b) of row min(a, b)
+    keep = cols > rows
+    return rows[keep] * N + cols[keep]
+
+
+def _symmetric_csr(key: torch.Tensor, N: int, device):
+    u = torch.div(key, N, rounding_mode="floor")
+    v = key - u * N
+    return exclusion_csr((torch.cat([u, v]), torch.cat([v, u])), N, device)
+
+
+def recon_sets(positives, ignore, N: int, device) -> ReconSets:
+    """Normalise ``positives`` and ``ignore`` (each whatever ``pair_exclusion`` accepts; ``ignore`` may be None) for
+    ``score_recon_loss``: self pairs and duplicates go, an asymmetric listing is symmetrised, a pair in both sets is ignored.
+    ONE host read (the two set sizes)."""
+    N, device = int(N), torch.device(device)
+    pos, ign = _unordered_keys(positives, N, device), _unordered_keys(ignore, N, device)
+    if ign.numel() and pos.numel():
+        pos = pos[~torch.isin(pos, ign)]
+    n_pos, n_ign = int(pos.numel()), int(ign.numel())                   # (sizes of device tensors: the host read)
+    pr, pc = _symmetric_csr(pos, N, device)
+    ir, ic = _symmetric_csr(ign, N, device) if n_ign else (None, None)
+    return ReconSets(N, pr, pc, ir, ic, n_pos, N * (N - 1) // 2 - n_ign - n_pos, n_ign)
+
+
+def _sets_arg(positives, ignore, N: int, device) -> ReconSets:
+    if isinstance(positives, ReconSets):
+        if ignore is not None:
+            raise ValueError("prepared ReconSets carry their ignored pairs: pass ignore=None")
+        if positives.n_nodes != N:
+            raise ValueError(f"reconstruction sets of {positives.n_nodes} nodes, tables of {N}")
+        if positives.pos_rowptr.device != device:
+            raise ValueError(f"reconstruction sets on {positives.pos_rowptr.device}, tables on {device}")
+        return positives
+    return recon_sets(positives, ignore, N, device)
+
+
+def _recon_tables(Z, H):
+    """fp32 [N,K,d] tables on the device with 1 <= d <= 128; anything else raises (there is no fallback)."""
+    if Z.dtype != torch.float32 or H.dtype != torch.float32:
+        raise TypeError(f"the reconstruction loss takes fp32 tables, got {Z.dtype} / {H.dtype}")
+    _need_cuda(Z, H)
+    N, K, d = _nkd(Z)
+    if tuple(H.shape) != tuple(Z.shape):
+        raise ValueError("Z and H differ in shape")
+    if N < 1 or not _lib.load().dl_score_recon_supported(K, d):
+        raise _lib.DisenlinkHipError(f"the reconstruction loss serves N >= 1, K <= 64 and 1 <= d <= 128 (got N={N}, K={K}, "
+                                     f"d={d}); there is no eager fallback")
+    return Z.contiguous(), H.contiguous(), N, K, d
+
+
+def recon_weights(sets: ReconSets, pos_weight=None):
+    """(w_pos, w_neg) = (pos_weight / C, 1 / C), C = n_pos + n_neg; ``pos_weight`` defaults to n_neg / n_pos (1 where
+    there is no positive).  No included pair at all: (0, 0)."""
+    C = sets.n_pos + sets.n_neg
+    if C <= 0:
+        return 0.0, 0.0
+    if pos_weight is None:
+        pos_weight = sets.n_neg / sets.n_pos if sets.n_pos else 1.0
+    return float(pos_weight) / C, 1.0 / C
+
+
+def _block_rows(block_rows) -> int:
+    b = 0 if block_rows is None else int(block_rows)
+    if b < 0 or b % 128:
+        raise ValueError(f"block_rows must be a positive multiple of 128 (or None for the default), got {block_rows}")
+    return b
+
+
+def score_recon_loss(Z, H, t: float, positives, ignore=None, pos_weight=None, block_rows=None):
+    """-> (loss f64 [], dZ f32 [N,K,d], dH f32 [N,K,d], counts int64 [2]): the whole-graph reconstruction loss of the
+    module docstring and its gradient with respect to the tables, by strips of ``block_rows`` rows (None: the largest
+    multiple of 128 whose strip of G^ stays at or under 1 GiB — the whole graph where that fits).  ``positives`` /
+    ``ignore``: unordered pair sets as ``pair_exclusion`` takes them, or ``positives`` = a prepared ``recon_sets(...)`` (then
+    no host read happens here).  ``counts`` = the included positives and negatives the scan saw, DEVICE values to compare
+    with the sets' ``n_pos`` / ``n_neg`` wherever the caller synchronises anyway (``check_recon_counts``).  fp32 tables
+    with 1 <= d <= 128, anything else raises.  No float atomics, no host read and no synchronisation in the call; launches
+    follow the current stream; the same bits on every call, for every ``block_rows`` and every DL_RANK_SLICES."""
+    Z, H, N, K, d = _recon_tables(Z, H)
+    sets = _sets_arg(positives, ignore, N, Z.device)
+    return _recon_call(Z, H, N, K, d, float(t), sets, recon_weights(sets, pos_weight), _block_rows(block_rows))
+
+
+def _recon_call(Z, H, N, K, d, t, sets, weights, block_rows):
+    lib = _lib.load()
+    dev = Z.device
+    loss = _empty((1,), torch.float64, dev)
+    counts = _empty((2,), torch.int64, dev)
+    dZ, dH = _empty(Z.shape, torch.float32, dev), _empty(Z.shape, torch.float32, dev)
+    pr, pc, keep_p = _csr_args(sets.pos_rowptr, sets.pos_col, dev)
+    ir, ic, keep_i = _csr_args(sets.ign_rowptr, sets.ign_col, dev)
+    ws = _ws.get(max(256, int(lib.dl_score_recon_workspace_bytes(N, K, d, block_rows))), dev)
+    _lib.check(lib.dl_score_recon(Z.data_ptr(), H.data_ptr(), N, K, d, t, pr, pc, ir, ic, weights[0], weights[1], block_rows,
+                                  loss.data_ptr(), counts.data_ptr(), dZ.data_ptr(), dH.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  _stream()), "dl_score_recon")
+    del keep_p, keep_i
+    return loss.reshape(()), dZ, dH, counts
+
+
+def check_recon_counts(counts, sets: ReconSets) -> None:
+    """The scans' "exact count" check: ``counts`` (a host list or a tensor: then this synchronises) against the host's
+    n_pos and N (N - 1) / 2 - |ignored| - n_pos; a mismatch raises."""
+    got = [int(c) for c in (counts.tolist() if torch.is_tensor(counts) else counts)]
+    if got != [sets.n_pos, sets.n_neg]:
+        raise _lib.DisenlinkHipError(f"the reconstruction scan saw {got[0]} positives and {got[1]} negatives, the host counts "
+                                     f"{sets.n_pos} and {sets.n_neg}")
+
+
+class ReconLoss(torch.autograd.Function):
+    """(Z, H) -> loss (fp32 scalar) of ``score_recon_loss``; the forward keeps dZ, dH and the backward scales them by the
+    incoming scalar.  ``sets``: a prepared ``recon_sets(...)``.  The device counts of the last forward stand in
+    ``ReconLoss.last_counts`` for ``check_recon_counts``."""
+    last_counts = None
+
+    @staticmethod
+    def forward(ctx, Z, H, t: float, sets: ReconSets, pos_weight=None, block_rows=None):
+        Z, H, N, K, d = _recon_tables(Z, H)
+        sets = _sets_arg(sets, None, N, Z.device)
+        loss, dZ, dH, counts = _recon_call(Z, H, N, K, d, float(t), sets, recon_weights(sets, pos_weight), _block_rows(block_rows))
+        ctx.save_for_backward(dZ, dH)
+        ReconLoss.last_counts = counts
+        return loss.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        dZ, dH = ctx.saved_tensors
+        return dZ * g, dH * g, None, None, None, None

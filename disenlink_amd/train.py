@@ -167,9 +167,21 @@ def _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, es
 
 
 def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 2000, lr: float = 1e-4,
-                        patience: int = 200, weight_decay: float = 5e-4, log=None, use_graph: bool = False) -> RunResult:
+                        patience: int = 200, weight_decay: float = 5e-4, log=None, use_graph: bool = False,
+                        objective: str = "pairs", pos_weight=None, recon_block_rows=None) -> RunResult:
     """``use_graph=True`` (GPU only): replay each epoch from a captured HIP graph (same arithmetic, same
-    schedule; only the host-side launch cost disappears)."""
+    schedule; only the host-side launch cost disappears).
+    ``objective``: "pairs" (the default: the reference's loss on the sampled pair list) or "recon" — the whole-graph
+    reconstruction loss (``model.forward_recon_loss``: every non-edge of the training graph a negative, positives weighted
+    by ``pos_weight``, default n_neg / n_pos, all validation and test pairs ignored, by strips of ``recon_block_rows``
+    rows), in the eager loop with the bookkeeping on the host; validation and test AUC as ever."""
+    if objective not in ("pairs", "recon"):
+        raise ValueError(f"objective must be \"pairs\" or \"recon\", got {objective!r}")
+    if objective == "recon":
+        if use_graph:
+            raise ValueError("objective=\"recon\" runs in the eager loop only (HIP-graph replay of the reconstruction epoch "
+                             "is not implemented): pass use_graph=False")
+        return _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, recon_block_rows)
     if use_graph and x.is_cuda:
         return _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log)
     # same update rule as the reference's Adam (main_disentangled.py:150); on the GPU torch's single-kernel
@@ -236,6 +248,57 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     model.load_state_dict(weights)
     with torch.no_grad():
         _emb, prob = model.forward_pairs(x, run.graph, run.test_pairs)
+    res.test_auc = float(auc_tie_avg(run.label_test, prob, check=False))
+    res.best_val_auc = best_auc
+    return res
+
+
+def _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, block_rows) -> RunResult:
+    """run_link_prediction's eager loop with the reconstruction loss: the loss of ``model.forward_recon_loss`` over the
+    training graph with every validation and test pair ignored; the validation AUC from ``forward_pairs`` under no_grad on
+    the weights before the step (:202-204); one host read per epoch, which also carries the device's counts of the pairs
+    the scan saw — compared with the host's, a mismatch raises."""
+    from . import ops
+    for lab in (run.label_val, run.label_test):
+        if not 0 < float(lab.sum()) < lab.numel():
+            raise ValueError("AUC undefined with one class")
+    b = run.n_pos + run.n_neg
+    tv, te = run.train_val_pairs, run.test_pairs
+    held = (torch.cat([tv.pu[b:], te.pu]).long(), torch.cat([tv.pv[b:], te.pv]).long())
+    sets = ops.recon_sets(run.graph, held, run.graph.n_nodes, x.device)
+    opt = _make_adam(model, bool(x.is_cuda), lr, weight_decay)
+    snapshot = getattr(model, "snapshot_state", None) or (lambda: deepcopy(model.state_dict()))
+    best_auc, stale, weights = 0.0, 0, snapshot()
+    res = RunResult(float("nan"), 0.0, 0)
+    val_plan = AucPlan(run.label_val)
+    for epoch in range(epochs):
+        model.train()
+        _emb, loss = model.forward_recon_loss(x, run.graph, sets, pos_weight, block_rows)
+        counts = ops.ReconLoss.last_counts
+        with torch.no_grad():
+            _emb, prob = model.forward_pairs(x, run.graph, tv)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        model.eval()
+        loss_v, auc, n_pos, n_neg = torch.cat([torch.stack([loss.detach().double(), val_plan.auc(prob[b:])]),
+                                               counts.double()]).tolist()     # ONE device->host sync per epoch
+        ops.check_recon_counts([n_pos, n_neg], sets)
+        res.losses.append(loss_v)
+        res.val_aucs.append(auc)
+        res.epochs_run = epoch + 1
+        if auc > best_auc:
+            stale, best_auc = 0, auc
+            weights = snapshot()
+        else:
+            stale += 1
+        if stale > patience:
+            break
+        if log is not None:
+            log(f"epoch: {epoch} loss: {res.losses[-1]} val_auc: {best_auc}")
+    model.load_state_dict(weights)
+    with torch.no_grad():
+        _emb, prob = model.forward_pairs(x, run.graph, te)
     res.test_auc = float(auc_tie_avg(run.label_test, prob, check=False))
     res.best_val_auc = best_auc
     return res

@@ -459,6 +459,46 @@ int dl_score_allpairs_bwd_dense(const float* Z, const float* H, int N, int K, in
                                 float* dZ, float* dH,                     /* [N][K][d], every element written */
                                 void* ws, size_t ws_bytes, void* stream);
 
+/* Whole-graph reconstruction loss and its gradient with nothing of size N x N in memory: every non-edge is a negative, the
+ * positives are up-weighted (the objective of the GAE family), and the gradient of the tables comes from the same call.
+ * Included pairs: all unordered {u, v}, u != v, that are not in the ignored set; a pair in both sets is ignored.  For an
+ * included pair, with s = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) and p = sigmoid(s):
+ *   y = 1 if the pair is a positive, else 0;   w = w_pos for y = 1, else w_neg   (the caller's pos_weight / C and 1 / C,
+ *   C = the number of included pairs, known on the host before the launch);
+ *   loss = sum w BCE(p, y), the logs clamped at -100 as F.binary_cross_entropy and dl_pair_bce clamp them;
+ *   d loss / d s = w (p - y), in the one-pass scorer's form with its max(p (1 - p), 1e-12) clamp (dl_score_pairs_train):
+ *   a saturated pair contributes exactly 0.
+ * pos_rowptr / pos_col and ign_rowptr / ign_col: SYMMETRIC CSRs over the N nodes (int32, rowptr [N + 1], columns ascending
+ * and distinct within a row, every pair listed in both of its rows); the ignored set may be NULL / NULL.  Self entries of
+ * either set mean nothing: the diagonal never carries loss.
+ * Outputs: loss_out [1] double, counts_out [2] int64 = included positives and negatives as the scan saw them (DEVICE
+ * values: the caller compares them with its own n_pos and N (N - 1) / 2 - |ignored| - n_pos), dZ, dH fp32 [N][K][d], every
+ * element written.
+ * Method: block_rows rows at a time (0 = the default: the largest multiple of 128 whose strip of block_rows x Np floats
+ * stays at or under 1 GiB, the whole graph where that fits; otherwise a positive multiple of 128), the ranking scan in a
+ * mode of its own forms the logits of the strip's rows against all nodes, and per value the loss term and
+ * G^[u][v] = d loss / d s_uv (0 for ignored pairs, the diagonal and outside N); dl_score_allpairs_bwd_dense's kernel then
+ * runs over the strip's rows with the strip as its G^.  Every unordered pair is visited from both of its rows: loss and
+ * counts are the row sums halved (exactly).  No tile is skipped, so a zero of G^ against an overflowed exp gives NaN in the
+ * gradients exactly as dl_score_allpairs_bwd_dense documents.  No float atomics, no host read, no allocation, the caller's
+ * stream; the same bits on every call, for every block_rows and for every DL_RANK_SLICES.
+ * Limits: fp32 tables, 1 <= d <= 128 (dl_score_recon_supported), 1 <= N <= DL_SCORE_RECON_MAX_N, t != 0.
+ * ws: dl_score_recon_workspace_bytes(N, K, d, block_rows) bytes (0 for arguments out of range): with Np = N rounded up to 128
+ * and dp = d to 32, four plane arrays of 6 K Np dp bytes, one strip of 4 block_rows Np, two cell arrays of block_rows Np / 32,
+ * 24 N of row sums and the dense backward's slice partials (8 nslice N K d, none for nslice = 1), each rounded up to 256;
+ * a missing or short workspace fails with DL_E_WORKSPACE. */
+#define DL_SCORE_RECON_MAX_N 4194304
+int dl_score_recon_supported(int K, int d);                          /* fp32 tables, 1 <= d <= 128 */
+/* The launch form (host only).  out[DL_SCORE_RECON_FORM_LEN] = [0] Np  [1] strips  [2] rows per strip  [3] slices of the
+ * v range of the backward: dl_score_allpairs_bwd_dense_form's for the whole N, whatever block_rows is. */
+#define DL_SCORE_RECON_FORM_LEN 4
+int dl_score_recon_form(int N, int K, int d, int block_rows, int* out);
+size_t dl_score_recon_workspace_bytes(int N, int K, int d, int block_rows);
+int dl_score_recon(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* pos_rowptr,
+                   const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
+                   int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
+                   void* stream);
+
 /* Ranking of ALL candidate links of query nodes (an extension; the reference has no counterpart): the logit of the dense
  * scorer, s(u,v) = sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), for every
  * (query, candidate) pair on the matrix cores (the dense scorer's three-plane products, the query as the A operand;
