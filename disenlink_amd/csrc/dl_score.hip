@@ -314,12 +314,19 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
         for (int q = 0; q < 16; ++q) val[q] = 0.0f;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
+            // the chunk's eight LDS reads are issued together, ahead of its dot products: left in one loop with them, the reads
+            // of the second chunk go out one or two at a time, each behind the wait of the one before (profiles/r12_*)
+            float4 a4[U], b4[U];
 #pragma unroll
             for (int e = 0; e < U; ++e) {
                 const float4* mine = urow + (su[e] & (DL_HUB_W - 1)) * R4;     // this slot's own u row
-                const float4 a4 = mine[j * 64 + lane], b4 = mine[ROW / 4 + j * 64 + lane];
-                val[j * 4 + e] = dot4_packed(a4, zv[e * NV / 4][j]);
-                val[8 + j * 4 + e] = dot4_packed(b4, hv[e * NV / 4][j]);
+                a4[e] = mine[j * 64 + lane], b4[e] = mine[ROW / 4 + j * 64 + lane];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int e = 0; e < U; ++e) {
+                val[j * 4 + e] = dot4_packed(a4[e], zv[e * NV / 4][j]);
+                val[8 + j * 4 + e] = dot4_packed(b4[e], hv[e * NV / 4][j]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }

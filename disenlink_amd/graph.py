@@ -534,9 +534,10 @@ HUB_W = 16                  # rows of a hub block (DL_HUB_W: 16 [Z | H] rows of 
 HUB_MIN_SHARE = 1.25
 # A (block, slice) whose steps gather more partner rows than this is cut into several work items, each staging the
 # block's rows again: the longest (block, slice) of squirrel_real has ~1,300 steps, five times what a workgroup gets on
-# average, and uncut it would be the tail of the launch.  256 is what every figure above was measured with; its sweep
-# (tools/fwd_hub_ab.py --items) is still to be run (profiles/r10_fwd_hub.txt, section 4).
-HUB_ITEM_ROWS = 256
+# average, and uncut it would be the tail of the launch.  256 is what every figure above was measured with.  The sweep on
+# the benchmark's own plan (profiles/r12_fwd_hub_pipeline.txt, section 3; us per call): 128 / 256 / 384 / 512 / 768 / 1,024
+# = 129.3 / 118.7 / 116.4 / 116.3 / 117.7 / 116.1 — 512 and 1,024 pass the keep rule against 256 and tie; 512 is the shorter.
+HUB_ITEM_ROWS = 512
 
 
 def hub_gathers(c: torch.Tensor) -> torch.Tensor:

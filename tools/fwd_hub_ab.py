@@ -3,7 +3,8 @@ rows (PairList.build(hub_rows=0): the wave-per-entry kernel alone), the scorer c
 All forms interleaved in one process: 12 rounds, order reversed every other round, HIP events around 100 calls after 50
 warm-up calls per form; median / min / max per form, torch.equal of all probabilities against hub_rows=0, and the
 project's keep rule (worst of the form below the reference's best, gain above twice the reference's min-max spread).
-usage: python tools/fwd_hub_ab.py [workload] [K] [d] [t] [--items]     (--items: sweep graph.HUB_ITEM_ROWS at T = 2048 instead of T)"""
+usage: python tools/fwd_hub_ab.py [workload] [K] [d] [t] [--items [--auto]]     (--items: sweep graph.HUB_ITEM_ROWS at T = 2048
+instead of T; with --auto at the automatic hub rows, the plan the benchmark runs)"""
 import os, sys
 import numpy as np
 import torch
@@ -33,9 +34,10 @@ print("  entries per gathered row pair of block 0, 16, 32, ...: " + " ".join(f"{
 build = lambda T: PairList.build(pu, pv, N, row_bytes=K * d * 4, hub_rows=T)
 forms = {"hub_rows=0": build(0)}
 if "--items" in sys.argv:
-    for cap in (64, 128, 256, 512, 1 << 30):
+    T_items = auto if "--auto" in sys.argv else 2048
+    for cap in (64, 128, 256, 384, 512, 768, 1024, 1 << 30):
         graph.HUB_ITEM_ROWS = cap
-        forms[f"T=2048 item<={cap}"] = build(2048)
+        forms[f"T={T_items} item<={cap}"] = build(T_items)
 else:
     for T in sorted({512, 1024, 2048, at_thr, auto, n_live} - {0}):
         forms[f"T={T}" + (" (auto)" if T == auto else "") + (" (all rows)" if T == n_live else "")] = build(T)
