@@ -121,6 +121,9 @@ EXPORTS = {
     "dl_score_recon_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "dl_score_recon_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "dl_score_recon": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _P, _f, _f, _i, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_score_recon_form_dtype": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "dl_score_recon_workspace_bytes_dtype": (_z, [_i, _i, _i, _i, _i]),
+    "dl_score_recon_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _P, _P, _f, _f, _i, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_topk_supported": (_i, [_i, _i]),
     "dl_score_mine_supported": (_i, [_i, _i]),
     "dl_score_mine_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
@@ -297,11 +300,12 @@ def score_allpairs_bwd_dense_form(N: int, K: int, d: int) -> dict:
 SCORE_RECON_FORM = ("Np", "strips", "block_rows", "nslice")
 
 
-def score_recon_form(N: int, K: int, d: int, block_rows: int = 0) -> dict:
+def score_recon_form(N: int, K: int, d: int, block_rows: int = 0, dtype: int = DL_F32) -> dict:
     """The strips of dl_score_recon for this problem (``block_rows`` = 0: the default height) and the slice count of its
-    backward, which is the dense backward's for the whole N (dl_score_recon_form)."""
+    backward, which is the dense backward's for the whole N (dl_score_recon_form_dtype; the form is the same for both table
+    types)."""
     out = (C.c_int * len(SCORE_RECON_FORM))()
-    check(load().dl_score_recon_form(N, K, d, block_rows, out), "dl_score_recon_form")
+    check(load().dl_score_recon_form_dtype(N, K, d, dtype, block_rows, out), "dl_score_recon_form_dtype")
     return dict(zip(SCORE_RECON_FORM, out))
 
 

@@ -1002,37 +1002,54 @@ int dl_score_allpairs_bwd_dense(const float* Z, const float* H, int N, int K, in
 int dl_score_recon_supported(int K, int d) { return K >= 1 && K <= DL_MAX_FACTORS && score_recon_supported(K, d) ? 1 : 0; }
 
 // block_rows: 0 (the default) or a positive multiple of 128
-static bool recon_shape_ok(int N, int K, int d, int block_rows) {
-    return N >= 1 && N <= DL_SCORE_RECON_MAX_N && dl_score_recon_supported(K, d) && block_rows >= 0 && block_rows % 128 == 0;
+static bool recon_shape_ok(int N, int K, int d, dl_dtype dtype, int block_rows) {
+    return N >= 1 && N <= DL_SCORE_RECON_MAX_N && known_dtype(dtype) && dl_score_recon_supported(K, d) && block_rows >= 0 &&
+           block_rows % 128 == 0;
 }
 
-int dl_score_recon_form(int N, int K, int d, int block_rows, int* out) {
-    DL_REQUIRE(out != nullptr && recon_shape_ok(N, K, d, block_rows), "bad argument");
-    score_recon_form(N, K, d, block_rows, out);
+int dl_score_recon_form(int N, int K, int d, int block_rows, int* out) { return dl_score_recon_form_dtype(N, K, d, DL_F32, block_rows, out); }
+
+int dl_score_recon_form_dtype(int N, int K, int d, dl_dtype dtype, int block_rows, int* out) {
+    DL_REQUIRE(out != nullptr && recon_shape_ok(N, K, d, dtype, block_rows), "bad argument");
+    score_recon_form(N, K, d, dtype, block_rows, out);
     return DL_OK;
 }
 
 size_t dl_score_recon_workspace_bytes(int N, int K, int d, int block_rows) {
-    return recon_shape_ok(N, K, d, block_rows) ? score_recon_workspace_bytes(N, K, d, block_rows) : 0;
+    return dl_score_recon_workspace_bytes_dtype(N, K, d, DL_F32, block_rows);
+}
+
+size_t dl_score_recon_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype, int block_rows) {
+    return recon_shape_ok(N, K, d, dtype, block_rows) ? score_recon_workspace_bytes(N, K, d, dtype, block_rows) : 0;
 }
 
 int dl_score_recon(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* pos_rowptr, const int32_t* pos_col,
                    const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg, int block_rows, double* loss_out,
                    int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes, void* stream) {
+    return dl_score_recon_dtype(Z, H, N, K, d, DL_F32, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, loss_out,
+                                counts_out, dZ, dH, ws, ws_bytes, stream);
+}
+
+int dl_score_recon_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
+                         const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
+                         int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
+                         void* stream) {
+    DL_REQUIRE(known_dtype(dtype), "unknown dtype %d", (int)dtype);
     if (int rc = check_shape(K, d)) return rc;
-    DL_REQUIRE(dl_score_recon_supported(K, d), "the reconstruction loss serves fp32 tables with 1 <= d <= 128, got d=%d", d);
+    DL_REQUIRE(dl_score_recon_supported(K, d), "the reconstruction loss serves fp32 and bf16 tables with 1 <= d <= 128, got d=%d", d);
     DL_REQUIRE(N >= 1 && N <= DL_SCORE_RECON_MAX_N, "N=%d outside 1..%d", N, DL_SCORE_RECON_MAX_N);
     DL_REQUIRE(block_rows >= 0 && block_rows % 128 == 0, "block_rows=%d is neither 0 nor a positive multiple of 128", block_rows);
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     DL_REQUIRE(Z && H && pos_rowptr && pos_col && loss_out && counts_out && dZ && dH, "NULL argument");
     DL_REQUIRE((ign_rowptr == nullptr) == (ign_col == nullptr), "ign_rowptr and ign_col must both be given or both be NULL");
-    const size_t need = score_recon_workspace_bytes(N, K, d, block_rows);
+    const size_t need = score_recon_workspace_bytes(N, K, d, dtype, block_rows);
     if (!ws || ws_bytes < need) {
-        set_error("workspace too small: have %zu, need %zu (dl_score_recon_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
+        set_error("workspace too small: have %zu, need %zu (dl_score_recon_workspace_bytes%s)", ws ? ws_bytes : (size_t)0, need,
+                  dtype == DL_F32 ? "" : "_dtype");
         return DL_E_WORKSPACE;
     }
-    return score_recon(Z, H, N, K, d, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, loss_out, counts_out,
-                       dZ, dH, ws, (hipStream_t)stream);
+    return score_recon(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, loss_out,
+                       counts_out, dZ, dH, ws, (hipStream_t)stream);
 }
 
 int dl_score_pairs_train_supported(const dl_pair_incidence* inc, int K, int d, dl_dtype dtype) {

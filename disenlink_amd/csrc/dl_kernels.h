@@ -78,22 +78,25 @@ int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d
 // slices.  The v range is cut into dense_bwd_nslice(N, K) slices whatever the u range.
 int dense_bwd_nslice(int N, int K);
 size_t dense_bwd_part_floats(int N, int K, int d);
+// dt = DL_BF16 (the reconstruction loss on bf16 tables): copy_cols for the transposed planes, one plane per array, and the
+// one-plane form of the main kernel.
 void dense_bwd_cols(const float* Z, const float* H, int N, int K, int d, __bf16* zT, __bf16* hT, hipStream_t st);
-void dense_bwd_tiles(const __bf16* zp, const __bf16* hp, const __bf16* zT, const __bf16* hT, const float* ghat, int N, int K, int d,
-                     float t, int ut0, int n_ut, bool strip, float* part, float* dZ, float* dH, hipStream_t st);
+void copy_cols(const __bf16* Z, const __bf16* H, int N, int K, int d, __bf16* zT, __bf16* hT, hipStream_t st);
+void dense_bwd_tiles(const __bf16* zp, const __bf16* hp, const __bf16* zT, const __bf16* hT, dl_dtype dt, const float* ghat, int N,
+                     int K, int d, float t, int ut0, int n_ut, bool strip, float* part, float* dZ, float* dH, hipStream_t st);
 void dense_bwd_combine(const float* part, int N, int K, int d, float* dZ, float* dH, hipStream_t st);
 
 // whole-graph reconstruction loss and gradient by strips of rows (dl_score_recon.hip; its scan is the RECON mode of
-// dl_score_rank.hip): fp32 tables, 1 <= d <= 128
+// dl_score_rank.hip): fp32 or bf16 tables (dt), 1 <= d <= 128; the form does not depend on dt, the workspace does
 bool score_recon_supported(int K, int d);
-void score_recon_form(int N, int K, int d, int block_rows, int* out);
-size_t score_recon_workspace_bytes(int N, int K, int d, int block_rows);
-void score_recon_strip(const __bf16* cz, const __bf16* ch, int N, int K, int d, float t, int q0, int rows, const int32_t* pos_rowptr,
-                       const int32_t* pos_col, const int32_t* ig_rowptr, const int32_t* ig_col, float w_pos, float w_neg, float* ghat,
-                       float* lcell, unsigned* ccell, hipStream_t st);
-int score_recon(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* pos_rowptr, const int32_t* pos_col,
-                const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg, int block_rows, double* loss,
-                int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st);
+void score_recon_form(int N, int K, int d, dl_dtype dt, int block_rows, int* out);
+size_t score_recon_workspace_bytes(int N, int K, int d, dl_dtype dt, int block_rows);
+void score_recon_strip(const __bf16* cz, const __bf16* ch, dl_dtype dt, int N, int K, int d, float t, int q0, int rows,
+                       const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* ig_rowptr, const int32_t* ig_col, float w_pos,
+                       float w_neg, float* ghat, float* lcell, unsigned* ccell, hipStream_t st);
+int score_recon(const void* Z, const void* H, int N, int K, int d, dl_dtype dt, float t, const int32_t* pos_rowptr,
+                const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg, int block_rows,
+                double* loss, int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st);
 
 // ranking of all candidates of query rows on the matrix cores (dl_score_rank.hip): fp32 tables, 1 <= d <= 128
 bool score_rank_supported(int K, int d);

@@ -39,6 +39,13 @@ constexpr int WLD = VH + 8;                    // its row pitch (144 bytes: conf
 constexpr int WIMG = 3 * TT * WLD;             // one weight: [3 planes][128 u][WLD]
 constexpr size_t LDS_BYTES = (size_t)4 * STAGE * sizeof(__bf16);
 static_assert(2 * WIMG <= 4 * STAGE, "the weight images alias the Gram staging buffers");
+// One-plane tables (P = 1, bf16): the staging buffers are a third of that, [2][1][128][SLD] per operand, while the weights are
+// fp32 values formed in registers and keep their three planes: the two weight images no longer fit over the staging buffers,
+// so the dynamic LDS of a form is the larger of the two and the images still start where the staging buffers start.
+constexpr size_t lds_bytes(int P) { return sizeof(__bf16) * (size_t)std::max(4 * (STAGE / 3) * P, 2 * WIMG); }
+static_assert(lds_bytes(3) == LDS_BYTES, "the three-plane form keeps its LDS");
+static_assert(lds_bytes(1) == sizeof(__bf16) * (size_t)2 * WIMG && 4 * (STAGE / 3) <= 2 * WIMG && lds_bytes(1) <= LDS_BYTES,
+              "one plane: the weight images cover the Gram staging buffers, and the form needs no more LDS than three planes");
 constexpr int KB = TT / 16;                    // K = 16 blocks of a v tile
 
 // ---- 1. G^ = G + G^T, G = g o p o (1 - p), zero-filled out to Np x Np ---------------------------------------------
@@ -108,6 +115,33 @@ __global__ __launch_bounds__(256) void split_cols_kernel(ColsJob j) {
     }
 }
 
+// The same operand order from bf16 tables, which are their own single plane: [v tile][kb (8)][c (dp)][16 v], no arithmetic on
+// the values.  Zero outside N and d; the same grid, the same coalesced reads through LDS and 16-byte stores.
+struct CopyColsJob { const __bf16* Z; const __bf16* H; __bf16* zT; __bf16* hT; int N, K, d, dp; size_t batch; };
+__global__ __launch_bounds__(256) void copy_cols_kernel(CopyColsJob j) {
+    __shared__ __bf16 tile[TT][34];                             // 17-word rows: the column reads below spread over the banks
+    const int ncb = j.dp / 32;
+    const int vt = blockIdx.x / ncb, cb = blockIdx.x % ncb, k = blockIdx.y;
+    const __bf16* __restrict__ src = (blockIdx.z ? j.H : j.Z) + (size_t)k * j.d;
+    __bf16* __restrict__ dst = (blockIdx.z ? j.hT : j.zT) + (size_t)k * j.batch;
+    const int ld = j.K * j.d;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int idx = threadIdx.x + 256 * i, r = idx >> 5, c = idx & 31;
+        const int v = vt * TT + r, col = cb * 32 + c;
+        tile[r][c] = (v < j.N && col < j.d) ? src[(size_t)v * ld + col] : (__bf16)0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int idx = threadIdx.x + 256 * i, half = idx & 1, c = (idx >> 1) & 31, kb = idx >> 6;
+        bf16x8 p;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) p[e] = tile[kb * 16 + 8 * half + e][c];
+        *reinterpret_cast<bf16x8*>(dst + ((size_t)(vt * KB + kb) * j.dp + cb * 32 + c) * 16 + half * 8) = p;
+    }
+}
+
 // ---- 3. the main kernel -------------------------------------------------------------------------------------------
 struct BwdArgs {
     const __bf16 *zp, *hp;     // row planes (split_rows): per factor plane_array_elems(N, d, 32) elements
@@ -124,26 +158,34 @@ struct BwdArgs {
 
 // NCB: 32-column chunks of the padded factor width.  STRIP (dl_score_recon.hip): the launch covers the u tiles from ut0 on
 // and ghat holds their rows only; everything a workgroup computes for its u tile is the same.
-template <int NCB, bool STRIP = false>
+// P: planes per table operand, 3 (fp32 tables) or 1 (bf16 tables: copy_rows / copy_cols_kernel planes, batch = Np dp).  With one
+// plane the Gram products are gram_block<1> and the second products weight (3 planes) x table^T (1 plane) = mfma_split3: on
+// bf16-exact finite tables the bits of the three-plane form, which multiplies the same values against planes of zeros.
+template <int NCB, bool STRIP = false, int P = 3>
 __global__ __launch_bounds__(BTHR) void score_dense_bwd_kernel(BwdArgs A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][3][TT][SLD]
-    __bf16* vs = us + 2 * STAGE;
+    constexpr int PSTAGE = P * TT * SLD;                       // one staged operand tile of this form (STAGE for P = 3)
+    __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][P][TT][SLD]
+    __bf16* vs = us + 2 * PSTAGE;
     __bf16* wim = us;                                          // [2 weights][3][TT][WLD], aliasing us / vs between Gram phases
     constexpr int nd = NCB, steps = 2 * nd, dp = 32 * NCB;
     const int nvt = A.Np / TT;
     const int slice = blockIdx.x % A.nslice, rest = blockIdx.x / A.nslice;
-    const int k = rest % A.K, ut = STRIP ? A.ut0 + rest / A.K : rest / A.K;
+    const int k0 = rest % A.K, ut_0 = STRIP ? A.ut0 + rest / A.K : rest / A.K;
+    // (one plane: the division runs on the vector unit; its uniform results go to scalar registers, see `wave` below)
+    const int k = P == 1 ? __builtin_amdgcn_readfirstlane(k0) : k0, ut = P == 1 ? __builtin_amdgcn_readfirstlane(ut_0) : ut_0;
     const int vt_beg = (int)((long long)slice * nvt / A.nslice), vt_end = (int)((long long)(slice + 1) * nvt / A.nslice);
     const int u0 = ut * TT;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    // (one plane: the wave index as a scalar, so that what depends on it alone — the table pointer of the second products, the
+    // store pointer, row offsets — lives in scalar registers; the three-plane forms keep their text as measured)
+    const int tid = threadIdx.x, wave = P == 1 ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6, lane = tid & 63;
     const int li = lane & 31, half = lane >> 5;
     const int wu = wave >> 1, wv = wave & 1;                   // Gram: u quarter, v half; second products: u quarter, weight wv
     const __bf16* zsrc = A.zp + (size_t)k * A.batch;
     const __bf16* hsrc = A.hp + (size_t)k * A.batch;
     const __bf16* tsrc = (wv ? A.zT : A.hT) + (size_t)k * A.batch + (size_t)li * 16 + half * 8;
 
-    PlaneStage<BTHR, SDC> uq, vq;
+    PlaneStage<BTHR, SDC, P> uq, vq;
     static_assert(TT == PLANE_ROWS, "tiles of the plane arrays");
     f32x16 out[NCB];
 #pragma unroll
@@ -153,12 +195,12 @@ __global__ __launch_bounds__(BTHR) void score_dense_bwd_kernel(BwdArgs A) {
         auto fetch = [&](int s) {
             const __bf16* src = s < nd ? zsrc : hsrc;
             const int dc = s < nd ? s : s - nd;
-            uq.fetch(src + plane_tile<SDC>(ut, dc, nd), tid);
-            vq.fetch(src + plane_tile<SDC>(vt, dc, nd), tid);
+            uq.fetch(src + plane_tile<SDC, P>(ut, dc, nd), tid);
+            vq.fetch(src + plane_tile<SDC, P>(vt, dc, nd), tid);
         };
         auto stash = [&](int s) {
-            uq.stash(us + (s & 1) * STAGE, tid);
-            vq.stash(vs + (s & 1) * STAGE, tid);
+            uq.stash(us + (s & 1) * PSTAGE, tid);
+            vq.stash(vs + (s & 1) * PSTAGE, tid);
         };
         fetch(0);
         stash(0);                                               // (the previous tile's last barrier freed the buffers)
@@ -170,15 +212,30 @@ __global__ __launch_bounds__(BTHR) void score_dense_bwd_kernel(BwdArgs A) {
         __syncthreads();
         auto gram_step = [&](int s, auto last_tag) {
             constexpr bool LAST = decltype(last_tag)::value;
-            const __bf16* ub = us + (s & 1) * STAGE + (wu * 32 + li) * SLD + half * 8;
-            const __bf16* vb = vs + (s & 1) * STAGE + (wv * 64 + li) * SLD + half * 8;
+            const __bf16* ub = us + (s & 1) * PSTAGE + (wu * 32 + li) * SLD + half * 8;
+            const __bf16* vb = vs + (s & 1) * PSTAGE + (wv * 64 + li) * SLD + half * 8;
 #pragma unroll
             for (int kb = 0; kb < SDC / 16; ++kb) {
-                gram_block_split6(acc, ub, vb, kb);             // dl_tiles.h: the forward's products in the forward's order
+                gram_block<P>(acc, ub, vb, kb);                 // dl_tiles.h: the forward's products in the forward's order
                 if (kb == 0) {
                     if constexpr (!LAST) {
                         stash(s + 1);
                         fetch(min(s + 2, steps - 1));           // unconditional: see TileStage (dl_tiles.h)
+                    } else if constexpr (P == 1) {
+                        // One plane frees 2 staging registers, not 24, for the 32 values of G^.  Each address is a uniform
+                        // 64-bit row pointer (scalar registers) plus ONE 32-bit lane offset — 4 ((4 half) Np + column) < 32 Np bytes,
+                        // far under 2^32 for every N <= DL_SCORE_RECON_MAX_N — instead of a 64-bit address per row, which
+                        // is what keeps this form out of scratch.
+                        const float* gb = A.ghat + (size_t)((STRIP ? u0 - A.ut0 * TT : u0) + wu * 32) * A.Np + (size_t)vt * TT + wv * 64;
+                        unsigned go = 4u * ((unsigned)(4 * half) * (unsigned)A.Np + (unsigned)li);      // in bytes
+                        asm volatile("" : "+v"(go));            // (formed here: folded into a pointer outside the loop, it is 64-bit again)
+#pragma unroll
+                        for (int bb = 0; bb < 2; ++bb)
+#pragma unroll
+                            for (int q = 0; q < 16; ++q) {
+                                const float* row = gb + (size_t)((q & 3) + 8 * (q >> 2)) * A.Np + bb * 32;
+                                gh[bb][q] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(row) + go);
+                            }
                     } else {                                    // the staging registers are free: G^ arrives under the last products
                         const float* gp = A.ghat + (size_t)((STRIP ? u0 - A.ut0 * TT : u0) + wu * 32 + 4 * half) * A.Np + (size_t)vt * TT + wv * 64 + li;
 #pragma unroll
@@ -230,7 +287,7 @@ __global__ __launch_bounds__(BTHR) void score_dense_bwd_kernel(BwdArgs A) {
             __syncthreads();
             // A = weight wv, rows of this u quarter, 16 v per block; B = the v rows of H_k (wv = 0) / Z_k (wv = 1), transposed
             const __bf16* wa = wim + wv * WIMG + (wu * 32 + li) * WLD + half * 8;
-            const __bf16* tb = tsrc + (size_t)(vt * KB + hv * (VH / 16)) * 3 * dp * 16;
+            const __bf16* tb = tsrc + (size_t)(vt * KB + hv * (VH / 16)) * P * dp * 16;
 #pragma unroll
             for (int kb = 0; kb < VH / 16; ++kb) {
                 bf16x8 a[3];
@@ -238,11 +295,15 @@ __global__ __launch_bounds__(BTHR) void score_dense_bwd_kernel(BwdArgs A) {
                 for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(wa + p * TT * WLD + kb * 16);
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb) {
-                    bf16x8 b[3];
+                    if constexpr (P == 3) {
+                        bf16x8 b[3];
 #pragma unroll
-                    for (int p = 0; p < 3; ++p)
-                        b[p] = *reinterpret_cast<const bf16x8*>(tb + ((kb * 3 + p) * dp + cb * 32) * 16);
-                    mfma_split6(out[cb], a, b);                 // six products, smallest terms first
+                        for (int p = 0; p < 3; ++p)
+                            b[p] = *reinterpret_cast<const bf16x8*>(tb + ((kb * 3 + p) * dp + cb * 32) * 16);
+                        mfma_split6(out[cb], a, b);             // six products, smallest terms first
+                    } else {                                    // the table is its own plane: the three products against it
+                        mfma_split3(out[cb], a, *reinterpret_cast<const bf16x8*>(tb + (kb * dp + cb * 32) * 16));
+                    }
                 }
             }
             __syncthreads();
@@ -250,12 +311,18 @@ __global__ __launch_bounds__(BTHR) void score_dense_bwd_kernel(BwdArgs A) {
     }
     // out[cb]: lane = column c, registers = u rows.  Every (u < N, k, c < d) is written by exactly one lane.
     float* dst = (wv ? A.dZ : A.dH) + (size_t)slice * A.slice_stride;
+    int sli = li, shalf = half;                                 // the lane's column and row half of the stores
+    if constexpr (P == 1) {                                     // read anew (every lane is active here): nothing of the lane index
+        const int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));     // is kept across the v loop
+        sli = l & 31;
+        shalf = l >> 5;
+    }
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
-        const int c = cb * 32 + li;
+        const int c = cb * 32 + sli;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int u = u0 + wu * 32 + acc_row(q, half);
+            const int u = u0 + wu * 32 + acc_row(q, shalf);
             if (u < A.N && c < A.d) dst[((size_t)u * A.K + k) * A.d + c] = out[cb][q];
         }
     }
@@ -334,6 +401,14 @@ void dense_bwd_cols(const float* Z, const float* H, int N, int K, int d, __bf16*
                        ColsJob{Z, H, zT, hT, N, K, d, dp, plane_array_elems(N, d, SDC)});
 }
 
+// ... of bf16 tables: the one plane, K * plane_array_elems<1>(N, d, 32) elements each
+void copy_cols(const __bf16* Z, const __bf16* H, int N, int K, int d, __bf16* zT, __bf16* hT, hipStream_t st) {
+    using namespace dense_bwd;
+    const int nt = (int)round_up(N, TT) / TT, dp = (int)round_up(d, SDC);
+    hipLaunchKernelGGL(copy_cols_kernel, dim3((unsigned)(nt * (dp / SDC)), (unsigned)K, 2u), dim3(256), 0, st,
+                       CopyColsJob{Z, H, zT, hT, N, K, d, dp, plane_array_elems<1>(N, d, SDC)});
+}
+
 int dense_bwd_nslice(int N, int K) { return dense_bwd::slices(N, K); }
 
 // floats of the slices' partial sums (0 where the v range is not cut)
@@ -345,14 +420,16 @@ size_t dense_bwd_part_floats(int N, int K, int d) {
 // Stage 3 over the u tiles [ut0, ut0 + n_ut): ghat = the Np-wide rows of G^ from row ut0 * 128 on (`strip`), or the whole
 // matrix (ut0 = 0, n_ut = Np / 128: the dense entry's instantiation).  The v range is cut into dense_bwd_nslice(N, K) slices whatever the u range; with more than
 // one, the rows of the launch go to `part` (dense_bwd_part_floats) and dense_bwd_combine sums them once every row is there.
-void dense_bwd_tiles(const __bf16* zp, const __bf16* hp, const __bf16* zT, const __bf16* hT, const float* ghat, int N, int K, int d,
-                     float t, int ut0, int n_ut, bool strip, float* part, float* dZ, float* dH, hipStream_t st) {
+// dt = DL_BF16: zp .. hT are one-plane arrays (copy_rows, copy_cols) and the launch is the one-plane form, which exists as a
+// strip launch only (the whole matrix is the strip from ut0 = 0).
+void dense_bwd_tiles(const __bf16* zp, const __bf16* hp, const __bf16* zT, const __bf16* hT, dl_dtype dt, const float* ghat, int N,
+                     int K, int d, float t, int ut0, int n_ut, bool strip, float* part, float* dZ, float* dH, hipStream_t st) {
     using namespace dense_bwd;
     const int ncb = (int)round_up(d, SDC) / SDC, nslice = slices(N, K);
     const size_t n = (size_t)N * K * d;
     BwdArgs A;
     A.zp = zp; A.hp = hp; A.zT = zT; A.hT = hT;
-    A.batch = plane_array_elems(N, d, SDC);
+    A.batch = scan::table_plane_elems(dt, N, d);
     A.ghat = ghat;
     A.N = N; A.Np = (int)round_up(N, TT); A.K = K; A.d = d;
     A.ut0 = ut0;
@@ -364,7 +441,8 @@ void dense_bwd_tiles(const __bf16* zp, const __bf16* hp, const __bf16* zT, const
     const unsigned grid = (unsigned)((size_t)n_ut * K * nslice);
 #define DL_LAUNCH_BWD(NCB)                                                                                               \
     do {                                                                                                                 \
-        if (strip) scan::launch_lds<score_dense_bwd_kernel<NCB, true>>(grid, BTHR, LDS_BYTES, st, A);                    \
+        if (dt == DL_BF16) scan::launch_lds<score_dense_bwd_kernel<NCB, true, 1>>(grid, BTHR, lds_bytes(1), st, A);      \
+        else if (strip) scan::launch_lds<score_dense_bwd_kernel<NCB, true>>(grid, BTHR, LDS_BYTES, st, A);               \
         else scan::launch_lds<score_dense_bwd_kernel<NCB>>(grid, BTHR, LDS_BYTES, st, A);                                \
     } while (0)
     switch (ncb) {
@@ -397,7 +475,7 @@ int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d
     project::split_rows(Z, K, N, d, K * d, (size_t)d, zp, st);
     project::split_rows(H, K, N, d, K * d, (size_t)d, hp, st);
     dense_bwd_cols(Z, H, N, K, d, zT, hT, st);
-    dense_bwd_tiles(zp, hp, zT, hT, ghat, N, K, d, t, 0, L.Np / TT, false, part, dZ, dH, st);
+    dense_bwd_tiles(zp, hp, zT, hT, DL_F32, ghat, N, K, d, t, 0, L.Np / TT, false, part, dZ, dH, st);
     dense_bwd_combine(part, N, K, d, dZ, dH, st);
     return check_launch("score_allpairs_bwd_dense");
 }

@@ -79,11 +79,14 @@ template <> struct ModeArgs<RECON> { typedef ReconArgs type; };
 // exclusion mask, per-row bookkeeping, per-wave compaction scratch.  The epilogue passes each wave's logits through 4 KiB of
 // LDS: with three planes that is the staging image the step has finished reading (30 KiB, four waves each); a one-plane
 // image (10 KiB) is too small for that, so the one-plane instantiations keep 8 x 4 KiB of their own behind the images.
+// RECON's epilogue reads its values back transposed and keeps a pitch of its own (RPITCH), a little more per wave: `recon`.
 constexpr size_t LG_WAVE = 16 * DL_WAVE;                       // floats per wave
-constexpr size_t lg_bytes(int P) { return P == 3 ? 0 : 8 * LG_WAVE * 4; }
-constexpr size_t lds_bytes(int P) {
-    return (size_t)2 * 2 * P * TT * SLD * 2 + lg_bytes(P) + TT * 4 * 4 + 6 * TT * 4 + TT * 8 + 8 * MAX_CAP * 8;
+constexpr int RPITCH = DL_WAVE + 1, RLG = 16 * RPITCH;         // RECON: the pitch and the floats per wave (recon_epilogue)
+constexpr size_t lg_bytes(int P, bool recon = false) { return P == 3 ? 0 : 8 * (recon ? (size_t)RLG : LG_WAVE) * 4; }
+constexpr size_t lds_bytes(int P, bool recon = false) {
+    return (size_t)2 * 2 * P * TT * SLD * 2 + lg_bytes(P, recon) + TT * 4 * 4 + 6 * TT * 4 + TT * 8 + 8 * MAX_CAP * 8;
 }
+static_assert(lds_bytes(1, true) % 16 == 0 && lg_bytes(3, true) == 0, "RECON: three planes as before, one plane aligned");
 static_assert(lds_bytes(3) % 16 == 0 && lds_bytes(1) % 16 == 0 && lds_bytes(3) + FILTER_LDS_BYTES <= 160 * 1024, "LDS of a CU");
 static_assert(4 * LG_WAVE * 4 <= (size_t)3 * TT * SLD * 2, "four waves' logits fit a three-plane image");
 
@@ -191,7 +194,6 @@ __device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, 
 // (lg: RLG floats of the wave's own, pitch 65: the transposed read below is conflict-free); the loss terms come back the
 // same way and the 128 terms of a row are added in one fixed order — 16 consecutive columns by one lane, the two halves of a
 // 32-column block, the two blocks of a wave, the two waves — so a cell is a function of its logits alone.  Counts: ballots.
-constexpr int RPITCH = DL_WAVE + 1, RLG = 16 * RPITCH;
 static_assert(4 * RLG * 4 <= 3 * TT * SLD * 2, "four waves' terms fit a three-plane image");
 __device__ __forceinline__ void recon_epilogue(const ReconArgs& A, const f32x16 (&term)[2], float* lg, unsigned* pom, unsigned* scr,
                                                int* pocur, int* igcur, const int* rnode, int qt, int ct, int nt, int tid) {
@@ -274,7 +276,7 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(typename ModeArgs<MODE>
     __bf16* us = reinterpret_cast<__bf16*>(lds);               // [2][P][TT][SLD]
     __bf16* vs = us + 2 * P * TT * SLD;
     float* lgs = reinterpret_cast<float*>(vs + 2 * P * TT * SLD);         // P = 1: [8][LG_WAVE], see lg_bytes
-    unsigned* exm = reinterpret_cast<unsigned*>(lgs + lg_bytes(P) / 4);   // [TT][4]: excluded columns of the tile
+    unsigned* exm = reinterpret_cast<unsigned*>(lgs + lg_bytes(P, MODE == RECON) / 4);   // [TT][4]: excluded columns of the tile
     int* cnt = reinterpret_cast<int*>(exm + TT * 4);           // TOPK: keys in the row's list
     int* srt = cnt + TT;                                        // TOPK: of which sorted
     int* excur = srt + TT;                                      // next exclusion entry of the row
@@ -451,7 +453,8 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(typename ModeArgs<MODE>
                 }
             }
         } else if constexpr (MODE == RECON) {
-            float* lg = reinterpret_cast<float*>((wave < 4 ? us : vs) + (s & 1) * 3 * TT * SLD) + (wave & 3) * (3 * TT * SLD / 8);
+            float* lg = P == 3 ? reinterpret_cast<float*>((wave < 4 ? us : vs) + (s & 1) * 3 * TT * SLD) + (wave & 3) * (3 * TT * SLD / 8)
+                               : lgs + wave * RLG;              // one plane: the wave's own RLG floats behind the images
             recon_epilogue(A, term, lg, exm, reinterpret_cast<unsigned*>(scr), excur, cnt, rnode, qt, ct0 + s / per_tile, nt, tid);
         } else {
             if (tid < TT) {                                     // this tile's excluded columns of row tid
@@ -835,12 +838,13 @@ int score_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, 
 // ---- the RECON scan of one strip of rows (dl_score_recon.hip drives it): rows [q0, q0 + rows) of the graph, q0 a multiple of
 // 128, as the query tiles — read where they stand in the plane arrays of Z and H, which are the candidates too — against all
 // candidate tiles.  ghat: rows x Np floats and the cells [rows rounded up to 128][Np / 128], all of it written.
-void score_recon_strip(const __bf16* cz, const __bf16* ch, int N, int K, int d, float t, int q0, int rows, const int32_t* pos_rowptr,
-                       const int32_t* pos_col, const int32_t* ig_rowptr, const int32_t* ig_col, float w_pos, float w_neg, float* ghat,
-                       float* lcell, unsigned* ccell, hipStream_t st) {
-    const RankPlan p = rank_plan(N, d, rows, 0);
+// dt: the planes are three per operand (DL_F32, split_rows) or the one of a bf16 table (DL_BF16, copy_rows): the P = 1 form.
+void score_recon_strip(const __bf16* cz, const __bf16* ch, dl_dtype dt, int N, int K, int d, float t, int q0, int rows,
+                       const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* ig_rowptr, const int32_t* ig_col, float w_pos,
+                       float w_neg, float* ghat, float* lcell, unsigned* ccell, hipStream_t st) {
+    const RankPlan p = rank_plan(N, d, rows, 0, dt);
     ReconArgs a = {};
-    const size_t first = plane_tile<SDC, 3>(q0 / TT, 0, p.nd);
+    const size_t first = dt == DL_BF16 ? plane_tile<SDC, 1>(q0 / TT, 0, p.nd) : plane_tile<SDC, 3>(q0 / TT, 0, p.nd);
     a.qz = cz + first; a.qh = ch + first; a.qbatch = p.cbatch;
     a.cz = cz; a.ch = ch; a.cbatch = p.cbatch;
     a.Q = rows; a.N = N; a.K = K; a.nd = p.nd; a.t = t;
@@ -850,7 +854,9 @@ void score_recon_strip(const __bf16* cz, const __bf16* ch, int N, int K, int d, 
     a.ig_rowptr = ig_rowptr; a.ig_col = ig_col;
     a.w_pos = w_pos; a.w_neg = w_neg;
     a.ghat = ghat; a.lcell = lcell; a.ccell = ccell;
-    launch_lds<rank_scan_kernel<RECON>>((unsigned)xcd_grid(p.qtiles, p.slices), RTHR, lds_bytes(3), st, a);
+    const unsigned grid = (unsigned)xcd_grid(p.qtiles, p.slices);
+    if (dt == DL_BF16) launch_lds<rank_scan_kernel<RECON, false, 1>>(grid, RTHR, lds_bytes(1, true), st, a);
+    else launch_lds<rank_scan_kernel<RECON>>(grid, RTHR, lds_bytes(3), st, a);
 }
 
 // ---- dl_score_pair_logits: the DIAG pass on its own, with the plane arrays of Z and H as BOTH sides: pair i = (row a[i] as

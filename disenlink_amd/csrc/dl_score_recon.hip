@@ -8,7 +8,8 @@
 //                                            pair contributes exactly 0).
 // The gradient depends on the pair alone, so G^ (dl_score_dense_bwd.hip) is formed where the logit is formed, one strip of
 // block_rows rows at a time:
-//   1. planes of Z, H (split_rows) and of their transposes (split_cols_kernel), once per call;
+//   1. planes of Z, H (split_rows) and of their transposes (split_cols_kernel), once per call — bf16 tables (DL_BF16) are
+//      their own single plane, copied into the same layouts (copy_rows, copy_cols_kernel), and 2. runs in its one-plane forms;
 //   2. per strip: the ranking scan in its RECON mode (dl_score_rank.hip) over the strip's rows against ALL candidate tiles
 //      writes the strip of G^ (zero for ignored pairs, the diagonal and outside N) and, per (row, candidate tile), one loss
 //      cell and one count cell, each exactly once; row_sum_kernel adds a row's cells in tile order (fp64, integers);
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const double* __restrict__ 
 }
 
 struct Plan { int Np, nt, block_rows, strips, nslice; size_t batch; };
-static Plan plan(int N, int K, int d, int block_rows) {
+static Plan plan(int N, int K, int d, dl_dtype dt, int block_rows) {
     Plan p;
     p.Np = (int)round_up(N, TT);
     p.nt = p.Np / TT;
@@ -88,11 +89,11 @@ static Plan plan(int N, int K, int d, int block_rows) {
     p.block_rows = std::min(block_rows, p.Np);
     p.strips = (p.Np + p.block_rows - 1) / p.block_rows;
     p.nslice = dense_bwd_nslice(N, K);
-    p.batch = plane_array_elems(N, d, SPLIT_COLS);
+    p.batch = table_plane_elems(dt, N, d);                     // the one thing of a plan that depends on the table type
     return p;
 }
 
-// Workspace (256-byte aligned blocks): planes of Z | H | Z^T | H^T (2 K 3 Np dp bytes each) | one strip of G^ (4 block_rows Np)
+// Workspace (256-byte aligned blocks): planes of Z | H | Z^T | H^T (2 K 3 Np dp bytes each; bf16 tables: 2 K Np dp) | one strip of G^ (4 block_rows Np)
 // | loss cells | count cells (4 block_rows Np / 128 each) | row losses (8 N) | row counts (16 N) | the dense backward's slice
 // partials (4 nslice 2 N K d, none for nslice = 1).  Nothing of size N x N.
 struct Ws {
@@ -125,34 +126,37 @@ static Ws carve(const Plan& p, int N, int K, int d, void* ws) {
 bool score_recon_supported(int K, int d) { return score_rank_supported(K, d) && dense_bwd_supported(d); }
 
 // out = Np, strips, rows per strip, slices of the dense backward's v range
-void score_recon_form(int N, int K, int d, int block_rows, int* out) {
-    const recon::Plan p = recon::plan(N, K, d, block_rows);
+void score_recon_form(int N, int K, int d, dl_dtype dt, int block_rows, int* out) {
+    const recon::Plan p = recon::plan(N, K, d, dt, block_rows);
     out[0] = p.Np;
     out[1] = p.strips;
     out[2] = p.block_rows;
     out[3] = p.nslice;
 }
 
-size_t score_recon_workspace_bytes(int N, int K, int d, int block_rows) {
-    return recon::carve(recon::plan(N, K, d, block_rows), N, K, d, nullptr).bytes;
+size_t score_recon_workspace_bytes(int N, int K, int d, dl_dtype dt, int block_rows) {
+    return recon::carve(recon::plan(N, K, d, dt, block_rows), N, K, d, nullptr).bytes;
 }
 
-int score_recon(const float* Z, const float* H, int N, int K, int d, float t, const int32_t* pos_rowptr, const int32_t* pos_col,
-                const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg, int block_rows, double* loss,
-                int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st) {
+// dt: the type of Z and H.  DL_BF16: the tables are their own single plane (copy_rows, copy_cols), the scan and the backward
+// run in their one-plane forms, everything behind them is the same.
+int score_recon(const void* Z, const void* H, int N, int K, int d, dl_dtype dt, float t, const int32_t* pos_rowptr,
+                const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg, int block_rows,
+                double* loss, int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st) {
     using namespace recon;
-    const Plan p = plan(N, K, d, block_rows);
+    const Plan p = plan(N, K, d, dt, block_rows);
     const Ws w = carve(p, N, K, d, ws);
-    project::split_rows(Z, K, N, d, K * d, (size_t)d, w.zp, st);
-    project::split_rows(H, K, N, d, K * d, (size_t)d, w.hp, st);
-    dense_bwd_cols(Z, H, N, K, d, w.zT, w.hT, st);
+    table_planes(Z, dt, nullptr, N, K, d, w.zp, st);
+    table_planes(H, dt, nullptr, N, K, d, w.hp, st);
+    if (dt == DL_BF16) copy_cols((const __bf16*)Z, (const __bf16*)H, N, K, d, w.zT, w.hT, st);
+    else dense_bwd_cols((const float*)Z, (const float*)H, N, K, d, w.zT, w.hT, st);
     for (int q0 = 0; q0 < N; q0 += p.block_rows) {
         const int rows = std::min(p.block_rows, N - q0);
-        score_recon_strip(w.zp, w.hp, N, K, d, t, q0, rows, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, w.ghat, w.lcell,
+        score_recon_strip(w.zp, w.hp, dt, N, K, d, t, q0, rows, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, w.ghat, w.lcell,
                           w.ccell, st);
         hipLaunchKernelGGL(row_sum_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, w.lcell, w.ccell, rows, p.nt, q0,
                            w.rowloss, w.rowcnt);
-        dense_bwd_tiles(w.zp, w.hp, w.zT, w.hT, w.ghat, N, K, d, t, q0 / TT, (rows + TT - 1) / TT, true, w.part, dZ, dH, st);
+        dense_bwd_tiles(w.zp, w.hp, w.zT, w.hT, dt, w.ghat, N, K, d, t, q0 / TT, (rows + TT - 1) / TT, true, w.part, dZ, dH, st);
     }
     dense_bwd_combine(w.part, N, K, d, dZ, dH, st);
     hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, w.rowloss, w.rowcnt, N, loss, counts);

@@ -156,6 +156,18 @@ __device__ __forceinline__ void mfma_split6(f32x16& acc, const bf16x8 (&a)[3], c
     acc = c;
 }
 
+// The same block with a B operand that IS bf16 (b[0] = the value, b[1] = b[2] = 0): the three products of mfma_split6 that
+// multiply b[0], in the order in which they stand there.  The three it leaves out (a[1] b[1], a[0] b[2], a[0] b[1]) would add
+// exact zeros to an accumulator that can never hold -0 — it starts at +0, and +0 + +-0 = +0, x + +-0 = x — so for finite
+// a and b both forms leave the same bits: the argument of gram_block<1> below, with three planes left on the A side.
+__device__ __forceinline__ void mfma_split3(f32x16& acc, const bf16x8 (&a)[3], const bf16x8& b) {
+    f32x16 c = acc;
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b, c, 0, 0, 0);
+    acc = c;
+}
+
 // One K = 16 block (kb) of a 128 x 128 tile Gram product A . B^T from two LDS plane images [3][128][SPLIT_PITCH]: the wave
 // that owns rows 32 wu .. 32 wu + 31 of A and rows 64 wv .. 64 wv + 63 of B passes ub = A image + (32 wu + lane % 32) rows
 // + 8 (lane / 32) and vb likewise (64 wv), and accumulates the two 32 x 32 blocks acc[0] (B rows + 0) and acc[1] (+ 32).

@@ -52,7 +52,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="the training loss: pairs = the reference's BCE on m sampled negatives per edge; recon = the "
                         "whole-graph reconstruction loss, every non-edge a negative and the edges up-weighted, with the "
                         "validation and test pairs ignored (Disentangle.forward_recon_loss: nothing of size N x N is formed; "
-                        "one GPU, fp32 tables, eager loop)")
+                        "one GPU, eager loop; with --table-dtype bf16 it runs on the bf16 tables the model is evaluated on)")
     p.add_argument("--pos-weight", type=float, default=None,
                    help="with --objective recon: the weight of a positive pair (default: negatives / positives)")
     p.add_argument("--recon-block-rows", type=int, default=None,
@@ -413,9 +413,9 @@ def main(argv=None):
                                args.predict_top is not None):
         raise SystemExit("--link-rule restricts the candidates of --rank-eval, --global-rank-eval, --mine and --predict-links: "
                          "give one of them")
-    if args.objective == "recon" and (args.gpus > 1 or args.table_dtype == "bf16" or args.graph):
-        raise SystemExit("--objective recon runs on one GPU with fp32 tables in the eager loop only (sharded, bf16 and "
-                         "graph-replayed reconstruction epochs are not implemented): drop --gpus / --table-dtype bf16 / --graph")
+    if args.objective == "recon" and (args.gpus > 1 or args.graph):
+        raise SystemExit("--objective recon runs on one GPU in the eager loop only, with fp32 or bf16 tables (sharded and "
+                         "graph-replayed reconstruction epochs are not implemented): drop --gpus / --graph")
     if args.gpus > 1:
         from .launch import launch_ranks, under_launcher
         if not under_launcher():                                    # BEFORE any GPU call: the parent starts and waits

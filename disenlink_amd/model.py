@@ -398,15 +398,20 @@ class Disentangle(nn.Module):
 
     def forward_recon_loss(self, x, graph: Graph, ignore=None, pos_weight=None, block_rows=None):
         """(emb [N,K*d], loss): the whole-graph reconstruction loss (ops.score_recon_loss) of project -> RouteAggregate ->
-        ops.ReconLoss — every pair of nodes that is not an edge of ``graph`` is a negative, the edges are up-weighted by
+        ops.ReconLoss (a bf16 module, ``table_dtype=torch.bfloat16``: project -> ops.HotPathRecon, one node that routes,
+        aggregates and scores on the bf16 tables the module is evaluated, ranked and mined on) — every pair of nodes that is not an edge of ``graph`` is a negative, the edges are up-weighted by
         ``pos_weight`` (default n_neg / n_pos), pairs in ``ignore`` (held-out validation / test pairs) carry no loss —
         with nothing of size N x N in memory.  ``graph``: the training graph the model routes over; its edges are the
         positives.  ``ignore`` may be a prepared ``ops.recon_sets(graph, ignore, N, device)``, which then supplies both
         sets and skips the normalisation (and its host read) per call.  No tile is skipped: a zero gradient against an
-        overflowed exp gives NaN, as with ``link_pred_backward="dense"``.  fp32 tables and d <= 128; anything else raises."""
+        overflowed exp gives NaN, as with ``link_pred_backward="dense"``.  d <= 128; anything else raises."""
         Z = self.project(x)
-        H = ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
         sets = ignore if isinstance(ignore, ops.ReconSets) else ops.recon_sets(graph, ignore, Z.shape[0], Z.device)
+        if self.table_dtype == torch.bfloat16:
+            H, loss = ops.HotPathRecon.apply(Z, graph, sets, float(self.beta), float(self.temperature), self.table_dtype,
+                                             pos_weight, block_rows)
+            return H.view(H.shape[0], -1), loss
+        H = ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
         loss = ops.ReconLoss.apply(Z, H, float(self.temperature), sets, pos_weight, block_rows)
         return H.view(H.shape[0], -1), loss
 

@@ -382,6 +382,35 @@ class HotPathPairsLoss(torch.autograd.Function):
         return dZ, None, None, None, None, None, None, None
 
 
+class HotPathRecon(torch.autograd.Function):
+    """Z [N,K,d] fp32 -> (emb [N,K,d] fp32, loss): route + aggregate + the whole-graph reconstruction loss as ONE autograd
+    node on tables stored as ``table_dtype`` — the step of a bf16 module, in the shape of ``HotPathPairsLoss``: the cast of Z
+    happens inside (so dZ comes back in fp32), H is routed and aggregated from THAT table, and ``score_recon_loss`` has the
+    gradients of the loss with respect to both tables ready when the forward returns.  The backward scales them by the
+    incoming d/dloss, adds a gradient arriving on ``emb`` to dH and continues into aggregation and routing.  ``sets``: a
+    prepared ``recon_sets(...)``; the device counts stand in ``ReconLoss.last_counts``."""
+
+    @staticmethod
+    def forward(ctx, Z, graph: Graph, sets: ReconSets, beta: float, t: float, table_dtype, pos_weight=None, block_rows=None):
+        ctx.set_materialize_grads(False)
+        Zt, p, a, s, H = step_tables(graph, Z, beta, t, table_dtype)
+        loss, dZs, dHs, counts = score_recon_loss(Zt, H, t, sets, None, pos_weight, block_rows, table_dtype=table_dtype)
+        ctx.graph, ctx.beta, ctx.t, ctx.p = graph, beta, t, p
+        ctx.save_for_backward(Zt, a, s, dZs, dHs)
+        ReconLoss.last_counts = counts
+        return H.float(), loss.to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g_emb, g_loss):
+        Zt, a, s, dZs, dHs = ctx.saved_tensors
+        if g_loss is not None:
+            dZ, dH = dZs * g_loss, dHs * g_loss
+        else:
+            dZ, dH = torch.zeros_like(dZs), torch.zeros_like(dHs)
+        _step_backward_tail(ctx, Zt, a, s, dZ, dH, g_emb)
+        return dZ, None, None, None, None, None, None, None
+
+
 class ScorePairs(torch.autograd.Function):
     """(Z, H) -> prob[P] at the listed pairs: model.py:109-113 + sigmoid."""
 

@@ -9,6 +9,11 @@ C = n_pos + n_neg the number of included pairs;  loss = sum w BCE(p, y) with F.b
 d loss / d s = w (p - y) in the one-pass scorer's form (saturated pairs contribute exactly 0).  No tile of the scan is
 skipped: a zero gradient against an overflowed exp(z.z / t) = inf gives NaN in dZ / dH, exactly as the dense backward
 (``score_allpairs_bwd_dense``) documents — it is the same kernel.
+
+bf16 tables (``table_dtype=torch.bfloat16``, the scans' keyword and convention): the tables are their own single bf16
+plane, so scan and backward issue 10 matrix-core products per (tile pair, factor, K block) instead of 36 and the workspace
+is 16 K Np dp bytes smaller (dl_score_recon_dtype with DL_BF16).  Every finite output has the bits of the fp32 call on the
+same tables widened to fp32; gradients are fp32, with respect to the rounded tables.
 """
 from __future__ import annotations
 
@@ -18,7 +23,7 @@ import torch
 
 from . import _lib
 from ._dev import _empty, _need_cuda, _nkd, _stream, _ws
-from .scans import _csr_args, _csr_rows, _exclusion_arg, exclusion_csr
+from .scans import _csr_args, _csr_rows, _exclusion_arg, _scan_dtype, exclusion_csr
 
 
 ReconSets = namedtuple("ReconSets", ["n_nodes", "pos_rowptr", "pos_col", "ign_rowptr", "ign_col", "n_pos", "n_neg", "n_ignored"])
@@ -75,10 +80,20 @@ def _sets_arg(positives, ignore, N: int, device) -> ReconSets:
     return recon_sets(positives, ignore, N, device)
 
 
-def _recon_tables(Z, H):
-    """fp32 [N,K,d] tables on the device with 1 <= d <= 128; anything else raises (there is no fallback)."""
-    if Z.dtype != torch.float32 or H.dtype != torch.float32:
-        raise TypeError(f"the reconstruction loss takes fp32 tables, got {Z.dtype} / {H.dtype}")
+def _recon_tables(Z, H, table_dtype=torch.float32):
+    """[N,K,d] tables on the device with 1 <= d <= 128 -> (Z, H, N, K, d, dl_dtype); anything else raises (there is no
+    fallback).  ``table_dtype=torch.float32`` (the default): fp32 tensors, nothing else.  ``torch.bfloat16``: Z and H are both
+    bf16 tensors, used as they are, or both fp32 tensors, rounded to nearest-even here (``scans._rank_tables``' rule)."""
+    dt = _scan_dtype(table_dtype)
+    if dt == _lib.DL_F32:
+        if Z.dtype != torch.float32 or H.dtype != torch.float32:
+            raise TypeError(f"the reconstruction loss takes fp32 tables, got {Z.dtype} / {H.dtype} "
+                            f"(bf16 tables: table_dtype=torch.bfloat16)")
+    else:
+        if Z.dtype != H.dtype or Z.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"table_dtype=torch.bfloat16 takes Z and H both bf16 or both fp32, got {Z.dtype} / {H.dtype}")
+        _need_cuda(Z, H)
+        Z, H = Z.to(torch.bfloat16), H.to(torch.bfloat16)
     _need_cuda(Z, H)
     N, K, d = _nkd(Z)
     if tuple(H.shape) != tuple(Z.shape):
@@ -86,7 +101,7 @@ def _recon_tables(Z, H):
     if N < 1 or not _lib.load().dl_score_recon_supported(K, d):
         raise _lib.DisenlinkHipError(f"the reconstruction loss serves N >= 1, K <= 64 and 1 <= d <= 128 (got N={N}, K={K}, "
                                      f"d={d}); there is no eager fallback")
-    return Z.contiguous(), H.contiguous(), N, K, d
+    return Z.contiguous(), H.contiguous(), N, K, d, dt
 
 
 def recon_weights(sets: ReconSets, pos_weight=None):
@@ -107,21 +122,24 @@ def _block_rows(block_rows) -> int:
     return b
 
 
-def score_recon_loss(Z, H, t: float, positives, ignore=None, pos_weight=None, block_rows=None):
+def score_recon_loss(Z, H, t: float, positives, ignore=None, pos_weight=None, block_rows=None, table_dtype=torch.float32):
     """-> (loss f64 [], dZ f32 [N,K,d], dH f32 [N,K,d], counts int64 [2]): the whole-graph reconstruction loss of the
     module docstring and its gradient with respect to the tables, by strips of ``block_rows`` rows (None: the largest
     multiple of 128 whose strip of G^ stays at or under 1 GiB — the whole graph where that fits).  ``positives`` /
     ``ignore``: unordered pair sets as ``pair_exclusion`` takes them, or ``positives`` = a prepared ``recon_sets(...)`` (then
     no host read happens here).  ``counts`` = the included positives and negatives the scan saw, DEVICE values to compare
     with the sets' ``n_pos`` / ``n_neg`` wherever the caller synchronises anyway (``check_recon_counts``).  fp32 tables
-    with 1 <= d <= 128, anything else raises.  No float atomics, no host read and no synchronisation in the call; launches
-    follow the current stream; the same bits on every call, for every ``block_rows`` and every DL_RANK_SLICES."""
-    Z, H, N, K, d = _recon_tables(Z, H)
+    with 1 <= d <= 128, anything else raises; ``table_dtype=torch.bfloat16``: bf16 tables (both tensors bf16, or both fp32 and
+    rounded to nearest-even here; a mix raises TypeError), the one-plane kernels, the bits of the fp32 call on the rounded
+    tables, and dZ / dH (fp32) with respect to the rounded tables.  No float atomics, no host read and no synchronisation in
+    the call; launches follow the current stream; the same bits on every call, for every ``block_rows`` and every
+    DL_RANK_SLICES."""
+    Z, H, N, K, d, dt = _recon_tables(Z, H, table_dtype)
     sets = _sets_arg(positives, ignore, N, Z.device)
-    return _recon_call(Z, H, N, K, d, float(t), sets, recon_weights(sets, pos_weight), _block_rows(block_rows))
+    return _recon_call(Z, H, N, K, d, float(t), sets, recon_weights(sets, pos_weight), _block_rows(block_rows), dt)
 
 
-def _recon_call(Z, H, N, K, d, t, sets, weights, block_rows):
+def _recon_call(Z, H, N, K, d, t, sets, weights, block_rows, dt=_lib.DL_F32):
     lib = _lib.load()
     dev = Z.device
     loss = _empty((1,), torch.float64, dev)
@@ -129,10 +147,10 @@ def _recon_call(Z, H, N, K, d, t, sets, weights, block_rows):
     dZ, dH = _empty(Z.shape, torch.float32, dev), _empty(Z.shape, torch.float32, dev)
     pr, pc, keep_p = _csr_args(sets.pos_rowptr, sets.pos_col, dev)
     ir, ic, keep_i = _csr_args(sets.ign_rowptr, sets.ign_col, dev)
-    ws = _ws.get(max(256, int(lib.dl_score_recon_workspace_bytes(N, K, d, block_rows))), dev)
-    _lib.check(lib.dl_score_recon(Z.data_ptr(), H.data_ptr(), N, K, d, t, pr, pc, ir, ic, weights[0], weights[1], block_rows,
-                                  loss.data_ptr(), counts.data_ptr(), dZ.data_ptr(), dH.data_ptr(), ws.data_ptr(), ws.numel(),
-                                  _stream()), "dl_score_recon")
+    ws = _ws.get(max(256, int(lib.dl_score_recon_workspace_bytes_dtype(N, K, d, dt, block_rows))), dev)
+    _lib.check(lib.dl_score_recon_dtype(Z.data_ptr(), H.data_ptr(), N, K, d, dt, t, pr, pc, ir, ic, weights[0], weights[1],
+                                        block_rows, loss.data_ptr(), counts.data_ptr(), dZ.data_ptr(), dH.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream()), "dl_score_recon_dtype")
     del keep_p, keep_i
     return loss.reshape(()), dZ, dH, counts
 
@@ -148,15 +166,17 @@ def check_recon_counts(counts, sets: ReconSets) -> None:
 
 class ReconLoss(torch.autograd.Function):
     """(Z, H) -> loss (fp32 scalar) of ``score_recon_loss``; the forward keeps dZ, dH and the backward scales them by the
-    incoming scalar.  ``sets``: a prepared ``recon_sets(...)``.  The device counts of the last forward stand in
-    ``ReconLoss.last_counts`` for ``check_recon_counts``."""
+    incoming scalar.  ``sets``: a prepared ``recon_sets(...)``.  ``table_dtype=torch.bfloat16``: the tables as
+    ``score_recon_loss`` takes them; the rounding passes the gradient straight through (as ``ops.HotPathPairs``).  The device
+    counts of the last forward stand in ``ReconLoss.last_counts`` for ``check_recon_counts``."""
     last_counts = None
 
     @staticmethod
-    def forward(ctx, Z, H, t: float, sets: ReconSets, pos_weight=None, block_rows=None):
-        Z, H, N, K, d = _recon_tables(Z, H)
+    def forward(ctx, Z, H, t: float, sets: ReconSets, pos_weight=None, block_rows=None, table_dtype=torch.float32):
+        Z, H, N, K, d, dt = _recon_tables(Z, H, table_dtype)
         sets = _sets_arg(sets, None, N, Z.device)
-        loss, dZ, dH, counts = _recon_call(Z, H, N, K, d, float(t), sets, recon_weights(sets, pos_weight), _block_rows(block_rows))
+        loss, dZ, dH, counts = _recon_call(Z, H, N, K, d, float(t), sets, recon_weights(sets, pos_weight), _block_rows(block_rows),
+                                           dt)
         ctx.save_for_backward(dZ, dH)
         ReconLoss.last_counts = counts
         return loss.to(torch.float32)
@@ -164,4 +184,4 @@ class ReconLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         dZ, dH = ctx.saved_tensors
-        return dZ * g, dH * g, None, None, None, None
+        return dZ * g, dH * g, None, None, None, None, None

@@ -498,6 +498,25 @@ int dl_score_recon(const float* Z, const float* H, int N, int K, int d, float t,
                    const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
                    int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
                    void* stream);
+/* The same on tables of either type: each entry has the argument list of the one above with `dtype` behind d, and the entries
+ * above are these with DL_F32.  DL_BF16: Z and H are bf16 [N][K][d]; each table is its own single plane, so the scan and the
+ * Gram products of the backward issue one matrix-core product per K = 16 block instead of six, and the backward's second
+ * products (fp32 weights, three planes, against a one-plane table) three instead of six.  loss, counts, dZ and dH keep their
+ * types (dZ, dH fp32: the gradient with respect to the bf16 values).
+ * Bits: for every output element (loss, counts, dZ, dH) that is finite in the DL_F32 call on the same tables widened to fp32,
+ * the DL_BF16 call returns the same bits — the products left out multiply planes that are identically zero and add exact
+ * zeros.  An element that is non-finite in one call is non-finite in the other (which NaN or infinity is not promised); the
+ * "no tile is skipped" NaN of an overflowed exp is kept.
+ * Workspace: smaller than the DL_F32 one by exactly 16 K Np dp bytes (four plane arrays, each 6 K Np dp -> 2 K Np dp).
+ * Unchanged: the limits (dl_score_scan_supported(K, d, dtype) states those of the shape), the strip rule and the form, the
+ * determinism, the stream behaviour and the absence of atomics, host reads and synchronisation.  An unknown dtype is DL_E_ARG
+ * and 0 from dl_score_recon_workspace_bytes_dtype. */
+int dl_score_recon_form_dtype(int N, int K, int d, dl_dtype dtype, int block_rows, int* out);
+size_t dl_score_recon_workspace_bytes_dtype(int N, int K, int d, dl_dtype dtype, int block_rows);
+int dl_score_recon_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
+                         const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
+                         int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
+                         void* stream);
 
 /* Ranking of ALL candidate links of query nodes (an extension; the reference has no counterpart): the logit of the dense
  * scorer, s(u,v) = sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), for every

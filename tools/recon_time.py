@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""usage: tools/recon_time.py [--seconds S] [--shapes bench,penn94] [--out FILE]  -> JSON lines: the whole-graph
+"""usage: tools/recon_time.py [--seconds S] [--shapes bench,penn94] [--rows dense,bf16] [--out FILE]  -> JSON lines: the whole-graph
 reconstruction loss (ops.score_recon_loss) against the dense [N,N] path, interleaved in ONE process (HIP events; rounds
 that alternate between the candidates until each has run for S = 1 second in all after warm-up; the MEDIAN round counts):
   (a) score_recon_loss: loss, dZ, dH by strips, nothing of size N x N
@@ -14,7 +14,15 @@ dense forward uses.  The line says "met" when (a) <= 1.1 x that sum, else "misse
 GATE (exit status 1): peak allocation of (a) <= dl_score_recon_workspace_bytes + outputs + the allocator's rounding (torch's
 caching allocator rounds a block up to 512 bytes and hands out a whole fresh segment, a multiple of 2 MiB, when what would be
 left of it is 1 MiB or less: 2 MiB for each of the workspace, dZ and dH, 512 bytes for each of loss and counts), and below
-that of (c).  Any failing step ends the run there."""
+that of (c).  Any failing step ends the run there.
+The bf16 row of a size (--rows bf16; tools/scan_bf16_time.py's comparison for the scans): the bf16 entry
+(table_dtype=torch.bfloat16 on bf16 tensors) against the fp32 entry on the SAME rounded tables widened to fp32, interleaved
+the same way; time (median, best and worst round, every round listed), peak allocation and workspace bytes of both, and
+whether all four outputs have the same bits.  KEEP RULE (reported, no gate): worst bf16 round <= best fp32 round.
+PREDICTION (no gate; a lower bound on the bf16 time, there being no timing-bound split of these kernels into matrix-core
+time and the rest): fp32 time x 10 / 36, the ratio of the matrix-core products issued per (tile pair, factor, K block) —
+scan Gram 2 of 12, backward Gram 2 of 12, second products 6 of 12; exp, epilogue, the weights' split3, the LDS images
+and the G^ traffic are the same in both.  "met" when the bf16 median is within 1.1 x of it."""
 import json
 import os
 import statistics
@@ -50,7 +58,7 @@ def interleaved(cands, seconds, reps):
             ev[1].record()
             torch.cuda.synchronize()
             rounds[n].append(ev[0].elapsed_time(ev[1]) / reps[n])
-    return {n: (statistics.median(v), min(v), len(v) * reps[n]) for n, v in rounds.items()}
+    return {n: (statistics.median(v), min(v), len(v) * reps[n], v) for n, v in rounds.items()}
 
 
 def problem(N, seed):
@@ -150,21 +158,67 @@ def run(name, N, seconds):
     return line, gate
 
 
+def run_bf16(name, N, seconds):
+    Z, H, sets = problem(N, seed=N)
+    Zb, Hb = Z.to(torch.bfloat16), H.to(torch.bfloat16)
+    Zf, Hf = Zb.float(), Hb.float()
+    del Z, H
+
+    def f32():
+        return ops.score_recon_loss(Zf, Hf, T, sets)
+
+    def bf16():
+        return ops.score_recon_loss(Zb, Hb, T, sets, table_dtype=torch.bfloat16)
+
+    want, got = f32(), bf16()
+    ops.check_recon_counts(got[3], sets)
+    if not all(bool(torch.isfinite(x).all()) for x in want[:3]):
+        raise RuntimeError("non-finite result")
+    same = all(torch.equal(a.view(torch.int64 if a.dtype == torch.float64 else torch.int32 if a.dtype == torch.float32 else a.dtype),
+                           b.view(torch.int64 if b.dtype == torch.float64 else torch.int32 if b.dtype == torch.float32 else b.dtype))
+               for a, b in zip(want, got))
+    del want, got
+    reps = {"f32": 1 if N > 20000 else 5, "bf16": 1 if N > 20000 else 5}
+    r = interleaved({"f32": f32, "bf16": bf16}, seconds, reps)
+    peak = {"f32": peak_of(f32), "bf16": peak_of(bf16)}
+    lib = _lib.load()
+    ws = {"f32": int(lib.dl_score_recon_workspace_bytes_dtype(N, K, D, _lib.DL_F32, 0)),
+          "bf16": int(lib.dl_score_recon_workspace_bytes_dtype(N, K, D, _lib.DL_BF16, 0))}
+    Np, dp = -(-N // 128) * 128, -(-D // 32) * 32
+    predicted = r["f32"][0] * 10 / 36
+    line = {"row": "bf16", "shape": name, "N": N, "K": K, "d": D, "n_pos": sets.n_pos, "n_neg": sets.n_neg, "n_ignored": sets.n_ignored,
+            "f32_ms": round(r["f32"][0], 4), "bf16_ms": round(r["bf16"][0], 4), "bf16_over_f32": round(r["bf16"][0] / r["f32"][0], 3),
+            "best_round_ms": {n: round(v[1], 4) for n, v in r.items()}, "worst_round_ms": {n: round(max(v[3]), 4) for n, v in r.items()},
+            "rounds_ms": {n: [round(x, 4) for x in v[3]] for n, v in r.items()}, "repetitions_per_round": reps,
+            "keep_rule_worst_bf16_le_best_f32": bool(max(r["bf16"][3]) <= r["f32"][1]),
+            "predicted_lower_bound_bf16_ms": round(predicted, 4), "bf16_over_predicted": round(r["bf16"][0] / predicted, 3),
+            "prediction": "met" if r["bf16"][0] <= 1.1 * predicted else "missed",
+            "peak_bytes": peak, "workspace_bytes": ws, "workspace_difference": ws["f32"] - ws["bf16"],
+            "workspace_difference_is_16_K_Np_dp": ws["f32"] - ws["bf16"] == 16 * K * Np * dp, "same_bits": bool(same),
+            "measured": "HIP events, interleaved rounds in one process, >= %.1f s per candidate after warm-up; peaks from "
+                        "torch.cuda.max_memory_allocated in a pass of their own" % seconds}
+    return line, bool(same)
+
+
 def main():
     arg = lambda k, dflt: sys.argv[sys.argv.index(k) + 1] if k in sys.argv else dflt
     seconds = float(arg("--seconds", "1.0"))
     out = arg("--out", None)
     ok = True
+    rows = arg("--rows", "dense,bf16").split(",")
     for name in arg("--shapes", "bench,penn94").split(","):
-        line, gate = run(name, SHAPES[name], seconds)
-        text = json.dumps(line)
-        print(text, flush=True)
-        if out:
-            with open(out, "a") as fh:
-                fh.write(text + "\n")
-        ok = ok and gate
-        _dev._ws.buf.clear()
-        torch.cuda.empty_cache()
+        for row, fn in (("dense", run), ("bf16", run_bf16)):
+            if row not in rows:
+                continue
+            line, gate = fn(name, SHAPES[name], seconds)
+            text = json.dumps(line)
+            print(text, flush=True)
+            if out:
+                with open(out, "a") as fh:
+                    fh.write(text + "\n")
+            ok = ok and gate
+            _dev._ws.buf.clear()
+            torch.cuda.empty_cache()
     return 0 if ok else 1
 
 
