@@ -224,6 +224,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
 // rows nowhere else (disenlink_hip.h; graph.HubPlan.check refuses a plan that does before it is bound), so a full step has no
 // sign test and no zero fill of gather registers, and a wave requests the plan words of its next step while it works on
 // the current one.
+// Without per-factor terms (COEF == false) a step ends at its logit: a step yields 4 of them and a wave has 64 lanes, so the
+// wave keeps the logits of 16 steps in its lanes and runs ONE sigmoid and ONE store pass per batch (and one behind its last
+// step), with pair ids it read per lane when the batch opened — no second expf, no IEEE division, no pair-id selects and no
+// store on the chain a wave must finish before its next gathers go out (the scorer alone on squirrel: 116.9 -> 112.1 us; with the
+// bank-masked reduction below 107.8, profiles/r13_fwd_hub_tail.txt).
 // The base name is that kernel's on purpose: the per-phase accounting of the benchmark matches kernels by base name.
 namespace hub {
 constexpr int WAVES = 8, THREADS = WAVES * DL_WAVE;
@@ -241,6 +246,52 @@ struct StepWords {
     dl_vi4 v, u, q, p;
 };
 
+// TransposedReduce<16, 8> with the stages OFF = 8 and OFF = 4 as two bank-masked DPP adds per output: the select bit of a
+// stage is constant within a bank of 4 lanes, so "keep + (send of lane ^ OFF)" is one add written under the banks whose bit is
+// clear and one under the others — the same two addends per lane (IEEE addition commutes: the same bits), without the two
+// v_cndmask per output and, at OFF = 4, without the v_mov_dpp.  The builtins cannot say "the second add keeps the lanes of the
+// first", hence asm; one statement per stage, outputs early-clobber, and an s_nop 1 at its head: the hazard recogniser does not
+// see inside asm, and a DPP read of a VGPR needs two wait states behind the VALU write of it (store4_sc1 is the precedent).
+// Every lane must be active.
+__device__ __forceinline__ void transposed_reduce16_masked(float* v, int c) {
+    float a[8], b[4];
+    asm volatile("s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %8, %8 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+                 "v_add_f32_dpp %1, %9, %9 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+                 "v_add_f32_dpp %2, %10, %10 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+                 "v_add_f32_dpp %3, %11, %11 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+                 "v_add_f32_dpp %4, %12, %12 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+                 "v_add_f32_dpp %5, %13, %13 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+                 "v_add_f32_dpp %6, %14, %14 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+                 "v_add_f32_dpp %7, %15, %15 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+                 "v_add_f32_dpp %0, %16, %16 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+                 "v_add_f32_dpp %1, %17, %17 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+                 "v_add_f32_dpp %2, %18, %18 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+                 "v_add_f32_dpp %3, %19, %19 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+                 "v_add_f32_dpp %4, %20, %20 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+                 "v_add_f32_dpp %5, %21, %21 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+                 "v_add_f32_dpp %6, %22, %22 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+                 "v_add_f32_dpp %7, %23, %23 row_ror:8 row_mask:0xf bank_mask:0xc"
+                 : "=&v"(a[0]), "=&v"(a[1]), "=&v"(a[2]), "=&v"(a[3]), "=&v"(a[4]), "=&v"(a[5]), "=&v"(a[6]), "=&v"(a[7])
+                 : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]), "v"(v[9]),
+                   "v"(v[10]), "v"(v[11]), "v"(v[12]), "v"(v[13]), "v"(v[14]), "v"(v[15]));
+    asm volatile("s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %4, %4 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+                 "v_add_f32_dpp %1, %5, %5 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+                 "v_add_f32_dpp %2, %6, %6 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+                 "v_add_f32_dpp %3, %7, %7 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+                 "v_add_f32_dpp %0, %8, %8 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+                 "v_add_f32_dpp %1, %9, %9 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+                 "v_add_f32_dpp %2, %10, %10 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+                 "v_add_f32_dpp %3, %11, %11 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+                 "s_nop 1"                                           // the next stage's DPP reads are the compiler's: it does not know of these writes
+                 : "=&v"(b[0]), "=&v"(b[1]), "=&v"(b[2]), "=&v"(b[3])
+                 : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = b[q];
+    TransposedReduce<4, 2>::run(v, c);
+}
+
 template <int K, int D, bool T1, bool COEF, bool FOLD>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void score_fwd_wave_kernel(
     dl_pair_hub h, const float* __restrict__ Z, const float* __restrict__ H, float t, float* __restrict__ prob,
@@ -249,6 +300,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
     constexpr int NJ = FW::NJ, U = FW::U, ROW = K * D, R4 = 2 * ROW / 4;      // R4: float4 of one [Z row | H row]
     static_assert(D == 64 && NJ >= 1 && U == 4 && U * NJ <= 8, "the step geometry of score_fwd_wave_kernel");
     static_assert(DL_HUB_W == 2 * WAVES, "every wave stages two rows of the block");
+    constexpr bool BATCH = !COEF;      // the forms with per-factor terms store per step and per lane anyway: they keep the per-step tail
     __shared__ __attribute__((aligned(16))) float4 urow[DL_HUB_W * R4];
     const int x = blockIdx.x % h.n_slices;
     const int it = h.slice_item0[x] + (int)(blockIdx.x / h.n_slices);
@@ -279,10 +331,43 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
     auto fetch = [&](const int step) {
         const int s = __builtin_amdgcn_readfirstlane(step);
         StepWords w;
-        w.v = plan_words(h.step_v, s), w.u = plan_words(h.step_u, s), w.q = plan_words(h.step_q, s);
-        w.p = dl_vi4{-1, -1, -1, -1};
-        if constexpr (FOLD) w.p = plan_words(h.step_q2, s);
+        w.v = plan_words(h.step_v, s), w.u = plan_words(h.step_u, s);
+        w.q = w.p = dl_vi4{-1, -1, -1, -1};
+        if constexpr (!BATCH) {                                      // a batched tail reads the pair ids per lane, once per 16 steps
+            w.q = plan_words(h.step_q, s);
+            if constexpr (FOLD) w.p = plan_words(h.step_q2, s);
+        }
         return w;
+    };
+    // BATCH: the pending logits of up to 16 of the wave's steps, one per lane — lane L holds slot L & 3 of the batch's step
+    // number L >> 2 (the steps s0, s0 + 8, ...).  nb (wave-uniform) counts the steps captured since the last flush.  The pair
+    // ids of a batch are asked for per lane when it opens, -1 for the steps past the item's end (a wave takes every step
+    // s0 + 8 b below s_end, so these are exactly the lanes that capture nothing), and are there long before the flush.
+    const int slot_step = lane >> 2;
+    float lg = 0.0f;
+    int nb = 0, pq = -1, pq2 = -1;
+    auto open = [&](const int s0) {
+        const int sb = s0 + WAVES * slot_step;
+        pq = pq2 = -1;
+        if (sb < s_end) {
+            pq = h.step_q[4 * sb + (lane & 3)];
+            if constexpr (FOLD) pq2 = h.step_q2[4 * sb + (lane & 3)];
+        }
+    };
+    auto flush = [&]() {                                             // one sigmoid and one store pass for the whole batch
+        const float p = sigmoid_ref(lg);
+        if (pq >= 0) prob[pq] = p;                                   // a dead slot's id is -1 in the plan, like a dead lane's here
+        if (FOLD && pq2 >= 0) prob[pq2] = p;
+    };
+    // behind every step: at 16 captured steps flush, and open the batch that starts with the wave's next step
+    auto tick = [&](const int step) {
+        if constexpr (BATCH) {
+            if (__builtin_expect(nb == 16, 0)) {
+                flush();
+                nb = 0;
+                open(step + WAVES);
+            }
+        }
     };
     // LAST: the step may hold dead partner rows.  Only the last step of a list does (disenlink_hip.h); every other step
     // gathers its NV rows without a test and without the zero fill of a dead row's registers, as the wave-per-entry kernel
@@ -330,30 +415,44 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        TransposedReduce<16, 8>::run(val, i);
+        transposed_reduce16_masked(val, i);                         // TransposedReduce<16, 8>::run(val, i) in fewer instructions
         const float mine_v = val[0];
         const float ex = expf(T1 ? mine_v : mine_v / t);
         const float ttv = mine_v * xor_lane<8>(ex);
         float term = ttv;
         if constexpr (NJ == 2) term += xor_lane<4>(ttv);
-        const float logit = add_xor<32>(add_xor<16>(term));
-        const float p = sigmoid_ref(logit);
-        const int e_me = i & 3;
-        const int qq = e_me == 0 ? sq[0] : e_me == 1 ? sq[1] : e_me == 2 ? sq[2] : sq[3];
-        const int qq2 = e_me == 0 ? sq2[0] : e_me == 1 ? sq2[1] : e_me == 2 ? sq2[2] : sq2[3];
-        const bool live = qq >= 0;
-        if (lane >= 8 && lane < 12 && live) {
-            prob[qq] = p;
-            if (FOLD && qq2 >= 0) prob[qq2] = p;
-        }
-        if constexpr (COEF) {
-            const int k = 4 * ((i & 7) >> 2) + r;
-            if (live && (NJ == 2 || (i & 7) < 4)) {
-                if (i < 8) coef_e[(size_t)qq * K + k] = ex;
-                else coef_q[(size_t)qq * K + k] = ttv;
-                if (FOLD && qq2 >= 0) {
-                    if (i < 8) coef_e[(size_t)qq2 * K + k] = ex;
-                    else coef_q[(size_t)qq2 * K + k] = ttv;
+        if constexpr (BATCH) {
+            // term is valid in the lanes 8..11 of a DPP row: copied under bank masks into the other lanes of the row, the two adds
+            // over the rows leave the logit of slot lane & 3 in EVERY lane — the same addends in the same order as in lanes
+            // 8..11 — and the lanes of this step's batch slot keep it.  (At NJ == 2 the lanes 12..15 hold the same two addends the
+            // other way round, but hipcc contracts `ttv + xor_lane<4>(ttv)` into an FMA on the lane's own product: the halves of
+            // the row differ in the last bit of some pairs, and only 8..11 are the reference's bits.)
+            int tb = __float_as_int(term);
+            tb = __builtin_amdgcn_update_dpp(tb, tb, 0x114, 0xF, 0x8, false);                             // row_shr:4 -> lanes 12..15
+            tb = __builtin_amdgcn_update_dpp(tb, tb, 0x128, 0xF, 0x3, false);                             // row_ror:8 -> lanes 0..7
+            const float logit = add_xor<32>(add_xor<16>(__int_as_float(tb)));
+            lg = slot_step == nb ? logit : lg;
+            ++nb;
+        } else {
+            const float logit = add_xor<32>(add_xor<16>(term));
+            const float p = sigmoid_ref(logit);
+            const int e_me = i & 3;
+            const int qq = e_me == 0 ? sq[0] : e_me == 1 ? sq[1] : e_me == 2 ? sq[2] : sq[3];
+            const int qq2 = e_me == 0 ? sq2[0] : e_me == 1 ? sq2[1] : e_me == 2 ? sq2[2] : sq2[3];
+            const bool live = qq >= 0;
+            if (lane >= 8 && lane < 12 && live) {
+                prob[qq] = p;
+                if (FOLD && qq2 >= 0) prob[qq2] = p;
+            }
+            if constexpr (COEF) {
+                const int k = 4 * ((i & 7) >> 2) + r;
+                if (live && (NJ == 2 || (i & 7) < 4)) {
+                    if (i < 8) coef_e[(size_t)qq * K + k] = ex;
+                    else coef_q[(size_t)qq * K + k] = ttv;
+                    if (FOLD && qq2 >= 0) {
+                        if (i < 8) coef_e[(size_t)qq2 * K + k] = ex;
+                        else coef_q[(size_t)qq2 * K + k] = ttv;
+                    }
                 }
             }
         }
@@ -375,11 +474,15 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
         if (step + WAVES < s_end) nxt = fetch(step + WAVES);
         return w;
     };
-    for (; s < s_b - 1; s += WAVES) do_step(take(s), SHAPE_A, FULL{});
-    if (s == s_b - 1) do_step(take(s), SHAPE_A, LAST{}), s += WAVES;
-    for (; s < s_c - 1; s += WAVES) do_step(take(s), SHAPE_B, FULL{});
-    if (s == s_c - 1) do_step(take(s), SHAPE_B, LAST{}), s += WAVES;
-    for (; s < s_end; s += WAVES) do_step(take(s), SHAPE_C, FULL{});        // a C step has no dead row
+    if constexpr (BATCH) open(s);
+    for (; s < s_b - 1; s += WAVES) do_step(take(s), SHAPE_A, FULL{}), tick(s);
+    if (s == s_b - 1) do_step(take(s), SHAPE_A, LAST{}), tick(s), s += WAVES;
+    for (; s < s_c - 1; s += WAVES) do_step(take(s), SHAPE_B, FULL{}), tick(s);
+    if (s == s_c - 1) do_step(take(s), SHAPE_B, LAST{}), tick(s), s += WAVES;
+    for (; s < s_end; s += WAVES) do_step(take(s), SHAPE_C, FULL{}), tick(s);        // a C step has no dead row
+    if constexpr (BATCH) {
+        if (nb > 0) flush();                                        // a wave with no step flushes nothing
+    }
 }
 }  // namespace hub
 
