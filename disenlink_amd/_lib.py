@@ -23,10 +23,6 @@ class DlCsrPlan(C.Structure):
     ]
 
 
-class DlGraph(C.Structure):
-    _fields_ = [("csr", DlCsrPlan), ("route", DlCsrPlan), ("rev", C.c_void_p), ("route_mirror", C.c_int32)]
-
-
 class DlPairHub(C.Structure):
     _fields_ = [("n_blocks", C.c_int32), ("block_row", C.c_void_p),
                 ("n_items", C.c_int32), ("n_slices", C.c_int32), ("slice_max_item", C.c_int32),
@@ -34,6 +30,11 @@ class DlPairHub(C.Structure):
                 ("n_steps", C.c_int32), ("step_v", C.c_void_p), ("step_u", C.c_void_p), ("step_q", C.c_void_p),
                 ("step_q2", C.c_void_p), ("n_entries", C.c_int32),
                 ("rest", DlCsrPlan), ("rest_pair", C.c_void_p), ("rest_pair2", C.c_void_p)]
+
+
+class DlGraph(C.Structure):
+    _fields_ = [("csr", DlCsrPlan), ("route", DlCsrPlan), ("rev", C.c_void_p), ("route_mirror", C.c_int32),
+                ("route_hub", C.POINTER(DlPairHub))]
 
 
 class DlPairIncidence(C.Structure):

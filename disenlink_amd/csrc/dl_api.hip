@@ -248,7 +248,23 @@ int dl_route_fwd(const dl_graph* g, const void* Z, int K, int d, dl_dtype dtype,
         if (mirror)
             DL_REQUIRE((g->rev != nullptr || c->n_entries == 0) && c->row_offset == 0 && c->n_rows == c->n_total,
                        "route_mirror needs rev and an unsharded plan");
-        return fast_route_fwd(c, have ? rp : nullptr, mirror, g->rev, Z, K, d, dtype, t, p, a, s, w.vec_part,
+        // optional hub plan over the mirrored entries (dl_graph.route_hub): the shapes with a hub form only, same bits
+        const dl_pair_hub* hp = nullptr;
+        if (g->route_hub != nullptr && mirror && config().route_hub && fast_route_hub_supported(K, d, dtype) &&
+            g->route_hub->n_items > 0) {
+            hp = g->route_hub;
+            // the plan must stand for the whole routing plan: no residual, and one live slot per entry with col >= row —
+            // (n_entries + self-loops) / 2 of them; the exact count is checked where the plan is bound (graph.py), here its range
+            DL_REQUIRE(hp->rest.n_entries == 0 && 2LL * hp->n_entries >= c->n_entries && hp->n_entries <= c->n_entries,
+                       "route_hub must hold each of the graph's entries with col >= row (%d entries in all) and no residual plan: "
+                       "it holds %d + %d", c->n_entries, hp->n_entries, hp->rest.n_entries);
+            DL_REQUIRE(hp->n_slices >= 1 && hp->slice_max_item >= 1 && hp->n_blocks >= 1 && hp->n_steps >= 1, "route_hub: empty grid");
+            DL_REQUIRE(hp->block_row && hp->slice_item0 && hp->item_block && hp->item_step && hp->step_v && hp->step_u &&
+                       hp->step_q && hp->step_q2, "route_hub: NULL array");
+            DL_REQUIRE((((uintptr_t)hp->step_v | (uintptr_t)hp->step_u | (uintptr_t)hp->step_q | (uintptr_t)hp->step_q2) & 15) == 0,
+                       "route_hub: step_v, step_u, step_q and step_q2 must be 16-byte aligned");
+        }
+        return fast_route_fwd(c, have ? rp : nullptr, mirror, g->rev, hp, Z, K, d, dtype, t, p, a, s, w.vec_part,
                               (hipStream_t)stream);
     }
     return generic_route_fwd(c, (const float*)Z, K, d, t, p, a, s, (hipStream_t)stream);

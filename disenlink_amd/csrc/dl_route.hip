@@ -60,6 +60,208 @@ __global__ __launch_bounds__(BLOCK, (K <= 8 && sizeof(T) == 4) ? 8 : (K <= 10 ? 
     }
 }
 
+// ---------------------------------------------------------------------------- route over a hub plan
+// The kernel above gathers one whole Z row per entry with col >= row and is bound by those bytes (15.6 TB/s out of the L2 on
+// squirrel).  On a skewed graph most of them are repeats: the routing hub plan (dl_graph.route_hub, graph.py) hands every
+// undirected edge to its endpoint of larger degree, cuts those owners into blocks of 16 rows, and a workgroup that holds a
+// block's Z rows in LDS (32 KB at K = 8) gathers a partner row ONCE for up to four of them — the geometry, the three step
+// shapes and the whole step structure of hub::score_fwd_wave_kernel (dl_score.hip): scalar row bases, the plan words of
+// the wave's next step requested one step ahead, every gather of a step issued before the first wait, a chunk's LDS reads
+// issued together.
+// Lane l holds float4 number j * 64 + l of a row: a DPP row of 16 lanes is one factor slice (factor 4 j + r, r = l >> 4), and
+// lane i of it holds the elements 4 i .. 4 i + 3 — the elements lane c = i of a group holds in the kernel above.
+// Bits.  A pair's results are those of the kernel above, operation for operation:
+//   - the partial of (factor, lane) is dl::fast::dot — x0 * y0, then three fmaf; symmetric in its rows, so it does not
+//     matter which endpoint is the block row;
+//   - the 16 partials of a factor are added by the butterfly in stage order 8, 4, 2, 1 (TransposedReduce: the same tree
+//     whichever value index a sum sits at; an add's operands may swap sides, IEEE addition commutes);
+//   - S = group_allreduce_sum<16> over the primary lanes there adds the factors as ((e_f + e_f^4) + (e_f^2 + e_f^6)) +
+//     ((e_f^1 + e_f^5) + (e_f^3 + e_f^7)) at K = 8 and (e_f + e_f^2) + (e_f^1 + e_f^3) at K = 4, then zeros; here factor
+//     bit 2 is the chunk (lane ^ 8), bit 1 the DPP row pair (lane ^ 32), bit 0 the DPP row (lane ^ 16): the same tree;
+//   - al = ex / S is the IEEE division, and the winner is the first maximal QUOTIENT under `beats` (a total preorder with
+//     ties to the lower factor: which lanes are compared in which order cannot change the winner).
+// A step ends at its reduction: 16 / NVAL = NB lanes of a DPP row then hold the same sum, so the wave keeps the sums of NB of
+// its steps side by side — lane i keeps those of the batch's step number i & (NB - 1) — and runs ONE tail (expf, S, division,
+// arg-max, stores) per NB steps and one behind its last step; none of the tail's exchanges (lane ^ 8, ^ 16, ^ 32) crosses
+// these lanes.  The chunk-0 lanes of DPP row 0 store (p, a) at the entry, those of row 1 at the reverse entry (-1: a self-loop,
+// or a dead slot), at indices they read per lane from the plan when the batch opened.  The base name is that of the kernel above on purpose: the per-phase accounting of
+// the benchmark matches kernels by base name.
+namespace hub {
+template <int K, int D>
+struct RouteGeo {
+    static constexpr bool ok = D == 64 && (K == 4 || K == 8);
+    static constexpr int NJ = K * D / 256;            // float4 of a row per lane (chunks)
+    static constexpr int NVAL = 4 * NJ;               // partial dot products per lane and step: index = chunk * 4 + slot
+    static constexpr int SH = K == 8 ? 1 : 2;         // 1 << SH = 16 / NVAL lanes of a DPP row end up with the same sum
+};
+// waves per SIMD the register allocation aims at: 71 registers, three workgroups per CU.  Pinned at 4 / 6 / 8 (8: 64 registers,
+// no scratch) route_fwd alone takes 27.4 / 25.8 / 26.2 us on squirrel at one slice, and the per-step tail instead of the batched
+// one 27.9 (profiles/r14_route_hub.txt)
+constexpr int ROUTE_MAXW = 6;
+
+struct RouteWords {                                   // the plan words a step runs on: partner rows and u_local of its four slots
+    dl_vi4 v, u;
+};
+
+__device__ __forceinline__ float dot4_chain(const float4& x, const float4& y) {      // dl::fast::dot on float4
+    float r = x.x * y.x;
+    r = fmaf(x.y, y.y, r);
+    r = fmaf(x.z, y.z, r);
+    return fmaf(x.w, y.w, r);
+}
+
+// one exchange of the first-max arg-max: every lane holds a candidate (of a different factor than its partner lane's), both
+// lanes of a pair end with the same one.  `beats`, written without short-circuits: selects, no branches.
+template <int OFF>
+__device__ __forceinline__ void argmax_xor(float& best, int& win) {
+    const float ob = xor_lane<OFF>(best);
+    const int ow = xor_lane_i<OFF>(win);
+    const bool o_nan = ob != ob, b_nan = best != best;
+    const bool o_beats = (ob > best) | (o_nan & !b_nan), b_beats = (best > ob) | (b_nan & !o_nan);
+    const bool take = o_beats | (!b_beats & (ow < win));
+    best = take ? ob : best;
+    win = take ? ow : win;
+}
+
+template <int K, int D, bool T1>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, ROUTE_MAXW))) void route_seg_kernel(
+    dl_pair_hub h, const float* __restrict__ Z, float t, uint8_t* __restrict__ p, float* __restrict__ a) {
+    using RG = RouteGeo<K, D>;
+    constexpr int NJ = RG::NJ, NVAL = RG::NVAL, SH = RG::SH, ROW = K * D, R4 = ROW / 4;      // R4: float4 of one Z row
+    static_assert(RG::ok, "one DPP row of 16 lanes per factor slice, one or two chunks");
+    static_assert(DL_HUB_W == 2 * WAVES, "every wave stages two rows of the block");
+    __shared__ __attribute__((aligned(16))) float4 urow[DL_HUB_W * R4];
+    // (a routing plan has one stream of items: its item is the workgroup's index, without a round trip to the stream table)
+    int it = (int)blockIdx.x;
+    if (h.n_slices > 1) {
+        const int x = blockIdx.x % h.n_slices;
+        it = h.slice_item0[x] + (int)(blockIdx.x / h.n_slices);
+        if (it >= h.slice_item0[x + 1]) return;                      // the whole workgroup, before the barrier
+    } else if (it >= h.n_items) {
+        return;
+    }
+    const int wave = wave_index(), lane = lane_id();
+    const int i = lane & 15, r = lane >> 4;
+    const int blk = h.item_block[it];
+    const int s_a = h.item_step[4 * it], s_b = h.item_step[4 * it + 1], s_c = h.item_step[4 * it + 2],
+              s_end = h.item_step[4 * it + 3];
+    auto fetch = [&](const int step) {
+        const int s = __builtin_amdgcn_readfirstlane(step);
+        RouteWords w;
+        w.v = plan_words(h.step_v, s), w.u = plan_words(h.step_u, s);
+        return w;
+    };
+    // after the reduction lane i of a DPP row holds the sum number i >> SH = chunk * 4 + slot of its row's factors
+    constexpr int NB = 1 << SH;                                      // steps per batch
+    const int e_me = (i >> SH) & 3;                                  // this lane's slot
+    const int k_me = 4 * (i >> (SH + 2)) + r;                        // and factor (chunk j holds the factors 4 j + r)
+    const int b_me = i & (NB - 1);                                   // and step of the batch
+    const bool writer = (i >> (SH + 2)) == 0 && r < 2;               // chunk 0 of row 0: the entry, of row 1: the reverse entry
+    // the pending sums of up to NB of the wave's steps (s0, s0 + 8, ...); nb (wave-uniform) counts the steps captured since
+    // the last flush.  The store indices of a batch are asked for per lane when it opens, -1 for a step past the item's end
+    // (exactly the lanes that capture nothing), and are there long before the flush.
+    float sg = 0.0f;
+    int nb = 0, dst = -1;
+    const int32_t* const my_q = r == 0 ? h.step_q : h.step_q2;
+    auto open = [&](const int s0) {
+        const int sb = s0 + WAVES * b_me;
+        dst = -1;
+        if (writer && sb < s_end) dst = my_q[4 * sb + e_me];
+    };
+    auto flush = [&]() {                                             // one tail for the whole batch
+        const float ex = expf(T1 ? sg : sg / t);
+        float S = ex;
+        if constexpr (NJ == 2) S = add_xor<8>(S);
+        S = add_xor<16>(add_xor<32>(S));
+        float best = ex / S;
+        int win = k_me;
+        if constexpr (NJ == 2) argmax_xor<8>(best, win);
+        argmax_xor<32>(best, win);
+        argmax_xor<16>(best, win);
+        if (dst >= 0) {                                              // -1: no writer lane, a dead slot, no reverse entry, no step
+            p[dst] = (uint8_t)win;
+            a[dst] = best;
+        }
+    };
+    // behind every step: at NB captured steps flush, and open the batch that starts with the wave's next step
+    auto tick = [&](const int step) {
+        if (nb == NB) {
+            flush();
+            nb = 0;
+            open(step + WAVES);
+        }
+    };
+    // LAST: the step may hold dead partner rows.  Only the last step of list A and of list B does (disenlink_hip.h;
+    // graph.HubPlan.check refuses any other plan before it is bound).
+    auto do_step = [&](const RouteWords& w, auto shape, auto last) {
+        constexpr int NV = decltype(shape)::value;                   // gathered partner rows: 4 (A), 2 (B), 1 (C)
+        constexpr bool LAST = decltype(last)::value;
+        const int sv[4] = {w.v.x, w.v.y, w.v.z, w.v.w}, su[4] = {w.u.x, w.u.y, w.u.z, w.u.w};
+        float4 zv[NV][NJ];
+#pragma unroll
+        for (int n = 0; n < NV; ++n) {
+            if (!LAST || sv[n] >= 0) {                               // wave-uniform
+                const auto* zr = uniform_row<dl_vf4>(Z, (size_t)(unsigned)sv[n] * ROW * sizeof(float));
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) zv[n][j] = as_float4(zr[(unsigned)(lane + j * 64)]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) zv[n][j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+        }
+        float val[NVAL];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            float4 u4[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) u4[e] = urow[(su[e] & (DL_HUB_W - 1)) * R4 + j * 64 + lane];      // this slot's own u row
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) val[j * 4 + e] = dot4_chain(u4[e], zv[e * NV / 4][j]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        TransposedReduce<NVAL, 8>::run(val, i);
+        sg = b_me == nb ? val[0] : sg;                               // the lanes of this step's place in the batch keep it
+        ++nb;
+    };
+    using FULL = std::false_type;
+    using LAST = std::true_type;
+    constexpr std::integral_constant<int, 4> SHAPE_A{};
+    constexpr std::integral_constant<int, 2> SHAPE_B{};
+    constexpr std::integral_constant<int, 1> SHAPE_C{};
+    // wave w takes the steps s_a + w, + 8, ... of the item, whichever list they lie in; the words of its NEXT step are
+    // requested at the top of the current one and never past the item's last step.  Those of its first step and the store
+    // indices of its first batch are requested with the block's rows, ahead of the staging loads — not behind the barrier.
+    int s = s_a + wave;
+    RouteWords nxt = {};
+    if (s < s_end) nxt = fetch(s);
+    open(s);
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        const int ul = 2 * wave + rr;
+        const int row = h.block_row[blk * DL_HUB_W + ul];             // wave-uniform; -1: the last block is short
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (row >= 0) z4 = *reinterpret_cast<const float4*>(Z + (size_t)row * ROW + (j * 64 + lane) * 4);
+            urow[ul * R4 + j * 64 + lane] = z4;
+        }
+    }
+    __syncthreads();                                                 // the only one: nothing below waits for another wave
+    auto take = [&](const int step) {
+        const RouteWords w = nxt;
+        if (step + WAVES < s_end) nxt = fetch(step + WAVES);
+        return w;
+    };
+    for (; s < s_b - 1; s += WAVES) do_step(take(s), SHAPE_A, FULL{}), tick(s);
+    if (s == s_b - 1) do_step(take(s), SHAPE_A, LAST{}), tick(s), s += WAVES;
+    for (; s < s_c - 1; s += WAVES) do_step(take(s), SHAPE_B, FULL{}), tick(s);
+    if (s == s_c - 1) do_step(take(s), SHAPE_B, LAST{}), tick(s), s += WAVES;
+    for (; s < s_end; s += WAVES) do_step(take(s), SHAPE_C, FULL{}), tick(s);        // a C step has no dead row
+    if (nb > 0) flush();                                             // a wave with no step flushes nothing
+}
+}  // namespace hub
+
 // s[i][k] = sum_{e in row i, p[e]=k} a[e] (raw; model.py:70-71).  Four LANES per segment position (a wavefront per
 // segment would leave most lanes idle and spend its time in K all-reduces; one thread per segment walks 32 entries in
 // eight dependent round trips): lane `sub` of a position adds the entries sub, sub + 4, ... of the segment in order and
@@ -215,8 +417,21 @@ template <int K, int D, typename T>
 struct RouteOps {
     // `route`: the (possibly sliced / upper-triangle) plan the routing kernel walks, NULL = g itself;
     // mirror: it covers col >= row only and every result is also written through rev
+    // hp: the routing hub plan (every entry with col >= row, both directions written), NULL = none
     static int route_fwd(const dl_csr_plan* g, const dl_csr_plan* route, bool mirror, const int32_t* rev,
-                         const void* Z, float t, uint8_t* p, float* a, float* s, float* s_part, hipStream_t st) {
+                         const dl_pair_hub* hp, const void* Z, float t, uint8_t* p, float* a, float* s, float* s_part,
+                         hipStream_t st) {
+        if constexpr (std::is_same<T, float>::value && hub::RouteGeo<K, D>::ok) {
+            if (hp != nullptr) {
+                const dim3 grid((unsigned)hp->n_slices * (unsigned)hp->slice_max_item), block(hub::THREADS);
+                if (t == 1.0f)
+                    hipLaunchKernelGGL((hub::route_seg_kernel<K, D, true>), grid, block, 0, st, *hp, (const float*)Z, t, p, a);
+                else
+                    hipLaunchKernelGGL((hub::route_seg_kernel<K, D, false>), grid, block, 0, st, *hp, (const float*)Z, t, p, a);
+                launch_s_rowsum(g, K, p, a, s, st);
+                return check_launch("route_fwd(fast, hub blocks)");
+            }
+        }
         const dl_csr_plan* rp = route ? route : g;
         if (mirror)
             hipLaunchKernelGGL((route_seg_kernel<K, D, T, true>), dim3(seg_blocks(rp)), dim3(BLOCK), 0, st, *rp, rev,
@@ -240,13 +455,17 @@ bool fast_supported(int K, int d, int dtype) {
     return false;
 }
 
-int fast_route_fwd(const dl_csr_plan* g, const dl_csr_plan* route, bool mirror, const int32_t* rev, const void* Z,
-                   int K, int d, int dtype, float t, uint8_t* p, float* a, float* s, float* s_part, hipStream_t st) {
+// the shapes hub::route_seg_kernel is instantiated for (those of the hub scorer)
+bool fast_route_hub_supported(int K, int d, int dtype) { return dtype == DL_F32 && d == 64 && (K == 4 || K == 8); }
+
+int fast_route_fwd(const dl_csr_plan* g, const dl_csr_plan* route, bool mirror, const int32_t* rev, const dl_pair_hub* hub,
+                   const void* Z, int K, int d, int dtype, float t, uint8_t* p, float* a, float* s, float* s_part,
+                   hipStream_t st) {
 #define X_F32(KK, DD) \
-    if (K == KK && d == DD) return fast::RouteOps<KK, DD, float>::route_fwd(g, route, mirror, rev, Z, t, p, a, s, s_part, st);
+    if (K == KK && d == DD) return fast::RouteOps<KK, DD, float>::route_fwd(g, route, mirror, rev, hub, Z, t, p, a, s, s_part, st);
 #define X_BF16(KK, DD)      \
     if (K == KK && d == DD) \
-        return fast::RouteOps<KK, DD, fast::bf16_t>::route_fwd(g, route, mirror, rev, Z, t, p, a, s, s_part, st);
+        return fast::RouteOps<KK, DD, fast::bf16_t>::route_fwd(g, route, mirror, rev, hub, Z, t, p, a, s, s_part, st);
     DL_DISPATCH(X)
 #undef X_F32
 #undef X_BF16

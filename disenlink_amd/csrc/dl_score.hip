@@ -231,15 +231,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
 // bank-masked reduction below 107.8, profiles/r13_fwd_hub_tail.txt).
 // The base name is that kernel's on purpose: the per-phase accounting of the benchmark matches kernels by base name.
 namespace hub {
-constexpr int WAVES = 8, THREADS = WAVES * DL_WAVE;
-
-// Four consecutive plan words at a wave-uniform index, as ONE scalar load: the pointer is typed constant address space, which
-// is what lets hipcc use the scalar cache for a load that follows the kernel's own stores (to prob — never to a plan array).
-typedef int dl_vi4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dl_vi4 plan_words(const int32_t* a, int idx) {
-    const auto* g = (const __attribute__((address_space(1))) int32_t*)a;
-    return reinterpret_cast<const __attribute__((address_space(4))) dl_vi4*>((const __attribute__((address_space(4))) int32_t*)g)[idx];
-}
+// (WAVES, THREADS and plan_words: dl_fast.h — the routing kernel over a hub plan, dl_route.hip, shares them)
 
 // The 16 plan words of one step: partner rows, u_local, pair id and second pair id of its four slots.
 struct StepWords {

@@ -382,6 +382,7 @@ class Graph(_PlanOwner):
     route: CsrPlan | None = None         # plan walked by the routing kernel: XCD-sliced, and (unsharded builds)
     route_mirror: bool = False           # covering col >= row only — routing is symmetric, so each undirected
                                          # edge is computed once and written to both entries through rev
+    route_hub: HubPlan | None = None     # the entries with col >= row as hub blocks (route_hub_plan; None: walk `route`)
     _struct: _lib.DlGraph | None = field(default=None, repr=False)
     _ws_need: dict = field(default_factory=dict, repr=False)          # (K, d) -> bytes: workspace_bytes
 
@@ -402,11 +403,14 @@ class Graph(_PlanOwner):
     @staticmethod
     def from_edge_rows(src: torch.Tensor, dst: torch.Tensor, n_nodes: int, symmetrise: bool = True,
                        seg_len: int = DEFAULT_SEG_LEN, row_range: tuple[int, int] | None = None,
-                       row_bytes: int = 2048) -> "Graph":
+                       row_bytes: int = 2048, route_hub: bool | None = None) -> "Graph":
         """Directed edge rows (duplicates allowed) -> CSR of the binarised adjacency.
 
         ``symmetrise=True`` reproduces ``adj_sym = (adj + adj.T) != 0`` (main_disentangled.py:141-142).
         ``row_range=(lo, hi)`` keeps only rows lo..hi-1 (one shard); column ids stay global.
+        ``route_hub``: whether the routing kernel gets a hub plan (route_hub_plan) — None = where the graph's first block
+        of 16 owner rows shares gathered rows (auto_hub_rows; a uniform sparse graph or a row shard gets none and nothing
+        changes), True = always (unsharded builds only), False = never.  The results do not depend on it.
         """
         if n_nodes < 0 or n_nodes >= 2 ** 31:
             raise ValueError(f"n_nodes={n_nodes} out of int32 range")
@@ -450,11 +454,16 @@ class Graph(_PlanOwner):
                               seg_len=min(seg_len, route_seg_len((e1 - e0 + 1) // 2 if mirror else e1 - e0)), n_slices=1,
                               keep=(lc >= lr + lo) if mirror else None, unit_segs=1, by_length=by_len)
         route.rowptr, route.col = plan.rowptr, plan.col        # the SAME arrays: only the segments differ
-        return Graph(plan, _i32(rev) if mirror else None, route, mirror)
+        if route_hub and not mirror:
+            raise ValueError("a routing hub plan needs the unsharded graph (row_range=None)")
+        hub = route_hub_plan(lr, lc, rev, n_nodes, force=bool(route_hub)) if mirror and route_hub is not False else None
+        return Graph(plan, _i32(rev) if mirror else None, route, mirror, hub)
 
     @staticmethod
-    def from_dense(adj: torch.Tensor, seg_len: int = DEFAULT_SEG_LEN, row_bytes: int = 2048) -> "Graph":
-        """Dense ``adj_sym`` as the reference passes it to ``model(x, adj_sym)`` (main_disentangled.py:194)."""
+    def from_dense(adj: torch.Tensor, seg_len: int = DEFAULT_SEG_LEN, row_bytes: int = 2048,
+                   route_hub: bool | None = None) -> "Graph":
+        """Dense ``adj_sym`` as the reference passes it to ``model(x, adj_sym)`` (main_disentangled.py:194).
+        ``route_hub``: as in from_edge_rows."""
         if adj.dim() != 2 or adj.shape[0] != adj.shape[1]:
             raise ValueError("adj must be square")
         # The reference multiplies by adj (model.py:62: p * adj, compared with the factor numbers): its layer is only
@@ -466,25 +475,35 @@ class Graph(_PlanOwner):
                 raise ValueError("adj must hold 0 / 1 entries (the reference's layer multiplies by it, model.py:62)")
             keep = val != 0
             return Graph.from_edge_rows(idx[0][keep], idx[1][keep], adj.shape[0], symmetrise=False, seg_len=seg_len,
-                                        row_bytes=row_bytes)
+                                        row_bytes=row_bytes, route_hub=route_hub)
         nz = torch.nonzero(adj)
         if nz.shape[0] and bool((adj[nz[:, 0], nz[:, 1]] != 1).any()):
             raise ValueError("adj must hold 0 / 1 entries (the reference's layer multiplies by it, model.py:62)")
         return Graph.from_edge_rows(nz[:, 0], nz[:, 1], adj.shape[0], symmetrise=False, seg_len=seg_len,
-                                    row_bytes=row_bytes)
+                                    row_bytes=row_bytes, route_hub=route_hub)
 
     def to(self, device) -> "Graph":
         plan = self.plan.to(device)
         route = None if self.route is None else self.route.to(device)
         if route is not None:
             route.rowptr, route.col = plan.rowptr, plan.col
-        return Graph(plan, None if self.rev is None else self.rev.to(device), route, self.route_mirror)
+        return Graph(plan, None if self.rev is None else self.rev.to(device), route, self.route_mirror,
+                     None if self.route_hub is None else self.route_hub.to(device))
 
     def c_struct(self):
         if self._struct is None:
             rp = self.route.c_value() if self.route is not None else _lib.DlCsrPlan()
             self._struct = _lib.DlGraph(self.plan.c_value(), rp, self.rev.data_ptr() if self.rev is not None else None,
                                         1 if self.route_mirror else 0)
+            h = self.route_hub
+            if h is not None and h.n_items > 0:
+                # the kernel walks the hub plan INSTEAD of the routing plan: it must hold every entry with col >= row
+                row = torch.repeat_interleave(torch.arange(self.n_rows, device=self.device), (self.rowptr[1:] - self.rowptr[:-1]).long())
+                n_upper = int((self.col.long() >= row).sum())
+                if not self.route_mirror or h.rest is not None or h.step_q2 is None or h.n_entries != n_upper:
+                    raise ValueError(f"routing hub plan: needs a mirrored graph, no residual plan and each of the {n_upper} "
+                                     f"entries with col >= row as a slot (it holds {h.n_entries})")
+                self._struct.route_hub = C.pointer(h.c_value())
         return C.byref(self._struct)
 
     def c_plan(self):
@@ -612,9 +631,12 @@ class HubPlan:
         return int((self.step_v >= 0).sum())
 
     @staticmethod
-    def build(row, col, pair, pair2, n_nodes: int, n_rows: int, n_slices: int, bounds, rest_csr) -> "HubPlan":
+    def build(row, col, pair, pair2, n_nodes: int, n_rows: int, n_slices: int, bounds, rest_csr,
+              item_rows: int | None = None) -> "HubPlan":
         """``row, col, pair, pair2`` (int64; pair2 may be None): the forward entries; ``n_rows`` = T; ``bounds`` the
-        list's column slice boundaries; ``rest_csr(keep)`` builds the residual plan from the entries ``keep`` selects."""
+        list's column slice boundaries; ``rest_csr(keep)`` builds the residual plan from the entries ``keep`` selects;
+        ``item_rows``: gathered partner rows per work item (None = HUB_ITEM_ROWS, the scorer's)."""
+        item_rows = HUB_ITEM_ROWS if item_rows is None else int(item_rows)
         dev = row.device
         ar = lambda n: torch.arange(n, device=dev)
         excl = lambda x: torch.cumsum(x, 0) - x
@@ -652,7 +674,7 @@ class HubPlan:
         bs_first = torch.nonzero(bs_new).reshape(-1)
         bs_of = torch.cumsum(bs_new, 0) - 1
         cum = excl(gath)
-        part = torch.div(cum - cum[bs_first][bs_of], HUB_ITEM_ROWS, rounding_mode="floor")
+        part = torch.div(cum - cum[bs_first][bs_of], item_rows, rounding_mode="floor")
         inew = bs_new.clone()
         inew[1:] |= part[1:] != part[:-1]
         ifirst = torch.nonzero(inew).reshape(-1)
@@ -715,6 +737,13 @@ class HubPlan:
                        _i32(item_block), _i32(item_slice), _i32(item_step_s), _i32(step_v), _i32(step_u), _i32(step_q),
                        None if step_q2 is None else _i32(step_q2), E, rest, rest_pair, rest_pair2)
 
+    def to(self, device) -> "HubPlan":
+        mv = lambda t: None if t is None else t.to(device)
+        return HubPlan(self.n_rows, self.n_blocks, mv(self.block_row), self.n_items, self.n_slices, self.slice_max_item,
+                       mv(self.slice_item0), mv(self.item_block), mv(self.item_slice), mv(self.item_step), mv(self.step_v),
+                       mv(self.step_u), mv(self.step_q), mv(self.step_q2), self.n_entries, mv(self.rest),
+                       mv(self.rest_pair), mv(self.rest_pair2))
+
     def check(self) -> None:
         """Refuse a plan the kernel would fault on.  hub::score_fwd_wave_kernel gathers the partner rows of every step but
         the last of an item's A list and B list without looking at them: a dead partner row (-1) anywhere else, or in
@@ -750,6 +779,44 @@ class HubPlan:
                 ptr(self.step_q), ptr(self.step_q2), self.n_entries,
                 self.rest.c_value() if self.rest is not None else _lib.DlCsrPlan(), ptr(self.rest_pair), ptr(self.rest_pair2))
         return self._struct
+
+
+# Work item length of the ROUTING hub plan, in gathered partner rows, and its column slices (the partner rows of a slice are
+# gathered by the XCDs that serve its stream, like a pair list's).  The scorer's HUB_ITEM_ROWS = 512 would leave 299 items
+# for the 256 CUs of squirrel_real's 78,062 gathered rows, and a wave is a chain of dependent steps: the longest item is the
+# kernel's tail.  route_fwd alone on squirrel_real, us per call with the row sums, median of 12 interleaved rounds
+# (profiles/r14_route_hub.txt): 28.5 on the routing plan; 4 slices at 32 / 64 / 96 / 128 / 160 / 256 rows 26.6 / 24.3 / 24.0 /
+# 22.8 / 24.2 / 30.5; 128 rows in 1 / 2 / 8 slices 25.5 / 23.0 / 25.8 (a stream per XCD leaves items of a few steps).
+# The routing PLAN stays unsliced (from_edge_rows).
+ROUTE_HUB_ITEM_ROWS = 128
+ROUTE_HUB_SLICES = 4
+
+
+def route_hub_plan(row: torch.Tensor, col: torch.Tensor, rev: torch.Tensor, n_nodes: int, force: bool = False) -> HubPlan | None:
+    """The hub plan the routing kernel walks instead of the mirrored routing plan (dl_graph.route_hub), or None.
+    ``row, col`` (int64): every directed entry of the symmetric CSR, ``rev`` its reverse-edge permutation.  Each entry e
+    with col >= row — one per undirected edge — becomes a slot of the block row of its OWNER, the endpoint of larger
+    degree (ties: the smaller node id), scored against the other endpoint as the partner row: on a skewed graph the
+    hubs then own most edges and a block of 16 of them gathers a partner row once for several.  The slot carries e
+    and rev[e] (-1 for a self-loop): routing is symmetric, both entries get the result.  ROUTE_HUB_SLICES column slices of
+    the partner rows, no residual plan.
+    Built where the first block of 16 owners shares gathered rows (auto_hub_rows — the scorer's rule), always with
+    ``force``; a graph without entries has none."""
+    e = torch.nonzero(col >= row).reshape(-1)
+    if e.numel() == 0:
+        return None
+    r, c = row[e], col[e]
+    deg = torch.bincount(row, minlength=n_nodes)
+    swap = deg[c] > deg[r]                                         # c >= r: a tie stays with the smaller id
+    owner, partner = torch.where(swap, c, r), torch.where(swap, r, c)
+    e2 = rev[e]
+    e2 = torch.where(e2 == e, torch.full_like(e2, -1), e2)
+    T = int((torch.bincount(owner, minlength=n_nodes) > 0).sum()) if force else auto_hub_rows(owner, partner, n_nodes)
+    if T == 0:
+        return None
+    S = ROUTE_HUB_SLICES
+    bnd = slice_bounds(partner, S) if S > 1 else None
+    return HubPlan.build(owner, partner, e, e2, n_nodes, T, S, bnd, None, item_rows=ROUTE_HUB_ITEM_ROWS)
 
 
 @dataclass

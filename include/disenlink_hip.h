@@ -110,6 +110,13 @@ typedef struct dl_graph {
     dl_csr_plan route;
     const int32_t* rev;         /* [n_entries], needed when route_mirror != 0 */
     int32_t route_mirror;
+    /* Optional (NULL = none), read by dl_route_fwd only: the entries with col >= row of an unsharded, mirrored graph as
+     * a hub plan (dl_pair_hub below) — every undirected edge is a slot in a block row of its endpoint of LARGER degree,
+     * scored against the other endpoint as the partner row.  step_q holds the entry's index into p / a, step_q2 the index
+     * of the reverse entry (-1 for a self-loop); there is no residual plan (rest.n_entries == 0) and n_entries equals the
+     * number of entries with col >= row.  Used for fp32 tables with d = 64 and K in {4, 8} unless DL_ROUTE_HUB=0; every
+     * other call walks `route` as before.  Same bits either way. */
+    const struct dl_pair_hub* route_hub;
 } dl_graph;
 
 /* A CSR over pair slots: row u lists other endpoints (csr.col) and pair ids (inc_pair).
