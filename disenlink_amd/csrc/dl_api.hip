@@ -41,6 +41,16 @@ static int check_plan(const dl_csr_plan* c, const char* what) {
     return DL_OK;
 }
 
+// What every kernel over a dl_pair_hub needs of it (dl_hub.h: 16-byte scalar loads); which entries it holds is the caller's to check.
+static int check_hub(const dl_pair_hub* hp, const char* what, bool need_q2) {
+    DL_REQUIRE(hp->n_slices >= 1 && hp->slice_max_item >= 1 && hp->n_blocks >= 1 && hp->n_steps >= 1, "%s: empty grid", what);
+    DL_REQUIRE(hp->block_row && hp->slice_item0 && hp->item_block && hp->item_step && hp->step_v && hp->step_u && hp->step_q &&
+               (hp->step_q2 || !need_q2), "%s: NULL array", what);
+    DL_REQUIRE((((uintptr_t)hp->step_v | (uintptr_t)hp->step_u | (uintptr_t)hp->step_q | (uintptr_t)hp->step_q2) & 15) == 0,
+               "%s: step_v, step_u, step_q and step_q2 must be 16-byte aligned", what);
+    return DL_OK;
+}
+
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Workspace layout (256-byte aligned blocks):
@@ -258,11 +268,7 @@ int dl_route_fwd(const dl_graph* g, const void* Z, int K, int d, dl_dtype dtype,
             DL_REQUIRE(hp->rest.n_entries == 0 && 2LL * hp->n_entries >= c->n_entries && hp->n_entries <= c->n_entries,
                        "route_hub must hold each of the graph's entries with col >= row (%d entries in all) and no residual plan: "
                        "it holds %d + %d", c->n_entries, hp->n_entries, hp->rest.n_entries);
-            DL_REQUIRE(hp->n_slices >= 1 && hp->slice_max_item >= 1 && hp->n_blocks >= 1 && hp->n_steps >= 1, "route_hub: empty grid");
-            DL_REQUIRE(hp->block_row && hp->slice_item0 && hp->item_block && hp->item_step && hp->step_v && hp->step_u &&
-                       hp->step_q && hp->step_q2, "route_hub: NULL array");
-            DL_REQUIRE((((uintptr_t)hp->step_v | (uintptr_t)hp->step_u | (uintptr_t)hp->step_q | (uintptr_t)hp->step_q2) & 15) == 0,
-                       "route_hub: step_v, step_u, step_q and step_q2 must be 16-byte aligned");
+            if (int rc = check_hub(hp, "route_hub", true)) return rc;
         }
         return fast_route_fwd(c, have ? rp : nullptr, mirror, g->rev, hp, Z, K, d, dtype, t, p, a, s, w.vec_part,
                               (hipStream_t)stream);
@@ -307,14 +313,7 @@ int dl_score_pairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_dty
             DL_REQUIRE(hp->n_items >= 0 && hp->n_entries >= 0 && hp->rest.n_entries >= 0 &&
                        hp->n_entries + hp->rest.n_entries == by_u->csr.n_entries,
                        "by_u.hub must hold each of the plan's %d entries exactly once", by_u->csr.n_entries);
-            if (hp->n_items > 0) {
-                DL_REQUIRE(hp->n_slices >= 1 && hp->slice_max_item >= 1 && hp->n_blocks >= 1 && hp->n_steps >= 1, "by_u.hub: empty grid");
-                DL_REQUIRE(hp->block_row && hp->slice_item0 && hp->item_block && hp->item_step && hp->step_v && hp->step_u &&
-                           hp->step_q && (hp->step_q2 || !by_u->inc_pair2), "by_u.hub: NULL array");
-                // a step's four words are read as one 16-byte scalar load
-                DL_REQUIRE((((uintptr_t)hp->step_v | (uintptr_t)hp->step_u | (uintptr_t)hp->step_q | (uintptr_t)hp->step_q2) & 15) == 0,
-                           "by_u.hub: step_v, step_u, step_q and step_q2 must be 16-byte aligned");
-            }
+            if (int rc = hp->n_items > 0 ? check_hub(hp, "by_u.hub", by_u->inc_pair2 != nullptr) : DL_OK) return rc;
             if (hp->rest.n_entries > 0) {
                 if (int rc = check_plan(&hp->rest, "by_u.hub.rest")) return rc;
                 DL_REQUIRE(hp->rest.n_total == N && hp->rest.seg_len == by_u->csr.seg_len && hp->rest_pair &&

@@ -230,19 +230,7 @@ __device__ __forceinline__ const __attribute__((address_space(1))) V* uniform_ro
 }
 __device__ __forceinline__ float4 as_float4(dl_vf4 v) { return make_float4(v.x, v.y, v.z, v.w); }
 
-// ---------------------------------------------------------------------------- kernels over a hub plan (dl_pair_hub)
-// Shared by hub::score_fwd_wave_kernel (dl_score.hip) and hub::route_seg_kernel (dl_route.hip): eight waves per work item.
-namespace hub {
-constexpr int WAVES = 8, THREADS = WAVES * DL_WAVE;
-
-// Four consecutive plan words at a wave-uniform index, as ONE scalar load: the pointer is typed constant address space, which
-// is what lets hipcc use the scalar cache for a load that follows the kernel's own stores (to prob, p, a — never to a plan array).
-typedef int dl_vi4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dl_vi4 plan_words(const int32_t* a, int idx) {
-    const auto* g = (const __attribute__((address_space(1))) int32_t*)a;
-    return reinterpret_cast<const __attribute__((address_space(4))) dl_vi4*>((const __attribute__((address_space(4))) int32_t*)g)[idx];
-}
-}  // namespace hub
+// (the kernels over a hub plan, dl_pair_hub: what they share is in dl_hub.h)
 
 // ---------------------------------------------------------------------------- unit reduction through LDS
 // A segment kernel ends with per-GROUP partial results: lane c of group g holds elements kk*D + c*VEC .. of every factor

@@ -1,6 +1,7 @@
 // Routing: exp-Gram softmax over K, first-max arg-max per edge, row sums of the winning weights (model.py:56-72).
 // (one of the tuned-kernel translation units; the shared pieces and the design notes are in dl_fast.h)
 #include "dl_fast.h"
+#include "dl_hub.h"
 
 namespace dl {
 namespace fast {
@@ -64,10 +65,10 @@ __global__ __launch_bounds__(BLOCK, (K <= 8 && sizeof(T) == 4) ? 8 : (K <= 10 ? 
 // The kernel above gathers one whole Z row per entry with col >= row and is bound by those bytes (15.6 TB/s out of the L2 on
 // squirrel).  On a skewed graph most of them are repeats: the routing hub plan (dl_graph.route_hub, graph.py) hands every
 // undirected edge to its endpoint of larger degree, cuts those owners into blocks of 16 rows, and a workgroup that holds a
-// block's Z rows in LDS (32 KB at K = 8) gathers a partner row ONCE for up to four of them — the geometry, the three step
-// shapes and the whole step structure of hub::score_fwd_wave_kernel (dl_score.hip): scalar row bases, the plan words of
-// the wave's next step requested one step ahead, every gather of a step issued before the first wait, a chunk's LDS reads
-// issued together.
+// block's Z rows in LDS (32 KB at K = 8) gathers a partner row ONCE for up to four of them.  Item, staging, walk and batch
+// counter are those of every kernel over a hub plan (dl_hub.h, with the plan contract); the step is that of
+// hub::score_fwd_wave_kernel (dl_score.hip) on one table: scalar row bases, every gather of a step issued before the first
+// wait, a chunk's LDS reads issued together.
 // Lane l holds float4 number j * 64 + l of a row: a DPP row of 16 lanes is one factor slice (factor 4 j + r, r = l >> 4), and
 // lane i of it holds the elements 4 i .. 4 i + 3 — the elements lane c = i of a group holds in the kernel above.
 // Bits.  A pair's results are those of the kernel above, operation for operation:
@@ -87,9 +88,10 @@ __global__ __launch_bounds__(BLOCK, (K <= 8 && sizeof(T) == 4) ? 8 : (K <= 10 ? 
 // or a dead slot), at indices they read per lane from the plan when the batch opened.  The base name is that of the kernel above on purpose: the per-phase accounting of
 // the benchmark matches kernels by base name.
 namespace hub {
+constexpr bool route_shape_ok(int K, int D) { return D == 64 && (K == 4 || K == 8); }
 template <int K, int D>
 struct RouteGeo {
-    static constexpr bool ok = D == 64 && (K == 4 || K == 8);
+    static constexpr bool ok = route_shape_ok(K, D);
     static constexpr int NJ = K * D / 256;            // float4 of a row per lane (chunks)
     static constexpr int NVAL = 4 * NJ;               // partial dot products per lane and step: index = chunk * 4 + slot
     static constexpr int SH = K == 8 ? 1 : 2;         // 1 << SH = 16 / NVAL lanes of a DPP row end up with the same sum
@@ -99,9 +101,7 @@ struct RouteGeo {
 // one 27.9 (profiles/r14_route_hub.txt)
 constexpr int ROUTE_MAXW = 6;
 
-struct RouteWords {                                   // the plan words a step runs on: partner rows and u_local of its four slots
-    dl_vi4 v, u;
-};
+struct RouteWords { dl_vi4 v, u; };                   // the plan words a step runs on: partner rows and u_local of its four slots
 
 __device__ __forceinline__ float dot4_chain(const float4& x, const float4& y) {      // dl::fast::dot on float4
     float r = x.x * y.x;
@@ -129,22 +129,13 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, ROUT
     using RG = RouteGeo<K, D>;
     constexpr int NJ = RG::NJ, NVAL = RG::NVAL, SH = RG::SH, ROW = K * D, R4 = ROW / 4;      // R4: float4 of one Z row
     static_assert(RG::ok, "one DPP row of 16 lanes per factor slice, one or two chunks");
-    static_assert(DL_HUB_W == 2 * WAVES, "every wave stages two rows of the block");
     __shared__ __attribute__((aligned(16))) float4 urow[DL_HUB_W * R4];
-    // (a routing plan has one stream of items: its item is the workgroup's index, without a round trip to the stream table)
-    int it = (int)blockIdx.x;
-    if (h.n_slices > 1) {
-        const int x = blockIdx.x % h.n_slices;
-        it = h.slice_item0[x] + (int)(blockIdx.x / h.n_slices);
-        if (it >= h.slice_item0[x + 1]) return;                      // the whole workgroup, before the barrier
-    } else if (it >= h.n_items) {
-        return;
-    }
+    int it;
+    if (!workgroup_item<true>(h, it)) return;                        // (a routing plan has one stream of items)
     const int wave = wave_index(), lane = lane_id();
     const int i = lane & 15, r = lane >> 4;
-    const int blk = h.item_block[it];
-    const int s_a = h.item_step[4 * it], s_b = h.item_step[4 * it + 1], s_c = h.item_step[4 * it + 2],
-              s_end = h.item_step[4 * it + 3];
+    const int blk = h.item_block[it];                                // asked for first: block, rows, LDS is the chain to the barrier
+    const ItemSteps st = item_steps(h, it);
     auto fetch = [&](const int step) {
         const int s = __builtin_amdgcn_readfirstlane(step);
         RouteWords w;
@@ -157,16 +148,16 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, ROUT
     const int k_me = 4 * (i >> (SH + 2)) + r;                        // and factor (chunk j holds the factors 4 j + r)
     const int b_me = i & (NB - 1);                                   // and step of the batch
     const bool writer = (i >> (SH + 2)) == 0 && r < 2;               // chunk 0 of row 0: the entry, of row 1: the reverse entry
-    // the pending sums of up to NB of the wave's steps (s0, s0 + 8, ...); nb (wave-uniform) counts the steps captured since
-    // the last flush.  The store indices of a batch are asked for per lane when it opens, -1 for a step past the item's end
-    // (exactly the lanes that capture nothing), and are there long before the flush.
+    // the pending sums of up to NB of the wave's steps (s0, s0 + 8, ...).  The store indices of a batch are asked for per
+    // lane when it opens and are there long before the flush.
     float sg = 0.0f;
-    int nb = 0, dst = -1;
+    int dst = -1;
+    Batch<NB, false> batch;
     const int32_t* const my_q = r == 0 ? h.step_q : h.step_q2;
     auto open = [&](const int s0) {
         const int sb = s0 + WAVES * b_me;
         dst = -1;
-        if (writer && sb < s_end) dst = my_q[4 * sb + e_me];
+        if (writer && sb < st.end) dst = my_q[4 * sb + e_me];
     };
     auto flush = [&]() {                                             // one tail for the whole batch
         const float ex = expf(T1 ? sg : sg / t);
@@ -183,19 +174,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, ROUT
             a[dst] = best;
         }
     };
-    // behind every step: at NB captured steps flush, and open the batch that starts with the wave's next step
-    auto tick = [&](const int step) {
-        if (nb == NB) {
-            flush();
-            nb = 0;
-            open(step + WAVES);
-        }
-    };
-    // LAST: the step may hold dead partner rows.  Only the last step of list A and of list B does (disenlink_hip.h;
-    // graph.HubPlan.check refuses any other plan before it is bound).
     auto do_step = [&](const RouteWords& w, auto shape, auto last) {
         constexpr int NV = decltype(shape)::value;                   // gathered partner rows: 4 (A), 2 (B), 1 (C)
-        constexpr bool LAST = decltype(last)::value;
+        constexpr bool LAST = decltype(last)::value;                 // dead partner rows: dl_hub.h
         const int sv[4] = {w.v.x, w.v.y, w.v.z, w.v.w}, su[4] = {w.u.x, w.u.y, w.u.z, w.u.w};
         float4 zv[NV][NJ];
 #pragma unroll
@@ -221,44 +202,22 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, ROUT
             __builtin_amdgcn_sched_barrier(0);
         }
         TransposedReduce<NVAL, 8>::run(val, i);
-        sg = b_me == nb ? val[0] : sg;                               // the lanes of this step's place in the batch keep it
-        ++nb;
+        sg = b_me == batch.nb ? val[0] : sg;                         // the lanes of this step's place in the batch keep it
+        ++batch.nb;
     };
-    using FULL = std::false_type;
-    using LAST = std::true_type;
-    constexpr std::integral_constant<int, 4> SHAPE_A{};
-    constexpr std::integral_constant<int, 2> SHAPE_B{};
-    constexpr std::integral_constant<int, 1> SHAPE_C{};
-    // wave w takes the steps s_a + w, + 8, ... of the item, whichever list they lie in; the words of its NEXT step are
-    // requested at the top of the current one and never past the item's last step.  Those of its first step and the store
-    // indices of its first batch are requested with the block's rows, ahead of the staging loads — not behind the barrier.
-    int s = s_a + wave;
+    // The words of the wave's first step and the store indices of its first batch are requested with the block's rows, ahead
+    // of the staging loads — not behind the barrier.
+    const int s = st.a + wave;
     RouteWords nxt = {};
-    if (s < s_end) nxt = fetch(s);
+    if (s < st.end) nxt = fetch(s);
     open(s);
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-        const int ul = 2 * wave + rr;
-        const int row = h.block_row[blk * DL_HUB_W + ul];             // wave-uniform; -1: the last block is short
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (row >= 0) z4 = *reinterpret_cast<const float4*>(Z + (size_t)row * ROW + (j * 64 + lane) * 4);
-            urow[ul * R4 + j * 64 + lane] = z4;
-        }
-    }
+    stage_block<NJ, 1>((lds_vf4*)urow, h, blk, wave, lane, {Z});
     __syncthreads();                                                 // the only one: nothing below waits for another wave
-    auto take = [&](const int step) {
-        const RouteWords w = nxt;
-        if (step + WAVES < s_end) nxt = fetch(step + WAVES);
-        return w;
-    };
-    for (; s < s_b - 1; s += WAVES) do_step(take(s), SHAPE_A, FULL{}), tick(s);
-    if (s == s_b - 1) do_step(take(s), SHAPE_A, LAST{}), tick(s), s += WAVES;
-    for (; s < s_c - 1; s += WAVES) do_step(take(s), SHAPE_B, FULL{}), tick(s);
-    if (s == s_c - 1) do_step(take(s), SHAPE_B, LAST{}), tick(s), s += WAVES;
-    for (; s < s_end; s += WAVES) do_step(take(s), SHAPE_C, FULL{}), tick(s);        // a C step has no dead row
-    if (nb > 0) flush();                                             // a wave with no step flushes nothing
+    walk(s, st, nxt, fetch, [&](const RouteWords& w, const int step, auto shape, auto last) {
+        do_step(w, shape, last);
+        batch.tick(step, flush, open);
+    });
+    batch.close(flush);
 }
 }  // namespace hub
 
@@ -456,7 +415,7 @@ bool fast_supported(int K, int d, int dtype) {
 }
 
 // the shapes hub::route_seg_kernel is instantiated for (those of the hub scorer)
-bool fast_route_hub_supported(int K, int d, int dtype) { return dtype == DL_F32 && d == 64 && (K == 4 || K == 8); }
+bool fast_route_hub_supported(int K, int d, int dtype) { return dtype == DL_F32 && fast::hub::route_shape_ok(K, d); }
 
 int fast_route_fwd(const dl_csr_plan* g, const dl_csr_plan* route, bool mirror, const int32_t* rev, const dl_pair_hub* hub,
                    const void* Z, int K, int d, int dtype, float t, uint8_t* p, float* a, float* s, float* s_part,

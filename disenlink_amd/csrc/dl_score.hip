@@ -1,6 +1,7 @@
 // Pair scorer (model.py:109-113 on a pair list), the gather-form dense scorer, and the separate scorer backward.
 // (one of the tuned-kernel translation units; the shared pieces and the design notes are in dl_fast.h)
 #include "dl_fast.h"
+#include "dl_hub.h"
 #include "dl_score_bwd.h"
 
 namespace dl {
@@ -212,18 +213,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
 // The wave-per-entry kernel above gathers one [Z row | H row] pair per entry and is bound by those bytes.  On a skewed pair
 // list most entries sit in a few long rows that score against many of the SAME partner rows: a workgroup that holds a
 // block of 16 such rows in LDS (dl_pair_hub, disenlink_hip.h) gathers a partner row once for up to four of them.
-// Eight waves stage the block's rows (64 KB at K = 8: two workgroups per CU), ONE barrier, and from there on every wave
-// runs on its own: wave w takes the steps w, w + 8, ... of the item, counted through its three lists [A | B | C] so that
-// no two waves differ by more than one step.  A step is the step of the kernel above — 4 / 2 / 1 partner rows gathered
-// into registers through a scalar row base, 16 float4 in flight before anything waits, the same dot4_packed calls into
-// val[table * 8 + chunk * 4 + slot], the same reduction, expf and sigmoid — except that every slot reads ITS OWN u row
-// from LDS, and that the partner registers a slot uses are fixed by the step's shape (NV = gathered rows: slot e uses
-// set e * NV / 4).  The value of a slot never meets another slot's, and the reduction adds the same 16 lanes in the same
-// order whichever slot a value sits in: every pair gets the bits of the kernel above.
-// Like that kernel's TAIL, dead-row handling is compiled into the LAST step of list A and of list B only: the plan holds dead
-// rows nowhere else (disenlink_hip.h; graph.HubPlan.check refuses a plan that does before it is bound), so a full step has no
-// sign test and no zero fill of gather registers, and a wave requests the plan words of its next step while it works on
-// the current one.
+// Item, staging (64 KB at K = 8: two workgroups per CU), walk and batch counter are those of every kernel over a hub plan
+// (dl_hub.h, with the plan contract).  A step is the step of the kernel above — 4 / 2 / 1 partner rows gathered into
+// registers through a scalar row base, 16 float4 in flight before anything waits, the same dot4_packed calls into
+// val[table * 8 + chunk * 4 + slot], the same reduction, expf and sigmoid — except that every slot reads ITS OWN u row from
+// LDS, and that the partner registers a slot uses are fixed by the step's shape (NV = gathered rows: slot e uses set
+// e * NV / 4).  The value of a slot never meets another slot's, and the reduction adds the same 16 lanes in the same order
+// whichever slot a value sits in: every pair gets the bits of the kernel above.
 // Without per-factor terms (COEF == false) a step ends at its logit: a step yields 4 of them and a wave has 64 lanes, so the
 // wave keeps the logits of 16 steps in its lanes and runs ONE sigmoid and ONE store pass per batch (and one behind its last
 // step), with pair ids it read per lane when the batch opened — no second expf, no IEEE division, no pair-id selects and no
@@ -231,12 +227,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
 // bank-masked reduction below 107.8, profiles/r13_fwd_hub_tail.txt).
 // The base name is that kernel's on purpose: the per-phase accounting of the benchmark matches kernels by base name.
 namespace hub {
-// (WAVES, THREADS and plan_words: dl_fast.h — the routing kernel over a hub plan, dl_route.hip, shares them)
-
 // The 16 plan words of one step: partner rows, u_local, pair id and second pair id of its four slots.
-struct StepWords {
-    dl_vi4 v, u, q, p;
-};
+struct StepWords { dl_vi4 v, u, q, p; };
 
 // TransposedReduce<16, 8> with the stages OFF = 8 and OFF = 4 as two bank-masked DPP adds per output: the select bit of a
 // stage is constant within a bank of 4 lanes, so "keep + (send of lane ^ OFF)" is one add written under the banks whose bit is
@@ -291,33 +283,15 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
     using FW = FwdWave<K, D>;
     constexpr int NJ = FW::NJ, U = FW::U, ROW = K * D, R4 = 2 * ROW / 4;      // R4: float4 of one [Z row | H row]
     static_assert(D == 64 && NJ >= 1 && U == 4 && U * NJ <= 8, "the step geometry of score_fwd_wave_kernel");
-    static_assert(DL_HUB_W == 2 * WAVES, "every wave stages two rows of the block");
     constexpr bool BATCH = !COEF;      // the forms with per-factor terms store per step and per lane anyway: they keep the per-step tail
     __shared__ __attribute__((aligned(16))) float4 urow[DL_HUB_W * R4];
-    const int x = blockIdx.x % h.n_slices;
-    const int it = h.slice_item0[x] + (int)(blockIdx.x / h.n_slices);
-    if (it >= h.slice_item0[x + 1]) return;                          // the whole workgroup, before the barrier
+    int it;
+    if (!workgroup_item<false>(h, it)) return;
     const int wave = wave_index(), lane = lane_id();
     const int i = lane & 15, r = lane >> 4;
     const int blk = h.item_block[it];
-    // the item's boundaries are asked for with its block, ahead of the staging loads — not behind the barrier
-    const int s_a = h.item_step[4 * it], s_b = h.item_step[4 * it + 1], s_c = h.item_step[4 * it + 2],
-              s_end = h.item_step[4 * it + 3];
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-        const int ul = 2 * wave + rr;
-        const int row = h.block_row[blk * DL_HUB_W + ul];             // wave-uniform; -1: the last block is short
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
-            if (row >= 0) {
-                a = *reinterpret_cast<const float4*>(Z + (size_t)row * ROW + (j * 64 + lane) * 4);
-                b = *reinterpret_cast<const float4*>(H + (size_t)row * ROW + (j * 64 + lane) * 4);
-            }
-            urow[ul * R4 + j * 64 + lane] = a;
-            urow[ul * R4 + ROW / 4 + j * 64 + lane] = b;
-        }
-    }
+    const ItemSteps st = item_steps(h, it);                          // asked for with the block, ahead of the staging loads
+    stage_block<NJ, 2>((lds_vf4*)urow, h, blk, wave, lane, {Z, H});
     __syncthreads();                                                 // the only one: nothing below waits for another wave
     // a step's 16 words through the scalar cache (the plan is read-only for the whole launch)
     auto fetch = [&](const int step) {
@@ -332,16 +306,16 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
         return w;
     };
     // BATCH: the pending logits of up to 16 of the wave's steps, one per lane — lane L holds slot L & 3 of the batch's step
-    // number L >> 2 (the steps s0, s0 + 8, ...).  nb (wave-uniform) counts the steps captured since the last flush.  The pair
-    // ids of a batch are asked for per lane when it opens, -1 for the steps past the item's end (a wave takes every step
-    // s0 + 8 b below s_end, so these are exactly the lanes that capture nothing), and are there long before the flush.
+    // number L >> 2 (the steps s0, s0 + 8, ...).  The pair ids of a batch are asked for per lane when it opens (a wave takes
+    // every step s0 + 8 b below the item's end) and are there long before the flush.
     const int slot_step = lane >> 2;
     float lg = 0.0f;
-    int nb = 0, pq = -1, pq2 = -1;
+    int pq = -1, pq2 = -1;
+    Batch<16, true> batch;
     auto open = [&](const int s0) {
         const int sb = s0 + WAVES * slot_step;
         pq = pq2 = -1;
-        if (sb < s_end) {
+        if (sb < st.end) {
             pq = h.step_q[4 * sb + (lane & 3)];
             if constexpr (FOLD) pq2 = h.step_q2[4 * sb + (lane & 3)];
         }
@@ -351,22 +325,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
         if (pq >= 0) prob[pq] = p;                                   // a dead slot's id is -1 in the plan, like a dead lane's here
         if (FOLD && pq2 >= 0) prob[pq2] = p;
     };
-    // behind every step: at 16 captured steps flush, and open the batch that starts with the wave's next step
-    auto tick = [&](const int step) {
-        if constexpr (BATCH) {
-            if (__builtin_expect(nb == 16, 0)) {
-                flush();
-                nb = 0;
-                open(step + WAVES);
-            }
-        }
-    };
-    // LAST: the step may hold dead partner rows.  Only the last step of a list does (disenlink_hip.h); every other step
-    // gathers its NV rows without a test and without the zero fill of a dead row's registers, as the wave-per-entry kernel
-    // does outside its TAIL step.
     auto do_step = [&](const StepWords& w, auto shape, auto last) {
         constexpr int NV = decltype(shape)::value;                   // gathered partner rows: 4 (A), 2 (B), 1 (C)
-        constexpr bool LAST = decltype(last)::value;
+        constexpr bool LAST = decltype(last)::value;                 // dead partner rows: dl_hub.h; the kernel above's TAIL
         const int sv[4] = {w.v.x, w.v.y, w.v.z, w.v.w}, su[4] = {w.u.x, w.u.y, w.u.z, w.u.w}, sq[4] = {w.q.x, w.q.y, w.q.z, w.q.w},
                   sq2[4] = {w.p.x, w.p.y, w.p.z, w.p.w};
         float4 zv[NV][NJ], hv[NV][NJ];
@@ -423,8 +384,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
             tb = __builtin_amdgcn_update_dpp(tb, tb, 0x114, 0xF, 0x8, false);                             // row_shr:4 -> lanes 12..15
             tb = __builtin_amdgcn_update_dpp(tb, tb, 0x128, 0xF, 0x3, false);                             // row_ror:8 -> lanes 0..7
             const float logit = add_xor<32>(add_xor<16>(__int_as_float(tb)));
-            lg = slot_step == nb ? logit : lg;
-            ++nb;
+            lg = slot_step == batch.nb ? logit : lg;
+            ++batch.nb;
         } else {
             const float logit = add_xor<32>(add_xor<16>(term));
             const float p = sigmoid_ref(logit);
@@ -449,32 +410,15 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
             }
         }
     };
-    using FULL = std::false_type;
-    using LAST = std::true_type;
-    constexpr std::integral_constant<int, 4> SHAPE_A{};
-    constexpr std::integral_constant<int, 2> SHAPE_B{};
-    constexpr std::integral_constant<int, 1> SHAPE_C{};
-    // step number n of the item (n = wave, wave + 8, ...) lies in list A, B or C by its place in [s_a, s_end)
-    int s = s_a + wave;
-    // The words of the wave's NEXT step (s + WAVES, whichever list it lies in) are requested at the top of the current one,
-    // into a second set of SGPRs and never past the item's last step: a step starts from words that are already there
-    // instead of behind a scalar-cache round trip at the head of its chain.
+    const int s = st.a + wave;
     StepWords nxt = {};
-    if (s < s_end) nxt = fetch(s);
-    auto take = [&](const int step) {
-        const StepWords w = nxt;
-        if (step + WAVES < s_end) nxt = fetch(step + WAVES);
-        return w;
-    };
+    if (s < st.end) nxt = fetch(s);
     if constexpr (BATCH) open(s);
-    for (; s < s_b - 1; s += WAVES) do_step(take(s), SHAPE_A, FULL{}), tick(s);
-    if (s == s_b - 1) do_step(take(s), SHAPE_A, LAST{}), tick(s), s += WAVES;
-    for (; s < s_c - 1; s += WAVES) do_step(take(s), SHAPE_B, FULL{}), tick(s);
-    if (s == s_c - 1) do_step(take(s), SHAPE_B, LAST{}), tick(s), s += WAVES;
-    for (; s < s_end; s += WAVES) do_step(take(s), SHAPE_C, FULL{}), tick(s);        // a C step has no dead row
-    if constexpr (BATCH) {
-        if (nb > 0) flush();                                        // a wave with no step flushes nothing
-    }
+    walk(s, st, nxt, fetch, [&](const StepWords& w, const int step, auto shape, auto last) {
+        do_step(w, shape, last);
+        if constexpr (BATCH) batch.tick(step, flush, open);
+    });
+    if constexpr (BATCH) batch.close(flush);
 }
 }  // namespace hub
 

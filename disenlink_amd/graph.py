@@ -13,6 +13,8 @@ from __future__ import annotations
 
 import os
 import ctypes as C
+import itertools
+import weakref
 from dataclasses import dataclass, field
 
 import torch
@@ -63,8 +65,7 @@ def auto_slices(n_nodes: int, row_bytes: int, entries_per_row: float = 1e9, n_ta
     of n_nodes / n_slices nodes) near an XCD's 4 MiB L2, while a (row, slice) group keeps >= ~4 entries so
     that the per-segment staging of the row stays amortised.  Measured (tools/): squirrel
     483 -> 196 us with 8 slices; a 41.6k-node table (170 MB) 600 -> 357 us with 32."""
-    import os
-    forced = os.environ.get("DL_FORCE_SLICES")               # experiments only
+    forced = os.environ.get("DL_FORCE_SLICES")              # experiments only
     if forced:
         return int(forced)
     table = float(n_nodes) * row_bytes * n_tables
@@ -124,13 +125,9 @@ def column_slices(col: torch.Tensor, n_slices: int) -> torch.Tensor:
     the same amount of work whatever the degree distribution over node ids is (real squirrel: the heaviest of 8
     equal-width slices held 31 % more pairs than the average; scorer 226 -> see DESIGN.md).  Entries with the same
     column always share a slice.  dl_host_plan_build (dl_host.hip) computes the same boundaries."""
-    E = int(col.numel())
-    if E == 0 or n_slices <= 1:
+    if int(col.numel()) == 0 or n_slices <= 1:
         return torch.zeros_like(col)
-    sorted_col = torch.sort(col).values
-    cut = (torch.arange(1, n_slices, device=col.device, dtype=torch.int64) * E) // n_slices
-    bounds = sorted_col[cut]                                   # slice q = [bounds[q-1], bounds[q])
-    return torch.bucketize(col, bounds, right=True)
+    return torch.bucketize(col, slice_bounds(col, n_slices), right=True)
 
 
 def _i32(t: torch.Tensor) -> torch.Tensor:
@@ -140,9 +137,6 @@ def _i32(t: torch.Tensor) -> torch.Tensor:
 # Integer handles of live Graph / PairList objects (the registered operators of torch_ops.py take handles, not Python
 # objects).  Held WEAKLY and assigned at construction: reading a handle is then a plain attribute access — traceable by
 # torch.compile — and a caller that builds a new pair list per epoch does not accumulate GPU plans in a registry.
-import itertools
-import weakref
-
 _HANDLES: "weakref.WeakValueDictionary[int, object]" = weakref.WeakValueDictionary()
 _next_handle = itertools.count(1)
 

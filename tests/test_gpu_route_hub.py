@@ -9,7 +9,10 @@ gathered rows has at most a dozen steps, so no wave of those plans has more than
 a wave keeps the sums of two (K = 8) or four (K = 4) of its steps before it runs its tail, so what can go wrong depends on
 the steps per wave — come from engineered graphs in one work item, the lists of test_gpu_score_hub_tail.py as graphs (16
 hub rows that own every edge; nA partners on one hub, nB on two, nC on four): an item with only A steps, one with only C
-steps, A lists that end on 1, 2 and 3 live rows, a B list that ends on one live half, a block of 3 rows.  All of it is
+steps, A lists that end on 1, 2 and 3 live rows, a B list that ends on one live half, a block of 3 rows.  The walk and the
+batch counter are shared code (dl_hub.h), so the items also hold every length at which the closing flush changes: a multiple
+of 8 waves x the batch (16 steps at K = 8, 32 at K = 4: 128 does for both), one less (127) and one more (129, an item with
+all three lists), besides items of fewer than 8 steps (waves with none), without A, without B and of C steps only.  All of it is
 asserted on CPU copies of the plans, so that a change of the plan builder fails here instead of silently covering less.
 
 Tables: random; all zero (every quotient 1 / K: p is 0 everywhere); factor 1 an exact copy of factor 0 (the lower index
@@ -32,11 +35,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 D = 64
 ENGINEERED = {"512/0/0": (512, 0, 0), "0/0/130": (0, 0, 130), "0/0/264": (0, 0, 264), "0/0/127": (0, 0, 127),
-              "61/0/0": (61, 0, 0), "3/0/0": (3, 0, 0), "102/121/200": (102, 121, 200)}
+              "61/0/0": (61, 0, 0), "3/0/0": (3, 0, 0), "102/121/200": (102, 121, 200), "100/120/44": (100, 120, 44)}
 WANT_PER_WAVE = {"512/0/0": {16}, "0/0/130": {16, 17}, "0/0/264": {33}, "0/0/127": {15, 16}, "61/0/0": {2}, "3/0/0": {0, 1},
-                 "102/121/200": {35, 36}}
+                 "102/121/200": {35, 36}, "100/120/44": {16, 17}}
 WANT_ITEM_STEP = {"512/0/0": [0, 128, 128, 128], "0/0/130": [0, 0, 0, 130], "61/0/0": [0, 16, 16, 16], "3/0/0": [0, 1, 1, 1],
-                  "102/121/200": [0, 26, 87, 287]}
+                  "102/121/200": [0, 26, 87, 287], "100/120/44": [0, 25, 85, 129]}
 _graphs = {}
 
 
@@ -66,7 +69,7 @@ def _all_graphs():
     """name -> (hub graph, plain graph); the plans hold what the docstring says."""
     if _graphs:
         return _graphs
-    out, per_wave, a_tail, b_tail = {}, set(), set(), set()
+    out, per_wave, a_tail, b_tail, lengths, lists = {}, set(), set(), set(), set(), set()
     for name, maker in rg.SMALL.items():
         out[name] = _pair(*maker(), None)
         out[name + ", items of 8"] = _pair(*maker(), 8)
@@ -86,11 +89,15 @@ def _all_graphs():
         st, v = h.item_step.cpu().tolist(), h.step_v.cpu().numpy()
         per_wave |= steps_per_wave(st)
         for a, b, c, e in st:
+            lengths.add(e - a)
+            lists.add((b > a, c > b, e > c))                         # which of the lists A, B, C the item has
             if b > a:
                 a_tail.add(int((v[b - 1] >= 0).sum()))              # live rows of the A list's last step
             if c > b:
                 b_tail.add(int((v[c - 1, :2] >= 0).sum()))          # live halves of the B list's last step
     assert {0, 1, 2, 15, 16, 17, 33} <= per_wave, per_wave
+    assert {127, 128, 129} <= lengths and min(lengths) < 8, lengths  # 8 waves x 2 or 4 steps divides 128: nb == 0 at the closing flush
+    assert {(True, True, True), (False, True, True), (True, False, True), (False, False, True), (True, False, False)} <= lists, lists
     assert {1, 2, 3, 4} <= a_tail and {1, 2} <= b_tail, (a_tail, b_tail)
     short = [int((g.route_hub.block_row[-16:] >= 0).sum()) for g, _ in out.values()]
     assert 1 in short and 3 in short, short                          # blocks with fewer than 16 rows

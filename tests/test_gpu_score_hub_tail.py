@@ -6,7 +6,9 @@ slot L & 3 of the batch's step number L >> 2 — and runs one sigmoid and one st
 and once behind its last step.  The pair ids of a batch are read per lane when the batch opens.  What can go wrong depends
 on how many steps a wave has and on where in a batch a list ends, so the lists here are chosen by the steps per wave
 they give: 0, 1 and 2 (a rest only), 15, 16 (one full batch whose flush coincides with the end of the item), 17, 31, 32, 33
-(two flushes and a rest of one), 35 and 36 with the transitions A -> B -> C inside batches, the last steps of A and of B and
+(two flushes and a rest of one), 35 and 36 with the transitions A -> B -> C inside batches, an item of 129 steps over all
+three lists (one more than 8 waves x 16: besides 127 and 128 the lengths at which the closing flush changes — the walk and
+the batch counter are dl_hub.h's, shared with the routing kernel), the last steps of A and of B and
 a C step as a wave's 16th and 17th (dead slots at a batch's end and start), and many short items.  With want_coef the kernel
 stores per step as before; those cases run the same lists.
 
@@ -38,12 +40,13 @@ LISTS = {
     "0/0/3": ((0, 0, 3), 4096),
     "0/0/127": ((0, 0, 127), 4096),
     "0/0/255": ((0, 0, 255), 4096),
+    "100/120/44": ((100, 120, 44), 4096),
     "20/16/12, items of 8": ((20, 16, 12), 8),
 }
 # steps per wave the issue's plans give (the first seven lists), and by arithmetic the next two
 WANT_PER_WAVE = {"512/0/0": {16}, "0/0/130": {16, 17}, "0/0/264": {33}, "100/120/200": {35, 36}, "509/3/1": {16, 17},
-                 "61/0/0": {2}, "0/0/3": {0, 1}, "0/0/127": {15, 16}, "0/0/255": {31, 32}}
-WANT_ITEM_STEP = {"100/120/200": [0, 25, 85, 285], "509/3/1": [0, 128, 130, 131]}
+                 "61/0/0": {2}, "0/0/3": {0, 1}, "0/0/127": {15, 16}, "0/0/255": {31, 32}, "100/120/44": {16, 17}}
+WANT_ITEM_STEP = {"100/120/200": [0, 25, 85, 285], "509/3/1": [0, 128, 130, 131], "100/120/44": [0, 25, 85, 129]}
 _lists, _tabs, _refs = {}, {}, {}
 
 
@@ -89,7 +92,7 @@ def steps_per_wave(item_step):
 def _plans(fold):
     if fold not in _lists:
         plans = {name: _build(name, fold) for name in LISTS}
-        per_wave = set()
+        per_wave, lengths = set(), set()
         for name, pl in plans.items():
             h = pl.hub
             assert h is not None and h.n_blocks == 1, name
@@ -102,12 +105,14 @@ def _plans(fold):
             if name in WANT_ITEM_STEP:
                 assert st == [WANT_ITEM_STEP[name]], (name, st)
             per_wave |= waves
+            lengths |= {e - a for a, b, c, e in st}
             assert (int((h.step_q2 >= 0).sum()) > 0) if fold else h.step_q2 is None, name
             if nA + nB + nC >= 16:                                   # (0, 0, 3) lists 12 of the 16 rows: unfolded, three partners are hub rows too
                 assert h.block_row.cpu().tolist() == list(range(16)), name
                 assert st[-1][3] == h.n_steps == (nA + 3) // 4 + (nB + 1) // 2 + nC, name
                 assert h.n_entries == nA + 2 * nB + 4 * nC and (h.rest is None) == fold, name
         assert {0, 1, 2, 15, 16, 17, 31, 32, 33} <= per_wave and max(per_wave) >= 35, per_wave
+        assert {127, 128, 129} <= lengths, lengths                  # 8 waves x 16 steps, one less, one more
         _lists[fold] = plans
     return _lists[fold]
 
