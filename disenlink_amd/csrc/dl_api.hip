@@ -51,7 +51,6 @@ static int check_hub(const dl_pair_hub* hp, const char* what, bool need_q2) {
     return DL_OK;
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Workspace layout (256-byte aligned blocks):
 //   dw[E] | dwr[E] | ds[n_total*K] | vec_part[n_slots*K] | row_part[n_slots*2*K*d]

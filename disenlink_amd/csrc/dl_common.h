@@ -29,6 +29,9 @@ static inline unsigned wave_blocks(int n) { return (unsigned)((n + WAVES_PER_BLO
 static inline unsigned seg_blocks(const dl_csr_plan* c) {
     return (unsigned)c->n_slices * wave_blocks(c->slice_max_seg);
 }
+// workspace layouts: every part starts on a 256-byte boundary; counts of tiles, chunks and ranges round up
+static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ---- device helpers ---------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (DL_WAVE - 1); }

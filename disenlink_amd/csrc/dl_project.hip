@@ -4,7 +4,8 @@
 // DL_PROJECT_FP32_MFMA=1 — v_mfma_f32_32x32x2_f32, which is bit-for-bit a k-ordered fmaf chain; either way
 // the result keeps the reference's fp32 semantics up to rounding / summation order.
 //
-// Two-layer form (Factor2): one workgroup = 8 waves = 128 nodes x ONE factor k, looping over (a group
+// Two-layer form (Factor2), one kernel per arithmetic: project2_fwd_planes_kernel and project2_fwd_f32_kernel.  In both,
+// one workgroup = 8 waves = 128 nodes x ONE factor k, looping over (a group
 // of) 128-unit chunks of the hidden layer.  Waves are 4 x 2: node quarter wn, hidden half wh; each wave
 // owns a (64 hidden) x (32 nodes) tile = two independent accumulators; two waves share a SIMD, so one
 // wave's LDS reads and barrier waits hide behind the other's MFMA chain.
@@ -27,17 +28,12 @@
 #include <cstdlib>
 #include "dl_common.h"
 #include "dl_kernels.h"
-#include "dl_tiles.h"
+#include "dl_project.h"
 
 namespace dl {
 namespace project {
 
-constexpr int TN = 128;       // nodes per workgroup (4 wave quarters x 32)
 constexpr int TH = 128;       // hidden units per chunk (2 wave halves x 64)
-// feature chunk staged per step: 64 (one barrier per 64 MFMAs of a wave) where the registers allow, else 32;
-// LDS row pitch of the operand tiles = FC + 4 floats
-constexpr int fwd_fc(int D) { return D <= 64 ? 64 : 32; }
-constexpr int NTHR = 512;
 
 // stage rows [row0, row0+rows) x cols [col0, col0+cols) of a row-major [n_rows][n_cols] matrix into
 // LDS with leading dimension ld (zero fill outside the matrix)
@@ -80,8 +76,8 @@ __device__ __forceinline__ float4 zero4(const float4& q, int base, int n) {
 // was read straight from there by every wave, one K = 16 group ahead of its use: 16 bytes per lane from 32 different rows
 // per instruction (a quarter of every 128-byte line used), and a global round trip per group that no prefetch depth hid
 // (stamps: 9,000 cycles per chunk for 48 MFMAs = 1,536 cycles of issue).  Now the whole workgroup
-// copies the slice with fully coalesced 16-byte loads (issued at the top of the chunk's last layer-1 step) into the LDS tile
-// buffer that step has just finished reading, and layer 2 takes its A operands from there with ds_read_b128.
+// copies the slice with fully coalesced 16-byte loads (issued between the MFMA blocks of the chunk's last layer-1 step) into
+// the LDS tile buffer that step has just finished reading, and layer 2 takes its A operands from there with ds_read_b128.
 template <int D, int THREADS>
 struct W2Stage {
     static constexpr int PIECES = 3 * D * 16;                  // 16-byte pieces: 3 planes x D rows x (128 hidden / 8)
@@ -140,35 +136,275 @@ struct PlaneDma {
     }
 };
 
-// Two-layer projection.  W1 [K][nhid][F], b1 [K][nhid], W2 [K][D][nhid], b2 [K][D].
-// VEC: F % 4 == 0 and nhid % 4 == 0.  1-D grid of xcd_grid(node tiles of 128, K * G hidden-chunk groups).
-// out: Z [N][K][D] with b2 != nullptr (G == 1), or slab [G][N][K][D] of partial sums with b2 == nullptr.
-// SPLIT: layer 1 on the bf16 matrix path from three bf16 planes per operand (dl_tiles.h: fp32-grade accuracy at a
-// multiple of the fp32 MFMA rate); x and W1 arrive as padded plane arrays (dl_planes.hip) and the [128][32] tiles are
-// copied without masks.  VEC then only says nhid % 4 == 0 (W2 / b1 quads).
+// ---- what the two forward kernels share ----------------------------------------------------------------------
+// Both take one argument list (one launcher, one dispatch): W1 [K][nhid][F], b1 [K][nhid], W2 [K][D][nhid], b2 [K][D];
+// 1-D grid of xcd_grid(node tiles of 128, K * G hidden-chunk groups); out: Z [N][K][D] with b2 != nullptr (G == 1), or slab
+// [G][N][K][D] of partial sums with b2 == nullptr; hid_out != nullptr: the hidden layer is kept, hidT [K][nhid][ldh].
 struct FwdPlanes {
     const __bf16* x; const __bf16* w; size_t w_batch; int ncb;     // tile-major planes of x and of the K matrices W1_k
     const __bf16* w2; size_t w2_ps; int nhid_p;                    // planes [3][K*D][nhid_p] of W2 in layer 2's k-slot order
 };
 
-template <int D, bool VEC, bool SPLIT>
-__global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restrict__ x, int N, int F, int nhid,
-                                                            const float* __restrict__ W1, const float* __restrict__ b1,
-                                                            const float* __restrict__ W2, const float* __restrict__ b2,
-                                                            float* __restrict__ out, int K, int G, int chunks_per_group,
-                                                            float* __restrict__ hid_out, int ldh, FwdPlanes P) {
+// bias + ReLU on hidT (row = hidden unit, column = node) in the accumulator registers: quad g of a tile = its hidden rows
+// 8g + 4*half .. +3, b their biases (zero past nhid)
+__device__ __forceinline__ void bias_relu(f32x16& acc, int g, const float4& b) {
+    acc[4 * g + 0] = fmaxf(acc[4 * g + 0] + b.x, 0.0f);
+    acc[4 * g + 1] = fmaxf(acc[4 * g + 1] + b.y, 0.0f);
+    acc[4 * g + 2] = fmaxf(acc[4 * g + 2] + b.z, 0.0f);
+    acc[4 * g + 3] = fmaxf(acc[4 * g + 3] + b.w, 0.0f);
+}
+
+// Z hand-over, after the last step's barrier.  The two hidden halves (wh = 0, 1) of a node quarter hold partial Z sums: wave
+// wh = 1 hands its half over through LDS (z_give; red is [wn][dt][16][64]), the workgroup meets at a barrier, and wave wh = 0
+// adds (fixed order), adds b2 (nullptr: a slab of partial sums) and stores its node's row orow of factor k (z_take;
+// registers 4g..4g+3 are 4 consecutive dd of node column li).
+template <int DT>
+__device__ __forceinline__ void z_give(float* red, const f32x16 (&zacc)[DT], int wn, int lane) {
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) red[((wn * DT + dt) * 16 + r) * 64 + lane] = zacc[dt][r];
+}
+// registers 4g .. 4g+3 of acc + the four values handed over for them (rows row .. row+3 of red) + bb -> 4 consecutive dd at o4
+__device__ __forceinline__ void z_take(float* o4, const f32x16& acc, int g, const float* red, int row, int lane, const float4& bb) {
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = acc[4 * g + j] + red[(row + j) * 64 + lane];
+    *reinterpret_cast<float4*>(o4) = make_float4(o[0] + bb.x, o[1] + bb.y, o[2] + bb.z, o[3] + bb.w);
+}
+
+// ---- the bf16-plane forward ----------------------------------------------------------------------------------
+// Both layers on the bf16 matrix path from three bf16 planes per operand (dl_tiles.h: fp32-grade accuracy at a multiple of
+// the fp32 MFMA rate).  x and W1 arrive as padded, tile-major plane arrays (dl_planes.hip) and their [128][32] tiles are
+// copied without masks, so no instantiation depends on the alignment of F or nhid; of the fp32 arguments only the biases
+// are read.  LDS: two parity buffers, each [3][TN][SPLIT_PITCH] (x tile) followed by [3][TH][SPLIT_PITCH] (W1 tile) — one
+// buffer is one contiguous block, it also takes the W2 slice of a chunk's layer 2 (W2Stage) — and behind them bias_s, the
+// 128 biases of the current hidden chunk.
+constexpr size_t project2_planes_lds(int D) {
+    const size_t red = sizeof(float) * 4 * (D / 32) * 16 * 64;                 // the Z hand-over at the end
+    const size_t stage = sizeof(__bf16) * 2 * 3 * (TN + TH) * SPLIT_PITCH + sizeof(float) * TH;
+    return stage > red ? stage : red;
+}
+
+template <int D>
+__global__ __launch_bounds__(NTHR) void project2_fwd_planes_kernel(const float* __restrict__ /* x */, int N, int /* F */, int nhid,
+                                                                   const float* __restrict__ /* W1 */, const float* __restrict__ b1,
+                                                                   const float* __restrict__ /* W2 */, const float* __restrict__ b2,
+                                                                   float* __restrict__ out, int K, int G, int chunks_per_group,
+                                                                   float* __restrict__ hid_out, int ldh, FwdPlanes P) {
     constexpr int DT = D / 32;
-    constexpr int FC = SPLIT ? SPLIT_COLS : fwd_fc(D), LDT = FC + 4;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* xs = lds;                               // [2][TN][LDT]
-    float* w1s = xs + 2 * TN * LDT;                // [2][TH][LDT]
-    // SPLIT: two parity buffers, each [3][TN][SPLIT_PITCH] (x tile) followed by [3][TH][SPLIT_PITCH] (W1 tile): one buffer is
-    // one contiguous block (it also takes the W2 slice of a chunk's layer 2, W2Stage)
     constexpr int XBUF = 3 * TN * SPLIT_PITCH, PBUF = 3 * (TN + TH) * SPLIT_PITCH;
     __bf16* pbuf = reinterpret_cast<__bf16*>(lds);
-    constexpr bool W2LDS = SPLIT && D <= 64 && (size_t)W2Stage<D, NTHR>::PITCH * 3 * D <= (size_t)PBUF;
-    float* bias_s = reinterpret_cast<float*>(pbuf + 2 * PBUF);      // SPLIT: the 128 biases of the current hidden chunk
+    constexpr bool W2LDS = D <= 64 && (size_t)W2Stage<D, NTHR>::PITCH * 3 * D <= (size_t)PBUF;
+    float* bias_s = reinterpret_cast<float*>(pbuf + 2 * PBUF);
     float bias_q = 0.0f;
+    const XcdItem item = xcd_item(blockIdx.x, (N + TN - 1) / TN, K * G);
+    if (!item.valid) return;
+    const int k = item.b % K, grp = item.b / K;
+    const int n0 = item.a * TN;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 31, half = lane >> 5;
+    const int wn = wave >> 1, wh = wave & 1;
+    const float* b1k = b1 + (size_t)k * nhid;
+    const int nfc = P.ncb, nhc = (nhid + TH - 1) / TH;
+    const int hc0 = grp * chunks_per_group;
+    const int steps = nfc * max(0, min(chunks_per_group, nhc - hc0));
+
+    static_assert(TN == PLANE_ROWS && TH == PLANE_ROWS, "tiles of the plane arrays");
+    PlaneDma dma;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    dma.init(wave_s, lane);
+    // both tiles of step s straight into its parity buffer (which every wave left at the barrier before)
+    auto dma_tile = [&](int s) {
+        const int hc = hc0 + s / nfc, fc = s % nfc;
+        dma.issue(P.x + plane_tile<SPLIT_COLS>(item.a, fc, P.ncb), pbuf + (s & 1) * PBUF, wave_s);
+        dma.issue(P.w + (size_t)k * P.w_batch + plane_tile<SPLIT_COLS>(hc, fc, P.ncb), pbuf + (s & 1) * PBUF + XBUF, wave_s);
+    };
+
+    f32x16 hacc[2], zacc[DT];
+#pragma unroll
+    for (int ht = 0; ht < 2; ++ht) zero_acc(hacc[ht]);
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) zero_acc(zacc[dt]);
+
+    if (steps > 0) {
+        dma_tile(0);                                              // tiles 0 and 1 on their way into the two buffers together
+        if (steps > 1) dma_tile(1);
+    }
+    wait_vmem();
+    __syncthreads();
+    for (int s = 0; s < steps; ++s) {
+        const int hc = hc0 + s / nfc, fc = s % nfc;
+        const bool last = fc == nfc - 1;
+        const int hbase = hc * TH + wh * 64;                    // first hidden unit of this wave's tile
+        // tile s + 1 into the other buffer — free since the barrier that ended step s - 1 — with the whole step to land
+        // (tile 1 left in the prologue); the barrier at the end of this step waits for it (vmcnt(0) + s_barrier)
+        if (s >= 1 && s + 1 < steps) dma_tile(s + 1);
+        // Apart from the tile, nothing is requested from global memory at the top of a step.  s_waitcnt vmcnt counts in
+        // issue order, and the compiler cannot tell loads apart at the join of the `last` branch (it waits for vmcnt(0)): with
+        // the register-staged tiles this kernel had before LDS-DMA, a load issued HERE made the mid-step stash of the next tile
+        // sit out a whole global round trip (stamps: +2,800 cycles in every chunk's last step).  The chunk's biases and the
+        // W2 slice are requested between the step's MFMA blocks instead (below); the biases — asked for a step ahead — go to
+        // LDS here, at the top of the chunk's last step.  (F <= 32, one step per chunk: requested here, staged before their use.)
+        if (tid < TH) {
+            if (nfc == 1) {
+                const int h = hc * TH + tid;
+                bias_q = b1k[h < nhid ? h : 0];
+                bias_q = h < nhid ? bias_q : 0.0f;
+            } else if (last) {
+                bias_s[tid] = bias_q;
+            }
+        }
+        // the A operand of layer 2 for group grp = (d-tile, hidden tile, K = 16 block): one 16-byte load per plane
+        auto load_w2p = [&](bf16x8 (&a)[3], int grp) {
+            const int dt = grp >> 2, ht = (grp >> 1) & 1, b = grp & 1;
+            if constexpr (W2LDS) {                               // the slice staged in this step's (already read) tile buffer
+                const __bf16* src = pbuf + (s & 1) * PBUF + (dt * 32 + li) * W2Stage<D, NTHR>::PITCH + wh * 64 + ht * 32 + 16 * b + 8 * half;
+#pragma unroll
+                for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(src + p * D * W2Stage<D, NTHR>::PITCH);
+            } else {
+                const __bf16* src = P.w2 + ((size_t)k * D + dt * 32 + li) * P.nhid_p + hbase + ht * 32 + 16 * b + 8 * half;
+#pragma unroll
+                for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(src + p * P.w2_ps);
+            }
+        };
+        constexpr int W2PF = 1;     // groups in flight (the first issued a layer-1 step ahead; three measured no faster)
+        bf16x8 w2a[W2PF + 1][3];
+        W2Stage<D, NTHR> w2st;
+        // lane half h supplies features 8h .. 8h+7 of each 16-wide block: A = W1 rows (two hidden tiles), B = x rows
+        const __bf16* xb = pbuf + (s & 1) * PBUF + (wn * 32 + li) * SPLIT_PITCH + half * 8;
+        const __bf16* wb = pbuf + (s & 1) * PBUF + XBUF + (wh * 64 + li) * SPLIT_PITCH + half * 8;
+        // both K = 16 blocks of the chunk are read up front: block 1's LDS latency hides behind block 0's MFMAs
+        bf16x8 a0[2][3], a1[2][3], b[2][3];
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                b[kb][p] = *reinterpret_cast<const bf16x8*>(xb + p * TN * SPLIT_PITCH + kb * 16);
+                a0[kb][p] = *reinterpret_cast<const bf16x8*>(wb + p * TH * SPLIT_PITCH + kb * 16);
+                a1[kb][p] = *reinterpret_cast<const bf16x8*>(wb + (p * TH + 32) * SPLIT_PITCH + kb * 16);
+            }
+        mfma_split6(hacc[0], a0[0], b[0]);
+        mfma_split6(hacc[1], a1[0], b[0]);
+        // the step's other global requests, between the two MFMA blocks (see the top of the step): the chunk's 128
+        // biases — one float per thread of the first two waves, a step ahead of their use — and, in the chunk's last
+        // step, the W2 operand of layer 2.  (Staging in waves 4..7 before their first MFMA block instead, beside their
+        // SIMD partners' MFMAs, measured slower: 90.7 -> 95.4 us at the bench shape, 675 -> 748 at F = 2,088, 845 -> 868
+        // at d = 128.)  Kept a lambda: written inline, the same code compiles to a different register allocation.
+        auto stage_work = [&]() {
+            if (nfc >= 2 && fc == nfc - 2 && tid < TH) {
+                const int h = hc * TH + tid;
+                bias_q = b1k[h < nhid ? h : 0];
+                bias_q = h < nhid ? bias_q : 0.0f;
+            }
+            if (last) {
+                if constexpr (W2LDS) {
+                    w2st.fetch(P.w2, P.w2_ps, (size_t)k * D, P.nhid_p, hc * TH, tid);  // coalesced; lands under the rest of the step
+                } else {
+#pragma unroll
+                    for (int q = 0; q < W2PF; ++q) load_w2p(w2a[q], q);
+                }
+            }
+        };
+        stage_work();
+        mfma_split6(hacc[0], a0[1], b[1]);
+        mfma_split6(hacc[1], a1[1], b[1]);
+        if (last) {
+            if (nfc == 1 && tid < TH) bias_s[tid] = bias_q;
+            __syncthreads();        // the biases are staged; every wave has this step's operands in registers: the tile buffer is free
+            float4 bias[2][4];                                  // staged as zeros past nhid
+#pragma unroll
+            for (int ht = 0; ht < 2; ++ht)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    bias[ht][g] = *reinterpret_cast<const float4*>(bias_s + wh * 64 + ht * 32 + 8 * g + 4 * half);
+#pragma unroll
+            for (int ht = 0; ht < 2; ++ht)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) bias_relu(hacc[ht], g, bias[ht][g]);
+            if (hid_out != nullptr) {                           // keep the hidden layer for the backward: hidT[k][h][n]
+                const int n = n0 + wn * 32 + li;
+#pragma unroll
+                for (int ht = 0; ht < 2; ++ht)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int h = hbase + ht * 32 + acc_row(r, half);
+                        if (h < nhid && n < N) hid_out[((size_t)k * nhid + h) * ldh + n] = hacc[ht][r];
+                    }
+            }
+            // layer 2 straight from the registers, on the bf16 matrix path too: the post-ReLU accumulators split into
+            // their three planes (slot s of block b = register 8b + s), W2 comes pre-split in the matching order.  Written out,
+            // not split_acc_block (dl_project.h): through it the d <= 64 forms lose two waits and d = 64 takes four more registers.
+            bf16x8 hp[2][2][3];
+#pragma unroll
+            for (int ht = 0; ht < 2; ++ht)
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int s8 = 0; s8 < 8; ++s8) {
+                        __bf16 hi, mid, lo;
+                        split3(hacc[ht][8 * b + s8], hi, mid, lo);
+                        hp[ht][b][0][s8] = hi; hp[ht][b][1][s8] = mid; hp[ht][b][2][s8] = lo;
+                    }
+            if constexpr (W2LDS) {
+                // the slice was requested between this step's MFMA blocks (half a layer-1 step, the bias / ReLU and the plane split ago)
+                w2st.stash(pbuf + (s & 1) * PBUF, tid);
+                __syncthreads();                                 // the staged slice is complete
+#pragma unroll
+                for (int q = 0; q < W2PF; ++q) load_w2p(w2a[q], q);
+            }
+#pragma unroll
+            for (int grp = 0; grp < 4 * DT; ++grp) {
+                if (grp + W2PF < 4 * DT) load_w2p(w2a[(grp + W2PF) % (W2PF + 1)], grp + W2PF);
+                mfma_split6(zacc[grp >> 2], w2a[grp % (W2PF + 1)], hp[(grp >> 1) & 1][grp & 1]);
+            }
+#pragma unroll
+            for (int ht = 0; ht < 2; ++ht) zero_acc(hacc[ht]);
+        }
+        // LDS-DMA data is ordered for a ds_read only by the issuing wave's vmcnt followed by a barrier the reader has passed;
+        // the workgroup fence of __syncthreads() waits for LDS operations only.  (hipcc already emitted this wait here, for
+        // the pending bias load: written out so that the tile of step s + 1 does not depend on that.)
+        wait_vmem();
+        __syncthreads();
+    }
+    if (wh == 1) z_give<DT>(lds, zacc, wn, lane);
+    __syncthreads();
+    const int n = n0 + wn * 32 + li;
+    if (wh == 0 && n < N) {
+        float* orow = out + (((size_t)grp * N + n) * K + k) * D;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int dd = dt * 32 + 8 * g + 4 * half;
+                float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (b2 != nullptr) bb = *reinterpret_cast<const float4*>(b2 + (size_t)k * D + dd);
+                z_take(orow + dd, zacc[dt], g, lds, (wn * DT + dt) * 16 + 4 * g, lane, bb);
+            }
+    }
+}
+
+// ---- the fp32-MFMA forward -----------------------------------------------------------------------------------
+// Both layers by v_mfma_f32_32x32x2_f32, straight from x, W1 and W2 (no workspace, no planes).  VEC: F % 4 == 0 and
+// nhid % 4 == 0 (tile rows, W2 rows and b1 are sequences of aligned quads).  LDS: xs [2][TN][LDT], w1s [2][TH][LDT].
+constexpr size_t project2_f32_lds(int D) {
+    const size_t red = sizeof(float) * 4 * (D / 32) * 16 * 64;                 // the Z hand-over at the end
+    const size_t stage = sizeof(float) * (2 * TN + 2 * TH) * (fwd_fc(D) + 4);
+    return stage > red ? stage : red;
+}
+
+template <int D, bool VEC>
+__global__ __launch_bounds__(NTHR) void project2_fwd_f32_kernel(const float* __restrict__ x, int N, int F, int nhid,
+                                                                const float* __restrict__ W1, const float* __restrict__ b1,
+                                                                const float* __restrict__ W2, const float* __restrict__ b2,
+                                                                float* __restrict__ out, int K, int G, int chunks_per_group,
+                                                                float* __restrict__ hid_out, int ldh, FwdPlanes /* none */) {
+    constexpr int DT = D / 32;
+    constexpr int FC = fwd_fc(D), LDT = FC + 4;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* xs = lds;
+    float* w1s = xs + 2 * TN * LDT;
     const XcdItem item = xcd_item(blockIdx.x, (N + TN - 1) / TN, K * G);
     if (!item.valid) return;
     const int k = item.b % K, grp = item.b / K;
@@ -179,35 +415,21 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
     const float* W1k = W1 + (size_t)k * nhid * F;
     const float* W2k = W2 + (size_t)k * D * nhid;
     const float* b1k = b1 + (size_t)k * nhid;
-    const int nfc = SPLIT ? P.ncb : (F + FC - 1) / FC, nhc = (nhid + TH - 1) / TH;
+    const int nfc = (F + FC - 1) / FC, nhc = (nhid + TH - 1) / TH;
     const int hc0 = grp * chunks_per_group;
     const int steps = nfc * max(0, min(chunks_per_group, nhc - hc0));
 
+    // the fp32 tiles of step s into registers, and from there into its parity buffer
     TileStage<TN, FC, VEC, NTHR> xt;
     TileStage<TH, FC, VEC, NTHR> wt;
-    static_assert(TN == PLANE_ROWS && TH == PLANE_ROWS, "tiles of the plane arrays");
-    PlaneDma dma;
-    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    if constexpr (SPLIT) dma.init(wave_s, lane);
-    // SPLIT: both tiles of step s straight into its parity buffer (which every wave left at the barrier before)
-    auto dma_tile = [&](int s) {
-        const int hc = hc0 + s / nfc, fc = s % nfc;
-        dma.issue(P.x + plane_tile<SPLIT_COLS>(item.a, fc, P.ncb), pbuf + (s & 1) * PBUF, wave_s);
-        dma.issue(P.w + (size_t)k * P.w_batch + plane_tile<SPLIT_COLS>(hc, fc, P.ncb), pbuf + (s & 1) * PBUF + XBUF, wave_s);
-    };
-    // !SPLIT: the fp32 tiles of step s into registers, and from there into its parity buffer
     auto fetch = [&](int s) {
-        if constexpr (!SPLIT) {
-            const int hc = hc0 + s / nfc, fc = s % nfc;
-            xt.fetch(x + (size_t)n0 * F + fc * FC, F, N - n0, F - fc * FC, tid);
-            wt.fetch(W1k + (size_t)hc * TH * F + fc * FC, F, nhid - hc * TH, F - fc * FC, tid);
-        }
+        const int hc = hc0 + s / nfc, fc = s % nfc;
+        xt.fetch(x + (size_t)n0 * F + fc * FC, F, N - n0, F - fc * FC, tid);
+        wt.fetch(W1k + (size_t)hc * TH * F + fc * FC, F, nhid - hc * TH, F - fc * FC, tid);
     };
     auto stash = [&](int s) {
-        if constexpr (!SPLIT) {
-            xt.template stash<LDT>(xs + (s & 1) * TN * LDT, tid);
-            wt.template stash<LDT>(w1s + (s & 1) * TH * LDT, tid);
-        }
+        xt.template stash<LDT>(xs + (s & 1) * TN * LDT, tid);
+        wt.template stash<LDT>(w1s + (s & 1) * TH * LDT, tid);
     };
     // W2_k[dt*32 + li][hidden quad g of tile ht]: the A operand of layer 2 for d-tile dt
     auto load_w2 = [&](float4 (&wv)[2][4], int dt, int hbase) {
@@ -224,169 +446,47 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) zero_acc(zacc[dt]);
 
-    // !SPLIT software pipeline (one register set per tile, write-after-barrier): during step s the registers hold
+    // Software pipeline (one register set per tile, write-after-barrier): during step s the registers hold
     // tile s+1, whose global loads were issued one step earlier; it goes to the other LDS buffer in the shadow
     // of the first MFMA block of step s (every wave left that buffer at the barrier before), and the loads of
     // tile s+2 are issued right behind it.
     if (steps > 0) {
-        if constexpr (SPLIT) {
-            dma_tile(0);                                          // tiles 0 and 1 on their way into the two buffers together
-            if (steps > 1) dma_tile(1);
-        } else {
-            fetch(0);
-            stash(0);
-            if (steps > 1) fetch(1);
-        }
+        fetch(0);
+        stash(0);
+        if (steps > 1) fetch(1);
     }
-    if constexpr (SPLIT) wait_vmem();
     __syncthreads();
     for (int s = 0; s < steps; ++s) {
         const int hc = hc0 + s / nfc, fc = s % nfc;
         const bool last = fc == nfc - 1;
         const int hbase = hc * TH + wh * 64;                    // first hidden unit of this wave's tile
-        if constexpr (SPLIT) {
-            // tile s + 1 into the other buffer — free since the barrier that ended step s - 1 — with the whole step to land
-            // (tile 1 left in the prologue); the barrier at the end of this step waits for it (vmcnt(0) + s_barrier)
-            if (s >= 1 && s + 1 < steps) dma_tile(s + 1);
-        }
         float4 bias[2][4], wnext[2][4];                         // quad g of tile ht = hidden rows 8g+4*half .. +3
-        if constexpr (!SPLIT) {
-            if (last) {
+        if (last) {                                             // raw loads, a whole step ahead; zero4 at the use
 #pragma unroll
-                for (int ht = 0; ht < 2; ++ht)
+            for (int ht = 0; ht < 2; ++ht)
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) bias[ht][g] = load4_raw<VEC>(b1k, hbase + ht * 32 + 8 * g + 4 * half, nhid);
-                load_w2(wnext, 0, hbase);
-            }
+                for (int g = 0; g < 4; ++g) bias[ht][g] = load4_raw<VEC>(b1k, hbase + ht * 32 + 8 * g + 4 * half, nhid);
+            load_w2(wnext, 0, hbase);
         }
-        // SPLIT: apart from the tile, nothing is requested from global memory at the top of a step.  s_waitcnt vmcnt counts in
-        // issue order, and the compiler cannot tell loads apart at the join of the `last` branch (it waits for vmcnt(0)): with
-        // the register-staged tiles this kernel had before LDS-DMA, a load issued HERE made the mid-step stash of the next tile
-        // sit out a whole global round trip (stamps: +2,800 cycles in every chunk's last step).  The chunk's biases and the
-        // W2 slice are requested between the step's MFMA blocks instead (below); the biases — asked for a step ahead — go to
-        // LDS here, at the top of the chunk's last step.  (F <= 32, one step per chunk: requested here, staged before their use.)
-        if constexpr (SPLIT) {
-            if (tid < TH) {
-                if (nfc == 1) {
-                    const int h = hc * TH + tid;
-                    bias_q = b1k[h < nhid ? h : 0];
-                    bias_q = h < nhid ? bias_q : 0.0f;
-                } else if (last) {
-                    bias_s[tid] = bias_q;
-                }
-            }
-        }
-        // SPLIT: the A operand of layer 2 for group grp = (d-tile, hidden tile, K = 16 block): one 16-byte load per plane
-        auto load_w2p = [&](bf16x8 (&a)[3], int grp) {
-            const int dt = grp >> 2, ht = (grp >> 1) & 1, b = grp & 1;
-            if constexpr (W2LDS) {                               // the slice staged in this step's (already read) tile buffer
-                const __bf16* src = pbuf + (s & 1) * PBUF + (dt * 32 + li) * W2Stage<D, NTHR>::PITCH + wh * 64 + ht * 32 + 16 * b + 8 * half;
+        Layer1F32<FC, LDT, 2, false> l1{xs + (s & 1) * TN * LDT + (wn * 32 + li) * LDT + half * (FC / 2),
+                                        w1s + (s & 1) * TH * LDT + (wh * 64 + li) * LDT + half * (FC / 2)};
+        l1.read_block(0);
 #pragma unroll
-                for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(src + p * D * W2Stage<D, NTHR>::PITCH);
-            } else {
-                const __bf16* src = P.w2 + ((size_t)k * D + dt * 32 + li) * P.nhid_p + hbase + ht * 32 + 16 * b + 8 * half;
-#pragma unroll
-                for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(src + p * P.w2_ps);
-            }
-        };
-        constexpr int W2PF = 1;     // groups in flight (the first issued a layer-1 step ahead; three measured no faster)
-        bf16x8 w2a[W2PF + 1][3];
-        W2Stage<D, NTHR> w2st;
-        if constexpr (SPLIT) {
-            // lane half h supplies features 8h .. 8h+7 of each 16-wide block: A = W1 rows (two hidden tiles), B = x rows
-            const __bf16* xb = pbuf + (s & 1) * PBUF + (wn * 32 + li) * SPLIT_PITCH + half * 8;
-            const __bf16* wb = pbuf + (s & 1) * PBUF + XBUF + (wh * 64 + li) * SPLIT_PITCH + half * 8;
-            // both K = 16 blocks of the chunk are read up front: block 1's LDS latency hides behind block 0's MFMAs
-            bf16x8 a0[2][3], a1[2][3], b[2][3];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-                    b[kb][p] = *reinterpret_cast<const bf16x8*>(xb + p * TN * SPLIT_PITCH + kb * 16);
-                    a0[kb][p] = *reinterpret_cast<const bf16x8*>(wb + p * TH * SPLIT_PITCH + kb * 16);
-                    a1[kb][p] = *reinterpret_cast<const bf16x8*>(wb + (p * TH + 32) * SPLIT_PITCH + kb * 16);
-                }
-            mfma_split6(hacc[0], a0[0], b[0]);
-            mfma_split6(hacc[1], a1[0], b[0]);
-            // the step's other global requests, between the two MFMA blocks (see the top of the step): the chunk's 128
-            // biases — one float per thread of the first two waves, a step ahead of their use — and, in the chunk's last
-            // step, the W2 operand of layer 2.  (Staging in waves 4..7 before their first MFMA block instead, beside their
-            // SIMD partners' MFMAs, measured slower: 90.7 -> 95.4 us at the bench shape, 675 -> 748 at F = 2,088, 845 -> 868
-            // at d = 128.)  Kept a lambda: written inline, the same code compiles to a different register allocation.
-            auto stage_work = [&]() {
-                if (nfc >= 2 && fc == nfc - 2 && tid < TH) {
-                    const int h = hc * TH + tid;
-                    bias_q = b1k[h < nhid ? h : 0];
-                    bias_q = h < nhid ? bias_q : 0.0f;
-                }
-                if (last) {
-                    if constexpr (W2LDS) {
-                        w2st.fetch(P.w2, P.w2_ps, (size_t)k * D, P.nhid_p, hc * TH, tid);  // coalesced; lands under the rest of the step
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < W2PF; ++q) load_w2p(w2a[q], q);
-                    }
-                }
-            };
-            stage_work();
-            mfma_split6(hacc[0], a0[1], b[1]);
-            mfma_split6(hacc[1], a1[1], b[1]);
-        } else {
-        // lane half h owns features h*FC/2 .. h*FC/2 + FC/2-1 of the chunk; MFMA block j takes 2 quads of them
-        // per operand row (3 ds_read_b128, 16 MFMAs), block j+1's reads are issued ahead of block j's MFMAs
-        const float* xb = xs + (s & 1) * TN * LDT + (wn * 32 + li) * LDT + half * (FC / 2);
-        const float* wb = w1s + (s & 1) * TH * LDT + (wh * 64 + li) * LDT + half * (FC / 2);
-        constexpr int NB = FC / 16;
-        float4 a[2][2][2], b[2][2];                             // [parity of block][...]
-        auto read_block = [&](int j) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                b[j & 1][q] = *reinterpret_cast<const float4*>(xb + 8 * j + 4 * q);
-                a[j & 1][0][q] = *reinterpret_cast<const float4*>(wb + 8 * j + 4 * q);
-                a[j & 1][1][q] = *reinterpret_cast<const float4*>(wb + 32 * LDT + 8 * j + 4 * q);
-            }
-        };
-        read_block(0);
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            if (j + 1 < NB) read_block(j + 1);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                DL_MFMA(hacc[0], a[j & 1][0][q].x, b[j & 1][q].x);
-                DL_MFMA(hacc[1], a[j & 1][1][q].x, b[j & 1][q].x);
-                DL_MFMA(hacc[0], a[j & 1][0][q].y, b[j & 1][q].y);
-                DL_MFMA(hacc[1], a[j & 1][1][q].y, b[j & 1][q].y);
-                DL_MFMA(hacc[0], a[j & 1][0][q].z, b[j & 1][q].z);
-                DL_MFMA(hacc[1], a[j & 1][1][q].z, b[j & 1][q].z);
-                DL_MFMA(hacc[0], a[j & 1][0][q].w, b[j & 1][q].w);
-                DL_MFMA(hacc[1], a[j & 1][1][q].w, b[j & 1][q].w);
-            }
+        for (int j = 0; j < l1.NB; ++j) {
+            if (j + 1 < l1.NB) l1.read_block(j + 1);
+            l1.mfma_block(hacc, j);
             if (j == 0) {
                 if (s + 1 < steps) stash(s + 1);
                 if (s + 2 < steps) fetch(s + 2);
             }
         }
-        }   // !SPLIT
         if (last) {
-            if constexpr (SPLIT) {
-                if (nfc == 1 && tid < TH) bias_s[tid] = bias_q;
-                __syncthreads();        // the biases are staged; every wave has this step's operands in registers: the tile buffer is free
-#pragma unroll
-                for (int ht = 0; ht < 2; ++ht)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        bias[ht][g] = *reinterpret_cast<const float4*>(bias_s + wh * 64 + ht * 32 + 8 * g + 4 * half);
-            }
-            // bias + ReLU on hidT (row = hidden unit, column = node), then layer 2 straight from the registers
 #pragma unroll
             for (int ht = 0; ht < 2; ++ht)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    if constexpr (!SPLIT) bias[ht][g] = zero4<VEC>(bias[ht][g], hbase + ht * 32 + 8 * g + 4 * half, nhid);   // (SPLIT: staged as zeros)
-                    hacc[ht][4 * g + 0] = fmaxf(hacc[ht][4 * g + 0] + bias[ht][g].x, 0.0f);
-                    hacc[ht][4 * g + 1] = fmaxf(hacc[ht][4 * g + 1] + bias[ht][g].y, 0.0f);
-                    hacc[ht][4 * g + 2] = fmaxf(hacc[ht][4 * g + 2] + bias[ht][g].z, 0.0f);
-                    hacc[ht][4 * g + 3] = fmaxf(hacc[ht][4 * g + 3] + bias[ht][g].w, 0.0f);
+                    bias[ht][g] = zero4<VEC>(bias[ht][g], hbase + ht * 32 + 8 * g + 4 * half, nhid);
+                    bias_relu(hacc[ht], g, bias[ht][g]);
                 }
             if (hid_out != nullptr) {                           // keep the hidden layer for the backward: hidT[k][h][n]
                 const int n = n0 + wn * 32 + li;
@@ -398,33 +498,7 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
                         if (h < nhid && n < N) hid_out[((size_t)k * nhid + h) * ldh + n] = hacc[ht][r];
                     }
             }
-            if constexpr (SPLIT) {
-                // layer 2 on the bf16 matrix path too: the post-ReLU accumulator is split into its three planes in
-                // registers (slot s of block b = register 8b + s), W2 comes pre-split in the matching order
-                bf16x8 hp[2][2][3];
-#pragma unroll
-                for (int ht = 0; ht < 2; ++ht)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int s8 = 0; s8 < 8; ++s8) {
-                            __bf16 hi, mid, lo;
-                            split3(hacc[ht][8 * b + s8], hi, mid, lo);
-                            hp[ht][b][0][s8] = hi; hp[ht][b][1][s8] = mid; hp[ht][b][2][s8] = lo;
-                        }
-                if constexpr (W2LDS) {
-                    // the slice was requested at the top of this step (a layer-1 step, the bias / ReLU and the plane split ago)
-                    w2st.stash(pbuf + (s & 1) * PBUF, tid);
-                    __syncthreads();                                 // the staged slice is complete
-#pragma unroll
-                    for (int q = 0; q < W2PF; ++q) load_w2p(w2a[q], q);
-                }
-#pragma unroll
-                for (int grp = 0; grp < 4 * DT; ++grp) {
-                    if (grp + W2PF < 4 * DT) load_w2p(w2a[(grp + W2PF) % (W2PF + 1)], grp + W2PF);
-                    mfma_split6(zacc[grp >> 2], w2a[grp % (W2PF + 1)], hp[(grp >> 1) & 1][grp & 1]);
-                }
-            } else {
+            // layer 2 straight from the registers
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
                 float4 wv[2][4];
@@ -443,26 +517,12 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
                         DL_MFMA(zacc[dt], wv[ht][g].w, hacc[ht][4 * g + 3]);
                     }
             }
-            }   // !SPLIT
 #pragma unroll
             for (int ht = 0; ht < 2; ++ht) zero_acc(hacc[ht]);
         }
-        // LDS-DMA data is ordered for a ds_read only by the issuing wave's vmcnt followed by a barrier the reader has passed;
-        // the workgroup fence of __syncthreads() waits for LDS operations only.  (hipcc already emitted this wait here, for
-        // the pending bias load: written out so that the tile of step s + 1 does not depend on that.)
-        if constexpr (SPLIT) wait_vmem();
         __syncthreads();
     }
-    // The two hidden halves (wh = 0, 1) of a node quarter hold partial Z sums: wave wh = 1 hands its half
-    // over through LDS and wave wh = 0 adds (fixed order), adds b2 and stores (registers 4g..4g+3 are 4
-    // consecutive dd of node column li).
-    float* red = lds;                                           // [wn][dt][16][64]
-    if (wh == 1) {
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[((wn * DT + dt) * 16 + r) * 64 + lane] = zacc[dt][r];
-    }
+    if (wh == 1) z_give<DT>(lds, zacc, wn, lane);
     __syncthreads();
     const int n = n0 + wn * 32 + li;
     if (wh == 0 && n < N) {
@@ -474,19 +534,9 @@ __global__ __launch_bounds__(NTHR) void project2_fwd_kernel(const float* __restr
                 const int dd = dt * 32 + 8 * g + 4 * half;
                 float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (b2 != nullptr) bb = *reinterpret_cast<const float4*>(b2 + (size_t)k * D + dd);
-                float o[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = zacc[dt][4 * g + j] + red[((wn * DT + dt) * 16 + 4 * g + j) * 64 + lane];
-                *reinterpret_cast<float4*>(orow + dd) = make_float4(o[0] + bb.x, o[1] + bb.y, o[2] + bb.z, o[3] + bb.w);
+                z_take(orow + dd, zacc[dt], g, lds, (wn * DT + dt) * 16 + 4 * g, lane, bb);
             }
     }
-}
-
-
-constexpr size_t project2_lds(int D, bool split) {
-    const size_t red = sizeof(float) * 4 * (D / 32) * 16 * 64;                 // the Z hand-over at the end
-    const size_t stage = split ? sizeof(__bf16) * 2 * 3 * (TN + TH) * SPLIT_PITCH + sizeof(float) * TH : sizeof(float) * (2 * TN + 2 * TH) * (fwd_fc(D) + 4);
-    return stage > red ? stage : red;
 }
 
 // Z[n][c] = b2[c] + sum_g slab[g][n][c] (g ascending), c over K*D; 4 columns per thread.
@@ -587,18 +637,17 @@ static int fwd_block_rows(int N) {
 struct FwdLayout { int G, R, nhid_p; size_t off_xp, off_wp, off_w2p, bytes; };
 static FwdLayout fwd_layout(int N, int F, int K, int nhid, int d) {
     FwdLayout L{};
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     L.R = fwd_block_rows(N);
     L.G = L.R < N ? 1 : project2_groups(N, K, nhid);
-    size_t off = L.G > 1 ? al(sizeof(float) * (size_t)L.G * N * K * d) : 0;
+    size_t off = L.G > 1 ? align256(sizeof(float) * (size_t)L.G * N * K * d) : 0;
     L.off_xp = off;
     if (split_products()) {
-        off += al(sizeof(__bf16) * project::plane_array_elems(L.R, F, project::SPLIT_COLS));
+        off += align256(sizeof(__bf16) * project::plane_array_elems(L.R, F, project::SPLIT_COLS));
         L.off_wp = off;
-        off += al(sizeof(__bf16) * K * project::plane_array_elems(nhid, F, project::SPLIT_COLS));
+        off += align256(sizeof(__bf16) * K * project::plane_array_elems(nhid, F, project::SPLIT_COLS));
         L.off_w2p = off;
         L.nhid_p = (int)project::round_up(nhid, project::TH);
-        off += al(sizeof(__bf16) * 3 * (size_t)K * d * L.nhid_p);
+        off += align256(sizeof(__bf16) * 3 * (size_t)K * d * L.nhid_p);
     }
     L.bytes = off;
     return L;
@@ -609,9 +658,9 @@ size_t project_fwd_workspace_bytes(int N, int F, int K, int nhid, int d, bool tw
     return fwd_layout(N, F, K, nhid, d).bytes;
 }
 
-// What the two-layer forward does with a workspace of ws_bytes: which project2_fwd_kernel<D, VEC, SPLIT> runs, over how
-// many hidden-chunk groups, in how many launches of how many rows, and whether persistent x planes serve it.  project_fwd
-// dispatches on exactly this.  A layout of 0 bytes (fp32 MFMA, one group) needs no workspace, so it fits with or without one:
+// What the two-layer forward does with a workspace of ws_bytes: which kernel runs (split: project2_fwd_planes_kernel<D>,
+// where vec selects nothing; else project2_fwd_f32_kernel<D, vec>), over how many hidden-chunk groups, in how many launches of
+// how many rows, and whether persistent x planes serve it.  project_fwd dispatches on exactly this.  A layout of 0 bytes (fp32 MFMA, one group) needs no workspace, so it fits with or without one:
 // the form then does not depend on whether the caller's empty workspace has an address.
 struct FwdForm { bool fits, split, vec, xplanes; int G, cpg, R, launches; };
 static FwdForm fwd_form(const FwdLayout& L, int N, int F, int nhid, bool have_ws, size_t ws_bytes, bool have_xplanes) {
@@ -641,17 +690,15 @@ void project_fwd_form(int N, int F, int K, int nhid, int d, bool two_layer, size
     std::copy(two, two + 7, out);
 }
 
-template <int D, bool VEC, bool SPLIT>
+template <auto KERNEL, size_t LDS>
 static void launch2_t(int N, int K, int G, int cpg, hipStream_t st, const float* x, int F, int nhid, const float* W1,
                       const float* b1, const float* W2, const float* b2, float* out, float* hid_out, int ldh,
                       project::FwdPlanes P) {
     using namespace project;
     static unsigned long long lds_done = 0;
-    constexpr size_t lds = project2_lds(D, SPLIT);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&project2_fwd_kernel<D, VEC, SPLIT>), lds, lds_done);
+    ensure_dynamic_lds(reinterpret_cast<const void*>(KERNEL), LDS, lds_done);
     const dim3 grid((unsigned)xcd_grid((N + TN - 1) / TN, K * G));
-    hipLaunchKernelGGL((project2_fwd_kernel<D, VEC, SPLIT>), grid, dim3(NTHR), lds, st, x, N, F, nhid, W1, b1, W2, b2,
-                       out, K, G, cpg, hid_out, ldh, P);
+    hipLaunchKernelGGL(KERNEL, grid, dim3(NTHR), LDS, st, x, N, F, nhid, W1, b1, W2, b2, out, K, G, cpg, hid_out, ldh, P);
 }
 
 // Persistent planes of the (constant) feature matrix: [x planes, 32-column tiles | x^T planes, 16-column tiles], both
@@ -660,12 +707,11 @@ static void launch2_t(int N, int K, int G, int cpg, hipStream_t st, const float*
 size_t project_xplanes_bytes(int N, int F) {
     using namespace project;
     if (N <= 0 || F <= 0) return 0;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    return al(sizeof(__bf16) * plane_array_elems(N, F, SPLIT_COLS)) + al(sizeof(__bf16) * plane_array_elems(F, N, PLANE_ROWS));
+    return align256(sizeof(__bf16) * plane_array_elems(N, F, SPLIT_COLS)) + align256(sizeof(__bf16) * plane_array_elems(F, N, PLANE_ROWS));
 }
 static size_t xplanes_xT_offset(int N, int F) {
     using namespace project;
-    return (sizeof(__bf16) * plane_array_elems(N, F, SPLIT_COLS) + 255) & ~(size_t)255;
+    return align256(sizeof(__bf16) * plane_array_elems(N, F, SPLIT_COLS));
 }
 const void* project_xplanes_xT(const void* xplanes, int N, int F) {
     return xplanes ? static_cast<const char*>(xplanes) + xplanes_xT_offset(N, F) : nullptr;
@@ -722,10 +768,9 @@ int project_fwd(const float* x, int N, int F, int K, int nhid, int d, const floa
         if (split && form.R < N) split_rows(xb, 1, rows, F, F, 0, const_cast<__bf16*>(P.x), st);
 #define DL_P2(DD)                                                                                       \
     if (d == DD) {                                                                                      \
-        if (split && vec) launch2_t<DD, true, true>(rows, K, G, cpg, st, xb, F, nhid, W1, b1, W2, bias2, ob, hb, ldh, P);   \
-        else if (split) launch2_t<DD, false, true>(rows, K, G, cpg, st, xb, F, nhid, W1, b1, W2, bias2, ob, hb, ldh, P);    \
-        else if (vec) launch2_t<DD, true, false>(rows, K, G, cpg, st, xb, F, nhid, W1, b1, W2, bias2, ob, hb, ldh, P);      \
-        else launch2_t<DD, false, false>(rows, K, G, cpg, st, xb, F, nhid, W1, b1, W2, bias2, ob, hb, ldh, P);              \
+        if (split) launch2_t<project2_fwd_planes_kernel<DD>, project2_planes_lds(DD)>(rows, K, G, cpg, st, xb, F, nhid, W1, b1, W2, bias2, ob, hb, ldh, P);   \
+        else if (vec) launch2_t<project2_fwd_f32_kernel<DD, true>, project2_f32_lds(DD)>(rows, K, G, cpg, st, xb, F, nhid, W1, b1, W2, bias2, ob, hb, ldh, P);  \
+        else launch2_t<project2_fwd_f32_kernel<DD, false>, project2_f32_lds(DD)>(rows, K, G, cpg, st, xb, F, nhid, W1, b1, W2, bias2, ob, hb, ldh, P);          \
     }
         DL_P2(32) DL_P2(64) DL_P2(128)
 #undef DL_P2

@@ -1,10 +1,10 @@
 // Backward of the factor projection on the matrix cores: the weight gradients of the K factor MLPs
 // (autograd of model.py:13-15, 24-27 as driven by main_disentangled.py:198).  x is data: no dx.
 //
-//   two-layer:   hid = relu(x W1_k^T + b1_k)               recomputed, never read from HBM
-//                dhid = (dZ_k W2_k) . [hid > 0]            -> workspace [N][K][nhid]
-//                dW2_k = dZ_k^T hid,  db1_k = colsum(dhid)  (kernel A: project2_bwd_hidden_kernel)
-//                dW1_k = dhid^T x                           (kernel B: nodes_contract_kernel)
+//   two-layer:   hid = relu(x W1_k^T + b1_k)               recomputed, or kept by the forward
+//                dhid = (dZ_k W2_k) . [hid > 0]            -> workspace [N][K][nhid], or planes of dhid_k^T
+//                dW2_k = dZ_k^T hid,  db1_k = colsum(dhid)  (kernel A: project2_bwd_hidden_f32_kernel / _planes_kernel)
+//                dW1_k = dhid^T x                           (kernel B: nodes_contract_kernel / _planes_kernel)
 //                db2   = colsum(dZ)                         (colsum_kernel)
 //   one layer:   dW_k = dZ_k^T x (kernel B),  db = colsum(dZ)
 //
@@ -20,67 +20,84 @@
 #include <cstdlib>
 #include "dl_common.h"
 #include "dl_kernels.h"
-#include "dl_tiles.h"
+#include "dl_project.h"
 
 namespace dl {
 namespace project {
 
-constexpr int TILE_N = 128;   // nodes per workgroup step (4 wave quarters x 32)
-constexpr int BFC = 32;       // feature chunk staged per step
 constexpr int LDB = BFC + 4;  // LDS row pitch of the layer-1 operand tiles
-constexpr int BTHR = 512;
 
 // hidden units per workgroup of kernel A: 2 wave halves x HT tiles of 32 (HT = 1 for D = 128: LDS budget)
 constexpr int bwd_ht(int D) { return D <= 64 ? 2 : 1; }
 
 // ------------------------------------------------------------------------------------------------
-// Kernel A.  1-D grid of xcd_grid(S node ranges, hidden chunks of 64*HT x K); one workgroup = 8 waves = 128 nodes per
-// node tile: node quarter wn (32 nodes) x hidden half wh (32*HT units).  Same write-after-barrier staging
-// pipeline as the forward kernel (dl_project.hip).  Per node tile, once the layer-1 sum over F is complete:
-//   hid  = relu(acc + b1)                       [node][hidden]: node rows in registers, hidden on lanes
-//   dW2 += dZ^T . hid                           A = dZ^T from LDS (b32), B = hid registers
-//   dhid = (dZ . W2^T) masked by hid > 0        A = dZ rows, B = W2^T rows, both b128 from LDS
-// VEC: F % 4 == 0 (x and W1 rows are sequences of aligned quads).
-// RECOMPUTE = false: the forward kept the hidden layer (hidT [K][nhid][ldh], post-ReLU); it is read straight into the
-// B-operand registers (lane = hidden unit, 4 consecutive nodes per register quad) and layer 1 is not run again.
-// PLANES: dhid leaves as the tile-major bf16 planes of dhid_k^T ([hidden][node], 16-node tiles: the A operand of
+// Kernel A, one kernel per arithmetic: project2_bwd_hidden_f32_kernel (fp32 MFMA; layer 1 recomputed or the kept hidden
+// layer) and project2_bwd_hidden_planes_kernel (kept hidden layer, bf16 matrix path).  Both: 1-D grid of xcd_grid(S node
+// ranges, hidden chunks of 64*HT x K); one workgroup = 8 waves = 128 nodes per node tile: node quarter wn (32 nodes) x hidden
+// half wh (32*HT units); one argument list, one launcher.  Per node tile:
+//   hid  = relu(acc + b1), or the kept hidT     [node][hidden]: node rows in registers, hidden on lanes
+//   dW2 += dZ^T . hid                           B = hid registers
+//   dhid = (dZ . W2^T) masked by hid > 0
+// Kept hidden layer: hidT [K][nhid][ldh], post-ReLU, as the forward wrote it; it is read straight into the B-operand
+// registers (lane = hidden unit, 4 consecutive nodes per register quad) and layer 1 is not run again.
+// dhid as planes: the tile-major bf16 planes of dhid_k^T ([hidden][node], 16-node tiles: the A operand of
 // nodes_contract_planes_kernel) instead of fp32 [node][K][hidden]; every element of the padded array that kernel
 // reads along the node axis is written (zeros past N and past nhid).
 struct DhidPlanes { __bf16* base; size_t batch; int ncb; };       // factor k at base + k * batch; ncb 16-node chunks per row block
 
-// LDS bytes of kernel A (also used by its launcher below)
-constexpr size_t project2_bwd_lds_bytes(int D) {
-    const size_t ht = D <= 64 ? 2 : 1;
-    const size_t stage = 2 * 128 * (32 + 4) + 2 * 64 * ht * (32 + 4) + 128 * (size_t)(D + 4) + 64 * ht * (size_t)(D + 4);
-    const size_t red = 8 * (size_t)((D / 32) * ht * 16 + ht) * 64;
+// LDS bytes of both: [layer-1 tiles xs, w1s | dZ tile | W2^T chunk] in fp32, re-used for the cross-wave reduction at the end
+constexpr size_t project2_bwd_lds(int D) {
+    const size_t stage = 2 * TN * LDB + 2 * 64 * bwd_ht(D) * LDB + TN * (D + 4) + 64 * bwd_ht(D) * (D + 4);
+    const size_t red = 8 * (size_t)((D / 32) * bwd_ht(D) * 16 + bwd_ht(D)) * 64;
     return sizeof(float) * (stage > red ? stage : red);
 }
 
-template <int D, bool VEC, bool RECOMPUTE, bool PLANES>
-__global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
+// bit r: hid[r] > 0 (the mask of the dhid epilogue)
+__device__ __forceinline__ unsigned relu_bits_of(const float (&hid)[16]) {
+    unsigned bits = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bits |= (hid[r] > 0.0f ? 1u : 0u) << r;
+    return bits;
+}
+
+// The dW2 / db1 partials of a workgroup's node range leave through LDS: every wave gives its accumulators (red is
+// [8 waves][RW][64 lanes], RW = DT * HT * 16 + HT floats per lane: w2acc, then b1acc), the workgroup meets at a barrier, and
+// waves 0 (wh = 0) and 1 (wh = 1) add the 4 node quarters in fixed order and write out.
+template <int DT, int HT>
+__device__ __forceinline__ void red_give(float* red, const f32x16 (&w2acc)[DT][HT], const float (&b1acc)[HT], int wave, int lane) {
+    constexpr int RW = DT * HT * 16 + HT;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) red[(wave * RW + (dt * HT + ht) * 16 + r) * 64 + lane] = w2acc[dt][ht][r];
+#pragma unroll
+    for (int ht = 0; ht < HT; ++ht) red[(wave * RW + DT * HT * 16 + ht) * 64 + lane] = b1acc[ht];
+}
+
+// ---- kernel A on fp32 MFMA -----------------------------------------------------------------------------------
+// RECOMPUTE: layer 1 runs again, with the write-after-barrier staging pipeline of the forward (dl_project.hip); VEC: F % 4 == 0
+// (x and W1 rows are sequences of aligned quads).  !RECOMPUTE: the kept hidden layer (it reads no x / W1 rows: always the
+// aligned instantiation).  PLANES_OUT: dhid leaves as planes.  The kept hidden layer with dhid as planes is
+// project2_bwd_hidden_planes_kernel.
+//   dW2 += dZ^T . hid                           A = dZ^T from LDS (b32), B = hid registers
+//   dhid = (dZ . W2^T) masked by hid > 0        A = dZ rows, B = W2^T rows, both b128 from LDS
+template <int D, bool VEC, bool RECOMPUTE, bool PLANES_OUT>
+__global__ __launch_bounds__(NTHR) void project2_bwd_hidden_f32_kernel(
     const float* __restrict__ x, int N, int F, int nhid, const float* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ W2, const float* __restrict__ dZ, int K, int tiles_per_range,
     float* __restrict__ dhid, float* __restrict__ dW2p, float* __restrict__ db1p,
     const float* __restrict__ hidT, int ldh, int hid_cols, DhidPlanes dhp) {
+    static_assert(RECOMPUTE || (VEC && !PLANES_OUT), "the kept hidden layer: one fp32 form");
     constexpr int DT = D / 32, HT = bwd_ht(D), HB = 64 * HT;
     constexpr int LDZ = D + 4;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* xs = lds;                               // [2][TILE_N][LDB]
-    float* w1s = xs + 2 * TILE_N * LDB;            // [2][HB][LDB]
-    float* dzs = w1s + 2 * HB * LDB;               // [TILE_N][LDZ]   dZ_k rows of the current node tile
-    float* w2t = dzs + TILE_N * LDZ;               // [HB][LDZ]       W2_k[:, chunk]^T, staged once
-    // BF (round 5; kept hidden layer, d <= 64): both products of a node tile — dW2 += dZ^T . hid and dhid = dZ . W2^T — on
-    // the bf16 matrix path from three bf16 planes per operand (dl_tiles.h: six exact products per term, fp32-grade) instead
-    // of fp32 MFMA: 96 MFMAs of 32 cycles per wave and tile instead of 128 of 64 (stamps: fp32 MFMA
-    // issue was 58 % of a tile).  dZ tile and W2^T chunk live in LDS as planes [3][rows][ZP]; the A operand of the node
-    // contraction (dZ^T: lane = dd, k-slots = 8 nodes) comes out of the [node][dd] image by the transposed LDS read
-    // ds_read_b64_tr_b16; its B operand is the hidden layer in registers, split in place (slot s of block b = register 8b + s).
-    constexpr bool BF = PLANES && !RECOMPUTE;
-    static_assert(!BF || sizeof(__bf16) * 3 * (TILE_N + HB) * (D + 8) <= project2_bwd_lds_bytes(D), "planes of the dZ tile and the W2^T chunk fit the kernel's LDS");
-    constexpr int ZP = D + 8;                      // plane row pitch (bf16): 16-byte rows reads conflict-free, 8-byte aligned
-    __bf16* dzp = reinterpret_cast<__bf16*>(lds);  // BF: [3][TILE_N][ZP]
-    __bf16* w2p = dzp + 3 * TILE_N * ZP;           //     [3][HB][ZP]      W2_k[:, chunk]^T as planes
-    const int n_tiles = (N + TILE_N - 1) / TILE_N;
+    float* xs = lds;                               // [2][TN][LDB]
+    float* w1s = xs + 2 * TN * LDB;                // [2][HB][LDB]
+    float* dzs = w1s + 2 * HB * LDB;               // [TN][LDZ]   dZ_k rows of the current node tile
+    float* w2t = dzs + TN * LDZ;                   // [HB][LDZ]   W2_k[:, chunk]^T, staged once
+    const int n_tiles = (N + TN - 1) / TN;
     const int nhc = (nhid + HB - 1) / HB;
     // a = node range (shares the x tiles), b = (hidden chunk, factor) (shares the W1 chunk): see xcd_item
     const XcdItem item = xcd_item(blockIdx.x, (n_tiles + tiles_per_range - 1) / tiles_per_range, nhc * K);
@@ -101,28 +118,20 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
     {   // W2^T chunk: w2t[h][dd] = W2_k[dd][hc*HB + h].  All loads first, then the LDS stores: written as one loop the
         // compiler waited for every load before its store — 16 global round trips in a row, 16,000 cycles of a workgroup's
         // 183,000 (stamps).
-        constexpr int NW = HB * D / BTHR;
-        static_assert(HB * D % BTHR == 0, "the W2^T chunk divides over the workgroup");
+        constexpr int NW = HB * D / NTHR;
+        static_assert(HB * D % NTHR == 0, "the W2^T chunk divides over the workgroup");
         float wv[NW];
 #pragma unroll
         for (int j = 0; j < NW; ++j) {
-            const int i = tid + j * BTHR, dd = i / HB, h = i - dd * HB;
+            const int i = tid + j * NTHR, dd = i / HB, h = i - dd * HB;
             const int hh = hc * HB + h;
             wv[j] = W2k[(size_t)dd * nhid + (hh < nhid ? hh : 0)];
             wv[j] = hh < nhid ? wv[j] : 0.0f;
         }
 #pragma unroll
         for (int j = 0; j < NW; ++j) {
-            const int i = tid + j * BTHR, dd = i / HB, h = i - dd * HB;
-            if constexpr (BF) {
-                __bf16 hi, mid, lo;
-                split3(wv[j], hi, mid, lo);
-                w2p[(0 * HB + h) * ZP + dd] = hi;
-                w2p[(1 * HB + h) * ZP + dd] = mid;
-                w2p[(2 * HB + h) * ZP + dd] = lo;
-            } else {
-                w2t[h * LDZ + dd] = wv[j];
-            }
+            const int i = tid + j * NTHR, dd = i / HB, h = i - dd * HB;
+            w2t[h * LDZ + dd] = wv[j];
         }
     }
     float b1v[HT];
@@ -132,17 +141,17 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
         b1v[ht] = h < nhid ? b1[(size_t)k * nhid + h] : 0.0f;
     }
 
-    TileStage<TILE_N, BFC, VEC, BTHR> xt;
-    TileStage<HB, BFC, VEC, BTHR> wt;
-    TileStage<TILE_N, D, true, BTHR> zt;           // dZ rows: D % 32 == 0, row stride K*D: always aligned quads
+    TileStage<TN, BFC, VEC, NTHR> xt;
+    TileStage<HB, BFC, VEC, NTHR> wt;
+    TileStage<TN, D, true, NTHR> zt;               // dZ rows: D % 32 == 0, row stride K*D: always aligned quads
     auto fetch = [&](int s) {
         const int tl = s / nfc, fc = s % nfc;
-        const int n0 = (tile0 + tl) * TILE_N;
+        const int n0 = (tile0 + tl) * TN;
         xt.fetch(x + (size_t)n0 * F + fc * BFC, F, N - n0, F - fc * BFC, tid);
         wt.fetch(W1k + (size_t)hc * HB * F + fc * BFC, F, nhid - hc * HB, F - fc * BFC, tid);
     };
     auto stash = [&](int s) {
-        xt.template stash<LDB>(xs + (s & 1) * TILE_N * LDB, tid);
+        xt.template stash<LDB>(xs + (s & 1) * TN * LDB, tid);
         wt.template stash<LDB>(w1s + (s & 1) * HB * LDB, tid);
     };
 
@@ -158,7 +167,7 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
     for (int ht = 0; ht < HT; ++ht) b1acc[ht] = 0.0f;
 
     // Kept hidden layer: hidT rows of this wave's hidden units, quad g = nodes 8g + 4*half .. +3 of its node quarter.
-    // Raw loads from clamped addresses; the masking happens at the use (hq_masked), so a tile's loads can be issued
+    // Raw loads from clamped addresses; the masking happens at the use, so a tile's loads can be issued
     // one tile ahead, behind the MFMAs of the current one.
     float4 hraw[HT][4];
     auto load_hq = [&](int n0t) {
@@ -179,76 +188,36 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
         if (steps > 1) fetch(1);
     }
     if (!RECOMPUTE && steps > 0) {
-        zt.fetch(dZk + (size_t)tile0 * TILE_N * K * D, K * D, N - tile0 * TILE_N, D, tid);
-        load_hq(tile0 * TILE_N);
+        zt.fetch(dZk + (size_t)tile0 * TN * K * D, K * D, N - tile0 * TN, D, tid);
+        load_hq(tile0 * TN);
     }
     __syncthreads();
     for (int s = 0; s < steps; ++s) {
         const int tl = s / nfc, fc = s % nfc;
         const bool last = fc == nfc - 1;
-        const int n0 = (tile0 + tl) * TILE_N;
+        const int n0 = (tile0 + tl) * TN;
         if (RECOMPUTE && last) zt.fetch(dZk + (size_t)n0 * K * D, K * D, N - n0, D, tid);   // consumed after the MFMAs below
         if constexpr (RECOMPUTE) {
-        // hid[node][hidden] += x[node][f] . W1[hidden][f]: A = x rows of this node quarter, B = W1 rows
-        const float* xb = xs + (s & 1) * TILE_N * LDB + (wn * 32 + li) * LDB + half * (BFC / 2);
-        const float* wb = w1s + (s & 1) * HB * LDB + (wh * 32 * HT + li) * LDB + half * (BFC / 2);
-        constexpr int NB = BFC / 16;
-        float4 a[2][2], b[2][HT][2];
-        auto read_block = [&](int j) {
+            // hid[node][hidden] += x[node][f] . W1[hidden][f]: A = x rows of this node quarter, B = W1 rows
+            Layer1F32<BFC, LDB, HT, true> l1{xs + (s & 1) * TN * LDB + (wn * 32 + li) * LDB + half * (BFC / 2),
+                                             w1s + (s & 1) * HB * LDB + (wh * 32 * HT + li) * LDB + half * (BFC / 2)};
+            l1.read_block(0);
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                a[j & 1][q] = *reinterpret_cast<const float4*>(xb + 8 * j + 4 * q);
-#pragma unroll
-                for (int ht = 0; ht < HT; ++ht)
-                    b[j & 1][ht][q] = *reinterpret_cast<const float4*>(wb + ht * 32 * LDB + 8 * j + 4 * q);
-            }
-        };
-        read_block(0);
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            if (j + 1 < NB) read_block(j + 1);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-#pragma unroll
-                for (int ht = 0; ht < HT; ++ht) DL_MFMA(hacc[ht], a[j & 1][q].x, b[j & 1][ht][q].x);
-#pragma unroll
-                for (int ht = 0; ht < HT; ++ht) DL_MFMA(hacc[ht], a[j & 1][q].y, b[j & 1][ht][q].y);
-#pragma unroll
-                for (int ht = 0; ht < HT; ++ht) DL_MFMA(hacc[ht], a[j & 1][q].z, b[j & 1][ht][q].z);
-#pragma unroll
-                for (int ht = 0; ht < HT; ++ht) DL_MFMA(hacc[ht], a[j & 1][q].w, b[j & 1][ht][q].w);
-            }
-            if (j == 0) {
-                if (s + 1 < steps) stash(s + 1);
-                if (s + 2 < steps) fetch(s + 2);
+            for (int j = 0; j < l1.NB; ++j) {
+                if (j + 1 < l1.NB) l1.read_block(j + 1);
+                l1.mfma_block(hacc, j);
+                if (j == 0) {
+                    if (s + 1 < steps) stash(s + 1);
+                    if (s + 2 < steps) fetch(s + 2);
+                }
             }
         }
-        }   // RECOMPUTE
         if (last) {
             // every wave is past the previous tile's use of dzs (barrier at the end of that step)
-            if constexpr (BF) {                                 // the dZ tile as three bf16 planes [node][dd]
-                const bool full = zt.rows_valid >= TILE_N && zt.cols_valid >= D;
-#pragma unroll
-                for (int j = 0; j < zt.NV / 4; ++j) {
-                    const int i = tid + BTHR * j, r = i / (D / 4), c = 4 * (i % (D / 4));
-                    const unsigned m = (full || (r < zt.rows_valid && c < zt.cols_valid)) ? 0xFFFFFFFFu : 0u;
-                    bf16x4 p0, p1, p2;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        __bf16 hi, mid, lo;
-                        split3(mask_bits(zt.v[4 * j + e], m), hi, mid, lo);
-                        p0[e] = hi; p1[e] = mid; p2[e] = lo;
-                    }
-                    *reinterpret_cast<bf16x4*>(dzp + (0 * TILE_N + r) * ZP + c) = p0;
-                    *reinterpret_cast<bf16x4*>(dzp + (1 * TILE_N + r) * ZP + c) = p1;
-                    *reinterpret_cast<bf16x4*>(dzp + (2 * TILE_N + r) * ZP + c) = p2;
-                }
-            } else {
-                zt.template stash<LDZ>(dzs, tid);
-            }
+            zt.template stash<LDZ>(dzs, tid);
             __syncthreads();
             float hid[HT][16];
-            unsigned relu_bits[HT];                             // bit r: hid[ht][r] > 0 (the mask of the dhid epilogue)
+            unsigned relu_bits[HT];
 #pragma unroll
             for (int ht = 0; ht < HT; ++ht) {
                 if constexpr (RECOMPUTE) {
@@ -268,53 +237,14 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
                         hid[ht][4 * g + 3] = mask_bits(hraw[ht][g].w, ok && n + 3 < N ? 0xFFFFFFFFu : 0u);
                     }
                 }
-                relu_bits[ht] = 0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) relu_bits[ht] |= (hid[ht][r] > 0.0f ? 1u : 0u) << r;
+                relu_bits[ht] = relu_bits_of(hid[ht]);
             }
             // kept form: the next tile's dZ rows and hidden quads are fetched behind this tile's MFMAs (unconditional —
             // the last tile is fetched twice — see TileStage, dl_tiles.h)
-            const int n0n = (tile0 + min(tl + 1, my_tiles - 1)) * TILE_N;
+            const int n0n = (tile0 + min(tl + 1, my_tiles - 1)) * TN;
             if constexpr (!RECOMPUTE) zt.fetch(dZk + (size_t)n0n * K * D, K * D, N - n0n, D, tid);
             // dW2[dd][hidden] += dZ[node][dd] . hid[node][hidden]: the k-pair of register r is the node pair
             // {acc_row(r,0), acc_row(r,1)} of this quarter
-            if constexpr (BF) {
-                // B operand: the hidden layer split in place — registers 8b .. 8b+7 of lane half t are the nodes
-                // 16b + 8(s>>2) + 4t + (s&3), s = 0..7, of this node quarter: the 8 k-slots of K = 16 block b
-                bf16x8 hidp[HT][2][3];
-#pragma unroll
-                for (int ht = 0; ht < HT; ++ht)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int s8 = 0; s8 < 8; ++s8) {
-                            __bf16 hi, mid, lo;
-                            split3(hid[ht][8 * b + s8], hi, mid, lo);
-                            hidp[ht][b][0][s8] = hi; hidp[ht][b][1][s8] = mid; hidp[ht][b][2][s8] = lo;
-                        }
-                // A operand: dZ^T[dd = dt*32 + li][those 8 nodes] by two transposed reads per plane (4 node rows x 16 dd
-                // columns per group of 16 lanes: lane 4q+p gives the address of row q, columns 4p..4p+3, and receives
-                // column (lane & 15) of the 4 rows).  Every lane is active here (the read needs EXEC all ones).
-                const int i16 = lane & 15, trq = i16 >> 2, trp = i16 & 3, cb = (li >> 4) * 16;
-                typedef short v4s __attribute__((ext_vector_type(4)));
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        bf16x8 za[3];
-#pragma unroll
-                        for (int p = 0; p < 3; ++p) {
-                            const __bf16* a0 = dzp + (p * TILE_N + wn * 32 + 16 * b + 4 * half + trq) * ZP + dt * 32 + cb + 4 * trp;
-                            const v4s lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)a0);
-                            const v4s hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(a0 + 8 * ZP));
-                            typedef short v8s __attribute__((ext_vector_type(8)));
-                            const v8s both = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
-                            za[p] = __builtin_bit_cast(bf16x8, both);
-                        }
-#pragma unroll
-                        for (int ht = 0; ht < HT; ++ht) mfma_split6(w2acc[dt][ht], za, hidp[ht][b]);
-                    }
-            } else {
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
                 float zv[16];
@@ -325,30 +255,14 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
 #pragma unroll
                     for (int ht = 0; ht < HT; ++ht) DL_MFMA(w2acc[dt][ht], zv[r], hid[ht][r]);
             }
-            }
             if constexpr (!RECOMPUTE) load_hq(n0n);             // hid has been consumed by the MFMAs above
             // dhid[node][hidden] = dZ[node][dd] . W2^T[hidden][dd], masked by the ReLU
 #pragma unroll
             for (int ht = 0; ht < HT; ++ht) zero_acc(hacc[ht]);
-            if constexpr (BF) {
-#pragma unroll
-                for (int b = 0; b < D / 16; ++b) {              // A = dZ rows of this node quarter, B = W2^T rows, planes from LDS
-                    bf16x8 za[3], vb[HT][3];
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-                        za[p] = *reinterpret_cast<const bf16x8*>(dzp + (p * TILE_N + wn * 32 + li) * ZP + 16 * b + 8 * half);
-#pragma unroll
-                        for (int ht = 0; ht < HT; ++ht)
-                            vb[ht][p] = *reinterpret_cast<const bf16x8*>(w2p + (p * HB + wh * 32 * HT + ht * 32 + li) * ZP + 16 * b + 8 * half);
-                    }
-#pragma unroll
-                    for (int ht = 0; ht < HT; ++ht) mfma_split6(hacc[ht], za, vb[ht]);
-                }
-            }
             const float* za = dzs + (wn * 32 + li) * LDZ + half * (D / 2);
             const float* va = w2t + (wh * 32 * HT + li) * LDZ + half * (D / 2);
 #pragma unroll
-            for (int q = 0; q < (BF ? 0 : D / 8); ++q) {
+            for (int q = 0; q < D / 8; ++q) {
                 const float4 zq = *reinterpret_cast<const float4*>(za + 4 * q);
                 float4 vq[HT];
 #pragma unroll
@@ -370,13 +284,13 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
                 for (int r = 0; r < 16; ++r) {
                     const float g = (relu_bits[ht] >> r) & 1u ? hacc[ht][r] : 0.0f;
                     const int n = n0 + wn * 32 + acc_row(r, half);
-                    if constexpr (!PLANES) {
+                    if constexpr (!PLANES_OUT) {
                         if (n < N && h < nhid) dhid[((size_t)n * K + k) * nhid + h] = g;
                     }
                     colsum += g;
                     hacc[ht][r] = g;
                 }
-                if constexpr (PLANES) {
+                if constexpr (PLANES_OUT) {
                     // Registers 4q..4q+3 of lane half t are the nodes 8q + 4t .. +3 of row h.  A 16-node tile row
                     // (32 bytes per plane) is [t=0,q=0][t=1,q=0][t=0,q=1][t=1,q=1]: the halves swap one quad (half 0
                     // gives its q=1, half 1 its q=0) and each writes 16 contiguous bytes — whole 32-byte sectors.
@@ -416,19 +330,10 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
         }
         __syncthreads();
     }
-    // cross-wave reduction (fixed order over the 4 node quarters) of the dW2 / db1 partials of this range
-    constexpr int RW = DT * HT * 16 + HT;                       // floats per lane and wave
-    float* red = lds;                                           // [8 waves][RW][64 lanes]
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int ht = 0; ht < HT; ++ht)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[(wave * RW + (dt * HT + ht) * 16 + r) * 64 + lane] = w2acc[dt][ht][r];
-#pragma unroll
-    for (int ht = 0; ht < HT; ++ht) red[(wave * RW + DT * HT * 16 + ht) * 64 + lane] = b1acc[ht];
+    constexpr int RW = DT * HT * 16 + HT;
+    red_give<DT, HT>(lds, w2acc, b1acc, wave, lane);
     __syncthreads();
-    if (wn == 0) {                                              // waves 0 (wh = 0) and 1 (wh = 1) write out
+    if (wn == 0) {
         float* out = dW2p + ((size_t)rng * K + k) * D * nhid;
 #pragma unroll
         for (int ht = 0; ht < HT; ++ht) {
@@ -439,13 +344,13 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
                 for (int r = 0; r < 16; ++r) {
                     float v = 0.0f;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) v += red[((2 * q + wh) * RW + (dt * HT + ht) * 16 + r) * 64 + lane];
+                    for (int q = 0; q < 4; ++q) v += lds[((2 * q + wh) * RW + (dt * HT + ht) * 16 + r) * 64 + lane];
                     if (h < nhid) out[(size_t)(dt * 32 + acc_row(r, half)) * nhid + h] = v;
                 }
             float v = 0.0f;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float* p = red + ((2 * q + wh) * RW + DT * HT * 16 + ht) * 64;
+                const float* p = lds + ((2 * q + wh) * RW + DT * HT * 16 + ht) * 64;
                 v += p[li] + p[32 + li];
             }
             if (half == 0 && h < nhid) db1p[((size_t)rng * K + k) * nhid + h] = v;
@@ -453,10 +358,253 @@ __global__ __launch_bounds__(BTHR) void project2_bwd_hidden_kernel(
     }
 }
 
-constexpr size_t project2_bwd_lds(int D) {
-    const size_t stage = 2 * TILE_N * LDB + 2 * 64 * bwd_ht(D) * LDB + TILE_N * (D + 4) + 64 * bwd_ht(D) * (D + 4);
-    const size_t red = 8 * (size_t)((D / 32) * bwd_ht(D) * 16 + bwd_ht(D)) * 64;
-    return sizeof(float) * (stage > red ? stage : red);
+// ---- kernel A on the bf16 matrix path ------------------------------------------------------------------------
+// Kept hidden layer, dhid as planes (round 5).  Both products of a node tile — dW2 += dZ^T . hid and dhid = dZ . W2^T — from
+// three bf16 planes per operand (dl_tiles.h: six exact products per term, fp32-grade) instead of fp32 MFMA: 96 MFMAs of 32
+// cycles per wave and tile instead of 128 of 64 (stamps: fp32 MFMA issue was 58 % of a tile).  dZ tile and W2^T chunk live in
+// LDS as planes [3][rows][ZP]; the A operand of the node contraction (dZ^T: lane = dd, k-slots = 8 nodes) comes out of the
+// [node][dd] image by the transposed LDS read ds_read_b64_tr_b16; its B operand is the hidden layer in registers, split in
+// place (slot s of block b = register 8b + s).  Of x, F, W1 and dhid (fp32) nothing is read or written.
+template <int D>
+__global__ __launch_bounds__(NTHR) void project2_bwd_hidden_planes_kernel(
+    const float* __restrict__ /* x */, int N, int /* F */, int nhid, const float* __restrict__ /* W1 */, const float* __restrict__ /* b1 */,
+    const float* __restrict__ W2, const float* __restrict__ dZ, int K, int tiles_per_range,
+    float* __restrict__ /* dhid */, float* __restrict__ dW2p, float* __restrict__ db1p,
+    const float* __restrict__ hidT, int ldh, int hid_cols, DhidPlanes dhp) {
+    constexpr int DT = D / 32, HT = bwd_ht(D), HB = 64 * HT;
+    constexpr int ZP = D + 8;                      // plane row pitch (bf16): 16-byte rows reads conflict-free, 8-byte aligned
+    static_assert(sizeof(__bf16) * 3 * (TN + HB) * ZP <= project2_bwd_lds(D), "planes of the dZ tile and the W2^T chunk fit the kernel's LDS");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __bf16* dzp = reinterpret_cast<__bf16*>(lds);  // [3][TN][ZP]   dZ_k rows of the current node tile
+    __bf16* w2p = dzp + 3 * TN * ZP;               // [3][HB][ZP]   W2_k[:, chunk]^T, staged once
+    const int n_tiles = (N + TN - 1) / TN;
+    const int nhc = (nhid + HB - 1) / HB;
+    // a = node range, b = (hidden chunk, factor): see xcd_item
+    const XcdItem item = xcd_item(blockIdx.x, (n_tiles + tiles_per_range - 1) / tiles_per_range, nhc * K);
+    if (!item.valid) return;
+    const int hc = item.b % nhc, k = item.b / nhc, rng = item.a;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 31, half = lane >> 5;
+    const int wn = wave >> 1, wh = wave & 1;
+    const int tile0 = rng * tiles_per_range;
+    const int my_tiles = max(0, min(tiles_per_range, n_tiles - tile0));
+    const float* W2k = W2 + (size_t)k * D * nhid;
+    const float* dZk = dZ + (size_t)k * D;         // row n at dZk + n*K*D
+    const int hw0 = hc * HB + wh * 32 * HT;        // first hidden unit of this wave
+
+    {   // W2^T chunk as planes: w2p[plane][h][dd] = W2_k[dd][hc*HB + h].  All loads first, then the LDS stores (see the fp32 kernel)
+        constexpr int NW = HB * D / NTHR;
+        static_assert(HB * D % NTHR == 0, "the W2^T chunk divides over the workgroup");
+        float wv[NW];
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            const int i = tid + j * NTHR, dd = i / HB, h = i - dd * HB;
+            const int hh = hc * HB + h;
+            wv[j] = W2k[(size_t)dd * nhid + (hh < nhid ? hh : 0)];
+            wv[j] = hh < nhid ? wv[j] : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            const int i = tid + j * NTHR, dd = i / HB, h = i - dd * HB;
+            __bf16 hi, mid, lo;
+            split3(wv[j], hi, mid, lo);
+            w2p[(0 * HB + h) * ZP + dd] = hi;
+            w2p[(1 * HB + h) * ZP + dd] = mid;
+            w2p[(2 * HB + h) * ZP + dd] = lo;
+        }
+    }
+    TileStage<TN, D, true, NTHR> zt;               // dZ rows: D % 32 == 0, row stride K*D: always aligned quads
+    f32x16 hacc[HT], w2acc[DT][HT];
+#pragma unroll
+    for (int ht = 0; ht < HT; ++ht) {
+        zero_acc(hacc[ht]);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) zero_acc(w2acc[dt][ht]);
+    }
+    float b1acc[HT];
+#pragma unroll
+    for (int ht = 0; ht < HT; ++ht) b1acc[ht] = 0.0f;
+
+    // kept hidden layer: raw loads from clamped addresses, masked at the use (see the fp32 kernel)
+    float4 hraw[HT][4];
+    auto load_hq = [&](int n0t) {
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht) {
+            const int h = hw0 + ht * 32 + li;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int n = n0t + wn * 32 + 8 * g + 4 * half;
+                const bool ok = h < nhid && n + 3 < hid_cols;
+                hraw[ht][g] = *reinterpret_cast<const float4*>(hidT + (ok ? ((size_t)k * nhid + h) * ldh + n : 0));
+            }
+        }
+    };
+    if (my_tiles > 0) {
+        zt.fetch(dZk + (size_t)tile0 * TN * K * D, K * D, N - tile0 * TN, D, tid);
+        load_hq(tile0 * TN);
+    }
+    __syncthreads();
+    for (int tl = 0; tl < my_tiles; ++tl) {
+        const int n0 = (tile0 + tl) * TN;
+        {   // the dZ tile as three bf16 planes [node][dd]; every wave is past the previous tile's use of dzp (barrier at the end of that step)
+            const bool full = zt.rows_valid >= TN && zt.cols_valid >= D;
+#pragma unroll
+            for (int j = 0; j < zt.NV / 4; ++j) {
+                const int i = tid + NTHR * j, r = i / (D / 4), c = 4 * (i % (D / 4));
+                const unsigned m = (full || (r < zt.rows_valid && c < zt.cols_valid)) ? 0xFFFFFFFFu : 0u;
+                bf16x4 p0, p1, p2;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    __bf16 hi, mid, lo;
+                    split3(mask_bits(zt.v[4 * j + e], m), hi, mid, lo);
+                    p0[e] = hi; p1[e] = mid; p2[e] = lo;
+                }
+                *reinterpret_cast<bf16x4*>(dzp + (0 * TN + r) * ZP + c) = p0;
+                *reinterpret_cast<bf16x4*>(dzp + (1 * TN + r) * ZP + c) = p1;
+                *reinterpret_cast<bf16x4*>(dzp + (2 * TN + r) * ZP + c) = p2;
+            }
+        }
+        __syncthreads();
+        float hid[HT][16];
+        unsigned relu_bits[HT];
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht) {
+            const int h = hw0 + ht * 32 + li;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                // per element, before any MFMA: padding columns of hidT may hold NaN bit patterns (0 * NaN, see the fp32 kernel)
+                const int n = n0 + wn * 32 + 8 * g + 4 * half;
+                const bool ok = h < nhid && n + 3 < hid_cols;
+                hid[ht][4 * g + 0] = mask_bits(hraw[ht][g].x, ok && n + 0 < N ? 0xFFFFFFFFu : 0u);
+                hid[ht][4 * g + 1] = mask_bits(hraw[ht][g].y, ok && n + 1 < N ? 0xFFFFFFFFu : 0u);
+                hid[ht][4 * g + 2] = mask_bits(hraw[ht][g].z, ok && n + 2 < N ? 0xFFFFFFFFu : 0u);
+                hid[ht][4 * g + 3] = mask_bits(hraw[ht][g].w, ok && n + 3 < N ? 0xFFFFFFFFu : 0u);
+            }
+            relu_bits[ht] = relu_bits_of(hid[ht]);
+        }
+        // the next tile's dZ rows and hidden quads are fetched behind this tile's MFMAs (unconditional — the last tile is
+        // fetched twice — see TileStage, dl_tiles.h)
+        const int n0n = (tile0 + min(tl + 1, my_tiles - 1)) * TN;
+        zt.fetch(dZk + (size_t)n0n * K * D, K * D, N - n0n, D, tid);
+        // dW2[dd][hidden] += dZ[node][dd] . hid[node][hidden].  B operand: the hidden layer split in place — registers
+        // 8b .. 8b+7 of lane half t are the nodes 16b + 8(s>>2) + 4t + (s&3), s = 0..7, of this node quarter: the 8 k-slots
+        // of K = 16 block b
+        bf16x8 hidp[HT][2][3];
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) split_acc_block(hid[ht], b, hidp[ht][b]);
+        // A operand: dZ^T[dd = dt*32 + li][those 8 nodes] by two transposed reads per plane (4 node rows x 16 dd
+        // columns per group of 16 lanes: lane 4q+p gives the address of row q, columns 4p..4p+3, and receives
+        // column (lane & 15) of the 4 rows).  Every lane is active here (the read needs EXEC all ones).
+        const int i16 = lane & 15, trq = i16 >> 2, trp = i16 & 3, cb = (li >> 4) * 16;
+        typedef short v4s __attribute__((ext_vector_type(4)));
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                bf16x8 za[3];
+#pragma unroll
+                for (int p = 0; p < 3; ++p) {
+                    const __bf16* a0 = dzp + (p * TN + wn * 32 + 16 * b + 4 * half + trq) * ZP + dt * 32 + cb + 4 * trp;
+                    const v4s lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)a0);
+                    const v4s hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(a0 + 8 * ZP));
+                    typedef short v8s __attribute__((ext_vector_type(8)));
+                    const v8s both = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
+                    za[p] = __builtin_bit_cast(bf16x8, both);
+                }
+#pragma unroll
+                for (int ht = 0; ht < HT; ++ht) mfma_split6(w2acc[dt][ht], za, hidp[ht][b]);
+            }
+        load_hq(n0n);                                           // hid has been consumed by the MFMAs above
+        // dhid[node][hidden] = dZ[node][dd] . W2^T[hidden][dd], masked by the ReLU
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht) zero_acc(hacc[ht]);
+#pragma unroll
+        for (int b = 0; b < D / 16; ++b) {                      // A = dZ rows of this node quarter, B = W2^T rows, planes from LDS
+            bf16x8 za[3], vb[HT][3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                za[p] = *reinterpret_cast<const bf16x8*>(dzp + (p * TN + wn * 32 + li) * ZP + 16 * b + 8 * half);
+#pragma unroll
+                for (int ht = 0; ht < HT; ++ht)
+                    vb[ht][p] = *reinterpret_cast<const bf16x8*>(w2p + (p * HB + wh * 32 * HT + ht * 32 + li) * ZP + 16 * b + 8 * half);
+            }
+#pragma unroll
+            for (int ht = 0; ht < HT; ++ht) mfma_split6(hacc[ht], za, vb[ht]);
+        }
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht) {
+            const int h = hw0 + ht * 32 + li;
+            float colsum = 0.0f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float g = (relu_bits[ht] >> r) & 1u ? hacc[ht][r] : 0.0f;
+                colsum += g;
+                hacc[ht][r] = g;
+            }
+            {   // dhid to the planes of dhid_k^T: the lane halves swap one quad, 16 contiguous bytes each (see the fp32 kernel)
+#pragma unroll
+                for (int qq = 0; qq < 2; ++qq) {
+                    bf16x4 pl[2][3];                                    // [q - 2qq][plane]
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            __bf16 hi, mid, lo;
+                            split3(hacc[ht][4 * (2 * qq + j) + e], hi, mid, lo);
+                            pl[j][0][e] = hi; pl[j][1][e] = mid; pl[j][2][e] = lo;
+                        }
+                    const int n = n0 + wn * 32 + 16 * qq;
+                    __bf16* o = dhp.base + (size_t)k * dhp.batch + plane_tile<16>(h / PLANE_ROWS, n / 16, dhp.ncb) +
+                                (h % PLANE_ROWS) * 16 + half * 8;
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) {
+                        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+                        const u32x2 mine0 = __builtin_bit_cast(u32x2, pl[0][p]), mine1 = __builtin_bit_cast(u32x2, pl[1][p]);
+                        const u32x2 give = half ? mine0 : mine1;
+                        u32x2 got;
+                        got.x = __shfl_xor(give.x, 32);
+                        got.y = __shfl_xor(give.y, 32);
+                        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+                        u32x4 outv;
+                        if (half) { outv.x = got.x; outv.y = got.y; outv.z = mine1.x; outv.w = mine1.y; }
+                        else { outv.x = mine0.x; outv.y = mine0.y; outv.z = got.x; outv.w = got.y; }
+                        *reinterpret_cast<u32x4*>(o + p * PLANE_ROWS * 16) = outv;
+                    }
+                }
+            }
+            b1acc[ht] += colsum;
+            zero_acc(hacc[ht]);
+        }
+        __syncthreads();
+    }
+    constexpr int RW = DT * HT * 16 + HT;
+    red_give<DT, HT>(lds, w2acc, b1acc, wave, lane);
+    __syncthreads();
+    if (wn == 0) {
+        float* out = dW2p + ((size_t)rng * K + k) * D * nhid;
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht) {
+            const int h = hw0 + ht * 32 + li;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float v = 0.0f;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v += lds[((2 * q + wh) * RW + (dt * HT + ht) * 16 + r) * 64 + lane];
+                    if (h < nhid) out[(size_t)(dt * 32 + acc_row(r, half)) * nhid + h] = v;
+                }
+            float v = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float* p = lds + ((2 * q + wh) * RW + DT * HT * 16 + ht) * 64;
+                v += p[li] + p[32 + li];
+            }
+            if (half == 0 && h < nhid) db1p[((size_t)rng * K + k) * nhid + h] = v;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -682,8 +830,6 @@ struct BwdLayout {
     int ncb, n_chunks16;           // 16-node chunks per row block of the plane arrays / chunks that hold nodes
 };
 
-static int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 // Node block of the two-layer backward: the masked hidden gradient of one block ([rows][K][nhid] fp32) is capped
 // at 1 GiB, so the workspace does not grow with the graph (2.9M nodes x K=8 x 512 would be 48 GB); the blocks
 // are processed in order and accumulate into the gradients.
@@ -692,14 +838,13 @@ static int bwd_block_rows(int N, int K, int nhid, bool two_layer) {
     long long cap_bytes = 1LL << 30;
     if (config().bwd_block_bytes > 0) cap_bytes = config().bwd_block_bytes;                 // DL_BWD_BLOCK_BYTES (tests: force blocking)
     const long long cap = cap_bytes / ((long long)K * nhid * (split_products() ? 6 : 4));
-    const long long rows = std::max<long long>(4096, cap / TILE_N * TILE_N);
+    const long long rows = std::max<long long>(4096, cap / TN * TN);
     return (int)std::min<long long>(N, rows);
 }
 
 static BwdLayout bwd_layout(int N, int F, int K, int nhid, int d, bool two_layer, bool blocked = false,
                             bool recompute = true) {
     BwdLayout L{};
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // Node ranges per launch: enough workgroups to cover the 256 CUs (>= 256, at most ~1536 so the partial slabs
     // stay small), but never so many that a workgroup runs fewer than ~24 pipeline steps — its prologue (W2^T
     // staging, first tile) and the slab it writes are per-workgroup costs.  Measured (DL_BWD_TARGET sweeps):
@@ -714,7 +859,7 @@ static BwdLayout bwd_layout(int N, int F, int K, int nhid, int d, bool two_layer
     L.planes = two_layer && split_products();
     L.ncb = plane_chunks<PC>(N, PLANE_ROWS);
     L.n_chunks16 = ceil_div(N, PC);
-    const int n_tiles = ceil_div(N, TILE_N), n_chunks = L.planes ? L.n_chunks16 : ceil_div(N, NC);
+    const int n_tiles = ceil_div(N, TN), n_chunks = L.planes ? L.n_chunks16 : ceil_div(N, NC);
     L.Mb = two_layer ? nhid : d;
     const long long wgA = (long long)ceil_div(nhid, 64 * bwd_ht(d)) * K;
     L.sA = pick(n_tiles, recompute ? ceil_div(F, BFC) : 3, wgA, 24);
@@ -731,16 +876,16 @@ static BwdLayout bwd_layout(int N, int F, int K, int nhid, int d, bool two_layer
     size_t off = 0;
     L.off_dhid = off;
     if (L.planes) {
-        off += al(sizeof(__bf16) * K * plane_array_elems(nhid, N, PLANE_ROWS));
+        off += align256(sizeof(__bf16) * K * plane_array_elems(nhid, N, PLANE_ROWS));
         L.off_xT = off;
-        off += al(sizeof(__bf16) * plane_array_elems(F, N, PLANE_ROWS));
+        off += align256(sizeof(__bf16) * plane_array_elems(F, N, PLANE_ROWS));
     } else {
-        off += two_layer ? al(sizeof(float) * (size_t)N * K * nhid) : 0;
+        off += two_layer ? align256(sizeof(float) * (size_t)N * K * nhid) : 0;
     }
-    L.off_w1p = off;  off += (L.sB > 1 || blocked) ? al(sizeof(float) * (size_t)L.sB * K * L.Mb * F) : 0;
-    L.off_w2p = off;  off += two_layer ? al(sizeof(float) * (size_t)L.sA * K * d * nhid) : 0;
-    L.off_b1p = off;  off += two_layer ? al(sizeof(float) * (size_t)L.sA * K * nhid) : 0;
-    L.off_b2p = off;  off += al(sizeof(float) * (size_t)L.sC * K * d);
+    L.off_w1p = off;  off += (L.sB > 1 || blocked) ? align256(sizeof(float) * (size_t)L.sB * K * L.Mb * F) : 0;
+    L.off_w2p = off;  off += two_layer ? align256(sizeof(float) * (size_t)L.sA * K * d * nhid) : 0;
+    L.off_b1p = off;  off += two_layer ? align256(sizeof(float) * (size_t)L.sA * K * nhid) : 0;
+    L.off_b2p = off;  off += align256(sizeof(float) * (size_t)L.sC * K * d);
     L.bytes = off;
     return L;
 }
@@ -790,26 +935,33 @@ size_t project_bwd_workspace_bytes(int N, int F, int K, int nhid, int d, bool tw
     return bytes;
 }
 
-template <int D, bool VEC, bool RECOMPUTE, bool PLANES>
+template <auto KERNEL, int D>
 static void launchA_t(dim3 grid, hipStream_t st, const float* x, int N, int F, int nhid, const float* W1,
                       const float* b1, const float* W2, const float* dZ, int K, int tpr, float* dhid, float* dW2p,
                       float* db1p, const float* hidT, int ldh, int hid_cols, project::DhidPlanes dhp) {
     using namespace project;
     static unsigned long long lds_done = 0;
     constexpr size_t lds = project2_bwd_lds(D);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&project2_bwd_hidden_kernel<D, VEC, RECOMPUTE, PLANES>), lds, lds_done);
-    hipLaunchKernelGGL((project2_bwd_hidden_kernel<D, VEC, RECOMPUTE, PLANES>), grid, dim3(BTHR), lds, st, x, N, F, nhid, W1,
-                       b1, W2, dZ, K, tpr, dhid, dW2p, db1p, hidT, ldh, hid_cols, dhp);
+    ensure_dynamic_lds(reinterpret_cast<const void*>(KERNEL), lds, lds_done);
+    hipLaunchKernelGGL(KERNEL, grid, dim3(NTHR), lds, st, x, N, F, nhid, W1, b1, W2, dZ, K, tpr, dhid, dW2p, db1p, hidT, ldh,
+                       hid_cols, dhp);
 }
 
+// the kept hidden layer with dhid as planes is the bf16-plane kernel; every other form runs on fp32 MFMA
 template <int D, bool VEC, bool RECOMPUTE>
 static void launchA_p(bool planes, dim3 grid, hipStream_t st, const float* x, int N, int F, int nhid, const float* W1,
                       const float* b1, const float* W2, const float* dZ, int K, int tpr, float* dhid, float* dW2p,
                       float* db1p, const float* hidT, int ldh, int hid_cols, project::DhidPlanes dhp) {
-    if (planes) launchA_t<D, VEC, RECOMPUTE, true>(grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, tpr, dhid, dW2p, db1p, hidT, ldh,
-                                                   hid_cols, dhp);
-    else launchA_t<D, VEC, RECOMPUTE, false>(grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, tpr, dhid, dW2p, db1p, hidT, ldh,
-                                             hid_cols, dhp);
+    using namespace project;
+    if constexpr (!RECOMPUTE) {
+        if (planes) return launchA_t<project2_bwd_hidden_planes_kernel<D>, D>(grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, tpr, dhid, dW2p, db1p,
+                                                                            hidT, ldh, hid_cols, dhp);
+    } else {
+        if (planes) return launchA_t<project2_bwd_hidden_f32_kernel<D, VEC, true, true>, D>(grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, tpr, dhid,
+                                                                                      dW2p, db1p, hidT, ldh, hid_cols, dhp);
+    }
+    launchA_t<project2_bwd_hidden_f32_kernel<D, VEC, RECOMPUTE, false>, D>(grid, st, x, N, F, nhid, W1, b1, W2, dZ, K, tpr, dhid, dW2p, db1p, hidT,
+                                                                          ldh, hid_cols, dhp);
 }
 
 struct SlabBatch {
@@ -908,11 +1060,10 @@ struct KeptLayout { int sA, tiles_per_range, sC, rows_per_range; size_t off_w2p,
 static KeptLayout kept_layout(int N, int K, int nhid, int d, bool two) {
     const project::BwdLayout B = project::bwd_layout(N, 4, K, nhid, d, two, false, false);
     KeptLayout L{B.sA, B.tiles_per_range, B.sC, B.rows_per_range, 0, 0, 0, 0};
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t off = 0;
-    L.off_w2p = off;  off += two ? al(sizeof(float) * (size_t)L.sA * K * d * nhid) : 0;
-    L.off_b1p = off;  off += two ? al(sizeof(float) * (size_t)L.sA * K * nhid) : 0;
-    L.off_b2p = off;  off += al(sizeof(float) * (size_t)L.sC * K * d);
+    L.off_w2p = off;  off += two ? align256(sizeof(float) * (size_t)L.sA * K * d * nhid) : 0;
+    L.off_b1p = off;  off += two ? align256(sizeof(float) * (size_t)L.sA * K * nhid) : 0;
+    L.off_b2p = off;  off += align256(sizeof(float) * (size_t)L.sC * K * d);
     L.bytes = off;
     return L;
 }
@@ -945,9 +1096,9 @@ void project_bwd_kept(int N, int K, int nhid, int d, const float* b1, const floa
         const int ldh = (N + 3) & ~3;
         const dim3 grid((unsigned)xcd_grid(L.sA, ceil_div(nhid, 64 * bwd_ht(d)) * K));
         const DhidPlanes none{nullptr, 0, 0};
-        if (d == 32) launchA_t<32, true, false, false>(grid, st, nullptr, N, 4, nhid, nullptr, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p, b1p, hidT, ldh, ldh, none);
-        if (d == 64) launchA_t<64, true, false, false>(grid, st, nullptr, N, 4, nhid, nullptr, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p, b1p, hidT, ldh, ldh, none);
-        if (d == 128) launchA_t<128, true, false, false>(grid, st, nullptr, N, 4, nhid, nullptr, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p, b1p, hidT, ldh, ldh, none);
+        if (d == 32) launchA_p<32, true, false>(false, grid, st, nullptr, N, 4, nhid, nullptr, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p, b1p, hidT, ldh, ldh, none);
+        if (d == 64) launchA_p<64, true, false>(false, grid, st, nullptr, N, 4, nhid, nullptr, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p, b1p, hidT, ldh, ldh, none);
+        if (d == 128) launchA_p<128, true, false>(false, grid, st, nullptr, N, 4, nhid, nullptr, b1, W2, dZ, K, L.tiles_per_range, dhid, w2p, b1p, hidT, ldh, ldh, none);
         sums.add(w2p, L.sA, (size_t)K * d * nhid, dW2);
         sums.add(b1p, L.sA, (size_t)K * nhid, db1);
     }

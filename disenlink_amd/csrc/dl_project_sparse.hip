@@ -366,8 +366,6 @@ __global__ __launch_bounds__(256) void sparse_dw1_finish_kernel(dl_sparse_featur
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-static int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 struct Shape { int C, Cp, n_chunks; };
 static Shape shape_of(int K, int nhid, int d, bool two) {
@@ -390,8 +388,8 @@ struct FwdLayout { size_t off_w1t, off_csum, bytes; };
 static FwdLayout fwd_layout(int F, const Shape& s) {
     FwdLayout L;
     size_t off = 0;
-    L.off_w1t = off;   off += al(sizeof(float) * (size_t)F * s.Cp);
-    L.off_csum = off;  off += al(sizeof(float) * (size_t)s.Cp);
+    L.off_w1t = off;   off += align256(sizeof(float) * (size_t)F * s.Cp);
+    L.off_csum = off;  off += align256(sizeof(float) * (size_t)s.Cp);
     L.bytes = off;
     return L;
 }
@@ -401,10 +399,10 @@ static BwdLayout bwd_layout(int N, int n_seg, int K, int nhid, int d, bool two, 
     BwdLayout L;
     g_ranges(N, s.C, L.S, L.rows_per_range);
     size_t off = 0;
-    L.off_kept = off;     off += al(project_bwd_kept_workspace_bytes(N, K, nhid, d, two));
-    L.off_dhid = off;     off += two ? al(sizeof(float) * (size_t)N * s.C) : 0;
-    L.off_partial = off;  off += al(sizeof(float) * (size_t)std::max(n_seg, 1) * s.Cp);
-    L.off_gpart = off;    off += al(sizeof(float) * (size_t)L.S * s.Cp);
+    L.off_kept = off;     off += align256(project_bwd_kept_workspace_bytes(N, K, nhid, d, two));
+    L.off_dhid = off;     off += two ? align256(sizeof(float) * (size_t)N * s.C) : 0;
+    L.off_partial = off;  off += align256(sizeof(float) * (size_t)std::max(n_seg, 1) * s.Cp);
+    L.off_gpart = off;    off += align256(sizeof(float) * (size_t)L.S * s.Cp);
     L.bytes = off;
     return L;
 }

@@ -338,7 +338,6 @@ __global__ __launch_bounds__(256) void combine_kernel(const float* __restrict__ 
     if (i < n) dZ[i] = s; else dH[i - n] = s;
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // How many slices the v range is cut into: a function of (N, K, d) only.  A workgroup per (u tile, factor) leaves most
 // of the 256 CUs idle on small graphs; aim at two workgroups per CU, at least one v tile per slice, at most 16 slices.

@@ -468,8 +468,11 @@ def required() -> dict:
     """Every reachable combination of template arguments, every kernel-B family, every launch mode of the table."""
     D = (32, 64, 128)
     return {
-        "fwd": {(d, v, s) for d in D for v in (0, 1) for s in (0, 1)},                       # project2_fwd_kernel<D, VEC, SPLIT>
-        # project2_bwd_hidden_kernel<D, VEC, RECOMPUTE, PLANES>: the kept form is only launched with VEC = true
+        # form tuples (d, vec, split): the six with split = 1 reach the three project2_fwd_planes_kernel<D> (vec selects nothing
+        # there), the six with split = 0 are project2_fwd_f32_kernel<D, VEC>
+        "fwd": {(d, v, s) for d in D for v in (0, 1) for s in (0, 1)},
+        # (d, vec, recompute, planes): project2_bwd_hidden_f32_kernel<D, VEC, RECOMPUTE, PLANES_OUT>, but kept + planes is
+        # project2_bwd_hidden_planes_kernel<D>; the kept form is only launched with VEC = true
         "A": {(d, v, r, p) for d in D for v in (0, 1) for r in (0, 1) for p in (0, 1) if r or v},
         "B": {"planes", "fp32-vector", "fp32-scalar"},
         "one_layer": set(D),

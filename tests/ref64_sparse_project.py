@@ -412,7 +412,7 @@ def reached(all_forms: dict) -> dict:
         out["l1"].add(f["two_layer"])                                    # sparse_l1_fwd_kernel<TWO>
         if f["two_layer"]:
             out["l2"].add(f["width"])                                    # sparse_l2_fwd_kernel<D>
-            out["A"].add(f["width"])                                     # project2_bwd_hidden_kernel<D, true, false, false>
+            out["A"].add(f["width"])                                     # project2_bwd_hidden_f32_kernel<D, true, false, false>
         if r["col"].numel():
             out["seg"].add(f["vec"])                                     # sparse_dw1_seg_kernel<VEC>
         m = out["modes"]

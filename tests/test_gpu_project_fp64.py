@@ -1,5 +1,6 @@
-"""Every compiled form of the projection kernels (project2_fwd_kernel<D, VEC, SPLIT> with its slab sum, project1_fwd_kernel<D>,
-project2_bwd_hidden_kernel<D, VEC, RECOMPUTE, PLANES>, the node contractions on planes / fp32 vector / fp32 scalar, the slab
+"""Every compiled form of the projection kernels (project2_fwd_planes_kernel<D> and project2_fwd_f32_kernel<D, VEC> with their
+slab sum, project1_fwd_kernel<D>, project2_bwd_hidden_planes_kernel<D> and project2_bwd_hidden_f32_kernel<D, VEC, RECOMPUTE,
+PLANES_OUT>, the node contractions on planes / fp32 vector / fp32 scalar, the slab
 and column sums) against the plain fp64 reference of tests/ref64_project.py, per element, on the case list of
 ref64_project.cases(): the smallest shapes that reach each instantiation and launch mode, which the library itself confirms
 for every case before anything runs (dl_project_fwd_form / dl_project_bwd_form; tests/test_ref64_project_cpu.py asserts
