@@ -144,6 +144,12 @@ EXPORTS = {
     "dl_adam_step_at": (_i, [_i, _P, _P, _P, _P, _P, _P, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     "dl_pair_bce": (_i, [_P, _P, _P, _i, _P, _P, _P, _z, _P]),
     "dl_score_pairs_bwd": (_i, [_P, _P, _i, _i, _i, _f, _I, _P, _P, _P, _P, _P, _P, _z, _P]),
+    # the pair-list objective in logit space
+    "dl_score_pairs_logits_fwd": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _i, _I, _P, _P]),
+    "dl_score_pairs_logits_bwd": (_i, [_P, _P, _i, _i, _i, _f, _I, _P, _P, _P, _P, _z, _P]),
+    "dl_score_pairs_train_logits_supported": (_i, [_P, _i, _i, _i]),
+    "dl_score_pairs_train_logits": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_pair_bce_logits": (_i, [_P, _P, _P, _i, _P, _P, _P, _z, _P]),
     "dl_route_aggregate_bwd_phase1": (_i, [_G, _P, _i, _i, _i, _f, _P, _P, _P, _P, _P, _P, _P, _P, _z, _P]),
     "dl_route_aggregate_bwd_phase2": (_i, [_G, _P, _i, _i, _i, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _z, _P]),
     "dl_route_aggregate_bwd": (_i, [_G, _P, _i, _i, _i, _f, _f, _P, _P, _P, _P, _P, _i, _P, _z, _P]),

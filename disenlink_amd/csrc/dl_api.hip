@@ -293,9 +293,10 @@ int dl_aggregate_fwd(const dl_graph* g, const void* Z, int K, int d, dl_dtype dt
     return generic_aggregate_fwd(c, (const float*)Z, K, d, beta, p, a, s, (float*)H, (hipStream_t)stream);
 }
 
-int dl_score_pairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
-                       const int32_t* pu, const int32_t* pv, int n_pairs, const dl_pair_incidence* by_u,
-                       float* prob, float* coef, void* stream) {
+// dl_score_pairs_fwd and dl_score_pairs_logits_fwd: one set of checks, one dispatch (logit: logits out, no stored terms)
+static int score_pairs_fwd_space(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                                 const int32_t* pu, const int32_t* pv, int n_pairs, const dl_pair_incidence* by_u,
+                                 float* prob, float* coef, bool logit, void* stream) {
     if (int rc = check_shape(K, d)) return rc;
     if (int rc = check_dtype(by_u ? &by_u->csr : nullptr, K, d, dtype)) return rc;
     DL_REQUIRE(N >= 0 && n_pairs >= 0, "negative size");
@@ -320,11 +321,27 @@ int dl_score_pairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_dty
             }
         }
         if (use_fast(&by_u->csr, K, d, dtype))
-            return fast_score_pairs_fwd(by_u, Z, H, K, d, dtype, t, prob, coef, (hipStream_t)stream);
+            return logit ? fast_score_pairs_logits_fwd(by_u, Z, H, K, d, dtype, t, prob, (hipStream_t)stream)
+                         : fast_score_pairs_fwd(by_u, Z, H, K, d, dtype, t, prob, coef, (hipStream_t)stream);
     }
     DL_REQUIRE(coef == nullptr, "coef output needs the tuned scorer (a (K,d) with a fast path and a by_u plan)");
+    if (logit)
+        return generic_score_pairs_logits_fwd((const float*)Z, (const float*)H, K, d, t, pu, pv, n_pairs, prob,
+                                              (hipStream_t)stream);
     return generic_score_pairs_fwd((const float*)Z, (const float*)H, K, d, t, pu, pv, n_pairs, prob,
                                    (hipStream_t)stream);
+}
+
+int dl_score_pairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                       const int32_t* pu, const int32_t* pv, int n_pairs, const dl_pair_incidence* by_u,
+                       float* prob, float* coef, void* stream) {
+    return score_pairs_fwd_space(Z, H, N, K, d, dtype, t, pu, pv, n_pairs, by_u, prob, coef, false, stream);
+}
+
+int dl_score_pairs_logits_fwd(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                              const int32_t* pu, const int32_t* pv, int n_pairs, const dl_pair_incidence* by_u,
+                              float* logit, void* stream) {
+    return score_pairs_fwd_space(Z, H, N, K, d, dtype, t, pu, pv, n_pairs, by_u, logit, nullptr, true, stream);
 }
 
 size_t dl_score_allpairs_workspace_bytes(int N, int K, int d, dl_dtype dtype) {
@@ -913,6 +930,16 @@ int dl_pair_bce(const float* prob, const float* y, const float* w, int n_pairs, 
     return pair_bce(prob, y, w, n_pairs, loss, g, partial, (hipStream_t)stream);
 }
 
+int dl_pair_bce_logits(const float* logit, const float* y, const float* w, int n_pairs, float* loss, float* g, void* ws,
+                       size_t ws_bytes, void* stream) {
+    DL_REQUIRE(n_pairs >= 0, "negative size");
+    DL_REQUIRE(loss != nullptr, "loss is NULL");
+    DL_REQUIRE(ws != nullptr && ws_bytes >= 4096 + 256, "dl_pair_bce_logits needs >= 4352 bytes of workspace");
+    if (n_pairs > 0) DL_REQUIRE(logit && y && w && g, "NULL argument");
+    float* partial = (float*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    return pair_bce_logits(logit, y, w, n_pairs, loss, g, partial, (hipStream_t)stream);
+}
+
 int dl_adam_step(int n_bufs, float* const* params, const float* const* grads, float* const* exp_avg,
                  float* const* exp_avg_sq, const size_t* numel, float* state, double lr, double beta1, double beta2,
                  double eps, double weight_decay, void* stream) {
@@ -959,6 +986,27 @@ int dl_score_pairs_bwd(const void* Z, const void* H, int K, int d, dl_dtype dtyp
     }
     return generic_score_pairs_bwd(inc, (const float*)Z, (const float*)H, K, d, t, prob, g_prob, dZ, dH,
                                    (hipStream_t)stream);
+}
+
+int dl_score_pairs_logits_bwd(const void* Z, const void* H, int K, int d, dl_dtype dtype, float t,
+                              const dl_pair_incidence* inc, const float* g_logit, float* dZ, float* dH, void* ws,
+                              size_t ws_bytes, void* stream) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(inc != nullptr, "incidence is NULL");
+    const dl_csr_plan* c = &inc->csr;
+    if (int rc = check_plan(c, "incidence")) return rc;
+    if (int rc = check_dtype(c, K, d, dtype)) return rc;
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    if (c->n_rows == 0) return DL_OK;
+    DL_REQUIRE(Z && H && dZ && dH, "NULL argument");
+    if (c->n_entries > 0) DL_REQUIRE(inc->inc_pair && g_logit, "NULL pair argument");
+    if (use_fast(c, K, d, dtype)) {
+        Workspace w;
+        if (int rc = check_workspace(c, K, d, ws, ws_bytes, &w)) return rc;
+        return fast_score_pairs_logits_bwd(inc, Z, H, K, d, dtype, t, g_logit, dZ, dH, w.row_part, (hipStream_t)stream);
+    }
+    return generic_score_pairs_logits_bwd(inc, (const float*)Z, (const float*)H, K, d, t, g_logit, dZ, dH,
+                                          (hipStream_t)stream);
 }
 
 int dl_score_allpairs_bwd(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
@@ -1070,23 +1118,41 @@ int dl_score_pairs_train_supported(const dl_pair_incidence* inc, int K, int d, d
     return inc != nullptr && use_fast(&inc->csr, K, d, dtype) ? 1 : 0;
 }
 
-int dl_score_pairs_train(const void* Z, const void* H, int K, int d, dl_dtype dtype, float t,
-                         const dl_pair_incidence* inc, const float* y, const float* w, float* prob, float* dZ,
-                         float* dH, void* ws, size_t ws_bytes, void* stream) {
+// dl_score_pairs_train and dl_score_pairs_train_logits: one set of checks, one dispatch
+static int score_pairs_train_space(const void* Z, const void* H, int K, int d, dl_dtype dtype, float t,
+                                   const dl_pair_incidence* inc, const float* y, const float* w, float* prob, float* dZ,
+                                   float* dH, void* ws, size_t ws_bytes, bool logit, void* stream) {
+    const char* const entry = logit ? "dl_score_pairs_train_logits" : "dl_score_pairs_train";
     if (int rc = check_shape(K, d)) return rc;
     DL_REQUIRE(inc != nullptr, "incidence is NULL");
     const dl_csr_plan* c = &inc->csr;
     if (int rc = check_plan(c, "incidence")) return rc;
     if (int rc = check_dtype(c, K, d, dtype)) return rc;
     DL_REQUIRE(t != 0.0f, "temperature is 0");
-    DL_REQUIRE(use_fast(c, K, d, dtype), "dl_score_pairs_train needs a tuned kernel for K=%d d=%d (dl_score_pairs_train_supported)",
-               K, d);
+    DL_REQUIRE(use_fast(c, K, d, dtype), "%s needs a tuned kernel for K=%d d=%d (%s_supported)", entry, K, d, entry);
     if (c->n_rows == 0) return DL_OK;
     DL_REQUIRE(Z && H && dZ && dH, "NULL argument");
     if (c->n_entries > 0) DL_REQUIRE(inc->inc_pair && y && w && prob, "NULL pair argument");
     Workspace wsp;
     if (int rc = check_workspace(c, K, d, ws, ws_bytes, &wsp)) return rc;
+    if (logit) return fast_score_pairs_train_logits(inc, Z, H, K, d, dtype, t, y, w, prob, dZ, dH, wsp.row_part, (hipStream_t)stream);
     return fast_score_pairs_train(inc, Z, H, K, d, dtype, t, y, w, prob, dZ, dH, wsp.row_part, (hipStream_t)stream);
+}
+
+int dl_score_pairs_train(const void* Z, const void* H, int K, int d, dl_dtype dtype, float t,
+                         const dl_pair_incidence* inc, const float* y, const float* w, float* prob, float* dZ,
+                         float* dH, void* ws, size_t ws_bytes, void* stream) {
+    return score_pairs_train_space(Z, H, K, d, dtype, t, inc, y, w, prob, dZ, dH, ws, ws_bytes, false, stream);
+}
+
+int dl_score_pairs_train_logits_supported(const dl_pair_incidence* inc, int K, int d, dl_dtype dtype) {
+    return dl_score_pairs_train_supported(inc, K, d, dtype);
+}
+
+int dl_score_pairs_train_logits(const void* Z, const void* H, int K, int d, dl_dtype dtype, float t,
+                                const dl_pair_incidence* inc, const float* y, const float* w, float* logit, float* dZ,
+                                float* dH, void* ws, size_t ws_bytes, void* stream) {
+    return score_pairs_train_space(Z, H, K, d, dtype, t, inc, y, w, logit, dZ, dH, ws, ws_bytes, true, stream);
 }
 
 int dl_route_aggregate_bwd_phase1(const dl_graph* g, const void* Z, int K, int d, dl_dtype dtype, float beta,

@@ -245,6 +245,23 @@ __device__ __forceinline__ float one_if_zero(float s) { return s == 0.0f ? 1.0f 
 // sigmoid as ATen's CPU kernel writes it: 1 / (1 + exp(-x)).
 __device__ __forceinline__ float sigmoid_ref(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// sigmoid(x) - y of the LOGIT-space objective (dl_score_pairs_train_logits, dl_pair_bce_logits), without losing the small
+// side: with e = exp(-|x|) (never overflows) and s = 1 / (1 + e), sigma(|x|) = s and sigma(-|x|) = e s, and
+//   sigma(x) - y = (1 - y) sigma(x) - y sigma(-x) = s ((1 - y) - y e)  for x >= 0,   s ((1 - y) e - y)  for x < 0:
+// one fma and one product behind the reciprocal.  For y = 1 that is -sigma(-x) exactly (the other term is an exact 0), for
+// y = 0 it is sigma(x) exactly: no `1.0 - 1.0` past x = 16.64, where sigmoid_ref rounds to 1, and no flush to 0 on the
+// negative side before exp(-|x|) itself underflows (|x| > 103).  1 + e lies in [1, 2], so the hardware reciprocal (1 ulp)
+// serves: there is no reference bit pattern to meet here, unlike sigmoid_ref's IEEE division.  Relative error of either side
+// against the fp32 x it is given: expf (1 ulp) + the addition (0.5) + the reciprocal (1) + the product (0.5) < 4 ulp = 4.8e-7;
+// labels strictly between 0 and 1 add the fma's rounding, relative to the larger term.  NaN stays NaN; x = +inf gives 1 - y, -inf -y.
+__device__ __forceinline__ float sigmoid_minus_label(float x, float y) {
+    const float e = expf(-fabsf(x));
+    const float s = __builtin_amdgcn_rcpf(1.0f + e);
+    const bool pos = x >= 0.0f;
+    const float a = 1.0f - y, b = -y;
+    return s * fmaf(pos ? b : a, e, pos ? a : b);
+}
+
 // d s_raw -> ds of the normaliser: -(acc) / s~^2, zero where the raw sum was zero (model.py:72).
 __device__ __forceinline__ float ds_from_acc(float acc, float s_raw) {
     return s_raw == 0.0f ? 0.0f : -acc / (s_raw * s_raw);

@@ -1,4 +1,4 @@
-// Shared pieces of the tuned gfx950 kernels (dl_route.hip, dl_aggregate.hip, dl_bwd.hip, dl_score.hip, dl_train.hip):
+// Shared pieces of the tuned gfx950 kernels (dl_route.hip, dl_aggregate.hip, dl_bwd.hip, dl_score.h, dl_train.h, dl_pair_logits.hip):
 // typed 16-byte chunks, the lane geometry, the unit reduction through LDS, the row combine, shape lists and dispatch.
 //
 //

@@ -92,6 +92,9 @@ __global__ __launch_bounds__(BLOCK) void aggregate_fwd_kernel(dl_csr_plan c, con
     for (int x = lane; x < KD; x += DL_WAVE) hi[x] = beta * zi[x] + omb * acc[x];
 }
 
+// LOGIT: the logit-space entries (dl_score_pairs_logits_fwd / _bwd) — the forward stores the logit, the backward's
+// per-entry coefficient is g_prob[q] = d loss / d logit itself and prob is not read.
+template <bool LOGIT = false>
 __global__ __launch_bounds__(BLOCK) void score_pairs_fwd_kernel(
     const float* __restrict__ Z, const float* __restrict__ H, int K, int d, float t,
     const int32_t* __restrict__ pu, const int32_t* __restrict__ pv, int P, float* __restrict__ prob) {
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(BLOCK) void score_pairs_fwd_kernel(
         float ek = expf(wave_dot(zu + k * d, zv + k * d, d) / t);
         logit += qk * ek;                          // separate mul and add, like (q*e).sum(0)
     }
-    if (lane_id() == 0) prob[q] = sigmoid_ref(logit);
+    if (lane_id() == 0) prob[q] = LOGIT ? logit : sigmoid_ref(logit);
 }
 
 // dense [N][N] scorer: one wave per (u, v) entry, row-major
@@ -129,6 +132,7 @@ __global__ __launch_bounds__(BLOCK) void score_allpairs_fwd_kernel(const float* 
 }
 
 // dH[u] = sum_inc gl*e_k*h_k[v],  dZ[u] = sum_inc gl*q_k*e_k/t*z_k[v]  over the pair slots of node u.
+template <bool LOGIT = false>
 __global__ __launch_bounds__(BLOCK) void score_pairs_bwd_kernel(
     dl_csr_plan c, const int32_t* __restrict__ inc_pair, const float* __restrict__ Z, const float* __restrict__ H,
     int K, int d, float t, const float* __restrict__ prob, const float* __restrict__ g_prob,
@@ -148,8 +152,11 @@ __global__ __launch_bounds__(BLOCK) void score_pairs_bwd_kernel(
     for (int it = c.rowptr[row]; it < c.rowptr[row + 1]; ++it) {
         const int v = c.col[it];
         const int q = inc_pair[it];
-        const float pr = prob[q];
-        const float gl = g_prob[q] * pr * (1.0f - pr);      // sigmoid backward p(1-p)
+        float gl = g_prob[q];
+        if constexpr (!LOGIT) {
+            const float pr = prob[q];
+            gl = gl * pr * (1.0f - pr);                     // sigmoid backward p(1-p)
+        }
         const float* zv = Z + (size_t)v * KD;
         const float* hv = H + (size_t)v * KD;
         for (int k = 0; k < K; ++k) {
@@ -278,9 +285,16 @@ int generic_aggregate_fwd(const dl_csr_plan* c, const float* Z, int K, int d, fl
 
 int generic_score_pairs_fwd(const float* Z, const float* H, int K, int d, float t, const int32_t* pu,
                             const int32_t* pv, int P, float* prob, hipStream_t st) {
-    hipLaunchKernelGGL(score_pairs_fwd_kernel, dim3(wave_blocks(P)), dim3(BLOCK), 0, st, Z, H, K, d, t, pu, pv, P,
+    hipLaunchKernelGGL(score_pairs_fwd_kernel<false>, dim3(wave_blocks(P)), dim3(BLOCK), 0, st, Z, H, K, d, t, pu, pv, P,
                        prob);
     return check_launch("score_pairs_fwd(generic)");
+}
+
+int generic_score_pairs_logits_fwd(const float* Z, const float* H, int K, int d, float t, const int32_t* pu,
+                                   const int32_t* pv, int P, float* logit, hipStream_t st) {
+    hipLaunchKernelGGL(score_pairs_fwd_kernel<true>, dim3(wave_blocks(P)), dim3(BLOCK), 0, st, Z, H, K, d, t, pu, pv, P,
+                       logit);
+    return check_launch("score_pairs_logits_fwd(generic)");
 }
 
 static unsigned allpairs_blocks(long long n) { return (unsigned)((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK); }
@@ -328,9 +342,19 @@ int generic_score_pairs_bwd(const dl_pair_incidence* inc, const float* Z, const 
                             const float* prob, const float* g_prob, float* dZ, float* dH, hipStream_t st) {
     if (int rc = check_lds(K, d, 2)) return rc;
     size_t lds = (size_t)WAVES_PER_BLOCK * 2 * K * d * sizeof(float);
-    hipLaunchKernelGGL(score_pairs_bwd_kernel, dim3(wave_blocks(inc->csr.n_rows)), dim3(BLOCK), lds, st, inc->csr,
+    hipLaunchKernelGGL(score_pairs_bwd_kernel<false>, dim3(wave_blocks(inc->csr.n_rows)), dim3(BLOCK), lds, st, inc->csr,
                        inc->inc_pair, Z, H, K, d, t, prob, g_prob, dZ, dH);
     return check_launch("score_pairs_bwd(generic)");
+}
+
+int generic_score_pairs_logits_bwd(const dl_pair_incidence* inc, const float* Z, const float* H, int K, int d, float t,
+                                   const float* g_logit, float* dZ, float* dH, hipStream_t st) {
+    if (int rc = check_lds(K, d, 2)) return rc;
+    size_t lds = (size_t)WAVES_PER_BLOCK * 2 * K * d * sizeof(float);
+    const float* no_prob = nullptr;
+    hipLaunchKernelGGL(score_pairs_bwd_kernel<true>, dim3(wave_blocks(inc->csr.n_rows)), dim3(BLOCK), lds, st, inc->csr,
+                       inc->inc_pair, Z, H, K, d, t, no_prob, g_logit, dZ, dH);
+    return check_launch("score_pairs_logits_bwd(generic)");
 }
 
 int generic_bwd_phase1(const dl_csr_plan* c, const float* Z, int K, int d, float beta, const uint8_t* p,

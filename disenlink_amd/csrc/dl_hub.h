@@ -1,4 +1,4 @@
-// What a kernel over a hub plan (dl_pair_hub, disenlink_hip.h) shares: hub::score_fwd_wave_kernel (dl_score.hip) and
+// What a kernel over a hub plan (dl_pair_hub, disenlink_hip.h) shares: hub::score_fwd_wave_kernel (dl_score.h) and
 // hub::route_seg_kernel (dl_route.hip).  A workgroup of eight waves takes one work item: it stages the 16 rows of the item's
 // block in LDS, ONE barrier, and from there on wave w runs the steps s_a + w, + 8, ... of the item on its own, counted through
 // the three lists [A | B | C] so that no two waves differ by more than one step.

@@ -14,6 +14,11 @@ int generic_score_pairs_fwd(const float* Z, const float* H, int K, int d, float 
                             const int32_t* pv, int P, float* prob, hipStream_t st);
 int generic_score_pairs_bwd(const dl_pair_incidence* inc, const float* Z, const float* H, int K, int d, float t,
                             const float* prob, const float* g_prob, float* dZ, float* dH, hipStream_t st);
+// ... in logit space: logits out; the backward from d loss / d logit
+int generic_score_pairs_logits_fwd(const float* Z, const float* H, int K, int d, float t, const int32_t* pu,
+                                   const int32_t* pv, int P, float* logit, hipStream_t st);
+int generic_score_pairs_logits_bwd(const dl_pair_incidence* inc, const float* Z, const float* H, int K, int d, float t,
+                                   const float* g_logit, float* dZ, float* dH, hipStream_t st);
 int generic_bwd_phase1(const dl_csr_plan* c, const float* Z, int K, int d, float beta, const uint8_t* p,
                        const float* a, const float* s, const float* dH, float* dw, float* dwr, float* ds,
                        hipStream_t st);
@@ -43,6 +48,13 @@ int fast_score_pairs_train(const dl_pair_incidence* inc, const void* Z, const vo
 int fast_score_pairs_bwd(const dl_pair_incidence* inc, const void* Z, const void* H, int K, int d, int dtype,
                          float t, const float* prob, const float* g_prob, const float* coef, float* dZ, float* dH,
                          float* part, hipStream_t st);
+// the same three in logit space (the forward without stored terms, the one-pass step with gl = w (sigma(x) - y), the recompute backward)
+int fast_score_pairs_logits_fwd(const dl_pair_incidence* by_u, const void* Z, const void* H, int K, int d, int dtype,
+                                float t, float* logit, hipStream_t st);
+int fast_score_pairs_train_logits(const dl_pair_incidence* inc, const void* Z, const void* H, int K, int d, int dtype, float t,
+                                  const float* y, const float* w, float* logit, float* dZ, float* dH, float* part, hipStream_t st);
+int fast_score_pairs_logits_bwd(const dl_pair_incidence* inc, const void* Z, const void* H, int K, int d, int dtype,
+                                float t, const float* g_logit, float* dZ, float* dH, float* part, hipStream_t st);
 
 // prob / g_prob of the dense [N][N] scorer at the listed pairs (dl_generic.hip)
 int gather_dense_pairs(const int32_t* pu, const int32_t* pv, int N, int P, const float* prob, const float* g_prob,
@@ -185,6 +197,8 @@ int adam_step(int n_bufs, float* const* params, const float* const* grads, float
               const size_t* numel, float* state, double lr, double beta1, double beta2, double eps, double weight_decay,
               hipStream_t st, long long host_step = 0);
 
+int pair_bce_logits(const float* logit, const float* y, const float* w, int n, float* loss, float* g, float* partial,
+                    hipStream_t st);
 int pair_bce(const float* prob, const float* y, const float* w, int n, float* loss, float* g, float* partial,
              hipStream_t st);
 

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(BLOCK, (K <= 8 && sizeof(T) == 4) ? 8 : (K <= 10 ? 
 // undirected edge to its endpoint of larger degree, cuts those owners into blocks of 16 rows, and a workgroup that holds a
 // block's Z rows in LDS (32 KB at K = 8) gathers a partner row ONCE for up to four of them.  Item, staging, walk and batch
 // counter are those of every kernel over a hub plan (dl_hub.h, with the plan contract); the step is that of
-// hub::score_fwd_wave_kernel (dl_score.hip) on one table: scalar row bases, every gather of a step issued before the first
+// hub::score_fwd_wave_kernel (dl_score.h) on one table: scalar row bases, every gather of a step issued before the first
 // wait, a chunk's LDS reads issued together.
 // Lane l holds float4 number j * 64 + l of a row: a DPP row of 16 lanes is one factor slice (factor 4 j + r, r = l >> 4), and
 // lane i of it holds the elements 4 i .. 4 i + 3 — the elements lane c = i of a group holds in the kernel above.

@@ -1,5 +1,5 @@
-// Scorer backward by recomputation, and (FUSED) the group-per-entry one-pass training scorer: shared by dl_score.hip
-// (separate backward) and dl_train.hip (fallback of the one-pass scorer for shapes without a wave-per-entry kernel).
+// Scorer backward by recomputation, and (FUSED) the group-per-entry one-pass training scorer: shared by dl_score.h
+// (separate backward) and dl_train.h (fallback of the one-pass scorer for shapes without a wave-per-entry kernel).
 #pragma once
 #include "dl_fast.h"
 
@@ -20,7 +20,10 @@ namespace fast {
 constexpr int FUSED_TRAIN_WAVES = 3;          // waves per SIMD of that kernel (measured as above)
 template <int K_, int D_, bool FUSED_>
 struct TrainWaves { static constexpr int value = (FUSED_ && K_ == 8 && D_ == 64) ? FUSED_TRAIN_WAVES : 1; };
-template <int K, int D, typename T, bool FUSED>
+// LOGIT (the logit-space entries): FUSED stores the logit and forms gl = w (sigma(x) - y) through sigmoid_minus_label
+// (dl_common.h), with no p (1 - p) clamp factor; the separate backward takes the gradient of the LOGIT — its per-entry
+// coefficient is g_prob[q] itself and prob is not read.  Everything from gl on is the code of the probability form.
+template <int K, int D, typename T, bool FUSED, bool LOGIT = false>
 __global__ __launch_bounds__(BLOCK, (TrainWaves<K, D, FUSED>::value)) void score_bwd_seg_kernel(dl_csr_plan g, const int32_t* __restrict__ inc_pair,
                                                               const T* __restrict__ Z, const T* __restrict__ H,
                                                               float t, const float* __restrict__ prob,
@@ -64,6 +67,8 @@ __global__ __launch_bounds__(BLOCK, (TrainWaves<K, D, FUSED>::value)) void score
                     my_y = y[q];
                     my_w = w[q];
                 }
+            } else if constexpr (LOGIT) {
+                my_gl = g_prob[q];                          // d loss / d logit as it is
             } else {
                 const float pr = prob[q];
                 my_gl = g_prob[q] * pr * (1.0f - pr);       // sigmoid backward p(1-p)
@@ -96,14 +101,19 @@ __global__ __launch_bounds__(BLOCK, (TrainWaves<K, D, FUSED>::value)) void score
 #pragma unroll
                 for (int i = 0; i < VPL; ++i)
                     if (FL::primary(c) && FL::factor_base(c) + i < K) term += pq[i] * ek_lane[i];
-                const float p = sigmoid_ref(group_allreduce_sum<G>(term));
+                const float logit = group_allreduce_sum<G>(term);
+                const float p = LOGIT ? logit : sigmoid_ref(logit);    // the stored score
                 const float yy = __shfl(my_y, idx, DL_WAVE), wsg = __shfl(my_w, idx, DL_WAVE);  // w = 0 past the segment end
                 const float ww = fabsf(wsg);                       // a negative sign (per-entry weights only) = the pair's other entry writes prob
                 const int qq = __shfl(my_q, idx, DL_WAVE);
                 // dl_pair_bce's gradient times the sigmoid backward: w (p - y) / max(r, 1e-12) * r with r = p (1 - p) — i.e.
                 // w (p - y) itself unless r underflows the clamp (saturated scores: r = 0 gives exactly 0), without the division
-                const float r = p * (1.0f - p);
-                gl = ww == 0.0f ? 0.0f : ww * (p - yy) * (r >= 1e-12f ? 1.0f : r * 1e12f);
+                if constexpr (LOGIT) {
+                    gl = ww == 0.0f ? 0.0f : ww * sigmoid_minus_label(logit, yy);
+                } else {
+                    const float r = p * (1.0f - p);
+                    gl = ww == 0.0f ? 0.0f : ww * (p - yy) * (r >= 1e-12f ? 1.0f : r * 1e12f);
+                }
                 if (base + grp < si.end && c == 0 && !(__float_as_uint(wsg) >> 31)) prob_out[qq] = p;
             }
 #pragma unroll

@@ -189,7 +189,7 @@ __device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, 
 // RECON: the whole-graph reconstruction loss of a candidate tile (dl_score_recon.hip has the contract).  Two masks per row,
 // positives and ignored (the second one and the sums of the two v halves live where the top-k modes keep their compaction
 // scratch); per value p = sigmoid(s), the weighted BCE term with F.binary_cross_entropy's clamps and g = w (p - y) in the
-// one-pass scorer's form (dl_train.hip), written to the strip of G^ — zero where the pair carries no loss: ignored, the
+// one-pass scorer's form (dl_train.h), written to the strip of G^ — zero where the pair carries no loss: ignored, the
 // diagonal, outside N.  As in the other modes the values go through LDS so that the loop over a lane's 16 rows stays rolled
 // (lg: RLG floats of the wave's own, pitch 65: the transposed read below is conflict-free); the loss terms come back the
 // same way and the 128 terms of a row are added in one fixed order — 16 consecutive columns by one lane, the two halves of a

@@ -7,6 +7,9 @@
 //
 //   torch.ops.disenlink_native.hot_path_pairs_loss(Z, graph_ptr, inc_ptr, n_edges, beta, t, label, weight,
 //                                                  ws_graph, ws_pairs, ws_bce) -> (H, prob, loss)
+//   torch.ops.disenlink_native.hot_path_pair_logits_loss(... the same arguments ...) -> (H, logit, loss)
+//       the same step in LOGIT space (ops.HotPathPairLogitsLoss: dl_score_pairs_train_logits + dl_pair_bce_logits; a gradient
+//       arriving on the logits goes through dl_score_pairs_logits_bwd)
 //
 // graph_ptr / inc_ptr: addresses of the dl_graph / dl_pair_incidence structs the Python Graph / PairList objects own
 // (they must outlive the call and its backward: disenlink_amd/native.py hangs the Python objects on the node's metadata);
@@ -22,7 +25,7 @@
 
 // Operator set + schemas of this binding; native.py refuses a library built for another number (a stale .so would
 // otherwise fail deep inside a training step with an AttributeError or a schema error).  Bump with every schema change.
-#define DL_TORCH_BINDING_ABI 6
+#define DL_TORCH_BINDING_ABI 7
 
 namespace {
 
@@ -36,7 +39,9 @@ void check(int rc, const char* what) {
 
 void* stream() { return (void*)c10::hip::getCurrentHIPStream().stream(); }
 
-struct HotPathPairsLoss : public torch::autograd::Function<HotPathPairsLoss> {
+// LOGIT: the score space of the step — false: probabilities and the reference's BCE; true: logits and BCE with logits
+template <bool LOGIT>
+struct HotPathPairsLoss : public torch::autograd::Function<HotPathPairsLoss<LOGIT>> {
     static variable_list forward(AutogradContext* ctx, const Tensor& Z_in, int64_t graph_ptr, int64_t inc_ptr, int64_t n_edges,
                                  double beta, double t, const Tensor& label_in, const Tensor& weight_in, const Tensor& ws_g,
                                  const Tensor& ws_p, const Tensor& ws_b, int64_t table_bf16) {
@@ -61,11 +66,21 @@ struct HotPathPairsLoss : public torch::autograd::Function<HotPathPairsLoss> {
                            ws_g.data_ptr(), (size_t)ws_g.numel(), st), "dl_route_fwd");
         check(dl_aggregate_fwd(g, Z.data_ptr(), K, d, dt, (float)beta, p.data_ptr<uint8_t>(), a.data_ptr<float>(),
                                s.data_ptr<float>(), H.data_ptr(), ws_g.data_ptr(), (size_t)ws_g.numel(), st), "dl_aggregate_fwd");
+        if constexpr (LOGIT) {
+            check(dl_score_pairs_train_logits(Z.data_ptr(), H.data_ptr(), K, d, dt, (float)t, inc, label.data_ptr<float>(),
+                                              weight.data_ptr<float>(), prob.data_ptr<float>(), dZs.data_ptr<float>(),
+                                              dHs.data_ptr<float>(), ws_p.data_ptr(), (size_t)ws_p.numel(), st),
+                  "dl_score_pairs_train_logits");
+            check(dl_pair_bce_logits(prob.data_ptr<float>(), label.data_ptr<float>(), weight.data_ptr<float>(), (int)P,
+                                     loss.data_ptr<float>(), gbce.data_ptr<float>(), ws_b.data_ptr(), (size_t)ws_b.numel(), st),
+                  "dl_pair_bce_logits");
+        } else {
         check(dl_score_pairs_train(Z.data_ptr(), H.data_ptr(), K, d, dt, (float)t, inc, label.data_ptr<float>(),
                                    weight.data_ptr<float>(), prob.data_ptr<float>(), dZs.data_ptr<float>(), dHs.data_ptr<float>(),
                                    ws_p.data_ptr(), (size_t)ws_p.numel(), st), "dl_score_pairs_train");
         check(dl_pair_bce(prob.data_ptr<float>(), label.data_ptr<float>(), weight.data_ptr<float>(), (int)P, loss.data_ptr<float>(),
                           gbce.data_ptr<float>(), ws_b.data_ptr(), (size_t)ws_b.numel(), st), "dl_pair_bce");
+        }
         ctx->saved_data["graph"] = graph_ptr;
         ctx->saved_data["inc"] = inc_ptr;
         ctx->saved_data["beta"] = beta;
@@ -112,6 +127,11 @@ struct HotPathPairsLoss : public torch::autograd::Function<HotPathPairsLoss> {
             if (g_prob.defined()) {
                 const Tensor gp = g_prob.to(at::kFloat).contiguous();
                 Tensor dZ2 = at::empty(Z.sizes(), dZs.options()), dH2 = at::empty(Z.sizes(), dZs.options());
+                if constexpr (LOGIT)
+                    check(dl_score_pairs_logits_bwd(Z.data_ptr(), H.data_ptr(), K, d, dt, t, inc, gp.data_ptr<float>(),
+                                                    dZ2.data_ptr<float>(), dH2.data_ptr<float>(), ws_p.data_ptr(),
+                                                    (size_t)ws_p.numel(), st), "dl_score_pairs_logits_bwd");
+                else
                 check(dl_score_pairs_bwd(Z.data_ptr(), H.data_ptr(), K, d, dt, t, inc, prob.data_ptr<float>(), gp.data_ptr<float>(),
                                          nullptr, dZ2.data_ptr<float>(), dH2.data_ptr<float>(), ws_p.data_ptr(), (size_t)ws_p.numel(),
                                          st), "dl_score_pairs_bwd");
@@ -131,7 +151,14 @@ struct HotPathPairsLoss : public torch::autograd::Function<HotPathPairsLoss> {
 std::tuple<Tensor, Tensor, Tensor> hot_path_pairs_loss(const Tensor& Z, int64_t graph_ptr, int64_t inc_ptr, int64_t n_edges,
                                                        double beta, double t, const Tensor& label, const Tensor& weight,
                                                        const Tensor& ws_g, const Tensor& ws_p, const Tensor& ws_b, int64_t table_bf16) {
-    auto out = HotPathPairsLoss::apply(Z, graph_ptr, inc_ptr, n_edges, beta, t, label, weight, ws_g, ws_p, ws_b, table_bf16);
+    auto out = HotPathPairsLoss<false>::apply(Z, graph_ptr, inc_ptr, n_edges, beta, t, label, weight, ws_g, ws_p, ws_b, table_bf16);
+    return {out[0], out[1], out[2]};
+}
+
+std::tuple<Tensor, Tensor, Tensor> hot_path_pair_logits_loss(const Tensor& Z, int64_t graph_ptr, int64_t inc_ptr, int64_t n_edges,
+                                                             double beta, double t, const Tensor& label, const Tensor& weight,
+                                                             const Tensor& ws_g, const Tensor& ws_p, const Tensor& ws_b, int64_t table_bf16) {
+    auto out = HotPathPairsLoss<true>::apply(Z, graph_ptr, inc_ptr, n_edges, beta, t, label, weight, ws_g, ws_p, ws_b, table_bf16);
     return {out[0], out[1], out[2]};
 }
 
@@ -290,6 +317,8 @@ void epoch_finish(const Tensor& score_val, const Tensor& pos_idx, const Tensor& 
 TORCH_LIBRARY(disenlink_native, m) {
     m.def("hot_path_pairs_loss(Tensor Z, int graph_ptr, int inc_ptr, int n_edges, float beta, float t, Tensor label, "
           "Tensor weight, Tensor ws_graph, Tensor ws_pairs, Tensor ws_bce, int table_bf16) -> (Tensor, Tensor, Tensor)");
+    m.def("hot_path_pair_logits_loss(Tensor Z, int graph_ptr, int inc_ptr, int n_edges, float beta, float t, Tensor label, "
+          "Tensor weight, Tensor ws_graph, Tensor ws_pairs, Tensor ws_bce, int table_bf16) -> (Tensor, Tensor, Tensor)");
     m.def("project_stacked(Tensor x, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor[] params, bool keep_hid, Tensor? xplanes) -> Tensor");
     m.def("adam_step(Tensor[] bufs, Tensor[] params, Tensor[] exp_avg, Tensor[] exp_avg_sq, Tensor state, float lr, float beta1, "
           "float beta2, float eps, float weight_decay, int host_step=0) -> ()");
@@ -302,10 +331,12 @@ TORCH_LIBRARY(disenlink_native, m) {
 
 TORCH_LIBRARY_IMPL(disenlink_native, Autograd, m) {
     m.impl("hot_path_pairs_loss", hot_path_pairs_loss);
+    m.impl("hot_path_pair_logits_loss", hot_path_pair_logits_loss);
     m.impl("project_stacked", project_stacked);
 }
 TORCH_LIBRARY_IMPL(disenlink_native, CUDA, m) {
     m.impl("hot_path_pairs_loss", hot_path_pairs_loss);      // (no-grad calls)
+    m.impl("hot_path_pair_logits_loss", hot_path_pair_logits_loss);
     m.impl("project_stacked", project_stacked);
     m.impl("adam_step", adam_step);
     m.impl("auc_pair_counts", auc_pair_counts);

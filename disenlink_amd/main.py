@@ -48,8 +48,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--data-file", type=str, default=None, help="binary dataset written by datasets.save_binary")
     p.add_argument("--synthetic", action="store_true", help="seeded synthetic stand-in of --dataset")
     p.add_argument("--table-dtype", choices=["f32", "bf16"], default="f32")
-    p.add_argument("--objective", choices=["pairs", "recon"], default="pairs",
-                   help="the training loss: pairs = the reference's BCE on m sampled negatives per edge; recon = the "
+    p.add_argument("--objective", choices=["pairs", "pairs-logit", "recon"], default="pairs",
+                   help="the training loss: pairs = the reference's BCE on m sampled negatives per edge; pairs-logit = the same "
+                        "pairs with the BCE taken of the LOGITS (a saturated pair keeps its gradient, and the validation / test "
+                        "AUC is counted on logits, which do not tie at probability 1; one GPU); recon = the "
                         "whole-graph reconstruction loss, every non-edge a negative and the edges up-weighted, with the "
                         "validation and test pairs ignored (Disentangle.forward_recon_loss: nothing of size N x N is formed; "
                         "one GPU, eager loop; with --table-dtype bf16 it runs on the bf16 tables the model is evaluated on)")
@@ -416,6 +418,8 @@ def main(argv=None):
     if args.objective == "recon" and (args.gpus > 1 or args.graph):
         raise SystemExit("--objective recon runs on one GPU in the eager loop only, with fp32 or bf16 tables (sharded and "
                          "graph-replayed reconstruction epochs are not implemented): drop --gpus / --graph")
+    if args.objective == "pairs-logit" and args.gpus > 1:
+        raise SystemExit("--objective pairs-logit runs on one GPU only (the sharded step has no logit-space form): drop --gpus")
     if args.gpus > 1:
         from .launch import launch_ranks, under_launcher
         if not under_launcher():                                    # BEFORE any GPU call: the parent starts and waits
@@ -465,7 +469,7 @@ def main(argv=None):
                             t=args.temperature, table_dtype=tdt).to(device)
         res = run_link_prediction(model, x, prepared, epochs=args.epochs, lr=args.lr,
                                   log=None if args.quiet else print,
-                                  use_graph=_use_graph(args) and args.objective == "pairs", objective=args.objective,
+                                  use_graph=_use_graph(args) and args.objective != "recon", objective=args.objective,
                                   pos_weight=args.pos_weight, recon_block_rows=args.recon_block_rows)
         if not args.quiet:
             print("test auc:", res.test_auc)

@@ -396,6 +396,37 @@ class Disentangle(nn.Module):
         H, prob = ops.HotPathPairs.apply(Z, graph, pairs, float(self.beta), float(self.temperature), self.table_dtype)
         return H.view(H.shape[0], -1), prob, ops.PairBCE.apply(prob, label, weight)
 
+    def forward_pair_logits(self, x, graph: Graph, pairs: PairList):
+        """(emb [N,K*d], logit [P]): ``forward_pairs`` with the scores left in LOGIT space — the value the sigmoid is taken
+        of, differentiable (ops.HotPathPairLogits).  A fp32 probability is exactly 1 from logit 16.64 on; the logit keeps its
+        order (AUC, ranking) and its gradient there."""
+        Z = self.project(x)
+        H, logit = ops.HotPathPairLogits.apply(Z, graph, pairs, float(self.beta), float(self.temperature), self.table_dtype)
+        return H.view(H.shape[0], -1), logit
+
+    def forward_pair_logits_loss(self, x, graph: Graph, pairs: PairList, label, weight):
+        """(emb [N,K*d], logit [P], loss) with loss = sum_q weight BCE-with-logits(logit, label): ``forward_pairs_loss`` in
+        logit space, with its dispatch rule — one pass (ops.HotPathPairLogitsLoss, or the compiled node) where
+        ``one_pass_scorer_wanted`` and the shape say so, forward_pair_logits + ops.PairBCELogits otherwise.  A saturated pair
+        keeps its gradient and its loss; an overflowed exp is NOT cured (its gradient is huge, infinite or NaN)."""
+        if label.numel() != pairs.n_pairs or weight.numel() != pairs.n_pairs:
+            raise ValueError("label / weight must cover the pair list")
+        Z = self.project(x)
+        dt = ops.table_code(self.table_dtype)
+        one_pass = ops.one_pass_scorer_wanted(self.table_dtype, Z.shape[0], Z.shape[1], Z.shape[2])
+        if one_pass and ops.score_pairs_train_logits_supported(pairs, Z.shape[1], Z.shape[2], dt):
+            if Z.dtype == torch.float32 and graph.n_rows == graph.n_nodes:
+                from . import native
+                if native.available():
+                    H, logit, loss = native.hot_path_pair_logits_loss(Z, graph, pairs, float(self.beta), float(self.temperature),
+                                                                      label, weight, self.table_dtype)
+                    return H.view(H.shape[0], -1), logit, loss
+            H, logit, loss = ops.HotPathPairLogitsLoss.apply(Z, graph, pairs, float(self.beta), float(self.temperature),
+                                                             self.table_dtype, label, weight)
+            return H.view(H.shape[0], -1), logit, loss
+        H, logit = ops.HotPathPairLogits.apply(Z, graph, pairs, float(self.beta), float(self.temperature), self.table_dtype)
+        return H.view(H.shape[0], -1), logit, ops.PairBCELogits.apply(logit, label, weight)
+
     def forward_recon_loss(self, x, graph: Graph, ignore=None, pos_weight=None, block_rows=None):
         """(emb [N,K*d], loss): the whole-graph reconstruction loss (ops.score_recon_loss) of project -> RouteAggregate ->
         ops.ReconLoss (a bf16 module, ``table_dtype=torch.bfloat16``: project -> ops.HotPathRecon, one node that routes,

@@ -26,8 +26,8 @@ from .graph import Graph, PairList
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdisenlink_torch.so")
 _state = {"loaded": None}
-BINDING_ABI = 6                  # csrc/torch/dl_torch.cpp: DL_TORCH_BINDING_ABI
-_OPS = ("hot_path_pairs_loss", "project_stacked", "adam_step", "auc_pair_counts", "epoch_finish", "binding_abi")
+BINDING_ABI = 7                  # csrc/torch/dl_torch.cpp: DL_TORCH_BINDING_ABI
+_OPS = ("hot_path_pairs_loss", "hot_path_pair_logits_loss", "project_stacked", "adam_step", "auc_pair_counts", "epoch_finish", "binding_abi")
 
 
 def load() -> bool:
@@ -62,6 +62,17 @@ def hot_path_pairs_loss(Z: torch.Tensor, graph: Graph, pairs: PairList, beta: fl
                         table_dtype=torch.float32):
     """(H [N,K,d] fp32, prob [P], loss) — see ops.HotPathPairsLoss; Z fp32 on the GPU, graph unsharded; table_dtype =
     torch.bfloat16 stores the gathered Z / H tables as bf16 (arithmetic and gradients stay fp32)."""
+    return _hot_path_loss("hot_path_pairs_loss", Z, graph, pairs, beta, t, label, weight, table_dtype)
+
+
+def hot_path_pair_logits_loss(Z: torch.Tensor, graph: Graph, pairs: PairList, beta: float, t: float, label, weight,
+                              table_dtype=torch.float32):
+    """(H [N,K,d] fp32, logit [P], loss) — ops.HotPathPairLogitsLoss as the compiled node: the step in logit space."""
+    return _hot_path_loss("hot_path_pair_logits_loss", Z, graph, pairs, beta, t, label, weight, table_dtype)
+
+
+def _hot_path_loss(op: str, Z, graph, pairs, beta, t, label, weight, table_dtype):
+    """The one call of both step operators (same schema, same operands)."""
     if not load():
         raise _lib.DisenlinkHipError("libdisenlink_torch.so is not built (python -m disenlink_amd.build)")
     N, K, d = Z.shape
@@ -70,9 +81,9 @@ def hot_path_pairs_loss(Z: torch.Tensor, graph: Graph, pairs: PairList, beta: fl
     ws_g = ops._workspace(graph, Z.device, K, d)
     ws_p = ops._workspace(pairs, Z.device, K, d)
     ws_b = ops._ws_bce(Z.device)
-    H, prob, loss = torch.ops.disenlink_native.hot_path_pairs_loss(Z, C.addressof(graph._struct), C.addressof(pairs._struct),
-                                                                   graph.n_edges, float(beta), float(t), label, weight, ws_g, ws_p, ws_b,
-                                                                   ops.table_code(table_dtype))
+    H, prob, loss = getattr(torch.ops.disenlink_native, op)(Z, C.addressof(graph._struct), C.addressof(pairs._struct),
+                                                            graph.n_edges, float(beta), float(t), label, weight, ws_g, ws_p, ws_b,
+                                                            ops.table_code(table_dtype))
     # the node's backward dereferences the two structs (and the device arrays they point to): they live exactly as long as
     # the node does, whatever the caller does with its Graph / PairList in between (a per-epoch resampled pair list)
     if loss.grad_fn is not None:

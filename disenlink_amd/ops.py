@@ -217,6 +217,73 @@ def pair_bce(prob, label, weight):
     return loss[0], g
 
 
+# ---- the same four in LOGIT space (include/disenlink_hip.h: "The pair-list objective in LOGIT space")
+def score_pairs_logits_fwd(Z, H, pu, pv, t: float, pairs: PairList | None = None):
+    """-> logit f32[P]: the value ``score_pairs_fwd`` feeds its sigmoid, at the listed pairs (dl_score_pairs_logits_fwd; no
+    stored terms — the logit-space backward recomputes)."""
+    lib = _lib.load()
+    (Z, dt), (H, dth) = _tab(Z), _tab(H)
+    _need_cuda(Z, H, pu, pv)
+    N, K, d = _nkd(Z)
+    if H.shape != Z.shape or dt != dth:
+        raise ValueError("Z and H differ in shape or storage type")
+    if pu.dtype != torch.int32 or pv.dtype != torch.int32:
+        raise TypeError("pair indices must be int32")
+    P = int(pu.numel())
+    logit = _empty(P, torch.float32, Z.device)
+    by_u = pairs.c_struct_by_u() if pairs is not None else None
+    _lib.check(lib.dl_score_pairs_logits_fwd(Z.data_ptr(), H.data_ptr(), N, K, d, dt, float(t), pu.data_ptr(), pv.data_ptr(),
+                                             P, by_u, logit.data_ptr(), _stream()), "dl_score_pairs_logits_fwd")
+    return logit
+
+
+def score_pairs_logits_bwd(Z, H, pairs: PairList, t: float, g_logit, dZ_out=None, dH_out=None):
+    """-> dZ, dH f32[N,K,d] (rows of the incidence plan are written) from d loss / d logit per pair."""
+    (Z, dt), (H, _dth), g_logit = _tab(Z), _tab(H), _f32c(g_logit)
+    N, K, d = _plan_check(pairs, Z, H, g_logit)
+    if g_logit.numel() != pairs.n_pairs:
+        raise ValueError("g_logit must cover the pair list")
+    dZ = _empty(Z.shape, torch.float32, Z.device) if dZ_out is None else dZ_out
+    dH = _empty(Z.shape, torch.float32, Z.device) if dH_out is None else dH_out
+    _plan_call("dl_score_pairs_logits_bwd", pairs, Z, dt, float(t), pairs.c_struct(int(g_logit.numel())), g_logit.data_ptr(),
+               dZ.data_ptr(), dH.data_ptr(), H=H)
+    return dZ, dH
+
+
+def score_pairs_train_logits_supported(pairs: PairList, K: int, d: int, dt: int) -> bool:
+    return bool(_lib.load().dl_score_pairs_train_logits_supported(pairs.c_struct(pairs.n_pairs), K, d, dt))
+
+
+def score_pairs_train_logits(Z, H, pairs: PairList, t: float, label, weight):
+    """-> logit f32[P], dZ, dH f32[N,K,d]: ``score_pairs_train`` in logit space (dl_score_pairs_train_logits) — dZ / dH are the
+    gradients of sum_q weight BCE-with-logits(logit, label); a saturated pair keeps its gradient."""
+    (Z, dt), (H, _dth), label, weight = _tab(Z), _tab(H), _f32c(label), _f32c(weight)
+    _plan_check(pairs, Z, H, label, weight)
+    inc = _train_pairs(pairs, label, weight)
+    logit = _empty(pairs.n_pairs, torch.float32, Z.device)
+    dZ = _empty(Z.shape, torch.float32, Z.device)
+    dH = _empty(Z.shape, torch.float32, Z.device)
+    _plan_call("dl_score_pairs_train_logits", pairs, Z, dt, float(t), inc, label.data_ptr(), weight.data_ptr(), logit.data_ptr(),
+               dZ.data_ptr(), dH.data_ptr(), H=H)
+    return logit, dZ, dH
+
+
+def pair_bce_logits(logit, label, weight):
+    """-> (loss, d loss / d logit f32[P]) of loss = sum_q weight[q] (max(x, 0) - x label + log1p(exp(-|x|))), both from ONE
+    kernel (dl_pair_bce_logits) on dl_pair_bce's scratch."""
+    logit, label, weight = _f32c(logit), _f32c(label), _f32c(weight)
+    _need_cuda(logit, label, weight)
+    if not (logit.numel() == label.numel() == weight.numel()):
+        raise ValueError("logit, label and weight differ in length")
+    loss = _empty(1, torch.float32, logit.device)
+    g = _empty_like(logit)
+    ws = _ws_bce(logit.device)
+    _lib.check(_lib.load().dl_pair_bce_logits(logit.data_ptr(), label.data_ptr(), weight.data_ptr(), logit.numel(),
+                                              loss.data_ptr(), g.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "dl_pair_bce_logits")
+    return loss[0], g
+
+
 def route_aggregate_bwd(g: Graph, Z, beta: float, t: float, p, a, s, dH, dZ_accum=None) -> torch.Tensor:
     """-> dZ f32[N,K,d] (added onto ``dZ_accum`` in place when given).  Unsharded graphs only."""
     (Z, dt), dH = _tab(Z), _f32c(dH)
@@ -376,6 +443,76 @@ class HotPathPairsLoss(torch.autograd.Function):
             dZ, dH = torch.zeros_like(dZs), torch.zeros_like(dHs)
         if g_prob is not None:                                   # some other function of the scores
             dZ2, dH2 = score_pairs_bwd(Zt, H, ctx.pairs, ctx.t, prob, g_prob.contiguous())
+            dZ += dZ2
+            dH += dH2
+        _step_backward_tail(ctx, Zt, a, s, dZ, dH, g_emb)
+        return dZ, None, None, None, None, None, None, None
+
+
+class PairBCELogits(torch.autograd.Function):
+    """loss = sum_q w[q] BCE-with-logits(logit[q], label[q]), loss and d loss / d logit from ONE kernel (pair_bce_logits)."""
+
+    @staticmethod
+    def forward(ctx, logit, label, weight):
+        loss, g = pair_bce_logits(logit, label, weight)
+        ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        (g,) = ctx.saved_tensors
+        return g * g_loss, None, None
+
+
+class HotPathPairLogits(torch.autograd.Function):
+    """Z [N,K,d] fp32 -> (emb [N,K,d] fp32, logit [P]): ``HotPathPairs`` with the LOGITS out; the backward takes d loss / d logit
+    and recomputes the per-factor terms (score_pairs_logits_bwd)."""
+
+    @staticmethod
+    def forward(ctx, Z, graph: Graph, pairs: PairList, beta: float, t: float, table_dtype):
+        ctx.set_materialize_grads(False)
+        Zt, p, a, s, H = step_tables(graph, Z, beta, t, table_dtype)
+        logit = score_pairs_logits_fwd(Zt, H, pairs.pu, pairs.pv, t, pairs)
+        ctx.graph, ctx.pairs, ctx.beta, ctx.t, ctx.p = graph, pairs, beta, t, p
+        ctx.save_for_backward(Zt, H, a, s)
+        return H.float(), logit
+
+    @staticmethod
+    def backward(ctx, g_emb, g_logit):
+        Zt, H, a, s = ctx.saved_tensors
+        g_logit = torch.zeros(ctx.pairs.n_pairs, dtype=torch.float32, device=Zt.device) if g_logit is None else g_logit.contiguous()
+        dZ, dH = score_pairs_logits_bwd(Zt, H, ctx.pairs, ctx.t, g_logit)
+        _step_backward_tail(ctx, Zt, a, s, dZ, dH, g_emb)
+        return dZ, None, None, None, None, None
+
+
+class HotPathPairLogitsLoss(torch.autograd.Function):
+    """Z [N,K,d] fp32 -> (emb, logit [P], loss): ``HotPathPairsLoss`` in logit space — the one-pass scorer with
+    gl = w (sigma(x) - y) (score_pairs_train_logits) and the loss value of pair_bce_logits.  The backward is that node's: d/dloss
+    scales the result inside the last kernel; a gradient arriving on ``logit`` goes through score_pairs_logits_bwd."""
+
+    @staticmethod
+    def forward(ctx, Z, graph: Graph, pairs: PairList, beta: float, t: float, table_dtype, label, weight):
+        ctx.set_materialize_grads(False)
+        Zt, p, a, s, H = step_tables(graph, Z, beta, t, table_dtype)
+        logit, dZs, dHs = score_pairs_train_logits(Zt, H, pairs, t, label, weight)
+        loss, _g = pair_bce_logits(logit, label, weight)         # the loss VALUE is what is used
+        ctx.graph, ctx.pairs, ctx.beta, ctx.t, ctx.p = graph, pairs, beta, t, p
+        ctx.save_for_backward(Zt, H, a, s, dZs, dHs)
+        return H.float(), logit, loss
+
+    @staticmethod
+    def backward(ctx, g_emb, g_logit, g_loss):
+        Zt, H, a, s, dZs, dHs = ctx.saved_tensors
+        if g_loss is not None and g_logit is None and g_emb is None and g_loss.numel() == 1:
+            return (route_aggregate_bwd_scaled(ctx.graph, Zt, ctx.beta, ctx.t, ctx.p, a, s, dHs, dZs, g_loss),
+                    None, None, None, None, None, None, None)
+        if g_loss is not None:
+            dZ, dH = dZs * g_loss, dHs * g_loss
+        else:
+            dZ, dH = torch.zeros_like(dZs), torch.zeros_like(dHs)
+        if g_logit is not None:                                  # some other function of the scores
+            dZ2, dH2 = score_pairs_logits_bwd(Zt, H, ctx.pairs, ctx.t, g_logit.contiguous())
             dZ += dZ2
             dH += dH2
         _step_backward_tail(ctx, Zt, a, s, dZ, dH, g_emb)

@@ -83,14 +83,38 @@ def _make_adam(model, on_gpu: bool, lr: float, weight_decay: float, capturable: 
     return Adam(model.parameters(), lr=lr, weight_decay=weight_decay, fused=on_gpu and _FUSED_ADAM)
 
 
-def _scores_and_loss(model, x, run, label_all, weight_all):
+def _scores_and_loss(model, x, run, label_all, weight_all, logit: bool = False):
     """(prob over [pos | neg | validation], loss) of one training forward on the GPU path; the model decides whether
-    the scorer runs forward + loss gradient + backward in one pass (model.forward_pairs_loss, DL_ONE_PASS_SCORER)."""
+    the scorer runs forward + loss gradient + backward in one pass (model.forward_pairs_loss, DL_ONE_PASS_SCORER).
+    ``logit``: the step in logit space (model.forward_pair_logits_loss): the scores are logits, the loss BCE with logits."""
+    if logit:
+        _emb, score, loss = model.forward_pair_logits_loss(x, run.graph, run.train_val_pairs, label_all, weight_all)
+        return score, loss
     if hasattr(model, "forward_pairs_loss"):
         _emb, prob, loss = model.forward_pairs_loss(x, run.graph, run.train_val_pairs, label_all, weight_all)
         return prob, loss
     _emb, prob = model.forward_pairs(x, run.graph, run.train_val_pairs)
     return prob, pair_bce_loss_fused(prob, label_all, weight_all)
+
+
+def _scores(model, x, graph, pairs, logit: bool):
+    """The scores an AUC is counted on: probabilities, or (``logit``) the logits — a rank statistic takes either."""
+    _emb, score = (model.forward_pair_logits if logit else model.forward_pairs)(x, graph, pairs)
+    return score
+
+
+def _check_logit_run(model, run) -> None:
+    """What objective="pairs-logit" needs, refused before the first launch."""
+    if not hasattr(model, "forward_pair_logits_loss") or not hasattr(model, "forward_pair_logits"):
+        raise TypeError("objective=\"pairs-logit\" needs a model with forward_pair_logits and forward_pair_logits_loss "
+                        "(disenlink_amd.model.Disentangle)")
+    n_val = run.train_val_pairs.n_pairs - run.n_pos - run.n_neg
+    if run.label_pos.numel() != run.n_pos or run.label_neg.numel() != run.n_neg or run.label_val.numel() != n_val:
+        raise ValueError(f"label / weight must cover the pair list: {run.label_pos.numel()} + {run.label_neg.numel()} + "
+                         f"{run.label_val.numel()} labels for {run.n_pos} + {run.n_neg} + {n_val} pairs")
+    if run.label_test.numel() != run.test_pairs.n_pairs:
+        raise ValueError(f"label / weight must cover the pair list: {run.label_test.numel()} test labels for "
+                         f"{run.test_pairs.n_pairs} pairs")
 
 
 def _loss_vectors(run, device):
@@ -104,7 +128,7 @@ def _loss_vectors(run, device):
     return label, weight
 
 
-def _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, es_factory=None):
+def _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, es_factory=None, logit: bool = False):
     """Capture one full epoch (forward, fused loss, backward, Adam step, validation AUC) into a HIP graph:
     every launch of the epoch — ours and torch's — is replayed with one host call, which removes the
     launch-bound host time of small graphs.  Returns (replay, out) with out = [loss, auc] on the device."""
@@ -115,7 +139,7 @@ def _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, es
     es = es_factory(val_plan) if es_factory is not None else None   # early_stop.DeviceEarlyStop or None
 
     def epoch():
-        prob, loss = _scores_and_loss(model, x, run, label_all, weight_all)
+        prob, loss = _scores_and_loss(model, x, run, label_all, weight_all, logit)
         # gradients are (re)created by the backward inside the capture — they come from the graph's own memory pool, so
         # replays find them at the same addresses (torch's whole-network capture recipe).  Keeping pre-allocated
         # gradients instead (zero_grad(set_to_none=False)) cost 4K fills and 4K accumulating adds per epoch.
@@ -171,19 +195,27 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
                         objective: str = "pairs", pos_weight=None, recon_block_rows=None) -> RunResult:
     """``use_graph=True`` (GPU only): replay each epoch from a captured HIP graph (same arithmetic, same
     schedule; only the host-side launch cost disappears).
-    ``objective``: "pairs" (the default: the reference's loss on the sampled pair list) or "recon" — the whole-graph
+    ``objective``: "pairs" (the default: the reference's loss on the sampled pair list), "pairs-logit" — the same pair list
+    and schedule in LOGIT space (``model.forward_pair_logits_loss``: BCE with logits, so a saturated pair keeps its gradient;
+    validation and test AUC counted on the logits, which do not tie where fp32 probabilities round to 0 or 1; GPU only,
+    eager, device early stop and HIP-graph replay alike) — or "recon" — the whole-graph
     reconstruction loss (``model.forward_recon_loss``: every non-edge of the training graph a negative, positives weighted
     by ``pos_weight``, default n_neg / n_pos, all validation and test pairs ignored, by strips of ``recon_block_rows``
     rows), in the eager loop with the bookkeeping on the host; validation and test AUC as ever."""
-    if objective not in ("pairs", "recon"):
-        raise ValueError(f"objective must be \"pairs\" or \"recon\", got {objective!r}")
+    if objective not in ("pairs", "pairs-logit", "recon"):
+        raise ValueError(f"objective must be \"pairs\", \"pairs-logit\" or \"recon\", got {objective!r}")
+    logit = objective == "pairs-logit"
+    if logit:
+        _check_logit_run(model, run)
+        if not x.is_cuda:
+            raise ValueError("objective=\"pairs-logit\" runs on the GPU only (there is no CPU form of the logit-space step)")
     if objective == "recon":
         if use_graph:
             raise ValueError("objective=\"recon\" runs in the eager loop only (HIP-graph replay of the reconstruction epoch "
                              "is not implemented): pass use_graph=False")
         return _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, recon_block_rows)
     if use_graph and x.is_cuda:
-        return _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log)
+        return _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log, logit)
     # same update rule as the reference's Adam (main_disentangled.py:150); on the GPU torch's single-kernel
     # ("fused") implementation of it instead of one multi-tensor launch per elementwise step
     opt = _make_adam(model, bool(x.is_cuda), lr, weight_decay)
@@ -207,7 +239,7 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
 
         def launch_epoch():
             model.train()
-            prob, loss = _scores_and_loss(model, x, run, label_all, weight_all)
+            prob, loss = _scores_and_loss(model, x, run, label_all, weight_all, logit)
             opt.zero_grad()
             loss.backward(seed)
             opt.step()
@@ -217,13 +249,13 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
         res.best_val_auc = drive(es, epochs, patience, launch_epoch, res, log)
         es.restore()
         with torch.no_grad():
-            _emb, prob = model.forward_pairs(x, run.graph, run.test_pairs)
+            prob = _scores(model, x, run.graph, run.test_pairs, logit)
         res.test_auc = float(auc_tie_avg(run.label_test, prob, check=False))
         return res
     for epoch in range(epochs):
         model.train()
         if fused:
-            prob, loss = _scores_and_loss(model, x, run, label_all, weight_all)
+            prob, loss = _scores_and_loss(model, x, run, label_all, weight_all, logit)
         else:
             _emb, prob = model.forward_pairs(x, run.graph, run.train_val_pairs)
             loss = pair_bce_loss(prob[:a], run.label_pos, prob[a:b], run.label_neg, run.m)
@@ -247,7 +279,7 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
             log(f"epoch: {epoch} loss: {res.losses[-1]} val_auc: {best_auc}")
     model.load_state_dict(weights)
     with torch.no_grad():
-        _emb, prob = model.forward_pairs(x, run.graph, run.test_pairs)
+        prob = _scores(model, x, run.graph, run.test_pairs, logit)
     res.test_auc = float(auc_tie_avg(run.label_test, prob, check=False))
     res.best_val_auc = best_auc
     return res
@@ -304,7 +336,7 @@ def _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weigh
     return res
 
 
-def _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log) -> RunResult:
+def _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log, logit: bool = False) -> RunResult:
     for lab in (run.label_val, run.label_test):
         if not 0 < float(lab.sum()) < lab.numel():
             raise ValueError("AUC undefined with one class")
@@ -312,7 +344,7 @@ def _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log) -> RunR
     label_all, weight_all = _loss_vectors(run, x.device)
     from .early_stop import DeviceEarlyStop, drive
     factory = lambda plan: DeviceEarlyStop(model, plan, epochs, patience) if DeviceEarlyStop.usable(model, x, plan) else None
-    replay, out, keep_alive = _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, factory)
+    replay, out, keep_alive = _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, factory, logit)
     res = RunResult(float("nan"), 0.0, 0)
     if isinstance(out, DeviceEarlyStop):
         es = out
@@ -321,7 +353,7 @@ def _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log) -> RunR
         del replay, keep_alive                                      # only now may the graph's external tensors go
         es.restore()
         with torch.no_grad():
-            _emb, prob = model.forward_pairs(x, run.graph, run.test_pairs)
+            prob = _scores(model, x, run.graph, run.test_pairs, logit)
         res.test_auc = float(auc_tie_avg(run.label_test, prob, check=False))
         return res
     snapshot = getattr(model, "snapshot_state", None) or (lambda: deepcopy(model.state_dict()))
@@ -345,7 +377,7 @@ def _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log) -> RunR
     del replay, keep_alive                                          # only now may the graph's external tensors go
     model.load_state_dict(weights)
     with torch.no_grad():
-        _emb, prob = model.forward_pairs(x, run.graph, run.test_pairs)
+        prob = _scores(model, x, run.graph, run.test_pairs, logit)
     res.test_auc = float(auc_tie_avg(run.label_test, prob, check=False))
     res.best_val_auc = best_auc
     return res
@@ -396,7 +428,7 @@ def prepare_run_sharded(split: LinkSplit, rank: int, world: int, device, row_byt
 
 def run_link_prediction_sharded(model, x_local: torch.Tensor, run: ShardedRun, epochs: int = 2000, lr: float = 1e-4,
                                 patience: int = 200, weight_decay: float = 5e-4, log=None, backend=None,
-                                group=None) -> RunResult:
+                                group=None, objective: str = "pairs") -> RunResult:
     """main_disentangled.py:191-224 with the rows of the graph, of the features and of the pair list sharded over the
     ranks of `group` (one process per GPU): `x_local` = the feature rows of ``run.shard.local_real_rows()``; `model` = a
     replica with IDENTICAL initial weights on every rank.  Per epoch: dist.sharded_forward_loss (all-gathers of Z, s, H;
@@ -405,6 +437,11 @@ def run_link_prediction_sharded(model, x_local: torch.Tensor, run: ShardedRun, e
     validation AUC (metrics.ShardedAucPlan: from that forward's probabilities, i.e. the weights before the step) cross
     the ranks in one small all-reduce — every rank sees the same numbers, so early stopping and the best-weights
     snapshot stay in lock-step without a broadcast.  Test AUC with the best weights, as :215-219."""
+    if objective == "pairs-logit":
+        raise NotImplementedError("objective=\"pairs-logit\" runs on one GPU only: the sharded step (dist.sharded_forward_loss) "
+                                  "has no logit-space form")
+    if objective != "pairs":
+        raise ValueError(f"the sharded loop runs objective=\"pairs\" only, got {objective!r}")
     import torch.distributed as dist
     from . import dist as dd
     on_gpu = bool(x_local.is_cuda)

@@ -991,6 +991,49 @@ int dl_score_pairs_train(const void* Z, const void* H, int K, int d, dl_dtype dt
                          const dl_pair_incidence* inc, const float* y, const float* w,
                          float* prob, float* dZ, float* dH, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- The pair-list objective in LOGIT space (opt-in; the entries above keep the reference's probability space and their
+ * bits).  x[q] = sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t) is the value the entries above feed their sigmoid; here it
+ * is the score itself, and the loss is the binary cross entropy WITH LOGITS:
+ *   loss = sum_q w[q] (max(x, 0) - x y + log1p(exp(-|x|))),      d loss / d x[q] = w[q] (sigma(x[q]) - y[q]).
+ * A fp32 probability is exactly 1 from x = 16.64 on and p (1 - p) passes under the 1e-12 clamp below x = -27.6: in
+ * probability space such a pair has a zero gradient, a loss pinned at 100 w and a score that ties in the AUC.  In logit space
+ * it keeps all three.  sigma(x) - y is formed as (1 - y) sigma(x) - y sigma(-x) from e = exp(-|x|), sigma(|x|) = 1 / (1 + e),
+ * sigma(-|x|) = e / (1 + e): either side to < 4 ulp of its own size, so y = 1 gives -sigma(-x), never 1.0 - 1.0.
+ * Logit space cures the saturation of the sigmoid, not the overflow of exp: where an exponent e_k overflows, the logit is
+ * +-inf (or NaN) and the gradients of that pair are huge, infinite or NaN — in probability space such a pair had gradient 0.
+ *
+ * dl_score_pairs_logits_fwd: dl_score_pairs_fwd with logit[q] = x[q] out and no stored terms (same arguments otherwise, same
+ * checks, same kernels up to the sigmoid).  Bit contracts, where the probability entries have them (fp32 tables, d = 64,
+ * K in {4, 8}): the logits are those of dl_score_pairs_train_logits; a hub plan, its residual plan and the plain plan give
+ * the same bits; a folded mirrored pair (inc_pair2) stores the same bits under both ids. */
+int dl_score_pairs_logits_fwd(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                              const int32_t* pu, const int32_t* pv, int n_pairs,
+                              const dl_pair_incidence* by_u, float* logit, void* stream);
+
+/* Backward of dl_score_pairs_logits_fwd, recomputing e and q (dl_score_pairs_bwd with coef = NULL): g_logit = dLoss/dlogit
+ * per pair IS the per-entry coefficient,
+ *   gl = g_logit;  dH[u] += gl e_k H[v][k];  dZ[u] += gl (q_k e_k)/t Z[v][k].  */
+int dl_score_pairs_logits_bwd(const void* Z, const void* H, int K, int d, dl_dtype dtype, float t,
+                              const dl_pair_incidence* inc, const float* g_logit,
+                              float* dZ, float* dH, void* ws, size_t ws_bytes, void* stream);
+
+/* dl_score_pairs_train in logit space: one pass that writes logit[q] (same writer rule: the entry whose weight has a clear
+ * sign bit) and dZ, dH = d(sum_q w BCE-with-logits(x, y)) / d(Z, H) with gl = w (sigma(x) - y), gl = 0 for w == 0, and NO
+ * p (1 - p) clamp factor; from gl on it is dl_score_pairs_train (coefficient clamps, accumulation order, partial slots;
+ * entry_yw works unchanged).  Same shape rule as dl_score_pairs_train_supported. */
+int dl_score_pairs_train_logits_supported(const dl_pair_incidence* inc, int K, int d, dl_dtype dtype);
+int dl_score_pairs_train_logits(const void* Z, const void* H, int K, int d, dl_dtype dtype, float t,
+                                const dl_pair_incidence* inc, const float* y, const float* w,
+                                float* logit, float* dZ, float* dH, void* ws, size_t ws_bytes, void* stream);
+
+/* The loss above and its gradient in one pass, beside dl_pair_bce:
+ *   loss[0] = sum_q w[q] (max(x, 0) - x y + log1p(exp(-|x|)))          g[q] = w[q] (sigma(x[q]) - y[q])
+ * max(x, 0) - x y is formed as (1 - y) max(x, 0) + y max(-x, 0), a zero factor dropping its term: x = +-inf costs 0 under the
+ * agreeing label and inf under the other.  A NaN logit at w = 0 is ignored; at w != 0 it gives a NaN loss.
+ * ws: at least 4352 bytes of scratch (the same 1,024 partial sums, added in the same fixed order as dl_pair_bce's). */
+int dl_pair_bce_logits(const float* logit, const float* y, const float* w, int n_pairs, float* loss, float* g,
+                       void* ws, size_t ws_bytes, void* stream);
+
 /* Backward of aggregate + normaliser + routing softmax (autograd of model.py:56-75; argmax and
  * masks carry no gradient), SURVEY.md Appendix A.3, split at its one global dependency:
  *   phase 1:  dw[e] = (1-beta) dH[i][p].Z[j][p],  dwr[e] = (1-beta) dH[j][p].Z[i][p]  (reverse edge)
