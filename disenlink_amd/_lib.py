@@ -136,6 +136,7 @@ EXPORTS = {
     "dl_auc_pair_counts_supported": (_i, [_i, _i]),
     "dl_auc_pair_counts": (_i, [_P, _P, _i, _P, _i, _P, _P]),
     "dl_auc_pair_counts_add": (_i, [_P, _P, _i, _P, _i, _P, _P]),
+    "dl_auc_pair_counts_grid": (_i, [_i, _i, C.POINTER(C.c_int)]),
     "dl_epoch_state_bytes": (C.c_size_t, []),
     "dl_epoch_finish": (_i, [_i, _P, _P, _P, _P, _P, C.c_double, _P, _P, C.c_longlong, C.c_longlong, _P, _i, _P]),
     "dl_score_pairs_train_supported": (_i, [_P, _i, _i, _i]),

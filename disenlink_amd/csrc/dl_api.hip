@@ -904,6 +904,16 @@ int dl_auc_pair_counts_add(const float* score, const int64_t* pos_idx, int n_pos
     return auc_pair_counts(score, pos_idx, n_pos, neg_idx, n_neg, u2, (hipStream_t)stream, /*clear=*/false);
 }
 
+int dl_auc_pair_counts_grid(int n_pos, int n_neg, int* grid) {
+    DL_REQUIRE(n_pos >= 1 && n_neg >= 1, "both classes must be present (%d x %d)", n_pos, n_neg);
+    DL_REQUIRE(grid != nullptr, "grid is NULL");
+    DL_REQUIRE(auc_counts_supported(n_pos, n_neg), "n_pos * n_neg too large for the slice-and-search form (%d x %d)",
+               n_pos, n_neg);
+    const AucGrid g = auc_grid(n_pos, n_neg);
+    grid[0] = g.small_is_pos; grid[1] = g.slices; grid[2] = g.chunks; grid[3] = g.per;
+    return DL_OK;
+}
+
 size_t dl_epoch_state_bytes(void) { return epoch_state_bytes(); }
 
 int dl_epoch_finish(int n_bufs, const float* const* params, float* const* best, const size_t* numel, const float* loss,

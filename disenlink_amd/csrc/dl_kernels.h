@@ -188,6 +188,8 @@ int score_links_top_fill(dl_dtype dt, int N, int K, int d, float t, const int32_
 bool auc_counts_supported(int n_pos, int n_neg);           // the smaller class fits the LDS
 int auc_pair_counts(const float* score, const int64_t* pos_idx, int n_pos, const int64_t* neg_idx, int n_neg,
                     unsigned long long* u2, hipStream_t st, bool clear = true);
+struct AucGrid { int small_is_pos, slices, chunks, per; };  // grid = slices x chunks, `per` searched scores per chunk
+AucGrid auc_grid(int n_pos, int n_neg);                     // both sizes >= 1
 
 size_t epoch_state_bytes();
 int epoch_finish(int n_bufs, const float* const* params, float* const* best, const size_t* numel, const float* loss,

@@ -8,6 +8,9 @@
 // with two 10-step binary searches per element.  grid = slices x chunks; no sort of a whole class, no inter-workgroup
 // dependency, integer atomics (exact, order-independent).  ~10 us at 10^4 x 5*10^4 scores against ~130 us for a
 // device sort of the negatives plus the searches.
+// A NaN among the listed scores has no rank: a wavefront that loads one ORs DL_AUC_NAN_MARK (bit 63, which no count
+// reaches: 2 * 4e11 < 2^40) into *u2 — an integer atomic like the counts, in the same launch — and every reader of u2 turns
+// a marked value into a NaN AUC.  The counts of NaN-free input are untouched.  +-inf are ordinary scores.
 // (Tried first: all n_pos * n_neg comparisons with one v_cmp per 64 pairs and s_bcnt1: 115 us — the scalar unit, one
 // instruction per cycle per CU, is the bound; and a whole-class bitonic sort in LDS by every workgroup: 212 us.)
 #include <algorithm>
@@ -32,6 +35,7 @@ __global__ __launch_bounds__(AUC_THREADS) void auc_slice_search_kernel(const flo
     const int s0 = blockIdx.x * AUC_THREADS;
     const int cnt = min(AUC_THREADS, n_small - s0);             // real scores in this slice (>= 1), the rest is +inf
     float v = tid < cnt ? score[small_idx[s0 + tid]] : INFINITY;
+    bool nan_seen = v != v;                                     // (fminf / fmaxf below would drop it from the sorted slice)
     for (int k = 2; k <= AUC_THREADS; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
             float other;
@@ -54,6 +58,7 @@ __global__ __launch_bounds__(AUC_THREADS) void auc_slice_search_kernel(const flo
     unsigned long long mine = 0;
     for (int g = g0 + tid; g < g1; g += AUC_THREADS) {
         const float x = score[large_idx[g]];
+        nan_seen |= x != x;                                     // (fails every comparison below: lb = ub = 0)
         int lb = 0, ub = 0;                                     // first index with a[i] >= x / a[i] > x, within [0, cnt]
         for (int len = cnt; len > 0;) {
             const int half = len >> 1;
@@ -69,6 +74,7 @@ __global__ __launch_bounds__(AUC_THREADS) void auc_slice_search_kernel(const flo
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
     if ((tid & 63) == 0) red[tid >> 6] = mine;
+    if (__any(nan_seen) && (tid & 63) == 0) atomicOr(u2, DL_AUC_NAN_MARK);   // off the NaN-free path: a wavefront that saw one
     __syncthreads();
     if (tid == 0) {
         unsigned long long tot = 0;
@@ -82,25 +88,33 @@ bool auc_counts_supported(int n_pos, int n_neg) {
     return (double)std::min(n_pos, n_neg) * (double)std::max(n_pos, n_neg) <= 4.0e11;
 }
 
+// the launch geometry (host arithmetic only; dl_auc_pair_counts_grid shows it to a caller)
+AucGrid auc_grid(int n_pos, int n_neg) {
+    AucGrid g;
+    g.small_is_pos = n_pos <= n_neg ? 1 : 0;
+    const int n_small = g.small_is_pos ? n_pos : n_neg, n_large = g.small_is_pos ? n_neg : n_pos;
+    g.slices = (n_small + AUC_THREADS - 1) / AUC_THREADS;
+    // ~1,024 workgroups where the sizes allow; a chunk of the searched class is at least one pass of the workgroup
+    int target = 1024;                                          // tools/auc_time.py: flat from 128 to 2,048 at 11 slices x 54k, 1,024+ best at 67 x 340k
+    if (config().auc_target > 0) target = config().auc_target;   // DL_AUC_TARGET
+    int chunks = std::max(1, std::min((n_large + AUC_THREADS - 1) / AUC_THREADS, (target + g.slices - 1) / g.slices));
+    chunks = std::min(chunks, 65535);
+    g.per = (n_large + chunks - 1) / chunks;
+    g.chunks = (n_large + g.per - 1) / g.per;
+    return g;
+}
+
 int auc_pair_counts(const float* score, const int64_t* pos_idx, int n_pos, const int64_t* neg_idx, int n_neg,
                     unsigned long long* u2, hipStream_t st, bool clear) {
     // clear = false: the counts are ADDED to *u2 (the caller keeps it at zero between evaluations: dl_epoch_finish reads
     // and clears it in its own launch — no memset node in the epoch)
     if (clear && hipMemsetAsync(u2, 0, sizeof(unsigned long long), st) != hipSuccess) return check_launch("auc_pair_counts(memset)");
     if (n_pos == 0 || n_neg == 0) return DL_OK;
-    const bool small_is_pos = n_pos <= n_neg;
-    const int n_small = small_is_pos ? n_pos : n_neg, n_large = small_is_pos ? n_neg : n_pos;
-    const int slices = (n_small + AUC_THREADS - 1) / AUC_THREADS;
-    // ~1,024 workgroups where the sizes allow; a chunk of the searched class is at least one pass of the workgroup
-    int target = 1024;                                          // tools/auc_time.py: flat from 128 to 2,048 at 11 slices x 54k, 1,024+ best at 67 x 340k
-    if (config().auc_target > 0) target = config().auc_target;   // DL_AUC_TARGET
-    int chunks = std::max(1, std::min((n_large + AUC_THREADS - 1) / AUC_THREADS, (target + slices - 1) / slices));
-    chunks = std::min(chunks, 65535);
-    const int per = (n_large + chunks - 1) / chunks;
-    chunks = (n_large + per - 1) / per;
-    hipLaunchKernelGGL(auc_slice_search_kernel, dim3((unsigned)slices, (unsigned)chunks), dim3(AUC_THREADS), 0, st, score,
-                       small_is_pos ? pos_idx : neg_idx, n_small, small_is_pos ? neg_idx : pos_idx, n_large, per,
-                       small_is_pos ? 1 : 0, u2);
+    const AucGrid g = auc_grid(n_pos, n_neg);
+    const bool small_is_pos = g.small_is_pos != 0;
+    hipLaunchKernelGGL(auc_slice_search_kernel, dim3((unsigned)g.slices, (unsigned)g.chunks), dim3(AUC_THREADS), 0, st, score,
+                       small_is_pos ? pos_idx : neg_idx, small_is_pos ? n_pos : n_neg, small_is_pos ? neg_idx : pos_idx,
+                       small_is_pos ? n_neg : n_pos, g.per, g.small_is_pos, u2);
     return check_launch("auc_pair_counts");
 }
 
@@ -209,7 +223,7 @@ int adam_step(int n_bufs, float* const* params, const float* const* grads, float
 // the read-back until the host has launched the next epoch's first kernel (74 us of a 940 us epoch on the squirrel-shaped
 // graph, profiles/r5z_epoch_sequence.txt) and torch's scalar glue adds five launches.  Here the bookkeeping lives on the
 // device, in ONE launch at the end of the epoch:
-//   auc = u2 / denom2 (double, correctly rounded: the same value the host formed);  improved = !stopped && auc > best_auc
+//   auc = u2 / denom2 (double, correctly rounded: the same value the host formed; NaN when u2 carries DL_AUC_NAN_MARK);  improved = !stopped && auc > best_auc
 //   improved: the parameter buffers are copied to the best-weights buffers (state AFTER the step, like :209), stale = 0;
 //   else stale += 1;  stale > patience: stopped = 1 — from then on the launch changes nothing (the host, which reads the
 //   history one epoch behind, may have queued an epoch or two more: they must not touch the best weights);
@@ -238,7 +252,8 @@ __global__ __launch_bounds__(256) void epoch_finish_kernel(SnapBufs b, const flo
                                                            long long max_epochs, long long patience, double* host_ring,
                                                            int ring) {
     const unsigned long long cnt = *reinterpret_cast<volatile unsigned long long*>(u2);
-    const double auc = denom2 > 0.0 ? (double)cnt / denom2 : (double)NAN;
+    // DL_AUC_NAN_MARK: a validation score was NaN — the AUC is NaN, `auc > best_auc` is false: a stale epoch
+    const double auc = denom2 > 0.0 && !(cnt & DL_AUC_NAN_MARK) ? (double)cnt / denom2 : (double)NAN;
     // (epochs past max_epochs — the tail of a replayed graph that holds several epochs — count as stopped too)
     const bool stopped = *reinterpret_cast<volatile long long*>(&st->stopped) != 0 ||
                          *reinterpret_cast<volatile long long*>(&st->epoch) >= max_epochs;

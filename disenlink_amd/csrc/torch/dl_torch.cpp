@@ -276,6 +276,7 @@ void adam_step(at::TensorList bufs, at::TensorList params, at::TensorList exp_av
 }
 
 // ---------------------------------------------------------------------------- tie-averaged AUC counts (main_disentangled.py:202-204)
+// (the int64 result is negative — DL_AUC_NAN_MARK — when a listed score is NaN: the caller selects NaN on the device)
 Tensor auc_pair_counts(const Tensor& score, const Tensor& pos_idx, const Tensor& neg_idx) {
     TORCH_CHECK(score.is_cuda() && score.scalar_type() == at::kFloat && score.is_contiguous(), "score must be a dense CUDA fp32 vector");
     TORCH_CHECK(pos_idx.scalar_type() == at::kLong && neg_idx.scalar_type() == at::kLong, "index sets must be int64");

@@ -36,7 +36,8 @@ def pair_bce_loss_fused(prob_train, label_train, weight_train) -> torch.Tensor:
 
 def auc_tie_avg(label: torch.Tensor, score: torch.Tensor, check: bool = True) -> torch.Tensor:
     """0-dim float64 tensor on score.device.  ``check=True`` raises if only one class is present (one
-    device->host sync); with ``check=False`` nothing here synchronises and a one-class input gives nan."""
+    device->host sync); with ``check=False`` nothing here synchronises and a one-class input gives nan.
+    A NaN score has no rank (sklearn raises): any NaN among the scores gives nan, selected on the device."""
     label = label.reshape(-1)
     score = score.reshape(-1).detach()
     n = score.numel()
@@ -53,7 +54,17 @@ def auc_tie_avg(label: torch.Tensor, score: torch.Tensor, check: bool = True) ->
     last = torch.searchsorted(ss, ss, right=True) - 1
     rank_sorted = (first + last).to(torch.float64) / 2.0 + 1.0
     r_pos = (rank_sorted * pos[order].to(torch.float64)).sum()
-    return (r_pos - n_pos * (n_pos + 1.0) / 2.0) / (n_pos * n_neg)
+    return _nan_if(torch.isnan(score).any(), (r_pos - n_pos * (n_pos + 1.0) / 2.0) / (n_pos * n_neg))
+
+
+def _nan_if(bad: torch.Tensor, value: torch.Tensor) -> torch.Tensor:
+    """`value` (0-dim float64), or nan where the 0-dim bool `bad` holds: a select on the device, no read-back."""
+    return torch.where(bad, torch.full_like(value, float("nan")), value)
+
+
+def _counts_to_float(u2: torch.Tensor) -> torch.Tensor:
+    """dl_auc_pair_counts' int64 result as an exact float64 — nan when it carries DL_AUC_NAN_MARK (bit 63: a NaN score)."""
+    return _nan_if(u2 < 0, u2.to(torch.float64))
 
 
 class AucPlan:
@@ -64,7 +75,9 @@ class AucPlan:
         AUC = ( sum_p #{n: s_n < s_p} + 1/2 #{n: s_n == s_p} ) / (n_pos * n_neg)
 
     — the Mann-Whitney statistic with tie-averaged ranks, i.e. sklearn.roc_auc_score (main_disentangled.py:202-204,
-    :217-219), from integer counts.  No data-dependent shapes: nothing synchronises, and it can be graph-captured."""
+    :217-219), from integer counts.  No data-dependent shapes: nothing synchronises, and it can be graph-captured.
+    A NaN among the listed scores gives nan on every path (the kernel marks its count, the sort path looks); +-inf are
+    ordinary scores."""
 
     PAIR_LIMIT = 4.0e11              # dl_auc_pair_counts_supported: n_pos * n_neg up to which the kernel is used
 
@@ -89,13 +102,13 @@ class AucPlan:
             from . import _lib, native
             score = score.contiguous()
             if native.available():                                 # the same launch from the compiled binding
-                return native.auc_pair_counts(score, self.pos_idx, self.neg_idx)[0].to(torch.float64) / self._denom2
+                return _counts_to_float(native.auc_pair_counts(score, self.pos_idx, self.neg_idx)[0]) / self._denom2
             lib = _lib.load()
             u2 = torch.empty(1, dtype=torch.int64, device=score.device)
             _lib.check(lib.dl_auc_pair_counts(score.data_ptr(), self.pos_idx.data_ptr(), self.n_pos, self.neg_idx.data_ptr(),
                                               self.n_neg, u2.data_ptr(), torch.cuda.current_stream().cuda_stream),
                        "dl_auc_pair_counts")
-            return u2[0].to(torch.float64) / self._denom2
+            return _counts_to_float(u2[0]) / self._denom2
         sp = score.index_select(0, self.pos_idx)
         # stable=True: the merge-sort path, the one the rank-based auc_tie_avg has always used (also under HIP-graph
         # capture); which order equal negatives end up in does not matter here
@@ -103,8 +116,10 @@ class AucPlan:
         below = torch.searchsorted(sn, sp, right=False)
         upto = torch.searchsorted(sn, sp, right=True)
         u2 = (below + upto).sum()                                   # 2 * (below + (upto - below) / 2), in int64: exact
-        return u2.to(torch.float64) / self._denom2.to(score.device) if denom > 0 else torch.full((), float("nan"), dtype=torch.float64,
-                                                                                device=score.device)
+        if denom <= 0:
+            return torch.full((), float("nan"), dtype=torch.float64, device=score.device)
+        # (torch sorts NaN last and finds it above everything: a finite count of no meaning)
+        return _nan_if(torch.isnan(sp).any() | torch.isnan(sn).any(), u2.to(torch.float64) / self._denom2.to(score.device))
 
 
 class ShardedAucPlan:
@@ -118,7 +133,8 @@ class ShardedAucPlan:
     for a run), each rank counts ITS positives against all negatives (the same kernel as AucPlan — dl_auc_pair_counts — on
     the GPU, a sort + two binary searches elsewhere), and the integer counts are summed by the caller's all-reduce
     (`partial(score)` returns this rank's 2U as an exact float64; `auc(score)` does the all-reduce itself).  Equal to
-    sklearn.roc_auc_score on the concatenated vectors (main_disentangled.py:202-204, :217-219), whatever the sharding."""
+    sklearn.roc_auc_score on the concatenated vectors (main_disentangled.py:202-204, :217-219), whatever the sharding.
+    A NaN score on any rank makes that rank's share nan, hence the all-reduced sum and the AUC of every rank."""
 
     def __init__(self, label_local: torch.Tensor, group=None):
         import torch.distributed as dist
@@ -147,7 +163,8 @@ class ShardedAucPlan:
         self._denom2 = 2.0 * float(self.n_pos) * float(self.n_neg)
 
     def partial(self, score_local: torch.Tensor) -> torch.Tensor:
-        """This rank's share of 2U (0-dim float64 on score_local.device; exact: an integer below 2^53)."""
+        """This rank's share of 2U (0-dim float64 on score_local.device; exact: an integer below 2^53; nan if one of this
+        rank's scores is NaN)."""
         dist = self.dist
         score_local = score_local.reshape(-1).detach().float()
         dev = score_local.device
@@ -162,18 +179,19 @@ class ShardedAucPlan:
         else:
             dist.all_gather_into_tensor(gathered, send, group=self.group)
         buf[self.world * self.max_neg:] = score_local
-        if self.n_local_pos == 0 or self.n_neg == 0:
-            return torch.zeros((), dtype=torch.float64, device=dev)
+        if self.n_local_pos == 0 or self.n_neg == 0:                # nothing to count here, but this rank's scores still speak
+            return _nan_if(torch.isnan(score_local).any(), torch.zeros((), dtype=torch.float64, device=dev))
         if buf.is_cuda and float(self.n_local_pos) * float(self.n_neg) <= AucPlan.PAIR_LIMIT:
             from . import _lib
             u2 = torch.empty(1, dtype=torch.int64, device=dev)
             _lib.check(_lib.load().dl_auc_pair_counts(buf.data_ptr(), self.local_pos_idx.data_ptr(), self.n_local_pos,
                                                       self.all_neg_idx.data_ptr(), self.n_neg, u2.data_ptr(),
                                                       torch.cuda.current_stream().cuda_stream), "dl_auc_pair_counts")
-            return u2[0].to(torch.float64)
+            return _counts_to_float(u2[0])
         sp = buf.index_select(0, self.local_pos_idx)
         sn = torch.sort(buf.index_select(0, self.all_neg_idx), stable=True).values
-        return (torch.searchsorted(sn, sp, right=False) + torch.searchsorted(sn, sp, right=True)).sum().to(torch.float64)
+        u2 = (torch.searchsorted(sn, sp, right=False) + torch.searchsorted(sn, sp, right=True)).sum().to(torch.float64)
+        return _nan_if(torch.isnan(sp).any() | torch.isnan(sn).any(), u2)
 
     def auc_from_sum(self, u2_sum) -> float:
         return float(u2_sum) / self._denom2 if self._denom2 > 0 else float("nan")

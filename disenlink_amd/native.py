@@ -117,7 +117,8 @@ def adam_step(bufs, params, exp_avg, exp_avg_sq, state, lr, beta1, beta2, eps, w
 
 
 def auc_pair_counts(score: torch.Tensor, pos_idx: torch.Tensor, neg_idx: torch.Tensor) -> torch.Tensor:
-    """int64[1]: sum over positives of (2 #{negatives below} + #{negatives equal}) — dl_auc_pair_counts."""
+    """int64[1]: sum over positives of (2 #{negatives below} + #{negatives equal}) — dl_auc_pair_counts; negative
+    (DL_AUC_NAN_MARK, bit 63) when a listed score is NaN: metrics.AucPlan turns that into a nan AUC."""
     return torch.ops.disenlink_native.auc_pair_counts(score, pos_idx, neg_idx)
 
 

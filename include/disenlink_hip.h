@@ -912,7 +912,14 @@ int dl_score_links_between_fill_dtype(const void* ZA, const void* HA, int nA, co
  * the smaller class is cut into slices of 1,024 scores, a workgroup sorts its slice (bitonic network, shuffles +
  * LDS) and binary-searches its chunk of the other class in it; the counts of the slices add up.  Work grows as
  * ceil(min/1024) * max: dl_auc_pair_counts_supported says whether the sizes are in range (n_pos * n_neg <= 4e11;
- * beyond that a device sort on the caller's side is the better tool).  Scores are expected to be finite. */
+ * beyond that a device sort on the caller's side is the better tool).
+ * NaN: a NaN score has no rank, so the AUC of a list that holds one is NaN (sklearn raises).  Any NaN among the scores
+ * that pos_idx / neg_idx list sets DL_AUC_NAN_MARK (bit 63) in u2[0] — an integer OR from a wavefront that loaded it, in
+ * the same launch; counts stay below 2^40, so neither they nor the sums of dl_auc_pair_counts_add carry into it, and the
+ * other bits of a marked value mean nothing.  A reader tests the mark (u2 < 0 as int64) before it divides:
+ * dl_epoch_finish, metrics.AucPlan and metrics.ShardedAucPlan do.  Without a NaN the count is exact and the mark is
+ * clear.  +inf and -inf are ordinary scores (equal to themselves, above / below every finite one). */
+#define DL_AUC_NAN_MARK (1ull << 63)
 int dl_auc_pair_counts_supported(int n_pos, int n_neg);
 int dl_auc_pair_counts(const float* score, const int64_t* pos_idx, int n_pos, const int64_t* neg_idx, int n_neg,
                        unsigned long long* u2, void* stream);
@@ -920,11 +927,17 @@ int dl_auc_pair_counts(const float* score, const int64_t* pos_idx, int n_pos, co
  * *u2 at zero between evaluations — dl_epoch_finish reads and clears it. */
 int dl_auc_pair_counts_add(const float* score, const int64_t* pos_idx, int n_pos, const int64_t* neg_idx, int n_neg,
                            unsigned long long* u2, void* stream);
+/* The launch geometry of the two calls above for these sizes (both >= 1), host arithmetic only, no GPU work:
+ * grid[0] = 1 if the positives are the sliced (sorted) class — they are when n_pos <= n_neg — else 0, grid[1] = slices of
+ * 1,024 scores, grid[2] = chunks of the searched class, grid[3] = scores per chunk; slices x chunks workgroups
+ * (DL_AUC_TARGET: the number of workgroups aimed at, default 1,024). */
+int dl_auc_pair_counts_grid(int n_pos, int n_neg, int* grid);
 
 /* End-of-epoch bookkeeping of the training loop ON THE DEVICE (main_disentangled.py:199-214: loss and validation AUC of
  * the epoch, `if auc > best_auc: best_auc = auc; weights = deepcopy(state_dict); stale = 0 else stale += 1`, patience), in
  * one launch, so that the host need not read anything back before it launches the next epoch:
- *   auc = *u2 / denom2 in double (u2 = the counts of dl_auc_pair_counts[_add], denom2 = 2 n_pos n_neg; NaN if denom2 <= 0);
+ *   auc = *u2 / denom2 in double (u2 = the counts of dl_auc_pair_counts[_add], denom2 = 2 n_pos n_neg; NaN if denom2 <= 0
+ *   or if *u2 carries DL_AUC_NAN_MARK: `auc > best_auc` is then false, i.e. a stale epoch whose hist / ring entry is NaN);
  *   if !stopped && auc > best_auc: best[i][:] = params[i][:] for the n_bufs <= DL_ADAM_MAX_BUFS buffers (numel[i] floats
  *   each: the weights AFTER the step, like :209), best_auc = auc, stale = 0, best_epoch = epoch;  else stale += 1;
  *   hist[2 epoch] = loss[0], hist[2 epoch + 1] = auc;  epoch += 1;  stale > patience: stopped = 1;  *u2 = 0.
