@@ -118,6 +118,9 @@ EXPORTS = {
     "dl_score_allpairs_bwd_dense_supported": (_i, [_i, _i]),
     "dl_score_allpairs_bwd_dense_workspace_bytes": (_z, [_i, _i, _i]),
     "dl_score_allpairs_bwd_dense": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_score_allpairs_logits_workspace_bytes": (_z, [_i, _i, _i]),
+    "dl_score_allpairs_logits_fwd": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _z, _P]),
+    "dl_score_allpairs_logits_bwd_dense": (_i, [_P, _P, _i, _i, _i, _f, _P, _P, _P, _P, _z, _P]),
     "dl_score_recon_supported": (_i, [_i, _i]),
     "dl_score_recon_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "dl_score_recon_workspace_bytes": (_z, [_i, _i, _i, _i]),
@@ -125,6 +128,7 @@ EXPORTS = {
     "dl_score_recon_form_dtype": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
     "dl_score_recon_workspace_bytes_dtype": (_z, [_i, _i, _i, _i, _i]),
     "dl_score_recon_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _P, _P, _f, _f, _i, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_score_recon_logits": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _P, _P, _f, _f, _i, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_topk_supported": (_i, [_i, _i]),
     "dl_score_mine_supported": (_i, [_i, _i]),
     "dl_score_mine_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),

@@ -367,6 +367,28 @@ int dl_score_allpairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_
     return generic_score_allpairs_fwd((const float*)Z, (const float*)H, N, K, d, t, prob, (hipStream_t)stream);
 }
 
+size_t dl_score_allpairs_logits_workspace_bytes(int N, int K, int d) {
+    if (N <= 0 || N > 46340 || K < 1 || K > DL_MAX_FACTORS || d < 1) return 0;
+    return dense_logits_workspace_bytes(N, K, d);
+}
+
+int dl_score_allpairs_logits_fwd(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, float* logit,
+                                 void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(dtype == DL_F32, "the dense logits serve fp32 tables, got dtype %d", (int)dtype);
+    DL_REQUIRE(N >= 0 && N <= 46340, "dense [N,N] scoring needs 0 <= N <= 46340, got %d", N);
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    if (N == 0) return DL_OK;
+    DL_REQUIRE(Z && H && logit, "NULL argument");
+    const size_t need = dense_logits_workspace_bytes(N, K, d);
+    if (!ws || ws_bytes < need) {
+        set_error("workspace too small: have %zu, need %zu (dl_score_allpairs_logits_workspace_bytes)", ws ? ws_bytes : (size_t)0,
+                  need);
+        return DL_E_WORKSPACE;
+    }
+    return dense_mfma_score_allpairs_logits_fwd((const float*)Z, (const float*)H, N, K, d, t, logit, ws, (hipStream_t)stream);
+}
+
 int dl_score_allpairs_fwd_form(int N, int K, int d, dl_dtype dtype, size_t ws_bytes, int* out) {
     if (int rc = check_shape(K, d)) return rc;
     DL_REQUIRE(out != nullptr && (dtype == DL_F32 || dtype == DL_BF16) && N >= 1 && N <= 46340, "bad argument");
@@ -1071,6 +1093,23 @@ int dl_score_allpairs_bwd_dense(const float* Z, const float* H, int N, int K, in
     return dense_bwd_score_allpairs(Z, H, N, K, d, t, prob, g_prob, dZ, dH, ws, (hipStream_t)stream);
 }
 
+int dl_score_allpairs_logits_bwd_dense(const float* Z, const float* H, int N, int K, int d, float t, const float* g_logit,
+                                       float* dZ, float* dH, void* ws, size_t ws_bytes, void* stream) {
+    if (int rc = check_shape(K, d)) return rc;
+    DL_REQUIRE(dense_bwd_supported(d), "the dense backward serves fp32 tables with 1 <= d <= 128, got d=%d", d);
+    DL_REQUIRE(N >= 0 && N <= 46340, "dense [N,N] scoring needs 0 <= N <= 46340, got %d", N);
+    DL_REQUIRE(t != 0.0f, "temperature is 0");
+    if (N == 0) return DL_OK;
+    DL_REQUIRE(Z && H && g_logit && dZ && dH, "NULL argument");
+    const size_t need = dense_bwd_workspace_bytes(N, K, d);
+    if (!ws || ws_bytes < need) {
+        set_error("workspace too small: have %zu, need %zu (dl_score_allpairs_bwd_dense_workspace_bytes)", ws ? ws_bytes : (size_t)0,
+                  need);
+        return DL_E_WORKSPACE;
+    }
+    return dense_bwd_score_allpairs(Z, H, N, K, d, t, nullptr, g_logit, dZ, dH, ws, (hipStream_t)stream);
+}
+
 int dl_score_recon_supported(int K, int d) { return K >= 1 && K <= DL_MAX_FACTORS && score_recon_supported(K, d) ? 1 : 0; }
 
 // block_rows: 0 (the default) or a positive multiple of 128
@@ -1102,10 +1141,11 @@ int dl_score_recon(const float* Z, const float* H, int N, int K, int d, float t,
                                 counts_out, dZ, dH, ws, ws_bytes, stream);
 }
 
-int dl_score_recon_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
-                         const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
-                         int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
-                         void* stream) {
+// dl_score_recon_dtype and dl_score_recon_logits: one set of checks, one driver
+static int score_recon_space(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
+                             const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
+                             int block_rows, bool logit, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws,
+                             size_t ws_bytes, void* stream) {
     DL_REQUIRE(known_dtype(dtype), "unknown dtype %d", (int)dtype);
     if (int rc = check_shape(K, d)) return rc;
     DL_REQUIRE(dl_score_recon_supported(K, d), "the reconstruction loss serves fp32 and bf16 tables with 1 <= d <= 128, got d=%d", d);
@@ -1120,8 +1160,24 @@ int dl_score_recon_dtype(const void* Z, const void* H, int N, int K, int d, dl_d
                   dtype == DL_F32 ? "" : "_dtype");
         return DL_E_WORKSPACE;
     }
-    return score_recon(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, loss_out,
+    return score_recon(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, logit, loss_out,
                        counts_out, dZ, dH, ws, (hipStream_t)stream);
+}
+
+int dl_score_recon_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
+                         const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
+                         int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
+                         void* stream) {
+    return score_recon_space(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, false,
+                             loss_out, counts_out, dZ, dH, ws, ws_bytes, stream);
+}
+
+int dl_score_recon_logits(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
+                          const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
+                          int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
+                          void* stream) {
+    return score_recon_space(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, true,
+                             loss_out, counts_out, dZ, dH, ws, ws_bytes, stream);
 }
 
 int dl_score_pairs_train_supported(const dl_pair_incidence* inc, int K, int d, dl_dtype dtype) {

@@ -262,6 +262,17 @@ __device__ __forceinline__ float sigmoid_minus_label(float x, float y) {
     return s * fmaf(pos ? b : a, e, pos ? a : b);
 }
 
+// The loss term that goes with it: BCE-with-logits l(x, y) = max(x, 0) - x y + log1p(exp(-|x|)), with max(x, 0) - x y formed
+// as (1 - y) max(x, 0) + y max(-x, 0) and a zero factor dropping its term: the same value for every finite x (one rounding
+// apart), and x = +-inf costs 0 under the agreeing label and inf under the other instead of inf - inf.  No log of a rounded
+// probability and no clamp.  A NaN x stays NaN (fmaxf would drop it).  The body of pair_bce_logits_kernel (dl_train.hip),
+// which keeps its own copy: called from there the helper moved that kernel's instruction stream (two loads and a wait swapped).
+__device__ __forceinline__ float bce_logits_term(float x, float y) {
+    const float ny = 1.0f - y;
+    const float lin = (ny == 0.0f ? 0.0f : ny * fmaxf(x, 0.0f)) + (y == 0.0f ? 0.0f : y * fmaxf(-x, 0.0f));
+    return x != x ? x : lin + log1pf(expf(-fabsf(x)));
+}
+
 // d s_raw -> ds of the normaliser: -(acc) / s~^2, zero where the raw sum was zero (model.py:72).
 __device__ __forceinline__ float ds_from_acc(float acc, float s_raw) {
     return s_raw == 0.0f ? 0.0f : -acc / (s_raw * s_raw);

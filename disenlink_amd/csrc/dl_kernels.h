@@ -82,9 +82,15 @@ size_t dense_score_workspace_bytes(int N, int K, int d);
 int dense_mfma_score_allpairs_fwd(const float* Z, const float* H, int N, int K, int d, float t, float* prob, void* ws, size_t ws_bytes,
                                   hipStream_t st);
 
+// ... and the logits of the same pairs: the kernel from planes without its sigmoid, every d (the planes pad it), ws required
+size_t dense_logits_workspace_bytes(int N, int K, int d);
+int dense_mfma_score_allpairs_logits_fwd(const float* Z, const float* H, int N, int K, int d, float t, float* logit, void* ws,
+                                         hipStream_t st);
+
 // dense backward of the dense scorer on the matrix cores (dl_score_dense_bwd.hip): fp32 tables, 1 <= d <= 128
 bool dense_bwd_supported(int d);
 size_t dense_bwd_workspace_bytes(int N, int K, int d);
+// (prob == NULL: g_prob is the gradient with respect to the logits)
 int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d, float t, const float* prob, const float* g_prob,
                              float* dZ, float* dH, void* ws, hipStream_t st);
 
@@ -108,10 +114,11 @@ void score_recon_form(int N, int K, int d, dl_dtype dt, int block_rows, int* out
 size_t score_recon_workspace_bytes(int N, int K, int d, dl_dtype dt, int block_rows);
 void score_recon_strip(const __bf16* cz, const __bf16* ch, dl_dtype dt, int N, int K, int d, float t, int q0, int rows,
                        const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* ig_rowptr, const int32_t* ig_col, float w_pos,
-                       float w_neg, float* ghat, float* lcell, unsigned* ccell, hipStream_t st);
+                       float w_neg, bool logit, float* ghat, float* lcell, unsigned* ccell, hipStream_t st);
+// logit: loss term and gradient per pair in logit space (dl_score_recon_logits); everything but the scan's epilogue is shared
 int score_recon(const void* Z, const void* H, int N, int K, int d, dl_dtype dt, float t, const int32_t* pos_rowptr,
                 const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg, int block_rows,
-                double* loss, int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st);
+                bool logit, double* loss, int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st);
 
 // ranking of all candidates of query rows on the matrix cores (dl_score_rank.hip): fp32 tables, 1 <= d <= 128
 bool score_rank_supported(int K, int d);

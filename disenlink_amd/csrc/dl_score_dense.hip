@@ -41,7 +41,8 @@ constexpr int SDC = SPLIT_COLS, SLD = SPLIT_PITCH;
 // that stages them (each node tile is staged by ~nt workgroups); the staging is then a straight copy.
 struct DensePlanes { const __bf16* z; const __bf16* h; size_t batch; };
 
-template <bool PLANES>
+// LOGIT: the pre-sigmoid sum is stored as it stands (dl_score_allpairs_logits_fwd); the stores and the mirror are the same.
+template <bool PLANES, bool LOGIT = false>
 __global__ __launch_bounds__(DTHR) void score_allpairs_split_kernel(const float* __restrict__ Z, const float* __restrict__ H,
                                                                     int N, int K, int D, float t, float* __restrict__ prob,
                                                                     DensePlanes P) {
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(DTHR) void score_allpairs_split_kernel(const float*
         const int v = v0 + wv * 64 + bb * 32 + li;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            term[bb][q] = sigmoid_ref(term[bb][q]);
+            if constexpr (!LOGIT) term[bb][q] = sigmoid_ref(term[bb][q]);
             const int u = u0 + wu * 32 + acc_row(q, half);
             if (u < N && v < N && (!diag || u <= v)) prob[(size_t)u * N + v] = term[bb][q];
         }
@@ -202,6 +203,28 @@ int dense_mfma_score_allpairs_fwd(const float* Z, const float* H, int N, int K, 
         launch_lds<score_allpairs_split_kernel<false>>(L.grid, DTHR, lds, st, Z, H, N, K, d, t, prob, DensePlanes{nullptr, nullptr, 0});
     }
     return check_launch("score_allpairs_fwd(split bf16)");
+}
+
+// The logits of the same pairs (dl_score_allpairs_logits_fwd): the kernel from planes with its sigmoid left out.  The planes pad
+// every factor to a multiple of 32 columns with zeros, so every d is served (the kernel is handed the padded width); the
+// workspace for them is therefore not optional.
+size_t dense_logits_workspace_bytes(int N, int K, int d) {
+    return 2 * sizeof(__bf16) * (size_t)K * project::plane_array_elems(N, d, project::SPLIT_COLS);
+}
+
+int dense_mfma_score_allpairs_logits_fwd(const float* Z, const float* H, int N, int K, int d, float t, float* logit, void* ws,
+                                         hipStream_t st) {
+    using namespace dense;
+    constexpr size_t lds = (size_t)2 * 2 * 3 * TT * SLD * 2;
+    const Launch L = launch_of(N, K, d, false, 0);
+    const size_t batch = project::plane_array_elems(N, d, project::SPLIT_COLS);
+    const int dp = (int)round_up(d, SDC);
+    __bf16* zp = static_cast<__bf16*>(ws);
+    __bf16* hp = zp + (size_t)K * batch;
+    project::split_rows(Z, K, N, d, K * d, (size_t)d, zp, st);
+    project::split_rows(H, K, N, d, K * d, (size_t)d, hp, st);
+    launch_lds<score_allpairs_split_kernel<true, true>>(L.grid, DTHR, lds, st, Z, H, N, K, dp, t, logit, DensePlanes{zp, hp, batch});
+    return check_launch("score_allpairs_logits_fwd");
 }
 
 }  // namespace dl

@@ -49,6 +49,8 @@ static_assert(lds_bytes(1) == sizeof(__bf16) * (size_t)2 * WIMG && 4 * (STAGE / 
 constexpr int KB = TT / 16;                    // K = 16 blocks of a v tile
 
 // ---- 1. G^ = G + G^T, G = g o p o (1 - p), zero-filled out to Np x Np ---------------------------------------------
+// LOGIT: g is d loss / d logit, so G = g as it stands and prob is not read (dl_score_allpairs_logits_bwd_dense).
+template <bool LOGIT = false>
 __global__ __launch_bounds__(256) void ghat_kernel(const float* __restrict__ prob, const float* __restrict__ g, int N, int Np,
                                                    float* __restrict__ ghat) {
     __shared__ float mir[64][65];
@@ -60,8 +62,12 @@ __global__ __launch_bounds__(256) void ghat_kernel(const float* __restrict__ pro
         float x = 0.0f;
         if (row < N && col < N) {
             const size_t o = (size_t)row * N + col;
-            const float p = prob[o];
-            x = g[o] * p * (1.0f - p);                          // sigmoid backward p(1-p)
+            if constexpr (LOGIT) {
+                x = g[o];
+            } else {
+                const float p = prob[o];
+                x = g[o] * p * (1.0f - p);                      // sigmoid backward p(1-p)
+            }
         }
         mir[r][tc] = x;
     }
@@ -72,8 +78,12 @@ __global__ __launch_bounds__(256) void ghat_kernel(const float* __restrict__ pro
         float x = 0.0f;
         if (row < N && col < N) {
             const size_t o = (size_t)row * N + col;
-            const float p = prob[o];
-            x = g[o] * p * (1.0f - p);
+            if constexpr (LOGIT) {
+                x = g[o];
+            } else {
+                const float p = prob[o];
+                x = g[o] * p * (1.0f - p);
+            }
         }
         ghat[(size_t)row * Np + col] = x + mir[tc][r];          // G[row][col] + G[col][row]: symmetric bit for bit
     }
@@ -461,6 +471,7 @@ void dense_bwd_combine(const float* part, int N, int K, int d, float* dZ, float*
         hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, st, part, n, nslice, dZ, dH);
 }
 
+// prob == NULL: g_prob is the gradient with respect to the LOGITS (dl_score_allpairs_logits_bwd_dense), G^ = g + g^T
 int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d, float t, const float* prob, const float* g_prob,
                              float* dZ, float* dH, void* ws, hipStream_t st) {
     using namespace dense_bwd;
@@ -470,7 +481,9 @@ int dense_bwd_score_allpairs(const float* Z, const float* H, int N, int K, int d
     __bf16 *zp = (__bf16*)(base + L.zp), *hp = (__bf16*)(base + L.hp), *zT = (__bf16*)(base + L.zT), *hT = (__bf16*)(base + L.hT);
     float* part = (float*)(base + L.part);
 
-    hipLaunchKernelGGL(ghat_kernel, dim3((unsigned)(L.Np / 64), (unsigned)(L.Np / 64)), dim3(256), 0, st, prob, g_prob, N, L.Np, ghat);
+    const dim3 ggrid((unsigned)(L.Np / 64), (unsigned)(L.Np / 64));
+    if (prob == nullptr) hipLaunchKernelGGL(ghat_kernel<true>, ggrid, dim3(256), 0, st, prob, g_prob, N, L.Np, ghat);
+    else hipLaunchKernelGGL(ghat_kernel<false>, ggrid, dim3(256), 0, st, prob, g_prob, N, L.Np, ghat);
     project::split_rows(Z, K, N, d, K * d, (size_t)d, zp, st);
     project::split_rows(H, K, N, d, K * d, (size_t)d, hp, st);
     dense_bwd_cols(Z, H, N, K, d, zT, hT, st);

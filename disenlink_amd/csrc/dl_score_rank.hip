@@ -194,7 +194,10 @@ __device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, 
 // (lg: RLG floats of the wave's own, pitch 65: the transposed read below is conflict-free); the loss terms come back the
 // same way and the 128 terms of a row are added in one fixed order — 16 consecutive columns by one lane, the two halves of a
 // 32-column block, the two blocks of a wave, the two waves — so a cell is a function of its logits alone.  Counts: ballots.
+// LOGIT (dl_score_recon_logits): per value the term w l(s, y) of BCE-with-logits (bce_logits_term) and g = w (sigmoid(s) - y)
+// without a clamp (sigmoid_minus_label), both of dl_common.h; masks, stores, sums and counts are the same text.
 static_assert(4 * RLG * 4 <= 3 * TT * SLD * 2, "four waves' terms fit a three-plane image");
+template <bool LOGIT>
 __device__ __forceinline__ void recon_epilogue(const ReconArgs& A, const f32x16 (&term)[2], float* lg, unsigned* pom, unsigned* scr,
                                                int* pocur, int* igcur, const int* rnode, int qt, int ct, int nt, int tid) {
     unsigned* igm = scr;                                        // [TT][4]: ignored columns of the tile, the diagonal among them
@@ -228,11 +231,18 @@ __device__ __forceinline__ void recon_epilogue(const ReconArgs& A, const f32x16 
             const int row = wu * 32 + acc_row(q, half);
             const bool live = inside && rnode[row] >= 0 && !((igm[row * 4 + w] >> li) & 1u);
             const bool pos = (pom[row * 4 + w] >> li) & 1u;
-            const float p = sigmoid_ref(lg[q * RPITCH + lane]);
-            const float lgp = logf(pos ? p : 1.0f - p);         // F.binary_cross_entropy: the log clamped at -100 (dl_pair_bce)
-            const float ww = pos ? A.w_pos : A.w_neg, r = p * (1.0f - p);
-            const float bce = ww * -(lgp < -100.0f ? -100.0f : lgp);
-            const float gl = ww * (p - (pos ? 1.0f : 0.0f)) * (r >= 1e-12f ? 1.0f : r * 1e12f);
+            float bce, gl;
+            if constexpr (LOGIT) {                              // logit space: the pair objective's term and gradient, no clamp
+                const float x = lg[q * RPITCH + lane], y = pos ? 1.0f : 0.0f, ww = pos ? A.w_pos : A.w_neg;
+                bce = ww * bce_logits_term(x, y);
+                gl = ww * sigmoid_minus_label(x, y);
+            } else {
+                const float p = sigmoid_ref(lg[q * RPITCH + lane]);
+                const float lgp = logf(pos ? p : 1.0f - p);     // F.binary_cross_entropy: the log clamped at -100 (dl_pair_bce)
+                const float ww = pos ? A.w_pos : A.w_neg, r = p * (1.0f - p);
+                bce = ww * -(lgp < -100.0f ? -100.0f : lgp);
+                gl = ww * (p - (pos ? 1.0f : 0.0f)) * (r >= 1e-12f ? 1.0f : r * 1e12f);
+            }
             A.ghat[((size_t)qt * TT + row) * Np + v0 + w * 32 + li] = live ? gl : 0.0f;
             lg[q * RPITCH + lane] = live ? bce : 0.0f;
             const u64 mp = __ballot(live && pos), mn = __ballot(live && !pos);
@@ -268,8 +278,10 @@ __device__ __forceinline__ void recon_epilogue(const ReconArgs& A, const f32x16 
 // into it where the unfiltered kernel starts from zero.  The epilogue is the unfiltered one.
 // P: planes per operand, 3 (fp32 tables) or 1 (bf16 tables: one bf16x8 and one MFMA per operand and block, gram_block<1>); the
 // step keeps its 32 columns, so the k-blocks of a product are added in the same ascending order in both.
-template <int MODE, bool FILT = false, int P = 3>
+// LOGIT (RECON only): the loss term and the gradient of the epilogue in logit space (dl_score_recon_logits).
+template <int MODE, bool FILT = false, int P = 3, bool LOGIT = false>
 __global__ __launch_bounds__(RTHR) void rank_scan_kernel(typename ModeArgs<MODE>::type A) {
+    static_assert(!LOGIT || MODE == RECON, "only the reconstruction epilogue has a logit-space form");
     static_assert(!(FILT && (MODE == DIAG || MODE == TERMS)), "the target passes have no mask");
     constexpr bool PAIRS = MODE == DIAG || MODE == TERMS;      // TERMS: DIAG's geometry and gathers, other stores
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -455,7 +467,7 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(typename ModeArgs<MODE>
         } else if constexpr (MODE == RECON) {
             float* lg = P == 3 ? reinterpret_cast<float*>((wave < 4 ? us : vs) + (s & 1) * 3 * TT * SLD) + (wave & 3) * (3 * TT * SLD / 8)
                                : lgs + wave * RLG;              // one plane: the wave's own RLG floats behind the images
-            recon_epilogue(A, term, lg, exm, reinterpret_cast<unsigned*>(scr), excur, cnt, rnode, qt, ct0 + s / per_tile, nt, tid);
+            recon_epilogue<LOGIT>(A, term, lg, exm, reinterpret_cast<unsigned*>(scr), excur, cnt, rnode, qt, ct0 + s / per_tile, nt, tid);
         } else {
             if (tid < TT) {                                     // this tile's excluded columns of row tid
                 const int node = rnode[tid];
@@ -841,7 +853,7 @@ int score_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, 
 // dt: the planes are three per operand (DL_F32, split_rows) or the one of a bf16 table (DL_BF16, copy_rows): the P = 1 form.
 void score_recon_strip(const __bf16* cz, const __bf16* ch, dl_dtype dt, int N, int K, int d, float t, int q0, int rows,
                        const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* ig_rowptr, const int32_t* ig_col, float w_pos,
-                       float w_neg, float* ghat, float* lcell, unsigned* ccell, hipStream_t st) {
+                       float w_neg, bool logit, float* ghat, float* lcell, unsigned* ccell, hipStream_t st) {
     const RankPlan p = rank_plan(N, d, rows, 0, dt);
     ReconArgs a = {};
     const size_t first = dt == DL_BF16 ? plane_tile<SDC, 1>(q0 / TT, 0, p.nd) : plane_tile<SDC, 3>(q0 / TT, 0, p.nd);
@@ -855,7 +867,10 @@ void score_recon_strip(const __bf16* cz, const __bf16* ch, dl_dtype dt, int N, i
     a.w_pos = w_pos; a.w_neg = w_neg;
     a.ghat = ghat; a.lcell = lcell; a.ccell = ccell;
     const unsigned grid = (unsigned)xcd_grid(p.qtiles, p.slices);
-    if (dt == DL_BF16) launch_lds<rank_scan_kernel<RECON, false, 1>>(grid, RTHR, lds_bytes(1, true), st, a);
+    if (logit) {                                               // the same LDS: the epilogue keeps nothing more there
+        if (dt == DL_BF16) launch_lds<rank_scan_kernel<RECON, false, 1, true>>(grid, RTHR, lds_bytes(1, true), st, a);
+        else launch_lds<rank_scan_kernel<RECON, false, 3, true>>(grid, RTHR, lds_bytes(3), st, a);
+    } else if (dt == DL_BF16) launch_lds<rank_scan_kernel<RECON, false, 1>>(grid, RTHR, lds_bytes(1, true), st, a);
     else launch_lds<rank_scan_kernel<RECON>>(grid, RTHR, lds_bytes(3), st, a);
 }
 

@@ -30,6 +30,25 @@ def score_allpairs_fwd(Z, H, t: float) -> torch.Tensor:
     return prob
 
 
+def score_allpairs_logits_fwd(Z, H, t: float) -> torch.Tensor:
+    """-> logit f32[N,N] for all ordered pairs: model.py:109-113 without its sigmoid (dl_score_allpairs_logits_fwd), the
+    tensor ``F.binary_cross_entropy_with_logits`` is written on.  fp32 tables, every d (the matrix-core kernel from planes,
+    which pad d to a multiple of 32); symmetric bit for bit.  bf16 tables raise: there is no fallback."""
+    lib = _lib.load()
+    if Z.dtype != torch.float32 or H.dtype != torch.float32:
+        raise TypeError(f"the dense logits take fp32 tables, got {Z.dtype} / {H.dtype}")
+    _need_cuda(Z, H)
+    Z, H = Z.contiguous(), H.contiguous()
+    N, K, d = _nkd(Z)
+    if H.shape != Z.shape:
+        raise ValueError("Z and H differ in shape")
+    logit = _empty((N, N), torch.float32, Z.device)
+    ws = _ws.get(max(256, int(lib.dl_score_allpairs_logits_workspace_bytes(N, K, d))), Z.device)
+    _lib.check(lib.dl_score_allpairs_logits_fwd(Z.data_ptr(), H.data_ptr(), N, K, d, _lib.DL_F32, float(t), logit.data_ptr(),
+                                                ws.data_ptr(), ws.numel(), _stream()), "dl_score_allpairs_logits_fwd")
+    return logit
+
+
 def score_allpairs_bwd(Z, H, pairs: PairList, t: float, prob, g_prob):
     """-> dZ, dH f32[N,K,d]: backward of score_allpairs_fwd on the fixed pair plan ``pairs`` (the support of the
     caller's loss masks); prob and g_prob are the dense [N,N] arrays."""
@@ -60,24 +79,47 @@ def score_allpairs_bwd_dense(Z, H, t: float, prob, g_prob):
     symmetric, possibly expanded or transposed: it is made contiguous fp32 here) on the matrix cores
     (dl_score_dense_bwd.hip) — no pair plan, no host read.  ``prob`` is the forward's output.  Every element of dZ and dH
     is written."""
+    return _bwd_dense(Z, H, t, prob, g_prob)
+
+
+def score_allpairs_logits_bwd_dense(Z, H, t: float, g_logit):
+    """-> dZ, dH f32[N,K,d]: backward of score_allpairs_logits_fwd for ANY dense gradient ``g_logit`` [N,N] with respect to
+    the logits (dl_score_allpairs_logits_bwd_dense): G^ = g + g^T with no p (1 - p) factor and no saved forward output;
+    everything else, limits included, is ``score_allpairs_bwd_dense``."""
+    return _bwd_dense(Z, H, t, None, g_logit)
+
+
+def _bwd_dense(Z, H, t, prob, g):
+    """The dense backward of either score space; ``prob`` None: ``g`` is the gradient with respect to the logits."""
     lib = _lib.load()
-    Z, H, prob = _f32c(Z), _f32c(H), _f32c(prob)
-    _need_cuda(Z, H, prob, g_prob)
+    logits = prob is None
+    Z, H = _f32c(Z), _f32c(H)
+    if not logits:
+        prob = _f32c(prob)
+    _need_cuda(Z, H, g, *(() if logits else (prob,)))
     N, K, d = _nkd(Z)
     if H.shape != Z.shape:
         raise ValueError("Z and H differ in shape")
-    if tuple(prob.shape) != (N, N) or tuple(g_prob.shape) != (N, N):
+    if logits:
+        if tuple(g.shape) != (N, N):
+            raise ValueError("g_logit must be the dense [N, N] array")
+    elif tuple(prob.shape) != (N, N) or tuple(g.shape) != (N, N):
         raise ValueError("prob / g_prob must be the dense [N, N] arrays")
     if not lib.dl_score_allpairs_bwd_dense_supported(K, d):
         raise _lib.DisenlinkHipError(f"the dense backward of link_pred serves fp32 tables with 1 <= d <= 128 (got K = {K}, "
                                      f"d = {d}); there is no eager fallback")
-    g_prob = g_prob.to(torch.float32).contiguous()              # stride-0 (mean()) and transposed gradients arrive here
+    g = g.to(torch.float32).contiguous()                        # stride-0 (mean()) and transposed gradients arrive here
     dZ = _empty(Z.shape, torch.float32, Z.device)
     dH = _empty(Z.shape, torch.float32, Z.device)
     ws = _ws.get(int(lib.dl_score_allpairs_bwd_dense_workspace_bytes(N, K, d)), Z.device)
-    _lib.check(lib.dl_score_allpairs_bwd_dense(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), prob.data_ptr(),
-                                               g_prob.data_ptr(), dZ.data_ptr(), dH.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               _stream()), "dl_score_allpairs_bwd_dense")
+    if logits:
+        _lib.check(lib.dl_score_allpairs_logits_bwd_dense(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), g.data_ptr(),
+                                                          dZ.data_ptr(), dH.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "dl_score_allpairs_logits_bwd_dense")
+    else:
+        _lib.check(lib.dl_score_allpairs_bwd_dense(Z.data_ptr(), H.data_ptr(), N, K, d, float(t), prob.data_ptr(),
+                                                   g.data_ptr(), dZ.data_ptr(), dH.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   _stream()), "dl_score_allpairs_bwd_dense")
     return dZ, dH
 
 
@@ -308,4 +350,29 @@ class ScoreAllPairsDense(torch.autograd.Function):
     def backward(ctx, g_prob):
         Z, H, prob = ctx.saved_tensors
         dZ, dH = score_allpairs_bwd_dense(Z, H, ctx.t, prob, g_prob)
+        return dZ, dH, None
+
+
+class ScoreAllPairsLogits(torch.autograd.Function):
+    """(Z, H) -> logit [N,N] (score_allpairs_logits_fwd), a plain tensor for ``F.binary_cross_entropy_with_logits``; the
+    backward is the dense one (score_allpairs_logits_bwd_dense) and the only one: there is no pair plan in logit space.
+    Shapes the dense backward does not serve (d > 128) and non-fp32 tables raise in the forward."""
+
+    @staticmethod
+    def forward(ctx, Z, H, t: float):
+        if Z.dtype != torch.float32 or H.dtype != torch.float32:
+            raise TypeError(f"link_logits takes fp32 tables, got {Z.dtype} / {H.dtype}")
+        N, K, d = _nkd(Z)
+        if not score_allpairs_bwd_dense_supported(K, d):
+            raise _lib.DisenlinkHipError(f"link_logits serves fp32 tables with 1 <= d <= 128, the shapes of its dense backward "
+                                         f"(got K = {K}, d = {d}); there is no eager fallback")
+        Z, H = Z.contiguous(), H.contiguous()
+        ctx.t = t
+        ctx.save_for_backward(Z, H)
+        return score_allpairs_logits_fwd(Z, H, t)
+
+    @staticmethod
+    def backward(ctx, g_logit):
+        Z, H = ctx.saved_tensors
+        dZ, dH = score_allpairs_logits_bwd_dense(Z, H, ctx.t, g_logit)
         return dZ, dH, None

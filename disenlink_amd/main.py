@@ -48,17 +48,20 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--data-file", type=str, default=None, help="binary dataset written by datasets.save_binary")
     p.add_argument("--synthetic", action="store_true", help="seeded synthetic stand-in of --dataset")
     p.add_argument("--table-dtype", choices=["f32", "bf16"], default="f32")
-    p.add_argument("--objective", choices=["pairs", "pairs-logit", "recon"], default="pairs",
+    p.add_argument("--objective", choices=["pairs", "pairs-logit", "recon", "recon-logit"], default="pairs",
                    help="the training loss: pairs = the reference's BCE on m sampled negatives per edge; pairs-logit = the same "
                         "pairs with the BCE taken of the LOGITS (a saturated pair keeps its gradient, and the validation / test "
                         "AUC is counted on logits, which do not tie at probability 1; one GPU); recon = the "
                         "whole-graph reconstruction loss, every non-edge a negative and the edges up-weighted, with the "
                         "validation and test pairs ignored (Disentangle.forward_recon_loss: nothing of size N x N is formed; "
-                        "one GPU, eager loop; with --table-dtype bf16 it runs on the bf16 tables the model is evaluated on)")
+                        "one GPU, eager loop; with --table-dtype bf16 it runs on the bf16 tables the model is evaluated on); "
+                        "recon-logit = recon with the loss taken of the LOGITS (Disentangle.forward_recon_logits_loss: a non-edge "
+                        "the model scores past the saturation of the fp32 sigmoid keeps its cost and its gradient; AUC counted "
+                        "on logits; --pos-weight, --recon-block-rows and --table-dtype apply as for recon)")
     p.add_argument("--pos-weight", type=float, default=None,
-                   help="with --objective recon: the weight of a positive pair (default: negatives / positives)")
+                   help="with --objective recon / recon-logit: the weight of a positive pair (default: negatives / positives)")
     p.add_argument("--recon-block-rows", type=int, default=None,
-                   help="with --objective recon: rows per strip, a multiple of 128 (default: the largest strip of at most 1 GiB)")
+                   help="with --objective recon / recon-logit: rows per strip, a multiple of 128 (default: the largest strip of at most 1 GiB)")
     p.add_argument("--no-graph", action="store_true",
                    help="launch every epoch from Python instead of replaying it from a captured HIP graph")
     p.add_argument("--graph", action="store_true",
@@ -415,7 +418,7 @@ def main(argv=None):
                                args.predict_top is not None):
         raise SystemExit("--link-rule restricts the candidates of --rank-eval, --global-rank-eval, --mine and --predict-links: "
                          "give one of them")
-    if args.objective == "recon" and (args.gpus > 1 or args.graph):
+    if args.objective in ("recon", "recon-logit") and (args.gpus > 1 or args.graph):
         raise SystemExit("--objective recon runs on one GPU in the eager loop only, with fp32 or bf16 tables (sharded and "
                          "graph-replayed reconstruction epochs are not implemented): drop --gpus / --graph")
     if args.objective == "pairs-logit" and args.gpus > 1:
@@ -469,7 +472,7 @@ def main(argv=None):
                             t=args.temperature, table_dtype=tdt).to(device)
         res = run_link_prediction(model, x, prepared, epochs=args.epochs, lr=args.lr,
                                   log=None if args.quiet else print,
-                                  use_graph=_use_graph(args) and args.objective != "recon", objective=args.objective,
+                                  use_graph=_use_graph(args) and args.objective not in ("recon", "recon-logit"), objective=args.objective,
                                   pos_weight=args.pos_weight, recon_block_rows=args.recon_block_rows)
         if not args.quiet:
             print("test auc:", res.test_auc)

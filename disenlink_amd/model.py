@@ -376,6 +376,21 @@ class Disentangle(nn.Module):
         # (a Tensor whose indexing reports the entries taken to this module's pair-plan cache: ops.LinkPred)
         return H.view(H.shape[0], -1), ops.as_link_pred(link_pred, self._dense_plan)
 
+    def forward_logits(self, x, adj):
+        """(emb [N,K*d], link_logits [N,N]): ``forward`` with the dense scores left in LOGIT space — a plain tensor, for
+        ``F.binary_cross_entropy_with_logits(link_logits[mask], ...)`` or any other loss; ``emb`` has ``forward``'s bits.  Its
+        backward is the dense one (ops.ScoreAllPairsLogits: the gradient of whatever is done with it, no declaration of
+        where the loss is taken), so it raises where that does not serve — d > 128, non-fp32 tables — as
+        ``link_pred_backward="dense"`` does.  ``forward`` itself is untouched."""
+        if not (self.table_dtype == torch.float32 and ops.score_allpairs_bwd_dense_supported(self.nfactor, self.nebed)):
+            raise ops._lib.DisenlinkHipError(
+                f"forward_logits serves fp32 tables and factor widths d <= 128 (got {self.table_dtype}, d = {self.nebed}); "
+                f"there is no eager fallback")
+        graph = self._graph_of(adj)
+        Z = self.project(x)
+        H = ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
+        return H.view(H.shape[0], -1), ops.ScoreAllPairsLogits.apply(Z, H, float(self.temperature))
+
     def forward_pairs_loss(self, x, graph: Graph, pairs: PairList, label, weight):
         """(emb [N,K*d], prob [P], loss) with loss = sum_q weight BCE(prob, label) (main_disentangled.py:195 on a pair
         list; metrics.pair_bce_weights): the training step's scorer runs forward and backward in one pass
@@ -436,14 +451,25 @@ class Disentangle(nn.Module):
         positives.  ``ignore`` may be a prepared ``ops.recon_sets(graph, ignore, N, device)``, which then supplies both
         sets and skips the normalisation (and its host read) per call.  No tile is skipped: a zero gradient against an
         overflowed exp gives NaN, as with ``link_pred_backward="dense"``.  d <= 128; anything else raises."""
+        return self._forward_recon(x, graph, ignore, pos_weight, block_rows, ops.ReconLoss, ops.HotPathRecon)
+
+    def forward_recon_logits_loss(self, x, graph: Graph, ignore=None, pos_weight=None, block_rows=None):
+        """(emb [N,K*d], loss): ``forward_recon_loss`` in LOGIT space (ops.score_recon_logits_loss), with its arguments and its
+        dispatch — fp32: RouteAggregate + ops.ReconLogitsLoss, bf16: ops.HotPathReconLogits.  A pair past the saturation of
+        the fp32 sigmoid keeps its cost and its gradient (a non-edge scored at +20 is pushed back; the probability form
+        charges it 100 w with gradient exactly 0); an overflowed exp is NOT cured: loss and gradients are then non-finite.
+        The device counts stand in ``ops.ReconLogitsLoss.last_counts``."""
+        return self._forward_recon(x, graph, ignore, pos_weight, block_rows, ops.ReconLogitsLoss, ops.HotPathReconLogits)
+
+    def _forward_recon(self, x, graph, ignore, pos_weight, block_rows, loss_node, hot_node):
         Z = self.project(x)
         sets = ignore if isinstance(ignore, ops.ReconSets) else ops.recon_sets(graph, ignore, Z.shape[0], Z.device)
         if self.table_dtype == torch.bfloat16:
-            H, loss = ops.HotPathRecon.apply(Z, graph, sets, float(self.beta), float(self.temperature), self.table_dtype,
-                                             pos_weight, block_rows)
+            H, loss = hot_node.apply(Z, graph, sets, float(self.beta), float(self.temperature), self.table_dtype,
+                                     pos_weight, block_rows)
             return H.view(H.shape[0], -1), loss
         H = ops.RouteAggregate.apply(Z, graph, float(self.beta), float(self.temperature))
-        loss = ops.ReconLoss.apply(Z, H, float(self.temperature), sets, pos_weight, block_rows)
+        loss = loss_node.apply(Z, H, float(self.temperature), sets, pos_weight, block_rows)
         return H.view(H.shape[0], -1), loss
 
     def forward_pairs(self, x, graph: Graph, pairs: PairList):

@@ -17,13 +17,15 @@ from ._dev import (                                                     # noqa: 
     _POISON, _Workspace, _empty, _empty_like, _f32c, _need_cuda, _nkd, _stream, _tab, _ws, table_code)
 from .graph import Graph, PairList
 from .link_pred import (                                                # noqa: F401  (the dense link_pred: ops.* as before)
-    DensePairPlanCache, LinkPred, ScoreAllPairs, ScoreAllPairsDense, as_link_pred, score_allpairs_bwd, score_allpairs_bwd_dense,
-    score_allpairs_bwd_dense_supported, score_allpairs_fwd)
+    DensePairPlanCache, LinkPred, ScoreAllPairs, ScoreAllPairsDense, ScoreAllPairsLogits, as_link_pred, score_allpairs_bwd,
+    score_allpairs_bwd_dense, score_allpairs_bwd_dense_supported, score_allpairs_fwd, score_allpairs_logits_bwd_dense,
+    score_allpairs_logits_fwd)
 from .project import (                                                  # noqa: F401  (the projection: ops.project_* as before)
     Project, _pad_features, _XPlanes, keep_hidden, padded_features, project_bwd, project_fwd, project_sparse_bwd,
     project_sparse_fwd, project_supported, project_tile_width, xplanes_for)
 from .recon import (                                                    # noqa: F401  (the whole-graph reconstruction loss)
-    ReconLoss, ReconSets, check_recon_counts, recon_sets, recon_weights, score_recon_loss)
+    ReconLogitsLoss, ReconLoss, ReconSets, check_recon_counts, recon_sets, recon_weights, score_recon_logits_loss,
+    score_recon_loss)
 from .scans import (                                                    # noqa: F401  (the all-pairs scans: ops.score_* as before)
     BETWEEN_MAX_N, BLOCK_NODES, BLOCKS_MAX_N, LINKS_MAX_N, MINE_MAX_M, MINE_MAX_N, RANK_MAX_K, LinksBetween, NodeFilter,
     PairExclusion, PairTerms, bipartite_exclusion_csr, exclusion_csr, pair_exclusion, score_link_degrees,
@@ -526,15 +528,16 @@ class HotPathRecon(torch.autograd.Function):
     gradients of the loss with respect to both tables ready when the forward returns.  The backward scales them by the
     incoming d/dloss, adds a gradient arriving on ``emb`` to dH and continues into aggregation and routing.  ``sets``: a
     prepared ``recon_sets(...)``; the device counts stand in ``ReconLoss.last_counts``."""
+    _loss, _counts = staticmethod(score_recon_loss), ReconLoss
 
-    @staticmethod
-    def forward(ctx, Z, graph: Graph, sets: ReconSets, beta: float, t: float, table_dtype, pos_weight=None, block_rows=None):
+    @classmethod
+    def forward(cls, ctx, Z, graph: Graph, sets: ReconSets, beta: float, t: float, table_dtype, pos_weight=None, block_rows=None):
         ctx.set_materialize_grads(False)
         Zt, p, a, s, H = step_tables(graph, Z, beta, t, table_dtype)
-        loss, dZs, dHs, counts = score_recon_loss(Zt, H, t, sets, None, pos_weight, block_rows, table_dtype=table_dtype)
+        loss, dZs, dHs, counts = cls._loss(Zt, H, t, sets, None, pos_weight, block_rows, table_dtype=table_dtype)
         ctx.graph, ctx.beta, ctx.t, ctx.p = graph, beta, t, p
         ctx.save_for_backward(Zt, a, s, dZs, dHs)
-        ReconLoss.last_counts = counts
+        cls._counts.last_counts = counts
         return H.float(), loss.to(torch.float32)
 
     @staticmethod
@@ -546,6 +549,12 @@ class HotPathRecon(torch.autograd.Function):
             dZ, dH = torch.zeros_like(dZs), torch.zeros_like(dHs)
         _step_backward_tail(ctx, Zt, a, s, dZ, dH, g_emb)
         return dZ, None, None, None, None, None, None, None
+
+
+class HotPathReconLogits(HotPathRecon):
+    """``HotPathRecon`` with the loss in logit space (``score_recon_logits_loss``): the same single node; the device counts
+    stand in ``ReconLogitsLoss.last_counts``."""
+    _loss, _counts = staticmethod(score_recon_logits_loss), ReconLogitsLoss
 
 
 class ScorePairs(torch.autograd.Function):

@@ -14,6 +14,11 @@ bf16 tables (``table_dtype=torch.bfloat16``, the scans' keyword and convention):
 plane, so scan and backward issue 10 matrix-core products per (tile pair, factor, K block) instead of 36 and the workspace
 is 16 K Np dp bytes smaller (dl_score_recon_dtype with DL_BF16).  Every finite output has the bits of the fp32 call on the
 same tables widened to fp32; gradients are fp32, with respect to the rounded tables.
+
+Logit space (``score_recon_logits_loss``, ``ReconLogitsLoss``; dl_score_recon_logits, restated by tests/recon_logits_ref.py):
+the same pairs, labels and weights with loss = sum w (max(s, 0) - s y + log1p(exp(-|s|))) and d loss / d s =
+w (sigmoid(s) - y), neither clamped: what the fp32 sigmoid saturates (s > 16.64; p (1 - p) < 1e-12 below -27.6) keeps its
+cost and its gradient.  The probability and logit forms share every body here through a private flag.
 """
 from __future__ import annotations
 
@@ -134,13 +139,27 @@ def score_recon_loss(Z, H, t: float, positives, ignore=None, pos_weight=None, bl
     tables, and dZ / dH (fp32) with respect to the rounded tables.  No float atomics, no host read and no synchronisation in
     the call; launches follow the current stream; the same bits on every call, for every ``block_rows`` and every
     DL_RANK_SLICES."""
+    return _score_recon(Z, H, t, positives, ignore, pos_weight, block_rows, table_dtype, False)
+
+
+def score_recon_logits_loss(Z, H, t: float, positives, ignore=None, pos_weight=None, block_rows=None, table_dtype=torch.float32):
+    """``score_recon_loss`` in LOGIT space (dl_score_recon_logits): the same sets, weights, strips, outputs and guarantees,
+    with loss = sum w l(s, y), l = max(s, 0) - s y + log1p(exp(-|s|)) (``F.binary_cross_entropy_with_logits``) and
+    d loss / d s = w (sigmoid(s) - y) without a clamp: a pair past the saturation of the fp32 sigmoid (s > 16.64, or
+    s < -27.6 on a positive) keeps its cost and its gradient, where the probability form charges 100 w and returns exactly 0.
+    Logit space does not cure an overflowed exp(z.z / t): a non-finite logit gives a non-finite loss and gradients."""
+    return _score_recon(Z, H, t, positives, ignore, pos_weight, block_rows, table_dtype, True)
+
+
+def _score_recon(Z, H, t, positives, ignore, pos_weight, block_rows, table_dtype, logits):
     Z, H, N, K, d, dt = _recon_tables(Z, H, table_dtype)
     sets = _sets_arg(positives, ignore, N, Z.device)
-    return _recon_call(Z, H, N, K, d, float(t), sets, recon_weights(sets, pos_weight), _block_rows(block_rows), dt)
+    return _recon_call(Z, H, N, K, d, float(t), sets, recon_weights(sets, pos_weight), _block_rows(block_rows), dt, logits)
 
 
-def _recon_call(Z, H, N, K, d, t, sets, weights, block_rows, dt=_lib.DL_F32):
+def _recon_call(Z, H, N, K, d, t, sets, weights, block_rows, dt=_lib.DL_F32, logits=False):
     lib = _lib.load()
+    entry = "dl_score_recon_logits" if logits else "dl_score_recon_dtype"     # one argument list, one workspace
     dev = Z.device
     loss = _empty((1,), torch.float64, dev)
     counts = _empty((2,), torch.int64, dev)
@@ -148,9 +167,9 @@ def _recon_call(Z, H, N, K, d, t, sets, weights, block_rows, dt=_lib.DL_F32):
     pr, pc, keep_p = _csr_args(sets.pos_rowptr, sets.pos_col, dev)
     ir, ic, keep_i = _csr_args(sets.ign_rowptr, sets.ign_col, dev)
     ws = _ws.get(max(256, int(lib.dl_score_recon_workspace_bytes_dtype(N, K, d, dt, block_rows))), dev)
-    _lib.check(lib.dl_score_recon_dtype(Z.data_ptr(), H.data_ptr(), N, K, d, dt, t, pr, pc, ir, ic, weights[0], weights[1],
-                                        block_rows, loss.data_ptr(), counts.data_ptr(), dZ.data_ptr(), dH.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), _stream()), "dl_score_recon_dtype")
+    _lib.check(getattr(lib, entry)(Z.data_ptr(), H.data_ptr(), N, K, d, dt, t, pr, pc, ir, ic, weights[0], weights[1],
+                                   block_rows, loss.data_ptr(), counts.data_ptr(), dZ.data_ptr(), dH.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), _stream()), entry)
     del keep_p, keep_i
     return loss.reshape(()), dZ, dH, counts
 
@@ -170,18 +189,26 @@ class ReconLoss(torch.autograd.Function):
     ``score_recon_loss`` takes them; the rounding passes the gradient straight through (as ``ops.HotPathPairs``).  The device
     counts of the last forward stand in ``ReconLoss.last_counts`` for ``check_recon_counts``."""
     last_counts = None
+    _logits = False
 
-    @staticmethod
-    def forward(ctx, Z, H, t: float, sets: ReconSets, pos_weight=None, block_rows=None, table_dtype=torch.float32):
+    @classmethod
+    def forward(cls, ctx, Z, H, t: float, sets: ReconSets, pos_weight=None, block_rows=None, table_dtype=torch.float32):
         Z, H, N, K, d, dt = _recon_tables(Z, H, table_dtype)
         sets = _sets_arg(sets, None, N, Z.device)
         loss, dZ, dH, counts = _recon_call(Z, H, N, K, d, float(t), sets, recon_weights(sets, pos_weight), _block_rows(block_rows),
-                                           dt)
+                                           dt, cls._logits)
         ctx.save_for_backward(dZ, dH)
-        ReconLoss.last_counts = counts
+        cls.last_counts = counts
         return loss.to(torch.float32)
 
     @staticmethod
     def backward(ctx, g):
         dZ, dH = ctx.saved_tensors
         return dZ * g, dH * g, None, None, None, None, None
+
+
+class ReconLogitsLoss(ReconLoss):
+    """``ReconLoss`` over ``score_recon_logits_loss``: the same node, the logit-space entry; its device counts stand in
+    ``ReconLogitsLoss.last_counts``."""
+    last_counts = None
+    _logits = True

@@ -201,19 +201,28 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     eager, device early stop and HIP-graph replay alike) — or "recon" — the whole-graph
     reconstruction loss (``model.forward_recon_loss``: every non-edge of the training graph a negative, positives weighted
     by ``pos_weight``, default n_neg / n_pos, all validation and test pairs ignored, by strips of ``recon_block_rows``
-    rows), in the eager loop with the bookkeeping on the host; validation and test AUC as ever."""
-    if objective not in ("pairs", "pairs-logit", "recon"):
-        raise ValueError(f"objective must be \"pairs\", \"pairs-logit\" or \"recon\", got {objective!r}")
+    rows), in the eager loop with the bookkeeping on the host; validation and test AUC as ever — or "recon-logit": the same
+    loop on ``model.forward_recon_logits_loss`` (the reconstruction loss in logit space: a saturated pair keeps its cost and
+    its gradient), validation and test AUC counted on ``model.forward_pair_logits``; GPU only, refusals as for "recon"."""
+    if objective not in ("pairs", "pairs-logit", "recon", "recon-logit"):
+        raise ValueError(f"objective must be \"pairs\", \"pairs-logit\", \"recon\" or \"recon-logit\", got {objective!r}")
     logit = objective == "pairs-logit"
     if logit:
         _check_logit_run(model, run)
         if not x.is_cuda:
             raise ValueError("objective=\"pairs-logit\" runs on the GPU only (there is no CPU form of the logit-space step)")
-    if objective == "recon":
+    if objective in ("recon", "recon-logit"):
+        if objective == "recon-logit":                               # refused before the first launch, as "pairs-logit" is
+            if not hasattr(model, "forward_recon_logits_loss") or not hasattr(model, "forward_pair_logits"):
+                raise TypeError("objective=\"recon-logit\" needs a model with forward_recon_logits_loss and forward_pair_logits "
+                                "(disenlink_amd.model.Disentangle)")
         if use_graph:
-            raise ValueError("objective=\"recon\" runs in the eager loop only (HIP-graph replay of the reconstruction epoch "
-                             "is not implemented): pass use_graph=False")
-        return _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, recon_block_rows)
+            raise ValueError(f"objective=\"{objective}\" runs in the eager loop only (HIP-graph replay of the reconstruction "
+                             "epoch is not implemented): pass use_graph=False")
+        if objective == "recon-logit" and not x.is_cuda:
+            raise ValueError("objective=\"recon-logit\" runs on the GPU only (there is no CPU form of the reconstruction loss)")
+        return _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, recon_block_rows,
+                          objective == "recon-logit")
     if use_graph and x.is_cuda:
         return _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log, logit)
     # same update rule as the reference's Adam (main_disentangled.py:150); on the GPU torch's single-kernel
@@ -285,12 +294,16 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     return res
 
 
-def _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, block_rows) -> RunResult:
+def _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, block_rows, logit: bool = False) -> RunResult:
     """run_link_prediction's eager loop with the reconstruction loss: the loss of ``model.forward_recon_loss`` over the
     training graph with every validation and test pair ignored; the validation AUC from ``forward_pairs`` under no_grad on
     the weights before the step (:202-204); one host read per epoch, which also carries the device's counts of the pairs
-    the scan saw — compared with the host's, a mismatch raises."""
+    the scan saw — compared with the host's, a mismatch raises.  ``logit``: the loss of ``forward_recon_logits_loss`` and the
+    AUCs on ``forward_pair_logits`` (AucPlan / auc_tie_avg take any score; logits do not tie at probability 1)."""
     from . import ops
+    recon_loss = model.forward_recon_logits_loss if logit else model.forward_recon_loss
+    pair_scores = model.forward_pair_logits if logit else model.forward_pairs
+    node = ops.ReconLogitsLoss if logit else ops.ReconLoss
     for lab in (run.label_val, run.label_test):
         if not 0 < float(lab.sum()) < lab.numel():
             raise ValueError("AUC undefined with one class")
@@ -305,10 +318,10 @@ def _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weigh
     val_plan = AucPlan(run.label_val)
     for epoch in range(epochs):
         model.train()
-        _emb, loss = model.forward_recon_loss(x, run.graph, sets, pos_weight, block_rows)
-        counts = ops.ReconLoss.last_counts
+        _emb, loss = recon_loss(x, run.graph, sets, pos_weight, block_rows)
+        counts = node.last_counts
         with torch.no_grad():
-            _emb, prob = model.forward_pairs(x, run.graph, tv)
+            _emb, prob = pair_scores(x, run.graph, tv)
         opt.zero_grad()
         loss.backward()
         opt.step()
@@ -330,7 +343,7 @@ def _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weigh
             log(f"epoch: {epoch} loss: {res.losses[-1]} val_auc: {best_auc}")
     model.load_state_dict(weights)
     with torch.no_grad():
-        _emb, prob = model.forward_pairs(x, run.graph, te)
+        _emb, prob = pair_scores(x, run.graph, te)
     res.test_auc = float(auc_tie_avg(run.label_test, prob, check=False))
     res.best_val_auc = best_auc
     return res

@@ -421,6 +421,22 @@ int dl_score_allpairs_fwd_form(int N, int K, int d, dl_dtype dtype, size_t ws_by
 int dl_score_allpairs_fwd(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
                           float* prob, void* ws, size_t ws_bytes, void* stream);
 
+/* The LOGITS of the dense scorer: logit[u][v] = sum_k (h_k[u].h_k[v]) exp(z_k[u].z_k[v] / t) for all N*N ordered pairs
+ * (row-major fp32 [N][N]) — model.py:109-113 without its sigmoid, the tensor F.binary_cross_entropy_with_logits is written on
+ * (replaces link_pred of main_disentangled.py:195 for a caller that wants a loss without the saturation of the fp32 sigmoid:
+ * sigmoid_ref is exactly 1 from logit 16.64 on).  The argument list is dl_score_allpairs_fwd's with `logit` in place of
+ * `prob`.  It is that entry's matrix-core kernel from planes with the sigmoid left out: the same products in the same order,
+ * so wherever dl_score_allpairs_fwd takes that kernel (fp32 tables, d % 32 == 0) prob = sigmoid(logit) element by element, and
+ * logit is symmetric bit for bit (only the tile pairs u <= v are computed, and mirrored).  The planes pad every factor to a
+ * multiple of 32 columns with zeros, so every d of the library is served by this one kernel; fp32 tables only (DL_BF16 is
+ * DL_E_ARG), N <= 46340, t != 0, N = 0 succeeds.  Logit space does not cure an overflowed exp: such an entry is inf or NaN.
+ * ws: dl_score_allpairs_logits_workspace_bytes(N, K, d) bytes (0 for arguments out of range), the planes of Z and H — NOT
+ * optional here: a missing or short workspace fails with DL_E_WORKSPACE.  For d % 32 == 0 it is
+ * dl_score_allpairs_workspace_bytes(N, K, d, DL_F32).  No atomics, no host read, the caller's stream. */
+size_t dl_score_allpairs_logits_workspace_bytes(int N, int K, int d);
+int dl_score_allpairs_logits_fwd(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                                 float* logit, void* ws, size_t ws_bytes, void* stream);
+
 /* Backward of dl_score_allpairs_fwd (autograd of model.py:109-113 + sigmoid under main_disentangled.py:195-198) on a
  * FIXED pair plan: the reference's caller takes its loss on link_pred[mask == 1] with masks built once per run
  * (main_disentangled.py:167-190), so d loss / d link_pred can be non-zero only on the masks' support.  The caller
@@ -465,6 +481,16 @@ int dl_score_allpairs_bwd_dense(const float* Z, const float* H, int N, int K, in
                                 const float* prob, const float* g_prob,   /* dense [N][N], row-major */
                                 float* dZ, float* dH,                     /* [N][K][d], every element written */
                                 void* ws, size_t ws_bytes, void* stream);
+
+/* Dense backward of dl_score_allpairs_logits_fwd: the gradient of ANY loss on the logits (what autograd gives for model.py:109-113
+ * without the sigmoid).  g_logit = d loss / d logit, dense [N][N] row-major, not necessarily symmetric; G^ = g_logit + g_logit^T
+ * with no p (1 - p) factor and no saved forward output, and everything behind G^ is dl_score_allpairs_bwd_dense: the same
+ * kernels, limits (fp32 tables, 1 <= d <= 128, N <= 46340, t != 0), determinism and "every tile is formed" NaN, and the same
+ * workspace (dl_score_allpairs_bwd_dense_workspace_bytes; form: dl_score_allpairs_bwd_dense_form). */
+int dl_score_allpairs_logits_bwd_dense(const float* Z, const float* H, int N, int K, int d, float t,
+                                       const float* g_logit,                /* dense [N][N], row-major */
+                                       float* dZ, float* dH,                /* [N][K][d], every element written */
+                                       void* ws, size_t ws_bytes, void* stream);
 
 /* Whole-graph reconstruction loss and its gradient with nothing of size N x N in memory: every non-edge is a negative, the
  * positives are up-weighted (the objective of the GAE family), and the gradient of the tables comes from the same call.
@@ -524,6 +550,25 @@ int dl_score_recon_dtype(const void* Z, const void* H, int N, int K, int d, dl_d
                          const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
                          int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
                          void* stream);
+
+/* The same objective in LOGIT space (replaces dl_score_recon_dtype where the fp32 sigmoid saturates — from logit 16.64 on it is
+ * exactly 1, p (1 - p) falls under the 1e-12 clamp below -27.6, and a saturated pair then costs 100 w with gradient exactly 0,
+ * so a confident false positive among the N^2 / 2 negatives is never pushed back; with the raw exp in the score such logits
+ * are the ordinary regime).  The argument list, the sets, the weights, the outputs, the limits and refusals, the strips, the
+ * form (dl_score_recon_form_dtype) and the workspace (dl_score_recon_workspace_bytes_dtype) are dl_score_recon_dtype's; there
+ * are no twins of those.  What differs is the scan's epilogue, per included pair with logit s, label y and weight w:
+ *   loss term = w l(s, y),   l = (1 - y) max(s, 0) + y max(-s, 0) + log1p(exp(-|s|))   (F.binary_cross_entropy_with_logits;
+ *                            a zero factor drops its term; the body of dl_pair_bce_logits),
+ *   d loss / d s = w (sigmoid(s) - y), formed without cancellation as dl_score_pairs_train_logits forms it: no clamp factor,
+ *                            a gradient for every finite s.
+ * Logit space cures the saturation of the sigmoid, not the overflow of exp: a non-finite logit (an overflowed exp, a NaN
+ * table entry) gives a non-finite loss and non-finite gradients, never a silent zero; the "no tile is skipped" NaN of a zero
+ * of G^ against E = inf is kept.  Launches, determinism (the same bits on every call, for every block_rows and DL_RANK_SLICES),
+ * the DL_BF16 bits rule and the absence of atomics, host reads and synchronisation are dl_score_recon_dtype's. */
+int dl_score_recon_logits(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
+                          const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
+                          int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
+                          void* stream);
 
 /* Ranking of ALL candidate links of query nodes (an extension; the reference has no counterpart): the logit of the dense
  * scorer, s(u,v) = sum_k (h_k[u].h_k[v]) * exp(z_k[u].z_k[v] / t) (pre-sigmoid link_pred, model.py:109-113), for every
