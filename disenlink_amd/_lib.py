@@ -32,6 +32,10 @@ class DlPairHub(C.Structure):
                 ("rest", DlCsrPlan), ("rest_pair", C.c_void_p), ("rest_pair2", C.c_void_p)]
 
 
+class DlPairHubMixed(C.Structure):
+    _fields_ = [("hub", DlPairHub), ("n_lists", C.c_int32)]
+
+
 class DlGraph(C.Structure):
     _fields_ = [("csr", DlCsrPlan), ("route", DlCsrPlan), ("rev", C.c_void_p), ("route_mirror", C.c_int32),
                 ("route_hub", C.POINTER(DlPairHub))]
@@ -39,7 +43,8 @@ class DlGraph(C.Structure):
 
 class DlPairIncidence(C.Structure):
     _fields_ = [("csr", DlCsrPlan), ("inc_pair", C.c_void_p), ("n_pairs", C.c_int32), ("entry_yw", C.c_void_p),
-                ("inc_pair2", C.c_void_p), ("n_second", C.c_int32), ("hub", C.POINTER(DlPairHub))]
+                ("inc_pair2", C.c_void_p), ("n_second", C.c_int32), ("hub", C.POINTER(DlPairHub)),
+                ("hub_mixed", C.POINTER(DlPairHubMixed))]
 
 
 class DlHostCsr(C.Structure):

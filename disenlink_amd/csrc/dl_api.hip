@@ -309,15 +309,23 @@ static int score_pairs_fwd_space(const void* Z, const void* H, int N, int K, int
         DL_REQUIRE(n_second >= 0 && by_u->csr.n_entries + n_second == n_pairs && by_u->n_pairs == n_pairs && by_u->inc_pair,
                    "by_u must list each of the %d pairs exactly once", n_pairs);
         DL_REQUIRE(by_u->csr.n_total == N, "by_u.n_total=%d != N=%d", by_u->csr.n_total, N);
-        if (const dl_pair_hub* hp = by_u->hub) {                        // hub blocks + residual plan: the same entries, cut in two
+        if (by_u->hub_mixed != nullptr)
+            DL_REQUIRE(by_u->hub_mixed->n_lists == DL_HUB_MIXED_LISTS, "by_u.hub_mixed: n_lists=%d, the kernels walk %d",
+                       by_u->hub_mixed->n_lists, DL_HUB_MIXED_LISTS);
+        // hub blocks + residual plan: the same entries, cut in two — as three lists per item (hub), as five (hub_mixed), or both
+        const dl_pair_hub* const hubs[2] = {by_u->hub, by_u->hub_mixed ? &by_u->hub_mixed->hub : nullptr};
+        const char* const names[2][2] = {{"by_u.hub", "by_u.hub.rest"}, {"by_u.hub_mixed", "by_u.hub_mixed.rest"}};
+        for (int x = 0; x < 2; ++x) {
+            const dl_pair_hub* hp = hubs[x];
+            if (hp == nullptr) continue;
             DL_REQUIRE(hp->n_items >= 0 && hp->n_entries >= 0 && hp->rest.n_entries >= 0 &&
                        hp->n_entries + hp->rest.n_entries == by_u->csr.n_entries,
-                       "by_u.hub must hold each of the plan's %d entries exactly once", by_u->csr.n_entries);
-            if (int rc = hp->n_items > 0 ? check_hub(hp, "by_u.hub", by_u->inc_pair2 != nullptr) : DL_OK) return rc;
+                       "%s must hold each of the plan's %d entries exactly once", names[x][0], by_u->csr.n_entries);
+            if (int rc = hp->n_items > 0 ? check_hub(hp, names[x][0], by_u->inc_pair2 != nullptr) : DL_OK) return rc;
             if (hp->rest.n_entries > 0) {
-                if (int rc = check_plan(&hp->rest, "by_u.hub.rest")) return rc;
+                if (int rc = check_plan(&hp->rest, names[x][1])) return rc;
                 DL_REQUIRE(hp->rest.n_total == N && hp->rest.seg_len == by_u->csr.seg_len && hp->rest_pair &&
-                           (hp->rest_pair2 || !by_u->inc_pair2), "by_u.hub.rest does not match by_u");
+                           (hp->rest_pair2 || !by_u->inc_pair2), "%s does not match by_u", names[x][1]);
             }
         }
         if (use_fast(&by_u->csr, K, d, dtype))

@@ -11,6 +11,7 @@ struct Config {
     bool fwd_group_kernel;      // DL_FWD_GROUP_KERNEL: group-per-entry forward scorer instead of the wave-per-entry one
     bool fwd_hub;               // DL_FWD_HUB: 0 = ignore a pair list's hub plan (dl_pair_hub) and walk the whole forward plan (default 1)
     bool route_hub;             // DL_ROUTE_HUB: 0 = ignore a graph's routing hub plan (dl_graph.route_hub) and walk the routing plan (default 1)
+    bool score_hub_mixed;       // DL_SCORE_HUB_MIXED: 0 = ignore a pair list's mixed hub plan (dl_pair_incidence.hub_mixed) and walk `hub` (default 1)
     int auc_target;             // DL_AUC_TARGET: workgroups of the AUC count kernel (0 = default)
     bool project_fp32_mfma;     // DL_PROJECT_FP32_MFMA: plain fp32 MFMA projection instead of the three-plane products
     int fwd_groups;             // DL_FWD_GROUPS: hidden-chunk groups of the projection forward (0 = default)

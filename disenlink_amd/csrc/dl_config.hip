@@ -29,6 +29,8 @@ void read_environment() {
     c.fwd_hub = !(fh != nullptr && fh[0] == '0' && fh[1] == '\0');
     const char* rh = getenv("DL_ROUTE_HUB");
     c.route_hub = !(rh != nullptr && rh[0] == '0' && rh[1] == '\0');
+    const char* hm = getenv("DL_SCORE_HUB_MIXED");
+    c.score_hub_mixed = !(hm != nullptr && hm[0] == '0' && hm[1] == '\0');
     c.auc_target = (int)std::max(0LL, number("DL_AUC_TARGET"));
     c.project_fp32_mfma = getenv("DL_PROJECT_FP32_MFMA") != nullptr;
     c.fwd_groups = (int)std::max(0LL, number("DL_FWD_GROUPS"));

@@ -8,6 +8,8 @@
 //   - an item's steps are [item_step[0], item_step[3]): the walk requests the words of a wave's next step one step ahead and
 //     never past the item's last step, and a batch asks for no word of a step past it;
 //   - every lane is active at a step's reduction: the walk's branches are wave-uniform (a wave takes a step or does not).
+// A mixed plan (dl_pair_hub_mixed; graph.HubPlan.build_mixed, the forward scorer only) has five lists [A | A211 | B | B31 | C]
+// under the same contract: dead partner rows only in the last step of each of its first four lists.
 #pragma once
 #include "dl_fast.h"
 
@@ -65,12 +67,20 @@ __device__ __forceinline__ void stage_block(lds_vf4* urow, const dl_pair_hub& h,
     }
 }
 
-// The walk of wave w = (s - st.a): step(words, s, shape, last) for each of its steps, in order.  shape: gathered partner rows.
+// The walk of wave w = (s - st.a): step(words, s, shape, last) for each of its steps, in order.  shape: gathered partner rows
+// (value) and which of them each of the four slots scores against (row).
 using FULL = std::false_type;
 using LAST = std::true_type;                                         // the step may hold dead partner rows
-constexpr std::integral_constant<int, 4> SHAPE_A{};
-constexpr std::integral_constant<int, 2> SHAPE_B{};
-constexpr std::integral_constant<int, 1> SHAPE_C{};
+template <int NV, int R0, int R1, int R2, int R3>
+struct Shape {
+    static constexpr int value = NV;
+    static constexpr int row(int e) { return e == 0 ? R0 : e == 1 ? R1 : e == 2 ? R2 : R3; }
+};
+constexpr Shape<4, 0, 1, 2, 3> SHAPE_A{};
+constexpr Shape<2, 0, 0, 1, 1> SHAPE_B{};
+constexpr Shape<1, 0, 0, 0, 0> SHAPE_C{};
+constexpr Shape<3, 0, 0, 1, 2> SHAPE_A211{};                         // the two shapes only a mixed plan has (dl_pair_hub_mixed)
+constexpr Shape<2, 0, 0, 0, 1> SHAPE_B31{};
 // nxt: the words of step s, requested by the caller (if s < st.end) as early as it likes; those of the wave's NEXT step are
 // requested at the top of the current one, into a second set of SGPRs — not behind a round trip at the head of its chain.
 template <typename Words, typename Fetch, typename Step>
@@ -84,6 +94,30 @@ __device__ __forceinline__ void walk(int s, const ItemSteps& st, Words nxt, Fetc
     if (s == st.b - 1) step(take(s), s, SHAPE_A, LAST{}), s += WAVES;
     for (; s < st.c - 1; s += WAVES) step(take(s), s, SHAPE_B, FULL{});
     if (s == st.c - 1) step(take(s), s, SHAPE_B, LAST{}), s += WAVES;
+    for (; s < st.end; s += WAVES) step(take(s), s, SHAPE_C, FULL{});
+}
+
+// The same over the five lists [A | A211 | B | B31 | C] of a mixed plan (dl_pair_hub_mixed: item_step has six boundaries).
+struct MixedItemSteps { int a, a211, b, b31, c, end; };
+__device__ __forceinline__ MixedItemSteps mixed_item_steps(const dl_pair_hub& h, int it) {
+    return {h.item_step[6 * it],     h.item_step[6 * it + 1], h.item_step[6 * it + 2],
+            h.item_step[6 * it + 3], h.item_step[6 * it + 4], h.item_step[6 * it + 5]};
+}
+template <typename Words, typename Fetch, typename Step>
+__device__ __forceinline__ void walk(int s, const MixedItemSteps& st, Words nxt, Fetch&& fetch, Step&& step) {
+    auto take = [&](const int cur) {
+        const Words w = nxt;
+        if (cur + WAVES < st.end) nxt = fetch(cur + WAVES);
+        return w;
+    };
+    for (; s < st.a211 - 1; s += WAVES) step(take(s), s, SHAPE_A, FULL{});
+    if (s == st.a211 - 1) step(take(s), s, SHAPE_A, LAST{}), s += WAVES;
+    for (; s < st.b - 1; s += WAVES) step(take(s), s, SHAPE_A211, FULL{});
+    if (s == st.b - 1) step(take(s), s, SHAPE_A211, LAST{}), s += WAVES;
+    for (; s < st.b31 - 1; s += WAVES) step(take(s), s, SHAPE_B, FULL{});
+    if (s == st.b31 - 1) step(take(s), s, SHAPE_B, LAST{}), s += WAVES;
+    for (; s < st.c - 1; s += WAVES) step(take(s), s, SHAPE_B31, FULL{});
+    if (s == st.c - 1) step(take(s), s, SHAPE_B31, LAST{}), s += WAVES;
     for (; s < st.end; s += WAVES) step(take(s), s, SHAPE_C, FULL{});
 }
 

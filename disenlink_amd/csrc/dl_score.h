@@ -222,8 +222,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(4, FWD_WA
 // (dl_hub.h, with the plan contract).  A step is the step of the kernel above — 4 / 2 / 1 partner rows gathered into
 // registers through a scalar row base, 16 float4 in flight before anything waits, the same dot4_packed calls into
 // val[table * 8 + chunk * 4 + slot], the same reduction, expf and sigmoid — except that every slot reads ITS OWN u row from
-// LDS, and that the partner registers a slot uses are fixed by the step's shape (NV = gathered rows: slot e uses set
-// e * NV / 4).  The value of a slot never meets another slot's, and the reduction adds the same 16 lanes in the same order
+// LDS, and that the partner registers a slot uses are fixed by the step's shape (NV = gathered rows: slot e uses the set
+// its shape's row map names, dl_hub.h).  The value of a slot never meets another slot's, and the reduction adds the same 16 lanes in the same order
 // whichever slot a value sits in: every pair gets the bits of the kernel above.
 // Without per-factor terms (COEF == false) a step ends at its logit: a step yields 4 of them and a wave has 64 lanes, so the
 // wave keeps the logits of 16 steps in its lanes and runs ONE sigmoid and ONE store pass per batch (and one behind its last
@@ -281,7 +281,11 @@ __device__ __forceinline__ void transposed_reduce16_masked(float* v, int c) {
     TransposedReduce<4, 2>::run(v, c);
 }
 
-template <int K, int D, bool T1, bool COEF, bool FOLD, bool LOGIT = false>
+// MIXED: h is the plan of a dl_pair_hub_mixed — five lists per item, walked by the five-list walk of dl_hub.h, whose two further
+// shapes differ from A, B and C in nothing but the number of gathered rows and the slot -> row map below.  A partner row is
+// then gathered once per remainder of its group, and a slot's hub row is the heavier endpoint of its pair: fewer gathered
+// rows for the same steps, the same LDS reads and the same arithmetic (profiles/r17_fwd_hub_mixed.txt).
+template <int K, int D, bool T1, bool COEF, bool FOLD, bool LOGIT = false, bool MIXED = false>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void score_fwd_wave_kernel(
     dl_pair_hub h, const float* __restrict__ Z, const float* __restrict__ H, float t, float* __restrict__ prob,
     float* __restrict__ coef_e, float* __restrict__ coef_q) {
@@ -296,7 +300,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
     const int wave = wave_index(), lane = lane_id();
     const int i = lane & 15, r = lane >> 4;
     const int blk = h.item_block[it];
-    const ItemSteps st = item_steps(h, it);                          // asked for with the block, ahead of the staging loads
+    const std::conditional_t<MIXED, MixedItemSteps, ItemSteps> st = [&] {      // asked for with the block, ahead of the staging loads
+        if constexpr (MIXED) return mixed_item_steps(h, it);
+        else return item_steps(h, it);
+    }();
     stage_block<NJ, 2>((lds_vf4*)urow, h, blk, wave, lane, {Z, H});
     __syncthreads();                                                 // the only one: nothing below waits for another wave
     // a step's 16 words through the scalar cache (the plan is read-only for the whole launch)
@@ -332,7 +339,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
         if (FOLD && pq2 >= 0) prob[pq2] = p;
     };
     auto do_step = [&](const StepWords& w, auto shape, auto last) {
-        constexpr int NV = decltype(shape)::value;                   // gathered partner rows: 4 (A), 2 (B), 1 (C)
+        using SH = decltype(shape);
+        constexpr int NV = SH::value;                                // gathered partner rows: 4 (A), 3 (A211), 2 (B, B31), 1 (C)
         constexpr bool LAST = decltype(last)::value;                 // dead partner rows: dl_hub.h; the kernel above's TAIL
         const int sv[4] = {w.v.x, w.v.y, w.v.z, w.v.w}, su[4] = {w.u.x, w.u.y, w.u.z, w.u.w}, sq[4] = {w.q.x, w.q.y, w.q.z, w.q.w},
                   sq2[4] = {w.p.x, w.p.y, w.p.z, w.p.w};
@@ -369,8 +377,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int e = 0; e < U; ++e) {
-                val[j * 4 + e] = dot4_packed(a4[e], zv[e * NV / 4][j]);
-                val[8 + j * 4 + e] = dot4_packed(b4[e], hv[e * NV / 4][j]);
+                // (A, B and C: row(e) == e * NV / 4 — the three-list forms keep that expression and with it their register allocation)
+                const int rw = MIXED ? SH::row(e) : e * NV / 4;
+                val[j * 4 + e] = dot4_packed(a4[e], zv[rw][j]);
+                val[8 + j * 4 + e] = dot4_packed(b4[e], hv[rw][j]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -598,6 +608,17 @@ struct ScoreOps {
                     });
                 };
                 const dl_pair_hub* hp = config().fwd_hub ? by_u->hub : nullptr;
+                const dl_pair_hub* hm = config().fwd_hub && config().score_hub_mixed && by_u->hub_mixed ? &by_u->hub_mixed->hub : nullptr;
+                if (hm != nullptr && hm->n_items > 0) {
+                    // the same, over the mixed plan: five step shapes, and its own residual plan
+                    pick([&](auto t1, auto cf, auto fo) {
+                        hipLaunchKernelGGL((hub::score_fwd_wave_kernel<K, D, decltype(t1)::value, decltype(cf)::value, decltype(fo)::value, LOGIT, true>),
+                                           dim3((unsigned)hm->n_slices * (unsigned)hm->slice_max_item), dim3(hub::THREADS), 0,
+                                           st, *hm, (const float*)Z, (const float*)H, t, prob, coef, coef_q);
+                    });
+                    if (hm->rest.n_entries > 0) wave_plan(&hm->rest, hm->rest_pair, hm->rest_pair2);
+                    return check_launch("score_pairs_fwd(fast, mixed hub blocks + wave per entry)");
+                }
                 if (hp != nullptr && hp->n_items > 0) {
                     // hub rows by blocks of 16 (hub::score_fwd_wave_kernel), then every other row as before
                     pick([&](auto t1, auto cf, auto fo) {

@@ -24,8 +24,9 @@
 #include "disenlink_hip.h"
 
 // Operator set + schemas of this binding; native.py refuses a library built for another number (a stale .so would
-// otherwise fail deep inside a training step with an AttributeError or a schema error).  Bump with every schema change.
-#define DL_TORCH_BINDING_ABI 7
+// otherwise fail deep inside a training step with an AttributeError or a schema error).  Bump with every schema change, and
+// with every change of a struct the operators dereference (8: dl_pair_incidence.hub_mixed).
+#define DL_TORCH_BINDING_ABI 8
 
 namespace {
 

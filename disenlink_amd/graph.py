@@ -551,12 +551,37 @@ HUB_MIN_SHARE = 1.25
 # the benchmark's own plan (profiles/r12_fwd_hub_pipeline.txt, section 3; us per call): 128 / 256 / 384 / 512 / 768 / 1,024
 # = 129.3 / 118.7 / 116.4 / 116.3 / 117.7 / 116.1 — 512 and 1,024 pass the keep rule against 256 and tie; 512 is the shorter.
 HUB_ITEM_ROWS = 512
+# Slot -> gathered partner row of a step, list by list (dl_hub.h: SHAPE_*): the three lists [A | B | C] of HubPlan.build and the
+# five [A | A211 | B | B31 | C] of HubPlan.build_mixed.  A shape gathers (its last slot's row + 1) rows.
+HUB_SHAPES = ((0, 1, 2, 3), (0, 0, 1, 1), (0, 0, 0, 0))
+HUB_MIXED_SHAPES = ((0, 1, 2, 3), (0, 0, 1, 2), (0, 0, 1, 1), (0, 0, 0, 1), (0, 0, 0, 0))
+# The two parts of the mixed plan, for A/B runs (tools/fwd_hub_ab.py; both on is what ships): the heavier endpoint of a pair is
+# its hub row (hub_owner); a group's remainder stays one piece (HubPlan.build_mixed(mixed=True)).
+HUB_MIXED_OWNER = True
+HUB_MIXED_SHAPES_ON = True
+# Gathered partner rows per work item of the mixed plan.  A step of the mixed plan gathers fewer rows, so at HUB_ITEM_ROWS = 512
+# its longest item is 407 steps on squirrel_real (324 on the three lists) and 434 on chameleon_real (356) — and the longest
+# chain of steps is the launch's tail.  The scorer alone, us per call at 192 / 256 / 320 / 384 / 448 / 512 rows
+# (profiles/r17_fwd_hub_mixed.txt): squirrel_real 99.1 / 98.0 / 96.6 / 96.4 / 96.4 / 96.7 (three lists 110.1 in that run),
+# chameleon_real 32.5 / 29.9 / 32.8 / 36.8 / 41.4 / 46.7 (three lists 41.3: at 512 the mixed plan LOSES there).  320 ties the
+# best on squirrel_real and keeps most of chameleon_real's gain.  (None = HUB_ITEM_ROWS)
+HUB_MIXED_ITEM_ROWS = 320
 
 
 def hub_gathers(c: torch.Tensor) -> torch.Tensor:
     """Partner rows gathered for c slots on one partner row: c // 4 steps of shape C, a remainder of 2 or 3 a half of a
     shape B step, a remainder of 1 or 3 a slot of a shape A step."""
     return c // 4 + torch.tensor([0, 1, 1, 2], device=c.device)[c % 4]
+
+
+def hub_owner(row: torch.Tensor, col: torch.Tensor, n_nodes: int):
+    """(hub row, partner row) of every forward entry under the owner rule of the mixed plan: the endpoint with more
+    forward entries, counted over both endpoints of all entries; ties go to the smaller id.  The score is symmetric bit
+    for bit (fold_mirrors relies on it), so which endpoint is staged in LDS and which is gathered changes no result —
+    but the heavy rows then share more partner rows, as in route_hub_plan."""
+    deg = torch.bincount(torch.cat([row, col]), minlength=n_nodes)
+    swap = (deg[col] > deg[row]) | ((deg[col] == deg[row]) & (col < row))
+    return torch.where(swap, col, row), torch.where(swap, row, col)
 
 
 def hub_rank(row: torch.Tensor, n_nodes: int):
@@ -614,10 +639,21 @@ class HubPlan:
     rest_pair: torch.Tensor | None
     rest_pair2: torch.Tensor | None
     _struct: _lib.DlPairHub | None = field(default=None, repr=False)
+    _struct_mixed: _lib.DlPairHubMixed | None = field(default=None, repr=False)
 
     @property
     def n_steps(self) -> int:
         return int(self.step_v.shape[0])
+
+    @property
+    def mixed(self) -> bool:
+        """A plan of build_mixed: five lists per item (dl_pair_hub_mixed), not three."""
+        return int(self.item_step.shape[1]) == len(HUB_MIXED_SHAPES) + 1
+
+    @property
+    def shapes(self):
+        """Slot -> gathered row of the step shapes, list by list."""
+        return HUB_MIXED_SHAPES if self.mixed else HUB_SHAPES
 
     @property
     def n_gathered(self) -> int:
@@ -731,6 +767,154 @@ class HubPlan:
                        _i32(item_block), _i32(item_slice), _i32(item_step_s), _i32(step_v), _i32(step_u), _i32(step_q),
                        None if step_q2 is None else _i32(step_q2), E, rest, rest_pair, rest_pair2)
 
+    @staticmethod
+    def build_mixed(row, col, pair, pair2, n_nodes: int, n_rows: int, n_slices: int, bounds, rest_csr,
+                    item_rows: int | None = None, mixed: bool = True) -> "HubPlan":
+        """The MIXED plan (dl_pair_hub_mixed): arguments, ranks, blocks, column slices and work items as in ``build`` —
+        ``row`` is the hub row of an entry, which PairList.build chooses by ``hub_owner`` — but an item holds FIVE lists
+        [A | A211 | B | B31 | C] and ``item_step`` is [n_items, 6].  The c slots of a group give c // 4 C steps and, for a
+        remainder of 1, 2 or 3, ONE piece that gathers its partner row once.  Per item: 3-pieces pair with 1-pieces (B31),
+        2-pieces with each other (B), an odd 2-piece takes up to two 1-pieces (A211; none left: it closes list B), the
+        1-pieces left go in fours (A).  A list's leftover closes its last step with dead slots and dead rows; a 3-piece that
+        finds no 1-piece closes list B31, and any further one is a C step whose fourth slot is dead — a dead slot, never a
+        dead row, so the kernel's contract holds (check).  ``mixed=False`` cuts a remainder of 3 into 2 + 1 and fills A
+        and B only: the packing of ``build`` in this layout, for A/B runs."""
+        item_rows = HUB_ITEM_ROWS if item_rows is None else int(item_rows)
+        dev = row.device
+        ar = lambda n: torch.arange(n, device=dev)
+        excl = lambda x: torch.cumsum(x, 0) - x
+        # ranks, blocks, groups and work items: build's, with one gather per remainder
+        rank, order, n_live = hub_rank(row, n_nodes)
+        T = max(0, min(int(n_rows), n_live))
+        nb = (T + HUB_W - 1) // HUB_W
+        block_row = torch.full((nb * HUB_W,), -1, dtype=torch.int64, device=dev)
+        block_row[:T] = order[:T]
+        in_hub = rank[row] < T
+        hrow, v, q = row[in_hub], col[in_hub], pair[in_hub]
+        q2 = None if pair2 is None else pair2[in_hub]
+        E = int(v.numel())
+        blk = torch.div(rank[hrow], HUB_W, rounding_mode="floor")
+        ul = rank[hrow] - blk * HUB_W
+        sl = torch.bucketize(v, bounds.to(dev), right=True) if n_slices > 1 else torch.zeros_like(v)
+        n_streams = min(n_slices, DEFAULT_SLICES)
+        key = (blk * n_slices + sl) * n_nodes + v
+        perm = torch.argsort(key, stable=True)
+        key, v, ul, q = key[perm], v[perm], ul[perm], q[perm]
+        q2 = None if q2 is None else q2[perm]
+        gnew = torch.ones(E, dtype=torch.bool, device=dev)
+        gnew[1:] = key[1:] != key[:-1]
+        gfirst = torch.nonzero(gnew).reshape(-1)
+        g_of = torch.cumsum(gnew, 0) - 1
+        G = int(gfirst.numel())
+        c = torch.bincount(g_of, minlength=G)
+        g_bs = torch.div(key[gfirst], n_nodes, rounding_mode="floor")
+        nC, rem = torch.div(c, 4, rounding_mode="floor"), c % 4
+        gath = nC + (rem > 0).long() if mixed else hub_gathers(c)
+        bs_new = torch.ones(G, dtype=torch.bool, device=dev)
+        bs_new[1:] = g_bs[1:] != g_bs[:-1]
+        bs_first = torch.nonzero(bs_new).reshape(-1)
+        bs_of = torch.cumsum(bs_new, 0) - 1
+        cum = excl(gath)
+        part = torch.div(cum - cum[bs_first][bs_of], item_rows, rounding_mode="floor")
+        inew = bs_new.clone()
+        inew[1:] |= part[1:] != part[:-1]
+        ifirst = torch.nonzero(inew).reshape(-1)
+        i_of = torch.cumsum(inew, 0) - 1
+        I = int(ifirst.numel())
+        tot = lambda at, x: torch.zeros(I, dtype=torch.int64, device=dev).index_add_(0, at, x)
+        cC, nC_i = excl(nC) - excl(nC)[ifirst][i_of], tot(i_of, nC)
+        # pieces, in group order: (group, slots, first slot inside the group)
+        if mixed:
+            pg = torch.nonzero(rem > 0).reshape(-1)
+            psz, poff = rem[pg], 4 * nC[pg]
+        else:
+            g2, g1 = torch.nonzero(rem >= 2).reshape(-1), torch.nonzero((rem == 1) | (rem == 3)).reshape(-1)
+            pg = torch.cat([g2, g1])
+            psz = torch.cat([torch.full_like(g2, 2), torch.ones_like(g1)])
+            poff = torch.cat([4 * nC[g2], 4 * nC[g1] + 2 * (rem[g1] == 3).long()])
+            o = torch.argsort(pg * 2 + (psz == 1).long(), stable=True)
+            pg, psz, poff = pg[o], psz[o], poff[o]
+        Pn = int(pg.numel())
+        pit = i_of[pg]
+
+        def ranked(size):                                           # (pieces of this size per item, a piece's number among them)
+            m = (psz == size).long()
+            n = tot(pit, m)
+            return n, excl(m) - excl(n)[pit]
+        (n1, k1), (n2, k2), (n3, k3) = ranked(1), ranked(2), ranked(3)
+        m31 = torch.minimum(n3, n1)                                  # full B31 steps
+        x3, r1 = n3 - m31, n1 - m31                                  # 3-pieces / 1-pieces without a partner
+        nB, odd2 = torch.div(n2, 2, rounding_mode="floor"), n2 % 2
+        s211 = odd2 * torch.clamp(r1, max=2) if mixed else torch.zeros_like(r1)      # 1-pieces beside the odd 2-piece
+        lens = torch.stack([(r1 - s211 + 3) // 4, (s211 > 0).long(), nB + odd2 * (s211 == 0).long(), m31 + (x3 > 0).long(),
+                            nC_i + torch.clamp(x3 - 1, min=0)], dim=1)
+        n_i = lens.sum(1)
+        i_blk = torch.div(g_bs[ifirst], n_slices, rounding_mode="floor")
+        i_sl = g_bs[ifirst] - i_blk * n_slices
+        big = int(n_i.max()) + 1 if I else 1
+        iperm = torch.argsort(((i_sl % n_streams) * (n_slices + 1) + i_sl) * big + (big - 1 - n_i), stable=True)
+        ipos = torch.empty_like(iperm)
+        ipos[iperm] = ar(I)
+        base = torch.empty(I, dtype=torch.int64, device=dev)
+        base[iperm] = excl(n_i[iperm])
+        item_step = torch.cat([base[:, None], base[:, None] + torch.cumsum(lens, 1)], dim=1)      # [I, 6]
+        per_stream = torch.bincount(i_sl % n_streams, minlength=n_streams)
+        slice_item0 = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+        slice_item0[1:] = torch.cumsum(per_stream, 0)
+        S = int(n_i.sum())
+        # where a piece goes: (list, step inside the list, its first slot, its row of the step)
+        LA, LA211, LB, LB31, LC = range(5)
+        m31p, s211p, nBp = m31[pit], s211[pit], nB[pit]
+        j1 = k1 - m31p                                               # a 1-piece's number among those without a 3-piece
+        in31, in211, jA = k1 < m31p, (k1 >= m31p) & (j1 < s211p), j1 - s211p
+        last2 = k2 == 2 * nBp                                        # the odd 2-piece
+        w = torch.where
+        is1, is2 = psz == 1, psz == 2
+        p_list = w(is1, w(in31, LB31, w(in211, LA211, LA)), w(is2, w(last2 & (s211p > 0), LA211, LB), w(k3 <= m31p, LB31, LC)))
+        p_step = w(is1, w(in31, k1, w(in211, 0, torch.div(jA, 4, rounding_mode="floor"))),
+                   w(is2, w(last2, w(s211p > 0, 0, nBp), torch.div(k2, 2, rounding_mode="floor")),
+                     w(k3 <= m31p, k3, nC_i[pit] + k3 - m31p - 1)))
+        p_slot = w(is1, w(in31, 3, w(in211, 2 + j1, jA % 4)), w(is2 & ~last2, 2 * (k2 % 2), 0))
+        p_row = w(is1, w(in31, 1, w(in211, 1 + j1, jA % 4)), w(is2 & ~last2, k2 % 2, 0))
+        p_at = item_step[pit, p_list] + p_step
+        # slots: the first 4 * (c // 4) entries of a group fill its C steps, the others are its piece(s)
+        p = ar(E) - gfirst[g_of]
+        isC = p < 4 * nC[g_of]
+        g_piece = torch.full((G,), Pn, dtype=torch.int64, device=dev)
+        if Pn:
+            g_piece.scatter_reduce_(0, pg, ar(Pn), reduce="amin")
+        pe = torch.clamp(g_piece[g_of], max=max(Pn - 1, 0))
+        if not mixed and Pn:
+            pe = pe + (~isC & (p >= poff[pe] + psz[pe])).long()      # the 1 of a 2 + 1
+        if Pn == 0:
+            p_at = p_slot = p_row = poff = torch.zeros(1, dtype=torch.int64, device=dev)
+        step = w(isC, item_step[i_of[g_of], LC] + cC[g_of] + torch.div(p, 4, rounding_mode="floor"), p_at[pe])
+        slot = w(isC, p % 4, p_slot[pe] + p - poff[pe])
+        vset = w(isC, torch.zeros_like(p), p_row[pe])
+        mk = lambda fill: torch.full((S, 4), fill, dtype=torch.int64, device=dev)
+        step_v, step_u, step_q = mk(-1), mk(0), mk(-1)
+        step_v[step, vset] = v
+        step_u[step, slot] = ul
+        step_q[step, slot] = q
+        step_q2 = None
+        if q2 is not None:
+            step_q2 = mk(-1)
+            step_q2[step, slot] = q2
+        rest = rest_pair = rest_pair2 = None
+        if int((~in_hub).sum()):
+            got = rest_csr(~in_hub)
+            rest, rest_pair = got[0], got[1]
+            rest_pair2 = got[2] if len(got) > 2 else None
+        item_block = torch.empty(I, dtype=torch.int64, device=dev)
+        item_block[ipos] = i_blk
+        item_slice = torch.empty(I, dtype=torch.int64, device=dev)
+        item_slice[ipos] = i_sl
+        item_step_s = torch.empty_like(item_step)
+        item_step_s[ipos] = item_step
+        return HubPlan(T, nb, _i32(block_row), I, n_streams, int(per_stream.max()) if I else 0, _i32(slice_item0),
+                       _i32(item_block), _i32(item_slice), _i32(item_step_s), _i32(step_v), _i32(step_u), _i32(step_q),
+                       None if step_q2 is None else _i32(step_q2), E, rest, rest_pair, rest_pair2)
+
     def to(self, device) -> "HubPlan":
         mv = lambda t: None if t is None else t.to(device)
         return HubPlan(self.n_rows, self.n_blocks, mv(self.block_row), self.n_items, self.n_slices, self.slice_max_item,
@@ -746,22 +930,29 @@ class HubPlan:
             return
         dev = self.step_v.device
         st = self.item_step.long()
-        lens = torch.stack([st[:, 1] - st[:, 0], st[:, 2] - st[:, 1], st[:, 3] - st[:, 2]], dim=1).reshape(-1)
+        shapes = self.shapes                                                    # slot -> row of every list; the last list is C
+        lens = (st[:, 1:] - st[:, :-1]).reshape(-1)
         ends = torch.cumsum(lens, 0)
-        ok = bool((lens >= 0).all()) and int(ends[-1]) == self.n_steps and bool((st[1:, 0] == st[:-1, 3]).all()) \
+        ok = bool((lens >= 0).all()) and int(ends[-1]) == self.n_steps and bool((st[1:, 0] == st[:-1, -1]).all()) \
             and int(st[0, 0]) == 0
         if ok:
-            nv = torch.repeat_interleave(torch.tensor([4, 2, 1], device=dev).repeat(self.n_items), lens)
+            smap = torch.repeat_interleave(torch.tensor(shapes, device=dev).repeat(self.n_items, 1), lens, dim=0)    # [n_steps, 4]
+            nv = smap[:, 3] + 1
+            is_c = torch.repeat_interleave(torch.arange(len(shapes), device=dev).repeat(self.n_items), lens) == len(shapes) - 1
             last = torch.zeros(self.n_steps, dtype=torch.bool, device=dev)
             last[(ends - 1)[lens > 0]] = True
             used = torch.arange(4, device=dev)[None, :] < nv[:, None]            # the partner rows a step of this shape gathers
             live = (self.step_v >= 0) & used
-            full = ~last | (nv == 1)                                            # a C step is never short
+            full = ~last | is_c                                                 # a C step is never short
             ok = not bool(((used & ~live)[full]).any()) and bool(live[:, 0].all()) \
                 and not bool((live[:, 1:] & ~live[:, :-1]).any())
+            if ok and self.mixed:                                               # a live slot scores against a live row
+                ok = not bool(((self.step_q >= 0) & ~torch.gather(live, 1, smap)).any())
         if not ok:
             raise ValueError("hub plan: dead partner rows may only close the last step of an item's A list and B list "
-                             "(dl_pair_hub, disenlink_hip.h)")
+                             "(dl_pair_hub, disenlink_hip.h)" if not self.mixed else
+                             "mixed hub plan: dead partner rows may only close the last step of an item's A, A211, B and B31 "
+                             "lists, and no live slot scores against one (dl_pair_hub_mixed, disenlink_hip.h)")
 
     def c_value(self) -> _lib.DlPairHub:
         if self._struct is None:
@@ -773,6 +964,13 @@ class HubPlan:
                 ptr(self.step_q), ptr(self.step_q2), self.n_entries,
                 self.rest.c_value() if self.rest is not None else _lib.DlCsrPlan(), ptr(self.rest_pair), ptr(self.rest_pair2))
         return self._struct
+
+    def c_value_mixed(self) -> _lib.DlPairHubMixed:
+        if self._struct_mixed is None:
+            if not self.mixed:
+                raise ValueError("not a mixed hub plan (HubPlan.build_mixed)")
+            self._struct_mixed = _lib.DlPairHubMixed(self.c_value(), len(HUB_MIXED_SHAPES))
+        return self._struct_mixed
 
 
 # Work item length of the ROUTING hub plan, in gathered partner rows, and its column slices (the partner rows of a slice are
@@ -835,6 +1033,7 @@ class PairList(_PlanOwner):
     fwd_pair: torch.Tensor | None = None
     fwd_pair2: torch.Tensor | None = None
     hub: HubPlan | None = None                       # the forward entries as hub blocks + a residual plan (None: no hub rows)
+    hub_mixed: HubPlan | None = None                 # the same entries as a mixed plan (HubPlan.build_mixed), walked instead of `hub`
     _struct: _lib.DlPairIncidence | None = field(default=None, repr=False)
     _struct_u: _lib.DlPairIncidence | None = field(default=None, repr=False)
     _yw: torch.Tensor | None = field(default=None, repr=False)      # per-entry (label, signed weight): bind_labels
@@ -891,7 +1090,7 @@ class PairList(_PlanOwner):
               run_len: int = DEFAULT_RUN_LEN, row_range: tuple[int, int] | None = None,
               n_slices: int | None = None, by_u_range: tuple[int, int] | None = None,
               build_by_u: bool = True, row_bytes: int = 2048, inc_slices: int | None = None,
-              fold_mirrors: bool = True, hub_rows: int | None = None) -> "PairList":
+              fold_mirrors: bool = True, hub_rows: int | None = None, hub_mixed: bool | None = None) -> "PairList":
         """``row_range`` restricts the incidence rows to one shard's nodes (the pair ids in ``inc_pair``
         then index prob / g_prob arrays covering the whole pair list); ``by_u_range`` restricts the rows
         of the forward plan (every pu must lie inside it).  ``n_slices`` / ``inc_slices``: column slices of the forward
@@ -899,7 +1098,9 @@ class PairList(_PlanOwner):
         per (row, slice) group, the forward plan sums nothing across segments).  ``fold_mirrors=False`` keeps the forward
         scorer on ``by_u`` (one entry per listed pair), which is built the same either way.  ``hub_rows``: how many of the
         rows with the most forward entries are scored by blocks of HUB_W rows (HubPlan) — None = auto_hub_rows (a list
-        without hub rows, or a row shard, gets none and nothing changes), 0 = none."""
+        without hub rows, or a row shard, gets none and nothing changes), 0 = none.  ``hub_mixed``: whether the list also
+        gets the mixed plan (HubPlan.build_mixed over the hub_owner orientation, the same number of hub rows), which the
+        scorer then walks instead of ``hub`` — None = wherever it gets a hub plan, False = never, True = it must."""
         pu = pu.reshape(-1).to(torch.int64)
         pv = pv.reshape(-1).to(torch.int64)
         if pu.numel() != pv.numel():
@@ -961,7 +1162,19 @@ class PairList(_PlanOwner):
                 rest_csr = lambda keep: csr(f_u[keep], f_v[keep], f_q[keep], 0, n_nodes, run_len, unit_segs=1,
                                             pair2=None if f_q2 is None else f_q2[keep], bnd=bnd)
                 hub = HubPlan.build(f_u, f_v, f_q, f_q2, n_nodes, T, n_slices, bnd, rest_csr)
-        return PairList(n_nodes, _i32(pu), _i32(pv), by_u, by_u_pair, inc, inc_pair, fwd, fwd_pair, fwd_pair2, hub)
+        mixed = None
+        if hub_mixed and hub is None:
+            raise ValueError("a mixed hub plan needs a list that gets a hub plan (hub_rows)")
+        if hub is not None and hub_mixed is not False:
+            # the decision and the number of hub rows are the listed orientation's (no list changes category); every row
+            # with entries there = every owner row with entries here
+            o_u, o_v = hub_owner(f_u, f_v, n_nodes) if HUB_MIXED_OWNER else (f_u, f_v)
+            o_bnd = slice_bounds(o_v, n_slices) if n_slices > 1 else None
+            o_rest = lambda keep: csr(o_u[keep], o_v[keep], f_q[keep], 0, n_nodes, run_len, unit_segs=1,
+                                      pair2=None if f_q2 is None else f_q2[keep], bnd=o_bnd)
+            mixed = HubPlan.build_mixed(o_u, o_v, f_q, f_q2, n_nodes, n_nodes if hub_rows is None else T, n_slices, o_bnd,
+                                        o_rest, item_rows=HUB_MIXED_ITEM_ROWS, mixed=HUB_MIXED_SHAPES_ON)
+        return PairList(n_nodes, _i32(pu), _i32(pv), by_u, by_u_pair, inc, inc_pair, fwd, fwd_pair, fwd_pair2, hub, mixed)
 
     def c_struct(self, n_pairs_total: int | None = None):
         if self._struct is None:
@@ -978,7 +1191,11 @@ class PairList(_PlanOwner):
                 self._struct_u = _lib.DlPairIncidence(self.fwd.c_value(), self.fwd_pair.data_ptr(), self.n_pairs, None,
                                                       self.fwd_pair2.data_ptr(), self.n_pairs - self.fwd.n_entries)
             if self.hub is not None and self.hub.n_items > 0:
+                if self.hub.mixed:
+                    raise ValueError("PairList.hub holds a mixed plan: that is PairList.hub_mixed")
                 self._struct_u.hub = C.pointer(self.hub.c_value())
+            if self.hub_mixed is not None and self.hub_mixed.n_items > 0:
+                self._struct_u.hub_mixed = C.pointer(self.hub_mixed.c_value_mixed())
         return C.byref(self._struct_u)
 
     def c_plan(self):

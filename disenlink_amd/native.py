@@ -26,7 +26,7 @@ from .graph import Graph, PairList
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libdisenlink_torch.so")
 _state = {"loaded": None}
-BINDING_ABI = 7                  # csrc/torch/dl_torch.cpp: DL_TORCH_BINDING_ABI
+BINDING_ABI = 8                  # csrc/torch/dl_torch.cpp: DL_TORCH_BINDING_ABI
 _OPS = ("hot_path_pairs_loss", "hot_path_pair_logits_loss", "project_stacked", "adam_step", "auc_pair_counts", "epoch_finish", "binding_abi")
 
 

@@ -144,6 +144,10 @@ typedef struct dl_pair_incidence {
     /* Optional (NULL = not given), read by dl_score_pairs_fwd only: the same entries cut into a hub plan and a residual
      * plan (dl_pair_hub below).  csr / inc_pair / inc_pair2 still describe the whole list. */
     const struct dl_pair_hub* hub;
+    /* Optional (NULL = not given), read by dl_score_pairs_fwd only: the same entries once more as a hub plan of five step
+     * shapes (dl_pair_hub_mixed below), which gathers fewer partner rows for the same scores.  Where it is given it is
+     * walked INSTEAD of `hub` (fp32 tables, d = 64, K in {4, 8}) unless DL_SCORE_HUB_MIXED=0; same bits either way. */
+    const struct dl_pair_hub_mixed* hub_mixed;
 } dl_pair_incidence;
 
 /* Hub plan of the forward scorer.  The rows with the most entries ("hub rows", ranked by entry count) are cut into
@@ -180,6 +184,24 @@ typedef struct dl_pair_hub {
     const int32_t* rest_pair;   /* [rest.n_entries] */
     const int32_t* rest_pair2;  /* [rest.n_entries], NULL when inc_pair2 is NULL */
 } dl_pair_hub;
+
+/* Hub plan of the forward scorer with MIXED step shapes.  The c slots of one block on one partner row give c / 4 steps of
+ * shape C as above, but the remainder of 1, 2 or 3 slots stays ONE piece that gathers its partner row once, and pieces of
+ * different partner rows share a step.  An item holds five lists of steps, stored [A | A211 | B | B31 | C]:
+ *   A    1+1+1+1  four gathered rows,  slot e against row e;
+ *   A211 2+1+1    three gathered rows, slots 0,1 against the first, 2 against the second, 3 against the third;
+ *   B    2+2      two gathered rows,   slots 0,1 against the first and 2,3 against the second;
+ *   B31  3+1      two gathered rows,   slots 0,1,2 against the first and 3 against the second;
+ *   C    4        one gathered row,    all four slots against it.
+ * `hub` is a dl_pair_hub whose item_step is [n_items][6] — the six boundaries of the five lists — and whose step_v holds
+ * the gathered rows of a step in its first 4 / 3 / 2 / 2 / 1 words.  A slot's hub row may be EITHER endpoint of its pair
+ * (the score is symmetric).  Dead partner rows stand only in the last step of each of the first four lists, behind the
+ * live ones; a dead slot (pair id -1) scores nothing wherever it stands.  Everything else is as in dl_pair_hub. */
+#define DL_HUB_MIXED_LISTS 5
+typedef struct dl_pair_hub_mixed {
+    dl_pair_hub hub;
+    int32_t n_lists;            /* DL_HUB_MIXED_LISTS */
+} dl_pair_hub_mixed;
 
 /* ---- host-side graph preparation (no GPU; the only entry points that allocate: malloc'd outputs are
  * released by the matching *_free).  Counterpart of the dense adjacency construction of
