@@ -134,6 +134,8 @@ EXPORTS = {
     "dl_score_recon_workspace_bytes_dtype": (_z, [_i, _i, _i, _i, _i]),
     "dl_score_recon_dtype": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _P, _P, _f, _f, _i, _P, _P, _P, _P, _P, _z, _P]),
     "dl_score_recon_logits": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _P, _P, _f, _f, _i, _P, _P, _P, _P, _P, _z, _P]),
+    "dl_score_recon_filtered": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _P, _P, _f, _f, _i, _P, _P, _P, _P, _P, _z, _P, _NF]),
+    "dl_score_recon_logits_filtered": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _P, _P, _f, _f, _i, _P, _P, _P, _P, _P, _z, _P, _NF]),
     "dl_score_topk_supported": (_i, [_i, _i]),
     "dl_score_mine_supported": (_i, [_i, _i]),
     "dl_score_mine_form": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),

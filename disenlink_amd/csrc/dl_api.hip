@@ -1149,11 +1149,11 @@ int dl_score_recon(const float* Z, const float* H, int N, int K, int d, float t,
                                 counts_out, dZ, dH, ws, ws_bytes, stream);
 }
 
-// dl_score_recon_dtype and dl_score_recon_logits: one set of checks, one driver
+// dl_score_recon_dtype, dl_score_recon_logits and their _filtered forms: one set of checks, one driver
 static int score_recon_space(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
                              const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
                              int block_rows, bool logit, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws,
-                             size_t ws_bytes, void* stream) {
+                             size_t ws_bytes, void* stream, const dl_node_filter* filter) {
     DL_REQUIRE(known_dtype(dtype), "unknown dtype %d", (int)dtype);
     if (int rc = check_shape(K, d)) return rc;
     DL_REQUIRE(dl_score_recon_supported(K, d), "the reconstruction loss serves fp32 and bf16 tables with 1 <= d <= 128, got d=%d", d);
@@ -1162,6 +1162,7 @@ static int score_recon_space(const void* Z, const void* H, int N, int K, int d, 
     DL_REQUIRE(t != 0.0f, "temperature is 0");
     DL_REQUIRE(Z && H && pos_rowptr && pos_col && loss_out && counts_out && dZ && dH, "NULL argument");
     DL_REQUIRE((ign_rowptr == nullptr) == (ign_col == nullptr), "ign_rowptr and ign_col must both be given or both be NULL");
+    if (int rc = check_filter(filter)) return rc;
     const size_t need = score_recon_workspace_bytes(N, K, d, dtype, block_rows);
     if (!ws || ws_bytes < need) {
         set_error("workspace too small: have %zu, need %zu (dl_score_recon_workspace_bytes%s)", ws ? ws_bytes : (size_t)0, need,
@@ -1169,23 +1170,40 @@ static int score_recon_space(const void* Z, const void* H, int N, int K, int d, 
         return DL_E_WORKSPACE;
     }
     return score_recon(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, logit, loss_out,
-                       counts_out, dZ, dH, ws, (hipStream_t)stream);
+                       counts_out, dZ, dH, ws, (hipStream_t)stream, filter);
 }
 
 int dl_score_recon_dtype(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
                          const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
                          int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
                          void* stream) {
+    return dl_score_recon_filtered(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows,
+                                   loss_out, counts_out, dZ, dH, ws, ws_bytes, stream, nullptr);
+}
+
+int dl_score_recon_filtered(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
+                            const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
+                            int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
+                            void* stream, const dl_node_filter* filter) {
     return score_recon_space(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, false,
-                             loss_out, counts_out, dZ, dH, ws, ws_bytes, stream);
+                             loss_out, counts_out, dZ, dH, ws, ws_bytes, stream, filter);
 }
 
 int dl_score_recon_logits(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
                           const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
                           int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
                           void* stream) {
+    return dl_score_recon_logits_filtered(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows,
+                                          loss_out, counts_out, dZ, dH, ws, ws_bytes, stream, nullptr);
+}
+
+int dl_score_recon_logits_filtered(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                                   const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* ign_rowptr,
+                                   const int32_t* ign_col, float w_pos, float w_neg, int block_rows, double* loss_out,
+                                   int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes, void* stream,
+                                   const dl_node_filter* filter) {
     return score_recon_space(Z, H, N, K, d, dtype, t, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, block_rows, true,
-                             loss_out, counts_out, dZ, dH, ws, ws_bytes, stream);
+                             loss_out, counts_out, dZ, dH, ws, ws_bytes, stream, filter);
 }
 
 int dl_score_pairs_train_supported(const dl_pair_incidence* inc, int K, int d, dl_dtype dtype) {

@@ -114,11 +114,13 @@ void score_recon_form(int N, int K, int d, dl_dtype dt, int block_rows, int* out
 size_t score_recon_workspace_bytes(int N, int K, int d, dl_dtype dt, int block_rows);
 void score_recon_strip(const __bf16* cz, const __bf16* ch, dl_dtype dt, int N, int K, int d, float t, int q0, int rows,
                        const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* ig_rowptr, const int32_t* ig_col, float w_pos,
-                       float w_neg, bool logit, float* ghat, float* lcell, unsigned* ccell, hipStream_t st);
+                       float w_neg, bool logit, const dl_node_filter* filter, float* ghat, float* lcell, unsigned* ccell, hipStream_t st);
 // logit: loss term and gradient per pair in logit space (dl_score_recon_logits); everything but the scan's epilogue is shared
+// filter (NULL: none; checked by the caller): a symmetric node-group rule, a pair it denies is ignored (dl_score_recon_filtered)
 int score_recon(const void* Z, const void* H, int N, int K, int d, dl_dtype dt, float t, const int32_t* pos_rowptr,
                 const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg, int block_rows,
-                bool logit, double* loss, int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st);
+                bool logit, double* loss, int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st,
+                const dl_node_filter* filter = nullptr);
 
 // ranking of all candidates of query rows on the matrix cores (dl_score_rank.hip): fp32 tables, 1 <= d <= 128
 bool score_rank_supported(int K, int d);

@@ -88,6 +88,7 @@ constexpr size_t lds_bytes(int P, bool recon = false) {
 }
 static_assert(lds_bytes(1, true) % 16 == 0 && lg_bytes(3, true) == 0, "RECON: three planes as before, one plane aligned");
 static_assert(lds_bytes(3) % 16 == 0 && lds_bytes(1) % 16 == 0 && lds_bytes(3) + FILTER_LDS_BYTES <= 160 * 1024, "LDS of a CU");
+static_assert(lds_bytes(1, true) + FILTER_LDS_BYTES <= 160 * 1024, "LDS of a CU: RECON x FILT on one plane (three planes: lds_bytes(3))");
 static_assert(4 * LG_WAVE * 4 <= (size_t)3 * TT * SLD * 2, "four waves' logits fit a three-plane image");
 
 // A PlaneStage tile whose 128 rows are gathered: row r of the tile is row rows[min(base + r, n - 1)] of the plane array.
@@ -196,8 +197,11 @@ __device__ __forceinline__ void compact_row(u64* __restrict__ L, u64* S, int n, 
 // 32-column block, the two blocks of a wave, the two waves — so a cell is a function of its logits alone.  Counts: ballots.
 // LOGIT (dl_score_recon_logits): per value the term w l(s, y) of BCE-with-logits (bce_logits_term) and g = w (sigmoid(s) - y)
 // without a clamp (sigmoid_minus_label), both of dl_common.h; masks, stores, sums and counts are the same text.
+// FILT (dl_score_recon_filtered): a pair the node-group rule denies is an ignored pair.  The scan has put the rule's deny words
+// of the tile into igm (see rank_scan_kernel), so the row threads OR the ignored columns and the diagonal into them where the
+// unfiltered epilogue starts from zero; everything behind the masks is the same text.
 static_assert(4 * RLG * 4 <= 3 * TT * SLD * 2, "four waves' terms fit a three-plane image");
-template <bool LOGIT>
+template <bool LOGIT, bool FILT>
 __device__ __forceinline__ void recon_epilogue(const ReconArgs& A, const f32x16 (&term)[2], float* lg, unsigned* pom, unsigned* scr,
                                                int* pocur, int* igcur, const int* rnode, int qt, int ct, int nt, int tid) {
     unsigned* igm = scr;                                        // [TT][4]: ignored columns of the tile, the diagonal among them
@@ -209,7 +213,7 @@ __device__ __forceinline__ void recon_epilogue(const ReconArgs& A, const f32x16 
         const int node = rnode[tid];
         unsigned *m = pom + tid * 4, *g = igm + tid * 4;
         m[0] = m[1] = m[2] = m[3] = 0u;
-        g[0] = g[1] = g[2] = g[3] = 0u;
+        if constexpr (!FILT) g[0] = g[1] = g[2] = g[3] = 0u;
         if (node >= 0) {
             pocur[tid] = exclusion_mask(A.ex_col, pocur[tid], A.ex_rowptr[node + 1], v0, m);
             if (A.ig_rowptr != nullptr) igcur[tid] = exclusion_mask(A.ig_col, igcur[tid], A.ig_rowptr[node + 1], v0, g);
@@ -276,6 +280,14 @@ __device__ __forceinline__ void recon_epilogue(const ReconArgs& A, const f32x16 
 // the tile's last pipeline step (the candidates' groups were staged one step earlier: a tile has K * 2 * nd >= 2 steps, and
 // every reader of the previous tile's mask and groups is behind a barrier by then); the row threads then OR the exclusion
 // into it where the unfiltered kernel starts from zero.  The epilogue is the unfiltered one.
+// RECON x FILT (dl_score_recon_filtered): exm holds the positives there, and a denied pair is an IGNORED one, so the words go to
+// the ignored mask igm, the first [TT][4] words of scr.  The same ordering holds for it: the only readers of igm are the value
+// loops of the previous tile's recon_epilogue, which lie before that epilogue's last __syncthreads, and the words are written
+// in step per_tile - 1 >= 1 of this tile, behind that barrier and the one that ends step 0; what the epilogue keeps in scr
+// behind igm (redl, redc) is not touched.  The first tile of a work item has no earlier reader, and all TT * 4 words are
+// written, so igm never holds what the last work item left.  The barrier that ends the step stands between the 512 writers and
+// the row threads that OR the ignored columns and the diagonal in.  A row outside the strip (rnode < 0) takes group 0 and a
+// column >= N group 0: either word is formed and never read as live (the epilogue tests rnode and N itself).
 // P: planes per operand, 3 (fp32 tables) or 1 (bf16 tables: one bf16x8 and one MFMA per operand and block, gram_block<1>); the
 // step keeps its 32 columns, so the k-blocks of a product are added in the same ascending order in both.
 // LOGIT (RECON only): the loss term and the gradient of the epilogue in logit space (dl_score_recon_logits).
@@ -445,7 +457,8 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(typename ModeArgs<MODE>
             if (rem == per_tile - 2) {
                 if (tid < TT) cgrp[tid] = gb;
             } else if (rem == per_tile - 1) {                   // word tid & 3 of row tid >> 2
-                exm[tid] = filter_word(fal[rgrp[tid >> 2] & 63], cgrp + (tid & 3) * 32);
+                unsigned* fm = MODE == RECON ? reinterpret_cast<unsigned*>(scr) : exm;      // RECON: igm, see above
+                fm[tid] = filter_word(fal[rgrp[tid >> 2] & 63], cgrp + (tid & 3) * 32);
             }
         }
         __syncthreads();
@@ -467,7 +480,7 @@ __global__ __launch_bounds__(RTHR) void rank_scan_kernel(typename ModeArgs<MODE>
         } else if constexpr (MODE == RECON) {
             float* lg = P == 3 ? reinterpret_cast<float*>((wave < 4 ? us : vs) + (s & 1) * 3 * TT * SLD) + (wave & 3) * (3 * TT * SLD / 8)
                                : lgs + wave * RLG;              // one plane: the wave's own RLG floats behind the images
-            recon_epilogue<LOGIT>(A, term, lg, exm, reinterpret_cast<unsigned*>(scr), excur, cnt, rnode, qt, ct0 + s / per_tile, nt, tid);
+            recon_epilogue<LOGIT, FILT>(A, term, lg, exm, reinterpret_cast<unsigned*>(scr), excur, cnt, rnode, qt, ct0 + s / per_tile, nt, tid);
         } else {
             if (tid < TT) {                                     // this tile's excluded columns of row tid
                 const int node = rnode[tid];
@@ -851,9 +864,10 @@ int score_ranks(const void* Z, const void* H, dl_dtype dt, int N, int K, int d, 
 // 128, as the query tiles — read where they stand in the plane arrays of Z and H, which are the candidates too — against all
 // candidate tiles.  ghat: rows x Np floats and the cells [rows rounded up to 128][Np / 128], all of it written.
 // dt: the planes are three per operand (DL_F32, split_rows) or the one of a bf16 table (DL_BF16, copy_rows): the P = 1 form.
+// nf (NULL: none): a symmetric node-group rule; a pair it denies is ignored (the RECON x FILT instantiations).
 void score_recon_strip(const __bf16* cz, const __bf16* ch, dl_dtype dt, int N, int K, int d, float t, int q0, int rows,
                        const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* ig_rowptr, const int32_t* ig_col, float w_pos,
-                       float w_neg, bool logit, float* ghat, float* lcell, unsigned* ccell, hipStream_t st) {
+                       float w_neg, bool logit, const dl_node_filter* nf, float* ghat, float* lcell, unsigned* ccell, hipStream_t st) {
     const RankPlan p = rank_plan(N, d, rows, 0, dt);
     ReconArgs a = {};
     const size_t first = dt == DL_BF16 ? plane_tile<SDC, 1>(q0 / TT, 0, p.nd) : plane_tile<SDC, 3>(q0 / TT, 0, p.nd);
@@ -866,12 +880,18 @@ void score_recon_strip(const __bf16* cz, const __bf16* ch, dl_dtype dt, int N, i
     a.ig_rowptr = ig_rowptr; a.ig_col = ig_col;
     a.w_pos = w_pos; a.w_neg = w_neg;
     a.ghat = ghat; a.lcell = lcell; a.ccell = ccell;
+    a.filt = filter_args(nf);
     const unsigned grid = (unsigned)xcd_grid(p.qtiles, p.slices);
     if (logit) {                                               // the same LDS: the epilogue keeps nothing more there
-        if (dt == DL_BF16) launch_lds<rank_scan_kernel<RECON, false, 1, true>>(grid, RTHR, lds_bytes(1, true), st, a);
-        else launch_lds<rank_scan_kernel<RECON, false, 3, true>>(grid, RTHR, lds_bytes(3), st, a);
-    } else if (dt == DL_BF16) launch_lds<rank_scan_kernel<RECON, false, 1>>(grid, RTHR, lds_bytes(1, true), st, a);
-    else launch_lds<rank_scan_kernel<RECON>>(grid, RTHR, lds_bytes(3), st, a);
+        if (dt == DL_BF16)
+            launch_scan<rank_scan_kernel<RECON, false, 1, true>, rank_scan_kernel<RECON, true, 1, true>>(nf, grid, RTHR, lds_bytes(1, true), st, a);
+        else
+            launch_scan<rank_scan_kernel<RECON, false, 3, true>, rank_scan_kernel<RECON, true, 3, true>>(nf, grid, RTHR, lds_bytes(3), st, a);
+    } else if (dt == DL_BF16) {
+        launch_scan<rank_scan_kernel<RECON, false, 1>, rank_scan_kernel<RECON, true, 1>>(nf, grid, RTHR, lds_bytes(1, true), st, a);
+    } else {
+        launch_scan<rank_scan_kernel<RECON>, rank_scan_kernel<RECON, true>>(nf, grid, RTHR, lds_bytes(3), st, a);
+    }
 }
 
 // ---- dl_score_pair_logits: the DIAG pass on its own, with the plane arrays of Z and H as BOTH sides: pair i = (row a[i] as

@@ -22,6 +22,12 @@
 //   loss term = w l(s, y),  l = (1 - y) max(s, 0) + y max(-s, 0) + log1p(exp(-|s|))   (bce_logits_term, dl_common.h),
 //   d loss / d s = w (sigmoid(s) - y)                                                  (sigmoid_minus_label: no clamp factor),
 // so a saturated pair keeps its cost and its gradient; a non-finite logit gives a non-finite loss and gradient.
+// Node-group rule (dl_score_recon_filtered, dl_score_recon_logits_filtered; dl_node_filter, NULL = none): the included pairs are
+// further those the rule admits, allow[group[u]] bit group[v], which the caller gives in its symmetric (unordered) form.  A
+// denied pair behaves exactly like an ignored one, edge or not: no loss term, G^ = 0, not counted; the caller's w_pos, w_neg
+// are taken over the pairs that remain.  The scan's RECON x FILT instantiations form the rule's 128 x 128 deny mask of a
+// candidate tile into the ignored mask; strips, launches, workspace and every guarantee below are the unfiltered call's, and
+// no tile is skipped under a rule either (a tile pair denied whole still writes its zeros of G^ and is still multiplied).
 // No float atomics, no host read, everything on the caller's stream; the same bits on every call, for every block_rows and
 // for every slice count of the scan (DL_RANK_SLICES).
 #include <algorithm>
@@ -144,10 +150,10 @@ size_t score_recon_workspace_bytes(int N, int K, int d, dl_dtype dt, int block_r
 
 // logit: the scan's epilogue takes the loss term and G^ in logit space (the contract below); every launch behind it is the same.
 // dt: the type of Z and H.  DL_BF16: the tables are their own single plane (copy_rows, copy_cols), the scan and the backward
-// run in their one-plane forms, everything behind them is the same.
+// run in their one-plane forms, everything behind them is the same.  nf: the node-group rule of the scan, NULL = none.
 int score_recon(const void* Z, const void* H, int N, int K, int d, dl_dtype dt, float t, const int32_t* pos_rowptr,
                 const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg, int block_rows,
-                bool logit, double* loss, int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st) {
+                bool logit, double* loss, int64_t* counts, float* dZ, float* dH, void* ws, hipStream_t st, const dl_node_filter* nf) {
     using namespace recon;
     const Plan p = plan(N, K, d, dt, block_rows);
     const Ws w = carve(p, N, K, d, ws);
@@ -157,7 +163,7 @@ int score_recon(const void* Z, const void* H, int N, int K, int d, dl_dtype dt, 
     else dense_bwd_cols((const float*)Z, (const float*)H, N, K, d, w.zT, w.hT, st);
     for (int q0 = 0; q0 < N; q0 += p.block_rows) {
         const int rows = std::min(p.block_rows, N - q0);
-        score_recon_strip(w.zp, w.hp, dt, N, K, d, t, q0, rows, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, logit, w.ghat, w.lcell,
+        score_recon_strip(w.zp, w.hp, dt, N, K, d, t, q0, rows, pos_rowptr, pos_col, ign_rowptr, ign_col, w_pos, w_neg, logit, nf, w.ghat, w.lcell,
                           w.ccell, st);
         hipLaunchKernelGGL(row_sum_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, w.lcell, w.ccell, rows, p.nt, q0,
                            w.rowloss, w.rowcnt);

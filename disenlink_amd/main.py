@@ -108,6 +108,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--link-rule", choices=["same", "different"], default=None,
                    help="with --node-groups: --rank-eval, --global-rank-eval, --mine and --predict-links take as candidates "
                         "only links between nodes of the same / of different groups (ops.NodeFilter)")
+    p.add_argument("--recon-link-rule", action="store_true",
+                   help="with --objective recon / recon-logit and --node-groups / --link-rule: the objective itself takes only "
+                        "pairs the rule admits (a denied pair, edge or not, carries no loss and is not counted; the default "
+                        "--pos-weight is that of the admitted pairs), so training charges what the filtered evaluation considers")
     p.add_argument("--sparse-features", action="store_true",
                    help="hand the features to the model as features.SparseFeatures (scale * X + shift with X a CSR): layer 1 "
                         "of the projection and its gradient run as gathers over the non-zero entries; for binary / one-hot "
@@ -415,9 +419,14 @@ def main(argv=None):
     if (args.node_groups is None) != (args.link_rule is None):
         raise SystemExit("--node-groups FILE and --link-rule {same,different} go together")
     if args.link_rule and not (args.rank_eval or args.global_rank_eval or args.mine or args.predict_links is not None or
-                               args.predict_top is not None):
-        raise SystemExit("--link-rule restricts the candidates of --rank-eval, --global-rank-eval, --mine and --predict-links: "
-                         "give one of them")
+                               args.predict_top is not None or args.recon_link_rule):
+        raise SystemExit("--link-rule restricts the candidates of --rank-eval, --global-rank-eval, --mine and --predict-links "
+                         "(and, with --recon-link-rule, the pairs of --objective recon / recon-logit): give one of them")
+    if args.recon_link_rule and not args.link_rule:
+        raise SystemExit("--recon-link-rule puts the rule of --node-groups FILE --link-rule {same,different} on the objective: "
+                         "give them")
+    if args.recon_link_rule and args.objective not in ("recon", "recon-logit"):
+        raise SystemExit("--recon-link-rule restricts the reconstruction loss: give --objective recon or recon-logit")
     if args.objective in ("recon", "recon-logit") and (args.gpus > 1 or args.graph):
         raise SystemExit("--objective recon runs on one GPU in the eager loop only, with fp32 or bf16 tables (sharded and "
                          "graph-replayed reconstruction epochs are not implemented): drop --gpus / --graph")
@@ -473,7 +482,8 @@ def main(argv=None):
         res = run_link_prediction(model, x, prepared, epochs=args.epochs, lr=args.lr,
                                   log=None if args.quiet else print,
                                   use_graph=_use_graph(args) and args.objective not in ("recon", "recon-logit"), objective=args.objective,
-                                  pos_weight=args.pos_weight, recon_block_rows=args.recon_block_rows)
+                                  pos_weight=args.pos_weight, recon_block_rows=args.recon_block_rows,
+                                  recon_node_filter=node_filter if args.recon_link_rule else None)
         if not args.quiet:
             print("test auc:", res.test_auc)
         result.append(res.test_auc)

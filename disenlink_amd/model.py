@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from . import ops
 from .features import SparseFeatures
 from .graph import Graph, PairList
+from .recon import _own_filter
 
 
 TopLinks = namedtuple("TopLinks", ["index", "logit", "prob"])
@@ -442,7 +443,7 @@ class Disentangle(nn.Module):
         H, logit = ops.HotPathPairLogits.apply(Z, graph, pairs, float(self.beta), float(self.temperature), self.table_dtype)
         return H.view(H.shape[0], -1), logit, ops.PairBCELogits.apply(logit, label, weight)
 
-    def forward_recon_loss(self, x, graph: Graph, ignore=None, pos_weight=None, block_rows=None):
+    def forward_recon_loss(self, x, graph: Graph, ignore=None, pos_weight=None, block_rows=None, node_filter=None):
         """(emb [N,K*d], loss): the whole-graph reconstruction loss (ops.score_recon_loss) of project -> RouteAggregate ->
         ops.ReconLoss (a bf16 module, ``table_dtype=torch.bfloat16``: project -> ops.HotPathRecon, one node that routes,
         aggregates and scores on the bf16 tables the module is evaluated, ranked and mined on) — every pair of nodes that is not an edge of ``graph`` is a negative, the edges are up-weighted by
@@ -450,20 +451,24 @@ class Disentangle(nn.Module):
         with nothing of size N x N in memory.  ``graph``: the training graph the model routes over; its edges are the
         positives.  ``ignore`` may be a prepared ``ops.recon_sets(graph, ignore, N, device)``, which then supplies both
         sets and skips the normalisation (and its host read) per call.  No tile is skipped: a zero gradient against an
-        overflowed exp gives NaN, as with ``link_pred_backward="dense"``.  d <= 128; anything else raises."""
-        return self._forward_recon(x, graph, ignore, pos_weight, block_rows, ops.ReconLoss, ops.HotPathRecon)
+        overflowed exp gives NaN, as with ``link_pred_backward="dense"``.  d <= 128; anything else raises.
+        ``node_filter`` (an ``ops.NodeFilter``): only pairs its unordered rule admits carry loss — a denied pair, edge or not,
+        is an ignored one, and the default ``pos_weight`` is that of the admitted pairs; it goes into ``ops.recon_sets`` where
+        ``ignore`` is not already prepared sets, which carry their own (another beside them raises ValueError)."""
+        return self._forward_recon(x, graph, ignore, pos_weight, block_rows, ops.ReconLoss, ops.HotPathRecon, node_filter)
 
-    def forward_recon_logits_loss(self, x, graph: Graph, ignore=None, pos_weight=None, block_rows=None):
+    def forward_recon_logits_loss(self, x, graph: Graph, ignore=None, pos_weight=None, block_rows=None, node_filter=None):
         """(emb [N,K*d], loss): ``forward_recon_loss`` in LOGIT space (ops.score_recon_logits_loss), with its arguments and its
         dispatch — fp32: RouteAggregate + ops.ReconLogitsLoss, bf16: ops.HotPathReconLogits.  A pair past the saturation of
         the fp32 sigmoid keeps its cost and its gradient (a non-edge scored at +20 is pushed back; the probability form
         charges it 100 w with gradient exactly 0); an overflowed exp is NOT cured: loss and gradients are then non-finite.
         The device counts stand in ``ops.ReconLogitsLoss.last_counts``."""
-        return self._forward_recon(x, graph, ignore, pos_weight, block_rows, ops.ReconLogitsLoss, ops.HotPathReconLogits)
+        return self._forward_recon(x, graph, ignore, pos_weight, block_rows, ops.ReconLogitsLoss, ops.HotPathReconLogits, node_filter)
 
-    def _forward_recon(self, x, graph, ignore, pos_weight, block_rows, loss_node, hot_node):
+    def _forward_recon(self, x, graph, ignore, pos_weight, block_rows, loss_node, hot_node, node_filter=None):
+        _own_filter(ignore, node_filter)                               # beside prepared sets: their own, or none
         Z = self.project(x)
-        sets = ignore if isinstance(ignore, ops.ReconSets) else ops.recon_sets(graph, ignore, Z.shape[0], Z.device)
+        sets = ignore if isinstance(ignore, ops.ReconSets) else ops.recon_sets(graph, ignore, Z.shape[0], Z.device, node_filter)
         if self.table_dtype == torch.bfloat16:
             H, loss = hot_node.apply(Z, graph, sets, float(self.beta), float(self.temperature), self.table_dtype,
                                      pos_weight, block_rows)

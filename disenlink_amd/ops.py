@@ -527,7 +527,8 @@ class HotPathRecon(torch.autograd.Function):
     happens inside (so dZ comes back in fp32), H is routed and aggregated from THAT table, and ``score_recon_loss`` has the
     gradients of the loss with respect to both tables ready when the forward returns.  The backward scales them by the
     incoming d/dloss, adds a gradient arriving on ``emb`` to dH and continues into aggregation and routing.  ``sets``: a
-    prepared ``recon_sets(...)``; the device counts stand in ``ReconLoss.last_counts``."""
+    prepared ``recon_sets(...)``, whose node filter, if it has one, is the rule of the loss; the device counts stand in
+    ``ReconLoss.last_counts``."""
     _loss, _counts = staticmethod(score_recon_loss), ReconLoss
 
     @classmethod

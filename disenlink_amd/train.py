@@ -192,7 +192,7 @@ def _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, es
 
 def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 2000, lr: float = 1e-4,
                         patience: int = 200, weight_decay: float = 5e-4, log=None, use_graph: bool = False,
-                        objective: str = "pairs", pos_weight=None, recon_block_rows=None) -> RunResult:
+                        objective: str = "pairs", pos_weight=None, recon_block_rows=None, recon_node_filter=None) -> RunResult:
     """``use_graph=True`` (GPU only): replay each epoch from a captured HIP graph (same arithmetic, same
     schedule; only the host-side launch cost disappears).
     ``objective``: "pairs" (the default: the reference's loss on the sampled pair list), "pairs-logit" — the same pair list
@@ -203,9 +203,14 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     by ``pos_weight``, default n_neg / n_pos, all validation and test pairs ignored, by strips of ``recon_block_rows``
     rows), in the eager loop with the bookkeeping on the host; validation and test AUC as ever — or "recon-logit": the same
     loop on ``model.forward_recon_logits_loss`` (the reconstruction loss in logit space: a saturated pair keeps its cost and
-    its gradient), validation and test AUC counted on ``model.forward_pair_logits``; GPU only, refusals as for "recon"."""
+    its gradient), validation and test AUC counted on ``model.forward_pair_logits``; GPU only, refusals as for "recon".
+    ``recon_node_filter`` (an ``ops.NodeFilter``, with "recon" / "recon-logit" only; any other objective raises ValueError):
+    the reconstruction loss takes only pairs the filter's unordered rule admits (``ops.recon_sets(..., node_filter=...)``)."""
     if objective not in ("pairs", "pairs-logit", "recon", "recon-logit"):
         raise ValueError(f"objective must be \"pairs\", \"pairs-logit\", \"recon\" or \"recon-logit\", got {objective!r}")
+    if recon_node_filter is not None and objective not in ("recon", "recon-logit"):
+        raise ValueError(f"recon_node_filter restricts the reconstruction loss: objective=\"recon\" or \"recon-logit\", "
+                         f"got {objective!r}")
     logit = objective == "pairs-logit"
     if logit:
         _check_logit_run(model, run)
@@ -222,7 +227,7 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
         if objective == "recon-logit" and not x.is_cuda:
             raise ValueError("objective=\"recon-logit\" runs on the GPU only (there is no CPU form of the reconstruction loss)")
         return _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, recon_block_rows,
-                          objective == "recon-logit")
+                          objective == "recon-logit", recon_node_filter)
     if use_graph and x.is_cuda:
         return _run_graphed(model, x, run, epochs, lr, patience, weight_decay, log, logit)
     # same update rule as the reference's Adam (main_disentangled.py:150); on the GPU torch's single-kernel
@@ -294,12 +299,14 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     return res
 
 
-def _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, block_rows, logit: bool = False) -> RunResult:
+def _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weight, block_rows, logit: bool = False,
+               node_filter=None) -> RunResult:
     """run_link_prediction's eager loop with the reconstruction loss: the loss of ``model.forward_recon_loss`` over the
     training graph with every validation and test pair ignored; the validation AUC from ``forward_pairs`` under no_grad on
     the weights before the step (:202-204); one host read per epoch, which also carries the device's counts of the pairs
     the scan saw — compared with the host's, a mismatch raises.  ``logit``: the loss of ``forward_recon_logits_loss`` and the
-    AUCs on ``forward_pair_logits`` (AucPlan / auc_tie_avg take any score; logits do not tie at probability 1)."""
+    AUCs on ``forward_pair_logits`` (AucPlan / auc_tie_avg take any score; logits do not tie at probability 1).
+    ``node_filter``: the node-group rule of the loss; it goes into the prepared sets, whose counts the check compares."""
     from . import ops
     recon_loss = model.forward_recon_logits_loss if logit else model.forward_recon_loss
     pair_scores = model.forward_pair_logits if logit else model.forward_pairs
@@ -310,7 +317,7 @@ def _run_recon(model, x, run, epochs, lr, patience, weight_decay, log, pos_weigh
     b = run.n_pos + run.n_neg
     tv, te = run.train_val_pairs, run.test_pairs
     held = (torch.cat([tv.pu[b:], te.pu]).long(), torch.cat([tv.pv[b:], te.pv]).long())
-    sets = ops.recon_sets(run.graph, held, run.graph.n_nodes, x.device)
+    sets = ops.recon_sets(run.graph, held, run.graph.n_nodes, x.device, node_filter)
     opt = _make_adam(model, bool(x.is_cuda), lr, weight_decay)
     snapshot = getattr(model, "snapshot_state", None) or (lambda: deepcopy(model.state_dict()))
     best_auc, stale, weights = 0.0, 0, snapshot()

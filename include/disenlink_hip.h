@@ -780,6 +780,28 @@ int dl_score_pair_ranks_filtered(const float* Z, const float* H, int N, int K, i
                                  unsigned long long* equal, unsigned long long* n_candidates, void* ws, size_t ws_bytes,
                                  void* stream, const dl_node_filter* filter);
 
+/* The rule on the one all-pairs pass that trains, the whole-graph reconstruction loss: the arguments of dl_score_recon_dtype
+ * and dl_score_recon_logits followed by the filter.  It is an unordered scan: allow MUST be symmetric.  Included pairs are then
+ * the unordered {u, v} with u != v, outside the ignored set, whose bit group[v] of allow[group[u]] is set.  A pair the rule
+ * denies behaves exactly like an ignored one, whether it is a positive or not: no loss term, G^ = 0, not counted in
+ * counts_out.  The caller takes w_pos = pos_weight / C and w_neg = 1 / C over the pairs that remain (C = positives the rule
+ * admits + allowed pairs - ignored allowed pairs - those positives); with nothing included the loss is 0, the gradients are
+ * zero and counts_out is (0, 0).  The rule's deny words of a candidate tile go into the scan's ignored mask (768 more bytes of
+ * LDS); form and workspace are the unfiltered entries', no tile is skipped (a tile pair the rule denies whole still writes its
+ * zeros of G^ and keeps the "zero against E = inf" NaN), and the bits are those of the unfiltered entry given an ignored set
+ * that also lists every denied pair: the same on every call, for every block_rows and every DL_RANK_SLICES, and under the
+ * DL_BF16 bits rule.  filter == NULL: the launches and bits of the unfiltered entry.  n_groups outside 1..64 or a NULL member
+ * fails with DL_E_ARG before any launch.  No float atomics, no allocation, no synchronisation, no host read. */
+int dl_score_recon_filtered(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* pos_rowptr,
+                            const int32_t* pos_col, const int32_t* ign_rowptr, const int32_t* ign_col, float w_pos, float w_neg,
+                            int block_rows, double* loss_out, int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes,
+                            void* stream, const dl_node_filter* filter);
+int dl_score_recon_logits_filtered(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                                   const int32_t* pos_rowptr, const int32_t* pos_col, const int32_t* ign_rowptr,
+                                   const int32_t* ign_col, float w_pos, float w_neg, int block_rows, double* loss_out,
+                                   int64_t* counts_out, float* dZ, float* dH, void* ws, size_t ws_bytes, void* stream,
+                                   const dl_node_filter* filter);
+
 /* The thresholded link graph (an extension; the reference has no counterpart): EVERY unordered pair whose logit reaches a
  * floor, as a symmetric CSR over all N nodes, with nothing of size N x N in memory and no cap on the number of pairs.
  * Eligible: exactly dl_score_mine's rule without m — u < v < N, v not among the columns of row u of the exclusion CSR
