@@ -104,7 +104,10 @@ __global__ __launch_bounds__(BLOCK, (TrainWaves<K, D, FUSED>::value)) void score
                 const float logit = group_allreduce_sum<G>(term);
                 const float p = LOGIT ? logit : sigmoid_ref(logit);    // the stored score
                 const float yy = __shfl(my_y, idx, DL_WAVE), wsg = __shfl(my_w, idx, DL_WAVE);  // w = 0 past the segment end
-                const float ww = fabsf(wsg);                       // a negative sign (per-entry weights only) = the pair's other entry writes prob
+                // per-entry weights (w == NULL): a negative sign = the pair's other entry writes prob, the weight is |.|;
+                // a caller's w array is used signed and every entry writes (dl_train.h, the D = 64 kernel)
+                const unsigned sign_mask = w == nullptr ? 0x80000000u : 0u;
+                const float ww = __uint_as_float(__float_as_uint(wsg) & ~sign_mask);
                 const int qq = __shfl(my_q, idx, DL_WAVE);
                 // dl_pair_bce's gradient times the sigmoid backward: w (p - y) / max(r, 1e-12) * r with r = p (1 - p) — i.e.
                 // w (p - y) itself unless r underflows the clamp (saturated scores: r = 0 gives exactly 0), without the division
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(BLOCK, (TrainWaves<K, D, FUSED>::value)) void score
                     const float r = p * (1.0f - p);
                     gl = ww == 0.0f ? 0.0f : ww * (p - yy) * (r >= 1e-12f ? 1.0f : r * 1e12f);
                 }
-                if (base + grp < si.end && c == 0 && !(__float_as_uint(wsg) >> 31)) prob_out[qq] = p;
+                if (base + grp < si.end && c == 0 && !(__float_as_uint(wsg) & sign_mask)) prob_out[qq] = p;
             }
 #pragma unroll
             for (int i = 0; i < VPL; ++i) {

@@ -102,6 +102,7 @@ __global__ __launch_bounds__(BLOCK, (UREG ? 3 : 4)) void score_train_wave_kernel
                 mine[ROW / 4 + j * 64 + lane] = b4;
             }
         }
+        const unsigned sign_mask = w == nullptr ? 0x80000000u : 0u;   // entry_yw: the weight's sign is the writer flag
         int my_col = si.grow;
         {
             int my_q = 0;
@@ -174,7 +175,10 @@ __global__ __launch_bounds__(BLOCK, (UREG ? 3 : 4)) void score_train_wave_kernel
             const float p = LOGIT ? logit : sigmoid_ref(logit);    // the stored score
             const int idx = step * U + (i & 3);
             const float yy = ent_y[wave][idx & 63], wsg = ent_w[wave][idx & 63];
-            const float ww = fabsf(wsg);                           // a negative sign (per-entry weights only) = the pair's other entry writes prob
+            // per-entry weights (w == NULL) carry the writer flag in their sign: a negative sign = the pair's other entry
+            // writes prob, the weight is |.|.  A caller's w array is any real weight: used signed, and every entry writes
+            // (both entries of a pair form the same bits).  sign_mask is wave-uniform: 0 for a caller's array
+            const float ww = __uint_as_float(__float_as_uint(wsg) & ~sign_mask);
             const int qq = ent_q[wave][idx & 63];
             float gl;                                              // the gradient coefficient, valid in lanes 8..15
             if constexpr (LOGIT) {
@@ -185,7 +189,7 @@ __global__ __launch_bounds__(BLOCK, (UREG ? 3 : 4)) void score_train_wave_kernel
                 const float pr = p * (1.0f - p);
                 gl = ww == 0.0f ? 0.0f : ww * (p - yy) * (pr >= 1e-12f ? 1.0f : pr * 1e12f);
             }
-            if (lane >= 8 && lane < 12 && si.beg + idx < si.end && !(__float_as_uint(wsg) >> 31)) prob_out[qq] = p;
+            if (lane >= 8 && lane < 12 && si.beg + idx < si.end && !(__float_as_uint(wsg) & sign_mask)) prob_out[qq] = p;
             // the two coefficients of (entry, chunk), formed ONCE in the lane that holds its exponent / its product and
             // handed to the row afterwards: lanes 0..7: gl e^., lanes 8..15: gl (h.h) e^. / t.  0 * inf must stay 0 (an
             // overflowed exponent saturates p, so its gl is exactly 0): the factors are clamped to the largest finite value
@@ -375,6 +379,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void score_train_wide_kernel(
             mine[j * DL_WAVE + lane] = zu[j * DL_WAVE + lane];       // read back by this lane only: no barrier needed
             mine[(NJ + j) * DL_WAVE + lane] = hu[j * DL_WAVE + lane];
         }
+        const unsigned sign_mask = w == nullptr ? 0x80000000u : 0u;   // entry_yw: the weight's sign is the writer flag
         int my_col = si.grow;
         {
             int my_q = 0;
@@ -440,7 +445,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void score_train_wide_kernel(
             const float p = LOGIT ? logit : sigmoid_ref(logit);    // the stored score
             const int idx = step * U + (((c & (G / 2 - 1)) / DUPL) & (U - 1));
             const float yy = ent_y[wave][idx & 63], wsg = ent_w[wave][idx & 63];
-            const float ww = fabsf(wsg);                           // (sign: see the D = 64 kernel)
+            const float ww = __uint_as_float(__float_as_uint(wsg) & ~sign_mask);   // (sign: see the D = 64 kernel)
             const int qq = ent_q[wave][idx & 63];
             float gl;                                              // the gradient coefficient, valid above G/2
             if constexpr (LOGIT) {
@@ -449,7 +454,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void score_train_wide_kernel(
                 const float pr = p * (1.0f - p);
                 gl = ww == 0.0f ? 0.0f : ww * (p - yy) * (pr >= 1e-12f ? 1.0f : pr * 1e12f);
             }
-            if (lane >= G / 2 && lane < G / 2 + U * DUPL && (lane & (DUPL - 1)) == 0 && si.beg + idx < si.end && !(__float_as_uint(wsg) >> 31)) prob_out[qq] = p;
+            if (lane >= G / 2 && lane < G / 2 + U * DUPL && (lane & (DUPL - 1)) == 0 && si.beg + idx < si.end && !(__float_as_uint(wsg) & sign_mask)) prob_out[qq] = p;
             const float exc = fminf(ex, 3.402823466e38f);          // 0 * inf must stay 0 (see the D = 64 kernel)
             const float ttc = __builtin_amdgcn_fmed3f(T1 ? ttv : ttv / t, -3.402823466e38f, 3.402823466e38f);
             const float gl_partner = xor_lane<G / 2>(gl);           // OUTSIDE the select (a DPP move under a divergent branch reads 0)

@@ -1039,6 +1039,8 @@ class PairList(_PlanOwner):
     _yw: torch.Tensor | None = field(default=None, repr=False)      # per-entry (label, signed weight): bind_labels
     _yw_key: tuple | None = field(default=None, repr=False)
     _yw_seen: tuple | None = field(default=None, repr=False)
+    _yw_signed: tuple | None = field(default=None, repr=False)     # the (label, weight) found to hold a sign bit: not bound
+    static_labels: bool = False                                   # the caller's word that label / weight never change: bind_labels
     _ws_need: dict = field(default_factory=dict, repr=False)          # (K, d) -> bytes: workspace_bytes
 
     def __post_init__(self):
@@ -1051,8 +1053,24 @@ class PairList(_PlanOwner):
         are fixed for a run).  Keyed on the tensors' identity and version counter; built the second time the same pair
         of tensor OBJECTS is seen, so a caller that draws new labels for every step never pays for it — and never gets the
         stream of an earlier tensor that lived at the same address.  Writes that bypass the
-        version counter (``.data``, raw kernels) are not seen: call ``unbind_labels()`` after such a write."""
-        if os.environ.get("DL_ENTRY_LABELS", "1") == "0" or label.is_inference() or weight.is_inference():   # (A/B runs; no version counter)
+        version counter (``.data``, raw kernels) are not seen: call ``unbind_labels()`` after such a write.
+
+        Signed weights.  The weight is any real number, and the kernels read a caller's array signed; the stream has no
+        room for that, because the sign of ITS weight is the writer flag.  Of the two ways out — carrying the flag elsewhere
+        (a third stream column, or the sign of the label, which soft labels leave free but which a -0.0 label would not)
+        or not binding such a tensor — the second is taken: a weight tensor that holds a set sign bit anywhere (negative,
+        -0.0, a NaN with the bit set) is never bound and keeps the gathers, where every entry writes prob and the weight
+        keeps its sign.  That costs one host read of one flag at bind time (the second sight only, never per step) and
+        leaves the stream, its 8 bytes per entry and the kernels' fast path for the weights training loops have: w >= 0.
+
+        Captured steps.  While the current stream is capturing, nothing is bound and the gathers are recorded: a replay
+        then reads what ``label`` and ``weight`` hold at replay time, which is how a captured graph is fed.  A caller
+        whose labels never change during the run says so with ``static_labels = True`` (train._graphed_epoch does): the
+        stream its warm-up calls bound is then recorded instead, and a later in-place write is the caller's breach.  No
+        stream is ever BUILT during a capture (that takes a host read)."""
+        capturing = label.is_cuda and torch.cuda.is_current_stream_capturing()
+        if os.environ.get("DL_ENTRY_LABELS", "1") == "0" or label.is_inference() or weight.is_inference() \
+                or (capturing and not self.static_labels):          # (A/B runs; no version counter; a replay reads live labels)
             self.unbind_labels()
             return
         # identity = the tensor OBJECTS (weak references) and their version counters: an address can be handed to a new
@@ -1064,6 +1082,13 @@ class PairList(_PlanOwner):
             key = (weakref.ref(label), weakref.ref(weight), label._version, weight._version)
             if not same(self._yw_seen):                             # first sight: keep the gathers, remember the pair
                 self._yw_seen = key
+                self.unbind_labels()
+                return
+            # a capture in progress (no host read allowed), or a set sign bit anywhere (one host read per tensor version,
+            # remembered in _yw_signed): the gathers
+            if capturing or same(self._yw_signed) or bool(torch.signbit(weight).any()):
+                if not capturing:
+                    self._yw_signed = key
                 self.unbind_labels()
                 return
             q = self.inc_pair.long()

@@ -137,6 +137,9 @@ def _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, es
     val_plan = AucPlan(run.label_val)
     seed = torch.ones((), dtype=torch.float32, device=x.device)
     es = es_factory(val_plan) if es_factory is not None else None   # early_stop.DeviceEarlyStop or None
+    # label_all / weight_all are fixed for the run: said out loud, so that the capture records the per-entry stream the
+    # warm-up epochs bind (PairList.bind_labels; without the declaration a captured step gathers live labels)
+    run.train_val_pairs.static_labels = True
 
     def epoch():
         prob, loss = _scores_and_loss(model, x, run, label_all, weight_all, logit)

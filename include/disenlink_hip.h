@@ -1086,7 +1086,14 @@ int dl_score_pairs_bwd(const void* Z, const void* H, int K, int d, dl_dtype dtyp
  * just gathered: the partner rows are gathered once per direction (2 x n_pairs x 2 rows) instead of once for the
  * forward plus twice for the backward.  Writes prob[q] for every pair of the plan (for the loss VALUE — call
  * dl_pair_bce on it — and for the validation AUC) and dZ, dH for the plan's rows = d(sum_q w BCE(prob, y)) / d(Z, H).
- * Pairs with w = 0 (validation pairs riding along) contribute exactly nothing to the gradients.
+ * y is any label in [0, 1] and w ANY real weight, negative ones included: the gradients are those of sum_q w BCE with the
+ * weight's sign, as dl_score_pairs_fwd / dl_pair_bce / dl_score_pairs_bwd give them, and prob[q] is written whatever w[q]
+ * is (every entry of a pair writes it: both form the same bits).  Pairs with w = +-0.0 (validation pairs riding along)
+ * contribute exactly nothing to the gradients and are still scored.  A NaN or infinite w[q] reaches the rows of that pair's
+ * two endpoints and no other row.  The sign convention of dl_pair_incidence.entry_yw (a negative sign = "the pair's
+ * other entry writes prob", the weight is the magnitude) belongs to that stream ALONE: it is read when inc->entry_yw is
+ * set, in which case y / w are not read, and it cannot carry a weight with a set sign bit — whoever builds the stream
+ * builds it for weights >= +0.0 only and leaves entry_yw NULL otherwise (PairList.bind_labels does).
  * Tuned (K, d) only: dl_score_pairs_train_supported; otherwise use dl_score_pairs_fwd / dl_pair_bce / _bwd. */
 int dl_score_pairs_train_supported(const dl_pair_incidence* inc, int K, int d, dl_dtype dtype);
 int dl_score_pairs_train(const void* Z, const void* H, int K, int d, dl_dtype dtype, float t,
@@ -1119,8 +1126,8 @@ int dl_score_pairs_logits_bwd(const void* Z, const void* H, int K, int d, dl_dty
                               const dl_pair_incidence* inc, const float* g_logit,
                               float* dZ, float* dH, void* ws, size_t ws_bytes, void* stream);
 
-/* dl_score_pairs_train in logit space: one pass that writes logit[q] (same writer rule: the entry whose weight has a clear
- * sign bit) and dZ, dH = d(sum_q w BCE-with-logits(x, y)) / d(Z, H) with gl = w (sigma(x) - y), gl = 0 for w == 0, and NO
+/* dl_score_pairs_train in logit space: one pass that writes logit[q] (for every pair of the plan, under the same rules: any
+ * real w, signed; the sign-bit writer flag on the entry_yw stream only) and dZ, dH = d(sum_q w BCE-with-logits(x, y)) / d(Z, H) with gl = w (sigma(x) - y), gl = 0 for w == 0, and NO
  * p (1 - p) clamp factor; from gl on it is dl_score_pairs_train (coefficient clamps, accumulation order, partial slots;
  * entry_yw works unchanged).  Same shape rule as dl_score_pairs_train_supported. */
 int dl_score_pairs_train_logits_supported(const dl_pair_incidence* inc, int K, int d, dl_dtype dtype);

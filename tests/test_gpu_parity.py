@@ -1452,7 +1452,11 @@ def test_graph_replayed_epochs_follow_the_eager_trajectory(name, K, d, nhid, epo
         torch.manual_seed(0)
         model = Disentangle(sg.n_feat, nhid, d, nfactor=K, beta=0.6, t=1).to(DEV)
         out[use_graph] = run_link_prediction(model, x, run, epochs=epochs, lr=1e-3, use_graph=use_graph)
-        junk = [torch.randn(1 << 18, device=DEV) for _ in range(8)]      # churn the allocator between the two runs
+        if use_graph:
+            # the loop declares its labels static, so the capture recorded the per-entry stream of the warm-up epochs: a
+            # capture without the declaration unbinds (PairList.bind_labels) and would leave _yw None here
+            assert run.train_val_pairs.static_labels and run.train_val_pairs._yw is not None
+        junk =[torch.randn(1 << 18, device=DEV) for _ in range(8)]      # churn the allocator between the two runs
         del junk
     np.testing.assert_allclose(out[True].losses, out[False].losses, rtol=2e-3)
     np.testing.assert_allclose(out[True].val_aucs, out[False].val_aucs, atol=2e-3)
@@ -1930,6 +1934,56 @@ def test_compiled_binding_and_python_operator_agree_at_temperature_2_and_with_a_
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("space", ["prob", "logit"])
+def test_compiled_binding_and_python_operator_agree_on_soft_labels_and_signed_weights(space, monkeypatch):
+    """Disentangle.forward_pairs_loss / forward_pair_logits_loss on soft labels (exact 0 and 1 among them) and signed weights
+    (negative ones, +0.0 and -0.0: tests/label_weight_ref.py) through the compiled node and through the Python operators, three
+    steps on the same tensors each (the sights at which a stream would bind): the scores and every parameter gradient bit for
+    bit, every score written."""
+    import sys, os
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import label_weight_ref as lw
+    import ref64
+    from disenlink_amd import native
+    from disenlink_amd.graph import PairList
+    from disenlink_amd.model import Disentangle
+    st = ref64.structure()
+    G = st.graph.to(DEV)
+    P = st.pu.numel()
+    y, w = lw.labels_weights(("soft", "signed"), P, 4242)
+    label, weight = y.to(DEV), w.to(DEV)
+    x = torch.randn(ref64.N_NODES, 24, generator=torch.Generator().manual_seed(3)).to(DEV) * 0.5
+    monkeypatch.setenv("DL_ONE_PASS_SCORER", "1")
+    res = {}
+    try:
+        for mode in ("1", "0"):
+            monkeypatch.setenv("DL_NATIVE_OPS", mode)
+            native._state["loaded"] = None                            # re-read DL_NATIVE_OPS
+            assert native.available() == (mode == "1")
+            torch.manual_seed(0)
+            model = Disentangle(24, 32, 64, nfactor=8, beta=0.6, t=2).to(DEV)
+            pairs = PairList.build(st.pu.to(DEV), st.pv.to(DEV), ref64.N_NODES)
+            steps = []
+            for _sight in range(3):
+                model.zero_grad(set_to_none=True)
+                fwd = model.forward_pairs_loss if space == "prob" else model.forward_pair_logits_loss
+                _emb, score, loss = fwd(x, G, pairs, label, weight)
+                loss.backward()
+                steps.append([score.detach().clone(), loss.detach().clone()] + [p.grad.clone() for p in model.parameters()])
+            assert pairs._yw is None                                  # signed weights are never bound
+            res[mode] = steps
+    finally:
+        monkeypatch.delenv("DL_NATIVE_OPS")
+        native._state["loaded"] = None
+    for a, b in zip(res["1"], res["0"]):
+        assert bool(torch.isfinite(a[0]).all()) and len(a) == len(b) > 4
+        for i, (u_, v_) in enumerate(zip(a, b)):
+            assert torch.equal(u_, v_), (space, i, float((u_ - v_).abs().max()))
+    for a in res["1"][1:]:
+        assert all(torch.equal(u_, v_) for u_, v_ in zip(a, res["1"][0]))          # ... and the three sights agree
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("native_ops", ["1", "0"])
 @pytest.mark.parametrize("fixture,shape", [("traj_k8_d64_t2", (8, 64, 2)), ("traj_k16_d128", (16, 128, 1))])
 def test_pair_list_training_with_the_one_pass_scorer_follows_the_reference_trajectory_at_t2(fixture, shape, native_ops,
@@ -2355,6 +2409,36 @@ def test_per_entry_labels_give_the_same_bits_and_every_probability(K, d, dtype, 
             label.add_(0.0)                                                       # an in-place write bumps the version: the old binding must go
             got3 = ops.score_pairs_train(Zt, H, pl, t, label, weight)
             assert all(torch.equal(a[lo:hi], b[lo:hi]) for a, b in zip(ref[1:], got3[1:]))
+    # SIGNED weights beside them, over the same row shards: a third of the live weights negated, half of the zeros -0.0.  The
+    # weight is any real number (the sign convention belongs to the stream alone), so such a tensor is never bound, every
+    # entry writes its pair's probability — each pair whose first endpoint lies in the shard has it written by that shard —
+    # and the shard's gradient rows are the unsharded bits.
+    srng = np.random.default_rng(991 + K)
+    signed = weight.clone()
+    live, dead = torch.nonzero(weight != 0)[:, 0].cpu().numpy(), torch.nonzero(weight == 0)[:, 0].cpu().numpy()
+    signed[torch.from_numpy(srng.choice(live, live.size // 3, replace=False)).to(DEV)] *= -1.0
+    signed[torch.from_numpy(srng.choice(dead, dead.size // 2, replace=False)).to(DEV)] = -0.0
+    assert int((signed < 0).sum()) > 2000 and int(torch.signbit(signed[weight == 0]).sum()) == 250
+    for t in (1.0, 2.0):
+        whole = None
+        for rng_ in (None, (0, 4), (4, 301), (301, N)):
+            pl = PairList.build(tpu, tpv, N, row_range=rng_, build_by_u=False, row_bytes=K * d * wb)
+            monkeypatch.setenv("DL_ENTRY_LABELS", "0")
+            ref = ops.score_pairs_train(Zt, H, pl, t, label, signed)
+            monkeypatch.setenv("DL_ENTRY_LABELS", "1")
+            first = ops.score_pairs_train(Zt, H, pl, t, label, signed)
+            got = ops.score_pairs_train(Zt, H, pl, t, label, signed)
+            assert pl._yw is None                                                  # a set sign bit: the gathers, at every sight
+            whole = ref if rng_ is None else whole
+            lo, hi = (0, N) if rng_ is None else rng_
+            mine = torch.from_numpy((pu >= lo) & (pu < hi)).to(DEV)
+            for a, b, c, w_ in zip(ref[1:], first[1:], got[1:], whole[1:]):
+                assert torch.equal(a[lo:hi], b[lo:hi]) and torch.equal(a[lo:hi], c[lo:hi]) and torch.equal(a[lo:hi], w_[lo:hi]), (K, d, t, rng_)
+            for out_ in (ref, first, got):
+                assert torch.equal(out_[0][mine], whole[0][mine]) and not bool(torch.isnan(out_[0][mine]).any()), (K, d, t, rng_)
+        # ... and it is the gradient of sum w BCE, sign and all: linear in w, so w and -w give opposite gradients
+        neg = ops.score_pairs_train(Zt, H, PairList.build(tpu, tpv, N, build_by_u=False, row_bytes=K * d * wb), t, label, -signed)
+        assert torch.equal(neg[0], whole[0]) and torch.equal(neg[1], -whole[1]) and torch.equal(neg[2], -whole[2]), (K, d, t)
     # Labels made AFRESH for every step (a new tensor object each time, which the allocator places at the address of the one
     # just freed, version 0 again): identity is the object, not the address — no step may see an earlier step's stream.
     pl = PairList.build(tpu, tpv, N, build_by_u=False, row_bytes=K * d * wb)
