@@ -166,7 +166,13 @@ EXPORTS = {
     "dl_route_aggregate_bwd_phase2": (_i, [_G, _P, _i, _i, _i, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _z, _P]),
     "dl_route_aggregate_bwd": (_i, [_G, _P, _i, _i, _i, _f, _f, _P, _P, _P, _P, _P, _i, _P, _z, _P]),
     "dl_route_aggregate_bwd_scaled": (_i, [_G, _P, _i, _i, _i, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P, _z, _P]),
+    # fresh training negatives every epoch: the sampler and the trainer over sampled partners
+    "dl_sample_negatives": (_i, [_P, _i, _i, _i, _P, _P, C.c_uint64, _P, _i, _P, _P, _P]),
 }
+_SAMPLED = [_P, _P, _i, _i, _i, _i, _f, _P, _i, _i, _P, _P, _P, _P, _f, _P, _P, _P, _P, _i, _P, _z, _P]
+for _name in ("dl_score_sampled_train", "dl_score_sampled_train_logits"):
+    EXPORTS.update({_name + "_supported": (_i, [_i, _i, _i]), _name + "_workspace_bytes": (_z, [_i] * 4),
+                    _name: (_i, _SAMPLED)})
 
 
 def _scan_rows(name: str, res, codes: list, at: int, filtered: bool = False) -> dict:

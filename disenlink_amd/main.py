@@ -48,6 +48,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--data-file", type=str, default=None, help="binary dataset written by datasets.save_binary")
     p.add_argument("--synthetic", action="store_true", help="seeded synthetic stand-in of --dataset")
     p.add_argument("--table-dtype", choices=["f32", "bf16"], default="f32")
+    p.add_argument("--resample-negatives", action="store_true",
+                   help="with --objective pairs / pairs-logit: draw the training negatives anew every epoch on the device "
+                        "(m per training edge row, never an edge row of the dataset; duplicates kept) instead of training on "
+                        "the split's fixed sample; one GPU, eager loop, fp32 tables")
+    p.add_argument("--resample-seed", type=int, default=0, help="seed of --resample-negatives (the draw is a pure function of "
+                                                                "seed, epoch and entry)")
     p.add_argument("--objective", choices=["pairs", "pairs-logit", "recon", "recon-logit"], default="pairs",
                    help="the training loss: pairs = the reference's BCE on m sampled negatives per edge; pairs-logit = the same "
                         "pairs with the BCE taken of the LOGITS (a saturated pair keeps its gradient, and the validation / test "
@@ -430,6 +436,12 @@ def main(argv=None):
     if args.objective in ("recon", "recon-logit") and (args.gpus > 1 or args.graph):
         raise SystemExit("--objective recon runs on one GPU in the eager loop only, with fp32 or bf16 tables (sharded and "
                          "graph-replayed reconstruction epochs are not implemented): drop --gpus / --graph")
+    if args.resample_negatives:
+        if args.objective not in ("pairs", "pairs-logit"):
+            raise SystemExit("--resample-negatives goes with --objective pairs or pairs-logit")
+        if args.gpus > 1 or args.graph or args.table_dtype == "bf16":
+            raise SystemExit("--resample-negatives runs on one GPU in the eager loop with fp32 tables (the sharded step, HIP-graph "
+                             "replay of a resampled epoch and bf16 tables are not implemented): drop --gpus / --graph / bf16")
     if args.objective == "pairs-logit" and args.gpus > 1:
         raise SystemExit("--objective pairs-logit runs on one GPU only (the sharded step has no logit-space form): drop --gpus")
     if args.gpus > 1:
@@ -475,16 +487,21 @@ def main(argv=None):
         if not args.quiet:
             print("run:", run)
         split = make_link_split(ds.src, ds.dst, ds.n_nodes, m=args.m, seed=args.seed + run)
-        prepared = prepare_run(split, device, row_bytes=args.nfactor * args.nembed * (2 if args.table_dtype == "bf16" else 4))
+        prepared = prepare_run(split, device, row_bytes=args.nfactor * args.nembed * (2 if args.table_dtype == "bf16" else 4),
+                               resample_negatives=args.resample_negatives)
         torch.manual_seed(args.seed + run)
         model = Disentangle(x.shape[1], args.nhidden, args.nembed, nfactor=args.nfactor, beta=args.beta,
                             t=args.temperature, table_dtype=tdt).to(device)
         res = run_link_prediction(model, x, prepared, epochs=args.epochs, lr=args.lr,
                                   log=None if args.quiet else print,
-                                  use_graph=_use_graph(args) and args.objective not in ("recon", "recon-logit"), objective=args.objective,
+                                  use_graph=_use_graph(args) and args.objective not in ("recon", "recon-logit")
+                                  and not args.resample_negatives, objective=args.objective,
+                                  resample_negatives=args.resample_negatives, resample_seed=args.resample_seed + run,
                                   pos_weight=args.pos_weight, recon_block_rows=args.recon_block_rows,
                                   recon_node_filter=node_filter if args.recon_link_rule else None)
         if not args.quiet:
+            if args.resample_negatives:
+                print("failed draws:", res.failed_draws)
             print("test auc:", res.test_auc)
         result.append(res.test_auc)
         if args.rank_eval:

@@ -443,6 +443,50 @@ class Disentangle(nn.Module):
         H, logit = ops.HotPathPairLogits.apply(Z, graph, pairs, float(self.beta), float(self.temperature), self.table_dtype)
         return H.view(H.shape[0], -1), logit, ops.PairBCELogits.apply(logit, label, weight)
 
+    def forward_pairs_resampled_loss(self, x, graph: Graph, pos_pairs: PairList, label, weight, sampled, k, neg_weight: float,
+                                     order=None, k_rowptr=None):
+        """(emb [N,K*d], prob [P], neg_prob [E], loss): the positive list ``pos_pairs`` with (label, weight) through the one-pass
+        scorer, plus this epoch's sampled negatives — ``sampled`` (an ``ops.SampledNegatives``) with the partners ``k`` of
+        ``ops.sample_negatives``, label 0 and the one weight ``neg_weight`` — through ``ops.score_sampled_train``, over one
+        hot-path forward and one backward (ops.HotPathPairsResampledLoss).  Duplicated draws are separate loss terms and a
+        failed draw (k = -1) is no term.  fp32 tables only; a shape without a one-pass scorer runs the positive list through
+        forward_pairs' node and the sampled trainer as a node of its own."""
+        return self._forward_resampled(x, graph, pos_pairs, label, weight, sampled, k, neg_weight, False, order, k_rowptr)
+
+    def forward_pair_logits_resampled_loss(self, x, graph: Graph, pos_pairs: PairList, label, weight, sampled, k,
+                                           neg_weight: float, order=None, k_rowptr=None):
+        """``forward_pairs_resampled_loss`` in LOGIT space: the scores are logits, the loss BCE with logits on both lists."""
+        return self._forward_resampled(x, graph, pos_pairs, label, weight, sampled, k, neg_weight, True, order, k_rowptr)
+
+    def _forward_resampled(self, x, graph, pos_pairs, label, weight, sampled, k, neg_weight, logit, order, k_rowptr):
+        if self.table_dtype != torch.float32:
+            raise TypeError("resampled negatives are trained on fp32 tables only (bf16 tables are not served)")
+        if label.numel() != pos_pairs.n_pairs or weight.numel() != pos_pairs.n_pairs:
+            raise ValueError("label / weight must cover the pair list")
+        Z = self.project(x)
+        K, d = Z.shape[1], Z.shape[2]
+        if not ops.score_sampled_supported(K, d):
+            raise ops._lib.DisenlinkHipError(f"the sampled trainer serves K <= 64 and K d <= 2048 (got K={K}, d={d}); there is no "
+                                             "eager fallback")
+        ok = ops.score_pairs_train_logits_supported if logit else ops.score_pairs_train_supported
+        if not ok(pos_pairs, K, d, ops.table_code(torch.float32)):
+            # no one-pass scorer for the positive list at this shape: forward_pairs' node and the fused loss for it, the
+            # sampled trainer as a node of its own over (Z, H) — its gradient on H arrives at the first node as d/d emb
+            beta, t = float(self.beta), float(self.temperature)
+            if logit:
+                H, score = ops.HotPathPairLogits.apply(Z, graph, pos_pairs, beta, t, torch.float32)
+                loss = ops.PairBCELogits.apply(score, label, weight)
+            else:
+                H, score = ops.HotPathPairs.apply(Z, graph, pos_pairs, beta, t, torch.float32)
+                loss = ops.PairBCE.apply(score, label, weight)
+            node = ops.SampledLogitsLoss if logit else ops.SampledLoss
+            loss_neg, neg_score = node.apply(Z, H, t, sampled, k, float(neg_weight))
+            return H.view(H.shape[0], -1), score, neg_score, loss + loss_neg
+        H, score, neg_score, loss = ops.HotPathPairsResampledLoss.apply(
+            Z, graph, pos_pairs, float(self.beta), float(self.temperature), label, weight, sampled, k, float(neg_weight),
+            logit, order, k_rowptr)
+        return H.view(H.shape[0], -1), score, neg_score, loss
+
     def forward_recon_loss(self, x, graph: Graph, ignore=None, pos_weight=None, block_rows=None, node_filter=None):
         """(emb [N,K*d], loss): the whole-graph reconstruction loss (ops.score_recon_loss) of project -> RouteAggregate ->
         ops.ReconLoss (a bf16 module, ``table_dtype=torch.bfloat16``: project -> ops.HotPathRecon, one node that routes,

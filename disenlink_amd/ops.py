@@ -26,6 +26,9 @@ from .project import (                                                  # noqa: 
 from .recon import (                                                    # noqa: F401  (the whole-graph reconstruction loss)
     ReconLogitsLoss, ReconLoss, ReconSets, check_recon_counts, recon_sets, recon_weights, score_recon_logits_loss,
     score_recon_loss)
+from .sampled import (                                                  # noqa: F401  (fresh training negatives every epoch)
+    SampledLogitsLoss, SampledLoss, SampledNegatives, sample_negatives, sampled_order, score_sampled_logits_loss,
+    score_sampled_loss, score_sampled_supported, score_sampled_train)
 from .scans import (                                                    # noqa: F401  (the all-pairs scans: ops.score_* as before)
     BETWEEN_MAX_N, BLOCK_NODES, BLOCKS_MAX_N, LINKS_MAX_N, MINE_MAX_M, MINE_MAX_N, RANK_MAX_K, LinksBetween, NodeFilter,
     PairExclusion, PairTerms, bipartite_exclusion_csr, exclusion_csr, pair_exclusion, score_link_degrees,
@@ -519,6 +522,45 @@ class HotPathPairLogitsLoss(torch.autograd.Function):
             dH += dH2
         _step_backward_tail(ctx, Zt, a, s, dZ, dH, g_emb)
         return dZ, None, None, None, None, None, None, None
+
+
+class HotPathPairsResampledLoss(torch.autograd.Function):
+    """Z [N,K,d] fp32 -> (emb, score [P], neg_score [E], loss): ``HotPathPairsLoss`` (``logit``: ``HotPathPairLogitsLoss``) over
+    the POSITIVE list ``pairs`` with (label, weight), plus this epoch's sampled negatives (``sampled``, ``k``, one weight
+    ``neg_weight``) through ``score_sampled_train``, over ONE routing / aggregation forward and one backward: the sampled
+    trainer adds its gradients onto the positive list's in its finishing launch, and loss = positive part + negative part.
+    The backward takes a gradient on the loss (and on emb); the scores carry none.  fp32 tables only."""
+
+    @staticmethod
+    def forward(ctx, Z, graph: Graph, pairs: PairList, beta: float, t: float, label, weight, sampled, k, neg_weight: float,
+                logit: bool, order=None, k_rowptr=None):
+        ctx.set_materialize_grads(False)
+        Zt, p, a, s, H = step_tables(graph, Z, beta, t, torch.float32)
+        if logit:
+            score, dZs, dHs = score_pairs_train_logits(Zt, H, pairs, t, label, weight)
+            loss_pos, _g = pair_bce_logits(score, label, weight)
+        else:
+            score, dZs, dHs = score_pairs_train(Zt, H, pairs, t, label, weight)
+            loss_pos, _g = pair_bce(score, label, weight)
+        loss_neg, neg_score, dZs, dHs = score_sampled_train(Zt, H, t, sampled, k, neg_weight, logit, order, k_rowptr,
+                                                            dZ_accum=dZs, dH_accum=dHs)
+        ctx.graph, ctx.beta, ctx.t, ctx.p = graph, beta, t, p
+        ctx.save_for_backward(Zt, a, s, dZs, dHs)
+        ctx.mark_non_differentiable(score, neg_score)
+        return H.float(), score, neg_score, loss_pos + loss_neg
+
+    @staticmethod
+    def backward(ctx, g_emb, _g_score, _g_neg, g_loss):
+        Zt, a, s, dZs, dHs = ctx.saved_tensors
+        none = (None,) * 12
+        if g_loss is not None and g_emb is None and g_loss.numel() == 1:
+            return (route_aggregate_bwd_scaled(ctx.graph, Zt, ctx.beta, ctx.t, ctx.p, a, s, dHs, dZs, g_loss),) + none
+        if g_loss is not None:
+            dZ, dH = dZs * g_loss, dHs * g_loss
+        else:
+            dZ, dH = torch.zeros_like(dZs), torch.zeros_like(dHs)
+        _step_backward_tail(ctx, Zt, a, s, dZ, dH, g_emb)
+        return (dZ,) + none
 
 
 class HotPathRecon(torch.autograd.Function):

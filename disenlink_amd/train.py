@@ -35,10 +35,17 @@ class PreparedRun:
     test_pairs: PairList
     label_test: torch.Tensor
     m: int
+    # prepare_run(..., resample_negatives=True): the positive and validation pairs as a list of their own and the fixed side
+    # of the negatives drawn anew each epoch (run_link_prediction(resample_negatives=True))
+    pos_val_pairs: PairList | None = None
+    sampled: object | None = None
 
 
-def prepare_run(split: LinkSplit, device, seg_len: int = 32, row_bytes: int = 2048) -> PreparedRun:
-    """``row_bytes`` = K * d * (4, or 2 with bf16 tables) of the model (sizes the XCD slicing of the pair plans)."""
+def prepare_run(split: LinkSplit, device, seg_len: int = 32, row_bytes: int = 2048, resample_negatives: bool = False) -> PreparedRun:
+    """``row_bytes`` = K * d * (4, or 2 with bf16 tables) of the model (sizes the XCD slicing of the pair plans).
+    ``resample_negatives``: also prepare what ``run_link_prediction(resample_negatives=True)`` trains on — the list
+    [pos_train | val] and an ``ops.SampledNegatives`` over the sources of the training edge rows (duplicates kept, m draws
+    each) whose exclusion set is every edge row of the dataset, the rule of ``splits.structured_negatives``."""
     t = lambda a, dt=None: torch.as_tensor(a, device=device) if dt is None else torch.as_tensor(a, dtype=dt, device=device)
     graph = Graph.from_edge_rows(t(split.train_src), t(split.train_dst), split.n_nodes, seg_len=seg_len,
                                  row_bytes=row_bytes)
@@ -46,9 +53,20 @@ def prepare_run(split: LinkSplit, device, seg_len: int = 32, row_bytes: int = 20
     pv = np.concatenate([split.pos_train.v, split.neg_train.v, split.val.v])
     tv = PairList.build(t(pu), t(pv), split.n_nodes, row_bytes=row_bytes)
     te = PairList.build(t(split.test.u), t(split.test.v), split.n_nodes, row_bytes=row_bytes)
-    return PreparedRun(graph, tv, split.pos_train.u.size, split.neg_train.u.size,
-                       t(split.pos_train.label, torch.float32), t(split.neg_train.label, torch.float32),
-                       t(split.val.label, torch.float32), te, t(split.test.label, torch.float32), split.m)
+    run = PreparedRun(graph, tv, split.pos_train.u.size, split.neg_train.u.size,
+                      t(split.pos_train.label, torch.float32), t(split.neg_train.label, torch.float32),
+                      t(split.val.label, torch.float32), te, t(split.test.label, torch.float32), split.m)
+    if resample_negatives:
+        from .sampled import SampledNegatives
+        run.pos_val_pairs = PairList.build(t(np.concatenate([split.pos_train.u, split.val.u])),
+                                           t(np.concatenate([split.pos_train.v, split.val.v])), split.n_nodes, row_bytes=row_bytes)
+        edge_u, edge_v = [split.train_src], [split.train_dst]           # every edge row of the dataset: train rows + the held-out
+        for held in (split.val, split.test):                            # pairs that ARE edge rows (label = membership)
+            edge_u.append(held.u[held.label == 1])
+            edge_v.append(held.v[held.label == 1])
+        run.sampled = SampledNegatives(t(split.train_src), split.m, split.n_nodes,
+                                       (t(np.concatenate(edge_u)), t(np.concatenate(edge_v))), device)
+    return run
 
 
 @dataclass
@@ -58,6 +76,7 @@ class RunResult:
     epochs_run: int
     losses: list = field(default_factory=list)
     val_aucs: list = field(default_factory=list)
+    failed_draws: int = 0          # resample_negatives: entries whose 64 attempts all hit excluded partners, over the run
 
 
 _FUSED_ADAM = os.environ.get("DL_FUSED_ADAM", "1") != "0"
@@ -195,7 +214,8 @@ def _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, es
 
 def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 2000, lr: float = 1e-4,
                         patience: int = 200, weight_decay: float = 5e-4, log=None, use_graph: bool = False,
-                        objective: str = "pairs", pos_weight=None, recon_block_rows=None, recon_node_filter=None) -> RunResult:
+                        objective: str = "pairs", pos_weight=None, recon_block_rows=None, recon_node_filter=None,
+                        resample_negatives: bool = False, resample_seed: int = 0) -> RunResult:
     """``use_graph=True`` (GPU only): replay each epoch from a captured HIP graph (same arithmetic, same
     schedule; only the host-side launch cost disappears).
     ``objective``: "pairs" (the default: the reference's loss on the sampled pair list), "pairs-logit" — the same pair list
@@ -208,13 +228,33 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     loop on ``model.forward_recon_logits_loss`` (the reconstruction loss in logit space: a saturated pair keeps its cost and
     its gradient), validation and test AUC counted on ``model.forward_pair_logits``; GPU only, refusals as for "recon".
     ``recon_node_filter`` (an ``ops.NodeFilter``, with "recon" / "recon-logit" only; any other objective raises ValueError):
-    the reconstruction loss takes only pairs the filter's unordered rule admits (``ops.recon_sets(..., node_filter=...)``)."""
+    the reconstruction loss takes only pairs the filter's unordered rule admits (``ops.recon_sets(..., node_filter=...)``).
+    ``resample_negatives`` (with "pairs" / "pairs-logit", GPU, eager, a run of ``prepare_run(..., resample_negatives=True)``):
+    the training negatives are drawn anew EVERY epoch on the device — one sampler call (``ops.sample_negatives``, seed
+    ``resample_seed``, counter = the epoch), one sort, and the step over [pos_train | val] plus the sampled entries
+    (``model.forward_pairs_resampled_loss``) — in place of the fixed split's ``neg_train``.  Their weight is term 2 of the
+    reference's loss, BCE_mean(neg) / m = 1 / (m E) per entry over the E = m x train-rows entries; duplicated draws stay separate
+    terms.  Validation and test sets stay the fixed split's.  ``use_graph=True`` raises (HIP-graph replay of a resampled epoch
+    is not implemented), as does the sharded loop."""
     if objective not in ("pairs", "pairs-logit", "recon", "recon-logit"):
         raise ValueError(f"objective must be \"pairs\", \"pairs-logit\", \"recon\" or \"recon-logit\", got {objective!r}")
     if recon_node_filter is not None and objective not in ("recon", "recon-logit"):
         raise ValueError(f"recon_node_filter restricts the reconstruction loss: objective=\"recon\" or \"recon-logit\", "
                          f"got {objective!r}")
     logit = objective == "pairs-logit"
+    if resample_negatives:
+        if objective not in ("pairs", "pairs-logit"):
+            raise ValueError(f"resample_negatives replaces the sampled negatives of objective=\"pairs\" / \"pairs-logit\", got {objective!r}")
+        if use_graph:
+            raise ValueError("resample_negatives runs in the eager loop only (HIP-graph replay of a resampled epoch is not "
+                             "implemented): pass use_graph=False")
+        if not x.is_cuda:
+            raise ValueError("resample_negatives runs on the GPU only (the sampler and its trainer have no CPU form)")
+        if run.sampled is None or run.pos_val_pairs is None:
+            raise ValueError("resample_negatives needs a run of prepare_run(..., resample_negatives=True)")
+        if not hasattr(model, "forward_pairs_resampled_loss"):
+            raise TypeError("resample_negatives needs a model with forward_pairs_resampled_loss (disenlink_amd.model.Disentangle)")
+        return _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit, int(resample_seed))
     if logit:
         _check_logit_run(model, run)
         if not x.is_cuda:
@@ -299,6 +339,91 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
         prob = _scores(model, x, run.graph, run.test_pairs, logit)
     res.test_auc = float(auc_tie_avg(run.label_test, prob, check=False))
     res.best_val_auc = best_auc
+    return res
+
+
+def _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit: bool, seed: int) -> RunResult:
+    """run_link_prediction's eager loop with the negatives drawn anew each epoch (see there).  Per epoch: the sampler (its
+    epoch counter a device tensor advanced by ``add_``), the sort, the step; nothing of it is read by the host.  The count
+    of failed draws is copied to pinned memory behind each epoch and looked at one epoch (or more) later: a warning, once."""
+    import warnings
+    from . import ops
+    from .early_stop import DeviceEarlyStop, drive
+    sp, pairs, dev = run.sampled, run.pos_val_pairs, x.device
+    for lab in (run.label_val, run.label_test):
+        if not 0 < float(lab.sum()) < lab.numel():
+            raise ValueError("AUC undefined with one class")
+    a, n_val = run.n_pos, run.label_val.numel()
+    if pairs.n_pairs != a + n_val:
+        raise ValueError(f"label / weight must cover the pair list: {a} + {n_val} labels for {pairs.n_pairs} pairs")
+    label = torch.cat([run.label_pos, run.label_val.to(run.label_pos.dtype)])
+    weight = torch.cat([torch.full((a,), 1.0 / max(a, 1), dtype=torch.float32, device=dev),
+                        torch.zeros(n_val, dtype=torch.float32, device=dev)])
+    neg_weight = 1.0 / (sp.m * max(sp.n_entries, 1))                 # BCE_mean(neg) / m over the epoch's entries
+    epoch_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+    n_failed = torch.zeros(1, dtype=torch.int32, device=dev)
+    failed_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+    warned = [False]
+    step_fn = model.forward_pair_logits_resampled_loss if logit else model.forward_pairs_resampled_loss
+    opt = _make_adam(model, True, lr, weight_decay)
+    val_plan = AucPlan(run.label_val)
+    res = RunResult(float("nan"), 0.0, 0)
+
+    def step():
+        if int(failed_host[0]) > 0 and not warned[0]:              # written behind an EARLIER epoch: no wait
+            warned[0] = True
+            warnings.warn(f"resample_negatives: {int(failed_host[0])} draws so far found no admissible partner in 64 attempts "
+                          "(their entries carry weight 0)")
+        model.train()
+        k, _ = ops.sample_negatives(sp, seed=seed, epoch=epoch_dev, n_failed=n_failed)
+        order, k_rowptr = ops.sampled_order(k, sp.n_nodes)
+        _emb, score, _neg, loss = step_fn(x, run.graph, pairs, label, weight, sp, k, neg_weight, order, k_rowptr)
+        epoch_dev.add_(1)
+        failed_host.copy_(n_failed, non_blocking=True)
+        return score, loss
+
+    if DeviceEarlyStop.usable(model, x, val_plan):
+        es = DeviceEarlyStop(model, val_plan, epochs, patience)
+        one = torch.ones((), dtype=torch.float32, device=dev)
+
+        def launch_epoch():
+            score, loss = step()
+            opt.zero_grad()
+            loss.backward(one)
+            opt.step()
+            model.eval()
+            es.finish(loss, score[a:])
+
+        res.best_val_auc = drive(es, epochs, patience, launch_epoch, res, log)
+        es.restore()
+    else:
+        snapshot = getattr(model, "snapshot_state", None) or (lambda: deepcopy(model.state_dict()))
+        best_auc, stale, weights = 0.0, 0, snapshot()
+        for epoch in range(epochs):
+            score, loss = step()
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            model.eval()
+            loss_v, auc = torch.stack([loss.detach().double(), val_plan.auc(score[a:])]).tolist()
+            res.losses.append(loss_v)
+            res.val_aucs.append(auc)
+            res.epochs_run = epoch + 1
+            if auc > best_auc:
+                stale, best_auc = 0, auc
+                weights = snapshot()
+            else:
+                stale += 1
+            if stale > patience:
+                break
+            if log is not None:
+                log(f"epoch: {epoch} loss: {loss_v} val_auc: {best_auc}")
+        model.load_state_dict(weights)
+        res.best_val_auc = best_auc
+    with torch.no_grad():
+        prob = _scores(model, x, run.graph, run.test_pairs, logit)
+    res.test_auc = float(auc_tie_avg(run.label_test, prob, check=False))
+    res.failed_draws = int(n_failed[0])
     return res
 
 

@@ -1175,6 +1175,54 @@ int dl_route_aggregate_bwd_scaled(const dl_graph* g, const void* Z, int K, int d
                                   const float* dH, const float* dZ_in, const float* scale, float* dZ,
                                   void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Fresh training negatives every epoch, drawn and trained on the device (opt-in; nothing above changes).
+ *
+ * dl_sample_negatives: for entry e = r m + j (r < n_rows, j < m) draw a partner k uniformly over [0, N) such that
+ * (src[r], k) is not in the exclusion CSR (ex_rowptr [N+1], ex_col ascending per row: the normal form the scans read;
+ * both NULL = nothing excluded) and, with exclude_self != 0, k != src[r] — the rule of the fixed split's structured
+ * negatives: an edge row of the whole dataset is never a negative.
+ * Randomness is counter-based: Philox4x32-10 with key = (seed low, seed high) and counter = (e, attempt, epoch low, epoch
+ * high); k = (uint64(word 0) * N) >> 32.  The draw is a pure function of (seed, epoch, e): no dependence on the grid, the wave
+ * order or the call.  Bias of the map: a value receives floor or ceil of 2^32 / N of the 2^32 words, i.e. at most N / 2^32
+ * relative to uniform.  epoch_dev: ONE uint64 in device memory, read by the kernel (a loop advances it with a device add; no
+ * host value changes between epochs).
+ * At most 64 attempts per entry: an entry that exhausts them writes k = -1 and adds 1 to *n_failed (device uint32, an integer
+ * atomic; the caller zeroes it); the trainers below give such an entry weight 0.  A src[r] outside [0, N) fails likewise.
+ * Duplicated draws inside an epoch are KEPT as separate entries: nothing is de-duplicated (the fixed split does).
+ * One thread per entry, no LDS, no workspace, no host read, no synchronisation; the caller's stream. */
+int dl_sample_negatives(const int32_t* src, int n_rows, int m, int N, const int32_t* ex_rowptr, const int32_t* ex_col,
+                        uint64_t seed, const uint64_t* epoch_dev, int exclude_self, int32_t* k_out, uint32_t* n_failed,
+                        void* stream);
+
+/* dl_score_sampled_train: the outputs of dl_score_pairs_train for the n_rows m entries (u_e, k_e), u_e = src[e / m], label 0
+ * and ONE weight w, without a plan:
+ *   score[e] = sigmoid(x_e) (_logits: x_e),  x_e = sum_f (h_f[u].h_f[k]) exp(z_f[u].z_f[k] / t);   0 for an entry with k = -1;
+ *   loss[0]  = sum_e -w max(log(1 - score), -100)          (_logits: sum_e w (max(x, 0) + log1p(exp(-|x|))));
+ *   dZ, dH [N][K][d] = d loss / d (Z, H) with g = w (p - 0) under dl_pair_bce's max(p (1 - p), 1e-12) clamp (_logits:
+ *   g = w sigma(x), no clamp), every pair in both endpoints' rows; accumulate != 0 adds onto dZ / dH instead (another list's
+ *   gradients and these then sum without a launch of their own).  EVERY row of dZ / dH is written: a node no entry names reads
+ *   exactly 0.  w = 0 and k = -1 contribute exactly nothing.  k == u is legal.
+ * src ascending; u_rowptr [N+1]: the CSR of the u side in ENTRIES (u_rowptr[n] = m x the number of src values < n);
+ * order [E]: the STABLE ascending sort of k over the entries (the -1 entries first); k_rowptr [N+1]: k_rowptr[n] = the number
+ * of entries with k < n (so k_rowptr[0] = the failed draws, k_rowptr[N] = E).  Both are the caller's to compute on the device.
+ * Two passes over chunks of 64 list positions (row side, then partner side through 2K stored coefficients per entry), partial
+ * slots where a row spans chunks, one finishing launch that adds partner side first, then row side: fixed orders throughout,
+ * no float atomics, no host read, no synchronisation; the same bits on every call.  fp32 tables with 1 <= K <= 64 and
+ * K d <= 2048 (dl_score_sampled_train_supported; d = 64 with K in {4, 8} has its own kernels, whose scores are the bits of
+ * dl_score_pairs_train's); bf16 tables are refused.  ws: dl_score_sampled_train_workspace_bytes(n_rows m, N, K, d). */
+int dl_score_sampled_train_supported(int K, int d, dl_dtype dtype);
+size_t dl_score_sampled_train_workspace_bytes(int n_entries, int N, int K, int d);
+int dl_score_sampled_train(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                           const int32_t* src, int n_rows, int m, const int32_t* u_rowptr, const int32_t* k,
+                           const int32_t* order, const int32_t* k_rowptr, float w, float* score, float* loss,
+                           float* dZ, float* dH, int accumulate, void* ws, size_t ws_bytes, void* stream);
+int dl_score_sampled_train_logits_supported(int K, int d, dl_dtype dtype);
+size_t dl_score_sampled_train_logits_workspace_bytes(int n_entries, int N, int K, int d);
+int dl_score_sampled_train_logits(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                                  const int32_t* src, int n_rows, int m, const int32_t* u_rowptr, const int32_t* k,
+                                  const int32_t* order, const int32_t* k_rowptr, float w, float* score, float* loss,
+                                  float* dZ, float* dH, int accumulate, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
