@@ -173,6 +173,12 @@ _SAMPLED = [_P, _P, _i, _i, _i, _i, _f, _P, _i, _i, _P, _P, _P, _P, _f, _P, _P, 
 for _name in ("dl_score_sampled_train", "dl_score_sampled_train_logits"):
     EXPORTS.update({_name + "_supported": (_i, [_i, _i, _i]), _name + "_workspace_bytes": (_z, [_i] * 4),
                     _name: (_i, _SAMPLED)})
+# the pairwise ranking trainer on the same draws: ... t, src, dst, n_rows, m, six lists, w, five outputs, accumulate, workspace
+EXPORTS.update({
+    "dl_score_sampled_bpr_train_supported": (_i, [_i, _i, _i]),
+    "dl_score_sampled_bpr_train_workspace_bytes": (_z, [_i] * 5),
+    "dl_score_sampled_bpr_train": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _P, _i, _i] + [_P] * 6 + [_f] + [_P] * 5 + [_i, _P, _z, _P]),
+})
 
 
 def _scan_rows(name: str, res, codes: list, at: int, filtered: bool = False) -> dict:

@@ -54,8 +54,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "the split's fixed sample; one GPU, eager loop, fp32 tables")
     p.add_argument("--resample-seed", type=int, default=0, help="seed of --resample-negatives (the draw is a pure function of "
                                                                 "seed, epoch and entry)")
-    p.add_argument("--objective", choices=["pairs", "pairs-logit", "recon", "recon-logit"], default="pairs",
-                   help="the training loss: pairs = the reference's BCE on m sampled negatives per edge; pairs-logit = the same "
+    p.add_argument("--objective", choices=["pairs", "pairs-logit", "recon", "recon-logit", "bpr"], default="pairs",
+                   help="the training loss: bpr = the pairwise ranking loss, every training edge (u, v) must score above (u, k) "
+                        "for m negatives k drawn anew every epoch on the device (softplus of the logit difference; implies "
+                        "--resample-negatives, --resample-seed applies; AUC counted on logits; one GPU, eager loop, fp32 "
+                        "tables); pairs = the reference's BCE on m sampled negatives per edge; pairs-logit = the same "
                         "pairs with the BCE taken of the LOGITS (a saturated pair keeps its gradient, and the validation / test "
                         "AUC is counted on logits, which do not tie at probability 1; one GPU); recon = the "
                         "whole-graph reconstruction loss, every non-edge a negative and the edges up-weighted, with the "
@@ -436,9 +439,13 @@ def main(argv=None):
     if args.objective in ("recon", "recon-logit") and (args.gpus > 1 or args.graph):
         raise SystemExit("--objective recon runs on one GPU in the eager loop only, with fp32 or bf16 tables (sharded and "
                          "graph-replayed reconstruction epochs are not implemented): drop --gpus / --graph")
+    if args.objective == "bpr" and (args.gpus > 1 or args.graph or args.table_dtype == "bf16"):
+        raise SystemExit("--objective bpr runs on one GPU in the eager loop with fp32 tables (the sharded step, HIP-graph replay "
+                         "of a resampled epoch and bf16 tables are not implemented): drop --gpus / --graph / bf16")
+    resample = args.resample_negatives or args.objective == "bpr"    # the ranking objective draws its negatives every epoch
     if args.resample_negatives:
-        if args.objective not in ("pairs", "pairs-logit"):
-            raise SystemExit("--resample-negatives goes with --objective pairs or pairs-logit")
+        if args.objective not in ("pairs", "pairs-logit", "bpr"):
+            raise SystemExit("--resample-negatives goes with --objective pairs or pairs-logit (--objective bpr implies it)")
         if args.gpus > 1 or args.graph or args.table_dtype == "bf16":
             raise SystemExit("--resample-negatives runs on one GPU in the eager loop with fp32 tables (the sharded step, HIP-graph "
                              "replay of a resampled epoch and bf16 tables are not implemented): drop --gpus / --graph / bf16")
@@ -488,19 +495,20 @@ def main(argv=None):
             print("run:", run)
         split = make_link_split(ds.src, ds.dst, ds.n_nodes, m=args.m, seed=args.seed + run)
         prepared = prepare_run(split, device, row_bytes=args.nfactor * args.nembed * (2 if args.table_dtype == "bf16" else 4),
-                               resample_negatives=args.resample_negatives)
+                               resample_negatives=resample)
         torch.manual_seed(args.seed + run)
         model = Disentangle(x.shape[1], args.nhidden, args.nembed, nfactor=args.nfactor, beta=args.beta,
                             t=args.temperature, table_dtype=tdt).to(device)
         res = run_link_prediction(model, x, prepared, epochs=args.epochs, lr=args.lr,
                                   log=None if args.quiet else print,
                                   use_graph=_use_graph(args) and args.objective not in ("recon", "recon-logit")
-                                  and not args.resample_negatives, objective=args.objective,
-                                  resample_negatives=args.resample_negatives, resample_seed=args.resample_seed + run,
+                                  and not resample, objective=args.objective,
+                                  resample_negatives=args.resample_negatives and args.objective != "bpr",
+                                  resample_seed=args.resample_seed + run,
                                   pos_weight=args.pos_weight, recon_block_rows=args.recon_block_rows,
                                   recon_node_filter=node_filter if args.recon_link_rule else None)
         if not args.quiet:
-            if args.resample_negatives:
+            if resample:
                 print("failed draws:", res.failed_draws)
             print("test auc:", res.test_auc)
         result.append(res.test_auc)

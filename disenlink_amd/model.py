@@ -487,6 +487,24 @@ class Disentangle(nn.Module):
             logit, order, k_rowptr)
         return H.view(H.shape[0], -1), score, neg_score, loss
 
+    def forward_bpr_loss(self, x, graph: Graph, sampled, k, weight: float, val_pairs: PairList = None, order=None, k_rowptr=None):
+        """(emb [N,K*d], pos_logit [n_rows], neg_logit [E], val_logit [P] | None, loss): the pairwise ranking objective (BPR) —
+        every training edge row (src, dst) of ``sampled`` (an ``ops.SampledNegatives`` built with ``dst``) must score above
+        (src, k) for its m partners ``k`` of ``ops.sample_negatives``: loss = sum weight softplus(neg_logit - pos_logit[row])
+        over the entries with k >= 0, through ``ops.score_sampled_bpr_train`` over one hot-path forward and one backward
+        (ops.HotPathBprLoss).  ``val_pairs``: a list whose logits come out of the same forward (forward only: no gradient).
+        Duplicated draws are separate terms, a failed draw (k = -1) is none.  fp32 tables only, logit space only."""
+        if self.table_dtype != torch.float32:
+            raise TypeError("the ranking objective is trained on fp32 tables only (bf16 tables are not served)")
+        Z = self.project(x)
+        K, d = Z.shape[1], Z.shape[2]
+        if not ops.score_sampled_bpr_supported(K, d):
+            raise ops._lib.DisenlinkHipError(f"the ranking trainer serves K <= 64 and K d <= 2048 (got K={K}, d={d}); there is no "
+                                             "eager fallback")
+        H, pos, neg, val, loss = ops.HotPathBprLoss.apply(Z, graph, float(self.beta), float(self.temperature), sampled, k,
+                                                          float(weight), val_pairs, order, k_rowptr)
+        return H.view(H.shape[0], -1), pos, neg, (None if val_pairs is None else val), loss
+
     def forward_recon_loss(self, x, graph: Graph, ignore=None, pos_weight=None, block_rows=None, node_filter=None):
         """(emb [N,K*d], loss): the whole-graph reconstruction loss (ops.score_recon_loss) of project -> RouteAggregate ->
         ops.ReconLoss (a bf16 module, ``table_dtype=torch.bfloat16``: project -> ops.HotPathRecon, one node that routes,

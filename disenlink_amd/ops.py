@@ -28,7 +28,8 @@ from .recon import (                                                    # noqa: 
     score_recon_loss)
 from .sampled import (                                                  # noqa: F401  (fresh training negatives every epoch)
     SampledLogitsLoss, SampledLoss, SampledNegatives, sample_negatives, sampled_order, score_sampled_logits_loss,
-    score_sampled_loss, score_sampled_supported, score_sampled_train)
+    score_sampled_loss, score_sampled_supported, score_sampled_train,
+    SampledBprLoss, score_sampled_bpr_loss, score_sampled_bpr_supported, score_sampled_bpr_train)   # (... the ranking objective)
 from .scans import (                                                    # noqa: F401  (the all-pairs scans: ops.score_* as before)
     BETWEEN_MAX_N, BLOCK_NODES, BLOCKS_MAX_N, LINKS_MAX_N, MINE_MAX_M, MINE_MAX_N, RANK_MAX_K, LinksBetween, NodeFilter,
     PairExclusion, PairTerms, bipartite_exclusion_csr, exclusion_csr, pair_exclusion, score_link_degrees,
@@ -553,6 +554,41 @@ class HotPathPairsResampledLoss(torch.autograd.Function):
     def backward(ctx, g_emb, _g_score, _g_neg, g_loss):
         Zt, a, s, dZs, dHs = ctx.saved_tensors
         none = (None,) * 12
+        if g_loss is not None and g_emb is None and g_loss.numel() == 1:
+            return (route_aggregate_bwd_scaled(ctx.graph, Zt, ctx.beta, ctx.t, ctx.p, a, s, dHs, dZs, g_loss),) + none
+        if g_loss is not None:
+            dZ, dH = dZs * g_loss, dHs * g_loss
+        else:
+            dZ, dH = torch.zeros_like(dZs), torch.zeros_like(dHs)
+        _step_backward_tail(ctx, Zt, a, s, dZ, dH, g_emb)
+        return (dZ,) + none
+
+
+class HotPathBprLoss(torch.autograd.Function):
+    """Z [N,K,d] fp32 -> (emb, pos_logit [n_rows], neg_logit [E], val_logit [P] or an empty tensor, loss): one routing /
+    aggregation forward, the pairwise ranking loss of ``score_sampled_bpr_train`` over ``sampled`` (built with ``dst``) and this
+    epoch's partners ``k`` with the one weight ``weight``, and — ``val_pairs`` given — the logits of that list through
+    ``score_pairs_logits_fwd``, forward only.  The backward is ``HotPathPairsResampledLoss``'s: a gradient on the loss (scaled
+    inside the last kernel) and on emb; the logits carry none.  fp32 tables only."""
+
+    @staticmethod
+    def forward(ctx, Z, graph: Graph, beta: float, t: float, sampled, k, weight: float, val_pairs=None, order=None, k_rowptr=None):
+        ctx.set_materialize_grads(False)
+        Zt, p, a, s, H = step_tables(graph, Z, beta, t, torch.float32)
+        loss, pos, neg, dZs, dHs = score_sampled_bpr_train(Zt, H, t, sampled, k, weight, order, k_rowptr)
+        if val_pairs is None:
+            val = torch.empty(0, dtype=torch.float32, device=Zt.device)
+        else:
+            val = score_pairs_logits_fwd(Zt, H, val_pairs.pu, val_pairs.pv, t, val_pairs)
+        ctx.graph, ctx.beta, ctx.t, ctx.p = graph, beta, t, p
+        ctx.save_for_backward(Zt, a, s, dZs, dHs)
+        ctx.mark_non_differentiable(pos, neg, val)
+        return H.float(), pos, neg, val, loss
+
+    @staticmethod
+    def backward(ctx, g_emb, _g_pos, _g_neg, _g_val, g_loss):
+        Zt, a, s, dZs, dHs = ctx.saved_tensors
+        none = (None,) * 9
         if g_loss is not None and g_emb is None and g_loss.numel() == 1:
             return (route_aggregate_bwd_scaled(ctx.graph, Zt, ctx.beta, ctx.t, ctx.p, a, s, dHs, dZs, g_loss),) + none
         if g_loss is not None:

@@ -10,6 +10,9 @@ synchronisation in the epoch.
 What differs from the fixed split: duplicated draws inside an epoch are KEPT as separate loss terms (the fixed split keeps only
 the pairs drawn once); an entry whose 64 attempts all hit excluded partners is k = -1, weight 0, and counted in ``n_failed``.
 fp32 tables only (bf16 tables raise).
+
+The same draws also serve the pairwise ranking objective (csrc/dl_train_bpr.hip): ``SampledNegatives(..., dst=...)`` keeps the
+positives' other end, and ``score_sampled_bpr_train`` trains every edge row (u, v) to score above (u, k) for its m draws.
 """
 from __future__ import annotations
 
@@ -25,16 +28,35 @@ class SampledNegatives:
     training edge rows, duplicates kept), ``m`` draws per row, ``u_rowptr`` int32 [N+1] (the CSR of the u side, in ENTRIES:
     entry e = r m + j belongs to src[r]) and the exclusion CSR (``ops.exclusion_csr`` normal form: ascending distinct columns
     per row, directed — (u, k) excluded says nothing about (k, u)).  ``exclusion``: what ``ops.exclusion_csr`` takes (a
-    ``(rows, cols)`` pair, a dense mask, a ``Graph``) or None."""
+    ``(rows, cols)`` pair, a dense mask, a ``Graph``) or None.
+    ``dst`` (aligned with ``src``; what the pairwise ranking trainer ``score_sampled_bpr_train`` needs): the other end of every
+    edge row, carried through a STABLE sort by ``src`` and kept as ``.dst`` int32 [n_rows], with ``.dst_order`` int32 [n_rows]
+    (the stable ascending sort of ``.dst`` over the rows) and ``.dst_rowptr`` int32 [N+1] (the number of rows with dst < n),
+    built once.  Without it the three are None and everything else is what it was."""
 
-    def __init__(self, src, m: int, n_nodes: int, exclusion=None, device=None):
+    def __init__(self, src, m: int, n_nodes: int, exclusion=None, device=None, dst=None):
         src = torch.as_tensor(src)
         device = src.device if device is None else torch.device(device)
         if src.dim() != 1 or src.dtype.is_floating_point:
             raise ValueError("src must be a 1-D integer array")
         if int(m) < 1 or int(n_nodes) < 1:
             raise ValueError(f"m and n_nodes must be positive, got {m}, {n_nodes}")
-        src = torch.sort(src.to(device=device, dtype=torch.int64)).values
+        self.dst = self.dst_order = self.dst_rowptr = None
+        if dst is None:
+            src = torch.sort(src.to(device=device, dtype=torch.int64)).values
+        else:
+            dst = torch.as_tensor(dst)
+            if dst.dim() != 1 or dst.dtype.is_floating_point or dst.numel() != src.numel():
+                raise ValueError("dst must be a 1-D integer array aligned with src")
+            src, perm = torch.sort(src.to(device=device, dtype=torch.int64), stable=True)
+            dst = dst.to(device=device, dtype=torch.int64)[perm]
+            if dst.numel() and (int(dst.min()) < 0 or int(dst.max()) >= n_nodes):
+                raise ValueError(f"dst outside [0, {n_nodes})")
+            sd, order = torch.sort(dst, stable=True)
+            self.dst = dst.to(torch.int32).contiguous()
+            self.dst_order = order.to(torch.int32).contiguous()
+            self.dst_rowptr = torch.searchsorted(sd, torch.arange(int(n_nodes) + 1, device=device, dtype=torch.int64)) \
+                .to(torch.int32).contiguous()
         if src.numel() and (int(src[0]) < 0 or int(src[-1]) >= n_nodes):          # built once: the one host read
             raise ValueError(f"src outside [0, {n_nodes})")
         if src.numel() * int(m) > (2 ** 31 - 1) // 128:
@@ -199,3 +221,92 @@ def score_sampled_loss(Z, H, t: float, sampled: SampledNegatives, k, weight: flo
 def score_sampled_logits_loss(Z, H, t: float, sampled: SampledNegatives, k, weight: float):
     """-> (loss, logit [E]), differentiable in (Z, H): the same in logit space (``SampledLogitsLoss``)."""
     return SampledLogitsLoss.apply(Z, H, float(t), sampled, k, float(weight))
+
+
+# ------------------------------------------------------------------------------------------------ pairwise ranking (BPR)
+BPR_MAX_M = 63                           # a chunk of the row pass holds floor(64 / (m + 1)) whole rows
+
+
+def score_sampled_bpr_supported(K: int, d: int, dtype=torch.float32) -> bool:
+    code = _lib.DL_F32 if dtype == torch.float32 else _lib.DL_BF16 if dtype == torch.bfloat16 else -1
+    return code >= 0 and bool(_lib.load().dl_score_sampled_bpr_train_supported(int(K), int(d), code))
+
+
+def score_sampled_bpr_train(Z, H, t: float, sampled: SampledNegatives, k, weight: float, order=None, k_rowptr=None, dZ_accum=None,
+                            dH_accum=None):
+    """-> (loss f32 [], pos_logit f32 [n_rows], neg_logit f32 [E], dZ, dH f32 [N,K,d]): the pairwise ranking loss (BPR) of
+    ``sampled`` (built with ``dst``) and this epoch's partners ``k`` — edge row r = (src[r], dst[r]) must score above
+    (src[r], k[r m + j]) for its m draws: loss = sum weight softplus(neg_logit - pos_logit[row]) over the entries with k >= 0,
+    dZ / dH its gradient, every pair in both endpoints' rows (dl_score_sampled_bpr_train).  Logit space only.  ``pos_logit`` is
+    written for every row, ``neg_logit`` is 0 for k = -1; a row whose draws all failed has no loss and no gradient.
+    ``dZ_accum`` / ``dH_accum`` (both or neither): the gradient is ADDED onto them in place, in the finishing launch.
+    Duplicates are separate terms; k == dst, k == src and dst == src are legal.  No float atomics, no host read, no
+    synchronisation; the same bits on every call.  fp32 tables with K d <= 2048 and m <= 63; bf16 tables raise."""
+    lib = _lib.load()
+    if Z.dtype != torch.float32 or H.dtype != torch.float32:
+        raise TypeError(f"the ranking trainer takes fp32 tables, got {Z.dtype} / {H.dtype} (bf16 tables are not served)")
+    Z, H = _f32c(Z), _f32c(H)
+    _need_cuda(Z, H, k)
+    N, K, d = _nkd(Z)
+    if tuple(H.shape) != tuple(Z.shape):
+        raise ValueError("Z and H differ in shape")
+    if N != sampled.n_nodes:
+        raise ValueError(f"tables of {N} nodes, sampled negatives of {sampled.n_nodes}")
+    if sampled.dst is None:
+        raise ValueError("the ranking trainer needs the positives: build SampledNegatives(..., dst=...)")
+    if sampled.m > BPR_MAX_M:
+        raise ValueError(f"the ranking trainer serves m <= {BPR_MAX_M} negatives per row, got m = {sampled.m}")
+    if not lib.dl_score_sampled_bpr_train_supported(K, d, _lib.DL_F32):
+        raise _lib.DisenlinkHipError(f"the ranking trainer serves fp32 tables with K <= 64 and K d <= 2048 (got K={K}, d={d}); "
+                                     "there is no eager fallback")
+    E = sampled.n_entries
+    if k.dtype != torch.int32 or k.numel() != E or not k.is_contiguous():
+        raise ValueError(f"k must be a contiguous int32 tensor of {E} entries")
+    if (order is None) != (k_rowptr is None):
+        raise ValueError("order and k_rowptr come together")
+    if order is None:
+        order, k_rowptr = sampled_order(k, N)
+    if order.dtype != torch.int32 or order.numel() != E or k_rowptr.dtype != torch.int32 or k_rowptr.numel() != N + 1:
+        raise ValueError("order must be int32 [E] and k_rowptr int32 [N + 1]")
+    if (dZ_accum is None) != (dH_accum is None):
+        raise ValueError("dZ_accum and dH_accum come together")
+    dev = Z.device
+    if dZ_accum is None:
+        dZ, dH, acc = _empty(Z.shape, torch.float32, dev), _empty(Z.shape, torch.float32, dev), 0
+    else:
+        for g in (dZ_accum, dH_accum):
+            if g.dtype != torch.float32 or tuple(g.shape) != tuple(Z.shape) or not g.is_contiguous():
+                raise ValueError("dZ_accum / dH_accum must be contiguous fp32 [N,K,d] tensors")
+        dZ, dH, acc = dZ_accum, dH_accum, 1
+    pos = _empty(sampled.n_rows, torch.float32, dev)
+    neg = _empty(E, torch.float32, dev)
+    loss = _empty(1, torch.float32, dev)
+    ws = _ws.get(max(256, int(lib.dl_score_sampled_bpr_train_workspace_bytes(sampled.n_rows, sampled.m, N, K, d))), dev)
+    _lib.check(lib.dl_score_sampled_bpr_train(
+        Z.data_ptr(), H.data_ptr(), N, K, d, _lib.DL_F32, float(t), sampled.src.data_ptr(), sampled.dst.data_ptr(), sampled.n_rows,
+        sampled.m, sampled.u_rowptr.data_ptr(), sampled.dst_order.data_ptr(), sampled.dst_rowptr.data_ptr(), k.data_ptr(),
+        order.data_ptr(), k_rowptr.data_ptr(), float(weight), pos.data_ptr(), neg.data_ptr(), loss.data_ptr(), dZ.data_ptr(),
+        dH.data_ptr(), acc, ws.data_ptr(), ws.numel(), _stream()), "dl_score_sampled_bpr_train")
+    return loss.reshape(()), pos, neg, dZ, dH
+
+
+class SampledBprLoss(torch.autograd.Function):
+    """(Z, H) -> (loss, pos_logit [n_rows], neg_logit [E]) of ``score_sampled_bpr_train``; the forward keeps dZ, dH and the
+    backward scales them by the gradient arriving on the loss (the logits carry none)."""
+
+    @staticmethod
+    def forward(ctx, Z, H, t: float, sampled: SampledNegatives, k, weight: float, order=None, k_rowptr=None):
+        loss, pos, neg, dZ, dH = score_sampled_bpr_train(Z, H, t, sampled, k, weight, order, k_rowptr)
+        ctx.save_for_backward(dZ, dH)
+        ctx.mark_non_differentiable(pos, neg)
+        return loss, pos, neg
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_pos, _g_neg):
+        dZ, dH = ctx.saved_tensors
+        return dZ * g_loss, dH * g_loss, None, None, None, None, None, None
+
+
+def score_sampled_bpr_loss(Z, H, t: float, sampled: SampledNegatives, k, weight: float, order=None, k_rowptr=None):
+    """-> (loss, pos_logit [n_rows], neg_logit [E]), differentiable in (Z, H): the pairwise ranking loss (``SampledBprLoss``)."""
+    return SampledBprLoss.apply(Z, H, float(t), sampled, k, float(weight), order, k_rowptr)

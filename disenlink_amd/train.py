@@ -39,6 +39,7 @@ class PreparedRun:
     # of the negatives drawn anew each epoch (run_link_prediction(resample_negatives=True))
     pos_val_pairs: PairList | None = None
     sampled: object | None = None
+    val_pairs: PairList | None = None       # the validation pairs alone (run_link_prediction(objective="bpr") scores them)
 
 
 def prepare_run(split: LinkSplit, device, seg_len: int = 32, row_bytes: int = 2048, resample_negatives: bool = False) -> PreparedRun:
@@ -65,7 +66,8 @@ def prepare_run(split: LinkSplit, device, seg_len: int = 32, row_bytes: int = 20
             edge_u.append(held.u[held.label == 1])
             edge_v.append(held.v[held.label == 1])
         run.sampled = SampledNegatives(t(split.train_src), split.m, split.n_nodes,
-                                       (t(np.concatenate(edge_u)), t(np.concatenate(edge_v))), device)
+                                       (t(np.concatenate(edge_u)), t(np.concatenate(edge_v))), device, dst=t(split.train_dst))
+        run.val_pairs = PairList.build(t(split.val.u), t(split.val.v), split.n_nodes, row_bytes=row_bytes)
     return run
 
 
@@ -235,13 +237,32 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     (``model.forward_pairs_resampled_loss``) — in place of the fixed split's ``neg_train``.  Their weight is term 2 of the
     reference's loss, BCE_mean(neg) / m = 1 / (m E) per entry over the E = m x train-rows entries; duplicated draws stay separate
     terms.  Validation and test sets stay the fixed split's.  ``use_graph=True`` raises (HIP-graph replay of a resampled epoch
-    is not implemented), as does the sharded loop."""
-    if objective not in ("pairs", "pairs-logit", "recon", "recon-logit"):
-        raise ValueError(f"objective must be \"pairs\", \"pairs-logit\", \"recon\" or \"recon-logit\", got {objective!r}")
+    is not implemented), as does the sharded loop.
+    ``objective="bpr"``: the pairwise ranking loss — every training edge row (u, v) must score above (u, k) for its m negatives k,
+    drawn anew every epoch as above (``resample_seed`` applies; ``resample_negatives`` is implied): loss = sum_e w softplus(x(u, k_e)
+    - x(u, v)) with w = 1 / n_entries (``model.forward_bpr_loss``, no plan build and no host read in the epoch).  Validation and
+    test AUC are counted on logits, as in "pairs-logit"; failed draws are reported as with ``resample_negatives``.  GPU, eager
+    loop, fp32 tables, a run of ``prepare_run(..., resample_negatives=True)``; anything else raises before the first launch."""
+    if objective not in ("pairs", "pairs-logit", "recon", "recon-logit", "bpr"):
+        raise ValueError(f"objective must be \"pairs\", \"pairs-logit\", \"recon\", \"recon-logit\" or \"bpr\", got {objective!r}")
     if recon_node_filter is not None and objective not in ("recon", "recon-logit"):
         raise ValueError(f"recon_node_filter restricts the reconstruction loss: objective=\"recon\" or \"recon-logit\", "
                          f"got {objective!r}")
     logit = objective == "pairs-logit"
+    if objective == "bpr":                                           # refused before the first launch; implies resampling
+        if use_graph:
+            raise ValueError("objective=\"bpr\" runs in the eager loop only (HIP-graph replay of a resampled epoch is not "
+                             "implemented): pass use_graph=False")
+        if not x.is_cuda:
+            raise ValueError("objective=\"bpr\" runs on the GPU only (the sampler and the ranking trainer have no CPU form)")
+        if run.sampled is None or run.val_pairs is None or getattr(run.sampled, "dst", None) is None:
+            raise ValueError("objective=\"bpr\" needs a run of prepare_run(..., resample_negatives=True)")
+        if not hasattr(model, "forward_bpr_loss") or not hasattr(model, "forward_pair_logits"):
+            raise TypeError("objective=\"bpr\" needs a model with forward_bpr_loss and forward_pair_logits "
+                            "(disenlink_amd.model.Disentangle)")
+        if getattr(model, "table_dtype", torch.float32) != torch.float32:
+            raise TypeError("objective=\"bpr\" is trained on fp32 tables only (bf16 tables are not served)")
+        return _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, True, int(resample_seed), bpr=True)
     if resample_negatives:
         if objective not in ("pairs", "pairs-logit"):
             raise ValueError(f"resample_negatives replaces the sampled negatives of objective=\"pairs\" / \"pairs-logit\", got {objective!r}")
@@ -342,10 +363,12 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     return res
 
 
-def _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit: bool, seed: int) -> RunResult:
+def _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit: bool, seed: int, bpr: bool = False) -> RunResult:
     """run_link_prediction's eager loop with the negatives drawn anew each epoch (see there).  Per epoch: the sampler (its
     epoch counter a device tensor advanced by ``add_``), the sort, the step; nothing of it is read by the host.  The count
-    of failed draws is copied to pinned memory behind each epoch and looked at one epoch (or more) later: a warning, once."""
+    of failed draws is copied to pinned memory behind each epoch and looked at one epoch (or more) later: a warning, once.
+    ``bpr``: the step is ``model.forward_bpr_loss`` — the ranking loss over the edge rows of ``run.sampled`` and the epoch's
+    draws, weight 1 / n_entries, the validation logits of ``run.val_pairs`` out of the same forward."""
     import warnings
     from . import ops
     from .early_stop import DeviceEarlyStop, drive
@@ -354,17 +377,24 @@ def _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit
         if not 0 < float(lab.sum()) < lab.numel():
             raise ValueError("AUC undefined with one class")
     a, n_val = run.n_pos, run.label_val.numel()
-    if pairs.n_pairs != a + n_val:
-        raise ValueError(f"label / weight must cover the pair list: {a} + {n_val} labels for {pairs.n_pairs} pairs")
-    label = torch.cat([run.label_pos, run.label_val.to(run.label_pos.dtype)])
-    weight = torch.cat([torch.full((a,), 1.0 / max(a, 1), dtype=torch.float32, device=dev),
-                        torch.zeros(n_val, dtype=torch.float32, device=dev)])
+    if bpr:
+        a = 0                                                        # the scored list is the validation pairs alone
+        if run.val_pairs.n_pairs != n_val:
+            raise ValueError(f"label / weight must cover the pair list: {n_val} labels for {run.val_pairs.n_pairs} pairs")
+        bpr_weight = 1.0 / max(sp.n_entries, 1)
+    else:
+        if pairs.n_pairs != a + n_val:
+            raise ValueError(f"label / weight must cover the pair list: {a} + {n_val} labels for {pairs.n_pairs} pairs")
+        label = torch.cat([run.label_pos, run.label_val.to(run.label_pos.dtype)])
+        weight = torch.cat([torch.full((a,), 1.0 / max(a, 1), dtype=torch.float32, device=dev),
+                            torch.zeros(n_val, dtype=torch.float32, device=dev)])
     neg_weight = 1.0 / (sp.m * max(sp.n_entries, 1))                 # BCE_mean(neg) / m over the epoch's entries
     epoch_dev = torch.zeros(1, dtype=torch.int64, device=dev)
     n_failed = torch.zeros(1, dtype=torch.int32, device=dev)
     failed_host = torch.zeros(1, dtype=torch.int32).pin_memory()
     warned = [False]
-    step_fn = model.forward_pair_logits_resampled_loss if logit else model.forward_pairs_resampled_loss
+    if not bpr:
+        step_fn = model.forward_pair_logits_resampled_loss if logit else model.forward_pairs_resampled_loss
     opt = _make_adam(model, True, lr, weight_decay)
     val_plan = AucPlan(run.label_val)
     res = RunResult(float("nan"), 0.0, 0)
@@ -377,7 +407,10 @@ def _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit
         model.train()
         k, _ = ops.sample_negatives(sp, seed=seed, epoch=epoch_dev, n_failed=n_failed)
         order, k_rowptr = ops.sampled_order(k, sp.n_nodes)
-        _emb, score, _neg, loss = step_fn(x, run.graph, pairs, label, weight, sp, k, neg_weight, order, k_rowptr)
+        if bpr:
+            _emb, _pos, _neg, score, loss = model.forward_bpr_loss(x, run.graph, sp, k, bpr_weight, run.val_pairs, order, k_rowptr)
+        else:
+            _emb, score, _neg, loss = step_fn(x, run.graph, pairs, label, weight, sp, k, neg_weight, order, k_rowptr)
         epoch_dev.add_(1)
         failed_host.copy_(n_failed, non_blocking=True)
         return score, loss

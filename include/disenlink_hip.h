@@ -1223,6 +1223,36 @@ int dl_score_sampled_train_logits(const void* Z, const void* H, int N, int K, in
                                   const int32_t* order, const int32_t* k_rowptr, float w, float* score, float* loss,
                                   float* dZ, float* dH, int accumulate, void* ws, size_t ws_bytes, void* stream);
 
+/* dl_score_sampled_bpr_train: the pairwise ranking loss (BPR) on the sampled negatives, in logit space, without a plan.  Edge
+ * row r < n_rows has the positive (u_r, v_r) = (src[r], dst[r]) and the m entries e = r m + j with partners k[e] (-1 = a failed
+ * draw: no term).  With x(a, b) the logit of dl_score_sampled_train_logits and delta_rj = x(u_r, k_rj) - x(u_r, v_r) (in fp32):
+ *   pos_logit[r] = x(u_r, v_r) (written for EVERY row, also one whose draws all failed);   neg_logit[e] = x(u_r, k_e), 0 for k = -1;
+ *   loss[0] = sum_{r, j live} w (max(delta, 0) + log1p(exp(-|delta|)));
+ *   dZ, dH [N][K][d] = d loss / d (Z, H) with g_rj = w sigma(delta_rj) on the negative's logit and -G_r = -sum_j g_rj (ascending
+ *   j) on the positive's, per-factor coefficients and finite clamps as in dl_score_sampled_train_logits, every pair in both
+ *   endpoints' rows; accumulate != 0 adds onto dZ / dH.  EVERY row of dZ / dH is written: a node no list names reads exactly
+ *   0.  w = 0, k = -1 and a row without a live draw contribute exactly nothing.  k == v, k == u and v == u are legal;
+ *   duplicated draws are separate terms.  An overflowed exp is not cured: inf - inf is NaN and stays NaN.
+ * Preconditions: src ascending; u_rowptr [N+1] the CSR of the u side in ENTRIES (u_rowptr[n] = m x the number of src values
+ * < n); dst_order [n_rows] the STABLE ascending sort of dst over the rows and dst_rowptr [N+1], dst_rowptr[n] = the number of
+ * rows with dst < n (fixed for the run); order [n_rows m] / k_rowptr [N+1] the epoch's, as for dl_score_sampled_train.  An
+ * endpoint outside [0, N) makes its row no term (logits 0).  1 <= m <= 63 (a chunk of the row pass is floor(64 / (m + 1))
+ * whole rows; larger m is refused), n_rows m <= (2^31 - 1) / (2 K), and n_rows m, N K d each below 2^31.
+ * Row pass over chunks of whole rows, two partner passes over chunks of 64 list positions (k side, positives' partner side)
+ * through 2K stored coefficients per pair, partial slots where a node spans chunks, one finishing launch that adds k side,
+ * then positives' partner side, then row side; the loss through 1,024 partial sums: fixed orders throughout, no float
+ * atomics, no host read, no synchronisation; the same bits on every call.  fp32 tables with 1 <= K <= 64 and K d <= 2048
+ * (dl_score_sampled_bpr_train_supported; d = 64 with K in {4, 8} has its own kernels, whose logits are the bits of
+ * dl_score_sampled_train_logits'); bf16 tables are refused.  ws: dl_score_sampled_bpr_train_workspace_bytes(n_rows, m, N, K, d)
+ * (0 for arguments the entry refuses). */
+int dl_score_sampled_bpr_train_supported(int K, int d, dl_dtype dtype);
+size_t dl_score_sampled_bpr_train_workspace_bytes(int n_rows, int m, int N, int K, int d);
+int dl_score_sampled_bpr_train(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t,
+                               const int32_t* src, const int32_t* dst, int n_rows, int m, const int32_t* u_rowptr,
+                               const int32_t* dst_order, const int32_t* dst_rowptr, const int32_t* k, const int32_t* order,
+                               const int32_t* k_rowptr, float w, float* pos_logit, float* neg_logit, float* loss,
+                               float* dZ, float* dH, int accumulate, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
