@@ -168,6 +168,9 @@ EXPORTS = {
     "dl_route_aggregate_bwd_scaled": (_i, [_G, _P, _i, _i, _i, _f, _f, _P, _P, _P, _P, _P, _P, _P, _P, _z, _P]),
     # fresh training negatives every epoch: the sampler and the trainer over sampled partners
     "dl_sample_negatives": (_i, [_P, _i, _i, _i, _P, _P, C.c_uint64, _P, _i, _P, _P, _P]),
+    # hard negatives: Z, H, N, K, d, dtype, t, src, n_rows, m, c, exclusion, seed, epoch, exclude_self, k, logit, n_failed, stream
+    "dl_sample_negatives_hard_supported": (_i, [_i, _i, _i]),
+    "dl_sample_negatives_hard": (_i, [_P, _P, _i, _i, _i, _i, _f, _P, _i, _i, _i, _P, _P, C.c_uint64, _P, _i, _P, _P, _P, _P]),
 }
 _SAMPLED = [_P, _P, _i, _i, _i, _i, _f, _P, _i, _i, _P, _P, _P, _P, _f, _P, _P, _P, _P, _i, _P, _z, _P]
 for _name in ("dl_score_sampled_train", "dl_score_sampled_train_logits"):

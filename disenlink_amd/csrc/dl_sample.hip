@@ -13,28 +13,11 @@
 // At most DL_SAMPLE_ATTEMPTS = 64 attempts per entry; an entry that exhausts them writes k = -1 and adds 1 to *n_failed
 // (an integer atomic: the sum does not depend on order) and the trainers give it weight 0.
 // Duplicated draws inside an epoch are KEPT as separate entries (the fixed split de-duplicates; here nothing does).
-#include "dl_common.h"
+#include "dl_sample.h"
 
 namespace dl {
 
-constexpr int SAMPLE_ATTEMPTS = 64;
-
-__device__ __forceinline__ uint32_t philox4x32_10_word0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                        uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
-
+// (Philox and the rejection rule: sample_partner, dl_sample.h — shared with dl_sample_hard.hip, whose candidate 0 is this draw)
 __global__ __launch_bounds__(BLOCK) void sample_negatives_kernel(const int32_t* __restrict__ src, int n_rows, int m, int N,
                                                                  const int32_t* __restrict__ ex_rowptr,
                                                                  const int32_t* __restrict__ ex_col, uint32_t seed_lo,
@@ -44,28 +27,7 @@ __global__ __launch_bounds__(BLOCK) void sample_negatives_kernel(const int32_t* 
     const long long e = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (e >= (long long)n_rows * m) return;
     const uint64_t epoch = epoch_dev[0];
-    const int u = src[e / m];
-    int result = -1;
-    if (u >= 0 && u < N) {                                              // (a source outside the table: a failed entry, never a read)
-        const int beg = ex_rowptr ? ex_rowptr[u] : 0, end = ex_rowptr ? ex_rowptr[u + 1] : 0;
-        for (int attempt = 0; attempt < SAMPLE_ATTEMPTS; ++attempt) {
-            const uint32_t word = philox4x32_10_word0((uint32_t)e, (uint32_t)attempt, (uint32_t)epoch, (uint32_t)(epoch >> 32),
-                                                      seed_lo, seed_hi);
-            const int k = (int)(((uint64_t)word * (uint64_t)(uint32_t)N) >> 32);
-            bool bad = exclude_self && k == u;
-            int lo = beg, hi = end;                                     // first column >= k of the row
-            while (lo < hi) {
-                const int mid = lo + ((hi - lo) >> 1);
-                if (ex_col[mid] < k) lo = mid + 1;
-                else hi = mid;
-            }
-            bad = bad || (lo < end && ex_col[lo] == k);
-            if (!bad) {
-                result = k;
-                break;
-            }
-        }
-    }
+    const int result = sample_partner((uint32_t)e, 0u, epoch, seed_lo, seed_hi, src[e / m], N, ex_rowptr, ex_col, exclude_self);
     k_out[e] = result;
     if (result < 0) atomicAdd(n_failed, 1u);
 }

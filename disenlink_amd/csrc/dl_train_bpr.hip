@@ -36,12 +36,11 @@
 //   bpr_partner_generic_kernel   26 VGPRs -> 8               K d = 2048: two workgroups per CU) bound it first from K d = 640 on
 // (sampled_d64_kernel<2> has 108 VGPRs and 4 waves: z[v], h[v] and the positive's 2 NJ factors held across the walk cost the
 // K = 8 row pass one wave; a launch bound of 4 waves spills 64 bytes per lane, so it is not set.)
-#include "dl_fast.h"
+#include "dl_bpr_logit.h"
 
 namespace dl {
 namespace bpr {
 
-using fast::dot4_packed;
 using fast::store4;
 
 constexpr int SEG = 64;                 // list positions per chunk of a partner pass; lanes that preload a row chunk's indices
@@ -150,34 +149,16 @@ __global__ __launch_bounds__(BLOCK) void bpr_row_d64_kernel(const float* __restr
             if (cur >= 0) flush();
             cur = u;
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                az[j] = ah[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                uz[j] = *reinterpret_cast<const float4*>(Z + (size_t)u * ROW + (j * 64 + lane) * 4);
-                uh[j] = *reinterpret_cast<const float4*>(H + (size_t)u * ROW + (j * 64 + lane) * 4);
-            }
+            for (int j = 0; j < NJ; ++j) az[j] = ah[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            load_row_d64<NJ>(Z, u, lane, uz);
+            load_row_d64<NJ>(H, u, lane, uh);
         }
         // the positive first: its logit, and e_f, (h.h)_f e_f kept with z[v], h[v] until G_r is known
         float4 zp[NJ], hp[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            zp[j] = *reinterpret_cast<const float4*>(Z + (size_t)v * ROW + (j * 64 + lane) * 4);
-            hp[j] = *reinterpret_cast<const float4*>(H + (size_t)v * ROW + (j * 64 + lane) * 4);
-        }
+        load_row_d64<NJ>(Z, v, lane, zp);
+        load_row_d64<NJ>(H, v, lane, hp);
         float exp_[NJ], ttp[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            // sums over the DPP row in the order of TransposedReduce<16, 8> (xor 8, 4, 2, 1): sampled_d64_kernel's bits
-            const float zz = butterfly_down<8, 1>(dot4_packed(uz[j], zp[j]));
-            const float hh = butterfly_down<8, 1>(dot4_packed(uh[j], hp[j]));
-            exp_[j] = expf(div_t(zz, t));
-            ttp[j] = hh * exp_[j];
-        }
-        float xp;
-        {
-            float term = ttp[0];
-            if constexpr (NJ == 2) term += ttp[1];
-            xp = add_xor<32>(add_xor<16>(term));                    // (rows 0 + 1) + (rows 2 + 3): all factors
-        }
+        const float xp = logit_d64<NJ>(uz, uh, zp, hp, t, exp_, ttp);       // (the lane geometry and the order: dl_bpr_logit.h)
         if (lane == 0) pos_logit[r] = xp;
         float G = 0.0f;
 #pragma unroll 1
@@ -189,22 +170,10 @@ __global__ __launch_bounds__(BLOCK) void bpr_row_d64_kernel(const float* __restr
                 continue;
             }
             float4 zv[NJ], hv[NJ];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                zv[j] = *reinterpret_cast<const float4*>(Z + (size_t)kk * ROW + (j * 64 + lane) * 4);
-                hv[j] = *reinterpret_cast<const float4*>(H + (size_t)kk * ROW + (j * 64 + lane) * 4);
-            }
+            load_row_d64<NJ>(Z, kk, lane, zv);
+            load_row_d64<NJ>(H, kk, lane, hv);
             float ex[NJ], ttv[NJ], c[NJ], b[NJ];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const float zz = butterfly_down<8, 1>(dot4_packed(uz[j], zv[j]));
-                const float hh = butterfly_down<8, 1>(dot4_packed(uh[j], hv[j]));
-                ex[j] = expf(div_t(zz, t));
-                ttv[j] = hh * ex[j];
-            }
-            float term = ttv[0];
-            if constexpr (NJ == 2) term += ttv[1];
-            const float xn = add_xor<32>(add_xor<16>(term));
+            const float xn = logit_d64<NJ>(uz, uh, zv, hv, t, ex, ttv);
             const float gl = bpr_coef(xn - xp, w);
             G += gl;
             if (lane == 0) neg_logit[e] = xn;
@@ -319,15 +288,8 @@ __global__ __launch_bounds__(BLOCK) void bpr_row_generic_kernel(const float* __r
         const float* hk = H + (size_t)p * ROW;
         float logit = 0.0f;
         for (int f = 0; f < K; ++f) {
-            float pz = 0.0f, ph = 0.0f;
-            for (int x = f * d + lane; x < (f + 1) * d; x += DL_WAVE) {
-                pz = fmaf(zu[x], zk[x], pz);
-                ph = fmaf(hu[x], hk[x], ph);
-            }
-            const float zz = wave_allreduce_sum(pz), hh = wave_allreduce_sum(ph);
-            const float ex = expf(div_t(zz, t));
-            const float ttv = hh * ex;
-            logit += ttv;
+            float ex;
+            const float ttv = factor_term_generic(zu, hu, zk, hk, f, d, lane, t, ex, logit);   // (the order: dl_bpr_logit.h)
             r[f] = fminf(ex, FMAX);                                 // (the clamps: see the d = 64 kernel)
             r[K + f] = __builtin_amdgcn_fmed3f(div_t(ttv, t), -FMAX, FMAX);
         }

@@ -54,6 +54,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "the split's fixed sample; one GPU, eager loop, fp32 tables")
     p.add_argument("--resample-seed", type=int, default=0, help="seed of --resample-negatives (the draw is a pure function of "
                                                                 "seed, epoch and entry)")
+    p.add_argument("--hard-negatives", type=int, default=0, metavar="C",
+                   help="with --resample-negatives or --objective bpr: hard negatives — every epoch draw C candidates per entry "
+                        "(2 <= C <= 64) and keep the one the current model scores highest (dynamic negative sampling, on the "
+                        "device, no plan build); 0 or 1: the plain uniform draw.  Biased towards false negatives on graphs with "
+                        "many unobserved true links")
     p.add_argument("--objective", choices=["pairs", "pairs-logit", "recon", "recon-logit", "bpr"], default="pairs",
                    help="the training loss: bpr = the pairwise ranking loss, every training edge (u, v) must score above (u, k) "
                         "for m negatives k drawn anew every epoch on the device (softplus of the logit difference; implies "
@@ -449,6 +454,11 @@ def main(argv=None):
         if args.gpus > 1 or args.graph or args.table_dtype == "bf16":
             raise SystemExit("--resample-negatives runs on one GPU in the eager loop with fp32 tables (the sharded step, HIP-graph "
                              "replay of a resampled epoch and bf16 tables are not implemented): drop --gpus / --graph / bf16")
+    if not 0 <= args.hard_negatives <= 64:
+        raise SystemExit(f"--hard-negatives takes 0 .. 64 candidates per entry (one lane draws one candidate), got {args.hard_negatives}")
+    if args.hard_negatives and not resample:
+        raise SystemExit("--hard-negatives chooses among candidates drawn every epoch: give --resample-negatives (with --objective "
+                         "pairs or pairs-logit) or --objective bpr")
     if args.objective == "pairs-logit" and args.gpus > 1:
         raise SystemExit("--objective pairs-logit runs on one GPU only (the sharded step has no logit-space form): drop --gpus")
     if args.gpus > 1:
@@ -504,7 +514,7 @@ def main(argv=None):
                                   use_graph=_use_graph(args) and args.objective not in ("recon", "recon-logit")
                                   and not resample, objective=args.objective,
                                   resample_negatives=args.resample_negatives and args.objective != "bpr",
-                                  resample_seed=args.resample_seed + run,
+                                  resample_seed=args.resample_seed + run, hard_negatives=args.hard_negatives,
                                   pos_weight=args.pos_weight, recon_block_rows=args.recon_block_rows,
                                   recon_node_filter=node_filter if args.recon_link_rule else None)
         if not args.quiet:

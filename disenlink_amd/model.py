@@ -450,7 +450,10 @@ class Disentangle(nn.Module):
         ``ops.sample_negatives``, label 0 and the one weight ``neg_weight`` — through ``ops.score_sampled_train``, over one
         hot-path forward and one backward (ops.HotPathPairsResampledLoss).  Duplicated draws are separate loss terms and a
         failed draw (k = -1) is no term.  fp32 tables only; a shape without a one-pass scorer runs the positive list through
-        forward_pairs' node and the sampled trainer as a node of its own."""
+        forward_pairs' node and the sampled trainer as a node of its own.
+        ``k`` may be an ``ops.HardDraw`` in place of a tensor (hard negatives): the forward then draws its candidates, under
+        no_grad, from the tables it has just computed and keeps the highest-scoring one per entry; ``order`` / ``k_rowptr``
+        cannot be given with it; afterwards ``k.k`` and ``k.logit`` hold the draw."""
         return self._forward_resampled(x, graph, pos_pairs, label, weight, sampled, k, neg_weight, False, order, k_rowptr)
 
     def forward_pair_logits_resampled_loss(self, x, graph: Graph, pos_pairs: PairList, label, weight, sampled, k,
@@ -459,6 +462,7 @@ class Disentangle(nn.Module):
         return self._forward_resampled(x, graph, pos_pairs, label, weight, sampled, k, neg_weight, True, order, k_rowptr)
 
     def _forward_resampled(self, x, graph, pos_pairs, label, weight, sampled, k, neg_weight, logit, order, k_rowptr):
+        ops.check_hard_draw(k, order, k_rowptr)
         if self.table_dtype != torch.float32:
             raise TypeError("resampled negatives are trained on fp32 tables only (bf16 tables are not served)")
         if label.numel() != pos_pairs.n_pairs or weight.numel() != pos_pairs.n_pairs:
@@ -493,7 +497,9 @@ class Disentangle(nn.Module):
         (src, k) for its m partners ``k`` of ``ops.sample_negatives``: loss = sum weight softplus(neg_logit - pos_logit[row])
         over the entries with k >= 0, through ``ops.score_sampled_bpr_train`` over one hot-path forward and one backward
         (ops.HotPathBprLoss).  ``val_pairs``: a list whose logits come out of the same forward (forward only: no gradient).
-        Duplicated draws are separate terms, a failed draw (k = -1) is none.  fp32 tables only, logit space only."""
+        Duplicated draws are separate terms, a failed draw (k = -1) is none.  fp32 tables only, logit space only.
+        ``k`` may be an ``ops.HardDraw`` (hard negatives: the forward draws from its own tables; no ``order`` / ``k_rowptr``)."""
+        ops.check_hard_draw(k, order, k_rowptr)
         if self.table_dtype != torch.float32:
             raise TypeError("the ranking objective is trained on fp32 tables only (bf16 tables are not served)")
         Z = self.project(x)

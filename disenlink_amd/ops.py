@@ -29,7 +29,8 @@ from .recon import (                                                    # noqa: 
 from .sampled import (                                                  # noqa: F401  (fresh training negatives every epoch)
     SampledLogitsLoss, SampledLoss, SampledNegatives, sample_negatives, sampled_order, score_sampled_logits_loss,
     score_sampled_loss, score_sampled_supported, score_sampled_train,
-    SampledBprLoss, score_sampled_bpr_loss, score_sampled_bpr_supported, score_sampled_bpr_train)   # (... the ranking objective)
+    SampledBprLoss, score_sampled_bpr_loss, score_sampled_bpr_supported, score_sampled_bpr_train,   # (... the ranking objective)
+    HardDraw, check_hard_draw, sample_hard_negatives, sample_hard_supported)                        # (... hard negatives)
 from .scans import (                                                    # noqa: F401  (the all-pairs scans: ops.score_* as before)
     BETWEEN_MAX_N, BLOCK_NODES, BLOCKS_MAX_N, LINKS_MAX_N, MINE_MAX_M, MINE_MAX_N, RANK_MAX_K, LinksBetween, NodeFilter,
     PairExclusion, PairTerms, bipartite_exclusion_csr, exclusion_csr, pair_exclusion, score_link_degrees,
@@ -530,11 +531,13 @@ class HotPathPairsResampledLoss(torch.autograd.Function):
     the POSITIVE list ``pairs`` with (label, weight), plus this epoch's sampled negatives (``sampled``, ``k``, one weight
     ``neg_weight``) through ``score_sampled_train``, over ONE routing / aggregation forward and one backward: the sampled
     trainer adds its gradients onto the positive list's in its finishing launch, and loss = positive part + negative part.
-    The backward takes a gradient on the loss (and on emb); the scores carry none.  fp32 tables only."""
+    The backward takes a gradient on the loss (and on emb); the scores carry none.  fp32 tables only.
+    ``k``: the epoch's partners, or a ``HardDraw`` — the sampled trainer then draws them from the (Zt, H) of this forward."""
 
     @staticmethod
     def forward(ctx, Z, graph: Graph, pairs: PairList, beta: float, t: float, label, weight, sampled, k, neg_weight: float,
                 logit: bool, order=None, k_rowptr=None):
+        check_hard_draw(k, order, k_rowptr)
         ctx.set_materialize_grads(False)
         Zt, p, a, s, H = step_tables(graph, Z, beta, t, torch.float32)
         if logit:
@@ -569,10 +572,12 @@ class HotPathBprLoss(torch.autograd.Function):
     aggregation forward, the pairwise ranking loss of ``score_sampled_bpr_train`` over ``sampled`` (built with ``dst``) and this
     epoch's partners ``k`` with the one weight ``weight``, and — ``val_pairs`` given — the logits of that list through
     ``score_pairs_logits_fwd``, forward only.  The backward is ``HotPathPairsResampledLoss``'s: a gradient on the loss (scaled
-    inside the last kernel) and on emb; the logits carry none.  fp32 tables only."""
+    inside the last kernel) and on emb; the logits carry none.  fp32 tables only.
+    ``k``: the epoch's partners, or a ``HardDraw`` — the ranking trainer then draws them from the (Zt, H) of this forward."""
 
     @staticmethod
     def forward(ctx, Z, graph: Graph, beta: float, t: float, sampled, k, weight: float, val_pairs=None, order=None, k_rowptr=None):
+        check_hard_draw(k, order, k_rowptr)
         ctx.set_materialize_grads(False)
         Zt, p, a, s, H = step_tables(graph, Z, beta, t, torch.float32)
         loss, pos, neg, dZs, dHs = score_sampled_bpr_train(Zt, H, t, sampled, k, weight, order, k_rowptr)

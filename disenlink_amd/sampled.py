@@ -7,6 +7,10 @@ function of (seed, epoch, entry)) and trained by ``score_sampled_train`` without
 for the run (``SampledNegatives``), the partner side needs one stable device sort (``sampled_order``).  No host read and no
 synchronisation in the epoch.
 
+Hard negatives (csrc/dl_sample_hard.hip): ``sample_hard_negatives`` draws c candidates per entry by the same rule and keeps the
+one the current tables score highest; a ``HardDraw`` handed to a trainer or a step in place of ``k`` makes that draw inside the
+step, on the tables the loss is taken on.
+
 What differs from the fixed split: duplicated draws inside an epoch are KEPT as separate loss terms (the fixed split keeps only
 the pairs drawn once); an entry whose 64 attempts all hit excluded partners is k = -1, weight 0, and counted in ``n_failed``.
 fp32 tables only (bf16 tables raise).
@@ -133,6 +137,108 @@ def sampled_order(k: torch.Tensor, n_nodes: int):
     return order.to(torch.int32), torch.searchsorted(sk, nodes).to(torch.int32)
 
 
+# ------------------------------------------------------------------------------------------------ hard negatives
+HARD_MAX_CANDIDATES = 64                 # one lane of a wave draws one candidate
+
+
+def _check_candidates(candidates) -> int:
+    c = int(candidates)
+    if not 1 <= c <= HARD_MAX_CANDIDATES:
+        raise ValueError(f"candidates must be 1 .. {HARD_MAX_CANDIDATES} per entry, got {candidates}")
+    return c
+
+
+def sample_hard_supported(K: int, d: int, dtype=torch.float32) -> bool:
+    code = _lib.DL_F32 if dtype == torch.float32 else _lib.DL_BF16 if dtype == torch.bfloat16 else -1
+    return code >= 0 and bool(_lib.load().dl_sample_negatives_hard_supported(int(K), int(d), code))
+
+
+def sample_hard_negatives(Z, H, t: float, src, candidates: int, m: int = None, n_nodes: int = None, exclusion=None, seed: int = 0,
+                          epoch=0, exclude_self: bool = False, n_failed: torch.Tensor | None = None):
+    """-> (k int32 [n_rows m], logit f32 [n_rows m], n_failed int32 [1]): hard negatives (dynamic negative sampling) —
+    ``candidates`` = c draws per entry instead of one (1 <= c <= 64), each by the rule of ``sample_negatives`` with the Philox
+    counter (e, i 64 + attempt, epoch), and the live candidate that the tables ``Z``, ``H`` [N,K,d] score highest is kept:
+    x(u, k) = sum_f (h_f[u].h_f[k]) exp(z_f[u].z_f[k] / t) in fp32, ties to the lowest candidate index, a NaN below every number
+    (all NaN: the first live candidate) — dl_sample_negatives_hard.  Candidate 0 is ``sample_negatives``' draw for the entry, so
+    c = 1 returns its k.  ``logit``: the kept candidate's logit, the bits ``score_sampled_bpr_train`` returns as ``neg_logit``
+    for the same pair; 0 where k = -1 (all c candidates failed, or a src outside the table), which counts ONCE in ``n_failed``
+    (given: added onto it).  ``src``, ``m``, ``n_nodes``, ``exclusion``, ``epoch``: as in ``sample_negatives``.  A pure function of
+    (seed, epoch, entry, Z, H, t): the same bits on every call; no host read, no synchronisation.  The selection favours
+    unobserved TRUE links where the graph has many.  fp32 tables with K d <= 2048; bf16 tables raise."""
+    c = _check_candidates(candidates)
+    if Z.dtype != torch.float32 or H.dtype != torch.float32:
+        raise TypeError(f"the hard-negative sampler takes fp32 tables, got {Z.dtype} / {H.dtype} (bf16 tables are not served)")
+    if isinstance(src, SampledNegatives):
+        s = src
+        src, m, n_nodes, ex = s.src, s.m, s.n_nodes, (s.ex_rowptr, s.ex_col)
+    else:
+        ex = (None, None) if exclusion is None else tuple(exclusion)
+        if m is None or n_nodes is None:
+            raise ValueError("m and n_nodes are required with a raw src array")
+    if t == 0:
+        raise ValueError("temperature is 0")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must fit 64 bits")
+    Z, H = _f32c(Z), _f32c(H)
+    _need_cuda(Z, H, src)
+    N, K, d = _nkd(Z)
+    if tuple(H.shape) != tuple(Z.shape):
+        raise ValueError("Z and H differ in shape")
+    if N != int(n_nodes):
+        raise ValueError(f"tables of {N} nodes, negatives over {n_nodes}")
+    if src.dtype != torch.int32 or not src.is_contiguous():
+        raise TypeError("src must be a contiguous int32 tensor")
+    lib = _lib.load()
+    if not lib.dl_sample_negatives_hard_supported(K, d, _lib.DL_F32):
+        raise _lib.DisenlinkHipError(f"the hard-negative sampler serves fp32 tables with K <= 64 and K d <= 2048 (got K={K}, d={d}); "
+                                     "there is no eager fallback")
+    dev = src.device
+    for a in ex:
+        if a is not None and (a.dtype != torch.int32 or a.device != dev):
+            raise TypeError("the exclusion CSR must be int32 tensors on the device of src")
+    ep = _epoch_tensor(epoch, dev)
+    E = src.numel() * int(m)
+    k = _empty(E, torch.int32, dev)
+    logit = _empty(E, torch.float32, dev)
+    if n_failed is None:
+        n_failed = torch.zeros(1, dtype=torch.int32, device=dev)
+    er, ec, keep = _csr_args(ex[0], ex[1], dev)
+    _lib.check(lib.dl_sample_negatives_hard(Z.data_ptr(), H.data_ptr(), N, K, d, _lib.DL_F32, float(t), src.data_ptr(), src.numel(),
+                                            int(m), c, er, ec, int(seed), ep.data_ptr(), int(bool(exclude_self)), k.data_ptr(),
+                                            logit.data_ptr(), n_failed.data_ptr(), _stream()), "dl_sample_negatives_hard")
+    del keep
+    return k, logit, n_failed
+
+
+class HardDraw:
+    """What a training step takes in place of this epoch's ``k`` to train on hard negatives: ``candidates`` draws per entry
+    (1 .. 64), ``seed``, ``epoch`` (an int, or the 1-element int64 DEVICE tensor a loop advances), ``n_failed`` (an int32 [1]
+    device tensor the failed entries are added onto; None: the record makes its own at the first draw) and ``exclude_self``.
+    The step — ``score_sampled_train`` / ``score_sampled_bpr_train`` and everything built on them — calls ``draw`` on the tables
+    its loss is taken on, under no_grad; afterwards ``.k`` and ``.logit`` hold that step's draw (None before the first)."""
+
+    def __init__(self, candidates: int, seed: int = 0, epoch=0, n_failed: torch.Tensor | None = None, exclude_self: bool = False):
+        self.candidates = _check_candidates(candidates)
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must fit 64 bits")
+        self.seed, self.epoch, self.n_failed, self.exclude_self = int(seed), epoch, n_failed, bool(exclude_self)
+        self.k = self.logit = None
+
+    def draw(self, Z, H, t: float, sampled: SampledNegatives) -> torch.Tensor:
+        """``sample_hard_negatives`` for the entries of ``sampled`` on (Z, H) -> k; kept in ``.k`` / ``.logit``."""
+        with torch.no_grad():
+            self.k, self.logit, self.n_failed = sample_hard_negatives(
+                Z.detach(), H.detach(), t, sampled, self.candidates, seed=self.seed, epoch=self.epoch,
+                exclude_self=self.exclude_self, n_failed=self.n_failed)
+        return self.k
+
+
+def check_hard_draw(k, order, k_rowptr) -> None:
+    """A ``HardDraw`` draws its partners inside the step, so their sort cannot exist beforehand: ``order`` / ``k_rowptr`` raise."""
+    if isinstance(k, HardDraw) and (order is not None or k_rowptr is not None):
+        raise ValueError("with a HardDraw the partners are drawn inside the step: order / k_rowptr cannot be given")
+
+
 def score_sampled_supported(K: int, d: int, dtype=torch.float32) -> bool:
     code = _lib.DL_F32 if dtype == torch.float32 else _lib.DL_BF16 if dtype == torch.bfloat16 else -1
     return code >= 0 and bool(_lib.load().dl_score_sampled_train_supported(int(K), int(d), code))
@@ -146,17 +252,21 @@ def score_sampled_train(Z, H, t: float, sampled: SampledNegatives, k, weight: fl
     (dl_score_sampled_train / _logits).  ``dZ_accum`` / ``dH_accum`` (both or neither): the gradient is ADDED onto them in
     place, in the finishing launch.  Every row is written; an entry with k = -1 has score 0 and no part in the loss.
     Duplicates are separate terms.  No float atomics, no host read, no synchronisation; the same bits on every call.
-    fp32 tables with K d <= 2048; bf16 tables raise."""
+    fp32 tables with K d <= 2048; bf16 tables raise.
+    ``k`` may be a ``HardDraw``: the partners are then drawn here, from (Z, H), and ``order`` / ``k_rowptr`` cannot be given."""
+    check_hard_draw(k, order, k_rowptr)
     lib = _lib.load()
     if Z.dtype != torch.float32 or H.dtype != torch.float32:
         raise TypeError(f"the sampled trainer takes fp32 tables, got {Z.dtype} / {H.dtype} (bf16 tables are not served)")
     Z, H = _f32c(Z), _f32c(H)
-    _need_cuda(Z, H, k)
+    _need_cuda(Z, H, *(() if isinstance(k, HardDraw) else (k,)))
     N, K, d = _nkd(Z)
     if tuple(H.shape) != tuple(Z.shape):
         raise ValueError("Z and H differ in shape")
     if N != sampled.n_nodes:
         raise ValueError(f"tables of {N} nodes, sampled negatives of {sampled.n_nodes}")
+    if isinstance(k, HardDraw):
+        k = k.draw(Z, H, t, sampled)
     if not lib.dl_score_sampled_train_supported(K, d, _lib.DL_F32):
         raise _lib.DisenlinkHipError(f"the sampled trainer serves fp32 tables with K <= 64 and K d <= 2048 (got K={K}, d={d}); "
                                      "there is no eager fallback")
@@ -241,12 +351,14 @@ def score_sampled_bpr_train(Z, H, t: float, sampled: SampledNegatives, k, weight
     written for every row, ``neg_logit`` is 0 for k = -1; a row whose draws all failed has no loss and no gradient.
     ``dZ_accum`` / ``dH_accum`` (both or neither): the gradient is ADDED onto them in place, in the finishing launch.
     Duplicates are separate terms; k == dst, k == src and dst == src are legal.  No float atomics, no host read, no
-    synchronisation; the same bits on every call.  fp32 tables with K d <= 2048 and m <= 63; bf16 tables raise."""
+    synchronisation; the same bits on every call.  fp32 tables with K d <= 2048 and m <= 63; bf16 tables raise.
+    ``k`` may be a ``HardDraw``: the partners are then drawn here, from (Z, H), and ``order`` / ``k_rowptr`` cannot be given."""
+    check_hard_draw(k, order, k_rowptr)
     lib = _lib.load()
     if Z.dtype != torch.float32 or H.dtype != torch.float32:
         raise TypeError(f"the ranking trainer takes fp32 tables, got {Z.dtype} / {H.dtype} (bf16 tables are not served)")
     Z, H = _f32c(Z), _f32c(H)
-    _need_cuda(Z, H, k)
+    _need_cuda(Z, H, *(() if isinstance(k, HardDraw) else (k,)))
     N, K, d = _nkd(Z)
     if tuple(H.shape) != tuple(Z.shape):
         raise ValueError("Z and H differ in shape")
@@ -259,6 +371,8 @@ def score_sampled_bpr_train(Z, H, t: float, sampled: SampledNegatives, k, weight
     if not lib.dl_score_sampled_bpr_train_supported(K, d, _lib.DL_F32):
         raise _lib.DisenlinkHipError(f"the ranking trainer serves fp32 tables with K <= 64 and K d <= 2048 (got K={K}, d={d}); "
                                      "there is no eager fallback")
+    if isinstance(k, HardDraw):
+        k = k.draw(Z, H, t, sampled)
     E = sampled.n_entries
     if k.dtype != torch.int32 or k.numel() != E or not k.is_contiguous():
         raise ValueError(f"k must be a contiguous int32 tensor of {E} entries")

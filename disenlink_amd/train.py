@@ -217,7 +217,7 @@ def _graphed_epoch(model, x, run, lr, weight_decay, b, label_all, weight_all, es
 def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 2000, lr: float = 1e-4,
                         patience: int = 200, weight_decay: float = 5e-4, log=None, use_graph: bool = False,
                         objective: str = "pairs", pos_weight=None, recon_block_rows=None, recon_node_filter=None,
-                        resample_negatives: bool = False, resample_seed: int = 0) -> RunResult:
+                        resample_negatives: bool = False, resample_seed: int = 0, hard_negatives: int = 0) -> RunResult:
     """``use_graph=True`` (GPU only): replay each epoch from a captured HIP graph (same arithmetic, same
     schedule; only the host-side launch cost disappears).
     ``objective``: "pairs" (the default: the reference's loss on the sampled pair list), "pairs-logit" — the same pair list
@@ -242,7 +242,18 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     drawn anew every epoch as above (``resample_seed`` applies; ``resample_negatives`` is implied): loss = sum_e w softplus(x(u, k_e)
     - x(u, v)) with w = 1 / n_entries (``model.forward_bpr_loss``, no plan build and no host read in the epoch).  Validation and
     test AUC are counted on logits, as in "pairs-logit"; failed draws are reported as with ``resample_negatives``.  GPU, eager
-    loop, fp32 tables, a run of ``prepare_run(..., resample_negatives=True)``; anything else raises before the first launch."""
+    loop, fp32 tables, a run of ``prepare_run(..., resample_negatives=True)``; anything else raises before the first launch.
+    ``hard_negatives`` (with ``resample_negatives=True`` or ``objective="bpr"``; any other objective raises, as does a value
+    outside [0, 64]): hard negatives — a value c >= 2 draws c candidates per entry every epoch and keeps the one the tables of
+    THAT epoch's forward score highest (``ops.HardDraw``: the step draws inside its forward, ``ops.sample_hard_negatives``; no
+    plan build, no host read); candidate 0 is the plain draw.  0 or 1: the plain sampler call, launches and bits as without
+    the argument.  The selection is biased towards false negatives where many true links are unobserved."""
+    hard_negatives = int(hard_negatives)
+    if not 0 <= hard_negatives <= 64:
+        raise ValueError(f"hard_negatives takes 0 .. 64 candidates per entry, got {hard_negatives}")
+    if hard_negatives and not (resample_negatives or objective == "bpr"):
+        raise ValueError(f"hard_negatives chooses among candidates drawn every epoch: it goes with resample_negatives=True or "
+                         f"objective=\"bpr\", got objective={objective!r} without resampling")
     if objective not in ("pairs", "pairs-logit", "recon", "recon-logit", "bpr"):
         raise ValueError(f"objective must be \"pairs\", \"pairs-logit\", \"recon\", \"recon-logit\" or \"bpr\", got {objective!r}")
     if recon_node_filter is not None and objective not in ("recon", "recon-logit"):
@@ -262,7 +273,8 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
                             "(disenlink_amd.model.Disentangle)")
         if getattr(model, "table_dtype", torch.float32) != torch.float32:
             raise TypeError("objective=\"bpr\" is trained on fp32 tables only (bf16 tables are not served)")
-        return _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, True, int(resample_seed), bpr=True)
+        return _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, True, int(resample_seed), bpr=True,
+                              hard=hard_negatives)
     if resample_negatives:
         if objective not in ("pairs", "pairs-logit"):
             raise ValueError(f"resample_negatives replaces the sampled negatives of objective=\"pairs\" / \"pairs-logit\", got {objective!r}")
@@ -275,7 +287,7 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
             raise ValueError("resample_negatives needs a run of prepare_run(..., resample_negatives=True)")
         if not hasattr(model, "forward_pairs_resampled_loss"):
             raise TypeError("resample_negatives needs a model with forward_pairs_resampled_loss (disenlink_amd.model.Disentangle)")
-        return _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit, int(resample_seed))
+        return _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit, int(resample_seed), hard=hard_negatives)
     if logit:
         _check_logit_run(model, run)
         if not x.is_cuda:
@@ -363,12 +375,15 @@ def run_link_prediction(model, x: torch.Tensor, run: PreparedRun, epochs: int = 
     return res
 
 
-def _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit: bool, seed: int, bpr: bool = False) -> RunResult:
+def _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit: bool, seed: int, bpr: bool = False,
+                   hard: int = 0) -> RunResult:
     """run_link_prediction's eager loop with the negatives drawn anew each epoch (see there).  Per epoch: the sampler (its
     epoch counter a device tensor advanced by ``add_``), the sort, the step; nothing of it is read by the host.  The count
     of failed draws is copied to pinned memory behind each epoch and looked at one epoch (or more) later: a warning, once.
     ``bpr``: the step is ``model.forward_bpr_loss`` — the ranking loss over the edge rows of ``run.sampled`` and the epoch's
-    draws, weight 1 / n_entries, the validation logits of ``run.val_pairs`` out of the same forward."""
+    draws, weight 1 / n_entries, the validation logits of ``run.val_pairs`` out of the same forward.
+    ``hard`` >= 2: no sampler call and no sort here — the step gets an ``ops.HardDraw`` and draws ``hard`` candidates per entry
+    from the tables of its own forward (same seed, same device epoch counter, same failed-draw counter)."""
     import warnings
     from . import ops
     from .early_stop import DeviceEarlyStop, drive
@@ -393,6 +408,7 @@ def _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit
     n_failed = torch.zeros(1, dtype=torch.int32, device=dev)
     failed_host = torch.zeros(1, dtype=torch.int32).pin_memory()
     warned = [False]
+    draw = ops.HardDraw(hard, seed, epoch_dev, n_failed=n_failed) if hard >= 2 else None
     if not bpr:
         step_fn = model.forward_pair_logits_resampled_loss if logit else model.forward_pairs_resampled_loss
     opt = _make_adam(model, True, lr, weight_decay)
@@ -405,8 +421,11 @@ def _run_resampled(model, x, run, epochs, lr, patience, weight_decay, log, logit
             warnings.warn(f"resample_negatives: {int(failed_host[0])} draws so far found no admissible partner in 64 attempts "
                           "(their entries carry weight 0)")
         model.train()
-        k, _ = ops.sample_negatives(sp, seed=seed, epoch=epoch_dev, n_failed=n_failed)
-        order, k_rowptr = ops.sampled_order(k, sp.n_nodes)
+        if draw is not None:
+            k, order, k_rowptr = draw, None, None
+        else:
+            k, _ = ops.sample_negatives(sp, seed=seed, epoch=epoch_dev, n_failed=n_failed)
+            order, k_rowptr = ops.sampled_order(k, sp.n_nodes)
         if bpr:
             _emb, _pos, _neg, score, loss = model.forward_bpr_loss(x, run.graph, sp, k, bpr_weight, run.val_pairs, order, k_rowptr)
         else:

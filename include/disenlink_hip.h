@@ -1194,6 +1194,28 @@ int dl_sample_negatives(const int32_t* src, int n_rows, int m, int N, const int3
                         uint64_t seed, const uint64_t* epoch_dev, int exclude_self, int32_t* k_out, uint32_t* n_failed,
                         void* stream);
 
+/* dl_sample_negatives_hard: hard negatives (dynamic negative sampling) — c candidates per entry instead of one, the one
+ * the caller's CURRENT tables score highest is kept.  Entry e = r m + j has 1 <= c <= 64 candidates; candidate i is drawn by the
+ * rule of dl_sample_negatives (at most 64 attempts, rejection against the exclusion row of src[r], and of k == src[r] with
+ * exclude_self) with the Philox counter (e, i 64 + attempt, epoch low, epoch high), key = seed: candidate 0 is, bit for bit,
+ * the draw dl_sample_negatives makes for e, and c = 1 is that sampler.  A candidate that spends its attempts is dead.
+ * k_out[e] = the live candidate with the largest logit x(u, k) = sum_f (h_f[u].h_f[k]) exp(z_f[u].z_f[k] / t), taken in fp32
+ * from Z, H [N][K][d]; ties go to the lowest i; a NaN logit ranks below every number, -inf included, and if every live
+ * candidate's logit is NaN the first live one is kept.  All c dead, or src[r] outside [0, N) (never read): k_out[e] = -1 and
+ * ONE count in *n_failed (entries, not candidates; device uint32, the caller zeroes it).  Duplicated candidates are legal.
+ * x_out (may be NULL): the kept candidate's logit, 0 where k_out[e] = -1 — the bits dl_score_sampled_bpr_train writes to
+ * neg_logit for the same (u, k) at the same shape (d = 64 with K in {4, 8}: its register form; otherwise its generic order).
+ * The result is a pure function of (seed, epoch, e, Z, H, t): the same bits on every call, whatever the grid.  One wave per
+ * floor(64 / c) consecutive entries, one lane per candidate for the draw, then a serial walk that gathers the rows of each live
+ * candidate (c E 2 K d 4 bytes gathered in all); no LDS, no workspace, no float atomics, no host read, no synchronisation; the
+ * one atomic is the integer n_failed.  fp32 tables with 1 <= K <= 64 and K d <= 2048 (dl_sample_negatives_hard_supported);
+ * bf16 tables are refused.  src ascending is not required for the result, only for the reuse of the loaded u rows. */
+int dl_sample_negatives_hard_supported(int K, int d, dl_dtype dtype);
+int dl_sample_negatives_hard(const void* Z, const void* H, int N, int K, int d, dl_dtype dtype, float t, const int32_t* src,
+                             int n_rows, int m, int c, const int32_t* ex_rowptr, const int32_t* ex_col, uint64_t seed,
+                             const uint64_t* epoch_dev, int exclude_self, int32_t* k_out, float* x_out, uint32_t* n_failed,
+                             void* stream);
+
 /* dl_score_sampled_train: the outputs of dl_score_pairs_train for the n_rows m entries (u_e, k_e), u_e = src[e / m], label 0
  * and ONE weight w, without a plan:
  *   score[e] = sigmoid(x_e) (_logits: x_e),  x_e = sum_f (h_f[u].h_f[k]) exp(z_f[u].z_f[k] / t);   0 for an entry with k = -1;
